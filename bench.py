@@ -10,7 +10,12 @@ per-exit CTC loss (one launch for all 6 x 64 lattices; reference train.py:53-65)
 RCCL all-reduce of the 6 per-exit losses -- the only exchange of the batch-sharded path.  The same
 work runs at every N (weak scaling); ``forward_only`` reports the encoder forward alone at N = 1.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the per-exit losses
+(``exit_losses.npy``, [6] fp32) and the log-probs of a fixed, seeded sample of the batch's utterances
+(``log_probs.npy``, [6, n, T', 256] fp32; ``log_probs_utterances.npy`` holds the sampled batch indices) -- at most 64 MB
+in all.  Inputs and weights come from seeded generators, so runs with the same arguments compare output for output.
 
 N > 1: either started under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (the ranks read
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started plainly, in which case this process becomes a
@@ -205,6 +210,26 @@ def plumbing_check(args, rank, world):
     return 0
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, logp, losses):
+    """--dump-outputs: the arrays a caller of the timed step receives, as float32 .npy files -- the per-exit losses [E] whole and
+    the log-probs [E, B, T', V] of a fixed sample of utterances (seeded, independent of the run; their batch indices as float64)
+    that keeps the total under DUMP_LIMIT_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    E, Bo, Tq, V = logp.shape
+    per_utt = E * Tq * V * 4
+    n = max(1, min(Bo, (DUMP_LIMIT_BYTES - (1 << 20)) // per_utt))  # 1 MiB left for the losses, indices and .npy headers
+    pick = torch.randperm(Bo, generator=torch.Generator().manual_seed(0))[:n].sort().values
+    assert n * per_utt + (1 << 20) <= DUMP_LIMIT_BYTES, "one utterance's log-probs exceed the dump limit"
+    arrays = {"exit_losses": losses.float(), "log_probs": logp[:, pick.to(logp.device)].float(),
+              "log_probs_utterances": pick.double()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -218,7 +243,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-modes", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the training-step secondary lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))  # launcher mode: no GPU call in this process
@@ -293,7 +322,7 @@ def main():
         torch.cuda.synchronize()
 
     def run_steps(n, with_loss=True):
-        out = None
+        out, loss = None, None
         for _ in range(n):
             with torch.no_grad():
                 out = model(mel, lengths)
@@ -301,14 +330,17 @@ def main():
                     # summed per-exit CTC loss of this rank's shard, then the one collective of the
                     # path: global-batch mean of the 6 per-exit losses (7 floats over RCCL/xGMI)
                     loss = parallel.combine_exit_losses(exit_ctc_losses(out, tgt, tgt_len), B)
-        return out
+        return out, loss
 
     run_steps(args.warmup)
     sync_all()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last_out, last_loss = run_steps(args.steps)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, last_loss)
+    del last_out, last_loss
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -13,7 +13,6 @@ if ROOT not in sys.path:
 torch.set_num_threads(min(8, os.cpu_count() or 1))
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):

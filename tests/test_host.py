@@ -440,6 +440,26 @@ def test_bench_parent_makes_no_gpu_call_before_spawning():
     assert "torch.cuda" not in launcher and "import torch" not in launcher
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the timed step's per-exit losses whole and the log-probs of the same seeded utterance sample every run,
+    float32 / float64 .npy files within the 64 MB limit at the headline shape [6, 64, 256, 256]."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    logp, losses = torch.randn(6, 64, 256, 256), torch.randn(6)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), logp, losses)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["exit_losses.npy", "log_probs.npy", "log_probs_utterances.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    pick = np.load(tmp_path / "a" / "log_probs_utterances.npy")
+    assert np.array_equal(pick, np.load(tmp_path / "b" / "log_probs_utterances.npy")) and len(pick) >= 32
+    got = np.load(tmp_path / "a" / "log_probs.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logp[:, torch.from_numpy(pick).long()].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "exit_losses.npy"), losses.numpy())
+
+
 class _ToyDecoderModel:
     """A deterministic stand-in for ``model._decoder_``: log-probs depend on the whole prefix, so beam bookkeeping errors
     (wrong parent beam, wrong order) change the result."""

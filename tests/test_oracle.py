@@ -1,77 +1,84 @@
-"""CPU tests: the oracle against the reference's own class bodies (build container only),
-against the committed golden fixtures, and the semantics of the callers' arithmetic."""
+"""CPU tests: the oracle against what the reference's own class bodies computed (tests/golden/reference_bodies.npz), against
+the committed golden fixtures, and the semantics of the callers' arithmetic."""
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REFERENCE, base_kwargs, load_golden
+from conftest import GOLDEN, base_kwargs, load_golden
 from early_exit_transformer_amd import synth
 from oracle import conformer_ref as R
 
-
-def _import_reference():
-    ta, tam, tac = (types.ModuleType(n) for n in ("torchaudio", "torchaudio.models", "torchaudio.models.conformer"))
-    tac.Conformer = R.Conformer
-    tam.conformer, ta.models = tac, tam
-    sys.modules.update({"torchaudio": ta, "torchaudio.models": tam, "torchaudio.models.conformer": tac})
-    if REFERENCE not in sys.path:
-        sys.path.insert(0, REFERENCE)
-    from models.model import early_exit
-    return early_exit
+# replaying a stored output on another host: 16 fp32 ulps of the output's largest magnitude (the same oracle run with one
+# thread instead of eight moves it by up to 5)
+REPLAY_ULPS = 16 * torch.finfo(torch.float32).eps
+REF_STRIDE = 8  # tests/golden/make_golden.py: reference_bodies.npz keeps every 8th frame of an output whole
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
+def _reference_body(tag):
+    """tests/golden/reference_bodies.npz (make_golden.py reference_bodies): what the reference's own class body -- imported
+    unmodified, the missing torchaudio symbol bound to the oracle's restatement -- returned, after the generator had checked that
+    the oracle returns the same bits in the same process.  Here the oracle replays it on whatever host runs the suite."""
+    z = np.load(os.path.join(GOLDEN, "reference_bodies.npz"))
+    over = eval(str(z[f"{tag}_kwargs"]))
+    cases = eval(str(z[f"{tag}_cases"]))
+    return z, base_kwargs(**over), cases, int(z[f"{tag}_seed"]), z[f"{tag}_keys"].tolist(), eval(str(z[f"{tag}_shapes"]))
+
+
+def _assert_reproduces(z, tag, i, got):
+    """Every REF_STRIDE-th frame entry by entry, and every frame through its sum over the vocabulary."""
+    want, rowsum = torch.from_numpy(z[f"{tag}_out{i}"]), torch.from_numpy(z[f"{tag}_rowsum{i}"])
+    assert got.dtype == want.dtype and got.shape[:-1] == rowsum.shape
+    assert got[:, :, ::REF_STRIDE].shape == want.shape
+    # bit for bit against the reference in the generator's process; here the host's BLAS may order fp32 sums differently
+    tol = REPLAY_ULPS * max(1.0, want.abs().max().item())
+    err = (got[:, :, ::REF_STRIDE] - want).abs().max().item()
+    assert err <= tol, (tag, i, err)
+    err = (got.double().sum(-1) - rowsum).abs().max().item()
+    assert err <= got.size(-1) * tol, (tag, i, "frame sums", err)
+
+
 def test_oracle_equals_reference_class_body():
-    """Pins the reference-owned half of the path: the reference's Early_conformer (early_exit.py:565-634),
-    imported unmodified with the missing torchaudio symbol bound, equals the oracle bit for bit."""
-    ee = _import_reference()
-    kw = base_kwargs(n_enc_exits=2, n_enc_layers=1, d_feed_forward=256)
-    ref, mine = ee.Early_conformer(**kw).eval(), R.EarlyConformerRef(**kw).eval()
-    assert list(ref.state_dict().keys()) == list(mine.state_dict().keys())
-    sd = synth.synth_state_dict(ref.state_dict(), seed=5, style="trained")
-    ref.load_state_dict(sd, strict=True)
-    mine.load_state_dict(sd, strict=True)
-    mel, lens = synth.synth_mel(3, 80, 203, seed=5), torch.tensor([203, 150, 99])
-    with torch.no_grad():
-        assert torch.equal(ref(mel, lens), mine(mel, lens))
+    """Pins the reference-owned half of the path: the reference's Early_conformer (early_exit.py:565-634) -- its state_dict keys
+    in order and shapes, and its output -- equals the oracle."""
+    z, kw, cases, seed, keys, shapes = _reference_body("conformer")
+    mine = R.EarlyConformerRef(**kw).eval()
+    assert list(mine.state_dict().keys()) == keys
+    assert [tuple(v.shape) for v in mine.state_dict().values()] == shapes
+    mine.load_state_dict(synth.synth_state_dict(mine.state_dict(), seed=seed, style="trained"), strict=True)
+    for i, (B, T, lens) in enumerate(cases):
+        with torch.no_grad():
+            _assert_reproduces(z, "conformer", i, mine(synth.synth_mel(B, 80, T, seed=seed), torch.tensor(lens)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
 def test_splitformer_oracle_equals_reference_class_body():
-    """the reference's Splitformer (early_exit.py:227-364), imported unmodified, equals
-    oracle.SplitformerRef bit for bit -- odd T' (the branch zero-pads one frame) and even T', ragged lengths."""
-    ee = _import_reference()
-    kw = base_kwargs(n_enc_exits=3, n_enc_layers=1, d_feed_forward=256, depthwise_kernel_size=15, dec_voc_size=64)
-    ref, mine = ee.Splitformer(**kw).eval(), R.SplitformerRef(**kw).eval()
-    assert sorted(ref.state_dict().keys()) == sorted(mine.state_dict().keys())
-    sd = synth.synth_state_dict(ref.state_dict(), seed=5, style="trained")
-    ref.load_state_dict(sd, strict=True)
+    """the reference's Splitformer (early_exit.py:227-364) equals oracle.SplitformerRef -- odd T' (the branch
+    zero-pads one frame) and even T', ragged lengths."""
+    z, kw, cases, seed, keys, shapes = _reference_body("splitformer")
+    mine = R.SplitformerRef(**kw).eval()
+    assert sorted(mine.state_dict().keys()) == sorted(keys)
+    assert dict(zip(keys, shapes)) == {k: tuple(v.shape) for k, v in mine.state_dict().items()}
+    sd = synth.synth_state_dict({k: mine.state_dict()[k] for k in keys}, seed=seed, style="trained")
     mine.load_state_dict(sd, strict=True)
-    for T, lens in ((203, [203, 150, 99]), (201, [201, 64, 201]), (410, [410, 100, 30])):
-        mel, lt = synth.synth_mel(3, 80, T, seed=5), torch.tensor(lens)
+    for i, (B, T, lens) in enumerate(cases):
         with torch.no_grad():
-            assert torch.equal(ref(mel, lt), mine(mel, lt))
+            _assert_reproduces(z, "splitformer", i, mine(synth.synth_mel(B, 80, T, seed=seed), torch.tensor(lens)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
 def test_zipformer_oracle_equals_reference_class_body():
-    """the reference's Early_zipformer (early_exit.py:117-224), imported unmodified, equals
-    oracle.EarlyZipformerRef bit for bit (632 state_dict keys at 19 one-layer groups)."""
-    ee = _import_reference()
-    kw = base_kwargs(n_enc_exits=19, n_enc_layers=1, d_feed_forward=128, depthwise_kernel_size=7, dec_voc_size=64)
-    ref, mine = ee.Early_zipformer(**kw).eval(), R.EarlyZipformerRef(**kw).eval()
-    assert sorted(ref.state_dict().keys()) == sorted(mine.state_dict().keys())
-    sd = synth.synth_state_dict(ref.state_dict(), seed=6, style="trained")
-    ref.load_state_dict(sd, strict=True)
+    """the reference's Early_zipformer (early_exit.py:117-224) equals oracle.EarlyZipformerRef (632
+    state_dict keys at 19 one-layer groups)."""
+    z, kw, cases, seed, keys, shapes = _reference_body("zipformer")
+    mine = R.EarlyZipformerRef(**kw).eval()
+    assert len(keys) == 632 and sorted(mine.state_dict().keys()) == sorted(keys)
+    assert dict(zip(keys, shapes)) == {k: tuple(v.shape) for k, v in mine.state_dict().items()}
+    sd = synth.synth_state_dict({k: mine.state_dict()[k] for k in keys}, seed=seed, style="trained")
     mine.load_state_dict(sd, strict=True)
-    for T, lens in ((203, [203, 150]), (211, [120, 211]), (330, [330, 64])):
-        mel, lt = synth.synth_mel(2, 80, T, seed=6), torch.tensor(lens)
+    for i, (B, T, lens) in enumerate(cases):
         with torch.no_grad():
-            assert torch.equal(ref(mel, lt), mine(mel, lt))
+            _assert_reproduces(z, "zipformer", i, mine(synth.synth_mel(B, 80, T, seed=seed), torch.tensor(lens)))
 
 
 def test_zipformer_oracle_reproduces_golden():
@@ -94,39 +101,34 @@ def test_splitformer_oracle_reproduces_golden():
         assert torch.allclose(out, torch.from_numpy(z[f"logp{i}"]), atol=2e-5)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
 def test_reference_legacy_attention_matches_torch_sdpa():
     """SURVEY 8a row a14: the legacy models/layers attention (importable as-is) is softmax(qk^T/sqrt(d))v;
-    this is the un-masked special case of what the attention kernel computes."""
-    if REFERENCE not in sys.path:
-        sys.path.insert(0, REFERENCE)
-    from models.layers.scale_dot_product_attention import ScaleDotProductAttention
+    this is the un-masked special case of what the attention kernel computes.  Its output on seeded q, k, v is stored."""
+    z = np.load(os.path.join(GOLDEN, "reference_bodies.npz"))
     torch.manual_seed(0)
     q, k, v = (torch.randn(2, 4, 37, 32) for _ in range(3))
-    out = ScaleDotProductAttention()(q, k, v)
-    out = out[0] if isinstance(out, tuple) else out
+    qkv = torch.stack([q, k, v]).double()
+    # the inputs the output was made from
+    assert np.allclose([qkv.sum().item(), qkv.square().sum().item()], z["sdpa_qkv_checksum"], rtol=1e-12, atol=1e-9)
+    out = torch.from_numpy(z["sdpa_out"])
     want = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     assert torch.allclose(out, want, atol=1e-5)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only exists in the build container")
 def test_legacy_oracle_and_product_tree_equal_reference_early_encoder():
     """the legacy Early_encoder (early_exit.py:497-562) and everything below it IS in the reference
-    tree; the oracle restatement equals it bit for bit and the product mirror has the same state_dict keys."""
+    tree; the oracle restatement equals it and the product mirror has the same state_dict keys and shapes."""
     from early_exit_transformer_amd.legacy import Early_encoder
     from oracle import legacy_ref as LR
-    ee = _import_reference()
-    kw = base_kwargs(n_enc_exits=2, n_enc_layers=2, d_feed_forward=256)
+    z, kw, cases, seed, keys, shapes = _reference_body("legacy")
     kw.pop("depthwise_kernel_size")
-    ref, mine, prod = ee.Early_encoder(**kw).eval(), LR.EarlyEncoderRef(**kw).eval(), Early_encoder(**kw)
-    assert list(ref.state_dict().keys()) == list(mine.state_dict().keys()) == list(prod.state_dict().keys())
-    assert all(ref.state_dict()[k].shape == prod.state_dict()[k].shape for k in ref.state_dict())
-    sd = synth.synth_state_dict(ref.state_dict(), seed=6, style="trained")
-    ref.load_state_dict(sd, strict=True)
-    mine.load_state_dict(sd, strict=True)
-    mel = synth.synth_mel(2, 80, 203, seed=6)
-    with torch.no_grad():
-        assert torch.equal(ref(mel), mine(mel))
+    mine, prod = LR.EarlyEncoderRef(**kw).eval(), Early_encoder(**kw)
+    assert keys == list(mine.state_dict().keys()) == list(prod.state_dict().keys())
+    assert shapes == [tuple(v.shape) for v in prod.state_dict().values()]
+    mine.load_state_dict(synth.synth_state_dict(mine.state_dict(), seed=seed, style="trained"), strict=True)
+    for i, (B, T, _) in enumerate(cases):
+        with torch.no_grad():
+            _assert_reproduces(z, "legacy", i, mine(synth.synth_mel(B, 80, T, seed=seed)))
 
 
 def test_legacy_oracle_reproduces_golden():
@@ -152,7 +154,10 @@ def test_oracle_reproduces_golden(name):
     with torch.no_grad():
         out = model(mel, torch.from_numpy(z["lengths"]))
     stride = int(z["stride"])
-    np.testing.assert_allclose(out[:, :, ::stride].numpy(), z["logp"], atol=2e-5, rtol=0)
+    # 2e-5, or 16 fp32 ulps of the largest |log-prob| where that is more: the rounding of a log-softmax grows with the logit
+    # scale, and on config1_peaky (max |log-prob| 59) the same oracle moves by 2.9e-5 with one thread instead of eight
+    atol = max(2e-5, REPLAY_ULPS * float(np.abs(z["logp"]).max()))
+    np.testing.assert_allclose(out[:, :, ::stride].numpy(), z["logp"], atol=atol, rtol=0)
     assert np.array_equal(out.argmax(-1).numpy().astype(np.int16), z["argmax"]) or \
         (out.argmax(-1).numpy() != z["argmax"]).mean() < 1e-3
     flat = [t for e in range(out.size(0)) for b in range(out.size(1)) for t in R.greedy_ctc(out[e, b])]
