@@ -527,23 +527,14 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
   // MFMA-bound at three passes: -8 us of 169 per launch, profiles/r03_ab_chain_knobs.txt), heads too 4.0e-4
   // (d_model 512 keeps the fragment formats there: its f8 projection kernels do not fit the register file yet)
   const int np_p = (precision == EEC_PREC_F16F8 && c.arch == EEC_ARCH_CONFORMER && c.d_model == 256 && c.d_ff % 128 == 0) ? 8 : np_o;
-  // operand format per GEMM group of the production plan (a diagnostic build can override them one by one)
-  int np_qkv = np_p, np_att = np_o, np_glu = np_p, np_front = np_p, np_head = np_o;
+  // operand format per GEMM group of the production plan
+  const int np_qkv = np_p, np_att = np_o, np_glu = np_p, np_front = np_p, np_head = np_o;
   half_t* const vt_lo = np_o == 3 ? ws.vt + (size_t)B * Tp * c.d_model : nullptr;  // V keeps its fp16 residual in the split modes
   // exact parity mode (f16x3): Q, K and the attention probabilities keep their fp16 residuals as well (three MFMA products per
   // attention product, attention as its own launch): what remains of the log-prob error is the GLU output's fp16 rounding
   const bool exact_attn = precision == EEC_PREC_F16X3 && c.arch == EEC_ARCH_CONFORMER;
   half_t* const q_lo = exact_attn ? ws.q + (size_t)B * Tp * c.d_model : nullptr;
   half_t* const k_lo = exact_attn ? ws.k + (size_t)B * Tp * c.d_model : nullptr;
-#ifdef EEC_NP_EXPERIMENT
-  if (const char* ov = getenv("EEC_NP_OVERRIDE")) {  // e.g. "qkv=1,glu=1": error-budget experiments (tools/np_budget.py)
-    auto pick = [&](const char* key, int& dst) {
-      const char* p = strstr(ov, key);
-      if (p) dst = atoi(p + strlen(key));
-    };
-    pick("qkv=", np_qkv), pick("att=", np_att), pick("glu=", np_glu), pick("front=", np_front), pick("head=", np_head);
-  }
-#endif
   const int M = B * Tq, D = c.d_model, H = c.n_heads;
   int step = 0;
   auto done = [&](void) -> bool { return stop_after >= 0 && step > stop_after; };

@@ -42,7 +42,7 @@ __device__ __forceinline__ void acc_init_bias(f32x16 (&acc)[MT][NT], const float
 }
 
 // The same start values in the layout the format's k-loop wants: the quadrant layout for the split format on the 16x16x32 shape
-// (eec_device.h, EEC_MFMA16: register 4 (2 ra + cb) + j <-> output feature 16 ra + 8 hh + 4 u + j, both frame blocks cb), so that
+// (eec_device.h: register 4 (2 ra + cb) + j <-> output feature 16 ra + 8 hh + 4 u + j, both frame blocks cb), so that
 // the product needs no conversion on the way in; the standard layout otherwise.
 template <int NP, int MT, int NT>
 __device__ __forceinline__ void acc_init_bias_np(f32x16 (&acc)[MT][NT], const float* __restrict__ bias_n0, float scale = 1.0f) {
@@ -113,7 +113,7 @@ __device__ __forceinline__ void proj_gemm(f32x16 (&acc)[MT][NT], const char* sme
   if constexpr (NP == 8) {
     const char* a8_lane = smem + G::kAPlane + (lane & 31) * G::kA8Ld + hh * 32;
     const uint4* rec = w.wf8 + (size_t)t0 * NG * kF8Rec + lane;
-    gemm_ring_f8<NG, NT, true, PF, NoSide, 0, kProjNWB, 0, MT, false, (EEC_X_HI8 ? G::kA8Hi : 0)>(acc, a_lane, G::kALd, a8_lane, G::kA8Ld, rec,
+    gemm_ring_f8<NG, NT, true, PF, NoSide, 0, kProjNWB, MT>(acc, a_lane, G::kALd, a8_lane, G::kA8Ld, rec,
                                                                                                     (size_t)NG * kF8Rec, st.r, st.wg);
   } else {
     // (the accumulators come from acc_init_bias_np: already in the layout this format's k-loop wants)
@@ -236,8 +236,8 @@ __device__ __forceinline__ void qkv_body(char* smem, const QkvArgs& a, int row0,
               o[i] = to_half_sat(v);
               ol[i] = (half_t)(v - (float)o[i]);
             }
-            store_maybe_nt<EEC_NT_QKV != 0>((h4*)(dst + 8 * g), o);
-            if (a.q_lo) store_maybe_nt<EEC_NT_QKV != 0>((h4*)(a.q_lo + qoff + 8 * g), ol);
+            *(h4*)(dst + 8 * g) = o;
+            if (a.q_lo) *(h4*)(a.q_lo + qoff + 8 * g) = ol;
           }
         }
       }
@@ -267,8 +267,8 @@ __device__ __forceinline__ void qkv_body(char* smem, const QkvArgs& a, int row0,
             o[i] = to_half_sat(v);
             ol[i] = (half_t)(v - (float)o[i]);
           }
-          store_maybe_nt<EEC_NT_QKV != 0>((h4*)(dst + 8 * g), o);
-          if (a.k_lo) store_maybe_nt<EEC_NT_QKV != 0>((h4*)(a.k_lo + koff + 8 * g), ol);
+          *(h4*)(dst + 8 * g) = o;
+          if (a.k_lo) *(h4*)(a.k_lo + koff + 8 * g) = ol;
         }
       }
     }
@@ -335,8 +335,11 @@ __device__ __forceinline__ void qkv_body(char* smem, const QkvArgs& a, int row0,
           for (int i = 0; i < 4; ++i) {
             const float v = acc[mt][j][4 * g + i];
             const half_t hi = to_half_sat(v);
-            store_maybe_nt<EEC_NT_QKV != 0>(dst + (size_t)(8 * g + i) * a.Tp, hi);
-            if (a.vt_lo) store_maybe_nt<EEC_NT_QKV != 0>(a.vt_lo + voff + (size_t)(8 * g + i) * a.Tp, (half_t)(v - (float)hi));
+            *(dst + (size_t)(8 * g + i) * a.Tp) = hi;
+            if (a.vt_lo) {
+              half_t* const lo = a.vt_lo + voff + (size_t)(8 * g + i) * a.Tp;
+              *lo = (half_t)(v - (float)hi);
+            }
           }
       }
     }
@@ -515,10 +518,6 @@ __device__ __forceinline__ void dw_front(char* smem, const DwArgs& d, int M, int
       if (NP == 8) {  // e5m2 bytes of the two residuals (adjacent channels are adjacent in the permuted byte plane)
         const unsigned lb = __builtin_bit_cast(unsigned, lo8_gain(sp.lo));
         *(unsigned short*)(smem + G::kAPlane + rl * G::kA8Ld + lo8_pos(c)) = (unsigned short)(((lb >> 8) & 0xffu) | ((lb >> 16) & 0xff00u));
-        if (EEC_X_HI8) {
-          const unsigned hb = __builtin_bit_cast(unsigned, sp.hi);
-          *(unsigned short*)(smem + G::kAPlane + rl * G::kA8Ld + G::kA8Hi + lo8_pos(c)) = (unsigned short)(((hb >> 8) & 0xffu) | ((hb >> 16) & 0xff00u));
-        }
       }
     }
   }

@@ -49,27 +49,6 @@ typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
-// Streaming-store experiments (profiles/r04_ab_nt_stores.txt): which of the large write-once outputs of the inference kernels carry the
-// non-temporal hint, so that they do not push the weight streams out of the L2.  NT = a compile-time flag per site.
-template <bool NT, typename T>
-__device__ __forceinline__ void store_maybe_nt(T* p, T v) {
-#ifdef EEC_ABLATE_QKV_STORES  // timing-only build: what the Q / K / V / GLU / head stores cost (the value stays live, nothing is written)
-  asm volatile("" ::"v"(v), "v"(p));
-  return;
-#endif
-  if constexpr (NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
-#ifndef EEC_NT_QKV
-#define EEC_NT_QKV 0
-#endif
-#ifndef EEC_NT_HEAD
-#define EEC_NT_HEAD 0
-#endif
-#ifndef EEC_NT_G
-#define EEC_NT_G 0
-#endif
-
 constexpr int kWave = 64;
 constexpr float kLnEps = 1e-5f;
 constexpr float kLog2e = 1.4426950408889634f;
@@ -79,14 +58,6 @@ constexpr float kHalfMax = 65504.0f;
 // 32-row tiles (acc[2][1]); D = 512: 32-row tiles, a wave owns TWO adjacent column tiles and one row tile (acc[1][2]).
 // LDS geometry in bytes; row pads of one 16-B slot make ds_read_b128 of "32 different rows, same column"
 // conflict-free (stride = 4 banks mod 64).
-// EEC_X_HI8 (experiment knob, off): the activations' e5m2 hi bytes (the a_hi8 operand of the weight-residual correction product)
-// are written ONCE by whoever writes the planes and read as MFMA operands straight from LDS, instead of being re-made with two
-// v_perm per fragment and k-step by every wave that multiplies the tile (chain kernel producers: -64 VALU per slot and wave).
-// Bit-identical results; same-box A/B: 171.6 us with, 171.0 us without (profiles/r03_ab_chain_knobs.txt) -- the producers' VALU
-// issue is not what bounds the slot.
-#ifndef EEC_X_HI8
-#define EEC_X_HI8 0
-#endif
 template <int D>
 struct Geo {
   static_assert(D == 256 || D == 512, "d_model must be 256 or 512");
@@ -98,11 +69,8 @@ struct Geo {
   static constexpr int kRPW = kRows / 8;        // rows per wave in a row pass: 8 / 4
   static constexpr int kALd = (D + 8) * 2;      // 528 / 1040 : [rows][D] fp16 activation plane
   static constexpr int kAPlane = kRows * kALd;  // 33792 / 33280
-  // NP == 8 byte plane, per row: [D e5m2 residual bytes][D e5m2 top bytes of the hi halves (EEC_X_HI8)][16 pad], both in the
-  // permuted MX slot order (lo8_pos).  With the hi bytes the row stride equals the fp16 plane's (conflict-free ds_read_b128) and the
-  // plane fills exactly the region the fp16 lo plane of the split format has: no extra LDS.
-  static constexpr int kA8Ld = EEC_X_HI8 ? 2 * D + 16 : D + 16;  // 528 / 1040 (272 / 528 without the hi bytes)
-  static constexpr int kA8Hi = D;               // byte offset of the hi8 half inside a row
+  // NP == 8 byte plane, per row: [D e5m2 residual bytes][16 pad], in the permuted MX slot order (lo8_pos)
+  static constexpr int kA8Ld = D + 16;          // 272 / 528
   static constexpr int kELd = (D + 4) * 4;      // 1040 / 2064: [rows][D] fp32 exchange tile
   static constexpr int kETile = kRows * kELd;   // 66560 / 66048
 };
@@ -110,18 +78,13 @@ struct Geo {
 // Row tile of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share an XCD and its
 // L2); consecutive row tiles -- the four tiles of an utterance at T' = 256 -- exchange data between launches (K / V of the
 // utterance, the +-15-frame halo of the depthwise conv) and every tile re-reads its own residual rows in the next launch.
-// EEC_XCD_TILES: inside each group of 32 blocks, XCD x (= b % 8) gets the four CONSECUTIVE tiles 4x .. 4x+3, and the same
+// Inside each group of 32 blocks, XCD x (= b % 8) gets the four CONSECUTIVE tiles 4x .. 4x+3, and the same
 // map is used by every row-tile kernel, so that traffic is served by the XCD's own L2 instead of the fabric.  Speed only:
 // correctness does not depend on the placement (kernel boundaries order all global traffic).
-#ifndef EEC_XCD_TILES
-#define EEC_XCD_TILES 1
-#endif
 __device__ __forceinline__ int row_tile_index() {
   const int b = blockIdx.x;
-#if EEC_XCD_TILES
   const int full = (int)(gridDim.x & ~31u);  // blocks in whole groups of 32; a ragged tail keeps the identity map
   if (b < full) return (b & ~31) + (b & 7) * 4 + ((b >> 3) & 3);
-#endif
   return b;
 }
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
@@ -252,18 +215,8 @@ __device__ __forceinline__ int acc_row(int i, int lane) { return (i & 3) + 8 * (
 #ifdef EEC_KSTEP_STAMPS
 __device__ void eec_kstep_stamp();
 #endif
-// weight-stream load (experiment knob EEC_W_NT: non-temporal = L1-bypassing loads for the streamed fragments)
-#ifndef EEC_W_NT
-#define EEC_W_NT 0
-#endif
-__device__ __forceinline__ uint4 wload(const uint4* p) {
-#if EEC_W_NT
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(uint4, __builtin_nontemporal_load((const u32x4_t*)p));
-#else
-  return *p;
-#endif
-}
+// weight-stream load of the f8 stream (a function of its own: hipcc orders the surrounding code differently for a plain dereference)
+__device__ __forceinline__ uint4 wload(const uint4* p) { return *p; }
 template <int NP, int PF, int NT = 1>
 struct WRing {
   uint4 q[PF][NT][(NP == 3) ? 2 : 1];
@@ -272,20 +225,13 @@ struct WRing {
 template <int NP, int PF, int NT>
 __device__ __forceinline__ void ring_fill_32(WRing<NP, PF, NT>& r, const uint4* __restrict__ w_lane, size_t nt_stride,
                                           int steps_avail) {
-#ifdef EEC_ABLATE_W
-  if (threadIdx.x > 100000)  // timing-only build: no weight loads at all
-#endif
 #pragma unroll
   for (int p = 0; p < PF; ++p)
     if (p < steps_avail) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         r.q[p][nt][0] = w_lane[nt * nt_stride + (size_t)p * 128];
-#ifdef EEC_X3_LO_SKIP  // timing-only build: the lo fragments are not loaded (what a 2 B / weight stream would cost)
-        if (NP == 3) r.q[p][nt][(NP == 3) ? 1 : 0] = r.q[p][nt][0];
-#else
         if (NP == 3) r.q[p][nt][(NP == 3) ? 1 : 0] = w_lane[nt * nt_stride + (size_t)p * 128 + 64];
-#endif
       }
     }
   __builtin_amdgcn_sched_barrier(0);  // keep these loads HERE: one stage ahead of their consumer
@@ -317,11 +263,7 @@ __device__ __forceinline__ void gemm_ring_32(f32x16 (&acc)[MT][NT], const char* 
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     const int cur = s & 1, nxt = cur ^ 1;
-#ifdef EEC_ABLATE_A
-    if (s == 0) {  // timing-only build: one LDS fragment read per stage, reused for every k-step
-#else
     if (s + 1 < KS) {
-#endif
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         ah[nxt][mt] = *(const h8*)(a_lane + mt * 32 * ld_bytes + (s + 1) * 32);
@@ -350,19 +292,11 @@ __device__ __forceinline__ void gemm_ring_32(f32x16 (&acc)[MT][NT], const char* 
         }
       }
     }
-#ifdef EEC_ABLATE_W
-    if (false) {  // timing-only build: no in-loop weight loads
-#else
     if (s + PF < KS) {
-#endif
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         r.q[s % PF][nt][0] = w_lane[nt * nt_stride + (size_t)(s + PF) * 128];
-#ifdef EEC_X3_LO_SKIP
-        if (NP == 3) r.q[s % PF][nt][LO] = r.q[s % PF][nt][0];
-#else
         if (NP == 3) r.q[s % PF][nt][LO] = w_lane[nt * nt_stride + (size_t)(s + PF) * 128 + 64];
-#endif
       }
     }
     side(s);
@@ -445,7 +379,7 @@ __device__ __forceinline__ void gemm_plain_ring(f32x16 (&acc)[2][NT], const char
 }
 
 // ===========================================================================
-// The same products on v_mfma_f32_16x16x32_f16 (EEC_MFMA16, the default).  The two fp16 shapes have the same MACs per cycle, but
+// The same products on v_mfma_f32_16x16x32_f16.  The two fp16 shapes have the same MACs per cycle, but
 // under load the chip holds a higher clock on 16x16x32 (tools/mfma_shape_bench.hip: 2.02-2.08 GHz against 1.69-1.74 GHz in bare
 // loops on random data; timing-only swap inside these kernels: chain launch -7.7 %, profiles/r04_micro_mfma_shape_clock.txt).
 // Everything around the k-loops keeps its layouts; only the lane <-> element map of the loads and of the accumulators differs:
@@ -458,11 +392,8 @@ __device__ __forceinline__ void gemm_plain_ring(f32x16 (&acc)[2][NT], const char
 //     is restored with v_permlane16_swap + v_permlane32_swap on the register pairs (4 (2 ra) + i, 4 (2 ra + 1) + i): 32 cross-lane
 //     instructions per tile, once per accumulation (acc_q_to_std / acc_std_to_q).
 // ===========================================================================
-#ifndef EEC_MFMA16
-#define EEC_MFMA16 1
-#endif
-// (a translation-unit switch, off: the single-product format on the 16x16x32 shape too -- slower in the inference kernels; an experiment of
-// the training step's fused feed-forward, whose tape stores want the quadrant layout's 16 rows x 64 B per instruction)
+// EEC_MFMA16_NP1 (a translation-unit switch, off: the single-product format on the 16x16x32 shape too -- slower in the inference kernels;
+// set by the training step's fused feed-forward objects of ffn.hip, whose tape stores want the quadrant layout's 16 rows x 64 B per instruction)
 #ifndef EEC_MFMA16_NP1
 #define EEC_MFMA16_NP1 0
 #endif
@@ -537,46 +468,19 @@ __device__ __forceinline__ const uint4* w_lane16(const uint4* w_lane) {
   return w_lane + 96 * hh + 16 * u;
 }
 
-// EEC_W_SADDR (experiment, off): the weight stream's loads as SGPR base + 32-bit lane offset (`global_load_dwordx4 v, v_off,
-// s[base:base+1]`) instead of a 64-bit address per lane -- half the address payload per load instruction.  Measured SLOWER: chain
-// launch 207.8 -> 217.6 us same-box (the uniform part has to be pinned in SGPRs per load with readfirstlane, or hipcc folds it back
-// into one 64-bit VGPR address): the ~75 cycles a fragment load costs its wave are not address traffic.
-#ifndef EEC_W_SADDR
-#define EEC_W_SADDR 0
-#endif
 struct WAddr16 {
-  const char* base;  // wave-uniform
-  unsigned voff;     // this lane's byte offset: slot (lane & 15) + 32 u of fragment hh
-  __device__ __forceinline__ uint4 load(size_t uniform_u4) const {
-#if EEC_W_SADDR
-    // the uniform part is pinned in SGPRs (readfirstlane is opaque to the optimiser: left alone it folds base + voff into ONE 64-bit
-    // VGPR address and adds the uniform offsets to that)
-    const size_t a = (size_t)base + uniform_u4 * 16;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return *(const uint4*)((const char*)(((size_t)hi << 32) | lo) + voff);
-#else
-    return *(const uint4*)(base + uniform_u4 * 16 + voff);
-#endif
-  }
+  const char* base;  // this lane's fragment slot (lane & 15) + 32 u of fragment hh
+  __device__ __forceinline__ uint4 load(size_t uniform_u4) const { return *(const uint4*)(base + uniform_u4 * 16); }
 };
 __device__ __forceinline__ WAddr16 w_addr16(const uint4* w_lane) {
   const int lane = lane_id(), hh = lane >> 5, u = (lane >> 4) & 1;
-#if EEC_W_SADDR
-  const uint4* b = w_lane - lane;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(size_t)b), hi = __builtin_amdgcn_readfirstlane((unsigned)((size_t)b >> 32));
-  return WAddr16{(const char*)(((size_t)hi << 32) | lo), (unsigned)(lane + 96 * hh + 16 * u) * 16u};
-#else
-  return WAddr16{(const char*)(w_lane + 96 * hh + 16 * u), 0u};
-#endif
+  return WAddr16{(const char*)(w_lane + 96 * hh + 16 * u)};
 }
 
 template <int NP, int PF, int NT>
 __device__ __forceinline__ void ring_fill_16(WRing<NP, PF, NT>& r, const uint4* __restrict__ w_lane, size_t nt_stride, int steps_avail) {
   static_assert(PF % 2 == 0, "the ring is dealt in double k-steps");
   const WAddr16 w16 = w_addr16(w_lane);
-#ifdef EEC_ABLATE_W
-  if (threadIdx.x > 100000)  // timing-only build: no weight loads at all
-#endif
 #pragma unroll
   for (int p = 0; p < PF; ++p)
     if (p < steps_avail) {
@@ -617,11 +521,7 @@ __device__ __forceinline__ void gemm_ring_16(f32x16 (&acc)[MT][NT], const char* 
 #pragma unroll
   for (int p = 0; p < KS; ++p) {
     const int S = p >> 1, rb = p & 1, cur = p & 1, nxt = cur ^ 1;
-#ifdef EEC_ABLATE_A
-    if (p == 0) {
-#else
     if (p + 1 < KS) {
-#endif
       const int off = (16 * ((p + 1) & 1)) * ld_bytes + ((p + 1) >> 1) * 64;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -650,17 +550,9 @@ __device__ __forceinline__ void gemm_ring_16(f32x16 (&acc)[MT][NT], const char* 
         // this (row block, column tile) of the ring is finished: refill it right away -- the loads leave in pairs spread over the
         // step instead of in one burst at its end (an in-order wave stalls at issue while the CU's load path is backed up)
         if (rb == 1) {
-#ifdef EEC_ABLATE_W
-          if (false) {
-#else
           if (2 * S + PF < KS) {
-#endif
             r.q[(2 * S + wb) % PF][nt][0] = w16.load(nt * nt_stride + 16 * wb + (size_t)(S + PF / 2) * 256);
-#ifdef EEC_X3_LO_SKIP
-            if (NP == 3) r.q[(2 * S + wb) % PF][nt][LO] = r.q[(2 * S + wb) % PF][nt][0];
-#else
             if (NP == 3) r.q[(2 * S + wb) % PF][nt][LO] = w16.load(nt * nt_stride + 16 * wb + (size_t)(S + PF / 2) * 256 + 64);
-#endif
           }
         }
       }
@@ -719,12 +611,12 @@ __device__ __forceinline__ void gemm_plain_16(f32x16 (&acc)[MT][NT], const char*
   if constexpr (OUT_STD) accs_q_to_std<MT, NT>(acc);
 }
 
-// The names the kernels use: the 16x16x32 forms for the split format NP = 3 (-DEEC_MFMA16=0: the 32x32x16 forms everywhere).
+// The names the kernels use: the 16x16x32 forms for the split format NP = 3.
 // NP = 1 keeps 32x32x16: with a third of the MFMAs per SiLU the producers are VALU-bound, and a 16x16x32 MFMA holds the SIMD's
 // vector issue for 8 of its 16 cycles instead of 8 of 32 (measured: `mixed` 27.0 -> 22.9 M, `f16` 30.3 -> 23.9 M frames/s).
 // IN_STD / OUT_STD only matter for the 16x16x32 forms (the 32x32x16 accumulators are always in the standard layout).
 template <int NP>
-constexpr bool kMfma16For = (EEC_MFMA16 != 0) && (NP == 3 || (EEC_MFMA16_NP1 != 0 && NP == 1));
+constexpr bool kMfma16For = NP == 3 || (EEC_MFMA16_NP1 != 0 && NP == 1);
 template <int NP, int PF, int NT>
 __device__ __forceinline__ void ring_fill(WRing<NP, PF, NT>& r, const uint4* __restrict__ w_lane, size_t nt_stride, int steps_avail) {
   if constexpr (kMfma16For<NP>) ring_fill_16<NP, PF, NT>(r, w_lane, nt_stride, steps_avail);
@@ -797,18 +689,11 @@ struct WGroupF8 {      // lo8 + scale of ONE 64-k group for NT n-tiles
 template <int NT>
 __device__ __forceinline__ void f8_group_load(WGroupF8<NT>& g, const uint4* __restrict__ rec_lane, size_t nt_stride) {
   // rec_lane = record base + lane
-#ifdef EEC_ABLATE_W
-  if (threadIdx.x > 100000)  // timing-only build: no weight loads at all
-#endif
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const uint4* r = rec_lane + nt * nt_stride - lane_id();
     g.lo[nt][0] = wload(r + 256 + 2 * lane_id());
-#ifdef EEC_LO_HALF  // timing-only build: half the residual bytes (what an fp4 residual would stream)
-    g.lo[nt][1] = g.lo[nt][0];
-#else
     g.lo[nt][1] = wload(r + 256 + 2 * lane_id() + 1);
-#endif
     g.sc[nt] = ((const int*)(r + 384))[lane_id()];
   }
 }
@@ -823,10 +708,7 @@ __device__ __forceinline__ void f8_group_load(WGroupF8<NT>& g, const uint4* __re
 // CONT: the stream CONTINUES into another product of the same shape whose first record (+lane) is `next_lane` (wave-uniform,
 // may be null): the last PF k-steps refill the ring -- and the last NW groups their lo8 buffers -- with that product's first
 // steps / groups, so the caller starts it with a full pipeline and no separate fill.
-// A8HI > 0: the activation tile's byte plane also holds the hi bytes, A8HI bytes behind the residual bytes of the same row
-// (Geo::kA8Hi; EEC_X_HI8): they are read as the group's operand instead of being permuted out of the fp16 fragments.
-template <int NG, int NT, bool SWAP, int PF, typename Side = NoSide, int SIDE_VALU = 0, int NW = NG, int DROP = 0, int MT = 2, bool CONT = false,
-          int A8HI = 0>
+template <int NG, int NT, bool SWAP, int PF, typename Side = NoSide, int SIDE_VALU = 0, int NW = NG, int MT = 2, bool CONT = false>
 __device__ __forceinline__ void gemm_ring_f8(f32x16 (&acc)[MT][NT], const char* a_lane, int ld_bytes, const char* a8_lane,
                                              int ld8_bytes, const uint4* __restrict__ rec_lane, size_t nt_stride,
                                              WRing<1, PF, NT>& r, WGroupF8<NT> (&wg)[NW], Side side = Side(),
@@ -837,43 +719,27 @@ __device__ __forceinline__ void gemm_ring_f8(f32x16 (&acc)[MT][NT], const char* 
   h8 ah[2][MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) ah[0][mt] = *(const h8*)(a_lane + mt * 32 * ld_bytes);
-  [[maybe_unused]] uint2 a8[MT][4];  // [mt][step in group]: e5m2 of the activation hi fragments (A8HI == 0)
-  [[maybe_unused]] i32x8 ahi8[MT];   // ... or the group's hi bytes read from the byte plane (A8HI > 0)
+  uint2 a8[MT][4];  // [mt][step in group]: e5m2 of the activation hi fragments
   uint2 w8[NT][4];  // [nt][step in group]: e5m2 of the weight hi fragments
   i32x8 alo[MT];    // activation lo8 of the current group
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     const int cur = s & 1, nxt = cur ^ 1, q = s & 3, g = s >> 2;
-#ifdef EEC_ABLATE_A
-    if (s == 0) {  // timing-only build: one LDS fragment read per stage
-#else
     if (s + 1 < KS) {
-#endif
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) ah[nxt][mt] = *(const h8*)(a_lane + mt * 32 * ld_bytes + (s + 1) * 32);
     }
-#ifdef EEC_ABLATE_A
-    if (s == 0) {
-#else
     if (q == 0) {
-#endif
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const uint4 l0 = *(const uint4*)(a8_lane + mt * 32 * ld8_bytes + g * 64);
         const uint4 l1 = *(const uint4*)(a8_lane + mt * 32 * ld8_bytes + g * 64 + 16);
         alo[mt] = (i32x8){(int)l0.x, (int)l0.y, (int)l0.z, (int)l0.w, (int)l1.x, (int)l1.y, (int)l1.z, (int)l1.w};
-        if constexpr (A8HI > 0) {
-          const uint4 h0 = *(const uint4*)(a8_lane + A8HI + mt * 32 * ld8_bytes + g * 64);
-          const uint4 h1 = *(const uint4*)(a8_lane + A8HI + mt * 32 * ld8_bytes + g * 64 + 16);
-          ahi8[mt] = (i32x8){(int)h0.x, (int)h0.y, (int)h0.z, (int)h0.w, (int)h1.x, (int)h1.y, (int)h1.z, (int)h1.w};
-        }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (A8HI == 0) {
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) a8[mt][q] = top_bytes(__builtin_bit_cast(uint4, ah[cur][mt]));
-    }
+    for (int mt = 0; mt < MT; ++mt) a8[mt][q] = top_bytes(__builtin_bit_cast(uint4, ah[cur][mt]));
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const uint4 wq = r.q[s % PF][nt][0];
@@ -883,18 +749,12 @@ __device__ __forceinline__ void gemm_ring_f8(f32x16 (&acc)[MT][NT], const char* 
       for (int mt = 0; mt < MT; ++mt)
         acc[mt][nt] = SWAP ? mfma16(bh, ah[cur][mt], acc[mt][nt]) : mfma16(ah[cur][mt], bh, acc[mt][nt]);
     }
-#ifdef EEC_ABLATE_W
-    if (false) {
-#else
     if (s + PF < KS) {
-#endif
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) r.q[s % PF][nt][0] = wload(rec_lane + nt * nt_stride + hi_addr(s + PF));
     } else if (CONT && next_lane) {
-#ifndef EEC_ABLATE_W
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) r.q[s % PF][nt][0] = wload(next_lane + nt * nt_stride + hi_addr(s + PF - KS));
-#endif
     }
     if (q == 3) {  // the group's two correction products
 #pragma unroll
@@ -906,17 +766,14 @@ __device__ __forceinline__ void gemm_ring_f8(f32x16 (&acc)[MT][NT], const char* 
                            (int)G.lo[nt][1].x, (int)G.lo[nt][1].y, (int)G.lo[nt][1].z, (int)G.lo[nt][1].w};
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          i32x8 ahi;
-          if constexpr (A8HI > 0) ahi = ahi8[mt];
-          else ahi = (i32x8){(int)a8[mt][0].x, (int)a8[mt][0].y, (int)a8[mt][1].x, (int)a8[mt][1].y,
+          const i32x8 ahi = {(int)a8[mt][0].x, (int)a8[mt][0].y, (int)a8[mt][1].x, (int)a8[mt][1].y,
                              (int)a8[mt][2].x, (int)a8[mt][2].y, (int)a8[mt][3].x, (int)a8[mt][3].y};
-          // DROP (diagnostic builds only): bit 0 skips the activation-residual term, bit 1 the weight-residual term
           if (SWAP) {
-            if (!(DROP & 1)) acc[mt][nt] = mfma_f8(whi, alo[mt], acc[mt][nt], kE8M0One, kE8M0One);
-            if (!(DROP & 2)) acc[mt][nt] = mfma_f8(wlo, ahi, acc[mt][nt], G.sc[nt], kE8M0One);
+            acc[mt][nt] = mfma_f8(whi, alo[mt], acc[mt][nt], kE8M0One, kE8M0One);
+            acc[mt][nt] = mfma_f8(wlo, ahi, acc[mt][nt], G.sc[nt], kE8M0One);
           } else {
-            if (!(DROP & 1)) acc[mt][nt] = mfma_f8(alo[mt], whi, acc[mt][nt], kE8M0One, kE8M0One);
-            if (!(DROP & 2)) acc[mt][nt] = mfma_f8(ahi, wlo, acc[mt][nt], kE8M0One, G.sc[nt]);
+            acc[mt][nt] = mfma_f8(alo[mt], whi, acc[mt][nt], kE8M0One, kE8M0One);
+            acc[mt][nt] = mfma_f8(ahi, wlo, acc[mt][nt], kE8M0One, G.sc[nt]);
           }
         }
       }
@@ -938,9 +795,6 @@ __device__ __forceinline__ void gemm_ring_f8(f32x16 (&acc)[MT][NT], const char* 
 // ring fill for the f8 stream: hi fragments of the first PF k-steps of a stage
 template <int PF, int NT>
 __device__ __forceinline__ void ring_fill_f8(WRing<1, PF, NT>& r, const uint4* __restrict__ rec_lane, size_t nt_stride) {
-#ifdef EEC_ABLATE_W
-  if (threadIdx.x > 100000)  // timing-only build: no weight loads at all
-#endif
 #pragma unroll
   for (int p = 0; p < PF; ++p)
 #pragma unroll
@@ -1087,10 +941,6 @@ __device__ __forceinline__ void rows_to_planes(char* lds_act, RowV<Geo<D>::kQ> (
         lg.xy = lo8_gain(s0.lo), lg.zw = lo8_gain(s1.lo);
         const uint2 lb = __builtin_bit_cast(uint2, lg);
         *(unsigned*)(lds_act + G::kAPlane + rl * G::kA8Ld + lo8_pos(col)) = __builtin_amdgcn_perm(lb.y, lb.x, 0x07050301u);
-        if (EEC_X_HI8) {
-          const uint2 hb = __builtin_bit_cast(uint2, hi);
-          *(unsigned*)(lds_act + G::kAPlane + rl * G::kA8Ld + G::kA8Hi + lo8_pos(col)) = __builtin_amdgcn_perm(hb.y, hb.x, 0x07050301u);
-        }
       }
     }
   }

@@ -160,7 +160,7 @@ struct ChainTrain {
 struct ChainArgs {
   float* x;  // [M][D] residual stream, updated in place
   int M, F, nstage, D;
-  int Tq;  // frames per utterance (0: unknown); only the EEC_FFN_ROT == 2 chunk order reads it
+  int Tq;  // frames per utterance (0: unknown); read by no kernel, kept so that the argument layout stays put
   FfnStage st[2];
   QkvArgs qkv;      // tail (x / M of this block are ignored)
   DwArgs dw;        // front

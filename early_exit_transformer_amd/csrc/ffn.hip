@@ -52,30 +52,24 @@ struct FfnGeo {
   // (D = 256: it fits inside them; D = 512: it is the larger of the two)
   static constexpr int kLds = 2 * G::kAPlane + (4 * kHPlane > G::kETile ? 4 * kHPlane : G::kETile);  // 137216 / 132608
 };
-#ifndef EEC_TR_ABLATE
-#define EEC_TR_ABLATE 0
-#endif
 #ifndef EEC_TR_NT
 #define EEC_TR_NT 1  // TR variants: tape stores with the non-temporal hint
-#endif
-#ifndef EEC_TR_BURST
-#define EEC_TR_BURST 0  // TR variants: 1 = tape stores of a chunk in one burst before the slot's barrier (measured slower: 136-139 against 125.5 us)
 #endif
 // k-steps of W1 / W2 fragments a producer / consumer wave keeps in flight.  The shared weight stream
 // out of L2 is latency x concurrency bound (tools/l2bw.hip: 64 KiB in flight per CU -> 18 TB/s,
 // 128 KiB -> 28 TB/s), so the rings are as deep as the register budget allows.
-#if (defined(EEC_FFN_TRAIN_BWD) || (defined(EEC_FFN_TRAIN) && EEC_TR_BURST)) && !defined(EEC_PF1_NP3)
-// these variants' producers hold 32 more values across a slot (backward: the requested pre-activations): paid for with two k-steps of the ring
+#if defined(EEC_FFN_TRAIN_BWD) && !defined(EEC_PF1_NP3)
+// the backward variants' producers hold 32 more values across a slot (the requested pre-activations): paid for with two k-steps of the ring
 #define EEC_PF1_NP3 6
-#define EEC_PF2_NP3 (EEC_MFMA16 ? 2 : 4)
+#define EEC_PF2_NP3 2
 #define EEC_PF1_NP1 12
 #define EEC_PF2_NP1 8
 #endif
 #ifndef EEC_PF1_NP3
 #define EEC_PF1_NP3 8
-// (4 with the 32x32x16 k-loops; the 16x16x32 consumer loop of the split format needs a few registers more, and with four steps
-// in flight it spilled 35 of them into the chunk loop: same-box A/B 217.3 us per chain launch with 4, 214.3 us with 2)
-#define EEC_PF2_NP3 (EEC_MFMA16 ? 2 : 4)
+// (the 16x16x32 consumer loop of the split format needs a few registers more than a 32x32x16 one, and with four steps in flight
+// it spilled 35 of them into the chunk loop: same-box A/B 217.3 us per chain launch with 4, 214.3 us with 2)
+#define EEC_PF2_NP3 2
 #define EEC_PF1_NP1 12
 #define EEC_PF2_NP1 8
 #endif
@@ -87,10 +81,6 @@ template <int D> struct FfnPf<D, 1> { static constexpr int P1 = EEC_PF1_NP1, P2 
 #define EEC_PF2_NP8 3
 #endif
 template <int D> struct FfnPf<D, 8> { static constexpr int P1 = EEC_PF1_NP8, P2 = D == 512 ? 2 : EEC_PF2_NP8; };  // D = 512: continued stream, PF | k-steps  // hi fragments only ride the ring in the f8 stream
-#ifndef EEC_DROP1
-#define EEC_DROP1 0  // diagnostic: correction terms of GEMM1 / GEMM2 to skip (see gemm_ring_f8)
-#define EEC_DROP2 0
-#endif
 #ifndef EEC_SIDE_VALU_NP8
 #define EEC_SIDE_VALU_NP8 5  // VALU instructions of the SiLU side work pinned behind each MFMA of GEMM1 (f8 stream)
 #endif
@@ -150,43 +140,6 @@ __device__ __forceinline__ unsigned touch_share(const void* base, size_t bytes, 
   const size_t k = (size_t)j * 64 + lane;
   const size_t ln = ((blockIdx.x >> 3) & 31) * per_wg + wl * per_wave + k;
   return (k < per_wave && ln < n_lines) ? *(const unsigned*)((const char*)base + ln * 128) : 0u;
-}
-// Rolling L2 prefetch inside a stage (f8 stream, d_model 256): the stage's weights (6.5 MB) exceed an XCD's L2 (4 MB), so
-// behind the first 4 MB every line's first reader pays the trip to the Infinity Cache and the 32 CUs of the XCD, walking the
-// same stream in near lockstep, all wait on that one fill.  Each slot, ONE wave per workgroup touches (one dword per 128-B
-// line) the workgroup's 1/32 share of the W1 + W2 records of the chunk EEC_ROLL_WARM slots ahead: 1600 lines per chunk,
-// 50 per workgroup = one wave-instruction.
-#ifndef EEC_ROLL_WARM
-#define EEC_ROLL_WARM 0
-#endif
-template <int D>
-__device__ __forceinline__ unsigned touch_chunk(const uint4* w1f8, const uint4* w2f8, int c, int F, int lane) {
-  constexpr int kRecLines = kF8Rec * 16 / 128;                 // 50 lines per record
-  constexpr int n1 = 4 * (D / 64) * kRecLines;                 // W1: 4 hidden tiles x D/64 records, contiguous
-  constexpr int n2 = 2 * kRecLines;                            // W2: per n-tile 2 records
-  constexpr int total = n1 + (D / 32) * n2, per_wg = (total + 31) / 32;
-  static_assert(per_wg <= 64, "one wave-instruction per workgroup and chunk");
-  const int li = (int)((blockIdx.x >> 3) & 31) * per_wg + lane;
-  if (lane >= per_wg || li >= total) return 0u;
-  const char* p;
-  if (li < n1) {
-    p = (const char*)(w1f8 + (size_t)(4 * c) * (D / 64) * kF8Rec) + (size_t)li * 128;
-  } else {
-    const int t = li - n1, nt = t / n2, r = t - nt * n2;
-    p = (const char*)(w2f8 + ((size_t)nt * (F / 64) + 2 * c) * kF8Rec) + (size_t)r * 128;
-  }
-#if defined(EEC_ROLL_WARM_DMA)
-  // no register destination: the dword lands in 256 dead bytes of LDS (m0 = LDS byte address, + 4 * lane), so nothing stays
-  // live across the slot; m0 is saved and restored around the instruction
-  {
-    unsigned m0_save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(m0_save) : "v"(p), "s"(EEC_ROLL_WARM_DMA) : "memory");
-  }
-  return 0u;
-#else
-  return *(const unsigned*)p;
-#endif
 }
 // 16-byte store to the training tape.  Non-temporal: 268 MB of [M, F] tensors per launch written through the L2 as ordinary lines push
 // the weight stream -- 6.5 MB per stage against 4 MB of L2 per XCD -- out of it (same-box A/B: 172.6 us per launch with plain stores,
@@ -292,19 +245,13 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
   // NTP = 2 tiles over the same H chunk, each pass's weight stream continuing into the next (gemm_ring_f8 CONT).
   constexpr int NH = (NP == 8 && NT2 > 2) ? NT2 / 2 : 1, NTP = NT2 / NH;
   const int lane = lane_id(), w = wave_id();
-#ifndef EEC_ROLE_PAIR
-#define EEC_ROLE_PAIR 0  // experiment: 1 = both waves of a SIMD get the SAME role (waves w and w + 4 share a SIMD)
-#endif
-  const int hh = lane >> 5, wl = EEC_ROLE_PAIR ? ((w & 1) + 2 * (w >> 2)) : (w & 3);  // index inside the role (0 .. 3)
+  const int hh = lane >> 5, wl = w & 3;  // index inside the role (0 .. 3)
   const int w_s = wave_id_sgpr();
-  const int wl_s = EEC_ROLE_PAIR ? ((w_s & 1) + 2 * (w_s >> 2)) : (w_s & 3);  // the same index from the SGPR copy
+  const int wl_s = w_s & 3;  // the same index from the SGPR copy
   // wave-uniform.  The producers are the OLDER waves (0-3): issue arbitration between the two waves of a SIMD goes by
   // priority, then age, and the producers are the critical path of the chunk pipeline (measured -2.3 % forward against
   // the opposite assignment; raising their priority with s_setprio instead makes it slower)
-#ifndef EEC_PROD_YOUNG
-#define EEC_PROD_YOUNG 0  // experiment: 1 = in the split format (NP = 3) the CONSUMERS are the older waves (0-3)
-#endif
-  const bool is_producer = EEC_ROLE_PAIR ? (w & 2) == 0 : ((EEC_PROD_YOUNG && NP == 3) ? w >= 4 : w < 4);
+  const bool is_producer = w < 4;
   const int row0 = row_tile_index() * G::kRows;
   const int M = a.M, F = a.F;
   float* __restrict__ x = a.x;
@@ -315,30 +262,14 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
   const int nft = F / 32;  // 32-wide hidden tiles
   const int nchunk = (nft + 3) / 4;
   const int ks2_total = F / 16;
-  // The hidden chunks can be summed in a ROTATED order that differs between the workgroups of an XCD (all 32
-  // CUs of an XCD stream the same weights out of the same L2 in lockstep): -4 % FFN time, but the fp32
-  // summation order then depends on the tile index, i.e. on an utterance's position in the batch.  Off by
-  // default: results are bit-identical under batch sharding.
 #ifndef EEC_SKEW
 #define EEC_SKEW 56
 #endif
 #ifndef EEC_WARM_SLOTS
 #define EEC_WARM_SLOTS 4  // slots before the end of a stage at which the consumers start the L2 warm-up
 #endif
-#ifndef EEC_WARM_PROD
-#define EEC_WARM_PROD 0  // experiment: 1 = the producers issue the warm-up, one touch per slot right before the barrier
-#endif
-#ifndef EEC_FFN_ROT
-#define EEC_FFN_ROT 0
-#endif
-#if EEC_FFN_ROT == 2
-  // rotation by the tile's position INSIDE its utterance (4 chunks per tile step): the summation order of a frame then
-  // depends on nothing but its own frame index, so results stay bit-identical under batch sharding / reordering
-  const int rot = ((nft & 3) == 0 && a.Tq > 0 && a.Tq % G::kRows == 0) ? (int)((unsigned)((row0 % a.Tq) / G::kRows * 4) % (unsigned)nchunk) : 0;
-#else
-  const int rot = (EEC_FFN_ROT && (nft & 3) == 0) ? (int)((blockIdx.x >> 3) % (unsigned)nchunk) : 0;
-#endif
-  auto phys = [&](int c) { const int p = c + rot; return p >= nchunk ? p - nchunk : p; };
+  // chunk index wrapped into [0, nchunk): the identity for every index the loops below pass
+  auto phys = [&](int c) { return c >= nchunk ? c - nchunk : c; };
   const size_t w2_nt_stride = (size_t)ks2_total * 128;
 
 #ifdef EEC_TIMELINE
@@ -347,18 +278,14 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
   TL_STAMP();  // 0: kernel entry
 #if EEC_SKEW > 0
   // De-phase the workgroups that share an XCD (blockIdx % 8) by up to 3 x EEC_SKEW x 64 cycles (~5 us): all 32 CUs of
-  // an XCD otherwise walk the same weight stream in lockstep and hit the same L2 channels at the same time.  Unlike a
-  // rotated chunk order (EEC_FFN_ROT) this changes no arithmetic.  Measured: neutral on boxes that run the forward in
+  // an XCD otherwise walk the same weight stream in lockstep and hit the same L2 channels at the same time.  It changes
+  // no arithmetic.  Measured: neutral on boxes that run the forward in
   // 2.8 ms, -9 % on a box that ran it in 3.3 ms.
-#ifdef EEC_SKEW_FINE  // experiment: 32 phases (one per CU of the XCD) of EEC_SKEW_FINE x 64 cycles
-  for (int i = 0; i < (int)((blockIdx.x >> 3) & 31); ++i) __builtin_amdgcn_s_sleep(EEC_SKEW_FINE);
-#else
   for (int i = 0; i < (int)((blockIdx.x >> 3) & 3); ++i) __builtin_amdgcn_s_sleep(EEC_SKEW);
-#endif
 #endif
   constexpr int RNP = NP == 8 ? 1 : NP;  // the f8 stream keeps only the hi fragments in the ring
   // split format (NP = 3): the products run on the 16x16x32 shape and the accumulators live in the quadrant layout inside
-  // the chunk loops (eec_device.h, EEC_MFMA16); NP = 1 and the f8 stream keep the 32x32 shapes and the standard layout
+  // the chunk loops (eec_device.h); NP = 1 and the f8 stream keep the 32x32 shapes and the standard layout
   constexpr bool Q16 = kMfma16For<NP>;
   // Everything below is instantiated ONCE PER ROLE (the tag is a compile-time bool) and the role split is the
   // outermost branch: each role then carries only its own rings and accumulators through the stage loop
@@ -576,8 +503,6 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
       // SiLU + hi/lo split + ds_write of values [2q, 2q+1] of tile mt of a finished accumulator.  Standard layout: register quad
       // g = q >> 1 of lane (hh, r32) is hidden units 8 g + 4 hh .. + 3 of frame r32.  Quadrant layout (Q16): quad g = 2 ra + cb is
       // hidden units 16 ra + 8 hh + 4 u .. + 3 of frame 16 cb + (lane & 15) -- either way four consecutive halves of one H row.
-      // TR: the dropped activations of the chunk being activated, kept for the burst of tape stores at the end of the slot
-      [[maybe_unused]] f32x16 hq[TR == 1 && EEC_TR_BURST ? MT : 1];
       // TR = 2: the pre-activations of the chunk this wave multiplied last, in the accumulator's element order
       [[maybe_unused]] f32x16 preq[TR == 2 ? MT : 1];
       [[maybe_unused]] auto request_pre = [&](int hcol0) {
@@ -641,20 +566,12 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
           const int row = row0 + frame;
           const size_t idx = (size_t)row * F + hcol0 + hid;
           float m[4];
-#if EEC_TR_ABLATE & 2  // timing-only builds (tools/ffn_train_bench.hip): no mask / no tape stores
-          m[0] = m[1] = m[2] = m[3] = 1.0f;
-#else
           ds_act.mul4(idx, m);
-#endif
           const float h0 = __builtin_bit_cast(float, keep_hi) * m[0], h1 = __builtin_bit_cast(float, keep_lo) * m[1], h2v = s0 * m[2], h3 = s1 * m[3];
-#if EEC_TR_BURST
-          hq[mt][4 * g + 0] = h0, hq[mt][4 * g + 1] = h1, hq[mt][4 * g + 2] = h2v, hq[mt][4 * g + 3] = h3;
-#else
-          if (row < M && !(EEC_TR_ABLATE & 1)) {
+          if (row < M) {
             tape_store4(a.tr.pre + idx, acc[mt][0][2 * q - 2], acc[mt][0][2 * q - 1], u0, u1);
             tape_store4(a.tr.act + idx, h0, h1, h2v, h3);
           }
-#endif
           constexpr int SNPT = NP == 1 ? 1 : 3;
           const hl2_t sa = split2<SNPT>(h0, h1), sb = split2<SNPT>(h2v, h3);
           char* dst = hb + frame * kHLd + hid * 2;
@@ -664,11 +581,6 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
           if (NP == 3) *(h4*)(dst + kHPlane) = lo;
           return;
         }
-#ifdef EEC_ABLATE_SILU  // timing-only build: no activation work at all (H stays uninitialised)
-        asm volatile("" ::"v"(u0), "v"(u1));
-        (void)hb, (void)keep_hi, (void)keep_lo;
-        return;
-#endif
         constexpr int SNP = NP == 1 ? 1 : 3;
         const hl2_t sp = ACT == 0 ? split2<SNP>(silu_exp2(u0), silu_exp2(u1)) : split2<SNP>(fmaxf(u0, 0.f), fmaxf(u1, 0.f));
         if ((q & 1) == 0) {
@@ -691,31 +603,6 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
                 __builtin_amdgcn_perm(lb.y, lb.x, 0x07050301u);
           }
         }
-      };
-      // TR: the tape stores of a chunk (pre-activations from `acc`, dropped activations from hq) as ONE burst at the end of the slot.
-      // vmcnt retires in issue order, loads and stores alike: a store between two ring loads makes the wait for the second load a wait for
-      // the store's acknowledgement too (stores in the k-loop: 157 us per launch against 102 us without any; tools/ffn_train_bench.hip).
-      // Issued together right before the slot's barrier, they are acknowledged while the wave waits there.
-      [[maybe_unused]] auto tape_burst = [&](const f32x16 (&acc)[MT][1], int hcol0) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int frame = Q16 ? mt * 32 + 16 * (g & 1) + (lane & 15) : mt * 32 + (lane & 31);
-            const int hid = Q16 ? wl * 32 + 16 * (g >> 1) + 8 * hh + 4 * ((lane >> 4) & 1) : wl * 32 + 4 * hh + g * 8;
-#if EEC_TR_ABLATE & 8  // timing-only: the same bytes as whole 128-byte lines per instruction (8 frames x 128 B; values land in the wrong places)
-            const int c16 = lane & 15;
-            const int row = row0 + mt * 32 + 16 * (g & 1) + (c16 & 7) + 8 * (g >> 1);
-            const size_t idx = (size_t)row * F + hcol0 + wl * 32 + 16 * (c16 >> 3) + 8 * hh + 4 * ((lane >> 4) & 1);
-#else
-            const int row = row0 + frame;
-            const size_t idx = (size_t)row * F + hcol0 + hid;
-#endif
-            if (row < M && !(EEC_TR_ABLATE & 1)) {
-              tape_store4(a.tr.pre + idx, acc[mt][0][4 * g], acc[mt][0][4 * g + 1], acc[mt][0][4 * g + 2], acc[mt][0][4 * g + 3]);
-              tape_store4(a.tr.act + idx, hq[mt][4 * g], hq[mt][4 * g + 1], hq[mt][4 * g + 2], hq[mt][4 * g + 3]);
-            }
-          }
       };
       auto init_bias = [&](f32x16 (&acc)[MT][1], int ft) {
         if constexpr (TR == 2) {
@@ -754,9 +641,6 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
       // one slot: GEMM1 of chunk s into `cur` while the SiLU of chunk s-1 (held in `prev`) rides along
       // the SiLU side work of one chunk = 8 MT value pairs, spread over the KS k-steps of the next chunk's GEMM1
       constexpr int kSideEvery = KS / (8 * MT);  // 1 (D = 256) / 4 (D = 512)
-#if EEC_WARM_SLOTS > 0 && EEC_WARM_PROD
-      unsigned warm_p[4] = {0u, 0u, 0u, 0u};
-#endif
       auto slot = [&](int s, f32x16 (&cur)[MT][1], f32x16 (&prev)[MT][1]) {
         const int ft = (s < nchunk ? phys(s) : s) * 4 + wl;  // s >= nchunk: no GEMM1 (ft is out of range)
         const bool do_gemm = s < nchunk && ft < nft;
@@ -773,14 +657,14 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
               if (st % kSideEvery == 0) silu_pair(prev, hb_prev, st / kSideEvery, khi, klo, hcol_prev);
             };
             if constexpr (NP == 8)
-              gemm_ring_f8<D / 64, 1, true, kPF1, decltype(side), EEC_SIDE_VALU_NP8, kNW1, EEC_DROP1, MT, false, (EEC_X_HI8 ? G::kA8Hi : 0)>(
+              gemm_ring_f8<D / 64, 1, true, kPF1, decltype(side), EEC_SIDE_VALU_NP8, kNW1, MT>(
                   cur, a_lane, kALd, a8_lane, kA8Ld, w1f8_lane(W, ft), 0, r1, wg1, side);
             else
               gemm_ring<RNP, KS, 1, true, kPF1, decltype(side), (NP == 3 ? EEC_SIDE_VALU_NP3 : 7), MT, !Q16, !Q16>(cur, a_lane, kALd, kAPlane, w1_lane,
                                                                                                   0, r1, side);
           } else {
             if constexpr (NP == 8)
-              gemm_ring_f8<D / 64, 1, true, kPF1, NoSide, 0, kNW1, EEC_DROP1, MT, false, (EEC_X_HI8 ? G::kA8Hi : 0)>(cur, a_lane, kALd, a8_lane, kA8Ld,
+              gemm_ring_f8<D / 64, 1, true, kPF1, NoSide, 0, kNW1, MT>(cur, a_lane, kALd, a8_lane, kA8Ld,
                                                                                                                     w1f8_lane(W, ft), 0, r1, wg1);
             else
               gemm_ring<RNP, KS, 1, true, kPF1, NoSide, 0, MT, !Q16, !Q16>(cur, a_lane, kALd, kAPlane, w1_lane, 0, r1);
@@ -791,31 +675,6 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
 #pragma unroll
           for (int st = 0; st < 8 * MT; ++st) silu_pair(prev, hb_prev, st, khi, klo, hcol_prev);
         }
-        if constexpr (TR == 1 && EEC_TR_BURST) {
-          if (do_silu) tape_burst(prev, hcol_prev);
-        }
-#if EEC_WARM_SLOTS > 0 && EEC_WARM_PROD
-        // L2 warm-up for the stage boundary from the PRODUCERS, right before the barrier they wait at anyway (the consumers are the longer
-        // role of the split format: the touches' cold misses retire in order with their ring loads); one touch per slot
-        if constexpr (!TR) {
-          const int wk = s - (nslots - EEC_WARM_SLOTS);
-          if (wk >= 0 && wk < 4) {
-            const int lane_t = fresh_lane();
-            unsigned t = 0;
-            if constexpr (si + 1 < NS) {
-              const WPtrs Wn = wptrs(si + 1);
-              const size_t wbytes = NP == 8 ? (size_t)(F / 32) * (D / 64) * kF8Rec * 16 : (size_t)F * D * 2 * (NP == 3 ? 2 : 1);
-              const void* base = (wk & 2) ? (NP == 8 ? (const void*)Wn.w2f8 : (const void*)Wn.w2p) : (NP == 8 ? (const void*)Wn.w1f8 : (const void*)Wn.w1p);
-              t = touch_share(base, wbytes, wl_s, wk & 1, lane_t);
-            } else if constexpr (QNP != 0) {
-              if (wk == 0)
-                t = QNP == 8 ? touch_share(a.qkv.wf8, (size_t)(3 * D / 32) * (D / 64) * kF8Rec * 16, wl_s, 0, lane_t)
-                             : touch_share(a.qkv.wp, (size_t)3 * D * D * 2 * (QNP == 3 ? 2 : 1), wl_s, 0, lane_t);
-            }
-            warm_p[wk] = t;
-          }
-        }
-#endif
         TL_STAMP();  // producer: slot work done
         __syncthreads();
         TL_STAMP();  // producer: barrier passed
@@ -825,20 +684,14 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
         slot(s, accA, accB);
         if (s + 1 < nslots) slot(s + 1, accB, accA);
       }
-#if EEC_WARM_SLOTS > 0 && EEC_WARM_PROD
-      sink ^= warm_p[0] ^ warm_p[1] ^ warm_p[2] ^ warm_p[3];
-#endif
     } else {
 #pragma unroll
       for (int h = 0; h < NH; ++h) zero_acc(acc2c[h]);
-#if EEC_WARM_SLOTS > 0 && !EEC_WARM_PROD
+#if EEC_WARM_SLOTS > 0
       unsigned warm[4] = {0u, 0u, 0u, 0u};
 #endif
-#if EEC_ROLL_WARM > 0
-      unsigned roll_prev = 0u;
-#endif
       for (int s = 0; s < nslots; ++s) {
-#if EEC_WARM_SLOTS > 0 && !EEC_WARM_PROD
+#if EEC_WARM_SLOTS > 0
         if (s == nslots - EEC_WARM_SLOTS) {
           // L2 warm-up for the stage boundary, in the consumers' slack: this workgroup's 1/32 share of what the next
           // phase streams (the next stage's weights, or the in_proj weights of the tail).  Without it the boundary
@@ -858,27 +711,20 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
           }
         }
 #endif
-#if EEC_ROLL_WARM > 0
-        if constexpr (NP == 8 && D == 256) {
-          sink ^= roll_prev;  // the touch of the previous slot (long complete): keeps exactly one result register live
-          roll_prev = 0u;
-          if (wl_s == 0 && s + EEC_ROLL_WARM < nchunk) roll_prev = touch_chunk<D>(W.w1f8, W.w2f8, phys(s + EEC_ROLL_WARM), F, lane);
-        }
-#endif
         if (s >= 2) {
-          const int cl = s - 2, c = phys(cl);  // logical slot chunk (picks the H buffer) / physical hidden chunk
+          const int cl = s - 2, c = phys(cl);  // slot chunk (picks the H buffer) / hidden chunk
           const char* h_lane = lds_h + (cl & 1) * 2 * kHPlane + (lane & 31) * kHLd + hh * 16;
           const int ks2 = min(kFC / 16, ks2_total - c * (kFC / 16));
           const uint4* w2_lane = W.w2p + ((size_t)(NT2 * wl) * ks2_total + c * (kFC / 16)) * 128 + lane;
           if constexpr (NP == 8) {  // the launcher guarantees F % 128 == 0 for this stream
             const char* h8_lane = lds_h + (cl & 1) * 2 * kHPlane + kHPlane + (lane & 31) * kH8Ld + hh * 32;
             if constexpr (NH == 1) {
-              gemm_ring_f8<2, NTP, false, kPF2, NoSide, 0, kNW2, EEC_DROP2, MT>(acc2c[0], h_lane, kHLd, h8_lane, kH8Ld, w2f8_lane(W, c), w2f8_nt, r2, wg2);
+              gemm_ring_f8<2, NTP, false, kPF2, NoSide, 0, kNW2, MT>(acc2c[0], h_lane, kHLd, h8_lane, kH8Ld, w2f8_lane(W, c), w2f8_nt, r2, wg2);
             } else {
 #pragma unroll
               for (int h = 0; h < NH; ++h) {
                 const uint4* next = h + 1 < NH ? w2f8_lane(W, c, h + 1) : (cl + 1 < nchunk ? w2f8_lane(W, phys(cl + 1), 0) : nullptr);
-                gemm_ring_f8<2, NTP, false, kPF2, NoSide, 0, kNW2, EEC_DROP2, MT, true>(acc2c[h], h_lane, kHLd, h8_lane, kH8Ld, w2f8_lane(W, c, h), w2f8_nt, r2, wg2, NoSide(), next);
+                gemm_ring_f8<2, NTP, false, kPF2, NoSide, 0, kNW2, MT, true>(acc2c[h], h_lane, kHLd, h8_lane, kH8Ld, w2f8_lane(W, c, h), w2f8_nt, r2, wg2, NoSide(), next);
               }
             }
           } else if (ks2 == kFC / 16) {
@@ -892,11 +738,8 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
         __syncthreads();
         TL_STAMP();  // consumer: barrier passed
       }
-#if EEC_WARM_SLOTS > 0 && !EEC_WARM_PROD
+#if EEC_WARM_SLOTS > 0
       sink ^= warm[0] ^ warm[1] ^ warm[2] ^ warm[3];
-#endif
-#if EEC_ROLL_WARM > 0
-      sink ^= roll_prev;
 #endif
     }
     // ---- stage epilogue ----
@@ -1060,15 +903,10 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
   if ((sink ^ sink_front) == 0x9e3779b9u && M == -7) x[0] = 0.f;  // never true: the warm-up loads must not be optimised away
   TL_STAMP();  // last: epilogue done
   };
-#if defined(EEC_ONLY_ROLE)  // register-budget diagnostics: compile one role only (the kernel is then wrong, never run it)
-  (void)is_producer;
-  run(BoolTag<EEC_ONLY_ROLE != 0>{});
-#else
   if (is_producer)
     run(BoolTag<true>{});
   else
     run(BoolTag<false>{});
-#endif
 }
 
 #if defined(EEC_TIMELINE) && (!defined(EEC_FFN_D) || EEC_FFN_D == 256)
@@ -1165,9 +1003,6 @@ hipError_t launch_ffn_chain_d<EEC_FFN_D>(const ChainArgs& a_in, int np, int np_f
   EEC_CHAIN_CASE(3, 0, 0) EEC_CHAIN_CASE(3, 3, 0) EEC_CHAIN_CASE(3, 0, 3) EEC_CHAIN_CASE(3, 3, 3)
   EEC_CHAIN_CASE(1, 0, 0) EEC_CHAIN_CASE(1, 3, 0) EEC_CHAIN_CASE(1, 0, 3) EEC_CHAIN_CASE(1, 3, 3)
   EEC_CHAIN_CASE(1, 1, 0) EEC_CHAIN_CASE(1, 0, 1) EEC_CHAIN_CASE(1, 1, 1)
-#ifdef EEC_NP_EXPERIMENT  // diagnostic build: independent operand formats for the conv front and the in_proj tail
-  EEC_CHAIN_CASE(8, 1, 0) EEC_CHAIN_CASE(8, 0, 1) EEC_CHAIN_CASE(8, 1, 1) EEC_CHAIN_CASE(8, 3, 8) EEC_CHAIN_CASE(8, 0, 3) EEC_CHAIN_CASE(8, 8, 3) EEC_CHAIN_CASE(8, 3, 0) EEC_CHAIN_CASE(8, 3, 3)
-#endif
 #undef EEC_CHAIN_CASE
   return hipErrorInvalidValue;
 #endif

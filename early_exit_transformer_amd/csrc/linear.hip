@@ -85,7 +85,6 @@ __device__ __forceinline__ void planes_commit512(char* lds_act, const PlaneRegs<
       typedef _Float16 h8v __attribute__((ext_vector_type(8)));
       const h8v lg = __builtin_bit_cast(h8v, pr.l[it]) * (half_t)kF8ALoGain;  // gain-compensated (eec_device.h, kF8ALoGain)
       *(uint2*)(lds_act + G::kAPlane + rl * G::kA8Ld + lo8_pos(c16 * 8)) = top_bytes(__builtin_bit_cast(uint4, lg));
-      if (EEC_X_HI8) *(uint2*)(lds_act + G::kAPlane + rl * G::kA8Ld + G::kA8Hi + lo8_pos(c16 * 8)) = top_bytes(pr.h[it]);
     }
   }
 }
@@ -156,9 +155,6 @@ constexpr int kProjGluLds = 2 * Geo<D>::kAPlane + Geo<D>::kETile;  // 134144 / 1
 // so both products run as three fp16 MFMA products like every GEMM of the mode (what attn_kernel<.., 3, true> does in its own
 // launch, with K and its residual staged in LDS).  The second fragment set costs the registers of one key tile: blocks of 32 keys
 // instead of 64.
-#ifndef EEC_ATTN_LAZY
-#define EEC_ATTN_LAZY 0  // experiment (8 measured: 42.4 -> 42.2 us, not adopted): log2 units a block maximum may exceed the running maximum before the accumulators are rescaled (0: every block)
-#endif
 template <int D, int NP, bool X3 = false>
 __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& a, int row0) {
   using G = Geo<D>;
@@ -261,21 +257,14 @@ __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& 
 #pragma unroll
         for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, sc[j][mt][i]);
       tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      // Lazy running maximum: it moves (and the row sums and the O accumulators are rescaled) only when some row of the tile sees a score
-      // more than kLazyMax above it -- a wave-uniform test; otherwise the block's probabilities are taken against the standing maximum
-      // (<= 2^kLazyMax: exact in the fp16 pair / fp32 sums all the same) and the exp2, the 16 DT + 1 multiplies per row tile are skipped.
-      const bool bump = EEC_ATTN_LAZY == 0 || __builtin_amdgcn_ballot_w64(tmax > m_run[mt] + (float)EEC_ATTN_LAZY) != 0;
-      if (bump) {
-        const float m_up = fmaxf(m_run[mt], tmax);
-        const float alpha = __builtin_amdgcn_exp2f(m_run[mt] - m_up);
-        m_run[mt] = m_up;
-        l_run[mt] *= alpha;
+      const float m_new = fmaxf(m_run[mt], tmax);
+      const float alpha = __builtin_amdgcn_exp2f(m_run[mt] - m_new);
+      m_run[mt] = m_new;
+      l_run[mt] *= alpha;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
+      for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) o[mt][dt][i] *= alpha;
-      }
-      const float m_new = m_run[mt];
+        for (int i = 0; i < 16; ++i) o[mt][dt][i] *= alpha;
       float psum = 0.f;
       h8 pf[KB][2];
       [[maybe_unused]] h8 pfl[KB][2];
@@ -308,23 +297,14 @@ __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& 
     }
   };
   Blk fa, fb;
-#ifdef EEC_ATTN_LATE_FETCH  // A/B knob: the round-2 order (first fetch behind the length)
-  len = min(len_raw, a.Tq);
-  nkt = (len + 31) / 32;
-  if (nkt > 0) fetch(fa, 0, nkt - 1);
-#else
   fetch(fa, 0, a.Tp / 32 - 1);
   __builtin_amdgcn_sched_barrier(0);
   len = min(len_raw, a.Tq);
   nkt = (len + 31) / 32;
-#endif
   // static priority for the younger half of the workgroup: waves 4-7 lose every issue arbitration against their SIMD partners
   // (wave 7 reached its first key block 4.4 k cycles after wave 0 and stayed behind: the tile's barrier waited 6.8 k cycles for it;
   // profiles/r03_proj_glu_timeline.txt).  One setprio, no per-phase flips; A/B 37.7 -> 36.6 us per launch.
-#ifndef EEC_ATTN_PRIO
-#define EEC_ATTN_PRIO 1
-#endif
-  if (EEC_ATTN_PRIO > 0 && w >= 4) __builtin_amdgcn_s_setprio(EEC_ATTN_PRIO);
+  if (w >= 4) __builtin_amdgcn_s_setprio(1);
   EEC_TL_STAMP(glu, 11);
   for (int kt0 = 0; kt0 < nkt; kt0 += 2 * KB) {
     if (kt0 + KB < nkt) fetch(fb, kt0 + KB, nkt - 1);
@@ -336,7 +316,7 @@ __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& 
     }
     EEC_TL_STAMP(glu, kt0 == 0 ? 13 : 15);
   }
-  if (EEC_ATTN_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
   // normalise and write the planes.  No valid key at all (length 0): the installed torch returns zeros ("safe softmax").
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
@@ -359,10 +339,6 @@ __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& 
           lg.xy = lo8_gain(s0.lo), lg.zw = lo8_gain(s1.lo);
           const uint2 lb = __builtin_bit_cast(uint2, lg);
           *(unsigned*)(smem + G::kAPlane + rl * G::kA8Ld + lo8_pos(col)) = __builtin_amdgcn_perm(lb.y, lb.x, 0x07050301u);
-          if (EEC_X_HI8) {
-            const uint2 hb = __builtin_bit_cast(uint2, hi);
-            *(unsigned*)(smem + G::kAPlane + rl * G::kA8Ld + G::kA8Hi + lo8_pos(col)) = __builtin_amdgcn_perm(hb.y, hb.x, 0x07050301u);
-          }
         }
       }
   }
@@ -491,7 +467,7 @@ __global__ __launch_bounds__(kLinThreads, 2) void proj_glu_kernel(ProjResArgs a,
             const float gate = ag[mt][j][4 * g + i];
             o[i] = to_half_sat(av[mt][j][4 * g + i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-kLog2e * gate)));
           }
-          store_maybe_nt<EEC_NT_G != 0>((h4*)(dst + 8 * g), o);
+          *(h4*)(dst + 8 * g) = o;
         }
       }
     }
@@ -569,7 +545,10 @@ __device__ __forceinline__ void head_body(char* smem, const HeadArgs& a) {
     const float mx = wave_max(fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
     const float sm = wave_sum(has ? __expf(v.x - mx) + __expf(v.y - mx) + __expf(v.z - mx) + __expf(v.w - mx) : 0.f);
     const float lse = mx + __logf(sm);
-    if (has && row < a.M) store_maybe_nt<EEC_NT_HEAD != 0>((f32x4*)(a.out + (size_t)row * a.V + c0), (f32x4){v.x - lse, v.y - lse, v.z - lse, v.w - lse});
+    if (has && row < a.M) {
+      f32x4* const out = (f32x4*)(a.out + (size_t)row * a.V + c0);
+      *out = (f32x4){v.x - lse, v.y - lse, v.z - lse, v.w - lse};
+    }
   }
 }
 

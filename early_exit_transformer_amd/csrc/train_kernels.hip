@@ -153,24 +153,10 @@ __device__ __forceinline__ void store_tile(bf16* __restrict__ hi, bf16* __restri
     if (NP == 3) *(bf16x4*)(lo + off) = l;
   }
 }
-// MFMA operand fragment (8 consecutive k of row rbase + lane % 32, k half lane / 32) of k-step ks from a tile image
-template <int R, bool KC>
-__device__ __forceinline__ bf16x8 read_frag(const bf16* __restrict__ t, int rbase, int ks, int lane) {
-  if (KC) return *(const bf16x8*)(t + (rbase + (lane & 31)) * kLdk + ks * 16 + (lane >> 5) * 8);
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int i = lane & 15, gi = lane >> 4;
-  const bf16* a = t + (ks * 16 + 8 * (gi >> 1) + (i >> 2)) * TileGeo<R>::kLdt + rbase + 16 * (gi & 1) + 4 * (i & 3);
-  const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(a + 4 * TileGeo<R>::kLdt));
-  return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
-// The same tile images read as operands of v_mfma_f32_16x16x32_bf16 (EECT_MFMA16; csrc/eec_device.h has the inference path's form of
-// this): the chip holds a higher clock on that shape under load (profiles/r04_micro_mfma_shape_clock.txt; timing-only swap in this
+// The tile images are read as operands of v_mfma_f32_16x16x32_bf16 (csrc/eec_device.h has the inference path's form of this): the chip
+// holds a higher clock on that shape under load than on 32x32x16 (profiles/r04_micro_mfma_shape_clock.txt; timing-only swap in this
 // kernel: training step 25.5 -> 24.1 ms).  Lane l = 16 g + c holds row rbase + 16 rb + c, k = 8 g .. 8 g + 7 of the 32-deep tile.
-#ifndef EECT_MFMA16
-#define EECT_MFMA16 1
-#endif
 template <int R, bool KC>
 __device__ __forceinline__ bf16x8 read_frag16(const bf16* __restrict__ t, int rbase, int rb, int lane) {
   const int c = lane & 15, g = lane >> 4;
@@ -227,14 +213,6 @@ struct FastTag {
 // EPI_RELU_DROP: C = v, C2 = drop(relu(v));  EPI_DRELU: C = v * dropmask * (aux > 0)   (the ReLU feed-forward of the AED decoder)
 enum { EPI_NONE = 0, EPI_SILU = 1, EPI_DSILU = 2, EPI_RELU = 3, EPI_RESID = 4, EPI_RELU_DROP = 5, EPI_DRELU = 6 };
 
-// STAGES: register prefetch depth of the k-loop.  2: the loads of tile kt + 2 are in flight across two MFMA phases (long
-// contractions); 1: 64 registers fewer, so that three workgroups share a CU (short contractions, many tiles: +25-50 %)
-#ifndef EECT_PIPE_SCHED
-#define EECT_PIPE_SCHED 7  // STAGES == 3 only: VALU instructions placed behind every MFMA of the interval (0: the compiler's order)
-#endif
-#ifndef EECT_EPI_DIRECT
-#define EECT_EPI_DIRECT 0  // 1: 4-byte stores straight from the accumulators (measured: epilogue 23.5 k cycles against 13.6 k through the slabs)
-#endif
 #ifdef EECT_TL
 // Diagnostic build only (tools/train_gemm_timeline.py): s_memtime stamps of thread 0 of the first 64 workgroups of a launch.
 __device__ unsigned long long eect_tl_buf[64 * 16];
@@ -259,21 +237,21 @@ extern "C" int eect_debug_tl(unsigned long long* out) {
 // training plan uses them with.
 constexpr int kEpiPlain = -2, kEpiAny = -1;
 // LDS of one workgroup: the operand plane sets of the k-loop, reused as a [32][BN + 4] fp32 slab of the output tile in the epilogue
-template <int TM, int TN, int WGM, int WGN, int NP, int STAGES>
+template <int TM, int TN, int WGM, int WGN, int NP>
 constexpr int gemm_lds_bytes() {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
-  constexpr int planes = (STAGES == 3 ? 2 : 1) * (NP == 3 ? 2 : 1) * (TileGeo<BM>::kElems + TileGeo<BN>::kElems) * 2;
+  constexpr int planes = (NP == 3 ? 2 : 1) * (TileGeo<BM>::kElems + TileGeo<BN>::kElems) * 2;
   constexpr int slab = 32 * (BN + 4) * 4, red = 4 * 256 * 4;  // red: the row-sum reduction's [256 / (BM / 4)][BM] floats
   return planes > slab ? (planes > red ? planes : red) : (slab > red ? slab : red);
 }
-template <int TM, int TN, int WGM, int WGN, int NP, bool AKC, bool BKC, int STAGES, int EPI_T>
-__global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs g) {
+// The k-loop keeps one k-tile in registers (64 registers fewer than a second stage, so that three workgroups share a CU: short
+// contractions, many tiles, +25-50 %).
+template <int TM, int TN, int WGM, int WGN, int NP, bool AKC, bool BKC, int EPI_T>
+__global__ __launch_bounds__(256, 3) void gemm_kernel(GemmArgs g) {
   static_assert(WGM * WGN == 4, "4 waves");
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
   // one LDS block: the operand planes during the k-loop, a [32][BN + 4] fp32 slab of the output tile in the epilogue
   constexpr int EA = TileGeo<BM>::kElems, EB = TileGeo<BN>::kElems, kSlabLd = BN + 4;
-  constexpr int kPlaneBytes = (NP == 3 ? 2 : 1) * (EA + EB) * 2;
-  // STAGES == 3: two plane sets, one barrier per k-tile (below); the block is dynamic LDS (gemm_lds_bytes: 80 KB at 128 x 128 x 3)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* a_hi = (bf16*)smem;
   bf16* b_hi = a_hi + EA;
@@ -307,9 +285,8 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-  // two register stages: the global loads of tile kt + 2 are issued as soon as stage (kt & 1) has been written to LDS, so
-  // they have the MFMA phases of two k-tiles to land (one phase does not cover the L2 / HBM latency)
-  float ra0[BM / 32][4], rb0[BN / 32][4], ra1[BM / 32][4], rb1[BN / 32][4];
+  // the global loads of tile kt + 1 are issued as soon as tile kt has been written to LDS
+  float ra0[BM / 32][4], rb0[BN / 32][4];
   const int K = g.ktot > 0 ? min(g.K, g.ktot - z0 * g.K) : g.K;
   const int nk = (K + kBK - 1) / kBK;
   TileLoader<BM, AKC> la;
@@ -337,9 +314,8 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs
   // (its BM / 32 groups of four all belong to the same four rows: 256 % (BM / 4) == 0)
   float rs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   const bool do_rs = !AKC && g.rowsum != nullptr && bx == 0;
-  constexpr int kBufElems = kPlaneBytes / 2;  // bf16 elements between the two plane sets
-  // registers -> (split) -> plane set `buf`
-  auto split_store = [&](float (&ra)[BM / 32][4], float (&rb)[BN / 32][4], int buf) __attribute__((always_inline)) {
+  // registers -> (split) -> planes
+  auto split_store = [&](float (&ra)[BM / 32][4], float (&rb)[BN / 32][4]) __attribute__((always_inline)) {
     if constexpr (!AKC) {
       if (do_rs) {
 #pragma unroll
@@ -348,183 +324,83 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs
           for (int j = 0; j < 4; ++j) rs[j] += ra[it][j];
       }
     }
-    store_tile<BM, NP, AKC>(a_hi + buf * kBufElems, a_lo + buf * kBufElems, ra, tid);
-    store_tile<BN, NP, BKC>(b_hi + buf * kBufElems, b_lo + buf * kBufElems, rb, tid);
+    store_tile<BM, NP, AKC>(a_hi, a_lo, ra, tid);
+    store_tile<BN, NP, BKC>(b_hi, b_lo, rb, tid);
   };
-  // the 32-deep k-tile in plane set `buf`: fragments from LDS, 4 x TM x TN x (1 or 3) MFMAs
-#ifndef EECT_MFMA16_KC_ONLY
-#define EECT_MFMA16_KC_ONLY 0  // 1: the 16x16x32 form only where both operands are k-contiguous (no spills there)
-#endif
-  constexpr bool kM16 = EECT_MFMA16 && EECT_EPI_DIRECT != 2 && (!EECT_MFMA16_KC_ONLY || (AKC && BKC));
-  auto mfma_tile = [&](int buf) __attribute__((always_inline)) {
-#if EECT_MFMA16 && EECT_EPI_DIRECT != 2
-    if constexpr (kM16)
-    // 16x16x32 form: the 32-deep tile is ONE k-step.  Row block ra of A (fragments of every row tile, hi / lo) against row block cb of
-    // B, in the order (0,0) (0,1) (1,1) (1,0) so that a B fragment set is read three times, not four; the same eight fragment
-    // registers as a 16-deep step of the 32x32x16 form.
-    {
-      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-      auto load_a = [&](int ra) __attribute__((always_inline)) {
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt) {
-          ah[mt] = read_frag16<BM, AKC>(a_hi + buf * kBufElems, (wm * TM + mt) * 32, ra, lane);
-          if (NP == 3) al[mt] = read_frag16<BM, AKC>(a_lo + buf * kBufElems, (wm * TM + mt) * 32, ra, lane);
-        }
-      };
-      auto load_b = [&](int cb) __attribute__((always_inline)) {
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-          bh[nt] = read_frag16<BN, BKC>(b_hi + buf * kBufElems, (wn * TN + nt) * 32, cb, lane);
-          if (NP == 3) bl[nt] = read_frag16<BN, BKC>(b_lo + buf * kBufElems, (wn * TN + nt) * 32, cb, lane);
-        }
-      };
-      auto macs = [&](int ra, int cb) __attribute__((always_inline)) {
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < TN; ++nt) {
-            if (NP == 3) {
-              quad_mac16(acc[mt][nt], ra, cb, al[mt], bh[nt]);
-              quad_mac16(acc[mt][nt], ra, cb, ah[mt], bl[nt]);
-            }
-            quad_mac16(acc[mt][nt], ra, cb, ah[mt], bh[nt]);
-          }
-      };
-      // (fenced: left alone, hipcc hoists every fragment read of the tile in front of the first MFMA -- 20 fragments live at once)
-      load_a(0);
-      load_b(0);
-      __builtin_amdgcn_sched_barrier(0);
-      macs(0, 0);
-      load_b(1);
-      __builtin_amdgcn_sched_barrier(0);
-      macs(0, 1);
-      load_a(1);
-      __builtin_amdgcn_sched_barrier(0);
-      macs(1, 1);
-      load_b(0);
-      __builtin_amdgcn_sched_barrier(0);
-      macs(1, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      return;
-    }
-#endif
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+  // the 32-deep k-tile in LDS: fragments from LDS, 4 x TM x TN x (1 or 3) MFMAs of the 16x16x32 form.  The tile is ONE k-step: row
+  // block ra of A (fragments of every row tile, hi / lo) against row block cb of B, in the order (0,0) (0,1) (1,1) (1,0) so that a B
+  // fragment set is read three times, not four.
+  auto mfma_tile = [&]() __attribute__((always_inline)) {
+    bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+    auto load_a = [&](int ra) __attribute__((always_inline)) {
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt) {
-        ah[mt] = read_frag<BM, AKC>(a_hi + buf * kBufElems, (wm * TM + mt) * 32, ks, lane);
-        if (NP == 3) al[mt] = read_frag<BM, AKC>(a_lo + buf * kBufElems, (wm * TM + mt) * 32, ks, lane);
+        ah[mt] = read_frag16<BM, AKC>(a_hi, (wm * TM + mt) * 32, ra, lane);
+        if (NP == 3) al[mt] = read_frag16<BM, AKC>(a_lo, (wm * TM + mt) * 32, ra, lane);
       }
+    };
+    auto load_b = [&](int cb) __attribute__((always_inline)) {
 #pragma unroll
       for (int nt = 0; nt < TN; ++nt) {
-        bh[nt] = read_frag<BN, BKC>(b_hi + buf * kBufElems, (wn * TN + nt) * 32, ks, lane);
-        if (NP == 3) bl[nt] = read_frag<BN, BKC>(b_lo + buf * kBufElems, (wn * TN + nt) * 32, ks, lane);
+        bh[nt] = read_frag16<BN, BKC>(b_hi, (wn * TN + nt) * 32, cb, lane);
+        if (NP == 3) bl[nt] = read_frag16<BN, BKC>(b_lo, (wn * TN + nt) * 32, cb, lane);
       }
+    };
+    auto macs = [&](int ra, int cb) __attribute__((always_inline)) {
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
-#if EECT_EPI_DIRECT == 2
           if (NP == 3) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[nt], al[mt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[nt], ah[mt], acc[mt][nt], 0, 0, 0);
+            quad_mac16(acc[mt][nt], ra, cb, al[mt], bh[nt]);
+            quad_mac16(acc[mt][nt], ra, cb, ah[mt], bl[nt]);
           }
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[nt], ah[mt], acc[mt][nt], 0, 0, 0);
-#else
-          if (NP == 3) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-          }
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-#endif
+          quad_mac16(acc[mt][nt], ra, cb, ah[mt], bh[nt]);
         }
-    }
+    };
+    // (fenced: left alone, hipcc hoists every fragment read of the tile in front of the first MFMA -- 20 fragments live at once)
+    load_a(0);
+    load_b(0);
+    __builtin_amdgcn_sched_barrier(0);
+    macs(0, 0);
+    load_b(1);
+    __builtin_amdgcn_sched_barrier(0);
+    macs(0, 1);
+    load_a(1);
+    __builtin_amdgcn_sched_barrier(0);
+    macs(1, 1);
+    load_b(0);
+    __builtin_amdgcn_sched_barrier(0);
+    macs(1, 0);
+    __builtin_amdgcn_sched_barrier(0);
   };
   auto k_tile = [&](int kt, float (&ra)[BM / 32][4], float (&rb)[BN / 32][4], auto fast_tag) __attribute__((always_inline)) {
-    split_store(ra, rb, 0);
+    split_store(ra, rb);
     __syncthreads();
 #ifdef EECT_TL
     if (kt < 4) EECT_STAMP(4 + 2 * kt);
 #endif
-    if (kt + STAGES < nk) load_ab(ra, rb, k_of(kt + STAGES), fast_tag);
-    mfma_tile(0);
+    if (kt + 1 < nk) load_ab(ra, rb, k_of(kt + 1), fast_tag);
+    mfma_tile();
 #ifdef EECT_TL
     if (kt < 4) EECT_STAMP(5 + 2 * kt);
 #endif
     __syncthreads();
   };
-  // STAGES == 3, the pipelined form: two plane sets in LDS and two register sets.  While the MFMAs run on plane set kt % 2 the
-  // same wave splits tile kt + 1 (already in registers) into the other set, and tile kt + 2's loads are in flight: ONE barrier per
-  // k-tile, and the split's VALU work sits in the shadow of the MFMAs of the same wave instead of in a phase of its own.
-  // steady_tag: both tiles ahead exist -- no conditions, so that the interval is ONE basic block (the scheduling hints below only
-  // reorder inside one)
-  auto pipe_step = [&](int kt, int buf, float (&r_next_a)[BM / 32][4], float (&r_next_b)[BN / 32][4], float (&r_load_a)[BM / 32][4],
-                       float (&r_load_b)[BN / 32][4], auto fast_tag, auto steady_tag) __attribute__((always_inline)) {
-    constexpr bool steady = decltype(steady_tag)::value;
-    if (steady || kt + 2 < nk) load_ab(r_load_a, r_load_b, k_of(kt + 2), fast_tag);  // into the set whose tile went to LDS a step ago
-    mfma_tile(buf);
-    if (steady || kt + 1 < nk) split_store(r_next_a, r_next_b, buf ^ 1);
-#if EECT_PIPE_SCHED
-    // the interval as one interleaved stream: fragment reads of a k-step, then its MFMAs with the split's VALU work and LDS stores
-    // in their shadows (hipcc otherwise emits the MFMAs and the split as two blocks)
-    {
-      constexpr int kMfma = 2 * TM * TN * (NP == 3 ? 3 : 1), kReads = (NP == 3 ? 2 : 1) * (TM + TN) * ((AKC ? 1 : 2) + (BKC ? 1 : 2)) / 2;
-      constexpr int kValuPer = EECT_PIPE_SCHED;
-      __builtin_amdgcn_sched_group_barrier(0x100, kReads, 0);
-#pragma unroll
-      for (int i = 0; i < kMfma; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, kValuPer, 0);
-        if (i & 1) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-        if (i == kMfma / 4) __builtin_amdgcn_sched_group_barrier(0x100, kReads, 0);
-      }
-    }
-#endif
-#ifdef EECT_TL
-    if (kt < 4) EECT_STAMP(4 + 2 * kt), EECT_STAMP(5 + 2 * kt);
-#endif
-    __syncthreads();  // set buf ^ 1 complete; everybody done with set buf
-  };
   auto k_loop = [&](auto fast_tag) __attribute__((always_inline)) {
     load_ab(ra0, rb0, k_of(0), fast_tag);
-    if constexpr (STAGES == 1) {
-      for (int kt = 0; kt < nk; ++kt) k_tile(kt, ra0, rb0, fast_tag);
-    } else if constexpr (STAGES == 3) {
-      if (nk > 1) load_ab(ra1, rb1, k_of(1), fast_tag);
-      split_store(ra0, rb0, 0);
-      __syncthreads();
-      int kt = 0;
-      for (; kt + 3 < nk; kt += 2) {
-        pipe_step(kt, 0, ra1, rb1, ra0, rb0, fast_tag, FastTag<true>{});
-        pipe_step(kt + 1, 1, ra0, rb0, ra1, rb1, fast_tag, FastTag<true>{});
-      }
-      for (; kt < nk; kt += 2) {
-        pipe_step(kt, 0, ra1, rb1, ra0, rb0, fast_tag, FastTag<false>{});
-        if (kt + 1 < nk) pipe_step(kt + 1, 1, ra0, rb0, ra1, rb1, fast_tag, FastTag<false>{});
-      }
-    } else {
-      if (nk > 1) load_ab(ra1, rb1, k_of(1), fast_tag);
-      for (int kt = 0; kt < nk; kt += 2) {
-        k_tile(kt, ra0, rb0, fast_tag);
-        if (kt + 1 < nk) k_tile(kt + 1, ra1, rb1, fast_tag);
-      }
-    }
+    for (int kt = 0; kt < nk; ++kt) k_tile(kt, ra0, rb0, fast_tag);
   };
   EECT_STAMP(1);
   if (fast) k_loop(FastTag<true>{});
   else k_loop(FastTag<false>{});
-#if EECT_MFMA16 && EECT_EPI_DIRECT != 2
   // the k-loop kept the accumulators in the quadrant layout: back to the layout of the epilogues, once.  (The swaps are inline asm:
   // the MFMA-result -> VALU-read hazard in front of them is padded by hand -- 19 wait states cover a 16-pass MFMA.)
-  if constexpr (kM16) {
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" ::: "memory");
+  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc_q_to_std(acc[i][j]);
-  }
-#endif
+    for (int j = 0; j < TN; ++j) acc_q_to_std(acc[i][j]);
   EECT_STAMP(2);
   if constexpr (!AKC) {
     if (do_rs) {  // uniform over the workgroup.  The k-loop ended with a barrier: LDS is free.
@@ -621,71 +497,6 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs
       }
     }
   };
-#if EECT_EPI_DIRECT == 2
-  // operands swapped in the k-loop: the accumulators hold the TRANSPOSED 32 x 32 tiles, i.e. lane l has row m = l % 32 and, per
-  // register quad q, the four consecutive columns 8 q + 4 (l / 32) ..: 16-byte stores straight from the registers, no LDS, no barrier
-  {
-    const bool want_pre = cvec && (g.accumulate || epi == EPI_DSILU || epi == EPI_RESID || epi == EPI_DRELU);
-    const float* __restrict__ pre_src = g.accumulate ? (const float*)C : aux;
-#pragma unroll
-    for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < TN; ++nt) {
-        const int m = m0 + (wm * TM + mt) * 32 + (lane & 31), nb = n0 + (wn * TN + nt) * 32 + 4 * (lane >> 5);
-        f32x4 pre4[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          pre4[q] = (want_pre && m < g.M && nb + 8 * q < g.N) ? *(const f32x4*)(pre_src + (long)m * g.c_m + nb + 8 * q) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = nb + 8 * q;
-          if (m < g.M && n < g.N)
-            finish4(m, n, (f32x4){acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]}, pre4[q]);
-        }
-      }
-  }
-#elif EECT_EPI_DIRECT
-  // straight from the accumulators: for a fixed register index the 64 lanes of a wave hold two rows x 32 consecutive columns,
-  // i.e. every store (and every load of old C / aux) instruction covers two full 128-byte segments -- no LDS round trip and no
-  // barrier (the slab form below spent 13.6 k of a K = 256 workgroup's 47 k cycles on its 8 barriers)
-  {
-    const bool want_pre = g.accumulate || epi == EPI_DSILU || epi == EPI_RESID || epi == EPI_DRELU;
-    const float* __restrict__ pre_src = g.accumulate ? (const float*)C : aux;
-#pragma unroll
-    for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < TN; ++nt) {
-        const int n = n0 + (wn * TN + nt) * 32 + (lane & 31), mb = m0 + (wm * TM + mt) * 32;
-        const bool nok = n < g.N;
-        const float bv = (g.bias && nok) ? g.bias[n] : 0.0f;
-        float pre[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int m = mb + acc_row(i, lane);
-          pre[i] = (want_pre && nok && m < g.M) ? pre_src[(long)m * g.c_m + n] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int m = mb + acc_row(i, lane);
-          if (nok && m < g.M) {
-            const long ci = (long)m * g.c_m + n;
-            float t = g.alpha * acc[mt][nt][i] + bv;
-            if (g.accumulate) t += pre[i];
-            if (epi == EPI_DSILU) {
-              const float x = pre[i], sg = sigmoidf_(x);
-              t *= ds.mul((uint64_t)ci) * sg * (1.0f + x * (1.0f - sg));
-            }
-            if (epi == EPI_RELU) t = fmaxf(t, 0.0f);
-            if (epi == EPI_DRELU) t *= pre[i] > 0.0f ? ds.mul((uint64_t)ci) : 0.0f;
-            if (epi == EPI_RESID) t = pre[i] + g.res_scale * t * ds.mul((uint64_t)ci);
-            C[ci] = t;
-            if (epi == EPI_SILU) C2[ci] = t * sigmoidf_(t) * ds.mul((uint64_t)ci);
-            if (epi == EPI_RELU_DROP) C2[ci] = fmaxf(t, 0.0f) * ds.mul((uint64_t)ci);
-          }
-        }
-      }
-  }
-#else
   float* slab = (float*)smem;
   // what a slab's elements need from memory -- old C (accumulate) or aux (EPI_DSILU), never both -- is requested one slab
   // ahead: the loads of slab s + 1 are in flight while slab s goes through LDS and out
@@ -721,7 +532,6 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_kernel(GemmArgs
     }
     __syncthreads();
   });
-#endif
   EECT_STAMP(3);
 }
 
@@ -730,27 +540,13 @@ static hipError_t launch_gemm_t(const GemmArgs& g, int np, hipStream_t st) {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
   const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nz);
   const bool akc = g.a_k == 1, bkc = g.b_k == 1;
-#ifndef EECT_PIPE_MIN_K
-#define EECT_PIPE_MIN_K 0  // > 0: also build the pipelined loop and use it for contractions at least this long (EEC_TRAIN_PIPE_MIN_K overrides)
-#endif
-#ifndef EECT_STAGES
-#define EECT_STAGES 1  // measured on one box, default model: 1 -> 38.9 ms per step, 2 -> 40.6 ms, 2 for >= 32 k-tiles only -> 39.8 ms
-#endif
   const bool fancy = g.epi != EPI_NONE && g.epi != EPI_RELU;
   // bodies of their own: (epilogue, tile, layout) as the encoder's training plan launches them
   constexpr bool big = TM == 2 && TN == 2 && WGM == 2 && WGN == 2, wide = TM == 2 && TN == 1 && WGM == 2 && WGN == 2;
-  // the pipelined loop (STAGES 3: one barrier per k-tile, the split in the MFMAs' shadow, two workgroups per CU) is faster for long
-  // contractions ALONE (same-box A/B, bf16x3: K = 2048 87.6 -> 74.4 us, one workgroup per CU 330 -> 220 us; K = 256 75 -> 81 us) but
-  // buys nothing in the step, where the long GEMMs (weight gradients, side stream) share the chip with the dX chain: 25.2 vs 25.3 ms.
-  // Built only with -DEECT_PIPE_MIN_K=<K>.
-#if EECT_PIPE_MIN_K > 0
-  static const int pipe_min_k = [] { const char* e = getenv("EEC_TRAIN_PIPE_MIN_K"); return e ? atoi(e) : EECT_PIPE_MIN_K; }();  // tuning knob
-  const bool pipe = EECT_STAGES == 1 && g.K >= pipe_min_k;
-#endif
-#define EECT_GEMM_S(NP, AK, BK, E, ST)                                                                          \
+#define EECT_GEMM_E(NP, AK, BK, E)                                                                              \
   do {                                                                                                          \
-    auto kfn = gemm_kernel<TM, TN, WGM, WGN, NP, AK, BK, ST, E>;                                                \
-    constexpr int lds = gemm_lds_bytes<TM, TN, WGM, WGN, NP, ST>();                                             \
+    auto kfn = gemm_kernel<TM, TN, WGM, WGN, NP, AK, BK, E>;                                                    \
+    constexpr int lds = gemm_lds_bytes<TM, TN, WGM, WGN, NP>();                                                 \
     if (lds > 65536) {                                                                                          \
       static bool raised = false; /* per instantiation */                                                       \
       if (!raised) {                                                                                            \
@@ -760,15 +556,6 @@ static hipError_t launch_gemm_t(const GemmArgs& g, int np, hipStream_t st) {
     }                                                                                                           \
     hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, g);                                                       \
   } while (0)
-#if EECT_PIPE_MIN_K > 0
-#define EECT_GEMM_E(NP, AK, BK, E)                     \
-  do {                                                 \
-    if (pipe) EECT_GEMM_S(NP, AK, BK, E, 3);           \
-    else EECT_GEMM_S(NP, AK, BK, E, EECT_STAGES);      \
-  } while (0)
-#else
-#define EECT_GEMM_E(NP, AK, BK, E) EECT_GEMM_S(NP, AK, BK, E, EECT_STAGES)
-#endif
   if constexpr (big || wide) {
     if (akc && bkc && g.epi == EPI_RESID) {
       if (np == 1) EECT_GEMM_E(1, true, true, EPI_RESID);
@@ -806,7 +593,6 @@ static hipError_t launch_gemm_t(const GemmArgs& g, int np, hipStream_t st) {
   }
 #undef EECT_GEMM
 #undef EECT_GEMM_E
-#undef EECT_GEMM_S
   return hipGetLastError();
 }
 hipError_t launch_gemm(const GemmArgs& g_in, int np, hipStream_t st) {

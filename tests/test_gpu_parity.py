@@ -52,7 +52,7 @@ def test_native_library_is_loaded():
 
 def test_mfma16_gemm_forms_equal_the_32x32_forms():
     """Device check of the k-loops of the default (split) format: the 16x16x32 forms (re-addressed fragments of the same
-    packing, quadrant accumulators restored by lane swaps; csrc/eec_device.h, EEC_MFMA16) against the 32x32x16 forms on the
+    packing, quadrant accumulators restored by lane swaps; csrc/eec_device.h) against the 32x32x16 forms on the
     same LDS planes, packed weights and rings -- both orientations, 1 / 2 row tiles, 1 / 2 column tiles, ring refills.  Built
     by `make` (csrc/build/mfma16_gemm_check); exits non-zero if any accumulator element differs by more than 1e-4."""
     import os

@@ -1,9 +1,9 @@
-// Stand-alone timing of the training step's fused feed-forward forward (csrc/ffn.hip, TR variants) with its ablation builds:
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I early_exit_transformer_amd/csrc -DEEC_FFN_TRAIN [-DEEC_TR_ABLATE=n] [-DEEC_SIDE_VALU_NP3=n]
+// Stand-alone timing of the training step's fused feed-forward forward (csrc/ffn.hip, TR variants):
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I early_exit_transformer_amd/csrc -DEEC_FFN_TRAIN [-DEEC_SIDE_VALU_NP3=n]
 //         tools/ffn_train_bench.hip early_exit_transformer_amd/csrc/pack.hip -o tools/ffn_train_bench
 // (-DEEC_FFN_TRAIN_BWD instead of -DEEC_FFN_TRAIN: the backward variant)
 // M = 16384 rows, d_model 256, F = 2048, p = 0.1 and p = 0; six weight sets in rotation (as consecutive modules do), HIP events.
-// Numerics are the training tests' business (tests/test_gpu_train.py); this prints one checksum so that ablations are visibly different.
+// Numerics are the training tests' business (tests/test_gpu_train.py); this prints one checksum so that builds are visibly different.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -95,7 +95,7 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(yo.data(), y + (size_t)(M / 2) * D, 4096, hipMemcpyDeviceToHost));
     double cs = 0;
     for (float v : yo) cs += v;
-    printf("M=%d np=%d p=%.1f ablate=%d side_valu=%d: %.2f us per launch (best of 4 x %d; mean %.2f)  checksum %.6f\n", M, np, p, EEC_TR_ABLATE, EEC_SIDE_VALU_NP3,
+    printf("M=%d np=%d p=%.1f side_valu=%d: %.2f us per launch (best of 4 x %d; mean %.2f)  checksum %.6f\n", M, np, p, EEC_SIDE_VALU_NP3,
            best * 1e3, N, total / 4 * 1e3, cs);
   }
   return 0;

@@ -1,4 +1,4 @@
-// Device check of the 16x16x32 GEMM forms (eec_device.h, EEC_MFMA16) against the 32x32x16 forms on the same LDS planes, packed
+// Device check of the 16x16x32 GEMM forms (eec_device.h) against the 32x32x16 forms on the same LDS planes, packed
 // weights and rings: both orientations, one / two row tiles, one / two column tiles, ring refills, and the layout conversions.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I early_exit_transformer_amd/csrc tools/mfma16_gemm_check.hip -o tools/mfma16_gemm_check
 #include <stdio.h>
