@@ -1,6 +1,9 @@
 // Training step of the Early_conformer path behind the C ABI (include/eec.h, eec_trainer_*): the forward in train mode
 // (batch-statistics BatchNorm, dropout at the reference's sites) that records what the backward needs, and the backward
 // that produces the gradient of every parameter -- what `enc_out = model(...)` / `loss.backward()` do in train.py:53-68.
+// One set of routines -- stem, layer loop, exit head, each forward and backward -- serves both the whole-model step
+// (eec_train_forward / _backward) and the stateless block entries the other model types use (eec_train_group_*, _stem_*,
+// _head_*); every entry sizes its workspace by one dry run of the same carve (plan).
 // Host code only; the kernels are in train_kernels.hip (+ the log-softmax backward of ctc.hip, the length kernel of pack.hip).
 //
 // Layer semantics follow torchaudio's ConformerLayer as restated in oracle/conformer_ref.py:
@@ -64,6 +67,14 @@ struct LayerTape {
   ConvTape cv;
   float *x4, *fmean, *frstd, *out;
 };
+// stem: Conv1d(k3, s2) [-> Conv1d(k3, s2)] -> + positional encoding -> dropout; x [B][To][D], To = T1 (one conv) or T' (two)
+struct StemGeo {
+  int B, C, T, T1, To, D;
+  bool two;
+};
+struct StemTape {
+  float *a1, *out1, *w2p;
+};
 
 }  // namespace
 
@@ -76,10 +87,12 @@ struct eec_trainer {
   float p = 0.0f;
   uint64_t seed = 0;
   std::vector<LayerTape> lt;
-  float *a1 = nullptr, *out1 = nullptr, *w2p = nullptr;
+  StemTape stem{};
   int32_t* key_len = nullptr;
   uint32_t site_pe = 0;
   size_t tape_bytes = 0;
+  // EEC_TRAIN_FFN_FUSED=0 / EEC_TRAIN_FFN_FUSED_BWD=0, read once per entry-point call (read_ffn_switches)
+  bool ffn_gemm_fwd = false, ffn_gemm_bwd = false;
   // weight-gradient GEMMs run on a second stream, beside the dX chain they do not feed (created at the first backward)
   hipStream_t side = nullptr;
   hipEvent_t ev_main = nullptr, ev_side = nullptr;
@@ -105,6 +118,12 @@ struct Run {
   do {                                 \
     if (!r.dry) r.ok((expr), #expr);   \
   } while (0)
+int finish(const Run& r) {
+  if (r.tape.overflow || r.scr.overflow || r.sscr.overflow) return tfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
+  if (r.err != hipSuccess) return tfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
+  return 0;
+}
+size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 
 Drop drop_of(const Run& r, uint32_t site) { return Drop{r.tr->p, r.tr->seed, site}; }
 
@@ -194,19 +213,14 @@ void ln_bwd(Run& r, const float* dln, const float* x, const float* g, const floa
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
-// the feed-forward module as one launch (a property of the configuration: the sizing pass carves the same way);
-// EEC_TRAIN_FFN_FUSED=0 keeps the LayerNorm + two-GEMM path (A/B runs, and what other geometries take)
-bool ffn_fused_fwd_supported(const eec_trainer* tr) {
-  const char* e = getenv("EEC_TRAIN_FFN_FUSED");  // read per call: the tests flip it between steps of one process
-  const bool off = e && atoi(e) == 0;
-  const int D = tr->cfg.d_model, F = tr->cfg.d_ff;
-  return !off && (D == 256 || D == 512) && F >= 32 && F % 32 == 0 && (tr->np == 1 || tr->np == 3);
-}
-bool ffn_fused_bwd_supported(const eec_trainer* tr) {
-  const char* e = getenv("EEC_TRAIN_FFN_FUSED_BWD");
-  const bool off = e && atoi(e) == 0;
-  const int D = tr->cfg.d_model, F = tr->cfg.d_ff;
-  return !off && (D == 256 || D == 512) && F >= 32 && F % 32 == 0 && (tr->np == 1 || tr->np == 3);
+// the feed-forward module as one launch per direction where the configuration allows it; EEC_TRAIN_FFN_FUSED=0 / EEC_TRAIN_FFN_FUSED_BWD=0
+// keep the LayerNorm + two-GEMM path (A/B runs, and what other geometries take).  Either way the tape has the same layout.
+bool ffn_fused_geometry(const eec_config& c) { return (c.d_model == 256 || c.d_model == 512) && c.d_ff >= 32 && c.d_ff % 32 == 0; }
+bool ffn_fused_fwd_supported(const eec_trainer* tr) { return !tr->ffn_gemm_fwd && ffn_fused_geometry(tr->cfg) && (tr->np == 1 || tr->np == 3); }
+bool ffn_fused_bwd_supported(const eec_trainer* tr) { return !tr->ffn_gemm_bwd && ffn_fused_geometry(tr->cfg) && (tr->np == 1 || tr->np == 3); }
+void read_ffn_switches(eec_trainer& tr) {  // per call: the tests flip the switches between steps of one process
+  auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
+  tr.ffn_gemm_fwd = off("EEC_TRAIN_FFN_FUSED"), tr.ffn_gemm_bwd = off("EEC_TRAIN_FFN_FUSED_BWD");
 }
 // Room for the fragment images of every feed-forward module's W1 / W2 (4 x F x D x 4 bytes per module), carved from the tape at the
 // start of a forward by geometry alone (the tape layout must not depend on the operand mode of a particular step); a module's images
@@ -214,7 +228,7 @@ bool ffn_fused_bwd_supported(const eec_trainer* tr) {
 void carve_ffn_weights(Run& r, int n_layers) {
   eec_trainer* tr = r.tr;
   const int D = tr->cfg.d_model, F = tr->cfg.d_ff;
-  if (!((D == 256 || D == 512) && F >= 32 && F % 32 == 0)) return;
+  if (!ffn_fused_geometry(tr->cfg)) return;
   for (int l = 0; l < n_layers; ++l)
     for (int m = 0; m < 2; ++m) {
       FfnTape& t = m == 0 ? tr->lt[l].f1 : tr->lt[l].f2;
@@ -227,31 +241,32 @@ void pack_ffn_module(Run& r, const FfnTape& t, const float* w1, const float* w2,
   for (int k = 0; k < 4; ++k) jb.out[0][k] = t.wp[k];
   RUN(eec::launch_pack_ffn_batch(jb, r.tr->cfg.d_ff, r.tr->cfg.d_model, kind0, 2, r.st));
 }
-// LayerNorm rows + statistics that a feed-forward module's fused launch writes for whoever normalises its output next
+// LayerNorm rows + statistics of a feed-forward module's output for whoever normalises it next (the attention module's LayerNorm, the
+// layer's final one): carved right after the module's output on either path, written by the fused launch's row pass or by a LayerNorm
+// launch of its own
 struct NextLn {
-  const float *g = nullptr, *b = nullptr;       // in: the parameters
-  float *ln = nullptr, *mean = nullptr, *rstd = nullptr;  // out: tape buffers, set (and filled) when the fused launch ran
+  const float *g = nullptr, *b = nullptr;                 // in: the parameters
+  float *ln = nullptr, *mean = nullptr, *rstd = nullptr;  // out: tape buffers
 };
 float* ffn_fwd(Run& r, FfnTape& t, float* x, const float* ln_w, const float* ln_b, const float* w1, const float* b1, const float* w2, const float* b2,
-               NextLn* next = nullptr) {
+               NextLn& next) {
   const int M = r.tr->M, D = r.tr->cfg.d_model, F = r.tr->cfg.d_ff;
   t.x = x, t.ln = r.tape.f((size_t)M * D), t.mean = r.tape.f(M), t.rstd = r.tape.f(M), t.pre = r.tape.f((size_t)M * F);
   t.act = r.tape.f((size_t)M * F);
   t.site_act = r.site++, t.site_res = r.site++;
+  float* y = r.tape.f((size_t)M * D);
+  next.ln = r.tape.f((size_t)M * D), next.mean = r.tape.f(M), next.rstd = r.tape.f(M);
   if (ffn_fused_fwd_supported(r.tr)) {
     // ONE launch (ffn.hip, TR variants of the chain kernel): LayerNorm, both GEMMs, SiLU, both dropout sites and the residual; the
     // [M, F] tensors are written to the tape from the accumulators and never read back by the forward.  Its GEMMs run on split
     // fp16 fragments of THIS step's parameters, made right before it.
-    float* y = r.tape.f((size_t)M * D);
     pack_ffn_module(r, t, w1, w2, 0);
     eec::ChainArgs a{};
     a.x = x, a.M = M, a.F = F, a.nstage = 1, a.D = D;
     a.st[0] = eec::FfnStage{ln_w, ln_b, t.wp[0], b1, t.wp[1], b2, nullptr, nullptr, nullptr, nullptr, 0.5f, nullptr};
     a.tr = eec::ChainTrain{y, t.ln, t.mean, t.rstd, t.pre, t.act, r.tr->p, (unsigned long long)r.tr->seed, t.site_act, t.site_res};
-    if (next) {  // the consumer's LayerNorm rides in this launch's row pass (saves a launch and a pass over the rows)
-      next->ln = r.tape.f((size_t)M * D), next->mean = r.tape.f(M), next->rstd = r.tape.f(M);
-      a.tr.ln2_g = next->g, a.tr.ln2_b = next->b, a.tr.ln2 = next->ln, a.tr.mean2 = next->mean, a.tr.rstd2 = next->rstd;
-    }
+    // the consumer's LayerNorm rides in this launch's row pass (saves a launch and a pass over the rows)
+    a.tr.ln2_g = next.g, a.tr.ln2_b = next.b, a.tr.ln2 = next.ln, a.tr.mean2 = next.mean, a.tr.rstd2 = next.rstd;
     RUN(eec::launch_ffn_train_fwd(a, r.tr->np, r.st));
     return y;
   }
@@ -262,8 +277,8 @@ float* ffn_fwd(Run& r, FfnTape& t, float* x, const float* ln_w, const float* ln_
     RUN(launch_gemm(g, r.tr->np, r.st));
   }
   r.scr.reset();
-  float* y = r.tape.f((size_t)M * D);
   linear_residual_fwd(r, t.act, w2, b2, x, 0.5f, t.site_res, y, M, D, F);
+  RUN(launch_ln_fwd(y, next.g, next.b, next.ln, next.mean, next.rstd, M, D, r.st));
   return y;
 }
 
@@ -284,15 +299,13 @@ void batched(GemmArgs& g, const AttnGeo& a, long az0, long az1, long bz0, long b
   g.a_z0 = az0, g.a_z1 = az1, g.b_z0 = bz0, g.b_z1 = bz1, g.c_z0 = cz0, g.c_z1 = cz1;
 }
 
-float* attn_fwd(Run& r, AttnTape& t, float* x, const eec_layer_params& L, const NextLn* pre = nullptr) {
+// ln: the module's LayerNorm of x, computed by the feed-forward module in front of it (ffn_fwd)
+float* attn_fwd(Run& r, AttnTape& t, float* x, const eec_layer_params& L, const NextLn& ln) {
   const eec_trainer* tr = r.tr;
   const AttnGeo a = attn_geo(tr);
   const int M = tr->M, D = a.D, Tq = a.Tq;
   const bool fused = attn_fused_supported(D, a.H);  // a property of the configuration: the sizing pass carves the same way
-  const bool have_ln = pre && pre->ln;  // the module's LayerNorm already ran in the preceding feed-forward launch
-  t.x = x;
-  if (have_ln) t.ln = pre->ln, t.mean = pre->mean, t.rstd = pre->rstd;
-  else t.ln = r.tape.f((size_t)M * D), t.mean = r.tape.f(M), t.rstd = r.tape.f(M);
+  t.x = x, t.ln = ln.ln, t.mean = ln.mean, t.rstd = ln.rstd;
   t.qkv = r.tape.f((size_t)M * 3 * D);
   t.ctx = r.tape.f((size_t)M * D);
   t.P = t.Pd = t.lse = nullptr;
@@ -304,7 +317,6 @@ float* attn_fwd(Run& r, AttnTape& t, float* x, const eec_layer_params& L, const 
     t.Pd = tr->p > 0.0f ? pd : t.P;
   }
   t.site_p = r.site++, t.site_res = r.site++;
-  if (!have_ln) RUN(launch_ln_fwd(x, L.attn_ln_w, L.attn_ln_b, t.ln, t.mean, t.rstd, M, D, r.st));
   linear_fwd(r, t.ln, L.attn_in_w, L.attn_in_b, t.qkv, M, 3 * D, D);
   r.scr.reset();
   if (fused) {
@@ -346,60 +358,77 @@ float* conv_fwd(Run& r, ConvTape& t, float* x, const eec_layer_params& L, float*
   return y;
 }
 
-// One Conformer layer (torchaudio ConformerLayer: ffn1, attention, conv module, ffn2, final LayerNorm).  When a feed-forward module runs
-// as the fused launch, the LayerNorm that reads its output next -- the attention module's, the layer's final one -- is computed in that
-// launch's row pass (ffn_fwd NextLn) instead of by its own kernel.
+// One Conformer layer (torchaudio ConformerLayer: ffn1, attention, conv module, ffn2, final LayerNorm).  The LayerNorm that reads a
+// feed-forward module's output next -- the attention module's, the layer's final one -- is computed by that module (ffn_fwd NextLn).
 float* layer_fwd(Run& r, LayerTape& t, float* x, const eec_layer_params& L, float* bn_mv_layer) {
-  const int M = r.tr->M, D = r.tr->cfg.d_model;
-  const bool fuse_ln = ffn_fused_fwd_supported(r.tr);
   NextLn attn_ln{L.attn_ln_w, L.attn_ln_b}, fin_ln{L.final_ln_w, L.final_ln_b};
-  x = ffn_fwd(r, t.f1, x, L.ffn1_ln_w, L.ffn1_ln_b, L.ffn1_w1, L.ffn1_b1, L.ffn1_w2, L.ffn1_b2, fuse_ln ? &attn_ln : nullptr);
-  x = attn_fwd(r, t.at, x, L, &attn_ln);
+  x = ffn_fwd(r, t.f1, x, L.ffn1_ln_w, L.ffn1_ln_b, L.ffn1_w1, L.ffn1_b1, L.ffn1_w2, L.ffn1_b2, attn_ln);
+  x = attn_fwd(r, t.at, x, L, attn_ln);
   x = conv_fwd(r, t.cv, x, L, bn_mv_layer);
-  x = ffn_fwd(r, t.f2, x, L.ffn2_ln_w, L.ffn2_ln_b, L.ffn2_w1, L.ffn2_b1, L.ffn2_w2, L.ffn2_b2, fuse_ln ? &fin_ln : nullptr);
-  t.x4 = x;
-  if (fin_ln.ln) {
-    t.out = fin_ln.ln, t.fmean = fin_ln.mean, t.frstd = fin_ln.rstd;
-  } else {
-    t.fmean = r.tape.f(M), t.frstd = r.tape.f(M), t.out = r.tape.f((size_t)M * D);
-    RUN(launch_ln_fwd(x, L.final_ln_w, L.final_ln_b, t.out, t.fmean, t.frstd, M, D, r.st));
-  }
+  t.x4 = ffn_fwd(r, t.f2, x, L.ffn2_ln_w, L.ffn2_ln_b, L.ffn2_w1, L.ffn2_b1, L.ffn2_w2, L.ffn2_b2, fin_ln);
+  t.out = fin_ln.ln, t.fmean = fin_ln.mean, t.frstd = fin_ln.rstd;
   return t.out;
+}
+
+// layers [first, first + count) of `layers` (nullptr: the sizing pass) on the residual stream x; bn_mv: every layer's BatchNorm batch
+// statistics, indexed like `layers`.  The tapes are r.tr->lt[first ...].
+const eec_layer_params kNoLayer{};
+float* layers_fwd(Run& r, const eec_layer_params* layers, int first, int count, float* x, float* bn_mv) {
+  const int D = r.tr->cfg.d_model;
+  for (int li = first; li < first + count; ++li)
+    x = layer_fwd(r, r.tr->lt[li], x, layers ? layers[li] : kNoLayer, bn_mv ? bn_mv + (size_t)li * 2 * D : nullptr);
+  return x;
+}
+
+// the stem's recorded tensors: im2col of the mel frames, the first convolution's output and the second's weights in GEMM order
+StemTape stem_carve(Bump& t, const StemGeo& g) {
+  StemTape s{};
+  s.a1 = t.f((size_t)g.B * g.T1 * 3 * g.C);
+  if (g.two) s.out1 = t.f((size_t)g.B * g.T1 * g.D), s.w2p = t.f((size_t)g.D * 3 * g.D);
+  return s;
+}
+StemGeo model_stem(const eec_trainer* tr) { return StemGeo{tr->B, tr->cfg.n_mels, tr->T, tr->T1, tr->Tq, tr->cfg.d_model, true}; }
+void stem_forward(Run& r, const StemGeo& g, const StemTape& s, const float* w0, const float* b0, const float* w1, const float* b1, const float* pe,
+                  const float* mel, float* x, uint32_t site) {
+  RUN(launch_im2col_mel(mel, s.a1, g.B, g.C, g.T, g.T1, r.st));
+  if (g.two) {
+    linear_fwd(r, s.a1, w0, b0, s.out1, g.B * g.T1, g.D, 3 * g.C);
+    RUN(launch_permute_w3(w1, s.w2p, g.D, g.D, 1, r.st));
+    // second conv: three consecutive rows of out1 are one contiguous K = 3D operand row
+    GemmArgs a = gemm_args(s.out1, 2 * g.D, 1, s.w2p, 3 * g.D, 1, x, g.D, g.To, g.D, 3 * g.D);
+    a.bias = b1, a.nz = g.B, a.zdiv = 1, a.a_z0 = (long)g.T1 * g.D, a.c_z0 = (long)g.To * g.D;
+    RUN(launch_gemm(a, r.tr->np, r.st));
+  } else {
+    linear_fwd(r, s.a1, w0, b0, x, g.B * g.T1, g.D, 3 * g.C);
+  }
+  RUN(launch_add_pe_drop(x, pe, g.B, g.To, g.D, drop_of(r, site), r.st));
+}
+
+// exit head: logp = log_softmax(x . W^T + b), the logits in the main scratch
+void head_fwd(Run& r, const float* x, const float* W, const float* b, float* logp, int M, int V, int D) {
+  r.scr.reset();
+  float* logits = r.scr.f((size_t)M * V);
+  linear_fwd(r, x, W, b, logits, M, V, D);
+  RUN(launch_logsoftmax_fwd(logits, logp, M, V, r.st));
 }
 
 void forward(Run& r, const eec_params* P, const float* mel, const int64_t* lengths, float* out, float* bn_mv, float* taps) {
   eec_trainer* tr = r.tr;
   const eec_config& c = tr->cfg;
-  const int B = tr->B, T = tr->T, T1 = tr->T1, Tq = tr->Tq, M = tr->M, D = c.d_model, C = c.n_mels, V = c.vocab;
-  const int nl = c.n_exits * c.layers_per_exit;
-  tr->lt.assign(nl, LayerTape{});
+  const int B = tr->B, Tq = tr->Tq, M = tr->M, D = c.d_model, V = c.vocab, lpe = c.layers_per_exit;
+  const StemGeo sg = model_stem(tr);
+  tr->lt.assign(c.n_exits * lpe, LayerTape{});
   tr->key_len = (int32_t*)r.tape.f(B);
-  tr->a1 = r.tape.f((size_t)B * T1 * 3 * C), tr->out1 = r.tape.f((size_t)B * T1 * D), tr->w2p = r.tape.f((size_t)D * 3 * D);
+  tr->stem = stem_carve(r.tape, sg);
   float* x = r.tape.f((size_t)M * D);
   tr->site_pe = r.site++;
   RUN(eec::launch_enc_lengths((const long long*)lengths, B, Tq, tr->key_len, r.st));
-  RUN(launch_im2col_mel(mel, tr->a1, B, C, T, T1, r.st));
-  linear_fwd(r, tr->a1, P->sub0_w, P->sub0_b, tr->out1, B * T1, D, 3 * C);
-  RUN(launch_permute_w3(P->sub1_w, tr->w2p, D, D, 1, r.st));
-  {  // second conv: three consecutive rows of out1 are one contiguous K = 3D operand row
-    GemmArgs g = gemm_args(tr->out1, 2 * D, 1, tr->w2p, 3 * D, 1, x, D, Tq, D, 3 * D);
-    g.bias = P->sub1_b, g.nz = B, g.zdiv = 1, g.a_z0 = (long)T1 * D, g.c_z0 = (long)Tq * D;
-    RUN(launch_gemm(g, tr->np, r.st));
-  }
-  RUN(launch_add_pe_drop(x, P->pe, B, Tq, D, drop_of(r, tr->site_pe), r.st));
-  carve_ffn_weights(r, nl);
+  stem_forward(r, sg, tr->stem, P->sub0_w, P->sub0_b, P->sub1_w, P->sub1_b, P->pe, mel, x, tr->site_pe);
+  carve_ffn_weights(r, c.n_exits * lpe);
   for (int e = 0; e < c.n_exits; ++e) {
-    for (int l = 0; l < c.layers_per_exit; ++l) {
-      const int li = e * c.layers_per_exit + l;
-      const eec_layer_params& L = P->layers[li];
-      LayerTape& t = tr->lt[li];
-      x = layer_fwd(r, t, x, L, bn_mv ? bn_mv + (size_t)li * 2 * D : nullptr);
-    }
+    x = layers_fwd(r, P->layers, e * lpe, lpe, x, bn_mv);
     if (taps) RUN(hipMemcpyAsync(taps + (size_t)e * M * D, x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-    r.scr.reset();
-    float* logits = r.scr.f((size_t)M * V);
-    linear_fwd(r, x, P->head_w[e], P->head_b[e], logits, M, V, D);
-    RUN(launch_logsoftmax_fwd(logits, out + (size_t)e * M * V, M, V, r.st));
+    head_fwd(r, x, P->head_w[e], P->head_b[e], out + (size_t)e * M * V, M, V, D);
   }
 }
 
@@ -534,260 +563,12 @@ void conv_bwd(Run& r, const ConvTape& t, float* dx, const eec_layer_params& L, e
   ln_bwd(r, dln, t.x, L.conv_ln_w, t.mean, t.rstd, dx, true, (float*)G.conv_ln_w, (float*)G.conv_ln_b, M, D);
 }
 
-void backward(Run& r, const eec_params* P, const eec_params* Gp, const float* out, const float* grad_out, const float* grad_taps,
-              eec_group_done_fn on_group = nullptr, void* user = nullptr) {
-  eec_trainer* tr = r.tr;
-  const eec_config& c = tr->cfg;
-  const int B = tr->B, T1 = tr->T1, Tq = tr->Tq, M = tr->M, D = c.d_model, C = c.n_mels, V = c.vocab;
-  // the gradient of the residual stream lives at the start of the scratch region for the whole backward
-  float* dx = r.tape.f((size_t)M * D);
-  for (int e = c.n_exits - 1; e >= 0; --e) {
-    const float* tap = tr->lt[(e + 1) * c.layers_per_exit - 1].out;
-    bwd_scratch_reset(r);
-    float* dlogits = r.scr.f((size_t)M * V);
-    RUN(eec::launch_logsoftmax_backward(out + (size_t)e * M * V, grad_out + (size_t)e * M * V, M, V, dlogits, r.st));
-    linear_bwd_weight(r, dlogits, tap, (float*)Gp->head_w[e], (float*)Gp->head_b[e], M, V, D);
-    linear_bwd_data(r, dlogits, P->head_w[e], dx, M, V, D, e != c.n_exits - 1);
-    if (grad_taps) RUN(launch_axpy(dx, grad_taps + (size_t)e * M * D, 1.0f, (long)M * D, r.st));  // what the caller did with the tap itself
-    for (int l = c.layers_per_exit - 1; l >= 0; --l) {
-      const int li = e * c.layers_per_exit + l;
-      const eec_layer_params& L = P->layers[li];
-      eec_layer_params G = Gp->layers[li];
-      const LayerTape& t = tr->lt[li];
-      const PreLnBwd fin{t.x4, t.fmean, t.frstd, L.final_ln_w, (float*)G.final_ln_w, (float*)G.final_ln_b};
-      ffn_bwd(r, t.f2, dx, L.ffn2_ln_w, L.ffn2_w1, L.ffn2_w2, (float*)G.ffn2_ln_w, (float*)G.ffn2_ln_b, (float*)G.ffn2_w1, (float*)G.ffn2_b1,
-              (float*)G.ffn2_w2, (float*)G.ffn2_b2, &fin);
-      conv_bwd(r, t.cv, dx, L, G);
-      attn_bwd(r, t.at, dx, L, G);
-      ffn_bwd(r, t.f1, dx, L.ffn1_ln_w, L.ffn1_w1, L.ffn1_w2, (float*)G.ffn1_ln_w, (float*)G.ffn1_ln_b, (float*)G.ffn1_w1, (float*)G.ffn1_b1,
-              (float*)G.ffn1_w2, (float*)G.ffn1_b2);
-    }
-    if (on_group && !r.dry) {
-      // every gradient of exit group e (its layers and its head) is now enqueued; the weight-gradient jobs of the side
-      // stream are joined first (the join the next group's scratch reset would make anyway), so "after everything on the
-      // main stream so far" is a sufficient dependency for the caller's collective
-      join_side(r);
-      on_group(e, user);
-    }
-  }
-  // stem
-  bwd_scratch_reset(r);
-  float* dx0 = r.scr.f((size_t)M * D);
-  float* Gc = r.scr.f((size_t)M * 3 * D);
-  float* dout1 = r.scr.f((size_t)B * T1 * D);
-  float* dw2p = r.scr.f((size_t)D * 3 * D);
-  RUN(launch_scale_drop(dx, 1.0f, dx0, (long)M * D, drop_of(r, tr->site_pe), r.st));
-  {
-    const size_t mark = r.scr.off;
-    float* part = r.scr.f((size_t)B * D * 3 * D);
-    GemmArgs g = gemm_args(dx0, 1, D, tr->out1, 1, 2 * D, part, 3 * D, D, 3 * D, Tq);
-    g.nz = B, g.zdiv = 1, g.a_z0 = (long)Tq * D, g.b_z0 = (long)T1 * D, g.c_z0 = (long)D * 3 * D;
-    RUN(launch_gemm(g, tr->np, r.st));
-    RUN(launch_reduce_leading(part, B, (long)D * 3 * D, (long)D * 3 * D, dw2p, r.st));
-    RUN(launch_permute_w3(dw2p, (float*)Gp->sub1_w, D, D, 0, r.st));
-    r.scr.reset(mark);
-    const int nb = colsum_blocks(M);
-    float* bpart = r.scr.f((size_t)nb * D);
-    RUN(launch_colsum_partial(dx0, M, D, bpart, r.st));
-    RUN(launch_reduce_leading(bpart, nb, D, D, (float*)Gp->sub1_b, r.st));
-    r.scr.reset(mark);
-  }
-  {  // G[m][(j, c)] = sum_o dx0[m][o] w2p[o][(j, c)]
-    GemmArgs g = gemm_args(dx0, D, 1, tr->w2p, 1, 3 * D, Gc, 3 * D, M, 3 * D, D);
-    RUN(launch_gemm(g, tr->np, r.st));
-  }
-  RUN(launch_col2im_stride2(Gc, dout1, B, T1, Tq, D, r.st));
-  linear_bwd_weight(r, dout1, tr->a1, (float*)Gp->sub0_w, (float*)Gp->sub0_b, B * T1, D, 3 * C);
-  join_side(r);  // every gradient is complete in main-stream order
-  if (on_group && !r.dry) on_group(-1, user);
-}
-
-int check_trainer_cfg(const eec_config& c) {
-  if (c.arch != EEC_ARCH_CONFORMER) return tfail(EEC_ERR_UNSUPPORTED, "the training step covers the Conformer architecture");
-  if (c.d_model <= 0 || c.d_model > 1024 || c.n_heads <= 0 || c.d_model % c.n_heads) return tfail(EEC_ERR_BAD_ARG, "d_model <= 1024, divisible by n_heads");
-  if (c.dw_kernel < 1 || c.dw_kernel > 31 || !(c.dw_kernel & 1)) return tfail(EEC_ERR_BAD_ARG, "depthwise kernel: odd, <= 31");
-  if (c.d_ff <= 0 || c.n_exits <= 0 || c.layers_per_exit <= 0 || c.n_mels <= 0 || c.vocab <= 0) return tfail(EEC_ERR_BAD_ARG, "bad configuration");
-  // the log-softmax backward and the CTC gradient hold a vocabulary row in one wave (csrc/ctc.hip): refuse here, before a
-  // forward has recorded a multi-GB tape that loss.backward() could not use
-  if (c.vocab > 256 || c.vocab % 4) return tfail(EEC_ERR_UNSUPPORTED, "the training step needs vocab <= 256 and a multiple of 4 (got " + std::to_string(c.vocab) + ")");
-  return 0;
-}
-
-int set_geometry(eec_trainer* tr, int B, int T) {
-  if (B <= 0 || T < 7) return tfail(EEC_ERR_BAD_ARG, "B >= 1, T >= 7");
-  tr->B = B, tr->T = T, tr->T1 = (T - 3) / 2 + 1, tr->Tq = (tr->T1 - 3) / 2 + 1, tr->M = B * tr->Tq;
-  if (tr->Tq > tr->cfg.max_len) return tfail(EEC_ERR_BAD_ARG, "T' exceeds max_len");
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-const char* eec_trainer_last_error(void) { return g_terr.c_str(); }
-
-int eec_trainer_create(const eec_config* cfg, eec_trainer** out) {
-  if (!cfg || !out) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (int rc = check_trainer_cfg(*cfg)) return rc;
-  eec_trainer* tr = new eec_trainer();
-  tr->cfg = *cfg;
-  tr->device = -1;  // bound to the device that is current in the first eec_train_forward
-  *out = tr;
-  return 0;
-}
-void eec_trainer_destroy(eec_trainer* tr) {
-  if (!tr) return;
-  if (tr->side) (void)hipStreamDestroy(tr->side);
-  if (tr->ev_main) (void)hipEventDestroy(tr->ev_main);
-  if (tr->ev_side) (void)hipEventDestroy(tr->ev_side);
-  delete tr;
-}
-
-size_t eec_trainer_workspace_bytes(const eec_trainer* tr_in, int B, int T) {
-  if (!tr_in) return 0;
-  eec_trainer tmp = *tr_in;
-  if (set_geometry(&tmp, B, T)) return 0;
-  Run r{&tmp, true, nullptr};
-  std::vector<eec_layer_params> layers(tmp.cfg.n_exits * tmp.cfg.layers_per_exit);
-  std::vector<const float*> heads(tmp.cfg.n_exits, nullptr);
-  eec_params P{};
-  P.layers = layers.data(), P.head_w = heads.data(), P.head_b = heads.data();
-  forward(r, &P, nullptr, nullptr, nullptr, nullptr, nullptr);
-  const size_t fwd_scr = r.scr.peak;
-  r.scr = Bump{};
-  backward(r, &P, &P, nullptr, nullptr, nullptr);
-  return (r.tape.peak + 256) + (r.sscr.peak + 256) + std::max(fwd_scr, r.scr.peak) + 4096;
-}
-
-int eec_train_forward(eec_trainer* tr, const eec_params* params, const float* mel, const int64_t* lengths, int B, int T, int passes,
-                      float drop_prob, uint64_t seed, float* out, float* taps, float* bn_batch_stats, void* workspace, size_t workspace_bytes,
-                      void* stream) {
-  if (!tr || !params || !mel || !lengths || !out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return tfail(EEC_ERR_BAD_ARG, "no current HIP device");
-  if (tr->device < 0) tr->device = dev;
-  if (dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
-  if (int rc = set_geometry(tr, B, T)) return rc;
-  if (workspace_bytes < eec_trainer_workspace_bytes(tr, B, T)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
-  tr->np = passes, tr->p = drop_prob, tr->seed = seed, tr->recorded = false;
-  Run r{tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace;
-  // forward once with a null scratch to learn where the tape ends (pointer arithmetic only), then for real
-  {
-    eec_trainer tmp = *tr;
-    Run d{&tmp, true, nullptr};
-    forward(d, params, mel, lengths, out, bn_batch_stats, taps);
-    tr->tape_bytes = (d.tape.peak + 255) / 256 * 256;
-  }
-  r.scr.base = (char*)workspace + tr->tape_bytes;
-  r.tape.cap = tr->tape_bytes;
-  if (workspace_bytes < tr->tape_bytes) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
-  r.scr.cap = workspace_bytes - tr->tape_bytes;
-  {  // the scratch need of this forward, before any launch
-    eec_trainer tmp = *tr;
-    Run d{&tmp, true, nullptr};
-    forward(d, params, mel, lengths, out, bn_batch_stats, taps);
-    if (d.scr.peak > r.scr.cap) return tfail(EEC_ERR_WORKSPACE, "workspace too small for the forward scratch");
-  }
-  forward(r, params, mel, lengths, out, bn_batch_stats, taps);
-  if (r.tape.overflow || r.scr.overflow) return tfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return tfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  tr->recorded = true;
-  return 0;
-}
-
-int eec_train_backward(eec_trainer* tr, const eec_params* params, const eec_params* grads, const float* out, const float* grad_out,
-                       const float* grad_taps, void* workspace, size_t workspace_bytes, void* stream) {
-  return eec_train_backward_ex(tr, params, grads, out, grad_out, grad_taps, workspace, workspace_bytes, stream, nullptr, nullptr);
-}
-
-int eec_train_backward_ex(eec_trainer* tr, const eec_params* params, const eec_params* grads, const float* out, const float* grad_out,
-                          const float* grad_taps, void* workspace, size_t workspace_bytes, void* stream, eec_group_done_fn on_group,
-                          void* user) {
-  if (!tr || !params || !grads || !out || !grad_out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (!tr->recorded) return tfail(EEC_ERR_BAD_ARG, "no recorded forward (eec_train_forward first, same workspace)");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
-  if (workspace_bytes < eec_trainer_workspace_bytes(tr, tr->B, tr->T)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
-  Run r{tr, false, (hipStream_t)stream};
-  // the residual-stream gradient is carved from the head of the scratch region through `tape` (kept for the whole backward)
-  r.tape.base = (char*)workspace + tr->tape_bytes;
-  const size_t dx_bytes = ((size_t)tr->M * tr->cfg.d_model * sizeof(float) + 511) / 256 * 256;
-  size_t side_bytes = 0;
-  {  // the scratch needs of this backward, before any launch: [tape][dx][side-stream scratch][main scratch]
-    eec_trainer tmp = *tr;
-    Run d{&tmp, true, nullptr};
-    backward(d, params, grads, out, grad_out, grad_taps);
-    side_bytes = (d.sscr.peak + 255) / 256 * 256;
-    if (workspace_bytes < tr->tape_bytes + dx_bytes + side_bytes || d.scr.peak > workspace_bytes - tr->tape_bytes - dx_bytes - side_bytes ||
-        d.tape.peak > dx_bytes)
-      return tfail(EEC_ERR_WORKSPACE, "workspace too small for the backward scratch: need " + std::to_string(d.scr.peak) + " + " +
-                                          std::to_string(d.sscr.peak) + " + " + std::to_string(d.tape.peak) + " beside the tape of " +
-                                          std::to_string(tr->tape_bytes) + ", workspace " + std::to_string(workspace_bytes));
-  }
-  const char* no_side = getenv("EEC_TRAIN_NO_SIDE");  // diagnostic: every job on the main stream (results are bit-identical)
-  if (no_side && no_side[0] == '1') {
-    r.side = nullptr;
-  } else if (!tr->side) {  // a failure here only means the jobs run on the main stream
-    if (hipStreamCreateWithFlags(&tr->side, hipStreamNonBlocking) != hipSuccess) tr->side = nullptr;
-    if (tr->side && (hipEventCreateWithFlags(&tr->ev_main, hipEventDisableTiming) != hipSuccess ||
-                     hipEventCreateWithFlags(&tr->ev_side, hipEventDisableTiming) != hipSuccess)) {
-      (void)hipStreamDestroy(tr->side);
-      tr->side = nullptr;
-    }
-  }
-  if (!(no_side && no_side[0] == '1')) r.side = tr->side;
-  r.sscr.base = (char*)workspace + tr->tape_bytes + dx_bytes, r.sscr.cap = side_bytes;
-  r.scr.base = (char*)workspace + tr->tape_bytes + dx_bytes + side_bytes;
-  r.tape.cap = dx_bytes, r.scr.cap = workspace_bytes - tr->tape_bytes - dx_bytes - side_bytes;
-  backward(r, params, grads, out, grad_out, grad_taps, on_group, user);
-  if (r.tape.overflow || r.scr.overflow || r.sscr.overflow) return tfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return tfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  return 0;
-}
-
-// ---- Building blocks of the training step (the other model types of train.py:180-208: Splitformer, Early_zipformer) ---------
-// The same forward / backward modules as the monolithic step above, cut at the places where those models put their own glue
-// (strided slices, repeats, adds: torch ops under autograd): a GROUP of Conformer layers on given rows, the STEM (one or two
-// convolutions + positional encoding) and an exit HEAD.  The entries are stateless: the recorded activations live in the
-// caller's workspace, whose layout is a function of the geometry, so the backward re-derives the pointers by a dry run of the
-// forward's carve (same seed / drop_prob / site_base regenerate the masks).  Everything runs on the caller's stream.
-}  // extern "C"
-
-namespace {
-
-struct BlockSizes {
-  size_t tape, fwd_scr, bwd_tape, bwd_scr, side;
-  size_t total() const { return tape + std::max(fwd_scr, bwd_tape + side + bwd_scr) + 1024; }
-};
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
-void group_forward(Run& r, const eec_layer_params* layers, int n_layers, const float* x_in, float* x_out, float* bn_mv) {
-  eec_trainer* tr = r.tr;
-  const int M = tr->M, D = tr->cfg.d_model;
-  tr->lt.assign(n_layers, LayerTape{});
-  float* x = (float*)x_in;
-  static const eec_layer_params kNone{};
-  carve_ffn_weights(r, n_layers);
-  for (int l = 0; l < n_layers; ++l) {
-    const eec_layer_params& L = layers ? layers[l] : kNone;
-    LayerTape& t = tr->lt[l];
-    x = layer_fwd(r, t, x, L, bn_mv ? bn_mv + (size_t)l * 2 * D : nullptr);
-  }
-  if (x_out) RUN(hipMemcpyAsync(x_out, x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-}
-void group_backward(Run& r, const eec_layer_params* layers, const eec_layer_params* grads, int n_layers, const float* grad_out, float* grad_in) {
-  eec_trainer* tr = r.tr;
-  const int M = tr->M, D = tr->cfg.d_model;
-  float* dx = r.tape.f((size_t)M * D);
-  if (grad_out) RUN(hipMemcpyAsync(dx, grad_out, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-  static const eec_layer_params kNone{};
-  for (int l = n_layers - 1; l >= 0; --l) {
-    const eec_layer_params& L = layers ? layers[l] : kNone;
-    eec_layer_params G = grads ? grads[l] : kNone;
-    const LayerTape& t = tr->lt[l];
+// the backward of layers_fwd: dx holds the gradient of the last layer's output and receives that of the first layer's input
+void layers_bwd(Run& r, const eec_layer_params* layers, const eec_layer_params* grads, int first, int count, float* dx) {
+  for (int li = first + count - 1; li >= first; --li) {
+    const eec_layer_params& L = layers ? layers[li] : kNoLayer;
+    eec_layer_params G = grads ? grads[li] : kNoLayer;
+    const LayerTape& t = r.tr->lt[li];
     const PreLnBwd fin{t.x4, t.fmean, t.frstd, L.final_ln_w, (float*)G.final_ln_w, (float*)G.final_ln_b};
     ffn_bwd(r, t.f2, dx, L.ffn2_ln_w, L.ffn2_w1, L.ffn2_w2, (float*)G.ffn2_ln_w, (float*)G.ffn2_ln_b, (float*)G.ffn2_w1, (float*)G.ffn2_b1,
             (float*)G.ffn2_w2, (float*)G.ffn2_b2, &fin);
@@ -796,63 +577,13 @@ void group_backward(Run& r, const eec_layer_params* layers, const eec_layer_para
     ffn_bwd(r, t.f1, dx, L.ffn1_ln_w, L.ffn1_w1, L.ffn1_w2, (float*)G.ffn1_ln_w, (float*)G.ffn1_ln_b, (float*)G.ffn1_w1, (float*)G.ffn1_b1,
             (float*)G.ffn1_w2, (float*)G.ffn1_b2);
   }
-  join_side(r);
-  if (grad_in) RUN(hipMemcpyAsync(grad_in, dx, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-}
-BlockSizes group_sizes(eec_trainer tmp, int n_layers) {
-  Run d{&tmp, true, nullptr};
-  group_forward(d, nullptr, n_layers, nullptr, nullptr, nullptr);
-  BlockSizes z{};
-  z.tape = up256(d.tape.peak), z.fwd_scr = up256(d.scr.peak);
-  Run b{&tmp, true, nullptr};
-  group_backward(b, nullptr, nullptr, n_layers, nullptr, nullptr);
-  z.bwd_tape = up256(b.tape.peak), z.bwd_scr = up256(b.scr.peak), z.side = up256(b.sscr.peak);
-  return z;
-}
-int block_trainer(eec_trainer& tr, const eec_config* cfg, int B, int Tq, int passes, float drop_prob, uint64_t seed, const int32_t* key_len) {
-  if (!cfg) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (int rc = check_trainer_cfg(*cfg)) return rc;
-  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
-  if (B <= 0 || Tq <= 0 || Tq > cfg->max_len) return tfail(EEC_ERR_BAD_ARG, "B >= 1, 1 <= T' <= max_len");
-  tr.cfg = *cfg;
-  tr.B = B, tr.Tq = Tq, tr.M = B * Tq, tr.np = passes, tr.p = drop_prob, tr.seed = seed, tr.key_len = (int32_t*)key_len;
-  return 0;
 }
 
-// stem: Conv1d(k3, s2) [-> Conv1d(k3, s2)] -> + positional encoding -> dropout; x [B][To][D], To = T1 (one conv) or T' (two)
-struct StemGeo {
-  int B, C, T, T1, To, D;
-  bool two;
-};
-struct StemTape {
-  float *a1, *out1, *w2p;
-};
-StemTape stem_carve(Bump& t, const StemGeo& g) {
-  StemTape s{};
-  s.a1 = t.f((size_t)g.B * g.T1 * 3 * g.C);
-  if (g.two) s.out1 = t.f((size_t)g.B * g.T1 * g.D), s.w2p = t.f((size_t)g.D * 3 * g.D);
-  return s;
-}
-void stem_forward(Run& r, const StemGeo& g, const float* w0, const float* b0, const float* w1, const float* b1, const float* pe, const float* mel,
-                  float* x, uint32_t site) {
-  const StemTape s = stem_carve(r.tape, g);
-  RUN(launch_im2col_mel(mel, s.a1, g.B, g.C, g.T, g.T1, r.st));
-  if (g.two) {
-    linear_fwd(r, s.a1, w0, b0, s.out1, g.B * g.T1, g.D, 3 * g.C);
-    RUN(launch_permute_w3(w1, s.w2p, g.D, g.D, 1, r.st));
-    GemmArgs a = gemm_args(s.out1, 2 * g.D, 1, s.w2p, 3 * g.D, 1, x, g.D, g.To, g.D, 3 * g.D);
-    a.bias = b1, a.nz = g.B, a.zdiv = 1, a.a_z0 = (long)g.T1 * g.D, a.c_z0 = (long)g.To * g.D;
-    RUN(launch_gemm(a, r.tr->np, r.st));
-  } else {
-    linear_fwd(r, s.a1, w0, b0, x, g.B * g.T1, g.D, 3 * g.C);
-  }
-  RUN(launch_add_pe_drop(x, pe, g.B, g.To, g.D, drop_of(r, site), r.st));
-}
-void stem_backward(Run& r, const StemGeo& g, const float* grad_x, float* g_w0, float* g_b0, float* g_w1, float* g_b1, uint32_t site) {
-  const StemTape s = stem_carve(r.tape, g);
+// the backward of stem_forward from grad_x, the gradient of its output; ends with the side stream joined
+void stem_backward(Run& r, const StemGeo& g, const StemTape& s, const float* grad_x, float* g_w0, float* g_b0, float* g_w1, float* g_b1,
+                   uint32_t site) {
   const int B = g.B, D = g.D, T1 = g.T1, To = g.To, M = B * To;
-  r.scr.reset();
+  bwd_scratch_reset(r);
   float* dx0 = r.scr.f((size_t)M * D);
   RUN(launch_scale_drop(grad_x, 1.0f, dx0, (long)M * D, drop_of(r, site), r.st));
   if (!g.two) {
@@ -886,6 +617,72 @@ void stem_backward(Run& r, const StemGeo& g, const float* grad_x, float* g_w0, f
   linear_bwd_weight(r, dout1, s.a1, g_w0, g_b0, B * T1, D, 3 * g.C);
   join_side(r);
 }
+
+// the backward of head_fwd: dlogits = grad_logp - exp(logp) * rowsum(grad_logp) in the main scratch; dW, db from it (a weight-gradient
+// job); dx (optional) (+)= dlogits . W
+void head_bwd(Run& r, const float* x, const float* W, const float* logp, const float* grad_logp, float* dx, bool accumulate, float* dW, float* db,
+              int M, int V, int D) {
+  bwd_scratch_reset(r);
+  float* dlogits = r.scr.f((size_t)M * V);
+  RUN(eec::launch_logsoftmax_backward(logp, grad_logp, M, V, dlogits, r.st));
+  linear_bwd_weight(r, dlogits, x, dW, db, M, V, D);
+  if (dx) linear_bwd_data(r, dlogits, W, dx, M, V, D, accumulate);
+}
+
+void backward(Run& r, const eec_params* P, const eec_params* Gp, const float* out, const float* grad_out, const float* grad_taps,
+              eec_group_done_fn on_group = nullptr, void* user = nullptr) {
+  eec_trainer* tr = r.tr;
+  const eec_config& c = tr->cfg;
+  const int M = tr->M, D = c.d_model, V = c.vocab, lpe = c.layers_per_exit;
+  // the gradient of the residual stream lives at the start of the scratch region for the whole backward
+  float* dx = r.tape.f((size_t)M * D);
+  for (int e = c.n_exits - 1; e >= 0; --e) {
+    head_bwd(r, tr->lt[(e + 1) * lpe - 1].out, P->head_w[e], out + (size_t)e * M * V, grad_out + (size_t)e * M * V, dx, e != c.n_exits - 1,
+             (float*)Gp->head_w[e], (float*)Gp->head_b[e], M, V, D);
+    if (grad_taps) RUN(launch_axpy(dx, grad_taps + (size_t)e * M * D, 1.0f, (long)M * D, r.st));  // what the caller did with the tap itself
+    layers_bwd(r, P->layers, Gp->layers, e * lpe, lpe, dx);
+    if (on_group && !r.dry) {
+      // every gradient of exit group e (its layers and its head) is now enqueued; the weight-gradient jobs of the side
+      // stream are joined first (the join the next group's scratch reset would make anyway), so "after everything on the
+      // main stream so far" is a sufficient dependency for the caller's collective
+      join_side(r);
+      on_group(e, user);
+    }
+  }
+  // every gradient is complete in main-stream order when the stem's backward returns
+  stem_backward(r, model_stem(tr), tr->stem, dx, (float*)Gp->sub0_w, (float*)Gp->sub0_b, (float*)Gp->sub1_w, (float*)Gp->sub1_b, tr->site_pe);
+  if (on_group && !r.dry) on_group(-1, user);
+}
+
+int check_trainer_cfg(const eec_config& c) {
+  if (c.arch != EEC_ARCH_CONFORMER) return tfail(EEC_ERR_UNSUPPORTED, "the training step covers the Conformer architecture");
+  if (c.d_model <= 0 || c.d_model > 1024 || c.n_heads <= 0 || c.d_model % c.n_heads) return tfail(EEC_ERR_BAD_ARG, "d_model <= 1024, divisible by n_heads");
+  if (c.dw_kernel < 1 || c.dw_kernel > 31 || !(c.dw_kernel & 1)) return tfail(EEC_ERR_BAD_ARG, "depthwise kernel: odd, <= 31");
+  if (c.d_ff <= 0 || c.n_exits <= 0 || c.layers_per_exit <= 0 || c.n_mels <= 0 || c.vocab <= 0) return tfail(EEC_ERR_BAD_ARG, "bad configuration");
+  // the log-softmax backward and the CTC gradient hold a vocabulary row in one wave (csrc/ctc.hip): refuse here, before a
+  // forward has recorded a multi-GB tape that loss.backward() could not use
+  if (c.vocab > 256 || c.vocab % 4) return tfail(EEC_ERR_UNSUPPORTED, "the training step needs vocab <= 256 and a multiple of 4 (got " + std::to_string(c.vocab) + ")");
+  return 0;
+}
+
+int set_geometry(eec_trainer* tr, int B, int T) {
+  if (B <= 0 || T < 7) return tfail(EEC_ERR_BAD_ARG, "B >= 1, T >= 7");
+  tr->B = B, tr->T = T, tr->T1 = (T - 3) / 2 + 1, tr->Tq = (tr->T1 - 3) / 2 + 1, tr->M = B * tr->Tq;
+  if (tr->Tq > tr->cfg.max_len) return tfail(EEC_ERR_BAD_ARG, "T' exceeds max_len");
+  return 0;
+}
+
+int block_trainer(eec_trainer& tr, const eec_config* cfg, int B, int Tq, int passes, float drop_prob, uint64_t seed, const int32_t* key_len) {
+  if (!cfg) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_trainer_cfg(*cfg)) return rc;
+  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
+  if (B <= 0 || Tq <= 0 || Tq > cfg->max_len) return tfail(EEC_ERR_BAD_ARG, "B >= 1, 1 <= T' <= max_len");
+  tr.cfg = *cfg;
+  tr.B = B, tr.Tq = Tq, tr.M = B * Tq, tr.np = passes, tr.p = drop_prob, tr.seed = seed, tr.key_len = (int32_t*)key_len;
+  read_ffn_switches(tr);
+  return 0;
+}
 int stem_geo(StemGeo& g, const eec_config* cfg, int B, int T, int two) {
   if (!cfg || B <= 0 || T < (two ? 7 : 3)) return tfail(EEC_ERR_BAD_ARG, "B >= 1 and T >= 3 (one convolution) / 7 (two)");
   const int T1 = (T - 3) / 2 + 1;
@@ -893,28 +690,161 @@ int stem_geo(StemGeo& g, const eec_config* cfg, int B, int T, int two) {
   if (g.To > cfg->max_len) return tfail(EEC_ERR_BAD_ARG, "output frames exceed max_len");
   return 0;
 }
-struct StemSizes {
-  size_t tape, scr, side;
+
+// ---- Building blocks of the training step (the other model types of train.py:180-208: Splitformer, Early_zipformer) ---------
+// The routines of the whole-model step (layers_fwd / layers_bwd, stem_forward / stem_backward, head_fwd / head_bwd) behind entries
+// cut at the places where those models put their own glue (strided slices, repeats, adds: torch ops under autograd): a GROUP of
+// Conformer layers on given rows, the STEM (one or two convolutions + positional encoding) and an exit HEAD.  The entries are
+// stateless: the recorded activations live in the caller's workspace, whose layout is a function of the geometry alone, so the
+// backward re-derives the pointers by a dry run of the forward's carve (same seed / drop_prob / site_base regenerate the masks).
+// Everything runs on the caller's stream.
+void group_forward(Run& r, const eec_layer_params* layers, int n_layers, const float* x_in, float* x_out, float* bn_mv) {
+  r.tr->lt.assign(n_layers, LayerTape{});
+  carve_ffn_weights(r, n_layers);
+  float* x = layers_fwd(r, layers, 0, n_layers, (float*)x_in, bn_mv);
+  if (x_out) RUN(hipMemcpyAsync(x_out, x, (size_t)r.tr->M * r.tr->cfg.d_model * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+}
+void group_backward(Run& r, const eec_layer_params* layers, const eec_layer_params* grads, int n_layers, const float* grad_out, float* grad_in) {
+  const size_t n = (size_t)r.tr->M * r.tr->cfg.d_model;
+  float* dx = r.tape.f(n);
+  if (grad_out) RUN(hipMemcpyAsync(dx, grad_out, n * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+  layers_bwd(r, layers, grads, 0, n_layers, dx);
+  join_side(r);
+  if (grad_in) RUN(hipMemcpyAsync(grad_in, dx, n * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+}
+
+// ---- workspace sizing ------------------------------------------------------------------------------------------------
+// What an entry carves, from one dry run of its forward and one of its backward (pointer arithmetic only, nothing is launched): the
+// peaks of the forward's tape and scratch, and of the backward's residual-stream gradient (the `tape` of its Run), side-stream scratch
+// and main scratch, in bytes.
+struct Sizes {
+  size_t tape, fwd_scr, dx, side, bwd_scr;
 };
-StemSizes stem_sizes(eec_trainer tmp, const StemGeo& g) {
-  Run d{&tmp, true, nullptr};
-  stem_backward(d, g, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-  return StemSizes{up256(d.tape.peak), up256(d.scr.peak), up256(d.sscr.peak)};
+template <class Fwd, class Bwd>
+Sizes plan(eec_trainer tmp, Fwd&& fwd, Bwd&& bwd) {
+  Run f{&tmp, true, nullptr}, b{&tmp, true, nullptr};
+  fwd(f);
+  bwd(b);  // reads the tape pointers the forward left in tmp
+  return Sizes{f.tape.peak, f.scr.peak, b.tape.peak, b.sscr.peak, b.scr.peak};
 }
-int finish(const Run& r) {
-  if (r.tape.overflow || r.scr.overflow || r.sscr.overflow) return tfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return tfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  return 0;
+// whole-model step: [tape][dx][side-stream scratch][main scratch] in the backward; the forward's scratch follows the tape
+Sizes model_plan(const eec_trainer& tr) {
+  std::vector<const float*> heads(tr.cfg.n_exits, nullptr);
+  eec_params P{};
+  P.head_w = heads.data(), P.head_b = heads.data();
+  return plan(tr, [&](Run& r) { forward(r, &P, nullptr, nullptr, nullptr, nullptr, nullptr); },
+              [&](Run& r) { backward(r, &P, &P, nullptr, nullptr, nullptr); });
 }
+size_t model_workspace(const Sizes& z) { return up256(z.tape) + (z.dx + 256) + (z.side + 256) + std::max(z.fwd_scr, z.bwd_scr) + 4096; }
+// group: the same regions; stem: [tape][side-stream scratch][main scratch]
+Sizes group_plan(const eec_trainer& tr, int n_layers) {
+  return plan(tr, [&](Run& r) { group_forward(r, nullptr, n_layers, nullptr, nullptr, nullptr); },
+              [&](Run& r) { group_backward(r, nullptr, nullptr, n_layers, nullptr, nullptr); });
+}
+size_t group_workspace(const Sizes& z) { return up256(z.tape) + std::max(up256(z.fwd_scr), up256(z.dx) + up256(z.side) + up256(z.bwd_scr)) + 1024; }
+Sizes stem_plan(const eec_trainer& tr, const StemGeo& g) {
+  return plan(tr, [&](Run& r) { stem_forward(r, g, stem_carve(r.tape, g), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0); },
+              [&](Run& r) { stem_backward(r, g, StemTape{}, nullptr, nullptr, nullptr, nullptr, nullptr, 0); });
+}
+size_t stem_workspace(const Sizes& z) { return up256(z.tape) + up256(z.side) + up256(z.bwd_scr); }
 
 }  // namespace
 
 extern "C" {
 
+const char* eec_trainer_last_error(void) { return g_terr.c_str(); }
+
+int eec_trainer_create(const eec_config* cfg, eec_trainer** out) {
+  if (!cfg || !out) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_trainer_cfg(*cfg)) return rc;
+  eec_trainer* tr = new eec_trainer();
+  tr->cfg = *cfg;
+  tr->device = -1;  // bound to the device that is current in the first eec_train_forward
+  *out = tr;
+  return 0;
+}
+void eec_trainer_destroy(eec_trainer* tr) {
+  if (!tr) return;
+  if (tr->side) (void)hipStreamDestroy(tr->side);
+  if (tr->ev_main) (void)hipEventDestroy(tr->ev_main);
+  if (tr->ev_side) (void)hipEventDestroy(tr->ev_side);
+  delete tr;
+}
+
+size_t eec_trainer_workspace_bytes(const eec_trainer* tr_in, int B, int T) {
+  if (!tr_in) return 0;
+  eec_trainer tmp = *tr_in;
+  if (set_geometry(&tmp, B, T)) return 0;
+  read_ffn_switches(tmp);
+  return model_workspace(model_plan(tmp));
+}
+
+int eec_train_forward(eec_trainer* tr, const eec_params* params, const float* mel, const int64_t* lengths, int B, int T, int passes,
+                      float drop_prob, uint64_t seed, float* out, float* taps, float* bn_batch_stats, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  if (!tr || !params || !mel || !lengths || !out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return tfail(EEC_ERR_BAD_ARG, "no current HIP device");
+  if (tr->device < 0) tr->device = dev;
+  if (dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
+  if (int rc = set_geometry(tr, B, T)) return rc;
+  tr->np = passes, tr->p = drop_prob, tr->seed = seed, tr->recorded = false;
+  read_ffn_switches(*tr);
+  const Sizes z = model_plan(*tr);
+  if (workspace_bytes < model_workspace(z)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
+  tr->tape_bytes = up256(z.tape);
+  Run r{tr, false, (hipStream_t)stream};
+  r.tape.base = (char*)workspace, r.tape.cap = tr->tape_bytes;
+  r.scr.base = (char*)workspace + tr->tape_bytes, r.scr.cap = workspace_bytes - tr->tape_bytes;
+  forward(r, params, mel, lengths, out, bn_batch_stats, taps);
+  if (int rc = finish(r)) return rc;
+  tr->recorded = true;
+  return 0;
+}
+
+int eec_train_backward(eec_trainer* tr, const eec_params* params, const eec_params* grads, const float* out, const float* grad_out,
+                       const float* grad_taps, void* workspace, size_t workspace_bytes, void* stream) {
+  return eec_train_backward_ex(tr, params, grads, out, grad_out, grad_taps, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+int eec_train_backward_ex(eec_trainer* tr, const eec_params* params, const eec_params* grads, const float* out, const float* grad_out,
+                          const float* grad_taps, void* workspace, size_t workspace_bytes, void* stream, eec_group_done_fn on_group,
+                          void* user) {
+  if (!tr || !params || !grads || !out || !grad_out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (!tr->recorded) return tfail(EEC_ERR_BAD_ARG, "no recorded forward (eec_train_forward first, same workspace)");
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
+  read_ffn_switches(*tr);
+  const Sizes z = model_plan(*tr);
+  if (workspace_bytes < model_workspace(z)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
+  const char* no_side = getenv("EEC_TRAIN_NO_SIDE");  // diagnostic: every job on the main stream (results are bit-identical)
+  const bool use_side = !(no_side && no_side[0] == '1');
+  if (use_side && !tr->side) {  // a failure here only means the jobs run on the main stream
+    if (hipStreamCreateWithFlags(&tr->side, hipStreamNonBlocking) != hipSuccess) tr->side = nullptr;
+    if (tr->side && (hipEventCreateWithFlags(&tr->ev_main, hipEventDisableTiming) != hipSuccess ||
+                     hipEventCreateWithFlags(&tr->ev_side, hipEventDisableTiming) != hipSuccess)) {
+      (void)hipStreamDestroy(tr->side);
+      tr->side = nullptr;
+    }
+  }
+  Run r{tr, false, (hipStream_t)stream};
+  if (use_side) r.side = tr->side;
+  // [tape][dx][side-stream scratch][main scratch]; the residual-stream gradient is carved through `tape`, kept for the whole backward
+  const size_t dx_bytes = up256(z.dx + 256), side_bytes = up256(z.side);
+  char* base = (char*)workspace + tr->tape_bytes;
+  r.tape.base = base, r.tape.cap = dx_bytes;
+  r.sscr.base = base + dx_bytes, r.sscr.cap = side_bytes;
+  r.scr.base = base + dx_bytes + side_bytes, r.scr.cap = workspace_bytes - tr->tape_bytes - dx_bytes - side_bytes;
+  backward(r, params, grads, out, grad_out, grad_taps, on_group, user);
+  return finish(r);
+}
+
 size_t eec_train_group_workspace_bytes(const eec_config* cfg, int n_layers, int B, int Tq) {
   eec_trainer tmp;
   if (n_layers <= 0 || n_layers > 64 || block_trainer(tmp, cfg, B, Tq, 3, 0.0f, 0, nullptr)) return 0;
-  return group_sizes(tmp, n_layers).total();
+  return group_workspace(group_plan(tmp, n_layers));
 }
 
 int eec_train_group_forward(const eec_config* cfg, const eec_layer_params* layers, int n_layers, const float* x_in, const int32_t* key_len, int B,
@@ -924,12 +854,13 @@ int eec_train_group_forward(const eec_config* cfg, const eec_layer_params* layer
   if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, Tq, passes, drop_prob, seed, key_len)) return rc;
-  const BlockSizes z = group_sizes(tr, n_layers);
-  if (workspace_bytes < z.total()) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const Sizes z = group_plan(tr, n_layers);
+  if (workspace_bytes < group_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const size_t tape = up256(z.tape);
   Run r{&tr, false, (hipStream_t)stream};
   r.site = site_base;
-  r.tape.base = (char*)workspace, r.tape.cap = z.tape;
-  r.scr.base = (char*)workspace + z.tape, r.scr.cap = workspace_bytes - z.tape;
+  r.tape.base = (char*)workspace, r.tape.cap = tape;
+  r.scr.base = (char*)workspace + tape, r.scr.cap = workspace_bytes - tape;
   group_forward(r, layers, n_layers, x_in, x_out, bn_batch_stats);
   return finish(r);
 }
@@ -942,19 +873,20 @@ int eec_train_group_backward(const eec_config* cfg, const eec_layer_params* laye
   if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, Tq, passes, drop_prob, seed, key_len)) return rc;
-  const BlockSizes z = group_sizes(tr, n_layers);
-  if (workspace_bytes < z.total()) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const Sizes z = group_plan(tr, n_layers);
+  if (workspace_bytes < group_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
   {  // the recorded tape's pointers: the forward's carve again, without launches
     Run d{&tr, true, nullptr};
     d.site = site_base;
     d.tape.base = (char*)workspace;
     group_forward(d, layers, n_layers, x_in, nullptr, nullptr);
   }
+  const size_t tape = up256(z.tape), dx = up256(z.dx), side = up256(z.side);
   Run r{&tr, false, (hipStream_t)stream};
-  char* base = (char*)workspace + z.tape;
-  r.tape.base = base, r.tape.cap = z.bwd_tape;
-  r.sscr.base = base + z.bwd_tape, r.sscr.cap = z.side;
-  r.scr.base = base + z.bwd_tape + z.side, r.scr.cap = workspace_bytes - z.tape - z.bwd_tape - z.side;
+  char* base = (char*)workspace + tape;
+  r.tape.base = base, r.tape.cap = dx;
+  r.sscr.base = base + dx, r.sscr.cap = side;
+  r.scr.base = base + dx + side, r.scr.cap = workspace_bytes - tape - dx - side;
   group_backward(r, layers, grads, n_layers, grad_out, grad_in);
   return finish(r);
 }
@@ -963,8 +895,7 @@ size_t eec_train_stem_workspace_bytes(const eec_config* cfg, int B, int T, int t
   StemGeo g;
   eec_trainer tmp;
   if (stem_geo(g, cfg, B, T, two_convs) || block_trainer(tmp, cfg, B, g.To, 3, 0.0f, 0, nullptr)) return 0;
-  const StemSizes z = stem_sizes(tmp, g);
-  return z.tape + z.scr + z.side + 1024;
+  return stem_workspace(stem_plan(tmp, g)) + 1024;
 }
 
 int eec_train_stem_forward(const eec_config* cfg, const float* sub0_w, const float* sub0_b, const float* sub1_w, const float* sub1_b,
@@ -976,12 +907,13 @@ int eec_train_stem_forward(const eec_config* cfg, const float* sub0_w, const flo
   if (int rc = stem_geo(g, cfg, B, T, sub1_w != nullptr)) return rc;
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, g.To, passes, drop_prob, seed, nullptr)) return rc;
-  const StemSizes z = stem_sizes(tr, g);
-  if (workspace_bytes < z.tape + z.scr + z.side) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const Sizes z = stem_plan(tr, g);
+  if (workspace_bytes < stem_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const size_t tape = up256(z.tape);
   Run r{&tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace, r.tape.cap = z.tape;
-  r.scr.base = (char*)workspace + z.tape, r.scr.cap = workspace_bytes - z.tape;
-  stem_forward(r, g, sub0_w, sub0_b, sub1_w, sub1_b, pe, mel, x_out, site);
+  r.tape.base = (char*)workspace, r.tape.cap = tape;
+  r.scr.base = (char*)workspace + tape, r.scr.cap = workspace_bytes - tape;
+  stem_forward(r, g, stem_carve(r.tape, g), sub0_w, sub0_b, sub1_w, sub1_b, pe, mel, x_out, site);
   return finish(r);
 }
 
@@ -994,47 +926,44 @@ int eec_train_stem_backward(const eec_config* cfg, int two_convs, int B, int T, 
   if (int rc = stem_geo(g, cfg, B, T, two_convs)) return rc;
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, g.To, passes, drop_prob, seed, nullptr)) return rc;
-  const StemSizes z = stem_sizes(tr, g);
-  if (workspace_bytes < z.tape + z.scr + z.side) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const Sizes z = stem_plan(tr, g);
+  if (workspace_bytes < stem_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  const size_t tape = up256(z.tape), side = up256(z.side);
   Run r{&tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace, r.tape.cap = z.tape;
-  r.sscr.base = (char*)workspace + z.tape, r.sscr.cap = z.side;
-  r.scr.base = (char*)workspace + z.tape + z.side, r.scr.cap = workspace_bytes - z.tape - z.side;
-  stem_backward(r, g, grad_x, g_sub0_w, g_sub0_b, g_sub1_w, g_sub1_b, site);
+  r.tape.base = (char*)workspace, r.tape.cap = tape;
+  r.sscr.base = (char*)workspace + tape, r.sscr.cap = side;
+  r.scr.base = (char*)workspace + tape + side, r.scr.cap = workspace_bytes - tape - side;
+  stem_backward(r, g, stem_carve(r.tape, g), grad_x, g_sub0_w, g_sub0_b, g_sub1_w, g_sub1_b, site);
   return finish(r);
 }
 
 /* exit head: logp = log_softmax(x . W^T + b); scratch = M * V floats */
 int eec_train_head_forward(const float* x, const float* W, const float* b, int M, int V, int D, int passes, float* logp, float* scratch, void* stream) {
   if (!x || !W || !b || !logp || !scratch || M <= 0 || V <= 0 || D <= 0 || (passes != 1 && passes != 3)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  GemmArgs g = gemm_args(x, D, 1, W, D, 1, scratch, V, M, V, D);
-  g.bias = b;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipError_t e = launch_gemm(g, passes, st); e != hipSuccess) return tfail((int)e, hipGetErrorString(e));
-  if (hipError_t e = launch_logsoftmax_fwd(scratch, logp, M, V, st); e != hipSuccess) return tfail((int)e, hipGetErrorString(e));
-  return 0;
+  eec_trainer tr{};
+  tr.np = passes;
+  Run r{&tr, false, (hipStream_t)stream};
+  r.scr.base = (char*)scratch;
+  head_fwd(r, x, W, b, logp, M, V, D);
+  return finish(r);
 }
 /* dx (optional) = dlogits . W, dW = dlogits^T . x, db = column sums of dlogits, with dlogits = grad_logp - exp(logp) * rowsum(grad_logp);
- * scratch: eec_train_head_backward_scratch_floats(M, V, D) floats */
+ * scratch: eec_train_head_backward_scratch_floats(M, V, D) floats: dlogits, then the weight gradient's split-K partials */
 size_t eec_train_head_backward_scratch_floats(int M, int V, int D) {
   if (M <= 0 || V <= 0 || D <= 0) return 0;
-  eec_trainer tmp;
-  Run d{&tmp, true, nullptr};
-  linear_bwd_weight(d, nullptr, nullptr, nullptr, nullptr, M, V, D);
-  return (size_t)M * V + 64 + d.sscr.peak / sizeof(float) + 64;
+  const Sizes z = plan(eec_trainer{}, [](Run&) {}, [&](Run& r) { head_bwd(r, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, M, V, D); });
+  return (size_t)M * V + 64 + z.side / sizeof(float) + 64;
 }
 int eec_train_head_backward(const float* x, const float* W, const float* logp, const float* grad_logp, int M, int V, int D, int passes, float* dx,
                             float* dW, float* db, float* scratch, void* stream) {
   if (!x || !W || !logp || !grad_logp || !dW || !db || !scratch || M <= 0 || D <= 0 || (passes != 1 && passes != 3)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
   if (V <= 0 || V > 256 || V % 4) return tfail(EEC_ERR_UNSUPPORTED, "the log-softmax backward needs vocab <= 256, a multiple of 4");
-  eec_trainer tr;
+  eec_trainer tr{};
   tr.np = passes;
   Run r{&tr, false, (hipStream_t)stream};
-  float* dlogits = scratch;
+  r.scr.base = (char*)scratch;
   r.sscr.base = (char*)(scratch + (((size_t)M * V + 63) / 64) * 64);
-  RUN(eec::launch_logsoftmax_backward(logp, grad_logp, M, V, dlogits, r.st));
-  linear_bwd_weight(r, dlogits, x, dW, db, M, V, D);
-  if (dx) linear_bwd_data(r, dlogits, W, dx, M, V, D);
+  head_bwd(r, x, W, logp, grad_logp, dx, false, dW, db, M, V, D);
   return finish(r);
 }
 

@@ -452,6 +452,42 @@ def test_fused_feed_forward_equals_the_gemm_path_at_the_benchmark_shape():
     compare_grads(g_m, g_g, 2e-3, "fused forward + GEMM-path backward vs GEMM path")
 
 
+def test_group_backward_reads_the_tape_whatever_the_feed_forward_switch_says():
+    """The block entries keep no state: eec_train_group_backward finds the recorded tape by carving the forward's layout again.  That
+    layout is a function of the geometry alone, so EEC_TRAIN_FFN_FUSED=0 set between a Splitformer's forward (fused feed-forward
+    launches) and its loss.backward() must not move what the backward reads: every gradient matches a step run wholly under the
+    default setting."""
+    import os
+    kw = base_kwargs(d_model=256, n_head=8, d_feed_forward=512, n_enc_exits=2, n_enc_layers=1, drop_prob=0.1)
+    ref = R.SplitformerRef(**kw)
+    sd = synth.synth_state_dict(ref.state_dict(), seed=61, style="trained")
+    gpu = Splitformer(**{**kw, "device": "cuda"})
+    gpu.load_state_dict(sd, strict=True)
+    gpu = gpu.cuda().train()
+    B, T = 3, 259
+    mel, lens = synth.synth_mel(B, 80, T, seed=61).cuda(), torch.tensor([259, 200, 131])
+    tgt, tl = synth.synth_targets(B, 5, kw["dec_voc_size"], seed=61)
+
+    def step(backward_env):
+        torch.manual_seed(5)
+        gpu.zero_grad()
+        out = gpu(mel, lens)
+        loss = exit_ctc_losses(out, tgt, tl).sum()
+        os.environ.update(backward_env)
+        loss.backward()
+        return out.detach().cpu(), {n: p.grad.detach().cpu().double() for n, p in gpu.named_parameters()}
+
+    saved = os.environ.get("EEC_TRAIN_FFN_FUSED")
+    try:
+        os.environ.pop("EEC_TRAIN_FFN_FUSED", None)
+        o_d, g_d = step({})
+        o_s, g_s = step({"EEC_TRAIN_FFN_FUSED": "0"})
+    finally:
+        os.environ.pop("EEC_TRAIN_FFN_FUSED", None) if saved is None else os.environ.__setitem__("EEC_TRAIN_FFN_FUSED", saved)
+    assert torch.isfinite(o_d).all() and torch.equal(o_s, o_d)
+    compare_grads(g_s, g_d, 2e-3, "switch flipped between forward and backward vs default")
+
+
 def test_train_mode_without_autograd_keeps_train_semantics():
     """model.train() under torch.no_grad() (the reference would still use batch statistics and dropout): same output as the
     autograd forward with the same seed, different from eval mode."""
