@@ -10,6 +10,8 @@ serve without torchaudio.
   ``eec_encoder_forward`` with taps) where the reference re-runs the first n exit groups for every n
   (inference.py:44-46: O(E^2) groups per utterance), and the decoder advances step-wise over a key / value cache
   (``model.decoder_session``, csrc/decoder_step.hip) where the reference re-runs it on the whole prefix per step.
+* ``BeamInference.decode_batch``  inference.py:18-62 (evaluate_batch_ae) for a whole padded batch: the encoder once per
+  batch, then the searches of every exit and utterance in lockstep (``beam_search_batch``, csrc/decoder_batch.hip).
 """
 from __future__ import annotations
 
@@ -209,3 +211,70 @@ class BeamInference:
         best = scores.argmax(dim=1).tolist()
         tokens_h = tokens.cpu()
         return [(list(tokens[e]), list(scores[e]), tokens_h[e, best[e]].tolist()) for e in range(n)]
+
+    @torch.no_grad()
+    def beam_search_batch(self, model, taps, layer_ns: Sequence[int], vocab_size: Optional[int] = None, max_length: int = 500,
+                          min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
+                          PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None):
+        """``beam_search_exits`` for every utterance of a padded batch at once: ``taps`` [E, B, T', D] (or E tensors [B, T', D]),
+        exit ``layer_ns[e]``'s encoder output of every utterance.  The E * B searches are independent and run in lockstep through
+        one ``model.decoder_batch_session`` (every decoder launch covers all of them) and one ``eec_beam_select`` per step.
+        Returns ``out[b][e] = (final_tokens, final_scores, best_tokens)``, what ``beam_search`` returns for utterance b and exit
+        ``layer_ns[e]`` -- or None where ``beam_search_exits`` declines: EOS could finalise beams (``max_length - 1 >
+        min_length``), or no batch session for this model / geometry / device."""
+        V = self._arg(vocab_size, "dec_voc_size")
+        sos = self._arg(SOS_token, "trg_sos_idx")
+        self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")
+        beam = self._arg(beam_size, "beam_size")
+        alpha = self._arg(pen_alpha, "pen_alpha")
+        if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
+            return None
+        session = model.decoder_batch_session(taps, layer_ns, max_length)
+        if session is None or beam > session.max_beams:
+            return None
+        E, B, dev = session.E, session.B, session.dev
+        n = E * B  # search i = e * B + b
+        scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+        bufs = [torch.zeros((n, beam, max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
+        bufs[0][:, 0, 0] = sos
+        last = bufs[0][:, :1, 0].contiguous()
+        parent: Optional[Tensor] = None
+        for i in range(max_length):
+            logp = session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1))
+            scores, parent, last = beam_select(logp.view(n, -1, V), scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1],
+                                               bufs[(i + 1) & 1], i + 1)
+        tokens = bufs[max_length & 1]
+        best = scores.argmax(dim=1).tolist()
+        tokens_h = tokens.cpu()
+        return [[(list(tokens[e * B + b]), list(scores[e * B + b]), tokens_h[e * B + b, best[e * B + b]].tolist()) for e in range(E)]
+                for b in range(B)]
+
+    @torch.no_grad()
+    def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
+                     max_batch: Optional[int] = None, **kw) -> List[List[List[int]]]:
+        """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
+        utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
+        ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
+        lockstep.  Where the batched search declines, every utterance goes through ``decode_all_exits``, so the result is
+        always the reference's."""
+        T = spec.size(2)
+        if max_length is None:  # inference.py:31-39: one length for the whole padded batch
+            max_length = int(30 - T * 5 / 200) if T < 200 else int(T / 12)
+        E = model._cfg.n_exits
+        exits = list(range(1, E + 1))
+        valid_len = valid_len.reshape(-1)
+        step = max_batch or spec.size(0)
+        out: List[List[List[int]]] = []
+        for c0 in range(0, spec.size(0), step):
+            sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
+            together = None
+            if kw.get("kv_cache", True):
+                taps = model._run_encoder(sp, vl, want_out=False, want_taps=True, n_groups=E)[1]
+                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size,
+                                                  **{k: v for k, v in kw.items() if k != "kv_cache"})
+                del taps
+            if together is None:
+                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, **kw) for b in range(sp.size(0))]
+            else:
+                out += [[best for _, _, best in row] for row in together]
+        return out

@@ -490,6 +490,11 @@ bool geometry_ok(int d_model, int n_heads, int d_ff, int vocab, int n_layers, in
 
 }  // namespace
 
+namespace eec {
+// the batched step decoder (decoder_batch.hip) reports through eec_decoder_step_last_error() as well
+int decoder_step_fail(int code, const char* msg) { return sfail(code, msg); }
+}  // namespace eec
+
 extern "C" {
 
 const char* eec_decoder_step_last_error(void) { return g_serr.c_str(); }

@@ -1306,6 +1306,64 @@ class DecoderSessionGroup:
         return out
 
 
+class DecoderBatchSession:
+    """Step-wise AED decoding of E exits x B utterances of a padded batch in lockstep, one cache for all of them
+    (include/eec.h, eec_decoder_batch_begin / eec_decoder_batch_step): ``step(tokens [E, B, R], parent [E, B, R] | None)`` ->
+    log-probs [E, B, R, V].  The launches of a step do not depend on E or B (csrc/decoder_batch.hip)."""
+
+    def __init__(self, model, ps_list, d_ff: int, V: int, taps: Tensor, max_steps: int, nbytes: int):
+        lib = capi.load()
+        self.model, self.d_ff, self.V, self.max_steps, self.nbytes = model, d_ff, V, max_steps, nbytes
+        self.E, self.B, self.Tq = taps.size(0), taps.size(1), taps.size(2)
+        self.dev = taps.device
+        self.s, self.rows = 0, 0
+        self.max_beams = lib.eec_decoder_step_max_beams()
+        self._ps_keep = ps_list
+        self.ps = (C.POINTER(capi.EecDecoderParams) * self.E)(*[C.pointer(p) for p in ps_list])
+        cfg = model._cfg
+        with torch.cuda.device(self.dev):
+            self.cache = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
+            self.ptr = (self.cache.data_ptr() + 255) // 256 * 256
+            taps_c = taps.contiguous().float()
+            stream = torch.cuda.current_stream(self.dev)
+            rc = lib.eec_decoder_batch_begin(self.ps, self.E, self.B, cfg.d_model, cfg.n_heads, d_ff, V, taps_c.data_ptr(), self.Tq, max_steps,
+                                             int(model.decoder_passes), self.ptr, nbytes, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"eec_decoder_batch_begin failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
+            taps_c.record_stream(stream)
+            self.cache.record_stream(stream)
+
+    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None) -> Tensor:
+        lib = capi.load()
+        cfg = self.model._cfg
+        E, B = self.E, self.B
+        if last_tokens.dim() != 3 or tuple(last_tokens.shape[:2]) != (E, B):
+            raise ValueError(f"last_tokens must be [{E}, {B}, live beams]")
+        R = int(last_tokens.size(2))
+        if not 1 <= R <= self.max_beams:
+            raise ValueError(f"1 .. {self.max_beams} live beams per utterance, got {R}")
+        if self.s >= self.max_steps:
+            raise RuntimeError(f"the session was opened for {self.max_steps} steps")
+        if parent is not None and tuple(parent.shape) != (E, B, R):
+            raise ValueError("parent: one row of the previous step per live beam, exit and utterance")
+        with torch.cuda.device(self.dev):
+            tok = last_tokens.to(device=self.dev, dtype=torch.int64).contiguous()
+            par = parent.to(device=self.dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            out = torch.empty((E, B, R, self.V), dtype=torch.float32, device=self.dev)
+            stream = torch.cuda.current_stream(self.dev)
+            rc = lib.eec_decoder_batch_step(self.ps, E, B, cfg.d_model, cfg.n_heads, self.d_ff, self.V, int(self.model.trg_pad_idx), tok.data_ptr(),
+                                            par.data_ptr() if par is not None else None, R, self.rows, self.s, self.Tq, self.max_steps,
+                                            out.data_ptr(), self.ptr, self.nbytes, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"eec_decoder_batch_step failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
+            tok.record_stream(stream)
+            if par is not None:
+                par.record_stream(stream)
+        self.s += 1
+        self.rows = R
+        return out
+
+
 class _DecoderTrainFn(torch.autograd.Function):
     """Exit ``idx``'s attention decoder in train mode and its backward on the HIP training kernels (eec_decoder_train_forward /
     _backward): ``linears_2[idx](decoders[idx](positional_encoder_2(emb(trg)), enc, causal + padding masks))`` -> raw logits
@@ -1538,6 +1596,32 @@ class full_conformer(_HipEncoderMixin, nn.Module):
         if any(s is None for s in sessions):
             return None
         return DecoderSessionGroup(sessions)
+
+    def decoder_batch_session(self, taps, layer_ns: Sequence[int], max_steps: int) -> Optional["DecoderBatchSession"]:
+        """Step-wise decoding of exits ``layer_ns`` for every utterance of a padded batch in lockstep (csrc/decoder_batch.hip):
+        ``taps`` [E, B, T', D] (or E tensors [B, T', D]) holds exit ``layer_ns[e]``'s encoder output of every utterance,
+        ``max_steps`` the longest prefix that will be decoded.  None when this geometry or device is not served."""
+        if isinstance(taps, (list, tuple)):
+            if not taps:
+                return None
+            taps = torch.stack(list(taps))
+        if taps.dim() != 4 or taps.size(0) != len(layer_ns) or not taps.is_cuda or (self.training and torch.is_grad_enabled()):
+            return None
+        if max_steps < 1 or max_steps > self.positional_encoder_2.pe.size(0) or taps.size(3) != self._cfg.d_model:
+            return None
+        idxs = [(int(n) if 1 <= int(n) <= self._cfg.n_exits else self._cfg.n_exits) - 1 for n in layer_ns]
+        params = [self._decoder_params(i, taps.device) for i in idxs]
+        d_ff, V = params[0][1], params[0][2]
+        n_layers = len(self.decoders[idxs[0]].layers)
+        if any((p[1], p[2], len(self.decoders[i].layers)) != (d_ff, V, n_layers) for p, i in zip(params, idxs)):
+            return None
+        lib = capi.load()
+        cfg = self._cfg
+        nbytes = lib.eec_decoder_batch_cache_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, taps.size(0), taps.size(1), int(max_steps),
+                                                   taps.size(2))
+        if nbytes == 0:
+            return None
+        return DecoderBatchSession(self, [p[0] for p in params], d_ff, V, taps, int(max_steps), nbytes)
 
     def _decoder_(self, trg: Tensor, enc: Tensor, layer_n: int) -> Tensor:
         idx = (int(layer_n) if 1 <= int(layer_n) <= self._cfg.n_exits else self._cfg.n_exits) - 1

@@ -415,6 +415,24 @@ int eec_decoder_step(const eec_decoder_params* p, int d_model, int n_heads, int 
 int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_model, int n_heads, int d_ff, int vocab, int pad_idx,
                            const int64_t* last_tokens, const int64_t* parent, int R, int R_prev, int s, int Tq, int S_max, int log_softmax,
                            float* out, void* const* caches, size_t cache_bytes, void* stream);
+/* ---- Batched step-wise AED decoding (csrc/decoder_batch.hip) ----------------------------------------------------------------
+ * The step above for every exit AND every utterance of a padded batch at once: E <= 8 exits x B utterances, R <= 16 live beams per
+ * utterance, one cache (eec_decoder_batch_cache_bytes) for all of them.  The launches of a step do not depend on E or B: each linear
+ * is one GEMM over the B * R rows of every exit (f16x3 MFMA operands, ~2^-21 relative per product), the cross-attention reads an
+ * utterance's memory once for all of its beams.  The search's bookkeeping is eec_beam_select with n = E * B.
+ *   eec_decoder_batch_begin(ps, E, B, ..., taps [E][B][Tq][D], Tq, S_max, passes, cache, bytes, stream)
+ *   eec_decoder_batch_step (ps, E, B, ..., pad_idx, last_tokens [E][B][R], parent [E][B][R] | NULL, R, R_prev, s, Tq, S_max,
+ *                           out [E][B][R][V], cache, bytes, stream)
+ * ps: HOST array of E pointers (exit e's decoder; one geometry).  Every utterance has the full padded Tq memory frames (no memory
+ * mask, as the reference's per-utterance search).  Step semantics as eec_decoder_step; out holds log-probs.  The cache size is
+ * host arithmetic: 0 for geometries eec_decoder_cache_bytes does not serve, or E outside 1 .. 8.  Errors through
+ * eec_decoder_step_last_error(); arguments are checked before any device call. */
+size_t eec_decoder_batch_cache_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int E, int B, int S_max, int Tq);
+int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, int d_model, int n_heads, int d_ff, int vocab, const float* taps,
+                            int Tq, int S_max, int passes, void* cache, size_t cache_bytes, void* stream);
+int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, int d_model, int n_heads, int d_ff, int vocab, int pad_idx,
+                           const int64_t* last_tokens, const int64_t* parent, int R, int R_prev, int s, int Tq, int S_max, float* out, void* cache,
+                           size_t cache_bytes, void* stream);
 /* The bookkeeping of one beam-search step (util/beam_infer.py:241-262) for n searches in lockstep, one launch: over the R live beams'
  * V next-token log-probs, cand = scores_in[r] + logp[r][v] / penalty; the K best, best first (ties: the lower r * V + v) ->
  * scores_out [n][K], parent [n][K] (= index / V), tok [n][K] (= index % V); tokens_new[i][b][0 .. len] = tokens_old[i][parent][0 .. len)
