@@ -8,9 +8,11 @@ generator.  One step = one ``Early_conformer.forward`` through the drop-in nn.Mo
 layers -> 6 CTC heads -> [6, 64, 256, 256] fp32 log-probs resident in HBM) followed by the fused
 per-exit CTC loss (one launch for all 6 x 64 lattices; reference train.py:53-65) and, for N > 1, the
 RCCL all-reduce of the 6 per-exit losses -- the only exchange of the batch-sharded path.  The same
-work runs at every N (weak scaling); ``forward_only`` reports the encoder forward alone at N = 1.
+work runs at every N (weak scaling).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the record; nothing else.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the per-exit losses
 (``exit_losses.npy``, [6] fp32) and the log-probs of a fixed, seeded sample of the batch's utterances
@@ -22,13 +24,16 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started plai
 launcher: it starts the N rank processes itself BEFORE touching the GPU (it never initialises HIP), relays rank 0's JSON
 line and exits non-zero if any rank fails.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Extra objects:
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step), its configuration
+and what follows from its timing alone.  Extra objects, measured under --full only:
+  forward_only the encoder forward alone (N=1)
   roofline     dominant kernel (fused row-tile chain: conv tail + feed-forward stages + in_proj): algorithmic flop per launch / mean launch
                duration from HIP events on the launch stream, vs the 2.5 PFLOP/s dense 16-bit MFMA peak
   cpu_baseline the CPU oracle (oracle/conformer_ref.py, a port of the reference path) timed on
                this box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
   modes        the same step in the faster, lower-precision operand modes (not the headline value)
   secondary_shapes  forward-only at SURVEY 8d's secondary shapes: ragged lengths, T=2051 (T'=512)
+  also         kernel_time, parity, step_ms, config3, frontend, aed_decode and train_step
 """
 import argparse
 import json
@@ -138,13 +143,14 @@ class RecordGuard:
         self.rank, self.line = rank, line
         self._lock, self._emitted, self._done = threading.Lock(), False, threading.Event()
 
-    def emit(self, train_obj):
+    def emit(self, train_obj=None):
         with self._lock:  # whichever of the main thread and the watchdog gets here first
             if self._emitted:
                 return
             self._emitted = True
             if self.rank == 0 and self.line is not None:
-                self.line["train_step"] = train_obj
+                if train_obj is not None:  # None: the section did not run (plain run, --no-train)
+                    self.line["train_step"] = train_obj
                 _RECORD_OUT.write(json.dumps(self.line) + "\n")
                 _RECORD_OUT.flush()
 
@@ -172,7 +178,8 @@ class RecordGuard:
 
 def plumbing_check(args, rank, world):
     """EEC_BENCH_PLUMBING=1 (host tests, no GPU): the N > 1 control flow only -- rendezvous, barrier, the loss all-reduce
-    through parallel.combine_exit_losses, max-over-ranks timing, rank 0's one JSON line -- over gloo on CPU tensors."""
+    through parallel.combine_exit_losses, max-over-ranks timing, rank 0's one JSON line and, under --full, the guarded last
+    section -- over gloo on CPU tensors."""
     import torch.distributed as dist
     from early_exit_transformer_amd import parallel
     if os.environ.get("EEC_BENCH_FAIL_RANK") == str(rank):
@@ -189,22 +196,23 @@ def plumbing_check(args, rank, world):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     line = {"plumbing": True, "n_gpus": world, "steps": args.steps, "combined": combined.tolist(),
             "max_rank_seconds": float(dt.item())} if rank == 0 else None
-    # the guarded last section, as in the real run: EEC_BENCH_FAIL_STEP_RANK makes that rank fail INSIDE a step, i.e. before
-    # the step's collectives, which its peers then wait in for ever -- until the launcher has seen the non-zero status
+    # the guarded last section, as in the real run (--full only): EEC_BENCH_FAIL_STEP_RANK makes that rank fail INSIDE a step,
+    # i.e. before the step's collectives, which its peers then wait in for ever -- until the launcher has seen the non-zero status
     guard = RecordGuard(rank, line)
-    guard.start_watchdog(float(os.environ.get("EEC_BENCH_TRAIN_TIMEOUT", "240")))
     guard.catch_sigterm()
-    try:
-        if os.environ.get("EEC_BENCH_FAIL_STEP_RANK") == str(rank):
-            raise RuntimeError("injected failure inside a training step")
-        if world > 1 and os.environ.get("EEC_BENCH_FAIL_STEP_RANK") is not None:
-            dist.all_reduce(torch.zeros(1))  # the collective of a step the failed rank never reaches
-    except Exception as e:
-        if world > 1:
-            guard.fail(f"{type(e).__name__}: {e}", 4)
-        raise
+    if args.full:
+        guard.start_watchdog(float(os.environ.get("EEC_BENCH_TRAIN_TIMEOUT", "240")))
+        try:
+            if os.environ.get("EEC_BENCH_FAIL_STEP_RANK") == str(rank):
+                raise RuntimeError("injected failure inside a training step")
+            if world > 1 and os.environ.get("EEC_BENCH_FAIL_STEP_RANK") is not None:
+                dist.all_reduce(torch.zeros(1))  # the collective of a step the failed rank never reaches
+        except Exception as e:
+            if world > 1:
+                guard.fail(f"{type(e).__name__}: {e}", 4)
+            raise
     guard.finish()
-    guard.emit("ok")
+    guard.emit("ok" if args.full else None)
     if world > 1:
         dist.destroy_process_group()
     return 0
@@ -240,9 +248,11 @@ def main():
     # default = the mode whose log-probs stay within the north-star 1e-3 (flat) on every committed fixture, trained-like (peaky)
     # outputs included; "f16f8" (fp8 correction products) is the faster opt-in that keeps 1e-3 on near-uniform outputs only
     ap.add_argument("--precision", default="f16x3", choices=["f16f8", "f16x3", "mixed", "f16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step secondary lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure (roofline, parity, other modes and shapes, CPU baseline, training step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true", help="with --full: skip the other modes, shapes and geometries and the training step")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training-step secondary lines")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
@@ -349,9 +359,15 @@ def main():
     value = world * B * T * args.steps / dt
     flop_fwd, Tq = flops_per_forward(B, T)
 
+    # A plain run ends here: the record below carries the headline and what follows from its timing alone.  Every other figure
+    # -- per-kernel times and the roofline, parity against the fixtures, other modes, shapes and geometries, the CPU baseline,
+    # the training step -- takes runs of its own and is measured under --full only.
+    full0 = args.full and rank == 0
+    solo = full0 and world == 1
+
     # ---- roofline of the dominant kernel (the fused chain), HIP events on the launch stream ----
     roofline, kernel_ms = None, None
-    if rank == 0:
+    if full0:
         model.set_profiling(True)
         run_steps(max(3, min(args.steps, 10)), with_loss=False)  # forward only: no collective outside the timed region
         torch.cuda.synchronize()
@@ -386,7 +402,7 @@ def main():
                      for k, v in prof.items()}
 
     forward_only = None
-    if rank == 0 and world == 1:
+    if solo:
         run_steps(3, with_loss=False)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -399,7 +415,7 @@ def main():
     # build container, make_golden.py), measured in this run for the mode that is timed: the default 12-layer model on
     # B = 4, T = 1027 with random-init heads (near-uniform outputs) and with heads x8 (peaky, trained-like outputs) ----
     parity = None
-    if rank == 0 and world == 1:
+    if solo:
         import numpy as np
         parity = {"policy": "the default mode f16x3 is held to the north-star tolerance FLAT (|dlogp| <= 1e-3 on every fixture, the peaky "
                             "trained-like one included: within_flat_tol).  The opt-in faster modes state a weaker bound, tol * max(1, "
@@ -488,7 +504,7 @@ def main():
 
     # ---- BASELINE.json configs[2] geometry (secondary line): 6 exits x 3 layers, d_model 512, forward + fused exit losses ----
     config3 = None
-    if rank == 0 and world == 1 and not args.no_modes:
+    if solo and not args.no_modes:
         cfg3 = dict(CFG, d_model=512, n_enc_layers=3)
         m3 = Early_conformer(device=dev, **cfg3).eval()
         m3.load_state_dict(synth.synth_state_dict(m3.state_dict(), seed=1, style="init"))
@@ -518,7 +534,7 @@ def main():
     # ---- AED inference (BASELINE.json configs[4] substitute; secondary line): evaluate_batch_ae of inference.py:18-62 for one
     # synthetic utterance -- ONE HIP encoder run for all exits, then beam search (beam 10) per exit with the HIP decoder ----
     aed = None
-    if rank == 0 and world == 1 and not args.no_modes:
+    if solo and not args.no_modes:
         try:
             from early_exit_transformer_amd.beam import BeamInference
             from early_exit_transformer_amd.model import full_conformer
@@ -554,7 +570,7 @@ def main():
 
     # ---- mel front end: waveform -> [B, 80, T] power mel for the same batch (secondary line) ----
     frontend = None
-    if rank == 0 and world == 1 and not args.no_modes:
+    if solo and not args.no_modes:
         from early_exit_transformer_amd.frontend import MelFrontend
         fe = MelFrontend()
         n_samples = (T - 1) * 160  # the waveform length whose front end yields T mel frames
@@ -597,7 +613,7 @@ def main():
 
     # ---- the other operand modes (reported, never the headline) ----
     modes = {}
-    if rank == 0 and world == 1 and not args.no_modes:
+    if solo and not args.no_modes:
         for prec in ("f16f8", "f16x3", "mixed", "f16"):
             if prec == args.precision:
                 continue
@@ -614,7 +630,7 @@ def main():
 
     # ---- per-step distribution (median, p10 / p90): HIP events between consecutive steps of a second pass ----
     step_ms = None
-    if rank == 0 and world == 1:
+    if solo:
         n_ev = min(args.steps, 50)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
         run_steps(2)
@@ -629,7 +645,7 @@ def main():
 
     # ---- secondary shapes: forward-only, same model; reported, never the headline ----
     secondary = {}
-    if rank == 0 and world == 1 and not args.no_modes:
+    if solo and not args.no_modes:
         def timed_forward(mel_s, len_s, n):
             with torch.no_grad():
                 for _ in range(3):
@@ -657,7 +673,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, the FULL batch of this workload ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if solo and not args.no_cpu_baseline:
         from oracle import conformer_ref as R
         ref = R.EarlyConformerRef(device="cpu", **CFG).eval()
         ref.load_state_dict(sd)
@@ -701,14 +717,14 @@ def main():
                        "global_batch": B * world, "mel_frames": T, "parallelism": f"dp{world} (utterance-batch shards)",
                        "precision_mode": args.precision,
                        **({"single_rank_rehearsal": f"every collective of the path issued through a process group of ONE rank on backend {backend!r} (EEC_BENCH_SINGLE_RANK=1)"} if single_rank else {})},
-            "parity": parity,
             "frac_of_mfma_peak_whole_forward": round(flop_fwd * world * args.steps / dt / (MFMA_PEAK_FLOPS * world), 4),
             "algorithmic_flop_per_mel_frame": round(flop_fwd / (B * T), 1),
             "distributed": dist_info,
-            "roofline": roofline, "cpu_baseline": cpu, "forward_only": forward_only, "kernel_time": kernel_ms,
-            "step_ms": step_ms, "modes": modes, "secondary_shapes": secondary, "config3": config3, "frontend": frontend,
-            "train_step": None, "aed_decode": aed,
         }
+        if args.full:
+            line.update({"parity": parity, "roofline": roofline, "cpu_baseline": cpu, "forward_only": forward_only,
+                         "kernel_time": kernel_ms, "step_ms": step_ms, "modes": modes, "secondary_shapes": secondary,
+                         "config3": config3, "frontend": frontend, "train_step": None, "aed_decode": aed})
     else:
         line = None
 
@@ -718,7 +734,7 @@ def main():
     emit, fail_section = guard.emit, guard.fail
 
     guard.catch_sigterm()
-    if not args.no_modes and not args.no_train:
+    if args.full and not args.no_modes and not args.no_train:
         guard.start_watchdog(float(os.environ.get("EEC_BENCH_TRAIN_TIMEOUT", "240")))
         n_tr = max(3, args.steps // 10)
         lab4 = (f"CTC training step, default 12-layer d_model=256, batch {B}/GPU x {world} GPU(s), mel [80 x {T}] "
@@ -776,7 +792,7 @@ def main():
         emit(train if rank == 0 else None)
     else:
         guard.finish()
-        emit(None)
+        emit()
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -408,19 +408,53 @@ def test_bench_launcher_propagates_a_failed_rank():
 def test_bench_rank_failing_inside_a_step_fails_the_job():
     """A rank that raises inside a training step skips collectives its peers wait in.  It must leave with a non-zero status
     (never a record with rc 0): the launcher then terminates the stuck peers and propagates the status; when the failing rank
-    is rank 0 the record is still emitted once, with the error in place of the training-step lines."""
+    is rank 0 the record is still emitted once, with the error in place of the training-step lines.  The training step is a
+    --full section."""
     import json
-    res = _run_bench({"EEC_BENCH_FAIL_STEP_RANK": "1", "EEC_BENCH_TRAIN_TIMEOUT": "60"}, "--gpus", "2", "--steps", "1")
+    res = _run_bench({"EEC_BENCH_FAIL_STEP_RANK": "1", "EEC_BENCH_TRAIN_TIMEOUT": "60"}, "--gpus", "2", "--steps", "1", "--full")
     assert res.returncode == 4, (res.returncode, res.stderr)
     assert "rank 1 exited with status 4" in res.stderr
     # rank 0 was blocked in a collective when the launcher terminated it: its SIGTERM thread still emits the ONE record
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout
     assert "peer rank failed" in json.loads(lines[0])["train_step"]["error"]
-    res = _run_bench({"EEC_BENCH_FAIL_STEP_RANK": "0", "EEC_BENCH_TRAIN_TIMEOUT": "60"}, "--gpus", "2", "--steps", "1")
+    res = _run_bench({"EEC_BENCH_FAIL_STEP_RANK": "0", "EEC_BENCH_TRAIN_TIMEOUT": "60"}, "--gpus", "2", "--steps", "1", "--full")
     assert res.returncode == 4, (res.returncode, res.stderr)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and "injected failure" in json.loads(lines[0])["train_step"]["error"]
+
+
+def test_bench_plain_run_has_no_training_step_section():
+    """Without --full the run ends after the headline: the guarded training-step section is not entered (the injected failure
+    inside a step never fires) and the record carries no train_step."""
+    import json
+    res = _run_bench({"EEC_BENCH_FAIL_STEP_RANK": "1", "EEC_BENCH_TRAIN_TIMEOUT": "60"}, "--gpus", "2", "--steps", "1")
+    assert res.returncode == 0, (res.returncode, res.stderr)
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and "train_step" not in json.loads(lines[0])
+
+
+def test_bench_plain_run_measures_nothing_after_its_steps():
+    """Every figure after the headline's timing is a --full one: from ``solo = ...`` to the record, main() only binds constants
+    and defines helpers, and every section is gated on full0 / solo (or on roofline, which only they set); the training-step
+    section after the record is gated on args.full."""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+    body = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main").body
+
+    def binds(n, name):
+        return isinstance(n, ast.Assign) and any(isinstance(t, ast.Name) and t.id == name for t in n.targets)
+    start = next(i for i, n in enumerate(body) if binds(n, "solo"))
+    end = next(i for i, n in enumerate(body) if isinstance(n, ast.If) and any(binds(s, "line") for s in n.body))
+    assert start < end
+    for n in body[start + 1:end]:
+        if isinstance(n, ast.If):
+            names = {x.id for x in ast.walk(n.test) if isinstance(x, ast.Name)}
+            assert names & {"full0", "solo", "roofline"}, ast.unparse(n.test)
+        elif not isinstance(n, ast.FunctionDef):
+            assert isinstance(n, ast.Assign) and not any(isinstance(x, ast.Call) for x in ast.walk(n)), ast.unparse(n)
+    train = [n for n in body[end:] if isinstance(n, ast.If) and "train_bench" in ast.unparse(n)]
+    assert len(train) == 1 and "args.full" in ast.unparse(train[0].test)
 
 
 def test_bench_hung_section_ends_non_zero():

@@ -2,8 +2,8 @@
 
     python tools/pmc_summary.py <outdir> [grid_size]
 
-grid_size (work-items, e.g. 131072 = 256 workgroups x 512 threads): only dispatches of that size are averaged -- bench.py also
-launches the same kernels on the small parity fixtures (B = 4), which would drag the averages of the headline shape down."""
+grid_size (work-items, e.g. 131072 = 256 workgroups x 512 threads): only dispatches of that size are averaged -- bench.py --full
+also launches the same kernels on the small parity fixtures (B = 4), which would drag the averages of the headline shape down."""
 import csv, glob, sys, collections
 out = sys.argv[1]
 grid = int(sys.argv[2]) if len(sys.argv) > 2 else 0
