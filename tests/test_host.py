@@ -607,17 +607,31 @@ def test_beam_search_equals_the_reference_algorithm(min_length, max_length, beam
 
 def test_named_tensor_index_matches_the_module_tree_walks():
     """model._named_tensors (the cached index the training forward uses) == named_parameters() / state_dict(keep_vars=True): names,
-    order and the very tensors -- also after .to() replaced them and after load_state_dict."""
+    order and the very tensors -- also after .to() replaced them, after load_state_dict, and after submodules were replaced once
+    the index existed (a new exit head for fine-tuning, another BatchNorm in a Conformer layer's convolution module, a head list
+    that grew)."""
     from conftest import base_kwargs
     from early_exit_transformer_amd.model import Early_conformer, full_conformer, _named_tensors
     kw = base_kwargs(n_enc_exits=2, n_enc_layers=1, d_feed_forward=64)
     fkw = {k: v for k, v in kw.items() if k != "src_pad_idx"}
+
+    def matches_the_walks(m):
+        a, b = _named_tensors(m)
+        want_p = list(m.named_parameters())
+        assert [n for n, _ in a] == [n for n, _ in want_p] and all(x is y for (_, x), (_, y) in zip(a, want_p))
+        sd = m.state_dict(keep_vars=True)
+        assert [n for n, _ in b] == list(sd.keys()) and all(t is sd[n] for n, t in b)
+
     for m in (Early_conformer(**kw), full_conformer(trg_pad_idx=126, n_dec_layers=1, **fkw)):
         for _ in range(2):
-            a, b = _named_tensors(m)
-            want_p = list(m.named_parameters())
-            assert [n for n, _ in a] == [n for n, _ in want_p] and all(x is y for (_, x), (_, y) in zip(a, want_p))
-            sd = m.state_dict(keep_vars=True)
-            assert [n for n, _ in b] == list(sd.keys()) and all(t is sd[n] for n, t in b)
+            matches_the_walks(m)
             m = m.double().float()  # replaces every parameter's data and every buffer tensor
             m.load_state_dict(m.state_dict())
+        heads = m.linears if hasattr(m, "linears") else m.linears_1
+        heads[1] = torch.nn.Linear(heads[1].in_features, heads[1].out_features)
+        matches_the_walks(m)
+        conv = m.conformer[1].conformer_layers[0].conv_module
+        conv.sequential[3] = torch.nn.BatchNorm1d(conv.sequential[3].num_features)
+        matches_the_walks(m)
+        heads.append(torch.nn.Linear(heads[0].in_features, heads[0].out_features))
+        matches_the_walks(m)
