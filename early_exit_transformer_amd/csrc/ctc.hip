@@ -12,6 +12,20 @@
 // far") can be 1e60 times more probable than the states that will reach the end -- while the
 // dependent chain per step is 3 DPP lane shifts, a few ldexp, 2 adds and 1 multiply.  The emission
 // log-probs are gathered kCtcAhead steps ahead (their exp is independent of the alpha chain).
+//
+// RANGE.  A lane's states share one exponent and a lane is renormalised every second step, so a state more than 2^-126 below
+// its lane's scale -- two emissions below e^-44 between two renormalisations, an emission below the range of exp, a state far
+// behind its lane's maximum, a lane far below the one it receives from -- leaves the fp32 range and its mass is lost.  Whether
+// that mass mattered cannot be told where it is lost (it does whenever the flushed states carry the only, or the best, way to
+// the end: peaky log-probs with long or improbable targets), so both recursions WATCH for it: a value that is non-zero
+// before a product or an alignment and below kCtcTiny after it is an EVENT at the step's common scale 2^ec, i.e. at most
+// kCtcTiny * 2^ec of probability mass is gone.  Log-probs are <= 0, so what a state's mass can still add to p(target) (its
+// beta') and what a beta' can still meet (its alpha) are probabilities <= 1: all events together take at most
+// N * kCtcTiny * 2^(largest ec) from p(target), N = number of (state, step) pairs.  Where that is below 2^-26 of p(target)
+// the events are harmless (trailing states of a peaky lattice; the usual case); otherwise the lattice is MARKED and run again
+// by ctc_wide_kernel, the same recursion with one exponent per STATE (no range limit, a renormalisation per step; about
+// twice the fast path's time per lattice).  The fast path's own arithmetic is unchanged: the watch is compares only.
+// The bound is sufficient, not sharp: random log-probs with |log-prob| of 10 and more over 256 frames mark most lattices.
 #include <limits.h>
 
 #include "eec_kernels.h"
@@ -20,6 +34,16 @@ namespace eec {
 
 constexpr int kCtcPerLane = 8;  // up to 512 states = target length <= 255
 constexpr int kCtcEmpty = -(1 << 20);  // exponent of a lane that holds no probability mass yet
+constexpr float kCtcTiny = 7.52316385e-37f;  // 2^-120: a non-zero value that falls below it may have lost bits (fp32 normals end at 2^-126)
+// markers of a lattice the fast path gave up on: nll = -inf after ctc_alpha_kernel (replaced by ctc_wide_kernel before the
+// reduction), p(target) slot < 0 for the backward pass
+constexpr float kCtcRedo = -1.f;
+// events at scale 2^ec are harmless when ec <= exponent(p(target)) + ctc_watch_slack: -120 (kCtcTiny) + log2 N + 26 <= 0
+__host__ __device__ inline int ctc_watch_slack(int Tq) {
+  int lg = 0;
+  while (((long long)Tq * 2048) >> lg) ++lg;  // N < Tq * 2048 >= Tq * 4 * 512 states
+  return 120 - 26 - lg;
+}
 
 #define EEC_DPP_F(old, src, ctrl) \
   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (float)(old)), __builtin_bit_cast(int, (float)(src)), ctrl, 0xf, 0xf, false))
@@ -68,12 +92,17 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
     // its gather into s_load + s_waitcnt lgkmcnt(0), which serialises the prefetch ring
     asm volatile("" : "+v"(label[i]));
   }
-  float alpha[P];
+  float alpha[P], lim[P];
   int ex = kCtcEmpty;  // this lane's states are alpha[i] * 2^ex
+  static_assert(P % 2 == 0, "a lane's first state must be a blank");
+  int eloss = kCtcEmpty;  // largest scale at which a non-zero value left the fp32 range (see RANGE above)
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int s = lane * P + i;
-    alpha[i] = (s < 2 && s < L) ? __expf(lp[label[i]]) : 0.f;
+    const float l0 = lp[label[i]];
+    alpha[i] = (s < 2 && s < L) ? __expf(l0) : 0.f;
+    eloss = ((s < 2 && s < L) & (l0 > -INFINITY) & (alpha[i] < kCtcTiny)) ? 0 : eloss;
+    lim[i] = live[i] ? -INFINITY : INFINITY;  // an emission above lim is a finite log-prob of a live state
   }
   if (lane == 0) ex = 0;
   auto store = [&](int t) {
@@ -100,19 +129,27 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
     const int ex_up = EEC_DPP_I(ex, ex, 0x138);
     const int ec = max(ex, ex_up);  // common scale of this step
     const int d_own = max(ex - ec, -200), d_up = max(ex_up - ec, -200);
-    up1 = ldexpf(up1, d_up);
-    up2 = ldexpf(up2, d_up);
+    const float up1s = ldexpf(up1, d_up), up2s = ldexpf(up2, d_up);
+    bool lost = (up1 > 0.f) & (up1s < kCtcTiny);  // up2 is never taken: a lane's first state is a blank (P is even)
+    up1 = up1s;
+    up2 = up2s;
     float cur[P];
 #pragma unroll
-    for (int i = 0; i < P; ++i) cur[i] = ldexpf(alpha[i], d_own);
+    for (int i = 0; i < P; ++i) {
+      cur[i] = ldexpf(alpha[i], d_own);
+      lost |= (alpha[i] > 0.f) & (cur[i] < kCtcTiny);
+    }
     ex = ec;
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       const float p1 = i >= 1 ? cur[i - 1] : up1;
       const float p2 = i >= 2 ? cur[i - 2] : (i == 1 ? up1 : up2);
       // exp(em) * livef is independent of the alpha chain; states beyond 2*len+1 are zeroed by livef
-      alpha[i] = (cur[i] + p1 + (skip_ok[i] ? p2 : 0.f)) * (__expf(em[i]) * livef[i]);
+      const float sum = cur[i] + p1 + (skip_ok[i] ? p2 : 0.f);
+      alpha[i] = sum * (__expf(em[i]) * livef[i]);
+      lost |= (sum > 0.f) & (alpha[i] < kCtcTiny) & (em[i] > lim[i]);
     }
+    eloss = lost ? max(eloss, ec) : eloss;
     if (renorm) {  // compile-time: renormalise this lane every second step
       float m = alpha[0];
 #pragma unroll
@@ -152,13 +189,19 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
   const int e_lane = tail > 0.f ? ex : kCtcEmpty;
   const int e_max = (int)wave_max((float)e_lane);  // exponents are small integers: exact in fp32
   const float total = wave_sum(tail > 0.f ? ldexpf(tail, max(e_lane - e_max, -200)) : 0.f);
+  // the events are harmless where they cannot have taken 2^-26 of p(target) = total * 2^e_max
+  const int e_tot = total > 0.f ? e_max + (int)((__builtin_bit_cast(unsigned, total) >> 23) & 0xffu) - 127 : 2 * kCtcEmpty;
+  const bool redo = __any((int)(eloss > kCtcEmpty && eloss > e_tot + ctc_watch_slack(Tq))) != 0;
   // a NaN emission makes `total` NaN: (NaN > 0) is false, so test it explicitly instead of reporting "infeasible"
   if (lane == 0)
-    nll[lat] = (bad || total != total) ? __builtin_nanf("") : (total > 0.f) ? -(logf(total) + (float)e_max * 0.6931471805599453f) : INFINITY;
+    nll[lat] = (bad || total != total) ? __builtin_nanf("")
+               : redo                  ? -INFINITY
+               : (total > 0.f)         ? -(logf(total) + (float)e_max * 0.6931471805599453f)
+                                       : INFINITY;
   if constexpr (STORE) {  // p(target) = total * 2^e_max, kept exactly for the backward pass (nll alone rounds it to ~1e-4 relative)
     if (lane == 0) {
       float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
-      pinfo[0] = (bad || total != total) ? __builtin_nanf("") : total;
+      pinfo[0] = (bad || total != total) ? __builtin_nanf("") : redo ? kCtcRedo : total;
       pinfo[1] = __builtin_bit_cast(float, e_max);
     }
   }
@@ -180,18 +223,22 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
                                                       int S, int blank, const float* __restrict__ nll, float* __restrict__ astore) {
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
   const float* lp = logp + (size_t)lat * Tq * V;
+  float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
+  if (pinfo[0] < 0.f) return;  // the forward pass left this lattice to ctc_wide_kernel (wave-uniform)
   const long long len_raw = target_len[b];
   const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
   const int L = 2 * len + 1;
   int label[P];
   bool skip_ok[P];
-  float livef[P];
+  float livef[P], lim[P];
+  bool redo = false;
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int s = lane * P + i;
     label[i] = blank;
     skip_ok[i] = false;
     livef[i] = s < L ? 1.f : 0.f;
+    lim[i] = s < L ? -INFINITY : INFINITY;
     if (s < L && (s & 1)) {
       const int k = s >> 1;
       const long long lab = targets[(size_t)b * S + k];
@@ -209,11 +256,14 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
     for (int i = 0; i < P; ++i) skip_dn[i] = i + 2 < P ? skip_ok[i + 2] : ((i + 2 - P == 0 ? n0 : n1) != 0);
   }
   // p(target) = total * 2^e_max exactly as the forward pass left it: gamma = alpha beta' 2^(ea + eb - e_max) / total
-  const float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
   const float ptot = pinfo[0];
   const bool usable = ptot > 0.f && ptot < INFINITY;  // false for an infeasible (0) or invalid (NaN) lattice
   const int ishift = usable ? -__builtin_bit_cast(int, pinfo[1]) : 0;
   const float fscale = usable ? 1.0f / ptot : 0.f;
+  // events above this scale may have taken 2^-26 of p(target) (see RANGE at the top)
+  const int e_ptot = (int)((__builtin_bit_cast(unsigned, ptot) >> 23) & 0xffu) - 127;  // p(target) = ptot * 2^-ishift
+  const int e_harm = usable ? -ishift + e_ptot + ctc_watch_slack(Tq) : INT_MAX;
+  const int sh_harm = 120 - 26 - 2 + e_ptot;  // a product below kCtcTiny shifted by more than this: a posterior of 2^-26 or more
   float beta[P];
   int eb = kCtcEmpty;
   bool any0 = false;
@@ -240,22 +290,36 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
     const int ea = __builtin_bit_cast(int, al[slot][P]);
     const int sh = max(min(ea + eb + ishift, 126), -300);
 #pragma unroll
-    for (int i = 0; i < P; ++i)
-      astore[ctc_store_index(lat, Tq, P, t, i, lane)] = ldexpf(al[slot][i] * beta[i] * fscale, sh) * livef[i];
+    for (int i = 0; i < P; ++i) {
+      const float ab = al[slot][i] * beta[i];
+      redo |= (al[slot][i] > 0.f) & (beta[i] > 0.f) & (ab < kCtcTiny) & (sh > sh_harm);
+      astore[ctc_store_index(lat, Tq, P, t, i, lane)] = ldexpf(ab * fscale, sh) * livef[i];
+    }
     // beta'_{t-1}
     float bw[P];
+    bool lost = false;
 #pragma unroll
-    for (int i = 0; i < P; ++i) bw[i] = beta[i] * (__expf(emit[slot][i]) * livef[i]);
+    for (int i = 0; i < P; ++i) {
+      bw[i] = beta[i] * (__expf(emit[slot][i]) * livef[i]);
+      lost |= (beta[i] > 0.f) & (bw[i] < kCtcTiny) & (emit[slot][i] > lim[i]);
+    }
     float dn1 = EEC_DPP_F(0.f, bw[0], 0x130);  // next lane's first two weighted betas and its exponent
     float dn2 = EEC_DPP_F(0.f, bw[1], 0x130);
     const int eb_dn = EEC_DPP_I(kCtcEmpty, eb, 0x130);
     const int ec = max(eb, eb_dn);
     const int d_own = max(eb - ec, -200), d_dn = max(eb_dn - ec, -200);
-    dn1 = ldexpf(dn1, d_dn);
-    dn2 = ldexpf(dn2, d_dn);
+    const float dn1s = ldexpf(dn1, d_dn), dn2s = ldexpf(dn2, d_dn);
+    lost |= ((dn1 > 0.f) & (dn1s < kCtcTiny)) | ((dn2 > 0.f) & (dn2s < kCtcTiny));
+    dn1 = dn1s;
+    dn2 = dn2s;
 #pragma unroll
-    for (int i = 0; i < P; ++i) bw[i] = ldexpf(bw[i], d_own);
+    for (int i = 0; i < P; ++i) {
+      const float sh_own = ldexpf(bw[i], d_own);
+      lost |= (bw[i] > 0.f) & (sh_own < kCtcTiny);
+      bw[i] = sh_own;
+    }
     eb = ec;
+    redo |= lost & (ec > e_harm);
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       const float n1 = i + 1 < P ? bw[i + 1 < P ? i + 1 : 0] : dn1;
@@ -284,6 +348,7 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
 #pragma unroll
   for (int d = 0; d < kAhead; ++d)
     if (t - d >= 0) step(d, t - d, (d & 1) != 0);
+  if (usable && __any((int)redo) != 0 && lane == 0) pinfo[0] = kCtcRedo;  // an unusable lattice has no posteriors to lose
 }
 
 // dlogp[lat][t][c] = gs * (exp(logp) - sum of the posteriors of the states labelled c), gs = grad_loss[e] / (B max(len, 1))
@@ -336,6 +401,199 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------
+// The wide path: the lattices the block-floating kernels marked (see RANGE at the top).  Same linear-domain recursions, but
+// every state carries its own exponent -- value = m * 2^e, m in [1, 2) or 0 -- and is renormalised at every step, and an
+// emission enters as exp(l) = pm * 2^k with the product l * log2(e) split exactly, so nothing can leave the range whatever the
+// log-probs are (below -3e4 they count as -inf: impossible).  One wave per marked lattice, a 4-step look-ahead ring; the waves of
+// unmarked lattices return at once.  GRAD = false: the loss alone (after ctc_alpha_kernel).  GRAD = true (after
+// ctc_beta_kernel): the forward recursion again, its states kept (mantissas in the alpha slots of `astore`, exponents in the
+// region behind it), then the beta recursion, which overwrites the mantissas with the state posteriors for ctc_grad_kernel.
+constexpr int kCtcWideEmpty = -(1 << 30);
+
+__device__ __forceinline__ void ctc_wide_exp(float l, float& pm, int& k) {
+  const float hi = l * 1.44269502f;
+  const float lo = fmaf(l, 1.44269502f, -hi) + l * 1.92596299e-8f;  // log2(e) = 1.44269502 + 1.92596299e-8
+  const float kf = floorf(hi);
+  const bool zero = !(l > -3.0e4f);
+  pm = zero ? 0.f : exp2f((hi - kf) + lo);
+  k = zero ? 0 : (int)kf;
+}
+__device__ __forceinline__ void ctc_wide_norm(float v, int base, float& m, int& e) {  // v: 0 or a normal number
+  const int ex = (int)((__builtin_bit_cast(unsigned, v) >> 23) & 0xffu) - 127;
+  const bool any = v > 0.f;
+  m = any ? ldexpf(v, -ex) : 0.f;
+  e = any ? base + ex : kCtcWideEmpty;
+}
+__device__ __forceinline__ float ctc_wide_add3(float m0, int e0, float m1, int e1, float m2, int e2, int& ec) {
+  ec = max(e0, max(e1, e2));  // a term more than 2^-64 below the largest is below the fp32 sum's last bit
+  return ldexpf(m0, max(e0 - ec, -64)) + ldexpf(m1, max(e1 - ec, -64)) + ldexpf(m2, max(e2 - ec, -64));
+}
+
+template <int P, bool GRAD>
+__global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
+                                                      const long long* __restrict__ target_len, int B, int Tq, int V, int S,
+                                                      int blank, float* __restrict__ nll, float* __restrict__ astore) {
+  const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
+  if constexpr (GRAD) {
+    if (!(astore[ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat] < 0.f)) return;
+  } else {
+    if (!(nll[lat] == -INFINITY)) return;
+  }
+  const float* lp = logp + (size_t)lat * Tq * V;
+  int* estore = GRAD ? (int*)(astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)gridDim.x) : nullptr;  // [lat][t][P][64]
+  const long long len_raw = target_len[b];  // a marked lattice passed ctc_alpha_kernel's input checks
+  const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
+  const int L = 2 * len + 1;
+  int label[P];
+  bool skip_ok[P], live[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int s = lane * P + i;
+    label[i] = blank;
+    skip_ok[i] = false;
+    live[i] = s < L;
+    if (s < L && (s & 1)) {
+      const int k = s >> 1;
+      const long long lab = targets[(size_t)b * S + k];
+      label[i] = (lab < 0 || lab >= (long long)V) ? blank : (int)lab;
+      skip_ok[i] = k > 0 && lab != targets[(size_t)b * S + k - 1];
+    }
+  }
+  float am[P];
+  int ae[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int s = lane * P + i;
+    float pm;
+    int k;
+    ctc_wide_exp(lp[label[i]], pm, k);
+    ctc_wide_norm((s < 2 && s < L) ? pm : 0.f, k, am[i], ae[i]);
+  }
+  auto store = [&](int t) {
+    if constexpr (GRAD) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) {
+        astore[ctc_store_index(lat, Tq, P, t, i, lane)] = am[i];
+        estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane] = ae[i];
+      }
+    }
+  };
+  store(0);
+  // the emission log-probs are gathered kAhead steps ahead of their use, as in the fast path
+  constexpr int kAhead = 4;
+  float emit[kAhead][P];
+#pragma unroll
+  for (int d = 0; d < kAhead; ++d)
+#pragma unroll
+    for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)min(1 + d, Tq - 1) * V + label[i]];
+  for (int t0 = 1; t0 < Tq; t0 += kAhead)
+#pragma unroll
+  for (int d = 0; d < kAhead; ++d) {
+    const int t = t0 + d;
+    if (t >= Tq) break;  // wave-uniform
+    // the previous lane's last two states (wave_shr:1; lane 0 receives an empty state)
+    const float u1m = EEC_DPP_F(0.f, am[P - 1], 0x138), u2m = EEC_DPP_F(0.f, am[P - 2], 0x138);
+    const int u1e = EEC_DPP_I(kCtcWideEmpty, ae[P - 1], 0x138), u2e = EEC_DPP_I(kCtcWideEmpty, ae[P - 2], 0x138);
+    float nm[P];
+    int ne[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const float p1m = i >= 1 ? am[i >= 1 ? i - 1 : 0] : u1m;
+      const int p1e = i >= 1 ? ae[i >= 1 ? i - 1 : 0] : u1e;
+      float p2m = i >= 2 ? am[i >= 2 ? i - 2 : 0] : (i == 1 ? u1m : u2m);
+      int p2e = i >= 2 ? ae[i >= 2 ? i - 2 : 0] : (i == 1 ? u1e : u2e);
+      if (!skip_ok[i]) p2m = 0.f, p2e = kCtcWideEmpty;
+      float pm;
+      int k, ec;
+      ctc_wide_exp(emit[d][i], pm, k);
+      const float sum = ctc_wide_add3(am[i], ae[i], p1m, p1e, p2m, p2e, ec);
+      ctc_wide_norm(live[i] ? sum * pm : 0.f, ec + k, nm[i], ne[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      am[i] = nm[i], ae[i] = ne[i];
+      emit[d][i] = lp[(size_t)min(t + kAhead, Tq - 1) * V + label[i]];  // clamped: a harmless re-read near the end
+    }
+    store(t);
+  }
+  // p(target) = a[L-1] + a[L-2] = mt * 2^et
+  float tm = 0.f;
+  int te = kCtcWideEmpty;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int s = lane * P + i;
+    if (s == L - 1 || s == L - 2) {
+      int ec;
+      tm = ctc_wide_add3(tm, te, am[i], ae[i], 0.f, kCtcWideEmpty, ec);
+      te = tm > 0.f ? ec : kCtcWideEmpty;
+    }
+  }
+  int e_max = te;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) e_max = max(e_max, __shfl_xor(e_max, off, 64));
+  float total = ldexpf(tm, max(te - e_max, -64));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+  float mt;
+  int et;
+  ctc_wide_norm(total, e_max, mt, et);
+  if constexpr (!GRAD) {
+    if (lane == 0) nll[lat] = total > 0.f ? -(logf(mt) + (float)et * 0.6931471805599453f) : INFINITY;
+    return;
+  } else {
+    if (!(total > 0.f)) return;  // infeasible: nll is +inf and ctc_grad_kernel writes zeros
+    bool skip_dn[P];
+    {
+      int n0 = __shfl_down((int)skip_ok[0], 1, 64), n1 = __shfl_down((int)skip_ok[1], 1, 64);
+      if (lane == 63) n0 = n1 = 0;
+#pragma unroll
+      for (int i = 0; i < P; ++i) skip_dn[i] = i + 2 < P ? skip_ok[i + 2 < P ? i + 2 : 0] : ((i + 2 - P == 0 ? n0 : n1) != 0);
+    }
+    const float inv = 1.0f / mt;
+    float bm[P];
+    int be[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const int s = lane * P + i;
+      const bool last = s < L && (s == L - 1 || s == L - 2);
+      bm[i] = last ? 1.f : 0.f;
+      be[i] = last ? 0 : kCtcWideEmpty;
+    }
+    for (int t = Tq - 1; t >= 0; --t) {
+      float wm[P];
+      int we[P];
+#pragma unroll
+      for (int i = 0; i < P; ++i) {
+        const size_t ia = ctc_store_index(lat, Tq, P, t, i, lane);
+        const float a_m = astore[ia];
+        const int a_e = estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane];
+        const bool nz = a_m > 0.f && bm[i] > 0.f;
+        const int sh = nz ? min(max(a_e + be[i] - et, -200), 126) : 0;
+        astore[ia] = nz ? ldexpf(a_m * bm[i] * inv, sh) : 0.f;  // the posterior of state lane * P + i at time t
+        float pm;
+        int k;
+        ctc_wide_exp(lp[(size_t)t * V + label[i]], pm, k);
+        ctc_wide_norm(live[i] ? bm[i] * pm : 0.f, be[i] + k, wm[i], we[i]);
+      }
+      float d1m = __shfl_down(wm[0], 1, 64), d2m = __shfl_down(wm[1], 1, 64);
+      int d1e = __shfl_down(we[0], 1, 64), d2e = __shfl_down(we[1], 1, 64);
+      if (lane == 63) d1m = d2m = 0.f, d1e = d2e = kCtcWideEmpty;
+#pragma unroll
+      for (int i = 0; i < P; ++i) {
+        const float n1m = i + 1 < P ? wm[i + 1 < P ? i + 1 : 0] : d1m;
+        const int n1e = i + 1 < P ? we[i + 1 < P ? i + 1 : 0] : d1e;
+        float n2m = i + 2 < P ? wm[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1m : d2m);
+        int n2e = i + 2 < P ? we[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1e : d2e);
+        if (!skip_dn[i]) n2m = 0.f, n2e = kCtcWideEmpty;
+        int ec;
+        const float sum = ctc_wide_add3(wm[i], we[i], n1m, n1e, n2m, n2e, ec);
+        ctc_wide_norm(sum, ec, bm[i], be[i]);
+      }
+    }
+  }
+}
+
 int ctc_states_per_lane(int S) {
   if (2 * S + 1 <= 64 * 2) return 2;
   if (2 * S + 1 <= 64 * 4) return 4;
@@ -345,7 +603,8 @@ int ctc_states_per_lane(int S) {
 
 size_t ctc_store_floats(int E, int B, int Tq, int S) {
   const int P = ctc_states_per_lane(S);
-  return P ? (size_t)E * B * Tq * (P + 1) * 64 + 2 * (size_t)E * B : 0;
+  // the fast path's states and lane exponents, p(target) per lattice, the wide path's state exponents
+  return P ? (size_t)E * B * Tq * (P + 1) * 64 + 2 * (size_t)E * B + (size_t)E * B * Tq * P * 64 : 0;
 }
 
 hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, int E, int B, int Tq,
@@ -356,6 +615,8 @@ hipError_t launch_ctc_backward(const float* logp, const long long* targets, cons
 #define EEC_CTC_BWD(P_)                                                                                                      \
   hipLaunchKernelGGL(ctc_beta_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank, nll,  \
                      astore);                                                                                               \
+  hipLaunchKernelGGL((ctc_wide_kernel<P_, true>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,      \
+                     blank, (float*)nullptr, astore);                                                                        \
   hipLaunchKernelGGL(ctc_grad_kernel<P_>, dim3((n_rows + 3) / 4), dim3(256), 0, st, logp, targets, target_len, B, Tq, V, S,  \
                      blank, nll, astore, grad_loss, n_rows, dlogp);
   if (P == 2) {
@@ -401,7 +662,9 @@ hipError_t launch_ctc_loss(const float* logp, const long long* targets, const lo
                        blank, nll, astore);                                                                                    \
   else                                                                                                                         \
     hipLaunchKernelGGL((ctc_alpha_kernel<P_, false>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,    \
-                       blank, nll, astore);
+                       blank, nll, astore);                                                                                    \
+  hipLaunchKernelGGL((ctc_wide_kernel<P_, false>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,       \
+                     blank, nll, astore);
   if (P == 2) {
     EEC_CTC_FWD(2)
   } else if (P == 4) {

@@ -327,3 +327,74 @@ def test_ctc_beam_oracle_against_brute_force():
     # a repeated label across a skipped (blank) frame stays a repeat: "a <blank> a" -> [a, a]
     lp = np.log(np.array([[0.01, 0.98, 0.01], [0.98, 0.01, 0.01], [0.01, 0.98, 0.01]]))
     assert ctc_prefix_beam_search(lp, beam=4, blank_skip_threshold=0.95)[0] == [1, 1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Host checks of the inputs of tests/test_gpu_ctc.py (tests/ctc_cases.py): the reference values and the inclusion shares the GPU
+# tests rely on hold for the reference / the oracle ALONE, wherever the suite runs.
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_ctc_peaky_cases_have_the_intended_scale_and_finite_reference_losses():
+    import ctc_cases as C
+    cases = C.part1_cases()
+    for scale, (lo, hi) in C.PEAKY_SCALES.items():
+        assert lo < cases[f"scale{scale:g}"][0].abs().max().item() < hi, scale
+    assert 55 < cases["fixture"][0].abs().max().item() < 65
+    for name, (lp, match, mism) in cases.items():
+        for e in range(lp.size(0)):
+            for b in range(lp.size(1)):
+                m = C.ref_nll(lp[e, b], match[0][b, : int(match[1][b])].tolist())
+                x = C.ref_nll(lp[e, b], mism[0][b, : int(mism[1][b])].tolist())
+                assert np.isfinite(m) and np.isfinite(x), (name, e, b)
+                assert x / int(mism[1][b]) > 10.0, (name, e, b, x)  # unrelated targets: every path improbable (e^-10 per label at best)
+                if e == 0:  # the greedy decode of the same log-probs: the most probable path, far likelier than any of the others
+                    assert m / max(int(match[1][b]), 1) < x / int(mism[1][b]) / 3, (name, b, m, x)  # per label
+    big = cases["scale16"]
+    assert max(C.ref_nll(big[0][e, 0], big[2][0][0, : int(big[2][1][0])].tolist()) for e in range(2)) > 2000.0  # thousands of nats, finite
+
+
+def test_ctc_range_lattices_have_the_reference_values_the_gpu_test_assumes():
+    import ctc_cases as C
+    cases = C.range_cases()
+    assert len(cases) == len(C.RANGE_FRAMES) * len(C.RANGE_X) + 4
+    for name, lp, target in cases:
+        v = C.ref_nll(lp, target)
+        assert np.isfinite(v) and 50.0 < v < 400.0, (name, v)
+        assert lp.shape == (C.RANGE_T, C.RANGE_V)
+    for fr in C.RANGE_FRAMES:  # on the named frames blank and both labels sit at -x (to 1e-6), elsewhere they are likely
+        lp = C.range_lattice(fr, 60.0)
+        assert (lp[list(fr)][:, [0, 3, 4]] + 60.0).abs().max().item() < 1e-6
+        rest = [t for t in range(C.RANGE_T) if t not in fr]
+        assert lp[rest][:, [0, 3, 4]].min().item() > -8.0
+    assert C.range_lattice((5,), 95.0)[5, 0].item() < -94.0  # below the fp32 range of exp (-87.3)
+    masked = dict((n, l) for n, l, _ in cases)["masked-vocabulary"]
+    assert np.isneginf(masked[:, [1, 2, 5]].numpy()).all() and np.isfinite(masked[:, [0, 3, 4, 6, 7]].numpy()).all()
+    for name, lp, target in C.infeasible_cases():
+        assert C.ref_nll(lp, target) == float("inf"), name
+        z = C.ref_ctc(lp.float().view(1, 1, *lp.shape), torch.tensor([list(target)]), torch.tensor([len(target)]))
+        assert z[0].item() == 0.0 and (z[1] == 0).all()  # zero_infinity: zero loss, zero gradient
+
+
+def test_ctc_beam_cases_leave_at_most_a_quarter_of_the_sequences_uncompared():
+    """The GPU beam tests compare tokens only where the oracle's best prefix leads its runner-up by more than 5e-3 and require
+    that on at least 3/4 of the sequences: the oracle alone meets it on the same inputs, both readings of the skip rule."""
+    import ctc_cases as C
+    from oracle.ctc_beam_ref import ctc_prefix_beam_search
+
+    def share(logp, beam, **kw):
+        out = []
+        for drop in (False, True):
+            fin = [ctc_prefix_beam_search(logp[n].double().numpy(), beam=beam, return_beams=True, skip_drops_frame=drop, **kw)[2]
+                   for n in range(logp.size(0))]
+            out.append(sum(C.safe_margin(f) for f in fin) / logp.size(0))
+        return min(out)
+
+    for N, T, V, beam, scale in C.BEAM_CASES:
+        assert share(C.beam_logp(N, T, V, scale), beam) >= 0.75, (N, T, V, beam, scale)
+    assert share(C.fixture_beam_logp(), 10) >= 0.75
+    assert share(C.beam_logp(4, 30, 255, 4.0), 10) >= 0.75
+    assert share(C.beam_logp(8, 40, 32, 4.0, blank=31), 10, blank=31) >= 0.75
+    assert share(C.beam_logp(8, 40, 32, 6.0), 1) >= 0.75
+    assert len(C.BIG_SAMPLE) == 16 and sorted(n % 4 for n in C.BIG_SAMPLE) == [0] * 4 + [1] * 4 + [2] * 4 + [3] * 4
+    big = C.big_batch_logp()
+    safe = sum(C.safe_margin(ctc_prefix_beam_search(big[n].double().numpy(), beam=10, return_beams=True)[2]) for n in C.BIG_SAMPLE)
+    assert safe >= 12, safe
