@@ -52,6 +52,35 @@ class CTCHypothesis:
         return f"CTCHypothesis(tokens={self.tokens}, words={self.words}, score={self.score:.4f})"
 
 
+def default_max_length(T: int) -> int:
+    """inference.py:31-39 (p = 30, m = 5 / 200): the decoding length for T input frames."""
+    return int(30 - T * 5 / 200) if T < 200 else int(T / 12)
+
+
+def _lockstep_kw(kw: dict) -> Optional[dict]:
+    """The keywords for a lockstep search (it has no ``kv_cache`` switch), or None when the caller turned the cache off."""
+    return {k: v for k, v in kw.items() if k != "kv_cache"} if kw.get("kv_cache", True) else None
+
+
+def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float):
+    """``max_length`` steps of n independent beam searches in lockstep, none of which finalises a beam on the way:
+    ``step(last [n, R], parent [n, R] | None)`` returns the next token's log-probs [n, R, V] of every live beam.  The
+    bookkeeping of a step is ``beam_select`` over two token buffers.  Returns ``(final_tokens, final_scores, best_tokens)``
+    per search."""
+    scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+    bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
+    bufs[0][:, 0, 0] = sos
+    last = bufs[0][:, :1, 0].contiguous()
+    parent: Optional[Tensor] = None
+    for i in range(max_length):
+        scores, parent, last = beam_select(step(last, parent), scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1],
+                                           i + 1)
+    tokens = bufs[max_length & 1][:, :beam]
+    best = scores.argmax(dim=1).tolist()
+    tokens_h = tokens.cpu()
+    return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
+
+
 class BeamInference:
     """``args`` needs ``dec_voc_size, trg_sos_idx, trg_eos_idx, trg_pad_idx, beam_size, pen_alpha, device`` (the fields
     util/conf.py:455-486 injects); every one of them can also be given per call, as in the reference."""
@@ -154,15 +183,14 @@ class BeamInference:
                          **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
         ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits)."""
-        T = spec.size(1)
-        if max_length is None:  # inference.py:31-39 (p = 30, m = 5 / 200)
-            max_length = int(30 - T * 5 / 200) if T < 200 else int(T / 12)
+        if max_length is None:
+            max_length = default_max_length(spec.size(1))
         taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=False, want_taps=True,
                                   n_groups=model._cfg.n_exits)[1]
         exits = list(range(1, model._cfg.n_exits + 1))
-        if kw.get("kv_cache", True):
-            together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size,
-                                              **{k: v for k, v in kw.items() if k != "kv_cache"})
+        lockstep = _lockstep_kw(kw)
+        if lockstep is not None:
+            together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size, **lockstep)
             if together is not None:
                 return [best for _, _, best in together]
         return [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw)[2] for n in exits]
@@ -176,11 +204,7 @@ class BeamInference:
         ``(final_tokens, final_scores, best_tokens)`` per exit, the same values as ``beam_search`` exit by exit -- or None
         when the lockstep does not apply: no session group for this model / geometry, or EOS could finalise beams
         (``max_length - 1 > min_length``), which would let the exits' beam counts diverge."""
-        V = self._arg(vocab_size, "dec_voc_size")
-        sos = self._arg(SOS_token, "trg_sos_idx")
-        self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")
-        beam = self._arg(beam_size, "beam_size")
-        alpha = self._arg(pen_alpha, "pen_alpha")
+        _, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_session_group"):
             return None
         if any(e.size(0) != 1 for e in encoder_outputs):
@@ -188,29 +212,11 @@ class BeamInference:
         group = model.decoder_session_group(encoder_outputs, layer_ns, max_length)
         if group is None or beam > group.max_beams:
             return None
-        n, dev = len(layer_ns), encoder_outputs[0].device
-        scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
-        parent: Optional[Tensor] = None
-        if dev.type == "cuda":  # top-k, parent / token split and the token gather of a step in one launch (eec_beam_select)
-            rows = max(beam, 1)
-            bufs = [torch.zeros((n, rows, max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
-            bufs[0][:, 0, 0] = sos
-            last = bufs[0][:, :1, 0].contiguous()
-            for i in range(max_length):
-                logp = group.step(last, parent)
-                scores, parent, last = beam_select(logp, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
-            tokens = bufs[max_length & 1][:, :beam]
-        else:
-            tokens = torch.full((n, 1, 1), sos, dtype=torch.long, device=dev)  # [exits, live beams, s]
-            for i in range(max_length):
-                logp = group.step(tokens[:, :, -1], parent) / sequence_length_penalty(i + 1, alpha)
-                scores, idx = torch.topk((scores.unsqueeze(2) + logp).reshape(n, -1), beam, dim=1)
-                parent = torch.div(idx, V, rounding_mode="floor")
-                tok_idx = torch.remainder(idx, V)
-                tokens = torch.cat([torch.gather(tokens, 1, parent.unsqueeze(2).expand(-1, -1, tokens.size(2))), tok_idx.unsqueeze(2)], dim=2)
-        best = scores.argmax(dim=1).tolist()
-        tokens_h = tokens.cpu()
-        return [(list(tokens[e]), list(scores[e]), tokens_h[e, best[e]].tolist()) for e in range(n)]
+        return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha)
+
+    def _lockstep_args(self, vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha):
+        self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")  # accepted and unused: no beam finalises
+        return self._arg(vocab_size, "dec_voc_size"), self._arg(SOS_token, "trg_sos_idx"), self._arg(beam_size, "beam_size"), self._arg(pen_alpha, "pen_alpha")
 
     @torch.no_grad()
     def beam_search_batch(self, model, taps, layer_ns: Sequence[int], vocab_size: Optional[int] = None, max_length: int = 500,
@@ -222,32 +228,19 @@ class BeamInference:
         Returns ``out[b][e] = (final_tokens, final_scores, best_tokens)``, what ``beam_search`` returns for utterance b and exit
         ``layer_ns[e]`` -- or None where ``beam_search_exits`` declines: EOS could finalise beams (``max_length - 1 >
         min_length``), or no batch session for this model / geometry / device."""
-        V = self._arg(vocab_size, "dec_voc_size")
-        sos = self._arg(SOS_token, "trg_sos_idx")
-        self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")
-        beam = self._arg(beam_size, "beam_size")
-        alpha = self._arg(pen_alpha, "pen_alpha")
+        V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
             return None
         session = model.decoder_batch_session(taps, layer_ns, max_length)
         if session is None or beam > session.max_beams:
             return None
-        E, B, dev = session.E, session.B, session.dev
+        E, B = session.E, session.B
         n = E * B  # search i = e * B + b
-        scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
-        bufs = [torch.zeros((n, beam, max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
-        bufs[0][:, 0, 0] = sos
-        last = bufs[0][:, :1, 0].contiguous()
-        parent: Optional[Tensor] = None
-        for i in range(max_length):
-            logp = session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1))
-            scores, parent, last = beam_select(logp.view(n, -1, V), scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1],
-                                               bufs[(i + 1) & 1], i + 1)
-        tokens = bufs[max_length & 1]
-        best = scores.argmax(dim=1).tolist()
-        tokens_h = tokens.cpu()
-        return [[(list(tokens[e * B + b]), list(scores[e * B + b]), tokens_h[e * B + b, best[e * B + b]].tolist()) for e in range(E)]
-                for b in range(B)]
+
+        def step(last, parent):
+            return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
+        found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha)
+        return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
@@ -257,9 +250,8 @@ class BeamInference:
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
         lockstep.  Where the batched search declines, every utterance goes through ``decode_all_exits``, so the result is
         always the reference's."""
-        T = spec.size(2)
-        if max_length is None:  # inference.py:31-39: one length for the whole padded batch
-            max_length = int(30 - T * 5 / 200) if T < 200 else int(T / 12)
+        if max_length is None:  # one length for the whole padded batch
+            max_length = default_max_length(spec.size(2))
         E = model._cfg.n_exits
         exits = list(range(1, E + 1))
         valid_len = valid_len.reshape(-1)
@@ -267,11 +259,10 @@ class BeamInference:
         out: List[List[List[int]]] = []
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
-            together = None
-            if kw.get("kv_cache", True):
+            together, lockstep = None, _lockstep_kw(kw)
+            if lockstep is not None:
                 taps = model._run_encoder(sp, vl, want_out=False, want_taps=True, n_groups=E)[1]
-                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size,
-                                                  **{k: v for k, v in kw.items() if k != "kv_cache"})
+                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep)
                 del taps
             if together is None:
                 out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, **kw) for b in range(sp.size(0))]

@@ -11,40 +11,17 @@
 //   batch_linear (LN3 -> linear1 -> ReLU)            batch_linear (linear2, += x)
 // then batch_linear (final LN -> head) and the log_softmax.  The beam bookkeeping is eec_beam_select with n = E * B groups.
 //
-// Cache layout (one caller-owned buffer, carve() below), u = e * B + b is the (exit, utterance) index:
-//   mem [E][L][B][Tq][2D]        memory keys | values, projected once by _begin (one training GEMM per (exit, layer))
-//   kv  [E*B][L][S_max][16][2D]  self-attention keys | values of every (position, beam slot)
-//   anc [E*B][2][16][S_max]      each beam's ancestry slots (double-buffered by step parity); pad [E*B][S_max][16]
-//   activations [E][B*16][...]   rows of exit e at e * B * R + b * R + r (dense for the step's R)
-#include <algorithm>
-#include <string>
-
-#include "../../include/eec.h"
-#include "eec_train.h"
-
-namespace eec {
-hipError_t ensure_max_lds(const void* kernel, int bytes);  // pack.hip
-int decoder_step_fail(int code, const char* msg);          // decoder_step.hip: eec_decoder_step_last_error()
-}
+// One cache for all of them: the layout of eec_decoder_step.h (carve()) with u = e * B + b the (exit, utterance) index; the
+// memory keys | values are projected by _begin with one training GEMM per (exit, layer).
+#include "eec_decoder_step.h"
 
 using namespace eect;
+using namespace eecs;
 
 namespace {
 
-constexpr int kRows = 16;     // live beams per utterance
-constexpr int kMaxExits = 8;  // exits per call: per-exit weight pointers travel in the kernel arguments
-
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float xsum(float v, int from) {
-  for (int m = from; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float xmax(float v, int from) {
-  for (int m = from; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Y[e][m][n] (+)= act( LN_e?(X[e][m]) . W_e[n] + bias_e[n] ),  m < M = B * R, on v_mfma_f32_32x32x16_f16 with f16x3 operands:
@@ -73,7 +50,7 @@ struct BatchLinearArgs {
   float* Y;
   long ldy, y_e;
   int M, N, K, relu, accumulate;
-  ExitLinear ex[kMaxExits];
+  ExitLinear ex[kGroup];
 };
 
 // 8 consecutive fp32 of a row from k (a multiple of 8; K a multiple of 4), zero past K
@@ -121,7 +98,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
         v[j] = k < K ? *reinterpret_cast<const float4*>(xr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
       }
-      const float mean = xsum(s, 8) / K;
+      const float mean = wsum(s, 8) / K;
       float q = 0.0f;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
@@ -130,7 +107,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
           q += dx * dx + dy * dy + dz * dz + dw * dw;
         }
       }
-      const float rstd = rsqrtf(xsum(q, 8) / K + 1e-5f);
+      const float rstd = rsqrtf(wsum(q, 8) / K + 1e-5f);
       if (l16 == 0) mu[ml] = mean, rs[ml] = rstd;
     }
     __syncthreads();
@@ -198,8 +175,8 @@ hipError_t batch_linear(const BatchLinearArgs& a, int E, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------------
 struct BatchEmbedArgs {
   const long long *tok, *parent;  // [E*B][R]
-  const float* emb[kMaxExits];
-  const float* pe[kMaxExits];
+  const float* emb[kGroup];
+  const float* pe[kGroup];
   float* x;  // [E*B*R][D]
   unsigned char* pad;
   int* anc;
@@ -226,15 +203,7 @@ __global__ __launch_bounds__(256) void batch_embed_kernel(BatchEmbedArgs a) {
 
 // log_softmax of the exit heads' logits, a wave per row of E * B * R
 __global__ __launch_bounds__(64) void batch_logsoftmax_kernel(const float* __restrict__ logits, float* __restrict__ out, int V) {
-  const int lane = threadIdx.x;
-  const float* xr = logits + (long)blockIdx.x * V;
-  float mx = -INFINITY;
-  for (int k = lane; k < V; k += 64) mx = fmaxf(mx, xr[k]);
-  mx = xmax(mx, 32);
-  float sum = 0.0f;
-  for (int k = lane; k < V; k += 64) sum += expf(xr[k] - mx);
-  const float lse = mx + logf(xsum(sum, 32));
-  for (int k = lane; k < V; k += 64) out[(long)blockIdx.x * V + k] = xr[k] - lse;
+  log_softmax_row(logits + (long)blockIdx.x * V, out + (long)blockIdx.x * V, V, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -289,7 +258,7 @@ __global__ __launch_bounds__(256) void batch_self_attn_kernel(SelfAttnArgs a) {
     sc[t] = d;
     mx = fmaxf(mx, d);
   }
-  mx = xmax(mx, 32);
+  mx = wmax(mx);
   if (lane == 0) stat[0][w] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(stat[0][0], stat[0][1]), fmaxf(stat[0][2], stat[0][3]));
@@ -299,7 +268,7 @@ __global__ __launch_bounds__(256) void batch_self_attn_kernel(SelfAttnArgs a) {
     sc[t] = p;
     sum += p;
   }
-  sum = xsum(sum, 32);
+  sum = wsum(sum);
   if (lane == 0) stat[1][w] = sum;
   __syncthreads();
   const float inv = 1.0f / (stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]);  // no live key: nan, as torch
@@ -370,7 +339,7 @@ __global__ __launch_bounds__(256) void batch_cross_attn_kernel(CrossAttnArgs a) 
     if (rr < R) {
       float mx = -INFINITY;
       for (int j = l16; j < kChunk; j += 16) mx = fmaxf(mx, ps[rr][j]);
-      const float m_new = fmaxf(m_run, xmax(mx, 8));  // finite: the chunk holds at least one key
+      const float m_new = fmaxf(m_run, wmax(mx, 8));  // finite: the chunk holds at least one key
       float sum = 0.0f;
       for (int j = l16; j < kChunk; j += 16) {
         const float p = __expf(ps[rr][j] - m_new);
@@ -378,7 +347,7 @@ __global__ __launch_bounds__(256) void batch_cross_attn_kernel(CrossAttnArgs a) 
         sum += p;
       }
       const float al = __expf(m_run - m_new);
-      l_run = l_run * al + xsum(sum, 8);
+      l_run = l_run * al + wsum(sum, 8);
       m_run = m_new;
       if (l16 == 0) alpha[rr] = al;
     }
@@ -409,79 +378,22 @@ __global__ __launch_bounds__(256) void batch_cross_attn_kernel(CrossAttnArgs a) 
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-struct Geo {
-  int D, H, F, V, L, S_max, Tq, E, B;
-};
-struct Cache {
-  float *mem, *kv, *x, *qkv, *q, *ctx, *h, *logits;
-  int* anc;
-  unsigned char* pad;
-  size_t bytes;
-};
-Cache carve(char* base, const Geo& g) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) / 256 * 256;
-    char* p = base + off;
-    off += bytes;
-    return p;
-  };
-  Cache c{};
-  const size_t f = sizeof(float), U = (size_t)g.E * g.B, rows = U * kRows;
-  c.mem = (float*)take(U * g.L * g.Tq * 2 * g.D * f);
-  c.kv = (float*)take(U * g.L * g.S_max * kRows * 2 * g.D * f);
-  c.x = (float*)take(rows * g.D * f);
-  c.qkv = (float*)take(rows * 3 * g.D * f);
-  c.q = (float*)take(rows * g.D * f);
-  c.ctx = (float*)take(rows * g.D * f);
-  c.h = (float*)take(rows * g.F * f);
-  c.logits = (float*)take(rows * g.V * f);
-  c.anc = (int*)take(U * 2 * kRows * g.S_max * sizeof(int));
-  c.pad = (unsigned char*)take(U * g.S_max * kRows);
-  c.bytes = off + 256;
-  return c;
-}
-
-// the step decoder's geometry (eec_decoder_cache_bytes != 0), E <= 8 exits per call, E * B within a grid's y extent
-bool geometry_ok(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int E, int B, int S_max, int Tq) {
-  if (E <= 0 || E > kMaxExits || B <= 0 || (long)E * B > 65535) return false;
-  return eec_decoder_cache_bytes(d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq) != 0;
-}
-
-int bfail(int code, const std::string& msg) { return eec::decoder_step_fail(code, msg.c_str()); }
-
-#define BRUN(expr)                                                                          \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) return bfail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
 
 size_t eec_decoder_batch_cache_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int E, int B, int S_max, int Tq) {
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, n_layers, E, B, S_max, Tq)) return 0;
-  return carve(nullptr, Geo{d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq, E, B}).bytes;
+  const Geo g{d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq, E, B};
+  return geometry_ok(g) ? carve(nullptr, g).bytes : 0;
 }
 
 int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, int d_model, int n_heads, int d_ff, int vocab, const float* taps,
                             int Tq, int S_max, int passes, void* cache, size_t cache_bytes, void* stream) {
-  if (!ps || !taps || !cache || E <= 0 || E > kMaxExits) return bfail(EEC_ERR_BAD_ARG, "null argument, or not 1 .. 8 exits");
-  for (int e = 0; e < E; ++e)
-    if (!ps[e] || !ps[e]->layers) return bfail(EEC_ERR_BAD_ARG, "null argument");
-  if (passes != 1 && passes != 3) return bfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  const int L = ps[0]->n_layers;
-  for (int e = 0; e < E; ++e) {
-    if (ps[e]->n_layers != L) return bfail(EEC_ERR_BAD_ARG, "the exits of a call share one decoder geometry");
-    if (S_max > ps[e]->max_len) return bfail(EEC_ERR_UNSUPPORTED, "S_max beyond the positional-encoding table");
-  }
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, L, E, B, S_max, Tq))
-    return bfail(EEC_ERR_UNSUPPORTED, "geometry not served by the batched step decoder");
-  const Geo g{d_model, n_heads, d_ff, vocab, L, S_max, Tq, E, B};
-  const Cache c = carve((char*)cache, g);
-  if (c.bytes > cache_bytes) return bfail(EEC_ERR_WORKSPACE, "cache too small");
+  Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, E, B};
+  Cache c;
+  if (int rc = check_call(taps != nullptr, ps, E, g, nullptr, &cache, 1, cache_bytes, &c)) return rc;
+  if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  const int L = g.L;
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model;
   const size_t rows = (size_t)B * Tq;
@@ -491,7 +403,7 @@ int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, i
       GemmArgs a = gemm_args(taps + (size_t)e * rows * D, D, 1, P.ca_in_w + (size_t)D * D, D, 1, c.mem + ((size_t)e * L + l) * rows * 2 * D, 2 * D,
                              (int)rows, 2 * D, D);
       a.bias = P.ca_in_b + D;
-      BRUN(launch_gemm(a, passes, st));
+      EECS_RUN(launch_gemm(a, passes, st));
     }
   return 0;
 }
@@ -499,22 +411,11 @@ int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, i
 int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, int d_model, int n_heads, int d_ff, int vocab, int pad_idx,
                            const int64_t* last_tokens, const int64_t* parent, int R, int R_prev, int s, int Tq, int S_max, float* out, void* cache,
                            size_t cache_bytes, void* stream) {
-  if (!ps || !last_tokens || !out || !cache || E <= 0 || E > kMaxExits) return bfail(EEC_ERR_BAD_ARG, "null argument, or not 1 .. 8 exits");
-  for (int e = 0; e < E; ++e)
-    if (!ps[e] || !ps[e]->layers) return bfail(EEC_ERR_BAD_ARG, "null argument");
-  const int L = ps[0]->n_layers;
-  for (int e = 0; e < E; ++e) {
-    if (ps[e]->n_layers != L) return bfail(EEC_ERR_BAD_ARG, "the exits of a call share one decoder geometry");
-    if (S_max > ps[e]->max_len) return bfail(EEC_ERR_UNSUPPORTED, "S_max beyond the positional-encoding table");
-  }
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, L, E, B, S_max, Tq))
-    return bfail(EEC_ERR_UNSUPPORTED, "geometry not served by the batched step decoder");
-  if (R <= 0 || R > kRows) return bfail(EEC_ERR_BAD_ARG, "1 .. 16 live beams per utterance and step");
-  if (s < 0 || s >= S_max) return bfail(EEC_ERR_BAD_ARG, "step index outside the cache (S_max)");
-  if (s > 0 && (R_prev <= 0 || R_prev > kRows)) return bfail(EEC_ERR_BAD_ARG, "R_prev: the previous step's beam count");
-  const Geo g{d_model, n_heads, d_ff, vocab, L, S_max, Tq, E, B};
-  const Cache c = carve((char*)cache, g);
-  if (c.bytes > cache_bytes) return bfail(EEC_ERR_WORKSPACE, "cache too small");
+  Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, E, B};
+  const Step step{R, R_prev, s};
+  Cache c;
+  if (int rc = check_call(last_tokens && out, ps, E, g, &step, &cache, 1, cache_bytes, &c)) return rc;
+  const int L = g.L;
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model, H = n_heads, dh = D / H, F = d_ff, M = B * R;
   const float scale = 1.0f / sqrtf((float)dh);
@@ -527,7 +428,7 @@ int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, in
     a.x = c.x, a.pad = c.pad, a.anc = c.anc, a.anc_u = anc_u;
     a.B = B, a.R = R, a.R_prev = R_prev, a.s = s, a.S_max = S_max, a.D = D, a.V = vocab, a.pad_idx = pad_idx;
     hipLaunchKernelGGL(batch_embed_kernel, dim3(R, (unsigned)U), dim3(256), 0, st, a);
-    BRUN(hipGetLastError());
+    EECS_RUN(hipGetLastError());
   }
   // one batch_linear launch for all exits: exit e's weights through f(e)
   auto linear = [&](const float* X, long ldx, float* Y, long ldy, int N, int K, int relu, int accumulate, auto f) {
@@ -538,33 +439,33 @@ int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, in
     return batch_linear(a, E, st);
   };
   const size_t self_lds = (size_t)(s + 1) * 8;
-  BRUN(eec::ensure_max_lds((const void*)batch_self_attn_kernel, (int)self_lds));
+  EECS_RUN(eec::ensure_max_lds((const void*)batch_self_attn_kernel, (int)self_lds));
   for (int l = 0; l < L; ++l) {
     auto P = [&](int e) -> const eec_decoder_layer_params& { return ps[e]->layers[l]; };
     // self-attention over each beam's own prefix
-    BRUN(linear(c.x, D, c.qkv, 3L * D, 3 * D, D, 0, 0, [&](int e) { return ExitLinear{P(e).sa_in_w, P(e).sa_in_b, P(e).norm1_w, P(e).norm1_b}; }));
+    EECS_RUN(linear(c.x, D, c.qkv, 3L * D, 3 * D, D, 0, 0, [&](int e) { return ExitLinear{P(e).sa_in_w, P(e).sa_in_b, P(e).norm1_w, P(e).norm1_b}; }));
     {
       SelfAttnArgs a{c.qkv, c.kv + (size_t)l * S_max * kRows * 2 * D, kv_u, c.anc + (size_t)(s & 1) * kRows * S_max, anc_u, c.pad, c.ctx,
                      B, R, s, S_max, D, dh, scale};
       hipLaunchKernelGGL(batch_self_attn_kernel, dim3(M, H, E), dim3(256), self_lds, st, a);
-      BRUN(hipGetLastError());
+      EECS_RUN(hipGetLastError());
     }
-    BRUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).sa_out_w, P(e).sa_out_b, nullptr, nullptr}; }));
+    EECS_RUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).sa_out_w, P(e).sa_out_b, nullptr, nullptr}; }));
     // cross-attention over the utterance's memory
-    BRUN(linear(c.x, D, c.q, D, D, D, 0, 0, [&](int e) { return ExitLinear{P(e).ca_in_w, P(e).ca_in_b, P(e).norm2_w, P(e).norm2_b}; }));
+    EECS_RUN(linear(c.x, D, c.q, D, D, D, 0, 0, [&](int e) { return ExitLinear{P(e).ca_in_w, P(e).ca_in_b, P(e).norm2_w, P(e).norm2_b}; }));
     {
       CrossAttnArgs a{c.q, c.mem + (size_t)l * B * Tq * 2 * D, (long)L * B * Tq * 2 * D, c.ctx, B, R, Tq, D, dh, scale};
       hipLaunchKernelGGL(batch_cross_attn_kernel, dim3(H, B, E), dim3(256), 0, st, a);
-      BRUN(hipGetLastError());
+      EECS_RUN(hipGetLastError());
     }
-    BRUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).ca_out_w, P(e).ca_out_b, nullptr, nullptr}; }));
+    EECS_RUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).ca_out_w, P(e).ca_out_b, nullptr, nullptr}; }));
     // feed-forward, ReLU
-    BRUN(linear(c.x, D, c.h, F, F, D, 1, 0, [&](int e) { return ExitLinear{P(e).w1, P(e).b1, P(e).norm3_w, P(e).norm3_b}; }));
-    BRUN(linear(c.h, F, c.x, D, D, F, 0, 1, [&](int e) { return ExitLinear{P(e).w2, P(e).b2, nullptr, nullptr}; }));
+    EECS_RUN(linear(c.x, D, c.h, F, F, D, 1, 0, [&](int e) { return ExitLinear{P(e).w1, P(e).b1, P(e).norm3_w, P(e).norm3_b}; }));
+    EECS_RUN(linear(c.h, F, c.x, D, D, F, 0, 1, [&](int e) { return ExitLinear{P(e).w2, P(e).b2, nullptr, nullptr}; }));
   }
-  BRUN(linear(c.x, D, c.logits, vocab, vocab, D, 0, 0, [&](int e) { return ExitLinear{ps[e]->head_w, ps[e]->head_b, ps[e]->norm_w, ps[e]->norm_b}; }));
+  EECS_RUN(linear(c.x, D, c.logits, vocab, vocab, D, 0, 0, [&](int e) { return ExitLinear{ps[e]->head_w, ps[e]->head_b, ps[e]->norm_w, ps[e]->norm_b}; }));
   hipLaunchKernelGGL(batch_logsoftmax_kernel, dim3((unsigned)(U * R)), dim3(64), 0, st, c.logits, out, vocab);
-  BRUN(hipGetLastError());
+  EECS_RUN(hipGetLastError());
   return 0;
 }
 

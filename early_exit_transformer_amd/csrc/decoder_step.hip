@@ -14,37 +14,18 @@
 // A step is bound by that launch count (a dependent launch costs 4 - 6 us here), not by its work, so every kernel takes a
 // GROUP of up to 8 sessions -- the exits of one utterance, whose searches are independent -- as one more grid dimension
 // (eec_decoder_step_multi): E searches for the launches of one.
-#include <algorithm>
-#include <string>
-
-#include "../../include/eec.h"
-#include "eec_train.h"
-
-namespace eec {
-hipError_t ensure_max_lds(const void* kernel, int bytes);  // pack.hip
-}
+#include "eec_decoder_step.h"
 
 using namespace eect;
+using namespace eecs;
 
 namespace {
 
-constexpr int kRows = 16;   // live beams per step (rows of every activation of a step)
-constexpr int kGroup = 8;   // sessions (exits of one utterance) advanced by the same launches: one more grid dimension
+// the sessions (exits of one utterance) advanced by the same launches: one more grid dimension
 template <typename A>
 struct Group {
   A a[kGroup];
 };
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Y[r][n] (+)= act( LN?(X[r]) . W[n] + bias[n] ), r < R <= 16.  Threads are (column c = tid / KL, k-lane j = tid % KL):
@@ -263,15 +244,7 @@ struct LsmArgs {
 };
 __global__ __launch_bounds__(64) void step_logsoftmax_kernel(Group<LsmArgs> grp, int V) {
   const LsmArgs& a = grp.a[blockIdx.y];
-  const int lane = threadIdx.x;
-  const float* xr = a.logits + (long)blockIdx.x * V;
-  float mx = -INFINITY;
-  for (int k = lane; k < V; k += 64) mx = fmaxf(mx, xr[k]);
-  mx = wmax(mx);
-  float sum = 0.0f;
-  for (int k = lane; k < V; k += 64) sum += expf(xr[k] - mx);
-  const float lse = mx + logf(wsum(sum));
-  for (int k = lane; k < V; k += 64) a.out[(long)blockIdx.x * V + k] = xr[k] - lse;
+  log_softmax_row(a.logits + (long)blockIdx.x * V, a.out + (long)blockIdx.x * V, V, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -432,96 +405,32 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-thread_local std::string g_serr;
-int sfail(int code, const std::string& msg) {
-  g_serr = msg;
-  return code;
-}
-
-struct Geo {
-  int D, H, F, V, L, S_max, Tq;
-};
-struct Cache {
-  float *mem, *kv, *x, *qkv, *q, *ctx, *h, *logits;
-  int* anc;
-  unsigned char* pad;
-  size_t bytes;
-};
-Cache carve(char* base, const Geo& g) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) / 256 * 256;
-    char* p = base + off;
-    off += bytes;
-    return p;
-  };
-  Cache c{};
-  const size_t f = sizeof(float);
-  c.mem = (float*)take((size_t)g.L * g.Tq * 2 * g.D * f);
-  c.kv = (float*)take((size_t)g.L * g.S_max * kRows * 2 * g.D * f);
-  c.x = (float*)take((size_t)kRows * g.D * f);
-  c.qkv = (float*)take((size_t)kRows * 3 * g.D * f);
-  c.q = (float*)take((size_t)kRows * g.D * f);
-  c.ctx = (float*)take((size_t)kRows * g.D * f);
-  c.h = (float*)take((size_t)kRows * g.F * f);
-  c.logits = (float*)take((size_t)kRows * g.V * f);
-  c.anc = (int*)take((size_t)2 * kRows * g.S_max * sizeof(int));
-  c.pad = (unsigned char*)take((size_t)g.S_max * kRows);
-  c.bytes = off + 256;
-  return c;
-}
-
-bool geometry_ok(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int S_max, int Tq) {
-  if (d_model <= 0 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || n_layers <= 0 || S_max <= 0 || Tq <= 0) return false;
-  const int dh = d_model / n_heads;
-  if (dh != 8 && dh != 16 && dh != 32 && dh != 64) return false;  // a head's features on a power-of-two fraction of a wave
-  if (d_model % 4 || d_ff % 4) return false;                        // float4 weight rows
-  if (d_model > 1024 || d_ff > 2048) return false;                  // LayerNorm rows in registers; 16 rows of d_ff in LDS (128 KB)
-  if ((size_t)std::max(S_max, Tq) * 8 > 60000) return false;        // scores + slots of one query row in LDS
-  return true;
-}
-
-#define SRUN(expr)                                                                          \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) return sfail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 }  // namespace
-
-namespace eec {
-// the batched step decoder (decoder_batch.hip) reports through eec_decoder_step_last_error() as well
-int decoder_step_fail(int code, const char* msg) { return sfail(code, msg); }
-}  // namespace eec
 
 extern "C" {
 
-const char* eec_decoder_step_last_error(void) { return g_serr.c_str(); }
+const char* eec_decoder_step_last_error(void) { return g_err.c_str(); }
 
 int eec_decoder_step_max_beams(void) { return kRows; }
 
 size_t eec_decoder_cache_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int S_max, int Tq) {
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq)) return 0;
-  return carve(nullptr, Geo{d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq}).bytes;
+  const Geo g{d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq, 1, 1};
+  return geometry_ok(g) ? carve(nullptr, g).bytes : 0;
 }
 
 int eec_decoder_begin(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, const float* enc, int Tq, int S_max,
                       int passes, void* cache, size_t cache_bytes, void* stream) {
-  if (!p || !p->layers || !enc || !cache) return sfail(EEC_ERR_BAD_ARG, "null argument");
-  if (passes != 1 && passes != 3) return sfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, p->n_layers, S_max, Tq) || S_max > p->max_len)
-    return sfail(EEC_ERR_UNSUPPORTED, "geometry not served by the step-wise decoder (use eec_decoder_forward)");
-  const Geo g{d_model, n_heads, d_ff, vocab, p->n_layers, S_max, Tq};
-  const Cache c = carve((char*)cache, g);
-  if (c.bytes > cache_bytes) return sfail(EEC_ERR_WORKSPACE, "cache too small");
+  Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, 1, 1};
+  Cache c;
+  if (int rc = check_call(enc != nullptr, &p, 1, g, nullptr, &cache, 1, cache_bytes, &c)) return rc;
+  if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model;
   for (int l = 0; l < p->n_layers; ++l) {  // memory keys | values of every layer: enc . W[D:3D]^T + b[D:3D]
     const eec_decoder_layer_params& L = p->layers[l];
     GemmArgs a = gemm_args(enc, D, 1, L.ca_in_w + (size_t)D * D, D, 1, c.mem + (size_t)l * Tq * 2 * D, 2 * D, Tq, 2 * D, D);
     a.bias = L.ca_in_b + D;
-    SRUN(launch_gemm(a, passes, st));
+    EECS_RUN(launch_gemm(a, passes, st));
   }
   return 0;
 }
@@ -529,25 +438,11 @@ int eec_decoder_begin(const eec_decoder_params* p, int d_model, int n_heads, int
 int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_model, int n_heads, int d_ff, int vocab, int pad_idx,
                            const int64_t* last_tokens, const int64_t* parent, int R, int R_prev, int s, int Tq, int S_max, int log_softmax,
                            float* out, void* const* caches, size_t cache_bytes, void* stream) {
-  if (n <= 0 || n > kGroup) return sfail(EEC_ERR_BAD_ARG, "1 .. 8 sessions per call");
-  if (!ps || !last_tokens || !out || !caches) return sfail(EEC_ERR_BAD_ARG, "null argument");
-  for (int i = 0; i < n; ++i) {
-    if (!ps[i] || !ps[i]->layers || !caches[i]) return sfail(EEC_ERR_BAD_ARG, "null argument");
-    if (ps[i]->n_layers != ps[0]->n_layers) return sfail(EEC_ERR_BAD_ARG, "the sessions of a call share one decoder geometry");
-    if (S_max > ps[i]->max_len) return sfail(EEC_ERR_UNSUPPORTED, "S_max beyond the positional-encoding table");
-  }
-  const int n_layers = ps[0]->n_layers;
-  if (!geometry_ok(d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq))
-    return sfail(EEC_ERR_UNSUPPORTED, "geometry not served by the step-wise decoder (use eec_decoder_forward)");
-  if (R <= 0 || R > kRows) return sfail(EEC_ERR_BAD_ARG, "1 .. 16 live beams per step");
-  if (s < 0 || s >= S_max) return sfail(EEC_ERR_BAD_ARG, "step index outside the cache (S_max)");
-  if (s > 0 && (R_prev <= 0 || R_prev > kRows)) return sfail(EEC_ERR_BAD_ARG, "R_prev: the previous step's beam count");
-  const Geo g{d_model, n_heads, d_ff, vocab, n_layers, S_max, Tq};
+  Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, 1, 1};
+  const Step step{R, R_prev, s};
   Cache c[kGroup];
-  for (int i = 0; i < n; ++i) {
-    c[i] = carve((char*)caches[i], g);
-    if (c[i].bytes > cache_bytes) return sfail(EEC_ERR_WORKSPACE, "cache too small");
-  }
+  if (int rc = check_call(last_tokens && out, ps, n, g, &step, caches, n, cache_bytes, c)) return rc;
+  const int n_layers = g.L;
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model, H = n_heads, dh = D / H, F = d_ff;
   const float scale = 1.0f / sqrtf((float)dh);
@@ -558,7 +453,7 @@ int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_mod
       e.a[i] = EmbedArgs{(const long long*)last_tokens + (size_t)i * R, parent ? (const long long*)parent + (size_t)i * R : nullptr, ps[i]->emb,
                          ps[i]->pe, c[i].x, c[i].pad, c[i].anc + anc_old, c[i].anc + anc_new};
     hipLaunchKernelGGL(step_embed_kernel, dim3(R, n), dim3(256), 0, st, e, s, S_max, D, vocab, pad_idx, R_prev);
-    SRUN(hipGetLastError());
+    EECS_RUN(hipGetLastError());
   }
   // one skinny_linear launch for all sessions: session i's operands through f(i)
   auto linear = [&](auto f, int N, int K, int relu, int accumulate) {
@@ -572,53 +467,53 @@ int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_mod
   for (int l = 0; l < n_layers; ++l) {
     auto L = [&](int i) -> const eec_decoder_layer_params& { return ps[i]->layers[l]; };
     // self-attention over the beam's own prefix
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm1_w, L(i).norm1_b, L(i).sa_in_w, L(i).sa_in_b, c[i].qkv, 3L * D}; }, 3 * D, D, 0, 0));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm1_w, L(i).norm1_b, L(i).sa_in_w, L(i).sa_in_b, c[i].qkv, 3L * D}; }, 3 * D, D, 0, 0));
     {
       Group<StepAttnArgs> sa{};
       for (int i = 0; i < n; ++i)
         sa.a[i] = StepAttnArgs{c[i].qkv, 3L * D, c[i].qkv + D, c[i].qkv + 2 * D, c[i].kv + (size_t)l * S_max * kRows * 2 * D, c[i].anc + anc_new, c[i].pad,
                                c[i].ctx, s, S_max, 0, D, dh, scale};
-      SRUN(step_attn<true>(sa, n, R, H, st));
+      EECS_RUN(step_attn<true>(sa, n, R, H, st));
     }
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).sa_out_w, L(i).sa_out_b, c[i].x, D}; }, D, D, 0, 1));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).sa_out_w, L(i).sa_out_b, c[i].x, D}; }, D, D, 0, 1));
     // cross-attention over the utterance's memory
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm2_w, L(i).norm2_b, L(i).ca_in_w, L(i).ca_in_b, c[i].q, D}; }, D, D, 0, 0));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm2_w, L(i).norm2_b, L(i).ca_in_w, L(i).ca_in_b, c[i].q, D}; }, D, D, 0, 0));
     {
       Group<StepAttnArgs> ca{};
       for (int i = 0; i < n; ++i)
         ca.a[i] = StepAttnArgs{c[i].q, (long)D, nullptr, nullptr, c[i].mem + (size_t)l * Tq * 2 * D, nullptr, nullptr, c[i].ctx, s, S_max, Tq, D, dh, scale};
-      SRUN(step_attn<false>(ca, n, R, H, st));
+      EECS_RUN(step_attn<false>(ca, n, R, H, st));
     }
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).ca_out_w, L(i).ca_out_b, c[i].x, D}; }, D, D, 0, 1));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).ca_out_w, L(i).ca_out_b, c[i].x, D}; }, D, D, 0, 1));
     // feed-forward, ReLU
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm3_w, L(i).norm3_b, L(i).w1, L(i).b1, c[i].h, F}; }, F, D, 1, 0));
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].h, F, nullptr, nullptr, L(i).w2, L(i).b2, c[i].x, D}; }, D, F, 0, 1));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm3_w, L(i).norm3_b, L(i).w1, L(i).b1, c[i].h, F}; }, F, D, 1, 0));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].h, F, nullptr, nullptr, L(i).w2, L(i).b2, c[i].x, D}; }, D, F, 0, 1));
   }
   const size_t out_stride = (size_t)R * vocab;
   if (log_softmax) {
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, c[i].logits, vocab}; }, vocab, D, 0, 0));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, c[i].logits, vocab}; }, vocab, D, 0, 0));
     Group<LsmArgs> lg{};
     for (int i = 0; i < n; ++i) lg.a[i] = LsmArgs{c[i].logits, out + i * out_stride};
     hipLaunchKernelGGL(step_logsoftmax_kernel, dim3(R, n), dim3(64), 0, st, lg, vocab);
-    SRUN(hipGetLastError());
+    EECS_RUN(hipGetLastError());
   } else {
-    SRUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, out + i * out_stride, vocab}; }, vocab, D, 0, 0));
+    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, out + i * out_stride, vocab}; }, vocab, D, 0, 0));
   }
   return 0;
 }
 
 int eec_beam_select(int n, int R, int V, int K, const float* logp, const float* scores_in, float penalty, float* scores_out, int64_t* parent,
                     int64_t* tok, const int64_t* tokens_old, int64_t* tokens_new, int len, int ld, int rows_ld, void* stream) {
-  if (!logp || !scores_in || !scores_out || !parent || !tok || !tokens_old || !tokens_new) return sfail(EEC_ERR_BAD_ARG, "null argument");
+  if (!logp || !scores_in || !scores_out || !parent || !tok || !tokens_old || !tokens_new) return fail(EEC_ERR_BAD_ARG, "null argument");
   if (n <= 0 || R <= 0 || R > kRows || V <= 0 || K <= 0 || K > kRows || K > (long)R * V || rows_ld < std::max(R, K) || len < 0 || ld < len + 1 ||
       !(penalty > 0.0f))
-    return sfail(EEC_ERR_BAD_ARG, "eec_beam_select: 1 .. 16 beams in and out, token rows of at least len + 1");
+    return fail(EEC_ERR_BAD_ARG, "eec_beam_select: 1 .. 16 beams in and out, token rows of at least len + 1");
   const size_t lds = (size_t)R * V * sizeof(float);
-  if (lds > 150000) return sfail(EEC_ERR_UNSUPPORTED, "eec_beam_select: R * V candidates must fit the LDS");
-  SRUN(eec::ensure_max_lds((const void*)beam_select_kernel, (int)lds));
+  if (lds > 150000) return fail(EEC_ERR_UNSUPPORTED, "eec_beam_select: R * V candidates must fit the LDS");
+  EECS_RUN(eec::ensure_max_lds((const void*)beam_select_kernel, (int)lds));
   hipLaunchKernelGGL(beam_select_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream, logp, scores_in, penalty, R, V, K, scores_out,
                      (long long*)parent, (long long*)tok, (const long long*)tokens_old, (long long*)tokens_new, len, ld, rows_ld);
-  SRUN(hipGetLastError());
+  EECS_RUN(hipGetLastError());
   return 0;
 }
 

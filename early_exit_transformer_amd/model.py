@@ -1199,6 +1199,12 @@ def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old
     dev = logp.device
     if tokens_old.shape != tokens_new.shape or tokens_old.dim() != 3 or tokens_old.size(0) != n:
         raise ValueError("token buffers: two [n, rows, steps] int64 tensors")
+    if not logp.is_cuda:  # the same step as tensor ops, for sessions that live on the host (tests/test_host.py)
+        out_s, idx = torch.topk((scores.unsqueeze(2) + logp / penalty).reshape(n, -1), k, dim=1)
+        parent, tok = torch.div(idx, V, rounding_mode="floor"), torch.remainder(idx, V)
+        tokens_new[:, :k, :length] = torch.gather(tokens_old[:, :, :length], 1, parent.unsqueeze(2).expand(-1, -1, length))
+        tokens_new[:, :k, length] = tok
+        return out_s, parent, tok
     out_s = torch.empty((n, k), dtype=torch.float32, device=dev)
     parent = torch.empty((n, k), dtype=torch.int64, device=dev)
     tok = torch.empty((n, k), dtype=torch.int64, device=dev)
@@ -1212,169 +1218,99 @@ def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old
     return out_s, parent, tok
 
 
-class DecoderSession:
-    """One utterance's step-wise AED decoding state (include/eec.h, eec_decoder_begin / eec_decoder_step): ``step(tokens,
-    parent)`` returns the log-probs of the NEXT token for every live beam, [R, V] -- what
+class DecoderStepSession:
+    """Step-wise AED decoding state over key / value caches (include/eec.h): ``step(tokens [*lead, R], parent [*lead, R] | None)``
+    returns the log-probs of the NEXT token of every live beam, [*lead, R, V] -- what
     ``model._decoder_(prefixes, enc, layer_n)[:, -1]`` returns (util/beam_infer.py:236-240) -- from the last token of every
-    beam and the row of the previous step it extends."""
+    beam and the row of the previous step it extends.  ``lead`` is the shape of the searches advanced in lockstep by the same
+    launches; a subclass owns the cache(s) and contributes the two C calls, ``_begin`` (one per tensor of ``encs`` and cache)
+    and ``_step``."""
 
-    def __init__(self, model, ps, d_ff: int, V: int, enc: Tensor, max_steps: int, nbytes: int):
+    MAX = 8  # decoders per call
+
+    def __init__(self, model, ps_list, d_ff: int, V: int, encs: List[Tensor], lead: Tuple[int, ...], max_steps: int, nbytes: int):
         lib = capi.load()
-        self.model, self.ps, self.d_ff, self.V, self.max_steps, self.nbytes = model, ps, d_ff, V, max_steps, nbytes
-        self.dev, self.Tq = enc.device, enc.size(0)
-        self.s, self.rows = 0, 0
-        self.max_beams = lib.eec_decoder_step_max_beams()
         cfg = model._cfg
-        with torch.cuda.device(self.dev):
-            self.cache = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
-            self.ptr = (self.cache.data_ptr() + 255) // 256 * 256
-            enc_c = enc.contiguous().float()
-            stream = torch.cuda.current_stream(self.dev)
-            rc = lib.eec_decoder_begin(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, enc_c.data_ptr(), self.Tq, max_steps,
-                                       int(model.decoder_passes), self.ptr, nbytes, C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_begin failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-            enc_c.record_stream(stream)
-            self.cache.record_stream(stream)
-
-    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
-        lib = capi.load()
-        cfg = self.model._cfg
-        R = int(last_tokens.numel())
-        if not 1 <= R <= self.max_beams:
-            raise ValueError(f"1 .. {self.max_beams} live beams per step, got {R}")
-        if self.s >= self.max_steps:
-            raise RuntimeError(f"the session was opened for {self.max_steps} steps")
-        if parent is not None and parent.numel() != R:
-            raise ValueError("parent: one row of the previous step per live beam")
-        with torch.cuda.device(self.dev):
-            tok = last_tokens.to(device=self.dev, dtype=torch.int64).contiguous()
-            par = parent.to(device=self.dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty((R, self.V), dtype=torch.float32, device=self.dev)
-            stream = torch.cuda.current_stream(self.dev)
-            rc = lib.eec_decoder_step(C.byref(self.ps), cfg.d_model, cfg.n_heads, self.d_ff, self.V, int(self.model.trg_pad_idx),
-                                      tok.data_ptr(), par.data_ptr() if par is not None else None, R, self.rows, self.s, self.Tq,
-                                      self.max_steps, int(log_softmax), out.data_ptr(), self.ptr, self.nbytes,
-                                      C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_step failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-            tok.record_stream(stream)
-            if par is not None:
-                par.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        return out
-
-
-class DecoderSessionGroup:
-    """The step-wise decoding sessions of several exits of ONE utterance advanced in lockstep by the same launches
-    (eec_decoder_step_multi): ``step(tokens [n, R], parent [n, R])`` -> log-probs [n, R, V]."""
-
-    MAX = 8
-
-    def __init__(self, sessions: List["DecoderSession"]):
-        s0 = sessions[0]
-        if not 1 <= len(sessions) <= self.MAX:
-            raise ValueError(f"1 .. {self.MAX} sessions per group")
-        for s in sessions:
-            if (s.dev, s.Tq, s.max_steps, s.nbytes, s.V, s.d_ff, s.s) != (s0.dev, s0.Tq, s0.max_steps, s0.nbytes, s0.V, s0.d_ff, 0):
-                raise ValueError("the sessions of a group share device, geometry and step budget, and have not stepped yet")
-        self.sessions = sessions
-        n = len(sessions)
-        self.ps = (C.POINTER(capi.EecDecoderParams) * n)(*[C.pointer(s.ps) for s in sessions])
-        self.caches = (C.c_void_p * n)(*[s.ptr for s in sessions])
-        self.s, self.rows, self.max_beams = 0, 0, s0.max_beams
-
-    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
-        lib = capi.load()
-        s0 = self.sessions[0]
-        cfg = s0.model._cfg
-        n = len(self.sessions)
-        if last_tokens.dim() != 2 or last_tokens.size(0) != n:
-            raise ValueError(f"last_tokens must be [{n}, live beams]")
-        R = int(last_tokens.size(1))
-        if not 1 <= R <= self.max_beams:
-            raise ValueError(f"1 .. {self.max_beams} live beams per step, got {R}")
-        if self.s >= s0.max_steps:
-            raise RuntimeError(f"the sessions were opened for {s0.max_steps} steps")
-        if parent is not None and tuple(parent.shape) != (n, R):
-            raise ValueError("parent: one row of the previous step per live beam and session")
-        with torch.cuda.device(s0.dev):
-            tok = last_tokens.to(device=s0.dev, dtype=torch.int64).contiguous()
-            par = parent.to(device=s0.dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty((n, R, s0.V), dtype=torch.float32, device=s0.dev)
-            stream = torch.cuda.current_stream(s0.dev)
-            rc = lib.eec_decoder_step_multi(n, self.ps, cfg.d_model, cfg.n_heads, s0.d_ff, s0.V, int(s0.model.trg_pad_idx), tok.data_ptr(),
-                                            par.data_ptr() if par is not None else None, R, self.rows, self.s, s0.Tq, s0.max_steps,
-                                            int(log_softmax), out.data_ptr(), self.caches, s0.nbytes, C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_step_multi failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-            tok.record_stream(stream)
-            if par is not None:
-                par.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        for s in self.sessions:  # a session that joined a group is advanced only through it
-            s.s, s.rows = self.s, R
-        return out
-
-
-class DecoderBatchSession:
-    """Step-wise AED decoding of E exits x B utterances of a padded batch in lockstep, one cache for all of them
-    (include/eec.h, eec_decoder_batch_begin / eec_decoder_batch_step): ``step(tokens [E, B, R], parent [E, B, R] | None)`` ->
-    log-probs [E, B, R, V].  The launches of a step do not depend on E or B (csrc/decoder_batch.hip)."""
-
-    def __init__(self, model, ps_list, d_ff: int, V: int, taps: Tensor, max_steps: int, nbytes: int):
-        lib = capi.load()
-        self.model, self.d_ff, self.V, self.max_steps, self.nbytes = model, d_ff, V, max_steps, nbytes
-        self.E, self.B, self.Tq = taps.size(0), taps.size(1), taps.size(2)
-        self.dev = taps.device
+        self.lead, self.V, self.max_steps, self.nbytes = lead, V, max_steps, nbytes
+        self.dev, self.Tq = encs[0].device, encs[0].size(-2)
         self.s, self.rows = 0, 0
         self.max_beams = lib.eec_decoder_step_max_beams()
         self._ps_keep = ps_list
-        self.ps = (C.POINTER(capi.EecDecoderParams) * self.E)(*[C.pointer(p) for p in ps_list])
-        cfg = model._cfg
+        self.ps = (C.POINTER(capi.EecDecoderParams) * len(ps_list))(*[C.pointer(p) for p in ps_list])
+        self.geo = (cfg.d_model, cfg.n_heads, d_ff, V)
+        self.pad_idx, passes = int(model.trg_pad_idx), int(model.decoder_passes)
         with torch.cuda.device(self.dev):
-            self.cache = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
-            self.ptr = (self.cache.data_ptr() + 255) // 256 * 256
-            taps_c = taps.contiguous().float()
             stream = torch.cuda.current_stream(self.dev)
-            rc = lib.eec_decoder_batch_begin(self.ps, self.E, self.B, cfg.d_model, cfg.n_heads, d_ff, V, taps_c.data_ptr(), self.Tq, max_steps,
-                                             int(model.decoder_passes), self.ptr, nbytes, C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_batch_begin failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-            taps_c.record_stream(stream)
-            self.cache.record_stream(stream)
+            self._caches = [_aligned_ws(nbytes, self.dev) for _ in encs]
+            self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
+            for i, enc in enumerate(encs):
+                enc_c = enc.contiguous().float()
+                self._check(lib, self._begin(lib, i, enc_c.data_ptr(), passes, C.c_void_p(stream.cuda_stream)), "begin")
+                enc_c.record_stream(stream)
+                self._caches[i][0].record_stream(stream)
 
-    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None) -> Tensor:
+    def _check(self, lib, rc: int, what: str):
+        if rc != 0:
+            raise RuntimeError(f"{self.entry}{what} failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
+
+    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
         lib = capi.load()
-        cfg = self.model._cfg
-        E, B = self.E, self.B
-        if last_tokens.dim() != 3 or tuple(last_tokens.shape[:2]) != (E, B):
-            raise ValueError(f"last_tokens must be [{E}, {B}, live beams]")
-        R = int(last_tokens.size(2))
+        lead = self.lead
+        if last_tokens.dim() != len(lead) + 1 or last_tokens.shape[:-1] != lead:
+            raise ValueError(f"last_tokens must be [{', '.join(map(str, lead + ('live beams',)))}]")
+        R = int(last_tokens.size(-1))
         if not 1 <= R <= self.max_beams:
-            raise ValueError(f"1 .. {self.max_beams} live beams per utterance, got {R}")
+            raise ValueError(f"1 .. {self.max_beams} live beams per search and step, got {R}")
         if self.s >= self.max_steps:
             raise RuntimeError(f"the session was opened for {self.max_steps} steps")
-        if parent is not None and tuple(parent.shape) != (E, B, R):
-            raise ValueError("parent: one row of the previous step per live beam, exit and utterance")
-        with torch.cuda.device(self.dev):
-            tok = last_tokens.to(device=self.dev, dtype=torch.int64).contiguous()
-            par = parent.to(device=self.dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty((E, B, R, self.V), dtype=torch.float32, device=self.dev)
-            stream = torch.cuda.current_stream(self.dev)
-            rc = lib.eec_decoder_batch_step(self.ps, E, B, cfg.d_model, cfg.n_heads, self.d_ff, self.V, int(self.model.trg_pad_idx), tok.data_ptr(),
-                                            par.data_ptr() if par is not None else None, R, self.rows, self.s, self.Tq, self.max_steps,
-                                            out.data_ptr(), self.ptr, self.nbytes, C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_batch_step failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
+        if parent is not None and parent.shape != last_tokens.shape:
+            raise ValueError("parent: one row of the previous step per live beam of every search")
+        dev = self.dev
+        with torch.cuda.device(dev):
+            tok = last_tokens.to(device=dev, dtype=torch.int64).contiguous()
+            par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            self._check(lib, self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
+                                        C.c_void_p(stream.cuda_stream)), "step")
             tok.record_stream(stream)
             if par is not None:
                 par.record_stream(stream)
         self.s += 1
         self.rows = R
         return out
+
+
+class _ExitSessions(DecoderStepSession):
+    """n <= 8 exits of ONE utterance, a cache per exit (csrc/decoder_step.hip); ``lead`` is (n,), or () for a single exit.  A
+    single exit is a group of one, as eec_decoder_step is eec_decoder_step_multi with n = 1."""
+
+    entry = "eec_decoder_"
+
+    def _begin(self, lib, i, enc, passes, stream):
+        return lib.eec_decoder_begin(self.ps[i], *self.geo, enc, self.Tq, self.max_steps, passes, self.ptrs[i], self.nbytes, stream)
+
+    def _step(self, lib, tok, par, R, log_softmax, out, stream):
+        return lib.eec_decoder_step_multi(len(self.ps), self.ps, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps,
+                                          log_softmax, out, self.ptrs, self.nbytes, stream)
+
+
+class _BatchSession(DecoderStepSession):
+    """E exits x B utterances of a padded batch, one cache for all of them (csrc/decoder_batch.hip); ``lead`` is (E, B).  The
+    launches of a step do not depend on E or B.  Log-probs only."""
+
+    entry = "eec_decoder_batch_"
+    E = property(lambda self: self.lead[0])
+    B = property(lambda self: self.lead[1])
+
+    def _begin(self, lib, i, taps, passes, stream):
+        return lib.eec_decoder_batch_begin(self.ps, *self.lead, *self.geo, taps, self.Tq, self.max_steps, passes, self.ptrs[0], self.nbytes, stream)
+
+    def _step(self, lib, tok, par, R, log_softmax, out, stream):
+        if not log_softmax:
+            raise ValueError("the batch session returns log-probs only")
+        return lib.eec_decoder_batch_step(self.ps, *self.lead, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps, out,
+                                          self.ptrs[0], self.nbytes, stream)
 
 
 class _DecoderTrainFn(torch.autograd.Function):
@@ -1485,8 +1421,12 @@ class full_conformer(_HipEncoderMixin, nn.Module):
 
     def _encoder_(self, src: Tensor, lengths: Tensor, layer_n: int) -> Tensor:
         """Pre-head activations after ``layer_n`` exit groups, [B, T', D] (early_exit.py:719-737)."""
-        n = int(layer_n) if 1 <= int(layer_n) <= self._cfg.n_exits else self._cfg.n_exits  # reference loop
-        return self._run_encoder(src, lengths, want_out=False, want_x=True, n_groups=n)[2]
+        return self._run_encoder(src, lengths, want_out=False, want_x=True, n_groups=self._exit(layer_n))[2]
+
+    def _exit(self, layer_n) -> int:
+        """The exit ``layer_n`` stands for, 1 .. n_exits: any other value runs all groups, as the reference's loop does."""
+        n = int(layer_n)
+        return n if 1 <= n <= self._cfg.n_exits else self._cfg.n_exits
 
     decoder_passes = 3  # the HIP decoder's GEMM operands: 3 = bf16 hi/lo split (~1e-5 of fp32), 1 = plain bf16
 
@@ -1540,16 +1480,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             for t in tensors:
                 if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
                     raise RuntimeError(f"decoder parameters must be contiguous fp32 tensors on {dev}")
-            layers = (capi.EecDecoderLayerParams * len(dec.layers))()
-            for l, layer in enumerate(dec.layers):
-                sd = dict(layer.named_parameters())
-                for field, name in capi.DECODER_LAYER_KEYS.items():
-                    setattr(layers[l], field, sd[name].data_ptr())
-            ps = capi.EecDecoderParams(self.emb.weight.data_ptr(), self.positional_encoder_2.pe.data_ptr(), layers, len(dec.layers),
-                                       self.positional_encoder_2.pe.size(0), self.layer_norm.weight.data_ptr(),
-                                       self.layer_norm.bias.data_ptr(), self.linears_2[idx].weight.data_ptr(),
-                                       self.linears_2[idx].bias.data_ptr())
-            ent = (key, ps, layers)
+            ent = (key, *self._decoder_struct(idx, dict(self._decoder_named_params(idx)), with_pe=True))
             cache[idx] = ent
         return ent[1], dec.layers[0].linear1.out_features, self.linears_2[idx].out_features
 
@@ -1569,8 +1500,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             shared = Bm > 1 and enc.stride(0) == 0  # beam search: one utterance expanded over the beams (util/beam_infer.py:233)
             enc_c = (enc[:1] if shared else enc).contiguous().float()
             nbytes = lib.eec_decoder_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, Bm, S, Tq)
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-            ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+            ws, ws_ptr = _aligned_ws(nbytes, dev)
             out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = lib.eec_decoder_forward(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), trg_c.data_ptr(),
@@ -1582,63 +1512,70 @@ class full_conformer(_HipEncoderMixin, nn.Module):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out
 
-    def decoder_session(self, enc: Tensor, layer_n: int, max_steps: int) -> Optional["DecoderSession"]:
-        """Step-wise decoding of ONE utterance with a key / value cache (csrc/decoder_step.hip): ``enc`` [1, T', D] or
-        [T', D] is exit ``layer_n``'s encoder output, ``max_steps`` the longest prefix that will be decoded.  None when this
-        geometry or device is not served (callers then use ``_decoder_`` on the whole prefix, as the reference does)."""
-        if not enc.is_cuda or (self.training and torch.is_grad_enabled()):
+    def _steps_served(self, t: Tensor, max_steps: int) -> bool:
+        return t.is_cuda and not (self.training and torch.is_grad_enabled()) and 1 <= max_steps <= self.positional_encoder_2.pe.size(0)
+
+    def _decoders(self, layer_ns: Sequence[int], dev):
+        """``([eec_decoder_params of every exit of layer_ns], d_ff, V, n_layers)``, or None unless they share one geometry."""
+        idxs = [self._exit(n) - 1 for n in layer_ns]
+        params = [self._decoder_params(i, dev) for i in idxs]
+        geo = {(p[1], p[2], len(self.decoders[i].layers)) for p, i in zip(params, idxs)}
+        return ([p[0] for p in params], *geo.pop()) if len(geo) == 1 else None
+
+    def _exit_sessions(self, encs: Sequence[Tensor], layer_ns: Sequence[int], max_steps: int, lead) -> Optional["DecoderStepSession"]:
+        if any(not self._steps_served(e, max_steps) or (e.dim() != 2 and e.size(0) != 1) for e in encs):
             return None
-        idx = (int(layer_n) if 1 <= int(layer_n) <= self._cfg.n_exits else self._cfg.n_exits) - 1
-        enc2 = enc.reshape(-1, enc.size(-1)) if enc.dim() == 2 or enc.size(0) == 1 else None
-        if enc2 is None or max_steps < 1 or max_steps > self.positional_encoder_2.pe.size(0):
+        encs = [e.reshape(-1, e.size(-1)) for e in encs]
+        if len({(e.device, e.size(0)) for e in encs}) != 1:
+            raise ValueError("the exits of a group share device and geometry")
+        dec = self._decoders(layer_ns, encs[0].device)
+        if dec is None:
             return None
-        ps, d_ff, V = self._decoder_params(idx, enc.device)
-        lib = capi.load()
+        ps, d_ff, V, n_layers = dec
         cfg = self._cfg
-        nbytes = lib.eec_decoder_cache_bytes(cfg.d_model, cfg.n_heads, d_ff, V, len(self.decoders[idx].layers), int(max_steps), enc2.size(0))
+        nbytes = capi.load().eec_decoder_cache_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, int(max_steps), encs[0].size(0))
         if nbytes == 0:
             return None
-        return DecoderSession(self, ps, d_ff, V, enc2, int(max_steps), nbytes)
+        return _ExitSessions(self, ps, d_ff, V, encs, lead, int(max_steps), nbytes)
 
-    def decoder_session_group(self, encs: Sequence[Tensor], layer_ns: Sequence[int], max_steps: int) -> Optional["DecoderSessionGroup"]:
-        """Sessions for exits ``layer_ns`` of one utterance (``encs[i]``: that exit's encoder output), advanced together by
-        ``group.step``; None when a session is not available or there are more than 8 exits."""
-        if not 1 <= len(layer_ns) <= DecoderSessionGroup.MAX or len(encs) != len(layer_ns):
-            return None
-        sessions = [self.decoder_session(e, n, max_steps) for e, n in zip(encs, layer_ns)]
-        if any(s is None for s in sessions):
-            return None
-        return DecoderSessionGroup(sessions)
+    def decoder_session(self, enc: Tensor, layer_n: int, max_steps: int) -> Optional["DecoderStepSession"]:
+        """Step-wise decoding of ONE utterance with a key / value cache (csrc/decoder_step.hip): ``enc`` [1, T', D] or
+        [T', D] is exit ``layer_n``'s encoder output, ``max_steps`` the longest prefix that will be decoded;
+        ``step(tokens [R], parent [R])`` -> [R, V].  None when this geometry or device is not served (callers then use
+        ``_decoder_`` on the whole prefix, as the reference does)."""
+        return self._exit_sessions([enc], [layer_n], max_steps, ())
 
-    def decoder_batch_session(self, taps, layer_ns: Sequence[int], max_steps: int) -> Optional["DecoderBatchSession"]:
+    def decoder_session_group(self, encs: Sequence[Tensor], layer_ns: Sequence[int], max_steps: int) -> Optional["DecoderStepSession"]:
+        """One session for exits ``layer_ns`` of one utterance (``encs[i]``: that exit's encoder output), advanced together:
+        ``step(tokens [n, R], parent [n, R])`` -> [n, R, V]; None when a session is not available or there are more than 8 exits."""
+        if not 1 <= len(layer_ns) <= DecoderStepSession.MAX or len(encs) != len(layer_ns):
+            return None
+        return self._exit_sessions(encs, layer_ns, max_steps, (len(layer_ns),))
+
+    def decoder_batch_session(self, taps, layer_ns: Sequence[int], max_steps: int) -> Optional["DecoderStepSession"]:
         """Step-wise decoding of exits ``layer_ns`` for every utterance of a padded batch in lockstep (csrc/decoder_batch.hip):
         ``taps`` [E, B, T', D] (or E tensors [B, T', D]) holds exit ``layer_ns[e]``'s encoder output of every utterance,
-        ``max_steps`` the longest prefix that will be decoded.  None when this geometry or device is not served."""
+        ``max_steps`` the longest prefix that will be decoded; ``step(tokens [E, B, R], parent [E, B, R])`` -> [E, B, R, V].
+        None when this geometry or device is not served."""
         if isinstance(taps, (list, tuple)):
             if not taps:
                 return None
             taps = torch.stack(list(taps))
-        if taps.dim() != 4 or taps.size(0) != len(layer_ns) or not taps.is_cuda or (self.training and torch.is_grad_enabled()):
+        if taps.dim() != 4 or taps.size(0) != len(layer_ns) or taps.size(3) != self._cfg.d_model or not self._steps_served(taps, max_steps):
             return None
-        if max_steps < 1 or max_steps > self.positional_encoder_2.pe.size(0) or taps.size(3) != self._cfg.d_model:
+        dec = self._decoders(layer_ns, taps.device)
+        if dec is None:
             return None
-        idxs = [(int(n) if 1 <= int(n) <= self._cfg.n_exits else self._cfg.n_exits) - 1 for n in layer_ns]
-        params = [self._decoder_params(i, taps.device) for i in idxs]
-        d_ff, V = params[0][1], params[0][2]
-        n_layers = len(self.decoders[idxs[0]].layers)
-        if any((p[1], p[2], len(self.decoders[i].layers)) != (d_ff, V, n_layers) for p, i in zip(params, idxs)):
-            return None
-        lib = capi.load()
+        ps, d_ff, V, n_layers = dec
         cfg = self._cfg
-        nbytes = lib.eec_decoder_batch_cache_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, taps.size(0), taps.size(1), int(max_steps),
-                                                   taps.size(2))
+        E, B, Tq = taps.shape[:3]
+        nbytes = capi.load().eec_decoder_batch_cache_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, E, B, int(max_steps), Tq)
         if nbytes == 0:
             return None
-        return DecoderBatchSession(self, [p[0] for p in params], d_ff, V, taps, int(max_steps), nbytes)
+        return _BatchSession(self, ps, d_ff, V, [taps], (E, B), int(max_steps), nbytes)
 
     def _decoder_(self, trg: Tensor, enc: Tensor, layer_n: int) -> Tensor:
-        idx = (int(layer_n) if 1 <= int(layer_n) <= self._cfg.n_exits else self._cfg.n_exits) - 1
-        return self._decode_one(trg, enc, idx, log_softmax=True)
+        return self._decode_one(trg, enc, self._exit(layer_n) - 1, log_softmax=True)
 
     def forward(self, src: Tensor, lengths: Tensor, trg: Tensor):
         if self.training:

@@ -1,5 +1,5 @@
 """Batched AED beam search (csrc/decoder_batch.hip, eec_decoder_batch_*; BeamInference.beam_search_batch / decode_batch) against
-the per-utterance path it replaces (DecoderSessionGroup / beam_search_exits / decode_all_exits).  The batched linears run on
+the per-utterance path it replaces (decoder_session_group / beam_search_exits / decode_all_exits).  The batched linears run on
 bf16x3 MFMA operands and the per-utterance decoder in plain fp32, so log-probs agree to the bound the repository applies to bf16x3
 decoder GEMMs, 2e-5 * max(10, max |logp|), and searches agree up to near-ties."""
 import os
@@ -39,7 +39,7 @@ def fixture_model():
 
 
 def _batch_step_vs_groups(fc, E, B, Tq, rows, seed, V=256):
-    """Steps of one batch session against one DecoderSessionGroup per utterance, random tokens (PAD now and then) and parents
+    """Steps of one batch session against one session group (decoder_session_group) per utterance, random tokens (PAD now and then) and parents
     per (exit, utterance), beam counts ``rows`` step by step.  Returns the worst error over its bound."""
     g = torch.Generator().manual_seed(seed)
     D = fc._cfg.d_model

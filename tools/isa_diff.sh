@@ -18,10 +18,9 @@ cp -r "$repo/early_exit_transformer_amd/csrc" "$work/new/early_exit_transformer_
 cp "$repo/tools/mfma16_gemm_check.hip" "$work/new/tools/"
 cp -r "$repo/include" "$work/new/"
 
-# object name, source (relative to csrc), extra flags -- mirrors early_exit_transformer_amd/csrc/Makefile
+# object name, source (relative to csrc), extra flags: the Makefile's SRCS, then its extra objects of ffn.hip and the check program
 objects() {
-  for s in capi ffn linear attention conv stem ctc pack frontend ctc_beam train_kernels train_attention train \
-           decoder decoder_step decoder_train; do echo "$s $s.hip -fPIC"; done
+  for s in $(sed -n 's/^SRCS := //p' "$repo/early_exit_transformer_amd/csrc/Makefile"); do echo "${s%.hip} $s -fPIC"; done
   echo "ffn512 ffn.hip -fPIC -DEEC_FFN_D=512"
   echo "ffn_train ffn.hip -fPIC -DEEC_FFN_TRAIN"
   echo "ffn_train_bwd ffn.hip -fPIC -DEEC_FFN_TRAIN_BWD"
@@ -34,7 +33,7 @@ compile() {  # <tree> <side> <obj> <src> <flags...>
   "$HIPCC" -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -Wno-pass-failed "$@" \
     --cuda-$side-only -S "$src" -o - 2>"$work/$tree.$obj.$side.err" | grep -v __hip_cuid_ > "$work/$tree.$obj.$side.s"
 }
-export -f compile; export work HIPCC
+export -f compile; export work HIPCC repo
 
 objects | while read -r obj src flags; do
   for tree in old new; do for side in device host; do echo "$tree $side $obj $src $flags"; done; done
