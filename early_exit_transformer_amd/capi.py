@@ -6,6 +6,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import torch
+
 from .build import LIB_PATH
 
 PREC_F16X3, PREC_MIXED, PREC_F16, PREC_F16F8 = 0, 1, 2, 3
@@ -111,10 +113,9 @@ def load() -> C.CDLL:
         raise RuntimeError(
             f"{LIB_PATH} not found: the HIP library is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (or early_exit_transformer_amd.build.build_library()). There is no CPU fallback.")
-    # torch first: its bundled libamdhip64.so carries the soname libeec.so asks for (libamdhip64.so.7), so the loader
-    # reuses it.  Loaded the other way round, /opt/rocm's copy comes in as well and one process holds two HIP runtimes
-    # (the second to initialise then reports "no ROCm-capable device").
-    import torch  # noqa: F401
+    # torch is imported first (top of this module): its bundled libamdhip64.so carries the soname libeec.so asks for
+    # (libamdhip64.so.7), so the loader reuses it.  Loaded the other way round, /opt/rocm's copy comes in as well and one
+    # process holds two HIP runtimes (the second to initialise then reports "no ROCm-capable device").
     lib = C.CDLL(LIB_PATH)
     lib.eec_last_error.restype = C.c_char_p
     lib.eec_abi_version.restype = C.c_int
@@ -232,7 +233,124 @@ def load() -> C.CDLL:
     return lib
 
 
-def check(rc: int, what: str) -> None:
+def check(rc: int, what: str, err: str = "eec_last_error") -> None:
+    """Raise on a non-zero return code with the message of the entry's family (``err``: its ``eec_*_last_error()`` symbol)."""
     if rc != 0:
-        msg = load().eec_last_error().decode(errors="replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+        raise RuntimeError(f"{what} failed (code {rc}): {getattr(load(), err)().decode(errors='replace')}")
+
+
+def stream_ptr(dev) -> C.c_void_p:
+    """The current HIP stream of ``dev``, as the C entries take it."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def aligned_ws(nbytes: int, dev):
+    """A device workspace of ``nbytes`` usable bytes from a 256-byte boundary on: (tensor that owns it, aligned address)."""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return ws, (ws.data_ptr() + 255) // 256 * 256
+
+
+def require_fp32(name: str, t, dev):
+    """``t``, which a kernel is about to read through its raw pointer."""
+    if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous fp32 tensor on {dev}")
+    return t
+
+
+def new_seed() -> int:
+    """A dropout seed from torch's CPU generator (so ``torch.manual_seed`` fixes the masks)."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def to_device(t, dev: torch.device, dtype: torch.dtype = torch.int64):
+    """``t.to(dev, dtype).contiguous()``; a small CPU int64 tensor (the collate's ``lengths`` are CPU tensors in the
+    reference, train.py:34,54) travels in a kernel's argument block instead (eec_upload_i64): a host-to-device copy in front
+    of the forward drains the host's launch queue and leaves a hole on the stream once per step."""
+    if t.is_cuda or dev.type != "cuda" or dtype != torch.int64 or t.numel() == 0:
+        return t.to(device=dev, dtype=dtype).contiguous()
+    lib = load()
+    if t.numel() > lib.eec_upload_i64_max():
+        return t.to(device=dev, dtype=dtype).contiguous()
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+    host = t.to(torch.int64).contiguous()
+    out = torch.empty(host.shape, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.eec_upload_i64(host.data_ptr(), host.numel(), out.data_ptr(), stream_ptr(dev)), "eec_upload_i64")
+    return out
+
+
+def layer_params(ptr, prefix: str, n_groups: int, n_layers: int):
+    """HOST array of EecLayerParams for ``{prefix}.{g}.conformer_layers.{l}.*`` (group-major)."""
+    layers = (EecLayerParams * (n_groups * n_layers))()
+    for g in range(n_groups):
+        for l in range(n_layers):
+            lp = layers[g * n_layers + l]
+            for field, suffix in LAYER_KEYS.items():
+                setattr(lp, field, ptr(f"{prefix}.{g}.conformer_layers.{l}.{suffix}"))
+    return layers
+
+
+def params_struct(ptr, n_groups: int, n_layers: int, layers: str, stem=(None, None), head: Optional[str] = None,
+                  pe: Optional[str] = None):
+    """The one map from state_dict names to EecParams.  ``ptr(name)`` gives a tensor's address (or None: a null field);
+    ``layers`` is the prefix of the Conformer groups, ``stem`` the key prefixes of the one or two stem convolutions, ``head``
+    the key prefix of exit ``{e}``'s Linear, ``pe`` the key of the sinusoid table -- None for what is not packed.  Returns
+    (struct, the host arrays it points into: keep them alive as long as the struct)."""
+    at = lambda key: ptr(key) if key else None  # noqa: E731
+    lay = layer_params(ptr, layers, n_groups, n_layers)
+    hw = (C.c_void_p * n_groups)(*[ptr(head.format(e=e) + ".weight") for e in range(n_groups)]) if head else None
+    hb = (C.c_void_p * n_groups)(*[ptr(head.format(e=e) + ".bias") for e in range(n_groups)]) if head else None
+    st = EecParams(at(stem[0] and stem[0] + ".weight"), at(stem[0] and stem[0] + ".bias"),
+                   at(stem[1] and stem[1] + ".weight"), at(stem[1] and stem[1] + ".bias"), at(pe), lay, hw, hb)
+    return st, (lay, hw, hb)
+
+
+class EncoderHandle:
+    """Owner of one libeec encoder handle: its device, the key of what is packed into it, and the bounded caches of the
+    workspaces its entry points take.  One handle lives on one device (include/eec.h); the owner destroys it when the
+    model moved to another one, and when the owner goes."""
+
+    def __init__(self, cfg: EecConfig):
+        self.cfg, self.h, self.device, self.key = cfg, None, None, None
+        self._ws = {"": {}, "group_": {}}  # eec_encoder_workspace_bytes / eec_encoder_group_workspace_bytes
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def destroy(self) -> None:
+        if self.h is not None:
+            load().eec_encoder_destroy(self.h)
+            self.h = self.key = None
+            for cache in self._ws.values():
+                cache.clear()
+
+    def ensure(self, device, tensors, pack):
+        """The handle on ``device`` with ``tensors`` packed: ``pack(handle)`` runs when a tensor of the list was written,
+        moved or replaced since the last packing (``_version``, ``data_ptr``) and on a fresh handle."""
+        key = (device, tuple(t._version for t in tensors), tuple(t.data_ptr() for t in tensors))
+        if self.h is None or key != self.key:
+            if self.h is not None and self.device != device:
+                self.destroy()  # model.to(another device): the packed-weight arena lives on the old one
+            if self.h is None:
+                h = C.c_void_p()
+                check(load().eec_encoder_create(C.byref(self.cfg), C.byref(h)), "eec_encoder_create")
+                self.h, self.device = h, device
+            pack(self.h)
+            self.key = key
+        return self.h
+
+    def workspace(self, kind: str, B: int, T: int, device):
+        """(tensor, aligned address, bytes from there on) for ``eec_encoder_{kind}workspace_bytes(handle, B, T)``: at most
+        five geometries are kept."""
+        cache = self._ws[kind]
+        k = (B, T, device.index or 0)
+        ent = cache.get(k)
+        if ent is None:
+            if len(cache) > 4:
+                cache.clear()
+            ws, ptr = aligned_ws(getattr(load(), f"eec_encoder_{kind}workspace_bytes")(self.h, B, T), device)
+            ent = cache[k] = (ws, ptr, ws.numel() - (ptr - ws.data_ptr()))
+        return ent

@@ -1,0 +1,122 @@
+"""The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), greedy and prefix-beam
+decoding (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
+stream; there is no CPU path."""
+from __future__ import annotations
+
+from typing import Tuple
+
+import torch
+from torch import Tensor
+
+from . import capi
+from .capi import stream_ptr, to_device
+
+
+def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
+    """``clamp(lengths / 4, max=T').to(int)`` (early_exit.py:623) on the device: int64 [B] -> int32 [B]."""
+    if not lengths.is_cuda:
+        raise RuntimeError("encoder_lengths runs on a HIP device only")
+    lengths = lengths.to(torch.int64).contiguous()
+    out = torch.empty((lengths.numel(),), dtype=torch.int32, device=lengths.device)
+    with torch.cuda.device(lengths.device):
+        capi.check(capi.load().eec_encoder_lengths(lengths.data_ptr(), lengths.numel(), int(t_out), out.data_ptr(),
+                                                   stream_ptr(lengths.device)), "eec_encoder_lengths")
+    return out
+
+
+def greedy_ctc(logp: Tensor, blank: int = 0) -> Tuple[Tensor, Tensor]:
+    """[N, T', V] fp32 log-probs on the GPU -> (tokens [N, T'] int32, counts [N] int32)."""
+    if not logp.is_cuda:
+        raise RuntimeError("greedy_ctc runs on a HIP device only")
+    logp = logp.contiguous().float()
+    N, Tq, V = logp.shape
+    tokens = torch.empty((N, Tq), dtype=torch.int32, device=logp.device)
+    counts = torch.empty((N,), dtype=torch.int32, device=logp.device)
+    with torch.cuda.device(logp.device):
+        capi.check(capi.load().eec_greedy_ctc(logp.data_ptr(), N, Tq, V, blank, tokens.data_ptr(),
+                                              counts.data_ptr(), stream_ptr(logp.device)), "eec_greedy_ctc")
+    return tokens, counts
+
+
+def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
+                    skip_drops_frame: bool = False):
+    """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
+    sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
+    ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
+    readings of the third-party decoder's skip rule, include/eec.h).  Returns (tokens [N, T'] int32, counts [N] int32,
+    scores [N] fp32)."""
+    if not logp.is_cuda:
+        raise RuntimeError("ctc_beam_decode runs on a HIP device only")
+    logp = logp.contiguous().float()
+    N, Tq, V = logp.shape
+    dev = logp.device
+    lib = capi.load()
+    tokens = torch.empty((N, Tq), dtype=torch.int32, device=dev)
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    scores = torch.empty((N,), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_ctc_beam_decode_ex(logp.data_ptr(), N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)),
+                                              ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), stream_ptr(dev)),
+                   "eec_ctc_beam_decode")
+    return tokens, counts, scores
+
+
+class _ExitCtcLossFn(torch.autograd.Function):
+    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (eec_ctc_loss_forward / _backward):
+    what autograd computes through the reference's loop of E nn.CTCLoss calls (train.py:60-68)."""
+
+    @staticmethod
+    def forward(ctx, enc_out, tg, tl, blank):
+        E, B, Tq, V = enc_out.shape
+        if V > 256 or V % 4:
+            raise ValueError(f"exit_ctc_losses with a gradient needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
+                             "the CTC gradient kernel holds a vocabulary row in one wave")
+        dev = enc_out.device
+        lib = capi.load()
+        nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
+        out = torch.empty((E,), dtype=torch.float32, device=dev)
+        ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
+        with torch.cuda.device(dev):
+            capi.check(lib.eec_ctc_loss_forward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
+                                                nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+        ctx.save_for_backward(enc_out, tg, tl, nll, ws)
+        ctx.blank, ctx.ws_ptr = blank, ws_ptr
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        enc_out, tg, tl, nll, ws = ctx.saved_tensors
+        if getattr(ctx, "used", False):
+            raise RuntimeError("exit_ctc_losses: backward through the same forward twice (its workspace is consumed)")
+        ctx.used = True
+        E, B, Tq, V = enc_out.shape
+        dev = enc_out.device
+        g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
+        dlogp = torch.empty_like(enc_out)
+        with torch.cuda.device(dev):
+            capi.check(capi.load().eec_ctc_loss_backward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1),
+                                                         ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(), dlogp.data_ptr(),
+                                                         stream_ptr(dev)), "eec_ctc_loss_backward")
+        return dlogp, None, None, None
+
+
+def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank: int = 0) -> Tensor:
+    """Per-exit CTC losses [E] of an encoder output [E, B, T', V] in ONE launch: what train.py:53-65 computes with
+    E separate nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) calls and input length T' for every
+    utterance.  ``.sum()`` is the reference's training loss.  Differentiable with respect to ``enc_out`` (HIP backward:
+    beta recursion + dense gradient, the values torch autograd returns for the reference's loop)."""
+    if not enc_out.is_cuda:
+        raise RuntimeError("exit_ctc_losses runs on a HIP device only")
+    enc_out = enc_out.contiguous().float()
+    dev = enc_out.device
+    tg, tl = to_device(targets, dev), to_device(target_len, dev)
+    E, B, Tq, V = enc_out.shape
+    if torch.is_grad_enabled() and enc_out.requires_grad:
+        return _ExitCtcLossFn.apply(enc_out, tg, tl, blank)
+    nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
+    out = torch.empty((E,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().eec_ctc_loss(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
+                                            nll.data_ptr(), out.data_ptr(), stream_ptr(dev)), "eec_ctc_loss")
+    return out

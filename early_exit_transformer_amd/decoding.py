@@ -1,0 +1,196 @@
+"""Attention-decoder side of ``full_conformer`` on the HIP path: one step of beam bookkeeping (``beam_select``), the step-wise
+decoding sessions over key / value caches (csrc/decoder_step.hip, decoder_batch.hip) and the decoder's training step behind
+autograd (csrc/decoder_train.hip)."""
+from __future__ import annotations
+
+import ctypes as C
+from functools import partial
+from typing import List, Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import capi
+from .capi import aligned_ws, stream_ptr
+
+_step_check = partial(capi.check, err="eec_decoder_step_last_error")
+_train_check = partial(capi.check, err="eec_decoder_train_last_error")
+
+
+def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old: Tensor, tokens_new: Tensor, length: int):
+    """One step of beam-search bookkeeping for n searches in lockstep, in one launch (eec_beam_select): the ``k`` best of
+    ``scores[i, r] + logp[i, r, v] / penalty`` per search i, best first -> ``(scores [n, k], parent [n, k], token [n, k])``,
+    and ``tokens_new[i, b, :length + 1] = cat(tokens_old[i, parent[i, b], :length], token[i, b])``.  What
+    util/beam_infer.py:241-262 does with topk / index / cat, for every exit of an utterance at once."""
+    n, R, V = logp.shape
+    dev = logp.device
+    if tokens_old.shape != tokens_new.shape or tokens_old.dim() != 3 or tokens_old.size(0) != n:
+        raise ValueError("token buffers: two [n, rows, steps] int64 tensors")
+    if not logp.is_cuda:  # the same step as tensor ops, for sessions that live on the host (tests/test_host.py)
+        out_s, idx = torch.topk((scores.unsqueeze(2) + logp / penalty).reshape(n, -1), k, dim=1)
+        parent, tok = torch.div(idx, V, rounding_mode="floor"), torch.remainder(idx, V)
+        tokens_new[:, :k, :length] = torch.gather(tokens_old[:, :, :length], 1, parent.unsqueeze(2).expand(-1, -1, length))
+        tokens_new[:, :k, length] = tok
+        return out_s, parent, tok
+    out_s = torch.empty((n, k), dtype=torch.float32, device=dev)
+    parent = torch.empty((n, k), dtype=torch.int64, device=dev)
+    tok = torch.empty((n, k), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _step_check(capi.load().eec_beam_select(n, R, V, int(k), logp.contiguous().data_ptr(), scores.contiguous().data_ptr(), float(penalty),
+                                                out_s.data_ptr(), parent.data_ptr(), tok.data_ptr(), tokens_old.data_ptr(), tokens_new.data_ptr(),
+                                                int(length), tokens_old.size(2), tokens_old.size(1), stream_ptr(dev)), "eec_beam_select")
+    return out_s, parent, tok
+
+
+class DecoderStepSession:
+    """Step-wise AED decoding state over key / value caches (include/eec.h): ``step(tokens [*lead, R], parent [*lead, R] | None)``
+    returns the log-probs of the NEXT token of every live beam, [*lead, R, V] -- what
+    ``model._decoder_(prefixes, enc, layer_n)[:, -1]`` returns (util/beam_infer.py:236-240) -- from the last token of every
+    beam and the row of the previous step it extends.  ``lead`` is the shape of the searches advanced in lockstep by the same
+    launches; a subclass owns the cache(s) and contributes the two C calls, ``_begin`` (one per tensor of ``encs`` and cache)
+    and ``_step``."""
+
+    MAX = 8  # decoders per call
+
+    def __init__(self, model, ps_list, d_ff: int, V: int, encs: List[Tensor], lead: Tuple[int, ...], max_steps: int, nbytes: int):
+        lib = capi.load()
+        cfg = model._cfg
+        self.lead, self.V, self.max_steps, self.nbytes = lead, V, max_steps, nbytes
+        self.dev, self.Tq = encs[0].device, encs[0].size(-2)
+        self.s, self.rows = 0, 0
+        self.max_beams = lib.eec_decoder_step_max_beams()
+        self._ps_keep = ps_list
+        self.ps = (C.POINTER(capi.EecDecoderParams) * len(ps_list))(*[C.pointer(p) for p in ps_list])
+        self.geo = (cfg.d_model, cfg.n_heads, d_ff, V)
+        self.pad_idx, passes = int(model.trg_pad_idx), int(model.decoder_passes)
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev)
+            self._caches = [aligned_ws(nbytes, self.dev) for _ in encs]
+            self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
+            for i, enc in enumerate(encs):
+                enc_c = enc.contiguous().float()
+                _step_check(self._begin(lib, i, enc_c.data_ptr(), passes, stream_ptr(self.dev)), self.entry + "begin")
+                enc_c.record_stream(stream)
+                self._caches[i][0].record_stream(stream)
+
+    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
+        lib = capi.load()
+        lead = self.lead
+        if last_tokens.dim() != len(lead) + 1 or last_tokens.shape[:-1] != lead:
+            raise ValueError(f"last_tokens must be [{', '.join(map(str, lead + ('live beams',)))}]")
+        R = int(last_tokens.size(-1))
+        if not 1 <= R <= self.max_beams:
+            raise ValueError(f"1 .. {self.max_beams} live beams per search and step, got {R}")
+        if self.s >= self.max_steps:
+            raise RuntimeError(f"the session was opened for {self.max_steps} steps")
+        if parent is not None and parent.shape != last_tokens.shape:
+            raise ValueError("parent: one row of the previous step per live beam of every search")
+        dev = self.dev
+        with torch.cuda.device(dev):
+            tok = last_tokens.to(device=dev, dtype=torch.int64).contiguous()
+            par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            _step_check(self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
+                                   stream_ptr(dev)), self.entry + "step")
+            tok.record_stream(stream)
+            if par is not None:
+                par.record_stream(stream)
+        self.s += 1
+        self.rows = R
+        return out
+
+
+class _ExitSessions(DecoderStepSession):
+    """n <= 8 exits of ONE utterance, a cache per exit (csrc/decoder_step.hip); ``lead`` is (n,), or () for a single exit.  A
+    single exit is a group of one, as eec_decoder_step is eec_decoder_step_multi with n = 1."""
+
+    entry = "eec_decoder_"
+
+    def _begin(self, lib, i, enc, passes, stream):
+        return lib.eec_decoder_begin(self.ps[i], *self.geo, enc, self.Tq, self.max_steps, passes, self.ptrs[i], self.nbytes, stream)
+
+    def _step(self, lib, tok, par, R, log_softmax, out, stream):
+        return lib.eec_decoder_step_multi(len(self.ps), self.ps, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps,
+                                          log_softmax, out, self.ptrs, self.nbytes, stream)
+
+
+class _BatchSession(DecoderStepSession):
+    """E exits x B utterances of a padded batch, one cache for all of them (csrc/decoder_batch.hip); ``lead`` is (E, B).  The
+    launches of a step do not depend on E or B.  Log-probs only."""
+
+    entry = "eec_decoder_batch_"
+    E = property(lambda self: self.lead[0])
+    B = property(lambda self: self.lead[1])
+
+    def _begin(self, lib, i, taps, passes, stream):
+        return lib.eec_decoder_batch_begin(self.ps, *self.lead, *self.geo, taps, self.Tq, self.max_steps, passes, self.ptrs[0], self.nbytes, stream)
+
+    def _step(self, lib, tok, par, R, log_softmax, out, stream):
+        if not log_softmax:
+            raise ValueError("the batch session returns log-probs only")
+        return lib.eec_decoder_batch_step(self.ps, *self.lead, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps, out,
+                                          self.ptrs[0], self.nbytes, stream)
+
+
+class _DecoderTrainFn(torch.autograd.Function):
+    """Exit ``idx``'s attention decoder in train mode and its backward on the HIP training kernels (eec_decoder_train_forward /
+    _backward): ``linears_2[idx](decoders[idx](positional_encoder_2(emb(trg)), enc, causal + padding masks))`` -> raw logits
+    [B, S, V], differentiable with respect to every decoder parameter, the embedding table and ``enc`` (the encoder tap)."""
+
+    @staticmethod
+    def forward(ctx, model, idx, trg, enc, seed, names, *params):
+        lib = capi.load()
+        dev = trg.device
+        cfg = model._cfg
+        Bm, S = trg.shape
+        Tq = enc.size(1)
+        if enc.size(0) != Bm or enc.size(2) != cfg.d_model:
+            raise ValueError(f"enc must be [{Bm}, T', {cfg.d_model}], got {tuple(enc.shape)}")
+        tensors = dict(zip(names, params))
+        for k, t in tensors.items():
+            capi.require_fp32(f"parameter {k}", t, dev)
+        d_ff = model.decoders[idx].layers[0].linear1.out_features
+        V = model.linears_2[idx].out_features
+        n_layers = len(model.decoders[idx].layers)
+        with torch.cuda.device(dev):
+            ps, keep = model._decoder_struct(idx, tensors, with_pe=True)
+            nbytes = lib.eec_decoder_train_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, Bm, S, Tq)
+            if nbytes == 0:
+                raise ValueError("unsupported geometry for the decoder's training step")
+            ws, ws_ptr = aligned_ws(nbytes, dev)
+            out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
+            geo = (cfg.d_model, cfg.n_heads, d_ff, V)
+            _train_check(lib.eec_decoder_train_forward(C.byref(ps), *geo, int(model.trg_pad_idx), trg.data_ptr(), enc.data_ptr(), Bm, S, Tq,
+                                                       int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out.data_ptr(), ws_ptr,
+                                                       nbytes, stream_ptr(dev)), "eec_decoder_train_forward")
+        ctx.model, ctx.idx, ctx.names, ctx.seed, ctx.geo = model, idx, names, int(seed), geo
+        ctx.ws, ctx.ws_ptr, ctx.nbytes, ctx.drop, ctx.passes = ws, ws_ptr, nbytes, float(model.dropout), int(model.decoder_passes)
+        ctx.save_for_backward(trg, enc, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.ws is None:
+            raise RuntimeError("the decoder's recorded forward was already consumed by a backward")
+        model, idx, names = ctx.model, ctx.idx, ctx.names
+        trg, enc, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
+        dev = trg.device
+        lib = capi.load()
+        Bm, S = trg.shape
+        Tq = enc.size(1)
+        g = g.contiguous().float()
+        with torch.cuda.device(dev):
+            tensors = dict(zip(names, params))
+            ps, keep = model._decoder_struct(idx, tensors, with_pe=True)
+            grads = {k: torch.empty_like(v) for k, v in tensors.items()}
+            gs, gkeep = model._decoder_struct(idx, grads, with_pe=False)
+            g_enc = torch.empty_like(enc)
+            _train_check(lib.eec_decoder_train_backward(C.byref(ps), C.byref(gs), *ctx.geo, trg.data_ptr(), enc.data_ptr(), Bm, S, Tq, ctx.passes,
+                                                        ctx.drop, ctx.seed, int(idx), g.data_ptr(), g_enc.data_ptr(), ctx.ws_ptr, ctx.nbytes,
+                                                        stream_ptr(dev)), "eec_decoder_train_backward")
+        ctx.ws = None
+        need = ctx.needs_input_grad[6:]
+        return (None, None, None, g_enc if ctx.needs_input_grad[3] else None, None, None,
+                *[grads[k] if nd else None for k, nd in zip(names, need)])

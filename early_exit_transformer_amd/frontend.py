@@ -41,8 +41,7 @@ class MelFrontend:
             h = C.c_void_p()
             with torch.cuda.device(device):
                 rc = lib.eec_frontend_create(self.sample_rate, 2 * self.n_fft, self.win_length, self.hop_length, self.n_mels, C.byref(h))
-            if rc != 0:
-                raise RuntimeError(f"eec_frontend_create failed (code {rc}): {lib.eec_frontend_last_error().decode()}")
+            capi.check(rc, "eec_frontend_create", "eec_frontend_last_error")
             self._fe, self._device = h, device
         return self._fe
 
@@ -62,11 +61,8 @@ class MelFrontend:
         len_dev = lengths.to(device=dev, dtype=torch.int64).contiguous() if lengths is not None else None
         with torch.cuda.device(dev):
             fe = self._handle(dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            lib = capi.load()
-            rc = lib.eec_frontend_forward(fe, wave.data_ptr(), len_dev.data_ptr() if len_dev is not None else None, B, L,
-                                          mel.data_ptr(), C.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_frontend_forward failed (code {rc}): {lib.eec_frontend_last_error().decode()}")
+            rc = capi.load().eec_frontend_forward(fe, wave.data_ptr(), len_dev.data_ptr() if len_dev is not None else None, B, L,
+                                                  mel.data_ptr(), capi.stream_ptr(dev))
+            capi.check(rc, "eec_frontend_forward", "eec_frontend_last_error")
             wave.record_stream(torch.cuda.current_stream(dev))
         return mel[0] if squeeze else mel

@@ -1,24 +1,29 @@
-"""Drop-in mirrors of the reference's ``Early_conformer`` / ``full_conformer``.
+"""Drop-in mirrors of the reference's model classes: ``Early_conformer`` / ``full_conformer``
+(the reference's models/model/early_exit.py:565-634, :637-811, as called from train.py:148-178,37,54 and
+inference.py:45-46,66), ``Splitformer`` (:227-364) and ``Early_zipformer`` (:117-224).
 
-Same constructor keywords, ``forward`` signatures, return shapes and state_dict keys as
-/root/reference/models/model/early_exit.py:565-634 (Early_conformer) and :637-811
-(full_conformer), as called from train.py:148-178,37,54 and inference.py:45-46,66.
-The encoder stack (subsampling, positional encoding, length mask, E x L Conformer layers,
-per-exit Linear + log_softmax) is ONE call into libeec.so on the caller's current HIP
-stream; there is no PyTorch implementation of it in this package and no CPU fallback.
+Same constructor keywords, ``forward`` signatures, return shapes and state_dict keys.  The encoder stack (subsampling,
+positional encoding, length mask, E x L Conformer layers, per-exit Linear + log_softmax) is ONE call into libeec.so on the
+caller's current HIP stream; there is no PyTorch implementation of it in this package and no CPU fallback.  The operators
+around the classes live beside this module and are re-exported here: ``ctc`` (losses and decoding on log-probs),
+``training`` (the training step behind autograd), ``decoding`` (the attention decoder's sessions and training step).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-import operator
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import capi
+from .capi import new_seed, stream_ptr
+from .capi import to_device as _to_device
 from .conformer import Conformer
+from .ctc import ctc_beam_decode, encoder_lengths, exit_ctc_losses, greedy_ctc  # noqa: F401
+from .decoding import DecoderStepSession, _BatchSession, _DecoderTrainFn, _ExitSessions, beam_select  # noqa: F401
+from .training import _ExitHeadsFn, _named_tensors, _train_group, _train_head, _TrainStemFn, forward_train  # noqa: F401
 
 
 class PositionalEncoding(nn.Module):
@@ -49,39 +54,12 @@ class Conv1dSubampling(nn.Module):
             nn.Conv1d(out_channels, out_channels, kernel_size=3, stride=2, padding=0))
 
 
-def _layer_params(ptr, prefix: str, n_groups: int, n_layers: int):
-    """HOST array of EecLayerParams for ``{prefix}.{g}.conformer_layers.{l}.*`` (group-major)."""
-    layers = (capi.EecLayerParams * (n_groups * n_layers))()
-    for g in range(n_groups):
-        for l in range(n_layers):
-            lp = layers[g * n_layers + l]
-            for field, suffix in capi.LAYER_KEYS.items():
-                setattr(lp, field, ptr(f"{prefix}.{g}.conformer_layers.{l}.{suffix}"))
-    return layers
-
-
-def _to_device(t: Tensor, dev: torch.device, dtype: torch.dtype = torch.int64) -> Tensor:
-    """``t.to(dev, dtype).contiguous()``; a small CPU int64 tensor (the collate's ``lengths`` are CPU tensors in the
-    reference, train.py:34,54) travels in a kernel's argument block instead (eec_upload_i64): a host-to-device copy in front
-    of the forward drains the host's launch queue and leaves a hole on the stream once per step."""
-    if t.is_cuda or dev.type != "cuda" or dtype != torch.int64 or t.numel() == 0:
-        return t.to(device=dev, dtype=dtype).contiguous()
-    lib = capi.load()
-    if t.numel() > lib.eec_upload_i64_max():
-        return t.to(device=dev, dtype=dtype).contiguous()
-    dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-    host = t.to(torch.int64).contiguous()
-    out = torch.empty(host.shape, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_upload_i64(host.data_ptr(), host.numel(), out.data_ptr(),
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "eec_upload_i64")
-    return out
-
-
 class _HipEncoderMixin:
-    """Owns the libeec encoder handle, the packed-weight cache and the workspace."""
+    """Holds the libeec encoder handle (``capi.EncoderHandle``: packed-weight cache and workspaces) and says, as data, where the
+    class keeps what is packed into it."""
 
-    _head_attr = "linears"
+    _stem_keys = ("conv_subsample.sequential.0", "conv_subsample.sequential.1")  # the second is None for a one-convolution stem
+    _head_key = "linears.{e}"  # exit e's Linear
     _pe_attr = "positional_encoder"
     # default operand mode: the one that keeps the north-star tolerance (|d log-prob| <= 1e-3, FLAT) on every committed fixture,
     # the peaky (trained-like) one included.  "f16f8" is the faster opt-in: 1e-3 on near-uniform outputs only (DESIGN.md section 3)
@@ -91,20 +69,10 @@ class _HipEncoderMixin:
     def _hip_init(self, d_model, n_head, d_ff, dw_kernel, n_exits, n_layers, n_mels, vocab, max_len):
         self._cfg = capi.EecConfig(d_model, n_head, d_ff, dw_kernel, n_exits, n_layers, n_mels, vocab, max_len,
                                    capi.ARCH_CONFORMER)
-        self._enc = None
-        self._enc_device = None
-        self._packed_key = None
-        self._ws: Dict[Tuple[int, int, int], Tensor] = {}
-        self._gws: Dict[Tuple[int, int, int], Tensor] = {}  # workspaces of the group-level entry points
-        self._keep: list = []
+        self._handle = capi.EncoderHandle(self._cfg)
+        self._enc = None  # the handle itself, once a forward has packed it
 
     def __del__(self):
-        enc = getattr(self, "_enc", None)
-        if enc is not None:
-            try:
-                capi.load().eec_encoder_destroy(enc)
-            except Exception:
-                pass
         tr = getattr(self, "_trainer", None)
         if tr is not None:
             try:
@@ -115,64 +83,44 @@ class _HipEncoderMixin:
     # -- packing ------------------------------------------------------------
     def _param_tensors(self) -> List[Tensor]:
         return list(self.conv_subsample.parameters()) + list(self.conformer.parameters()) + \
-            list(self.conformer.buffers()) + list(getattr(self, self._head_attr).parameters()) + \
+            list(self.conformer.buffers()) + list(getattr(self, self._head_key.split(".")[0]).parameters()) + \
             [getattr(self, self._pe_attr).pe]
 
+    def _params_struct(self, ptr):
+        """EecParams of this model over ``ptr(state_dict name)``; returns (struct, keep-alive)."""
+        return capi.params_struct(ptr, self._cfg.n_exits, self._cfg.layers_per_exit, "conformer", self._stem_keys, self._head_key,
+                                  self._pe_attr + ".pe")
+
+    def _packed(self, handle: capi.EncoderHandle, tensors: List[Tensor], device: torch.device, struct=None):
+        """``handle`` on ``device`` with ``tensors`` packed (again, if one of them changed) from ``struct(ptr)``."""
+        def repack(enc):
+            sd = self.state_dict(keep_vars=True)
+            self._pack(enc, lambda name: capi.require_fp32(f"parameter {name}", sd[name], device).data_ptr(), stream_ptr(device),
+                       struct or self._params_struct)
+        return handle.ensure(device, tensors, repack)
+
     def _ensure_packed(self, device: torch.device) -> None:
-        tensors = self._param_tensors()
-        key = (device, tuple(t._version for t in tensors), tuple(t.data_ptr() for t in tensors))
-        if self._enc is not None and key == self._packed_key:
-            return
-        lib = capi.load()
-        if self._enc is not None and self._enc_device != device:
-            # model.to(another device): the packed-weight arena lives on the old device (one handle per device, eec.h)
-            lib.eec_encoder_destroy(self._enc)
-            self._enc, self._packed_key = None, None
-            self._ws.clear()
-            self._gws.clear()
-        if self._enc is None:
-            h = C.c_void_p()
-            capi.check(lib.eec_encoder_create(C.byref(self._cfg), C.byref(h)), "eec_encoder_create")
-            self._enc, self._enc_device = h, device
-        sd = {k: v for k, v in self.state_dict(keep_vars=True).items()}
+        self._enc = self._packed(self._handle, self._param_tensors(), device)
 
-        def ptr(name: str) -> int:
-            t = sd[name]
-            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"parameter {name} must be a contiguous fp32 tensor on {device}")
-            return t.data_ptr()
+    def _pack(self, enc, ptr, stream, struct) -> None:
+        params, keep = struct(ptr)
+        capi.check(capi.load().eec_encoder_pack(enc, C.byref(params), stream), "eec_encoder_pack")
 
-        self._pack(lib, device, sd, ptr)
-        self._packed_key = key
-
-    def _pack(self, lib, device, sd, ptr) -> None:
-        E, L = self._cfg.n_exits, self._cfg.layers_per_exit
-        layers = _layer_params(ptr, "conformer", E, L)
-        hw = (C.c_void_p * E)(*[ptr(f"{self._head_attr}.{e}.weight") for e in range(E)])
-        hb = (C.c_void_p * E)(*[ptr(f"{self._head_attr}.{e}.bias") for e in range(E)])
-        params = capi.EecParams(ptr("conv_subsample.sequential.0.weight"), ptr("conv_subsample.sequential.0.bias"),
-                                ptr("conv_subsample.sequential.1.weight"), ptr("conv_subsample.sequential.1.bias"),
-                                ptr(f"{self._pe_attr}.pe"), layers, hw, hb)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        capi.check(lib.eec_encoder_pack(self._enc, C.byref(params), C.c_void_p(stream)), "eec_encoder_pack")
-
-    def _group(self, enc_handle, group: int, x: Tensor, key_len: Tensor) -> None:
-        """x [B, T', D] fp32 contiguous, in place; key_len [B] int32 on the device."""
-        lib, dev = capi.load(), x.device
+    def _group(self, handle: capi.EncoderHandle, group: int, x: Tensor, key_len: Tensor) -> Tensor:
+        """Group ``group`` of ``handle`` on x [B, T', D] fp32 contiguous, IN PLACE; key_len [B] int32 on the device."""
         B, Tq, _ = x.shape
-        k = (B, Tq, dev.index or 0)
-        ws = self._gws.get(k)
-        if ws is None:
-            if len(self._gws) > 4:
-                self._gws.clear()
-            ws = torch.empty(lib.eec_encoder_group_workspace_bytes(enc_handle, B, Tq) + 256, dtype=torch.uint8, device=dev)
-            self._gws[k] = ws
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.eec_encoder_group_forward(enc_handle, group, x.data_ptr(), key_len.data_ptr(), B, Tq,
-                                           capi.PRECISIONS[self.precision], ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()),
-                                           C.c_void_p(stream))
-        capi.check(rc, "eec_encoder_group_forward")
+        _, ws_ptr, ws_bytes = handle.workspace("group_", B, Tq, x.device)
+        capi.check(capi.load().eec_encoder_group_forward(handle.h, group, x.data_ptr(), key_len.data_ptr(), B, Tq,
+                                                         capi.PRECISIONS[self.precision], ws_ptr, ws_bytes, stream_ptr(x.device)),
+                   "eec_encoder_group_forward")
+        return x
+
+    def _head(self, index: int, rows: Tensor, out: Tensor) -> Tensor:
+        """Exit ``index``'s Linear + log_softmax of rows [..., D] into ``out`` [..., V]."""
+        capi.check(capi.load().eec_encoder_head_forward(self._enc, index, rows.data_ptr(), rows.numel() // rows.size(-1), out.data_ptr(),
+                                                        capi.PRECISIONS[self.precision], stream_ptr(rows.device)),
+                   "eec_encoder_head_forward")
+        return out
 
     # -- measurement hook -----------------------------------------------------
     def set_profiling(self, enable: bool, max_launches: int = 8192) -> None:
@@ -225,26 +173,15 @@ class _HipEncoderMixin:
         dp["reduced"] = set()
         return n
 
-    # -- forward ------------------------------------------------------------
-    def _workspace(self, B: int, T: int, device: torch.device) -> Tensor:
-        k = (B, T, device.index or 0)
-        ws = self._ws.get(k)
-        if ws is None:
-            n = capi.load().eec_encoder_workspace_bytes(self._enc, B, T)
-            if len(self._ws) > 4:
-                self._ws.clear()
-            ws = torch.empty(n + 256, dtype=torch.uint8, device=device)
-            self._ws[k] = ws
-        return ws
-
     def _run_encoder(self, src: Tensor, lengths: Tensor, want_out: bool = True, want_taps: bool = False,
-                     stop_after: int = -1, want_x: bool = False, n_groups: Optional[int] = None):
+                     stop_after: int = -1, want_x: bool = False, n_groups: Optional[int] = None, frozen: bool = False):
         """``n_groups`` (1 .. E): stop after that many exit groups (eec_encoder_forward_prefix, production launch plan);
-        ``out`` / ``taps`` then hold only the exits that were run."""
+        ``out`` / ``taps`` then hold only the exits that were run.  ``frozen``: the caller trains on top of this pass and means
+        the encoder to run without autograd, in eval semantics, although the module is in train mode."""
         if not src.is_cuda:
             raise RuntimeError("the MI355X encoder runs on a HIP device only; move the model and inputs to "
                                "'cuda' (there is no CPU fallback -- the CPU reference lives in oracle/).")
-        if self.training and torch.is_grad_enabled() and not getattr(self, "_frozen_encoder_pass", False):
+        if self.training and torch.is_grad_enabled() and not frozen:
             raise NotImplementedError("this class has no training step on the HIP path (Early_conformer and full_conformer do); "
                                       "call under model.eval() / torch.no_grad()")
         if src.dim() != 3 or src.size(1) != self._cfg.n_mels:
@@ -269,25 +206,24 @@ class _HipEncoderMixin:
             out = torch.empty((E, B, Tq, V), dtype=torch.float32, device=dev) if want_out else None
             taps = torch.empty((E, B, Tq, D), dtype=torch.float32, device=dev) if want_taps else None
             xdbg = torch.empty((B, Tq, D), dtype=torch.float32, device=dev) if want_x else None
-            ws = self._workspace(B, T, dev)
-            ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            _, ws_ptr, ws_bytes = self._handle.workspace("", B, T, dev)
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             if n_groups is not None:
                 rc = lib.eec_encoder_forward_prefix(
                     self._enc, src.data_ptr(), len_dev.data_ptr(), B, T, capi.PRECISIONS[self.precision], E,
-                    ptr(out), ptr(taps), ptr(xdbg), ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()), C.c_void_p(stream))
+                    ptr(out), ptr(taps), ptr(xdbg), ws_ptr, ws_bytes, stream_ptr(dev))
                 capi.check(rc, "eec_encoder_forward_prefix")
             else:
                 rc = lib.eec_encoder_forward(
                     self._enc, src.data_ptr(), len_dev.data_ptr(), B, T, capi.PRECISIONS[self.precision],
-                    ptr(out), ptr(taps), ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()), stop_after, ptr(xdbg),
-                    C.c_void_p(stream))
+                    ptr(out), ptr(taps), ws_ptr, ws_bytes, stop_after, ptr(xdbg), stream_ptr(dev))
                 capi.check(rc, "eec_encoder_forward")
             # src/len_dev must outlive the asynchronous launches on this stream
             src.record_stream(torch.cuda.current_stream(dev))
             len_dev.record_stream(torch.cuda.current_stream(dev))
         return out, taps, xdbg
+
+    _forward_train = forward_train  # the whole-encoder training step (Early_conformer, full_conformer)
 
 
 class Early_conformer(_HipEncoderMixin, nn.Module):
@@ -323,20 +259,6 @@ class Early_conformer(_HipEncoderMixin, nn.Module):
             return self._forward_heads_trainable(src, lengths)
         return self._run_encoder(src, lengths)[0]
 
-    def _forward_train(self, src: Tensor, lengths: Tensor, want_taps: bool = False):
-        """The training step's forward (train.py:54) on the HIP training kernels; autograd reaches every parameter of the
-        path (stem, Conformer groups, exit heads).  ``want_taps``: also return the group outputs [E, B, T', D] as a second
-        differentiable result (what full_conformer hands to its attention decoders)."""
-        if not src.is_cuda:
-            raise RuntimeError("the MI355X training step runs on a HIP device only (there is no CPU fallback)")
-        if src.dim() != 3 or src.size(1) != self._cfg.n_mels:
-            raise ValueError(f"src must be [B, {self._cfg.n_mels}, T], got {tuple(src.shape)}")
-        mine = ("conv_subsample.", "conformer.", self._head_attr + ".")
-        named = [(n, p) for n, p in _named_tensors(self)[0] if n.startswith(mine)]
-        names = tuple(n for n, _ in named)
-        len_dev = _to_device(lengths, src.device)
-        return _EncoderTrainFn.apply(self, src.contiguous().float(), len_dev, names, want_taps, *[p for _, p in named])
-
     def _forward_heads_trainable(self, src: Tensor, lengths: Tensor) -> Tensor:
         """First slice of the training path (train.py:53-70): the exit heads ``linears.*`` are trainable on a FROZEN
         encoder.  The encoder stack runs on the HIP path without autograd, in eval semantics (running BatchNorm
@@ -348,12 +270,7 @@ class Early_conformer(_HipEncoderMixin, nn.Module):
         if trainable:
             raise NotImplementedError("this class trains its exit heads (linears.*) only: freeze the encoder "
                                       f"(requires_grad_(False)); trainable now: {trainable[:3]}{' ...' if len(trainable) > 3 else ''}")
-        self._frozen_encoder_pass = True
-        try:
-            with torch.no_grad():
-                taps = self._run_encoder(src, lengths, want_out=False, want_taps=True, n_groups=self._cfg.n_exits)[1]
-        finally:
-            self._frozen_encoder_pass = False
+        taps = self._run_encoder(src, lengths, want_out=False, want_taps=True, n_groups=self._cfg.n_exits, frozen=True)[1]
         wb = [l.weight for l in self.linears] + [l.bias for l in self.linears]
         return _ExitHeadsFn.apply(self, taps, *wb)
 
@@ -368,203 +285,6 @@ class Early_conformer(_HipEncoderMixin, nn.Module):
         tokens, counts = greedy_ctc(enc_out.reshape(E * B, Tq, V), blank)
         tokens, counts = tokens.cpu(), counts.cpu()
         return [[tokens[e * B + b, : counts[e * B + b]].tolist() for b in range(B)] for e in range(E)]
-
-
-# ---- building blocks of the training step (Splitformer / Early_zipformer: train.py:180-208) ----------------------------------
-_GROUP_FIELDS = [f for f in capi._LAYER_FIELDS if f not in ("conv_bn_rm", "conv_bn_rv")]  # the 30 trainable tensors of a ConformerLayer
-
-
-def _group_layer_tensors(group: nn.Module) -> List[Tensor]:
-    """The parameters of a Conformer group, layer-major, in _GROUP_FIELDS order."""
-    out: List[Tensor] = []
-    for layer in group.conformer_layers:
-        sd = dict(layer.named_parameters())
-        out += [sd[capi.LAYER_KEYS[f]] for f in _GROUP_FIELDS]
-    return out
-
-
-def _group_struct(tensors: Sequence[Tensor], n_layers: int):
-    layers = (capi.EecLayerParams * n_layers)()
-    k = len(_GROUP_FIELDS)
-    for l in range(n_layers):
-        for i, f in enumerate(_GROUP_FIELDS):
-            setattr(layers[l], f, tensors[l * k + i].data_ptr())
-    return layers
-
-
-def _aligned_ws(nbytes: int, dev) -> Tuple[Tensor, int]:
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    return ws, (ws.data_ptr() + 255) // 256 * 256
-
-
-class _TrainGroupFn(torch.autograd.Function):
-    """One Conformer group (torchaudio ``Conformer(num_layers=L)``: early_exit.py:160-172, 266-297) in train mode on rows
-    x [B, T', D] with key lengths key_len [B] (int32, device), and its backward, on the HIP training kernels
-    (eec_train_group_forward / _backward).  BatchNorm uses the batch statistics and updates the running ones like nn.BatchNorm1d."""
-
-    @staticmethod
-    def forward(ctx, model, group, x, key_len, seed, site_base, *params):
-        lib = capi.load()
-        dev = x.device
-        cfg = model._cfg
-        B, Tq, D = x.shape
-        L = len(group.conformer_layers)
-        for t in params:
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"group parameters must be contiguous fp32 tensors on {dev}")
-        x = x.contiguous().float()
-        with torch.cuda.device(dev):
-            layers = _group_struct(params, L)
-            nbytes = lib.eec_train_group_workspace_bytes(C.byref(cfg), L, B, Tq)
-            if nbytes == 0:
-                raise ValueError("unsupported geometry for a training group")
-            ws, ws_ptr = _aligned_ws(nbytes, dev)
-            out = torch.empty_like(x)
-            bn = torch.empty((L, 2, D), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_group_forward(C.byref(cfg), layers, L, x.data_ptr(), key_len.data_ptr(), B, Tq, int(model.train_passes),
-                                                       float(model.dropout), int(seed), int(site_base), out.data_ptr(), bn.data_ptr(), ws_ptr, nbytes,
-                                                       C.c_void_p(stream)), "eec_train_group_forward")
-            n = B * Tq
-            with torch.no_grad():
-                for l, layer in enumerate(group.conformer_layers):
-                    bnm = layer.conv_module.sequential[3]
-                    if bnm.track_running_stats and bnm.running_mean is not None:
-                        m = bnm.momentum if bnm.momentum is not None else 0.1
-                        bnm.running_mean.mul_(1 - m).add_(bn[l, 0], alpha=m)
-                        bnm.running_var.mul_(1 - m).add_(bn[l, 1] * (n / max(n - 1, 1)), alpha=m)
-                        bnm.num_batches_tracked += 1
-        ctx.model, ctx.L, ctx.seed, ctx.site_base = model, L, int(seed), int(site_base)
-        ctx.ws, ctx.ws_ptr, ctx.nbytes = ws, ws_ptr, nbytes
-        ctx.passes, ctx.drop = int(model.train_passes), float(model.dropout)
-        ctx.save_for_backward(x, key_len, *params)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        if ctx.ws is None:
-            raise RuntimeError("this group's recorded forward was already consumed by a backward")
-        x, key_len, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
-        dev = x.device
-        lib = capi.load()
-        B, Tq, _ = x.shape
-        g = g.contiguous().float()
-        with torch.cuda.device(dev):
-            layers = _group_struct(params, ctx.L)
-            grads = [torch.empty_like(t) for t in params]
-            glayers = _group_struct(grads, ctx.L)
-            g_in = torch.empty_like(x)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_group_backward(C.byref(ctx.model._cfg), layers, glayers, ctx.L, x.data_ptr(), key_len.data_ptr(), B, Tq,
-                                                        ctx.passes, ctx.drop, ctx.seed, ctx.site_base, g.data_ptr(), g_in.data_ptr(), ctx.ws_ptr,
-                                                        ctx.nbytes, C.c_void_p(stream)), "eec_train_group_backward")
-        ctx.ws = None
-        need = ctx.needs_input_grad[6:]
-        return (None, None, g_in if ctx.needs_input_grad[2] else None, None, None, None, *[gr if nd else None for gr, nd in zip(grads, need)])
-
-
-class _TrainStemFn(torch.autograd.Function):
-    """Stem in train mode: Conv1d(k3, s2) [-> Conv1d(k3, s2)] -> + positional encoding -> dropout (early_exit.py:24-48 / 80-95,
-    positional_encoding.py:65-73) -> [B, To, D]; no gradient with respect to the mel input."""
-
-    @staticmethod
-    def forward(ctx, model, mel, pe, seed, site, w0, b0, w1, b1):
-        lib = capi.load()
-        dev = mel.device
-        cfg = model._cfg
-        B, _, T = mel.shape
-        two = w1 is not None
-        T1 = (T - 3) // 2 + 1
-        To = ((T1 - 3) // 2 + 1) if two else T1
-        with torch.cuda.device(dev):
-            nbytes = lib.eec_train_stem_workspace_bytes(C.byref(cfg), B, T, int(two))
-            if nbytes == 0:
-                raise ValueError("unsupported geometry for the training stem")
-            ws, ws_ptr = _aligned_ws(nbytes, dev)
-            out = torch.empty((B, To, cfg.d_model), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_stem_forward(C.byref(cfg), w0.data_ptr(), b0.data_ptr(), w1.data_ptr() if two else None,
-                                                      b1.data_ptr() if two else None, pe.data_ptr(), mel.data_ptr(), B, T, int(model.train_passes),
-                                                      float(model.dropout), int(seed), int(site), out.data_ptr(), ws_ptr, nbytes, C.c_void_p(stream)),
-                           "eec_train_stem_forward")
-        ctx.model, ctx.geo, ctx.two = model, (B, T), two
-        ctx.seed, ctx.site, ctx.passes, ctx.drop = int(seed), int(site), int(model.train_passes), float(model.dropout)
-        ctx.ws, ctx.ws_ptr, ctx.nbytes = ws, ws_ptr, nbytes
-        ctx.save_for_backward(mel, w0, b0, *((w1, b1) if two else ()))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        saved = ctx.saved_tensors
-        w0, b0 = saved[1], saved[2]
-        dev = g.device
-        lib = capi.load()
-        B, T = ctx.geo
-        g = g.contiguous().float()
-        with torch.cuda.device(dev):
-            g_w0, g_b0 = torch.empty_like(w0), torch.empty_like(b0)
-            g_w1 = torch.empty_like(saved[3]) if ctx.two else None
-            g_b1 = torch.empty_like(saved[4]) if ctx.two else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_stem_backward(C.byref(ctx.model._cfg), int(ctx.two), B, T, ctx.passes, ctx.drop, ctx.seed, ctx.site,
-                                                       g.data_ptr(), g_w0.data_ptr(), g_b0.data_ptr(), g_w1.data_ptr() if ctx.two else None,
-                                                       g_b1.data_ptr() if ctx.two else None, ctx.ws_ptr, ctx.nbytes, C.c_void_p(stream)),
-                           "eec_train_stem_backward")
-        ctx.ws = None
-        return (None, None, None, None, None, g_w0, g_b0, g_w1, g_b1)
-
-
-class _TrainHeadFn(torch.autograd.Function):
-    """Exit head ``log_softmax(x . W^T + b)`` (early_exit.py:629-631) and its backward on the training GEMM."""
-
-    @staticmethod
-    def forward(ctx, passes, x, W, b):
-        lib = capi.load()
-        dev = x.device
-        x = x.contiguous().float()
-        M, D = x.shape
-        V = W.size(0)
-        with torch.cuda.device(dev):
-            logp = torch.empty((M, V), dtype=torch.float32, device=dev)
-            scratch = torch.empty((M, V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_head_forward(x.data_ptr(), W.data_ptr(), b.data_ptr(), M, V, D, int(passes), logp.data_ptr(),
-                                                      scratch.data_ptr(), C.c_void_p(stream)), "eec_train_head_forward")
-            scratch.record_stream(torch.cuda.current_stream(dev))
-        ctx.passes = int(passes)
-        ctx.save_for_backward(x, W, logp)
-        return logp
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        x, W, logp = ctx.saved_tensors
-        lib = capi.load()
-        dev = x.device
-        M, D = x.shape
-        V = W.size(0)
-        g = g.contiguous().float()
-        with torch.cuda.device(dev):
-            dW, db = torch.empty_like(W), torch.empty((V,), dtype=torch.float32, device=dev)
-            dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-            scratch = torch.empty((lib.eec_train_head_backward_scratch_floats(M, V, D),), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_head_backward(x.data_ptr(), W.data_ptr(), logp.data_ptr(), g.data_ptr(), M, V, D, ctx.passes,
-                                                       dx.data_ptr() if dx is not None else None, dW.data_ptr(), db.data_ptr(), scratch.data_ptr(),
-                                                       C.c_void_p(stream)), "eec_train_head_backward")
-            scratch.record_stream(torch.cuda.current_stream(dev))
-        return (None, dx, dW, db)
-
-
-def _train_group(model, group: nn.Module, x: Tensor, key_len: Tensor, seed: int, site_base: int) -> Tensor:
-    return _TrainGroupFn.apply(model, group, x, key_len, seed, site_base, *_group_layer_tensors(group))
-
-
-def _train_head(model, linear: nn.Linear, x: Tensor) -> Tensor:
-    B, Tq, D = x.shape
-    return _TrainHeadFn.apply(model.train_passes, x.reshape(B * Tq, D), linear.weight, linear.bias).reshape(B, Tq, -1)
 
 
 class _TimeResample(nn.Module):
@@ -598,108 +318,61 @@ class Splitformer(Early_conformer):
             Conformer(input_dim=d_model, num_heads=n_head, ffn_dim=d_feed_forward, num_layers=1,
                       depthwise_conv_kernel_size=depthwise_kernel_size, dropout=drop_prob) for _ in range(2)])
         # second libeec handle: the two one-layer branch groups, packed without stem and heads
-        self._par_cfg = capi.EecConfig(d_model, n_head, d_feed_forward, depthwise_kernel_size, 2, 1, features_length,
-                                       dec_voc_size, max_len, capi.ARCH_CONFORMER)
-        self._par_enc = None
-        self._par_device = None
-        self._par_key = None
+        self._branch = capi.EncoderHandle(capi.EecConfig(d_model, n_head, d_feed_forward, depthwise_kernel_size, 2, 1, features_length,
+                                                         dec_voc_size, max_len, capi.ARCH_CONFORMER))
 
-    def __del__(self):
-        enc = getattr(self, "_par_enc", None)
-        if enc is not None:
-            try:
-                capi.load().eec_encoder_destroy(enc)
-            except Exception:
-                pass
-        super().__del__()
-
-    def _ensure_branch_packed(self, device: torch.device) -> None:
-        tensors = list(self.conformer_parallel.parameters()) + list(self.conformer_parallel.buffers())
-        key = (device, tuple(t._version for t in tensors), tuple(t.data_ptr() for t in tensors))
-        if self._par_enc is not None and key == self._par_key:
-            return
-        lib = capi.load()
-        if self._par_enc is not None and self._par_device != device:
-            lib.eec_encoder_destroy(self._par_enc)
-            self._par_enc, self._par_key = None, None
-        if self._par_enc is None:
-            h = C.c_void_p()
-            capi.check(lib.eec_encoder_create(C.byref(self._par_cfg), C.byref(h)), "eec_encoder_create")
-            self._par_enc, self._par_device = h, device
-        sd = dict(self.state_dict(keep_vars=True))
-
-        def ptr(name: str) -> int:
-            t = sd[name]
-            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"parameter {name} must be a contiguous fp32 tensor on {device}")
-            return t.data_ptr()
-
-        params = capi.EecParams(None, None, None, None, None, _layer_params(ptr, "conformer_parallel", 2, 1), None, None)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        capi.check(lib.eec_encoder_pack(self._par_enc, C.byref(params), C.c_void_p(stream)), "eec_encoder_pack")
-        self._par_key = key
-
-    def _forward_training(self, src: Tensor, lengths: Tensor) -> Tensor:
-        """train.py:180-208 (--model_type splitformer) in train mode: every module on the HIP training kernels behind autograd
-        functions (stem, Conformer groups -- the E main ones and the two down-sampled branches --, heads); the strided slice, the
-        repeat and the add that glue the branches in are the same torch ops as in inference, differentiated by autograd."""
-        if not src.is_cuda:
-            raise RuntimeError("the MI355X training step runs on a HIP device only (there is no CPU fallback)")
-        dev = src.device
-        E = self._cfg.n_exits
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        conv = self.conv_subsample.sequential
-        x = _TrainStemFn.apply(self, src.contiguous().float(), self.positional_encoder.pe, seed, 1, conv[0].weight, conv[0].bias,
-                               conv[1].weight, conv[1].bias)
+    def _walk(self, x: Tensor, lengths: Tensor, group, head, in_place: bool) -> list:
+        """The reference's topology (early_exit.py:299-364) from the stem's output x [B, T', D] on, over the two operations that
+        differ between the modes: ``group(which, index, x, key_len) -> x`` runs Conformer group ``index`` of ``self.<which>``,
+        ``head(index, x)`` exit ``index``'s head; returns the heads' results.  ``in_place``: ``group`` overwrites its input (the
+        inference entry does; the autograd functions return fresh tensors).  The strided slice, the repeat and the add that glue
+        a branch in are the same torch ops in both modes."""
         B, Tq, D = x.shape
-        mel_len = _to_device(lengths, dev)
+        E = self._cfg.n_exits
+        mel_len = _to_device(lengths, x.device)
         base = torch.clamp(mel_len / 4, max=Tq).to(torch.int32)
         outs = []
         for index in range(E):
             branch = index in (0, E - 1)
-            side = x
-            x = _train_group(self, self.conformer[index], x, base, seed, 16 + 128 * index)
+            side = x.clone() if branch and in_place else x  # the group's INPUT feeds the branch
+            x = group("conformer", index, x, base)
             if branch:
                 pad = (-Tq) % self.factor
                 if pad:
                     side = torch.cat((side, side.new_zeros(B, pad, D)), dim=1)
                 side = side[:, :: self.factor, :].contiguous()
                 side_len = torch.clamp((mel_len + pad) / self.factor, max=side.size(1)).to(torch.int32)
-                side = _train_group(self, self.conformer_parallel[index // (E - 1)], side, side_len, seed, 16 + 128 * index + 64)
+                side = group("conformer_parallel", index // (E - 1), side, side_len)
                 x = x + torch.repeat_interleave(side, self.factor, dim=1)[:, :Tq, :]
-            outs.append(_train_head(self, self.linears[index], x))
-        return torch.stack(outs)
+            outs.append(head(index, x))
+        return outs
 
     def forward(self, src: Tensor, lengths: Tensor) -> Tensor:
+        E = self._cfg.n_exits
         if self.training:
-            return self._forward_training(src, lengths)
+            # train.py:180-208 (--model_type splitformer) in train mode: every module on the HIP training kernels behind autograd
+            # functions (stem, Conformer groups -- the E main ones and the two down-sampled branches --, heads)
+            if not src.is_cuda:
+                raise RuntimeError("the MI355X training step runs on a HIP device only (there is no CPU fallback)")
+            seed = new_seed()
+            conv = self.conv_subsample.sequential
+            x = _TrainStemFn.apply(self, src.contiguous().float(), self.positional_encoder.pe, seed, 1, conv[0].weight, conv[0].bias,
+                                   conv[1].weight, conv[1].bias)
+
+            def group(which, i, t, key_len):  # dropout sites: 16 + 128 * exit index, + 64 for that exit's branch
+                site = 16 + 128 * i if which == "conformer" else 16 + 128 * i * (E - 1) + 64
+                return _train_group(self, getattr(self, which)[i], t, key_len, seed, site)
+            return torch.stack(self._walk(x, lengths, group, lambda i, t: _train_head(self, self.linears[i], t), in_place=False))
         # stem (+ PE) through the monolithic entry's first sub-step; also validates src and packs the main handle
         x = self._run_encoder(src, lengths, want_out=False, stop_after=0, want_x=True)[2]
         dev = x.device
         with torch.cuda.device(dev):
-            self._ensure_branch_packed(dev)
-            lib = capi.load()
-            B, Tq, D = x.shape
-            E, V = self._cfg.n_exits, self._cfg.vocab
-            mel_len = _to_device(lengths, dev)
-            base = torch.clamp(mel_len / 4, max=Tq).to(torch.int32)
-            out = torch.empty((E, B, Tq, V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for index in range(E):
-                branch = index in (0, E - 1)
-                side = x.clone() if branch else None  # the group's INPUT feeds the branch; the group runs in place
-                self._group(self._enc, index, x, base)
-                if branch:
-                    pad = (-Tq) % self.factor
-                    if pad:
-                        side = torch.cat((side, side.new_zeros(B, pad, D)), dim=1)
-                    side = side[:, :: self.factor, :].contiguous()
-                    side_len = torch.clamp((mel_len + pad) / self.factor, max=side.size(1)).to(torch.int32)
-                    self._group(self._par_enc, index // (E - 1), side, side_len)
-                    x = x + torch.repeat_interleave(side, self.factor, dim=1)[:, :Tq, :]
-                rc = lib.eec_encoder_head_forward(self._enc, index, x.data_ptr(), B * Tq, out[index].data_ptr(),
-                                                  capi.PRECISIONS[self.precision], C.c_void_p(stream))
-                capi.check(rc, "eec_encoder_head_forward")
+            handles = {"conformer": self._handle, "conformer_parallel": self._branch}
+            self._packed(self._branch, list(self.conformer_parallel.parameters()) + list(self.conformer_parallel.buffers()), dev,
+                         lambda ptr: capi.params_struct(ptr, 2, 1, "conformer_parallel"))
+            out = torch.empty((E, *x.shape[:2], self._cfg.vocab), dtype=torch.float32, device=dev)
+            self._walk(x, lengths, lambda which, i, t, key_len: self._group(handles[which], i, t, key_len),
+                       lambda i, t: self._head(i, t, out[i]), in_place=True)
         return out
 
 
@@ -720,6 +393,8 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
 
     factors = (2, 4, 8, 4, 2)
     stack = (2, 4, 5, 4, 2)
+    _stem_keys = ("conv_subsample.conv", None)
+    _head_key = "linear"  # one head, registered under every exit index
 
     def __init__(self, src_pad_idx, n_enc_exits, enc_voc_size, dec_voc_size, d_model, n_head, max_len,
                  d_feed_forward, n_enc_layers, features_length, drop_prob, depthwise_kernel_size, device=None):
@@ -741,18 +416,29 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
         self._hip_init(d_model, n_head, d_feed_forward, depthwise_kernel_size, n_enc_exits, n_enc_layers,
                        features_length, dec_voc_size, max_len)
 
-    def _param_tensors(self) -> List[Tensor]:
-        return list(self.conv_subsample.parameters()) + list(self.conformer.parameters()) + \
-            list(self.conformer.buffers()) + list(self.linear.parameters()) + [self.positional_encoder.pe]
-
-    def _pack(self, lib, device, sd, ptr) -> None:
-        E, L = self._cfg.n_exits, self._cfg.layers_per_exit
-        hw = (C.c_void_p * E)(*[ptr("linear.weight")] * E)  # one head, registered under every exit index
-        hb = (C.c_void_p * E)(*[ptr("linear.bias")] * E)
-        params = capi.EecParams(ptr("conv_subsample.conv.weight"), ptr("conv_subsample.conv.bias"), None, None,
-                                ptr("positional_encoder.pe"), _layer_params(ptr, "conformer", E, L), hw, hb)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        capi.check(lib.eec_encoder_pack(self._enc, C.byref(params), C.c_void_p(stream)), "eec_encoder_pack")
+    def _walk(self, enc: Tensor, lengths: Tensor, group, head):
+        """The reference's topology (early_exit.py:174-224) from the stem's output enc [B, T1, D] on, over the two operations that
+        differ between the modes: ``group(index, x, key_len) -> x`` (in place or not: every input that is needed again is a fresh
+        tensor here) and ``head(rows)``, whose result is returned.  pad / stride / repeat / add are the same torch ops in both."""
+        B, T1, D = enc.shape
+        mel_len = _to_device(lengths, enc.device)
+        base = torch.clamp(mel_len / 2, max=T1).to(torch.int32)
+        enc = group(0, enc, base)
+        enc = group(1, enc, base)
+        first = 2
+        for factor, count in zip(self.factors, self.stack):
+            skip = enc
+            n = enc.size(1)
+            pad = (-n) % factor
+            if pad:
+                enc = torch.cat((enc, enc.new_zeros(B, pad, D)), dim=1)
+            enc = enc[:, ::factor, :].contiguous()  # a fresh tensor: the groups below may run in place
+            key_len = torch.clamp((mel_len + pad) / factor, max=enc.size(1)).to(torch.int32)
+            for g in range(first, first + count):
+                enc = group(g, enc, key_len)
+            first += count
+            enc = torch.repeat_interleave(enc, factor, dim=1)[:, :n, :] + skip
+        return head(enc[:, ::2, :].contiguous())
 
     def forward(self, src: Tensor, lengths: Tensor) -> Tensor:
         if not src.is_cuda:
@@ -760,627 +446,27 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
                                "reference lives in oracle/).")
         if src.dim() != 3 or src.size(1) != self._cfg.n_mels or src.size(2) < 3:
             raise ValueError(f"src must be [B, {self._cfg.n_mels}, T >= 3], got {tuple(src.shape)}")
-        if self.training:
-            return self._forward_training(src, lengths)
         dev = src.device
+        src = src.contiguous().float()
+        if self.training:
+            # train.py:180-208 (--model_type zipformer) in train mode: one-convolution stem, the 19 Conformer groups at five frame
+            # rates and the head on the HIP training kernels behind autograd functions
+            seed = new_seed()
+            conv = self.conv_subsample.conv
+            enc = _TrainStemFn.apply(self, src, self.positional_encoder.pe, seed, 1, conv.weight, conv.bias, None, None)
+            return self._walk(enc, lengths, lambda g, x, key_len: _train_group(self, self.conformer[g], x, key_len, seed, 16 + 128 * g),
+                              lambda rows: _train_head(self, self.linear, rows).unsqueeze(0))
         with torch.cuda.device(dev):
             self._ensure_packed(dev)
-            lib = capi.load()
-            src = src.contiguous().float()
             B, _, T = src.shape
-            T1, D, V = (T - 3) // 2 + 1, self._cfg.d_model, self._cfg.vocab
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            enc = torch.empty((B, T1, D), dtype=torch.float32, device=dev)
-            capi.check(lib.eec_encoder_stem1_forward(self._enc, src.data_ptr(), B, T, enc.data_ptr(), C.c_void_p(stream)),
+            enc = torch.empty((B, (T - 3) // 2 + 1, self._cfg.d_model), dtype=torch.float32, device=dev)
+            capi.check(capi.load().eec_encoder_stem1_forward(self._enc, src.data_ptr(), B, T, enc.data_ptr(), stream_ptr(dev)),
                        "eec_encoder_stem1_forward")
-            mel_len = _to_device(lengths, dev)
-            base = torch.clamp(mel_len / 2, max=T1).to(torch.int32)
-            self._group(self._enc, 0, enc, base)
-            self._group(self._enc, 1, enc, base)
-            first = 2
-            for factor, count in zip(self.factors, self.stack):
-                skip = enc
-                n = enc.size(1)
-                pad = (-n) % factor
-                if pad:
-                    enc = torch.cat((enc, enc.new_zeros(B, pad, D)), dim=1)
-                enc = enc[:, ::factor, :].contiguous()  # a fresh tensor: the groups below run in place
-                key_len = torch.clamp((mel_len + pad) / factor, max=enc.size(1)).to(torch.int32)
-                for g in range(first, first + count):
-                    self._group(self._enc, g, enc, key_len)
-                first += count
-                enc = torch.repeat_interleave(enc, factor, dim=1)[:, :n, :] + skip
-            rows = enc[:, ::2, :].contiguous()
-            out = torch.empty((1, B, rows.size(1), V), dtype=torch.float32, device=dev)
-            rc = lib.eec_encoder_head_forward(self._enc, 0, rows.data_ptr(), B * rows.size(1), out.data_ptr(),
-                                              capi.PRECISIONS[self.precision], C.c_void_p(stream))
-            capi.check(rc, "eec_encoder_head_forward")
             src.record_stream(torch.cuda.current_stream(dev))
-        return out
 
-
-def _zipformer_forward_training(self, src: Tensor, lengths: Tensor) -> Tensor:
-    """train.py:180-208 (--model_type zipformer) in train mode: one-convolution stem, the 19 Conformer groups at five frame rates
-    and the head on the HIP training kernels behind autograd functions; pad / stride / repeat / add are torch ops under autograd."""
-    dev = src.device
-    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    conv = self.conv_subsample.conv
-    enc = _TrainStemFn.apply(self, src.contiguous().float(), self.positional_encoder.pe, seed, 1, conv.weight, conv.bias, None, None)
-    B, T1, D = enc.shape
-    mel_len = _to_device(lengths, dev)
-    base = torch.clamp(mel_len / 2, max=T1).to(torch.int32)
-    enc = _train_group(self, self.conformer[0], enc, base, seed, 16)
-    enc = _train_group(self, self.conformer[1], enc, base, seed, 16 + 128)
-    first = 2
-    for factor, count in zip(self.factors, self.stack):
-        skip = enc
-        n = enc.size(1)
-        pad = (-n) % factor
-        if pad:
-            enc = torch.cat((enc, enc.new_zeros(B, pad, D)), dim=1)
-        enc = enc[:, ::factor, :].contiguous()
-        key_len = torch.clamp((mel_len + pad) / factor, max=enc.size(1)).to(torch.int32)
-        for g in range(first, first + count):
-            enc = _train_group(self, self.conformer[g], enc, key_len, seed, 16 + 128 * g)
-        first += count
-        enc = torch.repeat_interleave(enc, factor, dim=1)[:, :n, :] + skip
-    rows = enc[:, ::2, :].contiguous()
-    return _train_head(self, self.linear, rows).unsqueeze(0)
-
-
-Early_zipformer._forward_training = _zipformer_forward_training
-
-
-def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
-    """``clamp(lengths / 4, max=T').to(int)`` (early_exit.py:623) on the device: int64 [B] -> int32 [B]."""
-    if not lengths.is_cuda:
-        raise RuntimeError("encoder_lengths runs on a HIP device only")
-    lengths = lengths.to(torch.int64).contiguous()
-    out = torch.empty((lengths.numel(),), dtype=torch.int32, device=lengths.device)
-    with torch.cuda.device(lengths.device):
-        stream = torch.cuda.current_stream(lengths.device).cuda_stream
-        capi.check(capi.load().eec_encoder_lengths(lengths.data_ptr(), lengths.numel(), int(t_out), out.data_ptr(),
-                                                   C.c_void_p(stream)), "eec_encoder_lengths")
-    return out
-
-
-def greedy_ctc(logp: Tensor, blank: int = 0) -> Tuple[Tensor, Tensor]:
-    """[N, T', V] fp32 log-probs on the GPU -> (tokens [N, T'] int32, counts [N] int32)."""
-    if not logp.is_cuda:
-        raise RuntimeError("greedy_ctc runs on a HIP device only")
-    logp = logp.contiguous().float()
-    N, Tq, V = logp.shape
-    tokens = torch.empty((N, Tq), dtype=torch.int32, device=logp.device)
-    counts = torch.empty((N,), dtype=torch.int32, device=logp.device)
-    with torch.cuda.device(logp.device):
-        stream = torch.cuda.current_stream(logp.device).cuda_stream
-        capi.check(capi.load().eec_greedy_ctc(logp.data_ptr(), N, Tq, V, blank, tokens.data_ptr(),
-                                              counts.data_ptr(), C.c_void_p(stream)), "eec_greedy_ctc")
-    return tokens, counts
-
-
-def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
-                    skip_drops_frame: bool = False):
-    """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
-    sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
-    ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
-    readings of the third-party decoder's skip rule, include/eec.h).  Returns (tokens [N, T'] int32, counts [N] int32,
-    scores [N] fp32)."""
-    if not logp.is_cuda:
-        raise RuntimeError("ctc_beam_decode runs on a HIP device only")
-    logp = logp.contiguous().float()
-    N, Tq, V = logp.shape
-    dev = logp.device
-    lib = capi.load()
-    tokens = torch.empty((N, Tq), dtype=torch.int32, device=dev)
-    counts = torch.empty((N,), dtype=torch.int32, device=dev)
-    scores = torch.empty((N,), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(lib.eec_ctc_beam_decode_ex(logp.data_ptr(), N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)),
-                                              ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), C.c_void_p(stream)),
-                   "eec_ctc_beam_decode")
-    return tokens, counts, scores
-
-
-def _ctc_prepare(enc_out: Tensor, targets: Tensor, target_len: Tensor):
-    if not enc_out.is_cuda:
-        raise RuntimeError("exit_ctc_losses runs on a HIP device only")
-    enc_out = enc_out.contiguous().float()
-    dev = enc_out.device
-    tg = _to_device(targets, dev)
-    tl = _to_device(target_len, dev)
-    return enc_out, tg, tl
-
-
-class _ExitCtcLossFn(torch.autograd.Function):
-    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (eec_ctc_loss_forward / _backward):
-    what autograd computes through the reference's loop of E nn.CTCLoss calls (train.py:60-68)."""
-
-    @staticmethod
-    def forward(ctx, enc_out, tg, tl, blank):
-        E, B, Tq, V = enc_out.shape
-        if V > 256 or V % 4:
-            raise ValueError(f"exit_ctc_losses with a gradient needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
-                             "the CTC gradient kernel holds a vocabulary row in one wave")
-        dev = enc_out.device
-        lib = capi.load()
-        nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
-        out = torch.empty((E,), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)) + 256,), dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(lib.eec_ctc_loss_forward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
-                                                nll.data_ptr(), out.data_ptr(), ws_ptr, C.c_void_p(stream)), "eec_ctc_loss_forward")
-        ctx.save_for_backward(enc_out, tg, tl, nll, ws)
-        ctx.blank = blank
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        enc_out, tg, tl, nll, ws = ctx.saved_tensors
-        if getattr(ctx, "used", False):
-            raise RuntimeError("exit_ctc_losses: backward through the same forward twice (its workspace is consumed)")
-        ctx.used = True
-        E, B, Tq, V = enc_out.shape
-        dev = enc_out.device
-        g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
-        dlogp = torch.empty_like(enc_out)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.load().eec_ctc_loss_backward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1),
-                                                         ctx.blank, nll.data_ptr(), ws_ptr, g.data_ptr(), dlogp.data_ptr(),
-                                                         C.c_void_p(stream)), "eec_ctc_loss_backward")
-        return dlogp, None, None, None
-
-
-def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank: int = 0) -> Tensor:
-    """Per-exit CTC losses [E] of an encoder output [E, B, T', V] in ONE launch: what train.py:53-65 computes with
-    E separate nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) calls and input length T' for every
-    utterance.  ``.sum()`` is the reference's training loss.  Differentiable with respect to ``enc_out`` (HIP backward:
-    beta recursion + dense gradient, the values torch autograd returns for the reference's loop)."""
-    enc_out, tg, tl = _ctc_prepare(enc_out, targets, target_len)
-    E, B, Tq, V = enc_out.shape
-    if torch.is_grad_enabled() and enc_out.requires_grad:
-        return _ExitCtcLossFn.apply(enc_out, tg, tl, blank)
-    dev = enc_out.device
-    nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
-    out = torch.empty((E,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(capi.load().eec_ctc_loss(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
-                                            nll.data_ptr(), out.data_ptr(), C.c_void_p(stream)), "eec_ctc_loss")
-    return out
-
-
-class _ExitHeadsFn(torch.autograd.Function):
-    """All exit heads on given encoder taps: log_softmax(taps[e] . W_e^T + b_e) (early_exit.py:629-631), forward through
-    the HIP head kernel, backward = HIP log-softmax backward + the two GEMMs of a Linear's backward on the training GEMM
-    (eec_train_head_backward)."""
-
-    @staticmethod
-    def forward(ctx, model, taps, *wb):
-        E, B, Tq, D = taps.shape
-        V = model._cfg.vocab
-        dev = taps.device
-        lib = capi.load()
-        out = torch.empty((E, B, Tq, V), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for e in range(E):
-                capi.check(lib.eec_encoder_head_forward(model._enc, e, taps[e].data_ptr(), B * Tq, out[e].data_ptr(),
-                                                        capi.PRECISIONS[model.precision], C.c_void_p(stream)), "eec_encoder_head_forward")
-        ctx.save_for_backward(taps, out, *wb[:E])
-        ctx.need_taps = taps.requires_grad
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        taps, out = ctx.saved_tensors[:2]
-        ws = ctx.saved_tensors[2:]
-        E, B, Tq, D = taps.shape
-        V = out.size(-1)
-        dev = taps.device
-        g = g.contiguous().float()
-        lib = capi.load()
-        M = B * Tq
-        dW = [torch.empty_like(w) for w in ws]
-        db = [torch.empty((V,), dtype=torch.float32, device=dev) for _ in range(E)]
-        dtaps = torch.empty_like(taps) if ctx.need_taps else None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            scratch = torch.empty((lib.eec_train_head_backward_scratch_floats(M, V, D),), dtype=torch.float32, device=dev)
-            for e in range(E):  # log-softmax backward + the two GEMMs of a Linear's backward on the training GEMM (bf16x3)
-                _trainer_check(lib.eec_train_head_backward(taps[e].data_ptr(), ws[e].data_ptr(), out[e].data_ptr(), g[e].data_ptr(), M, V, D, 3,
-                                                           dtaps[e].data_ptr() if dtaps is not None else None, dW[e].data_ptr(), db[e].data_ptr(),
-                                                           scratch.data_ptr(), C.c_void_p(stream)), "eec_train_head_backward")
-            scratch.record_stream(torch.cuda.current_stream(dev))
-        return (None, dtaps, *dW, *db)
-
-
-def _trainer_check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed (code {rc}): {capi.load().eec_trainer_last_error().decode(errors='replace')}")
-
-
-def _params_struct(model, tensors: Dict[str, Optional[Tensor]]):
-    """EecParams over ``tensors`` (state_dict names -> tensor or None); returns (struct, keep-alive list)."""
-    E, L = model._cfg.n_exits, model._cfg.layers_per_exit
-
-    def ptr(name: str):
-        t = tensors.get(name)
-        return t.data_ptr() if t is not None else None
-
-    layers = _layer_params(ptr, "conformer", E, L)
-    hw = (C.c_void_p * E)(*[ptr(f"{model._head_attr}.{e}.weight") for e in range(E)])
-    hb = (C.c_void_p * E)(*[ptr(f"{model._head_attr}.{e}.bias") for e in range(E)])
-    st = capi.EecParams(ptr("conv_subsample.sequential.0.weight"), ptr("conv_subsample.sequential.0.bias"),
-                        ptr("conv_subsample.sequential.1.weight"), ptr("conv_subsample.sequential.1.bias"),
-                        ptr(f"{model._pe_attr}.pe"), layers, hw, hb)
-    return st, (layers, hw, hb)
-
-
-def _tree_unchanged(edges, counts) -> bool:
-    """True while every (parent's module dict, child name, child) edge of the index still holds, by identity, and no module
-    gained or lost a submodule, parameter or buffer entry since the index was built (map() keeps the ~1200 checks of the default
-    model in C: tens of microseconds against the walk's 1.7 ms)."""
-    (dicts, names, children), (tables, sizes) = edges, counts
-    return all(map(operator.is_, map(dict.get, dicts, names), children)) and list(map(len, tables)) == sizes
-
-
-def _named_tensors(model):
-    """(named parameters, state_dict entries) of ``model`` as lists of (name, tensor) -- the names and order of
-    ``named_parameters()`` / ``state_dict(keep_vars=True)`` -- from an index of (name, module, key): the training step asks
-    twice per forward and the walk over ~400 modules was 1.7 ms of its host time.  The tensors are read from the modules at every
-    call (``.to()``, ``load_state_dict`` and in-place updates are seen); the index is built again whenever the module tree
-    changed (a submodule replaced, added or removed: ``model.linears[1] = nn.Linear(...)``), which a check of its edges by
-    identity finds."""
-    idx = model.__dict__.get("_tensor_index")
-    if idx is None or not _tree_unchanged(idx[2], idx[3]):
-        pidx, sidx, seen, edges, tables = [], [], set(), [], []
-        for mname, mod in model.named_modules(remove_duplicate=False):  # state_dict() lists a shared module under every path
-            pre = mname + "." if mname else ""
-            edges.extend((mod._modules, k, c) for k, c in mod._modules.items())
-            tables += [mod._modules, mod._parameters, mod._buffers]
-            for k, v in mod._parameters.items():
-                if v is not None:
-                    sidx.append((pre + k, mod, k, True))
-                    if id(v) not in seen:  # named_parameters() lists a shared parameter once
-                        seen.add(id(v))
-                        pidx.append((pre + k, mod, k))
-            for k, v in mod._buffers.items():
-                if v is not None and k not in mod._non_persistent_buffers_set:
-                    sidx.append((pre + k, mod, k, False))
-        idx = model.__dict__["_tensor_index"] = (pidx, sidx, tuple(zip(*edges)) or ((), (), ()), (tables, [len(t) for t in tables]))
-    pidx, sidx = idx[0], idx[1]
-    return ([(n, m._parameters[k]) for n, m, k in pidx],
-            [(n, (m._parameters if is_p else m._buffers)[k]) for n, m, k, is_p in sidx])
-
-
-class _EncoderTrainFn(torch.autograd.Function):
-    """``Early_conformer.forward`` in train mode and its backward on the HIP training kernels (csrc/train.hip): what
-    ``enc_out = model(batch_0, valid_lengths)`` / ``loss.backward()`` do in the reference's train.py:53-68.  BatchNorm uses
-    the batch statistics (and updates running_mean / running_var / num_batches_tracked like nn.BatchNorm1d), dropout
-    runs at the reference's sites with probability ``model.dropout``."""
-
-    @staticmethod
-    def forward(ctx, model, src, len_dev, names, want_taps, *params):
-        lib = capi.load()
-        dev = src.device
-        cfg = model._cfg
-        B, _, T = src.shape
-        Tq = lib.eec_out_frames(T)
-        E, L, D, V = cfg.n_exits, cfg.layers_per_exit, cfg.d_model, cfg.vocab
-        with torch.cuda.device(dev):
-            if getattr(model, "_trainer", None) is None or model._trainer_device != dev:
-                if getattr(model, "_trainer", None) is not None:
-                    lib.eec_trainer_destroy(model._trainer)
-                h = C.c_void_p()
-                _trainer_check(lib.eec_trainer_create(C.byref(cfg), C.byref(h)), "eec_trainer_create")
-                model._trainer, model._trainer_device = h, dev
-            tensors = dict(zip(names, params))
-            for k, v in _named_tensors(model)[1]:  # what model.state_dict(keep_vars=True) holds, without walking the module tree again
-                tensors.setdefault(k, v)
-            for k, t in tensors.items():
-                if t.is_floating_point() and (t.device != dev or t.dtype != torch.float32 or not t.is_contiguous()):
-                    raise RuntimeError(f"parameter {k} must be a contiguous fp32 tensor on {dev}")
-            pst, keep = _params_struct(model, tensors)
-            nbytes = lib.eec_trainer_workspace_bytes(model._trainer, B, T)
-            if nbytes == 0:
-                raise ValueError("unsupported geometry for the training step")
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-            ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-            out = torch.empty((E, B, Tq, V), dtype=torch.float32, device=dev)
-            taps = torch.empty((E, B, Tq, D), dtype=torch.float32, device=dev) if want_taps else None
-            bn = torch.empty((E * L, 2, D), dtype=torch.float32, device=dev)
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _trainer_check(lib.eec_train_forward(model._trainer, C.byref(pst), src.data_ptr(), len_dev.data_ptr(), B, T,
-                                                 int(model.train_passes), float(model.dropout), seed, out.data_ptr(),
-                                                 taps.data_ptr() if want_taps else None, bn.data_ptr(), ws_ptr, nbytes, C.c_void_p(stream)),
-                           "eec_train_forward")
-            model._train_generation = getattr(model, "_train_generation", 0) + 1
-            ctx.generation = model._train_generation
-            # running statistics, as nn.BatchNorm1d(momentum=0.1) in train mode
-            n = B * Tq
-            li = 0
-            with torch.no_grad():
-                # one multi-tensor update per momentum value (12 layers x 6 tiny kernels otherwise): lists of (layer index, module)
-                by_m = {}
-                for grp in model.conformer:
-                    for layer in grp.conformer_layers:
-                        bnm = layer.conv_module.sequential[3]
-                        if bnm.track_running_stats and bnm.running_mean is not None:
-                            by_m.setdefault(bnm.momentum if bnm.momentum is not None else 0.1, []).append((li, bnm))
-                        li += 1
-                if by_m:
-                    bvar = bn[:, 1] * (n / max(n - 1, 1))  # unbiased, as nn.BatchNorm1d stores it
-                    for m, mods in by_m.items():
-                        means, vars_ = [b_.running_mean for _, b_ in mods], [b_.running_var for _, b_ in mods]
-                        torch._foreach_mul_(means, 1 - m)
-                        torch._foreach_add_(means, [bn[i, 0] for i, _ in mods], alpha=m)
-                        torch._foreach_mul_(vars_, 1 - m)
-                        torch._foreach_add_(vars_, [bvar[i] for i, _ in mods], alpha=m)
-                        torch._foreach_add_([b_.num_batches_tracked for _, b_ in mods], 1)
-        ctx.model, ctx.names, ctx.ws, ctx.ws_ptr, ctx.nbytes = model, names, ws, ws_ptr, nbytes
-        ctx.keep = (src, len_dev)
-        ctx.want_taps = bool(want_taps)
-        ctx.save_for_backward(out, *params)
-        return (out, taps) if want_taps else out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g, g_taps=None):
-        model, names = ctx.model, ctx.names
-        if ctx.generation != model._train_generation:
-            raise RuntimeError("the trainer records one forward at a time: run backward before the next training forward")
-        out, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        dev = out.device
-        lib = capi.load()
-        g = torch.zeros_like(out) if g is None else g.contiguous().float()
-        g_taps = g_taps.contiguous().float() if g_taps is not None else None
-        with torch.cuda.device(dev):
-            tensors = dict(zip(names, params))
-            for k, v in model.state_dict(keep_vars=True).items():
-                tensors.setdefault(k, v)
-            pst, keep = _params_struct(model, tensors)
-            # data-parallel mode (enable_data_parallel): gradients are written straight into the flat buckets and each exit
-            # group's bucket is all-reduced as soon as the backward has passed that group.  Only while no parameter holds a
-            # gradient yet (zero_grad(set_to_none=True), the torch default): autograd then installs the views as p.grad;
-            # otherwise it would ADD the view to a p.grad that may alias it, so the step falls back to fresh tensors and
-            # sync_gradients() reduces afterwards.
-            dp = getattr(model, "_dp", None)
-            use_views = dp is not None and all(p.grad is None for p in params)
-            grads = {}
-            for k, v in zip(names, params):
-                view = dp["buckets"].view(k, v) if use_views else None
-                grads[k] = view if view is not None else torch.empty_like(v)
-            gst, gkeep = _params_struct(model, grads)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            cb, err = capi.GROUP_DONE_FN(0), []
-            if dp is not None and dp["active"]:
-                buckets, weight, group = dp["buckets"], dp["weight"], dp["group"]
-                # a bucket may also hold parameters this function does not differentiate (full_conformer's decoders: their
-                # gradients are autograd's own tensors): such buckets, and every bucket when the views are not in use, are
-                # left to sync_gradients()
-                mine = set(names)
-                early = [use_views and all(n in mine for n, _ in b["params"]) for b in buckets.buckets]
-                dp["reduced"] = set()
-
-                def on_group(e, _user):
-                    try:
-                        for i in buckets.buckets_ready_after(e):
-                            if early[i]:
-                                buckets.allreduce_bucket(i, weight, group, trusted=True)
-                                dp["reduced"].add(i)
-                    except Exception as ex:  # never unwind through the C frames
-                        err.append(ex)
-                if any(early):
-                    cb = capi.GROUP_DONE_FN(on_group)
-            _trainer_check(lib.eec_train_backward_ex(model._trainer, C.byref(pst), C.byref(gst), out.data_ptr(), g.data_ptr(),
-                                                     g_taps.data_ptr() if g_taps is not None else None, ctx.ws_ptr, ctx.nbytes,
-                                                     C.c_void_p(stream), cb, None), "eec_train_backward")
-            if err:
-                raise err[0]
-        ctx.ws = None
-        need = ctx.needs_input_grad[5:]
-        return (None, None, None, None, None, *[grads[k] if nd else None for k, nd in zip(names, need)])
-
-
-def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old: Tensor, tokens_new: Tensor, length: int):
-    """One step of beam-search bookkeeping for n searches in lockstep, in one launch (eec_beam_select): the ``k`` best of
-    ``scores[i, r] + logp[i, r, v] / penalty`` per search i, best first -> ``(scores [n, k], parent [n, k], token [n, k])``,
-    and ``tokens_new[i, b, :length + 1] = cat(tokens_old[i, parent[i, b], :length], token[i, b])``.  What
-    util/beam_infer.py:241-262 does with topk / index / cat, for every exit of an utterance at once."""
-    n, R, V = logp.shape
-    dev = logp.device
-    if tokens_old.shape != tokens_new.shape or tokens_old.dim() != 3 or tokens_old.size(0) != n:
-        raise ValueError("token buffers: two [n, rows, steps] int64 tensors")
-    if not logp.is_cuda:  # the same step as tensor ops, for sessions that live on the host (tests/test_host.py)
-        out_s, idx = torch.topk((scores.unsqueeze(2) + logp / penalty).reshape(n, -1), k, dim=1)
-        parent, tok = torch.div(idx, V, rounding_mode="floor"), torch.remainder(idx, V)
-        tokens_new[:, :k, :length] = torch.gather(tokens_old[:, :, :length], 1, parent.unsqueeze(2).expand(-1, -1, length))
-        tokens_new[:, :k, length] = tok
-        return out_s, parent, tok
-    out_s = torch.empty((n, k), dtype=torch.float32, device=dev)
-    parent = torch.empty((n, k), dtype=torch.int64, device=dev)
-    tok = torch.empty((n, k), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        lib = capi.load()
-        rc = lib.eec_beam_select(n, R, V, int(k), logp.contiguous().data_ptr(), scores.contiguous().data_ptr(), float(penalty), out_s.data_ptr(),
-                                 parent.data_ptr(), tok.data_ptr(), tokens_old.data_ptr(), tokens_new.data_ptr(), int(length),
-                                 tokens_old.size(2), tokens_old.size(1), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"eec_beam_select failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-    return out_s, parent, tok
-
-
-class DecoderStepSession:
-    """Step-wise AED decoding state over key / value caches (include/eec.h): ``step(tokens [*lead, R], parent [*lead, R] | None)``
-    returns the log-probs of the NEXT token of every live beam, [*lead, R, V] -- what
-    ``model._decoder_(prefixes, enc, layer_n)[:, -1]`` returns (util/beam_infer.py:236-240) -- from the last token of every
-    beam and the row of the previous step it extends.  ``lead`` is the shape of the searches advanced in lockstep by the same
-    launches; a subclass owns the cache(s) and contributes the two C calls, ``_begin`` (one per tensor of ``encs`` and cache)
-    and ``_step``."""
-
-    MAX = 8  # decoders per call
-
-    def __init__(self, model, ps_list, d_ff: int, V: int, encs: List[Tensor], lead: Tuple[int, ...], max_steps: int, nbytes: int):
-        lib = capi.load()
-        cfg = model._cfg
-        self.lead, self.V, self.max_steps, self.nbytes = lead, V, max_steps, nbytes
-        self.dev, self.Tq = encs[0].device, encs[0].size(-2)
-        self.s, self.rows = 0, 0
-        self.max_beams = lib.eec_decoder_step_max_beams()
-        self._ps_keep = ps_list
-        self.ps = (C.POINTER(capi.EecDecoderParams) * len(ps_list))(*[C.pointer(p) for p in ps_list])
-        self.geo = (cfg.d_model, cfg.n_heads, d_ff, V)
-        self.pad_idx, passes = int(model.trg_pad_idx), int(model.decoder_passes)
-        with torch.cuda.device(self.dev):
-            stream = torch.cuda.current_stream(self.dev)
-            self._caches = [_aligned_ws(nbytes, self.dev) for _ in encs]
-            self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
-            for i, enc in enumerate(encs):
-                enc_c = enc.contiguous().float()
-                self._check(lib, self._begin(lib, i, enc_c.data_ptr(), passes, C.c_void_p(stream.cuda_stream)), "begin")
-                enc_c.record_stream(stream)
-                self._caches[i][0].record_stream(stream)
-
-    def _check(self, lib, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"{self.entry}{what} failed (code {rc}): {lib.eec_decoder_step_last_error().decode(errors='replace')}")
-
-    def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
-        lib = capi.load()
-        lead = self.lead
-        if last_tokens.dim() != len(lead) + 1 or last_tokens.shape[:-1] != lead:
-            raise ValueError(f"last_tokens must be [{', '.join(map(str, lead + ('live beams',)))}]")
-        R = int(last_tokens.size(-1))
-        if not 1 <= R <= self.max_beams:
-            raise ValueError(f"1 .. {self.max_beams} live beams per search and step, got {R}")
-        if self.s >= self.max_steps:
-            raise RuntimeError(f"the session was opened for {self.max_steps} steps")
-        if parent is not None and parent.shape != last_tokens.shape:
-            raise ValueError("parent: one row of the previous step per live beam of every search")
-        dev = self.dev
-        with torch.cuda.device(dev):
-            tok = last_tokens.to(device=dev, dtype=torch.int64).contiguous()
-            par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            self._check(lib, self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
-                                        C.c_void_p(stream.cuda_stream)), "step")
-            tok.record_stream(stream)
-            if par is not None:
-                par.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        return out
-
-
-class _ExitSessions(DecoderStepSession):
-    """n <= 8 exits of ONE utterance, a cache per exit (csrc/decoder_step.hip); ``lead`` is (n,), or () for a single exit.  A
-    single exit is a group of one, as eec_decoder_step is eec_decoder_step_multi with n = 1."""
-
-    entry = "eec_decoder_"
-
-    def _begin(self, lib, i, enc, passes, stream):
-        return lib.eec_decoder_begin(self.ps[i], *self.geo, enc, self.Tq, self.max_steps, passes, self.ptrs[i], self.nbytes, stream)
-
-    def _step(self, lib, tok, par, R, log_softmax, out, stream):
-        return lib.eec_decoder_step_multi(len(self.ps), self.ps, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps,
-                                          log_softmax, out, self.ptrs, self.nbytes, stream)
-
-
-class _BatchSession(DecoderStepSession):
-    """E exits x B utterances of a padded batch, one cache for all of them (csrc/decoder_batch.hip); ``lead`` is (E, B).  The
-    launches of a step do not depend on E or B.  Log-probs only."""
-
-    entry = "eec_decoder_batch_"
-    E = property(lambda self: self.lead[0])
-    B = property(lambda self: self.lead[1])
-
-    def _begin(self, lib, i, taps, passes, stream):
-        return lib.eec_decoder_batch_begin(self.ps, *self.lead, *self.geo, taps, self.Tq, self.max_steps, passes, self.ptrs[0], self.nbytes, stream)
-
-    def _step(self, lib, tok, par, R, log_softmax, out, stream):
-        if not log_softmax:
-            raise ValueError("the batch session returns log-probs only")
-        return lib.eec_decoder_batch_step(self.ps, *self.lead, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps, out,
-                                          self.ptrs[0], self.nbytes, stream)
-
-
-class _DecoderTrainFn(torch.autograd.Function):
-    """Exit ``idx``'s attention decoder in train mode and its backward on the HIP training kernels (eec_decoder_train_forward /
-    _backward): ``linears_2[idx](decoders[idx](positional_encoder_2(emb(trg)), enc, causal + padding masks))`` -> raw logits
-    [B, S, V], differentiable with respect to every decoder parameter, the embedding table and ``enc`` (the encoder tap)."""
-
-    @staticmethod
-    def forward(ctx, model, idx, trg, enc, seed, names, *params):
-        lib = capi.load()
-        dev = trg.device
-        cfg = model._cfg
-        Bm, S = trg.shape
-        Tq = enc.size(1)
-        if enc.size(0) != Bm or enc.size(2) != cfg.d_model:
-            raise ValueError(f"enc must be [{Bm}, T', {cfg.d_model}], got {tuple(enc.shape)}")
-        tensors = dict(zip(names, params))
-        for k, t in tensors.items():
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"parameter {k} must be a contiguous fp32 tensor on {dev}")
-        d_ff = model.decoders[idx].layers[0].linear1.out_features
-        V = model.linears_2[idx].out_features
-        n_layers = len(model.decoders[idx].layers)
-        with torch.cuda.device(dev):
-            ps, keep = model._decoder_struct(idx, tensors, with_pe=True)
-            nbytes = lib.eec_decoder_train_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, n_layers, Bm, S, Tq)
-            if nbytes == 0:
-                raise ValueError("unsupported geometry for the decoder's training step")
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-            ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-            out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            geo = (cfg.d_model, cfg.n_heads, d_ff, V)
-            rc = lib.eec_decoder_train_forward(C.byref(ps), *geo, int(model.trg_pad_idx), trg.data_ptr(), enc.data_ptr(), Bm, S, Tq,
-                                               int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out.data_ptr(), ws_ptr, nbytes,
-                                               C.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_train_forward failed (code {rc}): {lib.eec_decoder_train_last_error().decode(errors='replace')}")
-        ctx.model, ctx.idx, ctx.names, ctx.seed, ctx.geo = model, idx, names, int(seed), geo
-        ctx.ws, ctx.ws_ptr, ctx.nbytes, ctx.drop, ctx.passes = ws, ws_ptr, nbytes, float(model.dropout), int(model.decoder_passes)
-        ctx.save_for_backward(trg, enc, *params)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        if ctx.ws is None:
-            raise RuntimeError("the decoder's recorded forward was already consumed by a backward")
-        model, idx, names = ctx.model, ctx.idx, ctx.names
-        trg, enc, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
-        dev = trg.device
-        lib = capi.load()
-        Bm, S = trg.shape
-        Tq = enc.size(1)
-        g = g.contiguous().float()
-        with torch.cuda.device(dev):
-            tensors = dict(zip(names, params))
-            ps, keep = model._decoder_struct(idx, tensors, with_pe=True)
-            grads = {k: torch.empty_like(v) for k, v in tensors.items()}
-            gs, gkeep = model._decoder_struct(idx, grads, with_pe=False)
-            g_enc = torch.empty_like(enc)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = lib.eec_decoder_train_backward(C.byref(ps), C.byref(gs), *ctx.geo, trg.data_ptr(), enc.data_ptr(), Bm, S, Tq, ctx.passes, ctx.drop,
-                                                ctx.seed, int(idx), g.data_ptr(), g_enc.data_ptr(), ctx.ws_ptr, ctx.nbytes, C.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_train_backward failed (code {rc}): {lib.eec_decoder_train_last_error().decode(errors='replace')}")
-        ctx.ws = None
-        need = ctx.needs_input_grad[6:]
-        return (None, None, None, g_enc if ctx.needs_input_grad[3] else None, None, None,
-                *[grads[k] if nd else None for k, nd in zip(names, need)])
+            def head(rows):
+                return self._head(0, rows, torch.empty((1, B, rows.size(1), self._cfg.vocab), dtype=torch.float32, device=dev))
+            return self._walk(enc, lengths, lambda g, x, key_len: self._group(self._handle, g, x, key_len), head)
 
 
 class full_conformer(_HipEncoderMixin, nn.Module):
@@ -1388,7 +474,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
     decoder_step.hip, training (forward in train mode + backward, train.py:36-52) through csrc/decoder_train.hip
     behind an autograd function.  The ``nn.TransformerDecoder`` modules only hold the parameters (state_dict contract)."""
 
-    _head_attr = "linears_1"
+    _head_key = "linears_1.{e}"
     _pe_attr = "positional_encoder_1"
 
     def __init__(self, trg_pad_idx, n_enc_exits, enc_voc_size, dec_voc_size, d_model, n_head, max_len,
@@ -1438,7 +524,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
         # train mode (train.py:36-52), with or without autograd -- the reference's modules apply their dropout in train mode
         # whatever the grad mode: forward (and backward) on the HIP training kernels (csrc/decoder_train.hip)
         if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = new_seed()
         named = self._decoder_named_params(idx)
         out = _DecoderTrainFn.apply(self, idx, trg.to(torch.int64).contiguous(), enc.contiguous().float(), seed,
                                     tuple(n for n, _ in named), *[p for _, p in named])
@@ -1478,8 +564,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
         ent = cache.get(idx)
         if ent is None or ent[0] != key:
             for t in tensors:
-                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise RuntimeError(f"decoder parameters must be contiguous fp32 tensors on {dev}")
+                capi.require_fp32("a decoder parameter", t, dev)
             ent = (key, *self._decoder_struct(idx, dict(self._decoder_named_params(idx)), with_pe=True))
             cache[idx] = ent
         return ent[1], dec.layers[0].linear1.out_features, self.linears_2[idx].out_features
@@ -1500,14 +585,12 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             shared = Bm > 1 and enc.stride(0) == 0  # beam search: one utterance expanded over the beams (util/beam_infer.py:233)
             enc_c = (enc[:1] if shared else enc).contiguous().float()
             nbytes = lib.eec_decoder_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, Bm, S, Tq)
-            ws, ws_ptr = _aligned_ws(nbytes, dev)
+            ws, ws_ptr = capi.aligned_ws(nbytes, dev)
             out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
             rc = lib.eec_decoder_forward(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), trg_c.data_ptr(),
                                          enc_c.data_ptr(), Bm, S, Tq, int(shared), int(self.decoder_passes), int(log_softmax), out.data_ptr(),
-                                         ws_ptr, nbytes, C.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError(f"eec_decoder_forward failed (code {rc}): {lib.eec_decoder_last_error().decode(errors='replace')}")
+                                         ws_ptr, nbytes, stream_ptr(dev))
+            capi.check(rc, "eec_decoder_forward", "eec_decoder_last_error")
             for t in (ws, trg_c, enc_c):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out
@@ -1582,8 +665,8 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             # train.py:36-52 (aed): encoder AND decoders forward / backward on the HIP training kernels (eec_train_*,
             # eec_decoder_train_*: _EncoderTrainFn, _DecoderTrainFn); the decoders consume the differentiable taps.  nn.TransformerDecoder
             # only holds the parameters.  Without autograd the same train-mode forward runs (dropout in both halves) and the tape is dropped
-            enc_out, taps = Early_conformer._forward_train(self, src, lengths, want_taps=True)
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # one seed per forward: the exits share the embedding's dropout mask
+            enc_out, taps = self._forward_train(src, lengths, want_taps=True)
+            seed = new_seed()  # one seed per forward: the exits share the embedding's dropout mask
             dec_out = torch.stack([self._decode_one(trg, taps[e], e, seed=seed) for e in range(self._cfg.n_exits)])
             return dec_out, enc_out
         enc_out, taps, _ = self._run_encoder(src, lengths, want_taps=True)
