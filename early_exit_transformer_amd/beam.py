@@ -10,17 +10,22 @@ serve without torchaudio.
   ``eec_encoder_forward`` with taps) where the reference re-runs the first n exit groups for every n
   (inference.py:44-46: O(E^2) groups per utterance), and the decoder advances step-wise over a key / value cache
   (``model.decoder_session``, csrc/decoder_step.hip) where the reference re-runs it on the whole prefix per step.
+* ``BeamInference.get_trellis`` / ``backtrack``  util/beam_infer.py:129-191: the Viterbi forced alignment of a token
+  sequence against one exit's CTC log-probs, on the device (``ctc_align``, csrc/ctc_align.hip); ``ctc_rescore`` and the
+  ``ctc_weight`` keyword of the batched searches are the reference's dormant joint choice (util/beam_infer.py:309-383): the
+  best beam by ``weight_ctc * s_ctc + (1 - weight_ctc) * s_pred``.
 * ``BeamInference.decode_batch``  inference.py:18-62 (evaluate_batch_ae) for a whole padded batch: the encoder once per
   batch, then the searches of every exit and utterance in lockstep (``beam_search_batch``, csrc/decoder_batch.hip).
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from .model import beam_select, ctc_beam_decode, greedy_ctc
+from .model import beam_select, ctc_align, ctc_beam_decode, encoder_lengths, greedy_ctc
 
 
 class GreedyCTCDecoder(torch.nn.Module):
@@ -33,6 +38,14 @@ class GreedyCTCDecoder(torch.nn.Module):
     def forward(self, emission: Tensor) -> List[int]:
         tokens, counts = greedy_ctc(emission.unsqueeze(0), self.blank)
         return tokens[0, : int(counts[0])].tolist()
+
+
+@dataclass
+class Point:
+    """util/beam_infer.py:27-31: one frame of an alignment path (score: cumulative, summed from the last frame)."""
+    token_index: int
+    time_index: int
+    score: float
 
 
 def sequence_length_penalty(length: int, alpha: float = 0.6) -> float:
@@ -62,11 +75,43 @@ def _lockstep_kw(kw: dict) -> Optional[dict]:
     return {k: v for k, v in kw.items() if k != "kv_cache"} if kw.get("kv_cache", True) else None
 
 
-def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float):
+def _joint_scores(path_score: Tensor, status: Tensor, n_tokens, pred: Tensor, weight_ctc: float) -> Tensor:
+    """util/beam_infer.py:350-378 over the last dimension (the beams of one search): ``s_ctc = exp(path[0].score / len(f_t))``
+    (0 for a beam that could not be aligned), ``s_pred = exp(final_scores)``, each divided by its own maximum, mixed by
+    ``weight_ctc``.  A vector whose maximum is 0 (every beam underflowed or failed) is left as it is instead of becoming 0 / 0."""
+    s_ctc = torch.where(status == 0, torch.exp(path_score / n_tokens), torch.zeros_like(path_score))
+    s_pred = torch.exp(pred.to(torch.float32))
+
+    def by_max(v):
+        m = v.max(dim=-1, keepdim=True).values
+        return torch.where(m > 0, v / m, v)
+    return by_max(s_ctc) * weight_ctc + by_max(s_pred) * (1 - weight_ctc)
+
+
+def _first_argmax(v: Tensor) -> Tensor:
+    """argmax over the last dimension, ties to the lower index."""
+    K = v.size(-1)
+    at = torch.where(v == v.max(dim=-1, keepdim=True).values, torch.arange(K, device=v.device), K)
+    return at.min(dim=-1).values.clamp(max=K - 1)
+
+
+def _ctc_pick(emission: Tensor, em_len: Optional[Tensor], weight_ctc: float, blank: int = 0):
+    """The best-beam rule of n lockstep searches under a CTC weight: ``pick(tokens [n, R, L], scores [n, R]) -> best [n]``.
+    Search i's beams are aligned against ``emission[i]`` ([n, T', V], ``em_len`` [n] frames or None) in ONE ``ctc_align``
+    call, as given (SOS included, as in the reference); the joint score is tensor ops on the device."""
+    def pick(tokens: Tensor, scores: Tensor) -> Tensor:
+        n, R, L = tokens.shape
+        em_index = torch.arange(n, device=tokens.device, dtype=torch.int32).repeat_interleave(R)
+        _, _, path_score, _, status, _ = ctc_align(emission, tokens.reshape(n * R, L), em_index=em_index, em_len=em_len, blank=blank)
+        return _first_argmax(_joint_scores(path_score.view(n, R), status.view(n, R), L, scores, weight_ctc))
+    return pick
+
+
+def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None):
     """``max_length`` steps of n independent beam searches in lockstep, none of which finalises a beam on the way:
     ``step(last [n, R], parent [n, R] | None)`` returns the next token's log-probs [n, R, V] of every live beam.  The
     bookkeeping of a step is ``beam_select`` over two token buffers.  Returns ``(final_tokens, final_scores, best_tokens)``
-    per search."""
+    per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
@@ -76,7 +121,7 @@ def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, al
         scores, parent, last = beam_select(step(last, parent), scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1],
                                            i + 1)
     tokens = bufs[max_length & 1][:, :beam]
-    best = scores.argmax(dim=1).tolist()
+    best = (scores.argmax(dim=1) if pick is None else pick(tokens, scores)).tolist()
     tokens_h = tokens.cpu()
     return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
 
@@ -100,6 +145,56 @@ class BeamInference:
         tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95)
         tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
         return [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
+
+    @staticmethod
+    def _align_one(emission: Tensor, tokens, blank_id: int, want_trellis: bool):
+        """One hypothesis through ``ctc_align``; ValueError where the reference prints "Failed to align" (a stated
+        divergence: no tokens, or more tokens than frames) and for ids outside the vocabulary."""
+        if emission.dim() != 2:
+            raise ValueError(f"emission must be [T', V], got {tuple(emission.shape)}")
+        tok = torch.as_tensor(tokens, dtype=torch.long).reshape(1, -1)
+        T, N = emission.size(0), tok.size(1)
+        if N < 1 or N > T:
+            raise ValueError(f"Failed to align: {N} tokens against {T} frames")
+        out = ctc_align(emission.unsqueeze(0), tok, blank=blank_id, want_trellis=want_trellis)
+        if int(out[4][0]) != 0:
+            raise ValueError("Failed to align: a token id outside the vocabulary, or non-finite emissions")
+        return out
+
+    @torch.no_grad()
+    def get_trellis(self, emission: Tensor, tokens, blank_id: int = 0) -> Tensor:
+        """util/beam_infer.py:129-150: the Viterbi trellis [T' + 1, N + 1] of ``tokens`` against ``emission`` [T', V], with
+        the reference's quirks (column 0 accumulates ``emission[:, 0]`` whatever ``blank_id`` is; +inf below ``T' + 1 - N``
+        in column 0 and what it feeds).  One kernel call."""
+        return self._align_one(emission, tokens, blank_id, True)[5][0]
+
+    @torch.no_grad()
+    def backtrack(self, trellis: Tensor, emission: Tensor, tokens, blank_id: int = 0) -> List[Point]:
+        """util/beam_infer.py:153-191: the best path from the last frame back to the first token's frame, returned in time
+        order.  The kernel aligns ``(emission, tokens)`` itself; ``trellis`` is accepted for the signature and only its shape
+        is checked."""
+        N = torch.as_tensor(tokens).numel()
+        if tuple(trellis.shape) != (emission.size(0) + 1, N + 1):
+            raise ValueError(f"trellis must be [{emission.size(0) + 1}, {N + 1}], got {tuple(trellis.shape)}")
+        point_token, point_score = (t[0].cpu() for t in self._align_one(emission, tokens, blank_id, False)[:2])
+        return [Point(int(j), t, float(point_score[t])) for t, j in enumerate(point_token.tolist()) if j >= 0]
+
+    @torch.no_grad()
+    def ctc_rescore(self, final_tokens, final_scores, emission: Tensor, weight_ctc: float, blank_id: int = 0) -> Tuple[Tensor, int]:
+        """The dormant second half of the reference's ``beam_search`` (util/beam_infer.py:350-378) for the K final beams of ONE
+        search: every beam is aligned, as given (SOS included), against ``emission`` [T', V] in one kernel call;
+        ``s_ctc_i = exp(path[0].score_i / len(f_t_i))`` (0 for a beam that cannot be aligned), ``s_pred_i = exp(final_scores_i)``,
+        each vector divided by its own maximum, ``joint = weight_ctc * s_ctc + (1 - weight_ctc) * s_pred``.  Returns
+        ``(joint [K], best_index)``, ties to the lower index."""
+        dev = emission.device
+        toks = [torch.as_tensor(t, dtype=torch.long).reshape(-1) for t in final_tokens]
+        lens = torch.tensor([t.numel() for t in toks], dtype=torch.int32)
+        tokens = torch.nn.utils.rnn.pad_sequence(toks, batch_first=True).to(dev)
+        pred = torch.stack([torch.as_tensor(s, dtype=torch.float32, device=dev).reshape(()) for s in final_scores])
+        em_index = torch.zeros(len(toks), dtype=torch.int32, device=dev)
+        _, _, path_score, _, status, _ = ctc_align(emission.unsqueeze(0), tokens, tok_len=lens, em_index=em_index, blank=blank_id)
+        joint = _joint_scores(path_score, status, lens.to(dev), pred, weight_ctc)
+        return joint, int(_first_argmax(joint))
 
     def _arg(self, value, name):
         if value is not None:
@@ -180,30 +275,41 @@ class BeamInference:
 
     @torch.no_grad()
     def decode_all_exits(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
-                         **kw) -> List[List[int]]:
+                         ctc_weight: Optional[float] = None, **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
-        ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits)."""
+        ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits).  ``ctc_weight``: the best beam of every exit is
+        chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass)."""
         if max_length is None:
             max_length = default_max_length(spec.size(1))
-        taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=False, want_taps=True,
-                                  n_groups=model._cfg.n_exits)[1]
+        logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=ctc_weight is not None, want_taps=True,
+                                        n_groups=model._cfg.n_exits)[:2]
         exits = list(range(1, model._cfg.n_exits + 1))
+        ctc = {}
+        if ctc_weight is not None:
+            ctc = dict(ctc_weight=ctc_weight, emission=logp, emission_len=encoder_lengths(valid_len.reshape(1).to(logp.device), logp.size(2)))
         lockstep = _lockstep_kw(kw)
         if lockstep is not None:
-            together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size, **lockstep)
+            together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size,
+                                              **lockstep, **ctc)
             if together is not None:
                 return [best for _, _, best in together]
-        return [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw)[2] for n in exits]
+        found = [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw) for n in exits]
+        if ctc_weight is None:
+            return [best for _, _, best in found]
+        frames = int(ctc["emission_len"][0])
+        return [ft[self.ctc_rescore(ft, fs, logp[n - 1, 0, :frames], ctc_weight)[1]].tolist() for n, (ft, fs, _) in zip(exits, found)]
 
     @torch.no_grad()
     def beam_search_exits(self, model, encoder_outputs: Sequence[Tensor], layer_ns: Sequence[int], vocab_size: Optional[int] = None,
                           max_length: int = 500, min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
-                          PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None):
+                          PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
+                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None):
         """``beam_search`` for several exits of one utterance in lockstep: the searches are independent, so every decoder
         launch and every bookkeeping op covers all of them (``model.decoder_session_group``).  Returns the list of
         ``(final_tokens, final_scores, best_tokens)`` per exit, the same values as ``beam_search`` exit by exit -- or None
         when the lockstep does not apply: no session group for this model / geometry, or EOS could finalise beams
-        (``max_length - 1 > min_length``), which would let the exits' beam counts diverge."""
+        (``max_length - 1 > min_length``), which would let the exits' beam counts diverge.  ``ctc_weight`` with ``emission``
+        [len(layer_ns), 1, T', V] (and ``emission_len`` [1]): as in ``beam_search_batch``."""
         _, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_session_group"):
             return None
@@ -212,7 +318,18 @@ class BeamInference:
         group = model.decoder_session_group(encoder_outputs, layer_ns, max_length)
         if group is None or beam > group.max_beams:
             return None
-        return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha)
+        return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha,
+                                self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1))
+
+    @staticmethod
+    def _pick(ctc_weight, emission, emission_len, E: int, B: int):
+        """The best-beam rule of E * B lockstep searches (search e * B + b): None without a CTC weight."""
+        if ctc_weight is None:
+            return None
+        if emission is None or emission.dim() != 4 or emission.size(0) != E or emission.size(1) != B:
+            raise ValueError(f"ctc_weight needs emission [{E}, {B}, T', V]: the CTC log-probs of every exit and utterance")
+        em_len = None if emission_len is None else emission_len.to(emission.device, torch.int32).reshape(B).repeat(E)
+        return _ctc_pick(emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, float(ctc_weight))
 
     def _lockstep_args(self, vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha):
         self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")  # accepted and unused: no beam finalises
@@ -221,13 +338,17 @@ class BeamInference:
     @torch.no_grad()
     def beam_search_batch(self, model, taps, layer_ns: Sequence[int], vocab_size: Optional[int] = None, max_length: int = 500,
                           min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
-                          PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None):
+                          PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
+                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None):
         """``beam_search_exits`` for every utterance of a padded batch at once: ``taps`` [E, B, T', D] (or E tensors [B, T', D]),
         exit ``layer_ns[e]``'s encoder output of every utterance.  The E * B searches are independent and run in lockstep through
         one ``model.decoder_batch_session`` (every decoder launch covers all of them) and one ``eec_beam_select`` per step.
         Returns ``out[b][e] = (final_tokens, final_scores, best_tokens)``, what ``beam_search`` returns for utterance b and exit
         ``layer_ns[e]`` -- or None where ``beam_search_exits`` declines: EOS could finalise beams (``max_length - 1 >
-        min_length``), or no batch session for this model / geometry / device."""
+        min_length``), or no batch session for this model / geometry / device.  ``ctc_weight`` (None: the highest score, no
+        extra launch): ``best_tokens`` is chosen by ``ctc_rescore``'s joint score instead -- the E * B * beam final beams are
+        aligned in one ``ctc_align`` call against ``emission`` [E, B, T', V], the exits' CTC log-probs of the same encoder pass
+        (``emission_len`` [B]: their frames, None = T'); ``final_tokens`` / ``final_scores`` are untouched."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
             return None
@@ -239,17 +360,18 @@ class BeamInference:
 
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
-        found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha)
+        found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
-                     max_batch: Optional[int] = None, **kw) -> List[List[List[int]]]:
+                     max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, **kw) -> List[List[List[int]]]:
         """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
         utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
         lockstep.  Where the batched search declines, every utterance goes through ``decode_all_exits``, so the result is
-        always the reference's."""
+        always the reference's.  ``ctc_weight`` (None: unchanged, the encoder computes no log-probs): the two heads vote --
+        the encoder pass also returns the exits' CTC log-probs and every search's best beam is ``ctc_rescore``'s."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
         E = model._cfg.n_exits
@@ -261,11 +383,15 @@ class BeamInference:
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             together, lockstep = None, _lockstep_kw(kw)
             if lockstep is not None:
-                taps = model._run_encoder(sp, vl, want_out=False, want_taps=True, n_groups=E)[1]
-                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep)
-                del taps
+                logp, taps = model._run_encoder(sp, vl, want_out=ctc_weight is not None, want_taps=True, n_groups=E)[:2]
+                ctc = {}
+                if ctc_weight is not None:
+                    ctc = dict(ctc_weight=ctc_weight, emission=logp, emission_len=encoder_lengths(vl.to(logp.device), logp.size(2)))
+                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc)
+                del taps, logp, ctc
             if together is None:
-                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, **kw) for b in range(sp.size(0))]
+                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight, **kw)
+                        for b in range(sp.size(0))]
             else:
                 out += [[best for _, _, best in row] for row in together]
         return out

@@ -1,9 +1,9 @@
 """The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), greedy and prefix-beam
-decoding (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
+decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
 stream; there is no CPU path."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -60,6 +60,52 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
                                               ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), stream_ptr(dev)),
                    "eec_ctc_beam_decode")
     return tokens, counts, scores
+
+
+def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em_index: Optional[Tensor] = None,
+              em_len: Optional[Tensor] = None, blank: int = 0, want_trellis: bool = False):
+    """Viterbi forced alignment of H token sequences against CTC log-probs on the device (eec_ctc_align): what
+    ``BeamInference.get_trellis`` + ``backtrack`` compute per hypothesis (util/beam_infer.py:129-191; semantics and quirks in
+    include/eec.h).  ``logp`` [n_em, T', V]; ``tokens`` [H, S] int64 with ``tok_len`` [H] valid ids each (None: S);
+    ``em_index`` [H] the emission of every hypothesis (None: its own index); ``em_len`` [n_em] frames per emission (None: T').
+    Returns ``(point_token [H, T'] int32, point_score [H, T'], path_score [H], final_score [H], status [H] int32, trellis)``:
+    the Point of every frame (token index -1 / score -inf before the first token's frame and past the emission's length),
+    ``path[0].score``, ``trellis[T, N]``, 0 / 1 = aligned / not alignable (its row holds the fill values), and the trellis
+    [H, T' + 1, S + 1] when ``want_trellis`` (else None)."""
+    if not logp.is_cuda:
+        raise RuntimeError("ctc_align runs on a HIP device only")
+    logp = logp.contiguous().float()
+    dev = logp.device
+    n_em, Tq, V = logp.shape
+    tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
+    H, S = tokens.shape
+
+    def i32(t, n, name):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=torch.int32).contiguous()
+        if t.numel() != n:
+            raise ValueError(f"ctc_align: {name} must have {n} entries, got {t.numel()}")
+        return t
+    tok_len = torch.full((H,), S, dtype=torch.int32, device=dev) if tok_len is None else i32(tok_len, H, "tok_len")
+    em_index, em_len = i32(em_index, H, "em_index"), i32(em_len, n_em, "em_len")
+    if em_index is None and H > n_em:
+        raise ValueError(f"ctc_align: {H} hypotheses, {n_em} emissions and no em_index")
+    point_token = torch.empty((H, Tq), dtype=torch.int32, device=dev)
+    point_score = torch.empty((H, Tq), dtype=torch.float32, device=dev)
+    path_score = torch.empty((H,), dtype=torch.float32, device=dev)
+    final_score = torch.empty((H,), dtype=torch.float32, device=dev)
+    status = torch.empty((H,), dtype=torch.int32, device=dev)
+    trellis = torch.empty((H, Tq + 1, S + 1), dtype=torch.float32, device=dev) if want_trellis else None
+    lib = capi.load()
+    ws = torch.empty((lib.eec_ctc_align_workspace_bytes(H, Tq, S),), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_ctc_align(logp.data_ptr(), n_em, Tq, V, ptr(em_len), tokens.data_ptr(), tok_len.data_ptr(), ptr(em_index), H, S,
+                                     int(blank), point_token.data_ptr(), point_score.data_ptr(), path_score.data_ptr(),
+                                     final_score.data_ptr(), status.data_ptr(), ptr(trellis), ws.data_ptr() if ws.numel() else None,
+                                     stream_ptr(dev)), "eec_ctc_align")
+    return point_token, point_score, path_score, final_score, status, trellis
 
 
 class _ExitCtcLossFn(torch.autograd.Function):

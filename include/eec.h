@@ -246,6 +246,38 @@ int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, 
 int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                            int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream);
 
+/* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
+ * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam
+ * choice (util/beam_infer.py:309-383) --, for n_hyp hypotheses in one launch (one wavefront each; csrc/ctc_align.hip).
+ * The reference's semantics, quirks included.  With em [T, V] the emission of a hypothesis, tok its N ids, tr [T+1, N+1]:
+ *   tr[0,0] = 0;  tr[t+1,0] = tr[t,0] + em[t,0] (column 0 of the emission, not `blank`);  tr[0,1:] = -inf;
+ *   tr[T+1-N:,0] = +inf (after the cumulative sum);  tr[t+1,j] = max(tr[t,j] + em[t,blank], tr[t,j-1] + em[t,tok[j-1]]):
+ *   a token occupies exactly one frame, staying costs the blank, repeated tokens get no special treatment.  The +inf cells
+ *   (rows >= T+1-N+j) feed only each other and are never read by the backtrack.
+ *   Backtrack from (t, j) = (T, N): stayed = tr[t-1,j] + em[t-1,blank], changed = tr[t-1,j-1] + em[t-1,tok[j-1]]; the change is
+ *   taken only if changed > stayed (a tie stays); prob += em[t-1, changed ? tok[j-1] : 0] (the literal 0, not `blank`);
+ *   Point(j-1, t-1, prob); after a change --j, stop at j == 0.  path[0].score is the sum over the whole path.
+ *   logp [n_em, T', V] fp32; em_len [n_em] int32 frames T of every emission, or NULL = T' for all
+ *   tokens [n_hyp, tok_stride] int64, tok_len [n_hyp] int32 (N); em_index [n_hyp] int32 the emission of every hypothesis, or
+ *   NULL = its own index h (then n_em >= n_hyp)
+ *   point_token [n_hyp, T'] int32: the Point's token_index at frame t; -1 before the first token's frame and from T on
+ *   point_score [n_hyp, T'] fp32: the Point's cumulative score (summed from the last frame, as the reference does); -inf there
+ *   path_score [n_hyp] = path[0].score, final_score [n_hyp] = tr[T, N]
+ *   status [n_hyp] int32: 0 aligned; 1 not alignable -- N = 0, N > T (the reference prints "Failed to align" and returns a
+ *       fragment: a stated divergence), N > tok_stride, a token id outside [0, V), an em_index outside [0, n_em), an em_len
+ *       outside [1, T'], or non-finite emissions that leave the backtrack short of the first token.  None of these is used as
+ *       an address; the row's outputs are the fill values (-1, -inf).
+ *   trellis_opt: NULL, or [n_hyp, T' + 1, tok_stride + 1] fp32: the full trellis, +-inf cells included, rows past T and columns
+ *       past N (and every cell of a status-1 row) -inf.
+ *   workspace: eec_ctc_align_workspace_bytes(n_hyp, T', max tokens) bytes -- 0 today (decisions live in LDS), NULL is accepted.
+ * EEC_ERR_BAD_ARG: a null required pointer, blank outside [0, V), tok_stride < 1, n_hyp < 0, T' < 1, n_em < 1; n_hyp == 0 is a
+ * successful no-op.  EEC_ERR_UNSUPPORTED: tok_stride > 255, V < 2, or T' * (8 * ceil((tok_stride + 1) / 64) + 6) > 65536 bytes
+ * of LDS (T' <= 1724 at tok_stride 255, T' <= 2978 below 128).  No allocation, no synchronisation; graph-capturable. */
+size_t eec_ctc_align_workspace_bytes(int n_hyp, int Tq, int max_tokens);
+int eec_ctc_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int64_t* tokens, const int32_t* tok_len,
+                  const int32_t* em_index, int n_hyp, int tok_stride, int blank, int32_t* point_token, float* point_score,
+                  float* path_score, float* final_score, int32_t* status, float* trellis_opt, void* workspace, void* stream);
+
 /* Mel front end: replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
  * n_mels, n_stft = 513; htk scale, no normalisation), NO log -- on the device, as an exact-fp32 MFMA transform.
