@@ -1,8 +1,12 @@
 // Summed per-exit CTC loss, forward (reference train.py:53-65,259):
 //   loss_e = mean_b( CTC(logp[e, b], targets[b, :len_b]) / max(len_b, 1) ),  blank = 0,
 //   input length = T' for every utterance, zero_infinity=True;  train.py sums loss_e over exits.
-// All E*B lattices run in ONE launch: one wave per lattice, the extended label sequence
-// (2*len+1 states, <= 8 per lane) lives in registers.  The time recursion is latency-bound (T' serial
+// All E*B lattices run in ONE launch, the extended label sequence (2*len+1 states, <= 8 per lane) in registers.  Two entries:
+//   the loss alone (eec_ctc_loss, the benchmarked step): ctc_loss_kernel, then ctc_reduce_kernel.  Two waves per lattice walk
+//     it from both ends in the WIDE format (one exponent per state: no range limit) and meet in the middle; see the kernel.
+//   the training forward (eec_ctc_loss_forward): ctc_alpha_kernel, which stores what the backward pass needs, then
+//     ctc_loss_kernel on the lattices it marked (RANGE below), then ctc_reduce_kernel.
+// ctc_alpha_kernel: one wave per lattice.  The time recursion is latency-bound (T' serial
 // steps), so it runs in a BLOCK-FLOATING linear domain instead of log space:
 //   a_t[s] = ( a_{t-1}[s] + a_{t-1}[s-1] + [a_{t-1}[s-2]] ) * p_t(l'_s),   p = exp(logp)
 // Each lane keeps its states as fp32 mantissas times a lane-private power of two 2^e (renormalised
@@ -23,9 +27,10 @@
 // beta') and what a beta' can still meet (its alpha) are probabilities <= 1: all events together take at most
 // N * kCtcTiny * 2^(largest ec) from p(target), N = number of (state, step) pairs.  Where that is below 2^-26 of p(target)
 // the events are harmless (trailing states of a peaky lattice; the usual case); otherwise the lattice is MARKED and run again
-// by ctc_wide_kernel, the same recursion with one exponent per STATE (no range limit, a renormalisation per step; about
-// twice the fast path's time per lattice).  The fast path's own arithmetic is unchanged: the watch is compares only.
-// The bound is sufficient, not sharp: random log-probs with |log-prob| of 10 and more over 256 frames mark most lattices.
+// in the wide format, the same recursion with one exponent per STATE (no range limit, a renormalisation per step): its loss by
+// ctc_loss_kernel, its posteriors by ctc_wide_kernel.  The fast path's own arithmetic is unchanged: the watch is compares only.
+// The bound is sufficient, not sharp: random log-probs with |log-prob| of 10 and more over 256 frames mark most lattices, which
+// is why the loss alone does not take this path at all.
 #include <limits.h>
 
 #include "eec_kernels.h"
@@ -35,7 +40,7 @@ namespace eec {
 constexpr int kCtcPerLane = 8;  // up to 512 states = target length <= 255
 constexpr int kCtcEmpty = -(1 << 20);  // exponent of a lane that holds no probability mass yet
 constexpr float kCtcTiny = 7.52316385e-37f;  // 2^-120: a non-zero value that falls below it may have lost bits (fp32 normals end at 2^-126)
-// markers of a lattice the fast path gave up on: nll = -inf after ctc_alpha_kernel (replaced by ctc_wide_kernel before the
+// markers of a lattice the fast path gave up on: nll = -inf after ctc_alpha_kernel (replaced by ctc_loss_kernel before the
 // reduction), p(target) slot < 0 for the backward pass
 constexpr float kCtcRedo = -1.f;
 // events at scale 2^ec are harmless when ec <= exponent(p(target)) + ctc_watch_slack: -120 (kCtcTiny) + log2 N + 26 <= 0
@@ -49,13 +54,13 @@ __host__ __device__ inline int ctc_watch_slack(int Tq) {
   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (float)(old)), __builtin_bit_cast(int, (float)(src)), ctrl, 0xf, 0xf, false))
 #define EEC_DPP_I(old, src, ctrl) __builtin_amdgcn_update_dpp((int)(old), (int)(src), ctrl, 0xf, 0xf, false)
 
-// STORE: every step's scaled alphas and lane exponents are also written to `astore` (layout ctc_store_index below):
-// the backward pass multiplies them with the betas it recomputes (ctc_beta_kernel).
+// The training forward (ctc_alpha_kernel): every step's scaled alphas and lane exponents are written to `astore` (layout
+// ctc_store_index below); the backward pass multiplies them with the betas it recomputes (ctc_beta_kernel).
 __device__ __forceinline__ size_t ctc_store_index(int lat, int Tq, int P, int t, int k, int lane) {
   return (((size_t)lat * Tq + t) * (P + 1) + k) * 64 + lane;  // k < P: state lane*P + k; k == P: the lane's exponent
 }
 
-template <int P, bool STORE>
+template <int P>
 __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
                                                        const long long* __restrict__ target_len, int B, int Tq, int V,
                                                        int S, int blank, float* __restrict__ nll, float* __restrict__ astore) {
@@ -106,11 +111,9 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
   }
   if (lane == 0) ex = 0;
   auto store = [&](int t) {
-    if constexpr (STORE) {
 #pragma unroll
-      for (int i = 0; i < P; ++i) astore[ctc_store_index(lat, Tq, P, t, i, lane)] = alpha[i];
-      astore[ctc_store_index(lat, Tq, P, t, P, lane)] = __builtin_bit_cast(float, ex);
-    }
+    for (int i = 0; i < P; ++i) astore[ctc_store_index(lat, Tq, P, t, i, lane)] = alpha[i];
+    astore[ctc_store_index(lat, Tq, P, t, P, lane)] = __builtin_bit_cast(float, ex);
   };
   store(0);
   // emission log-probs are gathered kCtcAhead steps ahead of their use (exponentiated when used)
@@ -198,12 +201,10 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
                : redo                  ? -INFINITY
                : (total > 0.f)         ? -(logf(total) + (float)e_max * 0.6931471805599453f)
                                        : INFINITY;
-  if constexpr (STORE) {  // p(target) = total * 2^e_max, kept exactly for the backward pass (nll alone rounds it to ~1e-4 relative)
-    if (lane == 0) {
-      float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
-      pinfo[0] = (bad || total != total) ? __builtin_nanf("") : redo ? kCtcRedo : total;
-      pinfo[1] = __builtin_bit_cast(float, e_max);
-    }
+  if (lane == 0) {  // p(target) = total * 2^e_max, kept exactly for the backward pass (nll alone rounds it to ~1e-4 relative)
+    float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
+    pinfo[0] = (bad || total != total) ? __builtin_nanf("") : redo ? kCtcRedo : total;
+    pinfo[1] = __builtin_bit_cast(float, e_max);
   }
 }
 
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
   const float* lp = logp + (size_t)lat * Tq * V;
   float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
-  if (pinfo[0] < 0.f) return;  // the forward pass left this lattice to ctc_wide_kernel (wave-uniform)
+  if (pinfo[0] < 0.f) return;  // the forward pass left this lattice to the wide format (wave-uniform)
   const long long len_raw = target_len[b];
   const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
   const int L = 2 * len + 1;
@@ -405,10 +406,10 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
 // The wide path: the lattices the block-floating kernels marked (see RANGE at the top).  Same linear-domain recursions, but
 // every state carries its own exponent -- value = m * 2^e, m in [1, 2) or 0 -- and is renormalised at every step, and an
 // emission enters as exp(l) = pm * 2^k with the product l * log2(e) split exactly, so nothing can leave the range whatever the
-// log-probs are (below -3e4 they count as -inf: impossible).  One wave per marked lattice, a 4-step look-ahead ring; the waves of
-// unmarked lattices return at once.  GRAD = false: the loss alone (after ctc_alpha_kernel).  GRAD = true (after
-// ctc_beta_kernel): the forward recursion again, its states kept (mantissas in the alpha slots of `astore`, exponents in the
-// region behind it), then the beta recursion, which overwrites the mantissas with the state posteriors for ctc_grad_kernel.
+// log-probs are (below -3e4 they count as -inf: impossible).  ctc_wide_kernel (after ctc_beta_kernel; one wave per marked lattice,
+// a 4-step look-ahead ring; the waves of unmarked lattices return at once): the forward recursion again, its states kept
+// (mantissas in the alpha slots of `astore`, exponents in the region behind it), then the beta recursion, which overwrites the
+// mantissas with the state posteriors for ctc_grad_kernel.  ctc_loss_kernel (further down) is the same format's loss.
 constexpr int kCtcWideEmpty = -(1 << 30);
 
 __device__ __forceinline__ void ctc_wide_exp(float l, float& pm, int& k) {
@@ -430,18 +431,14 @@ __device__ __forceinline__ float ctc_wide_add3(float m0, int e0, float m1, int e
   return ldexpf(m0, max(e0 - ec, -64)) + ldexpf(m1, max(e1 - ec, -64)) + ldexpf(m2, max(e2 - ec, -64));
 }
 
-template <int P, bool GRAD>
+template <int P>
 __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
                                                       const long long* __restrict__ target_len, int B, int Tq, int V, int S,
                                                       int blank, float* __restrict__ nll, float* __restrict__ astore) {
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
-  if constexpr (GRAD) {
-    if (!(astore[ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat] < 0.f)) return;
-  } else {
-    if (!(nll[lat] == -INFINITY)) return;
-  }
+  if (!(astore[ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat] < 0.f)) return;
   const float* lp = logp + (size_t)lat * Tq * V;
-  int* estore = GRAD ? (int*)(astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)gridDim.x) : nullptr;  // [lat][t][P][64]
+  int* estore = (int*)(astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)gridDim.x);  // [lat][t][P][64]
   const long long len_raw = target_len[b];  // a marked lattice passed ctc_alpha_kernel's input checks
   const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
   const int L = 2 * len + 1;
@@ -471,12 +468,10 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
     ctc_wide_norm((s < 2 && s < L) ? pm : 0.f, k, am[i], ae[i]);
   }
   auto store = [&](int t) {
-    if constexpr (GRAD) {
 #pragma unroll
-      for (int i = 0; i < P; ++i) {
-        astore[ctc_store_index(lat, Tq, P, t, i, lane)] = am[i];
-        estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane] = ae[i];
-      }
+    for (int i = 0; i < P; ++i) {
+      astore[ctc_store_index(lat, Tq, P, t, i, lane)] = am[i];
+      estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane] = ae[i];
     }
   };
   store(0);
@@ -538,60 +533,269 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
   float mt;
   int et;
   ctc_wide_norm(total, e_max, mt, et);
-  if constexpr (!GRAD) {
-    if (lane == 0) nll[lat] = total > 0.f ? -(logf(mt) + (float)et * 0.6931471805599453f) : INFINITY;
-    return;
-  } else {
-    if (!(total > 0.f)) return;  // infeasible: nll is +inf and ctc_grad_kernel writes zeros
-    bool skip_dn[P];
-    {
-      int n0 = __shfl_down((int)skip_ok[0], 1, 64), n1 = __shfl_down((int)skip_ok[1], 1, 64);
-      if (lane == 63) n0 = n1 = 0;
+  if (!(total > 0.f)) return;  // infeasible: nll is +inf and ctc_grad_kernel writes zeros
+  bool skip_dn[P];
+  {
+    int n0 = __shfl_down((int)skip_ok[0], 1, 64), n1 = __shfl_down((int)skip_ok[1], 1, 64);
+    if (lane == 63) n0 = n1 = 0;
 #pragma unroll
-      for (int i = 0; i < P; ++i) skip_dn[i] = i + 2 < P ? skip_ok[i + 2 < P ? i + 2 : 0] : ((i + 2 - P == 0 ? n0 : n1) != 0);
+    for (int i = 0; i < P; ++i) skip_dn[i] = i + 2 < P ? skip_ok[i + 2 < P ? i + 2 : 0] : ((i + 2 - P == 0 ? n0 : n1) != 0);
+  }
+  const float inv = 1.0f / mt;
+  float bm[P];
+  int be[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int s = lane * P + i;
+    const bool last = s < L && (s == L - 1 || s == L - 2);
+    bm[i] = last ? 1.f : 0.f;
+    be[i] = last ? 0 : kCtcWideEmpty;
+  }
+  for (int t = Tq - 1; t >= 0; --t) {
+    float wm[P];
+    int we[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const size_t ia = ctc_store_index(lat, Tq, P, t, i, lane);
+      const float a_m = astore[ia];
+      const int a_e = estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane];
+      const bool nz = a_m > 0.f && bm[i] > 0.f;
+      const int sh = nz ? min(max(a_e + be[i] - et, -200), 126) : 0;
+      astore[ia] = nz ? ldexpf(a_m * bm[i] * inv, sh) : 0.f;  // the posterior of state lane * P + i at time t
+      float pm;
+      int k;
+      ctc_wide_exp(lp[(size_t)t * V + label[i]], pm, k);
+      ctc_wide_norm(live[i] ? bm[i] * pm : 0.f, be[i] + k, wm[i], we[i]);
     }
-    const float inv = 1.0f / mt;
-    float bm[P];
-    int be[P];
+    float d1m = __shfl_down(wm[0], 1, 64), d2m = __shfl_down(wm[1], 1, 64);
+    int d1e = __shfl_down(we[0], 1, 64), d2e = __shfl_down(we[1], 1, 64);
+    if (lane == 63) d1m = d2m = 0.f, d1e = d2e = kCtcWideEmpty;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const float n1m = i + 1 < P ? wm[i + 1 < P ? i + 1 : 0] : d1m;
+      const int n1e = i + 1 < P ? we[i + 1 < P ? i + 1 : 0] : d1e;
+      float n2m = i + 2 < P ? wm[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1m : d2m);
+      int n2e = i + 2 < P ? we[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1e : d2e);
+      if (!skip_dn[i]) n2m = 0.f, n2e = kCtcWideEmpty;
+      int ec;
+      const float sum = ctc_wide_add3(wm[i], we[i], n1m, n1e, n2m, n2e, ec);
+      ctc_wide_norm(sum, ec, bm[i], be[i]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The loss alone (eec_ctc_loss, and the marked lattices of the training forward): the wide format on EVERY lattice -- no range
+// limit, so no watch, no marking and no second pass -- with the T' - 1 dependent steps shared by two waves.  At any frame m
+//     p(target) = sum_s alpha_m(s) * beta'_m(s),     beta' as defined above ctc_beta_kernel,
+// so wave 0 of a workgroup walks alpha from frame 0 up to m = (T' - 1) / 2 while wave 1 walks from frame T' - 1 down to m + 1;
+// both keep state lane * P + i in slot i, share nothing until wave 1 hands beta'_m over through LDS (one barrier), and wave 0
+// forms the sum.  Both halves run ONE recursion, X_t(s) = p_t(l'_s) * (X_u(s) + X_u(s -+ 1) + [X_u(s -+ 2)]), u = t -+ 1:
+// upwards X = alpha (neighbours in the previous lane); downwards X_t(s) = beta'_t(s) p_t(l'_s) (neighbours in the next lane),
+// and beta'_m is one more neighbour sum without an emission.  T' = 1 .. 3: m = 0, 0, 1, wave 0 takes 0, 0, 1 steps, wave 1
+// none (T' = 1: beta'_0 is the indicator of the last two states, no emission; T' = 2, 3: its start and the closing sum).
+// NaN log-probs: a NaN emission makes its state's mantissa NaN and travels with it (ctc_loss_norm keeps it).  As in torch and
+// ctc_alpha_kernel, a NaN emission of a live state counts whether or not any mass has reached the state (upwards 0 * NaN = NaN;
+// a NaN beta'_m makes its term NaN even where alpha_m is 0): reachability from the START is never asked for.  What is asked
+// for is a way on to the END with non-zero probability: the downward half multiplies an emission in only where the sum behind
+// it is non-zero, and the closing sum drops a NaN alpha_m where beta'_m is 0.  So the loss is NaN when a live state's NaN
+// emission has such a way to the final states, and is not disturbed by one that has none (torch asks for a way by the
+// transitions alone: the two differ only where exact -inf log-probs close every way that the transitions leave open).
+__device__ __forceinline__ void ctc_loss_exp(float l, float& pm, int& k) {  // ctc_wide_exp that keeps a NaN
+  const float hi = l * 1.44269502f;
+  const float lo = fmaf(l, 1.44269502f, -hi) + l * 1.92596299e-8f;
+  const float kf = floorf(hi);
+  pm = l <= -3.0e4f ? 0.f : __builtin_amdgcn_exp2f((hi - kf) + lo);  // the argument is in [0, 1]: exp2f's range fix-up is idle
+  k = l > -3.0e4f ? (int)kf : 0;
+}
+__device__ __forceinline__ void ctc_loss_norm(float v, int base, float& m, int& e) {  // v: 0, a normal number or NaN
+  const int ex = (int)((__builtin_bit_cast(unsigned, v) >> 23) & 0xffu) - 127;
+  m = ldexpf(v, -ex);  // 0 stays 0
+  e = v != 0.f ? base + ex : kCtcWideEmpty;
+}
+
+// sum[i] * 2^ec[i] = X(s) + X(s -+ 1) + [X(s -+ 2) where the skip is allowed], s = lane * P + i
+template <int P, bool DOWN>
+__device__ __forceinline__ void ctc_loss_sums(const float (&xm)[P], const int (&xe)[P], const bool (&skip)[P], float (&sum)[P],
+                                              int (&ec)[P]) {
+  // the two states next to this lane's: the previous lane's last two (wave_shr:1) or the next lane's first two (wave_shl:1);
+  // the lane at the end of the wave receives empty states
+  constexpr int ctrl = DOWN ? 0x130 : 0x138;
+  const float u1m = EEC_DPP_F(0.f, xm[DOWN ? 0 : P - 1], ctrl), u2m = EEC_DPP_F(0.f, xm[DOWN ? 1 : P - 2], ctrl);
+  const int u1e = EEC_DPP_I(kCtcWideEmpty, xe[DOWN ? 0 : P - 1], ctrl), u2e = EEC_DPP_I(kCtcWideEmpty, xe[DOWN ? 1 : P - 2], ctrl);
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int d1 = DOWN ? i + 1 : i - 1, d2 = DOWN ? i + 2 : i - 2;  // slots of the neighbours; outside [0, P): the other lane's
+    const bool in1 = d1 >= 0 && d1 < P, in2 = d2 >= 0 && d2 < P;
+    const bool far2 = DOWN ? d2 == P + 1 : d2 == -2;
+    const float n1m = in1 ? xm[in1 ? d1 : 0] : u1m;
+    const int n1e = in1 ? xe[in1 ? d1 : 0] : u1e;
+    float n2m = in2 ? xm[in2 ? d2 : 0] : (far2 ? u2m : u1m);
+    int n2e = in2 ? xe[in2 ? d2 : 0] : (far2 ? u2e : u1e);
+    if (!skip[i]) n2m = 0.f, n2e = kCtcWideEmpty;
+    sum[i] = ctc_wide_add3(xm[i], xe[i], n1m, n1e, n2m, n2e, ec[i]);
+  }
+}
+
+// n steps of the recursion over the frames t_first, t_first +- 1, ...; the emission log-probs are gathered kAhead steps ahead of
+// their use (raw; split into mantissa and exponent when used), never from a frame beyond the walk's last one
+template <int P, bool DOWN>
+__device__ __forceinline__ void ctc_loss_walk(const float* __restrict__ lp, int V, const int (&label)[P], const bool (&skip)[P],
+                                              const bool (&live)[P], int t_first, int n, float (&xm)[P], int (&xe)[P]) {
+  // label: byte offsets of the states' classes in a row of log-probs (32 bits beside the row's wave-uniform address)
+  if (n <= 0) return;  // wave-uniform
+  constexpr int kAhead = P <= 4 ? 16 : 8;  // 78 / 144 / 148 VGPRs at P = 2 / 4 / 8, no scratch; at P = 2, 8 measures the same, 32 is 3 us slower
+  float emit[kAhead][P];
+  auto gather = [&](float (&em)[P], int j) {
+    const float* row = lp + (size_t)(DOWN ? t_first - min(j, n - 1) : t_first + min(j, n - 1)) * V;  // wave-uniform
+#pragma unroll
+    for (int i = 0; i < P; ++i) em[i] = *(const float*)((const char*)row + (unsigned)label[i]);
+  };
+#pragma unroll
+  for (int d = 0; d < kAhead; ++d) gather(emit[d], d);
+  auto step = [&](const float (&em)[P]) {
+    float sum[P];
+    int ec[P];
+    ctc_loss_sums<P, DOWN>(xm, xe, skip, sum, ec);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      float pm;
+      int k;
+      ctc_loss_exp(em[i], pm, k);
+      // upwards: states beyond 2 len + 1 stay empty (`live`).  Downwards `live` is not needed: those states receive from
+      // higher ones only and are empty anyway, and an emission (NaN included) counts only where the end can be reached from
+      const bool keep = DOWN ? sum[i] != 0.f : live[i];
+      ctc_loss_norm(keep ? sum[i] * pm : 0.f, ec[i] + k, xm[i], xe[i]);
+    }
+  };
+  int j0 = 0;
+  for (; j0 + kAhead <= n; j0 += kAhead) {  // full groups
+#pragma unroll
+    for (int d = 0; d < kAhead; ++d) {
+      step(emit[d]);
+      gather(emit[d], j0 + d + kAhead);  // clamped to the last frame of the walk: a harmless re-read near its end
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < kAhead; ++d)  // ragged tail (wave-uniform guard); its emissions are already in the ring
+    if (j0 + d < n) step(emit[d]);
+}
+
+// only_marked: the training forward's follow-up launch -- lattices ctc_alpha_kernel marked (nll == -inf) are run, the others keep
+// their nll
+template <int P>
+__global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
+                                                       const long long* __restrict__ target_len, int B, int Tq, int V, int S,
+                                                       int blank, int only_marked, float* __restrict__ nll) {
+  __shared__ float beta_m[P][64];
+  __shared__ int beta_e[P][64];
+  const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x & 63;
+  const bool down = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) != 0;  // wave 1
+  // read by both waves before the barrier; written by wave 0 behind it
+  if (only_marked && !(nll[lat] == -INFINITY)) return;
+  const float* lp = logp + (size_t)lat * Tq * V;
+  // inputs nn.CTCLoss validates on the host, as in ctc_alpha_kernel: such a lattice is not run, its nll becomes NaN
+  const long long len_raw = target_len[b];
+  bool bad = len_raw < 0 || len_raw > (long long)S;
+  const int len = bad ? 0 : (int)len_raw;
+  const int L = 2 * len + 1;
+  int label[P];
+  bool skip_ok[P], live[P], last[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int s = lane * P + i;
+    label[i] = blank;
+    skip_ok[i] = false;
+    live[i] = s < L;
+    last[i] = s < L && (s == L - 1 || s == L - 2);
+    if (s < L && (s & 1)) {
+      const int k = s >> 1;
+      const long long lab = targets[(size_t)b * S + k];
+      if (lab < 0 || lab >= (long long)V) bad = true;
+      label[i] = (lab < 0 || lab >= (long long)V) ? blank : (int)lab;
+      skip_ok[i] = k > 0 && lab != targets[(size_t)b * S + k - 1];
+    }
+  }
+  bad = __any((int)bad) != 0;  // wave-uniform, and the same in both waves (they hold the same states)
+  if (bad) {
+    if (threadIdx.x == 0) nll[lat] = __builtin_nanf("");
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    // keep every label in a VGPR: a label the compiler can prove wave-uniform (the blanks) would turn its gather into
+    // s_load + s_waitcnt lgkmcnt(0), which serialises the look-ahead ring
+    label[i] *= (int)sizeof(float);  // from here on: the class's byte offset in a row
+    asm volatile("" : "+v"(label[i]));
+  }
+  static_assert(P % 2 == 0, "a lane's first state must be a blank");
+  auto at = [&](int t, int i) { return *(const float*)((const char*)(lp + (size_t)t * V) + (unsigned)label[i]); };
+  const int m = (Tq - 1) / 2;
+  float xm[P];
+  int xe[P];
+  if (!down) {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       const int s = lane * P + i;
-      const bool last = s < L && (s == L - 1 || s == L - 2);
-      bm[i] = last ? 1.f : 0.f;
-      be[i] = last ? 0 : kCtcWideEmpty;
+      float pm;
+      int k;
+      ctc_loss_exp(at(0, i), pm, k);
+      ctc_loss_norm((s < 2 && s < L) ? pm : 0.f, k, xm[i], xe[i]);
     }
-    for (int t = Tq - 1; t >= 0; --t) {
-      float wm[P];
-      int we[P];
+    ctc_loss_walk<P, false>(lp, V, label, skip_ok, live, 1, m, xm, xe);
+  } else {
+    if (Tq - 1 > m) {
+      // the transition s -> s + 2 is allowed when state s + 2 may be entered by a skip
+      bool skip_dn[P];
+      const int n0 = EEC_DPP_I(0, (int)skip_ok[0], 0x130), n1 = EEC_DPP_I(0, (int)skip_ok[1], 0x130);
+#pragma unroll
+      for (int i = 0; i < P; ++i) skip_dn[i] = i + 2 < P ? skip_ok[i + 2 < P ? i + 2 : 0] : ((i + 2 - P == 0 ? n0 : n1) != 0);
 #pragma unroll
       for (int i = 0; i < P; ++i) {
-        const size_t ia = ctc_store_index(lat, Tq, P, t, i, lane);
-        const float a_m = astore[ia];
-        const int a_e = estore[(((size_t)lat * Tq + t) * P + i) * 64 + lane];
-        const bool nz = a_m > 0.f && bm[i] > 0.f;
-        const int sh = nz ? min(max(a_e + be[i] - et, -200), 126) : 0;
-        astore[ia] = nz ? ldexpf(a_m * bm[i] * inv, sh) : 0.f;  // the posterior of state lane * P + i at time t
         float pm;
         int k;
-        ctc_wide_exp(lp[(size_t)t * V + label[i]], pm, k);
-        ctc_wide_norm(live[i] ? bm[i] * pm : 0.f, be[i] + k, wm[i], we[i]);
+        ctc_loss_exp(at(Tq - 1, i), pm, k);
+        ctc_loss_norm(last[i] ? pm : 0.f, k, xm[i], xe[i]);
       }
-      float d1m = __shfl_down(wm[0], 1, 64), d2m = __shfl_down(wm[1], 1, 64);
-      int d1e = __shfl_down(we[0], 1, 64), d2e = __shfl_down(we[1], 1, 64);
-      if (lane == 63) d1m = d2m = 0.f, d1e = d2e = kCtcWideEmpty;
+      ctc_loss_walk<P, true>(lp, V, label, skip_dn, live, Tq - 2, Tq - 2 - m, xm, xe);
+      float sum[P];
+      int ec[P];
+      ctc_loss_sums<P, true>(xm, xe, skip_dn, sum, ec);
 #pragma unroll
-      for (int i = 0; i < P; ++i) {
-        const float n1m = i + 1 < P ? wm[i + 1 < P ? i + 1 : 0] : d1m;
-        const int n1e = i + 1 < P ? we[i + 1 < P ? i + 1 : 0] : d1e;
-        float n2m = i + 2 < P ? wm[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1m : d2m);
-        int n2e = i + 2 < P ? we[i + 2 < P ? i + 2 : 0] : (i + 2 - P == 0 ? d1e : d2e);
-        if (!skip_dn[i]) n2m = 0.f, n2e = kCtcWideEmpty;
-        int ec;
-        const float sum = ctc_wide_add3(wm[i], we[i], n1m, n1e, n2m, n2e, ec);
-        ctc_wide_norm(sum, ec, bm[i], be[i]);
-      }
+      for (int i = 0; i < P; ++i) ctc_loss_norm(sum[i], ec[i], xm[i], xe[i]);
+    } else {  // T' = 1: beta'_0
+#pragma unroll
+      for (int i = 0; i < P; ++i) xm[i] = last[i] ? 1.f : 0.f, xe[i] = last[i] ? 0 : kCtcWideEmpty;
     }
+#pragma unroll
+    for (int i = 0; i < P; ++i) beta_m[i][lane] = xm[i], beta_e[i][lane] = xe[i];
   }
+  __syncthreads();
+  if (down) return;
+  // p(target) = sum_s alpha_m(s) beta'_m(s) = mt * 2^et; the terms are brought to the lane's, then the wave's largest exponent
+  float tm[P];
+  int te[P], e_lane = kCtcWideEmpty;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const float bm = beta_m[i][lane];
+    tm[i] = bm == 0.f ? 0.f : xm[i] * bm;  // 0, in [1, 4), or NaN
+    te[i] = tm[i] != 0.f ? max(xe[i], kCtcWideEmpty / 2) + max(beta_e[i][lane], kCtcWideEmpty / 2) : kCtcWideEmpty;
+    e_lane = max(e_lane, te[i]);
+  }
+  float tl = 0.f;
+#pragma unroll
+  for (int i = 0; i < P; ++i) tl += ldexpf(tm[i], max(te[i] - e_lane, -64));
+  int e_max = e_lane;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) e_max = max(e_max, __shfl_xor(e_max, off, 64));
+  float total = ldexpf(tl, max(e_lane - e_max, -64));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+  float mt;
+  int et;
+  ctc_loss_norm(total, e_max, mt, et);
+  // a NaN total stays NaN (ctc_reduce_kernel propagates it); no common state of the two halves, or none at all: infeasible
+  if (lane == 0) nll[lat] = total != 0.f ? -(logf(mt) + (float)et * 0.6931471805599453f) : INFINITY;
 }
 
 int ctc_states_per_lane(int S) {
@@ -615,8 +819,8 @@ hipError_t launch_ctc_backward(const float* logp, const long long* targets, cons
 #define EEC_CTC_BWD(P_)                                                                                                      \
   hipLaunchKernelGGL(ctc_beta_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank, nll,  \
                      astore);                                                                                               \
-  hipLaunchKernelGGL((ctc_wide_kernel<P_, true>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,      \
-                     blank, (float*)nullptr, astore);                                                                        \
+  hipLaunchKernelGGL(ctc_wide_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank,       \
+                     (float*)nullptr, astore);                                                                               \
   hipLaunchKernelGGL(ctc_grad_kernel<P_>, dim3((n_rows + 3) / 4), dim3(256), 0, st, logp, targets, target_len, B, Tq, V, S,  \
                      blank, nll, astore, grad_loss, n_rows, dlogp);
   if (P == 2) {
@@ -656,15 +860,14 @@ hipError_t launch_ctc_loss(const float* logp, const long long* targets, const lo
   // state count 2*S+1 must fit 64 lanes x P
   const int P = ctc_states_per_lane(S);
   if (!P) return hipErrorInvalidValue;
-#define EEC_CTC_FWD(P_)                                                                                                        \
-  if (astore)                                                                                                                  \
-    hipLaunchKernelGGL((ctc_alpha_kernel<P_, true>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,     \
-                       blank, nll, astore);                                                                                    \
-  else                                                                                                                         \
-    hipLaunchKernelGGL((ctc_alpha_kernel<P_, false>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,    \
-                       blank, nll, astore);                                                                                    \
-  hipLaunchKernelGGL((ctc_wide_kernel<P_, false>), dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S,       \
-                     blank, nll, astore);
+  // the training forward keeps the block-floating recursion (the backward pass needs its stored alphas) and leaves the
+  // lattices it marked to the loss kernel; the loss alone is the loss kernel on every lattice
+#define EEC_CTC_FWD(P_)                                                                                                      \
+  if (astore)                                                                                                                \
+    hipLaunchKernelGGL(ctc_alpha_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank,    \
+                       nll, astore);                                                                                         \
+  hipLaunchKernelGGL(ctc_loss_kernel<P_>, dim3(E * B), dim3(128), 0, st, logp, targets, target_len, B, Tq, V, S, blank,      \
+                     astore ? 1 : 0, nll);
   if (P == 2) {
     EEC_CTC_FWD(2)
   } else if (P == 4) {
