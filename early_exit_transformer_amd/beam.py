@@ -16,6 +16,8 @@ serve without torchaudio.
   best beam by ``weight_ctc * s_ctc + (1 - weight_ctc) * s_pred``.
 * ``BeamInference.decode_batch``  inference.py:18-62 (evaluate_batch_ae) for a whole padded batch: the encoder once per
   batch, then the searches of every exit and utterance in lockstep (``beam_search_batch``, csrc/decoder_batch.hip).
+* ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
+  every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from .lexicon import as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, encoder_lengths, greedy_ctc
 
 
@@ -56,13 +59,24 @@ def sequence_length_penalty(length: int, alpha: float = 0.6) -> float:
 class CTCHypothesis:
     """One CTC beam-search hypothesis, with the attribute names of torchaudio's ``CUCTCHypothesis`` (tokens: List[int] without
     blanks / repeats, words: List[str] -- empty here, as for a lexicon-free decoder --, score: float)."""
-    __slots__ = ("tokens", "words", "score")
+    __slots__ = ("tokens", "words", "score", "text")
 
-    def __init__(self, tokens, words, score):
-        self.tokens, self.words, self.score = tokens, words, score
+    def __init__(self, tokens, words, score, text=None):
+        self.tokens, self.words, self.score, self.text = tokens, words, score, text
 
     def __repr__(self):
         return f"CTCHypothesis(tokens={self.tokens}, words={self.words}, score={self.score:.4f})"
+
+
+class DecodedTokens(list):
+    """The token ids of one decoded hypothesis -- a plain list to every caller -- that also carry ``text``: the detokenised ids
+    after ``apply_lex``."""
+    text: Optional[str] = None
+
+
+def _snapped_texts(token_lists, lexicon, detokenize) -> List[str]:
+    """inference.py:50-51 / 70-71 for many hypotheses: ``apply_lex(detokenize(ids), lexicon)`` each, the lexicon searched once."""
+    return as_lexicon(lexicon).apply_batch([detokenize(list(t)) for t in token_lists])
 
 
 def default_max_length(T: int) -> int:
@@ -135,16 +149,24 @@ class BeamInference:
 
     sequence_length_penalty = staticmethod(sequence_length_penalty)
 
-    def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None) -> List[List["CTCHypothesis"]]:
+    def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
+                         detokenize=None) -> List[List["CTCHypothesis"]]:
         """util/beam_infer.py:102-112: the nbest (= 1) beam-search hypotheses of one exit's log-probs ``emission`` [B, T', V],
         input length T' for every utterance, beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
         hypothesis objects with ``.tokens`` / ``.words`` / ``.score`` like torchaudio's, so the reference's call sites
         (``best[0][0].tokens`` train.py:82, ``best_[0].tokens`` inference.py:70) work unchanged.  ``tokens`` (the token file
-        the torchaudio decoder takes) is accepted and unused: ids are returned, blank = 0."""
+        the torchaudio decoder takes) is accepted and unused: ids are returned, blank = 0.  With ``lexicon`` (a
+        ``lexicon.Lexicon`` or the list ``load_dict`` returns) and ``detokenize`` (ids -> str: the caller's ``sp.decode`` or
+        ``int_to_text``) every hypothesis also carries ``.text``, its ``apply_lex``-ed transcript (inference.py:70-71), and
+        ``.words``, that text's words; with either None nothing changes."""
         beam = self._arg(beam_size, "beam_size")
         tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95)
         tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
-        return [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
+        hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
+        if lexicon is not None and detokenize is not None:
+            for (h,), text in zip(hyps, _snapped_texts([h.tokens for (h,) in hyps], lexicon, detokenize)):
+                h.text, h.words = text, text.split(" ")
+        return hyps
 
     @staticmethod
     def _align_one(emission: Tensor, tokens, blank_id: int, want_trellis: bool):
@@ -365,13 +387,17 @@ class BeamInference:
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
-                     max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, **kw) -> List[List[List[int]]]:
+                     max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, lexicon=None, detokenize=None,
+                     **kw) -> List[List[List[int]]]:
         """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
         utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
         lockstep.  Where the batched search declines, every utterance goes through ``decode_all_exits``, so the result is
         always the reference's.  ``ctc_weight`` (None: unchanged, the encoder computes no log-probs): the two heads vote --
-        the encoder pass also returns the exits' CTC log-probs and every search's best beam is ``ctc_rescore``'s."""
+        the encoder pass also returns the exits' CTC log-probs and every search's best beam is ``ctc_rescore``'s.
+        ``lexicon`` and ``detokenize`` (ids -> str) together: every ``out[b][e]`` is a ``DecodedTokens`` list whose ``.text`` is
+        ``apply_lex(detokenize(ids), lexicon)`` (inference.py:50-51), all E x B texts resolved in one lexicon search; with either
+        None nothing changes."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
         E = model._cfg.n_exits
@@ -394,4 +420,10 @@ class BeamInference:
                         for b in range(sp.size(0))]
             else:
                 out += [[best for _, _, best in row] for row in together]
+        if lexicon is not None and detokenize is not None:
+            texts = iter(_snapped_texts([ids for row in out for ids in row], lexicon, detokenize))
+            out = [[DecodedTokens(ids) for ids in row] for row in out]
+            for row in out:
+                for ids in row:
+                    ids.text = next(texts)
         return out

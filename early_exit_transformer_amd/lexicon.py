@@ -1,0 +1,179 @@
+"""Lexicon post-processing on the device: the reference's ``load_dict`` / ``apply_lex`` (util/tokenizer.py:28-50), which
+``inference.py`` applies to every hypothesis it prints.  A word of the text that is not in the lexicon is replaced by the
+lexicon word with the smallest edit distance, the first such word in file order; the scan over the lexicon -- a Python loop
+per word in the reference -- is one call into libeec.so for all words at once (``eec_lexicon_nearest``, csrc/lexicon.hip).
+There is no CPU path: without a HIP device ``nearest`` raises, and with it everything that has a word to look up."""
+from __future__ import annotations
+
+import ctypes as C
+import io
+from typing import Dict, Iterable, List, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import capi
+
+MAX_QUERY = 256   # EEC_LEX_MAX_QUERY (include/eec.h): symbols of the longest word that can be looked up
+BLOCK_WORDS = 256  # EEC_LEX_BLOCK_WORDS: lexicon words per workgroup
+TILE_SWITCH = 2048  # EEC_LEX_TILE_SWITCH: queries per call from which the 32-bit kernel advances 8 queries per workgroup, not 4
+
+
+def load_dict(file_path) -> List[str]:
+    """util/tokenizer.py:28-33: one entry per line, the line feed stripped, blank lines kept as ``""``."""
+    with io.open(file_path, encoding="utf-8") as f:
+        return [line.strip("\n") for line in f]
+
+
+class _Codes(dict):
+    """``str.translate`` table: a code point of the lexicon's alphabet -> its byte code, any other -> 0."""
+
+    def __missing__(self, key):
+        return 0
+
+
+class Lexicon:
+    """A word list packed once for the device.  ``words`` in file order (duplicates and empty entries allowed: the first
+    index of a word counts); ``device``: where ``nearest`` runs, None = the HIP device current at the call -- the packed image
+    is uploaded once and follows a change of device like the encoder handle does.  ``launches`` counts the
+    ``eec_lexicon_nearest`` calls made, ``last_stream`` is the stream handle the last of them was given."""
+
+    def __init__(self, words: Iterable[str], device=None):
+        self.words: List[str] = list(words)
+        self.index: Dict[str, int] = {}
+        for i, w in enumerate(self.words):
+            self.index.setdefault(w, i)
+        self.device = None if device is None else torch.device(device)
+        self.launches = 0
+        self.last_stream = None  # the stream handle the last ``eec_lexicon_nearest`` call was given
+        self.alphabet = 0
+        self._codes = _Codes()
+        self._image = None     # host copy of the packed image (uint8 tensor)
+        self._resident = None  # (device, device copy)
+        if self.words:
+            self._pack()
+
+    def __len__(self) -> int:
+        return len(self.words)
+
+    def __contains__(self, word) -> bool:
+        return word in self.index
+
+    def _pack(self) -> None:
+        lib = capi.load()
+        lens = np.fromiter((len(w) for w in self.words), dtype=np.int64, count=len(self.words))
+        offsets = np.zeros(len(self.words) + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        symbols = np.frombuffer("".join(self.words).encode("utf-32-le", "surrogatepass"), dtype=np.uint32)
+        if symbols.size != offsets[-1]:
+            raise ValueError("Lexicon: a word does not encode to one UTF-32 unit per character")
+        if len(np.unique(symbols)) > 255:  # stated here for the message; eec_lexicon_pack refuses it as well
+            raise ValueError(f"Lexicon: {len(np.unique(symbols))} distinct symbols, the packed alphabet holds at most 255")
+        nbytes = lib.eec_lexicon_pack_bytes(len(self.words), int(offsets[-1]), int(lens.max()))
+        if nbytes == 0:
+            raise ValueError("Lexicon: the word list is too large to pack")
+        image = torch.empty((nbytes,), dtype=torch.uint8)
+        code_map = np.empty(256, dtype=np.int32)
+        n_codes = C.c_int32()
+        capi.check(lib.eec_lexicon_pack(symbols.ctypes.data if symbols.size else None, offsets.ctypes.data, len(self.words), image.data_ptr(),
+                                        nbytes, code_map.ctypes.data, C.byref(n_codes)), "eec_lexicon_pack")
+        self.alphabet = n_codes.value
+        self._codes = _Codes({int(code_map[c]): c for c in range(1, self.alphabet + 1)})
+        self._image = image
+
+    def _packed_on(self, dev: torch.device) -> Tensor:
+        if self._resident is None or self._resident[0] != dev:
+            self._resident = (dev, self._image.to(dev))
+        return self._resident[1]
+
+    def encode(self, words: Sequence[str]) -> Tuple[np.ndarray, int]:
+        """The query block of ``eec_lexicon_nearest`` as one host buffer: int32 offsets [Q + 1], then the encoded bytes; and the
+        longest word's length.  Raises for a word over ``MAX_QUERY`` symbols."""
+        longest = max((len(w) for w in words), default=0)
+        if longest > MAX_QUERY:
+            raise ValueError(f"Lexicon: a word of {longest} symbols; at most {MAX_QUERY} can be looked up (EEC_LEX_MAX_QUERY)")
+        body = "".join(words).translate(self._codes).encode("latin-1")
+        Q = len(words)
+        buf = np.zeros(4 * (Q + 1) + len(body), dtype=np.uint8)
+        np.cumsum(np.fromiter((len(w) for w in words), dtype=np.int32, count=Q), dtype=np.int32, out=buf[:4 * (Q + 1)].view(np.int32)[1:])
+        buf[4 * (Q + 1):] = np.frombuffer(body, dtype=np.uint8)
+        return buf, longest
+
+    def nearest(self, words: Sequence[str]) -> Tuple[Tensor, Tensor]:
+        """``(index, distance)``, int32 device tensors [Q]: for every word the lexicon entry with the smallest Levenshtein
+        distance (the lowest index among equals) and that distance.  The host dict is not consulted: a word of the lexicon comes
+        back as its first index at distance 0.  One ``eec_lexicon_nearest`` call on the current stream, no host synchronisation."""
+        words = list(words)
+        buf, longest = self.encode(words)
+        if not self.words:
+            raise ValueError("Lexicon.nearest: the lexicon is empty")
+        if not torch.cuda.is_available():
+            raise RuntimeError("Lexicon.nearest runs on a HIP device only")
+        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise RuntimeError("Lexicon.nearest runs on a HIP device only")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        Q = len(words)
+        out = torch.empty((2, Q), dtype=torch.int32, device=dev)
+        if Q == 0:
+            return out[0], out[1]
+        lib = capi.load()
+        with torch.cuda.device(dev):
+            packed = self._packed_on(dev)
+            query = torch.from_numpy(buf).to(dev, non_blocking=True)
+            ws_bytes = lib.eec_lexicon_nearest_workspace_bytes(Q, len(self.words))
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            stream = capi.stream_ptr(dev)
+            capi.check(lib.eec_lexicon_nearest(packed.data_ptr(), len(self.words), query.data_ptr() + 4 * (Q + 1), query.data_ptr(), Q, longest,
+                                               out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws_bytes, stream),
+                       "eec_lexicon_nearest")
+            self.launches += 1
+            self.last_stream = stream.value or 0
+        return out[0], out[1]
+
+    def apply_batch(self, texts: Sequence[str]) -> List[str]:
+        """``apply_lex`` of every text.  The words that are not in the lexicon are collected over all texts, each once, and
+        resolved by one ``nearest`` call and one device-to-host copy."""
+        pieces = [t.split(" ") for t in texts]
+        if not self.words:  # the reference's scan over nothing leaves w_min = ""
+            return [" ".join("" for _ in p) for p in pieces]
+        missing = list(dict.fromkeys(w for p in pieces for w in p if w not in self.index))
+        snapped = {}
+        if missing:
+            index = self.nearest(missing)[0].cpu().tolist()
+            snapped = {w: self.words[i] for w, i in zip(missing, index)}
+        return [" ".join(w if w in self.index else snapped[w] for w in p) for p in pieces]
+
+    def apply(self, predicted: str) -> str:
+        """util/tokenizer.py:35-50 for one text: split on the single character ``" "`` (the empty pieces of doubled, leading or
+        trailing spaces are words too), keep a piece of the lexicon, replace any other by its first nearest word, join."""
+        return self.apply_batch([predicted])[0]
+
+
+_by_list: List[Tuple[list, Lexicon]] = []  # plain lists handed to apply_lex, by identity (the list is kept alive: its id stays its own)
+
+
+def as_lexicon(lexicon: Union[Lexicon, Sequence[str]]) -> Lexicon:
+    """``lexicon`` itself, or the ``Lexicon`` packed from this very list object at its first use (the last four lists are kept;
+    a list whose length changed since is packed again, one whose entries were replaced in place must be passed as a new
+    ``Lexicon``)."""
+    if isinstance(lexicon, Lexicon):
+        return lexicon
+    for i, (words, lex) in enumerate(_by_list):
+        if words is lexicon:
+            if len(words) == len(lex):
+                return lex
+            del _by_list[i]  # grown or shrunk in place since it was packed: pack it again
+            break
+    lex = Lexicon(lexicon)
+    _by_list.append((lexicon, lex))
+    del _by_list[:-4]
+    return lex
+
+
+def apply_lex(predicted: str, lexicon: Union[Lexicon, Sequence[str]]) -> str:
+    """The reference's ``apply_lex(predicted, lexicon)`` (util/tokenizer.py:35-50); ``lexicon`` is a ``Lexicon`` or the plain
+    list ``load_dict`` returns."""
+    return as_lexicon(lexicon).apply(predicted)

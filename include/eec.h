@@ -278,6 +278,59 @@ int eec_ctc_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_
                   const int32_t* em_index, int n_hyp, int tok_stride, int blank, int32_t* point_token, float* point_score,
                   float* path_score, float* final_score, int32_t* status, float* trellis_opt, void* workspace, void* stream);
 
+/* Lexicon post-processing: replaces the scan of apply_lex (util/tokenizer.py:35-50), which inference.py applies to every
+ * hypothesis it prints -- a word that is not in the lexicon becomes the lexicon word with the smallest Levenshtein distance,
+ * the first such word in file order (strict <) --, for n_queries words against the whole lexicon in one call
+ * (csrc/lexicon.hip: Myers / Hyyro bit-parallel edit distance, one work-item per (query, lexicon word) pair).
+ * Symbols are Unicode code points.  The packer maps the lexicon's distinct code points, in ascending order, to the byte codes
+ * 1..A (A <= 255); a query symbol outside that alphabet is encoded as 0, which matches nothing.
+ *
+ * eec_lexicon_pack is HOST code and needs no device:
+ *   symbols [offsets[n_words]] UTF-32 code points of all words, flat; offsets [n_words + 1] int64, offsets[0] = 0, ascending
+ *       (word i = symbols[offsets[i] .. offsets[i+1]); empty words are legal and keep their index)
+ *   image: image_bytes >= eec_lexicon_pack_bytes(n_words, offsets[n_words], longest word) bytes of host memory, 8-byte aligned;
+ *       the caller copies exactly that many bytes to the device (8-byte aligned) and passes them as `packed`
+ *   code_map [256] int32: code -> code point for 1..A, -1 elsewhere;  n_codes: NULL or where A is written
+ *   image layout, int32 units: header[16] = {magic, n_words, max_len, n_groups = ceil(max_len / 4), A, info offset, gbase
+ *       offset, sym offset, sym dwords, total dwords, 0..};  info [n_words][2] = (original index, length) of the word at sorted
+ *       position s -- the words are stably sorted by length, a speed choice only --;  gbase [n_groups]: the dword holding symbols
+ *       4g .. 4g+3 of sorted word s (symbol 4g+k in byte k, unused bytes 0) is sym[gbase[g] + s], stored for the words longer
+ *       than 4g only (a suffix of the sorted order), position-major.
+ *   eec_lexicon_pack_bytes is non-decreasing in each argument; 0 for n_words <= 0, negative sizes, total_symbols >
+ *       n_words * max_len, or an image of 2^31 dwords or more.
+ *   EEC_ERR_BAD_ARG: a null pointer, n_words <= 0, offsets not ascending from 0.  EEC_ERR_UNSUPPORTED: more than 255 distinct
+ *   code points.  EEC_ERR_WORKSPACE: image_bytes too small.
+ *
+ * eec_lexicon_nearest:
+ *   packed: the image on the device; n_words must be the count it was packed with
+ *   queries: encoded query bytes, flat, on the device; query_offsets [n_queries + 1] int32 on the device (query q =
+ *       queries[query_offsets[q] .. query_offsets[q+1]))
+ *   max_query_len: the longest query of the call, stated by the caller (the offsets are device memory): it selects the kernel
+ *       (32-bit vectors up to 32 symbols, 64-bit up to 64, 8 x 32-bit with carries up to EEC_LEX_MAX_QUERY)
+ *   out_index, out_distance [n_queries] int32: argmin_i levenshtein(query, word i) with ties to the LOWEST original index, and
+ *       that distance.  A query of no symbols gets the first shortest word.  (-1, -1) for a query whose offsets are negative,
+ *       descending or more than max_query_len apart (none of its bytes is read), and for every query when the image's header does
+ *       not carry n_words.
+ *   workspace: eec_lexicon_nearest_workspace_bytes(n_queries, n_words) bytes, 8-byte aligned: the per-share minima.
+ * The 32-bit kernel has two forms: a workgroup advances 4 queries side by side below EEC_LEX_TILE_SWITCH queries per call and 8
+ * from there on (same results; the wider tile reads the lexicon half as often).
+ * A workgroup is EEC_LEX_BLOCK_WORDS work-items, one lexicon word each; with few queries the lexicon is dealt over up to one
+ * workgroup per EEC_LEX_BLOCK_WORDS words.  Two kernels on `stream` (the search, then the reduction of the shares, one wave
+ * per query); integer keys (distance << 32 | index) under min, so results are bit-identical run to run.
+ * EEC_ERR_BAD_ARG: a null pointer, n_words <= 0, n_queries < 0, max_query_len < 0, a misaligned image or workspace;
+ * n_queries == 0 is a successful no-op.  EEC_ERR_UNSUPPORTED: max_query_len > EEC_LEX_MAX_QUERY.  EEC_ERR_WORKSPACE:
+ * workspace_bytes too small.  All checked before any device work.  No allocation, no synchronisation; graph-capturable. */
+#define EEC_LEX_MAX_QUERY 256
+#define EEC_LEX_BLOCK_WORDS 256
+#define EEC_LEX_TILE_SWITCH 2048
+size_t eec_lexicon_pack_bytes(int n_words, int64_t total_symbols, int max_len);
+int eec_lexicon_pack(const uint32_t* symbols, const int64_t* offsets, int n_words, void* image, size_t image_bytes, int32_t* code_map,
+                     int32_t* n_codes);
+size_t eec_lexicon_nearest_workspace_bytes(int n_queries, int n_words);
+int eec_lexicon_nearest(const void* packed, int n_words, const uint8_t* queries, const int32_t* query_offsets, int n_queries,
+                        int max_query_len, int32_t* out_index, int32_t* out_distance, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* Mel front end: replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
  * n_mels, n_stft = 513; htk scale, no normalisation), NO log -- on the device, as an exact-fp32 MFMA transform.
