@@ -90,7 +90,9 @@ Tape carve_tape(Bump& t, const Geo& g, bool drop) {
 // dropout sites: 0 = positional encoding (the reference embeds the targets ONCE for all exits: the same mask for every exit of a
 // forward); the others are private to (exit, layer, place)
 enum { kSitePsa = 0, kSiteRes1, kSitePca, kSiteRes2, kSiteAct, kSiteRes3, kSitesPerLayer };
-uint32_t site_of(int exit_index, int layer, int place) { return 1u + (uint32_t)exit_index * 1024u + (uint32_t)layer * kSitesPerLayer + (uint32_t)place; }
+constexpr int kMaxLayers = 64, kSitesPerExit = 1024;  // the entries refuse more layers: an exit's sites stay inside its own range
+static_assert(kMaxLayers * kSitesPerLayer <= kSitesPerExit, "the dropout sites of two exits would overlap");
+uint32_t site_of(int exit_index, int layer, int place) { return 1u + (uint32_t)exit_index * kSitesPerExit + (uint32_t)layer * kSitesPerLayer + (uint32_t)place; }
 
 struct Run {
   Geo g;
@@ -325,7 +327,7 @@ int check_geo(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, i
   if (passes != 1 && passes != 3) return dtfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
   if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return dtfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
   if (d_model <= 0 || d_model > 1024 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || vocab > 1024 || p->n_layers <= 0 ||
-      p->n_layers > 64 || Bm <= 0 || S <= 0 || Tq <= 0 || S > p->max_len)
+      p->n_layers > kMaxLayers || Bm <= 0 || S <= 0 || Tq <= 0 || S > p->max_len)
     return dtfail(EEC_ERR_BAD_ARG, "bad geometry");
   return 0;
 }
@@ -353,7 +355,7 @@ extern "C" {
 const char* eec_decoder_train_last_error(void) { return g_dterr.c_str(); }
 
 size_t eec_decoder_train_workspace_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int Bm, int S, int Tq) {
-  if (d_model <= 0 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || n_layers <= 0 || n_layers > 64 || Bm <= 0 || S <= 0 || Tq <= 0)
+  if (d_model <= 0 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || n_layers <= 0 || n_layers > kMaxLayers || Bm <= 0 || S <= 0 || Tq <= 0)
     return 0;
   const Sizes s = sizes_of(make_geo(d_model, n_heads, d_ff, vocab, n_layers, Bm, S, Tq));
   return s.tape + s.scratch + 512;

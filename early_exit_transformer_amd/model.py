@@ -24,7 +24,8 @@ from .conformer import Conformer
 from .ctc import ctc_align, ctc_beam_decode, encoder_lengths, exit_ctc_losses, greedy_ctc  # noqa: F401
 from .lexicon import Lexicon, apply_lex, load_dict  # noqa: F401
 from .decoding import DecoderStepSession, _BatchSession, _DecoderTrainFn, _ExitSessions, beam_select  # noqa: F401
-from .training import _ExitHeadsFn, _named_tensors, _train_group, _train_head, _TrainStemFn, forward_train  # noqa: F401
+from .training import (_ExitHeadsFn, _named_tensors, _train_group, _train_head, _TrainStemFn, forward_train,  # noqa: F401
+                       splitformer_sites, zipformer_sites)
 
 
 class PositionalEncoding(nn.Module):
@@ -356,12 +357,13 @@ class Splitformer(Early_conformer):
             if not src.is_cuda:
                 raise RuntimeError("the MI355X training step runs on a HIP device only (there is no CPU fallback)")
             seed = new_seed()
+            sites = splitformer_sites(E, self._cfg.layers_per_exit)
             conv = self.conv_subsample.sequential
-            x = _TrainStemFn.apply(self, src.contiguous().float(), self.positional_encoder.pe, seed, 1, conv[0].weight, conv[0].bias,
-                                   conv[1].weight, conv[1].bias)
+            x = _TrainStemFn.apply(self, src.contiguous().float(), self.positional_encoder.pe, seed, sites["stem"], conv[0].weight,
+                                   conv[0].bias, conv[1].weight, conv[1].bias)
 
-            def group(which, i, t, key_len):  # dropout sites: 16 + 128 * exit index, + 64 for that exit's branch
-                site = 16 + 128 * i if which == "conformer" else 16 + 128 * i * (E - 1) + 64
+            def group(which, i, t, key_len):
+                site = sites["groups" if which == "conformer" else "branches"][i]
                 return _train_group(self, getattr(self, which)[i], t, key_len, seed, site)
             return torch.stack(self._walk(x, lengths, group, lambda i, t: _train_head(self, self.linears[i], t), in_place=False))
         # stem (+ PE) through the monolithic entry's first sub-step; also validates src and packs the main handle
@@ -453,9 +455,10 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
             # train.py:180-208 (--model_type zipformer) in train mode: one-convolution stem, the 19 Conformer groups at five frame
             # rates and the head on the HIP training kernels behind autograd functions
             seed = new_seed()
+            sites = zipformer_sites(len(self.conformer), self._cfg.layers_per_exit)
             conv = self.conv_subsample.conv
-            enc = _TrainStemFn.apply(self, src, self.positional_encoder.pe, seed, 1, conv.weight, conv.bias, None, None)
-            return self._walk(enc, lengths, lambda g, x, key_len: _train_group(self, self.conformer[g], x, key_len, seed, 16 + 128 * g),
+            enc = _TrainStemFn.apply(self, src, self.positional_encoder.pe, seed, sites["stem"], conv.weight, conv.bias, None, None)
+            return self._walk(enc, lengths, lambda g, x, key_len: _train_group(self, self.conformer[g], x, key_len, seed, sites["groups"][g]),
                               lambda rows: _train_head(self, self.linear, rows).unsqueeze(0))
         with torch.cuda.device(dev):
             self._ensure_packed(dev)

@@ -81,6 +81,33 @@ def _update_running_stats(groups, bn: Tensor, n: int) -> None:
             torch._foreach_add_([b_.num_batches_tracked for _, b_ in mods], 1)
 
 
+# ---- dropout site numbers of one training step (include/eec.h: 7 per Conformer layer, calls of one step use disjoint ranges) ----
+SITES_PER_LAYER = 7  # ffn1 activation, ffn1 residual, attention probabilities, attention residual, conv residual, ffn2 activation, ffn2 residual
+STEM_SITE = 1        # the positional encoding's dropout (eec_train_forward numbers its own sites: 1, then 7 per layer from 2 on)
+_GROUP_STRIDE, _BRANCH_OFFSET, _FIRST_GROUP_SITE = 128, 64, 16
+
+
+def _group_sites(bases: Sequence[int], n_layers: Sequence[int], room: int) -> List[int]:
+    for b, n in zip(bases, n_layers):
+        if SITES_PER_LAYER * n > room:
+            raise ValueError(f"{n} layers per Conformer group need {SITES_PER_LAYER * n} dropout sites; the numbering leaves {room} per group")
+    return list(bases)
+
+
+def splitformer_sites(n_exits: int, n_layers: int) -> dict:
+    """site_base of every eec_train_group_forward call of a Splitformer step: exit group e, and the one-layer branch beside the
+    first and the last group half a stride further."""
+    groups = _group_sites([_FIRST_GROUP_SITE + _GROUP_STRIDE * e for e in range(n_exits)], [n_layers] * n_exits, _BRANCH_OFFSET)
+    branches = _group_sites([groups[0] + _BRANCH_OFFSET, groups[-1] + _BRANCH_OFFSET], [1, 1], _GROUP_STRIDE - _BRANCH_OFFSET)
+    return {"stem": STEM_SITE, "groups": groups, "branches": branches}
+
+
+def zipformer_sites(n_groups: int, n_layers: int) -> dict:
+    """site_base of every Conformer group of an Early_zipformer step."""
+    return {"stem": STEM_SITE, "branches": [],
+            "groups": _group_sites([_FIRST_GROUP_SITE + _GROUP_STRIDE * g for g in range(n_groups)], [n_layers] * n_groups, _GROUP_STRIDE)}
+
+
 # ---- building blocks of the training step (Splitformer / Early_zipformer: train.py:180-208) ----------------------------------
 def _group_layer_tensors(group: nn.Module) -> List[Tensor]:
     """The parameters of a Conformer group, layer-major, in _GROUP_FIELDS order."""

@@ -353,8 +353,16 @@ int eec_frontend_forward(eec_frontend* fe, const float* wave, const int64_t* len
  * padded ones included) -- `bn_batch_stats` [E*L][2][D] returns (mean, biased variance) per layer so the caller can update
  * running_mean / running_var (momentum 0.1, unbiased variance) --, dropout with probability `drop_prob` at the reference's
  * sites (after the positional encoding, inside and after each feed-forward module, on the attention probabilities, after
- * out_proj, after the convolution module) from a counter-based generator keyed by `seed` (its streams cannot match
- * torch's: parity with the reference is at drop_prob 0).
+ * out_proj, after the convolution module) from a counter-based generator keyed by `seed` and a site number.
+ * Dropout contract (csrc/eec_drop.h; restated in oracle/dropout_ref.py): element i of the tensor a site masks is kept when
+ * lowbias32(lo(i) * C1 + hi(i) * C2 + key(seed, site)) >= floor(drop_prob * 2^32) and then scaled by 1 / (1 - drop_prob); i is the
+ * flat row-major index of [B][T'][D] (positional encoding, the residual sites), [B][T'][F] (feed-forward activations) and
+ * [B*H][T'][T'] (attention probabilities), whichever kernel applies the mask.  Site numbers of eec_train_forward: 1 = positional
+ * encoding; then 7 per ConformerLayer in the order they run (layer l of exit e: from 2 + 7 * (e * L + l)) -- ffn1 activation, ffn1
+ * residual (the module's output), attention probabilities, attention residual (after out_proj), convolution residual (the
+ * module's output), ffn2 activation, ffn2 residual.  torch's own dropout streams cannot match these, but an oracle handed the
+ * masks of this generator can: parity with the reference's arithmetic holds at drop_prob 0 and, fed the same masks, at
+ * drop_prob > 0, at the same bounds (tests/test_gpu_dropout.py).
  * eec_train_forward records the activations the backward needs in `workspace` (eec_trainer_workspace_bytes; the caller
  * keeps it untouched until eec_train_backward); one recorded forward per trainer at a time.
  * eec_train_backward: `out` = the log-probs eec_train_forward returned, `grad_out` = dLoss/d out [E,B,T',V]; `grads` is
@@ -392,7 +400,9 @@ int eec_train_backward_ex(eec_trainer* tr, const eec_params* params, const eec_p
  * geometry, seed, drop_prob and site numbers).  A GROUP = n_layers ConformerLayers (torchaudio Conformer(num_layers=n_layers))
  * on rows x [B][T'][D] with key lengths key_len [B] (int32, device): x_out [B][T'][D], bn_batch_stats [n_layers][2][D] as in
  * eec_train_forward; the backward writes the gradient of every layer parameter (grads mirrors layers) and grad_in = dLoss/dx_in.
- * site_base numbers the group's dropout sites (7 per layer): calls of one step must use disjoint ranges.  The STEM =
+ * site_base numbers the group's dropout sites: layer l of the group uses site_base + 7 * l ... + 6 in the order given at
+ * eec_train_forward, the stem the one number `site`; calls of one step must use disjoint ranges (the models' numbering:
+ * training.splitformer_sites / zipformer_sites -- stem 1, group g from 16 + 128 * g, a Splitformer branch 64 further).  The STEM =
  * Conv1d(k3, s2) [-> Conv1d(k3, s2) when sub1_* are given] -> + positional encoding -> dropout: x_out [B][To][D], To = T1 or T';
  * no gradient with respect to mel.  The HEAD = log_softmax(x . W^T + b) and the backward of exactly that. */
 size_t eec_train_group_workspace_bytes(const eec_config* cfg, int n_layers, int B, int Tq);
@@ -462,7 +472,11 @@ int eec_decoder_forward(const eec_decoder_params* p, int d_model, int n_heads, i
  * `p` with pointers that are WRITTEN with the gradient of the parameter in the same position (emb [V][D]; pe ignored; layers a
  * host array); grad_enc [Bm][Tq][D] is written with the gradient of the memory (what flows on into the encoder's backward as
  * eec_train_backward's grad_taps).  The shared final LayerNorm and the embedding receive one such gradient per exit: the caller
- * sums them (autograd does).  Parity with the reference's modules is at drop_prob 0 (its dropout streams cannot match). */
+ * sums them (autograd does).  Dropout sites (generator and index convention as at eec_train_forward): 0 = positional encoding
+ * over [Bm*S][D], the same for every exit; layer l of exit e uses 1 + 1024 * e + 6 * l + place, place = 0 self-attention
+ * probabilities [Bm*H][S][S], 1 residual 1, 2 cross-attention probabilities [Bm*H][S][Tq], 3 residual 2, 4 feed-forward activation
+ * [Bm*S][F], 5 residual 3 ([Bm*S][D]).  Parity with the reference's modules holds at drop_prob 0 and, with the modules fed these
+ * masks, at drop_prob > 0 (tests/test_gpu_dropout.py). */
 const char* eec_decoder_train_last_error(void);
 size_t eec_decoder_train_workspace_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int Bm, int S, int Tq);
 int eec_decoder_train_forward(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, int pad_idx, const int64_t* trg,
