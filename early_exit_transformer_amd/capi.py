@@ -246,10 +246,10 @@ def load() -> C.CDLL:
     return lib
 
 
-def check(rc: int, what: str, err: str = "eec_last_error") -> None:
-    """Raise on a non-zero return code with the message of the entry's family (``err``: its ``eec_*_last_error()`` symbol)."""
+def check(rc: int, what: str) -> None:
+    """Raise on a non-zero return code with the library's message (one per thread, whichever family the entry belongs to)."""
     if rc != 0:
-        raise RuntimeError(f"{what} failed (code {rc}): {getattr(load(), err)().decode(errors='replace')}")
+        raise RuntimeError(f"{what} failed (code {rc}): {load().eec_last_error().decode(errors='replace')}")
 
 
 def stream_ptr(dev) -> C.c_void_p:

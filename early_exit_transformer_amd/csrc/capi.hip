@@ -10,27 +10,13 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "eec_host.h"
 #include "eec_kernels.h"
 
 using namespace eec;
+using namespace eech;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-int hip_fail(hipError_t e, const char* what) {
-  g_err = std::string(what) + ": " + hipGetErrorString(e);
-  return (int)e;
-}
-#define EEC_HIP(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #expr);  \
-  } while (0)
 
 struct PackedLayer {
   // device pointers into the encoder's arena
@@ -45,22 +31,74 @@ struct PackedLayer {
   float *final_ln_w, *final_ln_b;
 };
 
-size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-struct Arena {  // bump allocator over one hipMalloc
-  char* base = nullptr;
-  size_t cap = 0, off = 0;
-  template <typename T>
-  T* take(size_t count) {
-    off = align_up(off);
-    T* p = (T*)(base ? base + off : nullptr);
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
 size_t frag_u4(int N, int K) { return (size_t)((N + 31) / 32) * (K / 16) * 128; }
 size_t f8_u4(int N, int K) { return (size_t)((N + 31) / 32) * ((K + 63) / 64) * kF8Rec; }
+
+// The packed tensors of one layer, in arena order: where each comes from in eec_layer_params, where it goes in PackedLayer,
+// its extent as a function of (D, F), what packing makes it and with which scale.  eec_encoder::carve() sizes the arena
+// from this table and eec_encoder_pack fills it from the same rows.
+// Kinds: fp32 copy; fp32 copy times scale; MFMA fragment image of a [rows][cols] weight (fp16 hi / lo pairs); its f8 image; the
+// same for a feed-forward weight (made only when F % 128 == 0); made by the depthwise / BatchNorm fold from several sources.
+enum PackKind { PK_COPY, PK_SCALE, PK_FRAG, PK_F8, PK_F8_FFN, PK_FOLD };
+struct Ext {  // d * D + f * F + c
+  int d, f, c;
+  int of(int D, int F) const { return d * D + f * F + c; }
+};
+constexpr Ext kD{1, 0, 0}, k2D{2, 0, 0}, k3D{3, 0, 0}, kF{0, 1, 0}, kOne{0, 0, 1}, kTaps{0, 0, 31};
+struct LayerTensor {
+  const float* eec_layer_params::*src;
+  float* PackedLayer::*f32;  // destination of the fp32 kinds, else nullptr
+  uint4* PackedLayer::*img;  // destination of the image kinds, else nullptr
+  Ext rows, cols;
+  PackKind kind;
+  float scale;
+  size_t count(int D, int F) const {  // elements of the destination's type
+    const int N = rows.of(D, F), K = cols.of(D, F);
+    return f32 ? (size_t)N * K : kind == PK_FRAG ? frag_u4(N, K) : f8_u4(N, K);
+  }
+};
+using LP = eec_layer_params;
+using PL = PackedLayer;
+constexpr LayerTensor vec(const float* LP::*src, float* PL::*dst, Ext n, PackKind kind = PK_COPY, float scale = 1.0f) { return {src, dst, nullptr, n, kOne, kind, scale}; }
+constexpr LayerTensor img(const float* LP::*src, uint4* PL::*dst, Ext rows, Ext cols, PackKind kind, float scale = 1.0f) { return {src, nullptr, dst, rows, cols, kind, scale}; }
+const LayerTensor kLayerTensors[] = {  // the feed-forward modules are stored with W1 and b1 times log2(e) and W2 divided by it
+    vec(&LP::ffn1_ln_w, &PL::ffn1_ln_w, kD),
+    vec(&LP::ffn1_ln_b, &PL::ffn1_ln_b, kD),
+    vec(&LP::ffn1_b1, &PL::ffn1_b1, kF, PK_SCALE, kLog2e),
+    vec(&LP::ffn1_b2, &PL::ffn1_b2, kD),
+    img(&LP::ffn1_w1, &PL::ffn1_w1p, kF, kD, PK_FRAG, kLog2e),
+    img(&LP::ffn1_w2, &PL::ffn1_w2p, kD, kF, PK_FRAG, 1.0f / kLog2e),
+    img(&LP::ffn1_w1, &PL::ffn1_w1f8, kF, kD, PK_F8_FFN, kLog2e),
+    img(&LP::ffn1_w2, &PL::ffn1_w2f8, kD, kF, PK_F8_FFN, 1.0f / kLog2e),
+    vec(&LP::attn_ln_w, &PL::attn_ln_w, kD),
+    vec(&LP::attn_ln_b, &PL::attn_ln_b, kD),
+    vec(&LP::attn_in_b, &PL::attn_in_b, k3D),
+    vec(&LP::attn_out_b, &PL::attn_out_b, kD),
+    img(&LP::attn_in_w, &PL::attn_in_p, k3D, kD, PK_FRAG),
+    img(&LP::attn_out_w, &PL::attn_out_p, kD, kD, PK_FRAG),
+    img(&LP::attn_in_w, &PL::attn_in_f8, k3D, kD, PK_F8),
+    img(&LP::attn_out_w, &PL::attn_out_f8, kD, kD, PK_F8),
+    vec(&LP::conv_ln_w, &PL::conv_ln_w, kD),
+    vec(&LP::conv_ln_b, &PL::conv_ln_b, kD),
+    vec(&LP::conv_pw1_b, &PL::conv_pw1_b, k2D),
+    vec(&LP::conv_pw2_b, &PL::conv_pw2_b, kD),
+    LayerTensor{&LP::conv_dw_w, &PL::dw_wfold, nullptr, kTaps, kD, PK_FOLD, 1.0f},
+    vec(&LP::conv_dw_b, &PL::dw_bfold, kD, PK_FOLD),
+    img(&LP::conv_pw1_w, &PL::conv_pw1_p, k2D, kD, PK_FRAG),
+    img(&LP::conv_pw2_w, &PL::conv_pw2_p, kD, kD, PK_FRAG),
+    img(&LP::conv_pw1_w, &PL::conv_pw1_f8, k2D, kD, PK_F8),
+    img(&LP::conv_pw2_w, &PL::conv_pw2_f8, kD, kD, PK_F8),
+    vec(&LP::ffn2_ln_w, &PL::ffn2_ln_w, kD),
+    vec(&LP::ffn2_ln_b, &PL::ffn2_ln_b, kD),
+    vec(&LP::ffn2_b1, &PL::ffn2_b1, kF, PK_SCALE, kLog2e),
+    vec(&LP::ffn2_b2, &PL::ffn2_b2, kD),
+    img(&LP::ffn2_w1, &PL::ffn2_w1p, kF, kD, PK_FRAG, kLog2e),
+    img(&LP::ffn2_w2, &PL::ffn2_w2p, kD, kF, PK_FRAG, 1.0f / kLog2e),
+    img(&LP::ffn2_w1, &PL::ffn2_w1f8, kF, kD, PK_F8_FFN, kLog2e),
+    img(&LP::ffn2_w2, &PL::ffn2_w2f8, kD, kF, PK_F8_FFN, 1.0f / kLog2e),
+    vec(&LP::final_ln_w, &PL::final_ln_w, kD),
+    vec(&LP::final_ln_b, &PL::final_ln_b, kD),
+};
 
 }  // namespace
 
@@ -69,7 +107,7 @@ enum KernelClass { KC_STEM = 0, KC_FFN, KC_QKV, KC_ATTN, KC_PROJ_GLU, KC_PROJ, K
 struct eec_encoder {
   eec_config cfg;
   int device = -1;  // the HIP device the packed-weight arena lives on: every entry point must run with it current
-  Arena arena;
+  Bump arena;
   bool packed = false;
   bool has_stem = false, has_stem1 = false, has_heads = false;  // eec_encoder_pack may be given layers only (building-block use)
   // optional per-kernel-class timing with HIP events on the launch stream (bench/roofline only)
@@ -88,44 +126,11 @@ struct eec_encoder {
   void carve() {
     const int D = cfg.d_model, F = cfg.d_ff, nl = cfg.n_exits * cfg.layers_per_exit;
     layers.assign(nl, PackedLayer());
-    for (auto& L : layers) {
-      L.ffn1_ln_w = arena.take<float>(D);
-      L.ffn1_ln_b = arena.take<float>(D);
-      L.ffn1_b1 = arena.take<float>(F);
-      L.ffn1_b2 = arena.take<float>(D);
-      L.ffn1_w1p = arena.take<uint4>(frag_u4(F, D));
-      L.ffn1_w2p = arena.take<uint4>(frag_u4(D, F));
-      L.ffn1_w1f8 = arena.take<uint4>(f8_u4(F, D));
-      L.ffn1_w2f8 = arena.take<uint4>(f8_u4(D, F));
-      L.attn_ln_w = arena.take<float>(D);
-      L.attn_ln_b = arena.take<float>(D);
-      L.attn_in_b = arena.take<float>(3 * D);
-      L.attn_out_b = arena.take<float>(D);
-      L.attn_in_p = arena.take<uint4>(frag_u4(3 * D, D));
-      L.attn_out_p = arena.take<uint4>(frag_u4(D, D));
-      L.attn_in_f8 = arena.take<uint4>(f8_u4(3 * D, D));
-      L.attn_out_f8 = arena.take<uint4>(f8_u4(D, D));
-      L.conv_ln_w = arena.take<float>(D);
-      L.conv_ln_b = arena.take<float>(D);
-      L.conv_pw1_b = arena.take<float>(2 * D);
-      L.conv_pw2_b = arena.take<float>(D);
-      L.dw_wfold = arena.take<float>(31 * D);
-      L.dw_bfold = arena.take<float>(D);
-      L.conv_pw1_p = arena.take<uint4>(frag_u4(2 * D, D));
-      L.conv_pw2_p = arena.take<uint4>(frag_u4(D, D));
-      L.conv_pw1_f8 = arena.take<uint4>(f8_u4(2 * D, D));
-      L.conv_pw2_f8 = arena.take<uint4>(f8_u4(D, D));
-      L.ffn2_ln_w = arena.take<float>(D);
-      L.ffn2_ln_b = arena.take<float>(D);
-      L.ffn2_b1 = arena.take<float>(F);
-      L.ffn2_b2 = arena.take<float>(D);
-      L.ffn2_w1p = arena.take<uint4>(frag_u4(F, D));
-      L.ffn2_w2p = arena.take<uint4>(frag_u4(D, F));
-      L.ffn2_w1f8 = arena.take<uint4>(f8_u4(F, D));
-      L.ffn2_w2f8 = arena.take<uint4>(f8_u4(D, F));
-      L.final_ln_w = arena.take<float>(D);
-      L.final_ln_b = arena.take<float>(D);
-    }
+    for (auto& L : layers)
+      for (const LayerTensor& t : kLayerTensors) {
+        if (t.f32) L.*t.f32 = arena.take<float>(t.count(D, F));
+        else L.*t.img = arena.take<uint4>(t.count(D, F));
+      }
     sub_w1p = arena.take<uint4>(frag_u4(D, cfg.n_mels * 3));
     sub_b1 = arena.take<float>(D);
     sub_w2p = arena.take<uint4>(frag_u4(D, 3 * D));
@@ -139,39 +144,59 @@ struct eec_encoder {
       head_f8[e] = arena.take<uint4>(f8_u4(cfg.vocab, D));
       head_b[e] = arena.take<float>(cfg.vocab);
     }
-    arena.off = align_up(arena.off);
+    arena.off = up256(arena.off);
   }
 };
 
 namespace {
 
-struct Workspace {
-  float* x;
-  float* y;  // [(E-1)][M][256]: exit rows for the batched head launch when the caller passes no tap buffer
-  half_t *mid_hi, *mid_lo, *q, *k, *vt, *p_hi, *p_lo, *g;
-  int *enc_len, *mid_e;
+// the six planes a run of layers works in (eec_encoder_group_forward's whole workspace)
+struct GroupWs {
+  half_t *q, *k, *vt, *p_hi, *p_lo, *g;
   size_t bytes;
 };
-
-Workspace carve_ws(const eec_config& c, int B, int T, char* base) {
-  const int T1 = (T - 3) / 2 + 1, Tq = (T1 - 3) / 2 + 1, Tp = (Tq + 31) / 32 * 32;
+void carve_group_planes(Bump& a, GroupWs& w, const eec_config& c, int B, int Tq) {
+  const int Tp = (Tq + 31) / 32 * 32;
   const size_t M = (size_t)B * Tq, D = c.d_model;
-  Arena a;
-  a.base = base;
-  Workspace w;
-  w.x = a.take<float>(M * D);
-  w.y = a.take<float>((size_t)(c.n_exits > 1 ? c.n_exits - 1 : 0) * M * D);
-  w.mid_hi = a.take<half_t>((size_t)B * T1 * D);
-  w.mid_lo = a.take<half_t>((size_t)B * T1 * D);
   w.q = a.take<half_t>((size_t)2 * B * Tp * D);   // hi plane, then the residual plane (exact mode f16x3 only)
   w.k = a.take<half_t>((size_t)2 * B * Tp * D);
   w.vt = a.take<half_t>((size_t)2 * B * Tp * D);  // hi plane, then the residual plane
   w.p_hi = a.take<half_t>(M * D);
   w.p_lo = a.take<half_t>(M * D);
   w.g = a.take<half_t>(M * D);
+}
+GroupWs carve_group_ws(const eec_config& c, int B, int Tq, char* base) {
+  Bump a;
+  a.base = base;
+  GroupWs w;
+  carve_group_planes(a, w, c, B, Tq);
+  w.bytes = up256(a.off);
+  return w;
+}
+
+struct Workspace {
+  float* x;
+  float* y;  // [(E-1)][M][256]: exit rows for the batched head launch when the caller passes no tap buffer
+  half_t *mid_hi, *mid_lo;
+  GroupWs gw;
+  int *enc_len, *mid_e;
+  size_t bytes;
+};
+
+Workspace carve_ws(const eec_config& c, int B, int T, char* base) {
+  const int T1 = (T - 3) / 2 + 1, Tq = (T1 - 3) / 2 + 1;
+  const size_t M = (size_t)B * Tq, D = c.d_model;
+  Bump a;
+  a.base = base;
+  Workspace w;
+  w.x = a.take<float>(M * D);
+  w.y = a.take<float>((size_t)(c.n_exits > 1 ? c.n_exits - 1 : 0) * M * D);
+  w.mid_hi = a.take<half_t>((size_t)B * T1 * D);
+  w.mid_lo = a.take<half_t>((size_t)B * T1 * D);
+  carve_group_planes(a, w.gw, c, B, Tq);
   w.enc_len = a.take<int>(B);
   w.mid_e = a.take<int>((size_t)B * T1);
-  w.bytes = align_up(a.off);
+  w.bytes = up256(a.off);
   return w;
 }
 
@@ -231,6 +256,39 @@ struct LayerBufs {
 struct LayerFormats {
   int ffn, front, qkv, att, glu;  // operand formats of the GEMM groups (1, 3 or 8)
 };
+// What a precision means for the launch plans: the operand format of every GEMM group and which residual planes exist.
+struct Formats {
+  LayerFormats layer;  // the production plan's groups
+  int o, p, head;      // fragment formats (1 or 3) of the legacy plan and the attention; the projections' format; the exit heads'
+  bool v_res, qk_res;  // V keeps its fp16 residual plane; Q and K keep theirs (exact mode)
+};
+static Formats formats_of(const eec_config& c, int precision) {
+  const int np_ffn = precision == EEC_PREC_F16X3 ? 3 : (precision == EEC_PREC_F16F8 ? 8 : 1);
+  const int np_o = precision == EEC_PREC_F16 ? 1 : 3;
+  // f16f8 (default): besides the feed-forward, out_proj + pointwise-1, pointwise-2 and (round 3) in_proj run on the f8
+  // stream (fp16 + two fp8 correction products); the exit heads (their error is the logit error) keep the exact 3-pass
+  // split.  Measured on the default model, 3 weight / input seeds (profiles/r02_np_budget.txt): max |dlogp| 3.6e-4 (2.5e-4
+  // with in_proj on the 3-pass split: its error is amplified by the softmax, but the chain kernel's in_proj tail is
+  // MFMA-bound at three passes: -8 us of 169 per launch, profiles/r03_ab_chain_knobs.txt), heads too 4.0e-4
+  // (d_model 512 keeps the fragment formats there: its f8 projection kernels do not fit the register file yet)
+  const bool conformer = c.arch == EEC_ARCH_CONFORMER;
+  const int np_p = (precision == EEC_PREC_F16F8 && conformer && c.d_model == 256 && c.d_ff % 128 == 0) ? 8 : np_o;
+  Formats f;
+  f.layer = LayerFormats{np_ffn, np_p, np_p, np_o, np_p};
+  f.o = np_o, f.p = np_p, f.head = np_o;
+  f.v_res = np_o == 3;  // V keeps its fp16 residual in the split modes
+  // exact parity mode (f16x3): Q, K and the attention probabilities keep their fp16 residuals as well (three MFMA products per
+  // attention product, attention as its own launch): what remains of the log-prob error is the GLU output's fp16 rounding
+  f.qk_res = precision == EEC_PREC_F16X3 && conformer;
+  return f;
+}
+// the buffers of a run of layers on rows x: the residual planes are the second halves of the q / k / vt planes
+static LayerBufs layer_bufs(float* x, const GroupWs& w, const int* key_len, const Formats& f, int B, int Tq, int D) {
+  const size_t plane = (size_t)B * ((Tq + 31) / 32 * 32) * D;
+  LayerBufs b{x, w.q, w.k, w.vt, f.v_res ? w.vt + plane : nullptr, w.p_hi, w.p_lo, w.g, key_len};
+  if (f.qk_res) b.q_lo = w.q + plane, b.k_lo = w.k + plane;
+  return b;
+}
 template <typename TapFn>
 static int run_layer_plan(eec_encoder* enc, int l0, int l1, const LayerBufs& b, int B, int Tq, const LayerFormats& np,
                           TapFn tap_of, hipStream_t st) {
@@ -331,7 +389,7 @@ int eec_encoder_create(const eec_config* cfg, eec_encoder** out) {
     delete enc;
     return hip_fail(e, "hipMalloc(packed weights)");
   }
-  enc->arena = Arena();
+  enc->arena = Bump();
   enc->arena.base = (char*)mem;
   enc->arena.cap = need;
   enc->carve();
@@ -344,6 +402,38 @@ void eec_encoder_destroy(eec_encoder* enc) {
   for (hipEvent_t e : enc->ev) (void)hipEventDestroy(e);
   if (enc->arena.base) (void)hipFree(enc->arena.base);
   delete enc;
+}
+
+// The stem and the exit heads, for both pack entries; marks the encoder packed.  A stem may be given whole (two
+// convolutions), as its first convolution only (enough for eec_encoder_stem1_forward) or not at all; the heads likewise.
+static int pack_stem_and_heads(eec_encoder* enc, const float* sub0_w, const float* sub0_b, const float* sub1_w, const float* sub1_b,
+                               const float* pe, const float* const* head_w, const float* const* head_b, hipStream_t st) {
+  const eec_config& c = enc->cfg;
+  const int D = c.d_model;
+  auto cp = [&](float* dst, const float* src, size_t n) {
+    return hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
+  };
+  enc->has_stem1 = sub0_w && sub0_b && pe;
+  enc->has_stem = enc->has_stem1 && sub1_w && sub1_b;
+  if (enc->has_stem1) {
+    EEC_HIP(launch_pack_frags(sub0_w, D, c.n_mels * 3, enc->sub_w1p, 1.0f, st));
+    EEC_HIP(cp(enc->sub_b1, sub0_b, D));
+  }
+  if (enc->has_stem) {
+    EEC_HIP(launch_pack_conv_jci(sub1_w, D, D, enc->sub_w2p, st));
+    EEC_HIP(cp(enc->sub_b2, sub1_b, D));
+  }
+  if (enc->has_stem1) EEC_HIP(cp(enc->pe, pe, (size_t)c.max_len * D));
+  enc->has_heads = head_w != nullptr;
+  if (enc->has_heads)
+    for (int e = 0; e < c.n_exits; ++e) {
+      if (!head_w[e] || !head_b[e]) return fail(EEC_ERR_BAD_ARG, "null head parameter");
+      EEC_HIP(launch_pack_frags(head_w[e], c.vocab, D, enc->head_p[e], 1.0f, st));
+      EEC_HIP(launch_pack_frags_f8(head_w[e], c.vocab, D, enc->head_f8[e], 1.0f, st));
+      EEC_HIP(cp(enc->head_b[e], head_b[e], c.vocab));
+    }
+  enc->packed = true;
+  return 0;
 }
 
 int eec_encoder_pack(eec_encoder* enc, const eec_params* p, void* stream) {
@@ -360,71 +450,17 @@ int eec_encoder_pack(eec_encoder* enc, const eec_params* p, void* stream) {
   for (size_t i = 0; i < enc->layers.size(); ++i) {
     const eec_layer_params& s = p->layers[i];
     PackedLayer& L = enc->layers[i];
-    EEC_HIP(cp(L.ffn1_ln_w, s.ffn1_ln_w, D));
-    EEC_HIP(cp(L.ffn1_ln_b, s.ffn1_ln_b, D));
-    EEC_HIP(launch_scale_copy(s.ffn1_b1, L.ffn1_b1, F, kLog2e, st));
-    EEC_HIP(cp(L.ffn1_b2, s.ffn1_b2, D));
-    EEC_HIP(launch_pack_frags(s.ffn1_w1, F, D, L.ffn1_w1p, kLog2e, st));
-    EEC_HIP(launch_pack_frags(s.ffn1_w2, D, F, L.ffn1_w2p, 1.0f / kLog2e, st));
-    if (F % 128 == 0) {
-      EEC_HIP(launch_pack_frags_f8(s.ffn1_w1, F, D, L.ffn1_w1f8, kLog2e, st));
-      EEC_HIP(launch_pack_frags_f8(s.ffn1_w2, D, F, L.ffn1_w2f8, 1.0f / kLog2e, st));
+    for (const LayerTensor& t : kLayerTensors) {
+      const int N = t.rows.of(D, F), K = t.cols.of(D, F);
+      if (t.kind == PK_COPY) EEC_HIP(cp(L.*t.f32, s.*t.src, t.count(D, F)));
+      if (t.kind == PK_SCALE) EEC_HIP(launch_scale_copy(s.*t.src, L.*t.f32, N * K, t.scale, st));
+      if (t.kind == PK_FRAG) EEC_HIP(launch_pack_frags(s.*t.src, N, K, L.*t.img, t.scale, st));
+      if (t.kind == PK_F8 || (t.kind == PK_F8_FFN && F % 128 == 0)) EEC_HIP(launch_pack_frags_f8(s.*t.src, N, K, L.*t.img, t.scale, st));
     }
-    EEC_HIP(cp(L.attn_ln_w, s.attn_ln_w, D));
-    EEC_HIP(cp(L.attn_ln_b, s.attn_ln_b, D));
-    EEC_HIP(cp(L.attn_in_b, s.attn_in_b, 3 * D));
-    EEC_HIP(cp(L.attn_out_b, s.attn_out_b, D));
-    EEC_HIP(launch_pack_frags(s.attn_in_w, 3 * D, D, L.attn_in_p, 1.0f, st));
-    EEC_HIP(launch_pack_frags(s.attn_out_w, D, D, L.attn_out_p, 1.0f, st));
-    EEC_HIP(launch_pack_frags_f8(s.attn_in_w, 3 * D, D, L.attn_in_f8, 1.0f, st));
-    EEC_HIP(launch_pack_frags_f8(s.attn_out_w, D, D, L.attn_out_f8, 1.0f, st));
-    EEC_HIP(cp(L.conv_ln_w, s.conv_ln_w, D));
-    EEC_HIP(cp(L.conv_ln_b, s.conv_ln_b, D));
-    EEC_HIP(cp(L.conv_pw1_b, s.conv_pw1_b, 2 * D));
-    EEC_HIP(cp(L.conv_pw2_b, s.conv_pw2_b, D));
-    EEC_HIP(launch_pack_frags(s.conv_pw1_w, 2 * D, D, L.conv_pw1_p, 1.0f, st));
-    EEC_HIP(launch_pack_frags(s.conv_pw2_w, D, D, L.conv_pw2_p, 1.0f, st));
-    EEC_HIP(launch_pack_frags_f8(s.conv_pw1_w, 2 * D, D, L.conv_pw1_f8, 1.0f, st));
-    EEC_HIP(launch_pack_frags_f8(s.conv_pw2_w, D, D, L.conv_pw2_f8, 1.0f, st));
     EEC_HIP(launch_fold_dw(s.conv_dw_w, s.conv_dw_b, s.conv_bn_w, s.conv_bn_b, s.conv_bn_rm, s.conv_bn_rv,
                            c.dw_kernel, D, L.dw_wfold, L.dw_bfold, st));
-    EEC_HIP(cp(L.ffn2_ln_w, s.ffn2_ln_w, D));
-    EEC_HIP(cp(L.ffn2_ln_b, s.ffn2_ln_b, D));
-    EEC_HIP(launch_scale_copy(s.ffn2_b1, L.ffn2_b1, F, kLog2e, st));
-    EEC_HIP(cp(L.ffn2_b2, s.ffn2_b2, D));
-    EEC_HIP(launch_pack_frags(s.ffn2_w1, F, D, L.ffn2_w1p, kLog2e, st));
-    EEC_HIP(launch_pack_frags(s.ffn2_w2, D, F, L.ffn2_w2p, 1.0f / kLog2e, st));
-    if (F % 128 == 0) {
-      EEC_HIP(launch_pack_frags_f8(s.ffn2_w1, F, D, L.ffn2_w1f8, kLog2e, st));
-      EEC_HIP(launch_pack_frags_f8(s.ffn2_w2, D, F, L.ffn2_w2f8, 1.0f / kLog2e, st));
-    }
-    EEC_HIP(cp(L.final_ln_w, s.final_ln_w, D));
-    EEC_HIP(cp(L.final_ln_b, s.final_ln_b, D));
   }
-  enc->has_stem = p->sub0_w && p->sub0_b && p->sub1_w && p->sub1_b && p->pe;
-  enc->has_stem1 = p->sub0_w && p->sub0_b && p->pe;  // enough for the one-convolution stem (eec_encoder_stem1_forward)
-  if (enc->has_stem1 && !enc->has_stem) {
-    EEC_HIP(launch_pack_frags(p->sub0_w, D, c.n_mels * 3, enc->sub_w1p, 1.0f, st));
-    EEC_HIP(cp(enc->sub_b1, p->sub0_b, D));
-    EEC_HIP(cp(enc->pe, p->pe, (size_t)c.max_len * D));
-  }
-  if (enc->has_stem) {
-    EEC_HIP(launch_pack_frags(p->sub0_w, D, c.n_mels * 3, enc->sub_w1p, 1.0f, st));
-    EEC_HIP(cp(enc->sub_b1, p->sub0_b, D));
-    EEC_HIP(launch_pack_conv_jci(p->sub1_w, D, D, enc->sub_w2p, st));
-    EEC_HIP(cp(enc->sub_b2, p->sub1_b, D));
-    EEC_HIP(cp(enc->pe, p->pe, (size_t)c.max_len * D));
-  }
-  enc->has_heads = p->head_w != nullptr;
-  if (enc->has_heads)
-    for (int e = 0; e < c.n_exits; ++e) {
-      if (!p->head_w[e] || !p->head_b[e]) return fail(EEC_ERR_BAD_ARG, "null head parameter");
-      EEC_HIP(launch_pack_frags(p->head_w[e], c.vocab, D, enc->head_p[e], 1.0f, st));
-      EEC_HIP(launch_pack_frags_f8(p->head_w[e], c.vocab, D, enc->head_f8[e], 1.0f, st));
-      EEC_HIP(cp(enc->head_b[e], p->head_b[e], c.vocab));
-    }
-  enc->packed = true;
-  return 0;
+  return pack_stem_and_heads(enc, p->sub0_w, p->sub0_b, p->sub1_w, p->sub1_b, p->pe, p->head_w, p->head_b, st);
 }
 
 int eec_encoder_pack_legacy(eec_encoder* enc, const eec_legacy_params* p, void* stream) {
@@ -438,7 +474,7 @@ int eec_encoder_pack_legacy(eec_encoder* enc, const eec_legacy_params* p, void* 
   auto cp = [&](float* dst, const float* src, size_t n) {
     return hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
   };
-  const size_t tile8 = (size_t)(D / 32) * (D / 16) * 128;  // the D/32 n-tiles (D output columns) of one of w_q / w_k / w_v
+  const size_t tile8 = frag_u4(D, D);  // the D/32 n-tiles (D output columns) of one of w_q / w_k / w_v
   for (size_t i = 0; i < enc->layers.size(); ++i) {
     const eec_legacy_layer_params& s = p->layers[i];
     PackedLayer& L = enc->layers[i];
@@ -467,30 +503,7 @@ int eec_encoder_pack_legacy(eec_encoder* enc, const eec_legacy_params* p, void* 
     EEC_HIP(cp(L.final_ln_w, p->group_ln_w[e], D));
     EEC_HIP(cp(L.final_ln_b, p->group_ln_b[e], D));
   }
-  enc->has_stem = p->sub0_w && p->sub0_b && p->sub1_w && p->sub1_b && p->pe;
-  enc->has_stem1 = p->sub0_w && p->sub0_b && p->pe;  // enough for the one-convolution stem (eec_encoder_stem1_forward)
-  if (enc->has_stem1 && !enc->has_stem) {
-    EEC_HIP(launch_pack_frags(p->sub0_w, D, c.n_mels * 3, enc->sub_w1p, 1.0f, st));
-    EEC_HIP(cp(enc->sub_b1, p->sub0_b, D));
-    EEC_HIP(cp(enc->pe, p->pe, (size_t)c.max_len * D));
-  }
-  if (enc->has_stem) {
-    EEC_HIP(launch_pack_frags(p->sub0_w, D, c.n_mels * 3, enc->sub_w1p, 1.0f, st));
-    EEC_HIP(cp(enc->sub_b1, p->sub0_b, D));
-    EEC_HIP(launch_pack_conv_jci(p->sub1_w, D, D, enc->sub_w2p, st));
-    EEC_HIP(cp(enc->sub_b2, p->sub1_b, D));
-    EEC_HIP(cp(enc->pe, p->pe, (size_t)c.max_len * D));
-  }
-  enc->has_heads = p->head_w != nullptr;
-  if (enc->has_heads)
-    for (int e = 0; e < c.n_exits; ++e) {
-      if (!p->head_w[e] || !p->head_b[e]) return fail(EEC_ERR_BAD_ARG, "null head parameter");
-      EEC_HIP(launch_pack_frags(p->head_w[e], c.vocab, D, enc->head_p[e], 1.0f, st));
-      EEC_HIP(launch_pack_frags_f8(p->head_w[e], c.vocab, D, enc->head_f8[e], 1.0f, st));
-      EEC_HIP(cp(enc->head_b[e], p->head_b[e], c.vocab));
-    }
-  enc->packed = true;
-  return 0;
+  return pack_stem_and_heads(enc, p->sub0_w, p->sub0_b, p->sub1_w, p->sub1_b, p->pe, p->head_w, p->head_b, st);
 }
 
 size_t eec_encoder_workspace_bytes(const eec_encoder* enc, int B, int T) {
@@ -510,31 +523,17 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
   if (!enc->packed) return fail(EEC_ERR_NOT_PACKED, "eec_encoder_pack has not been called");
   if (int rc = check_device(enc)) return rc;
   if (B <= 0 || T < 7) return fail(EEC_ERR_BAD_ARG, "need B > 0 and T >= 7 (two k=3 s=2 convs)");
-  if (precision < EEC_PREC_F16X3 || precision > EEC_PREC_F16F8) return fail(EEC_ERR_BAD_ARG, "unknown precision");
+  if (int rc = check_precision(precision)) return rc;
   const eec_config& c = enc->cfg;
   const int T1 = (T - 3) / 2 + 1, Tq = (T1 - 3) / 2 + 1, Tp = (Tq + 31) / 32 * 32;
   if (Tq > c.max_len) return fail(EEC_ERR_BAD_ARG, "T' exceeds the positional-encoding table (max_len)");
-  if (((uintptr_t)workspace & 255) != 0) return fail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  Workspace ws = carve_ws(c, B, T, (char*)workspace);
-  if (workspace_bytes < ws.bytes) return fail(EEC_ERR_WORKSPACE, "workspace too small");
+  const Workspace ws = carve_ws(c, B, T, (char*)workspace);
+  if (int rc = check_workspace(workspace, workspace_bytes, ws.bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int np_ffn = precision == EEC_PREC_F16X3 ? 3 : (precision == EEC_PREC_F16F8 ? 8 : 1);
-  const int np_o = precision == EEC_PREC_F16 ? 1 : 3;
-  // f16f8 (default): besides the feed-forward, out_proj + pointwise-1, pointwise-2 and (round 3) in_proj run on the f8
-  // stream (fp16 + two fp8 correction products); the exit heads (their error is the logit error) keep the exact 3-pass
-  // split.  Measured on the default model, 3 weight / input seeds (profiles/r02_np_budget.txt): max |dlogp| 3.6e-4 (2.5e-4
-  // with in_proj on the 3-pass split: its error is amplified by the softmax, but the chain kernel's in_proj tail is
-  // MFMA-bound at three passes: -8 us of 169 per launch, profiles/r03_ab_chain_knobs.txt), heads too 4.0e-4
-  // (d_model 512 keeps the fragment formats there: its f8 projection kernels do not fit the register file yet)
-  const int np_p = (precision == EEC_PREC_F16F8 && c.arch == EEC_ARCH_CONFORMER && c.d_model == 256 && c.d_ff % 128 == 0) ? 8 : np_o;
-  // operand format per GEMM group of the production plan
-  const int np_qkv = np_p, np_att = np_o, np_glu = np_p, np_front = np_p, np_head = np_o;
-  half_t* const vt_lo = np_o == 3 ? ws.vt + (size_t)B * Tp * c.d_model : nullptr;  // V keeps its fp16 residual in the split modes
-  // exact parity mode (f16x3): Q, K and the attention probabilities keep their fp16 residuals as well (three MFMA products per
-  // attention product, attention as its own launch): what remains of the log-prob error is the GLU output's fp16 rounding
-  const bool exact_attn = precision == EEC_PREC_F16X3 && c.arch == EEC_ARCH_CONFORMER;
-  half_t* const q_lo = exact_attn ? ws.q + (size_t)B * Tp * c.d_model : nullptr;
-  half_t* const k_lo = exact_attn ? ws.k + (size_t)B * Tp * c.d_model : nullptr;
+  const Formats fm = formats_of(c, precision);
+  const int np_ffn = fm.layer.ffn, np_o = fm.o, np_p = fm.p;
+  const LayerBufs bufs = layer_bufs(ws.x, ws.gw, ws.enc_len, fm, B, Tq, c.d_model);
+  half_t *const vt_lo = bufs.vt_lo, *const q_lo = bufs.q_lo, *const k_lo = bufs.k_lo;
   const int M = B * Tq, D = c.d_model, H = c.n_heads;
   int step = 0;
   auto done = [&](void) -> bool { return stop_after >= 0 && step > stop_after; };
@@ -545,7 +544,7 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
 
 
   EEC_HIP(launch_enc_lengths((const long long*)lengths, B, Tq, ws.enc_len, st));
-  if (Tp != Tq) EEC_HIP(hipMemsetAsync(ws.vt, 0, (size_t)2 * B * Tp * D * sizeof(half_t), st));
+  if (Tp != Tq) EEC_HIP(hipMemsetAsync(ws.gw.vt, 0, (size_t)2 * B * Tp * D * sizeof(half_t), st));
   {
     SubsampleArgs a{mel, B, c.n_mels, T, T1, Tq, D, ws.mid_e, enc->sub_w1p, enc->sub_b1, enc->sub_w2p, enc->sub_b2, enc->pe, ws.mid_hi, ws.mid_lo, ws.x};
     TIMED(KC_STEM, launch_subsample(a, 3, st));  // raw power mel: always hi/lo split (1 % of the flops)
@@ -560,11 +559,11 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
       for (int l = 0; l < c.layers_per_exit; ++l) {
         const PackedLayer& L = enc->layers[e * c.layers_per_exit + l];
         {
-          QkvArgs a{ws.x, M, B, Tq, Tp, H, D, L.attn_ln_w, L.attn_ln_b, L.attn_in_p, L.attn_in_b, ws.q, ws.k, ws.vt, vt_lo};
+          QkvArgs a{ws.x, M, B, Tq, Tp, H, D, L.attn_ln_w, L.attn_ln_b, L.attn_in_p, L.attn_in_b, ws.gw.q, ws.gw.k, ws.gw.vt, vt_lo};
           TIMED(KC_QKV, launch_qkv(a, np_o, st));
-          AttnArgs at{ws.q, ws.k, ws.vt, ws.enc_len, B, H, Tq, Tp, D / H, ws.p_hi, ws.p_lo, vt_lo};
+          AttnArgs at{ws.gw.q, ws.gw.k, ws.gw.vt, ws.enc_len, B, H, Tq, Tp, D / H, ws.gw.p_hi, ws.gw.p_lo, vt_lo};
           TIMED(KC_ATTN, launch_attention(at, np_o, st));
-          ProjResArgs pr{ws.x, M, D, ws.p_hi, ws.p_lo, L.attn_out_p, L.attn_out_b};
+          ProjResArgs pr{ws.x, M, D, ws.gw.p_hi, ws.gw.p_lo, L.attn_out_p, L.attn_out_b};
           TIMED(KC_PROJ, launch_proj_residual(pr, np_o, st));
         }
         ++step;
@@ -600,10 +599,7 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
       if (taps_opt) return taps_opt + (size_t)e * M * D;
       return (out && li + 1 != n_layers) ? ws.y + (size_t)e * M * D : nullptr;
     };
-    LayerBufs bufs{ws.x, ws.q, ws.k, ws.vt, vt_lo, ws.p_hi, ws.p_lo, ws.g, ws.enc_len};
-    bufs.q_lo = q_lo, bufs.k_lo = k_lo;
-    const LayerFormats nps{np_ffn, np_front, np_qkv, np_att, np_glu};
-    if (int rc = run_layer_plan(enc, 0, n_layers, bufs, B, Tq, nps, tap_of, st)) return rc;
+    if (int rc = run_layer_plan(enc, 0, n_layers, bufs, B, Tq, fm.layer, tap_of, st)) return rc;
     if (out) {
       HeadBatchArgs hb{};
       hb.out = out, hb.M = M, hb.V = c.vocab, hb.E = n_groups, hb.D = D;
@@ -614,10 +610,10 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
           hb.x[e] = rows, hb.wp[e] = enc->head_p[e], hb.wf8[e] = enc->head_f8[e], hb.bias[e] = enc->head_b[e];
         } else {
           HeadArgs h{rows, M, c.vocab, D, enc->head_p[e], enc->head_b[e], out + (size_t)e * M * c.vocab, enc->head_f8[e]};
-          TIMED(KC_HEAD, launch_head(h, np_head, st));
+          TIMED(KC_HEAD, launch_head(h, fm.head, st));
         }
       }
-      if (batch_heads) TIMED(KC_HEAD, launch_head_batch(hb, np_head, st));
+      if (batch_heads) TIMED(KC_HEAD, launch_head_batch(hb, fm.head, st));
     }
     return finish_dbg();
   }
@@ -633,14 +629,14 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
       ++step;
       if (done()) return finish_dbg();
       {
-        QkvArgs a{ws.x, M, B, Tq, Tp, H, D, L.attn_ln_w, L.attn_ln_b, L.attn_in_p, L.attn_in_b, ws.q, ws.k, ws.vt, vt_lo, L.attn_in_f8};
+        QkvArgs a{ws.x, M, B, Tq, Tp, H, D, L.attn_ln_w, L.attn_ln_b, L.attn_in_p, L.attn_in_b, ws.gw.q, ws.gw.k, ws.gw.vt, vt_lo, L.attn_in_f8};
         a.q_lo = q_lo, a.k_lo = k_lo;
-        TIMED(KC_QKV, launch_qkv(a, np_qkv, st));
-        AttnArgs at{ws.q, ws.k, ws.vt, ws.enc_len, B, H, Tq, Tp, D / H, ws.p_hi, ws.p_lo, vt_lo};
+        TIMED(KC_QKV, launch_qkv(a, np_p, st));
+        AttnArgs at{ws.gw.q, ws.gw.k, ws.gw.vt, ws.enc_len, B, H, Tq, Tp, D / H, ws.gw.p_hi, ws.gw.p_lo, vt_lo};
         at.q_lo = q_lo, at.k_lo = k_lo;
         TIMED(KC_ATTN, launch_attention(at, np_o, st));
-        ProjResArgs pr{ws.x, M, D, ws.p_hi, ws.p_lo, L.attn_out_p, L.attn_out_b, L.attn_out_f8};
-        GluArgs ga{ws.x, M, L.conv_ln_w, L.conv_ln_b, L.conv_pw1_p, L.conv_pw1_b, ws.g, L.conv_pw1_f8};
+        ProjResArgs pr{ws.x, M, D, ws.gw.p_hi, ws.gw.p_lo, L.attn_out_p, L.attn_out_b, L.attn_out_f8};
+        GluArgs ga{ws.x, M, L.conv_ln_w, L.conv_ln_b, L.conv_pw1_p, L.conv_pw1_b, ws.gw.g, L.conv_pw1_f8};
         // out-proj + residual and the conv module's LN -> pointwise-1 -> GLU share one launch
         // (the sub-step hook stops between them, so it falls back to the two separate kernels)
         const bool split_here = stop_after >= 0 && step + 1 > stop_after;
@@ -653,7 +649,7 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
         if (done()) return finish_dbg();
       }
       {
-        DwArgs da{ws.g, B, Tq, L.dw_wfold, L.dw_bfold, ws.p_hi, ws.p_lo};
+        DwArgs da{ws.gw.g, B, Tq, L.dw_wfold, L.dw_bfold, ws.gw.p_hi, ws.gw.p_lo};
         ProjResArgs pr{ws.x, M, D, nullptr, nullptr, L.conv_pw2_p, L.conv_pw2_b, L.conv_pw2_f8};
         TIMED(KC_DW_PW2, launch_dw_pw2(da, pr, np_p, st));
       }
@@ -698,26 +694,6 @@ int eec_encoder_forward_prefix(eec_encoder* enc, const float* mel, const int64_t
 // Building blocks: one exit group / one head on caller-owned rows.  They let a host compose the reference's
 // other encoder topologies (Splitformer early_exit.py:227-364: parallel down-sampled branches) out of the same
 // kernels; Early_conformer itself goes through eec_encoder_forward.
-struct GroupWs {
-  half_t *q, *k, *vt, *p_hi, *p_lo, *g;
-  size_t bytes;
-};
-static GroupWs carve_group_ws(const eec_config& c, int B, int Tq, char* base) {
-  const int Tp = (Tq + 31) / 32 * 32;
-  const size_t M = (size_t)B * Tq, D = c.d_model;
-  Arena a;
-  a.base = base;
-  GroupWs w;
-  w.q = a.take<half_t>((size_t)2 * B * Tp * D);   // hi plane, then the residual plane (exact mode f16x3 only)
-  w.k = a.take<half_t>((size_t)2 * B * Tp * D);
-  w.vt = a.take<half_t>((size_t)2 * B * Tp * D);  // hi plane, then the residual plane
-  w.p_hi = a.take<half_t>(M * D);
-  w.p_lo = a.take<half_t>(M * D);
-  w.g = a.take<half_t>(M * D);
-  w.bytes = align_up(a.off);
-  return w;
-}
-
 size_t eec_encoder_group_workspace_bytes(const eec_encoder* enc, int B, int Tq) {
   if (!enc || B <= 0 || Tq <= 0) return 0;
   return carve_group_ws(enc->cfg, B, Tq, nullptr).bytes;
@@ -732,22 +708,16 @@ int eec_encoder_group_forward(eec_encoder* enc, int group, float* x, const int32
   if (c.arch != EEC_ARCH_CONFORMER) return fail(EEC_ERR_UNSUPPORTED, "group forward is built for EEC_ARCH_CONFORMER");
   if (group < 0 || group >= c.n_exits) return fail(EEC_ERR_BAD_ARG, "group out of range");
   if (B <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, "need B > 0 and T' > 0");
-  if (precision < EEC_PREC_F16X3 || precision > EEC_PREC_F16F8) return fail(EEC_ERR_BAD_ARG, "unknown precision");
-  if (((uintptr_t)workspace & 255) != 0) return fail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (int rc = check_precision(precision)) return rc;
   const GroupWs ws = carve_group_ws(c, B, Tq, (char*)workspace);
-  if (workspace_bytes < ws.bytes) return fail(EEC_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_workspace(workspace, workspace_bytes, ws.bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int np_ffn = precision == EEC_PREC_F16X3 ? 3 : (precision == EEC_PREC_F16F8 ? 8 : 1);
-  const int np_o = precision == EEC_PREC_F16 ? 1 : 3;
+  const Formats fm = formats_of(c, precision);
   const int Tp = (Tq + 31) / 32 * 32, D = c.d_model;
-  half_t* const vt_lo = np_o == 3 ? ws.vt + (size_t)B * Tp * D : nullptr;
   if (Tp != Tq) EEC_HIP(hipMemsetAsync(ws.vt, 0, (size_t)2 * B * Tp * D * sizeof(half_t), st));
-  LayerBufs bufs{x, ws.q, ws.k, ws.vt, vt_lo, ws.p_hi, ws.p_lo, ws.g, key_len};
-  if (precision == EEC_PREC_F16X3) bufs.q_lo = ws.q + (size_t)B * Tp * D, bufs.k_lo = ws.k + (size_t)B * Tp * D;  // exact mode (forward_impl)
-  const int np_p = (precision == EEC_PREC_F16F8 && c.d_model == 256 && c.d_ff % 128 == 0) ? 8 : np_o;
-  const LayerFormats nps{np_ffn, np_p, np_p, np_o, np_p};  // {ffn, front, qkv, att, glu}
+  const LayerBufs bufs = layer_bufs(x, ws, key_len, fm, B, Tq, D);
   const int l0 = group * c.layers_per_exit;
-  return run_layer_plan(enc, l0, l0 + c.layers_per_exit, bufs, B, Tq, nps, [](int) -> float* { return nullptr; }, st);
+  return run_layer_plan(enc, l0, l0 + c.layers_per_exit, bufs, B, Tq, fm.layer, [](int) -> float* { return nullptr; }, st);
 }
 
 int eec_encoder_stem1_forward(eec_encoder* enc, const float* mel, int B, int T, float* x, void* stream) {
@@ -769,19 +739,27 @@ int eec_encoder_head_forward(eec_encoder* enc, int exit, const float* x, int M, 
   if (!enc->packed || !enc->has_heads) return fail(EEC_ERR_NOT_PACKED, "no packed head parameters");
   if (int rc = check_device(enc)) return rc;
   if (exit < 0 || exit >= enc->cfg.n_exits || M <= 0) return fail(EEC_ERR_BAD_ARG, "exit / M out of range");
-  if (precision < EEC_PREC_F16X3 || precision > EEC_PREC_F16F8) return fail(EEC_ERR_BAD_ARG, "unknown precision");
+  if (int rc = check_precision(precision)) return rc;
   HeadArgs h{x, M, enc->cfg.vocab, enc->cfg.d_model, enc->head_p[exit], enc->head_b[exit], out, enc->head_f8[exit]};
   hipStream_t st = (hipStream_t)stream;
   TIMED(KC_HEAD, launch_head(h, precision == EEC_PREC_F16 ? 1 : 3, st));
   return 0;
 }
 
+// what the three CTC loss entries ask of their sizes (each checks its own pointers first); the two forward entries take any
+// vocabulary and check the blank label, the backward holds a vocabulary row in one wave and does not read `blank`
+static int check_ctc_args(int E, int B, int Tq, int V, int S, int blank, bool backward) {
+  if (E <= 0 || B <= 0 || Tq <= 0 || V <= 0 || S <= 0) return fail(EEC_ERR_BAD_ARG, "bad size");
+  if (!backward && (blank < 0 || blank >= V)) return fail(EEC_ERR_BAD_ARG, "blank must be a label in [0, V)");
+  if (backward && (V > 256 || V % 4)) return fail(EEC_ERR_UNSUPPORTED, "vocab must be a multiple of 4, <= 256");
+  if (2 * S + 1 > 512) return fail(EEC_ERR_UNSUPPORTED, "target length above 255");
+  return 0;
+}
+
 int eec_ctc_loss(const float* logp, const int64_t* targets, const int64_t* target_len, int E, int B, int Tq, int V, int S,
                  int blank, float* nll_scratch, float* loss_per_exit, void* stream) {
   if (!logp || !targets || !target_len || !nll_scratch || !loss_per_exit) return fail(EEC_ERR_BAD_ARG, "null argument");
-  if (E <= 0 || B <= 0 || Tq <= 0 || V <= 0 || S <= 0) return fail(EEC_ERR_BAD_ARG, "bad size");
-  if (blank < 0 || blank >= V) return fail(EEC_ERR_BAD_ARG, "blank must be a label in [0, V)");
-  if (2 * S + 1 > 512) return fail(EEC_ERR_UNSUPPORTED, "target length above 255");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, false)) return rc;
   EEC_HIP(launch_ctc_loss(logp, (const long long*)targets, (const long long*)target_len, E, B, Tq, V, S, blank, nll_scratch,
                           loss_per_exit, nullptr, (hipStream_t)stream));
   return 0;
@@ -795,9 +773,7 @@ size_t eec_ctc_backward_workspace_bytes(int E, int B, int Tq, int S) {
 int eec_ctc_loss_forward(const float* logp, const int64_t* targets, const int64_t* target_len, int E, int B, int Tq, int V, int S,
                          int blank, float* nll, float* loss_per_exit, void* bwd_workspace, void* stream) {
   if (!logp || !targets || !target_len || !nll || !loss_per_exit || !bwd_workspace) return fail(EEC_ERR_BAD_ARG, "null argument");
-  if (E <= 0 || B <= 0 || Tq <= 0 || V <= 0 || S <= 0) return fail(EEC_ERR_BAD_ARG, "bad size");
-  if (blank < 0 || blank >= V) return fail(EEC_ERR_BAD_ARG, "blank must be a label in [0, V)");
-  if (2 * S + 1 > 512) return fail(EEC_ERR_UNSUPPORTED, "target length above 255");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, false)) return rc;
   EEC_HIP(launch_ctc_loss(logp, (const long long*)targets, (const long long*)target_len, E, B, Tq, V, S, blank, nll,
                           loss_per_exit, (float*)bwd_workspace, (hipStream_t)stream));
   return 0;
@@ -806,9 +782,7 @@ int eec_ctc_loss_forward(const float* logp, const int64_t* targets, const int64_
 int eec_ctc_loss_backward(const float* logp, const int64_t* targets, const int64_t* target_len, int E, int B, int Tq, int V, int S,
                           int blank, const float* nll, void* bwd_workspace, const float* grad_loss, float* dlogp, void* stream) {
   if (!logp || !targets || !target_len || !nll || !bwd_workspace || !grad_loss || !dlogp) return fail(EEC_ERR_BAD_ARG, "null argument");
-  if (E <= 0 || B <= 0 || Tq <= 0 || V <= 0 || S <= 0) return fail(EEC_ERR_BAD_ARG, "bad size");
-  if (V > 256 || V % 4) return fail(EEC_ERR_UNSUPPORTED, "vocab must be a multiple of 4, <= 256");
-  if (2 * S + 1 > 512) return fail(EEC_ERR_UNSUPPORTED, "target length above 255");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, true)) return rc;
   EEC_HIP(launch_ctc_backward(logp, (const long long*)targets, (const long long*)target_len, E, B, Tq, V, S, blank, nll,
                               (float*)bwd_workspace, grad_loss, dlogp, (hipStream_t)stream));
   return 0;

@@ -30,6 +30,7 @@
 #include <math.h>
 
 #include "../../include/eec.h"
+#include "eec_host.h"
 #include "eec_kernels.h"
 
 namespace eec {
@@ -262,11 +263,16 @@ int eec_ctc_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_
                   const int32_t* em_index, int n_hyp, int tok_stride, int blank, int32_t* point_token, float* point_score, float* path_score,
                   float* final_score, int32_t* status, float* trellis_opt, void* workspace, void* stream) {
   (void)workspace;
-  if (n_hyp < 0 || Tq < 1 || tok_stride < 1 || n_em < 1 || V < 1 || blank < 0 || blank >= V) return EEC_ERR_BAD_ARG;
+  using eech::fail;
+  if (n_hyp < 0 || Tq < 1 || tok_stride < 1 || n_em < 1 || V < 1 || blank < 0 || blank >= V)
+    return fail(EEC_ERR_BAD_ARG, "eec_ctc_align: needs n_hyp >= 0, Tq, tok_stride, n_em, V >= 1 and blank in [0, V)");
   if (n_hyp == 0) return 0;
-  if (!logp || !tokens || !tok_len || !point_token || !point_score || !path_score || !final_score || !status) return EEC_ERR_BAD_ARG;
+  if (!logp || !tokens || !tok_len || !point_token || !point_score || !path_score || !final_score || !status)
+    return fail(EEC_ERR_BAD_ARG, "eec_ctc_align: null argument");
   const int C = (tok_stride + 1 + 63) / 64;
-  if (V < 2 || C > eec::kAlMaxC || eec::al_lds_bytes(Tq, C) > eec::kAlMaxLds) return EEC_ERR_UNSUPPORTED;
+  if (V < 2 || C > eec::kAlMaxC || eec::al_lds_bytes(Tq, C) > eec::kAlMaxLds)
+    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_align: needs V >= 2, tok_stride <= " + std::to_string(64 * eec::kAlMaxC - 1) +
+                                         " and a Tq x tok_stride lattice that fits the LDS");
   const size_t lds = eec::al_lds_bytes(Tq, C);
   const dim3 grid(n_hyp);
   hipStream_t st = (hipStream_t)stream;
@@ -275,7 +281,7 @@ int eec_ctc_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_
                              tok_stride, blank, point_token, point_score, path_score, final_score, status, trellis_opt)
   hipError_t e = C == 1 ? EEC_AL_LAUNCH(1) : C == 2 ? EEC_AL_LAUNCH(2) : C == 3 ? EEC_AL_LAUNCH(3) : EEC_AL_LAUNCH(4);
 #undef EEC_AL_LAUNCH
-  return (int)e;
+  return e == hipSuccess ? 0 : eech::hip_fail(e, "eec_ctc_align launch");
 }
 
 }  // extern "C"

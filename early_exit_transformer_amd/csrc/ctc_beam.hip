@@ -15,6 +15,7 @@
 #include <limits.h>
 
 #include "../../include/eec.h"
+#include "eec_host.h"
 #include "eec_kernels.h"
 
 namespace eec {
@@ -215,10 +216,14 @@ int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, 
 
 int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                            int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream) {
-  if (!logp || !workspace || !tokens || !counts || !scores || n_seq <= 0 || Tq <= 0) return EEC_ERR_BAD_ARG;
-  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V) return EEC_ERR_UNSUPPORTED;
-  return (int)eec::launch_ctc_beam(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
-                                   counts, scores, (hipStream_t)stream);
+  using eech::fail;
+  if (!logp || !workspace || !tokens || !counts || !scores) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: null argument");
+  if (n_seq <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: n_seq and Tq must be positive");
+  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V)
+    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_beam_decode: needs 1 <= V <= 256, 1 <= beam_size <= " + std::to_string(eec::kCbMaxBeam) + ", blank in [0, V)");
+  EEC_HIP(eec::launch_ctc_beam(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens, counts,
+                               scores, (hipStream_t)stream));
+  return 0;
 }
 
 }  // extern "C"

@@ -392,7 +392,7 @@ int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, i
   Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, E, B};
   Cache c;
   if (int rc = check_call(taps != nullptr, ps, E, g, nullptr, &cache, 1, cache_bytes, &c)) return rc;
-  if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  if (int rc = eech::check_passes(passes)) return rc;
   const int L = g.L;
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model;
@@ -403,7 +403,7 @@ int eec_decoder_batch_begin(const eec_decoder_params* const* ps, int E, int B, i
       GemmArgs a = gemm_args(taps + (size_t)e * rows * D, D, 1, P.ca_in_w + (size_t)D * D, D, 1, c.mem + ((size_t)e * L + l) * rows * 2 * D, 2 * D,
                              (int)rows, 2 * D, D);
       a.bias = P.ca_in_b + D;
-      EECS_RUN(launch_gemm(a, passes, st));
+      EEC_HIP(launch_gemm(a, passes, st));
     }
   return 0;
 }
@@ -428,7 +428,7 @@ int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, in
     a.x = c.x, a.pad = c.pad, a.anc = c.anc, a.anc_u = anc_u;
     a.B = B, a.R = R, a.R_prev = R_prev, a.s = s, a.S_max = S_max, a.D = D, a.V = vocab, a.pad_idx = pad_idx;
     hipLaunchKernelGGL(batch_embed_kernel, dim3(R, (unsigned)U), dim3(256), 0, st, a);
-    EECS_RUN(hipGetLastError());
+    EEC_HIP(hipGetLastError());
   }
   // one batch_linear launch for all exits: exit e's weights through f(e)
   auto linear = [&](const float* X, long ldx, float* Y, long ldy, int N, int K, int relu, int accumulate, auto f) {
@@ -439,33 +439,33 @@ int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, in
     return batch_linear(a, E, st);
   };
   const size_t self_lds = (size_t)(s + 1) * 8;
-  EECS_RUN(eec::ensure_max_lds((const void*)batch_self_attn_kernel, (int)self_lds));
+  EEC_HIP(eec::ensure_max_lds((const void*)batch_self_attn_kernel, (int)self_lds));
   for (int l = 0; l < L; ++l) {
     auto P = [&](int e) -> const eec_decoder_layer_params& { return ps[e]->layers[l]; };
     // self-attention over each beam's own prefix
-    EECS_RUN(linear(c.x, D, c.qkv, 3L * D, 3 * D, D, 0, 0, [&](int e) { return ExitLinear{P(e).sa_in_w, P(e).sa_in_b, P(e).norm1_w, P(e).norm1_b}; }));
+    EEC_HIP(linear(c.x, D, c.qkv, 3L * D, 3 * D, D, 0, 0, [&](int e) { return ExitLinear{P(e).sa_in_w, P(e).sa_in_b, P(e).norm1_w, P(e).norm1_b}; }));
     {
       SelfAttnArgs a{c.qkv, c.kv + (size_t)l * S_max * kRows * 2 * D, kv_u, c.anc + (size_t)(s & 1) * kRows * S_max, anc_u, c.pad, c.ctx,
                      B, R, s, S_max, D, dh, scale};
       hipLaunchKernelGGL(batch_self_attn_kernel, dim3(M, H, E), dim3(256), self_lds, st, a);
-      EECS_RUN(hipGetLastError());
+      EEC_HIP(hipGetLastError());
     }
-    EECS_RUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).sa_out_w, P(e).sa_out_b, nullptr, nullptr}; }));
+    EEC_HIP(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).sa_out_w, P(e).sa_out_b, nullptr, nullptr}; }));
     // cross-attention over the utterance's memory
-    EECS_RUN(linear(c.x, D, c.q, D, D, D, 0, 0, [&](int e) { return ExitLinear{P(e).ca_in_w, P(e).ca_in_b, P(e).norm2_w, P(e).norm2_b}; }));
+    EEC_HIP(linear(c.x, D, c.q, D, D, D, 0, 0, [&](int e) { return ExitLinear{P(e).ca_in_w, P(e).ca_in_b, P(e).norm2_w, P(e).norm2_b}; }));
     {
       CrossAttnArgs a{c.q, c.mem + (size_t)l * B * Tq * 2 * D, (long)L * B * Tq * 2 * D, c.ctx, B, R, Tq, D, dh, scale};
       hipLaunchKernelGGL(batch_cross_attn_kernel, dim3(H, B, E), dim3(256), 0, st, a);
-      EECS_RUN(hipGetLastError());
+      EEC_HIP(hipGetLastError());
     }
-    EECS_RUN(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).ca_out_w, P(e).ca_out_b, nullptr, nullptr}; }));
+    EEC_HIP(linear(c.ctx, D, c.x, D, D, D, 0, 1, [&](int e) { return ExitLinear{P(e).ca_out_w, P(e).ca_out_b, nullptr, nullptr}; }));
     // feed-forward, ReLU
-    EECS_RUN(linear(c.x, D, c.h, F, F, D, 1, 0, [&](int e) { return ExitLinear{P(e).w1, P(e).b1, P(e).norm3_w, P(e).norm3_b}; }));
-    EECS_RUN(linear(c.h, F, c.x, D, D, F, 0, 1, [&](int e) { return ExitLinear{P(e).w2, P(e).b2, nullptr, nullptr}; }));
+    EEC_HIP(linear(c.x, D, c.h, F, F, D, 1, 0, [&](int e) { return ExitLinear{P(e).w1, P(e).b1, P(e).norm3_w, P(e).norm3_b}; }));
+    EEC_HIP(linear(c.h, F, c.x, D, D, F, 0, 1, [&](int e) { return ExitLinear{P(e).w2, P(e).b2, nullptr, nullptr}; }));
   }
-  EECS_RUN(linear(c.x, D, c.logits, vocab, vocab, D, 0, 0, [&](int e) { return ExitLinear{ps[e]->head_w, ps[e]->head_b, ps[e]->norm_w, ps[e]->norm_b}; }));
+  EEC_HIP(linear(c.x, D, c.logits, vocab, vocab, D, 0, 0, [&](int e) { return ExitLinear{ps[e]->head_w, ps[e]->head_b, ps[e]->norm_w, ps[e]->norm_b}; }));
   hipLaunchKernelGGL(batch_logsoftmax_kernel, dim3((unsigned)(U * R)), dim3(64), 0, st, c.logits, out, vocab);
-  EECS_RUN(hipGetLastError());
+  EEC_HIP(hipGetLastError());
   return 0;
 }
 

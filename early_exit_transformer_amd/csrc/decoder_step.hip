@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
 
 extern "C" {
 
-const char* eec_decoder_step_last_error(void) { return g_err.c_str(); }
+const char* eec_decoder_step_last_error(void) { return eech::g_err.c_str(); }
 
 int eec_decoder_step_max_beams(void) { return kRows; }
 
@@ -423,14 +423,14 @@ int eec_decoder_begin(const eec_decoder_params* p, int d_model, int n_heads, int
   Geo g{d_model, n_heads, d_ff, vocab, 0, S_max, Tq, 1, 1};
   Cache c;
   if (int rc = check_call(enc != nullptr, &p, 1, g, nullptr, &cache, 1, cache_bytes, &c)) return rc;
-  if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  if (int rc = eech::check_passes(passes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int D = d_model;
   for (int l = 0; l < p->n_layers; ++l) {  // memory keys | values of every layer: enc . W[D:3D]^T + b[D:3D]
     const eec_decoder_layer_params& L = p->layers[l];
     GemmArgs a = gemm_args(enc, D, 1, L.ca_in_w + (size_t)D * D, D, 1, c.mem + (size_t)l * Tq * 2 * D, 2 * D, Tq, 2 * D, D);
     a.bias = L.ca_in_b + D;
-    EECS_RUN(launch_gemm(a, passes, st));
+    EEC_HIP(launch_gemm(a, passes, st));
   }
   return 0;
 }
@@ -453,7 +453,7 @@ int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_mod
       e.a[i] = EmbedArgs{(const long long*)last_tokens + (size_t)i * R, parent ? (const long long*)parent + (size_t)i * R : nullptr, ps[i]->emb,
                          ps[i]->pe, c[i].x, c[i].pad, c[i].anc + anc_old, c[i].anc + anc_new};
     hipLaunchKernelGGL(step_embed_kernel, dim3(R, n), dim3(256), 0, st, e, s, S_max, D, vocab, pad_idx, R_prev);
-    EECS_RUN(hipGetLastError());
+    EEC_HIP(hipGetLastError());
   }
   // one skinny_linear launch for all sessions: session i's operands through f(i)
   auto linear = [&](auto f, int N, int K, int relu, int accumulate) {
@@ -467,37 +467,37 @@ int eec_decoder_step_multi(int n, const eec_decoder_params* const* ps, int d_mod
   for (int l = 0; l < n_layers; ++l) {
     auto L = [&](int i) -> const eec_decoder_layer_params& { return ps[i]->layers[l]; };
     // self-attention over the beam's own prefix
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm1_w, L(i).norm1_b, L(i).sa_in_w, L(i).sa_in_b, c[i].qkv, 3L * D}; }, 3 * D, D, 0, 0));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm1_w, L(i).norm1_b, L(i).sa_in_w, L(i).sa_in_b, c[i].qkv, 3L * D}; }, 3 * D, D, 0, 0));
     {
       Group<StepAttnArgs> sa{};
       for (int i = 0; i < n; ++i)
         sa.a[i] = StepAttnArgs{c[i].qkv, 3L * D, c[i].qkv + D, c[i].qkv + 2 * D, c[i].kv + (size_t)l * S_max * kRows * 2 * D, c[i].anc + anc_new, c[i].pad,
                                c[i].ctx, s, S_max, 0, D, dh, scale};
-      EECS_RUN(step_attn<true>(sa, n, R, H, st));
+      EEC_HIP(step_attn<true>(sa, n, R, H, st));
     }
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).sa_out_w, L(i).sa_out_b, c[i].x, D}; }, D, D, 0, 1));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).sa_out_w, L(i).sa_out_b, c[i].x, D}; }, D, D, 0, 1));
     // cross-attention over the utterance's memory
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm2_w, L(i).norm2_b, L(i).ca_in_w, L(i).ca_in_b, c[i].q, D}; }, D, D, 0, 0));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm2_w, L(i).norm2_b, L(i).ca_in_w, L(i).ca_in_b, c[i].q, D}; }, D, D, 0, 0));
     {
       Group<StepAttnArgs> ca{};
       for (int i = 0; i < n; ++i)
         ca.a[i] = StepAttnArgs{c[i].q, (long)D, nullptr, nullptr, c[i].mem + (size_t)l * Tq * 2 * D, nullptr, nullptr, c[i].ctx, s, S_max, Tq, D, dh, scale};
-      EECS_RUN(step_attn<false>(ca, n, R, H, st));
+      EEC_HIP(step_attn<false>(ca, n, R, H, st));
     }
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).ca_out_w, L(i).ca_out_b, c[i].x, D}; }, D, D, 0, 1));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].ctx, D, nullptr, nullptr, L(i).ca_out_w, L(i).ca_out_b, c[i].x, D}; }, D, D, 0, 1));
     // feed-forward, ReLU
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm3_w, L(i).norm3_b, L(i).w1, L(i).b1, c[i].h, F}; }, F, D, 1, 0));
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].h, F, nullptr, nullptr, L(i).w2, L(i).b2, c[i].x, D}; }, D, F, 0, 1));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].x, D, L(i).norm3_w, L(i).norm3_b, L(i).w1, L(i).b1, c[i].h, F}; }, F, D, 1, 0));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].h, F, nullptr, nullptr, L(i).w2, L(i).b2, c[i].x, D}; }, D, F, 0, 1));
   }
   const size_t out_stride = (size_t)R * vocab;
   if (log_softmax) {
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, c[i].logits, vocab}; }, vocab, D, 0, 0));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, c[i].logits, vocab}; }, vocab, D, 0, 0));
     Group<LsmArgs> lg{};
     for (int i = 0; i < n; ++i) lg.a[i] = LsmArgs{c[i].logits, out + i * out_stride};
     hipLaunchKernelGGL(step_logsoftmax_kernel, dim3(R, n), dim3(64), 0, st, lg, vocab);
-    EECS_RUN(hipGetLastError());
+    EEC_HIP(hipGetLastError());
   } else {
-    EECS_RUN(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, out + i * out_stride, vocab}; }, vocab, D, 0, 0));
+    EEC_HIP(linear([&](int i) { return SkinnyArgs{c[i].x, D, ps[i]->norm_w, ps[i]->norm_b, ps[i]->head_w, ps[i]->head_b, out + i * out_stride, vocab}; }, vocab, D, 0, 0));
   }
   return 0;
 }
@@ -510,10 +510,10 @@ int eec_beam_select(int n, int R, int V, int K, const float* logp, const float* 
     return fail(EEC_ERR_BAD_ARG, "eec_beam_select: 1 .. 16 beams in and out, token rows of at least len + 1");
   const size_t lds = (size_t)R * V * sizeof(float);
   if (lds > 150000) return fail(EEC_ERR_UNSUPPORTED, "eec_beam_select: R * V candidates must fit the LDS");
-  EECS_RUN(eec::ensure_max_lds((const void*)beam_select_kernel, (int)lds));
+  EEC_HIP(eec::ensure_max_lds((const void*)beam_select_kernel, (int)lds));
   hipLaunchKernelGGL(beam_select_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream, logp, scores_in, penalty, R, V, K, scores_out,
                      (long long*)parent, (long long*)tok, (const long long*)tokens_old, (long long*)tokens_new, len, ld, rows_ld);
-  EECS_RUN(hipGetLastError());
+  EEC_HIP(hipGetLastError());
   return 0;
 }
 

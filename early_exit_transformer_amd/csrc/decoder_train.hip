@@ -17,32 +17,12 @@
 #include <vector>
 
 #include "../../include/eec.h"
-#include "eec_train.h"
+#include "eec_train_host.h"
 
 using namespace eect;
+using namespace eech;
 
 namespace {
-
-thread_local std::string g_dterr;
-int dtfail(int code, const std::string& msg) {
-  g_dterr = msg;
-  return code;
-}
-
-struct Bump {  // bump allocator; base == nullptr: sizes only
-  char* base = nullptr;
-  size_t off = 0, peak = 0, cap = ~(size_t)0;
-  bool overflow = false;
-  float* f(size_t n) {
-    off = (off + 255) / 256 * 256;
-    float* p = (float*)(base + off);
-    off += n * sizeof(float);
-    if (off > peak) peak = off;
-    if (off > cap) overflow = true;
-    return p;
-  }
-  void reset(size_t to = 0) { off = to; }
-};
 
 struct Geo {
   int D, H, F, V, L, Bm, S, Tq, dh;
@@ -94,43 +74,21 @@ constexpr int kMaxLayers = 64, kSitesPerExit = 1024;  // the entries refuse more
 static_assert(kMaxLayers * kSitesPerLayer <= kSitesPerExit, "the dropout sites of two exits would overlap");
 uint32_t site_of(int exit_index, int layer, int place) { return 1u + (uint32_t)exit_index * kSitesPerExit + (uint32_t)layer * kSitesPerLayer + (uint32_t)place; }
 
-struct Run {
+struct Run : TrainRun {
   Geo g;
-  int np;
   float p;
   uint64_t seed;
   int exit_index;
-  bool dry;
-  hipStream_t st;
-  Bump scr;
-  hipError_t err = hipSuccess;
-  const char* where = "";
-  void ok(hipError_t e, const char* w) {
-    if (e != hipSuccess && err == hipSuccess) err = e, where = w;
-  }
+  Run(const Geo& g_, int np_, float p_, uint64_t seed_, int exit_index_, bool dry_, hipStream_t st_)
+      : TrainRun(dry_, st_, np_), g(g_), p(p_), seed(seed_), exit_index(exit_index_) {}
   Drop drop(int layer, int place) const { return Drop{p, seed, site_of(exit_index, layer, place)}; }
   Drop drop_pe() const { return Drop{p, seed, 0u}; }
 };
-#define RUN(expr)                    \
-  do {                               \
-    if (!r.dry) r.ok((expr), #expr); \
-  } while (0)
 
-void linear_fwd(Run& r, const float* x, const float* W, const float* bias, float* y, long M, int N, int K) {
-  GemmArgs g = gemm_args(x, K, 1, W, K, 1, y, N, (int)M, N, K);
-  g.bias = bias;
-  RUN(launch_gemm(g, r.np, r.st));
-}
 // y = res + drop(x . W^T + bias)
 void linear_residual_fwd(Run& r, const float* x, const float* W, const float* bias, const float* res, Drop d, float* y, long M, int N, int K) {
   GemmArgs g = gemm_args(x, K, 1, W, K, 1, y, N, (int)M, N, K);
   g.bias = bias, g.epi = 4, g.aux = res, g.res_scale = 1.0f, g.drop = d;
-  RUN(launch_gemm(g, r.np, r.st));
-}
-// dx[M][K] (+)= dy[M][N] . W[N][K]
-void linear_bwd_data(Run& r, const float* dy, const float* W, float* dx, long M, int N, int K, bool accumulate = false) {
-  GemmArgs g = gemm_args(dy, N, 1, W, 1, K, dx, K, (int)M, K, N);
-  g.accumulate = accumulate;
   RUN(launch_gemm(g, r.np, r.st));
 }
 // dW[N][K] = dy[M][N]^T . x[M][K] (split over the rows, partials summed in a fixed order); db[N] = column sums of dy
@@ -157,17 +115,6 @@ void linear_bwd_weight(Run& r, const float* dy, const float* x, float* dW, float
   }
   r.scr.reset(mark);
 }
-// dx = (add_res ? dx : 0) + LN'(dln); dg / db from the per-block partials
-void ln_bwd(Run& r, const float* dln, const float* x, const float* g, const float* mean, const float* rstd, float* dx, bool add_res, float* dg,
-            float* db, long M, int D) {
-  const size_t mark = r.scr.off;
-  const int nb = ln_bwd_blocks((int)M);
-  float* part = r.scr.f((size_t)nb * 2 * D);
-  RUN(launch_ln_bwd(dln, x, g, mean, rstd, add_res ? dx : nullptr, dx, part, (int)M, D, r.st));
-  RUN(launch_reduce_leading2(part, nb, D, dg, db, r.st));
-  r.scr.reset(mark);
-}
-
 // operands of one attention: queries [Bm*S] rows of stride q_m (batch stride q_b), keys / values [Bm*Tk] rows of stride kv_m
 struct AttnOps {
   const float *q, *k, *v;
@@ -323,12 +270,12 @@ void backward(Run& r, Bump& tb, const eec_decoder_params* p, const eec_decoder_p
 }
 
 int check_geo(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, int Bm, int S, int Tq, int passes, float drop_prob) {
-  if (!p) return dtfail(EEC_ERR_BAD_ARG, "null argument");
-  if (passes != 1 && passes != 3) return dtfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return dtfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
+  if (!p) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_passes(passes)) return rc;
+  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return fail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
   if (d_model <= 0 || d_model > 1024 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || vocab > 1024 || p->n_layers <= 0 ||
       p->n_layers > kMaxLayers || Bm <= 0 || S <= 0 || Tq <= 0 || S > p->max_len)
-    return dtfail(EEC_ERR_BAD_ARG, "bad geometry");
+    return fail(EEC_ERR_BAD_ARG, "bad geometry");
   return 0;
 }
 Geo make_geo(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int Bm, int S, int Tq) {
@@ -345,14 +292,14 @@ Sizes sizes_of(const Geo& g) {
   eec_decoder_params none{};
   none.n_layers = g.L;
   backward(r, tb2, &none, &none, nullptr, nullptr, nullptr, nullptr);
-  return Sizes{(tb.peak + 255) / 256 * 256, (r.scr.peak + 255) / 256 * 256};
+  return Sizes{up256(tb.peak), up256(r.scr.peak)};
 }
 
 }  // namespace
 
 extern "C" {
 
-const char* eec_decoder_train_last_error(void) { return g_dterr.c_str(); }
+const char* eec_decoder_train_last_error(void) { return g_err.c_str(); }
 
 size_t eec_decoder_train_workspace_bytes(int d_model, int n_heads, int d_ff, int vocab, int n_layers, int Bm, int S, int Tq) {
   if (d_model <= 0 || n_heads <= 0 || d_model % n_heads || d_ff <= 0 || vocab <= 0 || n_layers <= 0 || n_layers > kMaxLayers || Bm <= 0 || S <= 0 || Tq <= 0)
@@ -364,41 +311,35 @@ size_t eec_decoder_train_workspace_bytes(int d_model, int n_heads, int d_ff, int
 int eec_decoder_train_forward(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, int pad_idx, const int64_t* trg,
                               const float* enc, int Bm, int S, int Tq, int passes, float drop_prob, uint64_t seed, int exit_index, float* out,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (!p || !trg || !enc || !out || !workspace || !p->layers) return dtfail(EEC_ERR_BAD_ARG, "null argument");
+  if (!p || !trg || !enc || !out || !workspace || !p->layers) return fail(EEC_ERR_BAD_ARG, "null argument");
   if (int rc = check_geo(p, d_model, n_heads, d_ff, vocab, Bm, S, Tq, passes, drop_prob)) return rc;
-  if (((uintptr_t)workspace & 255) != 0) return dtfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
   const Geo g = make_geo(d_model, n_heads, d_ff, vocab, p->n_layers, Bm, S, Tq);
   const Sizes sz = sizes_of(g);
-  if (workspace_bytes < sz.tape + sz.scratch) return dtfail(EEC_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_workspace(workspace, workspace_bytes, sz.tape + sz.scratch)) return rc;
   Run r{g, passes, drop_prob, seed, exit_index, false, (hipStream_t)stream};
   Bump tb;
   tb.base = (char*)workspace, tb.cap = sz.tape;
   r.scr.base = (char*)workspace + sz.tape, r.scr.cap = workspace_bytes - sz.tape;
   forward(r, tb, p, pad_idx, trg, enc, out);
-  if (tb.overflow || r.scr.overflow) return dtfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return dtfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  return 0;
+  return finish(r, tb.overflow || r.scr.overflow);
 }
 
 int eec_decoder_train_backward(const eec_decoder_params* p, const eec_decoder_params* grads, int d_model, int n_heads, int d_ff, int vocab,
                                const int64_t* trg, const float* enc, int Bm, int S, int Tq, int passes, float drop_prob, uint64_t seed,
                                int exit_index, const float* grad_out, float* grad_enc, void* workspace, size_t workspace_bytes, void* stream) {
   if (!p || !grads || !trg || !enc || !grad_out || !grad_enc || !workspace || !p->layers || !grads->layers)
-    return dtfail(EEC_ERR_BAD_ARG, "null argument");
+    return fail(EEC_ERR_BAD_ARG, "null argument");
   if (int rc = check_geo(p, d_model, n_heads, d_ff, vocab, Bm, S, Tq, passes, drop_prob)) return rc;
-  if (grads->n_layers != p->n_layers) return dtfail(EEC_ERR_BAD_ARG, "grads must mirror params");
-  if (((uintptr_t)workspace & 255) != 0) return dtfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (grads->n_layers != p->n_layers) return fail(EEC_ERR_BAD_ARG, "grads must mirror params");
   const Geo g = make_geo(d_model, n_heads, d_ff, vocab, p->n_layers, Bm, S, Tq);
   const Sizes sz = sizes_of(g);
-  if (workspace_bytes < sz.tape + sz.scratch) return dtfail(EEC_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_workspace(workspace, workspace_bytes, sz.tape + sz.scratch)) return rc;
   Run r{g, passes, drop_prob, seed, exit_index, false, (hipStream_t)stream};
   Bump tb;
   tb.base = (char*)workspace, tb.cap = sz.tape;
   r.scr.base = (char*)workspace + sz.tape, r.scr.cap = workspace_bytes - sz.tape;
   backward(r, tb, p, grads, trg, enc, grad_out, grad_enc);
-  if (tb.overflow || r.scr.overflow) return dtfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return dtfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  return 0;
+  return finish(r, tb.overflow || r.scr.overflow);
 }
 
 }  // extern "C"

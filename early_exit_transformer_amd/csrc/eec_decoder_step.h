@@ -1,12 +1,12 @@
 // What the two step-wise AED decoders share (decoder_step.hip: the exits of one utterance; decoder_batch.hip: every exit and
-// utterance of a padded batch): the cache layout, the argument checks of their entry points, the error string behind
-// eec_decoder_step_last_error(), the wave reductions and the log-softmax of a row.  Their embed, attention and linear kernels
-// differ by design and stay in their own files.
+// utterance of a padded batch): the cache layout, the argument checks of their entry points, the wave reductions and the
+// log-softmax of a row.  Their embed, attention and linear kernels differ by design and stay in their own files.
 #pragma once
 #include <algorithm>
 #include <string>
 
 #include "../../include/eec.h"
+#include "eec_host.h"
 #include "eec_train.h"
 
 namespace eec {
@@ -42,17 +42,7 @@ __device__ __forceinline__ void log_softmax_row(const float* xr, float* out, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-inline thread_local std::string g_err;  // eec_decoder_step_last_error()
-inline int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define EECS_RUN(expr)                                                                                    \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) return eecs::fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using eech::fail;
 
 // E exits x B utterances in one cache: the per-utterance path has E = B = 1 per cache
 struct Geo {
@@ -74,26 +64,21 @@ struct Cache {
   size_t bytes;
 };
 inline Cache carve(char* base, const Geo& g) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) / 256 * 256;
-    char* p = base + off;
-    off += bytes;
-    return p;
-  };
+  eech::Bump a;
+  a.base = base;
   Cache c{};
-  const size_t f = sizeof(float), U = (size_t)g.E * g.B, rows = U * kRows;
-  c.mem = (float*)take(U * g.L * g.Tq * 2 * g.D * f);
-  c.kv = (float*)take(U * g.L * g.S_max * kRows * 2 * g.D * f);
-  c.x = (float*)take(rows * g.D * f);
-  c.qkv = (float*)take(rows * 3 * g.D * f);
-  c.q = (float*)take(rows * g.D * f);
-  c.ctx = (float*)take(rows * g.D * f);
-  c.h = (float*)take(rows * g.F * f);
-  c.logits = (float*)take(rows * g.V * f);
-  c.anc = (int*)take(U * 2 * kRows * g.S_max * sizeof(int));
-  c.pad = (unsigned char*)take(U * g.S_max * kRows);
-  c.bytes = off + 256;
+  const size_t U = (size_t)g.E * g.B, rows = U * kRows;
+  c.mem = a.f(U * g.L * g.Tq * 2 * g.D);
+  c.kv = a.f(U * g.L * g.S_max * kRows * 2 * g.D);
+  c.x = a.f(rows * g.D);
+  c.qkv = a.f(rows * 3 * g.D);
+  c.q = a.f(rows * g.D);
+  c.ctx = a.f(rows * g.D);
+  c.h = a.f(rows * g.F);
+  c.logits = a.f(rows * g.V);
+  c.anc = a.take<int>(U * 2 * kRows * g.S_max);
+  c.pad = a.take<unsigned char>(U * g.S_max * kRows);
+  c.bytes = a.off + 256;
   return c;
 }
 

@@ -1,0 +1,85 @@
+// What every host-side entry point of libeec.so shares (host code only): the calling thread's error string behind all
+// eec_*_last_error() symbols, the return-on-error and deferred-error idioms, the bump allocator that lays buffers over a
+// caller's workspace (or sizes them), and the argument checks that several families repeat.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/eec.h"
+
+namespace eech {
+
+// One message per thread for the whole library: every non-zero return of an extern "C" entry leaves its reason here.
+inline thread_local std::string g_err;
+inline int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+inline int hip_fail(hipError_t e, const char* what) {
+  g_err = std::string(what) + ": " + hipGetErrorString(e);
+  return (int)e;
+}
+// return from the enclosing entry point when a HIP call (or a launch wrapper) fails
+#define EEC_HIP(expr)                                      \
+  do {                                                     \
+    hipError_t _e = (expr);                                \
+    if (_e != hipSuccess) return eech::hip_fail(_e, #expr); \
+  } while (0)
+
+// Deferred errors, for code that carves and launches in one pass and may run dry (sizes only): the first failing call is
+// kept, later ones still run their carves, and finish() turns the outcome into the entry point's return code.
+struct Deferred {
+  bool dry = false;
+  hipError_t err = hipSuccess;
+  const char* where = "";
+  void ok(hipError_t e, const char* w) {
+    if (e != hipSuccess && err == hipSuccess) err = e, where = w;
+  }
+};
+#define RUN(expr)                    \
+  do {                               \
+    if (!r.dry) r.ok((expr), #expr); \
+  } while (0)
+inline int finish(const Deferred& r, bool overflow) {
+  if (overflow) return fail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
+  if (r.err != hipSuccess) return hip_fail(r.err, r.where);
+  return 0;
+}
+
+inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// Bump allocator over one buffer, every take aligned to 256 bytes; base == nullptr: sizes only (takes return nullptr).
+struct Bump {
+  char* base = nullptr;
+  size_t off = 0, peak = 0, cap = ~(size_t)0;
+  bool overflow = false;  // a take went past cap: checked by the entry points before anything is reported as done
+  template <typename T>
+  T* take(size_t n) {
+    off = up256(off);
+    T* p = (T*)(base ? base + off : nullptr);
+    off += n * sizeof(T);
+    if (off > peak) peak = off;
+    if (off > cap) overflow = true;
+    return p;
+  }
+  float* f(size_t n) { return take<float>(n); }
+  void reset(size_t to = 0) { off = to; }
+};
+
+inline int check_workspace(const void* ws, size_t have, size_t need) {
+  if (((uintptr_t)ws & 255) != 0) return fail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (have < need) return fail(EEC_ERR_WORKSPACE, "workspace too small");
+  return 0;
+}
+inline int check_precision(int precision) {
+  if (precision < EEC_PREC_F16X3 || precision > EEC_PREC_F16F8) return fail(EEC_ERR_BAD_ARG, "unknown precision");
+  return 0;
+}
+inline int check_passes(int passes) {
+  if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  return 0;
+}
+
+}  // namespace eech

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/eec.h"
+#include "eec_host.h"
 #include "eec_kernels.h"
 
 namespace eec {
@@ -149,26 +150,20 @@ struct eec_frontend {
   float* fb_w = nullptr;
 };
 
-namespace {
-thread_local std::string g_fe_err;
-}
-
 extern "C" {
 
-const char* eec_frontend_last_error(void) { return g_fe_err.c_str(); }
+const char* eec_frontend_last_error(void) { return eech::g_err.c_str(); }
 
 int eec_frontend_create(int sample_rate, int n_fft, int win_length, int hop_length, int n_mels, eec_frontend** out) {
-  if (!out) return EEC_ERR_BAD_ARG;
-  if (n_fft != 1024 || win_length != 320 || hop_length != 160 || n_mels <= 0 || n_mels > 256 || sample_rate <= 0) {
-    g_fe_err = "this build serves the reference's front end: 1024-point frames, window 320, hop 160, <= 256 mel bins";
-    return EEC_ERR_UNSUPPORTED;
-  }
+  using eech::fail;
+  if (!out) return fail(EEC_ERR_BAD_ARG, "null argument: out");
+  if (n_fft != 1024 || win_length != 320 || hop_length != 160 || n_mels <= 0 || n_mels > 256 || sample_rate <= 0)
+    return fail(EEC_ERR_UNSUPPORTED, "this build serves the reference's front end: 1024-point frames, window 320, hop 160, <= 256 mel bins");
   eec_frontend* fe = new eec_frontend();
   fe->sample_rate = sample_rate, fe->n_fft = n_fft, fe->win = win_length, fe->hop = hop_length, fe->n_mels = n_mels;
   if (hipGetDevice(&fe->device) != hipSuccess) {
     delete fe;
-    g_fe_err = "hipGetDevice failed";
-    return EEC_ERR_BAD_ARG;
+    return fail(EEC_ERR_BAD_ARG, "hipGetDevice failed");
   }
   const double kPi = 3.14159265358979323846;
   std::vector<float> window(win_length);
@@ -217,10 +212,8 @@ int eec_frontend_create(int sample_rate, int n_fft, int win_length, int hop_leng
     return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
   if (!up((void**)&fe->window, window.data(), window.size() * 4) || !up((void**)&fe->basis, basis.data(), basis.size() * 4) ||
-      !up((void**)&fe->fb_range, range.data(), range.size() * 4) || !up((void**)&fe->fb_w, weights.data(), weights.size() * 4)) {
-    g_fe_err = "device allocation / upload of the front-end tables failed";
-    return EEC_ERR_WORKSPACE;
-  }
+      !up((void**)&fe->fb_range, range.data(), range.size() * 4) || !up((void**)&fe->fb_w, weights.data(), weights.size() * 4))
+    return fail(EEC_ERR_WORKSPACE, "device allocation / upload of the front-end tables failed");
   *out = fe;
   return 0;
 }
@@ -234,26 +227,15 @@ void eec_frontend_destroy(eec_frontend* fe) {
 int eec_frontend_frames(int n_samples, int hop_length) { return n_samples > 0 && hop_length > 0 ? 1 + n_samples / hop_length : 0; }
 
 int eec_frontend_forward(eec_frontend* fe, const float* wave, const int64_t* lengths_opt, int B, int Lmax, float* mel, void* stream) {
-  if (!fe || !wave || !mel || B <= 0 || Lmax <= 0) {
-    g_fe_err = "bad argument";
-    return EEC_ERR_BAD_ARG;
-  }
+  using eech::fail;
+  if (!fe || !wave || !mel || B <= 0 || Lmax <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
   int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != fe->device) {
-    g_fe_err = "the front end was created on another device";
-    return EEC_ERR_BAD_ARG;
-  }
+  if (hipGetDevice(&dev) != hipSuccess || dev != fe->device) return fail(EEC_ERR_BAD_ARG, "the front end was created on another device");
   FrontendArgs a{wave, (const long long*)lengths_opt, B, Lmax, 1 + Lmax / fe->hop, fe->n_mels, fe->hop, fe->win,
                  fe->window, fe->basis, fe->fb_range, fe->fb_w, mel};
-  if (hipError_t e = ensure_max_lds((const void*)mel_frontend_kernel, kFeLds); e != hipSuccess) {
-    g_fe_err = hipGetErrorString(e);
-    return (int)e;
-  }
+  EEC_HIP(ensure_max_lds((const void*)mel_frontend_kernel, kFeLds));
   hipLaunchKernelGGL(mel_frontend_kernel, dim3((a.Tmax + kFeFrames - 1) / kFeFrames, B), dim3(kFeThreads), kFeLds, (hipStream_t)stream, a);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
-    g_fe_err = hipGetErrorString(e);
-    return (int)e;
-  }
+  EEC_HIP(hipGetLastError());
   return 0;
 }
 

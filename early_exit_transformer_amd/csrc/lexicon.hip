@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/eec.h"
+#include "eec_host.h"
 #include "eec_kernels.h"
 
 namespace eec {
@@ -282,25 +283,27 @@ size_t eec_lexicon_pack_bytes(int n_words, int64_t total_symbols, int max_len) {
 int eec_lexicon_pack(const uint32_t* symbols, const int64_t* offsets, int n_words, void* image, size_t image_bytes, int32_t* code_map,
                      int32_t* n_codes) {
   using namespace eec;
-  if (!offsets || !image || !code_map || n_words <= 0) return EEC_ERR_BAD_ARG;
-  if (offsets[0] != 0) return EEC_ERR_BAD_ARG;
+  using eech::fail;
+  if (!offsets || !image || !code_map) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_pack: null argument (offsets, image, code_map)");
+  if (n_words <= 0) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_pack: n_words must be positive");
+  if (offsets[0] != 0) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_pack: offsets[0] must be 0");
   int64_t max_len = 0;
   for (int i = 0; i < n_words; ++i) {
-    if (offsets[i + 1] < offsets[i]) return EEC_ERR_BAD_ARG;
+    if (offsets[i + 1] < offsets[i]) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_pack: offsets must not decrease");
     max_len = std::max(max_len, offsets[i + 1] - offsets[i]);
   }
   const int64_t total = offsets[n_words];
-  if (total > 0 && !symbols) return EEC_ERR_BAD_ARG;
-  if (max_len > 0x7fffffff) return EEC_ERR_UNSUPPORTED;
+  if (total > 0 && !symbols) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_pack: null symbols");
+  if (max_len > 0x7fffffff) return fail(EEC_ERR_UNSUPPORTED, "eec_lexicon_pack: a word longer than 2^31 - 1 symbols");
   const size_t need = eec_lexicon_pack_bytes(n_words, total, (int)max_len);
-  if (need == 0) return EEC_ERR_UNSUPPORTED;
-  if (image_bytes < need) return EEC_ERR_WORKSPACE;
+  if (need == 0) return fail(EEC_ERR_UNSUPPORTED, "eec_lexicon_pack: the image would pass 2^31 dwords");
+  if (image_bytes < need) return fail(EEC_ERR_WORKSPACE, "eec_lexicon_pack: image_bytes below eec_lexicon_pack_bytes()");
 
   // the alphabet: distinct code points in ascending order -> codes 1..A
   std::vector<uint32_t> alpha(symbols, symbols + total);
   std::sort(alpha.begin(), alpha.end());
   alpha.erase(std::unique(alpha.begin(), alpha.end()), alpha.end());
-  if (alpha.size() > 255) return EEC_ERR_UNSUPPORTED;
+  if (alpha.size() > 255) return fail(EEC_ERR_UNSUPPORTED, "eec_lexicon_pack: more than 255 distinct symbols");
   const int A = (int)alpha.size();
   for (int c = 0; c < 256; ++c) code_map[c] = (c >= 1 && c <= A) ? (int32_t)alpha[c - 1] : -1;
   if (n_codes) *n_codes = A;
@@ -348,12 +351,16 @@ size_t eec_lexicon_nearest_workspace_bytes(int n_queries, int n_words) {
 int eec_lexicon_nearest(const void* packed, int n_words, const uint8_t* queries, const int32_t* query_offsets, int n_queries, int max_query_len,
                         int32_t* out_index, int32_t* out_distance, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace eec;
-  if (n_queries < 0 || n_words <= 0 || max_query_len < 0) return EEC_ERR_BAD_ARG;
-  if (max_query_len > EEC_LEX_MAX_QUERY) return EEC_ERR_UNSUPPORTED;
+  using eech::fail;
+  if (n_queries < 0 || n_words <= 0 || max_query_len < 0)
+    return fail(EEC_ERR_BAD_ARG, "eec_lexicon_nearest: needs n_queries >= 0, n_words >= 1, max_query_len >= 0");
+  if (max_query_len > EEC_LEX_MAX_QUERY) return fail(EEC_ERR_UNSUPPORTED, "eec_lexicon_nearest: max_query_len above EEC_LEX_MAX_QUERY");
   if (n_queries == 0) return 0;
-  if (!packed || !queries || !query_offsets || !out_index || !out_distance || !workspace) return EEC_ERR_BAD_ARG;
-  if (((uintptr_t)packed | (uintptr_t)workspace) & 7) return EEC_ERR_BAD_ARG;
-  if (workspace_bytes < eec_lexicon_nearest_workspace_bytes(n_queries, n_words)) return EEC_ERR_WORKSPACE;
+  if (!packed || !queries || !query_offsets || !out_index || !out_distance || !workspace)
+    return fail(EEC_ERR_BAD_ARG, "eec_lexicon_nearest: null argument");
+  if (((uintptr_t)packed | (uintptr_t)workspace) & 7) return fail(EEC_ERR_BAD_ARG, "eec_lexicon_nearest: packed and workspace must be 8-byte aligned");
+  if (workspace_bytes < eec_lexicon_nearest_workspace_bytes(n_queries, n_words))
+    return fail(EEC_ERR_WORKSPACE, "eec_lexicon_nearest: workspace below eec_lexicon_nearest_workspace_bytes()");
   const int* img = (const int*)packed;
   lex_key_t* partial = (lex_key_t*)workspace;
   hipStream_t st = (hipStream_t)stream;
@@ -363,7 +370,7 @@ int eec_lexicon_nearest(const void* packed, int n_words, const uint8_t* queries,
   hipError_t e = max_query_len > 64 ? EEC_LEX_LAUNCH(8, 1) : max_query_len > 32 ? EEC_LEX_LAUNCH(2, 4)
                  : lex_tile_queries(1, n_queries) == 8 ? EEC_LEX_LAUNCH(1, 8) : EEC_LEX_LAUNCH(1, 4);
 #undef EEC_LEX_LAUNCH
-  return (int)e;
+  return e == hipSuccess ? 0 : eech::hip_fail(e, "eec_lexicon_nearest launch");
 }
 
 }  // extern "C"

@@ -18,32 +18,12 @@
 
 #include "../../include/eec.h"
 #include "eec_kernels.h"
-#include "eec_train.h"
+#include "eec_train_host.h"
 
 using namespace eect;
+using namespace eech;
 
 namespace {
-
-thread_local std::string g_terr;
-int tfail(int code, const std::string& msg) {
-  g_terr = msg;
-  return code;
-}
-
-struct Bump {  // bump allocator; base == nullptr: sizes only
-  char* base = nullptr;
-  size_t off = 0, peak = 0, cap = ~(size_t)0;
-  bool overflow = false;
-  float* f(size_t n) {
-    off = (off + 255) / 256 * 256;
-    float* p = (float*)(base + off);
-    off += n * sizeof(float);
-    if (off > peak) peak = off;
-    if (off > cap) overflow = true;  // checked by the entry points before anything is reported as done
-    return p;
-  }
-  void reset(size_t to = 0) { off = to; }
-};
 
 struct FfnTape {
   float *x, *ln, *mean, *rstd, *pre, *act;
@@ -100,30 +80,23 @@ struct eec_trainer {
 
 namespace {
 
-struct Run {
+struct Run : TrainRun {
   eec_trainer* tr;
-  bool dry;
-  hipStream_t st;
-  Bump tape, scr, sscr;  // sscr: scratch of the side stream (split-K partials), never shared with the main stream's
+  Bump tape, sscr;  // sscr: scratch of the side stream (split-K partials), never shared with the main stream's (scr)
   hipStream_t side = nullptr;
   bool side_busy = false;
-  hipError_t err = hipSuccess;
-  const char* where = "";
   uint32_t site = 1;
-  void ok(hipError_t e, const char* w) {
-    if (e != hipSuccess && err == hipSuccess) err = e, where = w;
+  Run(eec_trainer* tr_, bool dry_, hipStream_t st_) : TrainRun(dry_, st_, tr_->np), tr(tr_) {}
+  // Lays the regions over a workspace in their fixed order, from `skip` bytes in: [tape][side-stream scratch][main scratch];
+  // the main scratch takes what is left.  The entries differ only in the sizes they pass.
+  void place(void* workspace, size_t workspace_bytes, size_t skip, size_t tape_bytes, size_t side_bytes) {
+    char* p = (char*)workspace + skip;
+    tape.base = p, tape.cap = tape_bytes;
+    sscr.base = p + tape_bytes, sscr.cap = side_bytes;
+    scr.base = p + tape_bytes + side_bytes, scr.cap = workspace_bytes - skip - tape_bytes - side_bytes;
   }
 };
-#define RUN(expr)                      \
-  do {                                 \
-    if (!r.dry) r.ok((expr), #expr);   \
-  } while (0)
-int finish(const Run& r) {
-  if (r.tape.overflow || r.scr.overflow || r.sscr.overflow) return tfail(EEC_ERR_WORKSPACE, "internal: workspace carve exceeded its size");
-  if (r.err != hipSuccess) return tfail((int)r.err, std::string(r.where) + ": " + hipGetErrorString(r.err));
-  return 0;
-}
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+int finish(const Run& r) { return eech::finish(r, r.tape.overflow || r.scr.overflow || r.sscr.overflow); }
 
 Drop drop_of(const Run& r, uint32_t site) { return Drop{r.tr->p, r.tr->seed, site}; }
 
@@ -151,23 +124,11 @@ void bwd_scratch_reset(Run& r) {
   r.scr.reset();
 }
 
-// y[M][N] = x[M][K] . W[N][K]^T + bias
-void linear_fwd(Run& r, const float* x, const float* W, const float* bias, float* y, int M, int N, int K) {
-  GemmArgs g = gemm_args(x, K, 1, W, K, 1, y, N, M, N, K);
-  g.bias = bias;
-  RUN(launch_gemm(g, r.tr->np, r.st));
-}
 // y[M][N] = r + scale * drop(x[M][K] . W[N][K]^T + bias): a sub-module's last Linear with its residual connection
 void linear_residual_fwd(Run& r, const float* x, const float* W, const float* bias, const float* res, float scale, uint32_t site, float* y, int M,
                          int N, int K) {
   GemmArgs g = gemm_args(x, K, 1, W, K, 1, y, N, M, N, K);
   g.bias = bias, g.epi = 4, g.aux = res, g.res_scale = scale, g.drop = drop_of(r, site);
-  RUN(launch_gemm(g, r.tr->np, r.st));
-}
-// dx[M][K] (+)= dy[M][N] . W[N][K]
-void linear_bwd_data(Run& r, const float* dy, const float* W, float* dx, int M, int N, int K, bool accumulate = false) {
-  GemmArgs g = gemm_args(dy, N, 1, W, 1, K, dx, K, M, K, N);
-  g.accumulate = accumulate;
   RUN(launch_gemm(g, r.tr->np, r.st));
 }
 // dW[N][K] = dy[M][N]^T . x[M][K] (split over the rows, partials summed in a fixed order); db[N] = column sums of dy
@@ -201,17 +162,6 @@ void linear_bwd_weight(Run& r, const float* dy, const float* x, float* dW, float
   }
   side_end(r);
 }
-// dx = dx + LN'(dln) in place; dg / db from the per-block partials
-void ln_bwd(Run& r, const float* dln, const float* x, const float* g, const float* mean, const float* rstd, float* dx, bool add_res, float* dg,
-            float* db, int M, int D) {
-  const size_t mark = r.scr.off;
-  const int nb = ln_bwd_blocks(M);
-  float* part = r.scr.f((size_t)nb * 2 * D);
-  RUN(launch_ln_bwd(dln, x, g, mean, rstd, add_res ? dx : nullptr, dx, part, M, D, r.st));
-  RUN(launch_reduce_leading2(part, nb, D, dg, db, r.st));
-  r.scr.reset(mark);
-}
-
 // ---- forward ---------------------------------------------------------------------------------------------------------
 // the feed-forward module as one launch per direction where the configuration allows it; EEC_TRAIN_FFN_FUSED=0 / EEC_TRAIN_FFN_FUSED_BWD=0
 // keep the LayerNorm + two-GEMM path (A/B runs, and what other geometries take).  Either way the tape has the same layout.
@@ -655,39 +605,39 @@ void backward(Run& r, const eec_params* P, const eec_params* Gp, const float* ou
 }
 
 int check_trainer_cfg(const eec_config& c) {
-  if (c.arch != EEC_ARCH_CONFORMER) return tfail(EEC_ERR_UNSUPPORTED, "the training step covers the Conformer architecture");
-  if (c.d_model <= 0 || c.d_model > 1024 || c.n_heads <= 0 || c.d_model % c.n_heads) return tfail(EEC_ERR_BAD_ARG, "d_model <= 1024, divisible by n_heads");
-  if (c.dw_kernel < 1 || c.dw_kernel > 31 || !(c.dw_kernel & 1)) return tfail(EEC_ERR_BAD_ARG, "depthwise kernel: odd, <= 31");
-  if (c.d_ff <= 0 || c.n_exits <= 0 || c.layers_per_exit <= 0 || c.n_mels <= 0 || c.vocab <= 0) return tfail(EEC_ERR_BAD_ARG, "bad configuration");
+  if (c.arch != EEC_ARCH_CONFORMER) return fail(EEC_ERR_UNSUPPORTED, "the training step covers the Conformer architecture");
+  if (c.d_model <= 0 || c.d_model > 1024 || c.n_heads <= 0 || c.d_model % c.n_heads) return fail(EEC_ERR_BAD_ARG, "d_model <= 1024, divisible by n_heads");
+  if (c.dw_kernel < 1 || c.dw_kernel > 31 || !(c.dw_kernel & 1)) return fail(EEC_ERR_BAD_ARG, "depthwise kernel: odd, <= 31");
+  if (c.d_ff <= 0 || c.n_exits <= 0 || c.layers_per_exit <= 0 || c.n_mels <= 0 || c.vocab <= 0) return fail(EEC_ERR_BAD_ARG, "bad configuration");
   // the log-softmax backward and the CTC gradient hold a vocabulary row in one wave (csrc/ctc.hip): refuse here, before a
   // forward has recorded a multi-GB tape that loss.backward() could not use
-  if (c.vocab > 256 || c.vocab % 4) return tfail(EEC_ERR_UNSUPPORTED, "the training step needs vocab <= 256 and a multiple of 4 (got " + std::to_string(c.vocab) + ")");
+  if (c.vocab > 256 || c.vocab % 4) return fail(EEC_ERR_UNSUPPORTED, "the training step needs vocab <= 256 and a multiple of 4 (got " + std::to_string(c.vocab) + ")");
   return 0;
 }
 
 int set_geometry(eec_trainer* tr, int B, int T) {
-  if (B <= 0 || T < 7) return tfail(EEC_ERR_BAD_ARG, "B >= 1, T >= 7");
+  if (B <= 0 || T < 7) return fail(EEC_ERR_BAD_ARG, "B >= 1, T >= 7");
   tr->B = B, tr->T = T, tr->T1 = (T - 3) / 2 + 1, tr->Tq = (tr->T1 - 3) / 2 + 1, tr->M = B * tr->Tq;
-  if (tr->Tq > tr->cfg.max_len) return tfail(EEC_ERR_BAD_ARG, "T' exceeds max_len");
+  if (tr->Tq > tr->cfg.max_len) return fail(EEC_ERR_BAD_ARG, "T' exceeds max_len");
   return 0;
 }
 
 int block_trainer(eec_trainer& tr, const eec_config* cfg, int B, int Tq, int passes, float drop_prob, uint64_t seed, const int32_t* key_len) {
-  if (!cfg) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (!cfg) return fail(EEC_ERR_BAD_ARG, "null argument");
   if (int rc = check_trainer_cfg(*cfg)) return rc;
-  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
-  if (B <= 0 || Tq <= 0 || Tq > cfg->max_len) return tfail(EEC_ERR_BAD_ARG, "B >= 1, 1 <= T' <= max_len");
+  if (int rc = check_passes(passes)) return rc;
+  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return fail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
+  if (B <= 0 || Tq <= 0 || Tq > cfg->max_len) return fail(EEC_ERR_BAD_ARG, "B >= 1, 1 <= T' <= max_len");
   tr.cfg = *cfg;
   tr.B = B, tr.Tq = Tq, tr.M = B * Tq, tr.np = passes, tr.p = drop_prob, tr.seed = seed, tr.key_len = (int32_t*)key_len;
   read_ffn_switches(tr);
   return 0;
 }
 int stem_geo(StemGeo& g, const eec_config* cfg, int B, int T, int two) {
-  if (!cfg || B <= 0 || T < (two ? 7 : 3)) return tfail(EEC_ERR_BAD_ARG, "B >= 1 and T >= 3 (one convolution) / 7 (two)");
+  if (!cfg || B <= 0 || T < (two ? 7 : 3)) return fail(EEC_ERR_BAD_ARG, "B >= 1 and T >= 3 (one convolution) / 7 (two)");
   const int T1 = (T - 3) / 2 + 1;
   g = StemGeo{B, cfg->n_mels, T, T1, two ? (T1 - 3) / 2 + 1 : T1, cfg->d_model, two != 0};
-  if (g.To > cfg->max_len) return tfail(EEC_ERR_BAD_ARG, "output frames exceed max_len");
+  if (g.To > cfg->max_len) return fail(EEC_ERR_BAD_ARG, "output frames exceed max_len");
   return 0;
 }
 
@@ -752,10 +702,10 @@ size_t stem_workspace(const Sizes& z) { return up256(z.tape) + up256(z.side) + u
 
 extern "C" {
 
-const char* eec_trainer_last_error(void) { return g_terr.c_str(); }
+const char* eec_trainer_last_error(void) { return g_err.c_str(); }
 
 int eec_trainer_create(const eec_config* cfg, eec_trainer** out) {
-  if (!cfg || !out) return tfail(EEC_ERR_BAD_ARG, "null argument");
+  if (!cfg || !out) return fail(EEC_ERR_BAD_ARG, "null argument");
   if (int rc = check_trainer_cfg(*cfg)) return rc;
   eec_trainer* tr = new eec_trainer();
   tr->cfg = *cfg;
@@ -782,22 +732,21 @@ size_t eec_trainer_workspace_bytes(const eec_trainer* tr_in, int B, int T) {
 int eec_train_forward(eec_trainer* tr, const eec_params* params, const float* mel, const int64_t* lengths, int B, int T, int passes,
                       float drop_prob, uint64_t seed, float* out, float* taps, float* bn_batch_stats, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (!tr || !params || !mel || !lengths || !out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (passes != 1 && passes != 3) return tfail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
-  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return tfail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
+  if (!tr || !params || !mel || !lengths || !out || !workspace) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_passes(passes)) return rc;
+  if (!(drop_prob >= 0.0f && drop_prob < 1.0f)) return fail(EEC_ERR_BAD_ARG, "drop_prob in [0, 1)");
   int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return tfail(EEC_ERR_BAD_ARG, "no current HIP device");
+  if (hipGetDevice(&dev) != hipSuccess) return fail(EEC_ERR_BAD_ARG, "no current HIP device");
   if (tr->device < 0) tr->device = dev;
-  if (dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
+  if (dev != tr->device) return fail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
   if (int rc = set_geometry(tr, B, T)) return rc;
   tr->np = passes, tr->p = drop_prob, tr->seed = seed, tr->recorded = false;
   read_ffn_switches(*tr);
   const Sizes z = model_plan(*tr);
-  if (workspace_bytes < model_workspace(z)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
+  if (workspace_bytes < model_workspace(z)) return fail(EEC_ERR_BAD_ARG, "workspace too small");
   tr->tape_bytes = up256(z.tape);
   Run r{tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace, r.tape.cap = tr->tape_bytes;
-  r.scr.base = (char*)workspace + tr->tape_bytes, r.scr.cap = workspace_bytes - tr->tape_bytes;
+  r.place(workspace, workspace_bytes, 0, tr->tape_bytes, 0);
   forward(r, params, mel, lengths, out, bn_batch_stats, taps);
   if (int rc = finish(r)) return rc;
   tr->recorded = true;
@@ -812,13 +761,13 @@ int eec_train_backward(eec_trainer* tr, const eec_params* params, const eec_para
 int eec_train_backward_ex(eec_trainer* tr, const eec_params* params, const eec_params* grads, const float* out, const float* grad_out,
                           const float* grad_taps, void* workspace, size_t workspace_bytes, void* stream, eec_group_done_fn on_group,
                           void* user) {
-  if (!tr || !params || !grads || !out || !grad_out || !workspace) return tfail(EEC_ERR_BAD_ARG, "null argument");
-  if (!tr->recorded) return tfail(EEC_ERR_BAD_ARG, "no recorded forward (eec_train_forward first, same workspace)");
+  if (!tr || !params || !grads || !out || !grad_out || !workspace) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (!tr->recorded) return fail(EEC_ERR_BAD_ARG, "no recorded forward (eec_train_forward first, same workspace)");
   int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != tr->device) return tfail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
+  if (hipGetDevice(&dev) != hipSuccess || dev != tr->device) return fail(EEC_ERR_BAD_ARG, "the trainer belongs to another device");
   read_ffn_switches(*tr);
   const Sizes z = model_plan(*tr);
-  if (workspace_bytes < model_workspace(z)) return tfail(EEC_ERR_BAD_ARG, "workspace too small");
+  if (workspace_bytes < model_workspace(z)) return fail(EEC_ERR_BAD_ARG, "workspace too small");
   const char* no_side = getenv("EEC_TRAIN_NO_SIDE");  // diagnostic: every job on the main stream (results are bit-identical)
   const bool use_side = !(no_side && no_side[0] == '1');
   if (use_side && !tr->side) {  // a failure here only means the jobs run on the main stream
@@ -832,11 +781,7 @@ int eec_train_backward_ex(eec_trainer* tr, const eec_params* params, const eec_p
   Run r{tr, false, (hipStream_t)stream};
   if (use_side) r.side = tr->side;
   // [tape][dx][side-stream scratch][main scratch]; the residual-stream gradient is carved through `tape`, kept for the whole backward
-  const size_t dx_bytes = up256(z.dx + 256), side_bytes = up256(z.side);
-  char* base = (char*)workspace + tr->tape_bytes;
-  r.tape.base = base, r.tape.cap = dx_bytes;
-  r.sscr.base = base + dx_bytes, r.sscr.cap = side_bytes;
-  r.scr.base = base + dx_bytes + side_bytes, r.scr.cap = workspace_bytes - tr->tape_bytes - dx_bytes - side_bytes;
+  r.place(workspace, workspace_bytes, tr->tape_bytes, up256(z.dx + 256), up256(z.side));
   backward(r, params, grads, out, grad_out, grad_taps, on_group, user);
   return finish(r);
 }
@@ -850,17 +795,15 @@ size_t eec_train_group_workspace_bytes(const eec_config* cfg, int n_layers, int 
 int eec_train_group_forward(const eec_config* cfg, const eec_layer_params* layers, int n_layers, const float* x_in, const int32_t* key_len, int B,
                             int Tq, int passes, float drop_prob, uint64_t seed, uint32_t site_base, float* x_out, float* bn_batch_stats,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  if (!layers || !x_in || !key_len || !x_out || !workspace || n_layers <= 0 || n_layers > 64) return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (!layers || !x_in || !key_len || !x_out || !workspace || n_layers <= 0 || n_layers > 64) return fail(EEC_ERR_BAD_ARG, "bad argument");
+  if (int rc = check_workspace(workspace, workspace_bytes, 0)) return rc;  // alignment; the size follows the geometry checks
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, Tq, passes, drop_prob, seed, key_len)) return rc;
   const Sizes z = group_plan(tr, n_layers);
-  if (workspace_bytes < group_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
-  const size_t tape = up256(z.tape);
+  if (int rc = check_workspace(workspace, workspace_bytes, group_workspace(z))) return rc;
   Run r{&tr, false, (hipStream_t)stream};
   r.site = site_base;
-  r.tape.base = (char*)workspace, r.tape.cap = tape;
-  r.scr.base = (char*)workspace + tape, r.scr.cap = workspace_bytes - tape;
+  r.place(workspace, workspace_bytes, 0, up256(z.tape), 0);
   group_forward(r, layers, n_layers, x_in, x_out, bn_batch_stats);
   return finish(r);
 }
@@ -869,24 +812,20 @@ int eec_train_group_backward(const eec_config* cfg, const eec_layer_params* laye
                              const int32_t* key_len, int B, int Tq, int passes, float drop_prob, uint64_t seed, uint32_t site_base,
                              const float* grad_out, float* grad_in, void* workspace, size_t workspace_bytes, void* stream) {
   if (!layers || !grads || !x_in || !key_len || !grad_out || !grad_in || !workspace || n_layers <= 0 || n_layers > 64)
-    return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    return fail(EEC_ERR_BAD_ARG, "bad argument");
+  if (int rc = check_workspace(workspace, workspace_bytes, 0)) return rc;  // alignment; the size follows the geometry checks
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, Tq, passes, drop_prob, seed, key_len)) return rc;
   const Sizes z = group_plan(tr, n_layers);
-  if (workspace_bytes < group_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
+  if (int rc = check_workspace(workspace, workspace_bytes, group_workspace(z))) return rc;
   {  // the recorded tape's pointers: the forward's carve again, without launches
     Run d{&tr, true, nullptr};
     d.site = site_base;
     d.tape.base = (char*)workspace;
     group_forward(d, layers, n_layers, x_in, nullptr, nullptr);
   }
-  const size_t tape = up256(z.tape), dx = up256(z.dx), side = up256(z.side);
   Run r{&tr, false, (hipStream_t)stream};
-  char* base = (char*)workspace + tape;
-  r.tape.base = base, r.tape.cap = dx;
-  r.sscr.base = base + dx, r.sscr.cap = side;
-  r.scr.base = base + dx + side, r.scr.cap = workspace_bytes - tape - dx - side;
+  r.place(workspace, workspace_bytes, up256(z.tape), up256(z.dx), up256(z.side));
   group_backward(r, layers, grads, n_layers, grad_out, grad_in);
   return finish(r);
 }
@@ -901,18 +840,16 @@ size_t eec_train_stem_workspace_bytes(const eec_config* cfg, int B, int T, int t
 int eec_train_stem_forward(const eec_config* cfg, const float* sub0_w, const float* sub0_b, const float* sub1_w, const float* sub1_b,
                            const float* pe, const float* mel, int B, int T, int passes, float drop_prob, uint64_t seed, uint32_t site, float* x_out,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (!sub0_w || !sub0_b || !pe || !mel || !x_out || !workspace || (sub1_w != nullptr) != (sub1_b != nullptr)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (!sub0_w || !sub0_b || !pe || !mel || !x_out || !workspace || (sub1_w != nullptr) != (sub1_b != nullptr)) return fail(EEC_ERR_BAD_ARG, "bad argument");
+  if (int rc = check_workspace(workspace, workspace_bytes, 0)) return rc;  // alignment; the size follows the geometry checks
   StemGeo g;
   if (int rc = stem_geo(g, cfg, B, T, sub1_w != nullptr)) return rc;
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, g.To, passes, drop_prob, seed, nullptr)) return rc;
   const Sizes z = stem_plan(tr, g);
-  if (workspace_bytes < stem_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
-  const size_t tape = up256(z.tape);
+  if (int rc = check_workspace(workspace, workspace_bytes, stem_workspace(z))) return rc;
   Run r{&tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace, r.tape.cap = tape;
-  r.scr.base = (char*)workspace + tape, r.scr.cap = workspace_bytes - tape;
+  r.place(workspace, workspace_bytes, 0, up256(z.tape), 0);
   stem_forward(r, g, stem_carve(r.tape, g), sub0_w, sub0_b, sub1_w, sub1_b, pe, mel, x_out, site);
   return finish(r);
 }
@@ -920,26 +857,23 @@ int eec_train_stem_forward(const eec_config* cfg, const float* sub0_w, const flo
 int eec_train_stem_backward(const eec_config* cfg, int two_convs, int B, int T, int passes, float drop_prob, uint64_t seed, uint32_t site,
                             const float* grad_x, float* g_sub0_w, float* g_sub0_b, float* g_sub1_w, float* g_sub1_b, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  if (!grad_x || !g_sub0_w || !g_sub0_b || !workspace || (two_convs && (!g_sub1_w || !g_sub1_b))) return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  if (((uintptr_t)workspace & 255) != 0) return tfail(EEC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  if (!grad_x || !g_sub0_w || !g_sub0_b || !workspace || (two_convs && (!g_sub1_w || !g_sub1_b))) return fail(EEC_ERR_BAD_ARG, "bad argument");
+  if (int rc = check_workspace(workspace, workspace_bytes, 0)) return rc;  // alignment; the size follows the geometry checks
   StemGeo g;
   if (int rc = stem_geo(g, cfg, B, T, two_convs)) return rc;
   eec_trainer tr;
   if (int rc = block_trainer(tr, cfg, B, g.To, passes, drop_prob, seed, nullptr)) return rc;
   const Sizes z = stem_plan(tr, g);
-  if (workspace_bytes < stem_workspace(z)) return tfail(EEC_ERR_WORKSPACE, "workspace too small");
-  const size_t tape = up256(z.tape), side = up256(z.side);
+  if (int rc = check_workspace(workspace, workspace_bytes, stem_workspace(z))) return rc;
   Run r{&tr, false, (hipStream_t)stream};
-  r.tape.base = (char*)workspace, r.tape.cap = tape;
-  r.sscr.base = (char*)workspace + tape, r.sscr.cap = side;
-  r.scr.base = (char*)workspace + tape + side, r.scr.cap = workspace_bytes - tape - side;
+  r.place(workspace, workspace_bytes, 0, up256(z.tape), up256(z.side));
   stem_backward(r, g, stem_carve(r.tape, g), grad_x, g_sub0_w, g_sub0_b, g_sub1_w, g_sub1_b, site);
   return finish(r);
 }
 
 /* exit head: logp = log_softmax(x . W^T + b); scratch = M * V floats */
 int eec_train_head_forward(const float* x, const float* W, const float* b, int M, int V, int D, int passes, float* logp, float* scratch, void* stream) {
-  if (!x || !W || !b || !logp || !scratch || M <= 0 || V <= 0 || D <= 0 || (passes != 1 && passes != 3)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
+  if (!x || !W || !b || !logp || !scratch || M <= 0 || V <= 0 || D <= 0 || (passes != 1 && passes != 3)) return fail(EEC_ERR_BAD_ARG, "bad argument");
   eec_trainer tr{};
   tr.np = passes;
   Run r{&tr, false, (hipStream_t)stream};
@@ -956,12 +890,12 @@ size_t eec_train_head_backward_scratch_floats(int M, int V, int D) {
 }
 int eec_train_head_backward(const float* x, const float* W, const float* logp, const float* grad_logp, int M, int V, int D, int passes, float* dx,
                             float* dW, float* db, float* scratch, void* stream) {
-  if (!x || !W || !logp || !grad_logp || !dW || !db || !scratch || M <= 0 || D <= 0 || (passes != 1 && passes != 3)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
-  if (V <= 0 || V > 256 || V % 4) return tfail(EEC_ERR_UNSUPPORTED, "the log-softmax backward needs vocab <= 256, a multiple of 4");
+  if (!x || !W || !logp || !grad_logp || !dW || !db || !scratch || M <= 0 || D <= 0 || (passes != 1 && passes != 3)) return fail(EEC_ERR_BAD_ARG, "bad argument");
+  if (V <= 0 || V > 256 || V % 4) return fail(EEC_ERR_UNSUPPORTED, "the log-softmax backward needs vocab <= 256, a multiple of 4");
   eec_trainer tr{};
   tr.np = passes;
   Run r{&tr, false, (hipStream_t)stream};
-  r.scr.base = (char*)scratch;
+  r.scr.base = (char*)scratch;  // the head's scratch is [dlogits][side-stream partials]: the other way round from place()
   r.sscr.base = (char*)(scratch + (((size_t)M * V + 63) / 64) * 64);
   head_bwd(r, x, W, logp, grad_logp, dx, false, dW, db, M, V, D);
   return finish(r);
@@ -969,11 +903,11 @@ int eec_train_head_backward(const float* x, const float* W, const float* logp, c
 
 int eec_train_gemm(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, int passes, int a_transposed,
                    int b_transposed, void* stream) {
-  if (!A || !B || !C || (passes != 1 && passes != 3)) return tfail(EEC_ERR_BAD_ARG, "bad argument");
+  if (!A || !B || !C || (passes != 1 && passes != 3)) return fail(EEC_ERR_BAD_ARG, "bad argument");
   // a_transposed: A is stored [K][M]; b_transposed: B is stored [K][N]
   GemmArgs g = gemm_args(A, a_transposed ? 1 : K, a_transposed ? M : 1, B, b_transposed ? 1 : K, b_transposed ? N : 1, C, N, M, N, K);
   g.bias = bias;
-  if (hipError_t e = launch_gemm(g, passes, (hipStream_t)stream); e != hipSuccess) return tfail((int)e, hipGetErrorString(e));
+  EEC_HIP(launch_gemm(g, passes, (hipStream_t)stream));
   return 0;
 }
 

@@ -4,17 +4,13 @@ autograd (csrc/decoder_train.hip)."""
 from __future__ import annotations
 
 import ctypes as C
-from functools import partial
 from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import capi
-from .capi import aligned_ws, stream_ptr
-
-_step_check = partial(capi.check, err="eec_decoder_step_last_error")
-_train_check = partial(capi.check, err="eec_decoder_train_last_error")
+from .capi import aligned_ws, check as _check, stream_ptr
 
 
 def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old: Tensor, tokens_new: Tensor, length: int):
@@ -36,9 +32,9 @@ def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old
     parent = torch.empty((n, k), dtype=torch.int64, device=dev)
     tok = torch.empty((n, k), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _step_check(capi.load().eec_beam_select(n, R, V, int(k), logp.contiguous().data_ptr(), scores.contiguous().data_ptr(), float(penalty),
-                                                out_s.data_ptr(), parent.data_ptr(), tok.data_ptr(), tokens_old.data_ptr(), tokens_new.data_ptr(),
-                                                int(length), tokens_old.size(2), tokens_old.size(1), stream_ptr(dev)), "eec_beam_select")
+        _check(capi.load().eec_beam_select(n, R, V, int(k), logp.contiguous().data_ptr(), scores.contiguous().data_ptr(), float(penalty),
+                                           out_s.data_ptr(), parent.data_ptr(), tok.data_ptr(), tokens_old.data_ptr(), tokens_new.data_ptr(),
+                                           int(length), tokens_old.size(2), tokens_old.size(1), stream_ptr(dev)), "eec_beam_select")
     return out_s, parent, tok
 
 
@@ -69,7 +65,7 @@ class DecoderStepSession:
             self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
             for i, enc in enumerate(encs):
                 enc_c = enc.contiguous().float()
-                _step_check(self._begin(lib, i, enc_c.data_ptr(), passes, stream_ptr(self.dev)), self.entry + "begin")
+                _check(self._begin(lib, i, enc_c.data_ptr(), passes, stream_ptr(self.dev)), self.entry + "begin")
                 enc_c.record_stream(stream)
                 self._caches[i][0].record_stream(stream)
 
@@ -91,8 +87,8 @@ class DecoderStepSession:
             par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
             out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
             stream = torch.cuda.current_stream(dev)
-            _step_check(self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
-                                   stream_ptr(dev)), self.entry + "step")
+            _check(self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
+                              stream_ptr(dev)), self.entry + "step")
             tok.record_stream(stream)
             if par is not None:
                 par.record_stream(stream)
@@ -161,9 +157,9 @@ class _DecoderTrainFn(torch.autograd.Function):
             ws, ws_ptr = aligned_ws(nbytes, dev)
             out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
             geo = (cfg.d_model, cfg.n_heads, d_ff, V)
-            _train_check(lib.eec_decoder_train_forward(C.byref(ps), *geo, int(model.trg_pad_idx), trg.data_ptr(), enc.data_ptr(), Bm, S, Tq,
-                                                       int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out.data_ptr(), ws_ptr,
-                                                       nbytes, stream_ptr(dev)), "eec_decoder_train_forward")
+            _check(lib.eec_decoder_train_forward(C.byref(ps), *geo, int(model.trg_pad_idx), trg.data_ptr(), enc.data_ptr(), Bm, S, Tq,
+                                                 int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out.data_ptr(), ws_ptr,
+                                                 nbytes, stream_ptr(dev)), "eec_decoder_train_forward")
         ctx.model, ctx.idx, ctx.names, ctx.seed, ctx.geo = model, idx, names, int(seed), geo
         ctx.ws, ctx.ws_ptr, ctx.nbytes, ctx.drop, ctx.passes = ws, ws_ptr, nbytes, float(model.dropout), int(model.decoder_passes)
         ctx.save_for_backward(trg, enc, *params)
@@ -187,9 +183,9 @@ class _DecoderTrainFn(torch.autograd.Function):
             grads = {k: torch.empty_like(v) for k, v in tensors.items()}
             gs, gkeep = model._decoder_struct(idx, grads, with_pe=False)
             g_enc = torch.empty_like(enc)
-            _train_check(lib.eec_decoder_train_backward(C.byref(ps), C.byref(gs), *ctx.geo, trg.data_ptr(), enc.data_ptr(), Bm, S, Tq, ctx.passes,
-                                                        ctx.drop, ctx.seed, int(idx), g.data_ptr(), g_enc.data_ptr(), ctx.ws_ptr, ctx.nbytes,
-                                                        stream_ptr(dev)), "eec_decoder_train_backward")
+            _check(lib.eec_decoder_train_backward(C.byref(ps), C.byref(gs), *ctx.geo, trg.data_ptr(), enc.data_ptr(), Bm, S, Tq, ctx.passes,
+                                                  ctx.drop, ctx.seed, int(idx), g.data_ptr(), g_enc.data_ptr(), ctx.ws_ptr, ctx.nbytes,
+                                                  stream_ptr(dev)), "eec_decoder_train_backward")
         ctx.ws = None
         need = ctx.needs_input_grad[6:]
         return (None, None, None, g_enc if ctx.needs_input_grad[3] else None, None, None,

@@ -41,7 +41,7 @@ class MelFrontend:
             h = C.c_void_p()
             with torch.cuda.device(device):
                 rc = lib.eec_frontend_create(self.sample_rate, 2 * self.n_fft, self.win_length, self.hop_length, self.n_mels, C.byref(h))
-            capi.check(rc, "eec_frontend_create", "eec_frontend_last_error")
+            capi.check(rc, "eec_frontend_create")
             self._fe, self._device = h, device
         return self._fe
 
@@ -63,6 +63,6 @@ class MelFrontend:
             fe = self._handle(dev)
             rc = capi.load().eec_frontend_forward(fe, wave.data_ptr(), len_dev.data_ptr() if len_dev is not None else None, B, L,
                                                   mel.data_ptr(), capi.stream_ptr(dev))
-            capi.check(rc, "eec_frontend_forward", "eec_frontend_last_error")
+            capi.check(rc, "eec_frontend_forward")
             wave.record_stream(torch.cuda.current_stream(dev))
         return mel[0] if squeeze else mel

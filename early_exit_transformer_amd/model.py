@@ -594,7 +594,7 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             rc = lib.eec_decoder_forward(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), trg_c.data_ptr(),
                                          enc_c.data_ptr(), Bm, S, Tq, int(shared), int(self.decoder_passes), int(log_softmax), out.data_ptr(),
                                          ws_ptr, nbytes, stream_ptr(dev))
-            capi.check(rc, "eec_decoder_forward", "eec_decoder_last_error")
+            capi.check(rc, "eec_decoder_forward")
             for t in (ws, trg_c, enc_c):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out

@@ -6,16 +6,14 @@ from __future__ import annotations
 
 import ctypes as C
 import operator
-from functools import partial
 from typing import List, Sequence
 
 import torch
 from torch import Tensor, nn
 
 from . import capi
-from .capi import aligned_ws, stream_ptr, to_device
+from .capi import aligned_ws, check as _check, stream_ptr, to_device
 
-_check = partial(capi.check, err="eec_trainer_last_error")
 _GROUP_FIELDS = [f for f in capi._LAYER_FIELDS if f not in ("conv_bn_rm", "conv_bn_rv")]  # the 30 trainable tensors of a ConformerLayer
 
 

@@ -8,8 +8,11 @@
  * reference code it replaces.  Plain pointers and sizes only: all `const float*`,
  * `void* workspace` etc. are DEVICE pointers (HIP), `stream` is a hipStream_t passed as
  * void*.  Every function returns 0 on success, a non-zero hipError_t / EEC_ERR_* code
- * otherwise; eec_last_error() returns a thread-local message.  No entry point allocates,
- * frees or synchronises the device except create/destroy/pack.
+ * otherwise, and every non-zero return leaves its reason in one thread-local message.
+ * eec_last_error() and the eec_*_last_error() of the other families all return that one
+ * string: the calling thread's most recent message, whichever family the failing call
+ * belonged to.  No entry point allocates, frees or synchronises the device except
+ * create/destroy/pack.
  *
  * Devices: an eec_encoder handle belongs to the HIP device that was current in eec_encoder_create (its packed-weight
  * arena is a plain allocation on that device).  Every later call on the handle must be made with the same device

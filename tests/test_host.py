@@ -99,6 +99,45 @@ def test_decoder_step_cache_sizing_and_argument_checks(lib):
     assert rc != 0 and b"null" in lib.eec_decoder_step_last_error()
 
 
+def _decoder_null_failure(lib):
+    """A known message on the library's error string: eec_decoder_forward with null pointers."""
+    ps = capi.EecDecoderParams()
+    rc = lib.eec_decoder_forward(C.byref(ps), 256, 8, 2048, 256, 126, None, None, 1, 1, 1, 0, 3, 1, None, None, 0, None)
+    assert rc != 0
+    msg = lib.eec_last_error()
+    assert b"null" in msg
+    return msg
+
+
+def test_every_failing_entry_leaves_a_fresh_message(lib):
+    """The CTC beam / alignment, lexicon and front-end entries reject these calls before any device work, and each leaves its
+    own reason behind eec_last_error(), never the text of an earlier, unrelated failure."""
+    buf = (C.c_int32 * 64)()
+    fe = C.c_void_p()
+    calls = {
+        "eec_ctc_beam_decode": lambda: lib.eec_ctc_beam_decode(None, 1, 4, 32, 0, 4, 0.0, buf, buf, buf, buf, None),  # null logp
+        "eec_ctc_align": lambda: lib.eec_ctc_align(buf, 1, 0, 32, buf, buf, buf, None, 1, 4, 0, buf, buf, buf, buf, buf, None, None, None),  # Tq = 0
+        "eec_lexicon_nearest": lambda: lib.eec_lexicon_nearest(buf, 0, buf, buf, 1, 4, buf, buf, buf, 256, None),  # n_words = 0
+        "eec_lexicon_pack": lambda: lib.eec_lexicon_pack(buf, None, 1, buf, 256, buf, None),  # null offsets
+        "eec_frontend_create": lambda: lib.eec_frontend_create(16000, 1024, 400, 160, 80, C.byref(fe)),  # window 400
+    }
+    for name, call in calls.items():
+        stale = _decoder_null_failure(lib)
+        rc = call()
+        msg = lib.eec_last_error()
+        assert rc != 0, name
+        assert msg and msg != stale, (name, msg)
+    assert not fe.value
+
+
+def test_one_error_string_behind_all_last_error_symbols(lib):
+    """Every eec_*_last_error() returns the calling thread's most recent message, whichever family the failing call was in."""
+    ps = capi.EecDecoderParams()
+    assert lib.eec_decoder_begin(C.byref(ps), 256, 8, 2048, 256, None, 256, 40, 3, None, 0, None) != 0
+    msgs = [getattr(lib, name)() for name in capi.EXPORTS if name.endswith("last_error")]
+    assert len(msgs) == 6 and len(set(msgs)) == 1 and b"null" in msgs[0]
+
+
 def test_out_frames_matches_conv_arithmetic(lib):
     for T in (7, 8, 10, 11, 131, 1027, 2051, 8003):
         t1 = (T - 3) // 2 + 1
