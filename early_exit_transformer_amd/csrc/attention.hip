@@ -18,7 +18,6 @@
 namespace eec {
 
 constexpr int kKC = 256;  // keys staged in LDS per chunk
-constexpr float kNegBig = -1.0e30f;
 
 template <int DH>
 struct AttnLds {

@@ -524,12 +524,9 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
       te = tm > 0.f ? ec : kCtcWideEmpty;
     }
   }
-  int e_max = te;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) e_max = max(e_max, __shfl_xor(e_max, off, 64));
+  const int e_max = wave_all_max(te);
   float total = ldexpf(tm, max(te - e_max, -64));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
+  total = wave_all_sum(total);
   float mt;
   int et;
   ctc_wide_norm(total, e_max, mt, et);
@@ -785,7 +782,7 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
   float tl = 0.f;
 #pragma unroll
   for (int i = 0; i < P; ++i) tl += ldexpf(tm[i], max(te[i] - e_lane, -64));
-  int e_max = e_lane;
+  int e_max = e_lane;  // (written out: through wave_all_max / wave_all_sum this kernel's registers are allocated differently)
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) e_max = max(e_max, __shfl_xor(e_max, off, 64));
   float total = ldexpf(tl, max(e_lane - e_max, -64));

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
       if (bv == -INFINITY) bid = INT_MAX;
       const float wm = wave_max(bv);
       int cand = (bv == wm && wm > -INFINITY) ? bid : INT_MAX;
-      // lowest id among the lanes that hold the wave maximum
+      // lowest id among the lanes that hold the wave maximum (written out: as a shared eec_wave.h function its last exchange is scheduled elsewhere)
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) cand = min(cand, __shfl_xor(cand, off, 64));
       if (lane == 0) {

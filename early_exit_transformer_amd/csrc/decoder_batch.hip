@@ -15,13 +15,11 @@
 // memory keys | values are projected by _begin with one training GEMM per (exit, layer).
 #include "eec_decoder_step.h"
 
+using namespace eec;  // eec_wave.h
 using namespace eect;
 using namespace eecs;
 
 namespace {
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Y[e][m][n] (+)= act( LN_e?(X[e][m]) . W_e[n] + bias_e[n] ),  m < M = B * R, on v_mfma_f32_32x32x16_f16 with f16x3 operands:
@@ -37,8 +35,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kTM = 64, kTN = 32, kKB = 4;  // rows, columns of a workgroup; k-steps in flight per wave
 constexpr float kHalfMax = 65504.0f;
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 struct ExitLinear {
   const float *W, *bias;     // [N][K], [N]
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
         v[j] = k < K ? *reinterpret_cast<const float4*>(xr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
       }
-      const float mean = wsum(s, 8) / K;
+      const float mean = wave_all_sum(s, 8) / K;
       float q = 0.0f;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
           q += dx * dx + dy * dy + dz * dz + dw * dw;
         }
       }
-      const float rstd = rsqrtf(wsum(q, 8) / K + 1e-5f);
+      const float rstd = rsqrtf(wave_all_sum(q, 8) / K + 1e-5f);
       if (l16 == 0) mu[ml] = mean, rs[ml] = rstd;
     }
     __syncthreads();
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(256) void batch_self_attn_kernel(SelfAttnArgs a) {
     sc[t] = d;
     mx = fmaxf(mx, d);
   }
-  mx = wmax(mx);
+  mx = wave_all_max(mx);
   if (lane == 0) stat[0][w] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(stat[0][0], stat[0][1]), fmaxf(stat[0][2], stat[0][3]));
@@ -268,7 +264,7 @@ __global__ __launch_bounds__(256) void batch_self_attn_kernel(SelfAttnArgs a) {
     sc[t] = p;
     sum += p;
   }
-  sum = wsum(sum);
+  sum = wave_all_sum(sum);
   if (lane == 0) stat[1][w] = sum;
   __syncthreads();
   const float inv = 1.0f / (stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]);  // no live key: nan, as torch
@@ -339,7 +335,7 @@ __global__ __launch_bounds__(256) void batch_cross_attn_kernel(CrossAttnArgs a) 
     if (rr < R) {
       float mx = -INFINITY;
       for (int j = l16; j < kChunk; j += 16) mx = fmaxf(mx, ps[rr][j]);
-      const float m_new = fmaxf(m_run, wmax(mx, 8));  // finite: the chunk holds at least one key
+      const float m_new = fmaxf(m_run, wave_all_max(mx, 8));  // finite: the chunk holds at least one key
       float sum = 0.0f;
       for (int j = l16; j < kChunk; j += 16) {
         const float p = __expf(ps[rr][j] - m_new);
@@ -347,7 +343,7 @@ __global__ __launch_bounds__(256) void batch_cross_attn_kernel(CrossAttnArgs a) 
         sum += p;
       }
       const float al = __expf(m_run - m_new);
-      l_run = l_run * al + wsum(sum, 8);
+      l_run = l_run * al + wave_all_sum(sum, 8);
       m_run = m_new;
       if (l16 == 0) alpha[rr] = al;
     }

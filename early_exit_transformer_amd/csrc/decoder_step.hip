@@ -16,6 +16,7 @@
 // (eec_decoder_step_multi): E searches for the launches of one.
 #include "eec_decoder_step.h"
 
+using namespace eec;  // eec_wave.h
 using namespace eect;
 using namespace eecs;
 
@@ -44,24 +45,6 @@ struct SkinnyArgs {
   long ldy;
   int R, N, K, relu, accumulate;
 };
-
-#define EECS_DPP_ADD(v, ctrl, rmask) \
-  ((v) + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), ctrl, rmask, 0xf, false)))
-// sum over the 16 lanes of a DPP row, left in every lane of the row
-__device__ __forceinline__ float row16_sum(float v) {
-  v = EECS_DPP_ADD(v, 0xB1, 0xf);   // quad_perm [1,0,3,2]
-  v = EECS_DPP_ADD(v, 0x4E, 0xf);   // quad_perm [2,3,0,1]
-  v = EECS_DPP_ADD(v, 0x141, 0xf);  // row_half_mirror
-  v = EECS_DPP_ADD(v, 0x140, 0xf);  // row_mirror
-  return v;
-}
-// sum over the wave, wave-uniform
-__device__ __forceinline__ float wave64_sum(float v) {
-  v = row16_sum(v);
-  v = EECS_DPP_ADD(v, 0x142, 0xa);  // row_bcast15 -> rows 1, 3
-  v = EECS_DPP_ADD(v, 0x143, 0xc);  // row_bcast31 -> rows 2, 3
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 constexpr int kBatch = 8;
 
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(256) void skinny_linear_kernel(Group<SkinnyArgs> gr
   }
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
-    if (KL == 64) acc[r] = wave64_sum(acc[r]);
+    if (KL == 64) acc[r] = wave_sum(acc[r]);
     else {
       acc[r] = row16_sum(acc[r]);
       if (KL == 32) acc[r] += __shfl_xor(acc[r], 16, 64);
@@ -302,7 +285,7 @@ __global__ __launch_bounds__(256) void step_attn_kernel(Group<StepAttnArgs> grp)
     sc[t] = d;
     mx = fmaxf(mx, d);
   }
-  mx = wmax(mx);
+  mx = wave_all_max(mx);
   if (lane == 0) stat[0][w] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(stat[0][0], stat[0][1]), fmaxf(stat[0][2], stat[0][3]));
@@ -312,7 +295,7 @@ __global__ __launch_bounds__(256) void step_attn_kernel(Group<StepAttnArgs> grp)
     sc[t] = p;
     sum += p;
   }
-  sum = wsum(sum);
+  sum = wave_all_sum(sum);
   if (lane == 0) stat[1][w] = sum;
   __syncthreads();
   const float inv = 1.0f / (stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]);  // no live key: nan, as torch

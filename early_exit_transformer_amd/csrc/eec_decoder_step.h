@@ -1,6 +1,6 @@
 // What the two step-wise AED decoders share (decoder_step.hip: the exits of one utterance; decoder_batch.hip: every exit and
-// utterance of a padded batch): the cache layout, the argument checks of their entry points, the wave reductions and the
-// log-softmax of a row.  Their embed, attention and linear kernels differ by design and stay in their own files.
+// utterance of a padded batch): the cache layout, the argument checks of their entry points and the log-softmax of a
+// row.  Their embed, attention and linear kernels differ by design and stay in their own files.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -8,36 +8,21 @@
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_train.h"
-
-namespace eec {
-hipError_t ensure_max_lds(const void* kernel, int bytes);  // pack.hip
-}
+#include "eec_wave.h"
 
 namespace eecs {
 
 constexpr int kRows = 16;  // live beams per search and step (rows of every activation of a step)
 constexpr int kGroup = 8;  // decoders (exits) per call: their pointers travel in the kernel arguments
 
-// over the 2 * from lanes of a group, left in every lane of it: the whole wave by default
-__device__ __forceinline__ float wsum(float v, int from = 32) {
-#pragma unroll
-  for (int m = from; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v, int from = 32) {
-#pragma unroll
-  for (int m = from; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
 // out[0 .. V) = log_softmax(xr[0 .. V)), by one wave
 __device__ __forceinline__ void log_softmax_row(const float* xr, float* out, int V, int lane) {
   float mx = -INFINITY;
   for (int k = lane; k < V; k += 64) mx = fmaxf(mx, xr[k]);
-  mx = wmax(mx);
+  mx = eec::wave_all_max(mx);
   float sum = 0.0f;
   for (int k = lane; k < V; k += 64) sum += expf(xr[k] - mx);
-  const float lse = mx + logf(wsum(sum));
+  const float lse = mx + logf(eec::wave_all_sum(sum));
   for (int k = lane; k < V; k += 64) out[k] = xr[k] - lse;
 }
 

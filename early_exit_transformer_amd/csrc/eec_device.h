@@ -27,27 +27,9 @@
 //       ((nt * KS + s) * 2 + plane) * 64 + lane,   KS = K / 16, plane 0 = hi, 1 = lo
 //   so a wave reads one fragment as one contiguous 1 KiB global_load_dwordx4.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "eec_wave.h"
 
 namespace eec {
-
-typedef _Float16 half_t;
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// EEC_OPERAND_BF16 (a translation-unit switch; only the training step's fused feed-forward BACKWARD sets it, ffn.hip): the split
-// operands are bf16 hi / lo pairs (2^-16 per product, the fp32 exponent range: gradients) on v_mfma_*_bf16 instead of fp16 pairs.
-// Fragments keep their h8 / h2 storage types -- only the conversions and the MFMA builtins differ.
-#ifndef EEC_OPERAND_BF16
-#define EEC_OPERAND_BF16 0
-#endif
-typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kWave = 64;
 constexpr float kLnEps = 1e-5f;
@@ -87,8 +69,6 @@ __device__ __forceinline__ int row_tile_index() {
   if (b < full) return (b & ~31) + (b & 7) * 4 + ((b >> 3) & 3);
   return b;
 }
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 // Lane index recomputed from nothing (v_mbcnt of the full mask) behind an optimisation barrier: code after a long
 // register-starved loop derives its lane / row indices from THIS value, so the compiler recomputes them (a few
 // VALU ops) instead of keeping what it computed before the loop alive -- i.e. spilled to scratch and reloaded
@@ -100,32 +80,6 @@ __device__ __forceinline__ int fresh_lane() {
   return l;
 }
 __device__ __forceinline__ int wave_id_sgpr() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-
-// Wave-wide reductions on the DPP crossbar (no LDS traffic, unlike __shfl_xor = ds_bpermute): xor-1 / xor-2
-// inside each quad, half-row and row mirrors -> every lane of a 16-lane row holds the row total; row_bcast15
-// into rows 1,3 and row_bcast31 into rows 2,3 -> lane 63 holds the wave total, returned wave-uniform.
-#define EEC_DPP_ADD(v, ctrl, rmask) \
-  ((v) + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), ctrl, rmask, 0xf, false)))
-#define EEC_DPP_MAX(v, ctrl, rmask) \
-  fmaxf((v), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (v)), __builtin_bit_cast(int, (v)), ctrl, rmask, 0xf, false)))
-__device__ __forceinline__ float wave_sum(float v) {
-  v = EEC_DPP_ADD(v, 0xB1, 0xf);   // quad_perm [1,0,3,2]
-  v = EEC_DPP_ADD(v, 0x4E, 0xf);   // quad_perm [2,3,0,1]
-  v = EEC_DPP_ADD(v, 0x141, 0xf);  // row_half_mirror
-  v = EEC_DPP_ADD(v, 0x140, 0xf);  // row_mirror
-  v = EEC_DPP_ADD(v, 0x142, 0xa);  // row_bcast15 -> rows 1, 3
-  v = EEC_DPP_ADD(v, 0x143, 0xc);  // row_bcast31 -> rows 2, 3
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_max(float v) {
-  v = EEC_DPP_MAX(v, 0xB1, 0xf);
-  v = EEC_DPP_MAX(v, 0x4E, 0xf);
-  v = EEC_DPP_MAX(v, 0x141, 0xf);
-  v = EEC_DPP_MAX(v, 0x140, 0xf);
-  v = EEC_DPP_MAX(v, 0x142, 0xa);
-  v = EEC_DPP_MAX(v, 0x143, 0xc);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 __device__ __forceinline__ half_t to_half_sat(float x) {
   return (half_t)fminf(fmaxf(x, -kHalfMax), kHalfMax);
@@ -159,10 +113,10 @@ __device__ __forceinline__ hl2_t split2(float a, float b) {
   hl2_t r;
 #if EEC_OPERAND_BF16
   {
-    const f32x2_t x = {a, b};
-    const bf2_t hi = __builtin_convertvector(x, bf2_t);
+    const f32x2 x = {a, b};
+    const bf16x2 hi = __builtin_convertvector(x, bf16x2);
     r.hi = __builtin_bit_cast(h2, hi);
-    r.lo = NP == 3 ? __builtin_bit_cast(h2, __builtin_convertvector(x - __builtin_convertvector(hi, f32x2_t), bf2_t)) : r.hi;
+    r.lo = NP == 3 ? __builtin_bit_cast(h2, __builtin_convertvector(x - __builtin_convertvector(hi, f32x2), bf16x2)) : r.hi;
     return r;
   }
 #endif
@@ -198,13 +152,11 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 
 __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 #if EEC_OPERAND_BF16
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8_t, a), __builtin_bit_cast(bf8_t, b), c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 #else
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 #endif
 }
-// row of accumulator register i for this lane (within a 32x32 tile)
-__device__ __forceinline__ int acc_row(int i, int lane) { return (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5); }
 
 // ---------------------------------------------------------------------------
 // Register ring of weight fragments: the first PF k-steps of a stage are loaded by the caller
@@ -387,75 +339,20 @@ __device__ __forceinline__ void gemm_plain_ring(f32x16 (&acc)[2][NT], const char
 //     row 16 rb + c, k = 32 S + 8 (2 hh + u) + j.  From an LDS plane that is just another address; in the packed weights (1-KiB
 //     fragments per 16-deep k-step, lane-linear) it is fragment 2 S + hh, slot 16 rb + c + 32 u -- another per-lane pointer into
 //     the SAME packing.  A ring entry p is (S = p / 2, rb = p % 2): the ring holds the same bytes as before, differently dealt.
-//   * a 32 x 32 accumulator tile is four 16 x 16 quadrants (ra, cb) in registers 4 (2 ra + cb) + i: m = 16 ra + 4 (2 hh + u) + i,
-//     n = 16 cb + c ("quadrant layout").  The standard layout every epilogue expects (n = 16 u + c, m = (i & 3) + 8 (i >> 2) + 4 hh)
-//     is restored with v_permlane16_swap + v_permlane32_swap on the register pairs (4 (2 ra) + i, 4 (2 ra + 1) + i): 32 cross-lane
-//     instructions per tile, once per accumulation (acc_q_to_std / acc_std_to_q).
+//   * a 32 x 32 accumulator tile is four 16 x 16 quadrants in the "quadrant layout"; the standard layout every epilogue expects is
+//     restored by lane swaps, once per accumulation (eec_wave.h: quad_mac16, accs_q_to_std / accs_std_to_q and their hazard rule).
 // ===========================================================================
 // EEC_MFMA16_NP1 (a translation-unit switch, off: the single-product format on the 16x16x32 shape too -- slower in the inference kernels;
 // set by the training step's fused feed-forward objects of ffn.hip, whose tape stores want the quadrant layout's 16 rows x 64 B per instruction)
 #ifndef EEC_MFMA16_NP1
 #define EEC_MFMA16_NP1 0
 #endif
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 mfma32(h8 a, h8 b, f32x4 c) {
-#if EEC_OPERAND_BF16
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8_t, a), __builtin_bit_cast(bf8_t, b), c, 0, 0, 0);
-#else
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-#endif
-}
 // quadrant (ra, cb) of a tile += A[ra] . B[cb]^T for ra, cb in {0, 1}
 __device__ __forceinline__ void tile_mac16(f32x16& acc, const h8 (&a)[2], const h8 (&b)[2]) {
 #pragma unroll
   for (int ra = 0; ra < 2; ++ra)
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int q = 4 * (2 * ra + cb);
-      f32x4 t = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
-      t = mfma32(a[ra], b[cb], t);
-      acc[q] = t[0], acc[q + 1] = t[1], acc[q + 2] = t[2], acc[q + 3] = t[3];
-    }
-}
-// The lane exchanges of one tile as ONE block of in-place asm (both registers of a swap are read and written; a chain of the
-// builtins loses its second result in hipcc 7.2).  The eight pairs are independent, so inside the block no swap reads a register
-// written fewer than seven instructions earlier; the leading s_nop covers a VALU write right in front of the block.
-#define EEC_SWAP8(OP)                                                                                                        \
-  "v_permlane" OP "_swap_b32 %0, %4\n\tv_permlane" OP "_swap_b32 %1, %5\n\tv_permlane" OP "_swap_b32 %2, %6\n\t"            \
-  "v_permlane" OP "_swap_b32 %3, %7\n\tv_permlane" OP "_swap_b32 %8, %12\n\tv_permlane" OP "_swap_b32 %9, %13\n\t"          \
-  "v_permlane" OP "_swap_b32 %10, %14\n\tv_permlane" OP "_swap_b32 %11, %15\n\t"
-__device__ __forceinline__ void acc_q_to_std(f32x16& acc) {
-  float r0 = acc[0], r1 = acc[1], r2 = acc[2], r3 = acc[3], r4 = acc[4], r5 = acc[5], r6 = acc[6], r7 = acc[7];
-  float r8 = acc[8], r9 = acc[9], r10 = acc[10], r11 = acc[11], r12 = acc[12], r13 = acc[13], r14 = acc[14], r15 = acc[15];
-  asm volatile("s_nop 1\n\t" EEC_SWAP8("16") EEC_SWAP8("32") "s_nop 1"
-               : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "+v"(r8), "+v"(r9), "+v"(r10), "+v"(r11),
-                 "+v"(r12), "+v"(r13), "+v"(r14), "+v"(r15));
-  acc = (f32x16){r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15};
-}
-__device__ __forceinline__ void acc_std_to_q(f32x16& acc) {
-  float r0 = acc[0], r1 = acc[1], r2 = acc[2], r3 = acc[3], r4 = acc[4], r5 = acc[5], r6 = acc[6], r7 = acc[7];
-  float r8 = acc[8], r9 = acc[9], r10 = acc[10], r11 = acc[11], r12 = acc[12], r13 = acc[13], r14 = acc[14], r15 = acc[15];
-  asm volatile("s_nop 1\n\t" EEC_SWAP8("32") EEC_SWAP8("16") "s_nop 1"
-               : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "+v"(r8), "+v"(r9), "+v"(r10), "+v"(r11),
-                 "+v"(r12), "+v"(r13), "+v"(r14), "+v"(r15));
-  acc = (f32x16){r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15};
-}
-template <int MT, int NT>
-__device__ __forceinline__ void accs_q_to_std(f32x16 (&acc)[MT][NT]) {
-  // the swaps below are inline asm: hipcc does not pad the MFMA-result -> VALU-read hazard in front of them (with a single tile
-  // the last MFMA's quadrant was read stale: tools/mfma16_gemm_check.hip).  19 wait states cover a 16-pass MFMA.
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" ::: "memory");
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) acc_q_to_std(acc[a][b]);
-}
-template <int MT, int NT>
-__device__ __forceinline__ void accs_std_to_q(f32x16 (&acc)[MT][NT]) {
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) acc_std_to_q(acc[a][b]);
+    for (int cb = 0; cb < 2; ++cb) quad_mac16(acc, ra, cb, a[ra], b[cb]);
 }
 // per-lane bases of the 16x16x32 fragments, derived from the 32x32x16 ones the callers pass (a_lane = plane + (lane & 31) * ld +
 // 16 hh;  w_lane = fragment base + lane)
@@ -498,12 +395,6 @@ __device__ __forceinline__ void ring_fill_16(WRing<NP, PF, NT>& r, const uint4* 
 // The loop walks HALF double-steps p = 2 S + rb: step p multiplies row block rb of the activation operand (one fragment set: the
 // same registers per step as the 32x32x16 loop's k-step) with both row blocks of the weight operand (ring entries 2 S, 2 S + 1),
 // i.e. the two quadrants of each tile that row block rb of the activations belongs to.
-__device__ __forceinline__ void quad_mac16(f32x16& acc, int ra, int cb, h8 a, h8 b) {  // ra, cb constants after unrolling
-  const int q = 4 * (2 * ra + cb);
-  f32x4 t = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
-  t = mfma32(a, b, t);
-  acc[q] = t[0], acc[q + 1] = t[1], acc[q + 2] = t[2], acc[q + 3] = t[3];
-}
 template <int NP, int KS, int NT, bool SWAP, int PF, typename Side = NoSide, int SIDE_VALU = 0, int MT = 2, bool IN_STD = true, bool OUT_STD = true>
 __device__ __forceinline__ void gemm_ring_16(f32x16 (&acc)[MT][NT], const char* a_lane, int ld_bytes, int plane_bytes,
                                              const uint4* __restrict__ w_lane, size_t nt_stride, WRing<NP, PF, NT>& r, Side side = Side()) {
@@ -800,20 +691,6 @@ __device__ __forceinline__ void ring_fill_f8(WRing<1, PF, NT>& r, const uint4* _
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) r.q[p][nt][0] = wload(rec_lane + nt * nt_stride + (size_t)(p >> 2) * kF8Rec + (size_t)(p & 3) * 64);
   __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int I>
-struct IntTag {
-  static constexpr int value = I;
-};
-// f(IntTag<K0>{}), ..., f(IntTag<K1-1>{}): a loop whose index is a compile-time constant in the body (register arrays
-// indexed by it never fall back to scratch memory, whatever the unroller decides)
-template <int K0, int K1, typename F>
-__device__ __forceinline__ void static_range(F&& f) {
-  if constexpr (K0 < K1) {
-    f(IntTag<K0>{});
-    static_range<K0 + 1, K1>(f);
-  }
 }
 
 template <int MT, int NT>

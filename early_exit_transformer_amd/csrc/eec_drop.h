@@ -3,6 +3,7 @@
 // must produce the masks the backward regenerates.
 #pragma once
 #include "eec_train.h"
+#include "eec_wave.h"
 
 namespace eect {
 

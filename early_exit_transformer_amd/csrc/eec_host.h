@@ -9,6 +9,12 @@
 
 #include "../../include/eec.h"
 
+namespace eec {
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, DEVICE): the attribute is per device, so a
+// process-wide flag would leave the > 64 KiB launches of a second device failing.  Thread-safe.  (pack.hip)
+hipError_t ensure_max_lds(const void* kernel, int bytes);
+}  // namespace eec
+
 namespace eech {
 
 // One message per thread for the whole library: every non-zero return of an extern "C" entry leaves its reason here.

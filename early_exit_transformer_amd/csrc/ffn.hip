@@ -145,20 +145,12 @@ __device__ __forceinline__ unsigned touch_share(const void* base, size_t bytes, 
 // the weight stream -- 6.5 MB per stage against 4 MB of L2 per XCD -- out of it (same-box A/B: 172.6 us per launch with plain stores,
 // 135.4 us with the hint, 99.7 us without any tape stores; profiles/r04_micro_ffn_train_fwd.txt)
 __device__ __forceinline__ void tape_store4(float* p, float x, float y, float z, float w) {
-  typedef float f32x4_t __attribute__((ext_vector_type(4)));
-  const f32x4_t v = {x, y, z, w};
+  const f32x4 v = {x, y, z, w};
 #if EEC_TR_NT
-  __builtin_nontemporal_store(v, (f32x4_t*)p);
+  __builtin_nontemporal_store(v, (f32x4*)p);
 #else
-  *(f32x4_t*)p = v;
+  *(f32x4*)p = v;
 #endif
-}
-// f(IntTag<0>{}), ..., f(IntTag<N-1>{}) for N <= 2: a stage loop whose index is a compile-time constant
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_assert(N >= 1 && N <= 2, "one or two stages");
-  f(IntTag<0>{});
-  if constexpr (N == 2) f(IntTag<1>{});
 }
 template <bool B>
 struct BoolTag {
@@ -490,7 +482,7 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
   unsigned sink = 0;  // keeps the L2 warm-up loads alive
   const int nslots = nchunk + 2;
   f32x16 acc2c[NH][MT][NTP];  // consumers' [rows x D/4] output accumulators (unused by producers)
-  static_for<NS>([&](auto si_tag) {
+  static_range<0, NS>([&](auto si_tag) {
     constexpr int si = decltype(si_tag)::value;  // NS is a template parameter and the loop is unrolled: as a runtime loop it makes
                                      // every ring and accumulator loop-carried (~250 spilled VGPRs in the hot loops)
     const WPtrs W = wptrs(si);
@@ -513,8 +505,7 @@ __global__ __launch_bounds__(kFfnThreads, EEC_FFN_MINWAVES) void ffn_chain_kerne
             const int frame = Q16 ? mt * 32 + 16 * (g & 1) + (lane & 15) : mt * 32 + (lane & 31);
             const int hid = Q16 ? wl * 32 + 16 * (g >> 1) + 8 * hh + 4 * ((lane >> 4) & 1) : wl * 32 + 4 * hh + g * 8;
             const int row = min(row0 + frame, M - 1);  // clamped, not branched: rows past the end are never stored
-            typedef float f32x4_t __attribute__((ext_vector_type(4)));
-            const f32x4_t v = __builtin_nontemporal_load((const f32x4_t*)(a.tr.pre + (size_t)row * F + hcol0 + hid));
+            const f32x4 v = __builtin_nontemporal_load((const f32x4*)(a.tr.pre + (size_t)row * F + hcol0 + hid));
             preq[mt][4 * g] = v[0], preq[mt][4 * g + 1] = v[1], preq[mt][4 * g + 2] = v[2], preq[mt][4 * g + 3] = v[3];
           }
       };

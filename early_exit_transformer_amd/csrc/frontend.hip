@@ -41,8 +41,6 @@ struct FrontendArgs {
   float* mel;              // [B][n_mels][Tmax]
 };
 
-typedef float f32x16v __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(kFeThreads, 2) void mel_frontend_kernel(FrontendArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* lds_a = (float*)smem;                       // [32][324]
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(kFeThreads, 2) void mel_frontend_kernel(FrontendArg
   }
   __syncthreads();
   // ---- DFT: wave w owns bin tiles 2w, 2w+1 (cos and sin parts): 4 accumulators ----
-  f32x16v acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll

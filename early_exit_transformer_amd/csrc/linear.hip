@@ -82,8 +82,7 @@ __device__ __forceinline__ void planes_commit512(char* lds_act, const PlaneRegs<
     if (NP == 3) *(uint4*)(lds_act + G::kAPlane + rl * G::kALd + c16 * 16) = pr.l[it];
     if (NP == 8)  // the residual plane arrives as fp16: its top bytes (e5m2) go to the permuted byte plane, 8 k at a time
     {
-      typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-      const h8v lg = __builtin_bit_cast(h8v, pr.l[it]) * (half_t)kF8ALoGain;  // gain-compensated (eec_device.h, kF8ALoGain)
+      const h8 lg = __builtin_bit_cast(h8, pr.l[it]) * (half_t)kF8ALoGain;  // gain-compensated (eec_device.h, kF8ALoGain)
       *(uint2*)(lds_act + G::kAPlane + rl * G::kA8Ld + lo8_pos(c16 * 8)) = top_bytes(__builtin_bit_cast(uint4, lg));
     }
   }
@@ -159,7 +158,6 @@ template <int D, int NP, bool X3 = false>
 __device__ __forceinline__ void attn_tile_to_planes(char* smem, const AttnArgs& a, int row0) {
   using G = Geo<D>;
   constexpr int MT = G::kMT, DH = D / 8, KSQ = DH / 16, DT = DH / 32, KB = X3 ? 1 : 2;
-  constexpr float kNegBig = -1.0e30f;
   const int lane = lane_id(), w = wave_id(), r = lane & 31, hh = lane >> 5;
   const int b = row0 / a.Tq, q0 = row0 - b * a.Tq, bh = b * a.H + w;
   const int len_raw = a.enc_len[b];  // requested first, consumed after the first K / V requests have left

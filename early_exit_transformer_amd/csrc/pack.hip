@@ -50,7 +50,7 @@ __global__ void pack_frags_bf16_kernel(const float* __restrict__ w, int N, int K
   const int KS = K / 16;
   const int nt = frag / KS, s = frag - nt * KS;
   const int n = nt * 32 + (lane & 31), k0 = s * 16 + 8 * (lane >> 5);
-  bf8_t hi, lo;
+  bf16x8 hi, lo;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float v = (n < N) ? w[(size_t)n * ldn + (size_t)(k0 + j) * ldk] : 0.f;
@@ -93,7 +93,7 @@ __global__ void pack_ffn_batch_kernel(FfnPackJobs jb, int F, int D, int kind0, i
     out[(size_t)frag * 128 + lane] = __builtin_bit_cast(uint4, hi);
     out[(size_t)frag * 128 + 64 + lane] = __builtin_bit_cast(uint4, lo);
   } else {
-    bf8_t hi, lo;
+    bf16x8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const __bf16 h = (__bf16)v[j];

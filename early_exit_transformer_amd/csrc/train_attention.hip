@@ -9,17 +9,11 @@
 // of lane half h is tile row 16*(i/8) + 8*((i%8)/4) + 4*h + i%4, i.e. registers 8*ks .. 8*ks+7 are the eight k-slots of
 // k-step ks; the partner operand is gathered from memory with the same slot -> row map.
 #include "eec_drop.h"
-
-namespace eec {
-hipError_t ensure_max_lds(const void* kernel, int bytes);  // pack.hip: per-device MaxDynamicSharedMemorySize attribute
-}
+#include "eec_host.h"
 
 namespace eect {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace eec;  // eec_wave.h
 
 namespace {
 
@@ -47,6 +41,7 @@ __device__ __forceinline__ f32x16 mfma3(const Frag& a, const Frag& b, f32x16 c) 
 }
 // tile row of k-slot j (0..7) of k-step ks (0, 1) for lane half hh: the accumulator layout read as an operand
 __device__ __forceinline__ int slot_row(int ks, int j, int hh) { return 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3); }
+// eec::acc_row by the lane's half (hh = lane >> 5, which these kernels keep; passing the lane instead changes their code)
 __device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
 
 // operand fragment of row `row` (8 consecutive fp32 at p); zeros when !ok.  p is 32-byte aligned (head dim % 8 == 0).
@@ -85,8 +80,6 @@ __device__ __forceinline__ f32x16 zero16() {
   return z;
 }
 
-constexpr float kNegBig = -1.0e30f;
-
 struct AttnGeoK {  // pointers of one (b, h): rows are frames, ld = 3D for q / k / v, D for o / do
   const float *q, *k, *v;
   long ld;
@@ -110,9 +103,6 @@ __device__ __forceinline__ AttnGeoK attn_geo(const float* qkv, const int32_t* ke
 // of a row) and / or the slot layout ([DH][40]: ds_read_b128 = the 8 k-slots of column d, rows stored at slot_pos(row)).
 // Two buffers: the global loads of tile t + 1 are issued before tile t is consumed and written to LDS after it.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16;
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 template <int DH, int NP, bool ROWL, bool SLOTL>
 struct TileLds {
   static constexpr int kLdR = DH + 8, kLdT = 40, kPl = NP == 3 ? 2 : 1;  // planes per layout

@@ -1,44 +1,13 @@
 // Kernels of the training step (see eec_train.h): one general bf16-split MFMA GEMM and the row / column / pointwise
-// kernels around it.  fp32 in HBM everywhere; nothing here is shared with the fused inference path.
+// kernels around it.  fp32 in HBM everywhere.  The wave-level primitives are the inference path's (eec_wave.h).
 #include "eec_drop.h"
 
 namespace eect {
 
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace eec;  // eec_wave.h
 
 constexpr int kBK = 32;   // k extent of one LDS tile
 constexpr int kLdk = 40;  // bf16 elements per LDS tile row (80 B: the 16 lanes of a ds_read_b128 group cover all 64 banks once)
-
-__device__ __forceinline__ int acc_row(int i, int lane) { return (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5); }
-
-// wave-wide reductions on the DPP crossbar (no LDS traffic): quad swaps, half-row / row mirrors, then row broadcasts; lane 63
-// holds the total, returned wave-uniform
-#define EECT_DPP_ADD(v, ctrl, rmask) \
-  ((v) + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), ctrl, rmask, 0xf, false)))
-#define EECT_DPP_MAX(v, ctrl, rmask) \
-  fmaxf((v), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (v)), __builtin_bit_cast(int, (v)), ctrl, rmask, 0xf, false)))
-__device__ __forceinline__ float wave_sum(float v) {
-  v = EECT_DPP_ADD(v, 0xB1, 0xf);
-  v = EECT_DPP_ADD(v, 0x4E, 0xf);
-  v = EECT_DPP_ADD(v, 0x141, 0xf);
-  v = EECT_DPP_ADD(v, 0x140, 0xf);
-  v = EECT_DPP_ADD(v, 0x142, 0xa);
-  v = EECT_DPP_ADD(v, 0x143, 0xc);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_max(float v) {
-  v = EECT_DPP_MAX(v, 0xB1, 0xf);
-  v = EECT_DPP_MAX(v, 0x4E, 0xf);
-  v = EECT_DPP_MAX(v, 0x141, 0xf);
-  v = EECT_DPP_MAX(v, 0x140, 0xf);
-  v = EECT_DPP_MAX(v, 0x142, 0xa);
-  v = EECT_DPP_MAX(v, 0x143, 0xc);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 // sigmoid on the hardware reciprocal (1 ulp) instead of an IEEE division (a ~10-instruction sequence): the epilogues and
 // pointwise kernels evaluate it once per activation element
@@ -154,7 +123,7 @@ __device__ __forceinline__ void store_tile(bf16* __restrict__ hi, bf16* __restri
   }
 }
 
-// The tile images are read as operands of v_mfma_f32_16x16x32_bf16 (csrc/eec_device.h has the inference path's form of this): the chip
+// The tile images are read as operands of v_mfma_f32_16x16x32_bf16 (quad_mac16, eec_wave.h; eec_device.h has the inference path's loops): the chip
 // holds a higher clock on that shape under load than on 32x32x16 (profiles/r04_micro_mfma_shape_clock.txt; timing-only swap in this
 // kernel: training step 25.5 -> 24.1 ms).  Lane l = 16 g + c holds row rbase + 16 rb + c, k = 8 g .. 8 g + 7 of the 32-deep tile.
 template <int R, bool KC>
@@ -167,43 +136,6 @@ __device__ __forceinline__ bf16x8 read_frag16(const bf16* __restrict__ t, int rb
   const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(a + 4 * TileGeo<R>::kLdt));
   return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// quadrant (ra, cb) of a 32 x 32 tile (registers 4 (2 ra + cb) ..): m = 16 ra + 4 (lane >> 4) + i, n = 16 cb + (lane & 15)
-__device__ __forceinline__ void quad_mac16(f32x16& acc, int ra, int cb, bf16x8 a, bf16x8 b) {
-  const int q = 4 * (2 * ra + cb);
-  f32x4 t = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, t, 0, 0, 0);
-  acc[q] = t[0], acc[q + 1] = t[1], acc[q + 2] = t[2], acc[q + 3] = t[3];
-}
-// quadrant layout -> the 32x32x16 layout the epilogues expect: v_permlane16_swap + v_permlane32_swap on the register pairs
-// (4 (2 ra) + i, 4 (2 ra + 1) + i), one asm block per tile (derivation and checks: csrc/eec_device.h, tools/mfma16_gemm_check.hip)
-#define EECT_SWAP8(OP)                                                                                                       \
-  "v_permlane" OP "_swap_b32 %0, %4\n\tv_permlane" OP "_swap_b32 %1, %5\n\tv_permlane" OP "_swap_b32 %2, %6\n\t"            \
-  "v_permlane" OP "_swap_b32 %3, %7\n\tv_permlane" OP "_swap_b32 %8, %12\n\tv_permlane" OP "_swap_b32 %9, %13\n\t"          \
-  "v_permlane" OP "_swap_b32 %10, %14\n\tv_permlane" OP "_swap_b32 %11, %15\n\t"
-__device__ __forceinline__ void acc_q_to_std(f32x16& acc) {
-  float r0 = acc[0], r1 = acc[1], r2 = acc[2], r3 = acc[3], r4 = acc[4], r5 = acc[5], r6 = acc[6], r7 = acc[7];
-  float r8 = acc[8], r9 = acc[9], r10 = acc[10], r11 = acc[11], r12 = acc[12], r13 = acc[13], r14 = acc[14], r15 = acc[15];
-  asm volatile("s_nop 1\n\t" EECT_SWAP8("16") EECT_SWAP8("32") "s_nop 1"
-               : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "+v"(r8), "+v"(r9), "+v"(r10), "+v"(r11),
-                 "+v"(r12), "+v"(r13), "+v"(r14), "+v"(r15));
-  acc = (f32x16){r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15};
-}
-
-// f(IntTag<0>{}), ..., f(IntTag<N - 1>{}): a loop whose index is a compile-time constant in the body (register arrays indexed by
-// it never fall back to scratch memory, whatever the unroller decides)
-template <int I>
-struct IntTag {
-  static constexpr int value = I;
-};
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(IntTag<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 template <bool V>
 struct FastTag {
   static constexpr bool value = V;
@@ -394,13 +326,8 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel(GemmArgs g) {
   EECT_STAMP(1);
   if (fast) k_loop(FastTag<true>{});
   else k_loop(FastTag<false>{});
-  // the k-loop kept the accumulators in the quadrant layout: back to the layout of the epilogues, once.  (The swaps are inline asm:
-  // the MFMA-result -> VALU-read hazard in front of them is padded by hand -- 19 wait states cover a 16-pass MFMA.)
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc_q_to_std(acc[i][j]);
+  // the k-loop kept the accumulators in the quadrant layout: back to the layout of the epilogues, once
+  accs_q_to_std<TM, TN>(acc);
   EECT_STAMP(2);
   if constexpr (!AKC) {
     if (do_rs) {  // uniform over the workgroup.  The k-loop ended with a barrier: LDS is free.
@@ -514,7 +441,7 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel(GemmArgs g) {
     }
   };
   request(IntTag<0>{});
-  static_for<0, BM / 32>([&](auto sl_tag) __attribute__((always_inline)) {
+  static_range<0, BM / 32>([&](auto sl_tag) __attribute__((always_inline)) {
     constexpr int sl = decltype(sl_tag)::value;
     if constexpr (sl + 1 < BM / 32) request(IntTag<sl + 1>{});
     if (wm == sl / TM) {
