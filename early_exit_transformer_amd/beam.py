@@ -1,5 +1,4 @@
-"""Decoders on top of the HIP encoder: mirrors of the reference's ``util/beam_infer.py`` pieces that this package can
-serve without torchaudio.
+"""Decoders on top of the HIP encoder: mirrors of the reference's ``util/beam_infer.py``, served without torchaudio.
 
 * ``GreedyCTCDecoder``            util/beam_infer.py:9-24, on the batched HIP kernel (``eec_greedy_ctc``).
 * ``BeamInference.beam_search``   util/beam_infer.py:198-307: the AED beam search that ``inference.py:44-51`` drives per
@@ -16,6 +15,9 @@ serve without torchaudio.
   best beam by ``weight_ctc * s_ctc + (1 - weight_ctc) * s_pred``.
 * ``BeamInference.decode_batch``  inference.py:18-62 (evaluate_batch_ae) for a whole padded batch: the encoder once per
   batch, then the searches of every exit and utterance in lockstep (``beam_search_batch``, csrc/decoder_batch.hip).
+* ``BeamInference.ctc_predict`` / ``ctc_predict_``  util/beam_infer.py:93-126: the lexicon-constrained CTC beam search with
+  N-best (torchaudio's ``ctc_decoder(lexicon=...)`` without a language model) on the device (``ctc_lexicon_decode``,
+  csrc/ctc_lexbeam.hip): words that are lexicon entries by construction, and the posterior of the top hypothesis.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
@@ -27,8 +29,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .lexicon import as_lexicon
-from .model import beam_select, ctc_align, ctc_beam_decode, encoder_lengths, greedy_ctc
+from .lexicon import TokenTrie, as_lexicon
+from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, encoder_lengths, greedy_ctc
 
 
 class GreedyCTCDecoder(torch.nn.Module):
@@ -144,10 +146,55 @@ class BeamInference:
     """``args`` needs ``dec_voc_size, trg_sos_idx, trg_eos_idx, trg_pad_idx, beam_size, pen_alpha, device`` (the fields
     util/conf.py:455-486 injects); every one of them can also be given per call, as in the reference."""
 
-    def __init__(self, args=None):
+    N_BEST = 1       # util/beam_infer.py:42
+    W_INS = 0        # the word score of the reference's six lexicon decoders (w_ins, util/beam_infer.py:54); its WORD_SCORE = -4
+                     # (:41,74) belongs to the character-lexicon decoder of beam_predict, which is not served
+
+    def __init__(self, args=None, trie: Optional[TokenTrie] = None):
         self.args = args
+        self._trie = trie
 
     sequence_length_penalty = staticmethod(sequence_length_penalty)
+
+    def _lexicon_trie(self, trie: Optional[TokenTrie]) -> TokenTrie:
+        """``trie``, the one given to the constructor, or -- built at the first use -- the one of ``args.lexicon`` / ``args.tokens``
+        with the reference's ``blank_token="@"`` and ``sil_token="<pad>"`` (util/beam_infer.py:56-65)."""
+        if trie is not None:
+            return trie
+        if self._trie is None:
+            if self.args is None or not hasattr(self.args, "lexicon") or not hasattr(self.args, "tokens"):
+                raise ValueError("ctc_predict: no trie= was given and there is no args.lexicon / args.tokens")
+            self._trie = TokenTrie.from_files(self.args.lexicon, self.args.tokens, blank_token="@", sil_token="<pad>")
+        return self._trie
+
+    def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size):
+        """(transcript of the best hypothesis per utterance, scores [B, nbest] and n_hyp [B] on the host)."""
+        trie = self._lexicon_trie(trie)
+        nbest = self.N_BEST if nbest is None else nbest
+        words, word_count, _, _, _, scores, n_hyp = ctc_lexicon_decode(emission, trie, beam_size=self._arg(beam_size, "beam_size"), nbest=nbest,
+                                                                       word_score=self.W_INS)
+        words, word_count, n_hyp = words[:, 0].cpu(), word_count[:, 0].cpu().tolist(), n_hyp.cpu().tolist()
+        texts = [" ".join(trie.words[w] for w in words[b, : word_count[b]].tolist()).strip() if n_hyp[b] else "" for b in range(len(n_hyp))]
+        return texts, scores.cpu(), n_hyp
+
+    def ctc_predict_(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,
+                     beam_size: Optional[int] = None) -> List[str]:
+        """util/beam_infer.py:93-99: the transcript of the best lexicon-constrained hypothesis of every utterance of ``emission``
+        [B, T', V] (on the device; it stays there), its words joined by spaces and stripped.  ``index`` selects the reference's
+        per-exit decoder; all six are configured alike (w_ins = 0), so it is accepted and unused.  An utterance with no complete
+        hypothesis gives ``""`` (the reference would raise an IndexError: a stated divergence)."""
+        return self._lexicon_decode(emission, trie, nbest, beam_size)[0]
+
+    def ctc_predict(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,
+                    beam_size: Optional[int] = None):
+        """util/beam_infer.py:115-126: ``([transcript], pprob)`` for the FIRST utterance of ``emission`` [B, T', V]: the best
+        hypothesis' words, and ``softmax(scores of the returned hypotheses)[0]`` as a 0-D tensor -- with the reference's
+        ``N_BEST = 1`` that is always 1; ``nbest=`` returns a meaningful posterior.  No complete hypothesis: ``([""], 0.0)`` (the
+        reference would raise an IndexError: a stated divergence)."""
+        texts, scores, n_hyp = self._lexicon_decode(emission[:1], trie, nbest, beam_size)
+        if n_hyp[0] == 0:
+            return [""], torch.tensor(0.0)
+        return [texts[0]], torch.softmax(scores[0, : n_hyp[0]].double(), dim=0)[0].float()
 
     def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
                          detokenize=None) -> List[List["CTCHypothesis"]]:

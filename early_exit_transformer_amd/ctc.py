@@ -1,5 +1,5 @@
-"""The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), greedy and prefix-beam
-decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
+"""The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), greedy, prefix-beam and
+lexicon-constrained beam decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
 stream; there is no CPU path."""
 from __future__ import annotations
 
@@ -60,6 +60,43 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
                                               ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), stream_ptr(dev)),
                    "eec_ctc_beam_decode")
     return tokens, counts, scores
+
+
+def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
+                       beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None):
+    """Lexicon-constrained CTC beam search with N-best of [n, T', V] log-probs on the device (eec_ctc_lexbeam_decode): the
+    decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)`` without a language
+    model, util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
+    ``trie``: a ``lexicon.TokenTrie`` (it carries V, blank and sil); ``em_len`` [n] frames per sequence (None: T'); ``max_words``
+    (None: T', always enough): the words kept per hypothesis -- ``word_count`` is the true count even above it.  Returns
+    ``(words [n, nbest, max_words] int32 indices into trie.words, word_count [n, nbest], tokens [n, nbest, T'], token_count [n, nbest],
+    timesteps [n, nbest, T'], scores [n, nbest] fp32, n_hyp [n])``: hypotheses best first, absent ones with score -inf and counts
+    0, entries past a count -1.  One launch on the current stream, no host synchronisation."""
+    if not emission.is_cuda:
+        raise RuntimeError("ctc_lexicon_decode runs on a HIP device only")
+    logp = emission.contiguous().float()
+    n, Tq, V = logp.shape
+    if V != trie.V:
+        raise ValueError(f"ctc_lexicon_decode: the emission has {V} labels, the trie was packed for {trie.V}")
+    dev = logp.device
+    lib = capi.load()
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    max_words = Tq if max_words is None else int(max_words)
+    words, word_count, tokens, token_count, timesteps, n_hyp = i32(n, nbest, max(max_words, 0)), i32(n, nbest), i32(n, nbest, Tq), i32(n, nbest), i32(n, nbest, Tq), i32(n)
+    scores = torch.empty((n, nbest), dtype=torch.float32, device=dev)
+    if em_len is not None:
+        em_len = em_len.to(device=dev, dtype=torch.int32).contiguous()
+        if em_len.numel() != n:
+            raise ValueError(f"ctc_lexicon_decode: em_len must have {n} entries, got {em_len.numel()}")
+    ws_bytes = lib.eec_ctc_lexbeam_workspace_bytes(n, Tq, beam_size)
+    ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_ctc_lexbeam_decode(logp.data_ptr(), n, Tq, V, None if em_len is None else em_len.data_ptr(), trie.on(dev).data_ptr(),
+                                              trie.blank, trie.sil, int(beam_size), int(nbest), float(word_score), float(sil_score),
+                                              float(beam_threshold), max_words, words.data_ptr(), word_count.data_ptr(), tokens.data_ptr(),
+                                              token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
+                                              ws.data_ptr(), ws_bytes, stream_ptr(dev)), "eec_ctc_lexbeam_decode")
+    return words, word_count, tokens, token_count, timesteps, scores, n_hyp
 
 
 def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em_index: Optional[Tensor] = None,

@@ -2,12 +2,15 @@
 ``inference.py`` applies to every hypothesis it prints.  A word of the text that is not in the lexicon is replaced by the
 lexicon word with the smallest edit distance, the first such word in file order; the scan over the lexicon -- a Python loop
 per word in the reference -- is one call into libeec.so for all words at once (``eec_lexicon_nearest``, csrc/lexicon.hip).
-There is no CPU path: without a HIP device ``nearest`` raises, and with it everything that has a word to look up."""
+There is no CPU path: without a HIP device ``nearest`` raises, and with it everything that has a word to look up.
+
+``TokenTrie`` is the other use of a lexicon: the spellings of its words as token sequences, packed into the trie image that the
+lexicon-constrained CTC beam search walks (``ctc.ctc_lexicon_decode``, csrc/ctc_lexbeam.hip; layout in include/eec.h)."""
 from __future__ import annotations
 
 import ctypes as C
 import io
-from typing import Dict, Iterable, List, Sequence, Tuple, Union
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -150,6 +153,71 @@ class Lexicon:
         """util/tokenizer.py:35-50 for one text: split on the single character ``" "`` (the empty pieces of doubled, leading or
         trailing spaces are words too), keep a piece of the lexicon, replace any other by its first nearest word, join."""
         return self.apply_batch([predicted])[0]
+
+
+class TokenTrie:
+    """The token trie of a lexicon, packed once (``eec_ctc_trie_pack``, host code) and kept on the device.  ``words``: the words in
+    file order -- the decoder returns indices into it --, ``n_nodes`` the trie's size, ``n_shadowed`` how many spellings repeat an
+    earlier one and are therefore unreachable (the first word in file order with a spelling is the one it decodes to)."""
+
+    def __init__(self, words: Sequence[str], spellings: Sequence[Sequence[int]], V: int, blank: int = 0, sil: Optional[int] = None):
+        if len(words) != len(spellings):
+            raise ValueError(f"TokenTrie: {len(words)} words but {len(spellings)} spellings")
+        self.words: List[str] = list(words)
+        self.V, self.blank, self.sil = int(V), int(blank), -1 if sil is None else int(sil)
+        lib = capi.load()
+        lens = np.fromiter((len(sp) for sp in spellings), dtype=np.int64, count=len(spellings))
+        offsets = np.zeros(len(spellings) + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        flat = np.fromiter((t for sp in spellings for t in sp), dtype=np.int32, count=int(offsets[-1]))
+        nbytes = lib.eec_ctc_trie_pack_bytes(len(spellings), int(offsets[-1]))
+        image = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
+        n_nodes, n_shadowed = C.c_int32(), C.c_int32()
+        capi.check(lib.eec_ctc_trie_pack(flat.ctypes.data if flat.size else None, offsets.ctypes.data, len(spellings), self.V, self.blank,
+                                         self.sil, image.data_ptr(), nbytes, C.byref(n_nodes), C.byref(n_shadowed)), "eec_ctc_trie_pack")
+        self.n_nodes, self.n_shadowed = n_nodes.value, n_shadowed.value
+        self._image = image[: 4 * int(image[36:40].view(torch.int32))]  # header[9]: the dwords actually used
+        self._resident = None  # (device, device copy)
+
+    @classmethod
+    def from_spellings(cls, spellings: Sequence[Sequence[int]], V: int, blank: int = 0, sil: Optional[int] = None, words=None) -> "TokenTrie":
+        """``spellings``: one list of token ids per word; ``words`` (optional) their strings, else ``"w0", "w1", ...``."""
+        spellings = [list(sp) for sp in spellings]
+        return cls([f"w{i}" for i in range(len(spellings))] if words is None else words, spellings, V, blank, sil)
+
+    @classmethod
+    def from_files(cls, lexicon_path, tokens_path, blank_token: str = "@", sil_token: Optional[str] = None) -> "TokenTrie":
+        """The reference's files (args.lexicon / args.tokens): ``word<TAB>space-separated tokens`` per line, and one token per
+        line (its line number is its id)."""
+        with io.open(tokens_path, encoding="utf-8") as f:
+            tokens = [line.rstrip("\r\n") for line in f]
+        ids = {t: i for i, t in reversed(list(enumerate(tokens)))}
+        if blank_token not in ids or (sil_token is not None and sil_token not in ids):
+            raise ValueError(f"TokenTrie: {tokens_path} lacks the blank token {blank_token!r} or the sil token {sil_token!r}")
+        words, spellings = [], []
+        with io.open(lexicon_path, encoding="utf-8") as f:
+            for n, line in enumerate(f, 1):
+                line = line.rstrip("\r\n")
+                if not line.strip():
+                    continue
+                word, _, spelling = line.partition("\t")
+                if not word or not spelling.split():
+                    raise ValueError(f"TokenTrie: {lexicon_path}:{n}: expected word<TAB>tokens, got {line!r}")
+                try:
+                    spellings.append([ids[t] for t in spelling.split()])
+                except KeyError as e:
+                    raise ValueError(f"TokenTrie: {lexicon_path}:{n}: token {e.args[0]!r} is not in {tokens_path}") from None
+                words.append(word)
+        return cls(words, spellings, len(tokens), ids[blank_token], None if sil_token is None else ids[sil_token])
+
+    def __len__(self) -> int:
+        return len(self.words)
+
+    def on(self, dev: torch.device) -> Tensor:
+        """The packed image on ``dev`` (uploaded once; follows a change of device)."""
+        if self._resident is None or self._resident[0] != dev:
+            self._resident = (dev, self._image.to(dev))
+        return self._resident[1]
 
 
 _by_list: List[Tuple[list, Lexicon]] = []  # plain lists handed to apply_lex, by identity (the list is kept alive: its id stays its own)

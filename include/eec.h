@@ -249,6 +249,84 @@ int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, 
 int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                            int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream);
 
+/* Lexicon-constrained CTC beam search with N-best: replaces the decoder behind BeamInference.ctc_predict / ctc_predict_ /
+ * beam_predict (util/beam_infer.py:51-65, 85-126): torchaudio ctc_decoder(lexicon, tokens, nbest=N_BEST, log_add=False, beam_size,
+ * word_score=w_ins, blank_token="@", sil_token="<pad>") with lm=None, unk_score=-inf, for n_seq sequences in one launch
+ * (csrc/ctc_lexbeam.hip: one workgroup per sequence).  That decoder (flashlight-text) is third-party code outside the reference
+ * tree and is not installed: this is the published algorithm -- token-trie beam search under CTC, Viterbi merging, no language
+ * model -- as stated here; tests/lexbeam_cases.py is its plain-Python statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED.
+ * Out of scope: a language model, log_add=True (the reference's character-lexicon branch), unknown-word scores, beams over 16.
+ *
+ * Lexicon: n_words spellings, each a non-empty sequence of token ids in [0, V), none of them `blank` or (when given) `sil`.  The
+ *   trie's root is node 0.  A node "ends word w" when w is the FIRST word in file order with that spelling (later duplicates are
+ *   unreachable; the packer counts them in n_shadowed).  A node may both end a word and have children.
+ * Hypothesis: (node, tok, pb, hist, score) -- tok the label of the last frame, pb whether that frame was blank, hist the word
+ *   sequence so far, score fp32.  The start is (0, -1, true, (), 0.0f).
+ * Frame t, log-probs e[0..V), the beam in rank order i = 0..n-1.  Hypothesis i generates these candidates; every score is
+ *   computed in fp32 in exactly the order written:
+ *     blank            always                                       (node, blank, true, hist)   score + e[blank]           c = blank, w = 0
+ *     repeat           !pb and tok >= 0                             (node, tok, false, hist)    score + e[tok], and when tok == sil
+ *                                                                                               then + sil_score           c = tok,   w = 0
+ *     child, in-word   every child edge (c -> y) of node with
+ *                      c != tok or pb; y has children               (y, c, false, hist)         score + e[c]               w = 0
+ *     child, word end  the same edge; y ends word wd                (0, c, false, hist + wd)    (score + e[c]) + word_score  w = 1
+ *     sil              node == 0, sil >= 0, and sil != tok or pb    (0, sil, false, hist)       (score + e[sil]) + sil_score  c = sil, w = 0
+ *   An edge whose node both has children and ends a word emits both child candidates.  After a word ends, its last token may
+ *   repeat across frames through the repeat rule (ordinary CTC; a stated choice, the third-party code cannot be consulted).
+ *   Candidate id = (2 * c + w) * 16 + i: unique within a frame.
+ *   Merging: candidates with the same (node, tok, pb, hist) merge; the higher score survives, on equal scores the lower id; the
+ *   survivor keeps its own id and back-pointer.  (All members of a merge share the frame label c.)
+ *   Dropping: a candidate whose score is not > -inf is dropped (-inf and NaN).
+ *   Pruning: with best the highest score and beam_threshold finite, only candidates with score >= (float)(best - beam_threshold)
+ *   stay.  The new beam is the first beam_size candidates by descending score, then ascending id; that order is the next frame's
+ *   rank.  If nothing survives, the sequence ends with no hypothesis.
+ * End, after frame em_len[s] - 1: the complete hypotheses are those with node == 0 (an empty hist is a legal, empty transcript),
+ *   returned best first -- by score, then rank -- up to nbest; n_hyp[s] is how many.  It is 0 when none is complete, when em_len[s]
+ *   is outside [1, T'], or when a frame left no candidate.
+ * Per hypothesis: its words; its collapsed label sequence (blank frames dropped, runs collapsed, sil included: torchaudio's
+ *   CTCHypothesis.tokens); the first frame of each such label (timesteps); its score.
+ * hist identity on the device is a chained 64-bit hash (a collision is not handled).  There are no reductions and no log / exp in
+ * this arithmetic: scores are bit-identical to a statement that keeps fp32 and the written order of additions.
+ *
+ * eec_ctc_trie_pack is HOST code and needs no device:
+ *   spellings [offsets[n_words]] int32 token ids, flat; offsets [n_words + 1] int64, offsets[0] = 0, strictly ascending
+ *   sil: -1 = none.  image: image_bytes >= eec_ctc_trie_pack_bytes(n_words, offsets[n_words]) bytes of host memory, 8-byte
+ *       aligned; the caller copies it to the device (8-byte aligned) and passes it as `trie`.
+ *   n_nodes, n_shadowed: NULL or where the node count and the number of unreachable duplicate spellings are written
+ *   image layout, int32 units: header[16] = {magic, n_nodes, n_edges = n_nodes - 1, V, blank, sil, child_begin offset, child token
+ *       offset, word_of offset, total dwords, n_words, n_shadowed, 0..};  child_begin [n_nodes + 1]: the edges of node n are
+ *       child_begin[n] .. child_begin[n + 1];  child tokens: one BYTE per edge (padded to a dword), ascending within a node;
+ *       word_of [n_nodes]: the word a node ends, or -1.  Nodes are numbered breadth-first, children in token order, so that the
+ *       child reached by edge k is node k + 1: an edge needs no target.
+ *   eec_ctc_trie_pack_bytes is non-decreasing in each argument (it sizes the worst case, one node per token); 0 for n_words <= 0,
+ *       total_tokens < n_words, or an image of 2^31 dwords or more.
+ *   EEC_ERR_BAD_ARG: a null pointer (spellings, offsets, image), n_words <= 0, V < 2, blank / sil outside their ranges or equal,
+ *   offsets not ascending from 0, an empty spelling, a token outside [0, V) or equal to blank / sil.  EEC_ERR_UNSUPPORTED: V > 256.
+ *   EEC_ERR_WORKSPACE: image_bytes too small.
+ *
+ * eec_ctc_lexbeam_decode:
+ *   logp [n_seq, T', V] fp32 log-probs; em_len [n_seq] int32 frames of every sequence, or NULL = T' for all
+ *   trie: the image on the device; blank, sil (-1 none): must be the values it was packed with, as must V
+ *   beam_size 1..16, nbest 1..beam_size; word_score, sil_score; beam_threshold: +inf (any non-finite value) disables
+ *   words [n_seq][nbest][max_words] int32 word indices (file order); word_count [n_seq][nbest] the TRUE count, even above
+ *       max_words (the first max_words words are written; max_words = T' is always enough)
+ *   tokens, timesteps [n_seq][nbest][T'] int32 (timesteps may be NULL); token_count, scores [n_seq][nbest]; n_hyp [n_seq]
+ *   Absent hypotheses have score -inf and counts 0; entries past a hypothesis' counts are -1.
+ *   workspace: eec_ctc_lexbeam_workspace_bytes(n_seq, T', beam_size) bytes, 8-byte aligned: the back-pointers.
+ * EEC_ERR_BAD_ARG: a null required pointer, n_seq < 0, T' < 1, max_words < 1, blank / sil outside their ranges or equal, a
+ * misaligned image or workspace; n_seq == 0 is a successful no-op.  EEC_ERR_UNSUPPORTED: V > 256, V < 2, beam_size outside 1..16,
+ * nbest outside 1..beam_size.  EEC_ERR_WORKSPACE: workspace_bytes too small.  All checked before any device work.  A trie whose
+ * header does not carry the call's V, blank and sil gives n_hyp = 0 for every sequence and nothing else of it is read.
+ * One kernel on `stream`; no allocation, no synchronisation; graph-capturable; results are bit-identical run to run. */
+size_t eec_ctc_trie_pack_bytes(int n_words, int64_t total_tokens);
+int eec_ctc_trie_pack(const int32_t* spellings, const int64_t* offsets, int n_words, int V, int blank, int sil, void* image,
+                      size_t image_bytes, int32_t* n_nodes, int32_t* n_shadowed);
+size_t eec_ctc_lexbeam_workspace_bytes(int n_seq, int Tq, int beam_size);
+int eec_ctc_lexbeam_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                           int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                           int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
+                           int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream);
+
 /* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
  * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam
  * choice (util/beam_infer.py:309-383) --, for n_hyp hypotheses in one launch (one wavefront each; csrc/ctc_align.hip).

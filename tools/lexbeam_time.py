@@ -1,0 +1,141 @@
+"""Same-box timing of the lexicon-constrained CTC beam search (``eec_ctc_lexbeam_decode``, csrc/ctc_lexbeam.hip) on a synthetic
+trie of the real lexicon's measured size.  librispeech-bpe-256.lex (not part of this repository) has 89 114 words, 162 621 trie
+nodes, root degree 109, largest other degree 103, longest spelling 43, and never uses tokens 0, 1, 2, 126, 127; the spellings
+here are drawn from a seed to land on that size (the counts reached are printed).  Emissions: T' = 256, V = 256, log-softmax of
+noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/lexbeam_cases.py), beam 10, sil 126.
+
+    python tools/lexbeam_time.py [--reps 20] [--seqs 1,64,384] [--out profiles/lexbeam_time.json]          JSON lines
+
+* launch: device time by events around one call on prepared device buffers, median of ``--reps`` after three warm-up calls, and
+  per call in a train of 10 calls (the launch gap taken out).
+* yardstick: ``eec_ctc_beam_decode`` (the lexicon-free prefix beam search, unchanged by this tool's subject) on the same
+  emissions, in the same process, measured the same way.  It is another algorithm with other outputs: the ratio says what the
+  lexicon costs a caller who switches decoders, nothing else.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from early_exit_transformer_amd import capi  # noqa: E402
+from early_exit_transformer_amd.lexicon import TokenTrie  # noqa: E402
+import lexbeam_cases as L  # noqa: E402  (tests/: the emission generator)
+
+UNUSED = (0, 1, 2, 126, 127)
+
+
+def synthetic_spellings(n_words=89114, seed=1, mean_len=2.3, skew=1.0):
+    """Spellings over the 251 used tokens: 109 word-initial tokens, continuation tokens drawn from a skewed choice of 103, Poisson lengths
+    with a few up to 43, duplicates dropped.  The skew and the mean length are set so that the trie has about 164 000 nodes."""
+    rng = np.random.default_rng(seed)
+    toks = np.array([t for t in range(256) if t not in UNUSED])
+    first = rng.permutation(toks)[:109]
+    cont = rng.permutation(toks)[:103]
+    p_first = 1.0 / np.arange(1, 110) ** 0.9
+    p_cont = 1.0 / np.arange(1, 104) ** skew
+    draw = 2 * n_words  # duplicates are dropped (the real lexicon has none): draw more than needed
+    lens = np.clip(rng.poisson(mean_len, size=draw) + 1, 1, 43)
+    lens[:8] = [43, 30, 25, 21, 20, 19, 18, 17]
+    heads = rng.choice(first, size=draw, p=p_first / p_first.sum())
+    tails = rng.choice(cont, size=int(lens.sum()), p=p_cont / p_cont.sum())
+    out, seen, at = [], set(), 0
+    for n, h in zip(lens.tolist(), heads.tolist()):
+        sp = (h,) + tuple(tails[at:at + n - 1].tolist())
+        at += n - 1
+        if sp not in seen and len(out) < n_words:
+            seen.add(sp)
+            out.append(list(sp))
+    assert len(out) == n_words
+    return out
+
+
+def event_ms(fn, reps, per=1):
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(per):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / per)
+    return {"median": round(statistics.median(out), 4), "min": round(min(out), 4), "max": round(max(out), 4)}
+
+
+def prepared_calls(trie, em, beam, nbest, dev):
+    """The bare C calls of both decoders on buffers that are already on the device."""
+    lib = capi.load()
+    n, T, V = em.shape
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    words, wc, toks, tc, ts, nh = i32(n, nbest, T), i32(n, nbest), i32(n, nbest, T), i32(n, nbest), i32(n, nbest, T), i32(n)
+    sc = torch.empty((n, nbest), dtype=torch.float32, device=dev)
+    ws_bytes = lib.eec_ctc_lexbeam_workspace_bytes(n, T, beam)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    image = trie.on(dev)
+    ytok, ycnt, ysc = i32(n, T), i32(n), torch.empty((n,), dtype=torch.float32, device=dev)
+    yws = torch.empty(lib.eec_ctc_beam_workspace_bytes(n, T), dtype=torch.uint8, device=dev)
+    keep = (em, words, wc, toks, tc, ts, nh, sc, ws, image, ytok, ycnt, ysc, yws)
+
+    def lexbeam():
+        capi.check(lib.eec_ctc_lexbeam_decode(em.data_ptr(), n, T, V, None, image.data_ptr(), trie.blank, trie.sil, beam, nbest, 0.0, 0.0, 50.0, T,
+                                              words.data_ptr(), wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(),
+                                              nh.data_ptr(), ws.data_ptr(), ws_bytes, capi.stream_ptr(dev)), "eec_ctc_lexbeam_decode")
+        return keep
+
+    def yardstick():
+        capi.check(lib.eec_ctc_beam_decode(em.data_ptr(), n, T, V, trie.blank, beam, 0.95, yws.data_ptr(), ytok.data_ptr(), ycnt.data_ptr(),
+                                           ysc.data_ptr(), capi.stream_ptr(dev)), "eec_ctc_beam_decode")
+        return keep
+    return lexbeam, yardstick, nh
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--seqs", default="1,64,384")
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--beam", type=int, default=10)
+    ap.add_argument("--out", default=None, help="also write the records to this JSON file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a HIP device: there is nothing to time on the CPU")
+    dev = torch.device("cuda", 0)
+    records = [{"device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "torch": torch.__version__}]
+    spellings = synthetic_spellings()
+    trie = TokenTrie.from_spellings(spellings, 256, blank=0, sil=126)
+    image = trie._image.numpy().view(np.int32)
+    degree = np.diff(image[16:16 + trie.n_nodes + 1])
+    records.append({"what": "trie", "words": len(spellings), "nodes": trie.n_nodes, "shadowed": trie.n_shadowed, "root_degree": int(degree[0]),
+                    "largest_other_degree": int(degree[1:].max()), "longest_spelling": max(map(len, spellings)), "image_bytes": trie._image.numel()})
+    print(json.dumps(records[-1]), flush=True)
+    # the synthetic trie stands for the real one only while it has its size: nodes within 2 %, the same extreme degrees
+    assert abs(trie.n_nodes - 162621) <= 0.02 * 162621 and degree[0] == 109 and degree[1:].max() == 103 and trie.n_shadowed == 0, records[-1]
+    counts = [int(q) for q in args.seqs.split(",")]
+    pool = torch.from_numpy(L.emissions(3, spellings, max(counts), args.frames, 256, 0, 126)).to(dev)
+    for n in counts:
+        lexbeam, yardstick, nh = prepared_calls(trie, pool[:n].contiguous(), args.beam, 1, dev)
+        rec = {"what": "launch", "n_seq": n, "frames": args.frames, "beam": args.beam}
+        for name, call in (("lexbeam", lexbeam), ("ctc_beam_yardstick", yardstick)):
+            for _ in range(3):
+                call()
+            torch.cuda.synchronize()
+            rec[name + "_one_call_ms"] = event_ms(call, args.reps)
+            rec[name + "_train_of_10_ms_per_call"] = event_ms(call, max(args.reps // 4, 3), per=10)
+        rec["ratio_lexbeam_over_yardstick"] = round(rec["lexbeam_train_of_10_ms_per_call"]["median"] / rec["ctc_beam_yardstick_train_of_10_ms_per_call"]["median"], 2)
+        rec["sequences_with_a_hypothesis"] = int((nh > 0).sum())
+        records.append(rec)
+        print(json.dumps(rec), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(records, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
