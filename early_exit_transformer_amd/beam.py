@@ -16,8 +16,9 @@
 * ``BeamInference.decode_batch``  inference.py:18-62 (evaluate_batch_ae) for a whole padded batch: the encoder once per
   batch, then the searches of every exit and utterance in lockstep (``beam_search_batch``, csrc/decoder_batch.hip).
 * ``BeamInference.ctc_predict`` / ``ctc_predict_``  util/beam_infer.py:93-126: the lexicon-constrained CTC beam search with
-  N-best (torchaudio's ``ctc_decoder(lexicon=...)`` without a language model) on the device (``ctc_lexicon_decode``,
-  csrc/ctc_lexbeam.hip): words that are lexicon entries by construction, and the posterior of the top hypothesis.
+  N-best (torchaudio's ``ctc_decoder(lexicon=..., lm=..., lm_weight=LM_WEIGHT)``) on the device (``ctc_lexicon_decode``,
+  csrc/ctc_lexbeam.hip): words that are lexicon entries by construction, and the posterior of the top hypothesis; with ``lm=`` or
+  ``args.lm`` -- an ARPA file -- under a back-off n-gram word model (``lexicon.NGramLM``), else without one.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
@@ -29,7 +30,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .lexicon import TokenTrie, as_lexicon
+from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, encoder_lengths, greedy_ctc
 
 
@@ -150,9 +151,15 @@ class BeamInference:
     W_INS = 0        # the word score of the reference's six lexicon decoders (w_ins, util/beam_infer.py:54); its WORD_SCORE = -4
                      # (:41,74) belongs to the character-lexicon decoder of beam_predict, which is not served
 
-    def __init__(self, args=None, trie: Optional[TokenTrie] = None):
+    LM_WEIGHT = 1.0  # util/beam_infer.py:40 (its comment keeps 3.23, the value of the "bigger LM" setting)
+
+    def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None):
+        """``lm``: an ``NGramLM``, or the path of an ARPA file (None: ``args.lm`` if there is one) that is read at the first use
+        against the trie in use."""
         self.args = args
         self._trie = trie
+        self._lm = lm if lm is not None else getattr(args, "lm", None)
+        self._lm_read = None  # (the trie a path was read against, its NGramLM)
 
     sequence_length_penalty = staticmethod(sequence_length_penalty)
 
@@ -167,31 +174,42 @@ class BeamInference:
             self._trie = TokenTrie.from_files(self.args.lexicon, self.args.tokens, blank_token="@", sil_token="<pad>")
         return self._trie
 
-    def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size):
+    def _lexicon_lm(self, trie: TokenTrie) -> Optional[NGramLM]:
+        """The model given to the constructor; a path is read against ``trie`` at its first use (and again for another trie)."""
+        if self._lm is None or isinstance(self._lm, NGramLM):
+            return self._lm
+        if self._lm_read is None or self._lm_read[0] is not trie:
+            self._lm_read = (trie, NGramLM.from_arpa(self._lm, trie))
+        return self._lm_read[1]
+
+    def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size, lm_weight=None):
         """(transcript of the best hypothesis per utterance, scores [B, nbest] and n_hyp [B] on the host)."""
         trie = self._lexicon_trie(trie)
         nbest = self.N_BEST if nbest is None else nbest
+        lm = self._lexicon_lm(trie)
+        with_lm = {} if lm is None else {"lm": lm, "lm_weight": self.LM_WEIGHT if lm_weight is None else lm_weight}
         words, word_count, _, _, _, scores, n_hyp = ctc_lexicon_decode(emission, trie, beam_size=self._arg(beam_size, "beam_size"), nbest=nbest,
-                                                                       word_score=self.W_INS)
+                                                                       word_score=self.W_INS, **with_lm)
         words, word_count, n_hyp = words[:, 0].cpu(), word_count[:, 0].cpu().tolist(), n_hyp.cpu().tolist()
         texts = [" ".join(trie.words[w] for w in words[b, : word_count[b]].tolist()).strip() if n_hyp[b] else "" for b in range(len(n_hyp))]
         return texts, scores.cpu(), n_hyp
 
     def ctc_predict_(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,
-                     beam_size: Optional[int] = None) -> List[str]:
+                     beam_size: Optional[int] = None, lm_weight: Optional[float] = None) -> List[str]:
         """util/beam_infer.py:93-99: the transcript of the best lexicon-constrained hypothesis of every utterance of ``emission``
         [B, T', V] (on the device; it stays there), its words joined by spaces and stripped.  ``index`` selects the reference's
         per-exit decoder; all six are configured alike (w_ins = 0), so it is accepted and unused.  An utterance with no complete
-        hypothesis gives ``""`` (the reference would raise an IndexError: a stated divergence)."""
-        return self._lexicon_decode(emission, trie, nbest, beam_size)[0]
+        hypothesis gives ``""`` (the reference would raise an IndexError: a stated divergence).  With a model (``lm=`` of the
+        constructor or ``args.lm``) the search runs under it at ``lm_weight`` (None: ``LM_WEIGHT``)."""
+        return self._lexicon_decode(emission, trie, nbest, beam_size, lm_weight)[0]
 
     def ctc_predict(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,
-                    beam_size: Optional[int] = None):
+                    beam_size: Optional[int] = None, lm_weight: Optional[float] = None):
         """util/beam_infer.py:115-126: ``([transcript], pprob)`` for the FIRST utterance of ``emission`` [B, T', V]: the best
         hypothesis' words, and ``softmax(scores of the returned hypotheses)[0]`` as a 0-D tensor -- with the reference's
         ``N_BEST = 1`` that is always 1; ``nbest=`` returns a meaningful posterior.  No complete hypothesis: ``([""], 0.0)`` (the
-        reference would raise an IndexError: a stated divergence)."""
-        texts, scores, n_hyp = self._lexicon_decode(emission[:1], trie, nbest, beam_size)
+        reference would raise an IndexError: a stated divergence).  ``lm_weight``: as for ``ctc_predict_``."""
+        texts, scores, n_hyp = self._lexicon_decode(emission[:1], trie, nbest, beam_size, lm_weight)
         if n_hyp[0] == 0:
             return [""], torch.tensor(0.0)
         return [texts[0]], torch.softmax(scores[0, : n_hyp[0]].double(), dim=0)[0].float()

@@ -1,10 +1,13 @@
 // Lexicon-constrained CTC beam search on the device, with N-best: what the reference's ctc_predict / ctc_predict_ / beam_predict
 // call through torchaudio's ctc_decoder(lexicon=..., tokens=..., nbest=N_BEST, log_add=False, word_score=w_ins, sil_token="<pad>",
-// blank_token="@") without a language model (util/beam_infer.py:51-65, 85-126).  That decoder (flashlight-text) is third-party code
-// outside the reference tree and not installed: what is built is the published algorithm -- token-trie beam search under CTC,
-// Viterbi merging (log_add=False), no language model -- stated completely in include/eec.h; tests/lexbeam_cases.py is its
-// plain-Python statement and the judge of this kernel.  Parity with the third-party decoder is unpinned.
-// Out of scope: a language model, log_add=True (the reference's character-lexicon branch), unknown-word scores, beams over 16.
+// blank_token="@", lm=..., lm_weight=LM_WEIGHT) (util/beam_infer.py:39-78, 85-126), without a language model
+// (eec_ctc_lexbeam_decode) or with a back-off n-gram model read from an ARPA file (eec_ctc_lexbeam_lm_decode).  That decoder
+// (flashlight-text) is third-party code outside the reference tree and not installed: what is built is the published algorithm --
+// token-trie beam search under CTC, Viterbi merging (log_add=False), the word model's score at every word end and its end-of-sentence
+// term -- stated completely in include/eec.h; tests/lexbeam_cases.py and tests/lexbeam_lm_cases.py are its plain-Python statement
+// and the judge of this kernel.  Parity with the third-party decoder is unpinned.
+// Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
+// trie smearing, binary KenLM files, beams over 16.
 //
 // One 256-thread workgroup per sequence, one launch for the batch; thread c owns frame label c (V <= 256).  All candidates that
 // can merge share their frame label, so every merge is local to one thread.  Per frame:
@@ -23,6 +26,12 @@
 // the statement.  Latency-bound integer / scalar work over T' serial frames: it is sized to keep all E * B = 384 sequences of a
 // batch in flight at once (5.4 KB of LDS, well under two workgroups per CU), not for the roofline.  The real lexicon's image
 // (89 114 words, 162 621 nodes, 1.5 MB) is read-only and shared by all workgroups: it sits in L2.
+//
+// With a model (ctc_lexbeam_kernel<true>; <false> is the search without one) a hypothesis also carries an LM state, a node
+// of the packed n-gram image (layout in include/eec.h).  The back-off walk -- a binary search over the state's edge range, then the
+// suffix link -- runs where a word-end candidate is formed; only the candidate's score is kept, and the at most `beam` word-end
+// candidates that win a round redo their walk for the state they continue from.  After the last frame one thread adds the </s>
+// term to the complete hypotheses and orders the at most 16 of them by insertion.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -30,6 +39,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -51,7 +61,7 @@ struct LbBeam {
   int node, beg, deg;  // trie node, its first edge, its child count
   int tok;             // label of the last frame; -1 at the start.  "previous frame was blank" is tok == blank || tok < 0
   int ntok, nw;        // collapsed labels and words so far
-  int pad;
+  int pad;             // with a model: the LM state, a node of the n-gram image
 };
 
 // the history hash's step, as cb_mix in ctc_beam.hip
@@ -73,28 +83,105 @@ struct LbArgs {
   int2* backptr;
 };
 
-__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a) {
+struct LbLmArgs : LbArgs {
+  const int* lm;
+  float lm_weight;
+};
+
+constexpr int kLmMagic = 0x4E434545;  // "EECN"
+constexpr int kLmHeader = 16;
+constexpr int kLmMaxOrder = 5;
+
+// the n-gram image's sections (include/eec.h)
+struct LmView {
+  const int *begin, *eword, *suffix, *map;
+  const float *logp, *backoff;
+  int top_begin, bos, eos;
+};
+
+// log10 p(v | state s) by the back-off walk of include/eec.h, fp32 additions in the walk's order; `next`: the state after v.
+// The root finds every word without a search (the unigram of word v is node v + 1), so the walk ends after at most `order` steps;
+// the bound keeps a damaged image from looping.
+__device__ __forceinline__ float lm_walk(const LmView& m, int s, int v, int& next) {
+  float acc = 0.f;
+  for (int d = 0; d <= kLmMaxOrder; ++d) {
+    int x = v + 1;
+    if (s != 0) {
+      int lo = m.begin[s];
+      const int end = m.begin[s + 1];
+      int hi = end;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (m.eword[mid] < v)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      x = (lo < end && m.eword[lo] == v) ? lo + 1 : -1;
+    }
+    if (x >= 0) {
+      acc = acc + m.logp[x];
+      next = x < m.top_begin ? x : m.suffix[x];
+      return acc;
+    }
+    acc = acc + m.backoff[s];
+    s = m.suffix[s];
+  }
+  next = 0;
+  return acc;
+}
+
+// LM = false is the model-free search; LM = true adds the model's score at word ends and at the end of the sentence
+// s + lm_weight * acc, the product rounded on its own: the two operations must not contract into a fused multiply-add
+// (__fmul_rn / __fadd_rn are plain operators to this compiler and do contract)
+__device__ __forceinline__ float lm_add(float s, float lm_weight, float acc) {
+#pragma clang fp contract(off)
+  const float term = lm_weight * acc;
+  return s + term;
+}
+
+template <bool LM, typename Args>
+__device__ __forceinline__ bool lm_fits(const Args& a) {
+  if constexpr (LM)
+    return a.lm[0] == kLmMagic && a.lm[5] == a.trie[10];
+  else
+    return true;
+}
+
+template <bool LM>
+__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::conditional_t<LM, LbLmArgs, LbArgs> a) {
   __shared__ LbBeam bufs[2][kLbMaxBeam];
   __shared__ __attribute__((aligned(16))) unsigned char slot[kLbMaxBeam][256];  // edge offset of label c below beam i's node
   __shared__ float red_v[4];
   __shared__ int red_id[4];
   __shared__ int fin_rank[kLbMaxBeam], fin_ntok[kLbMaxBeam], fin_nw[kLbMaxBeam], fin_n;
+  __shared__ float fin_score[LM ? kLbMaxBeam : 1];  // with a model: the final scores, </s> term included
   const int seq = blockIdx.x, c = threadIdx.x, lane = c & 63, w = c >> 6;
   const int V = a.V, blank = a.blank, sil = a.sil, beam = a.beam, Tq = a.Tq;
 
   // a trie that is not the one the call describes is not read past its header: every sequence ends without a hypothesis
-  const bool ok = a.trie[0] == kLbMagic && a.trie[1] >= 1 && a.trie[3] == V && a.trie[4] == blank && a.trie[5] == sil;
+  // ... and so is a model that is none, or was packed for another lexicon
+  const bool ok = a.trie[0] == kLbMagic && a.trie[1] >= 1 && a.trie[3] == V && a.trie[4] == blank && a.trie[5] == sil && lm_fits<LM>(a);
   int L = a.em_len ? a.em_len[seq] : Tq;
   if (!ok || L < 1 || L > Tq) L = 0;
   const int* cbeg = a.trie + (ok ? a.trie[6] : 0);
   const unsigned char* ctok = (const unsigned char*)(a.trie + (ok ? a.trie[7] : 0));
   const int* word_of = a.trie + (ok ? a.trie[8] : 0);
   const int root_deg = L > 0 ? cbeg[1] : 0;
+  LmView m = {};
+  if constexpr (LM) {
+    const int* lm = a.lm;
+    if (ok) {
+      m.begin = lm + lm[9], m.eword = lm + lm[10], m.suffix = lm + lm[13], m.map = lm + lm[14];
+      m.logp = (const float*)(lm + lm[11]), m.backoff = (const float*)(lm + lm[12]);
+      m.top_begin = lm[8], m.bos = lm[6], m.eos = lm[7];
+    }
+  }
 
   const float* lp_seq = a.logp + (size_t)seq * Tq * V;
   int2* bp = a.backptr + (size_t)seq * Tq * beam;
   int cur = 0, nb = 1;
-  if (c == 0) bufs[0][0] = LbBeam{0x243F6A8885A308D3ull, 0.f, 0, 0, root_deg, -1, 0, 0, 0};
+  if (c == 0) bufs[0][0] = LbBeam{0x243F6A8885A308D3ull, 0.f, 0, 0, root_deg, -1, 0, 0, LM ? m.bos : 0};
   float lp_next = (L > 0 && c < V) ? lp_seq[c] : -INFINITY;
   __syncthreads();
 
@@ -151,6 +238,10 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
             }
             if (word >= 0) {
               s1[i] = base + a.word_score;
+              if constexpr (LM) {
+                int next;
+                s1[i] = lm_add(s1[i], a.lm_weight, lm_walk(m, b.pad, m.map[word], next));
+              }
               wd[i] = word;
               h1[i] = lb_mix(b.hash, word);
             }
@@ -227,7 +318,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
         const int ii = gid & 15;
         const bool end = (gid >> 4) & 1;
         const LbBeam par = B[ii];
-        LbBeam e = LbBeam{par.hash, gv, 0, 0, root_deg, c, par.ntok + (c != blank && c != par.tok), par.nw + end, 0};
+        LbBeam e = LbBeam{par.hash, gv, 0, 0, root_deg, c, par.ntok + (c != blank && c != par.tok), par.nw + end, LM ? par.pad : 0};
         int word = 0;
 #pragma unroll
         for (int i = 0; i < kLbMaxBeam; ++i)
@@ -241,6 +332,8 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
               s0[i] = -INFINITY;
             }
           }
+        if constexpr (LM)
+          if (end) lm_walk(m, par.pad, m.map[word - 1], e.pad);  // the walk again, for the state this time
         N[r] = e;
         bp[(size_t)t * beam + r] = make_int2((ii << 16) | c, word);
         rescan = true;
@@ -256,9 +349,27 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
   // the complete hypotheses (node 0) in rank order are best first; one thread walks each one's back-pointers
   if (c == 0) {
     int n = 0;
-    if (L > 0)
-      for (int i = 0; i < nb; ++i)
-        if (bufs[cur][i].node == 0 && n < a.nbest) fin_rank[n++] = i;
+    if constexpr (LM) {
+      // ... after the </s> term they no longer are: ordered by (final score descending, rank ascending), one thread's insertion
+      if (L > 0)
+        for (int i = 0; i < nb; ++i) {
+          const LbBeam e = bufs[cur][i];
+          if (e.node != 0) continue;
+          float f = e.score;
+          if (m.eos >= 0) {
+            int next;
+            f = lm_add(f, a.lm_weight, lm_walk(m, e.pad, m.eos, next));
+          }
+          int k = n++;
+          for (; k > 0 && f > fin_score[k - 1]; --k) fin_score[k] = fin_score[k - 1], fin_rank[k] = fin_rank[k - 1];
+          fin_score[k] = f, fin_rank[k] = i;
+        }
+      n = min(n, a.nbest);
+    } else {
+      if (L > 0)
+        for (int i = 0; i < nb; ++i)
+          if (bufs[cur][i].node == 0 && n < a.nbest) fin_rank[n++] = i;
+    }
     fin_n = n;
     a.n_hyp[seq] = n;
   }
@@ -270,7 +381,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
     if (c < fin_n) {
       int k = fin_rank[c];
       const LbBeam e = bufs[cur][k];
-      n = e.ntok, nw = e.nw, score = e.score;
+      n = e.ntok, nw = e.nw, score = LM ? fin_score[c] : e.score;
       int* tok_out = a.tokens + o * Tq;
       int* ts_out = a.timesteps ? a.timesteps + o * Tq : nullptr;
       int* w_out = a.words + o * a.max_words;
@@ -311,6 +422,46 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const LbArgs a)
 
 static size_t lb_image_dwords(unsigned long long nodes) {  // nodes >= 1
   return (size_t)(kLbHeader + (nodes + 1) + (nodes - 1 + 3) / 4 + nodes + 1) & ~(size_t)1;
+}
+
+static size_t lm_image_dwords(unsigned long long nodes, unsigned long long lex_words) {  // nodes >= 1
+  return (size_t)(kLmHeader + (nodes + 1) + (nodes - 1) + 3 * nodes + lex_words + 1) & ~(size_t)1;
+}
+
+// the checks and the launch of both entries; lm == nullptr: the model-free kernel
+static int lb_decode(const char* who, const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                     int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words, int32_t* words,
+                     int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores, int32_t* n_hyp, void* workspace,
+                     size_t workspace_bytes, void* stream, bool with_lm, const void* lm, float lm_weight) {
+  using eech::fail;
+  const std::string me(who);
+  if (n_seq < 0 || Tq < 1 || max_words < 1) return fail(EEC_ERR_BAD_ARG, me + ": needs n_seq >= 0, Tq >= 1, max_words >= 1");
+  if (V > 256 || V < 2 || beam_size < 1 || beam_size > kLbMaxBeam || nbest < 1 || nbest > beam_size)
+    return fail(EEC_ERR_UNSUPPORTED, me + ": needs 2 <= V <= 256, 1 <= beam_size <= " + std::to_string(kLbMaxBeam) + ", 1 <= nbest <= beam_size");
+  if (blank < 0 || blank >= V || sil < -1 || sil >= V || sil == blank)
+    return fail(EEC_ERR_BAD_ARG, me + ": needs blank in [0, V), sil -1 or in [0, V) and not the blank");
+  if (with_lm && !std::isfinite(lm_weight)) return fail(EEC_ERR_BAD_ARG, me + ": lm_weight must be finite");
+  if (with_lm && !lm) return fail(EEC_ERR_BAD_ARG, me + ": null argument (lm)");
+  if (n_seq == 0) return 0;
+  if (!logp || !trie || !words || !word_count || !tokens || !token_count || !scores || !n_hyp || !workspace)
+    return fail(EEC_ERR_BAD_ARG, me + ": null argument");
+  if (((uintptr_t)trie | (uintptr_t)workspace | (uintptr_t)lm) & 7) return fail(EEC_ERR_BAD_ARG, me + (with_lm ? ": trie, lm and workspace must be 8-byte aligned" : ": trie and workspace must be 8-byte aligned"));
+  if (workspace_bytes < eec_ctc_lexbeam_workspace_bytes(n_seq, Tq, beam_size))
+    return fail(EEC_ERR_WORKSPACE, me + ": workspace below eec_ctc_lexbeam_workspace_bytes()");
+  LbLmArgs a;
+  a.logp = logp, a.em_len = em_len, a.trie = (const int*)trie;
+  a.Tq = Tq, a.V = V, a.blank = blank, a.sil = sil, a.beam = beam_size, a.nbest = nbest, a.max_words = max_words;
+  a.use_thr = std::isfinite(beam_threshold) ? 1 : 0;
+  a.word_score = word_score, a.sil_score = sil_score, a.beam_threshold = beam_threshold;
+  a.words = words, a.word_count = word_count, a.tokens = tokens, a.token_count = token_count, a.timesteps = timesteps, a.n_hyp = n_hyp;
+  a.scores = scores, a.backptr = (int2*)workspace;
+  a.lm = (const int*)lm, a.lm_weight = lm_weight;
+  if (with_lm)
+    hipLaunchKernelGGL(ctc_lexbeam_kernel<true>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(ctc_lexbeam_kernel<false>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbArgs&)a);
+  EEC_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace eec
@@ -395,6 +546,128 @@ int eec_ctc_trie_pack(const int32_t* spellings, const int64_t* offsets, int n_wo
   return 0;
 }
 
+size_t eec_ngram_pack_bytes(int order, const int64_t* counts, int lex_words) {
+  if (order < 1 || order > eec::kLmMaxOrder || !counts || lex_words <= 0 || counts[0] <= 0) return 0;
+  unsigned long long nodes = 1;
+  for (int n = 0; n < order; ++n) {
+    if (counts[n] < 0 || counts[n] >= ((int64_t)1 << 31)) return 0;
+    nodes += (unsigned long long)counts[n];
+  }
+  const size_t dwords = eec::lm_image_dwords(nodes, (unsigned long long)lex_words);
+  return dwords >= ((size_t)1 << 31) ? 0 : dwords * 4;  // the kernel indexes the image with int32
+}
+
+int eec_ngram_pack(int order, const int64_t* counts, const int32_t* const* words, const float* const* logp, const float* const* backoff,
+                   const int32_t* word_map, int lex_words, int bos_word, int eos_word, void* image, size_t image_bytes, int32_t* n_nodes) {
+  using namespace eec;
+  using eech::fail;
+  if (order < 1 || order > kLmMaxOrder) return fail(EEC_ERR_UNSUPPORTED, "eec_ngram_pack: the order must be 1 .. " + std::to_string(kLmMaxOrder));
+  if (!counts || !words || !logp || !backoff || !word_map || !image)
+    return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: null argument (counts, words, logp, backoff, word_map, image)");
+  if (lex_words <= 0 || counts[0] <= 0) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: needs lex_words > 0 and at least one unigram");
+  for (int n = 0; n < order; ++n) {
+    if (counts[n] < 0) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: a negative count");
+    if (counts[n] > 0 && (!words[n] || !logp[n] || !backoff[n])) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: null array of order " + std::to_string(n + 1));
+  }
+  const size_t need = eec_ngram_pack_bytes(order, counts, lex_words);
+  if (need == 0) return fail(EEC_ERR_UNSUPPORTED, "eec_ngram_pack: the image would pass 2^31 dwords");
+  if (image_bytes < need) return fail(EEC_ERR_WORKSPACE, "eec_ngram_pack: image_bytes below eec_ngram_pack_bytes()");
+  const int W = (int)counts[0];
+  if (bos_word < -1 || bos_word >= W || eos_word < -1 || eos_word >= W)
+    return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: bos_word and eos_word must be -1 or an LM word");
+  for (int i = 0; i < lex_words; ++i)
+    if (word_map[i] < 0 || word_map[i] >= W) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: word_map[" + std::to_string(i) + "] is no LM word");
+  for (int n = 0; n < order; ++n)
+    for (int64_t i = 0; i < counts[n]; ++i)
+      if (!std::isfinite(logp[n][i]) || !std::isfinite(backoff[n][i]))
+        return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: a non-finite value in " + std::to_string(n + 1) + "-gram " + std::to_string(i));
+
+  int level[kLmMaxOrder + 2];  // level[n]: the first node of depth n; level[order + 1]: the node count
+  level[0] = 0, level[1] = 1;
+  for (int n = 1; n <= order; ++n) level[n + 1] = level[n] + (int)counts[n - 1];
+  const int nodes = level[order + 1], edges = nodes - 1;
+  int32_t* img = (int32_t*)image;
+  memset(img, 0, need);
+  const int off_begin = kLmHeader, off_eword = off_begin + nodes + 1, off_logp = off_eword + edges, off_backoff = off_logp + nodes,
+            off_suffix = off_backoff + nodes, off_map = off_suffix + nodes;
+  int32_t *begin = img + off_begin, *eword = img + off_eword, *suffix = img + off_suffix;
+  float *lp = (float*)(img + off_logp), *bo = (float*)(img + off_backoff);
+  for (int x = 0; x <= nodes; ++x) begin[x] = edges;  // a node without children: an empty range at its place
+
+  // the child of `node` labelled v, or -1; the ranges of all shallower levels are final when a level is built
+  auto child = [&](int node, int v) {
+    if (node == 0) return v + 1;
+    int lo = begin[node], hi = begin[node + 1];
+    const int end = hi;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (eword[mid] < v)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    return lo < end && eword[lo] == v ? lo + 1 : -1;
+  };
+  auto find = [&](const int32_t* w, int len) {  // the node of the n-gram w[0 .. len), or -1
+    int at = 0;
+    for (int k = 0; k < len && at >= 0; ++k) at = child(at, w[k]);
+    return at;
+  };
+
+  // unigrams: LM word v is node v + 1, edge v of the root
+  begin[0] = 0;
+  std::vector<char> seen(W, 0);
+  for (int i = 0; i < W; ++i) {
+    const int v = words[0][i];
+    if (v < 0 || v >= W) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: unigram " + std::to_string(i) + " is outside [0, counts[0])");
+    if (seen[v]) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: unigram " + std::to_string(i) + " is a duplicate");
+    seen[v] = 1;
+    eword[v] = v, lp[v + 1] = logp[0][i], bo[v + 1] = backoff[0][i];
+  }
+  // higher orders, breadth-first: the nodes of depth n in the order of (parent, last word)
+  for (int n = 2; n <= order; ++n) {
+    const int64_t cnt = counts[n - 1];
+    const int32_t* w = words[n - 1];
+    std::vector<std::pair<std::pair<int, int>, int64_t>> ent((size_t)cnt);  // ((parent, word), index)
+    for (int64_t i = 0; i < cnt; ++i) {
+      for (int k = 0; k < n; ++k)
+        if (w[i * n + k] < 0 || w[i * n + k] >= W)
+          return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: " + std::to_string(n) + "-gram " + std::to_string(i) + " has a word outside [0, counts[0])");
+      const int parent = find(w + i * n, n - 1);
+      if (parent < 0) return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: the prefix of " + std::to_string(n) + "-gram " + std::to_string(i) + " is absent");
+      ent[(size_t)i] = {{parent, w[i * n + n - 1]}, i};
+    }
+    std::sort(ent.begin(), ent.end());
+    for (int64_t r = 0; r < cnt; ++r) {
+      if (r > 0 && ent[(size_t)r].first == ent[(size_t)r - 1].first)
+        return fail(EEC_ERR_BAD_ARG, "eec_ngram_pack: " + std::to_string(n) + "-gram " + std::to_string(ent[(size_t)r].second) + " is a duplicate");
+      const int x = level[n] + (int)r;
+      eword[x - 1] = ent[(size_t)r].first.second;
+      lp[x] = logp[n - 1][ent[(size_t)r].second], bo[x] = backoff[n - 1][ent[(size_t)r].second];
+    }
+    // the parents' ranges: edges level[n] - 1 .. in parent order
+    int64_t r = 0;
+    for (int p = level[n - 1]; p < level[n]; ++p) {
+      begin[p] = level[n] - 1 + (int)r;
+      while (r < cnt && ent[(size_t)r].first.first == p) ++r;
+    }
+    for (int x = level[n]; x <= nodes; ++x) begin[x] = level[n] - 1 + (int)cnt;
+    // suffix links of this level: the longest proper suffix that is a node; the last word's unigram at worst
+    for (int64_t q = 0; q < cnt; ++q) {
+      const int32_t* g = w + ent[(size_t)q].second * n;
+      int to = -1;
+      for (int k = 1; k < n && to < 0; ++k) to = find(g + k, n - k);
+      suffix[level[n] + (int)q] = to;
+    }
+  }
+  for (int i = 0; i < lex_words; ++i) img[off_map + i] = word_map[i];
+  img[0] = kLmMagic, img[1] = order, img[2] = nodes, img[3] = edges, img[4] = W, img[5] = lex_words, img[6] = bos_word + 1, img[7] = eos_word;
+  img[8] = level[order], img[9] = off_begin, img[10] = off_eword, img[11] = off_logp, img[12] = off_backoff, img[13] = off_suffix;
+  img[14] = off_map, img[15] = off_map + lex_words;
+  if (n_nodes) *n_nodes = nodes;
+  return 0;
+}
+
 size_t eec_ctc_lexbeam_workspace_bytes(int n_seq, int Tq, int beam_size) {
   return n_seq > 0 && Tq > 0 && beam_size > 0 ? (size_t)n_seq * Tq * beam_size * sizeof(int2) : 0;
 }
@@ -403,30 +676,18 @@ int eec_ctc_lexbeam_decode(const float* logp, int n_seq, int Tq, int V, const in
                            int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
                            int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
                            int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream) {
-  using namespace eec;
-  using eech::fail;
-  if (n_seq < 0 || Tq < 1 || max_words < 1) return fail(EEC_ERR_BAD_ARG, "eec_ctc_lexbeam_decode: needs n_seq >= 0, Tq >= 1, max_words >= 1");
-  if (V > 256 || V < 2 || beam_size < 1 || beam_size > kLbMaxBeam || nbest < 1 || nbest > beam_size)
-    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_lexbeam_decode: needs 2 <= V <= 256, 1 <= beam_size <= " + std::to_string(kLbMaxBeam) +
-                                         ", 1 <= nbest <= beam_size");
-  if (blank < 0 || blank >= V || sil < -1 || sil >= V || sil == blank)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_lexbeam_decode: needs blank in [0, V), sil -1 or in [0, V) and not the blank");
-  if (n_seq == 0) return 0;
-  if (!logp || !trie || !words || !word_count || !tokens || !token_count || !scores || !n_hyp || !workspace)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_lexbeam_decode: null argument");
-  if (((uintptr_t)trie | (uintptr_t)workspace) & 7) return fail(EEC_ERR_BAD_ARG, "eec_ctc_lexbeam_decode: trie and workspace must be 8-byte aligned");
-  if (workspace_bytes < eec_ctc_lexbeam_workspace_bytes(n_seq, Tq, beam_size))
-    return fail(EEC_ERR_WORKSPACE, "eec_ctc_lexbeam_decode: workspace below eec_ctc_lexbeam_workspace_bytes()");
-  LbArgs a;
-  a.logp = logp, a.em_len = em_len, a.trie = (const int*)trie;
-  a.Tq = Tq, a.V = V, a.blank = blank, a.sil = sil, a.beam = beam_size, a.nbest = nbest, a.max_words = max_words;
-  a.use_thr = std::isfinite(beam_threshold) ? 1 : 0;
-  a.word_score = word_score, a.sil_score = sil_score, a.beam_threshold = beam_threshold;
-  a.words = words, a.word_count = word_count, a.tokens = tokens, a.token_count = token_count, a.timesteps = timesteps, a.n_hyp = n_hyp;
-  a.scores = scores, a.backptr = (int2*)workspace;
-  hipLaunchKernelGGL(ctc_lexbeam_kernel, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
-  EEC_HIP(hipGetLastError());
-  return 0;
+  return eec::lb_decode("eec_ctc_lexbeam_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score, sil_score,
+                        beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace, workspace_bytes,
+                        stream, false, nullptr, 0.f);
+}
+
+int eec_ctc_lexbeam_lm_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                              int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                              int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
+                              int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm, float lm_weight) {
+  return eec::lb_decode("eec_ctc_lexbeam_lm_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score, sil_score,
+                        beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace, workspace_bytes,
+                        stream, true, lm, lm_weight);
 }
 
 }  // extern "C"

@@ -63,10 +63,13 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
 
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
-                       beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None):
+                       beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None, lm=None,
+                       lm_weight: float = 0.0):
     """Lexicon-constrained CTC beam search with N-best of [n, T', V] log-probs on the device (eec_ctc_lexbeam_decode): the
-    decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)`` without a language
-    model, util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
+    decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)``,
+    util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
+    ``lm``: None, or a ``lexicon.NGramLM`` packed for this trie -- its score times ``lm_weight`` joins at every word end and at the
+    end of the sentence (eec_ctc_lexbeam_lm_decode), and ``scores`` are the final scores.
     ``trie``: a ``lexicon.TokenTrie`` (it carries V, blank and sil); ``em_len`` [n] frames per sequence (None: T'); ``max_words``
     (None: T', always enough): the words kept per hypothesis -- ``word_count`` is the true count even above it.  Returns
     ``(words [n, nbest, max_words] int32 indices into trie.words, word_count [n, nbest], tokens [n, nbest, T'], token_count [n, nbest],
@@ -78,6 +81,8 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     n, Tq, V = logp.shape
     if V != trie.V:
         raise ValueError(f"ctc_lexicon_decode: the emission has {V} labels, the trie was packed for {trie.V}")
+    if lm is not None and lm.n_words != len(trie.words):
+        raise ValueError(f"ctc_lexicon_decode: the model was packed for a lexicon of {lm.n_words} words, the trie has {len(trie.words)}")
     dev = logp.device
     lib = capi.load()
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
@@ -91,11 +96,14 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     ws_bytes = lib.eec_ctc_lexbeam_workspace_bytes(n, Tq, beam_size)
     ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_lexbeam_decode(logp.data_ptr(), n, Tq, V, None if em_len is None else em_len.data_ptr(), trie.on(dev).data_ptr(),
-                                              trie.blank, trie.sil, int(beam_size), int(nbest), float(word_score), float(sil_score),
-                                              float(beam_threshold), max_words, words.data_ptr(), word_count.data_ptr(), tokens.data_ptr(),
-                                              token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
-                                              ws.data_ptr(), ws_bytes, stream_ptr(dev)), "eec_ctc_lexbeam_decode")
+        args = (logp.data_ptr(), n, Tq, V, None if em_len is None else em_len.data_ptr(), trie.on(dev).data_ptr(), trie.blank, trie.sil,
+                int(beam_size), int(nbest), float(word_score), float(sil_score), float(beam_threshold), max_words, words.data_ptr(),
+                word_count.data_ptr(), tokens.data_ptr(), token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
+                ws.data_ptr(), ws_bytes, stream_ptr(dev))
+        if lm is None:
+            capi.check(lib.eec_ctc_lexbeam_decode(*args), "eec_ctc_lexbeam_decode")
+        else:
+            capi.check(lib.eec_ctc_lexbeam_lm_decode(*args, lm.on(dev).data_ptr(), float(lm_weight)), "eec_ctc_lexbeam_lm_decode")
     return words, word_count, tokens, token_count, timesteps, scores, n_hyp
 
 

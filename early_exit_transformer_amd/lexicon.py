@@ -5,11 +5,14 @@ per word in the reference -- is one call into libeec.so for all words at once (`
 There is no CPU path: without a HIP device ``nearest`` raises, and with it everything that has a word to look up.
 
 ``TokenTrie`` is the other use of a lexicon: the spellings of its words as token sequences, packed into the trie image that the
-lexicon-constrained CTC beam search walks (``ctc.ctc_lexicon_decode``, csrc/ctc_lexbeam.hip; layout in include/eec.h)."""
+lexicon-constrained CTC beam search walks (``ctc.ctc_lexicon_decode``, csrc/ctc_lexbeam.hip; layout in include/eec.h).
+``NGramLM`` is the back-off n-gram word model that search can take along: an ARPA file read against a trie's words and packed into
+the n-gram image of include/eec.h (``eec_ngram_pack``, host code)."""
 from __future__ import annotations
 
 import ctypes as C
 import io
+import math
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -212,6 +215,165 @@ class TokenTrie:
 
     def __len__(self) -> int:
         return len(self.words)
+
+    def on(self, dev: torch.device) -> Tensor:
+        """The packed image on ``dev`` (uploaded once; follows a change of device)."""
+        if self._resident is None or self._resident[0] != dev:
+            self._resident = (dev, self._image.to(dev))
+        return self._resident[1]
+
+
+class NGramLM:
+    """A back-off n-gram word model over the words of one ``TokenTrie``, packed once (``eec_ngram_pack``, host code) and kept on the
+    device.  ``order``; ``n_grams``: the kept n-grams per order; ``n_nodes`` = 1 + their sum; ``n_words``: the word count of the
+    lexicon it was packed for (the decoder refuses another trie); ``vocab``: the LM words, their index the LM word id;
+    ``word_map`` [n_words]: the LM word of every lexicon word (the ``<unk>`` word where the model lacks it); ``bos`` / ``eos`` /
+    ``unk``: the LM words of ``<s>`` / ``</s>`` / ``<unk>`` or -1."""
+
+    BOS, EOS, UNK = "<s>", "</s>", "<unk>"
+    MAX_ORDER = 5  # include/eec.h
+
+    def __init__(self, words: Sequence[np.ndarray], logp: Sequence[np.ndarray], backoff: Sequence[np.ndarray], word_map, bos: int = -1,
+                 eos: int = -1, unk: int = -1, vocab: Optional[Sequence[str]] = None):
+        """From arrays per order, as ``eec_ngram_pack`` takes them: ``words[n-1]`` int32 [count_n, n] LM word ids, ``logp[n-1]`` and
+        ``backoff[n-1]`` fp32 [count_n]; the unigrams are a permutation of the LM words 0 .. W - 1."""
+        order = len(words)
+        if not 1 <= order <= self.MAX_ORDER or len(logp) != order or len(backoff) != order:
+            raise ValueError(f"NGramLM: orders 1 to {self.MAX_ORDER} are served, with one array of words, logp and backoff each; got {order}")
+        ids = [np.ascontiguousarray(np.asarray(w, dtype=np.int32).reshape(-1, n + 1)) for n, w in enumerate(words)]
+        lps = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in logp]
+        bos_ = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in backoff]
+        if any(len(a) != len(b) or len(a) != len(c) for a, b, c in zip(ids, lps, bos_)):
+            raise ValueError("NGramLM: the words, logp and backoff arrays of an order differ in length")
+        self.word_map = np.ascontiguousarray(word_map, dtype=np.int32).reshape(-1)
+        self.order, self.n_grams, self.n_words = order, [len(a) for a in ids], int(self.word_map.size)
+        self.bos, self.eos, self.unk = int(bos), int(eos), int(unk)
+        self.vocab = None if vocab is None else list(vocab)
+        lib = capi.load()
+        counts = np.array(self.n_grams, dtype=np.int64)
+        nbytes = lib.eec_ngram_pack_bytes(order, counts.ctypes.data, self.n_words)
+        image = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
+        ptrs = lambda arrays: (C.c_void_p * order)(*[a.ctypes.data if a.size else None for a in arrays])  # noqa: E731
+        n_nodes = C.c_int32()
+        capi.check(lib.eec_ngram_pack(order, counts.ctypes.data, ptrs(ids), ptrs(lps), ptrs(bos_), self.word_map.ctypes.data if self.n_words else None,
+                                      self.n_words, self.bos, self.eos, image.data_ptr(), nbytes, C.byref(n_nodes)), "eec_ngram_pack")
+        self.n_nodes = n_nodes.value
+        self._image = image[: 4 * int(image[60:64].view(torch.int32))]  # header[15]: the dwords actually used
+        self._resident = None  # (device, device copy)
+
+    @classmethod
+    def from_arpa(cls, path, trie: "TokenTrie", normalize=None) -> "NGramLM":
+        """The ARPA file ``path`` read against ``trie.words``: an LM word is matched exactly, after ``normalize`` (None: identity;
+        ``<s>``, ``</s>`` and ``<unk>`` are matched as they stand) was applied to it; lexicon entries with the same string share an
+        LM word; a lexicon word the model lacks scores as ``<unk>``.  N-grams with a word outside the lexicon and those three can
+        never be asked for and are dropped.  The file's log10 values are kept as they are, rounded to fp32.  Raises a ``ValueError``
+        that names file and line for a malformed file, and one that counts the missing words when the model has no ``<unk>``."""
+        lex = set(trie.words)
+        special = (cls.BOS, cls.EOS, cls.UNK)
+
+        def bad(line_no, what):
+            return ValueError(f"NGramLM: {path}:{line_no}: {what}")
+
+        declared: Dict[int, int] = {}
+        vocab: List[str] = []
+        ids: Dict[str, int] = {}    # kept LM word (after normalize) -> LM word id
+        outside = set()             # unigrams that were dropped
+        grams: List[Dict[tuple, int]] = []  # per order: kept n-gram (ids) -> its row
+        rows: List[Tuple[list, list, list]] = []
+        n, seen_in_section, section_line, state = 0, 0, 0, "head"
+
+        def close_section(line_no):
+            if n and seen_in_section != declared[n]:
+                raise bad(line_no, f"the {n}-gram section that began at line {section_line} holds {seen_in_section} n-grams, \\data\\ states {declared[n]}")
+
+        line_no = 0
+        with io.open(path, encoding="utf-8") as f:
+            for line_no, line in enumerate(f, 1):
+                line = line.strip()
+                if not line:
+                    continue
+                if state == "head":
+                    if line == "\\data\\":
+                        state = "data"
+                    continue
+                if line.startswith("\\"):
+                    close_section(line_no)
+                    if line == "\\end\\":
+                        state = "end"
+                        break
+                    try:
+                        want = int(line[1:line.index("-grams:")])
+                    except ValueError:
+                        raise bad(line_no, f"expected \\N-grams: or \\end\\, got {line!r}") from None
+                    if want != n + 1 or want not in declared:
+                        raise bad(line_no, f"section {line!r} where the section of order {n + 1} {'is' if n + 1 in declared else 'is not'} expected")
+                    n, seen_in_section, section_line, state = want, 0, line_no, "grams"
+                    grams.append({})
+                    rows.append(([], [], []))
+                    continue
+                if state == "data":
+                    if not line.startswith("ngram ") or "=" not in line:
+                        raise bad(line_no, f"expected 'ngram N=count', got {line!r}")
+                    try:
+                        k, count = (int(v) for v in line[6:].split("="))
+                    except ValueError:
+                        raise bad(line_no, f"expected 'ngram N=count', got {line!r}") from None
+                    if k > cls.MAX_ORDER:
+                        raise bad(line_no, f"order {k}: orders above {cls.MAX_ORDER} are not served")
+                    if k != len(declared) + 1 or count < 0:
+                        raise bad(line_no, f"'ngram {k}={count}' where order {len(declared) + 1} is expected")
+                    declared[k] = count
+                    continue
+                fields = line.split()
+                if len(fields) not in (n + 1, n + 2):
+                    raise bad(line_no, f"a {n}-gram line holds a log-probability, {n} words and at most a back-off; got {len(fields)} fields")
+                try:
+                    lp = float(fields[0])
+                    bo = float(fields[n + 1]) if len(fields) == n + 2 else 0.0
+                except ValueError:
+                    raise bad(line_no, f"not a number in {line!r}") from None
+                if not (math.isfinite(lp) and math.isfinite(bo) and math.isfinite(float(np.float32(lp))) and math.isfinite(float(np.float32(bo)))):
+                    raise bad(line_no, f"a non-finite number in {line!r}")
+                seen_in_section += 1
+                names = [w if w in special or normalize is None else normalize(w) for w in fields[1:n + 1]]
+                if n == 1:
+                    w = names[0]
+                    if w in ids or w in outside:
+                        raise bad(line_no, f"duplicate n-gram {w!r}")
+                    if w not in lex and w not in special:
+                        outside.add(w)
+                        continue
+                    ids[w] = len(vocab)
+                    vocab.append(w)
+                    key = (ids[w],)
+                else:
+                    if any(w not in ids and w not in outside for w in names):
+                        raise bad(line_no, f"a word of {' '.join(names)!r} has no unigram")
+                    if any(w in outside for w in names):
+                        continue
+                    key = tuple(ids[w] for w in names)
+                    if key[:-1] not in grams[n - 2]:
+                        raise bad(line_no, f"the prefix {' '.join(names[:-1])!r} of {' '.join(names)!r} is not a {n - 1}-gram of the file")
+                    if key in grams[n - 1]:
+                        raise bad(line_no, f"duplicate n-gram {' '.join(names)!r}")
+                grams[n - 1][key] = len(rows[n - 1][1])
+                rows[n - 1][0].extend(key)
+                rows[n - 1][1].append(lp)
+                rows[n - 1][2].append(bo)
+        if state != "end":
+            raise bad(line_no if state != "head" else 1, "the file ends without \\end\\" if state != "head" else "no \\data\\ section")
+        if len(rows) != len(declared) or not declared:
+            raise bad(line_no, f"\\data\\ states {len(declared)} orders, the file holds the sections of {len(rows)}")
+        unk = ids.get(cls.UNK, -1)
+        missing = [w for w in dict.fromkeys(trie.words) if w not in ids]
+        if missing and unk < 0:
+            raise ValueError(f"NGramLM: {path}: the model has no <unk> and lacks {len(missing)} of the lexicon's words: "
+                             + ", ".join(repr(w) for w in missing[:5]) + (", ..." if len(missing) > 5 else ""))
+        if not vocab:
+            raise ValueError(f"NGramLM: {path}: no unigram of the model is a word of the lexicon")
+        word_map = np.fromiter((ids.get(w, unk) for w in trie.words), dtype=np.int32, count=len(trie.words))
+        return cls([np.array(r[0], dtype=np.int32).reshape(-1, k + 1) for k, r in enumerate(rows)], [np.array(r[1], dtype=np.float32) for r in rows],
+                   [np.array(r[2], dtype=np.float32) for r in rows], word_map, ids.get(cls.BOS, -1), ids.get(cls.EOS, -1), unk, vocab)
 
     def on(self, dev: torch.device) -> Tensor:
         """The packed image on ``dev`` (uploaded once; follows a change of device)."""

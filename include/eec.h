@@ -255,7 +255,9 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
  * (csrc/ctc_lexbeam.hip: one workgroup per sequence).  That decoder (flashlight-text) is third-party code outside the reference
  * tree and is not installed: this is the published algorithm -- token-trie beam search under CTC, Viterbi merging, no language
  * model -- as stated here; tests/lexbeam_cases.py is its plain-Python statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED.
- * Out of scope: a language model, log_add=True (the reference's character-lexicon branch), unknown-word scores, beams over 16.
+ * A back-off n-gram word model joins through eec_ctc_lexbeam_lm_decode, stated after this entry; without one nothing below changes.
+ * Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
+ * trie smearing, binary KenLM files, beams over 16.
  *
  * Lexicon: n_words spellings, each a non-empty sequence of token ids in [0, V), none of them `blank` or (when given) `sil`.  The
  *   trie's root is node 0.  A node "ends word w" when w is the FIRST word in file order with that spelling (later duplicates are
@@ -326,6 +328,64 @@ int eec_ctc_lexbeam_decode(const float* logp, int n_seq, int Tq, int V, const in
                            int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
                            int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
                            int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same search with a back-off n-gram word model: the reference's ctc_decoder(lexicon=..., lm="4gram_small.arpa.lm" / "lm.bin",
+ * lm_weight=LM_WEIGHT) (util/beam_infer.py:39-78).  The model is what an ARPA file states, its log10 values kept as they are (what
+ * KenLM's query interface returns, so the reference's LM_WEIGHT constants carry over); tests/lexbeam_lm_cases.py is the plain-Python
+ * statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED, as above.
+ *
+ * Model: n-grams (w1 .. wn), n <= order <= 5, over LM words 0 .. W - 1, each with logp and backoff (fp32).  Every LM word has a
+ *   unigram; the prefix (w1 .. wn-1) of every n-gram is an (n-1)-gram of the model (prefix-closed; a suffix may be absent).
+ *   lm_word(w): the LM word of lexicon word w -- the model's <unk> where the model lacks w.
+ * LM state: an n-gram of the model (a node of the image), the empty one included.  A hypothesis carries one; the start hypothesis
+ *   carries <s>'s unigram, or the empty n-gram when the model has no <s>.
+ * Scoring LM word v from state s, fp32 in the written order:
+ *     acc = 0
+ *     loop:  x = the n-gram s + v
+ *            x is in the model  -> acc = acc + logp[x]; stop
+ *            otherwise          -> acc = acc + backoff[s]; s = suffix[s]
+ *   suffix[s] is the longest proper suffix of s that is in the model.  The empty n-gram always finds v's unigram.  The state after
+ *   the hit is x when x is shorter than `order`, else suffix[x].
+ * Word-end candidate: ((score + e[c]) + word_score) + lm_weight * acc with acc for lm_word(wd) from the hypothesis' state; the
+ *   product is rounded on its own and then added (no fused multiply-add).  The new hypothesis carries the state after the hit;
+ *   every other candidate keeps its parent's.  Merging is still on (node, tok, pb, hist): the history determines the state.
+ *   Dropping, pruning, candidate ids and the other candidates are as above.
+ * End: when the model has </s>, every complete hypothesis' final score is score + lm_weight * acc with acc for </s> from its state
+ *   (formed the same way); otherwise its score.  The complete hypotheses are ordered by (final score descending, beam rank
+ *   ascending); the first nbest are returned, `scores` holds the final scores.
+ *
+ * eec_ngram_pack is HOST code and needs no device:
+ *   order 1..5; counts [order] int64: n-grams per order, counts[0] = W > 0
+ *   words [order] pointers: words[n-1] is [counts[n-1] * n] int32 LM word ids, n per n-gram; the unigrams are a permutation of
+ *       0 .. W - 1.  logp, backoff [order] pointers to [counts[n-1]] fp32 each (0 where the file has no back-off).
+ *   word_map [lex_words] int32: lm_word of every lexicon word (file order of the trie's lexicon)
+ *   bos_word, eos_word: the LM words of <s> and </s>, or -1
+ *   image: image_bytes >= eec_ngram_pack_bytes(order, counts, lex_words) bytes of host memory, 8-byte aligned; n_nodes: NULL or
+ *       where the node count (1 + all n-grams) is written
+ *   image layout, int32 units: header[16] = {magic "EECN", order, n_nodes, n_edges = n_nodes - 1, W, lex_words, <s> node (0: the
+ *       root), </s> word (-1: none), first node of depth `order`, child_begin offset, edge word offset, logp offset, backoff offset,
+ *       suffix offset, word_map offset, total dwords};  child_begin [n_nodes + 1]: the edges of node n are child_begin[n] ..
+ *       child_begin[n + 1];  edge words [n_edges] int32, ascending within a node;  logp, backoff [n_nodes] fp32 (0 for the root);
+ *       suffix [n_nodes] int32;  word_map [lex_words].  Node 0 is the empty n-gram.  Nodes are numbered breadth-first, children in
+ *       word order, so that the child reached by edge k is node k + 1 and the unigram of LM word v is node v + 1; a lookup below any
+ *       other node is a binary search over its edge range.  A node at or past header[8] has the full order.
+ *   eec_ngram_pack_bytes: 0 for an order outside 1..5, counts NULL or negative, counts[0] <= 0, lex_words <= 0, or an image of
+ *       2^31 dwords or more.
+ *   EEC_ERR_BAD_ARG: a null pointer, lex_words <= 0, no unigram, a word id outside [0, W), unigrams that are no permutation, an
+ *   n-gram whose prefix is absent, a duplicate n-gram, a non-finite value, bos_word / eos_word / a word_map entry that is no LM word.
+ *   EEC_ERR_UNSUPPORTED: an order outside 1..5, an image past 2^31 dwords.  EEC_ERR_WORKSPACE: image_bytes too small.
+ *
+ * eec_ctc_lexbeam_lm_decode: eec_ctc_lexbeam_decode's arguments, then lm: the model image on the device (8-byte aligned), and
+ *   lm_weight.  The same workspace.  EEC_ERR_BAD_ARG also for a null lm or a non-finite lm_weight, checked before any device work.
+ *   A model whose header does not carry the magic and the trie's n_words gives n_hyp = 0 for every sequence, as a foreign trie does.
+ * One kernel on `stream`; no allocation, no synchronisation; graph-capturable; results are bit-identical run to run. */
+size_t eec_ngram_pack_bytes(int order, const int64_t* counts, int lex_words);
+int eec_ngram_pack(int order, const int64_t* counts, const int32_t* const* words, const float* const* logp, const float* const* backoff,
+                   const int32_t* word_map, int lex_words, int bos_word, int eos_word, void* image, size_t image_bytes, int32_t* n_nodes);
+int eec_ctc_lexbeam_lm_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                              int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                              int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
+                              int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm, float lm_weight);
 
 /* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
  * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam

@@ -11,6 +11,16 @@ noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/le
 * yardstick: ``eec_ctc_beam_decode`` (the lexicon-free prefix beam search, unchanged by this tool's subject) on the same
   emissions, in the same process, measured the same way.  It is another algorithm with other outputs: the ratio says what the
   lexicon costs a caller who switches decoders, nothing else.
+
+    python tools/lexbeam_time.py --lm [--parent-record FILE ...] [--out profiles/lexbeam_lm_time.json]
+
+* ``--lm``: the search with a model (``eec_ctc_lexbeam_lm_decode``) against the search without one, same process, same emissions
+  (384 x 256, beam 10), lm_weight 1.  The model is synthetic and built as arrays, not as text: one unigram per lexicon word plus
+  ``<unk>``, ``<s>``, ``</s>``, and ``--bigrams`` / ``--trigrams`` (2 000 000 each: millions, as a pruned LibriSpeech 3-gram cut down
+  to the lexicon has) distinct random n-grams, a trigram always over a bigram that is there.  The emissions' paths spell random
+  words, so most word ends miss the state's edges and back off to the unigram: the walk is at its longest.
+* ``--parent-record``: records this tool wrote (``--out``) when run from a checkout of the parent commit on the same box; the
+  model-free time of that run joins the record with its ratio to this run's.
 """
 import argparse
 import json
@@ -24,7 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from early_exit_transformer_amd import capi  # noqa: E402
-from early_exit_transformer_amd.lexicon import TokenTrie  # noqa: E402
+from early_exit_transformer_amd.lexicon import NGramLM, TokenTrie  # noqa: E402
 import lexbeam_cases as L  # noqa: E402  (tests/: the emission generator)
 
 UNUSED = (0, 1, 2, 126, 127)
@@ -95,6 +105,65 @@ def prepared_calls(trie, em, beam, nbest, dev):
     return lexbeam, yardstick, nh
 
 
+def synthetic_model(n_words, n_bigrams, n_trigrams, seed=2):
+    """``NGramLM`` of order 3 over LM words 0 .. n_words + 2 (the lexicon's words in file order, then <unk>, <s>, </s>)."""
+    rng = np.random.default_rng(seed)
+    W = n_words + 3
+    unk, bos, eos = n_words, n_words + 1, n_words + 2
+    # contexts are skewed (a few words start many bigrams), successors are not; </s> starts nothing
+    ctx = np.minimum((rng.random(2 * n_bigrams) ** 3 * (W - 1)).astype(np.int64), W - 2)
+    key2 = np.unique(ctx * W + rng.integers(0, W, size=2 * n_bigrams))
+    key2 = np.sort(rng.permutation(key2)[:n_bigrams])
+    bi = np.stack([key2 // W, key2 % W], axis=1)
+    bi = bi[bi[:, 1] != bos]
+    over = bi[bi[:, 1] != eos]
+    key3 = np.unique(rng.integers(0, len(over), size=2 * n_trigrams) * W + rng.integers(0, W, size=2 * n_trigrams))
+    key3 = np.sort(rng.permutation(key3)[:n_trigrams])
+    tri = np.concatenate([over[key3 // W], (key3 % W)[:, None]], axis=1)
+    tri = tri[tri[:, 2] != bos]
+    words = [np.arange(W, dtype=np.int32)[:, None], bi.astype(np.int32), tri.astype(np.int32)]
+    logp = [rng.uniform(-6, -1, size=len(w)).astype(np.float32) for w in words]
+    backoff = [rng.uniform(-1, 0, size=len(w)).astype(np.float32) for w in words[:2]] + [np.zeros(len(tri), dtype=np.float32)]
+    return NGramLM(words, logp, backoff, np.arange(n_words, dtype=np.int32), bos, eos, unk)
+
+
+def lm_leg(args, trie, spellings, dev, records):
+    lib = capi.load()
+    lm = synthetic_model(len(spellings), args.bigrams, args.trigrams)
+    n, T, beam = 384, args.frames, args.beam
+    em = torch.from_numpy(L.emissions(3, spellings, n, T, 256, 0, 126)).to(dev)
+    free, _, nh = prepared_calls(trie, em, beam, 1, dev)
+    keep = free()
+    em_, words, wc, toks, tc, ts, nh, sc, ws, image = keep[:10]
+    lm_image = lm.on(dev)
+
+    def with_lm():
+        capi.check(lib.eec_ctc_lexbeam_lm_decode(em.data_ptr(), n, T, 256, None, image.data_ptr(), trie.blank, trie.sil, beam, 1, 0.0, 0.0, 50.0, T,
+                                                 words.data_ptr(), wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(),
+                                                 nh.data_ptr(), ws.data_ptr(), ws.numel(), capi.stream_ptr(dev), lm_image.data_ptr(), 1.0),
+                   "eec_ctc_lexbeam_lm_decode")
+    rec = {"what": "lm", "n_seq": n, "frames": T, "beam": beam, "lm_weight": 1.0, "order": lm.order, "n_grams": lm.n_grams, "lm_nodes": lm.n_nodes,
+           "lm_image_bytes": lm._image.numel(), "trie_image_bytes": trie._image.numel()}
+    for name, call in (("lm_free", free), ("with_lm", with_lm), ("lm_free_again", free)):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        rec[name + "_train_of_10_ms_per_call"] = event_ms(call, max(args.reps // 2, 5), per=10)
+        if name == "with_lm":
+            rec["sequences_with_a_hypothesis_with_lm"] = int((nh > 0).sum())
+    rec["ratio_with_lm_over_lm_free"] = round(rec["with_lm_train_of_10_ms_per_call"]["median"] / rec["lm_free_train_of_10_ms_per_call"]["median"], 3)
+    parents = []
+    for path in args.parent_record or []:
+        with open(path) as f:
+            parents += [r["lexbeam_train_of_10_ms_per_call"]["median"] for r in json.load(f) if r.get("what") == "launch" and r.get("n_seq") == n]
+    if parents:
+        mine = statistics.median([rec["lm_free_train_of_10_ms_per_call"]["median"], rec["lm_free_again_train_of_10_ms_per_call"]["median"]])
+        rec["parent_commit_lm_free_train_of_10_ms_per_call_medians"] = parents
+        rec["ratio_lm_free_over_parent_commit"] = round(mine / statistics.median(parents), 4)
+    records.append(rec)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -102,6 +171,10 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--beam", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the records to this JSON file")
+    ap.add_argument("--lm", action="store_true", help="time the search with a synthetic 3-gram model against the search without one")
+    ap.add_argument("--bigrams", type=int, default=2000000)
+    ap.add_argument("--trigrams", type=int, default=2000000)
+    ap.add_argument("--parent-record", nargs="*", help="records of this tool run from the parent commit on the same box")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device: there is nothing to time on the CPU")
@@ -116,8 +189,10 @@ def main():
     print(json.dumps(records[-1]), flush=True)
     # the synthetic trie stands for the real one only while it has its size: nodes within 2 %, the same extreme degrees
     assert abs(trie.n_nodes - 162621) <= 0.02 * 162621 and degree[0] == 109 and degree[1:].max() == 103 and trie.n_shadowed == 0, records[-1]
-    counts = [int(q) for q in args.seqs.split(",")]
-    pool = torch.from_numpy(L.emissions(3, spellings, max(counts), args.frames, 256, 0, 126)).to(dev)
+    counts = [] if args.lm else [int(q) for q in args.seqs.split(",")]
+    if args.lm:
+        lm_leg(args, trie, spellings, dev, records)
+    pool = torch.from_numpy(L.emissions(3, spellings, max(counts), args.frames, 256, 0, 126)).to(dev) if counts else None
     for n in counts:
         lexbeam, yardstick, nh = prepared_calls(trie, pool[:n].contiguous(), args.beam, 1, dev)
         rec = {"what": "launch", "n_seq": n, "frames": args.frames, "beam": args.beam}
