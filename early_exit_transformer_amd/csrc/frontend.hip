@@ -177,14 +177,18 @@ int eec_frontend_create(int sample_rate, int n_fft, int win_length, int hop_leng
             const double ang = 2.0 * kPi * (double)((k * j) % n_fft) / n_fft;
             basis[((((size_t)bt * 2 + p) * kFeQuads + s4) * 64 + lane) * 4 + q] = (float)(p ? -sin(ang) : cos(ang));
           }
-  // htk mel filterbank (torchaudio.functional.melscale_fbanks, norm=None), evaluated in fp32 like the reference's table
+  // htk mel filterbank (torchaudio.functional.melscale_fbanks, norm=None), evaluated in the order and precision of the
+  // reference's table: m_max in double and rounded once (an fp32 log10 moves the last point off sample_rate / 2 and hands
+  // the Nyquist bin a weight); the mel points as torch.linspace lays them out in fp32 (step * i over the first half,
+  // end - step * (n - 1 - i) in one rounding over the second); 10^x correctly rounded; the rest in fp32
   const int n_freqs = n_fft / 2 + 1;
   std::vector<float> all_freqs(n_freqs), f_pts(n_mels + 2);
   for (int k = 0; k < n_freqs; ++k) all_freqs[k] = (float)(sample_rate / 2) * (float)k / (float)(n_freqs - 1);
-  const float m_min = 0.0f, m_max = 2595.0f * log10f(1.0f + (float)(sample_rate / 2) / 700.0f);
+  const float m_max = (float)(2595.0 * log10(1.0 + (double)(sample_rate / 2) / 700.0));
+  const float m_step = m_max / (float)(n_mels + 1);
   for (int i = 0; i < n_mels + 2; ++i) {
-    const float m = m_min + (m_max - m_min) * (float)i / (float)(n_mels + 1);
-    f_pts[i] = 700.0f * (powf(10.0f, m / 2595.0f) - 1.0f);
+    const float m = i < (n_mels + 2) / 2 ? m_step * (float)i : fmaf(-m_step, (float)(n_mels + 1 - i), m_max);
+    f_pts[i] = 700.0f * ((float)pow(10.0, (double)(m / 2595.0f)) - 1.0f);
   }
   std::vector<int> range(3 * n_mels);
   std::vector<float> weights;

@@ -1,4 +1,4 @@
-"""fp32 torch-CPU restatement of the reference's mel front end (the oracle for csrc/frontend.hip).
+"""torch-CPU restatements of the reference's mel front end, fp32 and float64 (the oracles for csrc/frontend.hip).
 
 TEST INFRASTRUCTURE -- see oracle/__init__.py for who may import this.
 
@@ -15,17 +15,26 @@ unpinned): both transforms are restated from their published definiti
   ``melscale_fbanks``: triangular filters between points equally spaced on m = 2595 log10(1 + f / 700).
 
 Parity unpinned by the reference (it holds no vectors for the front end); torch.stft is the installed torch's kernel.
+
+``mel_frontend`` is that fp32 statement.  ``mel_frontend_fp64`` states the same transform in float64 without an FFT and without
+a padded copy of the wave (frames gathered by index, a direct DFT as two matrix products); it is what the kernel and the fp32
+statement are both measured against, and it pins the one case torch leaves open: an utterance of n_fft // 2 samples or fewer,
+where torch's reflect padding raises and the device front end reflects once and then clamps.
 """
 from __future__ import annotations
 
+import functools
 import math
 
+import numpy as np
 import torch
 from torch import Tensor
 
 
+@functools.lru_cache(maxsize=None)
 def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int) -> Tensor:
-    """[n_freqs, n_mels] triangular filterbank, htk mel scale, no area normalisation."""
+    """[n_freqs, n_mels] triangular filterbank, htk mel scale, no area normalisation.  One table per setting, shared by every
+    caller: read it, do not write to it."""
     all_freqs = torch.linspace(0, sample_rate // 2, n_freqs)
     m_min = 2595.0 * math.log10(1.0 + f_min / 700.0)
     m_max = 2595.0 * math.log10(1.0 + f_max / 700.0)
@@ -56,5 +65,59 @@ def mel_frontend_batch(wave: Tensor, lengths: Tensor, **kw) -> Tensor:
     T = max(o.size(1) for o in outs)
     out = torch.zeros(wave.size(0), outs[0].size(0), T)
     for b, o in enumerate(outs):
+        out[b, :, : o.size(1)] = o
+    return out
+
+
+def frame_indices(n_samples: int, win_length: int = 320, hop_length: int = 160) -> np.ndarray:
+    """[T, win] sample index read by slot j of frame t: hop t - win / 2 + j, reflected once at either end (-idx below 0,
+    2 (L - 1) - idx at or above L; no edge repeat) and then clamped to [0, L - 1].  T = 1 + L // hop, 0 frames for L <= 0.
+    For L > n_fft // 2 this is torch's centred reflect padding restricted to the samples under the window."""
+    L = int(n_samples)
+    T = 1 + L // hop_length if L > 0 else 0
+    idx = hop_length * np.arange(T, dtype=np.int64)[:, None] - win_length // 2 + np.arange(win_length, dtype=np.int64)[None, :]
+    idx = np.where(idx < 0, -idx, idx)
+    idx = np.where(idx >= L, 2 * (L - 1) - idx, idx)
+    return np.clip(idx, 0, max(L - 1, 0))
+
+
+def hann_fp64(win_length: int = 320) -> np.ndarray:
+    """Periodic hann window, float64."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
+
+
+def power_spectrum_fp64(wave, n_fft: int = 512, win_length: int = 320, hop_length: int = 160) -> np.ndarray:
+    """wave [L] -> [T, n_fft + 1] float64 power of the (2 n_fft)-point transform of the centred, hann-windowed frames: a direct
+    DFT over the win_length samples under the window (the window's offset inside the frame is a unit-modulus phase)."""
+    x = np.asarray(wave, dtype=np.float64).reshape(-1)
+    nfft = 2 * n_fft
+    idx = frame_indices(x.shape[0], win_length, hop_length)
+    if idx.shape[0] == 0:
+        return np.zeros((0, n_fft + 1))
+    frames = x[idx] * hann_fp64(win_length)[None, :]
+    kj = (np.arange(win_length, dtype=np.int64)[:, None] * np.arange(n_fft + 1, dtype=np.int64)[None, :]) % nfft
+    ang = 2.0 * np.pi * kj.astype(np.float64) / nfft
+    re, im = frames @ np.cos(ang), frames @ np.sin(ang)
+    return re * re + im * im
+
+
+def mel_frontend_fp64(wave, sample_rate: int = 16000, n_fft: int = 512, win_length: int = 320, hop_length: int = 160,
+                      n_mels: int = 80) -> Tensor:
+    """wave [L] (any real dtype) -> float64 power mel [n_mels, T], T = 1 + L // hop (0 frames for L = 0).  The filter table is
+    ``melscale_fbanks`` (torch's fp32 table, which is the reference's) cast to float64."""
+    P = power_spectrum_fp64(wave.detach().cpu().numpy() if isinstance(wave, Tensor) else wave, n_fft, win_length, hop_length)
+    fb = melscale_fbanks(n_fft + 1, 0.0, float(sample_rate // 2), n_mels, sample_rate).double().numpy()
+    return torch.from_numpy(np.ascontiguousarray((P @ fb).T))
+
+
+def mel_frontend_fp64_batch(wave, lengths=None, **kw) -> Tensor:
+    """The float64 front end per utterance + the collate's zero padding: wave [B, Lmax], lengths [B] (None: Lmax for all;
+    a length is taken into [0, Lmax]) -> float64 [B, n_mels, 1 + Lmax // hop]."""
+    hop = kw.get("hop_length", 160)
+    B, Lmax = wave.shape
+    lens = [Lmax] * B if lengths is None else [min(max(int(l), 0), Lmax) for l in lengths]
+    out = torch.zeros(B, kw.get("n_mels", 80), 1 + Lmax // hop if Lmax > 0 else 0, dtype=torch.float64)
+    for b in range(B):
+        o = mel_frontend_fp64(wave[b, : lens[b]], **kw)
         out[b, :, : o.size(1)] = o
     return out
