@@ -18,7 +18,9 @@
 * ``BeamInference.ctc_predict`` / ``ctc_predict_``  util/beam_infer.py:93-126: the lexicon-constrained CTC beam search with
   N-best (torchaudio's ``ctc_decoder(lexicon=..., lm=..., lm_weight=LM_WEIGHT)``) on the device (``ctc_lexicon_decode``,
   csrc/ctc_lexbeam.hip): words that are lexicon entries by construction, and the posterior of the top hypothesis; with ``lm=`` or
-  ``args.lm`` -- an ARPA file -- under a back-off n-gram word model (``lexicon.NGramLM``), else without one.
+  ``args.lm`` -- an ARPA file -- under a back-off n-gram word model (``lexicon.NGramLM``), else without one; with
+  ``smearing="max"`` or ``args.lm_smearing`` with LM look-ahead inside words (max trie smearing, which the third-party decoder
+  always applies; off by default here).
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
@@ -153,12 +155,17 @@ class BeamInference:
 
     LM_WEIGHT = 1.0  # util/beam_infer.py:40 (its comment keeps 3.23, the value of the "bigger LM" setting)
 
-    def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None):
+    def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None, smearing: Optional[str] = None):
         """``lm``: an ``NGramLM``, or the path of an ARPA file (None: ``args.lm`` if there is one) that is read at the first use
-        against the trie in use."""
+        against the trie in use.  ``smearing``: None (then ``args.lm_smearing`` if there is one) or ``"max"``: LM look-ahead by max
+        trie smearing in ``ctc_predict`` / ``ctc_predict_``.  The third-party decoder always smears; here the default is off, so
+        a model alone decodes as before.  Without a model there is nothing to smear and the setting is not used."""
         self.args = args
         self._trie = trie
         self._lm = lm if lm is not None else getattr(args, "lm", None)
+        self._smearing = smearing if smearing is not None else getattr(args, "lm_smearing", None)
+        if self._smearing not in (None, "max"):
+            raise ValueError(f"BeamInference: smearing must be None or 'max', got {self._smearing!r}")
         self._lm_read = None  # (the trie a path was read against, its NGramLM)
 
     sequence_length_penalty = staticmethod(sequence_length_penalty)
@@ -188,6 +195,8 @@ class BeamInference:
         nbest = self.N_BEST if nbest is None else nbest
         lm = self._lexicon_lm(trie)
         with_lm = {} if lm is None else {"lm": lm, "lm_weight": self.LM_WEIGHT if lm_weight is None else lm_weight}
+        if lm is not None and self._smearing is not None:
+            with_lm["smearing"] = self._smearing
         words, word_count, _, _, _, scores, n_hyp = ctc_lexicon_decode(emission, trie, beam_size=self._arg(beam_size, "beam_size"), nbest=nbest,
                                                                        word_score=self.W_INS, **with_lm)
         words, word_count, n_hyp = words[:, 0].cpu(), word_count[:, 0].cpu().tolist(), n_hyp.cpu().tolist()

@@ -7,7 +7,7 @@
 // term -- stated completely in include/eec.h; tests/lexbeam_cases.py and tests/lexbeam_lm_cases.py are its plain-Python statement
 // and the judge of this kernel.  Parity with the third-party decoder is unpinned.
 // Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
-// trie smearing, binary KenLM files, beams over 16.
+// binary KenLM files, beams over 16.
 //
 // One 256-thread workgroup per sequence, one launch for the batch; thread c owns frame label c (V <= 256).  All candidates that
 // can merge share their frame label, so every merge is local to one thread.  Per frame:
@@ -32,6 +32,12 @@
 // suffix link -- runs where a word-end candidate is formed; only the candidate's score is kept, and the at most `beam` word-end
 // candidates that win a round redo their walk for the state they continue from.  After the last frame one thread adds the </s>
 // term to the complete hypotheses and orders the at most 16 of them by insertion.
+//
+// With LM look-ahead (ctc_lexbeam_kernel<true, true>, eec_ctc_lexbeam_lm_smear_decode) the trie is smeared with the MAX mode, as
+// the third-party decoder always does: a host-built table (eec_ctc_trie_smear) gives every node the best start-state score of the
+// words at or below it, a step into a node is charged the increase of that maximum, and a word end takes the advance payment back.
+// smax[y] is loaded beside cbeg[y] / word_of[y]; the payment outstanding at a hypothesis' node rides in its beam entry in LDS and is
+// written by the round's winner.  The two other instantiations do not see any of it: their beam entry and arguments are unchanged.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -72,6 +78,20 @@ __device__ __forceinline__ unsigned long long lb_mix(unsigned long long h, int c
   return z ^ (z >> 31);
 }
 
+// ... with smearing also the advance payment outstanding at its node, smax[node] (0 at the root)
+struct LbBeamSm : LbBeam {
+  float pmax;
+  int pad2;
+};
+
+template <typename Beam>
+__device__ __forceinline__ Beam lb_entry(const LbBeam& b, float pmax) {
+  if constexpr (std::is_same_v<Beam, LbBeamSm>)
+    return LbBeamSm{b, pmax, 0};
+  else
+    return b;
+}
+
 struct LbArgs {
   const float* logp;
   const int* em_len;
@@ -88,6 +108,13 @@ struct LbLmArgs : LbArgs {
   float lm_weight;
 };
 
+struct LbSmArgs : LbLmArgs {
+  const int* smear;
+};
+
+constexpr int kSmMagic = 0x53434545;  // "EECS"
+constexpr int kSmHeader = 4;
+
 constexpr int kLmMagic = 0x4E434545;  // "EECN"
 constexpr int kLmHeader = 16;
 constexpr int kLmMaxOrder = 5;
@@ -101,8 +128,8 @@ struct LmView {
 
 // log10 p(v | state s) by the back-off walk of include/eec.h, fp32 additions in the walk's order; `next`: the state after v.
 // The root finds every word without a search (the unigram of word v is node v + 1), so the walk ends after at most `order` steps;
-// the bound keeps a damaged image from looping.
-__device__ __forceinline__ float lm_walk(const LmView& m, int s, int v, int& next) {
+// the bound keeps a damaged image from looping.  The smear table's host code runs this very function: one sequence of additions.
+__host__ __device__ __forceinline__ float lm_walk(const LmView& m, int s, int v, int& next) {
   float acc = 0.f;
   for (int d = 0; d <= kLmMaxOrder; ++d) {
     int x = v + 1;
@@ -140,17 +167,20 @@ __device__ __forceinline__ float lm_add(float s, float lm_weight, float acc) {
   return s + term;
 }
 
-template <bool LM, typename Args>
+template <bool LM, bool SM, typename Args>
 __device__ __forceinline__ bool lm_fits(const Args& a) {
-  if constexpr (LM)
-    return a.lm[0] == kLmMagic && a.lm[5] == a.trie[10];
-  else
-    return true;
+  bool fits = true;
+  if constexpr (LM) fits = a.lm[0] == kLmMagic && a.lm[5] == a.trie[10];
+  if constexpr (SM) fits = fits && a.smear[0] == kSmMagic && a.smear[1] == a.trie[1];
+  return fits;
 }
 
-template <bool LM>
-__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::conditional_t<LM, LbLmArgs, LbArgs> a) {
-  __shared__ LbBeam bufs[2][kLbMaxBeam];
+// SM (with LM only): LM look-ahead by the smear table
+template <bool LM, bool SM = false>
+__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::conditional_t<SM, LbSmArgs, std::conditional_t<LM, LbLmArgs, LbArgs>> a) {
+  static_assert(LM || !SM, "smearing needs a model");
+  using Beam = std::conditional_t<SM, LbBeamSm, LbBeam>;
+  __shared__ Beam bufs[2][kLbMaxBeam];
   __shared__ __attribute__((aligned(16))) unsigned char slot[kLbMaxBeam][256];  // edge offset of label c below beam i's node
   __shared__ float red_v[4];
   __shared__ int red_id[4];
@@ -160,14 +190,16 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
   const int V = a.V, blank = a.blank, sil = a.sil, beam = a.beam, Tq = a.Tq;
 
   // a trie that is not the one the call describes is not read past its header: every sequence ends without a hypothesis
-  // ... and so is a model that is none, or was packed for another lexicon
-  const bool ok = a.trie[0] == kLbMagic && a.trie[1] >= 1 && a.trie[3] == V && a.trie[4] == blank && a.trie[5] == sil && lm_fits<LM>(a);
+  // ... and so is a model that is none, or was packed for another lexicon, or a smear table that is none or another trie's
+  const bool ok = a.trie[0] == kLbMagic && a.trie[1] >= 1 && a.trie[3] == V && a.trie[4] == blank && a.trie[5] == sil && lm_fits<LM, SM>(a);
   int L = a.em_len ? a.em_len[seq] : Tq;
   if (!ok || L < 1 || L > Tq) L = 0;
   const int* cbeg = a.trie + (ok ? a.trie[6] : 0);
   const unsigned char* ctok = (const unsigned char*)(a.trie + (ok ? a.trie[7] : 0));
   const int* word_of = a.trie + (ok ? a.trie[8] : 0);
   const int root_deg = L > 0 ? cbeg[1] : 0;
+  const float* smax = nullptr;
+  if constexpr (SM) smax = (const float*)(a.smear + (ok ? kSmHeader : 0));
   LmView m = {};
   if constexpr (LM) {
     const int* lm = a.lm;
@@ -181,13 +213,13 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
   const float* lp_seq = a.logp + (size_t)seq * Tq * V;
   int2* bp = a.backptr + (size_t)seq * Tq * beam;
   int cur = 0, nb = 1;
-  if (c == 0) bufs[0][0] = LbBeam{0x243F6A8885A308D3ull, 0.f, 0, 0, root_deg, -1, 0, 0, LM ? m.bos : 0};
+  if (c == 0) bufs[0][0] = lb_entry<Beam>(LbBeam{0x243F6A8885A308D3ull, 0.f, 0, 0, root_deg, -1, 0, 0, LM ? m.bos : 0}, 0.f);
   float lp_next = (L > 0 && c < V) ? lp_seq[c] : -INFINITY;
   __syncthreads();
 
   for (int t = 0; t < L; ++t) {
-    const LbBeam* B = bufs[cur];
-    LbBeam* N = bufs[cur ^ 1];
+    const Beam* B = bufs[cur];
+    Beam* N = bufs[cur ^ 1];
     const float lpc = lp_next;
     if (t + 1 < L && c < V) lp_next = lp_seq[(size_t)(t + 1) * V + c];  // one frame ahead of its use
 
@@ -216,7 +248,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
       wd[i] = -1;
       h0[i] = h1[i] = 0;
       if (in_beam(i) && c < V) {
-        const LbBeam b = B[i];
+        const Beam b = B[i];
         const float base = b.score + lpc;
         h0[i] = b.hash;
         if (c == blank || c == b.tok) {  // blank, or the repeat of a non-blank label: the state stays
@@ -232,15 +264,20 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
           if (j != kLbNoChild) {
             const int y = b.beg + j + 1;
             const int yb = cbeg[y], ye = cbeg[y + 1], word = word_of[y];
+            float sy = 0.f;
+            if constexpr (SM) sy = smax[y];
             if (ye > yb) {
               s0[i] = base;
+              if constexpr (SM) s0[i] = lm_add(base, a.lm_weight, sy - b.pmax);  // the increase of the maximum, paid in advance
               nd0[i] = y, beg0[i] = yb, deg0[i] = ye - yb;
             }
             if (word >= 0) {
               s1[i] = base + a.word_score;
               if constexpr (LM) {
                 int next;
-                s1[i] = lm_add(s1[i], a.lm_weight, lm_walk(m, b.pad, m.map[word], next));
+                float acc = lm_walk(m, b.pad, m.map[word], next);
+                if constexpr (SM) acc = acc - b.pmax;  // the true score replaces what was paid
+                s1[i] = lm_add(s1[i], a.lm_weight, acc);
               }
               wd[i] = word;
               h1[i] = lb_mix(b.hash, word);
@@ -317,7 +354,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
       if (c == (gid >> 5)) {
         const int ii = gid & 15;
         const bool end = (gid >> 4) & 1;
-        const LbBeam par = B[ii];
+        const Beam par = B[ii];
         LbBeam e = LbBeam{par.hash, gv, 0, 0, root_deg, c, par.ntok + (c != blank && c != par.tok), par.nw + end, LM ? par.pad : 0};
         int word = 0;
 #pragma unroll
@@ -334,7 +371,10 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
           }
         if constexpr (LM)
           if (end) lm_walk(m, par.pad, m.map[word - 1], e.pad);  // the walk again, for the state this time
-        N[r] = e;
+        float pmax = 0.f;  // nothing is outstanding at the root
+        if constexpr (SM)
+          if (!end) pmax = e.node == par.node ? par.pmax : smax[e.node];
+        N[r] = lb_entry<Beam>(e, pmax);
         bp[(size_t)t * beam + r] = make_int2((ii << 16) | c, word);
         rescan = true;
       }
@@ -428,11 +468,12 @@ static size_t lm_image_dwords(unsigned long long nodes, unsigned long long lex_w
   return (size_t)(kLmHeader + (nodes + 1) + (nodes - 1) + 3 * nodes + lex_words + 1) & ~(size_t)1;
 }
 
-// the checks and the launch of both entries; lm == nullptr: the model-free kernel
+// the checks and the launch of the three entries
 static int lb_decode(const char* who, const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
                      int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words, int32_t* words,
                      int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores, int32_t* n_hyp, void* workspace,
-                     size_t workspace_bytes, void* stream, bool with_lm, const void* lm, float lm_weight) {
+                     size_t workspace_bytes, void* stream, bool with_lm, const void* lm, float lm_weight, bool with_smear = false,
+                     const void* smear = nullptr) {
   using eech::fail;
   const std::string me(who);
   if (n_seq < 0 || Tq < 1 || max_words < 1) return fail(EEC_ERR_BAD_ARG, me + ": needs n_seq >= 0, Tq >= 1, max_words >= 1");
@@ -442,22 +483,26 @@ static int lb_decode(const char* who, const float* logp, int n_seq, int Tq, int 
     return fail(EEC_ERR_BAD_ARG, me + ": needs blank in [0, V), sil -1 or in [0, V) and not the blank");
   if (with_lm && !std::isfinite(lm_weight)) return fail(EEC_ERR_BAD_ARG, me + ": lm_weight must be finite");
   if (with_lm && !lm) return fail(EEC_ERR_BAD_ARG, me + ": null argument (lm)");
+  if (with_smear && !smear) return fail(EEC_ERR_BAD_ARG, me + ": null argument (smear)");
+  if (with_smear && ((uintptr_t)smear & 7)) return fail(EEC_ERR_BAD_ARG, me + ": smear must be 8-byte aligned");
   if (n_seq == 0) return 0;
   if (!logp || !trie || !words || !word_count || !tokens || !token_count || !scores || !n_hyp || !workspace)
     return fail(EEC_ERR_BAD_ARG, me + ": null argument");
   if (((uintptr_t)trie | (uintptr_t)workspace | (uintptr_t)lm) & 7) return fail(EEC_ERR_BAD_ARG, me + (with_lm ? ": trie, lm and workspace must be 8-byte aligned" : ": trie and workspace must be 8-byte aligned"));
   if (workspace_bytes < eec_ctc_lexbeam_workspace_bytes(n_seq, Tq, beam_size))
     return fail(EEC_ERR_WORKSPACE, me + ": workspace below eec_ctc_lexbeam_workspace_bytes()");
-  LbLmArgs a;
+  LbSmArgs a;
   a.logp = logp, a.em_len = em_len, a.trie = (const int*)trie;
   a.Tq = Tq, a.V = V, a.blank = blank, a.sil = sil, a.beam = beam_size, a.nbest = nbest, a.max_words = max_words;
   a.use_thr = std::isfinite(beam_threshold) ? 1 : 0;
   a.word_score = word_score, a.sil_score = sil_score, a.beam_threshold = beam_threshold;
   a.words = words, a.word_count = word_count, a.tokens = tokens, a.token_count = token_count, a.timesteps = timesteps, a.n_hyp = n_hyp;
   a.scores = scores, a.backptr = (int2*)workspace;
-  a.lm = (const int*)lm, a.lm_weight = lm_weight;
-  if (with_lm)
-    hipLaunchKernelGGL(ctc_lexbeam_kernel<true>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
+  a.lm = (const int*)lm, a.lm_weight = lm_weight, a.smear = (const int*)smear;
+  if (with_smear)
+    hipLaunchKernelGGL((ctc_lexbeam_kernel<true, true>), dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
+  else if (with_lm)
+    hipLaunchKernelGGL(ctc_lexbeam_kernel<true>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbLmArgs&)a);
   else
     hipLaunchKernelGGL(ctc_lexbeam_kernel<false>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbArgs&)a);
   EEC_HIP(hipGetLastError());
@@ -668,6 +713,52 @@ int eec_ngram_pack(int order, const int64_t* counts, const int32_t* const* words
   return 0;
 }
 
+size_t eec_ctc_trie_smear_bytes(int n_nodes) {
+  return n_nodes >= 1 ? (((size_t)eec::kSmHeader + (size_t)n_nodes + 1) & ~(size_t)1) * 4 : 0;
+}
+
+int eec_ctc_trie_smear(const void* trie_image, const void* lm_image, void* table, size_t table_bytes) {
+  using namespace eec;
+  using eech::fail;
+  if (!trie_image || !lm_image || !table) return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: null argument (trie_image, lm_image, table)");
+  if (((uintptr_t)trie_image | (uintptr_t)lm_image | (uintptr_t)table) & 7)
+    return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: trie_image, lm_image and table must be 8-byte aligned");
+  const int32_t *trie = (const int32_t*)trie_image, *lm = (const int32_t*)lm_image;
+  if (trie[0] != kLbMagic || trie[1] < 1) return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: trie_image is no packed trie");
+  if (lm[0] != kLmMagic) return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: lm_image is no packed n-gram model");
+  if (lm[5] != trie[10])
+    return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: the model was packed for a lexicon of " + std::to_string(lm[5]) + " words, the trie has " +
+                                     std::to_string(trie[10]));
+  const int nodes = trie[1];
+  if (table_bytes < eec_ctc_trie_smear_bytes(nodes)) return fail(EEC_ERR_WORKSPACE, "eec_ctc_trie_smear: table_bytes below eec_ctc_trie_smear_bytes()");
+  const int32_t *cbeg = trie + trie[6], *word_of = trie + trie[8];
+  LmView m;
+  m.begin = lm + lm[9], m.eword = lm + lm[10], m.suffix = lm + lm[13], m.map = lm + lm[14];
+  m.logp = (const float*)(lm + lm[11]), m.backoff = (const float*)(lm + lm[12]);
+  m.top_begin = lm[8], m.bos = lm[6], m.eos = lm[7];
+  int32_t* tab = (int32_t*)table;
+  memset(tab, 0, eec_ctc_trie_smear_bytes(nodes));
+  float* smax = (float*)(tab + kSmHeader);
+  // children have higher numbers than their parent (the child of edge k is node k + 1): one descending sweep
+  for (int n = nodes - 1; n >= 1; --n) {
+    float best = -INFINITY;
+    const int word = word_of[n];
+    if (word >= lm[5]) return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: node " + std::to_string(n) + " ends a word outside the lexicon");
+    if (word >= 0) {
+      int next;
+      best = lm_walk(m, m.bos, m.map[word], next);  // u(word): the walk from the start state
+    }
+    if (cbeg[n] < n || cbeg[n + 1] > nodes - 1 || cbeg[n + 1] < cbeg[n])
+      return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: node " + std::to_string(n) + " has children that are not below it");
+    for (int k = cbeg[n]; k < cbeg[n + 1]; ++k) best = std::max(best, smax[k + 1]);
+    if (!std::isfinite(best)) return fail(EEC_ERR_BAD_ARG, "eec_ctc_trie_smear: node " + std::to_string(n) + " neither ends a word nor has children, or a model value is not finite");
+    smax[n] = best;
+  }
+  smax[0] = 0.f;
+  tab[0] = kSmMagic, tab[1] = nodes, tab[2] = trie[10], tab[3] = 0;
+  return 0;
+}
+
 size_t eec_ctc_lexbeam_workspace_bytes(int n_seq, int Tq, int beam_size) {
   return n_seq > 0 && Tq > 0 && beam_size > 0 ? (size_t)n_seq * Tq * beam_size * sizeof(int2) : 0;
 }
@@ -688,6 +779,16 @@ int eec_ctc_lexbeam_lm_decode(const float* logp, int n_seq, int Tq, int V, const
   return eec::lb_decode("eec_ctc_lexbeam_lm_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score, sil_score,
                         beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace, workspace_bytes,
                         stream, true, lm, lm_weight);
+}
+
+int eec_ctc_lexbeam_lm_smear_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                                    int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                                    int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps,
+                                    float* scores, int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm,
+                                    float lm_weight, const void* smear) {
+  return eec::lb_decode("eec_ctc_lexbeam_lm_smear_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score,
+                        sil_score, beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace,
+                        workspace_bytes, stream, true, lm, lm_weight, true, smear);
 }
 
 }  // extern "C"

@@ -64,17 +64,25 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
                        beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None, lm=None,
-                       lm_weight: float = 0.0):
+                       lm_weight: float = 0.0, smearing: Optional[str] = None):
     """Lexicon-constrained CTC beam search with N-best of [n, T', V] log-probs on the device (eec_ctc_lexbeam_decode): the
     decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)``,
     util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
     ``lm``: None, or a ``lexicon.NGramLM`` packed for this trie -- its score times ``lm_weight`` joins at every word end and at the
     end of the sentence (eec_ctc_lexbeam_lm_decode), and ``scores`` are the final scores.
+    ``smearing``: None, or ``"max"`` (needs ``lm``) -- LM look-ahead by max trie smearing (eec_ctc_lexbeam_lm_smear_decode): every
+    step inside a word is charged the increase of the best score the model gives any word still reachable, and the word end takes
+    that advance back.  A complete hypothesis scores what it scores without smearing; what changes is which hypotheses survive
+    pruning.  The third-party decoder always smears; the default here stays off, so existing calls return what they returned.
     ``trie``: a ``lexicon.TokenTrie`` (it carries V, blank and sil); ``em_len`` [n] frames per sequence (None: T'); ``max_words``
     (None: T', always enough): the words kept per hypothesis -- ``word_count`` is the true count even above it.  Returns
     ``(words [n, nbest, max_words] int32 indices into trie.words, word_count [n, nbest], tokens [n, nbest, T'], token_count [n, nbest],
     timesteps [n, nbest, T'], scores [n, nbest] fp32, n_hyp [n])``: hypotheses best first, absent ones with score -inf and counts
     0, entries past a count -1.  One launch on the current stream, no host synchronisation."""
+    if smearing not in (None, "max"):
+        raise ValueError(f"ctc_lexicon_decode: smearing must be None or 'max', got {smearing!r}")
+    if smearing is not None and lm is None:
+        raise ValueError("ctc_lexicon_decode: smearing='max' needs lm=: it is the model's scores that are smeared over the trie")
     if not emission.is_cuda:
         raise RuntimeError("ctc_lexicon_decode runs on a HIP device only")
     logp = emission.contiguous().float()
@@ -102,8 +110,11 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
                 ws.data_ptr(), ws_bytes, stream_ptr(dev))
         if lm is None:
             capi.check(lib.eec_ctc_lexbeam_decode(*args), "eec_ctc_lexbeam_decode")
-        else:
+        elif smearing is None:
             capi.check(lib.eec_ctc_lexbeam_lm_decode(*args, lm.on(dev).data_ptr(), float(lm_weight)), "eec_ctc_lexbeam_lm_decode")
+        else:
+            capi.check(lib.eec_ctc_lexbeam_lm_smear_decode(*args, lm.on(dev).data_ptr(), float(lm_weight), lm.smear(trie).on(dev).data_ptr()),
+                       "eec_ctc_lexbeam_lm_smear_decode")
     return words, word_count, tokens, token_count, timesteps, scores, n_hyp
 
 

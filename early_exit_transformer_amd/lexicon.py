@@ -7,7 +7,8 @@ There is no CPU path: without a HIP device ``nearest`` raises, and with it every
 ``TokenTrie`` is the other use of a lexicon: the spellings of its words as token sequences, packed into the trie image that the
 lexicon-constrained CTC beam search walks (``ctc.ctc_lexicon_decode``, csrc/ctc_lexbeam.hip; layout in include/eec.h).
 ``NGramLM`` is the back-off n-gram word model that search can take along: an ARPA file read against a trie's words and packed into
-the n-gram image of include/eec.h (``eec_ngram_pack``, host code)."""
+the n-gram image of include/eec.h (``eec_ngram_pack``, host code); ``NGramLM.smear(trie)`` is the table of its LM look-ahead (max
+trie smearing, ``eec_ctc_trie_smear``, host code)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -260,6 +261,7 @@ class NGramLM:
         self.n_nodes = n_nodes.value
         self._image = image[: 4 * int(image[60:64].view(torch.int32))]  # header[15]: the dwords actually used
         self._resident = None  # (device, device copy)
+        self._smear = None     # (the trie it was built for, its SmearTable)
 
     @classmethod
     def from_arpa(cls, path, trie: "TokenTrie", normalize=None) -> "NGramLM":
@@ -377,6 +379,41 @@ class NGramLM:
 
     def on(self, dev: torch.device) -> Tensor:
         """The packed image on ``dev`` (uploaded once; follows a change of device)."""
+        if self._resident is None or self._resident[0] != dev:
+            self._resident = (dev, self._image.to(dev))
+        return self._resident[1]
+
+
+    def smear(self, trie: "TokenTrie") -> "SmearTable":
+        """The LM look-ahead table of ``trie`` under this model (max trie smearing: every node carries the best start-state score
+        of the words at or below it; ``eec_ctc_trie_smear``, host code, from the two host images).  Built once per trie and
+        cached, the table of the last trie asked for is kept; it follows the device like ``on()``."""
+        if self._smear is None or self._smear[0] is not trie:
+            if self.n_words != len(trie.words):
+                raise ValueError(f"NGramLM.smear: the model was packed for a lexicon of {self.n_words} words, the trie has {len(trie.words)}")
+            lib = capi.load()
+            nbytes = lib.eec_ctc_trie_smear_bytes(trie.n_nodes)
+            table = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
+            capi.check(lib.eec_ctc_trie_smear(trie._image.data_ptr(), self._image.data_ptr(), table.data_ptr(), nbytes), "eec_ctc_trie_smear")
+            self._smear = (trie, SmearTable(table))
+        return self._smear[1]
+
+
+class SmearTable:
+    """The smear table of one (trie, model) pair (layout in include/eec.h): a host copy and, at the first use, a device copy."""
+
+    def __init__(self, table: Tensor):
+        self._image = table
+        self._resident = None  # (device, device copy)
+
+    @property
+    def values(self) -> np.ndarray:
+        """``smax`` [n_nodes] fp32, indexed by the trie image's node numbers."""
+        head = self._image[:16].view(torch.int32)
+        return self._image[16:16 + 4 * int(head[1])].view(torch.float32).numpy()
+
+    def on(self, dev: torch.device) -> Tensor:
+        """The table on ``dev`` (uploaded once; follows a change of device)."""
         if self._resident is None or self._resident[0] != dev:
             self._resident = (dev, self._image.to(dev))
         return self._resident[1]

@@ -256,8 +256,9 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
  * tree and is not installed: this is the published algorithm -- token-trie beam search under CTC, Viterbi merging, no language
  * model -- as stated here; tests/lexbeam_cases.py is its plain-Python statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED.
  * A back-off n-gram word model joins through eec_ctc_lexbeam_lm_decode, stated after this entry; without one nothing below changes.
+ * LM look-ahead (max trie smearing) joins through eec_ctc_lexbeam_lm_smear_decode, stated after that one.
  * Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
- * trie smearing, binary KenLM files, beams over 16.
+ * binary KenLM files, beams over 16.
  *
  * Lexicon: n_words spellings, each a non-empty sequence of token ids in [0, V), none of them `blank` or (when given) `sil`.  The
  *   trie's root is node 0.  A node "ends word w" when w is the FIRST word in file order with that spelling (later duplicates are
@@ -386,6 +387,53 @@ int eec_ctc_lexbeam_lm_decode(const float* logp, int n_seq, int Tq, int V, const
                               int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
                               int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
                               int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm, float lm_weight);
+
+/* The same search with the model AND LM look-ahead by max trie smearing.  eec_ctc_lexbeam_lm_decode asks the model only where a
+ * word ends; between word ends the beam is ordered by acoustic score alone.  The published lexicon decoder inserts every lexicon
+ * word into the token trie with the model's score for it from the start state and smears the trie (torchaudio's ctc_decoder builds
+ * its trie this way and smears it with the MAX mode, always): every node carries the maximum of those scores over the words at or
+ * below it, a step into a node is charged the increase of that maximum, a word end replaces the advance payment by the true
+ * conditional score.  For a complete hypothesis the payments telescope to exactly the word scores paid without smearing, so only
+ * pruning changes.  tests/lexbeam_smear_cases.py is the plain-Python statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED.
+ *
+ * Word score: for a lexicon word w that ends a trie node (the first word in file order with that spelling; shadowed duplicates do
+ *   not count), u(w) is `acc` of the walk above for lm_word(w) from the start state (<s>'s unigram, or the empty n-gram when the
+ *   model has no <s>): fp32, the additions in the walk's order.
+ * Smear table: smax[n], n >= 1, is the maximum of u(w) over the words that end at node n or at any node below it; smax[0] = 0.  A
+ *   maximum involves no rounding.  Every node but the root ends a word or has children and the packer refuses non-finite model
+ *   values, so every entry is finite.
+ * Search: eec_ctc_lexbeam_lm_decode's with two candidate rules changed; pmax = smax[node] of the hypothesis (0 at the root):
+ *     child, in-word   (edge c -> y, y has children)   (score + e[c]) + lm_weight * (smax[y] - pmax)
+ *     child, word end  (y ends wd)                     ((score + e[c]) + word_score) + lm_weight * (acc - pmax)
+ *   fp32 in the written order: the difference is rounded, the product is rounded on its own, then added (no fused multiply-add).
+ *   A node that ends a word and has children emits both.  Nothing else differs: blank, repeat, sil, ids, merging keys, dropping,
+ *   the threshold, the </s> term and its re-ordering, the outputs.  A complete hypothesis sits at the root: no payment is
+ *   outstanding at the end.  With lm_weight = 0, or a model whose word scores are all equal, every term is a zero and the results
+ *   equal eec_ctc_lexbeam_lm_decode's bitwise.
+ *
+ * eec_ctc_trie_smear is HOST code and needs no device:
+ *   trie_image, lm_image: HOST copies of the two packed images (8-byte aligned), the model packed for this trie's lexicon
+ *   table: table_bytes >= eec_ctc_trie_smear_bytes(the trie's n_nodes) bytes of host memory, 8-byte aligned; the caller copies it
+ *       to the device (8-byte aligned) and passes it as `smear`
+ *   table layout, int32 units: header[4] = {magic "EECS", the trie's n_nodes, the lexicon's word count, 0}, then smax [n_nodes] fp32,
+ *       padded to a multiple of 8 bytes.  One descending sweep over the nodes fills it (children have higher numbers than their
+ *       parent); the walk is the function the kernel runs, compiled for the host: the same sequence of fp32 additions.
+ *   eec_ctc_trie_smear_bytes: 0 for n_nodes < 1.
+ *   EEC_ERR_BAD_ARG: a null or misaligned pointer, an image without its magic, a model packed for another lexicon (its header's
+ *   lex_words is not the trie's n_words), a trie image whose nodes are not what the packer writes.  EEC_ERR_WORKSPACE: table_bytes
+ *   too small.
+ *
+ * eec_ctc_lexbeam_lm_smear_decode: eec_ctc_lexbeam_lm_decode's arguments, then smear: the table on the device.  The same workspace.
+ *   EEC_ERR_BAD_ARG also for a null or misaligned smear, checked before any device work.  A table whose header does not carry its
+ *   magic and the trie's n_nodes gives n_hyp = 0 for every sequence, as a foreign trie or model does.
+ * One kernel on `stream`; no allocation, no synchronisation; graph-capturable; results are bit-identical run to run. */
+size_t eec_ctc_trie_smear_bytes(int n_nodes);
+int eec_ctc_trie_smear(const void* trie_image, const void* lm_image, void* table, size_t table_bytes);
+int eec_ctc_lexbeam_lm_smear_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                                    int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                                    int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps,
+                                    float* scores, int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm,
+                                    float lm_weight, const void* smear);
 
 /* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
  * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam

@@ -21,12 +21,20 @@ noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/le
   words, so most word ends miss the state's edges and back off to the unigram: the walk is at its longest.
 * ``--parent-record``: records this tool wrote (``--out``) when run from a checkout of the parent commit on the same box; the
   model-free time of that run joins the record with its ratio to this run's.
+
+    python tools/lexbeam_time.py --lm --smear [--parent-record FILE ...] [--out profiles/lexbeam_smear_time.json]
+
+* ``--smear``: also the search with LM look-ahead (``eec_ctc_lexbeam_lm_smear_decode``, max trie smearing) on the same emissions
+  with the same model, against the unsmeared LM search of the same process; the host time of building the table
+  (``eec_ctc_trie_smear``) is recorded too.  ``--parent-record`` then takes the records of the parent commit's ``--lm`` run: its
+  model-free and its LM time join with their ratios to this run's.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -142,16 +150,49 @@ def lm_leg(args, trie, spellings, dev, records):
                                                  words.data_ptr(), wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(),
                                                  nh.data_ptr(), ws.data_ptr(), ws.numel(), capi.stream_ptr(dev), lm_image.data_ptr(), 1.0),
                    "eec_ctc_lexbeam_lm_decode")
-    rec = {"what": "lm", "n_seq": n, "frames": T, "beam": beam, "lm_weight": 1.0, "order": lm.order, "n_grams": lm.n_grams, "lm_nodes": lm.n_nodes,
-           "lm_image_bytes": lm._image.numel(), "trie_image_bytes": trie._image.numel()}
-    for name, call in (("lm_free", free), ("with_lm", with_lm), ("lm_free_again", free)):
+    calls = [("lm_free", free), ("with_lm", with_lm), ("lm_free_again", free)]
+    smear_rec = {}
+    if args.smear:
+        t0 = time.perf_counter()
+        table = lm.smear(trie)
+        smear_rec = {"smear_table_bytes": table._image.numel(), "smear_table_host_build_s": round(time.perf_counter() - t0, 3)}
+        smear_image = table.on(dev)
+
+        def with_smear():
+            capi.check(lib.eec_ctc_lexbeam_lm_smear_decode(em.data_ptr(), n, T, 256, None, image.data_ptr(), trie.blank, trie.sil, beam, 1, 0.0, 0.0,
+                                                           50.0, T, words.data_ptr(), wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(),
+                                                           sc.data_ptr(), nh.data_ptr(), ws.data_ptr(), ws.numel(), capi.stream_ptr(dev),
+                                                           lm_image.data_ptr(), 1.0, smear_image.data_ptr()), "eec_ctc_lexbeam_lm_smear_decode")
+        calls = [("lm_free", free), ("with_lm", with_lm), ("with_smear", with_smear), ("with_lm_again", with_lm), ("with_smear_again", with_smear),
+                 ("lm_free_again", free)]
+    rec = {"what": "smear" if args.smear else "lm", "n_seq": n, "frames": T, "beam": beam, "lm_weight": 1.0, "order": lm.order, "n_grams": lm.n_grams, "lm_nodes": lm.n_nodes,
+           "lm_image_bytes": lm._image.numel(), "trie_image_bytes": trie._image.numel(), **smear_rec}
+    for name, call in calls:
         for _ in range(3):
             call()
         torch.cuda.synchronize()
         rec[name + "_train_of_10_ms_per_call"] = event_ms(call, max(args.reps // 2, 5), per=10)
-        if name == "with_lm":
-            rec["sequences_with_a_hypothesis_with_lm"] = int((nh > 0).sum())
+        if name in ("with_lm", "with_smear"):
+            rec["sequences_with_a_hypothesis_" + name] = int((nh > 0).sum())
     rec["ratio_with_lm_over_lm_free"] = round(rec["with_lm_train_of_10_ms_per_call"]["median"] / rec["lm_free_train_of_10_ms_per_call"]["median"], 3)
+    med = lambda *names: statistics.median([rec[k + "_train_of_10_ms_per_call"]["median"] for k in names])  # noqa: E731
+    if args.smear:
+        rec["ratio_with_smear_over_with_lm"] = round(med("with_smear", "with_smear_again") / med("with_lm", "with_lm_again"), 4)
+        free_p, lm_p = [], []
+        for path in args.parent_record or []:
+            with open(path) as f:
+                for r in json.load(f):
+                    if r.get("what") == "lm" and r.get("n_seq") == n:
+                        free_p += [r["lm_free_train_of_10_ms_per_call"]["median"], r["lm_free_again_train_of_10_ms_per_call"]["median"]]
+                        lm_p.append(r["with_lm_train_of_10_ms_per_call"]["median"])
+        if free_p:
+            rec["parent_commit_lm_free_train_of_10_ms_per_call_medians"] = free_p
+            rec["parent_commit_with_lm_train_of_10_ms_per_call_medians"] = lm_p
+            rec["ratio_lm_free_over_parent_commit"] = round(med("lm_free", "lm_free_again") / statistics.median(free_p), 4)
+            rec["ratio_with_lm_over_parent_commit"] = round(med("with_lm", "with_lm_again") / statistics.median(lm_p), 4)
+        records.append(rec)
+        print(json.dumps(rec), flush=True)
+        return
     parents = []
     for path in args.parent_record or []:
         with open(path) as f:
@@ -172,10 +213,13 @@ def main():
     ap.add_argument("--beam", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the records to this JSON file")
     ap.add_argument("--lm", action="store_true", help="time the search with a synthetic 3-gram model against the search without one")
+    ap.add_argument("--smear", action="store_true", help="with --lm: also the search with LM look-ahead (max trie smearing)")
     ap.add_argument("--bigrams", type=int, default=2000000)
     ap.add_argument("--trigrams", type=int, default=2000000)
     ap.add_argument("--parent-record", nargs="*", help="records of this tool run from the parent commit on the same box")
     args = ap.parse_args()
+    if args.smear and not args.lm:
+        ap.error("--smear goes with --lm")
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device: there is nothing to time on the CPU")
     dev = torch.device("cuda", 0)
