@@ -118,8 +118,8 @@ struct eec_encoder {
   double prof_ms[KC_COUNT] = {0};
   long long prof_n[KC_COUNT] = {0};
   std::vector<PackedLayer> layers;
-  uint4 *sub_w1p, *sub_w2p;
-  float *sub_b1, *sub_b2, *pe;
+  uint4 *sub_w1p, *sub_wfp;          // the first convolution alone (one-convolution stem); both convolutions folded into one
+  float *sub_b1, *sub_bf, *sub_weff, *pe;  // sub_weff: the folded weight in fp32, [D][7 n_mels], as composed at pack time
   std::vector<uint4*> head_p, head_f8;
   std::vector<float*> head_b;
 
@@ -133,8 +133,9 @@ struct eec_encoder {
       }
     sub_w1p = arena.take<uint4>(frag_u4(D, cfg.n_mels * 3));
     sub_b1 = arena.take<float>(D);
-    sub_w2p = arena.take<uint4>(frag_u4(D, 3 * D));
-    sub_b2 = arena.take<float>(D);
+    sub_wfp = arena.take<uint4>(frag_u4(D, 7 * cfg.n_mels));
+    sub_bf = arena.take<float>(D);
+    sub_weff = arena.take<float>((size_t)D * 7 * cfg.n_mels);
     pe = arena.take<float>((size_t)cfg.max_len * D);
     head_p.assign(cfg.n_exits, nullptr);
     head_f8.assign(cfg.n_exits, nullptr);
@@ -177,9 +178,8 @@ GroupWs carve_group_ws(const eec_config& c, int B, int Tq, char* base) {
 struct Workspace {
   float* x;
   float* y;  // [(E-1)][M][256]: exit rows for the batched head launch when the caller passes no tap buffer
-  half_t *mid_hi, *mid_lo;
   GroupWs gw;
-  int *enc_len, *mid_e;
+  int* enc_len;
   size_t bytes;
 };
 
@@ -191,11 +191,8 @@ Workspace carve_ws(const eec_config& c, int B, int T, char* base) {
   Workspace w;
   w.x = a.take<float>(M * D);
   w.y = a.take<float>((size_t)(c.n_exits > 1 ? c.n_exits - 1 : 0) * M * D);
-  w.mid_hi = a.take<half_t>((size_t)B * T1 * D);
-  w.mid_lo = a.take<half_t>((size_t)B * T1 * D);
   carve_group_planes(a, w.gw, c, B, Tq);
   w.enc_len = a.take<int>(B);
-  w.mid_e = a.take<int>((size_t)B * T1);
   w.bytes = up256(a.off);
   return w;
 }
@@ -420,8 +417,9 @@ static int pack_stem_and_heads(eec_encoder* enc, const float* sub0_w, const floa
     EEC_HIP(cp(enc->sub_b1, sub0_b, D));
   }
   if (enc->has_stem) {
-    EEC_HIP(launch_pack_conv_jci(sub1_w, D, D, enc->sub_w2p, st));
-    EEC_HIP(cp(enc->sub_b2, sub1_b, D));
+    // the two convolutions compose into one (k = 7, stride 4): here, once per pack, and nowhere else
+    EEC_HIP(launch_stem_fold(sub0_w, sub0_b, sub1_w, sub1_b, D, c.n_mels, enc->sub_weff, enc->sub_bf, st));
+    EEC_HIP(launch_pack_frags(enc->sub_weff, D, 7 * c.n_mels, enc->sub_wfp, (float)(1 << kStemWShift), st));
   }
   if (enc->has_stem1) EEC_HIP(cp(enc->pe, pe, (size_t)c.max_len * D));
   enc->has_heads = head_w != nullptr;
@@ -546,7 +544,7 @@ static int forward_impl(eec_encoder* enc, const float* mel, const int64_t* lengt
   EEC_HIP(launch_enc_lengths((const long long*)lengths, B, Tq, ws.enc_len, st));
   if (Tp != Tq) EEC_HIP(hipMemsetAsync(ws.gw.vt, 0, (size_t)2 * B * Tp * D * sizeof(half_t), st));
   {
-    SubsampleArgs a{mel, B, c.n_mels, T, T1, Tq, D, ws.mid_e, enc->sub_w1p, enc->sub_b1, enc->sub_w2p, enc->sub_b2, enc->pe, ws.mid_hi, ws.mid_lo, ws.x};
+    SubsampleArgs a{mel, B, c.n_mels, T, T1, Tq, D, nullptr, nullptr, enc->sub_wfp, enc->sub_bf, enc->pe, ws.x};
     TIMED(KC_STEM, launch_subsample(a, 3, st));  // raw power mel: always hi/lo split (1 % of the flops)
   }
   ++step;
@@ -729,7 +727,7 @@ int eec_encoder_stem1_forward(eec_encoder* enc, const float* mel, int B, int T, 
   const int T1 = (T - 3) / 2 + 1;
   if (T1 > c.max_len) return fail(EEC_ERR_BAD_ARG, "T1 exceeds the positional-encoding table (max_len)");
   hipStream_t st = (hipStream_t)stream;
-  SubsampleArgs a{mel, B, c.n_mels, T, T1, T1, c.d_model, nullptr, enc->sub_w1p, enc->sub_b1, nullptr, nullptr, enc->pe, nullptr, nullptr, x};
+  SubsampleArgs a{mel, B, c.n_mels, T, T1, T1, c.d_model, enc->sub_w1p, enc->sub_b1, nullptr, nullptr, enc->pe, x};
   TIMED(KC_STEM, launch_subsample_single(a, st));
   return 0;
 }

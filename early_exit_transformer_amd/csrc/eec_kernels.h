@@ -175,20 +175,21 @@ hipError_t launch_ffn_train_fwd(const ChainArgs& a, int np, hipStream_t st);
 hipError_t launch_ffn_train_bwd(const ChainArgs& a, int np, hipStream_t st);
 hipError_t launch_ffn_chain(const ChainArgs& a, int np, int np_front, int np_tail, bool front, bool tail, bool relu, hipStream_t st);
 
+// The packed folded-stem weights carry 2^kStemWShift (exact), which keeps their lo halves out of fp16's subnormals; the stem kernel
+// starts its accumulators at b_eff * 2^kStemWShift and takes the factor out again in its epilogue.
+constexpr int kStemWShift = 8;
 struct SubsampleArgs {
   const float* mel;  // [B][n_mels][T]
   int B, n_mels, T, T1, Tq, D;
-  int* mid_e;        // [B*T1]: power-of-two exponent of every conv1 output row's scaled fp16 domain (scratch; unused by the one-conv stem)
-  const uint4* w1p;       // packed conv1 weight as [256][n_mels*3] (its own [ci][j] flattening)
+  const uint4* w1p;       // packed conv1 weight as [D][n_mels*3] (its own [ci][j] flattening): the one-convolution stem
   const float* b1;
-  const uint4* w2p;       // packed conv2 weight as [256][3*256], k ordered (j, ci)
-  const float* b2;
-  const float* pe;        // [max_len][256]
-  half_t *mid_hi, *mid_lo;  // [B*T1][256] scratch planes (scaled by 2^-6)
-  float* x;               // [B*Tq][256]
+  const uint4* wfp;       // packed folded weight 2^kStemWShift * W_eff as [D][7*n_mels], k ordered (tap, ci): the two-convolution stem
+  const float* bf;        // b_eff [D]
+  const float* pe;        // [max_len][D]
+  float* x;               // [B*Tq][D]  (one-convolution stem: [B*T1][D])
 };
-hipError_t launch_subsample(const SubsampleArgs& a, int np, hipStream_t st);
-hipError_t launch_subsample_single(const SubsampleArgs& a, hipStream_t st);  // conv1 only: x = conv + bias + pe (mid / w2p / b2 unused)
+hipError_t launch_subsample(const SubsampleArgs& a, int np, hipStream_t st);         // both convolutions as one k=7, s=4 product (w1p / b1 unused)
+hipError_t launch_subsample_single(const SubsampleArgs& a, hipStream_t st);  // conv1 only: x = conv + bias + pe (wfp / bf unused)
 
 // weight packing (device -> device)
 hipError_t launch_pack_frags(const float* w, int N, int K, uint4* out, float scale, hipStream_t st);  // out may point into a larger matrix: n-tile nt0 of [N'][K] starts at out + nt0*(K/16)*128  // scale*W[N][K] -> fragments
@@ -206,8 +207,9 @@ hipError_t launch_scale_copy(const float* src, float* dst, int n, float scale, h
 hipError_t launch_fold_dw(const float* dw_w, const float* dw_b, const float* bn_w, const float* bn_b,
                           const float* bn_rm, const float* bn_rv, int ksize, int D, float* wfold, float* bfold,
                           hipStream_t st);
-// conv weight [co][ci][3] -> fragments of the [co][3*ci_total] matrix with k ordered (j, ci)
-hipError_t launch_pack_conv_jci(const float* w, int cout, int cin, uint4* out, hipStream_t st);
+// Two Conv1d(k=3, s=2) back to back -> one Conv1d(k=7, s=4), composed in fp64 from w1 [D][cin][3], b1, w2 [D][D][3], b2:
+// weff [D][7*cin] with k ordered (tap, ci), beff [D]
+hipError_t launch_stem_fold(const float* w1, const float* b1, const float* w2, const float* b2, int D, int cin, float* weff, float* beff, hipStream_t st);
 hipError_t launch_fill_int(int* dst, int n, int v, hipStream_t st);
 hipError_t launch_enc_lengths(const long long* lengths, int B, int Tq, int* enc_len, hipStream_t st);
 

@@ -178,29 +178,35 @@ hipError_t launch_pack_frags_f8(const float* w, int N, int K, uint4* out, float 
   return hipGetLastError();
 }
 
-// conv2 weight [co][ci][3] -> fragments of W'[co][k], k = j*cin + ci  (frame-major im2col order)
-__global__ void pack_conv_jci_kernel(const float* __restrict__ w, int cout, int cin, uint4* __restrict__ out, int total) {
+// The stem's two Conv1d(k=3, stride=2) with nothing between them are one Conv1d(k=7, stride=4):
+//   W_eff[co][ci][k] = sum over (j1, j2) with 2 j2 + j1 = k, over c, of W2[co][c][j2] * W1[c][ci][j1]
+//   b_eff[co]        = b2[co] + sum over c, j2 of W2[co][c][j2] * b1[c]
+// accumulated in fp64 from the fp32 parameters; weff[co][k*cin + ci] (frame-major im2col order).  Taps 2 and 4 have two (j1, j2) pairs.
+__global__ void stem_fold_w_kernel(const float* __restrict__ w1, const float* __restrict__ w2, int D, int cin, float* __restrict__ weff, int total) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
-  const int lane = idx & 63, frag = idx >> 6;
-  const int K = 3 * cin, KS = K / 16;
-  const int nt = frag / KS, s = frag - nt * KS;
-  const int n = nt * 32 + (lane & 31), k0 = s * 16 + 8 * (lane >> 5);
-  h8 hi, lo;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int k = k0 + i, j = k / cin, ci = k - j * cin;
-    const float v = (n < cout) ? w[((size_t)n * cin + ci) * 3 + j] : 0.f;
-    EEC_SPLIT(v, hi, lo, i);
+  const int co = idx / (7 * cin), rem = idx - co * 7 * cin, k = rem / cin, ci = rem - k * cin;
+  double s = 0.0;
+  for (int j2 = 0; j2 < 3; ++j2) {
+    const int j1 = k - 2 * j2;
+    if (j1 < 0 || j1 > 2) continue;
+    for (int c = 0; c < D; ++c) s += (double)w2[((size_t)co * D + c) * 3 + j2] * (double)w1[((size_t)c * cin + ci) * 3 + j1];
   }
-  out[(size_t)frag * 128 + lane] = __builtin_bit_cast(uint4, hi);
-  out[(size_t)frag * 128 + 64 + lane] = __builtin_bit_cast(uint4, lo);
+  weff[idx] = (float)s;
 }
-
-hipError_t launch_pack_conv_jci(const float* w, int cout, int cin, uint4* out, hipStream_t st) {
-  if ((3 * cin) % 16) return hipErrorInvalidValue;
-  const int total = ((cout + 31) / 32) * (3 * cin / 16) * 64;
-  hipLaunchKernelGGL(pack_conv_jci_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, cout, cin, out, total);
+__global__ void stem_fold_b_kernel(const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2, int D, float* __restrict__ beff) {
+  const int co = blockIdx.x * blockDim.x + threadIdx.x;
+  if (co >= D) return;
+  double s = (double)b2[co];
+  for (int c = 0; c < D; ++c)
+    for (int j2 = 0; j2 < 3; ++j2) s += (double)w2[((size_t)co * D + c) * 3 + j2] * (double)b1[c];
+  beff[co] = (float)s;
+}
+hipError_t launch_stem_fold(const float* w1, const float* b1, const float* w2, const float* b2, int D, int cin, float* weff, float* beff, hipStream_t st) {
+  const int total = D * 7 * cin;
+  hipLaunchKernelGGL(stem_fold_w_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w1, w2, D, cin, weff, total);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(stem_fold_b_kernel, dim3((D + 63) / 64), dim3(64), 0, st, b1, w2, b2, D, beff);
   return hipGetLastError();
 }
 
