@@ -20,7 +20,9 @@
   csrc/ctc_lexbeam.hip): words that are lexicon entries by construction, and the posterior of the top hypothesis; with ``lm=`` or
   ``args.lm`` -- an ARPA file -- under a back-off n-gram word model (``lexicon.NGramLM``), else without one; with
   ``smearing="max"`` or ``args.lm_smearing`` with LM look-ahead inside words (max trie smearing, which the third-party decoder
-  always applies; off by default here).
+  always applies; off by default here); with ``log_add=True`` or ``args.lm_log_add`` with log-add merging.
+* ``BeamInference.beam_predict``  util/beam_infer.py:66-75, 85-90: the character-lexicon decoder (``log_add=True``,
+  ``word_score=WORD_SCORE``, torchaudio's default token names) over ``model.ctc_encoder``'s emission, on the same kernel.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
@@ -150,23 +152,28 @@ class BeamInference:
     util/conf.py:455-486 injects); every one of them can also be given per call, as in the reference."""
 
     N_BEST = 1       # util/beam_infer.py:42
-    W_INS = 0        # the word score of the reference's six lexicon decoders (w_ins, util/beam_infer.py:54); its WORD_SCORE = -4
-                     # (:41,74) belongs to the character-lexicon decoder of beam_predict, which is not served
+    W_INS = 0        # the word score of the reference's six lexicon decoders (w_ins, util/beam_infer.py:54)
+    WORD_SCORE = -4  # util/beam_infer.py:41,74: the word score of the character-lexicon decoder behind beam_predict
 
     LM_WEIGHT = 1.0  # util/beam_infer.py:40 (its comment keeps 3.23, the value of the "bigger LM" setting)
 
-    def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None, smearing: Optional[str] = None):
+    def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None, smearing: Optional[str] = None,
+                 log_add: Optional[bool] = None):
         """``lm``: an ``NGramLM``, or the path of an ARPA file (None: ``args.lm`` if there is one) that is read at the first use
         against the trie in use.  ``smearing``: None (then ``args.lm_smearing`` if there is one) or ``"max"``: LM look-ahead by max
         trie smearing in ``ctc_predict`` / ``ctc_predict_``.  The third-party decoder always smears; here the default is off, so
-        a model alone decodes as before.  Without a model there is nothing to smear and the setting is not used."""
+        a model alone decodes as before.  Without a model there is nothing to smear and the setting is not used.
+        ``log_add``: None (then ``args.lm_log_add`` if there is one, else False) or a bool: log-add instead of Viterbi merging in
+        ``ctc_predict`` / ``ctc_predict_``.  ``beam_predict`` always merges by log-add, as the reference's decoder does."""
         self.args = args
         self._trie = trie
         self._lm = lm if lm is not None else getattr(args, "lm", None)
         self._smearing = smearing if smearing is not None else getattr(args, "lm_smearing", None)
         if self._smearing not in (None, "max"):
             raise ValueError(f"BeamInference: smearing must be None or 'max', got {self._smearing!r}")
+        self._log_add = bool(getattr(args, "lm_log_add", False) if log_add is None else log_add)
         self._lm_read = None  # (the trie a path was read against, its NGramLM)
+        self._char_trie = None  # beam_predict's trie, apart from the BPE one
 
     sequence_length_penalty = staticmethod(sequence_length_penalty)
 
@@ -189,19 +196,36 @@ class BeamInference:
             self._lm_read = (trie, NGramLM.from_arpa(self._lm, trie))
         return self._lm_read[1]
 
-    def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size, lm_weight=None):
+    def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size, lm_weight=None, log_add=None, word_score=None):
         """(transcript of the best hypothesis per utterance, scores [B, nbest] and n_hyp [B] on the host)."""
         trie = self._lexicon_trie(trie)
         nbest = self.N_BEST if nbest is None else nbest
+        log_add = self._log_add if log_add is None else log_add
         lm = self._lexicon_lm(trie)
         with_lm = {} if lm is None else {"lm": lm, "lm_weight": self.LM_WEIGHT if lm_weight is None else lm_weight}
         if lm is not None and self._smearing is not None:
             with_lm["smearing"] = self._smearing
         words, word_count, _, _, _, scores, n_hyp = ctc_lexicon_decode(emission, trie, beam_size=self._arg(beam_size, "beam_size"), nbest=nbest,
-                                                                       word_score=self.W_INS, **with_lm)
+                                                                       word_score=self.W_INS if word_score is None else word_score,
+                                                                       log_add=log_add, **with_lm)
         words, word_count, n_hyp = words[:, 0].cpu(), word_count[:, 0].cpu().tolist(), n_hyp.cpu().tolist()
         texts = [" ".join(trie.words[w] for w in words[b, : word_count[b]].tolist()).strip() if n_hyp[b] else "" for b in range(len(n_hyp))]
         return texts, scores.cpu(), n_hyp
+
+    def beam_predict(self, model, input_sequence) -> str:
+        """util/beam_infer.py:85-90: ``model.ctc_encoder(input_sequence)`` -- any object with that method, [B, T', V] log-probs --
+        decoded by the reference's character-lexicon decoder (util/beam_infer.py:66-75): log-add merging, ``word_score=WORD_SCORE``,
+        ``nbest=1``, ``args.beam_size``, the trie of ``args.lexicon`` / ``args.tokens`` with torchaudio's default ``blank_token="-"``
+        and ``sil_token="|"`` (built at the first use and kept apart from the BPE trie), the configured model, if there is one, at
+        ``LM_WEIGHT``.  Returns the transcript of the FIRST utterance's best hypothesis, its words joined by spaces and stripped;
+        no complete hypothesis gives ``""`` (the reference would raise an IndexError: a stated divergence, as in ``ctc_predict_``).
+        The emission stays on the device (the reference moves it to the host for the third-party decoder)."""
+        emission = model.ctc_encoder(input_sequence)
+        if self._char_trie is None:
+            if self.args is None or not hasattr(self.args, "lexicon") or not hasattr(self.args, "tokens"):
+                raise ValueError("beam_predict: there is no args.lexicon / args.tokens")
+            self._char_trie = TokenTrie.from_files(self.args.lexicon, self.args.tokens, blank_token="-", sil_token="|")
+        return self._lexicon_decode(emission[:1], self._char_trie, 1, None, None, log_add=True, word_score=self.WORD_SCORE)[0][0]
 
     def ctc_predict_(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,
                      beam_size: Optional[int] = None, lm_weight: Optional[float] = None) -> List[str]:
@@ -209,7 +233,8 @@ class BeamInference:
         [B, T', V] (on the device; it stays there), its words joined by spaces and stripped.  ``index`` selects the reference's
         per-exit decoder; all six are configured alike (w_ins = 0), so it is accepted and unused.  An utterance with no complete
         hypothesis gives ``""`` (the reference would raise an IndexError: a stated divergence).  With a model (``lm=`` of the
-        constructor or ``args.lm``) the search runs under it at ``lm_weight`` (None: ``LM_WEIGHT``)."""
+        constructor or ``args.lm``) the search runs under it at ``lm_weight`` (None: ``LM_WEIGHT``); with ``log_add`` of the
+        constructor (or ``args.lm_log_add``) hypotheses that meet are summed instead of the best one kept."""
         return self._lexicon_decode(emission, trie, nbest, beam_size, lm_weight)[0]
 
     def ctc_predict(self, emission: Tensor, index: int = 5, trie: Optional[TokenTrie] = None, nbest: Optional[int] = None,

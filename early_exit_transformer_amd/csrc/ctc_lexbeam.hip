@@ -6,8 +6,9 @@
 // token-trie beam search under CTC, Viterbi merging (log_add=False), the word model's score at every word end and its end-of-sentence
 // term -- stated completely in include/eec.h; tests/lexbeam_cases.py and tests/lexbeam_lm_cases.py are its plain-Python statement
 // and the judge of this kernel.  Parity with the third-party decoder is unpinned.
-// Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
-// binary KenLM files, beams over 16.
+// log_add=True, the reference's character-lexicon branch (util/beam_infer.py:66-75), is eec_ctc_lexbeam_logadd_decode: the same
+// search with the merged hypotheses' probabilities summed (the LA instantiations, at the end of this comment).
+// Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 16.
 //
 // One 256-thread workgroup per sequence, one launch for the batch; thread c owns frame label c (V <= 256).  All candidates that
 // can merge share their frame label, so every merge is local to one thread.  Per frame:
@@ -22,8 +23,8 @@
 //     candidates only after it won a round.  The first round's winner gives the beam threshold;
 //   * every survivor leaves (parent rank, label, completed word + 1) in a back-pointer table, 8 bytes per (frame, rank).
 // At the end the complete hypotheses (node 0) are already in rank order; up to nbest threads walk their back-pointers, one each.
-// Scores are fp32 additions in the order include/eec.h writes them, no reductions, no log / exp: the result is bit-identical to
-// the statement.  Latency-bound integer / scalar work over T' serial frames: it is sized to keep all E * B = 384 sequences of a
+// In the three Viterbi entries scores are fp32 additions in the order include/eec.h writes them, no reductions, no log / exp: the
+// result is bit-identical to the statement.  Latency-bound integer / scalar work over T' serial frames: it is sized to keep all E * B = 384 sequences of a
 // batch in flight at once (5.4 KB of LDS, well under two workgroups per CU), not for the roofline.  The real lexicon's image
 // (89 114 words, 162 621 nodes, 1.5 MB) is read-only and shared by all workgroups: it sits in L2.
 //
@@ -38,6 +39,16 @@
 // words at or below it, a step into a node is charged the increase of that maximum, and a word end takes the advance payment back.
 // smax[y] is loaded beside cbeg[y] / word_of[y]; the payment outstanding at a hypothesis' node rides in its beam entry in LDS and is
 // written by the round's winner.  The two other instantiations do not see any of it: their beam entry and arguments are unchanged.
+//
+// With log-add merging (LA = true on any of the three, eec_ctc_lexbeam_logadd_decode) a thread keeps, beside the raw score of each of
+// its <= 32 candidates, an accumulator that starts as the raw score (32 KB of LDS per workgroup, a column per thread, touched only by
+// threads with two or more live candidates: as registers they pushed the kernel past 256 and the CU down to one workgroup).  The pairwise merge loop is the Viterbi one -- the raw scores
+// decide who is eliminated, in the same pair order --, and at every elimination the winner's accumulator takes log_add(winner's,
+// loser's): that pair order IS the fold order include/eec.h states.  After the loop the accumulators replace the scores, so the
+// rounds, the threshold and the beam work on merged scores.  log_add is the fixed fp32 sequence stated in include/eec.h (lb_log_add
+// below: add, subtract, multiply, compare, rintf, ldexpf; no libm transcendental, no division), the same function on the host: the
+// LA entries are bit-identical to the statement, whose log_add is that sequence.  It is called out of line (merges are rare per
+// thread and frame; 496 inlined copies would not be).  The LA = false instantiations compile to what they were.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -167,6 +178,56 @@ __device__ __forceinline__ float lm_add(float s, float lm_weight, float acc) {
   return s + term;
 }
 
+// log_add(a, b) = log(exp(a) + exp(b)) as the fixed sequence of fp32 operations include/eec.h states (constants, order, cutoff):
+// every step is an IEEE-exact operation and nothing contracts, so device, host and a numpy float32 restatement agree bit for bit
+constexpr float kLaCutoff = -17.34375f;  // exp(d) < 2^-25 at and below it: the sum would round back to hi
+__host__ __device__ __forceinline__ float lb_log_add(float a, float b) {
+#pragma clang fp contract(off)
+  const bool a_hi = a > b;
+  const float hi = a_hi ? a : b, lo = a_hi ? b : a;
+  const float d = lo - hi;
+  if (!(d > kLaCutoff)) return hi;
+  // x = exp(d): d = n ln 2 + r, |r| <= ln 2 / 2; exp(r) by its Taylor polynomial of degree 7
+  const float n = rintf(d * 1.44269502f);
+  float r = d - n * 0.693145751953125f;
+  r = r - n * 1.42860677e-06f;
+  float p = 1.98412701e-04f;
+  p = p * r + 1.38888892e-03f;
+  p = p * r + 8.33333377e-03f;
+  p = p * r + 4.16666679e-02f;
+  p = p * r + 0.166666672f;
+  p = p * r + 0.5f;
+  p = p * r + 1.0f;
+  p = p * r + 1.0f;
+  const float x = ldexpf(p, (int)n);
+  // log(1 + x): u = 1 + x in [1, 2], halved above sqrt 2; log u = m P(m), m = u - 1 (exact), P of degree 10
+  float u = 1.0f + x;
+  const bool halved = u > 1.41421354f;
+  if (halved) u = u * 0.5f;
+  const float m = u - 1.0f;
+  float q = 0.0657233745f;
+  q = q * m + -0.116206668f;
+  q = q * m + 0.119458839f;
+  q = q * m + -0.12420819f;
+  q = q * m + 0.142122895f;
+  q = q * m + -0.166665554f;
+  q = q * m + 0.20002535f;
+  q = q * m + -0.250000626f;
+  q = q * m + 0.333333015f;
+  q = q * m + -0.5f;
+  q = q * m + 1.0f;
+  float s = m * q;
+  if (halved) s = s + 0.693147182f;
+  return hi + s;
+}
+
+// the merge loop's call: one copy of the sequence for its 496 pairs
+__device__ __noinline__ float lb_log_add_call(float a, float b) { return lb_log_add(a, b); }
+
+__global__ void ctc_log_add_kernel(const float* a, const float* b, float* out, int n) {
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) out[k] = lb_log_add(a[k], b[k]);
+}
+
 template <bool LM, bool SM, typename Args>
 __device__ __forceinline__ bool lm_fits(const Args& a) {
   bool fits = true;
@@ -175,8 +236,8 @@ __device__ __forceinline__ bool lm_fits(const Args& a) {
   return fits;
 }
 
-// SM (with LM only): LM look-ahead by the smear table
-template <bool LM, bool SM = false>
+// SM (with LM only): LM look-ahead by the smear table.  LA: log-add merging instead of Viterbi merging
+template <bool LM, bool SM = false, bool LA = false>
 __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::conditional_t<SM, LbSmArgs, std::conditional_t<LM, LbLmArgs, LbArgs>> a) {
   static_assert(LM || !SM, "smearing needs a model");
   using Beam = std::conditional_t<SM, LbBeamSm, LbBeam>;
@@ -292,6 +353,15 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
 
     // merge equal (node, history) among this thread's candidates, in id order (w = 0 before w = 1, then the beam rank)
     if (live >= 2) {
+      // log-add: the accumulators, the raw scores to begin with.  They live in LDS, candidate-major (column c is this thread's:
+      // constant offsets, no bank conflict, no barrier): 32 more registers would cost the second workgroup of a CU
+      float* acc = nullptr;
+      if constexpr (LA) {
+        __shared__ float la_acc[2 * kLbMaxBeam * kLbThreads];
+        acc = la_acc + c;
+#pragma unroll
+        for (int i = 0; i < kLbMaxBeam; ++i) acc[i * kLbThreads] = s0[i], acc[(16 + i) * kLbThreads] = s1[i];
+      }
 #pragma unroll
       for (int p = 0; p < 2 * kLbMaxBeam; ++p) {
         if (!in_beam(p & 15)) continue;
@@ -302,12 +372,29 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
           const unsigned long long hp = p < 16 ? h0[p & 15] : h1[p & 15], hq = q < 16 ? h0[q & 15] : h1[q & 15];
           float& sp = p < 16 ? s0[p & 15] : s1[p & 15];
           float& sq = q < 16 ? s0[q & 15] : s1[q & 15];
-          if (np_ == nq_ && hp == hq) {
+          if constexpr (LA) {
+            // the raw scores decide as above; the winner's accumulator takes the sum.  Dead candidates take no part
+            if (np_ == nq_ && hp == hq && sp > -INFINITY && sq > -INFINITY) {
+              const float sum = lb_log_add_call(acc[p * kLbThreads], acc[q * kLbThreads]);
+              if (sq > sp)
+                acc[q * kLbThreads] = sum, sp = -INFINITY;
+              else
+                acc[p * kLbThreads] = sum, sq = -INFINITY;
+            }
+          } else if (np_ == nq_ && hp == hq) {
             if (sq > sp)
               sp = -INFINITY;
             else
               sq = -INFINITY;
           }
+        }
+      }
+      // from here on a survivor's score is its merged score
+      if constexpr (LA) {
+#pragma unroll
+        for (int i = 0; i < kLbMaxBeam; ++i) {
+          if (s0[i] > -INFINITY) s0[i] = acc[i * kLbThreads];
+          if (s1[i] > -INFINITY) s1[i] = acc[(16 + i) * kLbThreads];
         }
       }
     }
@@ -468,12 +555,12 @@ static size_t lm_image_dwords(unsigned long long nodes, unsigned long long lex_w
   return (size_t)(kLmHeader + (nodes + 1) + (nodes - 1) + 3 * nodes + lex_words + 1) & ~(size_t)1;
 }
 
-// the checks and the launch of the three entries
+// the checks and the launch of the four entries
 static int lb_decode(const char* who, const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
                      int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words, int32_t* words,
                      int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores, int32_t* n_hyp, void* workspace,
                      size_t workspace_bytes, void* stream, bool with_lm, const void* lm, float lm_weight, bool with_smear = false,
-                     const void* smear = nullptr) {
+                     const void* smear = nullptr, bool log_add = false) {
   using eech::fail;
   const std::string me(who);
   if (n_seq < 0 || Tq < 1 || max_words < 1) return fail(EEC_ERR_BAD_ARG, me + ": needs n_seq >= 0, Tq >= 1, max_words >= 1");
@@ -499,7 +586,13 @@ static int lb_decode(const char* who, const float* logp, int n_seq, int Tq, int 
   a.words = words, a.word_count = word_count, a.tokens = tokens, a.token_count = token_count, a.timesteps = timesteps, a.n_hyp = n_hyp;
   a.scores = scores, a.backptr = (int2*)workspace;
   a.lm = (const int*)lm, a.lm_weight = lm_weight, a.smear = (const int*)smear;
-  if (with_smear)
+  if (log_add && with_smear)
+    hipLaunchKernelGGL((ctc_lexbeam_kernel<true, true, true>), dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
+  else if (log_add && with_lm)
+    hipLaunchKernelGGL((ctc_lexbeam_kernel<true, false, true>), dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbLmArgs&)a);
+  else if (log_add)
+    hipLaunchKernelGGL((ctc_lexbeam_kernel<false, false, true>), dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbArgs&)a);
+  else if (with_smear)
     hipLaunchKernelGGL((ctc_lexbeam_kernel<true, true>), dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, a);
   else if (with_lm)
     hipLaunchKernelGGL(ctc_lexbeam_kernel<true>, dim3(n_seq), dim3(kLbThreads), 0, (hipStream_t)stream, (const LbLmArgs&)a);
@@ -789,6 +882,30 @@ int eec_ctc_lexbeam_lm_smear_decode(const float* logp, int n_seq, int Tq, int V,
   return eec::lb_decode("eec_ctc_lexbeam_lm_smear_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score,
                         sil_score, beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace,
                         workspace_bytes, stream, true, lm, lm_weight, true, smear);
+}
+
+int eec_ctc_lexbeam_logadd_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                                  int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                                  int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps,
+                                  float* scores, int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm,
+                                  float lm_weight, const void* smear) {
+  if (smear && !lm) return eech::fail(EEC_ERR_BAD_ARG, "eec_ctc_lexbeam_logadd_decode: smear without lm: it is the model's scores that are smeared");
+  return eec::lb_decode("eec_ctc_lexbeam_logadd_decode", logp, n_seq, Tq, V, em_len, trie, blank, sil, beam_size, nbest, word_score,
+                        sil_score, beam_threshold, max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, workspace,
+                        workspace_bytes, stream, lm != nullptr, lm, lm_weight, smear != nullptr, smear, true);
+}
+
+float eec_ctc_log_add_host(float a, float b) { return eec::lb_log_add(a, b); }
+
+int eec_ctc_log_add(const float* a, const float* b, float* out, int n, void* stream) {
+  using eech::fail;
+  if (n < 0) return fail(EEC_ERR_BAD_ARG, "eec_ctc_log_add: n must not be negative");
+  if (n == 0) return 0;
+  if (!a || !b || !out) return fail(EEC_ERR_BAD_ARG, "eec_ctc_log_add: null argument (a, b, out)");
+  const int blocks = std::min((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(eec::ctc_log_add_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
+  EEC_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

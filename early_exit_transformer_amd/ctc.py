@@ -64,7 +64,7 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
                        beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None, lm=None,
-                       lm_weight: float = 0.0, smearing: Optional[str] = None):
+                       lm_weight: float = 0.0, smearing: Optional[str] = None, log_add: bool = False):
     """Lexicon-constrained CTC beam search with N-best of [n, T', V] log-probs on the device (eec_ctc_lexbeam_decode): the
     decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)``,
     util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
@@ -74,6 +74,10 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     step inside a word is charged the increase of the best score the model gives any word still reachable, and the word end takes
     that advance back.  A complete hypothesis scores what it scores without smearing; what changes is which hypotheses survive
     pruning.  The third-party decoder always smears; the default here stays off, so existing calls return what they returned.
+    ``log_add``: False -- Viterbi merging: of the candidates that reach the same state the best one's score stays -- or True
+    (eec_ctc_lexbeam_logadd_decode; torchaudio's ``log_add=True``, the reference's ``beam_predict`` setting): the survivor scores the
+    log of the sum of their probabilities, by the bit-reproducible ``log_add`` of include/eec.h.  It combines with every ``lm`` /
+    ``smearing`` setting.
     ``trie``: a ``lexicon.TokenTrie`` (it carries V, blank and sil); ``em_len`` [n] frames per sequence (None: T'); ``max_words``
     (None: T', always enough): the words kept per hypothesis -- ``word_count`` is the true count even above it.  Returns
     ``(words [n, nbest, max_words] int32 indices into trie.words, word_count [n, nbest], tokens [n, nbest, T'], token_count [n, nbest],
@@ -108,7 +112,11 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
                 int(beam_size), int(nbest), float(word_score), float(sil_score), float(beam_threshold), max_words, words.data_ptr(),
                 word_count.data_ptr(), tokens.data_ptr(), token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
                 ws.data_ptr(), ws_bytes, stream_ptr(dev))
-        if lm is None:
+        if log_add:
+            capi.check(lib.eec_ctc_lexbeam_logadd_decode(*args, None if lm is None else lm.on(dev).data_ptr(), float(lm_weight),
+                                                         None if smearing is None else lm.smear(trie).on(dev).data_ptr()),
+                       "eec_ctc_lexbeam_logadd_decode")
+        elif lm is None:
             capi.check(lib.eec_ctc_lexbeam_decode(*args), "eec_ctc_lexbeam_decode")
         elif smearing is None:
             capi.check(lib.eec_ctc_lexbeam_lm_decode(*args, lm.on(dev).data_ptr(), float(lm_weight)), "eec_ctc_lexbeam_lm_decode")

@@ -257,8 +257,9 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
  * model -- as stated here; tests/lexbeam_cases.py is its plain-Python statement.  PARITY WITH THE THIRD-PARTY DECODER IS UNPINNED.
  * A back-off n-gram word model joins through eec_ctc_lexbeam_lm_decode, stated after this entry; without one nothing below changes.
  * LM look-ahead (max trie smearing) joins through eec_ctc_lexbeam_lm_smear_decode, stated after that one.
- * Out of scope: log_add=True (the reference's character-lexicon branch), unknown-word scores other than through the model's <unk>,
- * binary KenLM files, beams over 16.
+ * log_add=True (the reference's character-lexicon branch, util/beam_infer.py:66-75) is eec_ctc_lexbeam_logadd_decode, stated last:
+ * only the Merging rule below changes.
+ * Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 16.
  *
  * Lexicon: n_words spellings, each a non-empty sequence of token ids in [0, V), none of them `blank` or (when given) `sil`.  The
  *   trie's root is node 0.  A node "ends word w" when w is the FIRST word in file order with that spelling (later duplicates are
@@ -288,8 +289,9 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
  *   is outside [1, T'], or when a frame left no candidate.
  * Per hypothesis: its words; its collapsed label sequence (blank frames dropped, runs collapsed, sil included: torchaudio's
  *   CTCHypothesis.tokens); the first frame of each such label (timesteps); its score.
- * hist identity on the device is a chained 64-bit hash (a collision is not handled).  There are no reductions and no log / exp in
- * this arithmetic: scores are bit-identical to a statement that keeps fp32 and the written order of additions.
+ * hist identity on the device is a chained 64-bit hash (a collision is not handled).  In this entry and the two that follow there
+ * are no reductions and no log / exp in the arithmetic: scores are bit-identical to a statement that keeps fp32 and the written
+ * order of additions.  (eec_ctc_lexbeam_logadd_decode adds one function, log_add, itself a stated sequence of fp32 operations.)
  *
  * eec_ctc_trie_pack is HOST code and needs no device:
  *   spellings [offsets[n_words]] int32 token ids, flat; offsets [n_words + 1] int64, offsets[0] = 0, strictly ascending
@@ -434,6 +436,63 @@ int eec_ctc_lexbeam_lm_smear_decode(const float* logp, int n_seq, int Tq, int V,
                                     int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps,
                                     float* scores, int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm,
                                     float lm_weight, const void* smear);
+
+/* The same search with LOG-ADD merging: torchaudio's ctc_decoder(..., log_add=True), which the reference switches on for its
+ * character-lexicon decoder behind beam_predict (util/beam_infer.py:66-75, 85-90).  A hypothesis then scores the sum over the
+ * alignments merged into it, not the best single one.  It works without a model (lm == NULL: eec_ctc_lexbeam_decode's search), with
+ * the model (smear == NULL: eec_ctc_lexbeam_lm_decode's) and with the model plus max smearing (eec_ctc_lexbeam_lm_smear_decode's);
+ * of those statements only the Merging rule changes.  tests/lexbeam_logadd_cases.py is the plain-Python statement.  PARITY WITH THE
+ * THIRD-PARTY DECODER IS UNPINNED, as above.
+ *
+ * Merging (log-add): the candidates of a frame with the same (node, tok, pb, hist) form a group (dropped candidates -- score not
+ *   > -inf -- are no members: Dropping comes first).  Every member carries its raw score and an accumulator acc, acc = raw at first.
+ *   With the members in ascending id order m_0 .. m_{k-1}, all alive:
+ *       for p = 0 .. k-1:  for q = p+1 .. k-1:  if m_p and m_q are both alive:
+ *           sum = log_add(acc_p, acc_q)
+ *           if raw_q > raw_p:  acc_q = sum, m_p is eliminated      (m_p takes no part in any later pair)
+ *           else:              acc_p = sum, m_q is eliminated
+ *   This fixes the fold order (fp32 log_add is not associative).  The raw scores alone decide who wins a pair, so the survivor is
+ *   the member with the highest raw score, the lowest id among equals -- the Viterbi survivor --, and it keeps its own id and
+ *   back-pointer; its score becomes its acc, the log of the sum of the members' probabilities.  A group of one keeps its score.
+ *   The LM and smearing terms enter every member's raw score before the merge, exactly where they enter without log-add.
+ *   Pruning, the beam order, the next frame's scores, the </s> term and the final order all work on merged scores.
+ *
+ * log_add(a, b), fp32, every operation rounded on its own (no fused multiply-add), in this order:
+ *     hi = a if a > b else b;  lo = the other;  d = lo - hi
+ *     if not d > -17.34375:  return hi                        (the cutoff: exp(d) < 2^-25; also taken when d is NaN)
+ *     n = rint(d * 1.44269502)                                 (round to nearest, ties to even; n in -25 .. 0)
+ *     r = d - n * 0.693145751953125;  r = r - n * 1.42860677e-06
+ *     p = 1.98412701e-04;  then p = p * r + c for c = 1.38888892e-03, 8.33333377e-03, 4.16666679e-02, 0.166666672, 0.5, 1, 1
+ *     x = ldexp(p, n)                                          (exp(d); exact scaling)
+ *     u = 1 + x;  halved = u > 1.41421354;  if halved: u = u * 0.5
+ *     m = u - 1
+ *     q = 0.0657233745;  then q = q * m + c for c = -0.116206668, 0.119458839, -0.12420819, 0.142122895, -0.166665554,
+ *         0.20002535, -0.250000626, 0.333333015, -0.5, 1
+ *     s = m * q;  if halved: s = s + 0.693147182
+ *     return hi + s
+ *   Each decimal constant is the fp32 value nearest to it.  No libm transcendental, no division, no reciprocal: add, subtract,
+ *   multiply, compare, rint, ldexp are exact IEEE operations, so the device, the host and a numpy float32 restatement give the same
+ *   bits.  The function is symmetric in its arguments bit for bit.  a == b: d = 0, n = 0, x = 1, u = 2 is halved, m = 0, the result
+ *   is hi + 0.693147182.  -inf and NaN never reach it from the search (they are dropped first).
+ *   Accuracy: s against float64 log1p(exp(d)) over 6 000 001 equally spaced d in [-17.34375, 0], both ends included (at the cutoff
+ *   itself s = 0): the maximum absolute deviation measured is 9.9e-8; the bound the tests assert is 1.2e-7, well below 1e-6 -- half
+ *   an fp32 ulp of a score of magnitude 16 --, so the function's error stays below the rounding of the addition that follows it.
+ *
+ * eec_ctc_lexbeam_logadd_decode: eec_ctc_lexbeam_lm_smear_decode's arguments in the same order.  lm == NULL: no model (lm_weight
+ *   and smear unused; smear != NULL without lm is EEC_ERR_BAD_ARG); lm != NULL, smear == NULL: the model; both: the model and
+ *   smearing.  Everything else is as the three entries: the same checks before any device work, the same workspace, one kernel on
+ *   `stream`, no allocation, no synchronisation, graph-capturable, results bit-identical run to run.
+ * eec_ctc_log_add_host is HOST code and needs no device: log_add(a, b), the very function the kernel calls.
+ * eec_ctc_log_add: out[k] = log_add(a[k], b[k]) for k < n on the device (a, b, out: n fp32 each; out may alias a or b), one kernel on
+ *   `stream` -- for holding the function to its statement, and for combining scores (an N-best list's posterior mass, say).
+ *   EEC_ERR_BAD_ARG: n < 0, or a null pointer with n > 0; n == 0 is a successful no-op. */
+int eec_ctc_lexbeam_logadd_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                                  int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                                  int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps,
+                                  float* scores, int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm,
+                                  float lm_weight, const void* smear);
+float eec_ctc_log_add_host(float a, float b);
+int eec_ctc_log_add(const float* a, const float* b, float* out, int n, void* stream);
 
 /* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
  * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam

@@ -28,6 +28,13 @@ noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/le
   with the same model, against the unsmeared LM search of the same process; the host time of building the table
   (``eec_ctc_trie_smear``) is recorded too.  ``--parent-record`` then takes the records of the parent commit's ``--lm`` run: its
   model-free and its LM time join with their ratios to this run's.
+
+    python tools/lexbeam_time.py --log-add [--lm [--smear]] [--out profiles/lexbeam_logadd_time.json]
+
+* ``--log-add``: the search with log-add merging (``eec_ctc_lexbeam_logadd_decode``) against the Viterbi search of the same mode --
+  without a model, with ``--lm`` the model, with ``--lm --smear`` the model and smearing -- in the same process on the same
+  emissions (384 x 256, beam 10), each measured twice in turn (the spread between the two blocks of one entry is the noise to read
+  the ratio against).  The emissions are synthetic: how often hypotheses meet, and so how often ``log_add`` runs, is theirs.
 """
 import argparse
 import json
@@ -205,6 +212,49 @@ def lm_leg(args, trie, spellings, dev, records):
     print(json.dumps(rec), flush=True)
 
 
+def logadd_leg(args, trie, spellings, dev, records):
+    lib = capi.load()
+    n, T, beam = 384, args.frames, args.beam
+    em = torch.from_numpy(L.emissions(3, spellings, n, T, 256, 0, 126)).to(dev)
+    free, _, nh = prepared_calls(trie, em, beam, 1, dev)
+    words, wc, toks, tc, ts, nh, sc, ws, image = free()[1:10]
+    lm = synthetic_model(len(spellings), args.bigrams, args.trigrams) if args.lm else None
+    lm_ptr = lm.on(dev).data_ptr() if args.lm else None
+    smear_ptr = lm.smear(trie).on(dev).data_ptr() if args.smear else None
+    common = (em.data_ptr(), n, T, 256, None, image.data_ptr(), trie.blank, trie.sil, beam, 1, 0.0, 0.0, 50.0, T, words.data_ptr(), wc.data_ptr(),
+              toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(), nh.data_ptr(), ws.data_ptr(), ws.numel(), capi.stream_ptr(dev))
+    if args.smear:
+        name, tail = "eec_ctc_lexbeam_lm_smear_decode", (lm_ptr, 1.0, smear_ptr)
+    elif args.lm:
+        name, tail = "eec_ctc_lexbeam_lm_decode", (lm_ptr, 1.0)
+    else:
+        name, tail = "eec_ctc_lexbeam_decode", ()
+
+    def viterbi():
+        capi.check(getattr(lib, name)(*common, *tail), name)
+
+    def log_add():
+        capi.check(lib.eec_ctc_lexbeam_logadd_decode(*common, lm_ptr, 1.0, smear_ptr), "eec_ctc_lexbeam_logadd_decode")
+    rec = {"what": "log_add", "mode": "smear" if args.smear else "lm" if args.lm else "lm_free", "viterbi_entry": name, "n_seq": n, "frames": T,
+           "beam": beam, "lm_weight": 1.0 if args.lm else None}
+    best = {}
+    for key, call in (("viterbi", viterbi), ("log_add", log_add), ("viterbi_again", viterbi), ("log_add_again", log_add)):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        rec[key + "_train_of_10_ms_per_call"] = event_ms(call, max(args.reps // 2, 5), per=10)
+        rec["sequences_with_a_hypothesis_" + key] = int((nh > 0).sum())
+        best[key] = (words[:, 0].cpu(), wc[:, 0].cpu())
+    same = (best["viterbi"][1] == best["log_add"][1]) & (best["viterbi"][0] == best["log_add"][0]).all(dim=1)
+    rec["sequences_whose_best_words_differ"] = int((~same).sum())
+    med = lambda *names: statistics.median([rec[k + "_train_of_10_ms_per_call"]["median"] for k in names])  # noqa: E731
+    rec["ratio_log_add_over_viterbi"] = round(med("log_add", "log_add_again") / med("viterbi", "viterbi_again"), 4)
+    rec["spread_viterbi_blocks"] = round(rec["viterbi_again_train_of_10_ms_per_call"]["median"] / rec["viterbi_train_of_10_ms_per_call"]["median"], 4)
+    rec["spread_log_add_blocks"] = round(rec["log_add_again_train_of_10_ms_per_call"]["median"] / rec["log_add_train_of_10_ms_per_call"]["median"], 4)
+    records.append(rec)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -214,6 +264,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the records to this JSON file")
     ap.add_argument("--lm", action="store_true", help="time the search with a synthetic 3-gram model against the search without one")
     ap.add_argument("--smear", action="store_true", help="with --lm: also the search with LM look-ahead (max trie smearing)")
+    ap.add_argument("--log-add", action="store_true", help="time log-add merging against Viterbi merging; combines with --lm and --smear")
     ap.add_argument("--bigrams", type=int, default=2000000)
     ap.add_argument("--trigrams", type=int, default=2000000)
     ap.add_argument("--parent-record", nargs="*", help="records of this tool run from the parent commit on the same box")
@@ -233,8 +284,10 @@ def main():
     print(json.dumps(records[-1]), flush=True)
     # the synthetic trie stands for the real one only while it has its size: nodes within 2 %, the same extreme degrees
     assert abs(trie.n_nodes - 162621) <= 0.02 * 162621 and degree[0] == 109 and degree[1:].max() == 103 and trie.n_shadowed == 0, records[-1]
-    counts = [] if args.lm else [int(q) for q in args.seqs.split(",")]
-    if args.lm:
+    counts = [] if args.lm or args.log_add else [int(q) for q in args.seqs.split(",")]
+    if args.log_add:
+        logadd_leg(args, trie, spellings, dev, records)
+    elif args.lm:
         lm_leg(args, trie, spellings, dev, records)
     pool = torch.from_numpy(L.emissions(3, spellings, max(counts), args.frames, 256, 0, 126)).to(dev) if counts else None
     for n in counts:
