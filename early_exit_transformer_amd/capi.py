@@ -94,6 +94,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_ngram_pack_bytes", "eec_ngram_pack", "eec_ctc_lexbeam_lm_decode",
            "eec_ctc_trie_smear_bytes", "eec_ctc_trie_smear", "eec_ctc_lexbeam_lm_smear_decode",
            "eec_ctc_lexbeam_logadd_decode", "eec_ctc_log_add_host", "eec_ctc_log_add",
+           "eec_ctc_lexbeam_wide_workspace_bytes", "eec_ctc_lexbeam_wide_decode",
            "eec_lexicon_pack_bytes", "eec_lexicon_pack", "eec_lexicon_nearest_workspace_bytes", "eec_lexicon_nearest",
            "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
            "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
@@ -175,6 +176,9 @@ def load() -> C.CDLL:
     lib.eec_ctc_lexbeam_lm_decode.argtypes = lib.eec_ctc_lexbeam_decode.argtypes + [C.c_void_p, C.c_float]
     lib.eec_ctc_lexbeam_lm_smear_decode.argtypes = lib.eec_ctc_lexbeam_lm_decode.argtypes + [C.c_void_p]
     lib.eec_ctc_lexbeam_logadd_decode.argtypes = lib.eec_ctc_lexbeam_lm_smear_decode.argtypes
+    lib.eec_ctc_lexbeam_wide_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.eec_ctc_lexbeam_wide_workspace_bytes.restype = C.c_size_t
+    lib.eec_ctc_lexbeam_wide_decode.argtypes = lib.eec_ctc_lexbeam_lm_smear_decode.argtypes + [C.c_int]
     lib.eec_ctc_log_add_host.argtypes = [C.c_float, C.c_float]
     lib.eec_ctc_log_add_host.restype = C.c_float
     lib.eec_ctc_log_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

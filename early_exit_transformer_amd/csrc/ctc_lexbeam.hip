@@ -8,7 +8,7 @@
 // and the judge of this kernel.  Parity with the third-party decoder is unpinned.
 // log_add=True, the reference's character-lexicon branch (util/beam_infer.py:66-75), is eec_ctc_lexbeam_logadd_decode: the same
 // search with the merged hypotheses' probabilities summed (the LA instantiations, at the end of this comment).
-// Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 16.
+// Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 64 (17 to 64: ctc_lexbeam_wide.hip).
 //
 // One 256-thread workgroup per sequence, one launch for the batch; thread c owns frame label c (V <= 256).  All candidates that
 // can merge share their frame label, so every merge is local to one thread.  Per frame:
@@ -63,177 +63,15 @@
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
+#include "eec_lexbeam.h"
 
 namespace eec {
-
-constexpr int kLbMagic = 0x54434545;  // "EECT"
-constexpr int kLbHeader = 16;
-constexpr int kLbMaxBeam = 16;
-constexpr int kLbThreads = 256;
-constexpr int kLbNoChild = 255;  // a node has at most 255 children (V <= 256, no blank edge): offsets 0 .. 254
-
-struct LbBeam {
-  unsigned long long hash;  // identity of the word history
-  float score;
-  int node, beg, deg;  // trie node, its first edge, its child count
-  int tok;             // label of the last frame; -1 at the start.  "previous frame was blank" is tok == blank || tok < 0
-  int ntok, nw;        // collapsed labels and words so far
-  int pad;             // with a model: the LM state, a node of the n-gram image
-};
-
-// the history hash's step, as cb_mix in ctc_beam.hip
-__device__ __forceinline__ unsigned long long lb_mix(unsigned long long h, int c) {
-  unsigned long long z = h ^ ((unsigned long long)(c + 1) * 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// ... with smearing also the advance payment outstanding at its node, smax[node] (0 at the root)
-struct LbBeamSm : LbBeam {
-  float pmax;
-  int pad2;
-};
-
-template <typename Beam>
-__device__ __forceinline__ Beam lb_entry(const LbBeam& b, float pmax) {
-  if constexpr (std::is_same_v<Beam, LbBeamSm>)
-    return LbBeamSm{b, pmax, 0};
-  else
-    return b;
-}
-
-struct LbArgs {
-  const float* logp;
-  const int* em_len;
-  const int* trie;
-  int Tq, V, blank, sil, beam, nbest, max_words, use_thr;
-  float word_score, sil_score, beam_threshold;
-  int *words, *word_count, *tokens, *token_count, *timesteps, *n_hyp;
-  float* scores;
-  int2* backptr;
-};
-
-struct LbLmArgs : LbArgs {
-  const int* lm;
-  float lm_weight;
-};
-
-struct LbSmArgs : LbLmArgs {
-  const int* smear;
-};
-
-constexpr int kSmMagic = 0x53434545;  // "EECS"
-constexpr int kSmHeader = 4;
-
-constexpr int kLmMagic = 0x4E434545;  // "EECN"
-constexpr int kLmHeader = 16;
-constexpr int kLmMaxOrder = 5;
-
-// the n-gram image's sections (include/eec.h)
-struct LmView {
-  const int *begin, *eword, *suffix, *map;
-  const float *logp, *backoff;
-  int top_begin, bos, eos;
-};
-
-// log10 p(v | state s) by the back-off walk of include/eec.h, fp32 additions in the walk's order; `next`: the state after v.
-// The root finds every word without a search (the unigram of word v is node v + 1), so the walk ends after at most `order` steps;
-// the bound keeps a damaged image from looping.  The smear table's host code runs this very function: one sequence of additions.
-__host__ __device__ __forceinline__ float lm_walk(const LmView& m, int s, int v, int& next) {
-  float acc = 0.f;
-  for (int d = 0; d <= kLmMaxOrder; ++d) {
-    int x = v + 1;
-    if (s != 0) {
-      int lo = m.begin[s];
-      const int end = m.begin[s + 1];
-      int hi = end;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (m.eword[mid] < v)
-          lo = mid + 1;
-        else
-          hi = mid;
-      }
-      x = (lo < end && m.eword[lo] == v) ? lo + 1 : -1;
-    }
-    if (x >= 0) {
-      acc = acc + m.logp[x];
-      next = x < m.top_begin ? x : m.suffix[x];
-      return acc;
-    }
-    acc = acc + m.backoff[s];
-    s = m.suffix[s];
-  }
-  next = 0;
-  return acc;
-}
-
-// LM = false is the model-free search; LM = true adds the model's score at word ends and at the end of the sentence
-// s + lm_weight * acc, the product rounded on its own: the two operations must not contract into a fused multiply-add
-// (__fmul_rn / __fadd_rn are plain operators to this compiler and do contract)
-__device__ __forceinline__ float lm_add(float s, float lm_weight, float acc) {
-#pragma clang fp contract(off)
-  const float term = lm_weight * acc;
-  return s + term;
-}
-
-// log_add(a, b) = log(exp(a) + exp(b)) as the fixed sequence of fp32 operations include/eec.h states (constants, order, cutoff):
-// every step is an IEEE-exact operation and nothing contracts, so device, host and a numpy float32 restatement agree bit for bit
-constexpr float kLaCutoff = -17.34375f;  // exp(d) < 2^-25 at and below it: the sum would round back to hi
-__host__ __device__ __forceinline__ float lb_log_add(float a, float b) {
-#pragma clang fp contract(off)
-  const bool a_hi = a > b;
-  const float hi = a_hi ? a : b, lo = a_hi ? b : a;
-  const float d = lo - hi;
-  if (!(d > kLaCutoff)) return hi;
-  // x = exp(d): d = n ln 2 + r, |r| <= ln 2 / 2; exp(r) by its Taylor polynomial of degree 7
-  const float n = rintf(d * 1.44269502f);
-  float r = d - n * 0.693145751953125f;
-  r = r - n * 1.42860677e-06f;
-  float p = 1.98412701e-04f;
-  p = p * r + 1.38888892e-03f;
-  p = p * r + 8.33333377e-03f;
-  p = p * r + 4.16666679e-02f;
-  p = p * r + 0.166666672f;
-  p = p * r + 0.5f;
-  p = p * r + 1.0f;
-  p = p * r + 1.0f;
-  const float x = ldexpf(p, (int)n);
-  // log(1 + x): u = 1 + x in [1, 2], halved above sqrt 2; log u = m P(m), m = u - 1 (exact), P of degree 10
-  float u = 1.0f + x;
-  const bool halved = u > 1.41421354f;
-  if (halved) u = u * 0.5f;
-  const float m = u - 1.0f;
-  float q = 0.0657233745f;
-  q = q * m + -0.116206668f;
-  q = q * m + 0.119458839f;
-  q = q * m + -0.12420819f;
-  q = q * m + 0.142122895f;
-  q = q * m + -0.166665554f;
-  q = q * m + 0.20002535f;
-  q = q * m + -0.250000626f;
-  q = q * m + 0.333333015f;
-  q = q * m + -0.5f;
-  q = q * m + 1.0f;
-  float s = m * q;
-  if (halved) s = s + 0.693147182f;
-  return hi + s;
-}
 
 // the merge loop's call: one copy of the sequence for its 496 pairs
 __device__ __noinline__ float lb_log_add_call(float a, float b) { return lb_log_add(a, b); }
 
 __global__ void ctc_log_add_kernel(const float* a, const float* b, float* out, int n) {
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) out[k] = lb_log_add(a[k], b[k]);
-}
-
-template <bool LM, bool SM, typename Args>
-__device__ __forceinline__ bool lm_fits(const Args& a) {
-  bool fits = true;
-  if constexpr (LM) fits = a.lm[0] == kLmMagic && a.lm[5] == a.trie[10];
-  if constexpr (SM) fits = fits && a.smear[0] == kSmMagic && a.smear[1] == a.trie[1];
-  return fits;
 }
 
 // SM (with LM only): LM look-ahead by the smear table.  LA: log-add merging instead of Viterbi merging
@@ -473,78 +311,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_kernel(const std::cond
     if (nb == 0) break;  // no candidate survived the frame: the sequence ends without a hypothesis
   }
 
-  // the complete hypotheses (node 0) in rank order are best first; one thread walks each one's back-pointers
-  if (c == 0) {
-    int n = 0;
-    if constexpr (LM) {
-      // ... after the </s> term they no longer are: ordered by (final score descending, rank ascending), one thread's insertion
-      if (L > 0)
-        for (int i = 0; i < nb; ++i) {
-          const LbBeam e = bufs[cur][i];
-          if (e.node != 0) continue;
-          float f = e.score;
-          if (m.eos >= 0) {
-            int next;
-            f = lm_add(f, a.lm_weight, lm_walk(m, e.pad, m.eos, next));
-          }
-          int k = n++;
-          for (; k > 0 && f > fin_score[k - 1]; --k) fin_score[k] = fin_score[k - 1], fin_rank[k] = fin_rank[k - 1];
-          fin_score[k] = f, fin_rank[k] = i;
-        }
-      n = min(n, a.nbest);
-    } else {
-      if (L > 0)
-        for (int i = 0; i < nb; ++i)
-          if (bufs[cur][i].node == 0 && n < a.nbest) fin_rank[n++] = i;
-    }
-    fin_n = n;
-    a.n_hyp[seq] = n;
-  }
-  __syncthreads();
-  if (c < a.nbest) {
-    const size_t o = (size_t)seq * a.nbest + c;
-    int n = 0, nw = 0;
-    float score = -INFINITY;
-    if (c < fin_n) {
-      int k = fin_rank[c];
-      const LbBeam e = bufs[cur][k];
-      n = e.ntok, nw = e.nw, score = LM ? fin_score[c] : e.score;
-      int* tok_out = a.tokens + o * Tq;
-      int* ts_out = a.timesteps ? a.timesteps + o * Tq : nullptr;
-      int* w_out = a.words + o * a.max_words;
-      int nt = n, nwd = nw;
-      int2 at = bp[(size_t)(L - 1) * beam + k];
-      for (int t = L - 1; t >= 0; --t) {
-        const int lab = at.x & 0xffff;
-        const int2 prev = t > 0 ? bp[(size_t)(t - 1) * beam + (at.x >> 16)] : make_int2(0xffff, 0);
-        if (lab != blank && lab != (prev.x & 0xffff) && nt > 0) {  // the first frame of a run of one label
-          tok_out[--nt] = lab;
-          if (ts_out) ts_out[nt] = t;
-        }
-        if (at.y && nwd > 0 && --nwd < a.max_words) w_out[nwd] = at.y - 1;
-        at = prev;
-      }
-    }
-    a.scores[o] = score;
-    a.token_count[o] = n;
-    a.word_count[o] = nw;
-    fin_ntok[c] = n;
-    fin_nw[c] = min(nw, a.max_words);
-  }
-  __syncthreads();
-  // what lies past a hypothesis' counts is -1
-  for (int k = c; k < a.nbest * Tq; k += kLbThreads) {
-    const int j = k / Tq;
-    if (k - j * Tq >= fin_ntok[j]) {
-      const size_t o = ((size_t)seq * a.nbest + j) * Tq + (k - j * Tq);
-      a.tokens[o] = -1;
-      if (a.timesteps) a.timesteps[o] = -1;
-    }
-  }
-  for (int k = c; k < a.nbest * a.max_words; k += kLbThreads) {
-    const int j = k / a.max_words;
-    if (k - j * a.max_words >= fin_nw[j]) a.words[((size_t)seq * a.nbest + j) * a.max_words + (k - j * a.max_words)] = -1;
-  }
+#include "eec_lexbeam_epilogue.inc"
 }
 
 static size_t lb_image_dwords(unsigned long long nodes) {  // nodes >= 1

@@ -64,7 +64,7 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
                        beam_threshold: float = 50.0, em_len: Optional[Tensor] = None, max_words: Optional[int] = None, lm=None,
-                       lm_weight: float = 0.0, smearing: Optional[str] = None, log_add: bool = False):
+                       lm_weight: float = 0.0, smearing: Optional[str] = None, log_add: bool = False, wide: Optional[bool] = None):
     """Lexicon-constrained CTC beam search with N-best of [n, T', V] log-probs on the device (eec_ctc_lexbeam_decode): the
     decoder behind the reference's ``ctc_predict`` / ``ctc_predict_`` (torchaudio ``ctc_decoder(lexicon=...)``,
     util/beam_infer.py:51-65; the algorithm is stated in include/eec.h, parity with the third-party decoder is unpinned).
@@ -78,6 +78,11 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     (eec_ctc_lexbeam_logadd_decode; torchaudio's ``log_add=True``, the reference's ``beam_predict`` setting): the survivor scores the
     log of the sum of their probabilities, by the bit-reproducible ``log_add`` of include/eec.h.  It combines with every ``lm`` /
     ``smearing`` setting.
+    ``beam_size`` 1..64, ``nbest`` 1..``beam_size``.  Beams of 16 or less run the narrow kernels (a thread's candidates in registers),
+    beams of 17 to 64 the wide kernel (eec_ctc_lexbeam_wide_decode, csrc/ctc_lexbeam_wide.hip: the frame's merged candidates in LDS,
+    survivors by radix select), every ``lm`` / ``smearing`` / ``log_add`` setting included; a beam over 64 raises the library's
+    error.  ``wide``: None -- by beam size --, True -- the wide kernel at any beam (at 16 or less it returns what the narrow ones
+    return, bit for bit) --, or False -- the narrow kernels, a ``ValueError`` for a beam over 16.
     ``trie``: a ``lexicon.TokenTrie`` (it carries V, blank and sil); ``em_len`` [n] frames per sequence (None: T'); ``max_words``
     (None: T', always enough): the words kept per hypothesis -- ``word_count`` is the true count even above it.  Returns
     ``(words [n, nbest, max_words] int32 indices into trie.words, word_count [n, nbest], tokens [n, nbest, T'], token_count [n, nbest],
@@ -87,6 +92,10 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
         raise ValueError(f"ctc_lexicon_decode: smearing must be None or 'max', got {smearing!r}")
     if smearing is not None and lm is None:
         raise ValueError("ctc_lexicon_decode: smearing='max' needs lm=: it is the model's scores that are smeared over the trie")
+    if wide is None:
+        wide = int(beam_size) > 16
+    elif not wide and int(beam_size) > 16:
+        raise ValueError(f"ctc_lexicon_decode: wide=False serves beams up to 16, got beam_size={beam_size}")
     if not emission.is_cuda:
         raise RuntimeError("ctc_lexicon_decode runs on a HIP device only")
     logp = emission.contiguous().float()
@@ -105,14 +114,18 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
         em_len = em_len.to(device=dev, dtype=torch.int32).contiguous()
         if em_len.numel() != n:
             raise ValueError(f"ctc_lexicon_decode: em_len must have {n} entries, got {em_len.numel()}")
-    ws_bytes = lib.eec_ctc_lexbeam_workspace_bytes(n, Tq, beam_size)
+    ws_bytes = (lib.eec_ctc_lexbeam_wide_workspace_bytes if wide else lib.eec_ctc_lexbeam_workspace_bytes)(n, Tq, beam_size)
     ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         args = (logp.data_ptr(), n, Tq, V, None if em_len is None else em_len.data_ptr(), trie.on(dev).data_ptr(), trie.blank, trie.sil,
                 int(beam_size), int(nbest), float(word_score), float(sil_score), float(beam_threshold), max_words, words.data_ptr(),
                 word_count.data_ptr(), tokens.data_ptr(), token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
                 ws.data_ptr(), ws_bytes, stream_ptr(dev))
-        if log_add:
+        if wide:
+            capi.check(lib.eec_ctc_lexbeam_wide_decode(*args, None if lm is None else lm.on(dev).data_ptr(), float(lm_weight),
+                                                       None if smearing is None else lm.smear(trie).on(dev).data_ptr(), int(bool(log_add))),
+                       "eec_ctc_lexbeam_wide_decode")
+        elif log_add:
             capi.check(lib.eec_ctc_lexbeam_logadd_decode(*args, None if lm is None else lm.on(dev).data_ptr(), float(lm_weight),
                                                          None if smearing is None else lm.smear(trie).on(dev).data_ptr()),
                        "eec_ctc_lexbeam_logadd_decode")

@@ -259,7 +259,7 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
  * LM look-ahead (max trie smearing) joins through eec_ctc_lexbeam_lm_smear_decode, stated after that one.
  * log_add=True (the reference's character-lexicon branch, util/beam_infer.py:66-75) is eec_ctc_lexbeam_logadd_decode, stated last:
  * only the Merging rule below changes.
- * Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 16.
+ * Out of scope: unknown-word scores other than through the model's <unk>, binary KenLM files, beams over 64 (beams of 17 to 64: eec_ctc_lexbeam_wide_decode, stated after the log-add entry).
  *
  * Lexicon: n_words spellings, each a non-empty sequence of token ids in [0, V), none of them `blank` or (when given) `sil`.  The
  *   trie's root is node 0.  A node "ends word w" when w is the FIRST word in file order with that spelling (later duplicates are
@@ -493,6 +493,39 @@ int eec_ctc_lexbeam_logadd_decode(const float* logp, int n_seq, int Tq, int V, c
                                   float lm_weight, const void* smear);
 float eec_ctc_log_add_host(float a, float b);
 int eec_ctc_log_add(const float* a, const float* b, float* out, int n, void* stream);
+
+/* The same search for WIDE beams, 17 to 64 (any beam of 1 to 64 is served): what a word-level n-gram search over the full lexicon is
+ * normally run with (torchaudio's default for this decoder is 50).  One entry covers every mode, as eec_ctc_lexbeam_logadd_decode
+ * does, and log_add is an argument.  csrc/ctc_lexbeam_wide.hip; tests/lexbeam_wide_cases.py is the plain-Python statement.  PARITY
+ * WITH THE THIRD-PARTY DECODER IS UNPINNED, as above.
+ *
+ * Search: the one stated for eec_ctc_lexbeam_decode and its three successors, word for word -- candidates, the order of the fp32
+ *   operations, dropping, merging, pruning, the LM walk, lm_weight * acc without contraction, smearing, the stated log_add and its
+ *   fold order, the </s> term and the final order -- with one line changed:
+ *     Candidate id = (2 * c + w) * 64 + i: unique within a frame for i < 64.
+ *   That is the same lexicographic order on (label, word-end flag, beam rank) as the narrow id, so for every beam_size of 16 or less
+ *   this entry returns exactly what the narrow entries return, bit for bit.
+ *   beam_size 1..64, nbest 1..beam_size.
+ *
+ * eec_ctc_lexbeam_wide_decode: eec_ctc_lexbeam_decode's arguments in order, then lm, lm_weight, smear, log_add.
+ *   lm == NULL: the model-free search (lm_weight is ignored; smear must be NULL: smear != NULL without lm is EEC_ERR_BAD_ARG);
+ *   lm != NULL, smear == NULL: the model; both: the model and max smearing.  log_add != 0: log-add merging, else Viterbi merging.
+ *   workspace: eec_ctc_lexbeam_wide_workspace_bytes(n_seq, T', beam_size) = n_seq * T' * beam_size * 8 bytes, 8-byte aligned: the
+ *       back-pointers, 8 bytes per (frame, rank); the kernel uses no other global scratch (0 for an argument <= 0; non-decreasing in
+ *       each argument).
+ *   Checks, codes and their order are the narrow entries', all before any device work: EEC_ERR_UNSUPPORTED for beam_size outside
+ *   1..64, nbest outside 1..beam_size, V outside 2..256; EEC_ERR_BAD_ARG for a null required pointer, a misaligned trie / lm / smear /
+ *   workspace, a non-finite lm_weight with a model, smear without lm, n_seq < 0, T' < 1, max_words < 1, blank / sil outside their
+ *   ranges or equal; EEC_ERR_WORKSPACE for a short workspace; n_seq == 0 is a successful no-op.  Foreign images give n_hyp = 0.
+ * One kernel on `stream`; no allocation, no synchronisation; graph-capturable; results are bit-identical run to run (the kernel's
+ * LDS integer atomics decide where a candidate is stored, never what is computed; there are no floating-point atomics).
+ * Out of scope: beams over 64. */
+size_t eec_ctc_lexbeam_wide_workspace_bytes(int n_seq, int Tq, int beam_size);
+int eec_ctc_lexbeam_wide_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
+                                int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
+                                int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
+                                int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm, float lm_weight,
+                                const void* smear, int log_add);
 
 /* CTC forced alignment: replaces BeamInference.get_trellis / backtrack (util/beam_infer.py:129-150, 153-191), the Viterbi
  * alignment of a token sequence against one exit's CTC log-probs -- the CTC half of the reference's joint AED + CTC beam

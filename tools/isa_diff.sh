@@ -5,7 +5,7 @@
 # with the Makefile's flags and defines, and diffs the two after dropping the per-translation-unit
 # __hip_cuid_<hash> lines.  Device assembly must come out identical; host assembly may differ only in the
 # __LINE__ / __FILE__ constants of the error-reporting macros, so its diffs are printed for reading.
-# Exits non-zero if any device assembly differs.  Needs no GPU.
+# A source that only one of the two trees has is named and skipped.  Exits non-zero if any device assembly differs.  Needs no GPU.
 set -eo pipefail
 rev=${1:?usage: isa_diff.sh <rev> [jobs]}; jobs=${2:-8}
 repo=$(cd "$(dirname "$0")/.." && pwd)
@@ -30,6 +30,7 @@ objects() {
 compile() {  # <tree> <side> <obj> <src> <flags...>
   local tree=$1 side=$2 obj=$3 src=$4; shift 4
   cd "$work/$tree/early_exit_transformer_amd/csrc"
+  [ -f "$src" ] || { : > "$work/$tree.$obj.$side.s"; return 0; }  # a source only one side has: reported as such below
   "$HIPCC" -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -Wno-pass-failed "$@" \
     --cuda-$side-only -S "$src" -o - 2>"$work/$tree.$obj.$side.err" | grep -v __hip_cuid_ > "$work/$tree.$obj.$side.s"
 }
@@ -41,6 +42,9 @@ done | xargs -P "$jobs" -L 1 bash -c 'compile "$@" || { echo "compile failed: $*
 
 status=0
 while read -r obj src flags; do
+  if [ ! -s "$work/old.$obj.device.s" ] || [ ! -s "$work/new.$obj.device.s" ]; then
+    printf '%-18s only in one tree: nothing to compare\n' "$obj"; continue
+  fi
   if cmp -s "$work/old.$obj.device.s" "$work/new.$obj.device.s"; then dev=same; else dev=DIFFERENT; status=1; fi
   hostn=$(diff "$work/old.$obj.host.s" "$work/new.$obj.host.s" | grep -c '^[<>]' || true)
   printf '%-18s device %-9s host: %s changed lines\n' "$obj" "$dev" "$hostn"

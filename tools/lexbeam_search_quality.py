@@ -10,7 +10,8 @@ synthetic utterances.  Not a gate: a record of what smearing changes at small be
   (else a Zipf unigram), 2 to 7 words.  Emissions: the sentence's spelled label path (runs of 1 or 2 frames, a blank between
   doubled tokens, blanks and sil between words) plus unit Gaussian noise at every label, log-softmax; the path's peak height is one
   of ``--peaks`` in turn.
-* configurations: beams 2, 5, 10 and 16, each with and without smearing, at every ``--lm-weights``.  Per utterance the best final
+* configurations: beams 2, 5, 10 and 16 (``--beams``: any of 1 .. 64, e.g. ``2,5,10,16,32,50,64``; beams over 16 run the wide-beam
+  kernel, csrc/ctc_lexbeam_wide.hip), each with and without smearing, at every ``--lm-weights``.  Per utterance the best final
   score ANY configuration found is the yardstick (final scores are comparable: for one hypothesis the smeared payments telescope
   to the unsmeared word scores).  Per configuration: the share of utterances whose best hypothesis falls short of the yardstick
   (none counts as short), the share without a hypothesis, and the word errors (edit distance against the sampled sentence, an
@@ -116,7 +117,7 @@ def main():
     ap.add_argument("--bigrams", type=int, default=1000000)
     ap.add_argument("--peaks", default="3,4,5,7")
     ap.add_argument("--lm-weights", default="1.0,3.23")
-    ap.add_argument("--beams", default="2,5,10,16")
+    ap.add_argument("--beams", default="2,5,10,16", help="comma-separated beam sizes, each 1 .. 64")
     ap.add_argument("--out", default=None, help="also write the records to this JSON file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -140,7 +141,10 @@ def main():
     em = torch.from_numpy(L.log_softmax(x)).cuda()
     for weight in (float(w) for w in args.lm_weights.split(",")):
         found = {}
-        for beam in (int(b) for b in args.beams.split(",")):
+        beams = [int(b) for b in args.beams.split(",")]
+        if not all(1 <= b <= 64 for b in beams):
+            ap.error("--beams: every beam must be 1 .. 64")
+        for beam in beams:
             for smearing in (None, "max"):
                 words, wc, _, _, _, scores, nh = ctc_lexicon_decode(em, trie, beam_size=beam, nbest=1, lm=lm, lm_weight=weight, smearing=smearing)
                 words, wc, scores, nh = words[:, 0].cpu().numpy(), wc[:, 0].cpu().numpy(), scores[:, 0].cpu().numpy(), nh.cpu().numpy()

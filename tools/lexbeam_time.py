@@ -35,6 +35,16 @@ noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/le
   without a model, with ``--lm`` the model, with ``--lm --smear`` the model and smearing -- in the same process on the same
   emissions (384 x 256, beam 10), each measured twice in turn (the spread between the two blocks of one entry is the noise to read
   the ratio against).  The emissions are synthetic: how often hypotheses meet, and so how often ``log_add`` runs, is theirs.
+
+    python tools/lexbeam_time.py --wide [--lm --smear] [--log-add] [--parent-record FILE ...] [--out profiles/lexbeam_wide_time.json]
+
+* ``--wide``: the wide-beam kernel (``eec_ctc_lexbeam_wide_decode``, csrc/ctc_lexbeam_wide.hip) against the narrow entries, all in one
+  process on the same 384 x 256 emissions: narrow at beams 10 and 16, wide at 16, 32 and 64, model-free; with ``--lm --smear`` the same
+  five legs under the model with smearing, with ``--log-add`` the same under log-add merging of every mode measured.  Each record
+  carries the ratio wide@16 / narrow@16, the cost per doubling of the beam (wide@32 / wide@16, wide@64 / wide@32), and whether
+  wide@16 returned narrow@16's outputs byte for byte.  ``--parent-record``: records of ``lexbeam_time.py`` (the ``launch`` record of
+  384 sequences) run from the parent commit on the same box; the ratio of this run's narrow@10 to it shows the narrow entries did
+  not move.
 """
 import argparse
 import json
@@ -255,6 +265,59 @@ def logadd_leg(args, trie, spellings, dev, records):
     print(json.dumps(rec), flush=True)
 
 
+def wide_leg(args, trie, spellings, dev, records):
+    lib = capi.load()
+    n, T = 384, args.frames
+    em = torch.from_numpy(L.emissions(3, spellings, n, T, 256, 0, 126)).to(dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    words, wc, toks, tc, ts, nh = i32(n, 1, T), i32(n, 1), i32(n, 1, T), i32(n, 1), i32(n, 1, T), i32(n)
+    sc = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.eec_ctc_lexbeam_wide_workspace_bytes(n, T, 64), dtype=torch.uint8, device=dev)
+    image = trie.on(dev)
+    outputs = (words, wc, toks, tc, ts, sc, nh)
+    modes = [("lm_free", None, None)]
+    if args.lm:
+        lm = synthetic_model(len(spellings), args.bigrams, args.trigrams)
+        modes.append(("smear", lm.on(dev).data_ptr(), lm.smear(trie).on(dev).data_ptr()))
+    parents = []
+    for path in args.parent_record or []:
+        with open(path) as f:
+            parents += [r["lexbeam_train_of_10_ms_per_call"]["median"] for r in json.load(f) if r.get("what") == "launch" and r.get("n_seq") == n]
+    for mode, lm_ptr, smear_ptr in modes:
+        for log_add in ([0, 1] if args.log_add else [0]):
+            def call(kind, beam):
+                common = (em.data_ptr(), n, T, 256, None, image.data_ptr(), trie.blank, trie.sil, beam, 1, 0.0, 0.0, 50.0, T, words.data_ptr(),
+                          wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(), nh.data_ptr(), ws.data_ptr(), ws.numel(),
+                          capi.stream_ptr(dev))
+                if kind == "wide":
+                    capi.check(lib.eec_ctc_lexbeam_wide_decode(*common, lm_ptr, 1.0, smear_ptr, log_add), "eec_ctc_lexbeam_wide_decode")
+                elif log_add:
+                    capi.check(lib.eec_ctc_lexbeam_logadd_decode(*common, lm_ptr, 1.0, smear_ptr), "eec_ctc_lexbeam_logadd_decode")
+                elif lm_ptr is not None:
+                    capi.check(lib.eec_ctc_lexbeam_lm_smear_decode(*common, lm_ptr, 1.0, smear_ptr), "eec_ctc_lexbeam_lm_smear_decode")
+                else:
+                    capi.check(lib.eec_ctc_lexbeam_decode(*common), "eec_ctc_lexbeam_decode")
+            rec = {"what": "wide", "mode": mode, "log_add": bool(log_add), "n_seq": n, "frames": T, "lm_weight": 1.0 if lm_ptr else None}
+            kept = {}
+            for kind, beam in (("narrow", 10), ("narrow", 16), ("wide", 16), ("wide", 32), ("wide", 64)):
+                for _ in range(2):
+                    call(kind, beam)
+                torch.cuda.synchronize()
+                rec[f"{kind}_beam{beam}_train_of_10_ms_per_call"] = event_ms(lambda: call(kind, beam), max(args.reps // 4, 3), per=10)
+                rec[f"sequences_with_a_hypothesis_{kind}_beam{beam}"] = int((nh > 0).sum())
+                kept[kind, beam] = [o.cpu().numpy().tobytes() for o in outputs]
+            med = lambda kind, beam: rec[f"{kind}_beam{beam}_train_of_10_ms_per_call"]["median"]  # noqa: E731
+            rec["wide16_returns_narrow16_bytes"] = kept["wide", 16] == kept["narrow", 16]
+            rec["ratio_wide16_over_narrow16"] = round(med("wide", 16) / med("narrow", 16), 4)
+            rec["ratio_wide32_over_wide16"] = round(med("wide", 32) / med("wide", 16), 4)
+            rec["ratio_wide64_over_wide32"] = round(med("wide", 64) / med("wide", 32), 4)
+            if parents and mode == "lm_free" and not log_add:
+                rec["parent_commit_narrow_beam10_train_of_10_ms_per_call_medians"] = parents
+                rec["ratio_narrow_beam10_over_parent_commit"] = round(med("narrow", 10) / statistics.median(parents), 4)
+            records.append(rec)
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -265,6 +328,7 @@ def main():
     ap.add_argument("--lm", action="store_true", help="time the search with a synthetic 3-gram model against the search without one")
     ap.add_argument("--smear", action="store_true", help="with --lm: also the search with LM look-ahead (max trie smearing)")
     ap.add_argument("--log-add", action="store_true", help="time log-add merging against Viterbi merging; combines with --lm and --smear")
+    ap.add_argument("--wide", action="store_true", help="time the wide-beam kernel at beams 16, 32, 64 against the narrow entries at 10 and 16")
     ap.add_argument("--bigrams", type=int, default=2000000)
     ap.add_argument("--trigrams", type=int, default=2000000)
     ap.add_argument("--parent-record", nargs="*", help="records of this tool run from the parent commit on the same box")
@@ -284,8 +348,10 @@ def main():
     print(json.dumps(records[-1]), flush=True)
     # the synthetic trie stands for the real one only while it has its size: nodes within 2 %, the same extreme degrees
     assert abs(trie.n_nodes - 162621) <= 0.02 * 162621 and degree[0] == 109 and degree[1:].max() == 103 and trie.n_shadowed == 0, records[-1]
-    counts = [] if args.lm or args.log_add else [int(q) for q in args.seqs.split(",")]
-    if args.log_add:
+    counts = [] if args.lm or args.log_add or args.wide else [int(q) for q in args.seqs.split(",")]
+    if args.wide:
+        wide_leg(args, trie, spellings, dev, records)
+    elif args.log_add:
         logadd_leg(args, trie, spellings, dev, records)
     elif args.lm:
         lm_leg(args, trie, spellings, dev, records)
