@@ -793,6 +793,44 @@ int eec_logsoftmax_backward(const float* logp, const float* grad_logp, int M, in
   return 0;
 }
 
+// what the two distillation entries ask of their sizes, the temperature and the teacher map (each checks its own pointers first)
+static int check_distill_args(const int32_t* teacher, int E, int B, int T, int V, float tau) {
+  if (E <= 0 || B <= 0 || T <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "exit distillation: E, B, T and V must be positive");
+  if (E > EEC_DISTILL_MAX_EXITS)
+    return fail(EEC_ERR_BAD_ARG, "exit distillation: at most " + std::to_string(EEC_DISTILL_MAX_EXITS) + " exits, got " + std::to_string(E));
+  if (V > 256 || V % 4) return fail(EEC_ERR_BAD_ARG, "exit distillation: vocab must be a multiple of 4, <= 256");
+  if ((long long)B * T > 0x7fffffffLL) return fail(EEC_ERR_BAD_ARG, "exit distillation: B * T above 2^31 - 1");
+  if (!(tau > 0.f) || !(tau < INFINITY)) return fail(EEC_ERR_BAD_ARG, "exit distillation: the temperature must be a finite number above 0");
+  for (int e = 0; e < E; ++e) {
+    if (teacher[e] < -1 || teacher[e] >= E)
+      return fail(EEC_ERR_BAD_ARG, "exit distillation: teacher[" + std::to_string(e) + "] = " + std::to_string(teacher[e]) + " is outside [-1, E)");
+    if (teacher[e] == e) return fail(EEC_ERR_BAD_ARG, "exit distillation: exit " + std::to_string(e) + " cannot be its own teacher");
+  }
+  return 0;
+}
+
+size_t eec_exit_distill_workspace_bytes(int E, int B, int T) {
+  if (E <= 0 || B <= 0 || T <= 0) return 0;
+  return (size_t)E * B * T * sizeof(float);
+}
+
+int eec_exit_distill_forward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
+                             float* kl, float* loss_per_exit, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !teacher || !kl || !loss_per_exit || !workspace) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_distill_args(teacher, E, B, T, V, tau)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, eec_exit_distill_workspace_bytes(E, B, T))) return rc;
+  EEC_HIP(launch_distill_forward(x, frame_len, teacher, E, B, T, V, tau, kl, loss_per_exit, (float*)workspace, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_exit_distill_backward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
+                              const float* grad_loss, int accumulate, float* dx, void* stream) {
+  if (!x || !teacher || !grad_loss || !dx) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_distill_args(teacher, E, B, T, V, tau)) return rc;
+  EEC_HIP(launch_distill_backward(x, frame_len, teacher, E, B, T, V, tau, grad_loss, accumulate, dx, (hipStream_t)stream));
+  return 0;
+}
+
 int eec_encoder_set_profiling(eec_encoder* enc, int enable, int max_launches) {
   if (!enc) return fail(EEC_ERR_BAD_ARG, "null argument");
   for (hipEvent_t e : enc->ev) (void)hipEventDestroy(e);

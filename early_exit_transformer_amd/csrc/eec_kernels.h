@@ -228,4 +228,12 @@ hipError_t launch_ctc_backward(const float* logp, const long long* targets, cons
                                hipStream_t st);
 hipError_t launch_logsoftmax_backward(const float* logp, const float* g, int M, int V, float* dlogits, hipStream_t st);
 
+// self-distillation between exits (distill.hip; include/eec.h states the loss).  `teacher` is a HOST array the caller has validated.
+constexpr int kDistillMaxExits = EEC_DISTILL_MAX_EXITS;  // a frame's rows of all exits live in one wave's registers
+// ws: E * B * T floats (the per-frame terms); kl [E * B], out [E]
+hipError_t launch_distill_forward(const float* x, const int* frame_len, const int* teacher, int E, int B, int T, int V, float tau,
+                                  float* kl, float* out, float* ws, hipStream_t st);
+hipError_t launch_distill_backward(const float* x, const int* frame_len, const int* teacher, int E, int B, int T, int V, float tau,
+                                   const float* grad_loss, int accumulate, float* dx, hipStream_t st);
+
 }  // namespace eec

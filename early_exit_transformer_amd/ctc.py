@@ -1,9 +1,11 @@
-"""The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), greedy, prefix-beam and
+"""The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), self-distillation between the exits
+(the reference's unimplemented ``--distill``), greedy, prefix-beam and
 lexicon-constrained beam decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
 stream; there is no CPU path."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import ctypes as C
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -243,3 +245,159 @@ def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank:
         capi.check(capi.load().eec_ctc_loss(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
                                             nll.data_ptr(), out.data_ptr(), stream_ptr(dev)), "eec_ctc_loss")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Self-distillation between exits (include/eec.h states the loss; csrc/distill.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _teacher_map(teacher: Union[str, Sequence[int]], E: int) -> Tuple[int, ...]:
+    """``"last"`` (every exit but the last learns from the last), ``"next"`` (exit e learns from e + 1) or E ints (-1: no student)."""
+    if isinstance(teacher, str):
+        if teacher == "last":
+            return tuple([E - 1] * (E - 1) + [-1])
+        if teacher == "next":
+            return tuple(list(range(1, E)) + [-1])
+        raise ValueError(f"teacher must be 'last', 'next' or a sequence of {E} exit indices, got {teacher!r}")
+    if isinstance(teacher, Tensor):
+        teacher = teacher.tolist()
+    t = tuple(int(k) for k in teacher)
+    if len(t) != E:
+        raise ValueError(f"teacher must have one entry per exit ({E}), got {len(t)}")
+    return t
+
+
+def _distill_args(name: str, enc_out: Tensor, frame_len: Optional[Tensor], teacher, temperature: float):
+    """What both distillation wrappers check and normalise: (enc_out fp32 contiguous, frame_len int32 [B] on its device or None,
+    the teacher map, tau)."""
+    if not enc_out.is_cuda:
+        raise RuntimeError(f"{name} runs on a HIP device only")
+    if enc_out.dim() != 4:
+        raise ValueError(f"{name}: enc_out must be [E, B, T', V], got {tuple(enc_out.shape)}")
+    enc_out = enc_out.contiguous().float()
+    E, B, _, V = enc_out.shape
+    if V > 256 or V % 4:
+        raise ValueError(f"{name} needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
+                         "the distillation kernels hold a vocabulary row in one wave")
+    if frame_len is not None:
+        frame_len = frame_len.to(device=enc_out.device, dtype=torch.int32).contiguous()
+        if frame_len.numel() != B:
+            raise ValueError(f"{name}: frame_len must have {B} entries, got {frame_len.numel()}")
+    return enc_out, frame_len, _teacher_map(teacher, E), float(temperature)
+
+
+def _distill_forward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int, ...], tau: float) -> Tensor:
+    E, B, Tq, V = x.shape
+    dev = x.device
+    lib = capi.load()
+    kl = torch.empty((E * B,), dtype=torch.float32, device=dev)
+    out = torch.empty((E,), dtype=torch.float32, device=dev)
+    nbytes = lib.eec_exit_distill_workspace_bytes(E, B, Tq)
+    ws, ws_ptr = capi.aligned_ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_exit_distill_forward(x.data_ptr(), None if frame_len is None else frame_len.data_ptr(), (C.c_int32 * E)(*teacher),
+                                                E, B, Tq, V, tau, kl.data_ptr(), out.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)),
+                   "eec_exit_distill_forward")
+    return out
+
+
+def _distill_backward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int, ...], tau: float, grad_loss: Tensor, accumulate: bool,
+                      dx: Tensor) -> None:
+    E, B, Tq, V = x.shape
+    dev = x.device
+    g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        capi.check(capi.load().eec_exit_distill_backward(x.data_ptr(), None if frame_len is None else frame_len.data_ptr(),
+                                                         (C.c_int32 * E)(*teacher), E, B, Tq, V, tau, g.data_ptr(), int(accumulate),
+                                                         dx.data_ptr(), stream_ptr(dev)), "eec_exit_distill_backward")
+
+
+class _ExitDistillFn(torch.autograd.Function):
+    """Per-exit distillation losses [E] with their gradient with respect to the students' rows (eec_exit_distill_forward /
+    _backward); the teachers' rows receive none."""
+
+    @staticmethod
+    def forward(ctx, enc_out, frame_len, teacher, tau):
+        out = _distill_forward(enc_out, frame_len, teacher, tau)
+        ctx.save_for_backward(enc_out, frame_len)
+        ctx.teacher, ctx.tau = teacher, tau
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        enc_out, frame_len = ctx.saved_tensors
+        dx = torch.empty_like(enc_out)
+        _distill_backward(enc_out, frame_len, ctx.teacher, ctx.tau, grad_out, False, dx)
+        return dx, None, None, None
+
+
+def exit_distill_losses(enc_out: Tensor, frame_len: Optional[Tensor] = None, teacher: Union[str, Sequence[int]] = "last",
+                        temperature: float = 1.0) -> Tensor:
+    """Per-exit self-distillation losses [E] of an encoder output [E, B, T', V] (logits or log-probs: every row is normalised
+    inside): ``loss[e] = tau^2 * mean_b( KL(softmax(x[k] / tau) || softmax(x[e] / tau)) summed over the frames t < frame_len[b],
+    / max(frame_len[b], 1) )`` with ``k = teacher[e]`` -- what the reference's ``--distill`` flag ("whether to use knowledge
+    distillation") names and util/conf.py:48-57 leaves unimplemented.  ``teacher``: ``"last"`` -- every exit but the last learns
+    from the last --, ``"next"`` -- exit e learns from e + 1 --, or E ints (-1: the exit is no student, its loss is 0; a teacher
+    may be shallower than its student).  ``frame_len`` [B] (None: T' for every utterance, the reference's CTC convention;
+    ``encoder_lengths(lengths, T')`` gives the encoder's own).  The teacher is a constant: the gradient with respect to
+    ``enc_out`` (HIP backward) is non-zero on the students' rows only.  One pass over ``enc_out`` per direction."""
+    x, fl, tmap, tau = _distill_args("exit_distill_losses", enc_out, frame_len, teacher, temperature)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _ExitDistillFn.apply(x, fl, tmap, tau)
+    return _distill_forward(x, fl, tmap, tau)
+
+
+class _ExitTrainingFn(torch.autograd.Function):
+    """(CTC losses [E], distillation losses [E]) as ONE node: its backward runs eec_ctc_loss_backward into a fresh gradient buffer
+    and the distillation backward adds into the same buffer, so autograd neither copies nor re-adds the CTC gradient."""
+
+    @staticmethod
+    def forward(ctx, enc_out, tg, tl, blank, frame_len, teacher, tau):
+        E, B, Tq, V = enc_out.shape
+        dev = enc_out.device
+        lib = capi.load()
+        nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
+        ctc = torch.empty((E,), dtype=torch.float32, device=dev)
+        ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
+        with torch.cuda.device(dev):
+            capi.check(lib.eec_ctc_loss_forward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
+                                                nll.data_ptr(), ctc.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+        kd = _distill_forward(enc_out, frame_len, teacher, tau)
+        ctx.set_materialize_grads(False)  # a loss that uses one of the two outputs only: None for the other, and its launch is skipped
+        ctx.save_for_backward(enc_out, tg, tl, nll, ws, frame_len)
+        ctx.blank, ctx.ws_ptr, ctx.teacher, ctx.tau = blank, ws_ptr, teacher, tau
+        return ctc, kd
+
+    @staticmethod
+    def backward(ctx, grad_ctc, grad_kd):
+        enc_out, tg, tl, nll, ws, frame_len = ctx.saved_tensors
+        if getattr(ctx, "used", False):
+            raise RuntimeError("exit_training_losses: backward through the same forward twice (its workspace is consumed)")
+        ctx.used = True
+        E, B, Tq, V = enc_out.shape
+        dev = enc_out.device
+        dlogp = torch.empty_like(enc_out)
+        if grad_ctc is not None:
+            g = grad_ctc.to(device=dev, dtype=torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                capi.check(capi.load().eec_ctc_loss_backward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1),
+                                                             ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(), dlogp.data_ptr(),
+                                                             stream_ptr(dev)), "eec_ctc_loss_backward")
+        if grad_kd is not None:
+            _distill_backward(enc_out, frame_len, ctx.teacher, ctx.tau, grad_kd, grad_ctc is not None, dlogp)
+        elif grad_ctc is None:
+            dlogp.zero_()
+        return dlogp, None, None, None, None, None, None
+
+
+def exit_training_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, frame_len: Optional[Tensor] = None,
+                         teacher: Union[str, Sequence[int]] = "last", temperature: float = 1.0, blank: int = 0) -> Tuple[Tensor, Tensor]:
+    """``(exit_ctc_losses(enc_out, targets, target_len, blank), exit_distill_losses(enc_out, frame_len, teacher, temperature))``,
+    the same values bit for bit, as one autograd node: ``ctc.sum() + w * kd.sum()`` is the training loss with distillation, and its
+    backward writes the CTC gradient into a fresh buffer and adds the distillation gradient into the same buffer (with ``w = 0``
+    that is the gradient of ``exit_ctc_losses`` bit for bit).  ``frame_len`` masks the distillation term only: the CTC loss keeps the
+    reference's input length T' for every utterance."""
+    x, fl, tmap, tau = _distill_args("exit_training_losses", enc_out, frame_len, teacher, temperature)
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return exit_ctc_losses(x, targets, target_len, blank), _distill_forward(x, fl, tmap, tau)
+    dev = x.device
+    return _ExitTrainingFn.apply(x, to_device(targets, dev), to_device(target_len, dev), blank, fl, tmap, tau)

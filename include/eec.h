@@ -229,6 +229,40 @@ int eec_ctc_loss_backward(const float* logp, const int64_t* targets, const int64
                           int blank, const float* nll, void* bwd_workspace, const float* grad_loss, float* dlogp, void* stream);
 int eec_logsoftmax_backward(const float* logp, const float* grad_logp, int M, int V, float* grad_logits, void* stream);
 
+/* Self-distillation between exits: the second training recipe of a multi-exit network (the reference declares the flag
+ * `--distill`, "whether to use knowledge distillation", and leaves it unimplemented: util/conf.py:48-57).  A student exit's frame
+ * posteriors are pulled towards its teacher exit's by a temperature-softened KL term that is added to the per-exit CTC loss; it
+ * is a second producer of the gradient with respect to the encoder output, next to eec_ctc_loss_backward.
+ *   x [E, B, T, V] fp32: logits or log-probs; every row is normalised inside, so the result does not depend on a per-row shift
+ *   frame_len [B] int32 on the device, or NULL for T everywhere (the reference's CTC input-length convention); clamped to [0, T]
+ *   teacher [E] int32, a HOST array: teacher[e] = k makes exit k the teacher of exit e; -1: exit e is no student (loss 0).  A
+ *       teacher may be shallower than its student and may itself be a student of another exit.
+ *   tau > 0, the temperature
+ * With p = softmax(x[k, b, t, :] / tau) and q = softmax(x[e, b, t, :] / tau), k = teacher[e]:
+ *   kl[e, b] = sum_{t < len_b} sum_v p_v (log p_v - log q_v)
+ *   loss[e]  = tau^2 * mean_b( kl[e, b] / max(len_b, 1) )
+ *   d loss[e] / d x[e, b, t, v] = tau * (q_v - p_v) / (B * max(len_b, 1))    for t < len_b, else 0
+ * The teacher is a constant: no gradient flows into x[k] from its students (mutual distillation is not offered).  A term with
+ * p_v = 0 (an exact -inf teacher logit) is 0.  NaN logits propagate to the losses (and gradient rows) of the exits that read them
+ * -- the row's own exit as a student, and its students -- and to nothing else; frames at or past len_b are not read.
+ *   eec_exit_distill_forward: kl [E * B] and loss_per_exit [E]; workspace: eec_exit_distill_workspace_bytes(E, B, T) bytes of
+ *       256-byte aligned device memory (the per-frame terms; 0 for a non-positive size).  Frames, then utterances, are added in
+ *       index order without atomics: the losses are bit-reproducible from run to run.
+ *   eec_exit_distill_backward: dx [E, B, T, V] = d( sum_e grad_loss[e] * loss[e] ) / dx, grad_loss [E] on the device.
+ *       accumulate == 0: every element of dx is written (zeros on rows of exits that are no students or whose grad_loss is 0,
+ *       and on frames at or past len_b).  accumulate != 0: the gradient is ADDED into dx -- eec_ctc_loss_backward's dlogp, so the
+ *       two losses share one gradient buffer -- and those rows and frames are left untouched.
+ * EEC_ERR_BAD_ARG, with a message, before anything is launched: a null pointer (frame_len may be NULL), a size below 1,
+ * E > EEC_DISTILL_MAX_EXITS (a frame's rows of all exits are held in one wave's registers), V > 256 or V % 4 != 0 (a row is one
+ * float4 per lane, as in the CTC gradient kernel), tau not a finite number above 0, teacher[e] == e or outside [-1, E).
+ * EEC_ERR_WORKSPACE: a misaligned or short workspace. */
+#define EEC_DISTILL_MAX_EXITS 16
+size_t eec_exit_distill_workspace_bytes(int E, int B, int T);
+int eec_exit_distill_forward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
+                             float* kl, float* loss_per_exit, void* workspace, size_t workspace_bytes, void* stream);
+int eec_exit_distill_backward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
+                              const float* grad_loss, int accumulate, float* dx, void* stream);
+
 /* CTC prefix beam search: replaces BeamInference.ctc_cuda_predict (util/beam_infer.py:79-80,102-112:
  * torchaudio cuda_ctc_decoder(tokens, nbest=1, beam_size=10, blank_skip_threshold=0.95) on the log-probs of one exit,
  * input length T' for every utterance), batched over n_seq sequences.  That decoder is third-party CUDA code outside the
