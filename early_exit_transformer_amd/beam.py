@@ -23,6 +23,10 @@
   always applies; off by default here); with ``log_add=True`` or ``args.lm_log_add`` with log-add merging.
 * ``BeamInference.beam_predict``  util/beam_infer.py:66-75, 85-90: the character-lexicon decoder (``log_add=True``,
   ``word_score=WORD_SCORE``, torchaudio's default token names) over ``model.ctc_encoder``'s emission, on the same kernel.
+* ``BeamInference.joint_search_batch`` / ``joint_search_exits`` and ``joint_ctc_weight=`` on ``decode_batch`` /
+  ``decode_all_exits``: one-pass joint CTC / attention decoding (Watanabe et al. 2017; not in the reference).  Every candidate of
+  every step is scored by the decoder AND by the CTC prefix probability of the extended labels (``ctc_prefix_session``,
+  csrc/ctc_prefix.hip), EOS by the full-sequence CTC likelihood, so a beam can end; semantics in include/eec.h.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
@@ -35,7 +39,7 @@ import torch
 from torch import Tensor
 
 from .lexicon import NGramLM, TokenTrie, as_lexicon
-from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, encoder_lengths, greedy_ctc
+from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
 
 
 class GreedyCTCDecoder(torch.nn.Module):
@@ -145,6 +149,43 @@ def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, al
     best = (scores.argmax(dim=1) if pick is None else pick(tokens, scores)).tolist()
     tokens_h = tokens.cpu()
     return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
+
+
+def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float):
+    """``max_length`` steps of n one-pass joint CTC / attention beam searches in lockstep (include/eec.h, "CTC prefix scores"):
+    ``step(last [n, R], parent [n, R] | None)`` returns the decoder's log-probs [n, R, V] of every beam, ``prefix.step`` mixes in
+    the CTC prefix scores and closes the beams that took EOS, ``beam_select`` ranks the result as in ``_lockstep_search``.  After
+    ``max_length`` steps every row is final as it stands; a row holds only PAD after its EOS; the best beam is the one with the
+    highest score, ties to the lower index.  Returns ``(final_tokens, final_scores, best_tokens)`` per search."""
+    scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+    bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
+    bufs[0][:, 0, 0] = sos
+    last = bufs[0][:, :1, 0].contiguous()
+    parent: Optional[Tensor] = None
+    for i in range(max_length):
+        local = prefix.step(step(last, parent), last, parent)
+        scores, parent, last = beam_select(local, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
+    tokens = bufs[max_length & 1][:, :beam]
+    ended = torch.cumsum((tokens == eos).to(torch.int32), dim=2) > 0
+    tokens[:, :, 1:] = torch.where(ended[:, :, :-1], torch.full_like(tokens[:, :, 1:], pad), tokens[:, :, 1:])  # rows of score -inf too
+    best = _first_argmax(scores).tolist()
+    tokens_h = tokens.cpu()
+    return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
+
+
+def _before_eos(ids, eos: int):
+    """``ids`` up to, and excluding, the first EOS."""
+    ids = list(ids)
+    return ids[: ids.index(eos)] if eos in ids else ids
+
+
+def _check_joint_weight(joint_ctc_weight, ctc_weight=None) -> float:
+    if ctc_weight is not None:
+        raise ValueError("ctc_weight (the CTC head picks among the final beams) and joint_ctc_weight (one-pass joint decoding) exclude each other")
+    w = float(joint_ctc_weight)
+    if not 0 < w <= 1:
+        raise ValueError(f"joint_ctc_weight must be in (0, 1], got {joint_ctc_weight}")
+    return w
 
 
 class BeamInference:
@@ -396,12 +437,22 @@ class BeamInference:
 
     @torch.no_grad()
     def decode_all_exits(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
-                         ctc_weight: Optional[float] = None, **kw) -> List[List[int]]:
+                         ctc_weight: Optional[float] = None, joint_ctc_weight: Optional[float] = None, **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
         ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits).  ``ctc_weight``: the best beam of every exit is
-        chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass)."""
+        chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass).
+        ``joint_ctc_weight`` (None: unchanged): the search itself is the one-pass joint one (``joint_search_exits``; ``min_length=``
+        defaults to 0 there); not together with ``ctc_weight``."""
         if max_length is None:
             max_length = default_max_length(spec.size(1))
+        if joint_ctc_weight is not None:
+            _check_joint_weight(joint_ctc_weight, ctc_weight)
+            logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=True, want_taps=True, n_groups=model._cfg.n_exits)[:2]
+            exits = list(range(1, model._cfg.n_exits + 1))
+            found = self.joint_search_exits(model, [taps[n - 1] for n in exits], exits, logp,
+                                            encoder_lengths(valid_len.reshape(1).to(logp.device), logp.size(2)), joint_ctc_weight,
+                                            max_length, beam_size=beam_size, **(_lockstep_kw(kw) or {}))
+            return [best for _, _, best in found]
         logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=ctc_weight is not None, want_taps=True,
                                         n_groups=model._cfg.n_exits)[:2]
         exits = list(range(1, model._cfg.n_exits + 1))
@@ -484,10 +535,68 @@ class BeamInference:
         found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
+    def _joint_args(self, emission, emission_len, E: int, B: int, V: int, joint_ctc_weight, EOS_token, PAD_token, blank: int):
+        """The checked arguments of a joint search over E * B lockstep searches (search e * B + b)."""
+        w = _check_joint_weight(joint_ctc_weight)
+        eos, pad = self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")
+        if emission is None or emission.dim() != 4 or emission.size(0) != E or emission.size(1) != B:
+            raise ValueError(f"joint_ctc_weight needs emission [{E}, {B}, T', V]: the CTC log-probs of every exit and utterance")
+        if emission.size(3) != V:
+            raise ValueError(f"joint decoding needs one vocabulary for both heads: the decoder has {V} tokens, the emission {emission.size(3)}")
+        em_len = None if emission_len is None else emission_len.to(emission.device, torch.int32).reshape(B).repeat(E)
+        return w, eos, pad, emission.reshape(E * B, emission.size(2), V).float(), em_len, int(blank)
+
+    @torch.no_grad()
+    def joint_search_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor],
+                           joint_ctc_weight: float, max_length: int, min_length: int = 0, vocab_size: Optional[int] = None,
+                           SOS_token: Optional[int] = None, EOS_token: Optional[int] = None, PAD_token: Optional[int] = None,
+                           beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0):
+        """One-pass joint CTC / attention decoding (Watanabe et al. 2017; include/eec.h states the semantics) of every exit and
+        utterance of a padded batch in lockstep: ``taps`` as for ``beam_search_batch``, ``emission`` [E, B, T', V] the exits' CTC
+        log-probs of the same encoder pass (``emission_len`` [B]: their frames, None = T').  At every step the local score of a
+        candidate is ``(1 - w) * decoder log-prob + w * (CTC prefix log-prob of the extended labels - that of the beam)``; EOS is
+        scored by the full-sequence CTC likelihood (never before ``min_length`` steps), a beam that takes it is done and grows by
+        PAD at no cost, and a candidate the CTC head gives probability zero is dropped.  One decoder step, one
+        ``eec_ctc_prefix_step`` and one ``eec_beam_select`` per step.  Returns ``out[b][e] = (final_tokens, final_scores,
+        best_tokens)``; rows are ``max_length + 1`` long, SOS first.  ValueError where no batch session exists for the model /
+        geometry / device: there is no reference search to fall back to."""
+        V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        session = model.decoder_batch_session(taps, layer_ns, max_length) if max_length >= 1 and hasattr(model, "decoder_batch_session") else None
+        if session is None or beam > session.max_beams:
+            raise ValueError("joint_search_batch: no batched decoder session for this model, geometry, device or beam size")
+        E, B = session.E, session.B
+        n = E * B
+        w, eos, pad, em, em_len, blank = self._joint_args(emission, emission_len, E, B, V, joint_ctc_weight, EOS_token, PAD_token, blank)
+        prefix = ctc_prefix_session(em, em_len, beam, w, eos, pad, blank=blank, min_length=min_length)
+
+        def step(last, parent):
+            return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
+        found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha)
+        return [[found[e * B + b] for e in range(E)] for b in range(B)]
+
+    @torch.no_grad()
+    def joint_search_exits(self, model, encoder_outputs: Sequence[Tensor], layer_ns: Sequence[int], emission: Tensor,
+                           emission_len: Optional[Tensor], joint_ctc_weight: float, max_length: int, min_length: int = 0,
+                           vocab_size: Optional[int] = None, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
+                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0):
+        """``joint_search_batch`` for the exits of ONE utterance (``model.decoder_session_group``): ``encoder_outputs[i]`` [1, T', D]
+        is exit ``layer_ns[i]``'s encoder output, ``emission`` [len(layer_ns), 1, T', V].  Returns the list of ``(final_tokens,
+        final_scores, best_tokens)`` per exit; ValueError where no session group exists."""
+        V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        group = None
+        if max_length >= 1 and hasattr(model, "decoder_session_group") and all(e.size(0) == 1 for e in encoder_outputs):
+            group = model.decoder_session_group(encoder_outputs, layer_ns, max_length)
+        if group is None or beam > group.max_beams:
+            raise ValueError("joint_search_exits: no decoder session group for this model, geometry, device or beam size")
+        n = len(layer_ns)
+        w, eos, pad, em, em_len, blank = self._joint_args(emission, emission_len, n, 1, V, joint_ctc_weight, EOS_token, PAD_token, blank)
+        prefix = ctc_prefix_session(em, em_len, beam, w, eos, pad, blank=blank, min_length=min_length)
+        return _joint_lockstep_search(group.step, prefix, n, encoder_outputs[0].device, max_length, sos, eos, pad, beam, alpha)
+
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
                      max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, lexicon=None, detokenize=None,
-                     **kw) -> List[List[List[int]]]:
+                     joint_ctc_weight: Optional[float] = None, **kw) -> List[List[List[int]]]:
         """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
         utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
@@ -496,7 +605,11 @@ class BeamInference:
         the encoder pass also returns the exits' CTC log-probs and every search's best beam is ``ctc_rescore``'s.
         ``lexicon`` and ``detokenize`` (ids -> str) together: every ``out[b][e]`` is a ``DecodedTokens`` list whose ``.text`` is
         ``apply_lex(detokenize(ids), lexicon)`` (inference.py:50-51), all E x B texts resolved in one lexicon search; with either
-        None nothing changes."""
+        None nothing changes.  ``joint_ctc_weight`` w in (0, 1] (None: unchanged, no new launch): the search is the one-pass
+        joint CTC / attention one (``joint_search_batch``: every candidate of every step is also scored by the CTC prefix
+        probability, EOS ends a beam; ``min_length=`` defaults to 0 there).  Each ``out[b][e]`` is then the best row as it stands
+        -- SOS, the tokens, EOS, PAD up to ``max_length + 1`` -- and the lexicon step sees the tokens before EOS.  Not together
+        with ``ctc_weight``; ValueError where no batch session serves the model (there is no reference search to fall back to)."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
         E = model._cfg.n_exits
@@ -504,10 +617,17 @@ class BeamInference:
         valid_len = valid_len.reshape(-1)
         step = max_batch or spec.size(0)
         out: List[List[List[int]]] = []
+        if joint_ctc_weight is not None:
+            _check_joint_weight(joint_ctc_weight, ctc_weight)
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             together, lockstep = None, _lockstep_kw(kw)
-            if lockstep is not None:
+            if joint_ctc_weight is not None:
+                logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
+                together = self.joint_search_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), joint_ctc_weight,
+                                                   max_length, beam_size=beam_size, **(lockstep or {}))
+                del taps, logp
+            elif lockstep is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=ctc_weight is not None, want_taps=True, n_groups=E)[:2]
                 ctc = {}
                 if ctc_weight is not None:
@@ -520,7 +640,8 @@ class BeamInference:
             else:
                 out += [[best for _, _, best in row] for row in together]
         if lexicon is not None and detokenize is not None:
-            texts = iter(_snapped_texts([ids for row in out for ids in row], lexicon, detokenize))
+            cut = (lambda ids: ids) if joint_ctc_weight is None else (lambda ids: _before_eos(ids, self._arg(kw.get("EOS_token"), "trg_eos_idx")))
+            texts = iter(_snapped_texts([cut(ids) for row in out for ids in row], lexicon, detokenize))
             out = [[DecodedTokens(ids) for ids in row] for row in out]
             for row in out:
                 for ids in row:

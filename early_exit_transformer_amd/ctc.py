@@ -1,7 +1,8 @@
 """The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), self-distillation between the exits
 (the reference's unimplemented ``--distill``), greedy, prefix-beam and
 lexicon-constrained beam decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
-stream; there is no CPU path."""
+stream; there is no CPU path, except for the CTC prefix scorer of one-pass joint decoding (``ctc_prefix_session``), whose host path lets a
+search loop be tested without a device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -185,6 +186,213 @@ def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em
                                      final_score.data_ptr(), status.data_ptr(), ptr(trellis), ws.data_ptr() if ws.numel() else None,
                                      stream_ptr(dev)), "eec_ctc_align")
     return point_token, point_score, path_score, final_score, status, trellis
+
+
+_LA_EXP = (1.98412701e-04, 1.38888892e-03, 8.33333377e-03, 4.16666679e-02, 0.166666672, 0.5, 1.0, 1.0)
+_LA_LOG = (0.0657233745, -0.116206668, 0.119458839, -0.12420819, 0.142122895, -0.166665554, 0.20002535, -0.250000626, 0.333333015, -0.5, 1.0)
+
+
+def log_add32(a: Tensor, b: Tensor) -> Tensor:
+    """``log(exp(a) + exp(b))`` on fp32 tensors as the fixed sequence of fp32 operations include/eec.h states for
+    ``eec_ctc_log_add`` (every torch op is one IEEE operation, nothing contracts): the host restatement of the kernels'
+    log_add; ``log_add(-inf, a) = a``."""
+    a, b = torch.broadcast_tensors(a, b)
+    hi, lo = torch.where(a > b, a, b), torch.where(a > b, b, a)
+    d = lo - hi
+    near = d > -17.34375
+    d = torch.where(near, d, torch.zeros_like(d))
+    n = torch.round(d * 1.44269502)
+    r = d - n * 0.693145751953125
+    r = r - n * 1.42860677e-06
+    p = torch.full_like(d, _LA_EXP[0])
+    for c in _LA_EXP[1:]:
+        p = p * r + c
+    u = 1.0 + torch.ldexp(p, n.to(torch.int32))
+    halved = u > 1.41421354
+    m = torch.where(halved, u * 0.5, u) - 1.0
+    q = torch.full_like(d, _LA_LOG[0])
+    for c in _LA_LOG[1:]:
+        q = q * m + c
+    s = m * q
+    s = torch.where(halved, s + 0.693147182, s)
+    return torch.where(near, hi + s, hi)
+
+
+class CtcPrefixSession:
+    """CTC prefix scores of n lockstep beam searches for one-pass joint CTC / attention decoding (include/eec.h,
+    csrc/ctc_prefix.hip): ``step(att [n, R, V], last [n, R], parent [n, R] | None)`` first advances the state to the R current
+    beams -- beam r extends row ``parent[i, r]`` of the previous step by the token ``last[i, r]`` --, then returns the joint local
+    scores ``local`` [n, R, V] that ``beam_select`` ranks: ``(1 - w) * att + w * ctc``, -inf where the CTC head gives probability
+    zero, ``[pad] = 0`` alone for a beam that has taken EOS.  For a device emission every step is one launch on the current
+    stream (no allocation beyond the result, no synchronisation); for a CPU emission the same arithmetic runs as fp32 tensor ops
+    with a loop over the frames, so a search loop can be tested without a device."""
+
+    MAX_BEAMS, MAX_VOCAB, MAX_FRAMES = 16, 256, 2048
+
+    def __init__(self, emission: Tensor, em_len: Optional[Tensor], R_max: int, weight: float, eos: int, pad: int, blank: int = 0,
+                 min_length: int = 0):
+        if emission.dim() != 3 or emission.dtype != torch.float32:
+            raise ValueError(f"emission must be fp32 [n, T', V], got {emission.dtype} {tuple(emission.shape)}")
+        n, Tq, V = emission.shape
+        if not 0 < float(weight) <= 1:
+            raise ValueError(f"the CTC weight must be in (0, 1], got {weight}")
+        if len({int(blank), int(eos), int(pad)}) != 3:
+            raise ValueError("blank, eos and pad must be pairwise distinct")
+        self.n, self.Tq, self.V, self.R_max = n, Tq, V, int(R_max)
+        self.blank, self.eos, self.pad, self.weight, self.min_length = int(blank), int(eos), int(pad), float(weight), int(min_length)
+        self.dev = emission.device
+        self.emission = emission.contiguous()
+        self.s, self.rows = 0, 0
+        if em_len is not None:
+            em_len = em_len.to(device=self.dev, dtype=torch.int32).contiguous()
+            if em_len.numel() != n:
+                raise ValueError(f"em_len must have {n} entries, got {em_len.numel()}")
+        self.em_len = em_len
+        if not self.emission.is_cuda:
+            self._host_begin()
+            return
+        lib = capi.load()
+        self.nbytes = lib.eec_ctc_prefix_state_bytes(n, self.R_max, Tq)
+        with torch.cuda.device(self.dev):
+            self._state = capi.aligned_ws(self.nbytes, self.dev)
+            capi.check(lib.eec_ctc_prefix_begin(*self._head(), self._state[1], self.nbytes, stream_ptr(self.dev)), "eec_ctc_prefix_begin")
+
+    def _head(self):
+        return (self.emission.data_ptr(), None if self.em_len is None else self.em_len.data_ptr(), self.n, self.Tq, self.V, self.blank, self.R_max)
+
+    def step(self, att: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
+        n, V = self.n, self.V
+        if att.dim() != 3 or att.size(0) != n or att.size(2) != V:
+            raise ValueError(f"att must be [{n}, live beams, {V}], got {tuple(att.shape)}")
+        R = int(att.size(1))
+        if tuple(last.shape) != (n, R) or (parent is not None and tuple(parent.shape) != (n, R)):
+            raise ValueError(f"last and parent must be [{n}, {R}]")
+        if not self.emission.is_cuda:
+            if not 1 <= R <= self.R_max:
+                raise ValueError(f"1 .. {self.R_max} live beams per search and step, got {R}")
+            local = self._host_step(att.float(), last.to(torch.int64), None if parent is None else parent.to(torch.int64), R)
+        else:
+            dev = self.dev
+            att = capi.require_fp32("att", att, dev)
+            if last.device != dev or (parent is not None and parent.device != dev):
+                raise RuntimeError(f"last and parent must be on {dev}")
+            with torch.cuda.device(dev):
+                tok = last.to(torch.int64).contiguous()
+                par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
+                local = torch.empty((n, R, V), dtype=torch.float32, device=dev)
+                capi.check(capi.load().eec_ctc_prefix_step(*self._head(), None if par is None else par.data_ptr(), tok.data_ptr(), R, self.rows, self.s,
+                                                           att.data_ptr(), self.weight, self.eos, self.pad, self.min_length, local.data_ptr(),
+                                                           self._state[1], self.nbytes, stream_ptr(dev)), "eec_ctc_prefix_step")
+                stream = torch.cuda.current_stream(dev)
+                for t in (att, tok, par):
+                    if t is not None:
+                        t.record_stream(stream)
+        self.s += 1
+        self.rows = R
+        return local
+
+    def prefix_scores(self) -> Tensor:
+        """``pfx`` [n, R] of the current beams (after the last ``step``): the CTC log prefix probability of an open beam's
+        labels, the full-sequence CTC log-likelihood of a done one."""
+        if not self.emission.is_cuda:
+            return self._pfx.clone()
+        off = self._state[1] - self._state[0].data_ptr()
+        slots = self._state[0][off: off + self.nbytes].view(torch.float32).view(2, self.n, self.R_max, -1)
+        return slots[self.s & 1, :, : max(self.rows, 1), 0].clone()
+
+    # ---- the host path: the statement of include/eec.h as fp32 tensor ops ----
+    def _host_begin(self):
+        n, Tq = self.n, self.Tq
+        x = self.emission
+        T = torch.full((n,), Tq, dtype=torch.int64) if self.em_len is None else self.em_len.to(torch.int64).clamp(1, Tq)
+        self._T = T
+        self._live = torch.arange(Tq).unsqueeze(0) < T.unsqueeze(1)  # [n, Tq]
+        ninf = torch.full((n, 1, Tq), float("-inf"))
+        rb = ninf.clone()
+        acc = x[:, 0, self.blank].clone()
+        rb[:, 0, 0] = acc
+        for t in range(1, Tq):
+            acc = acc + x[:, t, self.blank]
+            rb[:, 0, t] = acc
+        rb = torch.where(self._live.unsqueeze(1), rb, ninf)
+        self._rn, self._rb, self._u = ninf, rb, rb.clone()
+        self._pfx = torch.zeros((n, 1))
+        self._last = torch.full((n, 1), -1, dtype=torch.int64)
+        self._done = torch.zeros((n, 1), dtype=torch.bool)
+        self._psi = torch.full((n, 1, self.V), float("-inf"))
+
+    def _host_step(self, att: Tensor, c: Tensor, parent: Optional[Tensor], R: int) -> Tensor:
+        n, Tq, V, x = self.n, self.Tq, self.V, self.emission
+        NINF = float("-inf")
+        at_T = (self._T - 1).view(n, 1, 1)
+        if self.s == 0:
+            grow = lambda t: t.expand(n, R, *t.shape[2:]).clone()  # noqa: E731
+            rn, rb, u, pfx, last, done = (grow(t) for t in (self._rn, self._rb, self._u, self._pfx, self._last, self._done))
+        else:
+            p = torch.arange(R).expand(n, R) if parent is None else parent
+            ok = (p >= 0) & (p < self.rows)
+            p = p.clamp(0, self.rows - 1)
+            pT = p.unsqueeze(2).expand(n, R, Tq)
+            p_rn, p_rb, p_u = self._rn.gather(1, pT), self._rb.gather(1, pT), self._u.gather(1, pT)
+            p_pfx, p_last, p_done = self._pfx.gather(1, p), self._last.gather(1, p), self._done.gather(1, p)
+            c_ok = (c >= 0) & (c < V)
+            cc = c.clamp(0, V - 1)
+            psi_c = self._psi.gather(1, p.unsqueeze(2).expand(n, R, V)).gather(2, cc.unsqueeze(2)).squeeze(2)
+            dead = ~ok | (~p_done & ~c_ok)
+            copy = ~dead & p_done
+            finish = ~dead & ~copy & (cc == self.eos)
+            ext = ~dead & ~copy & ~finish
+            e_pfx = torch.where(cc == self.blank, torch.full_like(psi_c, NINF), psi_c)
+            # the extension of every (parent, token), one frame at a time
+            same = (cc == p_last).unsqueeze(2)
+            phi = torch.where(same, p_rb, p_u)  # [n, R, Tq]: phi[t] reads column t - 1
+            xc = x.gather(2, cc.unsqueeze(1).expand(n, Tq, R)).transpose(1, 2)  # [n, R, Tq]
+            xb = x[:, :, self.blank].unsqueeze(1)  # [n, 1, Tq]
+            nn = torch.where(p_last < 0, xc[:, :, 0], torch.full_like(psi_c, NINF))
+            nb = torch.full_like(nn, NINF)
+            e_rn, e_rb = [nn], [nb]
+            for t in range(1, Tq):
+                nn, nb = log_add32(nn, phi[:, :, t - 1]) + xc[:, :, t], log_add32(nn, nb) + xb[:, :, t]
+                e_rn.append(nn)
+                e_rb.append(nb)
+            e_rn, e_rb = torch.stack(e_rn, 2), torch.stack(e_rb, 2)
+            gone = (~self._live.unsqueeze(1)) | (dead | (ext & (e_pfx == NINF))).unsqueeze(2)
+            keep = (copy | finish).unsqueeze(2)
+            ninf = torch.full_like(e_rn, NINF)
+            rn = torch.where(gone, ninf, torch.where(keep, p_rn, e_rn))
+            rb = torch.where(gone, ninf, torch.where(keep, p_rb, e_rb))
+            u = torch.where(gone, ninf, torch.where(keep, p_u, log_add32(e_rn, e_rb)))
+            full_p = p_u.gather(2, at_T.expand(n, R, 1)).squeeze(2)
+            pfx = torch.where(dead, torch.full_like(p_pfx, NINF), torch.where(copy, p_pfx, torch.where(finish, full_p, e_pfx)))
+            last = torch.where(dead, torch.full_like(cc, -1), torch.where(ext, cc, p_last))
+            done = copy | finish
+        # psi of every token of every current beam
+        v = torch.arange(V).view(1, 1, V)
+        same = v == last.unsqueeze(2)
+        psi = torch.where((last < 0).unsqueeze(2), x[:, 0, :].unsqueeze(1).expand(n, R, V), torch.full((n, R, V), NINF))
+        for t in range(1, Tq):
+            phi = torch.where(same, rb[:, :, t - 1].unsqueeze(2), u[:, :, t - 1].unsqueeze(2))
+            psi = torch.where(self._live[:, t].view(n, 1, 1), log_add32(psi, phi + x[:, t, :].unsqueeze(1)), psi)
+        closed = done | (pfx == NINF)
+        psi = torch.where(closed.unsqueeze(2), torch.full_like(psi, NINF), psi)
+        self._rn, self._rb, self._u, self._pfx, self._last, self._done, self._psi = rn, rb, u, pfx, last, done, psi
+        base = torch.where(closed, torch.zeros_like(pfx), pfx).unsqueeze(2)
+        full = u.gather(2, at_T.expand(n, R, 1))
+        ctc = psi - base
+        ctc = torch.where(v == self.eos, torch.full_like(ctc, NINF) if self.s < self.min_length else (full - base).expand(n, R, V), ctc)
+        ctc = torch.where((v == self.blank) | closed.unsqueeze(2), torch.full_like(ctc, NINF), ctc)
+        w = torch.tensor(self.weight, dtype=torch.float32)
+        mixed = (1.0 - w) * att + w * torch.where(ctc == NINF, torch.zeros_like(ctc), ctc)
+        local = torch.where((ctc == NINF) | (mixed != mixed), torch.full_like(ctc, NINF), mixed)
+        pad_only = torch.where(v == self.pad, torch.zeros_like(local), torch.full_like(local, NINF))
+        return torch.where(done.unsqueeze(2), pad_only, local)
+
+
+def ctc_prefix_session(emission: Tensor, em_len: Optional[Tensor], R_max: int, weight: float, eos: int, pad: int, blank: int = 0,
+                       min_length: int = 0) -> CtcPrefixSession:
+    """A ``CtcPrefixSession`` over ``emission`` [n, T', V] (fp32 CTC log-probs; ``em_len`` [n] frames each, None = T') for up to
+    ``R_max`` beams per search: the CTC half of one-pass joint decoding at weight ``weight`` in (0, 1]."""
+    return CtcPrefixSession(emission, em_len, R_max, weight, eos, pad, blank=blank, min_length=min_length)
 
 
 class _ExitCtcLossFn(torch.autograd.Function):

@@ -23,7 +23,11 @@ def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old
     if tokens_old.shape != tokens_new.shape or tokens_old.dim() != 3 or tokens_old.size(0) != n:
         raise ValueError("token buffers: two [n, rows, steps] int64 tensors")
     if not logp.is_cuda:  # the same step as tensor ops, for sessions that live on the host (tests/test_host.py)
-        out_s, idx = torch.topk((scores.unsqueeze(2) + logp / penalty).reshape(n, -1), k, dim=1)
+        cand = (scores.unsqueeze(2) + logp / penalty).reshape(n, -1)
+        if k > R * V:  # fewer candidates than beams: the kernel fills up with candidate 0 at -inf
+            cand = torch.cat([cand, cand.new_full((n, k - R * V), float("-inf"))], dim=1)
+        out_s, idx = torch.topk(cand, k, dim=1)
+        idx = torch.where(idx >= R * V, torch.zeros_like(idx), idx)
         parent, tok = torch.div(idx, V, rounding_mode="floor"), torch.remainder(idx, V)
         tokens_new[:, :k, :length] = torch.gather(tokens_old[:, :, :length], 1, parent.unsqueeze(2).expand(-1, -1, length))
         tokens_new[:, :k, length] = tok

@@ -21,7 +21,7 @@ from . import capi
 from .capi import new_seed, stream_ptr
 from .capi import to_device as _to_device
 from .conformer import Conformer
-from .ctc import (ctc_align, ctc_beam_decode, ctc_lexicon_decode, encoder_lengths, exit_ctc_losses, exit_distill_losses,  # noqa: F401
+from .ctc import (CtcPrefixSession, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, exit_ctc_losses, exit_distill_losses,  # noqa: F401
                   exit_training_losses, greedy_ctc)
 from .lexicon import Lexicon, TokenTrie, apply_lex, load_dict  # noqa: F401
 from .decoding import DecoderStepSession, _BatchSession, _DecoderTrainFn, _ExitSessions, beam_select  # noqa: F401

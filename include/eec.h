@@ -854,6 +854,65 @@ int eec_decoder_batch_step(const eec_decoder_params* const* ps, int E, int B, in
 int eec_beam_select(int n, int R, int V, int K, const float* logp, const float* scores_in, float penalty, float* scores_out, int64_t* parent,
                     int64_t* tok, const int64_t* tokens_old, int64_t* tokens_new, int len, int ld, int rows_ld, void* stream);
 
+/* ---- CTC prefix scores for one-pass joint CTC / attention decoding (csrc/ctc_prefix.hip) --------------------------------------
+ * The model is trained on 0.7 * CE + 0.3 * CTC at every exit; one-pass joint decoding (Watanabe et al. 2017) lets the two heads
+ * meet INSIDE the search: at every step each candidate extension of each live beam is scored by the decoder and by the CTC prefix
+ * probability of the extended label sequence, an EOS candidate by the full-sequence CTC likelihood -- which gives the search a
+ * principled way to stop.  The reference has no such search; the semantics are stated here, restated in float64 in
+ * tests/ctc_prefix_cases.py and pinned by a brute-force enumeration of all V^T paths.
+ *
+ * One search: x[t][v] the emission (CTC log-probs) for t < T (T = em_len clamped to [1, T'], T' without em_len), `blank` the blank id.
+ * A hypothesis is SOS followed by labels g; SOS is not a CTC label.  All arithmetic is fp32 in the written order; log_add is the
+ * sequence stated for eec_ctc_log_add, and log_add(-inf, a) = a.
+ *   State of a hypothesis: rn[t], rb[t] (t < T) and pfx.  rn[t]: log-probability of all paths over frames 0..t that collapse to g and
+ *     end in a non-blank; rb[t]: the same for paths that end in blank; pfx: the log prefix probability of g.  It also carries its
+ *     last label `last` (none for empty g) and a flag `done`.
+ *   Begin (empty g): rn[t] = -inf; rb[t] = x[0][blank] + ... + x[t][blank] (summed in that order); pfx = 0.
+ *   Extending g (state rn, rb) by a label c != blank:
+ *     nn[0] = x[0][c] if g is empty, else -inf;  nb[0] = -inf;  psi = nn[0];
+ *     for t = 1 .. T-1:  phi = rb[t-1] if c == last, else log_add(rn[t-1], rb[t-1]);
+ *                        nn[t] = log_add(nn[t-1], phi) + x[t][c];  nb[t] = log_add(nn[t-1], nb[t-1]) + x[t][blank];
+ *                        psi = log_add(psi, phi + x[t][c]).
+ *     psi is the prefix log-probability of g.c, (nn, nb) its state.  A sequence that contains the blank has probability zero:
+ *     extending by c == blank gives psi = -inf and a state of -inf.  Full-sequence score of g: full = log_add(rn[T-1], rb[T-1]).
+ *   Joint local score of live beam r, token v, weight w in (0, 1]:
+ *     done beam:  local[r][pad] = 0, every other token -inf.
+ *     open beam:  ctc[r][v] = -inf for v == blank;  -inf for every v when pfx_r == -inf;  full_r - pfx_r for v == eos (-inf while
+ *                 s < min_length);  psi(g_r.v) - pfx_r otherwise.
+ *                 local[r][v] = -inf if ctc[r][v] is -inf, else (1 - w) * att[r][v] + w * ctc[r][v]; a result that is a NaN (a
+ *                 non-finite att) becomes -inf.  No NaN ever leaves the kernel.
+ *   Selection is eec_beam_select on `local`, unchanged (the reference's division by the length penalty, its tie rule).
+ *   After the selection, beam b with parent p and token v:  parent done: the parent's state is copied and b stays done;  else
+ *     v == eos: done = 1 and pfx = full_p;  else: pfx = psi(g_p.v), last = v, and the state is the extended one.
+ *   End of the search: after max_length steps every row is final as it stands; after EOS a row holds only PAD.  The best beam is
+ *   the one with the highest score, ties to the lower index.
+ *
+ * eec_ctc_prefix_state_bytes(n, R_max, T'): the session's state, caller-owned device memory, 16-byte aligned: two buffers of
+ *   n * R_max slots of 4 + 256 + 3 * T' floats (rounded up to 4) -- O(n * R * T'); states of candidates are never stored.  0 for an
+ *   argument <= 0.
+ * eec_ctc_prefix_begin(logp [n][T'][V], em_len [n] | NULL, n, T', V, blank, R_max, state, bytes, stream): the empty hypothesis.
+ * eec_ctc_prefix_step(logp, em_len, n, T', V, blank, R_max, parent [n][R] | NULL, last_tokens [n][R], R, R_prev, s, att [n][R][V], w,
+ *                     eos, pad, min_length, local_out [n][R][V], state, bytes, stream):  step s = 0, 1, 2, ... in order, with the
+ *   arguments of eec_decoder_batch_step: last_tokens[i][r] is beam r's newest token (SOS at s = 0, where it is not read), parent[i][r]
+ *   the row of the previous step it extends (NULL: r itself; not read at s = 0), R_prev that step's beam count.  The call first
+ *   advances the state to the R current beams (the "after the selection" rule for the previous step's choice), then writes `local`
+ *   for all V tokens of every beam.  The whole vocabulary is scored; there is no attention pre-pruning.  A parent outside [0, R_prev)
+ *   or a token outside [0, V) is never used as an address: that beam's prefix probability becomes zero (pfx = -inf).
+ *   n = E * B searches (search e * B + b), R <= R_max <= 16, 2 <= V <= 256 (the decoder's vocabulary is the CTC vocabulary),
+ *   T' <= 2048; blank, eos and pad pairwise distinct.
+ * Checks, all before any device call, errors through eec_last_error(): EEC_ERR_BAD_ARG for n < 0, T' < 1, V < 2, R_max < 1, blank /
+ *   eos / pad outside [0, V) or not distinct, R or R_prev outside 1 .. R_max, s < 0, w outside (0, 1], a null required pointer;
+ *   EEC_ERR_UNSUPPORTED for V > 256, R_max > 16, T' > 2048; EEC_ERR_WORKSPACE for a misaligned or short state; n == 0 is a successful
+ *   no-op.  One launch per call on `stream` (one workgroup per (beam, search), one work-item per token; two dependent chains of T
+ *   log_adds); no allocation, no synchronisation; graph-capturable; no atomics, vector stores only; results are bit-identical run to
+ *   run and do not depend on n. */
+size_t eec_ctc_prefix_state_bytes(int n, int R_max, int Tq);
+int eec_ctc_prefix_begin(const float* logp, const int32_t* em_len, int n, int Tq, int V, int blank, int R_max, void* state, size_t state_bytes,
+                         void* stream);
+int eec_ctc_prefix_step(const float* logp, const int32_t* em_len, int n, int Tq, int V, int blank, int R_max, const int64_t* parent,
+                        const int64_t* last_tokens, int R, int R_prev, int s, const float* att, float w, int eos, int pad, int min_length,
+                        float* local_out, void* state, size_t state_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
