@@ -290,9 +290,9 @@ class BeamInference:
         return [texts[0]], torch.softmax(scores[0, : n_hyp[0]].double(), dim=0)[0].float()
 
     def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
-                         detokenize=None) -> List[List["CTCHypothesis"]]:
+                         detokenize=None, lengths: Optional[Tensor] = None) -> List[List["CTCHypothesis"]]:
         """util/beam_infer.py:102-112: the nbest (= 1) beam-search hypotheses of one exit's log-probs ``emission`` [B, T', V],
-        input length T' for every utterance, beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
+        input length T' for every utterance (``lengths`` [B] in encoder frames: the decoder's ``encoder_out_lens``), beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
         hypothesis objects with ``.tokens`` / ``.words`` / ``.score`` like torchaudio's, so the reference's call sites
         (``best[0][0].tokens`` train.py:82, ``best_[0].tokens`` inference.py:70) work unchanged.  ``tokens`` (the token file
         the torchaudio decoder takes) is accepted and unused: ids are returned, blank = 0.  With ``lexicon`` (a
@@ -300,7 +300,7 @@ class BeamInference:
         ``int_to_text``) every hypothesis also carries ``.text``, its ``apply_lex``-ed transcript (inference.py:70-71), and
         ``.words``, that text's words; with either None nothing changes."""
         beam = self._arg(beam_size, "beam_size")
-        tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95)
+        tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths)
         tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
         hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
         if lexicon is not None and detokenize is not None:

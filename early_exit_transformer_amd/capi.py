@@ -90,6 +90,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_ctc_backward_workspace_bytes", "eec_ctc_loss_forward", "eec_ctc_loss_backward", "eec_logsoftmax_backward",
            "eec_exit_distill_workspace_bytes", "eec_exit_distill_forward", "eec_exit_distill_backward",
            "eec_ctc_beam_workspace_bytes", "eec_ctc_beam_decode", "eec_ctc_beam_decode_ex",
+           "eec_ctc_loss_len", "eec_ctc_loss_forward_len", "eec_ctc_loss_backward_len", "eec_greedy_ctc_len", "eec_ctc_beam_decode_len",
            "eec_ctc_align_workspace_bytes", "eec_ctc_align",
            "eec_ctc_trie_pack_bytes", "eec_ctc_trie_pack", "eec_ctc_lexbeam_workspace_bytes", "eec_ctc_lexbeam_decode",
            "eec_ngram_pack_bytes", "eec_ngram_pack", "eec_ctc_lexbeam_lm_decode",
@@ -157,6 +158,11 @@ def load() -> C.CDLL:
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.eec_ctc_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # the _len entries: the lengths pointer follows the arguments it qualifies (NULL = T' everywhere = the entry without lengths)
+    lib.eec_ctc_loss_len.argtypes = lib.eec_ctc_loss.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss.argtypes[3:]
+    lib.eec_ctc_loss_forward_len.argtypes = lib.eec_ctc_loss_forward.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss_forward.argtypes[3:]
+    lib.eec_ctc_loss_backward_len.argtypes = lib.eec_ctc_loss_backward.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss_backward.argtypes[3:]
+    lib.eec_greedy_ctc_len.argtypes = lib.eec_greedy_ctc.argtypes[:1] + [C.c_void_p] + lib.eec_greedy_ctc.argtypes[1:]
     lib.eec_logsoftmax_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.eec_exit_distill_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.eec_exit_distill_workspace_bytes.restype = C.c_size_t
@@ -170,6 +176,7 @@ def load() -> C.CDLL:
                                         C.c_void_p, C.c_void_p, C.c_void_p]
     lib.eec_ctc_beam_decode_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.eec_ctc_beam_decode_len.argtypes = lib.eec_ctc_beam_decode_ex.argtypes[:1] + [C.c_void_p] + lib.eec_ctc_beam_decode_ex.argtypes[1:]
     lib.eec_ctc_align_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.eec_ctc_align_workspace_bytes.restype = C.c_size_t
     lib.eec_ctc_align.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

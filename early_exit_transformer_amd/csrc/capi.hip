@@ -786,6 +786,41 @@ int eec_ctc_loss_backward(const float* logp, const int64_t* targets, const int64
   return 0;
 }
 
+// the three with per-utterance input lengths: NULL lengths are the entries above, launch for launch
+int eec_ctc_loss_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E, int B,
+                     int Tq, int V, int S, int blank, float* nll_scratch, float* loss_per_exit, void* stream) {
+  if (!input_len) return eec_ctc_loss(logp, targets, target_len, E, B, Tq, V, S, blank, nll_scratch, loss_per_exit, stream);
+  if (!logp || !targets || !target_len || !nll_scratch || !loss_per_exit) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, false)) return rc;
+  EEC_HIP(launch_ctc_loss(logp, (const long long*)targets, (const long long*)target_len, input_len, E, B, Tq, V, S, blank,
+                          nll_scratch, loss_per_exit, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_ctc_loss_forward_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E,
+                             int B, int Tq, int V, int S, int blank, float* nll, float* loss_per_exit, void* bwd_workspace,
+                             void* stream) {
+  if (!input_len)
+    return eec_ctc_loss_forward(logp, targets, target_len, E, B, Tq, V, S, blank, nll, loss_per_exit, bwd_workspace, stream);
+  if (!logp || !targets || !target_len || !nll || !loss_per_exit || !bwd_workspace) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, false)) return rc;
+  EEC_HIP(launch_ctc_loss(logp, (const long long*)targets, (const long long*)target_len, input_len, E, B, Tq, V, S, blank, nll,
+                          loss_per_exit, (float*)bwd_workspace, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_ctc_loss_backward_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E,
+                              int B, int Tq, int V, int S, int blank, const float* nll, void* bwd_workspace, const float* grad_loss,
+                              float* dlogp, void* stream) {
+  if (!input_len)
+    return eec_ctc_loss_backward(logp, targets, target_len, E, B, Tq, V, S, blank, nll, bwd_workspace, grad_loss, dlogp, stream);
+  if (!logp || !targets || !target_len || !nll || !bwd_workspace || !grad_loss || !dlogp) return fail(EEC_ERR_BAD_ARG, "null argument");
+  if (int rc = check_ctc_args(E, B, Tq, V, S, blank, true)) return rc;
+  EEC_HIP(launch_ctc_backward(logp, (const long long*)targets, (const long long*)target_len, input_len, E, B, Tq, V, S, blank, nll,
+                              (float*)bwd_workspace, grad_loss, dlogp, (hipStream_t)stream));
+  return 0;
+}
+
 int eec_logsoftmax_backward(const float* logp, const float* grad_logp, int M, int V, float* grad_logits, void* stream) {
   if (!logp || !grad_logp || !grad_logits || M <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
   if (V > 256 || V % 4) return fail(EEC_ERR_UNSUPPORTED, "vocab must be a multiple of 4, <= 256");
@@ -869,6 +904,14 @@ int eec_greedy_ctc(const float* logp, int n_seq, int Tq, int V, int blank, int32
                    void* stream) {
   if (!logp || !tokens || !counts || n_seq <= 0 || Tq <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
   EEC_HIP(launch_greedy_ctc(logp, n_seq, Tq, V, blank, tokens, counts, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_greedy_ctc_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int32_t* tokens,
+                       int32_t* counts, void* stream) {
+  if (!em_len) return eec_greedy_ctc(logp, n_seq, Tq, V, blank, tokens, counts, stream);
+  if (!logp || !tokens || !counts || n_seq <= 0 || Tq <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
+  EEC_HIP(launch_greedy_ctc(logp, em_len, n_seq, Tq, V, blank, tokens, counts, (hipStream_t)stream));
   return 0;
 }
 

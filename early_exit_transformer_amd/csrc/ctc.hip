@@ -31,9 +31,16 @@
 // ctc_loss_kernel, its posteriors by ctc_wide_kernel.  The fast path's own arithmetic is unchanged: the watch is compares only.
 // The bound is sufficient, not sharp: random log-probs with |log-prob| of 10 and more over 256 frames mark most lattices, which
 // is why the loss alone does not take this path at all.
+//
+// INPUT LENGTHS (eec_len.h: this file is compiled a second time, with EEC_CTC_LEN, by ctc_len.hip, for eec_ctc_loss_len and its
+// forward / backward pair).  Every lattice of utterance b then has Tb = clamp(input_len[b], 0, T') frames: the recursions cover
+// t < Tb, their look-ahead is clamped to Tb - 1, so no frame at or past Tb is ever read, and ctc_grad_kernel writes zeros to the
+// rows t >= Tb.  Tb = 0: nll is 0 for an empty target and +inf for any other (zeroed by the reduction).  Strides and the `astore`
+// layout stay on T', and so does ctc_watch_slack(T'): N of RANGE only shrinks with Tb.
 #include <limits.h>
 
 #include "eec_kernels.h"
+#include "eec_len.h"
 
 namespace eec {
 
@@ -62,10 +69,12 @@ __device__ __forceinline__ size_t ctc_store_index(int lat, int Tq, int P, int t,
 
 template <int P>
 __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
-                                                       const long long* __restrict__ target_len, int B, int Tq, int V,
+                                                       const long long* __restrict__ target_len,
+                                                       EEC_LEN_PARAM(const int* __restrict__ input_len) int B, int Tq, int V,
                                                        int S, int blank, float* __restrict__ nll, float* __restrict__ astore) {
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
   const float* lp = logp + (size_t)lat * Tq * V;
+  const int Tb = EEC_LEN_FRAMES(input_len, b, Tq);
   // inputs nn.CTCLoss validates on the host: a length outside [0, S] or a label outside [0, V) would index out of
   // bounds.  Such a lattice is not run on the caller's data: its nll becomes NaN (ctc_reduce_kernel propagates it).
   const long long len_raw = target_len[b];
@@ -89,6 +98,15 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
     }
   }
   bad = __any((int)bad) != 0;  // wave-uniform
+  if (kLen && Tb == 0) {  // no frame (wave-uniform): only the empty target is feasible; frame 0 is padding and is not read
+    if (lane == 0) {
+      float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
+      nll[lat] = bad ? __builtin_nanf("") : len == 0 ? 0.f : INFINITY;
+      pinfo[0] = bad ? __builtin_nanf("") : len == 0 ? 1.f : 0.f;
+      pinfo[1] = __builtin_bit_cast(float, 0);
+    }
+    return;
+  }
   float livef[P];
 #pragma unroll
   for (int i = 0; i < P; ++i) {
@@ -122,7 +140,7 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
 #pragma unroll
   for (int d = 0; d < kCtcAhead; ++d)
 #pragma unroll
-    for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)min(1 + d, Tq - 1) * V + label[i]];
+    for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)min(1 + d, Tb - 1) * V + label[i]];
   // one time step, branch-free (selects only) so that the unrolled group below is a single basic
   // block and the emission loads keep their kCtcAhead-step lead (s_waitcnt vmcnt(N), not vmcnt(0))
   auto step = [&](const float (&em)[P], bool renorm) {
@@ -165,19 +183,19 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
     }
   };
   int t0 = 1;
-  for (; t0 + kCtcAhead <= Tq; t0 += kCtcAhead) {  // full groups
+  for (; t0 + kCtcAhead <= Tb; t0 += kCtcAhead) {  // full groups
 #pragma unroll
     for (int d = 0; d < kCtcAhead; ++d) {
       step(emit[d], (d & 1) != 0);
       store(t0 + d);
-      const int tn = min(t0 + d + kCtcAhead, Tq - 1);  // clamped: a harmless re-read near the end
+      const int tn = min(t0 + d + kCtcAhead, Tb - 1);  // clamped: a harmless re-read near the end
 #pragma unroll
       for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)tn * V + label[i]];  // raw: exp at use
     }
   }
 #pragma unroll
   for (int d = 0; d < kCtcAhead; ++d)  // ragged tail (wave-uniform guard); its emissions are already in the ring
-    if (t0 + d < Tq) {
+    if (t0 + d < Tb) {
       step(emit[d], (d & 1) != 0);
       store(t0 + d);
     }
@@ -220,12 +238,15 @@ __global__ __launch_bounds__(64) void ctc_alpha_kernel(const float* __restrict__
 // posteriors gamma_t(s); ctc_grad_kernel then turns them into the dense gradient, one wave per (lattice, frame).
 template <int P>
 __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
-                                                      const long long* __restrict__ target_len, int B, int Tq, int V,
+                                                      const long long* __restrict__ target_len,
+                                                      EEC_LEN_PARAM(const int* __restrict__ input_len) int B, int Tq, int V,
                                                       int S, int blank, const float* __restrict__ nll, float* __restrict__ astore) {
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
   const float* lp = logp + (size_t)lat * Tq * V;
   float* pinfo = astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat;
   if (pinfo[0] < 0.f) return;  // the forward pass left this lattice to the wide format (wave-uniform)
+  const int Tb = EEC_LEN_FRAMES(input_len, b, Tq);
+  if (kLen && Tb == 0) return;  // no frame, no posteriors (wave-uniform)
   const long long len_raw = target_len[b];
   const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
   const int L = 2 * len + 1;
@@ -285,7 +306,7 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
     for (int k = 0; k <= P; ++k) al[slot][k] = astore[ctc_store_index(lat, Tq, P, tc, k, lane)];
   };
 #pragma unroll
-  for (int d = 0; d < kAhead; ++d) fetch(d, Tq - 1 - d);
+  for (int d = 0; d < kAhead; ++d) fetch(d, Tb - 1 - d);
   auto step = [&](int slot, int t, bool renorm) {
     // posteriors of time t, in place of the stored alphas
     const int ea = __builtin_bit_cast(int, al[slot][P]);
@@ -338,7 +359,7 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
       eb = any ? eb + e : kCtcEmpty;
     }
   };
-  int t = Tq - 1;
+  int t = Tb - 1;
   for (; t - kAhead + 1 >= 0; t -= kAhead) {
 #pragma unroll
     for (int d = 0; d < kAhead; ++d) {
@@ -354,9 +375,11 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const float* __restrict__ 
 
 // dlogp[lat][t][c] = gs * (exp(logp) - sum of the posteriors of the states labelled c), gs = grad_loss[e] / (B max(len, 1))
 // (0 for an infeasible lattice: zero_infinity; NaN for a lattice whose loss is NaN).  One wave per (lattice, frame).
+// With input lengths a row t >= Tb is written as zeros, without a read of its log-probs or of its slots of `astore` (never stored).
 template <int P>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
-                                                       const long long* __restrict__ target_len, int B, int Tq, int V, int S,
+                                                       const long long* __restrict__ target_len,
+                                                       EEC_LEN_PARAM(const int* __restrict__ input_len) int B, int Tq, int V, int S,
                                                        int blank, const float* __restrict__ nll, const float* __restrict__ astore,
                                                        const float* __restrict__ grad_loss, int n_rows, float* __restrict__ dlogp) {
   __shared__ float bins_all[4][256];
@@ -370,7 +393,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   const long long len_raw = target_len[b];
   const int len = (len_raw < 0 || len_raw > (long long)S) ? 0 : (int)len_raw;
   const int L = 2 * len + 1;
-  if (row_ok) {
+  const bool pad = kLen && t >= EEC_LEN_FRAMES(input_len, b, Tq);  // wave-uniform
+  if (row_ok && !pad) {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       const int s = lane * P + i;
@@ -386,6 +410,10 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   }
   __syncthreads();
   if (!row_ok) return;
+  if (pad) {
+    if (lane * 4 < V) *(float4*)(dlogp + ((size_t)lat * Tq + t) * V + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   const float nl = nll[lat];
   float gs = grad_loss[e] / ((float)B * (float)(len > 0 ? len : 1));
   if (nl != nl) gs = nl;            // NaN loss: NaN gradient
@@ -433,10 +461,12 @@ __device__ __forceinline__ float ctc_wide_add3(float m0, int e0, float m1, int e
 
 template <int P>
 __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
-                                                      const long long* __restrict__ target_len, int B, int Tq, int V, int S,
+                                                      const long long* __restrict__ target_len,
+                                                      EEC_LEN_PARAM(const int* __restrict__ input_len) int B, int Tq, int V, int S,
                                                       int blank, float* __restrict__ nll, float* __restrict__ astore) {
   const int lat = blockIdx.x, b = lat % B, lane = threadIdx.x;
   if (!(astore[ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)lat] < 0.f)) return;
+  const int Tb = EEC_LEN_FRAMES(input_len, b, Tq);  // a marked lattice has a frame: Tb >= 1
   const float* lp = logp + (size_t)lat * Tq * V;
   int* estore = (int*)(astore + ctc_store_index(gridDim.x, Tq, P, 0, 0, 0) + 2 * (size_t)gridDim.x);  // [lat][t][P][64]
   const long long len_raw = target_len[b];  // a marked lattice passed ctc_alpha_kernel's input checks
@@ -481,12 +511,12 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
 #pragma unroll
   for (int d = 0; d < kAhead; ++d)
 #pragma unroll
-    for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)min(1 + d, Tq - 1) * V + label[i]];
-  for (int t0 = 1; t0 < Tq; t0 += kAhead)
+    for (int i = 0; i < P; ++i) emit[d][i] = lp[(size_t)min(1 + d, Tb - 1) * V + label[i]];
+  for (int t0 = 1; t0 < Tb; t0 += kAhead)
 #pragma unroll
   for (int d = 0; d < kAhead; ++d) {
     const int t = t0 + d;
-    if (t >= Tq) break;  // wave-uniform
+    if (t >= Tb) break;  // wave-uniform
     // the previous lane's last two states (wave_shr:1; lane 0 receives an empty state)
     const float u1m = EEC_DPP_F(0.f, am[P - 1], 0x138), u2m = EEC_DPP_F(0.f, am[P - 2], 0x138);
     const int u1e = EEC_DPP_I(kCtcWideEmpty, ae[P - 1], 0x138), u2e = EEC_DPP_I(kCtcWideEmpty, ae[P - 2], 0x138);
@@ -508,7 +538,7 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       am[i] = nm[i], ae[i] = ne[i];
-      emit[d][i] = lp[(size_t)min(t + kAhead, Tq - 1) * V + label[i]];  // clamped: a harmless re-read near the end
+      emit[d][i] = lp[(size_t)min(t + kAhead, Tb - 1) * V + label[i]];  // clamped: a harmless re-read near the end
     }
     store(t);
   }
@@ -548,7 +578,7 @@ __global__ __launch_bounds__(64) void ctc_wide_kernel(const float* __restrict__ 
     bm[i] = last ? 1.f : 0.f;
     be[i] = last ? 0 : kCtcWideEmpty;
   }
-  for (int t = Tq - 1; t >= 0; --t) {
+  for (int t = Tb - 1; t >= 0; --t) {
     float wm[P];
     int we[P];
 #pragma unroll
@@ -679,10 +709,11 @@ __device__ __forceinline__ void ctc_loss_walk(const float* __restrict__ lp, int 
 }
 
 // only_marked: the training forward's follow-up launch -- lattices ctc_alpha_kernel marked (nll == -inf) are run, the others keep
-// their nll
+// their nll.  With input lengths T' in the account above is Tb: the waves meet at m = (Tb - 1) / 2 and wave 1 starts at Tb - 1.
 template <int P>
 __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__ logp, const long long* __restrict__ targets,
-                                                       const long long* __restrict__ target_len, int B, int Tq, int V, int S,
+                                                       const long long* __restrict__ target_len,
+                                                       EEC_LEN_PARAM(const int* __restrict__ input_len) int B, int Tq, int V, int S,
                                                        int blank, int only_marked, float* __restrict__ nll) {
   __shared__ float beta_m[P][64];
   __shared__ int beta_e[P][64];
@@ -718,6 +749,11 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
     if (threadIdx.x == 0) nll[lat] = __builtin_nanf("");
     return;
   }
+  const int Tb = EEC_LEN_FRAMES(input_len, b, Tq);
+  if (kLen && Tb == 0) {  // no frame (the same in both waves): only the empty target is feasible
+    if (threadIdx.x == 0) nll[lat] = len == 0 ? 0.f : INFINITY;
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     // keep every label in a VGPR: a label the compiler can prove wave-uniform (the blanks) would turn its gather into
@@ -727,7 +763,7 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
   }
   static_assert(P % 2 == 0, "a lane's first state must be a blank");
   auto at = [&](int t, int i) { return *(const float*)((const char*)(lp + (size_t)t * V) + (unsigned)label[i]); };
-  const int m = (Tq - 1) / 2;
+  const int m = (Tb - 1) / 2;
   float xm[P];
   int xe[P];
   if (!down) {
@@ -741,7 +777,7 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
     }
     ctc_loss_walk<P, false>(lp, V, label, skip_ok, live, 1, m, xm, xe);
   } else {
-    if (Tq - 1 > m) {
+    if (Tb - 1 > m) {
       // the transition s -> s + 2 is allowed when state s + 2 may be entered by a skip
       bool skip_dn[P];
       const int n0 = EEC_DPP_I(0, (int)skip_ok[0], 0x130), n1 = EEC_DPP_I(0, (int)skip_ok[1], 0x130);
@@ -751,10 +787,10 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
       for (int i = 0; i < P; ++i) {
         float pm;
         int k;
-        ctc_loss_exp(at(Tq - 1, i), pm, k);
+        ctc_loss_exp(at(Tb - 1, i), pm, k);
         ctc_loss_norm(last[i] ? pm : 0.f, k, xm[i], xe[i]);
       }
-      ctc_loss_walk<P, true>(lp, V, label, skip_dn, live, Tq - 2, Tq - 2 - m, xm, xe);
+      ctc_loss_walk<P, true>(lp, V, label, skip_dn, live, Tb - 2, Tb - 2 - m, xm, xe);
       float sum[P];
       int ec[P];
       ctc_loss_sums<P, true>(xm, xe, skip_dn, sum, ec);
@@ -795,6 +831,7 @@ __global__ __launch_bounds__(128) void ctc_loss_kernel(const float* __restrict__
   if (lane == 0) nll[lat] = total != 0.f ? -(logf(mt) + (float)et * 0.6931471805599453f) : INFINITY;
 }
 
+#ifndef EEC_CTC_LEN  // one copy of what takes no lengths: ctc_len.hip calls these
 int ctc_states_per_lane(int S) {
   if (2 * S + 1 <= 64 * 2) return 2;
   if (2 * S + 1 <= 64 * 4) return 4;
@@ -807,19 +844,20 @@ size_t ctc_store_floats(int E, int B, int Tq, int S) {
   // the fast path's states and lane exponents, p(target) per lattice, the wide path's state exponents
   return P ? (size_t)E * B * Tq * (P + 1) * 64 + 2 * (size_t)E * B + (size_t)E * B * Tq * P * 64 : 0;
 }
+#endif
 
-hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, int E, int B, int Tq,
-                               int V, int S, int blank, const float* nll, float* astore, const float* grad_loss, float* dlogp,
+hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len,
+                               EEC_LEN_PARAM(const int* input_len) int E, int B, int Tq, int V, int S, int blank, const float* nll, float* astore, const float* grad_loss, float* dlogp,
                                hipStream_t st) {
   const int P = ctc_states_per_lane(S), n_rows = E * B * Tq;
   if (!P || V > 256 || V % 4) return hipErrorInvalidValue;
 #define EEC_CTC_BWD(P_)                                                                                                      \
-  hipLaunchKernelGGL(ctc_beta_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank, nll,  \
-                     astore);                                                                                               \
-  hipLaunchKernelGGL(ctc_wide_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank,       \
-                     (float*)nullptr, astore);                                                                               \
-  hipLaunchKernelGGL(ctc_grad_kernel<P_>, dim3((n_rows + 3) / 4), dim3(256), 0, st, logp, targets, target_len, B, Tq, V, S,  \
-                     blank, nll, astore, grad_loss, n_rows, dlogp);
+  hipLaunchKernelGGL(ctc_beta_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len,                           \
+                     EEC_LEN_PARAM(input_len) B, Tq, V, S, blank, nll, astore);                                              \
+  hipLaunchKernelGGL(ctc_wide_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len,                           \
+                     EEC_LEN_PARAM(input_len) B, Tq, V, S, blank, (float*)nullptr, astore);                                  \
+  hipLaunchKernelGGL(ctc_grad_kernel<P_>, dim3((n_rows + 3) / 4), dim3(256), 0, st, logp, targets, target_len,               \
+                     EEC_LEN_PARAM(input_len) B, Tq, V, S, blank, nll, astore, grad_loss, n_rows, dlogp);
   if (P == 2) {
     EEC_CTC_BWD(2)
   } else if (P == 4) {
@@ -831,6 +869,7 @@ hipError_t launch_ctc_backward(const float* logp, const long long* targets, cons
   return hipGetLastError();
 }
 
+#ifndef EEC_CTC_LEN
 // loss_e = mean_b( zero_inf(nll[e][b]) / max(len_b, 1) ): fixed summation order (bitwise reproducible).  The 64 lanes fetch 64
 // utterances' terms at once; lane order is then added up sequentially out of registers (one thread walking the batch with two
 // dependent loads per utterance took 10.7 us per launch: 0.4 % of the headline step).
@@ -852,8 +891,14 @@ __global__ void ctc_reduce_kernel(const float* nll, const long long* target_len,
   if (lane == 0) out[e] = s / (float)B;
 }
 
-hipError_t launch_ctc_loss(const float* logp, const long long* targets, const long long* target_len, int E, int B, int Tq,
-                           int V, int S, int blank, float* nll, float* out, float* astore, hipStream_t st) {
+hipError_t launch_ctc_reduce(const float* nll, const long long* target_len, int E, int B, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(ctc_reduce_kernel, dim3(E), dim3(64), 0, st, nll, target_len, B, out);
+  return hipGetLastError();
+}
+#endif
+
+hipError_t launch_ctc_loss(const float* logp, const long long* targets, const long long* target_len,
+                           EEC_LEN_PARAM(const int* input_len) int E, int B, int Tq, int V, int S, int blank, float* nll, float* out, float* astore, hipStream_t st) {
   // state count 2*S+1 must fit 64 lanes x P
   const int P = ctc_states_per_lane(S);
   if (!P) return hipErrorInvalidValue;
@@ -861,10 +906,10 @@ hipError_t launch_ctc_loss(const float* logp, const long long* targets, const lo
   // lattices it marked to the loss kernel; the loss alone is the loss kernel on every lattice
 #define EEC_CTC_FWD(P_)                                                                                                      \
   if (astore)                                                                                                                \
-    hipLaunchKernelGGL(ctc_alpha_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len, B, Tq, V, S, blank,    \
-                       nll, astore);                                                                                         \
-  hipLaunchKernelGGL(ctc_loss_kernel<P_>, dim3(E * B), dim3(128), 0, st, logp, targets, target_len, B, Tq, V, S, blank,      \
-                     astore ? 1 : 0, nll);
+    hipLaunchKernelGGL(ctc_alpha_kernel<P_>, dim3(E * B), dim3(64), 0, st, logp, targets, target_len,                        \
+                       EEC_LEN_PARAM(input_len) B, Tq, V, S, blank, nll, astore);                                            \
+  hipLaunchKernelGGL(ctc_loss_kernel<P_>, dim3(E * B), dim3(128), 0, st, logp, targets, target_len,                          \
+                     EEC_LEN_PARAM(input_len) B, Tq, V, S, blank, astore ? 1 : 0, nll);
   if (P == 2) {
     EEC_CTC_FWD(2)
   } else if (P == 4) {
@@ -875,10 +920,10 @@ hipError_t launch_ctc_loss(const float* logp, const long long* targets, const lo
 #undef EEC_CTC_FWD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ctc_reduce_kernel, dim3(E), dim3(64), 0, st, nll, target_len, B, out);
-  return hipGetLastError();
+  return launch_ctc_reduce(nll, target_len, E, B, out, st);
 }
 
+#ifndef EEC_CTC_LEN
 // dlogits = g - exp(logp) * sum_c g  (backward of log_softmax over the last axis); one wave per row, V <= 256, V % 4 == 0
 __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __restrict__ logp, const float* __restrict__ g, int M, int V,
                                                              float* __restrict__ dlogits) {
@@ -901,5 +946,6 @@ hipError_t launch_logsoftmax_backward(const float* logp, const float* g, int M, 
   hipLaunchKernelGGL(logsoftmax_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, logp, g, M, V, dlogits);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace eec

@@ -12,11 +12,15 @@
 // ties go to the lower candidate id.  Prefixes are not copied: every frame records (parent beam, appended label) per
 // survivor in a back-pointer table and the best prefix is read off backwards at the end.  Latency-bound integer / scalar
 // work (T' serial frames): it is sized to keep all E*B sequences of a batch in flight at once, not for the roofline.
+// With input lengths (eec_len.h: ctc_len.hip compiles the kernel and its launcher a second time, for eec_ctc_beam_decode_len)
+// sequence s is its first Ts = clamp(em_len[s], 0, T') frames and the back-trace starts at Ts - 1; Ts = 0 leaves the empty
+// prefix: count 0, score 0.  The rows of `tokens` and of the back-pointer table stay T' apart.
 #include <limits.h>
 
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
+#include "eec_len.h"
 
 namespace eec {
 
@@ -41,7 +45,8 @@ __device__ __forceinline__ unsigned long long cb_mix(unsigned long long h, int c
   return z ^ (z >> 31);
 }
 
-__global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __restrict__ logp, int Tq, int V, int blank, int beam,
+__global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __restrict__ logp, EEC_LEN_PARAM(const int* __restrict__ em_len)
+                                                              int Tq, int V, int blank, int beam,
                                                               float log_thr, int skip_drops, int* __restrict__ backptr, int* __restrict__ tokens,
                                                               int* __restrict__ counts, float* __restrict__ scores) {
   __shared__ CbBeam bufs[2][kCbMaxBeam];
@@ -53,13 +58,14 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
   const int seq = blockIdx.x, c = threadIdx.x, lane = c & 63, w = c >> 6;
   const float* lp_seq = logp + (size_t)seq * Tq * V;
   int* bp = backptr + (size_t)seq * Tq * kCbMaxBeam;
+  const int Ts = EEC_LEN_FRAMES(em_len, seq, Tq);
   int cur = 0;
   if (c == 0) {
     bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull};
     nb_s = 1;
   }
   __syncthreads();
-  for (int t = 0; t < Tq; ++t) {
+  for (int t = 0; t < Ts; ++t) {
     const CbBeam* B = bufs[cur];
     CbBeam* N = bufs[cur ^ 1];
     const int nb = nb_s;
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     int* out = tokens + (size_t)seq * Tq;
     counts[seq] = n;
     scores[seq] = bs;
-    for (int t = Tq - 1; t >= 0 && n > 0; --t) {
+    for (int t = Ts - 1; t >= 0 && n > 0; --t) {
       const int e = bp[t * kCbMaxBeam + k];
       if (e & 0xffff) out[--n] = (e & 0xffff) - 1;
       k = e >> 16;
@@ -192,17 +198,18 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
   }
 }
 
-hipError_t launch_ctc_beam(const float* logp, int n_seq, int Tq, int V, int blank, int beam, float blank_skip_threshold, int skip_drops,
-                           int* backptr, int* tokens, int* counts, float* scores, hipStream_t st) {
+hipError_t launch_ctc_beam(const float* logp, EEC_LEN_PARAM(const int* em_len) int n_seq, int Tq, int V, int blank, int beam,
+                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores, hipStream_t st) {
   if (V < 1 || V > 256 || beam < 1 || beam > kCbMaxBeam || blank < 0 || blank >= V) return hipErrorInvalidValue;
   const float log_thr = (blank_skip_threshold > 0.f && blank_skip_threshold < 1.f) ? logf(blank_skip_threshold) : INFINITY;
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, Tq, V, blank, beam, log_thr, skip_drops, backptr, tokens,
-                     counts, scores);
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, EEC_LEN_PARAM(em_len) Tq, V, blank, beam, log_thr, skip_drops,
+                     backptr, tokens, counts, scores);
   return hipGetLastError();
 }
 
 }  // namespace eec
 
+#ifndef EEC_CTC_LEN
 extern "C" {
 
 size_t eec_ctc_beam_workspace_bytes(int n_seq, int Tq) {
@@ -226,4 +233,21 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
   return 0;
 }
 
+int eec_ctc_beam_decode_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                            float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                            float* scores, void* stream) {
+  using eech::fail;
+  if (!em_len)
+    return eec_ctc_beam_decode_ex(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame, workspace, tokens, counts,
+                                  scores, stream);
+  if (!logp || !workspace || !tokens || !counts || !scores) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: null argument");
+  if (n_seq <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: n_seq and Tq must be positive");
+  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V)
+    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_beam_decode: needs 1 <= V <= 256, 1 <= beam_size <= " + std::to_string(eec::kCbMaxBeam) + ", blank in [0, V)");
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace,
+                               tokens, counts, scores, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"
+#endif

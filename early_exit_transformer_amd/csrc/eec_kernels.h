@@ -226,6 +226,19 @@ size_t ctc_store_floats(int E, int B, int Tq, int S);
 hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, int E, int B, int Tq,
                                int V, int S, int blank, const float* nll, float* astore, const float* grad_loss, float* dlogp,
                                hipStream_t st);
+// the same three with per-utterance frame counts input_len [B] (device; clamped to [0, Tq]); greedy / beam: em_len [n_seq]
+int ctc_states_per_lane(int S);  // 2, 4 or 8 states per lane; 0: the target width S does not fit
+hipError_t launch_ctc_reduce(const float* nll, const long long* target_len, int E, int B, float* out, hipStream_t st);
+hipError_t launch_ctc_loss(const float* logp, const long long* targets, const long long* target_len, const int* input_len, int E,
+                           int B, int Tq, int V, int S, int blank, float* nll, float* out, float* astore, hipStream_t st);
+hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, const int* input_len, int E,
+                               int B, int Tq, int V, int S, int blank, const float* nll, float* astore, const float* grad_loss,
+                               float* dlogp, hipStream_t st);
+hipError_t launch_greedy_ctc(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int* tokens, int* counts,
+                             hipStream_t st);
+hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam,
+                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores,
+                           hipStream_t st);
 hipError_t launch_logsoftmax_backward(const float* logp, const float* g, int M, int V, float* dlogits, hipStream_t st);
 
 // self-distillation between exits (distill.hip; include/eec.h states the loss).  `teacher` is a HOST array the caller has validated.

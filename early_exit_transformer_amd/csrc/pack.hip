@@ -4,8 +4,11 @@
 #include <utility>
 
 #include "eec_kernels.h"
+#include "eec_len.h"
 
 namespace eec {
+
+#ifndef EEC_CTC_LEN  // ctc_len.hip compiles the greedy decoder at the end of this file a second time (eec_len.h); the rest once
 
 hipError_t ensure_max_lds(const void* kernel, int bytes) {
   static std::mutex mu;
@@ -259,19 +262,23 @@ hipError_t launch_fill_int(int* dst, int n, int v, hipStream_t st) {
   return hipGetLastError();
 }
 
+#endif  // EEC_CTC_LEN
+
 // Greedy CTC (reference util/beam_infer.py:9-24): argmax over labels, collapse repeats, drop blank.
 // One wave per sequence; frames are walked 64 at a time, kept tokens compacted with a ballot.
 // Ties in the argmax resolve to the lowest label index (torch.argmax on CPU).
-__global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict__ logp, int Tq, int V, int blank,
-                                                        int* __restrict__ tokens, int* __restrict__ counts) {
+// With input lengths (eec_len.h) sequence s is its first Ts = clamp(em_len[s], 0, T') frames; the rows of `tokens` stay T' apart.
+__global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict__ logp, EEC_LEN_PARAM(const int* __restrict__ em_len)
+                                                        int Tq, int V, int blank, int* __restrict__ tokens, int* __restrict__ counts) {
   const int seq = blockIdx.x, lane = threadIdx.x;
   const float* base = logp + (size_t)seq * Tq * V;
   int* out = tokens + (size_t)seq * Tq;
+  const int Ts = EEC_LEN_FRAMES(em_len, seq, Tq);
   int n_out = 0, prev_last = -1;
-  for (int t0 = 0; t0 < Tq; t0 += 64) {
+  for (int t0 = 0; t0 < Ts; t0 += 64) {
     const int t = t0 + lane;
     int best = -1;
-    if (t < Tq) {
+    if (t < Ts) {
       const float* row = base + (size_t)t * V;
       float bv = row[0];
       best = 0;
@@ -285,20 +292,20 @@ __global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict_
     }
     int prev = __shfl_up(best, 1, 64);
     if (lane == 0) prev = prev_last;
-    const bool keep = (t < Tq) && (best != prev) && (best != blank);
+    const bool keep = (t < Ts) && (best != prev) && (best != blank);
     const unsigned long long mask = __ballot(keep);
     const int pos = __popcll(mask & ((1ull << lane) - 1ull));
     if (keep) out[n_out + pos] = best;
     n_out += __popcll(mask);
-    const int last_lane = min(63, Tq - 1 - t0);
+    const int last_lane = min(63, Ts - 1 - t0);
     prev_last = __shfl(best, last_lane, 64);
   }
   if (lane == 0) counts[seq] = n_out;
 }
 
-hipError_t launch_greedy_ctc(const float* logp, int n_seq, int Tq, int V, int blank, int* tokens, int* counts,
-                             hipStream_t st) {
-  hipLaunchKernelGGL(greedy_ctc_kernel, dim3(n_seq), dim3(64), 0, st, logp, Tq, V, blank, tokens, counts);
+hipError_t launch_greedy_ctc(const float* logp, EEC_LEN_PARAM(const int* em_len) int n_seq, int Tq, int V, int blank, int* tokens,
+                             int* counts, hipStream_t st) {
+  hipLaunchKernelGGL(greedy_ctc_kernel, dim3(n_seq), dim3(64), 0, st, logp, EEC_LEN_PARAM(em_len) Tq, V, blank, tokens, counts);
   return hipGetLastError();
 }
 

@@ -27,40 +27,64 @@ def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
     return out
 
 
-def greedy_ctc(logp: Tensor, blank: int = 0) -> Tuple[Tensor, Tensor]:
-    """[N, T', V] fp32 log-probs on the GPU -> (tokens [N, T'] int32, counts [N] int32)."""
+def _frame_counts(name: str, arg: str, lens: Optional[Tensor], n: int, dev: torch.device) -> Optional[Tensor]:
+    """A per-sequence frame count argument (int32 or int64, any device) as the kernels read it: int32 [n] on ``dev``, or None."""
+    if lens is None:
+        return None
+    if not isinstance(lens, Tensor):
+        lens = torch.as_tensor(lens)
+    if lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: {arg} must be an int32 or int64 tensor, got {lens.dtype}")
+    if lens.numel() != n:
+        raise ValueError(f"{name}: {arg} must have {n} entries, got {lens.numel()}")
+    if lens.dtype == torch.int64:
+        lens = lens.clamp(-2 ** 31, 2 ** 31 - 1)  # the kernels clamp to [0, T']: keep a count that int32 cannot hold on its side
+    return lens.reshape(n).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _ptr(t: Optional[Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """[N, T', V] fp32 log-probs on the GPU -> (tokens [N, T'] int32, counts [N] int32).  ``em_len`` [N] (None: T' for every
+    sequence): sequence s is its first ``clamp(em_len[s], 0, T')`` frames (eec_greedy_ctc_len)."""
     if not logp.is_cuda:
         raise RuntimeError("greedy_ctc runs on a HIP device only")
     logp = logp.contiguous().float()
     N, Tq, V = logp.shape
+    el = _frame_counts("greedy_ctc", "em_len", em_len, N, logp.device)
     tokens = torch.empty((N, Tq), dtype=torch.int32, device=logp.device)
     counts = torch.empty((N,), dtype=torch.int32, device=logp.device)
     with torch.cuda.device(logp.device):
-        capi.check(capi.load().eec_greedy_ctc(logp.data_ptr(), N, Tq, V, blank, tokens.data_ptr(),
-                                              counts.data_ptr(), stream_ptr(logp.device)), "eec_greedy_ctc")
+        capi.check(capi.load().eec_greedy_ctc_len(logp.data_ptr(), _ptr(el), N, Tq, V, blank, tokens.data_ptr(),
+                                                  counts.data_ptr(), stream_ptr(logp.device)), "eec_greedy_ctc")
     return tokens, counts
 
 
 def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
-                    skip_drops_frame: bool = False):
+                    skip_drops_frame: bool = False, em_len: Optional[Tensor] = None):
     """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
     sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
     ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
-    readings of the third-party decoder's skip rule, include/eec.h).  Returns (tokens [N, T'] int32, counts [N] int32,
-    scores [N] fp32)."""
+    readings of the third-party decoder's skip rule, include/eec.h).  ``em_len`` [N] (None: T' for every sequence, the
+    reference's ``encoder_out_lens``): sequence s is its first ``clamp(em_len[s], 0, T')`` frames; none gives count 0, score 0
+    (eec_ctc_beam_decode_len).  Returns (tokens [N, T'] int32, counts [N] int32, scores [N] fp32)."""
     if not logp.is_cuda:
         raise RuntimeError("ctc_beam_decode runs on a HIP device only")
     logp = logp.contiguous().float()
     N, Tq, V = logp.shape
     dev = logp.device
+    el = _frame_counts("ctc_beam_decode", "em_len", em_len, N, dev)
     lib = capi.load()
     tokens = torch.empty((N, Tq), dtype=torch.int32, device=dev)
     counts = torch.empty((N,), dtype=torch.int32, device=dev)
     scores = torch.empty((N,), dtype=torch.float32, device=dev)
     ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_beam_decode_ex(logp.data_ptr(), N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)),
-                                              ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), stream_ptr(dev)),
+        capi.check(lib.eec_ctc_beam_decode_len(logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold,
+                                               int(bool(skip_drops_frame)), ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(),
+                                               scores.data_ptr(), stream_ptr(dev)),
                    "eec_ctc_beam_decode")
     return tokens, counts, scores
 
@@ -396,11 +420,12 @@ def ctc_prefix_session(emission: Tensor, em_len: Optional[Tensor], R_max: int, w
 
 
 class _ExitCtcLossFn(torch.autograd.Function):
-    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (eec_ctc_loss_forward / _backward):
-    what autograd computes through the reference's loop of E nn.CTCLoss calls (train.py:60-68)."""
+    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (eec_ctc_loss_forward_len / _backward_len; no
+    ``input_len``: eec_ctc_loss_forward / _backward): what autograd computes through the reference's loop of E nn.CTCLoss calls
+    (train.py:60-68)."""
 
     @staticmethod
-    def forward(ctx, enc_out, tg, tl, blank):
+    def forward(ctx, enc_out, tg, tl, blank, il=None):
         E, B, Tq, V = enc_out.shape
         if V > 256 or V % 4:
             raise ValueError(f"exit_ctc_losses with a gradient needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
@@ -411,15 +436,15 @@ class _ExitCtcLossFn(torch.autograd.Function):
         out = torch.empty((E,), dtype=torch.float32, device=dev)
         ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
         with torch.cuda.device(dev):
-            capi.check(lib.eec_ctc_loss_forward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
-                                                nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
-        ctx.save_for_backward(enc_out, tg, tl, nll, ws)
+            capi.check(lib.eec_ctc_loss_forward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
+                                                    blank, nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+        ctx.save_for_backward(enc_out, tg, tl, nll, ws, il)
         ctx.blank, ctx.ws_ptr = blank, ws_ptr
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        enc_out, tg, tl, nll, ws = ctx.saved_tensors
+        enc_out, tg, tl, nll, ws, il = ctx.saved_tensors
         if getattr(ctx, "used", False):
             raise RuntimeError("exit_ctc_losses: backward through the same forward twice (its workspace is consumed)")
         ctx.used = True
@@ -428,30 +453,34 @@ class _ExitCtcLossFn(torch.autograd.Function):
         g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
         dlogp = torch.empty_like(enc_out)
         with torch.cuda.device(dev):
-            capi.check(capi.load().eec_ctc_loss_backward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1),
-                                                         ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(), dlogp.data_ptr(),
-                                                         stream_ptr(dev)), "eec_ctc_loss_backward")
-        return dlogp, None, None, None
+            capi.check(capi.load().eec_ctc_loss_backward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
+                                                             tg.size(1), ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(),
+                                                             dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
+        return dlogp, None, None, None, None
 
 
-def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank: int = 0) -> Tensor:
+def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank: int = 0, input_len: Optional[Tensor] = None) -> Tensor:
     """Per-exit CTC losses [E] of an encoder output [E, B, T', V] in ONE launch: what train.py:53-65 computes with
     E separate nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) calls and input length T' for every
     utterance.  ``.sum()`` is the reference's training loss.  Differentiable with respect to ``enc_out`` (HIP backward:
-    beta recursion + dense gradient, the values torch autograd returns for the reference's loop)."""
+    beta recursion + dense gradient, the values torch autograd returns for the reference's loop).
+    ``input_len`` [B] (None: T' for every utterance, the reference's convention; ``encoder_lengths(lengths, T')`` gives the
+    encoder's own) is nn.CTCLoss's ``input_lengths``, shared by the exits and clamped to [0, T']: the frames at or past it are not
+    read, whatever they hold, and their gradient rows are written as zeros.  The loss is still divided by the target length only."""
     if not enc_out.is_cuda:
         raise RuntimeError("exit_ctc_losses runs on a HIP device only")
     enc_out = enc_out.contiguous().float()
     dev = enc_out.device
     tg, tl = to_device(targets, dev), to_device(target_len, dev)
     E, B, Tq, V = enc_out.shape
+    il = _frame_counts("exit_ctc_losses", "input_len", input_len, B, dev)
     if torch.is_grad_enabled() and enc_out.requires_grad:
-        return _ExitCtcLossFn.apply(enc_out, tg, tl, blank)
+        return _ExitCtcLossFn.apply(enc_out, tg, tl, blank, il)
     nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
     out = torch.empty((E,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        capi.check(capi.load().eec_ctc_loss(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
-                                            nll.data_ptr(), out.data_ptr(), stream_ptr(dev)), "eec_ctc_loss")
+        capi.check(capi.load().eec_ctc_loss_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1), blank,
+                                                nll.data_ptr(), out.data_ptr(), stream_ptr(dev)), "eec_ctc_loss")
     return out
 
 
@@ -555,11 +584,12 @@ def exit_distill_losses(enc_out: Tensor, frame_len: Optional[Tensor] = None, tea
 
 
 class _ExitTrainingFn(torch.autograd.Function):
-    """(CTC losses [E], distillation losses [E]) as ONE node: its backward runs eec_ctc_loss_backward into a fresh gradient buffer
-    and the distillation backward adds into the same buffer, so autograd neither copies nor re-adds the CTC gradient."""
+    """(CTC losses [E], distillation losses [E]) as ONE node: its backward runs eec_ctc_loss_backward[_len] into a fresh gradient
+    buffer -- every element of it is written, the rows past an utterance's ``input_len`` as zeros -- and the distillation backward
+    adds into the same buffer, so autograd neither copies nor re-adds the CTC gradient."""
 
     @staticmethod
-    def forward(ctx, enc_out, tg, tl, blank, frame_len, teacher, tau):
+    def forward(ctx, enc_out, tg, tl, blank, frame_len, teacher, tau, il=None):
         E, B, Tq, V = enc_out.shape
         dev = enc_out.device
         lib = capi.load()
@@ -567,17 +597,17 @@ class _ExitTrainingFn(torch.autograd.Function):
         ctc = torch.empty((E,), dtype=torch.float32, device=dev)
         ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
         with torch.cuda.device(dev):
-            capi.check(lib.eec_ctc_loss_forward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1), blank,
-                                                nll.data_ptr(), ctc.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+            capi.check(lib.eec_ctc_loss_forward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
+                                                    blank, nll.data_ptr(), ctc.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
         kd = _distill_forward(enc_out, frame_len, teacher, tau)
         ctx.set_materialize_grads(False)  # a loss that uses one of the two outputs only: None for the other, and its launch is skipped
-        ctx.save_for_backward(enc_out, tg, tl, nll, ws, frame_len)
+        ctx.save_for_backward(enc_out, tg, tl, nll, ws, frame_len, il)
         ctx.blank, ctx.ws_ptr, ctx.teacher, ctx.tau = blank, ws_ptr, teacher, tau
         return ctc, kd
 
     @staticmethod
     def backward(ctx, grad_ctc, grad_kd):
-        enc_out, tg, tl, nll, ws, frame_len = ctx.saved_tensors
+        enc_out, tg, tl, nll, ws, frame_len, il = ctx.saved_tensors
         if getattr(ctx, "used", False):
             raise RuntimeError("exit_training_losses: backward through the same forward twice (its workspace is consumed)")
         ctx.used = True
@@ -587,25 +617,28 @@ class _ExitTrainingFn(torch.autograd.Function):
         if grad_ctc is not None:
             g = grad_ctc.to(device=dev, dtype=torch.float32).contiguous()
             with torch.cuda.device(dev):
-                capi.check(capi.load().eec_ctc_loss_backward(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), E, B, Tq, V, tg.size(1),
-                                                             ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(), dlogp.data_ptr(),
-                                                             stream_ptr(dev)), "eec_ctc_loss_backward")
+                capi.check(capi.load().eec_ctc_loss_backward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
+                                                                 tg.size(1), ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(),
+                                                                 dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
         if grad_kd is not None:
             _distill_backward(enc_out, frame_len, ctx.teacher, ctx.tau, grad_kd, grad_ctc is not None, dlogp)
         elif grad_ctc is None:
             dlogp.zero_()
-        return dlogp, None, None, None, None, None, None
+        return dlogp, None, None, None, None, None, None, None
 
 
 def exit_training_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, frame_len: Optional[Tensor] = None,
-                         teacher: Union[str, Sequence[int]] = "last", temperature: float = 1.0, blank: int = 0) -> Tuple[Tensor, Tensor]:
-    """``(exit_ctc_losses(enc_out, targets, target_len, blank), exit_distill_losses(enc_out, frame_len, teacher, temperature))``,
-    the same values bit for bit, as one autograd node: ``ctc.sum() + w * kd.sum()`` is the training loss with distillation, and its
-    backward writes the CTC gradient into a fresh buffer and adds the distillation gradient into the same buffer (with ``w = 0``
-    that is the gradient of ``exit_ctc_losses`` bit for bit).  ``frame_len`` masks the distillation term only: the CTC loss keeps the
-    reference's input length T' for every utterance."""
+                         teacher: Union[str, Sequence[int]] = "last", temperature: float = 1.0, blank: int = 0,
+                         input_len: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """``(exit_ctc_losses(enc_out, targets, target_len, blank, input_len), exit_distill_losses(enc_out, frame_len, teacher,
+    temperature))``, the same values bit for bit, as one autograd node: ``ctc.sum() + w * kd.sum()`` is the training loss with
+    distillation, and its backward writes the CTC gradient into a fresh buffer and adds the distillation gradient into the same
+    buffer (with ``w = 0`` that is the gradient of ``exit_ctc_losses`` bit for bit).  The two masks are separate arguments:
+    ``frame_len`` masks the distillation term only and ``input_len`` the CTC loss only (None: T' for every utterance, the
+    reference's convention, for either).  On a ragged batch pass ``encoder_lengths(lengths, T')`` as both."""
     x, fl, tmap, tau = _distill_args("exit_training_losses", enc_out, frame_len, teacher, temperature)
     if not (torch.is_grad_enabled() and x.requires_grad):
-        return exit_ctc_losses(x, targets, target_len, blank), _distill_forward(x, fl, tmap, tau)
+        return exit_ctc_losses(x, targets, target_len, blank, input_len), _distill_forward(x, fl, tmap, tau)
     dev = x.device
-    return _ExitTrainingFn.apply(x, to_device(targets, dev), to_device(target_len, dev), blank, fl, tmap, tau)
+    il = _frame_counts("exit_training_losses", "input_len", input_len, x.size(1), dev)
+    return _ExitTrainingFn.apply(x, to_device(targets, dev), to_device(target_len, dev), blank, fl, tmap, tau, il)

@@ -282,10 +282,15 @@ class Early_conformer(_HipEncoderMixin, nn.Module):
         ``n_exits`` exits only, [n_exits, B, T', V], at n_exits / E of the cost of ``forward``."""
         return self._run_encoder(src, lengths, n_groups=n_exits)[0]
 
-    def greedy_decode(self, enc_out: Tensor, blank: int = 0) -> List[List[List[int]]]:
-        """Batched GreedyCTCDecoder (util/beam_infer.py:9-24) over every exit and utterance."""
+    def greedy_decode(self, enc_out: Tensor, blank: int = 0, lengths: Optional[Tensor] = None) -> List[List[List[int]]]:
+        """Batched GreedyCTCDecoder (util/beam_infer.py:9-24) over every exit and utterance.  ``lengths`` [B], in encoder frames
+        (``encoder_lengths``; None: T' for every utterance), applies to every exit: frames at or past it are not transcribed."""
         E, B, Tq, V = enc_out.shape
-        tokens, counts = greedy_ctc(enc_out.reshape(E * B, Tq, V), blank)
+        if lengths is not None:
+            if lengths.numel() != B:
+                raise ValueError(f"greedy_decode: lengths must have {B} entries, got {lengths.numel()}")
+            lengths = lengths.reshape(B).repeat(E)  # sequence e * B + b
+        tokens, counts = greedy_ctc(enc_out.reshape(E * B, Tq, V), blank, em_len=lengths)
         tokens, counts = tokens.cpu(), counts.cpu()
         return [[tokens[e * B + b, : counts[e * B + b]].tolist() for b in range(B)] for e in range(E)]
 

@@ -229,6 +229,27 @@ int eec_ctc_loss_backward(const float* logp, const int64_t* targets, const int64
                           int blank, const float* nll, void* bwd_workspace, const float* grad_loss, float* dlogp, void* stream);
 int eec_logsoftmax_backward(const float* logp, const float* grad_logp, int M, int V, float* grad_logits, void* stream);
 
+/* The three CTC loss entries with per-utterance input lengths, what nn.CTCLoss takes as `input_lengths` (the reference fills them
+ * with T': train.py:57-58).  Every argument the entries above share keeps its meaning; the new one:
+ *   input_len [B] int32 on the device, in encoder frames (eec_encoder_lengths), shared by the E exits of an utterance and clamped:
+ *       Tb = clamp(input_len[b], 0, T').  NULL: T' for every utterance -- the call IS the entry above, launch for launch.
+ * Utterance b's lattices cover the frames t < Tb.  Frames at or past Tb are never read: no loss, no gradient and no zero depends
+ * on what they hold, NaN included.  Tb = 0: nll is 0 for an empty target and +inf (infeasible: zeroed) for any other.  A target
+ * that needs more than Tb frames is infeasible like one that needs more than T'.  The normalisation does not change:
+ * loss_e = batch mean of nll / max(target_len, 1); like torch, nothing is divided by the input length.
+ *   eec_ctc_loss_backward_len: dlogp is written in full -- the rows t >= Tb of every lattice as ZEROS, so a buffer that was never
+ *       initialised is a complete gradient afterwards (eec_exit_distill_backward with accumulate != 0 may then add into it).
+ * The forward / backward pair must be given the same input_len.  The workspace is still eec_ctc_backward_workspace_bytes(E, B, T', S)
+ * bytes.  Sizes, the limits (target length <= 255; V <= 256 and V % 4 == 0 for the backward) and the errors are the entries' above. */
+int eec_ctc_loss_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E, int B,
+                     int Tq, int V, int S, int blank, float* nll_scratch, float* loss_per_exit, void* stream);
+int eec_ctc_loss_forward_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E,
+                             int B, int Tq, int V, int S, int blank, float* nll, float* loss_per_exit, void* bwd_workspace,
+                             void* stream);
+int eec_ctc_loss_backward_len(const float* logp, const int64_t* targets, const int64_t* target_len, const int32_t* input_len, int E,
+                              int B, int Tq, int V, int S, int blank, const float* nll, void* bwd_workspace, const float* grad_loss,
+                              float* dlogp, void* stream);
+
 /* Self-distillation between exits: the second training recipe of a multi-exit network (the reference declares the flag
  * `--distill`, "whether to use knowledge distillation", and leaves it unimplemented: util/conf.py:48-57).  A student exit's frame
  * posteriors are pulled towards its teacher exit's by a temperature-softened KL term that is added to the per-exit CTC loss; it
@@ -282,6 +303,19 @@ int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, 
  * are tested against the CPU statement (oracle/ctc_beam_ref.py); the default stays the first until a torchaudio vector pins it. */
 int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                            int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream);
+
+/* The greedy decoder and the prefix beam search with per-sequence input lengths (torchaudio's cuda_ctc_decoder takes them as
+ * `encoder_out_lens`; the reference fills them with T': util/beam_infer.py:106-107):
+ *   em_len [n_seq] int32 on the device, clamped: sequence s is its first Ts = clamp(em_len[s], 0, T') frames, exactly as if
+ *       logp[s, :Ts] had been decoded alone; frames at or past Ts are never read.  NULL: T' for every sequence -- the call IS
+ *       eec_greedy_ctc / eec_ctc_beam_decode_ex, launch for launch.
+ * Ts = 0 gives counts[s] = 0, and scores[s] = 0 (the empty prefix, log 1).  The rows of `tokens` stay T' apart and the workspace
+ * is still eec_ctc_beam_workspace_bytes(n_seq, T') bytes.  skip_drops_frame as in eec_ctc_beam_decode_ex; errors as the entries above. */
+int eec_greedy_ctc_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int32_t* tokens,
+                       int32_t* counts, void* stream);
+int eec_ctc_beam_decode_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                            float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                            float* scores, void* stream);
 
 /* Lexicon-constrained CTC beam search with N-best: replaces the decoder behind BeamInference.ctc_predict / ctc_predict_ /
  * beam_predict (util/beam_infer.py:51-65, 85-126): torchaudio ctc_decoder(lexicon, tokens, nbest=N_BEST, log_add=False, beam_size,
