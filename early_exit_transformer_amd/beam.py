@@ -647,3 +647,55 @@ class BeamInference:
                 for ids in row:
                     ids.text = next(texts)
         return out
+
+    # -- adaptive inference: every utterance decoded at the one exit it left the encoder at --------------------------------
+    @torch.no_grad()
+    def ctc_adaptive_predict(self, model, src: Tensor, lengths: Tensor, threshold=None, beam_size: Optional[int] = None, lexicon=None,
+                             detokenize=None, **adaptive) -> Tuple[List[List["CTCHypothesis"]], Tensor]:
+        """``model.forward_adaptive(src, lengths, threshold, **adaptive)`` (``criterion=``, ``min_exit=``, ``max_exit=``, ``exit_of=``,
+        ``compact=``) and then ONE ``ctc_cuda_predict`` over the B emissions of the chosen exits, over the encoder's own frame counts
+        -- where decoding every exit of ``forward`` searches E * B sequences.  Returns ``(hypotheses, exit_of)``: per utterance the
+        list ``ctc_cuda_predict`` returns, and the 0-based exit int32 [B] it was decoded at."""
+        if adaptive.get("want_taps"):
+            raise ValueError("ctc_adaptive_predict: the CTC search reads no taps")
+        out = model.forward_adaptive(src, lengths, threshold, **adaptive)
+        em_len = encoder_lengths(lengths.to(out.logp.device), out.logp.size(1))
+        return self.ctc_cuda_predict(out.logp, beam_size=beam_size, lexicon=lexicon, detokenize=detokenize, lengths=em_len), out.exit_of
+
+    @torch.no_grad()
+    def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,
+                              beam_size: int = 10, joint_ctc_weight: Optional[float] = None, criterion: str = "entropy",
+                              min_exit: int = 0, max_exit: Optional[int] = None, exit_of: Optional[Tensor] = None, compact: bool = True,
+                              **kw) -> List[Tuple[List[int], int]]:
+        """``decode_batch`` at ONE exit per utterance: the adaptive encoder pass (``model.forward_adaptive(..., want_taps=True)``) and
+        then, for every distinct chosen exit, one ``beam_search_batch`` over that exit's utterances (``joint_search_batch`` with
+        ``joint_ctc_weight=``, over the chosen exits' CTC log-probs and the encoder's frame counts) -- where ``decode_batch`` searches
+        all E * B pairs.  Returns ``out[b] = (best_tokens, exit)``, the exit 0-based; ``best_tokens`` is what ``decode_batch``
+        returns as ``out[b][exit]``.  Where the batched search declines, the exit's utterances go through ``beam_search`` one by one."""
+        if max_length is None:
+            max_length = default_max_length(spec.size(2))
+        if joint_ctc_weight is not None:
+            _check_joint_weight(joint_ctc_weight)
+        ad = model.forward_adaptive(spec, valid_len.reshape(-1), threshold, criterion=criterion, min_exit=min_exit, max_exit=max_exit,
+                                    exit_of=exit_of, compact=compact, want_taps=True)
+        dev = ad.logp.device
+        chosen = ad.exit_of.cpu().tolist()
+        em_len = encoder_lengths(valid_len.reshape(-1).to(dev), ad.logp.size(1)) if joint_ctc_weight is not None else None
+        lockstep = _lockstep_kw(kw)
+        out: List[Optional[Tuple[List[int], int]]] = [None] * len(chosen)
+        for e in sorted(set(chosen)):
+            members = [b for b, c in enumerate(chosen) if c == e]
+            rows = torch.tensor(members, dtype=torch.int64, device=dev)
+            tap_rows = ad.taps[rows]
+            if joint_ctc_weight is not None:
+                together = self.joint_search_batch(model, [tap_rows], [e + 1], ad.logp[rows].unsqueeze(0), em_len[rows], joint_ctc_weight,
+                                                   max_length, beam_size=beam_size, **(lockstep or {}))
+            else:
+                together = None if lockstep is None else \
+                    self.beam_search_batch(model, [tap_rows], [e + 1], max_length=max_length, beam_size=beam_size, **lockstep)
+            if together is None:
+                together = [[self.beam_search(model, tap_rows[i:i + 1], e + 1, max_length=max_length, beam_size=beam_size, **kw)]
+                            for i in range(len(members))]
+            for b, row in zip(members, together):
+                out[b] = (row[0][2], e)
+        return out

@@ -866,6 +866,34 @@ int eec_exit_distill_backward(const float* x, const int32_t* frame_len, const in
   return 0;
 }
 
+size_t eec_exit_stats_workspace_bytes(int E, int B, int T) {
+  if (E <= 0 || B <= 0 || T <= 0) return 0;
+  return (size_t)3 * E * B * T * sizeof(float);
+}
+
+int eec_exit_stats(const float* x, const int32_t* frame_len, int E, int B, int T, int V, float* stats, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (!x || !stats || !workspace) return fail(EEC_ERR_BAD_ARG, "exit statistics: null argument");
+  if (E <= 0 || B <= 0 || T <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "exit statistics: E, B, T and V must be positive");
+  if (E > EEC_EXIT_STATS_MAX_EXITS)
+    return fail(EEC_ERR_BAD_ARG, "exit statistics: at most " + std::to_string(EEC_EXIT_STATS_MAX_EXITS) + " exits, got " + std::to_string(E));
+  if (V > 256 || V % 4) return fail(EEC_ERR_BAD_ARG, "exit statistics: vocab must be a multiple of 4, <= 256");
+  if ((long long)B * T > 0x7fffffffLL) return fail(EEC_ERR_BAD_ARG, "exit statistics: B * T above 2^31 - 1");
+  if ((long long)3 * E * B > 0x7fffffffLL) return fail(EEC_ERR_BAD_ARG, "exit statistics: 3 * E * B above 2^31 - 1");
+  if (int rc = check_workspace(workspace, workspace_bytes, eec_exit_stats_workspace_bytes(E, B, T))) return rc;
+  EEC_HIP(launch_exit_stats(x, frame_len, E, B, T, V, stats, (float*)workspace, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_exit_route(const float* score, int n, float threshold, int higher_is_better, int force_all, int32_t* stay_idx,
+                   int32_t* leave_idx, int32_t* counts, void* stream) {
+  if (!score || !stay_idx || !leave_idx || !counts) return fail(EEC_ERR_BAD_ARG, "exit route: null argument");
+  if (n <= 0) return fail(EEC_ERR_BAD_ARG, "exit route: n must be positive, got " + std::to_string(n));
+  if (threshold != threshold && !force_all) return fail(EEC_ERR_BAD_ARG, "exit route: the threshold is NaN");
+  EEC_HIP(launch_exit_route(score, n, threshold, higher_is_better != 0, force_all != 0, stay_idx, leave_idx, counts, (hipStream_t)stream));
+  return 0;
+}
+
 int eec_encoder_set_profiling(eec_encoder* enc, int enable, int max_launches) {
   if (!enc) return fail(EEC_ERR_BAD_ARG, "null argument");
   for (hipEvent_t e : enc->ev) (void)hipEventDestroy(e);

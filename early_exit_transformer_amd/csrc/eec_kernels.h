@@ -249,4 +249,11 @@ hipError_t launch_distill_forward(const float* x, const int* frame_len, const in
 hipError_t launch_distill_backward(const float* x, const int* frame_len, const int* teacher, int E, int B, int T, int V, float tau,
                                    const float* grad_loss, int accumulate, float* dx, hipStream_t st);
 
+// exit statistics and routing (exit_stats.hip; include/eec.h states both).  ws: 3 * E * B * T floats; stats [3, E, B]
+constexpr int kExitStatsMaxExits = EEC_EXIT_STATS_MAX_EXITS;
+hipError_t launch_exit_stats(const float* x, const int* frame_len, int E, int B, int T, int V, float* stats, float* ws, hipStream_t st);
+// stay_idx / leave_idx [n] (the first counts[0] / counts[1] entries are written), counts [2]
+hipError_t launch_exit_route(const float* score, int n, float threshold, int higher_is_better, int force_all, int* stay_idx,
+                             int* leave_idx, int* counts, hipStream_t st);
+
 }  // namespace eec

@@ -2,11 +2,12 @@
 (the reference's unimplemented ``--distill``), greedy, prefix-beam and
 lexicon-constrained beam decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
 stream; there is no CPU path, except for the CTC prefix scorer of one-pass joint decoding (``ctc_prefix_session``), whose host path lets a
-search loop be tested without a device."""
+search loop be tested without a device, and for the exit statistics and the exit choice of adaptive inference (``exit_statistics``,
+``select_exits``), whose host paths state them in torch ops."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple, Union
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -581,6 +582,139 @@ def exit_distill_losses(enc_out: Tensor, frame_len: Optional[Tensor] = None, tea
     if torch.is_grad_enabled() and x.requires_grad:
         return _ExitDistillFn.apply(x, fl, tmap, tau)
     return _distill_forward(x, fl, tmap, tau)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Adaptive inference: exit statistics and exit choice (include/eec.h states both; csrc/exit_stats.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+class ExitStatistics(NamedTuple):
+    """Per exit and utterance, [E, B] fp32 each: the average frame entropy (nats), the average frame confidence ``max_v p_v`` and
+    the log-probability of the greedy CTC path (a sum over the frames, not divided by their number)."""
+    entropy: Tensor
+    confidence: Tensor
+    greedy_logp: Tensor
+
+
+EXIT_CRITERIA = {"entropy": False, "confidence": True, "greedy_logp": True}  # criterion -> higher is better
+
+
+def _exit_stats_args(name: str, enc_out: Tensor, frame_len: Optional[Tensor]):
+    """(enc_out fp32 contiguous, frame_len int32 [B] on its device or None), checked as ``_distill_args`` checks them; a CPU tensor
+    is allowed (the host path)."""
+    if not isinstance(enc_out, Tensor) or enc_out.dim() != 4:
+        raise ValueError(f"{name}: enc_out must be [E, B, T', V], got {tuple(getattr(enc_out, 'shape', ()))}")
+    if not enc_out.is_floating_point():
+        raise ValueError(f"{name}: enc_out must be a floating-point tensor, got {enc_out.dtype}")
+    if min(enc_out.shape) < 1:
+        raise ValueError(f"{name}: enc_out must not be empty, got {tuple(enc_out.shape)}")
+    enc_out = enc_out.contiguous().float()
+    E, B, _, V = enc_out.shape
+    if E > 16:
+        raise ValueError(f"{name}: at most 16 exits, got {E}")
+    if V > 256 or V % 4:
+        raise ValueError(f"{name} needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
+                         "the statistics kernel holds a vocabulary row in one wave")
+    return enc_out, _frame_counts(name, "frame_len", frame_len, B, enc_out.device)
+
+
+def _exit_statistics_host(x: Tensor, frame_len: Optional[Tensor]) -> Tensor:
+    """[3, E, B]: the statement of include/eec.h in fp32 torch ops."""
+    E, B, T, _ = x.shape
+    lens = torch.full((B,), T, dtype=torch.int64, device=x.device) if frame_len is None else frame_len.to(torch.int64).clamp(0, T)
+    mask = torch.arange(T, device=x.device).view(1, T) < lens.view(B, 1)
+    lp = torch.log_softmax(x, dim=-1)
+    p = lp.exp()
+    ent = -torch.where(p == 0, torch.zeros_like(p), p * lp).sum(-1)
+    top = lp.max(dim=-1).values  # a NaN row gives NaN
+    n = lens.clamp(min=1).to(x.dtype)
+    add = lambda term: torch.where(mask, term, torch.zeros_like(term)).sum(-1)  # noqa: E731  (a masked frame reaches nothing)
+    return torch.stack([add(ent) / n, add(top.exp()) / n, add(top)])
+
+
+def exit_statistics(enc_out: Tensor, frame_len: Optional[Tensor] = None) -> ExitStatistics:
+    """``ExitStatistics(entropy, confidence, greedy_logp)``, each [E, B], of an encoder output [E, B, T', V] (logits or log-probs:
+    every row is normalised inside) over the frames ``t < clamp(frame_len[b], 0, T')`` (None: T' for every utterance;
+    ``encoder_lengths(lengths, T')`` gives the encoder's own) -- what an early-exit model chooses an utterance's exit by
+    (``select_exits``).  An utterance without frames gives 0 / 0 / 0; frames past the length are never read; a NaN inside reaches
+    its own (e, b) only.  On the device one pass over ``enc_out`` (eec_exit_stats), bit-reproducible; a CPU tensor takes the host
+    path, the same statement in fp32 torch ops."""
+    x, fl = _exit_stats_args("exit_statistics", enc_out, frame_len)
+    if not x.is_cuda:
+        return ExitStatistics(*_exit_statistics_host(x, fl))
+    E, B, Tq, V = x.shape
+    dev = x.device
+    lib = capi.load()
+    stats = torch.empty((3, E, B), dtype=torch.float32, device=dev)
+    nbytes = lib.eec_exit_stats_workspace_bytes(E, B, Tq)
+    ws, ws_ptr = capi.aligned_ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_exit_stats(x.data_ptr(), _ptr(fl), E, B, Tq, V, stats.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)), "eec_exit_stats")
+    return ExitStatistics(stats[0], stats[1], stats[2])
+
+
+def exit_route(score: Tensor, threshold: float, higher_is_better: bool = False, force_all: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """The stable partition of the rows of ``score`` [n] (fp32, on the device) into stayers and leavers (eec_exit_route): row i
+    leaves when ``score[i] < threshold`` (``>`` with ``higher_is_better``; a tie or a NaN stays), every row with ``force_all``.
+    Returns ``(stay_idx, leave_idx, counts)``, int32 on the device: ``counts = [stayers, leavers]``, the first ``counts[0]``
+    entries of ``stay_idx`` and the first ``counts[1]`` of ``leave_idx`` hold the rows in ascending order, the rest hold n."""
+    if not score.is_cuda:
+        raise RuntimeError("exit_route runs on a HIP device only (select_exits has the host path)")
+    if score.dim() != 1 or score.numel() < 1:
+        raise ValueError(f"exit_route: score must be [n] with n >= 1, got {tuple(score.shape)}")
+    score = score.contiguous().float()
+    n, dev = score.numel(), score.device
+    idx = torch.full((2, n), n, dtype=torch.int32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().eec_exit_route(score.data_ptr(), n, float(threshold), int(bool(higher_is_better)), int(bool(force_all)),
+                                              idx[0].data_ptr(), idx[1].data_ptr(), counts.data_ptr(), stream_ptr(dev)), "eec_exit_route")
+    return idx[0], idx[1], counts
+
+
+def _exit_thresholds(name: str, threshold, E: int) -> Tuple[float, ...]:
+    """``threshold`` as one float per exit: a number, or E of them."""
+    if isinstance(threshold, Tensor):
+        threshold = threshold.tolist()
+    t = tuple(float(v) for v in threshold) if isinstance(threshold, (list, tuple)) else (float(threshold),) * E
+    if len(t) != E:
+        raise ValueError(f"{name}: threshold must be a number or one per exit ({E}), got {len(t)}")
+    if any(v != v for v in t):
+        raise ValueError(f"{name}: a threshold is NaN")
+    return t
+
+
+def _exit_range(name: str, E: int, min_exit: int, max_exit: Optional[int]) -> Tuple[int, int]:
+    lo, hi = int(min_exit), E - 1 if max_exit is None else int(max_exit)
+    if not 0 <= lo <= hi < E:
+        raise ValueError(f"{name}: need 0 <= min_exit <= max_exit < {E}, got min_exit {lo}, max_exit {hi}")
+    return lo, hi
+
+
+def select_exits(score: Tensor, threshold, higher_is_better: bool = False, min_exit: int = 0, max_exit: Optional[int] = None) -> Tensor:
+    """The exit of every utterance, int32 [B], 0-based, from a table ``score`` [E, B] (a field of ``exit_statistics``, or any
+    caller-supplied criterion such as the N-best posterior ``ctc_predict`` returns): the first exit e in ``[min_exit, max_exit]``
+    whose score passes ``threshold[e]`` -- is below it, or above it with ``higher_is_better``; a tie or a NaN does not pass --, and
+    ``max_exit`` (default E - 1) where none does.  ``threshold``: a float, or E floats.  On the device one eec_exit_route launch per
+    exit considered and no host synchronisation; a CPU table takes the host path."""
+    if not isinstance(score, Tensor) or score.dim() != 2 or min(score.shape) < 1:
+        raise ValueError(f"select_exits: score must be [E, B], got {tuple(getattr(score, 'shape', ()))}")
+    if not score.is_floating_point():
+        raise ValueError(f"select_exits: score must be a floating-point tensor, got {score.dtype}")
+    E, B = score.shape
+    thr = _exit_thresholds("select_exits", threshold, E)
+    lo, hi = _exit_range("select_exits", E, min_exit, max_exit)
+    score = score.float()
+    out = torch.full((B,), hi, dtype=torch.int32, device=score.device)
+    for e in range(hi - 1, lo - 1, -1):  # the last exit takes whoever is left: its own score is not looked at
+        if score.is_cuda:
+            leave_idx = exit_route(score[e], thr[e], higher_is_better)[1]
+            passed = torch.zeros((B + 1,), dtype=torch.bool, device=score.device)
+            passed[leave_idx.long()] = True  # the unwritten tail of leave_idx holds B
+            passed = passed[:B]
+        else:
+            passed = score[e] > thr[e] if higher_is_better else score[e] < thr[e]
+        out = torch.where(passed, torch.full_like(out, e), out)
+    return out
 
 
 class _ExitTrainingFn(torch.autograd.Function):

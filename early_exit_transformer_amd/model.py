@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -23,6 +23,8 @@ from .capi import to_device as _to_device
 from .conformer import Conformer
 from .ctc import (CtcPrefixSession, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, exit_ctc_losses, exit_distill_losses,  # noqa: F401
                   exit_training_losses, greedy_ctc)
+from .ctc import EXIT_CRITERIA, ExitStatistics, exit_route, exit_statistics, select_exits  # noqa: F401
+from .ctc import _exit_range, _exit_thresholds
 from .lexicon import Lexicon, TokenTrie, apply_lex, load_dict  # noqa: F401
 from .decoding import DecoderStepSession, _BatchSession, _DecoderTrainFn, _ExitSessions, beam_select  # noqa: F401
 from .training import (_ExitHeadsFn, _named_tensors, _train_group, _train_head, _TrainStemFn, forward_train,  # noqa: F401
@@ -55,6 +57,16 @@ class Conv1dSubampling(nn.Module):
         self.sequential = nn.Sequential(
             nn.Conv1d(in_channels, out_channels, kernel_size=3, stride=2, padding=0),
             nn.Conv1d(out_channels, out_channels, kernel_size=3, stride=2, padding=0))
+
+
+class AdaptiveOutput(NamedTuple):
+    """What ``forward_adaptive`` returns: per utterance the log-probs [B, T', V] (and, asked for, the encoder output ``taps``
+    [B, T', D]) of the exit it left at, that exit ``exit_of`` int32 [B] (0-based), and ``scores`` [E, B], the criterion's score at
+    every exit the utterance reached (NaN elsewhere)."""
+    logp: Tensor
+    exit_of: Tensor
+    scores: Tensor
+    taps: Optional[Tensor]
 
 
 class _HipEncoderMixin:
@@ -228,6 +240,100 @@ class _HipEncoderMixin:
 
     _forward_train = forward_train  # the whole-encoder training step (Early_conformer, full_conformer)
 
+    # -- adaptive inference ---------------------------------------------------
+    @torch.no_grad()
+    def forward_adaptive(self, src: Tensor, lengths: Tensor, threshold=None, criterion: str = "entropy", min_exit: int = 0,
+                         max_exit: Optional[int] = None, exit_of: Optional[Tensor] = None, compact: bool = True,
+                         want_taps: bool = False) -> "AdaptiveOutput":
+        """Every utterance leaves the encoder at the shallowest exit that is good enough for it (extension; the reference's
+        forward always runs every group): ``AdaptiveOutput(logp [B, T', V], exit_of int32 [B], scores [E, B], taps [B, T', D] or
+        None)``.  ``logp[b]`` / ``taps[b]`` are the log-probs / encoder output of exit ``exit_of[b]`` (0-based) -- what ``forward``
+        computes for that exit and utterance: the walk runs the stem once and then, exit by exit, the same group and head launches
+        on the utterances still in flight, ``exit_statistics`` of that one exit and one ``exit_route``.
+        ``criterion``: ``"entropy"`` (an utterance leaves when its average frame entropy is BELOW ``threshold``), ``"confidence"``
+        (average frame confidence ABOVE) or ``"greedy_logp"`` (``greedy_logp / max(frames, 1)`` ABOVE), over the encoder's own
+        frame counts ``encoder_lengths(lengths, T')``.  ``threshold``: a float or one per exit.  Exits below ``min_exit`` let
+        nobody leave, ``max_exit`` (default E - 1) takes everyone left.  ``scores[e, b]`` is the score exit e gave utterance b,
+        NaN for an exit the utterance never reached.
+        ``exit_of`` (int [B], instead of ``threshold``): the routing is prescribed -- the "oracle exit" analysis -- and the
+        scores are still recorded; ``min_exit`` / ``max_exit`` are not looked at.
+        ``compact``: the rows and key lengths of the utterances that stay are gathered and the next group runs on them alone
+        (T' is never trimmed: that would move the depthwise convolution's zero padding); False: the whole batch runs every
+        group and only the early stop saves work.  One 8-byte device-to-host read (the route's counts) per exit evaluated but
+        the last; gathers and scatters are torch index ops.  Inference only: call under ``eval()``."""
+        if self._cfg.arch != capi.ARCH_CONFORMER:
+            raise NotImplementedError(f"{type(self).__name__} has no adaptive forward")
+        if self.training:
+            raise RuntimeError("forward_adaptive is an inference pass: call it under model.eval()")
+        if (threshold is None) == (exit_of is None):
+            raise ValueError("forward_adaptive: give exactly one of threshold= and exit_of=")
+        if criterion not in EXIT_CRITERIA:
+            raise ValueError(f"forward_adaptive: criterion must be one of {sorted(EXIT_CRITERIA)}, got {criterion!r}")
+        E, V = self._cfg.n_exits, self._cfg.vocab
+        higher = EXIT_CRITERIA[criterion]
+        if exit_of is None:
+            lo, hi = _exit_range("forward_adaptive", E, min_exit, max_exit)
+            thr = _exit_thresholds("forward_adaptive", threshold, E)
+        else:
+            planned = torch.as_tensor(exit_of).reshape(-1).cpu().to(torch.int64)
+            if planned.numel() != src.size(0) or planned.numel() == 0 or int(planned.min()) < 0 or int(planned.max()) >= E:
+                raise ValueError(f"forward_adaptive: exit_of must hold one exit in 0 .. {E - 1} per utterance")
+            lo, hi = 0, int(planned.max())
+        x = self._run_encoder(src, lengths, want_out=False, stop_after=0, want_x=True)[2]  # the stem; validates src, packs
+        dev = x.device
+        B, Tq, D = x.shape
+        with torch.cuda.device(dev):
+            key_len = encoder_lengths(_to_device(lengths, dev), Tq)
+            if key_len.numel() != B:
+                raise ValueError(f"forward_adaptive: lengths must have {B} entries, got {key_len.numel()}")
+            planned = None if exit_of is None else planned.to(device=dev, dtype=torch.int32)
+            logp = torch.empty((B, Tq, V), dtype=torch.float32, device=dev)
+            taps = torch.empty((B, Tq, D), dtype=torch.float32, device=dev) if want_taps else None
+            scores = torch.full((E, B), float("nan"), dtype=torch.float32, device=dev)
+            chosen = torch.full((B,), hi, dtype=torch.int32, device=dev)
+            idx = torch.arange(B, device=dev)              # original batch position of every row of x
+            alive = torch.ones(B, dtype=torch.bool, device=dev)  # compact=False: the rows of x still in flight
+            n_alive = B
+            for e in range(hi + 1):
+                self._group(self._handle, e, x, key_len)
+                lp = self._head(e, x, torch.empty((x.size(0), Tq, V), dtype=torch.float32, device=dev))
+                st = exit_statistics(lp.unsqueeze(0), key_len)
+                score = {"entropy": st.entropy, "confidence": st.confidence}[criterion][0] if criterion != "greedy_logp" else \
+                    st.greedy_logp[0] / key_len.clamp(min=1).to(torch.float32)
+                if not compact:
+                    score = torch.where(alive, score, torch.full_like(score, float("nan")))  # a NaN never leaves again
+                scores[e].index_copy_(0, idx, score)
+                if e == hi:  # takes everyone left: nothing to route, nothing to read
+                    rows = alive.view(-1, 1, 1)
+                    logp.index_copy_(0, idx, lp if compact else torch.where(rows, lp, logp))
+                    if want_taps:
+                        taps.index_copy_(0, idx, x if compact else torch.where(rows, x, taps))
+                    break
+                if e < lo:
+                    continue
+                if planned is None:
+                    stay, leave, counts = exit_route(score, thr[e], higher)
+                else:
+                    due = planned[idx] == e
+                    stay, leave, counts = exit_route((due if compact else due & alive).to(torch.float32), 0.5, True)
+                n_stay, n_leave = counts.tolist()  # the one host read of this exit
+                if n_leave:
+                    rows = leave[:n_leave].long()
+                    where = idx[rows]
+                    logp[where] = lp[rows]
+                    if want_taps:
+                        taps[where] = x[rows]
+                    chosen[where] = e
+                    n_alive -= n_leave
+                    if n_alive == 0:
+                        break
+                    if compact:
+                        rows = stay[:n_stay].long()
+                        x, key_len, idx = x[rows], key_len[rows], idx[rows]
+                    else:
+                        alive[rows] = False
+        return AdaptiveOutput(logp, chosen, scores, taps)
+
 
 class Early_conformer(_HipEncoderMixin, nn.Module):
     """CTC early-exit Conformer; ``forward(src[B,n_mels,T], lengths[B]) -> [E,B,T',V]`` log-probs."""
@@ -329,6 +435,9 @@ class Splitformer(Early_conformer):
         self._branch = capi.EncoderHandle(capi.EecConfig(d_model, n_head, d_feed_forward, depthwise_kernel_size, 2, 1, features_length,
                                                          dec_voc_size, max_len, capi.ARCH_CONFORMER))
 
+    def forward_adaptive(self, *args, **kwargs):
+        raise NotImplementedError("Splitformer has no adaptive forward: its walk adds the down-sampled branches at the first and last exit")
+
     def _walk(self, x: Tensor, lengths: Tensor, group, head, in_place: bool) -> list:
         """The reference's topology (early_exit.py:299-364) from the stem's output x [B, T', D] on, over the two operations that
         differ between the modes: ``group(which, index, x, key_len) -> x`` runs Conformer group ``index`` of ``self.<which>``,
@@ -424,6 +533,9 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
             for _ in range(n_enc_exits)])
         self._hip_init(d_model, n_head, d_feed_forward, depthwise_kernel_size, n_enc_exits, n_enc_layers,
                        features_length, dec_voc_size, max_len)
+
+    def forward_adaptive(self, *args, **kwargs):
+        raise NotImplementedError("Early_zipformer has no adaptive forward: it has one exit, after the last stack")
 
     def _walk(self, enc: Tensor, lengths: Tensor, group, head):
         """The reference's topology (early_exit.py:174-224) from the stem's output enc [B, T1, D] on, over the two operations that

@@ -284,6 +284,35 @@ int eec_exit_distill_forward(const float* x, const int32_t* frame_len, const int
 int eec_exit_distill_backward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
                               const float* grad_loss, int accumulate, float* dx, void* stream);
 
+/* Adaptive inference: the statistics an early-exit model chooses an utterance's exit by (average frame entropy, average frame
+ * confidence, log-probability of the greedy CTC path), and the routing of a batch by one of them.
+ *   x [E, B, T, V] fp32: logits or log-probs; every row is normalised inside: lp_v = x_v - lse(x), p_v = exp(lp_v)
+ *   frame_len [B] int32 on the device, or NULL for T everywhere; len_b = clamp(frame_len[b], 0, T), n_b = max(len_b, 1)
+ *   stats [3, E, B] fp32:
+ *     stats[0][e][b] = entropy     = (1 / n_b) sum_{t < len_b} -sum_v p_v lp_v     in nats; a term with p_v = 0 is 0
+ *     stats[1][e][b] = confidence  = (1 / n_b) sum_{t < len_b} max_v p_v
+ *     stats[2][e][b] = greedy_logp = sum_{t < len_b} max_v lp_v                     NOT divided by the length
+ * An utterance without frames gives 0 / 0 / 0.  Frames at or past len_b are never read: a NaN there reaches nothing.  A NaN inside
+ * the valid frames reaches the three statistics of that (e, b) and nothing else.  The per-frame terms go to the workspace
+ * (eec_exit_stats_workspace_bytes(E, B, T) bytes of 256-byte aligned device memory; 0 for a non-positive size) and an utterance's
+ * frames are added in index order without atomics: the statistics are bit-reproducible from run to run, and a call on a slice of
+ * the exits or of the batch returns the bits of the whole call.
+ * EEC_ERR_BAD_ARG, with a message, before anything is launched: a null pointer (frame_len may be NULL), a size below 1,
+ * E > EEC_EXIT_STATS_MAX_EXITS, V > 256 or V % 4 != 0 (a row is one float4 per lane), B * T or 3 * E * B above 2^31 - 1.
+ * EEC_ERR_WORKSPACE: a misaligned or short workspace.
+ *
+ * eec_exit_route: row i of score [n] LEAVES when score[i] < threshold (higher_is_better != 0: when score[i] > threshold); a tie
+ * stays, a NaN score never leaves; force_all != 0: every row leaves, whatever it scores.  leave_idx and stay_idx [n] int32 receive
+ * the stable partition of 0 .. n-1 -- the leavers, and the stayers, each in ascending order; only the first counts[1] entries of
+ * leave_idx and the first counts[0] of stay_idx are written -- and counts [2] int32 = {stayers, leavers}.  One launch for any
+ * n >= 1.  EEC_ERR_BAD_ARG: a null pointer, n < 1, a NaN threshold (without force_all). */
+#define EEC_EXIT_STATS_MAX_EXITS 16
+size_t eec_exit_stats_workspace_bytes(int E, int B, int T);
+int eec_exit_stats(const float* x, const int32_t* frame_len, int E, int B, int T, int V, float* stats, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int eec_exit_route(const float* score, int n, float threshold, int higher_is_better, int force_all, int32_t* stay_idx,
+                   int32_t* leave_idx, int32_t* counts, void* stream);
+
 /* CTC prefix beam search: replaces BeamInference.ctc_cuda_predict (util/beam_infer.py:79-80,102-112:
  * torchaudio cuda_ctc_decoder(tokens, nbest=1, beam_size=10, blank_skip_threshold=0.95) on the log-probs of one exit,
  * input length T' for every utterance), batched over n_seq sequences.  That decoder is third-party CUDA code outside the
