@@ -27,13 +27,17 @@
   ``decode_all_exits``: one-pass joint CTC / attention decoding (Watanabe et al. 2017; not in the reference).  Every candidate of
   every step is scored by the decoder AND by the CTC prefix probability of the extended labels (``ctc_prefix_session``,
   csrc/ctc_prefix.hip), EOS by the full-sequence CTC likelihood, so a beam can end; semantics in include/eec.h.
+* ``BeamInference.rescore_batch`` / ``decode_batch_rescoring`` and ``rescoring_ctc_weight=`` on ``decode_batch_adaptive``: two-pass
+  decoding (not in the reference).  The CTC head proposes an N-best list (``ctc_beam_decode(nbest=)``, csrc/ctc_nbest.hip), the
+  attention decoder scores the whole list in one teacher-forced pass (``model.score_hypotheses``, csrc/decoder_score.hip), and the
+  best hypothesis is the one with the highest ``(1 - w) * att + w * ctc``: no autoregressive loop, no key / value cache.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -83,6 +87,15 @@ class DecodedTokens(list):
     """The token ids of one decoded hypothesis -- a plain list to every caller -- that also carry ``text``: the detokenised ids
     after ``apply_lex``."""
     text: Optional[str] = None
+
+
+class RescoredList(NamedTuple):
+    """The N-best list of one two-pass search (``BeamInference.rescore_batch``), best CTC score first: the present hypotheses'
+    ids, their CTC and attention log-probabilities and the joint score the best one was chosen by."""
+    tokens: List[List[int]]
+    ctc: List[float]
+    att: List[float]
+    joint: List[float]
 
 
 def _snapped_texts(token_lists, lexicon, detokenize) -> List[str]:
@@ -290,7 +303,7 @@ class BeamInference:
         return [texts[0]], torch.softmax(scores[0, : n_hyp[0]].double(), dim=0)[0].float()
 
     def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
-                         detokenize=None, lengths: Optional[Tensor] = None) -> List[List["CTCHypothesis"]]:
+                         detokenize=None, lengths: Optional[Tensor] = None, nbest: Optional[int] = None) -> List[List["CTCHypothesis"]]:
         """util/beam_infer.py:102-112: the nbest (= 1) beam-search hypotheses of one exit's log-probs ``emission`` [B, T', V],
         input length T' for every utterance (``lengths`` [B] in encoder frames: the decoder's ``encoder_out_lens``), beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
         hypothesis objects with ``.tokens`` / ``.words`` / ``.score`` like torchaudio's, so the reference's call sites
@@ -298,13 +311,22 @@ class BeamInference:
         the torchaudio decoder takes) is accepted and unused: ids are returned, blank = 0.  With ``lexicon`` (a
         ``lexicon.Lexicon`` or the list ``load_dict`` returns) and ``detokenize`` (ids -> str: the caller's ``sp.decode`` or
         ``int_to_text``) every hypothesis also carries ``.text``, its ``apply_lex``-ed transcript (inference.py:70-71), and
-        ``.words``, that text's words; with either None nothing changes."""
+        ``.words``, that text's words; with either None nothing changes.  ``nbest`` (None: as above, one hypothesis): up to that
+        many hypotheses per utterance, best first, as torchaudio's ``nbest`` -- the beam the same search ends with
+        (``ctc_beam_decode(nbest=)``), so an utterance whose final beam is smaller returns fewer."""
         beam = self._arg(beam_size, "beam_size")
-        tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths)
-        tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
-        hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
+        if nbest is not None:
+            tok, cnt, score, n_hyp = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95,
+                                                                       em_len=lengths, nbest=nbest))
+            hyps = [[CTCHypothesis(tok[b, r, : int(cnt[b, r])].tolist(), [], float(score[b, r])) for r in range(int(n_hyp[b]))]
+                    for b in range(tok.size(0))]
+        else:
+            tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths)
+            tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
+            hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
         if lexicon is not None and detokenize is not None:
-            for (h,), text in zip(hyps, _snapped_texts([h.tokens for (h,) in hyps], lexicon, detokenize)):
+            flat = [h for row in hyps for h in row]
+            for h, text in zip(flat, _snapped_texts([h.tokens for h in flat], lexicon, detokenize)):
                 h.text, h.words = text, text.split(" ")
         return hyps
 
@@ -648,6 +670,101 @@ class BeamInference:
                     ids.text = next(texts)
         return out
 
+    # -- two-pass decoding: the CTC head proposes an N-best list, the attention decoder scores it in one teacher-forced pass ---
+    @torch.no_grad()
+    def rescore_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor], nbest: int,
+                      rescoring_ctc_weight: float, beam_size: Optional[int] = None, SOS_token: Optional[int] = None,
+                      EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30):
+        """Two-pass decoding of exits ``layer_ns`` for every utterance of a padded batch: ``taps`` [E, B, T', D] (or E tensors
+        [B, T', D]) and ``emission`` [E, B, T', V], the exits' encoder outputs and CTC log-probs of one encoder pass
+        (``emission_len`` [B]: their frames, None = T').  First pass: the N-best lists of all E * B emissions in ONE prefix beam
+        search (``ctc_beam_decode(nbest=)``: beam ``beam_size``, blank_skip_threshold 0.95, no lexicon, no language model).
+        Second pass, per exit: ``model.score_hypotheses`` -- every hypothesis of the exit's B lists through the attention decoder
+        at once, no autoregressive loop.  Then ``joint = (1 - w) * att + w * ctc`` with w = ``rescoring_ctc_weight`` in [0, 1]
+        (the convention of the one-pass joint search; a score with weight 0 does not enter), in fp64, and the best hypothesis
+        is the one with the highest joint score, ties to the lower rank; an absent hypothesis is never chosen.  No length
+        normalisation.  Returns ``out[b][e] = (best_tokens, RescoredList)``: the chosen ids (no SOS / EOS), and ``tokens``,
+        ``ctc``, ``att``, ``joint`` of that search's whole list, best CTC score first."""
+        w = float(rescoring_ctc_weight)
+        if not 0.0 <= w <= 1.0:
+            raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
+        if not hasattr(model, "score_hypotheses"):
+            raise ValueError("rescore_batch: the model has no attention decoder to rescore with (full_conformer)")
+        beam = self._arg(beam_size, "beam_size")
+        sos, eos = self._arg(SOS_token, "trg_sos_idx"), self._arg(EOS_token, "trg_eos_idx")
+        E = len(layer_ns)
+        if emission is None or emission.dim() != 4 or emission.size(0) != E or len(taps) != E or taps[0].size(0) != emission.size(1):
+            raise ValueError(f"rescore_batch needs taps [{E}, B, T', D] and emission [{E}, B, T', V] of one encoder pass")
+        B = emission.size(1)
+        dev = emission.device
+        em_len = None if emission_len is None else emission_len.to(dev, torch.int32).reshape(B).repeat(E)
+        groups = [(layer_ns[e], taps[e], torch.arange(e * B, (e + 1) * B, device=dev)) for e in range(E)]
+        found = self._rescore(model, emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, groups, nbest, w, beam, sos, eos, blank,
+                              max_workspace_bytes)
+        return [[found[e * B + b] for e in range(E)] for b in range(B)]
+
+    @staticmethod
+    def _rescore(model, em: Tensor, em_len: Optional[Tensor], groups, nbest: int, w: float, beam: int, sos: int, eos: int, blank: int,
+                 max_workspace_bytes: int):
+        """The two passes over n searches (``em`` [n, T', V], ``em_len`` [n] or None): one N-best launch for all of them, then one
+        ``score_hypotheses`` call per ``(layer_n, enc [m, T', D], rows int64 [m])`` of ``groups`` -- the searches ``rows`` belong to
+        exit ``layer_n``, search ``rows[i]`` has the memory ``enc[i]``; every search is in exactly one group.  Returns the list
+        of ``(best_tokens, RescoredList)`` per search."""
+        dev = em.device
+        tokens, counts, ctc, n_hyp = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest)
+        present = torch.arange(nbest, device=dev).view(1, -1) < n_hyp.view(-1, 1)
+        lengths = torch.where(present, counts, torch.full_like(counts, -1))
+        L = max(int(counts.max()), 1)  # the one host read in front of the second pass: the decoder rows are L + 1 long
+        tokens = tokens[:, :, :L].contiguous()
+        att = torch.empty_like(ctc)
+        for layer_n, enc, rows in groups:
+            att[rows] = model.score_hypotheses(enc, layer_n, tokens[rows], lengths[rows], sos, eos, max_workspace_bytes=max_workspace_bytes)
+        joint = torch.zeros_like(att, dtype=torch.float64)
+        if w < 1.0:
+            joint = joint + (1.0 - w) * att.double()
+        if w > 0.0:
+            joint = joint + w * ctc.double()
+        joint = torch.where(present, joint, torch.full_like(joint, -float("inf")))
+        best = _first_argmax(joint).cpu().tolist()
+        tokens, counts, n_hyp, ctc, att, joint = (t.cpu().tolist() for t in (tokens, counts, n_hyp, ctc, att, joint))
+
+        def one(i):
+            k = n_hyp[i]
+            toks = [tokens[i][r][: counts[i][r]] for r in range(k)]
+            return toks[best[i]], RescoredList(toks, ctc[i][:k], att[i][:k], joint[i][:k])
+        return [one(i) for i in range(em.size(0))]
+
+    @torch.no_grad()
+    def decode_batch_rescoring(self, model, spec: Tensor, valid_len: Tensor, nbest: int = 10, rescoring_ctc_weight: float = 0.5,
+                               beam_size: Optional[int] = None, max_batch: Optional[int] = None, lexicon=None, detokenize=None,
+                               **kw) -> List[List[List[int]]]:
+        """``decode_batch`` by two-pass decoding (``rescore_batch``): ``out[b][e]`` is the hypothesis of exit e's CTC N-best list
+        (``nbest`` of a beam of ``beam_size``, default ``max(args.beam_size, nbest)``) that scores best under ``(1 - w) * attention +
+        w * CTC``.  One encoder pass per chunk of at most ``max_batch`` utterances (taps and log-probs of all exits), one N-best
+        launch and one ``score_hypotheses`` call per exit; no decoder step loop.  ``rescoring_ctc_weight`` defaults to 0.5, WeNet's
+        customary value; it is not tuned here.  The ids carry no SOS / EOS.  ``lexicon`` / ``detokenize`` as in ``decode_batch``."""
+        if beam_size is None:
+            beam_size = max(int(getattr(self.args, "beam_size", nbest)), nbest)
+        E = model._cfg.n_exits
+        exits = list(range(1, E + 1))
+        valid_len = valid_len.reshape(-1)
+        step = max_batch or spec.size(0)
+        out: List[List[List[int]]] = []
+        for c0 in range(0, spec.size(0), step):
+            sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
+            logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
+            found = self.rescore_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), nbest,
+                                       rescoring_ctc_weight, beam_size=beam_size, **kw)
+            out += [[best for best, _ in row] for row in found]
+            del taps, logp
+        if lexicon is not None and detokenize is not None:
+            texts = iter(_snapped_texts([ids for row in out for ids in row], lexicon, detokenize))
+            out = [[DecodedTokens(ids) for ids in row] for row in out]
+            for row in out:
+                for ids in row:
+                    ids.text = next(texts)
+        return out
+
     # -- adaptive inference: every utterance decoded at the one exit it left the encoder at --------------------------------
     @torch.no_grad()
     def ctc_adaptive_predict(self, model, src: Tensor, lengths: Tensor, threshold=None, beam_size: Optional[int] = None, lexicon=None,
@@ -666,20 +783,43 @@ class BeamInference:
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,
                               beam_size: int = 10, joint_ctc_weight: Optional[float] = None, criterion: str = "entropy",
                               min_exit: int = 0, max_exit: Optional[int] = None, exit_of: Optional[Tensor] = None, compact: bool = True,
-                              **kw) -> List[Tuple[List[int], int]]:
+                              rescoring_ctc_weight: Optional[float] = None, nbest: int = 10, **kw) -> List[Tuple[List[int], int]]:
         """``decode_batch`` at ONE exit per utterance: the adaptive encoder pass (``model.forward_adaptive(..., want_taps=True)``) and
         then, for every distinct chosen exit, one ``beam_search_batch`` over that exit's utterances (``joint_search_batch`` with
         ``joint_ctc_weight=``, over the chosen exits' CTC log-probs and the encoder's frame counts) -- where ``decode_batch`` searches
         all E * B pairs.  Returns ``out[b] = (best_tokens, exit)``, the exit 0-based; ``best_tokens`` is what ``decode_batch``
-        returns as ``out[b][exit]``.  Where the batched search declines, the exit's utterances go through ``beam_search`` one by one."""
+        returns as ``out[b][exit]``.  Where the batched search declines, the exit's utterances go through ``beam_search`` one by one.
+        ``rescoring_ctc_weight`` (None: unchanged): two-pass decoding instead (``rescore_batch``) -- ONE N-best launch over the B
+        chosen emissions (``nbest`` of a beam of ``max(beam_size, nbest)``) and one ``score_hypotheses`` call per distinct chosen exit;
+        ``best_tokens`` is then what ``decode_batch_rescoring`` returns as ``out[b][exit]``.  Not together with ``joint_ctc_weight``.
+        There is no step loop, so ``max_length`` is not used, and the only further keywords are ``SOS_token``, ``EOS_token``,
+        ``blank`` and ``max_workspace_bytes`` (``rescore_batch``'s): any other one is a TypeError."""
         if max_length is None:
             max_length = default_max_length(spec.size(2))
         if joint_ctc_weight is not None:
             _check_joint_weight(joint_ctc_weight)
+        if rescoring_ctc_weight is not None:
+            if joint_ctc_weight is not None:
+                raise ValueError("decode_batch_adaptive: rescoring_ctc_weight and joint_ctc_weight are two different searches; give one")
+            w = float(rescoring_ctc_weight)
+            if not 0.0 <= w <= 1.0:
+                raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
+            unknown = sorted(set(kw) - {"SOS_token", "EOS_token", "blank", "max_workspace_bytes"})
+            if unknown:
+                raise TypeError(f"decode_batch_adaptive: with rescoring_ctc_weight the keywords {unknown} have no meaning")
         ad = model.forward_adaptive(spec, valid_len.reshape(-1), threshold, criterion=criterion, min_exit=min_exit, max_exit=max_exit,
                                     exit_of=exit_of, compact=compact, want_taps=True)
         dev = ad.logp.device
         chosen = ad.exit_of.cpu().tolist()
+        if rescoring_ctc_weight is not None:
+            groups = []
+            for e in sorted(set(chosen)):
+                rows = torch.tensor([b for b, c in enumerate(chosen) if c == e], dtype=torch.int64, device=dev)
+                groups.append((e + 1, ad.taps[rows], rows))
+            found = self._rescore(model, ad.logp, encoder_lengths(valid_len.reshape(-1).to(dev), ad.logp.size(1)), groups, nbest, w,
+                                  max(int(beam_size), nbest), self._arg(kw.get("SOS_token"), "trg_sos_idx"),
+                                  self._arg(kw.get("EOS_token"), "trg_eos_idx"), int(kw.get("blank", 0)), int(kw.get("max_workspace_bytes", 2 << 30)))
+            return [(best, e) for (best, _), e in zip(found, chosen)]
         em_len = encoder_lengths(valid_len.reshape(-1).to(dev), ad.logp.size(1)) if joint_ctc_weight is not None else None
         lockstep = _lockstep_kw(kw)
         out: List[Optional[Tuple[List[int], int]]] = [None] * len(chosen)

@@ -92,6 +92,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_exit_stats_workspace_bytes", "eec_exit_stats", "eec_exit_route",
            "eec_ctc_beam_workspace_bytes", "eec_ctc_beam_decode", "eec_ctc_beam_decode_ex",
            "eec_ctc_loss_len", "eec_ctc_loss_forward_len", "eec_ctc_loss_backward_len", "eec_greedy_ctc_len", "eec_ctc_beam_decode_len",
+           "eec_ctc_beam_decode_nbest",
            "eec_ctc_align_workspace_bytes", "eec_ctc_align",
            "eec_ctc_trie_pack_bytes", "eec_ctc_trie_pack", "eec_ctc_lexbeam_workspace_bytes", "eec_ctc_lexbeam_decode",
            "eec_ngram_pack_bytes", "eec_ngram_pack", "eec_ctc_lexbeam_lm_decode",
@@ -106,6 +107,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_train_stem_forward", "eec_train_stem_backward", "eec_train_head_forward", "eec_train_head_backward_scratch_floats",
            "eec_train_head_backward",
            "eec_decoder_last_error", "eec_decoder_workspace_bytes", "eec_decoder_forward",
+           "eec_decoder_score_workspace_bytes", "eec_decoder_score", "eec_hypothesis_score",
            "eec_decoder_train_last_error", "eec_decoder_train_workspace_bytes", "eec_decoder_train_forward", "eec_decoder_train_backward",
            "eec_decoder_step_last_error", "eec_decoder_step_max_beams", "eec_decoder_cache_bytes", "eec_decoder_begin", "eec_decoder_step", "eec_decoder_step_multi", "eec_upload_i64_max", "eec_upload_i64", "eec_beam_select",
            "eec_decoder_batch_cache_bytes", "eec_decoder_batch_begin", "eec_decoder_batch_step",
@@ -182,6 +184,9 @@ def load() -> C.CDLL:
     lib.eec_ctc_beam_decode_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     lib.eec_ctc_beam_decode_len.argtypes = lib.eec_ctc_beam_decode_ex.argtypes[:1] + [C.c_void_p] + lib.eec_ctc_beam_decode_ex.argtypes[1:]
+    # N-best: nbest follows skip_drops_frame, n_hyp follows scores
+    lib.eec_ctc_beam_decode_nbest.argtypes = lib.eec_ctc_beam_decode_len.argtypes[:9] + [C.c_int] + lib.eec_ctc_beam_decode_len.argtypes[9:13] + \
+        [C.c_void_p, C.c_void_p]
     lib.eec_ctc_align_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.eec_ctc_align_workspace_bytes.restype = C.c_size_t
     lib.eec_ctc_align.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -259,6 +264,11 @@ def load() -> C.CDLL:
     lib.eec_decoder_workspace_bytes.restype = C.c_size_t
     lib.eec_decoder_forward.argtypes = [C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eec_decoder_score_workspace_bytes.argtypes = [C.c_int] * 8
+    lib.eec_decoder_score_workspace_bytes.restype = C.c_size_t
+    lib.eec_decoder_score.argtypes = [C.POINTER(EecDecoderParams)] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + \
+        [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eec_hypothesis_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.eec_decoder_train_last_error.restype = C.c_char_p
     lib.eec_decoder_train_workspace_bytes.argtypes = [C.c_int] * 8
     lib.eec_decoder_train_workspace_bytes.restype = C.c_size_t

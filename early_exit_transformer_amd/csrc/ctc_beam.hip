@@ -15,12 +15,23 @@
 // With input lengths (eec_len.h: ctc_len.hip compiles the kernel and its launcher a second time, for eec_ctc_beam_decode_len)
 // sequence s is its first Ts = clamp(em_len[s], 0, T') frames and the back-trace starts at Ts - 1; Ts = 0 leaves the empty
 // prefix: count 0, score 0.  The rows of `tokens` and of the back-pointer table stay T' apart.
+// With EEC_CTC_NBEST (ctc_nbest.hip and ctc_nbest_len.hip compile the kernel and its launcher once more each, for
+// eec_ctc_beam_decode_nbest) the search is the same to the instruction and only the end differs: the final beam is ranked by
+// total log-probability (ties to the lower beam index) and the first min(nbest, live beams) prefixes are traced back, one
+// work-item per hypothesis, into tokens [n_seq][nbest][T'], counts / scores [n_seq][nbest] and n_hyp [n_seq].  Without the
+// macro the two extra parameters and that end are gone before code generation (tools/isa_diff.sh).
 #include <limits.h>
 
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
 #include "eec_len.h"
+
+#ifdef EEC_CTC_NBEST
+#define EEC_NBEST_PARAM(decl) , decl  // after the last parameter / argument: `, decl`
+#else
+#define EEC_NBEST_PARAM(decl)
+#endif
 
 namespace eec {
 
@@ -48,7 +59,8 @@ __device__ __forceinline__ unsigned long long cb_mix(unsigned long long h, int c
 __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __restrict__ logp, EEC_LEN_PARAM(const int* __restrict__ em_len)
                                                               int Tq, int V, int blank, int beam,
                                                               float log_thr, int skip_drops, int* __restrict__ backptr, int* __restrict__ tokens,
-                                                              int* __restrict__ counts, float* __restrict__ scores) {
+                                                              int* __restrict__ counts, float* __restrict__ scores
+                                                              EEC_NBEST_PARAM(int nbest) EEC_NBEST_PARAM(int* __restrict__ n_hyp)) {
   __shared__ CbBeam bufs[2][kCbMaxBeam];
   __shared__ float tot[kCbMaxBeam], stay_pb[kCbMaxBeam], stay_pnb[kCbMaxBeam], row[256];
   __shared__ unsigned merge_mask[kCbMaxBeam];  // bit i of word j: extension of beam i by last[j] spells beam j
@@ -174,6 +186,35 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     __syncthreads();
     cur ^= 1;
   }
+#ifdef EEC_CTC_NBEST
+  // N-best: thread i < live beams ranks prefix i (the number of prefixes ahead of it: a higher total, or the same total and a
+  // lower index) and, if it is among the first nbest, reads its labels off the back-pointers into row `rank` of the sequence
+  if (c < kCbMaxBeam) tot[c] = c < nb_s ? cb_lae(bufs[cur][c].pb, bufs[cur][c].pnb) : -INFINITY;
+  __syncthreads();
+  const int live = nb_s, n_out = min(live, nbest);
+  if (c < live) {
+    const CbBeam* B = bufs[cur];
+    const float s = tot[c];
+    int rank = 0;
+    for (int j = 0; j < live; ++j) rank += (tot[j] > s || (tot[j] == s && j < c)) ? 1 : 0;
+    if (rank < nbest) {
+      int n = B[c].len, k = c;
+      int* out = tokens + ((size_t)seq * nbest + rank) * Tq;
+      counts[(size_t)seq * nbest + rank] = n;
+      scores[(size_t)seq * nbest + rank] = s;
+      for (int t = Ts - 1; t >= 0 && n > 0; --t) {
+        const int e = bp[t * kCbMaxBeam + k];
+        if (e & 0xffff) out[--n] = (e & 0xffff) - 1;
+        k = e >> 16;
+      }
+    }
+  }
+  if (c >= n_out && c < nbest) {  // absent hypotheses
+    counts[(size_t)seq * nbest + c] = 0;
+    scores[(size_t)seq * nbest + c] = -INFINITY;
+  }
+  if (c == 0) n_hyp[seq] = n_out;
+#else
   // best prefix: highest total, ties to the lower beam index; read the labels off the back-pointers
   if (c == 0) {
     const CbBeam* B = bufs[cur];
@@ -196,20 +237,25 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
       k = e >> 16;
     }
   }
+#endif
 }
 
 hipError_t launch_ctc_beam(const float* logp, EEC_LEN_PARAM(const int* em_len) int n_seq, int Tq, int V, int blank, int beam,
-                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores, hipStream_t st) {
+                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores, hipStream_t st
+                           EEC_NBEST_PARAM(int nbest) EEC_NBEST_PARAM(int* n_hyp)) {
   if (V < 1 || V > 256 || beam < 1 || beam > kCbMaxBeam || blank < 0 || blank >= V) return hipErrorInvalidValue;
+#ifdef EEC_CTC_NBEST
+  if (nbest < 1 || nbest > beam) return hipErrorInvalidValue;
+#endif
   const float log_thr = (blank_skip_threshold > 0.f && blank_skip_threshold < 1.f) ? logf(blank_skip_threshold) : INFINITY;
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, EEC_LEN_PARAM(em_len) Tq, V, blank, beam, log_thr, skip_drops,
-                     backptr, tokens, counts, scores);
+                     backptr, tokens, counts, scores EEC_NBEST_PARAM(nbest) EEC_NBEST_PARAM(n_hyp));
   return hipGetLastError();
 }
 
 }  // namespace eec
 
-#ifndef EEC_CTC_LEN
+#if !defined(EEC_CTC_LEN) && !defined(EEC_CTC_NBEST)
 extern "C" {
 
 size_t eec_ctc_beam_workspace_bytes(int n_seq, int Tq) {

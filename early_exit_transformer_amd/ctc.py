@@ -64,13 +64,17 @@ def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) ->
 
 
 def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
-                    skip_drops_frame: bool = False, em_len: Optional[Tensor] = None):
+                    skip_drops_frame: bool = False, em_len: Optional[Tensor] = None, nbest: Optional[int] = None):
     """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
     sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
     ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
     readings of the third-party decoder's skip rule, include/eec.h).  ``em_len`` [N] (None: T' for every sequence, the
     reference's ``encoder_out_lens``): sequence s is its first ``clamp(em_len[s], 0, T')`` frames; none gives count 0, score 0
-    (eec_ctc_beam_decode_len).  Returns (tokens [N, T'] int32, counts [N] int32, scores [N] fp32)."""
+    (eec_ctc_beam_decode_len).  Returns (tokens [N, T'] int32, counts [N] int32, scores [N] fp32).
+    ``nbest`` (None: the call and the three return values above, unchanged): an integer in [1, beam_size] returns the beam the
+    same search ends with instead of its best prefix alone (eec_ctc_beam_decode_nbest) -- (tokens [N, nbest, T'] int32, counts
+    [N, nbest] int32, scores [N, nbest] fp32, n_hyp [N] int32), best first, ties to the lower beam index; hypothesis 0 is the
+    hypothesis the call without ``nbest`` returns, an absent one (rank >= n_hyp) has count 0 and score -inf."""
     if not logp.is_cuda:
         raise RuntimeError("ctc_beam_decode runs on a HIP device only")
     logp = logp.contiguous().float()
@@ -78,10 +82,22 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
     dev = logp.device
     el = _frame_counts("ctc_beam_decode", "em_len", em_len, N, dev)
     lib = capi.load()
+    ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
+    if nbest is not None:
+        nbest = int(nbest)
+        tokens = torch.zeros((N, nbest, Tq), dtype=torch.int32, device=dev)
+        counts = torch.empty((N, nbest), dtype=torch.int32, device=dev)
+        scores = torch.empty((N, nbest), dtype=torch.float32, device=dev)
+        n_hyp = torch.empty((N,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            capi.check(lib.eec_ctc_beam_decode_nbest(logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold,
+                                                     int(bool(skip_drops_frame)), nbest, ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(),
+                                                     scores.data_ptr(), n_hyp.data_ptr(), stream_ptr(dev)),
+                       "eec_ctc_beam_decode_nbest")
+        return tokens, counts, scores, n_hyp
     tokens = torch.empty((N, Tq), dtype=torch.int32, device=dev)
     counts = torch.empty((N,), dtype=torch.int32, device=dev)
     scores = torch.empty((N,), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         capi.check(lib.eec_ctc_beam_decode_len(logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold,
                                                int(bool(skip_drops_frame)), ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(),

@@ -717,6 +717,64 @@ class full_conformer(_HipEncoderMixin, nn.Module):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out
 
+    @torch.no_grad()
+    def score_hypotheses(self, taps_or_enc, layer_n: int, tokens: Tensor, lengths: Tensor, sos: int, eos: int,
+                         max_workspace_bytes: int = 2 << 30) -> Tensor:
+        """Teacher-forced scores of whole hypotheses under exit ``layer_n``'s decoder, in eval mode on the HIP path
+        (eec_decoder_score, csrc/decoder_score.hip): ``tokens`` int [n, R, L] and ``lengths`` int [n, R] are R hypotheses for each
+        of n memories, ``taps_or_enc`` that exit's encoder output [n, T', D] (or the taps of all exits, [E, n, T', D] or a list,
+        of which exit ``layer_n``'s is taken).  Returns fp32 [n, R]: ``log p(y_1 .. y_k, EOS | memory)`` of every hypothesis, the
+        sum over the decoder's log-probs of the row ``SOS, y_1 .. y_k, pad ...`` -- what ``_decoder_`` yields for that row alone,
+        gathered at the targets and summed; a negative length marks an absent hypothesis, which scores -inf and whose tokens
+        are not read.  One decoder per call: callers loop over exits.  The C entry's workspace grows with
+        n * heads * R * (L + 1) * T', so the call is split over memories to keep each part's workspace under
+        ``max_workspace_bytes``; its default, 2 GiB, is a choice, not a measurement.  One memory is the smallest part: ValueError
+        when the workspace of a single memory's R hypotheses is above the bound."""
+        if self.training:
+            raise RuntimeError("score_hypotheses is served in eval mode only")
+        idx = self._exit(layer_n) - 1
+        enc = taps_or_enc[idx] if isinstance(taps_or_enc, (list, tuple)) or taps_or_enc.dim() == 4 else taps_or_enc
+        if not enc.is_cuda:
+            raise RuntimeError("the MI355X decoder runs on a HIP device only (there is no CPU fallback)")
+        cfg = self._cfg
+        dev = enc.device
+        if tokens.dim() != 3 or lengths.shape != tokens.shape[:2] or enc.dim() != 3 or enc.size(0) != tokens.size(0) or enc.size(2) != cfg.d_model:
+            raise ValueError(f"score_hypotheses: tokens [n, R, L], lengths [n, R] and enc [n, T', {cfg.d_model}] expected, got "
+                             f"{tuple(tokens.shape)}, {tuple(lengths.shape)}, {tuple(enc.shape)}")
+        n, R, L = tokens.shape
+        Tq = enc.size(1)
+        out = torch.empty((n, R), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        lib = capi.load()
+        ps, d_ff, V = self._decoder_params(idx, dev)
+        tok = tokens.to(device=dev, dtype=torch.int32).contiguous()
+        ln = lengths.to(device=dev, dtype=torch.int32).contiguous()
+        enc_c = enc.contiguous().float()
+
+        def need(m):
+            return lib.eec_decoder_score_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, m, R, L, Tq)
+        part = n
+        while part > 1 and not 0 < need(part) <= max_workspace_bytes:  # 0: more memories than one call takes
+            part = (part + 1) // 2
+        nbytes = need(part)
+        if nbytes == 0:
+            raise ValueError("score_hypotheses: geometry not served by eec_decoder_score (include/eec.h)")
+        if nbytes > max_workspace_bytes:
+            raise ValueError(f"score_hypotheses: one memory's {R} hypotheses of {L} tokens need a workspace of {nbytes} bytes, above "
+                             f"max_workspace_bytes = {max_workspace_bytes}")
+        with torch.cuda.device(dev):
+            ws, ws_ptr = capi.aligned_ws(nbytes, dev)
+            for i in range(0, n, part):
+                m = min(part, n - i)
+                rc = lib.eec_decoder_score(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), int(sos), int(eos),
+                                           tok[i:i + m].data_ptr(), ln[i:i + m].data_ptr(), enc_c[i:i + m].data_ptr(), m, R, L, Tq,
+                                           int(self.decoder_passes), out[i:i + m].data_ptr(), ws_ptr, nbytes, stream_ptr(dev))
+                capi.check(rc, "eec_decoder_score")
+            for t in (ws, tok, ln, enc_c):
+                t.record_stream(torch.cuda.current_stream(dev))
+        return out
+
     def _steps_served(self, t: Tensor, max_steps: int) -> bool:
         return t.is_cuda and not (self.training and torch.is_grad_enabled()) and 1 <= max_steps <= self.positional_encoder_2.pe.size(0)
 

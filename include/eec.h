@@ -346,6 +346,23 @@ int eec_ctc_beam_decode_len(const float* logp, const int32_t* em_len, int n_seq,
                             float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
                             float* scores, void* stream);
 
+/* N-best from the prefix beam search (csrc/ctc_nbest.hip, ctc_nbest_len.hip: the kernel of eec_ctc_beam_decode_len compiled once
+ * more with a different end).  The search is exactly that of eec_ctc_beam_decode_len -- the same kernel body, candidate ids and
+ * tie rules, em_len (may be NULL), blank_skip_threshold and skip_drops_frame as there -- and the final beam, which that entry
+ * drops after its best prefix, is returned: its prefixes are ranked by total log-probability log_add(p_blank, p_non_blank),
+ * ties to the lower beam index (the order oracle/ctc_beam_ref.py returns with return_beams=True), and the first
+ * n_hyp[s] = min(nbest, live beams) of them are traced back.  1 <= nbest <= beam_size <= 16.
+ *   tokens [n_seq][nbest][T'] int32 (first counts[s][r] valid), counts [n_seq][nbest], scores [n_seq][nbest], n_hyp [n_seq]
+ *   hypothesis 0 is what eec_ctc_beam_decode_len returns; present hypotheses are distinct prefixes with non-increasing scores;
+ *   absent ones (r >= n_hyp[s]) have count 0 and score -inf; Ts = 0 gives one hypothesis, the empty prefix with score 0.
+ *   workspace: eec_ctc_beam_workspace_bytes(n_seq, T') bytes.
+ * The list is the beam the search ends with, not the N most probable label sequences: a prefix pruned on the way is gone.
+ * EEC_ERR_BAD_ARG: a null pointer (em_len may be NULL), n_seq or T' below 1, nbest outside [1, beam_size];
+ * EEC_ERR_UNSUPPORTED: V, beam_size or blank outside the limits above. */
+int eec_ctc_beam_decode_nbest(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                              float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens,
+                              int32_t* counts, float* scores, int32_t* n_hyp, void* stream);
+
 /* Lexicon-constrained CTC beam search with N-best: replaces the decoder behind BeamInference.ctc_predict / ctc_predict_ /
  * beam_predict (util/beam_infer.py:51-65, 85-126): torchaudio ctc_decoder(lexicon, tokens, nbest=N_BEST, log_add=False, beam_size,
  * word_score=w_ins, blank_token="@", sil_token="<pad>") with lm=None, unk_score=-inf, for n_seq sequences in one launch
@@ -836,6 +853,39 @@ size_t eec_decoder_workspace_bytes(int d_model, int n_heads, int d_ff, int vocab
 int eec_decoder_forward(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, int pad_idx, const int64_t* trg,
                         const float* enc, int Bm, int S, int Tq, int enc_shared, int passes, int log_softmax, float* out,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Teacher-forced scoring of whole hypotheses (csrc/decoder_score.hip): the second pass of two-pass decoding ------------------
+ * eec_decoder_score: att_score [n][R] = log p(y, EOS | memory) of R hypotheses for each of n memories under ONE decoder, in one
+ * pass.  hyp_tokens [n][R][L] int32, hyp_len [n][R] int32, enc [n][Tq][D]; S = L + 1 <= p->max_len.  Hypothesis y of length
+ * k = min(hyp_len, L) has the decoder input row SOS, y_1 .. y_k, then pad_idx up to S positions, and
+ *     att_score = sum_{t = 0 .. k} logp[t][target_t],   targets y_1 .. y_k, EOS,
+ * where logp is what eec_decoder_forward(..., log_softmax = 1) yields for that row alone against enc[i]: the same masks (causal;
+ * keys equal to pad_idx masked -- the reference's rule, so a pad_idx INSIDE a hypothesis is masked as a key too), the same
+ * arithmetic (`passes`).  k = 0 scores log p(EOS | SOS).  hyp_len < 0 marks an ABSENT hypothesis: its score is -inf and its
+ * tokens are never read.  Token ids outside [0, vocab) are clamped, as the embedding clamps them.  A term that is not a number
+ * counts as -inf: no NaN is written.
+ * Self-attention and every row-wise GEMM run over the M = n * R * S rows at once; the memory's keys | values are projected once
+ * per memory and the cross-attention is one batched GEMM with batch n * H and R * S query rows; the head's [M][V] logits are
+ * reduced by eec_hypothesis_score's kernel, and no [M][V] log-probs are written.  No allocation, no synchronisation; results are
+ * bit-identical from run to run (no atomics).
+ * All checks come before the first launch.  EEC_ERR_BAD_ARG: a null pointer; `passes` not 1 or 3; d_model outside [1, 1024] or
+ * not divisible by n_heads; vocab outside [1, 1024]; d_ff, R or Tq below 1; n or L below 0; L >= 8192; S > p->max_len;
+ * n * R * n_heads > 65535 or n * R * S > 32 * 65535 (grid dimensions of one call: callers split over memories); pad_idx, sos
+ * or eos outside [0, vocab).  EEC_ERR_WORKSPACE: a workspace that is not 256-byte aligned or shorter than
+ * eec_decoder_score_workspace_bytes (0 for a geometry the entry rejects, and for n = 0).  n = 0 succeeds and launches nothing.
+ * The workspace grows with n * H * R * S * max(S, Tq) (attention probabilities) and M * d_ff floats: callers bound it by
+ * splitting over memories.
+ *
+ * eec_hypothesis_score: the reduction alone, on given logits [n_hyp * (L + 1)][vocab] (16-byte aligned where
+ * vocab is a multiple of 4: such rows are read a float4 at a time): one wave per row takes
+ * the maximum, the log-sum-exp and (x[target] - max) - log(sum); the k + 1 terms of a hypothesis are added in index order in
+ * fp64 and rounded once.  Error of a hypothesis against the exact sum: within (k + 1) * (2^-22 * max|logit| + 4e-7). */
+size_t eec_decoder_score_workspace_bytes(int d_model, int n_heads, int d_ff, int vocab, int n, int R, int L, int Tq);
+int eec_decoder_score(const eec_decoder_params* p, int d_model, int n_heads, int d_ff, int vocab, int pad_idx, int sos, int eos,
+                      const int32_t* hyp_tokens, const int32_t* hyp_len, const float* enc, int n, int R, int L, int Tq, int passes,
+                      float* att_score, void* workspace, size_t workspace_bytes, void* stream);
+int eec_hypothesis_score(const float* logits, const int32_t* hyp_tokens, const int32_t* hyp_len, int n_hyp, int L, int vocab, int eos,
+                         float* att_score, void* stream);
 
 
 /* ---- Training step of the AED decoder (csrc/decoder_train.hip): what autograd does through the decoder half of
