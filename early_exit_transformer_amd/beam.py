@@ -28,7 +28,7 @@
   every step is scored by the decoder AND by the CTC prefix probability of the extended labels (``ctc_prefix_session``,
   csrc/ctc_prefix.hip), EOS by the full-sequence CTC likelihood, so a beam can end; semantics in include/eec.h.
 * ``BeamInference.rescore_batch`` / ``decode_batch_rescoring`` and ``rescoring_ctc_weight=`` on ``decode_batch_adaptive``: two-pass
-  decoding (not in the reference).  The CTC head proposes an N-best list (``ctc_beam_decode(nbest=)``, csrc/ctc_nbest.hip), the
+  decoding (not in the reference).  The CTC head proposes an N-best list (``ctc_beam_decode(nbest=)``, csrc/ctc_beam.hip), the
   attention decoder scores the whole list in one teacher-forced pass (``model.score_hypotheses``, csrc/decoder_score.hip), and the
   best hypothesis is the one with the highest ``(1 - w) * att + w * ctc``: no autoregressive loop, no key / value cache.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts

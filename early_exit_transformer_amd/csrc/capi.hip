@@ -930,14 +930,11 @@ int eec_encoder_profile_read(eec_encoder* enc, double* ms_by_class, long long* l
 
 int eec_greedy_ctc(const float* logp, int n_seq, int Tq, int V, int blank, int32_t* tokens, int32_t* counts,
                    void* stream) {
-  if (!logp || !tokens || !counts || n_seq <= 0 || Tq <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
-  EEC_HIP(launch_greedy_ctc(logp, n_seq, Tq, V, blank, tokens, counts, (hipStream_t)stream));
-  return 0;
+  return eec_greedy_ctc_len(logp, NULL, n_seq, Tq, V, blank, tokens, counts, stream);
 }
 
 int eec_greedy_ctc_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int32_t* tokens,
                        int32_t* counts, void* stream) {
-  if (!em_len) return eec_greedy_ctc(logp, n_seq, Tq, V, blank, tokens, counts, stream);
   if (!logp || !tokens || !counts || n_seq <= 0 || Tq <= 0 || V <= 0) return fail(EEC_ERR_BAD_ARG, "bad argument");
   EEC_HIP(launch_greedy_ctc(logp, em_len, n_seq, Tq, V, blank, tokens, counts, (hipStream_t)stream));
   return 0;

@@ -12,26 +12,20 @@
 // ties go to the lower candidate id.  Prefixes are not copied: every frame records (parent beam, appended label) per
 // survivor in a back-pointer table and the best prefix is read off backwards at the end.  Latency-bound integer / scalar
 // work (T' serial frames): it is sized to keep all E*B sequences of a batch in flight at once, not for the roofline.
-// With input lengths (eec_len.h: ctc_len.hip compiles the kernel and its launcher a second time, for eec_ctc_beam_decode_len)
-// sequence s is its first Ts = clamp(em_len[s], 0, T') frames and the back-trace starts at Ts - 1; Ts = 0 leaves the empty
-// prefix: count 0, score 0.  The rows of `tokens` and of the back-pointer table stay T' apart.
-// With EEC_CTC_NBEST (ctc_nbest.hip and ctc_nbest_len.hip compile the kernel and its launcher once more each, for
-// eec_ctc_beam_decode_nbest) the search is the same to the instruction and only the end differs: the final beam is ranked by
+// Input lengths: `em_len` [n_seq] is a device array of frame counts, or nullptr for T' frames everywhere.  Sequence s is its
+// first Ts = ctc_frames(em_len, s, T') = clamp(em_len[s], 0, T') frames (eec_kernels.h) and the back-trace starts at Ts - 1;
+// Ts = 0 leaves the empty prefix: count 0, score 0.  The rows of `tokens` and of the back-pointer table stay T' apart.
+// One kernel, two ENDS, chosen by `n_hyp` (block-uniform).  nullptr (eec_ctc_beam_decode and its _ex / _len forms): the best
+// prefix, traced back by one work-item.  Otherwise (eec_ctc_beam_decode_nbest) the final beam is ranked by
 // total log-probability (ties to the lower beam index) and the first min(nbest, live beams) prefixes are traced back, one
-// work-item per hypothesis, into tokens [n_seq][nbest][T'], counts / scores [n_seq][nbest] and n_hyp [n_seq].  Without the
-// macro the two extra parameters and that end are gone before code generation (tools/isa_diff.sh).
+// work-item per hypothesis, into tokens [n_seq][nbest][T'], counts / scores [n_seq][nbest] and n_hyp [n_seq].  The first end is
+// NOT the second with nbest = 1: when no prefix is live (nb_s == 0: every candidate of a frame was -inf) the N-best end reports
+// count 0 and n_hyp = 0, the best-prefix end the length of slot 0 and score -inf.
 #include <limits.h>
 
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
-#include "eec_len.h"
-
-#ifdef EEC_CTC_NBEST
-#define EEC_NBEST_PARAM(decl) , decl  // after the last parameter / argument: `, decl`
-#else
-#define EEC_NBEST_PARAM(decl)
-#endif
 
 namespace eec {
 
@@ -56,11 +50,11 @@ __device__ __forceinline__ unsigned long long cb_mix(unsigned long long h, int c
   return z ^ (z >> 31);
 }
 
-__global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __restrict__ logp, EEC_LEN_PARAM(const int* __restrict__ em_len)
+__global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __restrict__ logp, const int* __restrict__ em_len,
                                                               int Tq, int V, int blank, int beam,
                                                               float log_thr, int skip_drops, int* __restrict__ backptr, int* __restrict__ tokens,
-                                                              int* __restrict__ counts, float* __restrict__ scores
-                                                              EEC_NBEST_PARAM(int nbest) EEC_NBEST_PARAM(int* __restrict__ n_hyp)) {
+                                                              int* __restrict__ counts, float* __restrict__ scores,
+                                                              int nbest, int* __restrict__ n_hyp) {
   __shared__ CbBeam bufs[2][kCbMaxBeam];
   __shared__ float tot[kCbMaxBeam], stay_pb[kCbMaxBeam], stay_pnb[kCbMaxBeam], row[256];
   __shared__ unsigned merge_mask[kCbMaxBeam];  // bit i of word j: extension of beam i by last[j] spells beam j
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
   const int seq = blockIdx.x, c = threadIdx.x, lane = c & 63, w = c >> 6;
   const float* lp_seq = logp + (size_t)seq * Tq * V;
   int* bp = backptr + (size_t)seq * Tq * kCbMaxBeam;
-  const int Ts = EEC_LEN_FRAMES(em_len, seq, Tq);
+  const int Ts = ctc_frames(em_len, seq, Tq);
   int cur = 0;
   if (c == 0) {
     bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull};
@@ -186,37 +180,36 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     __syncthreads();
     cur ^= 1;
   }
-#ifdef EEC_CTC_NBEST
-  // N-best: thread i < live beams ranks prefix i (the number of prefixes ahead of it: a higher total, or the same total and a
-  // lower index) and, if it is among the first nbest, reads its labels off the back-pointers into row `rank` of the sequence
-  if (c < kCbMaxBeam) tot[c] = c < nb_s ? cb_lae(bufs[cur][c].pb, bufs[cur][c].pnb) : -INFINITY;
-  __syncthreads();
-  const int live = nb_s, n_out = min(live, nbest);
-  if (c < live) {
-    const CbBeam* B = bufs[cur];
-    const float s = tot[c];
-    int rank = 0;
-    for (int j = 0; j < live; ++j) rank += (tot[j] > s || (tot[j] == s && j < c)) ? 1 : 0;
-    if (rank < nbest) {
-      int n = B[c].len, k = c;
-      int* out = tokens + ((size_t)seq * nbest + rank) * Tq;
-      counts[(size_t)seq * nbest + rank] = n;
-      scores[(size_t)seq * nbest + rank] = s;
-      for (int t = Ts - 1; t >= 0 && n > 0; --t) {
-        const int e = bp[t * kCbMaxBeam + k];
-        if (e & 0xffff) out[--n] = (e & 0xffff) - 1;
-        k = e >> 16;
+  if (n_hyp) {  // block-uniform
+    // N-best: thread i < live beams ranks prefix i (the number of prefixes ahead of it: a higher total, or the same total and a
+    // lower index) and, if it is among the first nbest, reads its labels off the back-pointers into row `rank` of the sequence
+    if (c < kCbMaxBeam) tot[c] = c < nb_s ? cb_lae(bufs[cur][c].pb, bufs[cur][c].pnb) : -INFINITY;
+    __syncthreads();
+    const int live = nb_s, n_out = min(live, nbest);
+    if (c < live) {
+      const CbBeam* B = bufs[cur];
+      const float s = tot[c];
+      int rank = 0;
+      for (int j = 0; j < live; ++j) rank += (tot[j] > s || (tot[j] == s && j < c)) ? 1 : 0;
+      if (rank < nbest) {
+        int n = B[c].len, k = c;
+        int* out = tokens + ((size_t)seq * nbest + rank) * Tq;
+        counts[(size_t)seq * nbest + rank] = n;
+        scores[(size_t)seq * nbest + rank] = s;
+        for (int t = Ts - 1; t >= 0 && n > 0; --t) {
+          const int e = bp[t * kCbMaxBeam + k];
+          if (e & 0xffff) out[--n] = (e & 0xffff) - 1;
+          k = e >> 16;
+        }
       }
     }
-  }
-  if (c >= n_out && c < nbest) {  // absent hypotheses
-    counts[(size_t)seq * nbest + c] = 0;
-    scores[(size_t)seq * nbest + c] = -INFINITY;
-  }
-  if (c == 0) n_hyp[seq] = n_out;
-#else
-  // best prefix: highest total, ties to the lower beam index; read the labels off the back-pointers
-  if (c == 0) {
+    if (c >= n_out && c < nbest) {  // absent hypotheses
+      counts[(size_t)seq * nbest + c] = 0;
+      scores[(size_t)seq * nbest + c] = -INFINITY;
+    }
+    if (c == 0) n_hyp[seq] = n_out;
+  } else if (c == 0) {
+    // best prefix: highest total, ties to the lower beam index; read the labels off the back-pointers
     const CbBeam* B = bufs[cur];
     int best = 0;
     float bs = -INFINITY;
@@ -237,63 +230,68 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
       k = e >> 16;
     }
   }
-#endif
 }
 
-hipError_t launch_ctc_beam(const float* logp, EEC_LEN_PARAM(const int* em_len) int n_seq, int Tq, int V, int blank, int beam,
-                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores, hipStream_t st
-                           EEC_NBEST_PARAM(int nbest) EEC_NBEST_PARAM(int* n_hyp)) {
+// n_hyp != nullptr: the N-best end, into `nbest` rows per sequence; nullptr: the best prefix (nbest is not read)
+hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam, float blank_skip_threshold,
+                           int skip_drops, int* backptr, int* tokens, int* counts, float* scores, int nbest, int* n_hyp, hipStream_t st) {
   if (V < 1 || V > 256 || beam < 1 || beam > kCbMaxBeam || blank < 0 || blank >= V) return hipErrorInvalidValue;
-#ifdef EEC_CTC_NBEST
-  if (nbest < 1 || nbest > beam) return hipErrorInvalidValue;
-#endif
+  if (n_hyp && (nbest < 1 || nbest > beam)) return hipErrorInvalidValue;
   const float log_thr = (blank_skip_threshold > 0.f && blank_skip_threshold < 1.f) ? logf(blank_skip_threshold) : INFINITY;
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, EEC_LEN_PARAM(em_len) Tq, V, blank, beam, log_thr, skip_drops,
-                     backptr, tokens, counts, scores EEC_NBEST_PARAM(nbest) EEC_NBEST_PARAM(n_hyp));
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, em_len, Tq, V, blank, beam, log_thr, skip_drops, backptr, tokens,
+                     counts, scores, nbest, n_hyp);
   return hipGetLastError();
 }
 
 }  // namespace eec
 
-#if !defined(EEC_CTC_LEN) && !defined(EEC_CTC_NBEST)
 extern "C" {
 
 size_t eec_ctc_beam_workspace_bytes(int n_seq, int Tq) {
   return n_seq > 0 && Tq > 0 ? (size_t)n_seq * Tq * eec::kCbMaxBeam * sizeof(int) : 0;
 }
 
+// what the beam entries ask of their arguments; `entry` is the name their messages carry
+static int check_ctc_beam_args(const char* entry, bool have_pointers, int n_seq, int Tq, int V, int blank, int beam_size) {
+  using eech::fail;
+  const std::string name = entry;
+  if (!have_pointers) return fail(EEC_ERR_BAD_ARG, name + ": null argument");
+  if (n_seq <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, name + ": n_seq and Tq must be positive");
+  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V)
+    return fail(EEC_ERR_UNSUPPORTED, name + ": needs 1 <= V <= 256, 1 <= beam_size <= " + std::to_string(eec::kCbMaxBeam) + ", blank in [0, V)");
+  return 0;
+}
+
 int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                         void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream) {
-  return eec_ctc_beam_decode_ex(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, 0, workspace, tokens, counts, scores, stream);
+  return eec_ctc_beam_decode_len(logp, NULL, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, 0, workspace, tokens, counts, scores, stream);
 }
 
 int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                            int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream) {
-  using eech::fail;
-  if (!logp || !workspace || !tokens || !counts || !scores) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: null argument");
-  if (n_seq <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: n_seq and Tq must be positive");
-  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V)
-    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_beam_decode: needs 1 <= V <= 256, 1 <= beam_size <= " + std::to_string(eec::kCbMaxBeam) + ", blank in [0, V)");
-  EEC_HIP(eec::launch_ctc_beam(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens, counts,
-                               scores, (hipStream_t)stream));
-  return 0;
+  return eec_ctc_beam_decode_len(logp, NULL, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame, workspace, tokens, counts,
+                                 scores, stream);
 }
 
 int eec_ctc_beam_decode_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
                             float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
                             float* scores, void* stream) {
-  using eech::fail;
-  if (!em_len)
-    return eec_ctc_beam_decode_ex(logp, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame, workspace, tokens, counts,
-                                  scores, stream);
-  if (!logp || !workspace || !tokens || !counts || !scores) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: null argument");
-  if (n_seq <= 0 || Tq <= 0) return fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode: n_seq and Tq must be positive");
-  if (V < 1 || V > 256 || beam_size < 1 || beam_size > eec::kCbMaxBeam || blank < 0 || blank >= V)
-    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_beam_decode: needs 1 <= V <= 256, 1 <= beam_size <= " + std::to_string(eec::kCbMaxBeam) + ", blank in [0, V)");
-  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace,
-                               tokens, counts, scores, (hipStream_t)stream));
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode", logp && workspace && tokens && counts && scores, n_seq, Tq, V, blank, beam_size)) return rc;
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, 1, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int eec_ctc_beam_decode_nbest(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                              float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens, int32_t* counts,
+                              float* scores, int32_t* n_hyp, void* stream) {
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode_nbest", logp && workspace && tokens && counts && scores && n_hyp, n_seq, Tq, V, blank,
+                                   beam_size))
+    return rc;
+  if (nbest < 1 || nbest > beam_size) return eech::fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode_nbest: needs 1 <= nbest <= beam_size");
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, nbest, n_hyp, (hipStream_t)stream));
   return 0;
 }
 
 }  // extern "C"
-#endif

@@ -213,9 +213,20 @@ hipError_t launch_stem_fold(const float* w1, const float* b1, const float* w2, c
 hipError_t launch_fill_int(int* dst, int n, int v, hipStream_t st);
 hipError_t launch_enc_lengths(const long long* lengths, int B, int Tq, int* enc_len, hipStream_t st);
 
+// Per-sequence frame counts of the CTC decoders (ctc_beam.hip, the greedy kernel of pack.hip): `len` is a device array (em_len
+// [n_seq]) or nullptr, which means Tq frames for every sequence.  Counts are clamped to [0, Tq].
+// (The builtins, not the HIP headers' min / max: with those called here, pack_frags_f8_kernel of pack.hip, which does not use this
+// function, compiled to one more instruction -- a v_min_u32 that is otherwise proved away; tools/isa_kernel_diff.py.)
+__device__ __forceinline__ int ctc_frames(const int* __restrict__ len, int i, int Tq) {
+  return len ? __builtin_elementwise_min(__builtin_elementwise_max(len[i], 0), Tq) : Tq;
+}
+
 // greedy CTC (argmax -> unique_consecutive -> drop blank)
-hipError_t launch_greedy_ctc(const float* logp, int n_seq, int Tq, int V, int blank, int* tokens, int* counts,
+hipError_t launch_greedy_ctc(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int* tokens, int* counts,
                              hipStream_t st);
+// CTC prefix beam search (ctc_beam.hip); n_hyp != nullptr: N-best, `nbest` rows per sequence; nullptr: the best prefix
+hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam, float blank_skip_threshold,
+                           int skip_drops, int* backptr, int* tokens, int* counts, float* scores, int nbest, int* n_hyp, hipStream_t st);
 
 // batched CTC forward: per-lattice negative log-likelihoods nll[E*B] and per-exit batch-mean losses out[E];
 // astore (optional, ctc_store_floats() floats): the scaled alphas of every step, for launch_ctc_backward
@@ -226,7 +237,7 @@ size_t ctc_store_floats(int E, int B, int Tq, int S);
 hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, int E, int B, int Tq,
                                int V, int S, int blank, const float* nll, float* astore, const float* grad_loss, float* dlogp,
                                hipStream_t st);
-// the same three with per-utterance frame counts input_len [B] (device; clamped to [0, Tq]); greedy / beam: em_len [n_seq]
+// the same two with per-utterance frame counts input_len [B] (device; clamped to [0, Tq]): ctc.hip compiled a second time (eec_len.h)
 int ctc_states_per_lane(int S);  // 2, 4 or 8 states per lane; 0: the target width S does not fit
 hipError_t launch_ctc_reduce(const float* nll, const long long* target_len, int E, int B, float* out, hipStream_t st);
 hipError_t launch_ctc_loss(const float* logp, const long long* targets, const long long* target_len, const int* input_len, int E,
@@ -234,11 +245,6 @@ hipError_t launch_ctc_loss(const float* logp, const long long* targets, const lo
 hipError_t launch_ctc_backward(const float* logp, const long long* targets, const long long* target_len, const int* input_len, int E,
                                int B, int Tq, int V, int S, int blank, const float* nll, float* astore, const float* grad_loss,
                                float* dlogp, hipStream_t st);
-hipError_t launch_greedy_ctc(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int* tokens, int* counts,
-                             hipStream_t st);
-hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam,
-                           float blank_skip_threshold, int skip_drops, int* backptr, int* tokens, int* counts, float* scores,
-                           hipStream_t st);
 hipError_t launch_logsoftmax_backward(const float* logp, const float* g, int M, int V, float* dlogits, hipStream_t st);
 
 // self-distillation between exits (distill.hip; include/eec.h states the loss).  `teacher` is a HOST array the caller has validated.

@@ -1,10 +1,10 @@
-// Per-sequence input lengths as a compile-time switch.  ctc.hip, ctc_beam.hip and the greedy decoder of pack.hip assume the
-// reference's convention, T' frames for every sequence; ctc_len.hip compiles the three a second time with EEC_CTC_LEN defined, and
-// then every kernel and launcher among them takes one more argument, a device array of frame counts (`input_len` [B], shared by
-// the E exits of an utterance; `em_len` [n_seq] for the decoders), and walks clamp(count, 0, T') frames instead of T'.  The extra
-// parameter makes the second set overloads of the first: both live in one library.  Without the macro the parameter, the clamp
-// and every branch on kLen are gone before code generation, so the entries without lengths keep their device code to the byte
-// (tools/isa_diff.sh).  Strides, workspaces and output layouts stay on T' in both.
+// Per-utterance input lengths of the CTC loss as a compile-time switch.  ctc.hip assumes the reference's convention, T' frames for
+// every utterance; ctc_len.hip compiles it a second time with EEC_CTC_LEN defined, and then every kernel and launcher in it takes one
+// more argument, a device array of frame counts (`input_len` [B], shared by the E exits of an utterance), and walks clamp(count, 0,
+// T') frames instead of T'.  The extra parameter makes the second set overloads of the first: both live in one library.  Without the
+// macro the parameter, the clamp and every branch on kLen are gone before code generation.  Strides, workspaces and output layouts
+// stay on T' in both.  (The decoders take a nullable runtime pointer instead: ctc_frames, eec_kernels.h.  The loss keeps the switch
+// because its 8-states-per-lane loss kernel measured 0.5 % slower with the pointer than this compilation of it: DESIGN.md.)
 #pragma once
 
 namespace eec {

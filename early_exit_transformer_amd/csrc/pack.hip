@@ -4,11 +4,8 @@
 #include <utility>
 
 #include "eec_kernels.h"
-#include "eec_len.h"
 
 namespace eec {
-
-#ifndef EEC_CTC_LEN  // ctc_len.hip compiles the greedy decoder at the end of this file a second time (eec_len.h); the rest once
 
 hipError_t ensure_max_lds(const void* kernel, int bytes) {
   static std::mutex mu;
@@ -262,18 +259,17 @@ hipError_t launch_fill_int(int* dst, int n, int v, hipStream_t st) {
   return hipGetLastError();
 }
 
-#endif  // EEC_CTC_LEN
-
 // Greedy CTC (reference util/beam_infer.py:9-24): argmax over labels, collapse repeats, drop blank.
 // One wave per sequence; frames are walked 64 at a time, kept tokens compacted with a ballot.
 // Ties in the argmax resolve to the lowest label index (torch.argmax on CPU).
-// With input lengths (eec_len.h) sequence s is its first Ts = clamp(em_len[s], 0, T') frames; the rows of `tokens` stay T' apart.
-__global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict__ logp, EEC_LEN_PARAM(const int* __restrict__ em_len)
+// Sequence s is its first Ts = ctc_frames(em_len, s, T') frames (eec_kernels.h: clamp(em_len[s], 0, T'), or T' for em_len =
+// nullptr, which is what eec_greedy_ctc passes); the rows of `tokens` stay T' apart.
+__global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict__ logp, const int* __restrict__ em_len,
                                                         int Tq, int V, int blank, int* __restrict__ tokens, int* __restrict__ counts) {
   const int seq = blockIdx.x, lane = threadIdx.x;
   const float* base = logp + (size_t)seq * Tq * V;
   int* out = tokens + (size_t)seq * Tq;
-  const int Ts = EEC_LEN_FRAMES(em_len, seq, Tq);
+  const int Ts = ctc_frames(em_len, seq, Tq);
   int n_out = 0, prev_last = -1;
   for (int t0 = 0; t0 < Ts; t0 += 64) {
     const int t = t0 + lane;
@@ -303,9 +299,9 @@ __global__ __launch_bounds__(64) void greedy_ctc_kernel(const float* __restrict_
   if (lane == 0) counts[seq] = n_out;
 }
 
-hipError_t launch_greedy_ctc(const float* logp, EEC_LEN_PARAM(const int* em_len) int n_seq, int Tq, int V, int blank, int* tokens,
+hipError_t launch_greedy_ctc(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int* tokens,
                              int* counts, hipStream_t st) {
-  hipLaunchKernelGGL(greedy_ctc_kernel, dim3(n_seq), dim3(64), 0, st, logp, EEC_LEN_PARAM(em_len) Tq, V, blank, tokens, counts);
+  hipLaunchKernelGGL(greedy_ctc_kernel, dim3(n_seq), dim3(64), 0, st, logp, em_len, Tq, V, blank, tokens, counts);
   return hipGetLastError();
 }
 

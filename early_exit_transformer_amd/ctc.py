@@ -161,7 +161,7 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     ws_bytes = (lib.eec_ctc_lexbeam_wide_workspace_bytes if wide else lib.eec_ctc_lexbeam_workspace_bytes)(n, Tq, beam_size)
     ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        args = (logp.data_ptr(), n, Tq, V, None if em_len is None else em_len.data_ptr(), trie.on(dev).data_ptr(), trie.blank, trie.sil,
+        args = (logp.data_ptr(), n, Tq, V, _ptr(em_len), trie.on(dev).data_ptr(), trie.blank, trie.sil,
                 int(beam_size), int(nbest), float(word_score), float(sil_score), float(beam_threshold), max_words, words.data_ptr(),
                 word_count.data_ptr(), tokens.data_ptr(), token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
                 ws.data_ptr(), ws_bytes, stream_ptr(dev))
@@ -220,11 +220,10 @@ def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em
     trellis = torch.empty((H, Tq + 1, S + 1), dtype=torch.float32, device=dev) if want_trellis else None
     lib = capi.load()
     ws = torch.empty((lib.eec_ctc_align_workspace_bytes(H, Tq, S),), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_align(logp.data_ptr(), n_em, Tq, V, ptr(em_len), tokens.data_ptr(), tok_len.data_ptr(), ptr(em_index), H, S,
+        capi.check(lib.eec_ctc_align(logp.data_ptr(), n_em, Tq, V, _ptr(em_len), tokens.data_ptr(), tok_len.data_ptr(), _ptr(em_index), H, S,
                                      int(blank), point_token.data_ptr(), point_score.data_ptr(), path_score.data_ptr(),
-                                     final_score.data_ptr(), status.data_ptr(), ptr(trellis), ws.data_ptr() if ws.numel() else None,
+                                     final_score.data_ptr(), status.data_ptr(), _ptr(trellis), ws.data_ptr() if ws.numel() else None,
                                      stream_ptr(dev)), "eec_ctc_align")
     return point_token, point_score, path_score, final_score, status, trellis
 
@@ -299,7 +298,7 @@ class CtcPrefixSession:
             capi.check(lib.eec_ctc_prefix_begin(*self._head(), self._state[1], self.nbytes, stream_ptr(self.dev)), "eec_ctc_prefix_begin")
 
     def _head(self):
-        return (self.emission.data_ptr(), None if self.em_len is None else self.em_len.data_ptr(), self.n, self.Tq, self.V, self.blank, self.R_max)
+        return (self.emission.data_ptr(), _ptr(self.em_len), self.n, self.Tq, self.V, self.blank, self.R_max)
 
     def step(self, att: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
         n, V = self.n, self.V
@@ -321,7 +320,7 @@ class CtcPrefixSession:
                 tok = last.to(torch.int64).contiguous()
                 par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
                 local = torch.empty((n, R, V), dtype=torch.float32, device=dev)
-                capi.check(capi.load().eec_ctc_prefix_step(*self._head(), None if par is None else par.data_ptr(), tok.data_ptr(), R, self.rows, self.s,
+                capi.check(capi.load().eec_ctc_prefix_step(*self._head(), _ptr(par), tok.data_ptr(), R, self.rows, self.s,
                                                            att.data_ptr(), self.weight, self.eos, self.pad, self.min_length, local.data_ptr(),
                                                            self._state[1], self.nbytes, stream_ptr(dev)), "eec_ctc_prefix_step")
                 stream = torch.cuda.current_stream(dev)
@@ -436,9 +435,34 @@ def ctc_prefix_session(emission: Tensor, em_len: Optional[Tensor], R_max: int, w
     return CtcPrefixSession(emission, em_len, R_max, weight, eos, pad, blank=blank, min_length=min_length)
 
 
+def _ctc_forward(x: Tensor, tg: Tensor, tl: Tensor, blank: int, il: Optional[Tensor]):
+    """The training forward (eec_ctc_loss_forward_len): (losses [E], nll [E * B], the backward workspace and its aligned pointer)."""
+    E, B, Tq, V = x.shape
+    dev = x.device
+    lib = capi.load()
+    nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
+    out = torch.empty((E,), dtype=torch.float32, device=dev)
+    ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.eec_ctc_loss_forward_len(x.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
+                                                blank, nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+    return out, nll, ws, ws_ptr
+
+
+def _ctc_backward(x: Tensor, tg: Tensor, tl: Tensor, blank: int, il: Optional[Tensor], nll: Tensor, ws_ptr: int, grad_loss: Tensor,
+                  dlogp: Tensor) -> None:
+    """eec_ctc_loss_backward_len into ``dlogp`` (every element is written); consumes the workspace of ``_ctc_forward``."""
+    E, B, Tq, V = x.shape
+    dev = x.device
+    g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        capi.check(capi.load().eec_ctc_loss_backward_len(x.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
+                                                         tg.size(1), blank, nll.data_ptr(), ws_ptr, g.data_ptr(),
+                                                         dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
+
+
 class _ExitCtcLossFn(torch.autograd.Function):
-    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (eec_ctc_loss_forward_len / _backward_len; no
-    ``input_len``: eec_ctc_loss_forward / _backward): what autograd computes through the reference's loop of E nn.CTCLoss calls
+    """Per-exit CTC losses [E] with their gradient with respect to the log-probs (``_ctc_forward`` / ``_ctc_backward``): what autograd computes through the reference's loop of E nn.CTCLoss calls
     (train.py:60-68)."""
 
     @staticmethod
@@ -447,14 +471,7 @@ class _ExitCtcLossFn(torch.autograd.Function):
         if V > 256 or V % 4:
             raise ValueError(f"exit_ctc_losses with a gradient needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
                              "the CTC gradient kernel holds a vocabulary row in one wave")
-        dev = enc_out.device
-        lib = capi.load()
-        nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
-        out = torch.empty((E,), dtype=torch.float32, device=dev)
-        ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
-        with torch.cuda.device(dev):
-            capi.check(lib.eec_ctc_loss_forward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
-                                                    blank, nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+        out, nll, ws, ws_ptr = _ctc_forward(enc_out, tg, tl, blank, il)
         ctx.save_for_backward(enc_out, tg, tl, nll, ws, il)
         ctx.blank, ctx.ws_ptr = blank, ws_ptr
         return out
@@ -465,14 +482,8 @@ class _ExitCtcLossFn(torch.autograd.Function):
         if getattr(ctx, "used", False):
             raise RuntimeError("exit_ctc_losses: backward through the same forward twice (its workspace is consumed)")
         ctx.used = True
-        E, B, Tq, V = enc_out.shape
-        dev = enc_out.device
-        g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
         dlogp = torch.empty_like(enc_out)
-        with torch.cuda.device(dev):
-            capi.check(capi.load().eec_ctc_loss_backward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
-                                                             tg.size(1), ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(),
-                                                             dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
+        _ctc_backward(enc_out, tg, tl, ctx.blank, il, nll, ctx.ws_ptr, grad_out, dlogp)
         return dlogp, None, None, None, None
 
 
@@ -548,7 +559,7 @@ def _distill_forward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int,
     nbytes = lib.eec_exit_distill_workspace_bytes(E, B, Tq)
     ws, ws_ptr = capi.aligned_ws(nbytes, dev)
     with torch.cuda.device(dev):
-        capi.check(lib.eec_exit_distill_forward(x.data_ptr(), None if frame_len is None else frame_len.data_ptr(), (C.c_int32 * E)(*teacher),
+        capi.check(lib.eec_exit_distill_forward(x.data_ptr(), _ptr(frame_len), (C.c_int32 * E)(*teacher),
                                                 E, B, Tq, V, tau, kl.data_ptr(), out.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)),
                    "eec_exit_distill_forward")
     return out
@@ -560,7 +571,7 @@ def _distill_backward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int
     dev = x.device
     g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
     with torch.cuda.device(dev):
-        capi.check(capi.load().eec_exit_distill_backward(x.data_ptr(), None if frame_len is None else frame_len.data_ptr(),
+        capi.check(capi.load().eec_exit_distill_backward(x.data_ptr(), _ptr(frame_len),
                                                          (C.c_int32 * E)(*teacher), E, B, Tq, V, tau, g.data_ptr(), int(accumulate),
                                                          dx.data_ptr(), stream_ptr(dev)), "eec_exit_distill_backward")
 
@@ -740,15 +751,7 @@ class _ExitTrainingFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc_out, tg, tl, blank, frame_len, teacher, tau, il=None):
-        E, B, Tq, V = enc_out.shape
-        dev = enc_out.device
-        lib = capi.load()
-        nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
-        ctc = torch.empty((E,), dtype=torch.float32, device=dev)
-        ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
-        with torch.cuda.device(dev):
-            capi.check(lib.eec_ctc_loss_forward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
-                                                    blank, nll.data_ptr(), ctc.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+        ctc, nll, ws, ws_ptr = _ctc_forward(enc_out, tg, tl, blank, il)
         kd = _distill_forward(enc_out, frame_len, teacher, tau)
         ctx.set_materialize_grads(False)  # a loss that uses one of the two outputs only: None for the other, and its launch is skipped
         ctx.save_for_backward(enc_out, tg, tl, nll, ws, frame_len, il)
@@ -761,15 +764,9 @@ class _ExitTrainingFn(torch.autograd.Function):
         if getattr(ctx, "used", False):
             raise RuntimeError("exit_training_losses: backward through the same forward twice (its workspace is consumed)")
         ctx.used = True
-        E, B, Tq, V = enc_out.shape
-        dev = enc_out.device
         dlogp = torch.empty_like(enc_out)
         if grad_ctc is not None:
-            g = grad_ctc.to(device=dev, dtype=torch.float32).contiguous()
-            with torch.cuda.device(dev):
-                capi.check(capi.load().eec_ctc_loss_backward_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
-                                                                 tg.size(1), ctx.blank, nll.data_ptr(), ctx.ws_ptr, g.data_ptr(),
-                                                                 dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
+            _ctc_backward(enc_out, tg, tl, ctx.blank, il, nll, ctx.ws_ptr, grad_ctc, dlogp)
         if grad_kd is not None:
             _distill_backward(enc_out, frame_len, ctx.teacher, ctx.tau, grad_kd, grad_ctc is not None, dlogp)
         elif grad_ctc is None:

@@ -336,8 +336,8 @@ int eec_ctc_beam_decode_ex(const float* logp, int n_seq, int Tq, int V, int blan
 /* The greedy decoder and the prefix beam search with per-sequence input lengths (torchaudio's cuda_ctc_decoder takes them as
  * `encoder_out_lens`; the reference fills them with T': util/beam_infer.py:106-107):
  *   em_len [n_seq] int32 on the device, clamped: sequence s is its first Ts = clamp(em_len[s], 0, T') frames, exactly as if
- *       logp[s, :Ts] had been decoded alone; frames at or past Ts are never read.  NULL: T' for every sequence -- the call IS
- *       eec_greedy_ctc / eec_ctc_beam_decode_ex, launch for launch.
+ *       logp[s, :Ts] had been decoded alone; frames at or past Ts are never read.  NULL: T' for every sequence -- what
+ *       eec_greedy_ctc / eec_ctc_beam_decode / eec_ctc_beam_decode_ex pass: they are these with NULL.
  * Ts = 0 gives counts[s] = 0, and scores[s] = 0 (the empty prefix, log 1).  The rows of `tokens` stay T' apart and the workspace
  * is still eec_ctc_beam_workspace_bytes(n_seq, T') bytes.  skip_drops_frame as in eec_ctc_beam_decode_ex; errors as the entries above. */
 int eec_greedy_ctc_len(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int32_t* tokens,
@@ -346,8 +346,8 @@ int eec_ctc_beam_decode_len(const float* logp, const int32_t* em_len, int n_seq,
                             float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
                             float* scores, void* stream);
 
-/* N-best from the prefix beam search (csrc/ctc_nbest.hip, ctc_nbest_len.hip: the kernel of eec_ctc_beam_decode_len compiled once
- * more with a different end).  The search is exactly that of eec_ctc_beam_decode_len -- the same kernel body, candidate ids and
+/* N-best from the prefix beam search (csrc/ctc_beam.hip: the kernel of eec_ctc_beam_decode_len, which has a second end for this
+ * entry).  The search is exactly that of eec_ctc_beam_decode_len -- the same kernel body, candidate ids and
  * tie rules, em_len (may be NULL), blank_skip_threshold and skip_drops_frame as there -- and the final beam, which that entry
  * drops after its best prefix, is returned: its prefixes are ranked by total log-probability log_add(p_blank, p_non_blank),
  * ties to the lower beam index (the order oracle/ctc_beam_ref.py returns with return_beams=True), and the first

@@ -1,6 +1,7 @@
 """GPU tests of per-utterance input lengths in the CTC family: the loss and its gradient (csrc/ctc.hip compiled with lengths by
-csrc/ctc_len.hip: eec_ctc_loss_len, eec_ctc_loss_forward_len / _backward_len), the greedy decoder (eec_greedy_ctc_len) and the
-prefix beam search (eec_ctc_beam_decode_len).
+csrc/ctc_len.hip: eec_ctc_loss_len, eec_ctc_loss_forward_len / _backward_len), the greedy decoder (csrc/pack.hip:
+eec_greedy_ctc_len) and the prefix beam search (csrc/ctc_beam.hip: eec_ctc_beam_decode_len, eec_ctc_beam_decode_nbest), whose
+kernels serve the calls without lengths too.
 
 Judge of the loss and gradient: torch's CPU nn.CTCLoss(blank, 'mean', zero_infinity=True) in fp64 with the real input_lengths,
 per exit (ctc_len_cases.ref_ctc); of the decoders: the oracle's greedy decode and oracle/ctc_beam_ref.py on ``logp[s, :len_s]``.
@@ -173,8 +174,8 @@ def test_gradient_buffer_is_written_in_full():
 
 
 def test_without_lengths_nothing_changes():
-    """input_len=None is the existing call bit for bit; lengths all T' (and beyond: clamped) stay within the fp64 bounds -- whether
-    they are bit-identical to None is printed, not required."""
+    """input_len=None is the existing call bit for bit; lengths all T' (and beyond: clamped) stay within the fp64 bounds and are
+    bit-identical to None -- the loss, the training forward's loss and the gradient: the same arithmetic over the same Tb."""
     lp, tgt, tl, _ = L.ragged_case(5.0, 4)
     with torch.no_grad():
         base0 = exit_ctc_losses(lp.cuda(), tgt, tl).cpu()
@@ -187,8 +188,11 @@ def test_without_lengths_nothing_changes():
     assert torch.equal(gn.view(torch.int32), x.grad.cpu().view(torch.int32))
     for il in (torch.full((6,), 64), torch.tensor([64, 65, 1000, 64, 2 ** 31 - 1, 64]), torch.full((6,), 64, dtype=torch.int32).cuda()):
         got0, got1, g = check_against_fp64("all T'", lp, tgt, tl, il)
-        print(f"[ctc len all T'] bit-identical to None: loss {torch.equal(got0.float(), base0)} / {torch.equal(got1.float(), none1)}, "
-              f"gradient {torch.equal(g.float(), gn)}")
+        same = (torch.equal(got0.float(), base0), torch.equal(got1.float(), none1), torch.equal(g.float(), gn))
+        print(f"[ctc len all T'] bit-identical to None: loss {same[0]} / {same[1]}, gradient {same[2]}")
+        assert torch.equal(got0.float().view(torch.int32), base0.view(torch.int32)), il
+        assert torch.equal(got1.float().view(torch.int32), none1.view(torch.int32)), il
+        assert torch.equal(g.float().view(torch.int32), gn.view(torch.int32)), il
     # negative lengths clamp to 0
     assert hip_losses(lp, tgt, torch.zeros(6, dtype=torch.long), torch.tensor([-1, -5, 0, -2 ** 31, -1, 0])).tolist() == [0.0, 0.0]
 
@@ -275,6 +279,23 @@ def test_decoders_with_lengths_equal_the_oracle_on_the_slices(N, T, V, beam, sca
         for d, (tok, sc) in zip((False, True), clean):
             tok2, sc2 = run_beam(dirty, lens, beam, drop=d)
             assert tok2 == tok and torch.equal(sc2.view(torch.int32), sc.view(torch.int32)), (kind, d)
+
+
+@pytest.mark.parametrize("N,T,V,beam,scale", sorted(C.BEAM_CASES, key=lambda c: c[0] * c[1] * c[2])[:2])
+def test_decoders_with_lengths_all_T_equal_the_calls_without(N, T, V, beam, scale):
+    """em_len all T' against em_len=None, at the smallest entry of BEAM_CASES (beam 1) and at the next (beam 16, where the N-best
+    end has a beam to rank): greedy, the beam search and its N-best form with nbest = beam give the same counts, scores and n_hyp
+    (torch.equal) and the same tokens up to each count.  Both calls run one kernel with the same Ts."""
+    logp, full = C.beam_logp(N, T, V, scale).cuda(), torch.full((N,), T)
+    (tok0, cnt0), (tok1, cnt1) = greedy_ctc(logp, 0, em_len=None), greedy_ctc(logp, 0, em_len=full)
+    live = torch.arange(T, device="cuda") < cnt0.unsqueeze(-1)
+    assert torch.equal(cnt0, cnt1) and torch.equal(tok0[live], tok1[live])
+    for nbest in (None, beam):
+        a, b = (ctc_beam_decode(logp, beam_size=beam, em_len=el, nbest=nbest) for el in (None, full))
+        assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]), nbest
+        live = torch.arange(T, device="cuda") < a[1].unsqueeze(-1)
+        assert torch.equal(a[0][live], b[0][live]), nbest
+        assert nbest is None or (torch.equal(a[3], b[3]) and int(a[3].min()) >= 1), nbest
 
 
 def test_decoder_length_edges():

@@ -1,5 +1,5 @@
 """GPU tests of two-pass decoding (run with -m gpu on an MI355X): the N-best end of the CTC prefix beam search
-(csrc/ctc_nbest.hip) against the existing entry, the oracle's final beam and a brute-force enumeration; the hypothesis scoring
+(csrc/ctc_beam.hip) against the existing entry, the oracle's final beam and a brute-force enumeration; the hypothesis scoring
 kernel against its fp64 definition; eec_decoder_score against eec_decoder_forward on every hypothesis alone and against the
 model's own modules on the CPU; and the decoding mode against the fp64 mix and pick of tests/rescore_cases.py."""
 import sys

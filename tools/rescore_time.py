@@ -1,4 +1,4 @@
-"""Same-process timing of two-pass decoding (BeamInference.decode_batch_rescoring: CTC N-best, csrc/ctc_nbest.hip, rescored by the
+"""Same-process timing of two-pass decoding (BeamInference.decode_batch_rescoring: CTC N-best, csrc/ctc_beam.hip, rescored by the
 attention decoder in one teacher-forced pass, csrc/decoder_score.hip) beside the autoregressive searches it stands next to, at
 the bench's AED geometry: full_conformer (6 exits x 2 encoder layers, 6 decoder layers per exit, d_model 256, d_ff 2048, vocab
 256), B = 64, T = 1027 mel frames (T' = 256 CTC frames), beam 10, nbest 10.
