@@ -3,10 +3,16 @@
 // id is (2 c + w) * 64 + i; nothing else of the statement differs, so for beams of 16 or less the results are those of the narrow
 // entries bit for bit.  tests/lexbeam_wide_cases.py is the plain-Python statement and the judge.  Out of scope: beams over 64.
 //
+// This file holds the wide strategy alone: where the merged candidates live and how the survivors are picked.  Everything that is
+// the narrow kernel's statement too is called from eec_lexbeam.h -- lb_context and lb_start before the first frame, lb_fill_slots,
+// the candidate rules (lb_expand), a survivor's entry and back-pointer (lb_survive), the epilogue (lb_epilogue), log_add's one
+// out-of-line wrapper -- and the host path (the argument checks, the choice of the instantiation, eec_ctc_lexbeam_wide_decode
+// itself) is lb_decode in ctc_lexbeam.hip, which reaches the kernels here through lexbeam_wide_launch.
+//
 // One 256-thread workgroup per sequence, thread c owns frame label c, as in the narrow kernel: candidates that can merge share their
 // label, so every merge is still local to one thread.  What changes is where candidates live and how survivors are picked.  Per frame:
-//   * the child-lookup byte table slot[i][label] is built as in the narrow kernel (64 rows);
-//   * thread c walks the beam in rank order and OFFERS each live candidate to a list of merged candidates ("groups") in LDS.  A group
+//   * the child-lookup byte table slot[i][label] is built by the narrow kernel's lb_fill_slots (64 rows here);
+//   * thread c walks the beam in rank order and OFFERS each live candidate lb_expand returns to a list of merged candidates ("groups") in LDS.  A group
 //     is found through an open-addressing hash table on (c, node, history): a slot holds (c, list index), claimed with an LDS integer
 //     compare-and-swap; only thread c ever inserts or matches keys of label c, so the arrival order of other threads decides where a
 //     group sits, never what it holds.  A thread generates its candidates in ascending id order (the one w = 0 candidate that can
@@ -20,11 +26,11 @@
 //   * selection is an MSB-first radix select (8 bits a round, an LDS histogram with integer atomics) on the 48-bit key
 //     (score as an ordered integer, -0 as +0; 0xffff - id): (score descending, id ascending) is a total order and ids are unique, so
 //     exactly min(beam, groups) keys lie at or above the cut.  The survivors rank themselves by counting, the best one gives the beam
-//     threshold (score >= best - beam_threshold stays), and each builds its beam entry and back-pointer from its id.
-// The epilogue is the narrow kernel's (eec_lexbeam_epilogue.inc).
+//     threshold (score >= best - beam_threshold stays), and each works out from its id where it stands and hands that to lb_survive.
+// The epilogue is the narrow kernel's (lb_epilogue).
 //
-// Resources (tools/kernel_resources.py on build/ctc_lexbeam_wide.o, gfx950): 62 VGPRs (65 with smearing), 106 SGPRs, no scratch, no
-// vector spills (45 to 80 scalars parked in VGPR lanes); 50 736 B of LDS without a model, 50 992 B with one, 52 016 B with smearing,
+// Resources (tools/kernel_resources.py on build/ctc_lexbeam_wide.o, gfx950): 63 VGPRs (69 with the model, 65 with smearing), 106
+// SGPRs, no scratch, no vector spills (42 to 84 scalars parked in VGPR lanes); 50 736 B of LDS without a model, 50 992 B with one, 52 016 B with smearing,
 // and 4 096 B more with log-add (54 832 / 55 088 / 56 112 B) -- static, under the 64 KB that need no function attribute.  By LDS a
 // CU (160 KB) holds two workgroups (three of the Viterbi instantiations), so the standing batch of 384 sequences is resident at once
 // on 256 CUs, in one pass, as with the narrow kernel.
@@ -34,29 +40,20 @@
 #include <limits.h>
 #include <math.h>
 
-#include <cmath>
-#include <string>
-#include <type_traits>
-
-#include "../../include/eec.h"
-#include "eec_host.h"
 #include "eec_kernels.h"
 #include "eec_lexbeam.h"
 
 namespace eec {
 
-constexpr int kLwMaxBeam = 64;
-constexpr int kLwCap = 1024;                     // groups of one pass
+constexpr int kLwCap = 1024;                    // groups of one pass
 constexpr int kLwList = kLwMaxBeam + kLwCap;     // list slots: [0, 64) the survivors carried between chunks, then the pass's groups
 constexpr int kLwTable = 2048;                   // hash slots (a power of two, twice the groups)
 constexpr int kLwChunk = kLwCap - 2 * kLwMaxBeam;  // candidates at which a chunk closes; a thread adds at most 2 * 64 - 1 more
 
-__device__ __noinline__ float lw_log_add_call(float a, float b) { return lb_log_add(a, b); }
-
 template <bool LM, bool SM, bool LA>
-__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSmArgs a) {
+__global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbArgs a) {
   static_assert(LM || !SM, "smearing needs a model");
-  using Beam = std::conditional_t<SM, LbBeamSm, LbBeam>;
+  using Beam = LbBeamOf<SM>;
   __shared__ Beam bufs[2][kLwMaxBeam];
   __shared__ __attribute__((aligned(16))) unsigned char slot[kLwMaxBeam][256];  // edge offset of label c below beam i's node
   __shared__ unsigned long long g_hash[kLwCap];  // a group's key: (label of its id, node, history)
@@ -73,35 +70,14 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
   __shared__ float sh_best;
   __shared__ int fin_rank[kLwMaxBeam], fin_ntok[kLwMaxBeam], fin_nw[kLwMaxBeam], fin_n;
   __shared__ float fin_score[LM ? kLwMaxBeam : 1];
-  const int seq = blockIdx.x, c = threadIdx.x, lane = c & 63, w = c >> 6;
-  const int V = a.V, blank = a.blank, sil = a.sil, beam = a.beam, Tq = a.Tq;
+  const int c = threadIdx.x, lane = c & 63, w = c >> 6;
+  const int V = a.V, blank = a.blank, sil = a.sil, beam = a.beam;
+  const LbCtx cx = lb_context<LM, SM>(a, blockIdx.x);
+  const int L = cx.L;
 
-  // a foreign trie, model or smear table: as in the narrow kernel, nothing past the headers is read and no hypothesis is returned
-  const bool ok = a.trie[0] == kLbMagic && a.trie[1] >= 1 && a.trie[3] == V && a.trie[4] == blank && a.trie[5] == sil && lm_fits<LM, SM>(a);
-  int L = a.em_len ? a.em_len[seq] : Tq;
-  if (!ok || L < 1 || L > Tq) L = 0;
-  const int* cbeg = a.trie + (ok ? a.trie[6] : 0);
-  const unsigned char* ctok = (const unsigned char*)(a.trie + (ok ? a.trie[7] : 0));
-  const int* word_of = a.trie + (ok ? a.trie[8] : 0);
-  const int root_deg = L > 0 ? cbeg[1] : 0;
-  const float* smax = nullptr;
-  if constexpr (SM) smax = (const float*)(a.smear + (ok ? kSmHeader : 0));
-  LmView m = {};
-  if constexpr (LM) {
-    const int* lm = a.lm;
-    if (ok) {
-      m.begin = lm + lm[9], m.eword = lm + lm[10], m.suffix = lm + lm[13], m.map = lm + lm[14];
-      m.logp = (const float*)(lm + lm[11]), m.backoff = (const float*)(lm + lm[12]);
-      m.top_begin = lm[8], m.bos = lm[6], m.eos = lm[7];
-    }
-  }
-
-  const float* lp_seq = a.logp + (size_t)seq * Tq * V;
-  int2* bp = a.backptr + (size_t)seq * Tq * beam;
   float* const raw = LA ? g_raw : g_score + kLwMaxBeam;  // Viterbi: the merged score is the best raw score
   int cur = 0, nb = 1;
-  if (c == 0) bufs[0][0] = lb_entry<Beam>(LbBeam{0x243F6A8885A308D3ull, 0.f, 0, 0, root_deg, -1, 0, 0, LM ? m.bos : 0}, 0.f);
-  float lp_next = (L > 0 && c < V) ? lp_seq[c] : -INFINITY;
+  float lp_next = lb_start<LM, SM>(a, cx, &bufs[0][0], c);
   __syncthreads();
 
   // inclusive prefix sum of v over the workgroup's threads; a barrier must follow before the next call
@@ -121,13 +97,9 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
     const Beam* B = bufs[cur];
     Beam* N = bufs[cur ^ 1];
     const float lpc = lp_next;
-    if (t + 1 < L && c < V) lp_next = lp_seq[(size_t)(t + 1) * V + c];  // one frame ahead of its use
+    if (t + 1 < L && c < V) lp_next = cx.lp_seq[(size_t)(t + 1) * V + c];  // one frame ahead of its use
 
-    for (int k = c; k < nb * 64; k += kLbThreads) ((unsigned*)slot)[k] = ~0u;  // rows 0 .. nb - 1 <- kLbNoChild
-    __syncthreads();
-    for (int i = 0; i < nb; ++i)
-      if (c < B[i].deg) slot[i][ctok[B[i].beg + c]] = (unsigned char)c;
-    __syncthreads();
+    lb_fill_slots(slot, B, nb, cx.ctok, c);
 
     // a live candidate of this thread meets its group, or founds one.  Called in ascending id order within a group
     auto offer = [&](int node, unsigned long long h, float s, int id) {
@@ -150,7 +122,7 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
         if ((int)(v >> 16) == c) {
           const int g = (int)(v & 0xffff) - 1;
           if (g_node[g] == node && g_hash[g] == h) {
-            if constexpr (LA) g_score[kLwMaxBeam + g] = lw_log_add_call(g_score[kLwMaxBeam + g], s);
+            if constexpr (LA) g_score[kLwMaxBeam + g] = lb_log_add_call(g_score[kLwMaxBeam + g], s);
             if (s > raw[g]) raw[g] = s, g_id[kLwMaxBeam + g] = (unsigned short)id;  // the lower id stays on a tie
             return;
           }
@@ -159,51 +131,25 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
       }
     };
 
-    // this label's candidates from every beam entry, by the rules and in the fp32 order of the narrow kernel; returns how many live
+    // this label's candidates from every beam entry, by lb_expand's rules; returns how many live
     auto emit = [&](bool insert) {
       int live = 0;
       if (c >= V) return live;
       auto put = [&](int node, unsigned long long h, float s, int id) {
-        if (!(s > -INFINITY)) return;  // -inf and NaN are dropped
+        if (!(s > -INFINITY)) return;  // lb_expand left -inf where there is no candidate
         ++live;
         if (insert) offer(node, h, s, id);
       };
-      // the repeat of a word's last label at the root: the only w = 0 candidate that can meet word-end candidates, and the lowest id
-      if (c != blank && c != sil)
-        for (int i = 0; i < nb; ++i)
-          if (B[i].tok == c && B[i].node == 0) put(0, B[i].hash, B[i].score + lpc, 128 * c + i);
+      // The order is this kernel's concern, not the rules': offer() folds a group in id order.  The repeat of a word's last label at
+      // the root is the only w = 0 candidate that can meet word-end candidates (both stand at the root), and the lowest id: it goes first
+      auto root_repeat = [&](int i) { return c != blank && c != sil && B[i].tok == c && B[i].node == 0; };
+      for (int i = 0; i < nb; ++i)
+        if (root_repeat(i)) put(0, B[i].hash, lb_expand<LM, SM>(a, cx, B[i], c, lpc, slot[i][c]).s0, 128 * c + i);
       for (int i = 0; i < nb; ++i) {
-        const int tok = B[i].tok, node = B[i].node;
-        const float base = B[i].score + lpc;
-        if (c == blank || c == tok) {  // blank, or the repeat of a non-blank label: the state stays
-          if (c != blank && c != sil && node == 0) continue;  // went first
-          put(node, B[i].hash, (c == sil) ? base + a.sil_score : base, 128 * c + i);
-        } else if (c == sil) {
-          if (node == 0) put(0, B[i].hash, base + a.sil_score, 128 * c + i);
-        } else {
-          const int j = slot[i][c];
-          if (j != kLbNoChild) {
-            const int y = B[i].beg + j + 1;
-            const int yb = cbeg[y], ye = cbeg[y + 1], word = word_of[y];
-            float pmax = 0.f;
-            if constexpr (SM) pmax = B[i].pmax;
-            if (ye > yb) {
-              float s0 = base;
-              if constexpr (SM) s0 = lm_add(base, a.lm_weight, smax[y] - pmax);  // the increase of the maximum, paid in advance
-              put(y, B[i].hash, s0, 128 * c + i);
-            }
-            if (word >= 0) {
-              float s1 = base + a.word_score;
-              if constexpr (LM) {
-                int next;
-                float acc = lm_walk(m, B[i].pad, m.map[word], next);
-                if constexpr (SM) acc = acc - pmax;  // the true score replaces what was paid
-                s1 = lm_add(s1, a.lm_weight, acc);
-              }
-              put(0, lb_mix(B[i].hash, word), s1, 128 * c + 64 + i);
-            }
-          }
-        }
+        if (root_repeat(i)) continue;  // went first
+        const LbCand x = lb_expand<LM, SM>(a, cx, B[i], c, lpc, slot[i][c]);
+        put(x.node, B[i].hash, x.s0, 128 * c + i);
+        put(0, x.h1, x.s1, 128 * c + 64 + i);
       }
       return live;
     };
@@ -290,24 +236,20 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
           const int lab = id >> 7, ii = id & 63;
           const bool end_w = (id >> 6) & 1;
           const Beam par = B[ii];
-          LbBeam e = LbBeam{par.hash, s, 0, 0, root_deg, lab, par.ntok + (lab != blank && lab != par.tok), par.nw + end_w, LM ? par.pad : 0};
-          int word = 0;
+          // where the survivor stands, worked out again from its id and slot: a word end at the root with the new history, sil at the
+          // root, blank or a repeat where the parent stands, else the child
+          int node = 0, beg = 0, deg = cx.root_deg, word = -1;
+          unsigned long long hash = par.hash;
           if (end_w) {
-            const int wd = word_of[par.beg + slot[ii][lab] + 1];
-            e.hash = lb_mix(par.hash, wd);
-            word = wd + 1;
-            if constexpr (LM) lm_walk(m, par.pad, m.map[wd], e.pad);  // the walk again, for the state this time
+            word = cx.word_of[par.beg + slot[ii][lab] + 1];
+            hash = lb_mix(par.hash, word);
           } else if (lab == blank || lab == par.tok) {
-            e.node = par.node, e.beg = par.beg, e.deg = par.deg;
+            node = par.node, beg = par.beg, deg = par.deg;
           } else if (lab != sil) {
-            const int y = par.beg + slot[ii][lab] + 1;
-            e.node = y, e.beg = cbeg[y], e.deg = cbeg[y + 1] - cbeg[y];
+            node = par.beg + slot[ii][lab] + 1;
+            beg = cx.cbeg[node], deg = cx.cbeg[node + 1] - beg;
           }
-          float pmax = 0.f;  // nothing is outstanding at the root
-          if constexpr (SM)
-            if (!end_w) pmax = e.node == par.node ? par.pmax : smax[e.node];
-          N[rank] = lb_entry<Beam>(e, pmax);
-          bp[(size_t)t * beam + rank] = make_int2((ii << 16) | lab, word);
+          lb_survive<LM, SM>(a, cx, N, t, par, ii, lab, end_w, node, beg, deg, hash, word, s, rank);
         }
       }
       __syncthreads();
@@ -319,64 +261,19 @@ __global__ __launch_bounds__(kLbThreads) void ctc_lexbeam_wide_kernel(const LbSm
     if (nb == 0) break;  // no candidate survived the frame: the sequence ends without a hypothesis
   }
 
-#include "eec_lexbeam_epilogue.inc"
+  lb_epilogue<LM, SM>(a, cx, bufs[cur], nb, c, fin_rank, fin_ntok, fin_nw, fin_score, fin_n);
 }
+
+// the host path -- checks, the choice of the instantiation, eec_ctc_lexbeam_wide_decode itself -- is lb_decode in ctc_lexbeam.hip
+template <bool LM, bool SM, bool LA>
+void lexbeam_wide_launch(const LbArgs& a, int n_seq, hipStream_t stream) {
+  hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<LM, SM, LA>), dim3(n_seq), dim3(kLbThreads), 0, stream, a);
+}
+template void lexbeam_wide_launch<false, false, false>(const LbArgs&, int, hipStream_t);
+template void lexbeam_wide_launch<true, false, false>(const LbArgs&, int, hipStream_t);
+template void lexbeam_wide_launch<true, true, false>(const LbArgs&, int, hipStream_t);
+template void lexbeam_wide_launch<false, false, true>(const LbArgs&, int, hipStream_t);
+template void lexbeam_wide_launch<true, false, true>(const LbArgs&, int, hipStream_t);
+template void lexbeam_wide_launch<true, true, true>(const LbArgs&, int, hipStream_t);
 
 }  // namespace eec
-
-extern "C" {
-
-size_t eec_ctc_lexbeam_wide_workspace_bytes(int n_seq, int Tq, int beam_size) {
-  return n_seq > 0 && Tq > 0 && beam_size > 0 ? (size_t)n_seq * Tq * beam_size * sizeof(int2) : 0;
-}
-
-int eec_ctc_lexbeam_wide_decode(const float* logp, int n_seq, int Tq, int V, const int32_t* em_len, const void* trie, int blank, int sil,
-                                int beam_size, int nbest, float word_score, float sil_score, float beam_threshold, int max_words,
-                                int32_t* words, int32_t* word_count, int32_t* tokens, int32_t* token_count, int32_t* timesteps, float* scores,
-                                int32_t* n_hyp, void* workspace, size_t workspace_bytes, void* stream, const void* lm, float lm_weight,
-                                const void* smear, int log_add) {
-  using namespace eec;
-  using eech::fail;
-  const std::string me("eec_ctc_lexbeam_wide_decode");
-  const bool with_lm = lm != nullptr, with_smear = smear != nullptr;
-  if (smear && !lm) return fail(EEC_ERR_BAD_ARG, me + ": smear without lm: it is the model's scores that are smeared");
-  if (n_seq < 0 || Tq < 1 || max_words < 1) return fail(EEC_ERR_BAD_ARG, me + ": needs n_seq >= 0, Tq >= 1, max_words >= 1");
-  if (V > 256 || V < 2 || beam_size < 1 || beam_size > kLwMaxBeam || nbest < 1 || nbest > beam_size)
-    return fail(EEC_ERR_UNSUPPORTED, me + ": needs 2 <= V <= 256, 1 <= beam_size <= " + std::to_string(kLwMaxBeam) + ", 1 <= nbest <= beam_size");
-  if (blank < 0 || blank >= V || sil < -1 || sil >= V || sil == blank)
-    return fail(EEC_ERR_BAD_ARG, me + ": needs blank in [0, V), sil -1 or in [0, V) and not the blank");
-  if (with_lm && !std::isfinite(lm_weight)) return fail(EEC_ERR_BAD_ARG, me + ": lm_weight must be finite");
-  if (with_smear && ((uintptr_t)smear & 7)) return fail(EEC_ERR_BAD_ARG, me + ": smear must be 8-byte aligned");
-  if (n_seq == 0) return 0;
-  if (!logp || !trie || !words || !word_count || !tokens || !token_count || !scores || !n_hyp || !workspace)
-    return fail(EEC_ERR_BAD_ARG, me + ": null argument");
-  if (((uintptr_t)trie | (uintptr_t)workspace | (uintptr_t)lm) & 7) return fail(EEC_ERR_BAD_ARG, me + ": trie, lm and workspace must be 8-byte aligned");
-  if (workspace_bytes < eec_ctc_lexbeam_wide_workspace_bytes(n_seq, Tq, beam_size))
-    return fail(EEC_ERR_WORKSPACE, me + ": workspace below eec_ctc_lexbeam_wide_workspace_bytes()");
-  LbSmArgs a;
-  a.logp = logp, a.em_len = em_len, a.trie = (const int*)trie;
-  a.Tq = Tq, a.V = V, a.blank = blank, a.sil = sil, a.beam = beam_size, a.nbest = nbest, a.max_words = max_words;
-  a.use_thr = std::isfinite(beam_threshold) ? 1 : 0;
-  a.word_score = word_score, a.sil_score = sil_score, a.beam_threshold = beam_threshold;
-  a.words = words, a.word_count = word_count, a.tokens = tokens, a.token_count = token_count, a.timesteps = timesteps, a.n_hyp = n_hyp;
-  a.scores = scores, a.backptr = (int2*)workspace;
-  a.lm = (const int*)lm, a.lm_weight = with_lm ? lm_weight : 0.f, a.smear = (const int*)smear;
-  const dim3 grid(n_seq), block(kLbThreads);
-  hipStream_t st = (hipStream_t)stream;
-  if (log_add && with_smear)
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<true, true, true>), grid, block, 0, st, a);
-  else if (log_add && with_lm)
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<true, false, true>), grid, block, 0, st, a);
-  else if (log_add)
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<false, false, true>), grid, block, 0, st, a);
-  else if (with_smear)
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<true, true, false>), grid, block, 0, st, a);
-  else if (with_lm)
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<true, false, false>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((ctc_lexbeam_wide_kernel<false, false, false>), grid, block, 0, st, a);
-  EEC_HIP(hipGetLastError());
-  return 0;
-}
-
-}  // extern "C"

@@ -45,8 +45,20 @@ noise plus a peak of 0 / 2 / 4 / 8 on a path that spells lexicon words (tests/le
   wide@16 returned narrow@16's outputs byte for byte.  ``--parent-record``: records of ``lexbeam_time.py`` (the ``launch`` record of
   384 sequences) run from the parent commit on the same box; the ratio of this run's narrow@10 to it shows the narrow entries did
   not move.
+
+    python tools/lexbeam_time.py --parent-lib PATH [--rounds 11] [--out profiles/lexbeam_one_set_time.json]
+
+* ``--parent-lib``: a second libeec.so, built from another commit, loaded beside this tree's (a library of another ABI version is
+  refused).  Every search kernel is run out of both on the standing batch (384 x 256, V 256): the narrow kernel at ``--beam`` and the
+  wide kernel at beams 16, 32 and 64, each without a model, with the model, with the model and smearing, and each of those with
+  log-add merging, through the entry a caller of that mode reaches.  The two libraries take turns (parent, new, parent, new, ...),
+  ``--rounds`` trains each of 5 calls (narrow), 2 (wide at 16) or 1 (wide at 32 and 64), device events on the current stream after
+  two warm-up calls per library.  A leg's time mark: this tree's median may exceed the parent's by no more than the parent's own
+  min .. max range of that leg.  The outputs of the two libraries on the same inputs are compared byte for byte.  The exit status
+  is 1 when a mark is missed or outputs differ (the record is written first).
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -318,6 +330,80 @@ def wide_leg(args, trie, spellings, dev, records):
             print(json.dumps(rec), flush=True)
 
 
+LEXBEAM_ENTRIES = ("eec_ctc_lexbeam_decode", "eec_ctc_lexbeam_lm_decode", "eec_ctc_lexbeam_lm_smear_decode", "eec_ctc_lexbeam_logadd_decode",
+                   "eec_ctc_lexbeam_wide_decode")
+
+
+def parent_leg(args, trie, spellings, dev, records):
+    """Every search kernel out of two libraries in one process; returns the legs that miss the time mark or differ in their outputs."""
+    new = capi.load()
+    parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+    if parent.eec_abi_version() != new.eec_abi_version():
+        raise SystemExit(f"{args.parent_lib}: ABI v{parent.eec_abi_version()}, this tree has v{new.eec_abi_version()}")
+    for name in LEXBEAM_ENTRIES:
+        getattr(parent, name).argtypes = getattr(new, name).argtypes
+    libs = {"parent": parent, "new": new}
+    n, T = 384, args.frames
+    em = torch.from_numpy(L.emissions(3, spellings, n, T, 256, 0, 126)).to(dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    words, wc, toks, tc, ts, nh = i32(n, 1, T), i32(n, 1), i32(n, 1, T), i32(n, 1), i32(n, 1, T), i32(n)
+    sc = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    outputs = (words, wc, toks, tc, ts, sc, nh)
+    ws = torch.empty(new.eec_ctc_lexbeam_wide_workspace_bytes(n, T, 64), dtype=torch.uint8, device=dev)
+    image = trie.on(dev)
+    lm = synthetic_model(len(spellings), args.bigrams, args.trigrams)
+    lm_image, smear_image = lm.on(dev), lm.smear(trie).on(dev)
+    modes = {"lm_free": (None, None), "lm": (lm_image.data_ptr(), None), "smear": (lm_image.data_ptr(), smear_image.data_ptr())}
+    # (kernel, beam, calls per train): fewer calls where one lasts hundreds of milliseconds
+    shapes = (("narrow", args.beam, 5), ("wide", 16, 2), ("wide", 32, 1), ("wide", 64, 1))
+    missed = []
+    for mode, (lm_ptr, smear_ptr) in modes.items():
+        for log_add in (0, 1):
+            for kind, beam, per in shapes:
+                common = (em.data_ptr(), n, T, 256, None, image.data_ptr(), trie.blank, trie.sil, beam, 1, 0.0, 0.0, 50.0, T, words.data_ptr(),
+                          wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(), nh.data_ptr(), ws.data_ptr(), ws.numel(),
+                          capi.stream_ptr(dev))
+                # the entry a caller of this mode reaches (early_exit_transformer_amd/ctc.py)
+                if kind == "wide":
+                    name, tail = "eec_ctc_lexbeam_wide_decode", (lm_ptr, 1.0, smear_ptr, log_add)
+                elif log_add:
+                    name, tail = "eec_ctc_lexbeam_logadd_decode", (lm_ptr, 1.0, smear_ptr)
+                else:
+                    name, tail = {"lm_free": ("eec_ctc_lexbeam_decode", ()), "lm": ("eec_ctc_lexbeam_lm_decode", (lm_ptr, 1.0)),
+                                  "smear": ("eec_ctc_lexbeam_lm_smear_decode", (lm_ptr, 1.0, smear_ptr))}[mode]
+
+                def call(lib):
+                    rc = getattr(lib, name)(*common, *tail)
+                    if rc != 0:
+                        raise SystemExit(f"{name} returned {rc}: {lib.eec_last_error()}")
+                got = {}
+                for which, lib in libs.items():  # the comparison doubles as the warm-up
+                    for o in outputs:
+                        o.zero_()
+                    call(lib)
+                    call(lib)
+                    torch.cuda.synchronize()
+                    got[which] = [o.cpu().numpy().tobytes() for o in outputs]
+                ms = {which: [] for which in libs}
+                for _ in range(args.rounds):
+                    for which, lib in libs.items():
+                        ms[which].append(event_ms(lambda: call(lib), 1, per=per)["median"])  # one train of `per` calls
+                p = {"median": round(statistics.median(ms["parent"]), 4), "min": min(ms["parent"]), "max": max(ms["parent"])}
+                q = {"median": round(statistics.median(ms["new"]), 4), "min": min(ms["new"]), "max": max(ms["new"])}
+                rec = {"what": "parent_lib", "kernel": kind, "mode": mode, "log_add": bool(log_add), "beam": beam, "entry": name, "n_seq": n, "frames": T,
+                       "rounds": args.rounds, "calls_per_train": per, "parent_ms_per_call": p, "new_ms_per_call": q,
+                       "new_minus_parent_median_ms": round(q["median"] - p["median"], 4), "parent_range_ms": round(p["max"] - p["min"], 4),
+                       "time_mark_met": q["median"] - p["median"] <= p["max"] - p["min"], "outputs_bit_identical": got["parent"] == got["new"],
+                       "sequences_with_a_hypothesis": int((nh > 0).sum())}
+                if not rec["time_mark_met"]:
+                    missed.append(f"{kind} {mode} log_add={log_add} beam {beam}: time")
+                if not rec["outputs_bit_identical"]:
+                    missed.append(f"{kind} {mode} log_add={log_add} beam {beam}: outputs differ")
+                records.append(rec)
+                print(json.dumps(rec), flush=True)
+    return missed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -332,6 +418,8 @@ def main():
     ap.add_argument("--bigrams", type=int, default=2000000)
     ap.add_argument("--trigrams", type=int, default=2000000)
     ap.add_argument("--parent-record", nargs="*", help="records of this tool run from the parent commit on the same box")
+    ap.add_argument("--parent-lib", default=None, help="a libeec.so built from the commit to compare against (the same ABI version)")
+    ap.add_argument("--rounds", type=int, default=11, help="with --parent-lib: trains per library and leg, the two libraries in turn")
     args = ap.parse_args()
     if args.smear and not args.lm:
         ap.error("--smear goes with --lm")
@@ -348,8 +436,12 @@ def main():
     print(json.dumps(records[-1]), flush=True)
     # the synthetic trie stands for the real one only while it has its size: nodes within 2 %, the same extreme degrees
     assert abs(trie.n_nodes - 162621) <= 0.02 * 162621 and degree[0] == 109 and degree[1:].max() == 103 and trie.n_shadowed == 0, records[-1]
-    counts = [] if args.lm or args.log_add or args.wide else [int(q) for q in args.seqs.split(",")]
-    if args.wide:
+    counts = [] if args.lm or args.log_add or args.wide or args.parent_lib else [int(q) for q in args.seqs.split(",")]
+    missed = []
+    if args.parent_lib:
+        missed = parent_leg(args, trie, spellings, dev, records)
+        records[0]["missed"] = missed
+    elif args.wide:
         wide_leg(args, trie, spellings, dev, records)
     elif args.log_add:
         logadd_leg(args, trie, spellings, dev, records)
@@ -373,6 +465,9 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(records, f, indent=1)
+    if missed:
+        print("MISSED:\n  " + "\n  ".join(missed), flush=True)
+        sys.exit(1)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,8 @@
 // bound (plus the rounding of the final addition) of the float64 log-sum, and a non-decreasing result as lo rises.
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         early_exit_transformer_amd/csrc/ctc_lexbeam.hip tools/logadd_check.cpp -o logadd_check
+//         early_exit_transformer_amd/csrc/ctc_lexbeam.hip early_exit_transformer_amd/csrc/ctc_lexbeam_wide.hip \
+//         tools/logadd_check.cpp -o logadd_check
 //   ./logadd_check
 #include <math.h>
 #include <stdint.h>

@@ -1,10 +1,10 @@
-// Stand-alone host check of the n-gram packer (eec_ngram_pack, csrc/ctc_lexbeam.hip), meant to be built with the host sanitizers;
+// Stand-alone host check of the n-gram packer (eec_ngram_pack, csrc/lexpack.hip), meant to be built with the host sanitizers;
 // it makes no device call.  Generates a prefix-closed, not suffix-closed model of order 4 from a seed (argv[1]: words, default
 // 2000), packs it into an exactly sized heap buffer, walks the image by the documented layout -- every generated n-gram must be
 // found with its values, every suffix link must be the longest suffix that is a node --, and runs the packer's error cases.
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         early_exit_transformer_amd/csrc/ctc_lexbeam.hip tools/ngram_pack_check.cpp -o ngram_pack_check
+//         early_exit_transformer_amd/csrc/lexpack.hip tools/ngram_pack_check.cpp -o ngram_pack_check
 //   ./ngram_pack_check
 #include <math.h>
 #include <stdint.h>

@@ -1,10 +1,12 @@
-// Stand-alone host check of the trie packer (eec_ctc_trie_pack, csrc/ctc_lexbeam.hip), meant to be built with the host
+// Stand-alone host check of the trie packer (eec_ctc_trie_pack, csrc/lexpack.hip), meant to be built with the host
 // sanitizers; it makes no device call.  Reads a lexicon as text -- first line "n_words V blank sil", then one spelling per line
 // as token ids --, packs it into an exactly sized heap buffer, walks the image by the documented layout (every spelling must lead
-// to the first word that has it), and runs the packer's error cases.
+// to the first word that has it), and runs the packer's error cases.  (The two kernel files are on the line for the decoder's
+// workspace size function, which the program also checks.)
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         early_exit_transformer_amd/csrc/ctc_lexbeam.hip tools/trie_pack_check.cpp -o trie_pack_check
+//         early_exit_transformer_amd/csrc/lexpack.hip early_exit_transformer_amd/csrc/ctc_lexbeam.hip \
+//         early_exit_transformer_amd/csrc/ctc_lexbeam_wide.hip tools/trie_pack_check.cpp -o trie_pack_check
 //   python -c "import sys; sys.path.insert(0, 'tests'); import lexbeam_cases as L; t, w, s = L.load_fixture(); \
 //              print(len(s), 256, 0, 126); [print(*x) for x in s]" | ./trie_pack_check
 #include <stdint.h>

@@ -1,11 +1,11 @@
-// Stand-alone host check of the smear table (eec_ctc_trie_smear, csrc/ctc_lexbeam.hip), meant to be built with the host sanitizers;
+// Stand-alone host check of the smear table (eec_ctc_trie_smear, csrc/lexpack.hip), meant to be built with the host sanitizers;
 // it makes no device call.  Generates a lexicon (argv[1]: words, default 3000; duplicates and words that are prefixes of words
 // included) and a prefix-closed model of order 3 with <s> from a seed, packs both, computes the table into an exactly sized heap
 // buffer, and recomputes smax by brute force over the words: u(w) by a back-off walk written here against the documented image
 // layout, then for every prefix of every first spelling the maximum.  Then the entry's error cases.
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         early_exit_transformer_amd/csrc/ctc_lexbeam.hip tools/trie_smear_check.cpp -o trie_smear_check
+//         early_exit_transformer_amd/csrc/lexpack.hip tools/trie_smear_check.cpp -o trie_smear_check
 //   ./trie_smear_check
 #include <math.h>
 #include <stdint.h>
