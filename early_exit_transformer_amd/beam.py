@@ -33,6 +33,9 @@
   best hypothesis is the one with the highest ``(1 - w) * att + w * ctc``: no autoregressive loop, no key / value cache.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
+* ``BeamInference.error_table``: what any of the decoders above returned, scored against references (``scoring.error_table``;
+  csrc/edit_distance.hip): errors with their substitution / deletion / insertion split per exit and utterance, in tokens, or in
+  words / characters after ``detokenize`` and ``apply_lex``.  The reference leaves this to tools outside its tree.
 """
 from __future__ import annotations
 
@@ -839,3 +842,49 @@ class BeamInference:
             for b, row in zip(members, together):
                 out[b] = (row[0][2], e)
         return out
+
+    # -- error-rate scoring of what the decoders above return (scoring.py) ---------------------------------------------------------
+    def error_table(self, decoded, refs, unit: str = "token", detokenize=None, lexicon=None, device=None):
+        """``scoring.ErrorTable`` of ``decoded`` against ``refs`` [B].  ``decoded`` is what any decoder of this class returns:
+        ``decode_batch`` / ``decode_batch_rescoring``'s ``out[b][e]`` (errors [E, B]); ``ctc_cuda_predict``'s per-utterance hypothesis
+        lists of one exit, or a list of them over the exits (errors [E, B, N], -1 for a hypothesis a list does not have);
+        ``ctc_adaptive_predict``'s ``(hypotheses, exit_of)`` and ``decode_batch_adaptive``'s ``(tokens, exit)`` rows (E = 1: the
+        chosen exits).  ``unit="token"``: ids against ids, ``refs`` a list of id lists or ``(targets [B, L], lengths [B])``;
+        whatever SOS / EOS / PAD the ids carry is scored as it stands.  ``unit="word"`` / ``"char"``: ``refs`` are strings and every
+        hypothesis is ``detokenize(ids)`` -- with ``lexicon`` after ``apply_lex``, as inference.py prints it: the ``.text`` the decoder
+        left where it was given the same two, else one lexicon search for all hypotheses of the call.  ``device``: where to score
+        (None: ``args.device`` if that is a HIP device, else the host path)."""
+        from . import scoring
+        if isinstance(decoded, tuple) and len(decoded) == 2 and isinstance(decoded[1], Tensor):
+            decoded = decoded[0]  # (hypotheses, exit_of)
+        decoded = list(decoded)
+        is_hyp = lambda x: hasattr(x, "tokens")  # noqa: E731
+        is_ids = lambda x: isinstance(x, (list, tuple)) and all(isinstance(v, int) for v in x)  # noqa: E731
+        if decoded and isinstance(decoded[0], tuple) and len(decoded[0]) == 2 and isinstance(decoded[0][1], int) and is_ids(decoded[0][0]):
+            hyps, nbest = [[ids for ids, _ in decoded]], False  # (tokens, exit) rows
+        elif any(is_hyp(h) for row in decoded for h in row):
+            hyps, nbest = [decoded], True  # one exit's [B][N]
+        elif any(is_hyp(h) for ex in decoded for row in ex if not is_ids(row) or not row for h in row):
+            hyps, nbest = decoded, True  # [E][B][N]
+        else:
+            E = len(decoded[0]) if decoded else 0
+            hyps, nbest = [[row[e] for row in decoded] for e in range(E)], False  # out[b][e]
+        if isinstance(refs, tuple) and len(refs) == 2 and isinstance(refs[0], Tensor):
+            refs = [refs[0][b, : int(refs[1][b])].tolist() for b in range(refs[0].size(0))]
+        if unit != "token":
+            if detokenize is None:
+                raise ValueError("error_table: scoring words or characters needs detokenize (ids -> str)")
+            leaves = [h for ex in hyps for row in ex for h in (row if nbest else [row])]
+            ids_of = lambda h: list(getattr(h, "tokens", h))  # noqa: E731
+            if lexicon is None:
+                texts = [detokenize(ids_of(h)) for h in leaves]
+            elif all(getattr(h, "text", None) is not None for h in leaves):
+                texts = [h.text for h in leaves]
+            else:
+                texts = _snapped_texts([ids_of(h) for h in leaves], lexicon, detokenize)
+            it = iter(texts)
+            hyps = [[[next(it) for _ in row] if nbest else next(it) for row in ex] for ex in hyps]
+        if device is None:
+            dev = torch.device(getattr(self.args, "device", "cpu"))
+            device = dev if dev.type == "cuda" else None
+        return scoring.error_table(hyps, refs, unit=unit, layout="EB", device=device, want_nbest=nbest)

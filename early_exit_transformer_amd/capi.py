@@ -100,6 +100,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_ctc_lexbeam_logadd_decode", "eec_ctc_log_add_host", "eec_ctc_log_add",
            "eec_ctc_lexbeam_wide_workspace_bytes", "eec_ctc_lexbeam_wide_decode",
            "eec_lexicon_pack_bytes", "eec_lexicon_pack", "eec_lexicon_nearest_workspace_bytes", "eec_lexicon_nearest",
+           "eec_edit_distance_workspace_bytes", "eec_edit_distance",
            "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
            "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
            "eec_train_forward", "eec_train_backward", "eec_train_backward_ex", "eec_train_gemm",
@@ -221,6 +222,10 @@ def load() -> C.CDLL:
     lib.eec_lexicon_nearest_workspace_bytes.restype = C.c_size_t
     lib.eec_lexicon_nearest.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
+    lib.eec_edit_distance_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.eec_edit_distance_workspace_bytes.restype = C.c_size_t
+    lib.eec_edit_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.eec_frontend_last_error.restype = C.c_char_p
     lib.eec_frontend_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.eec_frontend_destroy.argtypes = [C.c_void_p]

@@ -726,7 +726,48 @@ int eec_lexicon_nearest(const void* packed, int n_words, const uint8_t* queries,
                         int max_query_len, int32_t* out_index, int32_t* out_distance, void* workspace, size_t workspace_bytes,
                         void* stream);
 
-/* Mel front end: replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
+/* ---- Edit distance: error-rate scoring of hypotheses against references (csrc/edit_distance.hip) ---------------------------------
+ * For a reference r of m tokens and a hypothesis h of n tokens, int32 each and compared by equality only, with the unit costs of
+ * Kaldi's compute-wer, jiwer and torchaudio's edit_distance (sclite's 4 / 3 / 3 weights are not served):
+ *     K[0][0] = 0;   K[i][0] = i << 16;   K[0][j] = j << 16
+ *     K[i][j] = min( K[i-1][j-1] + (r_i == h_j ? 0 : (1 << 16) + 1),     diag
+ *                    K[i-1][j]   + (1 << 16),                            del: a reference token unmatched
+ *                    K[i][j-1]   + (1 << 16) )                           ins: a hypothesis token unmatched
+ *     distance = K[m][n] >> 16        subs = K[m][n] & 0xffff
+ *     dels = (distance - subs - (n - m)) / 2      ins = dels + n - m      hits = m - subs - dels
+ * distance is the Levenshtein distance and depends on no convention.  The S / D / I split does: among all minimum-cost
+ * alignments this is the one with the FEWEST SUBSTITUTIONS (the key is minimised lexicographically; an additive pair under
+ * lexicographic min is a valid dynamic programme, so no evaluation order enters).  n - m = ins - dels, so (distance, subs) fixes
+ * all four counts.  Other tools may split the same distance differently.
+ * The op string, written only when asked for, is the canonical alignment: dir[i][j] is the FIRST of (diag, del, ins) whose
+ * candidate equals K[i][j]; del on the border j = 0, ins on the border i = 0; walked back from (m, n), emitted in forward order as
+ *     0 hit, 1 substitution, 2 deletion, 3 insertion.
+ * Its counts are the reported ones, and it has n + dels ops.
+ *
+ *   hyp [n_pairs][hyp_pitch], hyp_len [n_pairs]; ref [n_refs][ref_pitch], ref_len [n_refs]: int32 on the device.  Lengths are
+ *       clamped to [0, pitch]; tokens at or past a length are never read.  hyp / ref may be NULL when their pitch is 0.
+ *   ref_of [n_pairs] int32 or NULL: the reference of pair p; NULL: pair p scores against reference p and n_refs == n_pairs.
+ *       An entry outside [0, n_refs) gives counts (-1, -1, -1, -1) and n_ops 0 for that pair, and nothing of the pair is read.
+ *   counts [n_pairs][4] int32, 16-byte aligned: distance, subs, dels, ins.
+ *   ops [n_pairs][ref_pitch + hyp_pitch] uint8 or NULL; n_ops [n_pairs] int32 (needed with ops): the op string of pair p is
+ *       ops[p][0 .. n_ops[p]); bytes past it are not written.
+ *   workspace: eec_edit_distance_workspace_bytes(n_pairs, ref_pitch, hyp_pitch, ops != NULL) bytes, 256-byte aligned: two bits per
+ *       table cell when ops are wanted, nothing otherwise (then it may be NULL).  The size is non-decreasing in each argument and
+ *       0 for a non-positive one.
+ * One wave per pair, four pairs per workgroup, the hypothesis dealt over the lanes in strips of 4, 8 or 16 columns (by hyp_pitch),
+ * the rows as a systolic wavefront; with ops a second kernel of one work-item per pair walks back.  Integer only: two runs are
+ * bit-identical, and a call on a slice of the pairs returns the rows of the whole call.
+ * EEC_ERR_BAD_ARG: a null pointer where one is needed, a misaligned counts, n_pairs < 0, a pitch below 0 or above
+ * EEC_EDIT_MAX_LEN, n_refs < 1 or (without ref_of) != n_pairs with n_pairs > 0, ops without n_ops.  EEC_ERR_WORKSPACE: a short or
+ * misaligned workspace.  n_pairs == 0 is a successful no-op.  All checked before any device work.  No allocation, no
+ * synchronisation; graph-capturable. */
+#define EEC_EDIT_MAX_LEN 1024
+size_t eec_edit_distance_workspace_bytes(int n_pairs, int max_ref_len, int max_hyp_len, int want_ops);
+int eec_edit_distance(const int32_t* hyp, const int32_t* hyp_len, int n_pairs, int hyp_pitch, const int32_t* ref,
+                      const int32_t* ref_len, int n_refs, int ref_pitch, const int32_t* ref_of, int32_t* counts, uint8_t* ops,
+                      int32_t* n_ops, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Mel front end(SURVEY 8f row f3): replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
  * n_mels, n_stft = 513; htk scale, no normalisation), NO log -- on the device, as an exact-fp32 MFMA transform.
  *   wave [B, Lmax] fp32; lengths_opt [B] int64 valid samples per utterance or NULL (all Lmax)
