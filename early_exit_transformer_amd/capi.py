@@ -89,6 +89,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_encoder_head_forward", "eec_encoder_stem1_forward", "eec_encoder_lengths",
            "eec_ctc_backward_workspace_bytes", "eec_ctc_loss_forward", "eec_ctc_loss_backward", "eec_logsoftmax_backward",
            "eec_exit_distill_workspace_bytes", "eec_exit_distill_forward", "eec_exit_distill_backward",
+           "eec_ctc_mwer_workspace_bytes", "eec_ctc_hyp_logp", "eec_ctc_mwer_forward", "eec_ctc_mwer_backward",
            "eec_exit_stats_workspace_bytes", "eec_exit_stats", "eec_exit_route",
            "eec_ctc_beam_workspace_bytes", "eec_ctc_beam_decode", "eec_ctc_beam_decode_ex",
            "eec_ctc_loss_len", "eec_ctc_loss_forward_len", "eec_ctc_loss_backward_len", "eec_greedy_ctc_len", "eec_ctc_beam_decode_len",
@@ -174,6 +175,13 @@ def load() -> C.CDLL:
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.eec_exit_distill_backward.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.eec_ctc_mwer_workspace_bytes.argtypes = [C.c_int] * 5
+    lib.eec_ctc_mwer_workspace_bytes.restype = C.c_size_t
+    lib.eec_ctc_hyp_logp.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
+    # logp, input_len, hyp, hyp_len, risk; E, B, b0, nb, T', V, N, L, blank; ll, loss_eb, loss, workspace, its bytes, stream
+    lib.eec_ctc_mwer_forward.argtypes = [C.c_void_p] * 5 + [C.c_int] * 9 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+    # logp, input_len, hyp, hyp_len; E, B, b0, nb, T', V, N, L, blank; workspace, its bytes, grad_loss, accumulate, dlogp, stream
+    lib.eec_ctc_mwer_backward.argtypes = [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.eec_exit_stats_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.eec_exit_stats_workspace_bytes.restype = C.c_size_t
     lib.eec_exit_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -1,9 +1,10 @@
 """The CTC operators on encoder log-probs: per-exit losses with their gradient (train.py:53-68), self-distillation between the exits
-(the reference's unimplemented ``--distill``), greedy, prefix-beam and
+(the reference's unimplemented ``--distill``), MWER training against N-best lists, greedy, prefix-beam and
 lexicon-constrained beam decoding and forced alignment (util/beam_infer.py) and the encoder's frame lengths.  Each is one call into libeec.so on the caller's current HIP
 stream; there is no CPU path, except for the CTC prefix scorer of one-pass joint decoding (``ctc_prefix_session``), whose host path lets a
-search loop be tested without a device, and for the exit statistics and the exit choice of adaptive inference (``exit_statistics``,
-``select_exits``), whose host paths state them in torch ops."""
+search loop be tested without a device, for the exit statistics and the exit choice of adaptive inference (``exit_statistics``,
+``select_exits``), whose host paths state them in torch ops, and for MWER training (``ctc_hyp_logp``, ``exit_mwer_losses``), whose host
+path is the statement through torch's own ``F.ctc_loss`` and autograd."""
 from __future__ import annotations
 
 import ctypes as C
@@ -789,3 +790,305 @@ def exit_training_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, f
     dev = x.device
     il = _frame_counts("exit_training_losses", "input_len", input_len, x.size(1), dev)
     return _ExitTrainingFn.apply(x, to_device(targets, dev), to_device(target_len, dev), blank, fl, tmap, tau, il)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# MWER training of the CTC exits (include/eec.h states the loss; csrc/ctc_mwer.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+MWER_MAX_NBEST, MWER_MAX_LEN = 16, 255
+
+
+class MwerLists(NamedTuple):
+    """The N-best lists of every exit and utterance as MWER training takes them: ``tokens`` [E, B, N, L] int32, ``lengths``
+    [E, B, N] int32 (-1: no such hypothesis), ``risk`` [E, B, N] fp32 (the token edit distance to the utterance's target) and
+    ``scores`` [E, B, N] fp32 (the beam's pruned scores, -inf for an absent entry)."""
+    tokens: Tensor
+    lengths: Tensor
+    risk: Tensor
+    scores: Tensor
+
+
+def _mwer_args(name: str, enc_out: Tensor, hyp: Tensor, hyp_len: Tensor, risk: Optional[Tensor], input_len: Optional[Tensor]):
+    """(enc_out contiguous -- fp32 on a device, its own floating dtype on the CPU --, input_len int32 [B] or None, hyp int32
+    [E, B, N, L >= 1], hyp_len int32 [E, B, N], risk [E, B, N] in enc_out's dtype or None), all on enc_out's device."""
+    if not isinstance(enc_out, Tensor) or enc_out.dim() != 4 or not enc_out.is_floating_point() or min(enc_out.shape) < 1:
+        raise ValueError(f"{name}: enc_out must be a non-empty floating-point [E, B, T', V], got {tuple(getattr(enc_out, 'shape', ()))}")
+    dev = enc_out.device
+    x = enc_out.contiguous().float() if enc_out.is_cuda else enc_out.contiguous()
+    E, B = x.shape[:2]
+    if not isinstance(hyp, Tensor) or hyp.dim() != 4 or tuple(hyp.shape[:2]) != (E, B) or hyp.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: hyp must be an int32 or int64 [E, B, N, L] = [{E}, {B}, N, L], got {tuple(getattr(hyp, 'shape', ()))}")
+    N = hyp.size(2)
+    if not 1 <= N <= MWER_MAX_NBEST:
+        raise ValueError(f"{name}: lists of 1 to {MWER_MAX_NBEST} hypotheses are served, got N = {N}")
+    if hyp.dtype == torch.int64:
+        hyp = hyp.clamp(-1, 2 ** 31 - 1)  # a label int32 cannot hold is refused on the device like any label outside [0, V)
+    hyp = hyp.to(device=dev, dtype=torch.int32)
+    if hyp.size(3) == 0:
+        hyp = hyp.new_zeros((E, B, N, 1))
+    if not isinstance(hyp_len, Tensor) or tuple(hyp_len.shape) != (E, B, N) or hyp_len.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: hyp_len must be an int32 or int64 [{E}, {B}, {N}], got {tuple(getattr(hyp_len, 'shape', ()))}")
+    if hyp_len.dtype == torch.int64:
+        hyp_len = hyp_len.clamp(-2, 2 ** 31 - 1)
+    hl = hyp_len.to(device=dev, dtype=torch.int32).contiguous()
+    if risk is not None:
+        if not isinstance(risk, Tensor) or tuple(risk.shape) != (E, B, N):
+            raise ValueError(f"{name}: risk must be [{E}, {B}, {N}], got {tuple(getattr(risk, 'shape', ()))}")
+        risk = risk.detach().to(device=dev, dtype=x.dtype).contiguous()
+    return x, _frame_counts(name, "input_len", input_len, B, dev), hyp.contiguous(), hl, risk
+
+
+def _mwer_host_ll(x: Tensor, il: Optional[Tensor], hyp: Tensor, hl: Tensor, blank: int):
+    """The host path: (ll [E, B, N] in ``x``'s dtype, differentiable through torch's ``F.ctc_loss``; refused [E, B, N] bool)."""
+    E, B, T, V = x.shape
+    N, L = hyp.shape[2:]
+    G = E * B * N
+    ninf = float("-inf")
+    Tb = torch.full((B,), T, dtype=torch.int64) if il is None else il.to(torch.int64).clamp(0, T)
+    len_ok = (hl >= -1) & (hl <= min(L, MWER_MAX_LEN))
+    lens = torch.where(len_ok, hl, torch.full_like(hl, -1)).to(torch.int64)
+    tok = hyp.to(torch.int64)
+    inside = torch.arange(L).view(1, 1, 1, L) < lens.unsqueeze(-1)
+    refused = ~len_ok | (inside & ((tok < 0) | (tok >= V) | (tok == blank))).any(-1)
+    present = (lens >= 0) & ~refused
+    frames = Tb.view(1, B, 1).expand(E, B, N).reshape(G)
+    lp = x.unsqueeze(2).expand(E, B, N, T, V).reshape(G, T, V).permute(1, 0, 2)
+    lp = torch.where(torch.arange(T).view(T, 1, 1) < frames.view(1, G, 1), lp, torch.zeros_like(lp))  # frames at or past Tb are not read
+    tl = torch.where(present, lens, torch.zeros_like(lens)).reshape(G)
+    tg = tok.clamp(0, V - 1).reshape(G, L)
+    args = (tg, frames.clamp(min=1), tl)
+    with torch.no_grad():
+        infeasible = torch.nn.functional.ctc_loss(lp.detach(), *args, blank=blank, reduction="none", zero_infinity=False) == float("inf")
+    ll = -torch.nn.functional.ctc_loss(lp, *args, blank=blank, reduction="none", zero_infinity=True)
+    ll = torch.where(infeasible, torch.full_like(ll, ninf), ll)
+    ll = torch.where(frames == 0, torch.where(tl == 0, torch.zeros_like(ll), torch.full_like(ll, ninf)), ll)
+    ll = torch.where(present.reshape(G), ll, torch.full_like(ll, ninf))
+    ll = torch.where(refused.reshape(G), torch.full_like(ll, float("nan")), ll)
+    return ll.view(E, B, N), refused
+
+
+def _mwer_host_loss(ll: Tensor, refused: Tensor, risk: Tensor) -> Tensor:
+    """loss_eb [E, B] of include/eec.h from ll and risk [E, B, N], in torch ops (autograd gives sum_i c_i d ll_i)."""
+    ninf = float("-inf")
+    in_p = torch.isfinite(ll)
+    llm = torch.where(in_p, ll, torch.full_like(ll, ninf))
+    m = llm.max(-1, keepdim=True).values
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m)).detach()
+    w = torch.where(in_p, (llm - m).exp(), torch.zeros_like(ll))
+    z = w.sum(-1, keepdim=True)
+    phat = w / torch.where(z > 0, z, torch.ones_like(z))
+    cnt = in_p.sum(-1, keepdim=True)
+    rk = torch.where(in_p, risk, torch.zeros_like(risk))
+    rmin = torch.where(in_p, risk, torch.full_like(risk, float("inf"))).min(-1, keepdim=True).values
+    rmax = torch.where(in_p, risk, torch.full_like(risk, ninf)).max(-1, keepdim=True).values
+    rbar = torch.where(rmin == rmax, rmin, rk.sum(-1, keepdim=True) / cnt.clamp(min=1).to(risk.dtype))
+    # sum_i phat_i (risk_i - rbar) with the risks measured from the likeliest entry's, which changes neither the value nor the
+    # gradient; autograd's softmax backward then cancels nothing when that entry holds nearly all the mass
+    rdom = torch.where(in_p.any(-1, keepdim=True), risk.gather(-1, llm.argmax(-1, keepdim=True)), torch.zeros_like(rbar))
+    loss_eb = (phat * torch.where(in_p, risk - rdom, torch.zeros_like(risk))).sum(-1) + (rdom - rbar).squeeze(-1)
+    poisoned = refused.any(-1) | (torch.isnan(ll) & ~refused).any(-1)
+    return torch.where(poisoned, torch.full_like(loss_eb, float("nan")), loss_eb)
+
+
+def _mwer_chunks(x: Tensor, N: int, L: int, max_workspace_bytes: int):
+    """[(b0, nb)]: the batch in runs of utterances whose workspace stays inside ``max_workspace_bytes`` (one utterance at least)."""
+    E, B, Tq, _ = x.shape
+    per_utt = max(capi.load().eec_ctc_mwer_workspace_bytes(E, 1, Tq, N, L), 1)
+    step = min(B, max(1, int(max_workspace_bytes) // per_utt))
+    return [(b0, min(step, B - b0)) for b0 in range(0, B, step)]
+
+
+def _mwer_forward_chunk(x, il, hyp, hl, risk, blank, b0, nb, ll, loss_eb, loss, ws_ptr, nbytes):
+    E, B, Tq, V = x.shape
+    N, L = hyp.shape[2:]
+    capi.check(capi.load().eec_ctc_mwer_forward(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), risk.data_ptr(), E, B, b0, nb, Tq, V, N, L,
+                                                int(blank), ll.data_ptr(), loss_eb.data_ptr(), loss.data_ptr(), ws_ptr, nbytes,
+                                                stream_ptr(x.device)), "eec_ctc_mwer_forward")
+
+
+def _mwer_forward(x: Tensor, il: Optional[Tensor], hyp: Tensor, hl: Tensor, risk: Tensor, blank: int, max_workspace_bytes: int):
+    """(loss [E], ll [E, B, N], loss_eb [E, B], kept): ``kept`` = (workspace tensor, aligned address, bytes) when the batch went
+    through as one chunk -- the backward reads it --, None when it was split (the backward then redoes the forward chunk by chunk)."""
+    E, B, Tq, _ = x.shape
+    N, L = hyp.shape[2:]
+    dev = x.device
+    lib = capi.load()
+    ll = torch.empty((E, B, N), dtype=torch.float32, device=dev)
+    loss_eb = torch.empty((E, B), dtype=torch.float32, device=dev)
+    loss = torch.empty((E,), dtype=torch.float32, device=dev)
+    chunks = _mwer_chunks(x, N, L, max_workspace_bytes)
+    with torch.cuda.device(dev):
+        nbytes = lib.eec_ctc_mwer_workspace_bytes(E, chunks[0][1], Tq, N, L)  # the first chunk is the largest
+        ws, ws_ptr = capi.aligned_ws(nbytes, dev)
+        for b0, nb in chunks:
+            _mwer_forward_chunk(x, il, hyp, hl, risk, blank, b0, nb, ll, loss_eb, loss, ws_ptr, nbytes)
+    return loss, ll, loss_eb, ((ws, ws_ptr, nbytes) if len(chunks) == 1 else None)
+
+
+def _mwer_backward(x: Tensor, il: Optional[Tensor], hyp: Tensor, hl: Tensor, risk: Tensor, blank: int, max_workspace_bytes: int, kept,
+                   grad_loss: Tensor, accumulate: bool, dlogp: Tensor) -> None:
+    """eec_ctc_mwer_backward into ``dlogp`` (written in full, or added into)."""
+    E, B, Tq, V = x.shape
+    N, L = hyp.shape[2:]
+    dev = x.device
+    lib = capi.load()
+    g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+
+    def back(b0, nb, ws_ptr, nbytes):
+        capi.check(lib.eec_ctc_mwer_backward(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), E, B, b0, nb, Tq, V, N, L, int(blank),
+                                             ws_ptr, nbytes, g.data_ptr(), int(bool(accumulate)), dlogp.data_ptr(), stream_ptr(dev)),
+                   "eec_ctc_mwer_backward")
+    with torch.cuda.device(dev):
+        if kept is not None:
+            back(0, B, kept[1], kept[2])
+            return
+        chunks = _mwer_chunks(x, N, L, max_workspace_bytes)
+        nbytes = lib.eec_ctc_mwer_workspace_bytes(E, chunks[0][1], Tq, N, L)
+        ws, ws_ptr = capi.aligned_ws(nbytes, dev)
+        scratch = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((E, B, N), (E, B), (E,))]
+        for b0, nb in chunks:
+            _mwer_forward_chunk(x, il, hyp, hl, risk, blank, b0, nb, *scratch, ws_ptr, nbytes)
+            back(b0, nb, ws_ptr, nbytes)
+
+
+def _mwer_check_vocab(name: str, V: int) -> None:
+    if V > 256 or V % 4:
+        raise ValueError(f"{name} with a gradient needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
+                         "a gradient row is one float4 per lane")
+
+
+class _ExitMwerFn(torch.autograd.Function):
+    """Per-exit MWER losses [E] with their gradient with respect to the log-probs (eec_ctc_mwer_forward / _backward)."""
+
+    @staticmethod
+    def forward(ctx, enc_out, il, hyp, hl, risk, blank, max_ws):
+        _mwer_check_vocab("exit_mwer_losses", enc_out.size(3))
+        loss, _, _, kept = _mwer_forward(enc_out, il, hyp, hl, risk, blank, max_ws)
+        ctx.save_for_backward(enc_out, il, hyp, hl, risk)
+        ctx.blank, ctx.max_ws, ctx.kept = blank, max_ws, kept
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        enc_out, il, hyp, hl, risk = ctx.saved_tensors
+        dlogp = torch.empty_like(enc_out)
+        _mwer_backward(enc_out, il, hyp, hl, risk, ctx.blank, ctx.max_ws, ctx.kept, grad_out, False, dlogp)
+        return dlogp, None, None, None, None, None, None
+
+
+def ctc_hyp_logp(enc_out: Tensor, hyp: Tensor, hyp_len: Tensor, input_len: Optional[Tensor] = None, blank: int = 0) -> Tensor:
+    """The exact CTC log-likelihood ``ll`` [E, B, N] of every hypothesis ``hyp[e, b, i, :hyp_len[e, b, i]]`` of N-best lists
+    [E, B, N, L] against the log-probs ``enc_out[e, b, :input_len[b]]`` (eec_ctc_hyp_logp): the full forward sum, divided by
+    nothing -- where a beam's score is a pruned sum and ``exit_ctc_losses`` divides by the target length.  -inf for an infeasible
+    hypothesis and for an absent one (``hyp_len`` -1), NaN for a length outside [-1, min(L, 255)] or a label outside the
+    vocabulary or equal to ``blank``.  One launch, no workspace; not differentiable (``exit_mwer_losses`` is).  CPU tensors take
+    the host path: torch's own ``F.ctc_loss`` in the tensor's dtype."""
+    x, il, hyp, hl, _ = _mwer_args("ctc_hyp_logp", enc_out, hyp, hyp_len, None, input_len)
+    if not x.is_cuda:
+        with torch.no_grad():
+            return _mwer_host_ll(x, il, hyp, hl, int(blank))[0]
+    E, B, Tq, V = x.shape
+    N, L = hyp.shape[2:]
+    ll = torch.empty((E, B, N), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        capi.check(capi.load().eec_ctc_hyp_logp(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), E, B, Tq, V, N, L, int(blank),
+                                                ll.data_ptr(), stream_ptr(x.device)), "eec_ctc_hyp_logp")
+    return ll
+
+
+def exit_mwer_losses(enc_out: Tensor, hyp: Tensor, hyp_len: Tensor, risk: Tensor, input_len: Optional[Tensor] = None, blank: int = 0,
+                     max_workspace_bytes: int = 2 << 30) -> Tensor:
+    """Per-exit MWER losses [E] of an encoder output [E, B, T', V] (log-probs) against N-best lists ``hyp`` [E, B, N, L] /
+    ``hyp_len`` [E, B, N] (-1: absent) with the caller's error counts ``risk`` [E, B, N] (``mwer_nbest`` makes all three):
+    ``loss[e] = mean_b sum_i phat_i (risk_i - mean risk)``, ``phat`` the softmax over the list of the hypotheses' exact CTC
+    log-likelihoods (include/eec.h has the statement and its edge cases).  Differentiable with respect to ``enc_out``: the HIP
+    backward walks the N lattices of a list over the same frames and writes one gradient row per frame.  The lists and the risks
+    are constants.  The alphas of all lattices go to a workspace; above ``max_workspace_bytes`` the batch is split over utterances
+    (the backward then redoes each chunk's forward), with the bits of the unsplit call.  fp64 and non-contiguous device input is
+    converted; CPU tensors take the host path, the same statement through torch's ``F.ctc_loss`` and autograd in the tensor's dtype."""
+    x, il, hyp, hl, risk = _mwer_args("exit_mwer_losses", enc_out, hyp, hyp_len, risk, input_len)
+    if not x.is_cuda:
+        ll, refused = _mwer_host_ll(x, il, hyp, hl, int(blank))
+        return _mwer_host_loss(ll, refused, risk).mean(1)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _ExitMwerFn.apply(x, il, hyp, hl, risk, int(blank), int(max_workspace_bytes))
+    return _mwer_forward(x, il, hyp, hl, risk, int(blank), int(max_workspace_bytes))[0]
+
+
+def mwer_nbest(enc_out: Tensor, targets: Tensor, target_len: Tensor, nbest: int = 4, beam_size: int = 10, input_len: Optional[Tensor] = None,
+               blank: int = 0, blank_skip_threshold: float = 0.95) -> MwerLists:
+    """The ``MwerLists`` of an encoder output [E, B, T', V] on the device, under ``no_grad``: one ``ctc_beam_decode(nbest=)`` call
+    over the E * B emissions, the token pitch cut to the longest hypothesis, ``lengths`` -1 for the ranks at or past the beam's
+    ``n_hyp`` and for hypotheses of more than 255 tokens, and ``risk`` the token edit distance to ``targets[b, :target_len[b]]``
+    from one ``scoring.edit_counts`` call."""
+    from . import scoring
+    if not enc_out.is_cuda:
+        raise RuntimeError("mwer_nbest runs on a HIP device only")
+    with torch.no_grad():
+        x = enc_out.detach().contiguous().float()
+        E, B, Tq, V = x.shape
+        dev = x.device
+        il = _frame_counts("mwer_nbest", "input_len", input_len, B, dev)
+        tokens, counts, scores, n_hyp = ctc_beam_decode(x.view(E * B, Tq, V), beam_size, blank, blank_skip_threshold,
+                                                        em_len=None if il is None else il.repeat(E), nbest=int(nbest))
+        present = torch.arange(int(nbest), device=dev).view(1, -1) < n_hyp.view(-1, 1)
+        lengths = torch.where(present & (counts <= MWER_MAX_LEN), counts, torch.full_like(counts, -1))
+        L = max(int(lengths.max()), 1)
+        tokens = tokens[:, :, :L].contiguous()
+        ref = targets.to(device=dev)
+        ref_of = (torch.arange(E * B, device=dev, dtype=torch.int32) % B).repeat_interleave(int(nbest))
+        dist = scoring.edit_counts(tokens.view(-1, L), lengths.clamp(min=0).reshape(-1), ref if ref.dtype == torch.int32 else ref.to(torch.int64),
+                                   target_len.to(device=dev), ref_of=ref_of).distance
+        return MwerLists(tokens.view(E, B, int(nbest), L), lengths.view(E, B, int(nbest)), dist.to(torch.float32).view(E, B, int(nbest)),
+                         scores.view(E, B, int(nbest)))
+
+
+class _ExitMwerTrainingFn(torch.autograd.Function):
+    """(CTC losses [E], MWER losses [E]) as ONE node, in the manner of ``_ExitTrainingFn``: the backward writes the CTC gradient
+    into a fresh buffer and the MWER backward adds into the same buffer."""
+
+    @staticmethod
+    def forward(ctx, enc_out, tg, tl, blank, il, hyp, hl, risk, max_ws):
+        ctc, nll, ws, ws_ptr = _ctc_forward(enc_out, tg, tl, blank, il)
+        mwer, _, _, kept = _mwer_forward(enc_out, il, hyp, hl, risk, blank, max_ws)
+        ctx.set_materialize_grads(False)  # a loss that uses one of the two outputs only: None for the other, and its launch is skipped
+        ctx.save_for_backward(enc_out, tg, tl, nll, ws, il, hyp, hl, risk)
+        ctx.blank, ctx.ws_ptr, ctx.max_ws, ctx.kept = blank, ws_ptr, max_ws, kept
+        return ctc, mwer
+
+    @staticmethod
+    def backward(ctx, grad_ctc, grad_mwer):
+        enc_out, tg, tl, nll, ws, il, hyp, hl, risk = ctx.saved_tensors
+        if getattr(ctx, "used", False):
+            raise RuntimeError("exit_mwer_training_losses: backward through the same forward twice (the CTC workspace is consumed)")
+        ctx.used = True
+        dlogp = torch.empty_like(enc_out)
+        if grad_ctc is not None:
+            _ctc_backward(enc_out, tg, tl, ctx.blank, il, nll, ctx.ws_ptr, grad_ctc, dlogp)
+        if grad_mwer is not None:
+            _mwer_backward(enc_out, il, hyp, hl, risk, ctx.blank, ctx.max_ws, ctx.kept, grad_mwer, grad_ctc is not None, dlogp)
+        elif grad_ctc is None:
+            dlogp.zero_()
+        return (dlogp,) + (None,) * 8
+
+
+def exit_mwer_training_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, lists: Optional[MwerLists] = None, nbest: int = 4,
+                              beam_size: int = 10, input_len: Optional[Tensor] = None, blank: int = 0,
+                              max_workspace_bytes: int = 2 << 30) -> Tuple[Tensor, Tensor]:
+    """``(exit_ctc_losses(enc_out, targets, target_len, blank, input_len), exit_mwer_losses(enc_out, lists.tokens, lists.lengths,
+    lists.risk, input_len, blank))``, the same values bit for bit, as one autograd node: ``ctc.sum() * lam + mwer.sum()`` is the
+    usual interpolated MWER objective, and its backward writes the CTC gradient into a fresh buffer and adds the MWER gradient into
+    it (with the MWER output unused that is the gradient of ``exit_ctc_losses`` bit for bit).  ``lists``: None -- decoded here,
+    ``mwer_nbest(enc_out, targets, target_len, nbest, beam_size, input_len, blank)`` --, or lists made earlier."""
+    if not enc_out.is_cuda:
+        raise RuntimeError("exit_mwer_training_losses runs on a HIP device only")
+    if lists is None:
+        lists = mwer_nbest(enc_out, targets, target_len, nbest, beam_size, input_len, blank)
+    x, il, hyp, hl, risk = _mwer_args("exit_mwer_training_losses", enc_out, lists.tokens, lists.lengths, lists.risk, input_len)
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return (exit_ctc_losses(x, targets, target_len, blank, input_len),
+                _mwer_forward(x, il, hyp, hl, risk, int(blank), int(max_workspace_bytes))[0])
+    _mwer_check_vocab("exit_mwer_training_losses", x.size(3))
+    dev = x.device
+    return _ExitMwerTrainingFn.apply(x, to_device(targets, dev), to_device(target_len, dev), int(blank), il, hyp, hl, risk,
+                                     int(max_workspace_bytes))

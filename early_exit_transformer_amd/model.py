@@ -24,6 +24,7 @@ from .conformer import Conformer
 from .ctc import (CtcPrefixSession, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, exit_ctc_losses, exit_distill_losses,  # noqa: F401
                   exit_training_losses, greedy_ctc)
 from .ctc import EXIT_CRITERIA, ExitStatistics, exit_route, exit_statistics, select_exits  # noqa: F401
+from .ctc import MwerLists, ctc_hyp_logp, exit_mwer_losses, exit_mwer_training_losses, mwer_nbest  # noqa: F401
 from .ctc import _exit_range, _exit_thresholds
 from .lexicon import Lexicon, TokenTrie, apply_lex, load_dict  # noqa: F401
 from .decoding import DecoderStepSession, _BatchSession, _DecoderTrainFn, _ExitSessions, beam_select  # noqa: F401

@@ -284,6 +284,59 @@ int eec_exit_distill_forward(const float* x, const int32_t* frame_len, const int
 int eec_exit_distill_backward(const float* x, const int32_t* frame_len, const int32_t* teacher, int E, int B, int T, int V, float tau,
                               const float* grad_loss, int accumulate, float* dx, void* stream);
 
+/* Minimum word error rate (MWER) training of the CTC exits: the expected risk over an N-best list (Prabhavalkar et al. 2018), the
+ * usual second stage after CTC training.  Every exit has its own list and its own error counts.  The reference has nothing like
+ * it.  A third producer of the gradient with respect to the encoder output, next to eec_ctc_loss_backward and
+ * eec_exit_distill_backward: N CTC lattices share one emission and their posteriors are folded into one gradient row.
+ *   logp [E, B, T', V] fp32 log-probs (rows are log_softmax outputs)
+ *   input_len [B] int32 on the device, or NULL for T' everywhere; Tb = clamp(input_len[b], 0, T'); frames at or past Tb are never read
+ *   hyp [E, B, N, L] int32 tokens, hyp_len [E, B, N] int32 (-1: the entry is absent), risk [E, B, N] fp32: the caller's error count of
+ *       that hypothesis (tokens, words, anything), `blank`
+ * For lattice (e, b, i) with len = hyp_len[e, b, i] >= 0:
+ *   ll[e, b, i] = log p_ctc(hyp[e, b, i, :len] | logp[e, b, :Tb]), the exact forward log-likelihood, divided by nothing: -inf when
+ *       infeasible (too few frames, repeats included; Tb == 0 with len > 0), 0 for the empty hypothesis on zero frames; -inf for an
+ *       absent entry.  The recursions run in log space with the log_add stated under eec_ctc_log_add: there is no range limit.
+ *   gamma_i[t, v] = the posterior probability that an alignment of hypothesis i emits label v at frame t = d ll_i / d logp[e, b, t, v]
+ * P = the present entries with a finite ll.  |P| == 0: loss_eb = 0 and the gradient rows are 0.  Otherwise
+ *   phat_i = softmax over P of ll_i (the maximum subtracted; 0 outside P),  rbar = mean over P of risk (the common value itself
+ *   when all risks of P are equal),  r_i = risk_i - rbar,
+ *   loss_eb = sum_i phat_i r_i,   c_i = phat_i (r_i - loss_eb)      (sum_i c_i = 0; equal risks: loss and every c_i exactly 0)
+ *       c_i is evaluated as phat_i sum_j phat_j (risk_i - risk_j): the same number, without the cancellation that leaves nothing
+ *       of it when one hypothesis holds nearly all the mass
+ *   d loss_eb / d logp[e, b, t, v] = sum_i c_i gamma_i[t, v] for t < Tb, 0 for t >= Tb
+ * which, because the c_i add up to 0, is what torch autograd returns through F.ctc_loss (whose gradient folds the softmax in): it
+ * adds into the buffer eec_ctc_loss_backward wrote.  loss[e] = mean_b loss_eb; dlogp = d( sum_e grad_loss[e] loss[e] ) / d logp.
+ * Input only the device can see: a hyp_len outside [-1, min(L, 255)], or a label outside [0, V) or equal to blank among the first
+ * len tokens, makes that entry's ll, its loss_eb and loss[e] NaN and nothing else (its list's gradient rows are zero rows).  NaN
+ * log-probs a lattice reads make its ll NaN, and with it loss_eb, loss[e] and the gradient rows t < Tb of that (e, b), and reach no
+ * other (e, b).  No input makes a kernel read out of bounds.
+ * A call serves the utterances b0 .. b0 + nb - 1 of the batch (b0 = 0, nb = B: all of it), so that a caller can bound the
+ * workspace -- the alphas of every lattice: eec_ctc_mwer_workspace_bytes(E, nb, T', N, L) bytes of 256-byte aligned device memory,
+ * 64 P floats per lattice and frame, P = 2 / 4 / 8 for min(L, 255) <= 63 / 127 / 255.  All arrays are those of the whole batch.
+ *   eec_ctc_hyp_logp: ll [E, B, N] alone -- the exact CTC score of an N-best list; no workspace.
+ *   eec_ctc_mwer_forward: ll and loss_eb [E * B] of the chunk; loss [E] is written by the call whose chunk ends the batch
+ *       (b0 + nb == B), from loss_eb of the whole batch in index order; leaves what the backward needs in the workspace.
+ *   eec_ctc_mwer_backward: the rows of dlogp [E, B, T', V] of the chunk's utterances, from the workspace its forward left (read
+ *       only); grad_loss [E] on the device.  accumulate == 0: every element of those rows is written; accumulate != 0: the
+ *       gradient is ADDED into dlogp, and rows that would be written as zeros are left untouched, as in eec_exit_distill_backward.
+ * Reproducibility: no floating-point atomics; the hypotheses of a list are folded in index order, the occurrences of a label in a
+ * hypothesis in position order; two runs return the same bits, a call on a slice of the exits returns the bits of the whole call,
+ * and so does, for ll and loss_eb, a call on a slice of the batch or on a chunk (loss and dlogp carry 1 / B).
+ * EEC_ERR_BAD_ARG, with a message, before anything is launched: N outside [1, EEC_MWER_MAX_NBEST]; a null pointer (input_len may
+ * be NULL); E, B, nb, T', V or L below 1; a chunk outside the batch; blank outside [0, V); for the backward V > 256 or V % 4 != 0
+ * (a gradient row is one float4 per lane) or a dlogp that is not 16-byte aligned.  EEC_ERR_WORKSPACE: a short or misaligned
+ * workspace. */
+#define EEC_MWER_MAX_NBEST 16
+size_t eec_ctc_mwer_workspace_bytes(int E, int B, int Tq, int N, int L);
+int eec_ctc_hyp_logp(const float* logp, const int32_t* input_len, const int32_t* hyp, const int32_t* hyp_len, int E, int B, int Tq, int V,
+                     int N, int L, int blank, float* ll, void* stream);
+int eec_ctc_mwer_forward(const float* logp, const int32_t* input_len, const int32_t* hyp, const int32_t* hyp_len, const float* risk, int E,
+                         int B, int b0, int nb, int Tq, int V, int N, int L, int blank, float* ll, float* loss_eb, float* loss,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int eec_ctc_mwer_backward(const float* logp, const int32_t* input_len, const int32_t* hyp, const int32_t* hyp_len, int E, int B, int b0,
+                          int nb, int Tq, int V, int N, int L, int blank, const void* workspace, size_t workspace_bytes,
+                          const float* grad_loss, int accumulate, float* dlogp, void* stream);
+
 /* Adaptive inference: the statistics an early-exit model chooses an utterance's exit by (average frame entropy, average frame
  * confidence, log-probability of the greedy CTC path), and the routing of a batch by one of them.
  *   x [E, B, T, V] fp32: logits or log-probs; every row is normalised inside: lp_v = x_v - lse(x), p_v = exp(lp_v)
