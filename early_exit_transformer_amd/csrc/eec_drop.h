@@ -19,6 +19,12 @@ __device__ __forceinline__ bool drop_keep(uint32_t key, uint64_t i, uint32_t thr
   h ^= h >> 16, h *= 0x7FEB352Du, h ^= h >> 15, h *= 0x846CA68Bu, h ^= h >> 16;
   return h >= thr;
 }
+// the raw 32-bit word drop_keep compares with its threshold, for integer draws (specaug.hip): uniform in [0, m) = word * m >> 32
+__device__ __forceinline__ uint32_t drop_word(uint32_t key, uint64_t i) {
+  uint32_t h = (uint32_t)i * 0x9E3779B1u + (uint32_t)(i >> 32) * 0x85EBCA77u + key;
+  h ^= h >> 16, h *= 0x7FEB352Du, h ^= h >> 15, h *= 0x846CA68Bu, h ^= h >> 16;
+  return h;
+}
 __device__ __forceinline__ uint32_t drop_thr(float p) {
   const double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;

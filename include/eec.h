@@ -820,6 +820,64 @@ int eec_edit_distance(const int32_t* hyp, const int32_t* hyp_len, int n_pairs, i
                       const int32_t* ref_len, int n_refs, int ref_pitch, const int32_t* ref_of, int32_t* counts, uint8_t* ops,
                       int32_t* n_ops, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- SpecAugment: time warp, frequency and time masks of a mel batch (csrc/specaug.hip) -------------------------------------------
+ * The stage between the mel front end and the encoder in training; the reference has none (its collate hands the mel over as it
+ * is).  Two launches: eec_specaug_draw writes one row of integer parameters per utterance, eec_specaug_apply reads such rows --
+ * drawn or prescribed by the caller alike -- and writes the augmented copy.
+ *
+ *   mel, out [B][n_mels][T] fp32, T contiguous (what eec_frontend_forward writes and the encoder entries read); out != mel.
+ *   frame_len [B] int32 or NULL: valid mel frames per utterance, clamped to [0, T]; NULL: T everywhere.  n = the clamped length.
+ *       Frames t >= n are copied through bit for bit and are never read for a frame t < n: a NaN there reaches nothing.
+ *   params [B][P] int32, P = 2 + 2 * n_freq_masks + 2 * n_time_masks (n_freq_masks <= EEC_SPECAUG_MAX_FREQ_MASKS, n_time_masks <=
+ *       EEC_SPECAUG_MAX_TIME_MASKS):   c, w,   f0, fw per frequency mask,   t0, tw per time mask.   (c, w) = (0, 0): no warp.
+ *
+ * The draw is a pure function of (seed, utt_offset + b, slot) through the dropout generator (csrc/eec_drop.h, the contract above at
+ * eec_train_forward): u(slot) = lowbias32(lo(i) * C1 + hi(i) * C2 + key(seed, EEC_SPECAUG_SITE)) with i = (utt_offset + b) * 64 + slot
+ * in 64-bit wrap-around arithmetic, and a uniform integer in [0, m) is (uint64) u * m >> 32.  Slots, W = time_warp_window,
+ * F = freq_mask_width, Tmax = time_mask_width, ratio = time_mask_ratio:
+ *   0, 1          if W > 0 and n > 2 W:  c = W + [0, n - 2 W),  then  w = c - W + 1 + [0, 2 W);  otherwise c = w = 0
+ *   2 + 2 k, + 1  frequency mask k:  fw = [0, min(F, n_mels) + 1),  then  f0 = [0, n_mels - fw + 1)
+ *   2 + 2 n_freq_masks + 2 k, + 1   time mask k:  tw = [0, min(Tmax, n, floor((double) ratio * n)) + 1),  then  t0 = [0, n - tw + 1)
+ * so c lies in [W, n - W), w in [c - W + 1, c + W], every mask inside its axis, and -- utt_offset entering the index -- a call on a
+ * slice of the batch with utt_offset advanced by the slice's start returns the rows of the whole call.
+ *
+ * The warp (applied when 1 <= c <= n - 1 and 1 <= w <= n - 1, ignored otherwise) maps the source frames [0, c) onto the output
+ * frames [0, w) and the source frames [c, n) onto the output frames [w, n): torch.nn.functional.interpolate(align_corners=False) of
+ * the two segments separately, as ESPnet's and lhotse's time_warp do.  For output frame d of a segment of n_in source and n_out output
+ * frames, in exact integers:
+ *     num = (2 d + 1) * n_in - n_out   (EEC_SPECAUG_LINEAR: clamped at 0)      den = 2 * n_out
+ *     i = floor(num / den)             fraction f = (num - i * den) / den  in [0, 1)
+ *   EEC_SPECAUG_LINEAR:   taps i, min(i + 1, n_in - 1);  weights 1 - f, f
+ *   EEC_SPECAUG_BICUBIC:  taps i - 1, i, i + 1, i + 2, each clamped to [0, n_in - 1];  cubic convolution with A = -0.75:
+ *       weights k2(f + 1), k1(f), k1(1 - f), k2(2 - f),   k1(x) = ((A + 2) x - (A + 3)) x x + 1,   k2(x) = ((A x - 5 A) x + 8 A) x - 4 A
+ * Tap indices are relative to the segment and never cross c.  f and the weights are evaluated in fp64, each weight is rounded once to
+ * fp32, and the taps are combined in fp32 in index order (the compiler may fuse the multiply-adds):
+ *     |out - exact| <= 6 * 2^-24 * sum_k |w_k| |x_k|     (one rounding per weight, one per product, three additions).
+ *
+ * The masks are applied after the warp, to frames t < n only: an element whose mel row lies in some [f0, f0 + fw) or whose frame lies
+ * in some [t0, t0 + tw) becomes mask_value.  Parameters are never trusted: mask ranges are clipped to [0, n_mels) and [0, n) (sums in
+ * 64 bits; an empty or negative width masks nothing), a warp outside the range above is ignored, so nothing outside an utterance's
+ * valid frames is ever read, whatever params holds.
+ *
+ * eec_specaug_draw: one work-item per (utterance, slot group).  eec_specaug_apply: one workgroup per (tile of 128 output frames, group
+ * of 32 mel rows, utterance); with a warp one work-item per output frame computes segment, taps and weights once and walks down the
+ * rows; without one the rows move as aligned 16-byte quads (row heads and tails, and pointers off a 16-byte boundary, as single
+ * floats).  Masked elements are not loaded.  No atomics, no LDS, no scratch: two runs are bit-identical.
+ * EEC_ERR_BAD_ARG, before any device work: B < 0, n_mels < 1, T < 1, a mask count below 0 or over its limit; draw: W < 0, F < 0,
+ * Tmax < 0, a negative, NaN or infinite ratio, null params; apply: a mode other than the two, a NaN mask_value, null mel, params or
+ * out, out == mel.  B == 0 is a successful no-op.  Errors through eec_last_error().  No allocation, no synchronisation;
+ * graph-capturable. */
+#define EEC_SPECAUG_MAX_FREQ_MASKS 8
+#define EEC_SPECAUG_MAX_TIME_MASKS 16
+#define EEC_SPECAUG_SITE 0x53504341u
+#define EEC_SPECAUG_LINEAR 0
+#define EEC_SPECAUG_BICUBIC 1
+int eec_specaug_draw(const int32_t* frame_len, int B, int n_mels, int T, uint64_t seed, uint64_t utt_offset, int time_warp_window,
+                     int n_freq_masks, int freq_mask_width, int n_time_masks, float time_mask_ratio, int time_mask_width,
+                     int32_t* params, void* stream);
+int eec_specaug_apply(const float* mel, const int32_t* frame_len, const int32_t* params, int B, int n_mels, int T, int n_freq_masks,
+                      int n_time_masks, int mode, float mask_value, float* out, void* stream);
+
 /* Mel front end(SURVEY 8f row f3): replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
  * n_mels, n_stft = 513; htk scale, no normalisation), NO log -- on the device, as an exact-fp32 MFMA transform.
