@@ -1,19 +1,26 @@
-"""SpecAugment on the device: the stage between the mel front end and the encoder in training (include/eec.h, "SpecAugment";
-csrc/specaug.hip).
+"""Augmentation on the device: SpecAugment between the mel front end and the encoder (include/eec.h, "SpecAugment";
+csrc/specaug.hip) and speed perturbation / resampling in front of the mel front end (include/eec.h, "Resampling / speed perturbation";
+csrc/resample.hip).
 
 * ``spec_augment``   time warp, frequency masks and time masks of a mel batch ``[B, n_mels, T]``: one launch that draws a row of
   integer parameters per utterance from ``(seed, utt_offset + b)`` (the dropout generator, counter-based) and one that applies them
   -- or rows the caller prescribes.  No host synchronisation, graph-capturable.  CPU tensors take a host path that is the same
   statement in NumPy.
 * ``SpecAugment``    the module form: identity in eval mode, fresh parameters every call in train mode, a resumable call counter.
+* ``resample``       polyphase sinc resampling (Hann window) of a waveform batch ``[B, L]`` from one sample rate to another:
+  torchaudio's ``functional.resample``, every utterance as if resampled alone and padded afterwards.
+* ``speed_perturb``  the same kernel with one ratio per utterance, drawn from ``(seed, utt_offset + b)`` among ``factors`` or
+  prescribed: torchaudio's ``transforms.Speed``.  ``SpeedPerturb`` is its module form, built like ``SpecAugment``.
 
 The warp is ``F.interpolate(align_corners=False)`` of the frames left and right of a drawn centre, separately (ESPnet's and lhotse's
-``time_warp``), bicubic or linear; frames at or past an utterance's length are copied through and never read.  Out of scope: speed
-perturbation, mean-value fill, a backward (the input is data)."""
+``time_warp``), bicubic or linear; frames at or past an utterance's length are copied through and never read.  Out of scope:
+mean-value fill, ``sinc_interp_kaiser``, tempo change without pitch change, volume and noise perturbation, a backward (the input is
+data)."""
 from __future__ import annotations
 
+import ctypes as C
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -232,6 +239,234 @@ class SpecAugment(nn.Module):
         self.calls += 1
         out, self.last_params = spec_augment(mel, lengths, seed=seed, utt_offset=utt_offset, **self.kwargs)
         return out
+
+    def extra_repr(self) -> str:
+        return ", ".join(f"{k}={v!r}" for k, v in self.kwargs.items())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# resampling and speed perturbation
+# ---------------------------------------------------------------------------------------------------------------------------
+RESAMPLE_MAX_RATIOS, RESAMPLE_MAX_RATE, RESAMPLE_MAX_LPW = 8, 640, 64  # EEC_RESAMPLE_MAX_RATIOS, _MAX_RATE, _MAX_LPW
+RESAMPLE_MAGIC = 0x52534D50                                             # EEC_RESAMPLE_MAGIC
+SPEED_SITE = 0x53504545                                                 # EEC_SPEED_SITE
+MAX_SAMPLES = 1 << 30
+
+
+class ResamplePlan:
+    """The image ``eec_resample_plan`` builds for ``ratios`` (include/eec.h has the layout): ``image`` int32 on the host, ``ratios``
+    reduced, ``on(device)`` the uploaded copy, made once per device."""
+
+    def __init__(self, ratios: Sequence[Tuple[int, int]], lowpass_filter_width: int, rolloff: float):
+        lib = capi.load()
+        R = len(ratios)
+        orig, new = (C.c_int32 * R)(*[o for o, _ in ratios]), (C.c_int32 * R)(*[n for _, n in ratios])
+        nbytes = lib.eec_resample_plan_bytes(R, orig, new, lowpass_filter_width, rolloff)
+        if nbytes == 0:
+            raise ValueError(lib.eec_last_error().decode(errors="replace"))
+        self.image = np.zeros(nbytes // 4, dtype=np.int32)
+        capi.check(lib.eec_resample_plan(R, orig, new, lowpass_filter_width, rolloff, self.image.ctypes.data, nbytes), "eec_resample_plan")
+        self.ratios = [(int(self.image[4 + 8 * r]), int(self.image[5 + 8 * r])) for r in range(R)]
+        self._dev: Dict[torch.device, Tensor] = {}
+
+    def on(self, dev: torch.device) -> Tensor:
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = torch.from_numpy(self.image).to(dev)
+        return t
+
+    def out_samples(self, L: int) -> int:
+        """The width that holds every utterance of ``L`` samples under every ratio."""
+        return max((n * L + o - 1) // o for o, n in self.ratios)
+
+    def table(self, r: int):
+        """``(o, n, width, K, first [n], count [n], weights: n fp32 arrays)`` of ratio ``r``."""
+        o, n, width, K, phases, weights = (int(v) for v in self.image[4 + 8 * r:10 + 8 * r])
+        ph = self.image[phases:phases + 3 * n].reshape(n, 3)
+        w = self.image[weights:].view(np.float32)
+        return o, n, width, K, ph[:, 0].copy(), ph[:, 1].copy(), [w[a:a + c] for _, c, a in ph]
+
+
+_plans: Dict[tuple, ResamplePlan] = {}
+
+
+def resample_plan(ratios: Sequence[Tuple[int, int]], lowpass_filter_width: int = 6, rolloff: float = 0.99) -> ResamplePlan:
+    """The cached plan of ``ratios`` [(orig, new), ...]; ``ValueError`` for what the library refuses."""
+    if isinstance(lowpass_filter_width, bool) or int(lowpass_filter_width) != lowpass_filter_width or \
+            not 1 <= int(lowpass_filter_width) <= RESAMPLE_MAX_LPW:
+        raise ValueError(f"resample: lowpass_filter_width must be an integer in [1, {RESAMPLE_MAX_LPW}], got {lowpass_filter_width!r}")
+    rolloff = float(rolloff)
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"resample: rolloff must lie in (0, 1], got {rolloff}")
+    if not 1 <= len(ratios) <= RESAMPLE_MAX_RATIOS:
+        raise ValueError(f"resample: between 1 and {RESAMPLE_MAX_RATIOS} ratios per call, got {len(ratios)}")
+    red = []
+    for o, n in ratios:
+        if int(o) != o or int(n) != n or o < 1 or n < 1:
+            raise ValueError(f"resample: sample rates must be positive integers, got {o!r} and {n!r}")
+        g = math.gcd(int(o), int(n))
+        if max(int(o), int(n)) // g > RESAMPLE_MAX_RATE:
+            raise ValueError(f"resample: ratio {int(o) // g} / {int(n) // g} exceeds {RESAMPLE_MAX_RATE} after reduction")
+        red.append((int(o) // g, int(n) // g))
+    key = (tuple(red), int(lowpass_filter_width), rolloff)
+    plan = _plans.get(key)
+    if plan is None:
+        if len(_plans) > 15:
+            _plans.clear()
+        plan = _plans[key] = ResamplePlan(red, int(lowpass_filter_width), rolloff)
+    return plan
+
+
+def speed_ratios(factors: Sequence[float], sample_rate: int) -> list:
+    """``(int(f * sample_rate), sample_rate)`` per factor, as ``torchaudio.transforms.Speed`` computes it."""
+    if len(factors) == 0:
+        raise ValueError("speed_perturb: factors is empty")
+    if int(sample_rate) != sample_rate or sample_rate < 1:
+        raise ValueError(f"speed_perturb: sample_rate must be a positive integer, got {sample_rate!r}")
+    out = []
+    for f in factors:
+        if not (isinstance(f, (int, float)) and math.isfinite(f) and f > 0 and int(f * sample_rate) >= 1):
+            raise ValueError(f"speed_perturb: a factor must be positive and finite, got {f!r}")
+        out.append((int(f * sample_rate), int(sample_rate)))
+    return out
+
+
+def _host_choice(seed: int, utt_offset: int, B: int, R: int) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        at = (np.arange(B, dtype=np.uint64) + np.uint64(utt_offset & _M64)) * np.uint64(64)
+    u = _words(_key(seed, SPEED_SITE), at).astype(np.uint64)
+    return ((u * np.uint64(R)) >> np.uint64(32)).astype(np.int32)
+
+
+def _host_resample(wave: np.ndarray, n_all: np.ndarray, choice: np.ndarray, plan: ResamplePlan, L_out: int):
+    """The statement in NumPy: per phase, the taps in order, one fp32 multiply and one fp32 add each."""
+    B = wave.shape[0]
+    out, out_len = np.zeros((B, L_out), dtype=np.float32), np.zeros(B, dtype=np.int64)
+    tables: Dict[int, tuple] = {}
+    for b in range(B):
+        length, c = int(n_all[b]), int(choice[b])
+        if not 0 <= c < len(plan.ratios) or plan.ratios[c] == (1, 1):
+            out_len[b] = min(length, L_out)
+            out[b, :out_len[b]] = wave[b, :out_len[b]]
+            continue
+        o, n, width, K, first, count, weights = tables.setdefault(c, plan.table(c))
+        m = out_len[b] = min((n * length + o - 1) // o, L_out)
+        if m == 0:
+            continue
+        x = np.zeros(((m - 1) // n + 1) * o + K, dtype=np.float32)  # x[g + width] = sample g; zeros outside [0, length)
+        x[width:width + length] = wave[b, :length]
+        for j in range(min(n, m)):
+            start = np.arange((m - 1 - j) // n + 1, dtype=np.int64) * o + int(first[j])
+            acc = np.zeros(start.shape[0], dtype=np.float32)
+            for k in range(int(count[j])):
+                acc = acc + weights[j][k] * x[start + k]
+            out[b, j:m:n] = acc
+    return out, out_len
+
+
+def _resample_with(who: str, wave: Tensor, lengths: Optional[Tensor], plan_of, choice, seed: int, utt_offset: int):
+    """Checks, then the host path or the launches.  ``plan_of()`` builds the plan once the tensors are known to be sound; ``choice``
+    None: drawn; an integer: that ratio for every utterance."""
+    if not isinstance(wave, Tensor) or wave.dim() not in (1, 2) or wave.dtype != torch.float32:
+        raise ValueError(f"{who}: wave must be an fp32 tensor [B, L] or [L], got {getattr(wave, 'dtype', None)} {tuple(getattr(wave, 'shape', ()))}")
+    squeeze = wave.dim() == 1
+    if squeeze:
+        wave = wave.unsqueeze(0)
+    B, L = wave.shape
+    if L > MAX_SAMPLES:
+        raise ValueError(f"{who}: at most 2^30 samples per utterance, got {L}")
+    dev = wave.device
+    wave = wave.contiguous()
+    if lengths is not None:
+        if not isinstance(lengths, Tensor) or lengths.dtype not in (torch.int32, torch.int64) or lengths.numel() != B or lengths.dim() > 1:
+            raise ValueError(f"{who}: lengths must be an int32 or int64 tensor of {B} entries")
+        lengths = capi.to_device(lengths.reshape(B), dev, torch.int64).clamp(0, L).contiguous()
+    if isinstance(choice, int):
+        choice = torch.full((B,), choice, dtype=torch.int32, device=dev)
+    elif choice is not None:
+        if not isinstance(choice, Tensor) or choice.dtype not in (torch.int32, torch.int64) or choice.numel() != B or choice.dim() > 1:
+            raise ValueError(f"{who}: choice must be an int32 or int64 tensor of {B} entries")
+        choice = choice.reshape(B).to(dev).clamp(-1, RESAMPLE_MAX_RATIOS).to(torch.int32).contiguous()  # outside the plan: a copy
+    plan = plan_of()
+    R, L_out = len(plan.ratios), plan.out_samples(L)
+    if L_out >= 1 << 31:
+        raise ValueError(f"{who}: {L} samples grow to {L_out}, past 2^31 - 1")
+
+    if not wave.is_cuda:
+        n = np.full(B, L, dtype=np.int64) if lengths is None else lengths.numpy()
+        if choice is None:
+            choice = torch.from_numpy(_host_choice(seed, utt_offset, B, R))
+        out, out_len = _host_resample(wave.numpy(), n, choice.numpy(), plan, L_out)
+        out, out_len = torch.from_numpy(out), torch.from_numpy(out_len)
+    else:
+        lib = capi.load()
+        image = plan.on(dev)
+        len_ptr = None if lengths is None or B == 0 else lengths.data_ptr()
+        out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
+        out_len = torch.empty((B,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            if choice is None:
+                choice = torch.empty((B,), dtype=torch.int32, device=dev)
+                capi.check(lib.eec_speed_draw(len_ptr, B, L, seed, utt_offset, image.data_ptr(), choice.data_ptr(), out_len.data_ptr(),
+                                              capi.stream_ptr(dev)), "eec_speed_draw")
+            capi.check(lib.eec_resample(wave.data_ptr(), len_ptr, choice.data_ptr(), B, L, image.data_ptr(), out.data_ptr(), L_out,
+                                        out_len.data_ptr(), capi.stream_ptr(dev)), "eec_resample")
+    return (out[0], out_len[0], choice[0]) if squeeze else (out, out_len, choice)
+
+
+def resample(wave: Tensor, lengths: Optional[Tensor] = None, *, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
+             rolloff: float = 0.99) -> Tuple[Tensor, Tensor]:
+    """``(out, out_len)``: ``wave`` [B, L] or [L] (fp32) resampled from ``orig_freq`` to ``new_freq`` -- torchaudio's
+    ``functional.resample`` with ``sinc_interp_hann`` -- as ``out`` [B, ceil(new * L / orig)] and the int64 lengths
+    ``ceil(new * lengths / orig)`` (what ``MelFrontend`` takes).  ``lengths`` [B]: valid samples, clamped to [0, L]; None: L.  Samples
+    at or past a length are never read, outputs at or past an ``out_len`` are 0.0: every utterance comes out as if resampled alone
+    and padded afterwards.  Equal rates return a copy.  The reduced ratio may not exceed 640 on either side (8 / 16 / 22.05 / 24 / 32 /
+    44.1 / 48 kHz pairs all fit).  No host synchronisation; a CPU tensor takes the NumPy host path, bit-identical for finite input."""
+    out, out_len, _ = _resample_with("resample", wave, lengths, lambda: resample_plan([(orig_freq, new_freq)], lowpass_filter_width, rolloff), 0, 0, 0)
+    return out, out_len
+
+
+def speed_perturb(wave: Tensor, lengths: Optional[Tensor] = None, *, seed: int, utt_offset: int = 0,
+                  factors: Sequence[float] = (0.9, 1.0, 1.1), sample_rate: int = 16000, choice: Optional[Tensor] = None,
+                  lowpass_filter_width: int = 6, rolloff: float = 0.99) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(out, out_len, choice)``: every utterance of ``wave`` [B, L] or [L] played at one of ``factors`` -- resampled by
+    ``(int(f * sample_rate), sample_rate)``, torchaudio's ``transforms.Speed``, so 0.9 makes it longer and lower --, the int64 lengths
+    and the int32 index into ``factors`` each utterance took.  ``choice`` None: drawn uniformly from ``(seed, utt_offset + b)``, so a
+    call on a slice of the batch with ``utt_offset`` advanced returns the rows of the whole call.  Given: applied as it is; an entry
+    outside the factors copies its utterance.  ``out`` is as wide as the slowest factor needs for ``L`` samples, whatever was drawn
+    (nothing is read back).  At most eight factors; the rest as ``resample``."""
+    return _resample_with("speed_perturb", wave, lengths, lambda: resample_plan(speed_ratios(factors, sample_rate), lowpass_filter_width, rolloff),
+                          choice, int(seed) & _M64, int(utt_offset) & _M64)
+
+
+class SpeedPerturb(nn.Module):
+    """``wave, n = speed(wave, n)`` in front of the mel front end: ``speed_perturb`` with the arguments given here in train mode, the
+    input and its lengths in eval mode.  The call counter, the seed rule (call k draws from ``seed + k * 0x9E3779B97F4A7C15``) and
+    ``get_state`` / ``set_state`` are ``SpecAugment``'s; ``last_choice`` holds the choices of the last train-mode call.  No parameters,
+    no buffers.  The plan is uploaded at the first call on a device: make that call before capturing a graph."""
+
+    def __init__(self, seed: Optional[int] = None, factors: Sequence[float] = (0.9, 1.0, 1.1), sample_rate: int = 16000,
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        super().__init__()
+        resample_plan(speed_ratios(factors, sample_rate), lowpass_filter_width, rolloff)  # refused here rather than at the first step
+        self.seed = capi.new_seed() if seed is None else int(seed)
+        self.kwargs = dict(factors=tuple(factors), sample_rate=sample_rate, lowpass_filter_width=lowpass_filter_width, rolloff=rolloff)
+        self.calls = 0
+        self.last_choice: Optional[Tensor] = None
+
+    def get_state(self) -> Dict[str, int]:
+        return {"seed": self.seed, "calls": self.calls}
+
+    def set_state(self, state: Dict[str, int]) -> None:
+        self.seed, self.calls = int(state["seed"]), int(state["calls"])
+
+    def forward(self, wave: Tensor, lengths: Optional[Tensor] = None, utt_offset: int = 0) -> Tuple[Tensor, Optional[Tensor]]:
+        if not self.training:
+            return wave, lengths
+        seed = (self.seed + self.calls * 0x9E3779B97F4A7C15) & _M64
+        self.calls += 1
+        out, out_len, self.last_choice = speed_perturb(wave, lengths, seed=seed, utt_offset=utt_offset, **self.kwargs)
+        return out, out_len
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={v!r}" for k, v in self.kwargs.items())

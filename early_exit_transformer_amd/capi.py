@@ -103,6 +103,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_lexicon_pack_bytes", "eec_lexicon_pack", "eec_lexicon_nearest_workspace_bytes", "eec_lexicon_nearest",
            "eec_edit_distance_workspace_bytes", "eec_edit_distance",
            "eec_specaug_draw", "eec_specaug_apply",
+           "eec_resample_plan_bytes", "eec_resample_plan", "eec_speed_draw", "eec_resample_lengths", "eec_resample",
            "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
            "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
            "eec_train_forward", "eec_train_backward", "eec_train_backward_ex", "eec_train_gemm",
@@ -240,6 +241,16 @@ def load() -> C.CDLL:
                                      C.c_int, C.c_void_p, C.c_void_p]
     # mel, frame_len, params; B, n_mels, T, n_freq_masks, n_time_masks, mode; mask_value; out, stream
     lib.eec_specaug_apply.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
+    # R, orig, new, lowpass_filter_width, rolloff (; image, its bytes)
+    lib.eec_resample_plan_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double]
+    lib.eec_resample_plan_bytes.restype = C.c_size_t
+    lib.eec_resample_plan.argtypes = lib.eec_resample_plan_bytes.argtypes + [C.c_void_p, C.c_size_t]
+    # lengths; B, L; seed, utt_offset; plan, choice, out_len, stream
+    lib.eec_speed_draw.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # lengths, choice; B, L; plan, out_len, stream
+    lib.eec_resample_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    # wave, lengths, choice; B, L; plan, out; L_out; out_len, stream
+    lib.eec_resample.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.eec_frontend_last_error.restype = C.c_char_p
     lib.eec_frontend_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.eec_frontend_destroy.argtypes = [C.c_void_p]

@@ -878,6 +878,72 @@ int eec_specaug_draw(const int32_t* frame_len, int B, int n_mels, int T, uint64_
 int eec_specaug_apply(const float* mel, const int32_t* frame_len, const int32_t* params, int B, int n_mels, int T, int n_freq_masks,
                       int n_time_masks, int mode, float mask_value, float* out, void* stream);
 
+/* ---- Resampling / speed perturbation: batched polyphase sinc resampling of a waveform batch (csrc/resample.hip) -------------------
+ * The waveform-level stage in front of the mel front end: speed perturbation by the customary factors 0.9 / 1.0 / 1.1 (Ko et al. 2015)
+ * and sample-rate conversion.  The reference has neither; the definition is torchaudio's functional.resample / transforms.Speed with
+ * resampling_method "sinc_interp_hann".
+ *
+ * A ratio is (orig, new) in positive integers, reduced by their gcd to (o, n); a speed factor f at sample rate sr is the ratio
+ * (int(f * sr), sr), as transforms.Speed computes it (16 kHz: 0.9 -> (9, 10), 1.1 -> (11, 10)).  With lpw = lowpass_filter_width
+ * (default 6), rolloff (default 0.99) and a Hann window:
+ *     base  = min(o, n) * rolloff            width = ceil(lpw * o / base)            K = 2 * width + o
+ *     t(j, k) = clamp((-j / n + (k - width) / o) * base, -lpw, +lpw)                  j = 0 .. n - 1 (phase), k = 0 .. K - 1 (tap)
+ *     h(j, k) = sinc(pi * t) * cos(pi * t / (2 * lpw))^2 * base / o                   sinc(0) = 1
+ *               evaluated in fp64 on the host, rounded once to fp32
+ *     y[i]    = sum_{k = 0 .. K - 1} h(i % n, k) * x[(i / n) * o + k - width]         x outside [0, len) is 0
+ *     out_len = ceil(n * len / o) = (n * len + o - 1) / o                             int64 arithmetic
+ * The sum is fp32: each tap is one rounded multiply and one rounded add (no fused multiply-add), the taps run in the order
+ * k = 0, 1, ... from +0.  Taps whose fp32 weight is exactly zero may be skipped: the clamp makes every tap outside the window round to
+ * zero, and skipping them cannot change the bits for finite input.  The ratio (1, 1) is a bit-for-bit copy (torchaudio returns its
+ * input; the formula would low-pass it).  Samples at or past an utterance's length are never read, so a NaN there reaches nothing;
+ * output positions at or past out_len[b] are written as 0.0, the collate's padding value; the result for utterance b equals
+ * resampling that utterance alone and padding afterwards.  A non-finite sample inside the valid region is unspecified.
+ *
+ * The plan (host only, no device call): eec_resample_plan writes one image of int32 words for R <= EEC_RESAMPLE_MAX_RATIOS ratios;
+ * eec_resample_plan_bytes returns its size (0 with a message when the arguments are refused).  The caller uploads it once.
+ *     word 0 EEC_RESAMPLE_MAGIC, 1 R, 2 the image's size in words, 3 lpw
+ *     ratio r, words 4 + 8 r ..:  o, n, width, K, phases, weights, total, most
+ *         phases: word offset of n triples (first, count, at): phase j's non-zero fp32 weights are the taps first .. first + count - 1,
+ *                 stored at words weights + at ..;  zero heads and tails are not stored (zeros between two non-zero taps are)
+ *         weights: word offset of the ratio's `total` fp32 weights, phase after phase;  most: the largest count
+ * A call carries one plan; choice [B] int32 says which of its ratios each utterance takes.  A choice outside [0, R) is treated as a
+ * copy, and the kernel never indexes the plan with it.
+ *
+ * The draw: choice[b] = (uint64) word(key(seed, EEC_SPEED_SITE), (utt_offset + b) * 64 + 0) * R >> 32, word and key being those of
+ * the dropout generator (csrc/eec_drop.h; the contract at eec_train_forward), exactly as eec_specaug_draw uses them; the same launch
+ * writes out_len[b].  utt_offset enters the index, so a call on a slice of the batch with utt_offset advanced returns the rows of
+ * the whole call.  eec_resample_lengths writes out_len for prescribed choices.
+ *
+ *   wave [B][L] fp32, out [B][L_out] fp32, both contiguous in time, out != wave.  L_out is the caller's: max_r ceil(n_r * L / o_r) of
+ *       the plan's ratios holds every utterance; an out_len beyond L_out is cut to it.
+ *   lengths [B] int64 or NULL: valid samples per utterance, clamped to [0, L]; NULL: L everywhere.
+ *   choice [B] int32; out_len [B] int64 (eec_resample: written too, may be NULL).
+ * eec_resample: one workgroup of 256 work-items per (tile of 1024 output samples, utterance).  The tile's input window --
+ * (1024 / n) * o + K samples -- is staged in LDS with zeros outside [0, len) when it fits 4096 floats, and the ratio's weights when
+ * they fit 6144 floats; otherwise they are read through the caches.  One work-item per output sample, four rounds per tile, so a
+ * wave stores 256 consecutive bytes; a copy moves 16-byte quads where both rows are 16-byte aligned.  Workgroups past an utterance's
+ * out_len only write zeros.  No atomics, every output a pure
+ * function of its utterance: two runs, a split batch and lengths = NULL against lengths all L return the same bits.
+ * EEC_ERR_BAD_ARG, before any device work, through eec_last_error(): plan -- R outside [1, EEC_RESAMPLE_MAX_RATIOS], a rate below 1,
+ * max(o, n) > EEC_RESAMPLE_MAX_RATE after reduction, lpw outside [1, EEC_RESAMPLE_MAX_LPW], rolloff outside (0, 1], a null pointer,
+ * (EEC_ERR_WORKSPACE) a short image; device entries -- B < 0, L outside [0, 2^30], L_out < 0, a null pointer where one is needed,
+ * out == wave.  B == 0 is a successful no-op.  No allocation, no synchronisation, nothing read back; graph-capturable.
+ * Not served: sinc_interp_kaiser, a backward (the input is data), tempo change without pitch change, volume or noise perturbation. */
+#define EEC_RESAMPLE_MAX_RATIOS 8
+#define EEC_RESAMPLE_MAX_RATE 640
+#define EEC_RESAMPLE_MAX_LPW 64
+#define EEC_RESAMPLE_MAGIC 0x52534D50
+#define EEC_SPEED_SITE 0x53504545u
+size_t eec_resample_plan_bytes(int R, const int32_t* orig, const int32_t* new_, int lowpass_filter_width, double rolloff);
+int eec_resample_plan(int R, const int32_t* orig, const int32_t* new_, int lowpass_filter_width, double rolloff, void* image,
+                      size_t image_bytes);
+int eec_speed_draw(const int64_t* lengths, int B, int L, uint64_t seed, uint64_t utt_offset, const void* plan, int32_t* choice,
+                   int64_t* out_len, void* stream);
+int eec_resample_lengths(const int64_t* lengths, const int32_t* choice, int B, int L, const void* plan, int64_t* out_len,
+                         void* stream);
+int eec_resample(const float* wave, const int64_t* lengths, const int32_t* choice, int B, int L, const void* plan, float* out,
+                 int L_out, int64_t* out_len, void* stream);
+
 /* Mel front end(SURVEY 8f row f3): replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
  * n_mels, n_stft = 513; htk scale, no normalisation), NO log -- on the device, as an exact-fp32 MFMA transform.
