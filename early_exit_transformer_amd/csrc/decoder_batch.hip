@@ -24,8 +24,17 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------------
 // Y[e][m][n] (+)= act( LN_e?(X[e][m]) . W_e[n] + bias_e[n] ),  m < M = B * R, on v_mfma_f32_32x32x16_f16 with f16x3 operands:
 // x = hi + lo, hi = fp16(x) (saturated at the fp16 maximum, as the inference path's split in eec_device.h), lo = fp16(x - hi);
-// hi.hi + hi.lo + lo.hi with fp32 accumulation, ~2^-21 relative per product.  (The bf16x3 form, 2^-16, moved the final scores of
-// a 12-step search by 1.5e-4 against the fp32 step decoder; this one keeps them within 1e-4.)
+// hi.hi + hi.lo + lo.hi with fp32 accumulation, ~2^-21 relative per product WHILE lo is a normal fp16 number: below 2^-14 it
+// keeps absolute, not relative, precision (the device does not flush fp16 subnormals; their spacing is 2^-24).  Unscaled, that
+// already holds for |x| < 2^-3, and a decoder whose feed-forward or value weights are of the order 1e-4 .. 1e-3 lost the
+// precision of the split: tests/test_gpu_aed_step.py (weight domain) measured 0.017 / 0.077 / 1.30 of its bound -- twice
+// 2e-5 * max(10, max |logp|) -- on weights scaled by 2^0 / 2^-4 / 2^-8.  So the WEIGHT fragments are multiplied by kWScale = 2^8
+// before the split (exact; the factor the stem's packed weights carry, DESIGN.md "Stem domains") and the summed accumulators by
+// 2^-8 in the epilogue: weights keep the full split down to |w| ~ 2^-11 and saturate beyond |w| = 255 (the decoders of the AED
+// tests stay below 1; rescaled by 2^8, below 16).  With it the same test reads 0.014 / 0.017 / 0.112.  The ACTIVATIONS are split
+// as they are, which is what is left at 2^-8 (hidden rows of the order 4e-3): a row whose entries fall far below 2^-3 keeps
+// fewer bits, and a per-row exponent would be the next step if a checkpoint needed it.  (The bf16x3 form, 2^-16, moved the final
+// scores of a 12-step search by 1.5e-4 against the fp32 step decoder; this one keeps them within 1e-4.)
 // Workgroup = 64 rows x 32 columns of one exit (grid: column tiles, row tiles, exit).  The 4 waves split the contraction
 // (wave w takes the 16-deep k-steps w, w + 4, ...), each with 4 k-steps of loads in flight: at B = 1 a call is a chain of
 // dependent memory round trips, and the split cuts it 4-fold; the partial tiles are summed through LDS in the epilogue.
@@ -35,6 +44,7 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kTM = 64, kTN = 32, kKB = 4;  // rows, columns of a workgroup; k-steps in flight per wave
 constexpr float kHalfMax = 65504.0f;
+constexpr float kWScale = 256.0f;  // on the weight fragments before the split, undone on the accumulator sum
 
 struct ExitLinear {
   const float *W, *bias;     // [N][K], [N]
@@ -133,7 +143,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
         bv[i] = (bv[i] - mub) * rsb * g + be;
       }
       h8 wh, wl, ah, al, bh, bl;
-      split8(wv[i], wh, wl);
+      split8(wv[i] * kWScale, wh, wl);
       split8(av[i], ah, al);
       split8(bv[i], bh, bl);
       acc0 = mac3(acc0, ah, al, wh, wl);
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(256) void batch_linear_kernel(BatchLinearArgs a) {
   const float bias = ex.bias ? ex.bias[nc] : 0.0f;
   float* Y = a.Y + blockIdx.z * a.y_e + nc;
   for (int row = tid >> 5; row < kTM && m0 + row < a.M; row += 8) {
-    float v = ((part[0][row][c] + part[1][row][c]) + (part[2][row][c] + part[3][row][c])) + bias;
+    float v = ((part[0][row][c] + part[1][row][c]) + (part[2][row][c] + part[3][row][c])) * (1.0f / kWScale) + bias;
     if (a.relu) v = fmaxf(v, 0.0f);
     float* yp = Y + (long)(m0 + row) * a.ldy;
     *yp = a.accumulate ? *yp + v : v;

@@ -1,7 +1,8 @@
 """Batched AED beam search (csrc/decoder_batch.hip, eec_decoder_batch_*; BeamInference.beam_search_batch / decode_batch) against
 the per-utterance path it replaces (decoder_session_group / beam_search_exits / decode_all_exits).  The batched linears run on
-bf16x3 MFMA operands and the per-utterance decoder in plain fp32, so log-probs agree to the bound the repository applies to bf16x3
-decoder GEMMs, 2e-5 * max(10, max |logp|), and searches agree up to near-ties."""
+f16x3 MFMA operands (fp16 hi + lo, three products, fp32 accumulation) and the per-utterance decoder in plain fp32; log-probs are
+held to the bound the repository applies to its bf16x3 decoder GEMMs, 2e-5 * max(10, max |logp|), and searches agree up to
+near-ties.  Both decoders against an fp64 oracle: tests/test_gpu_aed_step.py."""
 import os
 import sys
 
