@@ -1,6 +1,7 @@
 """Augmentation on the device: SpecAugment between the mel front end and the encoder (include/eec.h, "SpecAugment";
-csrc/specaug.hip) and speed perturbation / resampling in front of the mel front end (include/eec.h, "Resampling / speed perturbation";
-csrc/resample.hip).
+csrc/specaug.hip), speed perturbation / resampling in front of the mel front end (include/eec.h, "Resampling / speed perturbation";
+csrc/resample.hip) and, between the two, reverberation, additive noise and volume perturbation of the waveform (include/eec.h,
+"Waveform augmentation: reverberation, noise, volume"; csrc/waveaug.hip).
 
 * ``spec_augment``   time warp, frequency masks and time masks of a mel batch ``[B, n_mels, T]``: one launch that draws a row of
   integer parameters per utterance from ``(seed, utt_offset + b)`` (the dropout generator, counter-based) and one that applies them
@@ -11,11 +12,17 @@ csrc/resample.hip).
   torchaudio's ``functional.resample``, every utterance as if resampled alone and padded afterwards.
 * ``speed_perturb``  the same kernel with one ratio per utterance, drawn from ``(seed, utt_offset + b)`` among ``factors`` or
   prescribed: torchaudio's ``transforms.Speed``.  ``SpeedPerturb`` is its module form, built like ``SpecAugment``.
+* ``wave_augment``   Kaldi's ``wav-reverberate`` order on a waveform batch: convolution with a room impulse response of a ``RirBank``
+  (the direct path stays in place, the length does not change), a tiled noise row of a ``NoiseBank`` added at a signal-to-noise ratio
+  drawn among ``snrs``, a volume gain; every stage switched per utterance by a row drawn from ``(seed, utt_offset + b)`` or
+  prescribed.  ``reverberate`` and ``add_noise`` are the prescribed single stages, ``WaveAugment`` the module form.
+
+The chain of a training step: ``wave, n = speed(wave, n); wave = waveaug(wave, n); mel = frontend(wave, n); mel = specaug(mel, frames)``.
 
 The warp is ``F.interpolate(align_corners=False)`` of the frames left and right of a drawn centre, separately (ESPnet's and lhotse's
 ``time_warp``), bicubic or linear; frames at or past an utterance's length are copied through and never read.  Out of scope:
-mean-value fill, ``sinc_interp_kaiser``, tempo change without pitch change, volume and noise perturbation, a backward (the input is
-data)."""
+mean-value fill, ``sinc_interp_kaiser``, tempo change without pitch change, reverberated point-source noises, babble, codec and
+clipping effects, FFT convolution, a backward (the input is data)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -470,3 +477,385 @@ class SpeedPerturb(nn.Module):
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={v!r}" for k, v in self.kwargs.items())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# waveform augmentation: reverberation, noise, volume
+# ---------------------------------------------------------------------------------------------------------------------------
+WAVEAUG_SITE = 0x57415547                                                     # EEC_WAVEAUG_SITE
+WAVEAUG_PARAMS, WAVEAUG_TILE, WAVEAUG_MAX_BANK, WAVEAUG_MAX_SNRS = 5, 1024, 4096, 64  # EEC_WAVEAUG_PARAMS, _TILE, _MAX_BANK, _MAX_SNRS
+REVERB_MAX_TAPS = 16384                                                       # EEC_REVERB_MAX_TAPS
+RIR_NORMS = {"none": 0, "l2": 1, "peak": 2}                                   # EEC_RIR_NORM_NONE, _L2, _PEAK
+RIR_MAGIC, NOISE_MAGIC = 0x52495242, 0x4E4F4953                               # EEC_RIR_MAGIC, EEC_NOISE_MAGIC
+_ONE_BITS = 0x3F800000                                                     # 1.0f
+
+
+def _rows_fp32(who: str, rows, most: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The 1-D arrays or tensors of ``rows`` as one fp32 array and their int32 counts; what the library would refuse, refused here."""
+    if isinstance(rows, (Tensor, np.ndarray)) or not hasattr(rows, "__len__"):
+        raise ValueError(f"{who}: a list of 1-D arrays or tensors is expected")
+    if not 1 <= len(rows) <= WAVEAUG_MAX_BANK:
+        raise ValueError(f"{who}: between 1 and {WAVEAUG_MAX_BANK} rows, got {len(rows)}")
+    flat = []
+    for r, row in enumerate(rows):
+        a = row.detach().cpu().numpy() if isinstance(row, Tensor) else np.asarray(row)
+        if a.ndim != 1 or a.dtype.kind not in "fiu":
+            raise ValueError(f"{who}: row {r} must be a 1-D array of numbers, got {a.dtype} {a.shape}")
+        if not 1 <= a.shape[0] <= most:
+            raise ValueError(f"{who}: row {r} must have between 1 and {most} values, got {a.shape[0]}")
+        a = a.astype(np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError(f"{who}: row {r} holds a value that is not finite")
+        flat.append(a)
+    return np.ascontiguousarray(np.concatenate(flat)), np.array([a.shape[0] for a in flat], dtype=np.int32)
+
+
+class _Bank:
+    """An image of int32 words on the host and its uploaded copies, made once per device."""
+
+    image: np.ndarray
+
+    def _build(self, who: str, size_of, build) -> None:
+        lib = capi.load()
+        nbytes = size_of(lib)
+        if nbytes == 0:
+            raise ValueError(lib.eec_last_error().decode(errors="replace"))
+        self.image = np.zeros(nbytes // 4, dtype=np.int32)
+        capi.check(build(lib, self.image.ctypes.data, nbytes), who)
+        self.count = int(self.image[1])
+        self._dev: Dict[torch.device, Tensor] = {}
+
+    def on(self, dev: torch.device) -> Tensor:
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = torch.from_numpy(self.image).to(dev)
+        return t
+
+    def __len__(self) -> int:
+        return self.count
+
+
+class RirBank(_Bank):
+    """The image ``eec_rir_bank`` builds of ``rirs``, a list of 1-D arrays or tensors of at most 16384 taps each (include/eec.h has
+    the layout).  ``normalize``: "l2" (unit energy), "peak" or "none", in fp64, each tap rounded once; zero heads and tails are
+    dropped.  ``shift`` True (Kaldi's ``--shift-output``): the peak of a RIR -- the first index of ``max |h|`` -- stays where the
+    sample was, so frame counts and CTC targets are untouched; False: the plain causal convolution cut to the input's length."""
+
+    def __init__(self, rirs, normalize: str = "l2", shift: bool = True):
+        if normalize not in RIR_NORMS:
+            raise ValueError(f"RirBank: normalize must be 'l2', 'peak' or 'none', got {normalize!r}")
+        taps, n = _rows_fp32("RirBank", rirs, REVERB_MAX_TAPS)
+        args = (len(n), taps.ctypes.data, n.ctypes.data, RIR_NORMS[normalize], int(bool(shift)))
+        self._build("eec_rir_bank", lambda lib: lib.eec_rir_bank_bytes(*args), lambda lib, image, nbytes: lib.eec_rir_bank(*args, image, nbytes))
+        self.normalize, self.shift = normalize, bool(shift)
+
+    def rir(self, r: int) -> Tuple[int, np.ndarray]:
+        """``(d, taps)`` of RIR ``r``: the shift and the stored fp32 taps."""
+        K, d, at, _ = (int(v) for v in self.image[4 + 4 * r:8 + 4 * r])
+        return d, self.image[at:at + K].view(np.float32)
+
+
+class NoiseBank(_Bank):
+    """The image ``eec_noise_bank`` builds of ``noises``, a list of 1-D arrays or tensors of 1 to 2^30 samples each."""
+
+    def __init__(self, noises):
+        samples, n = _rows_fp32("NoiseBank", noises, MAX_SAMPLES)
+        args = (len(n), samples.ctypes.data, n.ctypes.data)
+        self._build("eec_noise_bank", lambda lib: lib.eec_noise_bank_bytes(*args), lambda lib, image, nbytes: lib.eec_noise_bank(*args, image, nbytes))
+        self.lengths = self.image[4:4 + 2 * self.count:2].copy()
+
+    def noise(self, m: int) -> np.ndarray:
+        n, at = (int(v) for v in self.image[4 + 2 * m:6 + 2 * m])
+        return self.image[at:at + n].view(np.float32)
+
+
+def _host_waveaug_draw(B: int, seed: int, utt_offset: int, R: int, thr_reverb: int, noise_len: np.ndarray, thr_noise: int, n_snrs: int,
+                       volume: Optional[Tuple[float, float]]) -> np.ndarray:
+    key = _key(seed, WAVEAUG_SITE)
+    with np.errstate(over="ignore"):
+        at = (np.arange(B, dtype=np.uint64) + np.uint64(utt_offset & _M64)) * np.uint64(64)
+        u = [_words(key, at + np.uint64(slot)).astype(np.uint64) for slot in range(7)]
+    below = lambda w, m: ((w * np.asarray(m, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)  # noqa: E731
+    p = np.zeros((B, WAVEAUG_PARAMS), dtype=np.int64)
+    M = noise_len.shape[0]
+    p[:, 0] = np.where(u[0] < np.uint64(thr_reverb), below(u[1], R), -1) if R > 0 else -1
+    if M > 0 and n_snrs > 0:
+        on = u[2] < np.uint64(thr_noise)
+        m = below(u[3], M)
+        p[:, 1] = np.where(on, m, -1)
+        p[:, 2] = np.where(on, below(u[4], noise_len[m]), 0)
+        p[:, 3] = np.where(on, below(u[5], n_snrs), 0)
+    else:
+        p[:, 1] = -1
+    gain = np.ones(B, dtype=np.float32)
+    if volume is not None:
+        lo, hi = volume
+        gain = (lo + (hi - lo) * (u[6].astype(np.float64) * 2.0 ** -32)).astype(np.float32)
+    p[:, 4] = gain.view(np.int32)
+    return p.astype(np.int32)
+
+
+def _host_energy(v: np.ndarray) -> float:
+    """sum v^2 in fp64 in the stated order: groups of 8 in order, 64 groups by halving, two blocks, then the tiles in order."""
+    n = v.shape[0]
+    tiles = -(-n // WAVEAUG_TILE)
+    sq = np.zeros(tiles * WAVEAUG_TILE, dtype=np.float64)
+    sq[:n] = v.astype(np.float64) ** 2
+    a = sq.reshape(tiles, WAVEAUG_TILE // 8, 8)
+    e = np.zeros(a.shape[:2], dtype=np.float64)
+    for j in range(8):
+        e = e + a[:, :, j]
+    e = e.reshape(tiles, 2, 64)
+    for s in (32, 16, 8, 4, 2, 1):
+        e = e[:, :, :s] + e[:, :, s:2 * s]
+    total = 0.0
+    for part in e[:, 0, 0] + e[:, 1, 0]:
+        total = total + float(part)
+    return total
+
+
+def _host_reverb(x: np.ndarray, d: int, h: np.ndarray) -> np.ndarray:
+    """y[i] = sum_k h[k] x[i + d - k], the taps in order, one fp32 multiply and one fp32 add each."""
+    n, K = x.shape[0], h.shape[0]
+    pad = K + abs(d)
+    xp = np.zeros(n + 2 * pad, dtype=np.float32)
+    xp[pad:pad + n] = x
+    acc = np.zeros(n, dtype=np.float32)
+    for k in range(K):
+        acc = acc + h[k] * xp[pad + d - k:pad + d - k + n]
+    return acc
+
+
+def _host_waveaug(wave: np.ndarray, n_all: np.ndarray, params: np.ndarray, rirs: Optional[RirBank], noises: Optional[NoiseBank],
+                  snr_gain: Sequence[float], reverb: bool = True, mix: bool = True):
+    B = wave.shape[0]
+    out, applied = np.zeros_like(wave), np.zeros((B, 2), dtype=np.float32)
+    for b in range(B):
+        n = int(n_all[b])
+        r, m, start, snr_idx, bits = (int(v) for v in params[b])
+        y = wave[b, :n].copy()
+        if reverb and rirs is not None and 0 <= r < len(rirs) and n > 0:
+            y = _host_reverb(y, *rirs.rir(r))
+        gain = np.array([bits], dtype=np.int32).view(np.float32)[0]
+        scale = np.float32(0.0)
+        if mix:
+            if noises is not None and 0 <= m < len(noises) and 0 <= snr_idx < len(snr_gain) and n > 0:
+                row = noises.noise(m)
+                seg = row[(start % row.shape[0] + np.arange(n, dtype=np.int64)) % row.shape[0]]
+                es, en = _host_energy(y), _host_energy(seg)
+                if es > 0.0 and en > 0.0:
+                    scale = np.float32(np.sqrt(np.float64(es) / np.float64(en)) * np.float64(snr_gain[snr_idx]))
+                if scale != 0.0:
+                    y = y + scale * seg
+            y = y * gain
+            applied[b] = scale, gain
+        out[b, :n] = y
+    return out, applied
+
+
+def _waveaug_batch(who: str, wave: Tensor, lengths: Optional[Tensor]):
+    if not isinstance(wave, Tensor) or wave.dim() not in (1, 2) or wave.dtype != torch.float32:
+        raise ValueError(f"{who}: wave must be an fp32 tensor [B, L] or [L], got {getattr(wave, 'dtype', None)} {tuple(getattr(wave, 'shape', ()))}")
+    squeeze = wave.dim() == 1
+    if squeeze:
+        wave = wave.unsqueeze(0)
+    B, L = wave.shape
+    if L > MAX_SAMPLES:
+        raise ValueError(f"{who}: at most 2^30 samples per utterance, got {L}")
+    if lengths is not None:
+        if not isinstance(lengths, Tensor) or lengths.dtype not in (torch.int32, torch.int64) or lengths.numel() != B or lengths.dim() > 1:
+            raise ValueError(f"{who}: lengths must be an int32 or int64 tensor of {B} entries")
+    return wave.contiguous(), squeeze
+
+
+def _waveaug_bank(who: str, name: str, bank, cls):
+    if bank is not None and not isinstance(bank, cls):
+        raise ValueError(f"{who}: {name} must be a {cls.__name__} or None, got {type(bank).__name__}")
+    return bank
+
+
+def _coin(who: str, name: str, p) -> int:
+    if not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+        raise ValueError(f"{who}: {name} must lie in [0, 1], got {p!r}")
+    return int(math.floor(float(p) * 4294967296.0))
+
+
+def _snr_gains(who: str, snrs) -> list:
+    snrs = [snrs] if isinstance(snrs, (int, float)) else list(snrs)
+    if not 1 <= len(snrs) <= WAVEAUG_MAX_SNRS:
+        raise ValueError(f"{who}: between 1 and {WAVEAUG_MAX_SNRS} SNRs, got {len(snrs)}")
+    if not all(isinstance(s, (int, float)) and math.isfinite(s) and abs(s) <= 2000 for s in snrs):
+        raise ValueError(f"{who}: an SNR must be a finite number of dB, got {snrs!r}")
+    return [10.0 ** (-float(s) / 20.0) for s in snrs]
+
+
+def _volume(who: str, volume) -> Optional[Tuple[float, float]]:
+    if volume is None:
+        return None
+    if not hasattr(volume, "__len__") or len(volume) != 2 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in volume):
+        raise ValueError(f"{who}: volume must be None or a finite pair (lo, hi), got {volume!r}")
+    return float(volume[0]), float(volume[1])
+
+
+def _waveaug_run(who: str, wave: Tensor, lengths: Optional[Tensor], params: Optional[Tensor], draw, rirs: Optional[RirBank],
+                 noises: Optional[NoiseBank], gains: Sequence[float], reverb: bool = True, mix: bool = True):
+    """The host path or the launches for a checked batch.  ``params`` None: drawn with ``draw`` = (seed, utt_offset, thr_reverb,
+    thr_noise, volume).  ``reverb`` / ``mix`` False: that launch is left out (the prescribed single-stage forms)."""
+    B, L = wave.shape
+    dev = wave.device
+    if lengths is not None:
+        lengths = capi.to_device(lengths.reshape(B), dev, torch.int64).clamp(0, L).contiguous()
+    if params is not None:
+        if not isinstance(params, Tensor) or params.shape != (B, WAVEAUG_PARAMS) or params.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{who}: params must be an int32 or int64 tensor [{B}, {WAVEAUG_PARAMS}]")
+        lim = (1 << 31) - 1
+        params = params.to(dev).clamp(-lim - 1, lim).to(torch.int32).contiguous()
+
+    if not wave.is_cuda:
+        n = np.full(B, L, dtype=np.int64) if lengths is None else lengths.numpy()
+        if params is None:
+            seed, utt_offset, thr_r, thr_n, volume = draw
+            params = torch.from_numpy(_host_waveaug_draw(B, seed, utt_offset, 0 if rirs is None else len(rirs), thr_r,
+                                                         np.zeros(0, dtype=np.int32) if noises is None else noises.lengths, thr_n, len(gains),
+                                                         volume))
+        out, applied = _host_waveaug(wave.numpy(), n, params.numpy(), rirs, noises, gains, reverb, mix)
+        return torch.from_numpy(out), params, torch.from_numpy(applied)
+
+    lib = capi.load()
+    rir_ptr = None if rirs is None else rirs.on(dev).data_ptr()
+    noise_ptr = None if noises is None else noises.on(dev).data_ptr()
+    len_ptr = None if lengths is None or B == 0 else lengths.data_ptr()
+    out = torch.empty_like(wave)
+    applied = torch.zeros((B, 2), dtype=torch.float32, device=dev) if not mix else torch.empty((B, 2), dtype=torch.float32, device=dev)
+    table = (C.c_double * max(len(gains), 1))(*gains)
+    with torch.cuda.device(dev):
+        stream = capi.stream_ptr(dev)
+        if params is None:
+            seed, utt_offset, thr_r, thr_n, volume = draw
+            lo, hi = volume if volume is not None else (1.0, 1.0)
+            params = torch.empty((B, WAVEAUG_PARAMS), dtype=torch.int32, device=dev)
+            capi.check(lib.eec_waveaug_draw(B, seed, utt_offset, rir_ptr, thr_r, noise_ptr, thr_n, len(gains), int(volume is not None), lo, hi,
+                                            params.data_ptr(), stream), "eec_waveaug_draw")
+        partials = None
+        if mix and noises is not None:
+            partials = torch.empty(max(lib.eec_waveaug_partials_bytes(B, L) // 8, 1), dtype=torch.float64, device=dev)
+        part_ptr = None if partials is None else partials.data_ptr()
+        if reverb:
+            capi.check(lib.eec_reverb(wave.data_ptr(), len_ptr, params.data_ptr(), B, L, rir_ptr, out.data_ptr(), part_ptr, stream), "eec_reverb")
+        if mix:
+            if partials is not None:
+                capi.check(lib.eec_noise_energy(None if reverb else wave.data_ptr(), len_ptr, params.data_ptr(), B, L, noise_ptr, part_ptr, stream),
+                           "eec_noise_energy")
+            capi.check(lib.eec_noise_mix(out.data_ptr() if reverb else wave.data_ptr(), len_ptr, params.data_ptr(), B, L, noise_ptr, table, len(gains),
+                                         part_ptr, out.data_ptr(), applied.data_ptr(), stream), "eec_noise_mix")
+    return out, params, applied
+
+
+def wave_augment(wave: Tensor, lengths: Optional[Tensor] = None, *, seed: int, utt_offset: int = 0, rirs: Optional[RirBank] = None,
+                 noises: Optional[NoiseBank] = None, p_reverb: float = 1.0, p_noise: float = 1.0, snrs: Sequence[float] = (20, 15, 10, 5, 0),
+                 volume: Optional[Tuple[float, float]] = None, params: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(out, params, applied)``: ``wave`` [B, L] or [L] (fp32) reverberated, with noise added and its volume changed, in Kaldi's
+    ``wav-reverberate`` order; the int32 rows ``rir, noise, start, snr_idx, gain_bits`` it was made with; and the fp32 ``[B, 2]``
+    noise scale (0.0: none added) and gain applied.  ``lengths`` [B]: valid samples, clamped to [0, L]; None: L.  Samples at or past
+    a length are never read, outputs there are 0.0, the lengths do not change, and every utterance comes out as if processed alone.
+
+    ``params`` None: drawn from ``(seed, utt_offset + b)`` -- with probability ``p_reverb`` a RIR of ``rirs``, with probability
+    ``p_noise`` a row of ``noises``, a start inside it and one of ``snrs`` (dB; the noise is scaled so that the utterance's energy over
+    the noise segment's is that SNR), a gain uniform in ``volume`` = (lo, hi) (None: 1) -- so a call on a slice of the batch with
+    ``utt_offset`` advanced returns the rows of the whole call.  Given: applied as they are; an index outside its bank (-1) switches
+    the stage off, a start is reduced mod the row's length.  No host synchronisation; a CPU tensor takes the NumPy host path,
+    bit-identical for finite input.  The banks are uploaded at the first call on a device."""
+    who = "wave_augment"
+    wave, squeeze = _waveaug_batch(who, wave, lengths)
+    rirs, noises = _waveaug_bank(who, "rirs", rirs, RirBank), _waveaug_bank(who, "noises", noises, NoiseBank)
+    draw = (int(seed) & _M64, int(utt_offset) & _M64, _coin(who, "p_reverb", p_reverb), _coin(who, "p_noise", p_noise), _volume(who, volume))
+    out, params, applied = _waveaug_run(who, wave, lengths, params, draw, rirs, noises, _snr_gains(who, snrs))
+    return (out[0], params[0], applied[0]) if squeeze else (out, params, applied)
+
+
+def _rows_of(who: str, name: str, value, B: int, dev) -> Tensor:
+    if isinstance(value, int) and not isinstance(value, bool):
+        return torch.full((B,), value, dtype=torch.int64, device=dev).clamp(-(1 << 31), (1 << 31) - 1)
+    if not isinstance(value, Tensor) or value.dtype not in (torch.int32, torch.int64) or value.numel() != B or value.dim() > 1:
+        raise ValueError(f"{who}: {name} must be an integer or an int32 or int64 tensor of {B} entries")
+    return value.reshape(B).to(dev).to(torch.int64).clamp(-(1 << 31), (1 << 31) - 1)
+
+
+def reverberate(wave: Tensor, lengths: Optional[Tensor], rirs: RirBank, index) -> Tensor:
+    """``wave`` [B, L] or [L] convolved with the RIRs ``index`` (an integer or [B]) of ``rirs``; -1 or an index outside the bank copies
+    the utterance.  The rest as ``wave_augment``."""
+    who = "reverberate"
+    wave, squeeze = _waveaug_batch(who, wave, lengths)
+    if not isinstance(rirs, RirBank):
+        raise ValueError(f"{who}: rirs must be a RirBank, got {type(rirs).__name__}")
+    B, dev = wave.shape[0], wave.device
+    params = torch.zeros((B, WAVEAUG_PARAMS), dtype=torch.int64, device=dev)
+    params[:, 0], params[:, 1], params[:, 4] = _rows_of(who, "index", index, B, dev), -1, _ONE_BITS
+    out, _, _ = _waveaug_run(who, wave, lengths, params, None, rirs, None, [], mix=False)
+    return out[0] if squeeze else out
+
+
+def add_noise(wave: Tensor, lengths: Optional[Tensor], noises: NoiseBank, index, start, snr) -> Tensor:
+    """``wave`` [B, L] or [L] plus the noise rows ``index`` of ``noises`` read from ``start`` on (integers or [B]; tiled), scaled so that
+    the utterance's energy over the noise segment's is ``snr`` dB -- a number or B numbers on the host, at most 64 distinct --:
+    torchaudio's ``functional.add_noise`` up to rounding.  The rest as ``wave_augment``."""
+    who = "add_noise"
+    wave, squeeze = _waveaug_batch(who, wave, lengths)
+    if not isinstance(noises, NoiseBank):
+        raise ValueError(f"{who}: noises must be a NoiseBank, got {type(noises).__name__}")
+    B, dev = wave.shape[0], wave.device
+    snr = [snr] * B if isinstance(snr, (int, float)) else (snr.tolist() if isinstance(snr, (Tensor, np.ndarray)) else list(snr))
+    if len(snr) != B:
+        raise ValueError(f"{who}: snr must be a number or {B} numbers, got {len(snr)}")
+    levels = sorted(set(snr)) if B else [0.0]
+    gains = _snr_gains(who, levels)
+    params = torch.zeros((B, WAVEAUG_PARAMS), dtype=torch.int64, device=dev)
+    params[:, 1], params[:, 2] = _rows_of(who, "index", index, B, dev), _rows_of(who, "start", start, B, dev)
+    params[:, 3], params[:, 4] = torch.tensor([levels.index(s) for s in snr], dtype=torch.int64, device=dev), _ONE_BITS
+    out, _, _ = _waveaug_run(who, wave, lengths, params, None, None, noises, gains, reverb=False)
+    return out[0] if squeeze else out
+
+
+class WaveAugment(nn.Module):
+    """``wave = waveaug(wave, n)`` between ``SpeedPerturb`` and the mel front end: ``wave_augment`` with the arguments given here in
+    train mode, the input itself in eval mode; the lengths do not change.  ``rirs`` / ``noises``: a bank, or a list of 1-D arrays to
+    build one from.  The call counter, the seed rule (call k draws from ``seed + k * 0x9E3779B97F4A7C15``) and ``get_state`` /
+    ``set_state`` are ``SpecAugment``'s; ``last_params`` and ``last_applied`` hold the rows and the scale and gain of the last
+    train-mode call.  No parameters, no buffers.  The banks are uploaded at the first call on a device: make that call before
+    capturing a graph."""
+
+    def __init__(self, seed: Optional[int] = None, rirs=None, noises=None, p_reverb: float = 1.0, p_noise: float = 1.0,
+                 snrs: Sequence[float] = (20, 15, 10, 5, 0), volume: Optional[Tuple[float, float]] = None, normalize: str = "l2",
+                 shift: bool = True):
+        super().__init__()
+        who = "WaveAugment"
+        if rirs is not None and not isinstance(rirs, RirBank):
+            rirs = RirBank(rirs, normalize=normalize, shift=shift)
+        if noises is not None and not isinstance(noises, NoiseBank):
+            noises = NoiseBank(noises)
+        _coin(who, "p_reverb", p_reverb), _coin(who, "p_noise", p_noise), _snr_gains(who, snrs), _volume(who, volume)  # refused here
+        self.seed = capi.new_seed() if seed is None else int(seed)
+        self.rirs, self.noises = rirs, noises
+        self.kwargs = dict(p_reverb=p_reverb, p_noise=p_noise, snrs=tuple(snrs), volume=None if volume is None else tuple(volume))
+        self.calls = 0
+        self.last_params: Optional[Tensor] = None
+        self.last_applied: Optional[Tensor] = None
+
+    def get_state(self) -> Dict[str, int]:
+        return {"seed": self.seed, "calls": self.calls}
+
+    def set_state(self, state: Dict[str, int]) -> None:
+        self.seed, self.calls = int(state["seed"]), int(state["calls"])
+
+    def forward(self, wave: Tensor, lengths: Optional[Tensor] = None, utt_offset: int = 0) -> Tensor:
+        if not self.training:
+            return wave
+        seed = (self.seed + self.calls * 0x9E3779B97F4A7C15) & _M64
+        self.calls += 1
+        out, self.last_params, self.last_applied = wave_augment(wave, lengths, seed=seed, utt_offset=utt_offset, rirs=self.rirs,
+                                                                noises=self.noises, **self.kwargs)
+        return out
+
+    def extra_repr(self) -> str:
+        banks = f"rirs={0 if self.rirs is None else len(self.rirs)}, noises={0 if self.noises is None else len(self.noises)}, "
+        return banks + ", ".join(f"{k}={v!r}" for k, v in self.kwargs.items())

@@ -104,6 +104,8 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_edit_distance_workspace_bytes", "eec_edit_distance",
            "eec_specaug_draw", "eec_specaug_apply",
            "eec_resample_plan_bytes", "eec_resample_plan", "eec_speed_draw", "eec_resample_lengths", "eec_resample",
+           "eec_rir_bank_bytes", "eec_rir_bank", "eec_noise_bank_bytes", "eec_noise_bank", "eec_waveaug_partials_bytes", "eec_waveaug_draw",
+           "eec_reverb", "eec_noise_energy", "eec_noise_mix",
            "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
            "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
            "eec_train_forward", "eec_train_backward", "eec_train_backward_ex", "eec_train_gemm",
@@ -251,6 +253,24 @@ def load() -> C.CDLL:
     lib.eec_resample_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     # wave, lengths, choice; B, L; plan, out; L_out; out_len, stream
     lib.eec_resample.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    # R, taps, n_taps, normalize, shift (; image, its bytes);  M, samples, n_samples (; image, its bytes)
+    lib.eec_rir_bank_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.eec_rir_bank_bytes.restype = C.c_size_t
+    lib.eec_rir_bank.argtypes = lib.eec_rir_bank_bytes.argtypes + [C.c_void_p, C.c_size_t]
+    lib.eec_noise_bank_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.eec_noise_bank_bytes.restype = C.c_size_t
+    lib.eec_noise_bank.argtypes = lib.eec_noise_bank_bytes.argtypes + [C.c_void_p, C.c_size_t]
+    lib.eec_waveaug_partials_bytes.argtypes = [C.c_int, C.c_int]
+    lib.eec_waveaug_partials_bytes.restype = C.c_size_t
+    # B; seed, utt_offset; rir_bank, thr_reverb; noise_bank, thr_noise; n_snrs, volume, lo, hi; params, stream
+    lib.eec_waveaug_draw.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_double,
+                                     C.c_double, C.c_void_p, C.c_void_p]
+    # wave, lengths, params; B, L; rir_bank, out, partials, stream
+    lib.eec_reverb.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4
+    # signal, lengths, params; B, L; noise_bank, partials, stream
+    lib.eec_noise_energy.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+    # y, lengths, params; B, L; noise_bank, snr_gain; n_snrs; partials, out, applied, stream
+    lib.eec_noise_mix.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     lib.eec_frontend_last_error.restype = C.c_char_p
     lib.eec_frontend_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.eec_frontend_destroy.argtypes = [C.c_void_p]

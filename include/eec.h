@@ -928,7 +928,7 @@ int eec_specaug_apply(const float* mel, const int32_t* frame_len, const int32_t*
  * max(o, n) > EEC_RESAMPLE_MAX_RATE after reduction, lpw outside [1, EEC_RESAMPLE_MAX_LPW], rolloff outside (0, 1], a null pointer,
  * (EEC_ERR_WORKSPACE) a short image; device entries -- B < 0, L outside [0, 2^30], L_out < 0, a null pointer where one is needed,
  * out == wave.  B == 0 is a successful no-op.  No allocation, no synchronisation, nothing read back; graph-capturable.
- * Not served: sinc_interp_kaiser, a backward (the input is data), tempo change without pitch change, volume or noise perturbation. */
+ * Not served: sinc_interp_kaiser, a backward (the input is data), tempo change without pitch change. */
 #define EEC_RESAMPLE_MAX_RATIOS 8
 #define EEC_RESAMPLE_MAX_RATE 640
 #define EEC_RESAMPLE_MAX_LPW 64
@@ -943,6 +943,103 @@ int eec_resample_lengths(const int64_t* lengths, const int32_t* choice, int B, i
                          void* stream);
 int eec_resample(const float* wave, const int64_t* lengths, const int32_t* choice, int B, int L, const void* plan, float* out,
                  int L_out, int64_t* out_len, void* stream);
+
+/* ---- Waveform augmentation: reverberation, noise, volume (csrc/waveaug.hip) --------------------------------------------------------
+ * The waveform-level stages between speed perturbation and the mel front end, in the order of Kaldi's wav-reverberate: convolution
+ * with a room impulse response (RIR), additive noise at a chosen signal-to-noise ratio, a volume gain.  The reference has none of
+ * them.  Each stage is switched per utterance by a row of parameters, drawn (eec_waveaug_draw) or prescribed by the caller.
+ *
+ *   wave, out [B][L] fp32, contiguous in time; lengths [B] int64 or NULL: valid samples per utterance, clamped to [0, L]; NULL: L.
+ *       len = the clamped length.  Samples at or past len are never read (a NaN there reaches nothing), outputs at or past len are
+ *       0.0, and every utterance comes out as if it had been processed alone.
+ *   params [B][EEC_WAVEAUG_PARAMS] int32:  rir, noise, start, snr_idx, gain_bits (the fp32 gain as its bits).
+ *
+ * 1. Reverberation.  RIR r of the bank has K stored taps h[0 .. K) and a shift d (below).  For 0 <= i < len
+ *         y[i] = sum_{k = 0 .. K - 1} h[k] * x[i + d - k]                  x outside [0, len) is 0
+ *    in fp32, the taps in the order k = 0, 1, ... from +0, each one rounded multiply and one rounded add (no fused multiply-add), as
+ *    eec_resample states its sum; products with a sample outside [0, len) may be skipped, which cannot change the bits for finite
+ *    input.  The output is as long as the input.  rir outside [0, R) (-1 by convention), or no bank: y = x bit for bit.
+ * 2. Noise.  Noise row m has len_m >= 1 samples; s = start reduced into [0, len_m) (the non-negative remainder);
+ *         n[i] = noise[m][(s + i) mod len_m]                               the row is tiled, as Kaldi repeats it
+ *         E_s = sum_{i < len} y[i]^2      E_n = sum_{i < len} n[i]^2       in fp64 (the square of an fp32 value is exact there)
+ *         scale = (float) (sqrt(E_s / E_n) * g[snr_idx])                   fp64, IEEE division and square root, rounded once
+ *         z[i] = y[i] + scale * n[i]                                       one rounded multiply, one rounded add
+ *    g is the caller's table of n_snrs <= EEC_WAVEAUG_MAX_SNRS fp64 factors, g = 10^(-snr / 20) for an SNR in dB, evaluated on the host
+ *    (it travels in the launch's argument block; no transcendental is evaluated on the device).  noise outside [0, M), snr_idx
+ *    outside [0, n_snrs), no bank, E_s == 0 or E_n == 0: z = y bit for bit.
+ *    The order of the two energy sums is fixed.  The samples are cut into tiles of EEC_WAVEAUG_TILE = 1024.  Inside a tile, group t
+ *    (t = 0 .. 127) adds the squares of its samples 8 t .. 8 t + 7 that lie below len, in that order, from 0.0; the 128 group sums are
+ *    combined as two blocks of 64, inside a block by v[t] += v[t + s] for t < s, s = 32, 16, 8, 4, 2, 1 in turn, and the tile's partial
+ *    is block 0 + block 1.  The partials of the tiles 0 .. ceil(len / 1024) - 1 are added in tile order from 0.0.  Nothing else of
+ *    the launch geometry enters, and no atomics are used.
+ * 3. Volume.  out[i] = z[i] * gain, gain = the float of gain_bits; 1.0f leaves z as it is.
+ *
+ * The banks (host only, no device call) follow eec_resample_plan: *_bytes returns the image's size (0 with a message when the
+ * arguments are refused), the builder writes one image of int32 words the caller uploads once per device.
+ *   eec_rir_bank: R <= EEC_WAVEAUG_MAX_BANK RIRs, `taps` their fp32 taps one RIR after the other, n_taps [R] in
+ *       [1, EEC_REVERB_MAX_TAPS].  The peak p is the first index of max |h| of the taps as given.  Normalisation in fp64, each tap
+ *       rounded once to fp32: EEC_RIR_NORM_L2 divides by sqrt(sum h^2) (unit energy), EEC_RIR_NORM_PEAK by |h[p]|, EEC_RIR_NORM_NONE
+ *       keeps the taps.  The lo leading and the trailing taps that are exactly zero afterwards are not stored.  shift != 0 (Kaldi's
+ *       --shift-output): d = p - lo, the direct path stays where it was, so frame counts and CTC targets are untouched; shift == 0:
+ *       d = -lo, the plain causal convolution cut to the input's length.
+ *           word 0 EEC_RIR_MAGIC, 1 R, 2 the image's size in words, 3 normalize | shift << 8
+ *           RIR r, words 4 + 4 r ..:  K, d, taps (word offset of the K fp32 taps), p - lo
+ *   eec_noise_bank: M <= EEC_WAVEAUG_MAX_BANK rows, `samples` one row after the other, n_samples [M] in [1, 2^30].
+ *           word 0 EEC_NOISE_MAGIC, 1 M, 2 the image's size in words, 3 0
+ *           row m, words 4 + 2 m ..:  len_m, samples (word offset of the len_m fp32 samples)
+ *   Refused (EEC_ERR_BAD_ARG): a count outside its range, a null pointer, an unknown normalize, a value that is not finite, a RIR
+ *   without a non-zero tap (also one whose taps all round to zero), an image of 2^31 words or more; (EEC_ERR_WORKSPACE) a short image.
+ *
+ * The draw, one work-item per utterance, from the dropout generator exactly as eec_specaug_draw and eec_speed_draw use it:
+ * u(slot) = word(key(seed, EEC_WAVEAUG_SITE), (utt_offset + b) * 64 + slot); a coin fires when u < thr, thr = floor(p * 2^32) computed
+ * by the caller (2^32 always fires, 0 never); a uniform integer in [0, m) is (uint64) u * m >> 32.
+ *     slot 0  reverb coin (thr_reverb)         slot 1  rir = [0, R)              no coin, or no bank: rir = -1
+ *     slot 2  noise coin (thr_noise)           slot 3  noise = [0, M)            slot 4  start = [0, len_noise)
+ *     slot 5  snr_idx = [0, n_snrs)            no coin, no bank or n_snrs == 0: noise = -1, start = snr_idx = 0
+ *     slot 6  gain = (float) (lo + (hi - lo) * (u * 2^-32)) in fp64, operation by operation;  volume == 0: gain = 1.0f
+ * utt_offset enters the index, so a call on a slice of the batch with utt_offset advanced returns the rows of the whole call.
+ *
+ * The launches take such rows and never trust them: an index outside a bank switches its stage off, a start is reduced mod len_m.
+ *   eec_reverb        one workgroup of 128 work-items per (tile of 1024 outputs, utterance); a work-item holds 8 consecutive outputs in
+ *       registers.  The taps stream through LDS in chunks of 512 together with the 1536 input samples they meet (zeros outside
+ *       [0, len)); chunks whose samples all lie outside the utterance are skipped.  The tile leaves through LDS, so a wave stores 256
+ *       consecutive bytes whatever the row's alignment.  Without a RIR the tile moves as 16-byte quads where both rows are 16-byte
+ *       aligned.  Workgroups past len only write zeros.  partials (may be NULL) receives the tile's partial E_s.
+ *   eec_noise_energy  the same geometry: the partial E_n of the tiled noise segment per tile, and, when `signal` is not NULL, the
+ *       partial E_s of that buffer (for a caller that did not run eec_reverb).
+ *   eec_noise_mix     one workgroup of 256 work-items per (2048 samples, utterance): adds the partials in the stated order, forms
+ *       scale, writes out (out == y is allowed: every element is read and written by one work-item) and, from the first workgroup
+ *       of an utterance, applied[b] = (scale, gain) when applied is not NULL; scale is written as 0.0 where no noise was added.
+ *   partials: double [B][ceil(max(L, 1) / 1024)][2] (E_s, E_n), eec_waveaug_partials_bytes(B, L) bytes, 8-byte aligned.
+ * No atomics, nothing read back, no allocation, no synchronisation; graph-capturable.  Two runs, a split batch with utt_offset
+ * advanced, lengths = NULL against lengths all L and a storage off a 16-byte boundary return the same bits.
+ * EEC_ERR_BAD_ARG, before any device work, through eec_last_error(): B < 0, L outside [0, 2^30], n_snrs outside [0, 64], a threshold
+ * above 2^32, lo or hi not finite, a null pointer where one is needed, out == wave in eec_reverb.  B == 0 is a successful no-op.
+ * Not served: FFT convolution, reverberated point-source noises, babble, codec and clipping effects, a backward (the input is data). */
+#define EEC_WAVEAUG_SITE 0x57415547u
+#define EEC_WAVEAUG_PARAMS 5
+#define EEC_WAVEAUG_TILE 1024
+#define EEC_WAVEAUG_MAX_BANK 4096
+#define EEC_WAVEAUG_MAX_SNRS 64
+#define EEC_REVERB_MAX_TAPS 16384
+#define EEC_RIR_MAGIC 0x52495242
+#define EEC_NOISE_MAGIC 0x4E4F4953
+#define EEC_RIR_NORM_NONE 0
+#define EEC_RIR_NORM_L2 1
+#define EEC_RIR_NORM_PEAK 2
+size_t eec_rir_bank_bytes(int R, const float* taps, const int32_t* n_taps, int normalize, int shift);
+int eec_rir_bank(int R, const float* taps, const int32_t* n_taps, int normalize, int shift, void* image, size_t image_bytes);
+size_t eec_noise_bank_bytes(int M, const float* samples, const int32_t* n_samples);
+int eec_noise_bank(int M, const float* samples, const int32_t* n_samples, void* image, size_t image_bytes);
+size_t eec_waveaug_partials_bytes(int B, int L);
+int eec_waveaug_draw(int B, uint64_t seed, uint64_t utt_offset, const void* rir_bank, uint64_t thr_reverb, const void* noise_bank,
+                     uint64_t thr_noise, int n_snrs, int volume, double lo, double hi, int32_t* params, void* stream);
+int eec_reverb(const float* wave, const int64_t* lengths, const int32_t* params, int B, int L, const void* rir_bank, float* out,
+               double* partials, void* stream);
+int eec_noise_energy(const float* signal, const int64_t* lengths, const int32_t* params, int B, int L, const void* noise_bank,
+                     double* partials, void* stream);
+int eec_noise_mix(const float* y, const int64_t* lengths, const int32_t* params, int B, int L, const void* noise_bank,
+                  const double* snr_gain, int n_snrs, const double* partials, float* out, float* applied, void* stream);
 
 /* Mel front end(SURVEY 8f row f3): replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,
