@@ -2,3 +2,12 @@
 ``models.model.early_exit.Early_conformer`` / ``full_conformer`` encoder path; ``model.Splitformer`` and
 ``model.Early_zipformer`` are composed from the same kernels)."""
 __version__ = "0.1.0"
+
+_CONTEXT = ("ContextGraph", "ContextBiasSession")  # contextual biasing (context.py), resolved at first use: importing the package stays light
+
+
+def __getattr__(name):
+    if name in _CONTEXT:
+        from . import context
+        return getattr(context, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -45,6 +45,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from .context import ContextBiasSession
 from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
 
@@ -76,8 +77,9 @@ def sequence_length_penalty(length: int, alpha: float = 0.6) -> float:
 
 class CTCHypothesis:
     """One CTC beam-search hypothesis, with the attribute names of torchaudio's ``CUCTCHypothesis`` (tokens: List[int] without
-    blanks / repeats, words: List[str] -- empty here, as for a lexicon-free decoder --, score: float)."""
-    __slots__ = ("tokens", "words", "score", "text")
+    blanks / repeats, words: List[str] -- empty here, as for a lexicon-free decoder --, score: float).  ``bias`` is set by a search
+    under a context graph only: the contextual bias the hypothesis was ranked with, beside its ``score``."""
+    __slots__ = ("tokens", "words", "score", "text", "bias")
 
     def __init__(self, tokens, words, score, text=None):
         self.tokens, self.words, self.score, self.text = tokens, words, score, text
@@ -148,31 +150,53 @@ def _ctc_pick(emission: Tensor, em_len: Optional[Tensor], weight_ctc: float, bla
     return pick
 
 
-def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None):
+def _bias_session(context, graph_of, E: int, B: int, beam: int, V: int):
+    """The ``ContextBiasSession`` of E * B lockstep searches (search e * B + b) under ``context``, or None without one: ``graph_of``
+    [B] is given per utterance and repeated over the exits."""
+    if context is None:
+        if graph_of is not None:
+            raise ValueError("graph_of chooses among the graphs of context=, which was not given")
+        return None
+    if context.vocab_size != V:
+        raise ValueError(f"the context graph is over {context.vocab_size} tokens, the decoder over {V}")
+    if graph_of is not None:
+        graph_of = torch.as_tensor(graph_of).reshape(B).repeat(E)
+    return ContextBiasSession(context, E * B, beam, graph_of)
+
+
+def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None, bias=None):
     """``max_length`` steps of n independent beam searches in lockstep, none of which finalises a beam on the way:
     ``step(last [n, R], parent [n, R] | None)`` returns the next token's log-probs [n, R, V] of every live beam.  The
     bookkeeping of a step is ``beam_select`` over two token buffers.  Returns ``(final_tokens, final_scores, best_tokens)``
-    per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s."""
+    per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s.
+    ``bias`` (a ``ContextBiasSession``, or None): its ``step`` adds the contextual bias to the step's log-probs before the selection,
+    and after the last step ``bias.final`` takes the bonus of a still open partial match back (at the last step's penalty), as an
+    EOS would have."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
     last = bufs[0][:, :1, 0].contiguous()
     parent: Optional[Tensor] = None
     for i in range(max_length):
-        scores, parent, last = beam_select(step(last, parent), scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1],
-                                           i + 1)
+        logp = step(last, parent)
+        if bias is not None:
+            logp = bias.step(logp, last, parent)
+        scores, parent, last = beam_select(logp, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
+    if bias is not None:  # every row is final as it stands: an open partial match gives its provisional bonus back
+        scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
     tokens = bufs[max_length & 1][:, :beam]
     best = (scores.argmax(dim=1) if pick is None else pick(tokens, scores)).tolist()
     tokens_h = tokens.cpu()
     return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
 
 
-def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float):
+def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float, bias=None):
     """``max_length`` steps of n one-pass joint CTC / attention beam searches in lockstep (include/eec.h, "CTC prefix scores"):
     ``step(last [n, R], parent [n, R] | None)`` returns the decoder's log-probs [n, R, V] of every beam, ``prefix.step`` mixes in
     the CTC prefix scores and closes the beams that took EOS, ``beam_select`` ranks the result as in ``_lockstep_search``.  After
     ``max_length`` steps every row is final as it stands; a row holds only PAD after its EOS; the best beam is the one with the
-    highest score, ties to the lower index.  Returns ``(final_tokens, final_scores, best_tokens)`` per search."""
+    highest score, ties to the lower index.  Returns ``(final_tokens, final_scores, best_tokens)`` per search.  ``bias``: as in
+    ``_lockstep_search``, applied after ``prefix.step``."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
@@ -180,7 +204,11 @@ def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int,
     parent: Optional[Tensor] = None
     for i in range(max_length):
         local = prefix.step(step(last, parent), last, parent)
+        if bias is not None:
+            local = bias.step(local, last, parent)
         scores, parent, last = beam_select(local, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
+    if bias is not None:  # rows that never took EOS give the provisional bonus of an open partial match back (0 for the others)
+        scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
     tokens = bufs[max_length & 1][:, :beam]
     ended = torch.cumsum((tokens == eos).to(torch.int32), dim=2) > 0
     tokens[:, :, 1:] = torch.where(ended[:, :, :-1], torch.full_like(tokens[:, :, 1:], pad), tokens[:, :, 1:])  # rows of score -inf too
@@ -306,7 +334,8 @@ class BeamInference:
         return [texts[0]], torch.softmax(scores[0, : n_hyp[0]].double(), dim=0)[0].float()
 
     def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
-                         detokenize=None, lengths: Optional[Tensor] = None, nbest: Optional[int] = None) -> List[List["CTCHypothesis"]]:
+                         detokenize=None, lengths: Optional[Tensor] = None, nbest: Optional[int] = None, context=None,
+                         graph_of=None) -> List[List["CTCHypothesis"]]:
         """util/beam_infer.py:102-112: the nbest (= 1) beam-search hypotheses of one exit's log-probs ``emission`` [B, T', V],
         input length T' for every utterance (``lengths`` [B] in encoder frames: the decoder's ``encoder_out_lens``), beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
         hypothesis objects with ``.tokens`` / ``.words`` / ``.score`` like torchaudio's, so the reference's call sites
@@ -316,17 +345,25 @@ class BeamInference:
         ``int_to_text``) every hypothesis also carries ``.text``, its ``apply_lex``-ed transcript (inference.py:70-71), and
         ``.words``, that text's words; with either None nothing changes.  ``nbest`` (None: as above, one hypothesis): up to that
         many hypotheses per utterance, best first, as torchaudio's ``nbest`` -- the beam the same search ends with
-        (``ctc_beam_decode(nbest=)``), so an utterance whose final beam is smaller returns fewer."""
+        (``ctc_beam_decode(nbest=)``), so an utterance whose final beam is smaller returns fewer.  ``context`` (a
+        ``context.ContextGraph``; None: unchanged) and ``graph_of`` [B]: the search is biased towards the graph's phrases
+        (``ctc_beam_decode(context=)``); ``.score`` stays the CTC log-probability and every hypothesis also carries ``.bias``."""
         beam = self._arg(beam_size, "beam_size")
+        ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
         if nbest is not None:
-            tok, cnt, score, n_hyp = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95,
-                                                                       em_len=lengths, nbest=nbest))
+            tok, cnt, score, n_hyp, *bias = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95,
+                                                                              em_len=lengths, nbest=nbest, **ctx))
             hyps = [[CTCHypothesis(tok[b, r, : int(cnt[b, r])].tolist(), [], float(score[b, r])) for r in range(int(n_hyp[b]))]
                     for b in range(tok.size(0))]
+            for b, row in enumerate(hyps if bias else []):
+                for r, h in enumerate(row):
+                    h.bias = float(bias[0][b, r])
         else:
-            tok, cnt, score = ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths)
-            tok, cnt, score = tok.cpu(), cnt.cpu(), score.cpu()
+            tok, cnt, score, *bias = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths,
+                                                                       **ctx))
             hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
+            for b, row in enumerate(hyps if bias else []):
+                row[0].bias = float(bias[0][b])
         if lexicon is not None and detokenize is not None:
             flat = [h for row in hyps for h in row]
             for h, text in zip(flat, _snapped_texts([h.tokens for h in flat], lexicon, detokenize)):
@@ -462,21 +499,24 @@ class BeamInference:
 
     @torch.no_grad()
     def decode_all_exits(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
-                         ctc_weight: Optional[float] = None, joint_ctc_weight: Optional[float] = None, **kw) -> List[List[int]]:
+                         ctc_weight: Optional[float] = None, joint_ctc_weight: Optional[float] = None, context=None, graph_of=None,
+                         **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
         ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits).  ``ctc_weight``: the best beam of every exit is
         chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass).
         ``joint_ctc_weight`` (None: unchanged): the search itself is the one-pass joint one (``joint_search_exits``; ``min_length=``
-        defaults to 0 there); not together with ``ctc_weight``."""
+        defaults to 0 there); not together with ``ctc_weight``.  ``context`` / ``graph_of`` [1]: contextual biasing of the lockstep
+        searches (``beam_search_batch``); ValueError where only the step-by-step ``beam_search`` could serve the call."""
         if max_length is None:
             max_length = default_max_length(spec.size(1))
+        ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
         if joint_ctc_weight is not None:
             _check_joint_weight(joint_ctc_weight, ctc_weight)
             logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=True, want_taps=True, n_groups=model._cfg.n_exits)[:2]
             exits = list(range(1, model._cfg.n_exits + 1))
             found = self.joint_search_exits(model, [taps[n - 1] for n in exits], exits, logp,
                                             encoder_lengths(valid_len.reshape(1).to(logp.device), logp.size(2)), joint_ctc_weight,
-                                            max_length, beam_size=beam_size, **(_lockstep_kw(kw) or {}))
+                                            max_length, beam_size=beam_size, **(_lockstep_kw(kw) or {}), **ctx)
             return [best for _, _, best in found]
         logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=ctc_weight is not None, want_taps=True,
                                         n_groups=model._cfg.n_exits)[:2]
@@ -487,9 +527,12 @@ class BeamInference:
         lockstep = _lockstep_kw(kw)
         if lockstep is not None:
             together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size,
-                                              **lockstep, **ctc)
+                                              **lockstep, **ctc, **ctx)
             if together is not None:
                 return [best for _, _, best in together]
+        if ctx:
+            raise ValueError("decode_all_exits: contextual biasing runs in the lockstep searches only, and none serves this call "
+                             "(kv_cache=False, max_length - 1 > min_length, or no session group for this model / geometry)")
         found = [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw) for n in exits]
         if ctc_weight is None:
             return [best for _, _, best in found]
@@ -500,14 +543,15 @@ class BeamInference:
     def beam_search_exits(self, model, encoder_outputs: Sequence[Tensor], layer_ns: Sequence[int], vocab_size: Optional[int] = None,
                           max_length: int = 500, min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
-                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None):
+                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
+                          context=None, graph_of=None):
         """``beam_search`` for several exits of one utterance in lockstep: the searches are independent, so every decoder
         launch and every bookkeeping op covers all of them (``model.decoder_session_group``).  Returns the list of
         ``(final_tokens, final_scores, best_tokens)`` per exit, the same values as ``beam_search`` exit by exit -- or None
         when the lockstep does not apply: no session group for this model / geometry, or EOS could finalise beams
         (``max_length - 1 > min_length``), which would let the exits' beam counts diverge.  ``ctc_weight`` with ``emission``
-        [len(layer_ns), 1, T', V] (and ``emission_len`` [1]): as in ``beam_search_batch``."""
-        _, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        [len(layer_ns), 1, T', V] (and ``emission_len`` [1]): as in ``beam_search_batch``; ``context`` / ``graph_of`` [1] too."""
+        V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_session_group"):
             return None
         if any(e.size(0) != 1 for e in encoder_outputs):
@@ -516,7 +560,8 @@ class BeamInference:
         if group is None or beam > group.max_beams:
             return None
         return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha,
-                                self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1))
+                                self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1),
+                                _bias_session(context, graph_of, len(layer_ns), 1, beam, V))
 
     @staticmethod
     def _pick(ctc_weight, emission, emission_len, E: int, B: int):
@@ -536,7 +581,8 @@ class BeamInference:
     def beam_search_batch(self, model, taps, layer_ns: Sequence[int], vocab_size: Optional[int] = None, max_length: int = 500,
                           min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
-                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None):
+                          ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
+                          context=None, graph_of=None):
         """``beam_search_exits`` for every utterance of a padded batch at once: ``taps`` [E, B, T', D] (or E tensors [B, T', D]),
         exit ``layer_ns[e]``'s encoder output of every utterance.  The E * B searches are independent and run in lockstep through
         one ``model.decoder_batch_session`` (every decoder launch covers all of them) and one ``eec_beam_select`` per step.
@@ -545,7 +591,10 @@ class BeamInference:
         min_length``), or no batch session for this model / geometry / device.  ``ctc_weight`` (None: the highest score, no
         extra launch): ``best_tokens`` is chosen by ``ctc_rescore``'s joint score instead -- the E * B * beam final beams are
         aligned in one ``ctc_align`` call against ``emission`` [E, B, T', V], the exits' CTC log-probs of the same encoder pass
-        (``emission_len`` [B]: their frames, None = T'); ``final_tokens`` / ``final_scores`` are untouched."""
+        (``emission_len`` [B]: their frames, None = T'); ``final_tokens`` / ``final_scores`` are untouched.  ``context`` (a
+        ``context.ContextGraph`` built with ``eos=`` / ``pad=``; None: unchanged, no new launch) and ``graph_of`` [B]: one
+        ``eec_context_bias_step`` per step adds the contextual bias to the step's log-probs before the selection, so it shares the
+        step's length penalty (include/eec.h, "Contextual biasing")."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
             return None
@@ -557,7 +606,8 @@ class BeamInference:
 
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
-        found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B))
+        found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B),
+                                 _bias_session(context, graph_of, E, B, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     def _joint_args(self, emission, emission_len, E: int, B: int, V: int, joint_ctc_weight, EOS_token, PAD_token, blank: int):
@@ -575,7 +625,7 @@ class BeamInference:
     def joint_search_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor],
                            joint_ctc_weight: float, max_length: int, min_length: int = 0, vocab_size: Optional[int] = None,
                            SOS_token: Optional[int] = None, EOS_token: Optional[int] = None, PAD_token: Optional[int] = None,
-                           beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0):
+                           beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0, context=None, graph_of=None):
         """One-pass joint CTC / attention decoding (Watanabe et al. 2017; include/eec.h states the semantics) of every exit and
         utterance of a padded batch in lockstep: ``taps`` as for ``beam_search_batch``, ``emission`` [E, B, T', V] the exits' CTC
         log-probs of the same encoder pass (``emission_len`` [B]: their frames, None = T').  At every step the local score of a
@@ -584,7 +634,8 @@ class BeamInference:
         PAD at no cost, and a candidate the CTC head gives probability zero is dropped.  One decoder step, one
         ``eec_ctc_prefix_step`` and one ``eec_beam_select`` per step.  Returns ``out[b][e] = (final_tokens, final_scores,
         best_tokens)``; rows are ``max_length + 1`` long, SOS first.  ValueError where no batch session exists for the model /
-        geometry / device: there is no reference search to fall back to."""
+        geometry / device: there is no reference search to fall back to.  ``context`` / ``graph_of`` [B]: as in ``beam_search_batch``,
+        applied after the CTC prefix scores."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         session = model.decoder_batch_session(taps, layer_ns, max_length) if max_length >= 1 and hasattr(model, "decoder_batch_session") else None
         if session is None or beam > session.max_beams:
@@ -596,14 +647,16 @@ class BeamInference:
 
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
-        found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha)
+        found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha,
+                                       _bias_session(context, graph_of, E, B, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @torch.no_grad()
     def joint_search_exits(self, model, encoder_outputs: Sequence[Tensor], layer_ns: Sequence[int], emission: Tensor,
                            emission_len: Optional[Tensor], joint_ctc_weight: float, max_length: int, min_length: int = 0,
                            vocab_size: Optional[int] = None, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
-                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0):
+                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0,
+                           context=None, graph_of=None):
         """``joint_search_batch`` for the exits of ONE utterance (``model.decoder_session_group``): ``encoder_outputs[i]`` [1, T', D]
         is exit ``layer_ns[i]``'s encoder output, ``emission`` [len(layer_ns), 1, T', V].  Returns the list of ``(final_tokens,
         final_scores, best_tokens)`` per exit; ValueError where no session group exists."""
@@ -616,12 +669,13 @@ class BeamInference:
         n = len(layer_ns)
         w, eos, pad, em, em_len, blank = self._joint_args(emission, emission_len, n, 1, V, joint_ctc_weight, EOS_token, PAD_token, blank)
         prefix = ctc_prefix_session(em, em_len, beam, w, eos, pad, blank=blank, min_length=min_length)
-        return _joint_lockstep_search(group.step, prefix, n, encoder_outputs[0].device, max_length, sos, eos, pad, beam, alpha)
+        return _joint_lockstep_search(group.step, prefix, n, encoder_outputs[0].device, max_length, sos, eos, pad, beam, alpha,
+                                      _bias_session(context, graph_of, n, 1, beam, V))
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
                      max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, lexicon=None, detokenize=None,
-                     joint_ctc_weight: Optional[float] = None, **kw) -> List[List[List[int]]]:
+                     joint_ctc_weight: Optional[float] = None, context=None, graph_of=None, **kw) -> List[List[List[int]]]:
         """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
         utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
@@ -634,9 +688,15 @@ class BeamInference:
         joint CTC / attention one (``joint_search_batch``: every candidate of every step is also scored by the CTC prefix
         probability, EOS ends a beam; ``min_length=`` defaults to 0 there).  Each ``out[b][e]`` is then the best row as it stands
         -- SOS, the tokens, EOS, PAD up to ``max_length + 1`` -- and the lexicon step sees the tokens before EOS.  Not together
-        with ``ctc_weight``; ValueError where no batch session serves the model (there is no reference search to fall back to)."""
+        with ``ctc_weight``; ValueError where no batch session serves the model (there is no reference search to fall back to).
+        ``context`` (a ``context.ContextGraph`` over the decoder's vocabulary, built with ``eos=`` / ``pad=``; None: unchanged) and
+        ``graph_of`` [B] (a graph of a bank per utterance, the same for all its exits): the searches are biased towards the graph's
+        phrases, plain and joint alike (``beam_search_batch``)."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
+        if context is None and graph_of is not None:
+            raise ValueError("decode_batch: graph_of chooses among the graphs of context=, which was not given")
+        rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(-1)
         E = model._cfg.n_exits
         exits = list(range(1, E + 1))
         valid_len = valid_len.reshape(-1)
@@ -647,20 +707,22 @@ class BeamInference:
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             together, lockstep = None, _lockstep_kw(kw)
+            ctx = {} if context is None else {"context": context, "graph_of": None if rows_of is None else rows_of[c0:c0 + step]}
             if joint_ctc_weight is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
                 together = self.joint_search_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), joint_ctc_weight,
-                                                   max_length, beam_size=beam_size, **(lockstep or {}))
+                                                   max_length, beam_size=beam_size, **(lockstep or {}), **ctx)
                 del taps, logp
             elif lockstep is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=ctc_weight is not None, want_taps=True, n_groups=E)[:2]
                 ctc = {}
                 if ctc_weight is not None:
                     ctc = dict(ctc_weight=ctc_weight, emission=logp, emission_len=encoder_lengths(vl.to(logp.device), logp.size(2)))
-                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc)
+                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc, **ctx)
                 del taps, logp, ctc
             if together is None:
-                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight, **kw)
+                one = lambda b: {} if not ctx else {"context": context, "graph_of": None if rows_of is None else rows_of[c0 + b: c0 + b + 1]}  # noqa: E731
+                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight, **one(b), **kw)
                         for b in range(sp.size(0))]
             else:
                 out += [[best for _, _, best in row] for row in together]
@@ -677,7 +739,7 @@ class BeamInference:
     @torch.no_grad()
     def rescore_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor], nbest: int,
                       rescoring_ctc_weight: float, beam_size: Optional[int] = None, SOS_token: Optional[int] = None,
-                      EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30):
+                      EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30, context=None, graph_of=None):
         """Two-pass decoding of exits ``layer_ns`` for every utterance of a padded batch: ``taps`` [E, B, T', D] (or E tensors
         [B, T', D]) and ``emission`` [E, B, T', V], the exits' encoder outputs and CTC log-probs of one encoder pass
         (``emission_len`` [B]: their frames, None = T').  First pass: the N-best lists of all E * B emissions in ONE prefix beam
@@ -687,7 +749,9 @@ class BeamInference:
         (the convention of the one-pass joint search; a score with weight 0 does not enter), in fp64, and the best hypothesis
         is the one with the highest joint score, ties to the lower rank; an absent hypothesis is never chosen.  No length
         normalisation.  Returns ``out[b][e] = (best_tokens, RescoredList)``: the chosen ids (no SOS / EOS), and ``tokens``,
-        ``ctc``, ``att``, ``joint`` of that search's whole list, best CTC score first."""
+        ``ctc``, ``att``, ``joint`` of that search's whole list, best CTC score first.  ``context`` (a ``context.ContextGraph`` over
+        the CTC vocabulary; None: unchanged) and ``graph_of`` [B]: the first pass is the biased search (``ctc_beam_decode(context=)``:
+        the list is ordered by CTC score + bias) and ``joint = (1 - w) * att + w * ctc + bias`` in fp64, ties to the lower rank."""
         w = float(rescoring_ctc_weight)
         if not 0.0 <= w <= 1.0:
             raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
@@ -702,19 +766,28 @@ class BeamInference:
         dev = emission.device
         em_len = None if emission_len is None else emission_len.to(dev, torch.int32).reshape(B).repeat(E)
         groups = [(layer_ns[e], taps[e], torch.arange(e * B, (e + 1) * B, device=dev)) for e in range(E)]
+        if context is None and graph_of is not None:
+            raise ValueError("rescore_batch: graph_of chooses among the graphs of context=, which was not given")
+        rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(B).repeat(E)
         found = self._rescore(model, emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, groups, nbest, w, beam, sos, eos, blank,
-                              max_workspace_bytes)
+                              max_workspace_bytes, context, rows_of)
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @staticmethod
     def _rescore(model, em: Tensor, em_len: Optional[Tensor], groups, nbest: int, w: float, beam: int, sos: int, eos: int, blank: int,
-                 max_workspace_bytes: int):
+                 max_workspace_bytes: int, context=None, graph_of=None):
         """The two passes over n searches (``em`` [n, T', V], ``em_len`` [n] or None): one N-best launch for all of them, then one
         ``score_hypotheses`` call per ``(layer_n, enc [m, T', D], rows int64 [m])`` of ``groups`` -- the searches ``rows`` belong to
         exit ``layer_n``, search ``rows[i]`` has the memory ``enc[i]``; every search is in exactly one group.  Returns the list
-        of ``(best_tokens, RescoredList)`` per search."""
+        of ``(best_tokens, RescoredList)`` per search.  ``context`` / ``graph_of`` [n]: the first pass is biased and its bias enters
+        ``joint``."""
         dev = em.device
-        tokens, counts, ctc, n_hyp = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest)
+        bias = None
+        if context is None:
+            tokens, counts, ctc, n_hyp = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest)
+        else:
+            tokens, counts, ctc, n_hyp, bias = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
+                                                               context=context, graph_of=graph_of)
         present = torch.arange(nbest, device=dev).view(1, -1) < n_hyp.view(-1, 1)
         lengths = torch.where(present, counts, torch.full_like(counts, -1))
         L = max(int(counts.max()), 1)  # the one host read in front of the second pass: the decoder rows are L + 1 long
@@ -727,6 +800,8 @@ class BeamInference:
             joint = joint + (1.0 - w) * att.double()
         if w > 0.0:
             joint = joint + w * ctc.double()
+        if bias is not None:
+            joint = joint + bias.double()
         joint = torch.where(present, joint, torch.full_like(joint, -float("inf")))
         best = _first_argmax(joint).cpu().tolist()
         tokens, counts, n_hyp, ctc, att, joint = (t.cpu().tolist() for t in (tokens, counts, n_hyp, ctc, att, joint))
@@ -740,7 +815,7 @@ class BeamInference:
     @torch.no_grad()
     def decode_batch_rescoring(self, model, spec: Tensor, valid_len: Tensor, nbest: int = 10, rescoring_ctc_weight: float = 0.5,
                                beam_size: Optional[int] = None, max_batch: Optional[int] = None, lexicon=None, detokenize=None,
-                               **kw) -> List[List[List[int]]]:
+                               context=None, graph_of=None, **kw) -> List[List[List[int]]]:
         """``decode_batch`` by two-pass decoding (``rescore_batch``): ``out[b][e]`` is the hypothesis of exit e's CTC N-best list
         (``nbest`` of a beam of ``beam_size``, default ``max(args.beam_size, nbest)``) that scores best under ``(1 - w) * attention +
         w * CTC``.  One encoder pass per chunk of at most ``max_batch`` utterances (taps and log-probs of all exits), one N-best
@@ -756,8 +831,10 @@ class BeamInference:
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
+            ctx = {} if context is None and graph_of is None else \
+                {"context": context, "graph_of": None if graph_of is None else torch.as_tensor(graph_of).reshape(-1)[c0:c0 + step]}
             found = self.rescore_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), nbest,
-                                       rescoring_ctc_weight, beam_size=beam_size, **kw)
+                                       rescoring_ctc_weight, beam_size=beam_size, **ctx, **kw)
             out += [[best for best, _ in row] for row in found]
             del taps, logp
         if lexicon is not None and detokenize is not None:
@@ -771,16 +848,18 @@ class BeamInference:
     # -- adaptive inference: every utterance decoded at the one exit it left the encoder at --------------------------------
     @torch.no_grad()
     def ctc_adaptive_predict(self, model, src: Tensor, lengths: Tensor, threshold=None, beam_size: Optional[int] = None, lexicon=None,
-                             detokenize=None, **adaptive) -> Tuple[List[List["CTCHypothesis"]], Tensor]:
+                             detokenize=None, context=None, graph_of=None, **adaptive) -> Tuple[List[List["CTCHypothesis"]], Tensor]:
         """``model.forward_adaptive(src, lengths, threshold, **adaptive)`` (``criterion=``, ``min_exit=``, ``max_exit=``, ``exit_of=``,
         ``compact=``) and then ONE ``ctc_cuda_predict`` over the B emissions of the chosen exits, over the encoder's own frame counts
         -- where decoding every exit of ``forward`` searches E * B sequences.  Returns ``(hypotheses, exit_of)``: per utterance the
-        list ``ctc_cuda_predict`` returns, and the 0-based exit int32 [B] it was decoded at."""
+        list ``ctc_cuda_predict`` returns, and the 0-based exit int32 [B] it was decoded at.  ``context`` / ``graph_of`` [B]: as in
+        ``ctc_cuda_predict``."""
         if adaptive.get("want_taps"):
             raise ValueError("ctc_adaptive_predict: the CTC search reads no taps")
         out = model.forward_adaptive(src, lengths, threshold, **adaptive)
         em_len = encoder_lengths(lengths.to(out.logp.device), out.logp.size(1))
-        return self.ctc_cuda_predict(out.logp, beam_size=beam_size, lexicon=lexicon, detokenize=detokenize, lengths=em_len), out.exit_of
+        return self.ctc_cuda_predict(out.logp, beam_size=beam_size, lexicon=lexicon, detokenize=detokenize, lengths=em_len, context=context,
+                                     graph_of=graph_of), out.exit_of
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

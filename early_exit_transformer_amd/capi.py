@@ -117,7 +117,9 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_decoder_train_last_error", "eec_decoder_train_workspace_bytes", "eec_decoder_train_forward", "eec_decoder_train_backward",
            "eec_decoder_step_last_error", "eec_decoder_step_max_beams", "eec_decoder_cache_bytes", "eec_decoder_begin", "eec_decoder_step", "eec_decoder_step_multi", "eec_upload_i64_max", "eec_upload_i64", "eec_beam_select",
            "eec_decoder_batch_cache_bytes", "eec_decoder_batch_begin", "eec_decoder_batch_step",
-           "eec_ctc_prefix_state_bytes", "eec_ctc_prefix_begin", "eec_ctc_prefix_step"]
+           "eec_ctc_prefix_state_bytes", "eec_ctc_prefix_begin", "eec_ctc_prefix_step",
+           "eec_context_graph_bytes", "eec_context_graph", "eec_ctc_beam_decode_ctx", "eec_ctc_beam_decode_nbest_ctx",
+           "eec_context_bias_state_bytes", "eec_context_bias_step"]
 KERNEL_CLASSES = ["stem", "ffn", "qkv", "attn", "proj_glu", "proj", "dw_pw2", "head", "chain"]
 
 _lib: Optional[C.CDLL] = None
@@ -354,6 +356,18 @@ def load() -> C.CDLL:
     lib.eec_ctc_prefix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]
+    # G, n_phrases, phrase_len, tokens, boost; V, blank, eos, pad (; image, its bytes)
+    lib.eec_context_graph_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4
+    lib.eec_context_graph_bytes.restype = C.c_size_t
+    lib.eec_context_graph.argtypes = lib.eec_context_graph_bytes.argtypes + [C.c_void_p, C.c_size_t]
+    # the _len / _nbest entries, then image, its bytes, graph_of, bias in front of the stream
+    ctx = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.eec_ctc_beam_decode_ctx.argtypes = lib.eec_ctc_beam_decode_len.argtypes[:-1] + ctx + [C.c_void_p]
+    lib.eec_ctc_beam_decode_nbest_ctx.argtypes = lib.eec_ctc_beam_decode_nbest.argtypes[:-1] + ctx + [C.c_void_p]
+    lib.eec_context_bias_state_bytes.argtypes = [C.c_int, C.c_int]
+    lib.eec_context_bias_state_bytes.restype = C.c_size_t
+    # image, its bytes, graph_of; n, R, R_prev, R_max, V, s; parent, last, local, out, state, its bytes, stream
+    lib.eec_context_bias_step.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
     lib.eec_encoder_set_profiling.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.eec_encoder_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
     _lib = lib

@@ -21,11 +21,27 @@
 // work-item per hypothesis, into tokens [n_seq][nbest][T'], counts / scores [n_seq][nbest] and n_hyp [n_seq].  The first end is
 // NOT the second with nbest = 1: when no prefix is live (nb_s == 0: every candidate of a frame was -inf) the N-best end reports
 // count 0 and n_hyp = 0, the best-prefix end the length of slot 0 and score -inf.
+// Contextual biasing: EEC_CTC_CTX compiles this file a second time (ctc_beam_ctx.hip) into ctc_beam_ctx_kernel and the _ctx entries,
+// the same search ranked by key = fl(total + bias) (include/eec.h, "Contextual biasing").  A beam grows by `int state; float bias`;
+// work-item c reads delta[state_i][c] of every live beam i (one coalesced row per beam), the owner of a chosen extension reads its one
+// `next` entry and recomputes the extension's CTC mass from lpc, since the number that was ranked is the key.  Without the switch
+// every line of it is compiled out: the object of this file is the one it was.
 #include <limits.h>
 
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
+#ifdef EEC_CTC_CTX
+#include "eec_ctx.h"
+#define CbBeam CbBeamCtx
+#define ctc_beam_kernel ctc_beam_ctx_kernel
+#define launch_ctc_beam launch_ctc_beam_ctx
+#define CB_CTX(...) , __VA_ARGS__  // the two fields a beam grows by, at the end of its initialiser
+#define CB_CTX_ARGS(...) , __VA_ARGS__
+#else
+#define CB_CTX(...)
+#define CB_CTX_ARGS(...)
+#endif
 
 namespace eec {
 
@@ -36,6 +52,10 @@ struct CbBeam {
   float pb, pnb;
   int last, len;
   unsigned long long hash;
+#ifdef EEC_CTC_CTX
+  int state;
+  float bias;
+#endif
 };
 
 __device__ __forceinline__ float cb_lae(float a, float b) {  // log(exp a + exp b), -inf safe
@@ -54,7 +74,9 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
                                                               int Tq, int V, int blank, int beam,
                                                               float log_thr, int skip_drops, int* __restrict__ backptr, int* __restrict__ tokens,
                                                               int* __restrict__ counts, float* __restrict__ scores,
-                                                              int nbest, int* __restrict__ n_hyp) {
+                                                              int nbest, int* __restrict__ n_hyp
+                                                              CB_CTX_ARGS(const int* __restrict__ image, long long image_words,
+                                                                          const int* __restrict__ graph_of, float* __restrict__ bias_out)) {
   __shared__ CbBeam bufs[2][kCbMaxBeam];
   __shared__ float tot[kCbMaxBeam], stay_pb[kCbMaxBeam], stay_pnb[kCbMaxBeam], row[256];
   __shared__ unsigned merge_mask[kCbMaxBeam];  // bit i of word j: extension of beam i by last[j] spells beam j
@@ -65,9 +87,13 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
   const float* lp_seq = logp + (size_t)seq * Tq * V;
   int* bp = backptr + (size_t)seq * Tq * kCbMaxBeam;
   const int Ts = ctc_frames(em_len, seq, Tq);
+#ifdef EEC_CTC_CTX
+  __shared__ float fin_key[kCbMaxBeam], fin_bias[kCbMaxBeam];
+  const CtxTables G = ctx_tables(image, image_words, graph_of, seq, V);  // all-null: biasing is off for this sequence
+#endif
   int cur = 0;
   if (c == 0) {
-    bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull};
+    bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull CB_CTX(0, 0.f)};
     nb_s = 1;
   }
   __syncthreads();
@@ -83,7 +109,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
       if (c < nb) {
         // skip_drops == 0: the frame counts as a blank frame (all mass ends in blank: a label repeated across it stays a repeat)
         // skip_drops != 0: the frame is DROPPED, as if the sequence were one frame shorter (the repeat collapses)
-        N[c] = skip_drops ? B[c] : CbBeam{cb_lae(B[c].pb, B[c].pnb) + lpb, -INFINITY, B[c].last, B[c].len, B[c].hash};
+        N[c] = skip_drops ? B[c] : CbBeam{cb_lae(B[c].pb, B[c].pnb) + lpb, -INFINITY, B[c].last, B[c].len, B[c].hash CB_CTX(B[c].state, B[c].bias)};
         bp[t * kCbMaxBeam + c] = c << 16;
       }
       __syncthreads();
@@ -119,10 +145,17 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
         v = (B[i].last == c ? B[i].pb : tot[i]) + lpc;
         for (int j = 0; j < nb; ++j)
           if (B[j].last == c && (merge_mask[j] >> i & 1)) v = -INFINITY;
+#ifdef EEC_CTC_CTX
+        v = v + (B[i].bias + (G.delta ? G.delta[(size_t)B[i].state * V + c] : 0.f));  // the key; -inf stays -inf
+#endif
       }
       ext[i] = v;
     }
+#ifdef EEC_CTC_CTX
+    float stay = c < nb ? cb_lae(stay_pb[c], stay_pnb[c]) + B[c].bias : -INFINITY;
+#else
     float stay = c < nb ? cb_lae(stay_pb[c], stay_pnb[c]) : -INFINITY;
+#endif
     // `beam` rounds of block-wide arg-max; candidate id: stays = beam index (0 .. 15), extensions = 16 + 16 c + i
     int n_new = 0;
     for (int r = 0; r < beam; ++r) {
@@ -159,14 +192,20 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
       }
       if (gid < 16) {  // a stay: its owner is thread gid
         if (c == gid) {
-          N[r] = CbBeam{stay_pb[c], stay_pnb[c], B[c].last, B[c].len, B[c].hash};
+          N[r] = CbBeam{stay_pb[c], stay_pnb[c], B[c].last, B[c].len, B[c].hash CB_CTX(B[c].state, B[c].bias)};
           bp[t * kCbMaxBeam + r] = c << 16;
           stay = -INFINITY;
         }
       } else {
         const int cc = (gid - 16) >> 4, ii = (gid - 16) & 15;
         if (c == cc) {
+#ifdef EEC_CTC_CTX
+          const size_t at = (size_t)B[ii].state * V + cc;
+          N[r] = CbBeam{-INFINITY, (B[ii].last == cc ? B[ii].pb : tot[ii]) + lpc, cc, B[ii].len + 1, cb_mix(B[ii].hash, cc),
+                        G.delta ? ctx_state(G.next[at], G.S) : 0, B[ii].bias + (G.delta ? G.delta[at] : 0.f)};
+#else
           N[r] = CbBeam{-INFINITY, gv, cc, B[ii].len + 1, cb_mix(B[ii].hash, cc)};
+#endif
           bp[t * kCbMaxBeam + r] = (ii << 16) | (cc + 1);
 #pragma unroll
           for (int i = 0; i < kCbMaxBeam; ++i)
@@ -184,18 +223,32 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     // N-best: thread i < live beams ranks prefix i (the number of prefixes ahead of it: a higher total, or the same total and a
     // lower index) and, if it is among the first nbest, reads its labels off the back-pointers into row `rank` of the sequence
     if (c < kCbMaxBeam) tot[c] = c < nb_s ? cb_lae(bufs[cur][c].pb, bufs[cur][c].pnb) : -INFINITY;
+#ifdef EEC_CTC_CTX
+    // the open bonus is taken back, and the ranking is by the key: total + that final bias
+    if (c < kCbMaxBeam) {
+      const float b = c < nb_s ? bufs[cur][c].bias + (G.delta ? G.fin[ctx_state(bufs[cur][c].state, G.S)] : 0.f) : 0.f;
+      fin_bias[c] = b;
+      fin_key[c] = tot[c] + b;
+    }
+    const float* rank_by = fin_key;
+#else
+    const float* rank_by = tot;
+#endif
     __syncthreads();
     const int live = nb_s, n_out = min(live, nbest);
     if (c < live) {
       const CbBeam* B = bufs[cur];
-      const float s = tot[c];
+      const float s = rank_by[c];
       int rank = 0;
-      for (int j = 0; j < live; ++j) rank += (tot[j] > s || (tot[j] == s && j < c)) ? 1 : 0;
+      for (int j = 0; j < live; ++j) rank += (rank_by[j] > s || (rank_by[j] == s && j < c)) ? 1 : 0;
       if (rank < nbest) {
         int n = B[c].len, k = c;
         int* out = tokens + ((size_t)seq * nbest + rank) * Tq;
         counts[(size_t)seq * nbest + rank] = n;
-        scores[(size_t)seq * nbest + rank] = s;
+        scores[(size_t)seq * nbest + rank] = tot[c];
+#ifdef EEC_CTC_CTX
+        bias_out[(size_t)seq * nbest + rank] = fin_bias[c];
+#endif
         for (int t = Ts - 1; t >= 0 && n > 0; --t) {
           const int e = bp[t * kCbMaxBeam + k];
           if (e & 0xffff) out[--n] = (e & 0xffff) - 1;
@@ -206,6 +259,9 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     if (c >= n_out && c < nbest) {  // absent hypotheses
       counts[(size_t)seq * nbest + c] = 0;
       scores[(size_t)seq * nbest + c] = -INFINITY;
+#ifdef EEC_CTC_CTX
+      bias_out[(size_t)seq * nbest + c] = 0.f;
+#endif
     }
     if (c == 0) n_hyp[seq] = n_out;
   } else if (c == 0) {
@@ -213,6 +269,20 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     const CbBeam* B = bufs[cur];
     int best = 0;
     float bs = -INFINITY;
+#ifdef EEC_CTC_CTX
+    float best_key = -INFINITY, best_bias = 0.f;
+    for (int i = 0; i < nb_s; ++i) {
+      const float s = cb_lae(B[i].pb, B[i].pnb);
+      const float b = B[i].bias + (G.delta ? G.fin[ctx_state(B[i].state, G.S)] : 0.f);
+      if (s + b > best_key) {
+        best_key = s + b;
+        bs = s;
+        best_bias = b;
+        best = i;
+      }
+    }
+    bias_out[seq] = best_bias;
+#else
     for (int i = 0; i < nb_s; ++i) {
       const float s = cb_lae(B[i].pb, B[i].pnb);
       if (s > bs) {
@@ -220,6 +290,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
         best = i;
       }
     }
+#endif
     int n = B[best].len, k = best;
     int* out = tokens + (size_t)seq * Tq;
     counts[seq] = n;
@@ -234,12 +305,13 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
 
 // n_hyp != nullptr: the N-best end, into `nbest` rows per sequence; nullptr: the best prefix (nbest is not read)
 hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam, float blank_skip_threshold,
-                           int skip_drops, int* backptr, int* tokens, int* counts, float* scores, int nbest, int* n_hyp, hipStream_t st) {
+                           int skip_drops, int* backptr, int* tokens, int* counts, float* scores, int nbest, int* n_hyp, hipStream_t st
+                           CB_CTX_ARGS(const int* image, long long image_words, const int* graph_of, float* bias)) {
   if (V < 1 || V > 256 || beam < 1 || beam > kCbMaxBeam || blank < 0 || blank >= V) return hipErrorInvalidValue;
   if (n_hyp && (nbest < 1 || nbest > beam)) return hipErrorInvalidValue;
   const float log_thr = (blank_skip_threshold > 0.f && blank_skip_threshold < 1.f) ? logf(blank_skip_threshold) : INFINITY;
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, em_len, Tq, V, blank, beam, log_thr, skip_drops, backptr, tokens,
-                     counts, scores, nbest, n_hyp);
+                     counts, scores, nbest, n_hyp CB_CTX_ARGS(image, image_words, graph_of, bias));
   return hipGetLastError();
 }
 
@@ -247,9 +319,11 @@ hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int 
 
 extern "C" {
 
+#ifndef EEC_CTC_CTX
 size_t eec_ctc_beam_workspace_bytes(int n_seq, int Tq) {
   return n_seq > 0 && Tq > 0 ? (size_t)n_seq * Tq * eec::kCbMaxBeam * sizeof(int) : 0;
 }
+#endif
 
 // what the beam entries ask of their arguments; `entry` is the name their messages carry
 static int check_ctc_beam_args(const char* entry, bool have_pointers, int n_seq, int Tq, int V, int blank, int beam_size) {
@@ -262,6 +336,7 @@ static int check_ctc_beam_args(const char* entry, bool have_pointers, int n_seq,
   return 0;
 }
 
+#ifndef EEC_CTC_CTX
 int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                         void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream) {
   return eec_ctc_beam_decode_len(logp, NULL, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, 0, workspace, tokens, counts, scores, stream);
@@ -293,5 +368,37 @@ int eec_ctc_beam_decode_nbest(const float* logp, const int32_t* em_len, int n_se
                                counts, scores, nbest, n_hyp, (hipStream_t)stream));
   return 0;
 }
+#else
+// the _len / _nbest entries with a graph image (a device pointer, or NULL: no biasing), graph_of [n_seq] (NULL: graph 0) and `bias`
+static int check_ctx_image(const char* entry, const void* image, size_t image_bytes) {
+  if (image && (((uintptr_t)image & 3) != 0 || image_bytes < 16)) return eech::fail(EEC_ERR_BAD_ARG, std::string(entry) + ": image must be 4-byte aligned, image_bytes its size");
+  return 0;
+}
+
+int eec_ctc_beam_decode_ctx(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                            float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                            float* scores, const void* image, size_t image_bytes, const int32_t* graph_of, float* bias, void* stream) {
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode_ctx", logp && workspace && tokens && counts && scores && bias, n_seq, Tq, V, blank, beam_size))
+    return rc;
+  if (int rc = check_ctx_image("eec_ctc_beam_decode_ctx", image, image_bytes)) return rc;
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, 1, nullptr, (hipStream_t)stream, (const int*)image, (long long)(image_bytes / 4), graph_of, bias));
+  return 0;
+}
+
+int eec_ctc_beam_decode_nbest_ctx(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                                  float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens,
+                                  int32_t* counts, float* scores, int32_t* n_hyp, const void* image, size_t image_bytes,
+                                  const int32_t* graph_of, float* bias, void* stream) {
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode_nbest_ctx", logp && workspace && tokens && counts && scores && n_hyp && bias, n_seq, Tq, V,
+                                   blank, beam_size))
+    return rc;
+  if (nbest < 1 || nbest > beam_size) return eech::fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode_nbest_ctx: needs 1 <= nbest <= beam_size");
+  if (int rc = check_ctx_image("eec_ctc_beam_decode_nbest_ctx", image, image_bytes)) return rc;
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, nbest, n_hyp, (hipStream_t)stream, (const int*)image, (long long)(image_bytes / 4), graph_of, bias));
+  return 0;
+}
+#endif
 
 }  // extern "C"

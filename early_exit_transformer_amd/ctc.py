@@ -65,7 +65,8 @@ def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) ->
 
 
 def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
-                    skip_drops_frame: bool = False, em_len: Optional[Tensor] = None, nbest: Optional[int] = None):
+                    skip_drops_frame: bool = False, em_len: Optional[Tensor] = None, nbest: Optional[int] = None, context=None,
+                    graph_of=None):
     """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
     sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
     ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
@@ -75,7 +76,11 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
     ``nbest`` (None: the call and the three return values above, unchanged): an integer in [1, beam_size] returns the beam the
     same search ends with instead of its best prefix alone (eec_ctc_beam_decode_nbest) -- (tokens [N, nbest, T'] int32, counts
     [N, nbest] int32, scores [N, nbest] fp32, n_hyp [N] int32), best first, ties to the lower beam index; hypothesis 0 is the
-    hypothesis the call without ``nbest`` returns, an absent one (rank >= n_hyp) has count 0 and score -inf."""
+    hypothesis the call without ``nbest`` returns, an absent one (rank >= n_hyp) has count 0 and score -inf.
+    ``context`` (None: the call and its return values, unchanged): a ``context.ContextGraph`` -- the search ranks by total
+    log-probability + bias (eec_ctc_beam_decode_ctx / _nbest_ctx, include/eec.h "Contextual biasing") and ``bias`` ([N] or [N, nbest]
+    fp32, shaped like ``scores``) is appended to the tuple; ``scores`` stays the CTC log-probability alone.  ``graph_of`` [N] chooses a
+    graph of a bank per sequence (None: graph 0; an index outside the bank: no biasing for that sequence)."""
     if not logp.is_cuda:
         raise RuntimeError("ctc_beam_decode runs on a HIP device only")
     logp = logp.contiguous().float()
@@ -84,6 +89,30 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
     el = _frame_counts("ctc_beam_decode", "em_len", em_len, N, dev)
     lib = capi.load()
     ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
+    if context is None and graph_of is not None:
+        raise ValueError("ctc_beam_decode: graph_of chooses among the graphs of context=, which was not given")
+    if context is not None:
+        from .context import graph_rows
+        if context.vocab_size != V or context.blank != blank:
+            raise ValueError(f"ctc_beam_decode: the context graph is over {context.vocab_size} tokens with blank {context.blank}, "
+                             f"the emission over {V} with blank {blank}")
+        image, rows = context.to(dev), graph_rows("ctc_beam_decode", graph_of, N, dev)
+        tail = (image.data_ptr(), context.nbytes, _ptr(rows))
+        k = () if nbest is None else (int(nbest),)
+        tokens = torch.zeros((N, *k, Tq), dtype=torch.int32, device=dev)
+        counts = torch.empty((N, *k), dtype=torch.int32, device=dev)
+        scores = torch.empty((N, *k), dtype=torch.float32, device=dev)
+        bias = torch.empty((N, *k), dtype=torch.float32, device=dev)
+        head = (logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)))
+        with torch.cuda.device(dev):
+            if nbest is None:
+                capi.check(lib.eec_ctc_beam_decode_ctx(*head, ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), *tail,
+                                                       bias.data_ptr(), stream_ptr(dev)), "eec_ctc_beam_decode_ctx")
+                return tokens, counts, scores, bias
+            n_hyp = torch.empty((N,), dtype=torch.int32, device=dev)
+            capi.check(lib.eec_ctc_beam_decode_nbest_ctx(*head, k[0], ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(),
+                                                         n_hyp.data_ptr(), *tail, bias.data_ptr(), stream_ptr(dev)), "eec_ctc_beam_decode_nbest_ctx")
+        return tokens, counts, scores, n_hyp, bias
     if nbest is not None:
         nbest = int(nbest)
         tokens = torch.zeros((N, nbest, Tq), dtype=torch.int32, device=dev)

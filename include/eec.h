@@ -1344,6 +1344,89 @@ int eec_ctc_prefix_step(const float* logp, const int32_t* em_len, int n, int Tq,
                         const int64_t* last_tokens, int R, int R_prev, int s, const float* att, float w, int eos, int pad, int min_length,
                         float* local_out, void* state, size_t state_bytes, void* stream);
 
+/* ---- Contextual biasing: hot phrases in the CTC and AED beam searches (csrc/ctx_graph.hip, csrc/ctc_beam_ctx.hip) -------------------
+ * Telling a search which phrases to expect: WeNet's "context graph", icefall / sherpa's ContextGraph.  The reference has nothing of the
+ * kind (its cuda_ctc_decoder is third-party and takes no context): an addition, not a parity item.  tests/ctxbias_cases.py restates
+ * everything below in fp64 and Python integers.
+ *
+ * Graph.  P >= 0 phrases over a vocabulary of V <= 256 tokens; a phrase is a non-empty row of tokens of [0, V), none of them blank, eos
+ * or pad, with a finite per-token boost b_p >= 0.  The trie of the phrases has node 0 as its root; nodes are numbered in the order in
+ * which inserting the phrases one after the other creates them.
+ *     token_score(n)  the largest b_p over the phrases through n
+ *     node_score(n)   node_score(parent) + token_score(n), node_score(0) = 0
+ *     end(n)          a phrase ends at n
+ *     fail(n)         the longest proper suffix of n's path that is a trie node (the Aho-Corasick failure link); fail of a child of the
+ *                     root is the root
+ *     out(n)          (end(n) ? node_score(n) : 0) + out(fail(n)), out(0) = 0: the end nodes on the chain n, fail(n), fail(fail(n)), ...
+ *     goto(s, v)      child v of the first node on s's failure chain that has one, else the root
+ *     delta(s, v)     (node_score(goto) - node_score(s)) + out(goto)        final(s) = 0 - node_score(s)
+ * all in fp64 in the order written.  The open bonus node_score(s) is provisional: leaving a partial match pays it back, final(s) takes
+ * it back at the end of a hypothesis, and a completed phrase pays node_score of its end node once more, for good.  So the bias of a
+ * finished hypothesis y is the sum, over every occurrence of every phrase in y (overlapping and nested ones count), of node_score of
+ * that phrase's end node.  Special tokens: blank keeps the state and pays 0 (the CTC search never takes it; it is a row of the
+ * tables all the same).  With eos and / or pad given (-1: none) there is one more state behind the trie's, the dead one:
+ * goto(s, eos) = dead and delta(s, eos) = final(s), pad alike; every token leaves the dead state at 0 into itself and final(dead) = 0.
+ * The bias is accumulated in fp32 along the prefix, one rounded add per token, bias(y . v) = fl(bias(y) + delta): a function of the
+ * token row alone.
+ *
+ * Image (host only, no device call; the size-query-then-fill form of eec_resample_plan).  G graphs in one image of int32 words:
+ *     word 0 EEC_CTX_MAGIC, 1 G, 2 the image's size in words, 3 V
+ *     graph g, words 4 + 4 g ..:  S (states), then the word offsets of delta [S][V] fp32 (the fp64 value rounded once), of
+ *     next [S][V] int32 and of final [S] fp32
+ * n_phrases [G] phrases per graph (0: a graph that biases nothing), phrase_len / boost one entry per phrase, graph after graph,
+ * `tokens` the phrases' tokens one after the other.  Failure links are resolved here; the device never follows one.  Refused with a
+ * message (EEC_ERR_BAD_ARG, before anything is written; *_bytes returns 0): G outside [1, EEC_CTX_MAX_GRAPHS], more than
+ * EEC_CTX_MAX_STATES states over all graphs (64 MB of tables at V = 256), a phrase of more than EEC_CTX_MAX_PHRASE tokens or of none,
+ * a token outside [0, V), blank, eos or pad inside a phrase, a boost that is negative or not finite (or a phrase whose boosts add up
+ * beyond the fp32 range), V outside [1, 256], blank outside [0, V), a null pointer; (EEC_ERR_WORKSPACE) a short image.  The limits are
+ * choices, not measurements.
+ * A sequence chooses its graph by graph_of [n_seq] int32 on the device; NULL: graph 0 for all; an index outside [0, G) switches biasing
+ * off for that sequence, as does image == NULL.  The kernels never trust an image: a header that does not describe tables inside
+ * image_bytes switches biasing off, a `next` value outside [0, S) is taken as the root.
+ *
+ * CTC prefix beam search: eec_ctc_beam_decode_ctx (the best-prefix end) and eec_ctc_beam_decode_nbest_ctx (the N-best end) take the
+ * arguments of eec_ctc_beam_decode_len / _nbest and image, image_bytes, graph_of and bias ([n_seq], [n_seq][nbest]).  It is that search
+ * (csrc/ctc_beam.hip compiled with EEC_CTC_CTX) with one change: every ranking compares key = fl(total log-probability + bias).  A stay
+ * keeps its prefix's state and bias; an extension of beam i by label c has bias fl(bias_i + delta[state_i][c]) and state
+ * next[state_i][c], its key is fl(mass + that bias); an extension that spells an existing prefix merges into it as before (that
+ * prefix's bias is the same number by construction).  A blank-skipped frame changes nothing; candidate ids and tie rules are unchanged.
+ * At the end each prefix's bias becomes fl(bias + final[state]) and both ends rank by fl(total + that).  scores stays the CTC
+ * log-probability alone, so downstream mixing keeps its meaning; bias is returned beside it (0 for an absent hypothesis).  An empty
+ * graph, graph_of = -1, no image and all-zero boosts return the tokens, counts and scores of the entries without context bit for
+ * bit, with bias 0.  Nothing is read back and there are no atomics: graph-capturable; two runs and a split batch (graph_of sliced to
+ * match) return the same bits.
+ *
+ * AED lockstep search: eec_context_bias_step, with the place eec_ctc_prefix_step has in the loop.  One launch, one workgroup per
+ * (search, beam) row.  state: int32 [2][n][R_max], eec_context_bias_state_bytes(n, R_max) bytes; step s reads half s & 1 and writes
+ * the other.  Row (i, r): state = root at s == 0 (the token there is SOS and is not read), else
+ * next[state_prev[parent[i][r]]][last[i][r]] (parent == NULL: r; a parent outside [0, R_prev) or a token outside [0, V): the root);
+ * then out[i][r][v] = local[i][r][v] + delta[state][v], one fp32 add per element, an entry at -inf stays -inf; out == local is
+ * allowed.  The bonus is part of the step's log-prob and therefore shares the step's length penalty: the closed form above holds for
+ * pen_alpha = 0.  The graph for these searches is built with eos and pad, so a beam's bias stops at its EOS with the open bonus taken
+ * back.  A search that declares its rows final without an EOS (the lockstep searches do, after max_length steps) adds
+ * final[next[state][last token]] to each row's score itself, at the last step's penalty: one gather on the image, once per search
+ * (ContextBiasSession.final), so that every final score carries the closed form.  EEC_ERR_BAD_ARG: a null pointer, R or R_prev outside [1, R_max], R_max outside [1, 16], V outside [1, 256]; n == 0 is a
+ * successful no-op. */
+#define EEC_CTX_MAGIC 0x43545847
+#define EEC_CTX_MAX_GRAPHS 1024
+#define EEC_CTX_MAX_STATES 32768
+#define EEC_CTX_MAX_PHRASE 64
+size_t eec_context_graph_bytes(int G, const int32_t* n_phrases, const int32_t* phrase_len, const int32_t* tokens, const double* boost, int V,
+                               int blank, int eos, int pad);
+int eec_context_graph(int G, const int32_t* n_phrases, const int32_t* phrase_len, const int32_t* tokens, const double* boost, int V, int blank,
+                      int eos, int pad, void* image, size_t image_bytes);
+int eec_ctc_beam_decode_ctx(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                            float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                            float* scores, const void* image, size_t image_bytes, const int32_t* graph_of, float* bias, void* stream);
+int eec_ctc_beam_decode_nbest_ctx(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                                  float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens,
+                                  int32_t* counts, float* scores, int32_t* n_hyp, const void* image, size_t image_bytes,
+                                  const int32_t* graph_of, float* bias, void* stream);
+size_t eec_context_bias_state_bytes(int n, int R_max);
+int eec_context_bias_step(const void* image, size_t image_bytes, const int32_t* graph_of, int n, int R, int R_prev, int R_max, int V, int s,
+                          const int64_t* parent, const int64_t* last, const float* local, float* out, void* state, size_t state_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
