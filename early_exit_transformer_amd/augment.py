@@ -487,6 +487,10 @@ WAVEAUG_PARAMS, WAVEAUG_TILE, WAVEAUG_MAX_BANK, WAVEAUG_MAX_SNRS = 5, 1024, 4096
 REVERB_MAX_TAPS = 16384                                                       # EEC_REVERB_MAX_TAPS
 RIR_NORMS = {"none": 0, "l2": 1, "peak": 2}                                   # EEC_RIR_NORM_NONE, _L2, _PEAK
 RIR_MAGIC, NOISE_MAGIC = 0x52495242, 0x4E4F4953                               # EEC_RIR_MAGIC, EEC_NOISE_MAGIC
+REVERB_FFT_BLOCK = 2048                                                       # EEC_REVERB_FFT_BLOCK
+RIR_SPECTRA_MAGIC = 0x52495246                                                # EEC_RIR_SPECTRA_MAGIC
+REVERB_FFT_MIN_TAPS = 256                                                     # EEC_REVERB_FFT_MIN_TAPS
+REVERB_METHODS = ("direct", "fft")
 _ONE_BITS = 0x3F800000                                                     # 1.0f
 
 
@@ -539,15 +543,57 @@ class RirBank(_Bank):
     """The image ``eec_rir_bank`` builds of ``rirs``, a list of 1-D arrays or tensors of at most 16384 taps each (include/eec.h has
     the layout).  ``normalize``: "l2" (unit energy), "peak" or "none", in fp64, each tap rounded once; zero heads and tails are
     dropped.  ``shift`` True (Kaldi's ``--shift-output``): the peak of a RIR -- the first index of ``max |h|`` -- stays where the
-    sample was, so frame counts and CTC targets are untouched; False: the plain causal convolution cut to the input's length."""
+    sample was, so frame counts and CTC targets are untouched; False: the plain causal convolution cut to the input's length.
 
-    def __init__(self, rirs, normalize: str = "l2", shift: bool = True):
+    ``method``: how ``reverberate``, ``wave_augment`` and ``WaveAugment`` evaluate the convolution with this bank.  "direct" (the
+    default): the tap-order fp32 sum of ``eec_reverb``, bit-identical between kernel and host path, whose cost grows with the taps.
+    "fft": ``eec_reverb_fft``, partitioned overlap-save with blocks of ``REVERB_FFT_BLOCK`` samples, for RIRs of thousands of taps:
+    the same definition inside a stated error bound (include/eec.h, "Reverberation by FFT"), deterministic, but bit-identical neither
+    to the direct path nor to the host path, which for an FFT bank is ``np.fft`` in fp64 rounded once.  The spectral image is built
+    at the first FFT use of the bank and uploaded once per device.  ``max_workspace_bytes`` (an attribute, 2 GiB): above it the FFT
+    path splits a call over utterances, which changes no bit.  "auto": "fft" when the longest stored RIR has at least
+    ``REVERB_FFT_MIN_TAPS`` taps -- the smallest timed tap count from which the FFT path measured faster
+    (profiles/waveaug_fft_time.json) --, "direct" otherwise; resolved here, once, and kept as ``bank.method``."""
+
+    max_workspace_bytes = 2 << 30
+
+    def __init__(self, rirs, normalize: str = "l2", shift: bool = True, method: str = "direct"):
         if normalize not in RIR_NORMS:
             raise ValueError(f"RirBank: normalize must be 'l2', 'peak' or 'none', got {normalize!r}")
+        if method not in REVERB_METHODS + ("auto",):
+            raise ValueError(f"RirBank: method must be one of {', '.join(repr(m) for m in REVERB_METHODS)} or 'auto', got {method!r}")
         taps, n = _rows_fp32("RirBank", rirs, REVERB_MAX_TAPS)
         args = (len(n), taps.ctypes.data, n.ctypes.data, RIR_NORMS[normalize], int(bool(shift)))
         self._build("eec_rir_bank", lambda lib: lib.eec_rir_bank_bytes(*args), lambda lib, image, nbytes: lib.eec_rir_bank(*args, image, nbytes))
         self.normalize, self.shift = normalize, bool(shift)
+        self.max_taps = int(self.image[4:4 + 4 * self.count:4].max())  # the longest stored RIR
+        self.method = method if method != "auto" else "fft" if self.max_taps >= REVERB_FFT_MIN_TAPS else "direct"
+        self.spectra: Optional[np.ndarray] = None
+        self._spectra_dev: Dict[torch.device, Tensor] = {}
+
+    def spectra_image(self) -> np.ndarray:
+        """The image ``eec_rir_spectra`` builds of the tap image (int32 words; include/eec.h has the layout), made once."""
+        if self.spectra is None:
+            lib = capi.load()
+            nbytes = lib.eec_rir_spectra_bytes(self.image.ctypes.data)
+            if nbytes == 0:
+                raise ValueError(lib.eec_last_error().decode(errors="replace"))
+            image = np.zeros(nbytes // 4, dtype=np.int32)
+            capi.check(lib.eec_rir_spectra(self.image.ctypes.data, image.ctypes.data, nbytes), "eec_rir_spectra")
+            self.spectra = image
+        return self.spectra
+
+    def spectra_on(self, dev: torch.device) -> Tensor:
+        t = self._spectra_dev.get(dev)
+        if t is None:
+            t = self._spectra_dev[dev] = torch.from_numpy(self.spectra_image()).to(dev)
+        return t
+
+    def spectrum(self, r: int) -> np.ndarray:
+        """fp32 ``[P, 2 * REVERB_FFT_BLOCK]``: the stored spectra of RIR ``r``, partition after partition."""
+        image = self.spectra_image()
+        P, at = (int(v) for v in image[8 + 2 * r:10 + 2 * r])
+        return image[at:at + P * 2 * REVERB_FFT_BLOCK].view(np.float32).reshape(P, 2 * REVERB_FFT_BLOCK)
 
     def rir(self, r: int) -> Tuple[int, np.ndarray]:
         """``(d, taps)`` of RIR ``r``: the shift and the stored fp32 taps."""
@@ -626,8 +672,26 @@ def _host_reverb(x: np.ndarray, d: int, h: np.ndarray) -> np.ndarray:
     return acc
 
 
+def _host_reverb_fft(x: np.ndarray, d: int, h: np.ndarray) -> np.ndarray:
+    """The same y by ``np.fft`` in fp64: the full linear convolution, cut at ``d``, rounded once to fp32."""
+    n, K = x.shape[0], h.shape[0]
+    size = 1 << (n + K - 1).bit_length()
+    full = np.fft.irfft(np.fft.rfft(x.astype(np.float64), size) * np.fft.rfft(h.astype(np.float64), size), size)[:n + K - 1]
+    at = np.arange(n, dtype=np.int64) + d
+    inside = (at >= 0) & (at < n + K - 1)
+    return np.where(inside, full[np.clip(at, 0, n + K - 2)], 0.0).astype(np.float32)
+
+
+def _reverb_method(who: str, rirs: Optional["RirBank"], method: Optional[str]) -> str:
+    if method is None:
+        return "direct" if rirs is None else rirs.method
+    if method not in REVERB_METHODS:
+        raise ValueError(f"{who}: method must be one of {', '.join(repr(m) for m in REVERB_METHODS)} or None, got {method!r}")
+    return method
+
+
 def _host_waveaug(wave: np.ndarray, n_all: np.ndarray, params: np.ndarray, rirs: Optional[RirBank], noises: Optional[NoiseBank],
-                  snr_gain: Sequence[float], reverb: bool = True, mix: bool = True):
+                  snr_gain: Sequence[float], reverb: bool = True, mix: bool = True, method: str = "direct"):
     B = wave.shape[0]
     out, applied = np.zeros_like(wave), np.zeros((B, 2), dtype=np.float32)
     for b in range(B):
@@ -635,7 +699,7 @@ def _host_waveaug(wave: np.ndarray, n_all: np.ndarray, params: np.ndarray, rirs:
         r, m, start, snr_idx, bits = (int(v) for v in params[b])
         y = wave[b, :n].copy()
         if reverb and rirs is not None and 0 <= r < len(rirs) and n > 0:
-            y = _host_reverb(y, *rirs.rir(r))
+            y = (_host_reverb_fft if method == "fft" else _host_reverb)(y, *rirs.rir(r))
         gain = np.array([bits], dtype=np.int32).view(np.float32)[0]
         scale = np.float32(0.0)
         if mix:
@@ -698,10 +762,13 @@ def _volume(who: str, volume) -> Optional[Tuple[float, float]]:
 
 
 def _waveaug_run(who: str, wave: Tensor, lengths: Optional[Tensor], params: Optional[Tensor], draw, rirs: Optional[RirBank],
-                 noises: Optional[NoiseBank], gains: Sequence[float], reverb: bool = True, mix: bool = True):
+                 noises: Optional[NoiseBank], gains: Sequence[float], reverb: bool = True, mix: bool = True, method: Optional[str] = None,
+                 max_workspace_bytes: Optional[int] = None):
     """The host path or the launches for a checked batch.  ``params`` None: drawn with ``draw`` = (seed, utt_offset, thr_reverb,
-    thr_noise, volume).  ``reverb`` / ``mix`` False: that launch is left out (the prescribed single-stage forms)."""
+    thr_noise, volume).  ``reverb`` / ``mix`` False: that launch is left out (the prescribed single-stage forms).  ``method`` and
+    ``max_workspace_bytes`` None: the bank's."""
     B, L = wave.shape
+    method = _reverb_method(who, rirs, method)
     dev = wave.device
     if lengths is not None:
         lengths = capi.to_device(lengths.reshape(B), dev, torch.int64).clamp(0, L).contiguous()
@@ -718,7 +785,7 @@ def _waveaug_run(who: str, wave: Tensor, lengths: Optional[Tensor], params: Opti
             params = torch.from_numpy(_host_waveaug_draw(B, seed, utt_offset, 0 if rirs is None else len(rirs), thr_r,
                                                          np.zeros(0, dtype=np.int32) if noises is None else noises.lengths, thr_n, len(gains),
                                                          volume))
-        out, applied = _host_waveaug(wave.numpy(), n, params.numpy(), rirs, noises, gains, reverb, mix)
+        out, applied = _host_waveaug(wave.numpy(), n, params.numpy(), rirs, noises, gains, reverb, mix, method)
         return torch.from_numpy(out), params, torch.from_numpy(applied)
 
     lib = capi.load()
@@ -740,7 +807,19 @@ def _waveaug_run(who: str, wave: Tensor, lengths: Optional[Tensor], params: Opti
         if mix and noises is not None:
             partials = torch.empty(max(lib.eec_waveaug_partials_bytes(B, L) // 8, 1), dtype=torch.float64, device=dev)
         part_ptr = None if partials is None else partials.data_ptr()
-        if reverb:
+        if reverb and method == "fft" and rirs is not None and B > 0:
+            # the spectra of every window go to a workspace; above max_workspace_bytes the call is split over utterances
+            most = int(rirs.max_workspace_bytes if max_workspace_bytes is None else max_workspace_bytes)
+            step = min(B, max(1, most // lib.eec_reverb_fft_workspace_bytes(1, L)))
+            nbytes = lib.eec_reverb_fft_workspace_bytes(step, L)
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            spec_ptr, tiles = rirs.spectra_on(dev).data_ptr(), max(-(-L // WAVEAUG_TILE), 1)
+            for b0 in range(0, B, step):
+                capi.check(lib.eec_reverb_fft(wave.data_ptr() + 4 * b0 * L, None if len_ptr is None else len_ptr + 8 * b0,
+                                              params.data_ptr() + 4 * WAVEAUG_PARAMS * b0, min(step, B - b0), L, rir_ptr, spec_ptr,
+                                              out.data_ptr() + 4 * b0 * L, None if part_ptr is None else part_ptr + 16 * tiles * b0,
+                                              work.data_ptr(), nbytes, stream), "eec_reverb_fft")
+        elif reverb:
             capi.check(lib.eec_reverb(wave.data_ptr(), len_ptr, params.data_ptr(), B, L, rir_ptr, out.data_ptr(), part_ptr, stream), "eec_reverb")
         if mix:
             if partials is not None:
@@ -764,7 +843,8 @@ def wave_augment(wave: Tensor, lengths: Optional[Tensor] = None, *, seed: int, u
     the noise segment's is that SNR), a gain uniform in ``volume`` = (lo, hi) (None: 1) -- so a call on a slice of the batch with
     ``utt_offset`` advanced returns the rows of the whole call.  Given: applied as they are; an index outside its bank (-1) switches
     the stage off, a start is reduced mod the row's length.  No host synchronisation; a CPU tensor takes the NumPy host path,
-    bit-identical for finite input.  The banks are uploaded at the first call on a device."""
+    bit-identical for finite input (with a bank of ``method="fft"``: the same definition inside its bound, not the same bits).  The
+    banks are uploaded at the first call on a device."""
     who = "wave_augment"
     wave, squeeze = _waveaug_batch(who, wave, lengths)
     rirs, noises = _waveaug_bank(who, "rirs", rirs, RirBank), _waveaug_bank(who, "noises", noises, NoiseBank)
@@ -781,9 +861,11 @@ def _rows_of(who: str, name: str, value, B: int, dev) -> Tensor:
     return value.reshape(B).to(dev).to(torch.int64).clamp(-(1 << 31), (1 << 31) - 1)
 
 
-def reverberate(wave: Tensor, lengths: Optional[Tensor], rirs: RirBank, index) -> Tensor:
+def reverberate(wave: Tensor, lengths: Optional[Tensor], rirs: RirBank, index, *, method: Optional[str] = None,
+                max_workspace_bytes: Optional[int] = None) -> Tensor:
     """``wave`` [B, L] or [L] convolved with the RIRs ``index`` (an integer or [B]) of ``rirs``; -1 or an index outside the bank copies
-    the utterance.  The rest as ``wave_augment``."""
+    the utterance.  ``method`` ("direct", "fft") and ``max_workspace_bytes`` override the bank's for this call.  The rest as
+    ``wave_augment``."""
     who = "reverberate"
     wave, squeeze = _waveaug_batch(who, wave, lengths)
     if not isinstance(rirs, RirBank):
@@ -791,7 +873,8 @@ def reverberate(wave: Tensor, lengths: Optional[Tensor], rirs: RirBank, index) -
     B, dev = wave.shape[0], wave.device
     params = torch.zeros((B, WAVEAUG_PARAMS), dtype=torch.int64, device=dev)
     params[:, 0], params[:, 1], params[:, 4] = _rows_of(who, "index", index, B, dev), -1, _ONE_BITS
-    out, _, _ = _waveaug_run(who, wave, lengths, params, None, rirs, None, [], mix=False)
+    out, _, _ = _waveaug_run(who, wave, lengths, params, None, rirs, None, [], mix=False, method=_reverb_method(who, rirs, method),
+                             max_workspace_bytes=max_workspace_bytes)
     return out[0] if squeeze else out
 
 

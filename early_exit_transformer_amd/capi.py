@@ -106,6 +106,7 @@ EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_c
            "eec_resample_plan_bytes", "eec_resample_plan", "eec_speed_draw", "eec_resample_lengths", "eec_resample",
            "eec_rir_bank_bytes", "eec_rir_bank", "eec_noise_bank_bytes", "eec_noise_bank", "eec_waveaug_partials_bytes", "eec_waveaug_draw",
            "eec_reverb", "eec_noise_energy", "eec_noise_mix",
+           "eec_rir_spectra_bytes", "eec_rir_spectra", "eec_reverb_fft_workspace_bytes", "eec_reverb_fft", "eec_reverb_fft_stage",
            "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
            "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
            "eec_train_forward", "eec_train_backward", "eec_train_backward_ex", "eec_train_gemm",
@@ -269,6 +270,14 @@ def load() -> C.CDLL:
                                      C.c_double, C.c_void_p, C.c_void_p]
     # wave, lengths, params; B, L; rir_bank, out, partials, stream
     lib.eec_reverb.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.eec_rir_spectra_bytes.argtypes = [C.c_void_p]
+    lib.eec_rir_spectra_bytes.restype = C.c_size_t
+    lib.eec_rir_spectra.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.eec_reverb_fft_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.eec_reverb_fft_workspace_bytes.restype = C.c_size_t
+    # wave, lengths, params; B, L; rir_bank, rir_spectra, out, partials, workspace; workspace_bytes; stream
+    lib.eec_reverb_fft.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
+    lib.eec_reverb_fft_stage.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_int, C.c_void_p]
     # signal, lengths, params; B, L; noise_bank, partials, stream
     lib.eec_noise_energy.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
     # y, lengths, params; B, L; noise_bank, snr_gain; n_snrs; partials, out, applied, stream

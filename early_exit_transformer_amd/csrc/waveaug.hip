@@ -19,21 +19,16 @@
 #include "../../include/eec.h"
 #include "eec_drop.h"
 #include "eec_host.h"
+#include "eec_waveaug.h"
 
 #include <cmath>
 #include <vector>
 
 namespace eec {
 
-constexpr int kWaThreads = 128;
-constexpr int kWaPer = 8;                 // consecutive outputs per work-item
-constexpr int kWaTile = EEC_WAVEAUG_TILE;
-static_assert(kWaTile == kWaThreads * kWaPer, "a work-item owns eight consecutive samples of the tile");
 constexpr int kWaChunk = 512;             // taps per LDS stage
 constexpr int kWaWin = kWaTile + kWaChunk;
 constexpr int kWaMixThreads = 256, kWaMixTile = 2048;
-constexpr int kWaHead = 4, kWaRirRec = 4, kWaNoiseRec = 2;  // words of an image's header and of a record
-constexpr int kWaP = EEC_WAVEAUG_PARAMS;
 
 struct WaSnr {
   double g[EEC_WAVEAUG_MAX_SNRS];
@@ -109,18 +104,6 @@ static int wa_noise_words(int M, const float* samples, const int32_t* n_samples,
 // ---------------------------------------------------------------------------------------------------------------------------
 // the kernels
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long wa_len(const int64_t* __restrict__ lengths, int b, int L) {
-  const long long n = lengths ? (long long)lengths[b] : (long long)L;
-  return n < 0 ? 0 : n > L ? L : n;
-}
-// record of RIR / noise row `at`, or nullptr: the stage is off (no bank, an index outside it)
-__device__ __forceinline__ const int* wa_record(const int* __restrict__ bank, int at, int rec_words) {
-  if (!bank) return nullptr;
-  const int n = bank[1];
-  if (at < 0 || at >= n || n > EEC_WAVEAUG_MAX_BANK) return nullptr;
-  return bank + kWaHead + rec_words * at;
-}
-
 __global__ __launch_bounds__(64) void waveaug_draw_kernel(int B, uint64_t seed, uint64_t utt_offset, const int* __restrict__ rir_bank, uint64_t thr_reverb,
                                                           const int* __restrict__ noise_bank, uint64_t thr_noise, int n_snrs, int volume, double lo,
                                                           double hi, int* __restrict__ params) {
@@ -144,23 +127,6 @@ __global__ __launch_bounds__(64) void waveaug_draw_kernel(int B, uint64_t seed, 
   if (volume) gain = (float)(lo + (hi - lo) * ((double)word(6) * 0x1p-32));
   int* p = params + (size_t)b * kWaP;
   p[0] = rir, p[1] = noise, p[2] = start, p[3] = snr, p[4] = __float_as_int(gain);
-}
-
-// the stated order inside a tile: the work-item's own sum, 64 lanes by halving, block 0 + block 1.  Valid in work-item 0.
-__device__ __forceinline__ double wa_tile_energy(double e, double* wsum) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) e = e + __shfl_down(e, s, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = e;
-  __syncthreads();
-  return wsum[0] + wsum[1];
-}
-__device__ __forceinline__ double wa_own_energy(const float (&v)[kWaPer], int valid) {
-#pragma clang fp contract(off)
-  double e = 0.0;
-#pragma unroll
-  for (int j = 0; j < kWaPer; ++j)
-    if (j < valid) e = e + (double)v[j] * (double)v[j];
-  return e;
 }
 
 __global__ __launch_bounds__(kWaThreads) void reverb_kernel(const float* __restrict__ wave, const int64_t* __restrict__ lengths,
@@ -344,19 +310,6 @@ __global__ __launch_bounds__(kWaMixThreads) void noise_mix_kernel(const float* y
       for (long long i = i0 + tid; i < i1; i += kWaMixThreads) ob[i] = i < len ? yb[i] * gain : 0.0f;
     }
   }
-}
-
-static int wa_check_batch(const char* who, int B, int L) {
-  using eech::fail;
-  const std::string w(who);
-  if (B < 0) return fail(EEC_ERR_BAD_ARG, w + ": B must not be negative, got " + std::to_string(B));
-  if (L < 0 || L > (1 << 30)) return fail(EEC_ERR_BAD_ARG, w + ": L must lie in [0, 2^30], got " + std::to_string(L));
-  return 0;
-}
-static int wa_tiles(int L) { return L > 0 ? (L + kWaTile - 1) / kWaTile : 1; }
-static int wa_launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : eech::hip_fail(e, who);
 }
 
 }  // namespace eec

@@ -1015,7 +1015,7 @@ int eec_resample(const float* wave, const int64_t* lengths, const int32_t* choic
  * advanced, lengths = NULL against lengths all L and a storage off a 16-byte boundary return the same bits.
  * EEC_ERR_BAD_ARG, before any device work, through eec_last_error(): B < 0, L outside [0, 2^30], n_snrs outside [0, 64], a threshold
  * above 2^32, lo or hi not finite, a null pointer where one is needed, out == wave in eec_reverb.  B == 0 is a successful no-op.
- * Not served: FFT convolution, reverberated point-source noises, babble, codec and clipping effects, a backward (the input is data). */
+ * Not served: reverberated point-source noises, babble, codec and clipping effects, a backward (the input is data). */
 #define EEC_WAVEAUG_SITE 0x57415547u
 #define EEC_WAVEAUG_PARAMS 5
 #define EEC_WAVEAUG_TILE 1024
@@ -1040,6 +1040,64 @@ int eec_noise_energy(const float* signal, const int64_t* lengths, const int32_t*
                      double* partials, void* stream);
 int eec_noise_mix(const float* y, const int64_t* lengths, const int32_t* params, int B, int L, const void* noise_bank,
                   const double* snr_gain, int n_snrs, const double* partials, float* out, float* applied, void* stream);
+
+/* ---- Reverberation by FFT (csrc/reverb_fft.hip) -------------------------------------------------------------------------------------
+ * A second evaluation of stage 1 above, y[i] = sum_k h[k] x[i + d - k] over the stored taps with x = 0 outside [0, len), for RIRs of
+ * thousands of taps, where the direct sum's cost grows with K.  Uniformly partitioned overlap-save in output coordinates, with
+ * S = EEC_REVERB_FFT_BLOCK and N = 2 S: RIR r of K taps has P = ceil(K / S) partitions, partition p the taps [p S, (p + 1) S) padded
+ * with zeros to N; output block m is y[m S, (m + 1) S); input window j of an utterance is x[(j - 1) S + d, (j + 1) S + d); and
+ *         Y_m = sum_{p = 0 .. P - 1} X_{m - p} * H_p          in that order, X and H the N-point DFTs, * bin by bin
+ * of whose inverse transform the last S samples are the block.  The block grid starts at the utterance's own sample 0, so every
+ * utterance comes out as if processed alone.  Multiply-adds may be fused.
+ *
+ * What this path keeps: rows are never trusted (an index outside the bank, or a spectral image that is not the bank's, copies the
+ * utterance bit for bit, as eec_reverb does); samples at or past len are never read; outputs there are 0.0; all-zero input gives exact
+ * zeros; two runs, a split batch, lengths = NULL against lengths all L and a storage off a 16-byte boundary return the same bits;
+ * `partials` receives the tile energies E_s of the fp32 output in the layout and order stated above, so eec_noise_energy and
+ * eec_noise_mix run unchanged behind it.  What it does not keep: it is not bit-identical to eec_reverb or to any host path, and a
+ * one-tap RIR is no longer an exact scaled copy.
+ *
+ * The bound.  u = 2^-24.  The transforms are Cooley-Tukey factorisations of log2 N radix-2 stages (the radix-8 and radix-4 butterflies
+ * are three and two of them with fewer twiddle products, the real split is the last) with fp32 twiddles rounded from fp64, so by
+ * Higham, Accuracy and Stability of Numerical Algorithms, Thm 24.2, a computed transform is off by at most log2 N * eta in the 2-norm
+ * relative to its result, eta = mu + gamma_4 (sqrt 2 + mu) < 7 u with mu <= u the twiddles' error.  Per term X_{m-p} H_p: 7 u log2 N
+ * from the window's transform, u from the one rounding of H_p, 3 u from the complex product; P - 1 additions add (P - 1) u of the
+ * sum of the terms' norms; the inverse transform adds 7 u log2 N; the scalings by 1/2 and 1/N are exact.  With
+ * ||X H_p||_2 <= ||H_p||_inf ||X||_2 <= ||h_p||_1 ||X||_2, Parseval, sum_p ||h_p||_1 = ||h||_1 and max |e| <= ||e||_2, for every
+ * output block
+ *         max |y_fft - y| <= (14 log2 N + P + 8) * 2^-24 * ||h||_1 * max_j ||x_j||_2        x_j the N-sample windows
+ * where 8 covers the 1 + 3 - 1 above and the second-order terms.  It catches gross faults only; the kernels use at most 5e-3 of it in the tests.
+ *
+ *   eec_rir_spectra (host only, *_bytes as for the banks): the spectral image of a tap image eec_rir_bank wrote, so both methods see
+ *       the same normalised, trimmed taps and the same d.  Every partition's N-point DFT is evaluated in fp64 by a radix-2 transform
+ *       in that file and every component rounded once to fp32.  A spectrum is N floats: word pair 0 = (X[0], X[N/2]), both real;
+ *       word pair k = (Re X[k], Im X[k]), 0 < k < N/2.
+ *           word 0 EEC_RIR_SPECTRA_MAGIC, 1 R, 2 the image's size in words, 3 S, 4 the word offset of the twiddles, 5 .. 7 0
+ *           RIR r, words 8 + 2 r ..:  P, the word offset of its P spectra (partition after partition)
+ *           twiddles: N/2 pairs (cos, -sin)(2 pi u / N), u < N/2, evaluated in fp64 and rounded once; the device computes no sincos
+ *       Every offset is a multiple of 4 words.  Refused (EEC_ERR_BAD_ARG): a null pointer, a tap image whose header or records are
+ *       not eec_rir_bank's, an image of 2^31 words or more; (EEC_ERR_WORKSPACE) a short image.
+ *   eec_reverb_fft: eec_reverb's contract argument for argument, plus the spectral image (device copy) and a workspace of
+ *       eec_reverb_fft_workspace_bytes(B, L) = max(B, 1) * (ceil(L / S) + EEC_REVERB_MAX_TAPS / S - 1) * N * 4 bytes, 16-byte aligned:
+ *       the spectra of the windows j = -(EEC_REVERB_MAX_TAPS / S - 1) .. ceil(L / S) - 1 of every utterance.  Two launches of 256
+ *       work-items per workgroup: one workgroup per (window, utterance) transforms the windows that hold a valid sample and that a
+ *       block of the utterance meets; one per (block, utterance) accumulates the products over the live windows, transforms back,
+ *       writes the block through LDS and the two tile energies.  rir_bank or rir_spectra NULL: every utterance is copied and the
+ *       workspace is not touched.  No atomics, nothing read back, no allocation, no synchronisation; graph-capturable.
+ * Refused as eec_reverb refuses, and (EEC_ERR_WORKSPACE) a null, misaligned or short workspace when both images are given. */
+#define EEC_REVERB_FFT_BLOCK 2048
+#define EEC_REVERB_FFT_MIN_TAPS 256 /* from this many taps on eec_reverb_fft measured faster than eec_reverb (profiles/waveaug_fft_time.json) */
+#define EEC_RIR_SPECTRA_MAGIC 0x52495246
+size_t eec_rir_spectra_bytes(const void* rir_bank_image);
+int eec_rir_spectra(const void* rir_bank_image, void* image, size_t image_bytes);
+size_t eec_reverb_fft_workspace_bytes(int B, int L);
+int eec_reverb_fft(const float* wave, const int64_t* lengths, const int32_t* params, int B, int L, const void* rir_bank,
+                   const void* rir_spectra, float* out, double* partials, void* workspace, size_t workspace_bytes, void* stream);
+/* for the timing tool: stages = 1 the windows' launch alone, 2 the blocks' launch alone (it reads the workspace as it finds it: run
+ * the windows' launch on the same arguments first), 3 both, which is eec_reverb_fft */
+int eec_reverb_fft_stage(const float* wave, const int64_t* lengths, const int32_t* params, int B, int L, const void* rir_bank,
+                         const void* rir_spectra, float* out, double* partials, void* workspace, size_t workspace_bytes, int stages,
+                         void* stream);
 
 /* Mel front end(SURVEY 8f row f3): replaces util/data_loader.py:7-18 -- torchaudio Spectrogram(n_fft = 2 * args.n_fft = 1024,
  * hop_length 160, win_length 320; hann window, power 2, centred frames with reflect padding) followed by MelScale(sample_rate,

@@ -2,6 +2,7 @@
 batch as waveforms, [64, 164 000] samples with lengths of 100 433 to 164 000.
 
     python tools/waveaug_time.py [--rounds 7] [--reps 20] [--out profiles/waveaug_time.json]
+    python tools/waveaug_time.py --fft [--rounds 7] [--reps 20] [--out profiles/waveaug_fft_time.json]
 
 One process; the legs run in turn, ``--rounds`` times, each as a train of calls between two device events (alternating puts all of
 them under the same box noise); the record holds the median, minimum and maximum per call:
@@ -17,6 +18,13 @@ them under the same box noise); the record holds the median, minimum and maximum
   whole batch with one RIR, then add_noise from elementwise ops and ``sum`` (lengths are not honoured, which only makes it cheaper).
 For scale the record repeats the default model's training step, 22.9 ms (README).  The device results are also compared with the
 host path on a slice and with the torch composition.  Records, not targets; a run without a HIP device fails.
+
+``--fft``: the same batch and protocol for the reverberation alone at 256, 512, 1024, 2048, 4000 and 16 000 taps, every utterance
+(``all``) or every other one (``half``) reverberated: ``direct_*`` eec_reverb, ``fft_*`` eec_reverb_fft (both launches),
+``fft_windows_*`` and ``fft_blocks_*`` each launch alone (eec_reverb_fft_stage), ``torch_rfft_*`` the ``rfft`` / ``irfft`` convolution
+of the whole batch with one RIR (lengths and the ``half`` switch not honoured).  ``fft_faster_from_taps`` is the smallest timed tap
+count from which the FFT path's median is below the direct path's in both setups (null: none).  The FFT path's output is compared
+with the direct path's and with an fp64 FFT on a full-length utterance.
 """
 import argparse
 import ctypes as C
@@ -68,14 +76,104 @@ def torch_ops(wave, h, noise, gain_db, n_fft):
     return y + torch.sqrt(es / en) * gain_db * noise
 
 
+FFT_TAPS = (256, 512, 1024, 2048, 4000, 16000)
+
+
+def main_fft(args):
+    lib = capi.load()
+    dev = torch.device("cuda", 0)
+    st = capi.stream_ptr(dev)
+    rng = np.random.default_rng(0)
+    gen = torch.Generator().manual_seed(0)
+    wave = (torch.randn(B, L, generator=gen) * 0.1).to(dev)
+    lens_host = [L - (1009 * b) % 64001 for b in range(B)]  # ragged: 100 433 .. 164 000 samples
+    lens = torch.tensor(lens_host, dtype=torch.int64, device=dev)
+    sized = augment.RirBank([rir(K, rng) for K in FFT_TAPS], method="fft")
+    rir_img, spec_img = sized.on(dev), sized.spectra_on(dev)
+    out, ref = torch.empty_like(wave), torch.empty_like(wave)
+    partials = torch.zeros(lib.eec_waveaug_partials_bytes(B, L) // 8, dtype=torch.float64, device=dev)
+    nbytes = lib.eec_reverb_fft_workspace_bytes(B, L)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    params = {(K, name): torch.tensor([[k if b % every == 0 else -1, -1, 0, 0, ONE] for b in range(B)], dtype=torch.int32, device=dev)
+              for k, K in enumerate(FFT_TAPS) for name, every in (("all", 1), ("half", 2))}
+
+    def direct(kind, to=out):
+        capi.check(lib.eec_reverb(wave.data_ptr(), lens.data_ptr(), params[kind].data_ptr(), B, L, rir_img.data_ptr(), to.data_ptr(), partials.data_ptr(),
+                                  st), "eec_reverb")
+
+    def fft(kind, stages=3):
+        capi.check(lib.eec_reverb_fft_stage(wave.data_ptr(), lens.data_ptr(), params[kind].data_ptr(), B, L, rir_img.data_ptr(), spec_img.data_ptr(),
+                                            out.data_ptr(), partials.data_ptr(), work.data_ptr(), nbytes, stages, st), "eec_reverb_fft_stage")
+
+    n_fft = 1 << 18
+    assert n_fft >= L + max(FFT_TAPS) - 1
+    legs, slow = {}, {}
+    for k, K in enumerate(FFT_TAPS):
+        h = torch.from_numpy(sized.rir(k)[1].copy()).to(dev)
+        p = int(h.abs().argmax())
+        slow[f"torch_rfft_{K}"] = lambda h=h, p=p: torch.fft.irfft(torch.fft.rfft(wave, n_fft) * torch.fft.rfft(h, n_fft), n_fft)[:, p:p + L]
+        for name in ("all", "half"):
+            kind = (K, name)
+            (slow if K > 2048 else legs)[f"direct_{K}_{name}"] = lambda kind=kind: direct(kind)
+            legs[f"fft_{K}_{name}"] = lambda kind=kind: fft(kind)
+            legs[f"fft_windows_{K}_{name}"] = lambda kind=kind: fft(kind, 1)
+            legs[f"fft_blocks_{K}_{name}"] = lambda kind=kind: fft(kind, 2)
+
+    checks = {}
+    full = lens_host.index(L)
+    for k, K in enumerate(FFT_TAPS):
+        direct((K, "all"), ref)
+        fft((K, "all"))
+        h = torch.from_numpy(sized.rir(k)[1].copy()).to(dev)
+        p = int(h.abs().argmax())
+        y = torch.fft.irfft(torch.fft.rfft(wave[full].double(), n_fft) * torch.fft.rfft(h.double(), n_fft), n_fft)[p:p + L]
+        checks[f"fft_{K}_max_abs_diff_vs_fp64_fft_over_max_abs"] = float((out[full].double() - y).abs().max() / y.abs().max())
+        checks[f"direct_{K}_max_abs_diff_vs_fp64_fft_over_max_abs"] = float((ref[full].double() - y).abs().max() / y.abs().max())
+        checks[f"fft_{K}_max_abs_diff_vs_direct_over_max_abs"] = float((out.double() - ref.double()).abs().max() / ref.abs().max())
+
+    for fn in list(legs.values()) + list(slow.values()):
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in list(legs) + list(slow)}
+    for _ in range(args.rounds):
+        for k, fn in legs.items():
+            ms[k].append(train_of(fn, args.reps))
+        for k, fn in slow.items():
+            ms[k].append(train_of(fn, 2))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    faster = [K for K in FFT_TAPS if all(med[f"fft_{K}_{name}"] < med[f"direct_{K}_{name}"] for name in ("all", "half"))]
+    from_taps = None
+    for K in reversed(FFT_TAPS):  # the smallest tap count from which every timed one is faster
+        if K not in faster:
+            break
+        from_taps = K
+    rec = {"what": "waveaug_fft", "device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "torch": torch.__version__,
+           "shape": [B, L], "lengths": [min(lens_host), max(lens_host)], "taps": list(FFT_TAPS), "block": augment.REVERB_FFT_BLOCK,
+           "workspace_bytes": nbytes, "fft_size_of_torch_rfft": n_fft, "rounds": args.rounds, "calls_per_train": args.reps,
+           "calls_per_train_slow_legs": 2, "slow_legs": list(slow), "training_step_ms_for_scale": TRAIN_STEP_MS, "agreement": checks,
+           "fft_faster_from_taps": from_taps}
+    for k, v in ms.items():
+        rec[k + "_ms_per_call"] = spread(v)
+    print(json.dumps(rec))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump([rec], f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "waveaug_time.json"))
+    ap.add_argument("--fft", action="store_true", help="time the reverberation by FFT against the direct path")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "waveaug_fft_time.json" if args.fft else "waveaug_time.json")
     if not torch.cuda.is_available():
         raise SystemExit("waveaug_time.py measures on a HIP device; none found")
+    if args.fft:
+        return main_fft(args)
 
     lib = capi.load()
     dev = torch.device("cuda", 0)
