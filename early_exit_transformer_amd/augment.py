@@ -200,16 +200,12 @@ def spec_augment(mel: Tensor, frame_len: Optional[Tensor] = None, *, seed: int, 
         out = _host_apply(mel.numpy(), n, params.numpy(), n_freq, n_time, time_warp_mode == "bicubic", mask_value)
         return torch.from_numpy(out), params
 
-    lib = capi.load()
-    fl_ptr = None if frame_len is None or B == 0 else frame_len.data_ptr()
+    fl = None if B == 0 else frame_len
     out = torch.empty_like(mel)
-    with torch.cuda.device(dev):
-        if params is None:
-            params = torch.empty((B, P), dtype=torch.int32, device=dev)
-            capi.check(lib.eec_specaug_draw(fl_ptr, B, n_mels, T, seed, utt_offset, W, n_freq, F, n_time, ratio, Tmax, params.data_ptr(),
-                                            capi.stream_ptr(dev)), "eec_specaug_draw")
-        capi.check(lib.eec_specaug_apply(mel.data_ptr(), fl_ptr, params.data_ptr(), B, n_mels, T, n_freq, n_time, MODES[time_warp_mode],
-                                         mask_value, out.data_ptr(), capi.stream_ptr(dev)), "eec_specaug_apply")
+    if params is None:
+        params = torch.empty((B, P), dtype=torch.int32, device=dev)
+        capi.launch("eec_specaug_draw", dev, fl, B, n_mels, T, seed, utt_offset, W, n_freq, F, n_time, ratio, Tmax, params)
+    capi.launch("eec_specaug_apply", dev, mel, fl, params, B, n_mels, T, n_freq, n_time, MODES[time_warp_mode], mask_value, out)
     return out, params
 
 
@@ -272,7 +268,7 @@ class ResamplePlan:
         if nbytes == 0:
             raise ValueError(lib.eec_last_error().decode(errors="replace"))
         self.image = np.zeros(nbytes // 4, dtype=np.int32)
-        capi.check(lib.eec_resample_plan(R, orig, new, lowpass_filter_width, rolloff, self.image.ctypes.data, nbytes), "eec_resample_plan")
+        capi.call("eec_resample_plan", R, orig, new, lowpass_filter_width, rolloff, self.image.ctypes.data, nbytes)
         self.ratios = [(int(self.image[4 + 8 * r]), int(self.image[5 + 8 * r])) for r in range(R)]
         self._dev: Dict[torch.device, Tensor] = {}
 
@@ -406,18 +402,14 @@ def _resample_with(who: str, wave: Tensor, lengths: Optional[Tensor], plan_of, c
         out, out_len = _host_resample(wave.numpy(), n, choice.numpy(), plan, L_out)
         out, out_len = torch.from_numpy(out), torch.from_numpy(out_len)
     else:
-        lib = capi.load()
         image = plan.on(dev)
-        len_ptr = None if lengths is None or B == 0 else lengths.data_ptr()
+        lens = None if B == 0 else lengths
         out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
         out_len = torch.empty((B,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            if choice is None:
-                choice = torch.empty((B,), dtype=torch.int32, device=dev)
-                capi.check(lib.eec_speed_draw(len_ptr, B, L, seed, utt_offset, image.data_ptr(), choice.data_ptr(), out_len.data_ptr(),
-                                              capi.stream_ptr(dev)), "eec_speed_draw")
-            capi.check(lib.eec_resample(wave.data_ptr(), len_ptr, choice.data_ptr(), B, L, image.data_ptr(), out.data_ptr(), L_out,
-                                        out_len.data_ptr(), capi.stream_ptr(dev)), "eec_resample")
+        if choice is None:
+            choice = torch.empty((B,), dtype=torch.int32, device=dev)
+            capi.launch("eec_speed_draw", dev, lens, B, L, seed, utt_offset, image, choice, out_len)
+        capi.launch("eec_resample", dev, wave, lens, choice, B, L, image, out, L_out, out_len)
     return (out[0], out_len[0], choice[0]) if squeeze else (out, out_len, choice)
 
 
@@ -519,13 +511,14 @@ class _Bank:
 
     image: np.ndarray
 
-    def _build(self, who: str, size_of, build) -> None:
+    def _build(self, entry: str, *args) -> None:
+        """``entry(*args, image, its bytes)`` into an image of ``entry_bytes(*args)`` bytes."""
         lib = capi.load()
-        nbytes = size_of(lib)
+        nbytes = getattr(lib, entry + "_bytes")(*args)
         if nbytes == 0:
             raise ValueError(lib.eec_last_error().decode(errors="replace"))
         self.image = np.zeros(nbytes // 4, dtype=np.int32)
-        capi.check(build(lib, self.image.ctypes.data, nbytes), who)
+        capi.call(entry, *args, self.image.ctypes.data, nbytes)
         self.count = int(self.image[1])
         self._dev: Dict[torch.device, Tensor] = {}
 
@@ -563,8 +556,7 @@ class RirBank(_Bank):
         if method not in REVERB_METHODS + ("auto",):
             raise ValueError(f"RirBank: method must be one of {', '.join(repr(m) for m in REVERB_METHODS)} or 'auto', got {method!r}")
         taps, n = _rows_fp32("RirBank", rirs, REVERB_MAX_TAPS)
-        args = (len(n), taps.ctypes.data, n.ctypes.data, RIR_NORMS[normalize], int(bool(shift)))
-        self._build("eec_rir_bank", lambda lib: lib.eec_rir_bank_bytes(*args), lambda lib, image, nbytes: lib.eec_rir_bank(*args, image, nbytes))
+        self._build("eec_rir_bank", len(n), taps.ctypes.data, n.ctypes.data, RIR_NORMS[normalize], int(bool(shift)))
         self.normalize, self.shift = normalize, bool(shift)
         self.max_taps = int(self.image[4:4 + 4 * self.count:4].max())  # the longest stored RIR
         self.method = method if method != "auto" else "fft" if self.max_taps >= REVERB_FFT_MIN_TAPS else "direct"
@@ -579,7 +571,7 @@ class RirBank(_Bank):
             if nbytes == 0:
                 raise ValueError(lib.eec_last_error().decode(errors="replace"))
             image = np.zeros(nbytes // 4, dtype=np.int32)
-            capi.check(lib.eec_rir_spectra(self.image.ctypes.data, image.ctypes.data, nbytes), "eec_rir_spectra")
+            capi.call("eec_rir_spectra", self.image.ctypes.data, image.ctypes.data, nbytes)
             self.spectra = image
         return self.spectra
 
@@ -606,8 +598,7 @@ class NoiseBank(_Bank):
 
     def __init__(self, noises):
         samples, n = _rows_fp32("NoiseBank", noises, MAX_SAMPLES)
-        args = (len(n), samples.ctypes.data, n.ctypes.data)
-        self._build("eec_noise_bank", lambda lib: lib.eec_noise_bank_bytes(*args), lambda lib, image, nbytes: lib.eec_noise_bank(*args, image, nbytes))
+        self._build("eec_noise_bank", len(n), samples.ctypes.data, n.ctypes.data)
         self.lengths = self.image[4:4 + 2 * self.count:2].copy()
 
     def noise(self, m: int) -> np.ndarray:
@@ -789,44 +780,37 @@ def _waveaug_run(who: str, wave: Tensor, lengths: Optional[Tensor], params: Opti
         return torch.from_numpy(out), params, torch.from_numpy(applied)
 
     lib = capi.load()
-    rir_ptr = None if rirs is None else rirs.on(dev).data_ptr()
-    noise_ptr = None if noises is None else noises.on(dev).data_ptr()
-    len_ptr = None if lengths is None or B == 0 else lengths.data_ptr()
+    rir_bank = None if rirs is None else rirs.on(dev)
+    noise_bank = None if noises is None else noises.on(dev)
+    lens = None if B == 0 else lengths
     out = torch.empty_like(wave)
     applied = torch.zeros((B, 2), dtype=torch.float32, device=dev) if not mix else torch.empty((B, 2), dtype=torch.float32, device=dev)
     table = (C.c_double * max(len(gains), 1))(*gains)
-    with torch.cuda.device(dev):
-        stream = capi.stream_ptr(dev)
-        if params is None:
-            seed, utt_offset, thr_r, thr_n, volume = draw
-            lo, hi = volume if volume is not None else (1.0, 1.0)
-            params = torch.empty((B, WAVEAUG_PARAMS), dtype=torch.int32, device=dev)
-            capi.check(lib.eec_waveaug_draw(B, seed, utt_offset, rir_ptr, thr_r, noise_ptr, thr_n, len(gains), int(volume is not None), lo, hi,
-                                            params.data_ptr(), stream), "eec_waveaug_draw")
-        partials = None
-        if mix and noises is not None:
-            partials = torch.empty(max(lib.eec_waveaug_partials_bytes(B, L) // 8, 1), dtype=torch.float64, device=dev)
-        part_ptr = None if partials is None else partials.data_ptr()
-        if reverb and method == "fft" and rirs is not None and B > 0:
-            # the spectra of every window go to a workspace; above max_workspace_bytes the call is split over utterances
-            most = int(rirs.max_workspace_bytes if max_workspace_bytes is None else max_workspace_bytes)
-            step = min(B, max(1, most // lib.eec_reverb_fft_workspace_bytes(1, L)))
-            nbytes = lib.eec_reverb_fft_workspace_bytes(step, L)
-            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            spec_ptr, tiles = rirs.spectra_on(dev).data_ptr(), max(-(-L // WAVEAUG_TILE), 1)
-            for b0 in range(0, B, step):
-                capi.check(lib.eec_reverb_fft(wave.data_ptr() + 4 * b0 * L, None if len_ptr is None else len_ptr + 8 * b0,
-                                              params.data_ptr() + 4 * WAVEAUG_PARAMS * b0, min(step, B - b0), L, rir_ptr, spec_ptr,
-                                              out.data_ptr() + 4 * b0 * L, None if part_ptr is None else part_ptr + 16 * tiles * b0,
-                                              work.data_ptr(), nbytes, stream), "eec_reverb_fft")
-        elif reverb:
-            capi.check(lib.eec_reverb(wave.data_ptr(), len_ptr, params.data_ptr(), B, L, rir_ptr, out.data_ptr(), part_ptr, stream), "eec_reverb")
-        if mix:
-            if partials is not None:
-                capi.check(lib.eec_noise_energy(None if reverb else wave.data_ptr(), len_ptr, params.data_ptr(), B, L, noise_ptr, part_ptr, stream),
-                           "eec_noise_energy")
-            capi.check(lib.eec_noise_mix(out.data_ptr() if reverb else wave.data_ptr(), len_ptr, params.data_ptr(), B, L, noise_ptr, table, len(gains),
-                                         part_ptr, out.data_ptr(), applied.data_ptr(), stream), "eec_noise_mix")
+    if params is None:
+        seed, utt_offset, thr_r, thr_n, volume = draw
+        lo, hi = volume if volume is not None else (1.0, 1.0)
+        params = torch.empty((B, WAVEAUG_PARAMS), dtype=torch.int32, device=dev)
+        capi.launch("eec_waveaug_draw", dev, B, seed, utt_offset, rir_bank, thr_r, noise_bank, thr_n, len(gains), int(volume is not None), lo, hi,
+                    params)
+    partials = None
+    if mix and noises is not None:
+        partials = torch.empty(max(lib.eec_waveaug_partials_bytes(B, L) // 8, 1), dtype=torch.float64, device=dev)
+    if reverb and method == "fft" and rirs is not None and B > 0:
+        # the spectra of every window go to a workspace; above max_workspace_bytes the call is split over utterances
+        most = int(rirs.max_workspace_bytes if max_workspace_bytes is None else max_workspace_bytes)
+        step = min(B, max(1, most // lib.eec_reverb_fft_workspace_bytes(1, L)))
+        nbytes = lib.eec_reverb_fft_workspace_bytes(step, L)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        spectra, tiles = rirs.spectra_on(dev), max(-(-L // WAVEAUG_TILE), 1)
+        for b0 in range(0, B, step):
+            capi.launch("eec_reverb_fft", dev, wave[b0:], None if lens is None else lens[b0:], params[b0:], min(step, B - b0), L, rir_bank,
+                        spectra, out[b0:], None if partials is None else partials[2 * tiles * b0:], work, nbytes)
+    elif reverb:
+        capi.launch("eec_reverb", dev, wave, lens, params, B, L, rir_bank, out, partials)
+    if mix:
+        if partials is not None:
+            capi.launch("eec_noise_energy", dev, None if reverb else wave, lens, params, B, L, noise_bank, partials)
+        capi.launch("eec_noise_mix", dev, out if reverb else wave, lens, params, B, L, noise_bank, table, len(gains), partials, out, applied)
     return out, params, applied
 
 

@@ -350,20 +350,16 @@ class BeamInference:
         (``ctc_beam_decode(context=)``); ``.score`` stays the CTC log-probability and every hypothesis also carries ``.bias``."""
         beam = self._arg(beam_size, "beam_size")
         ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
-        if nbest is not None:
-            tok, cnt, score, n_hyp, *bias = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95,
-                                                                              em_len=lengths, nbest=nbest, **ctx))
-            hyps = [[CTCHypothesis(tok[b, r, : int(cnt[b, r])].tolist(), [], float(score[b, r])) for r in range(int(n_hyp[b]))]
-                    for b in range(tok.size(0))]
-            for b, row in enumerate(hyps if bias else []):
-                for r, h in enumerate(row):
-                    h.bias = float(bias[0][b, r])
-        else:
-            tok, cnt, score, *bias = (t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths,
-                                                                       **ctx))
-            hyps = [[CTCHypothesis(tok[b, : int(cnt[b])].tolist(), [], float(score[b]))] for b in range(tok.size(0))]
-            for b, row in enumerate(hyps if bias else []):
-                row[0].bias = float(bias[0][b])
+        out = [t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths, nbest=nbest,
+                                                **ctx)]
+        if nbest is None:  # the best prefix alone: an N-best list of one
+            out = [t.unsqueeze(1) for t in out[:3]] + [torch.ones(out[0].size(0), dtype=torch.int32)] + [t.unsqueeze(1) for t in out[3:]]
+        tok, cnt, score, n_hyp, *bias = out
+        hyps = [[CTCHypothesis(tok[b, r, : int(cnt[b, r])].tolist(), [], float(score[b, r])) for r in range(int(n_hyp[b]))]
+                for b in range(tok.size(0))]
+        for b, row in enumerate(hyps if bias else []):
+            for r, h in enumerate(row):
+                h.bias = float(bias[0][b, r])
         if lexicon is not None and detokenize is not None:
             flat = [h for row in hyps for h in row]
             for h, text in zip(flat, _snapped_texts([h.tokens for h in flat], lexicon, detokenize)):

@@ -82,45 +82,198 @@ class EecDecoderParams(C.Structure):
 # host callback of eec_train_backward_ex: (exit group just finished, or -1 after the stem; user pointer)
 GROUP_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)
 
-EXPORTS = ["eec_last_error", "eec_abi_version", "eec_out_frames", "eec_encoder_create", "eec_encoder_destroy",
-           "eec_encoder_pack", "eec_encoder_workspace_bytes", "eec_encoder_forward", "eec_greedy_ctc",
-           "eec_encoder_set_profiling", "eec_encoder_profile_read", "eec_ctc_loss", "eec_encoder_pack_legacy",
-           "eec_encoder_forward_prefix", "eec_encoder_group_workspace_bytes", "eec_encoder_group_forward",
-           "eec_encoder_head_forward", "eec_encoder_stem1_forward", "eec_encoder_lengths",
-           "eec_ctc_backward_workspace_bytes", "eec_ctc_loss_forward", "eec_ctc_loss_backward", "eec_logsoftmax_backward",
-           "eec_exit_distill_workspace_bytes", "eec_exit_distill_forward", "eec_exit_distill_backward",
-           "eec_ctc_mwer_workspace_bytes", "eec_ctc_hyp_logp", "eec_ctc_mwer_forward", "eec_ctc_mwer_backward",
-           "eec_exit_stats_workspace_bytes", "eec_exit_stats", "eec_exit_route",
-           "eec_ctc_beam_workspace_bytes", "eec_ctc_beam_decode", "eec_ctc_beam_decode_ex",
-           "eec_ctc_loss_len", "eec_ctc_loss_forward_len", "eec_ctc_loss_backward_len", "eec_greedy_ctc_len", "eec_ctc_beam_decode_len",
-           "eec_ctc_beam_decode_nbest",
-           "eec_ctc_align_workspace_bytes", "eec_ctc_align",
-           "eec_ctc_trie_pack_bytes", "eec_ctc_trie_pack", "eec_ctc_lexbeam_workspace_bytes", "eec_ctc_lexbeam_decode",
-           "eec_ngram_pack_bytes", "eec_ngram_pack", "eec_ctc_lexbeam_lm_decode",
-           "eec_ctc_trie_smear_bytes", "eec_ctc_trie_smear", "eec_ctc_lexbeam_lm_smear_decode",
-           "eec_ctc_lexbeam_logadd_decode", "eec_ctc_log_add_host", "eec_ctc_log_add",
-           "eec_ctc_lexbeam_wide_workspace_bytes", "eec_ctc_lexbeam_wide_decode",
-           "eec_lexicon_pack_bytes", "eec_lexicon_pack", "eec_lexicon_nearest_workspace_bytes", "eec_lexicon_nearest",
-           "eec_edit_distance_workspace_bytes", "eec_edit_distance",
-           "eec_specaug_draw", "eec_specaug_apply",
-           "eec_resample_plan_bytes", "eec_resample_plan", "eec_speed_draw", "eec_resample_lengths", "eec_resample",
-           "eec_rir_bank_bytes", "eec_rir_bank", "eec_noise_bank_bytes", "eec_noise_bank", "eec_waveaug_partials_bytes", "eec_waveaug_draw",
-           "eec_reverb", "eec_noise_energy", "eec_noise_mix",
-           "eec_rir_spectra_bytes", "eec_rir_spectra", "eec_reverb_fft_workspace_bytes", "eec_reverb_fft", "eec_reverb_fft_stage",
-           "eec_frontend_last_error", "eec_frontend_create", "eec_frontend_destroy", "eec_frontend_frames", "eec_frontend_forward",
-           "eec_trainer_last_error", "eec_trainer_create", "eec_trainer_destroy", "eec_trainer_workspace_bytes",
-           "eec_train_forward", "eec_train_backward", "eec_train_backward_ex", "eec_train_gemm",
-           "eec_train_group_workspace_bytes", "eec_train_group_forward", "eec_train_group_backward", "eec_train_stem_workspace_bytes",
-           "eec_train_stem_forward", "eec_train_stem_backward", "eec_train_head_forward", "eec_train_head_backward_scratch_floats",
-           "eec_train_head_backward",
-           "eec_decoder_last_error", "eec_decoder_workspace_bytes", "eec_decoder_forward",
-           "eec_decoder_score_workspace_bytes", "eec_decoder_score", "eec_hypothesis_score",
-           "eec_decoder_train_last_error", "eec_decoder_train_workspace_bytes", "eec_decoder_train_forward", "eec_decoder_train_backward",
-           "eec_decoder_step_last_error", "eec_decoder_step_max_beams", "eec_decoder_cache_bytes", "eec_decoder_begin", "eec_decoder_step", "eec_decoder_step_multi", "eec_upload_i64_max", "eec_upload_i64", "eec_beam_select",
-           "eec_decoder_batch_cache_bytes", "eec_decoder_batch_begin", "eec_decoder_batch_step",
-           "eec_ctc_prefix_state_bytes", "eec_ctc_prefix_begin", "eec_ctc_prefix_step",
-           "eec_context_graph_bytes", "eec_context_graph", "eec_ctc_beam_decode_ctx", "eec_ctc_beam_decode_nbest_ctx",
-           "eec_context_bias_state_bytes", "eec_context_bias_step"]
+_as_address = C.c_void_p.from_param  # None -> NULL; an int, a c_void_p, a ctypes array / pointer / byref: taken as they are
+
+
+class TensorPtr:
+    """A pointer parameter of include/eec.h as an ``argtypes`` entry: ctypes hands every argument to ``from_param``.  A tensor
+    becomes its address after its element type (``dtypes``; None: any), its layout (contiguous) and where it lives (``host``: the
+    entry dereferences the pointer on the host; else on the device) were checked; anything else is an address already.  A refused
+    tensor surfaces as ``ctypes.ArgumentError`` naming the argument's position, before the entry is called."""
+    elem, dtypes, host = "void", None, False
+
+    @classmethod
+    def from_param(cls, v):
+        if not isinstance(v, torch.Tensor):
+            return _as_address(v)
+        if cls.dtypes is not None and v.dtype not in cls.dtypes:
+            raise TypeError(f"expected a {cls.elem} tensor, got {v.dtype}")
+        if not v.is_contiguous():
+            raise TypeError(f"expected a contiguous tensor, got strides {tuple(v.stride())} for shape {tuple(v.shape)}")
+        if v.is_cuda == cls.host:
+            raise TypeError(f"expected a {'host (CPU)' if cls.host else 'device'} tensor, got one on {v.device}")
+        return _as_address(v.data_ptr())
+
+
+def _ptr_types(elem: str, *dtypes):
+    """(device, host) pointer types of element type ``elem``."""
+    return tuple(type(("Host" if host else "Device") + "Ptr_" + elem, (TensorPtr,),
+                      {"elem": elem, "dtypes": dtypes or None, "host": host}) for host in (False, True))
+
+
+class STREAM:
+    """The hipStream_t parameter of an entry: ``call`` puts the device's current stream where the table has this marker."""
+    from_param = _as_address
+
+
+F32, hF32 = _ptr_types("float", torch.float32)
+F64, hF64 = _ptr_types("double", torch.float64)
+I32, hI32 = _ptr_types("int32_t", torch.int32)
+I64, hI64 = _ptr_types("int64_t", torch.int64)
+U8, hU8 = _ptr_types("uint8_t", torch.uint8)
+W32, hW32 = _ptr_types("uint32_t", torch.int32, torch.uint32)  # 32-bit words
+VOID, hVOID = _ptr_types("void")
+i, f, d, z, i64, u32, u64, H = C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_int64, C.c_uint32, C.c_uint64, C.c_void_p  # H: handle
+CFG, PRM, LAY, DEC = C.POINTER(EecConfig), C.POINTER(EecParams), C.POINTER(EecLayerParams), C.POINTER(EecDecoderParams)
+DECS = C.POINTER(DEC)  # HOST array of decoder parameter structs, one per session / exit
+
+# eec_ctc_lexbeam_decode; its _lm / _lm_smear / _logadd / _wide variants append to it (the stream stays where it is)
+_LEXBEAM = [F32, i, i, i, I32, VOID, i, i, i, i, f, f, f, i, I32, I32, I32, I32, I32, F32, I32, VOID, z, STREAM]
+
+# Every export of libeec.so, parameter for parameter as include/eec.h declares it (tests/test_host.py compares the two):
+# name -> argtypes, or (restype, argtypes) where the entry does not return int.  h*: the pointer is host memory.
+PROTOTYPES = {
+    "eec_last_error": (C.c_char_p, []),
+    "eec_abi_version": [],
+    "eec_out_frames": [i],
+    "eec_encoder_lengths": [I64, i, i, I32, STREAM],
+    "eec_upload_i64_max": [],
+    "eec_upload_i64": [hI64, i, I64, STREAM],
+    "eec_encoder_create": [CFG, C.POINTER(H)],
+    "eec_encoder_destroy": (None, [H]),
+    "eec_encoder_pack": [H, PRM, STREAM],
+    "eec_encoder_pack_legacy": [H, H, STREAM],
+    "eec_encoder_workspace_bytes": (z, [H, i, i]),
+    "eec_encoder_forward": [H, F32, I64, i, i, i, F32, F32, VOID, z, i, F32, STREAM],
+    "eec_encoder_forward_prefix": [H, F32, I64, i, i, i, i, F32, F32, F32, VOID, z, STREAM],
+    "eec_encoder_group_workspace_bytes": (z, [H, i, i]),
+    "eec_encoder_stem1_forward": [H, F32, i, i, F32, STREAM],
+    "eec_encoder_group_forward": [H, i, F32, I32, i, i, i, VOID, z, STREAM],
+    "eec_encoder_head_forward": [H, i, F32, i, F32, i, STREAM],
+    "eec_encoder_set_profiling": [H, i, i],
+    "eec_encoder_profile_read": [H, hF64, hI64, i],
+    "eec_greedy_ctc": [F32, i, i, i, i, I32, I32, STREAM],
+    "eec_ctc_loss": [F32, I64, I64, i, i, i, i, i, i, F32, F32, STREAM],
+    "eec_ctc_backward_workspace_bytes": (z, [i, i, i, i]),
+    "eec_ctc_loss_forward": [F32, I64, I64, i, i, i, i, i, i, F32, F32, VOID, STREAM],
+    "eec_ctc_loss_backward": [F32, I64, I64, i, i, i, i, i, i, F32, VOID, F32, F32, STREAM],
+    "eec_logsoftmax_backward": [F32, F32, i, i, F32, STREAM],
+    "eec_ctc_loss_len": [F32, I64, I64, I32, i, i, i, i, i, i, F32, F32, STREAM],
+    "eec_ctc_loss_forward_len": [F32, I64, I64, I32, i, i, i, i, i, i, F32, F32, VOID, STREAM],
+    "eec_ctc_loss_backward_len": [F32, I64, I64, I32, i, i, i, i, i, i, F32, VOID, F32, F32, STREAM],
+    "eec_exit_distill_workspace_bytes": (z, [i, i, i]),
+    "eec_exit_distill_forward": [F32, I32, hI32, i, i, i, i, f, F32, F32, VOID, z, STREAM],
+    "eec_exit_distill_backward": [F32, I32, hI32, i, i, i, i, f, F32, i, F32, STREAM],
+    "eec_ctc_mwer_workspace_bytes": (z, [i, i, i, i, i]),
+    "eec_ctc_hyp_logp": [F32, I32, I32, I32, i, i, i, i, i, i, i, F32, STREAM],
+    "eec_ctc_mwer_forward": [F32, I32, I32, I32, F32, i, i, i, i, i, i, i, i, i, F32, F32, F32, VOID, z, STREAM],
+    "eec_ctc_mwer_backward": [F32, I32, I32, I32, i, i, i, i, i, i, i, i, i, VOID, z, F32, i, F32, STREAM],
+    "eec_exit_stats_workspace_bytes": (z, [i, i, i]),
+    "eec_exit_stats": [F32, I32, i, i, i, i, F32, VOID, z, STREAM],
+    "eec_exit_route": [F32, i, f, i, i, I32, I32, I32, STREAM],
+    "eec_ctc_beam_workspace_bytes": (z, [i, i]),
+    "eec_ctc_beam_decode": [F32, i, i, i, i, i, f, VOID, I32, I32, F32, STREAM],
+    "eec_ctc_beam_decode_ex": [F32, i, i, i, i, i, f, i, VOID, I32, I32, F32, STREAM],
+    "eec_greedy_ctc_len": [F32, I32, i, i, i, i, I32, I32, STREAM],
+    "eec_ctc_beam_decode_len": [F32, I32, i, i, i, i, i, f, i, VOID, I32, I32, F32, STREAM],
+    "eec_ctc_beam_decode_nbest": [F32, I32, i, i, i, i, i, f, i, i, VOID, I32, I32, F32, I32, STREAM],
+    "eec_ctc_trie_pack_bytes": (z, [i, i64]),
+    "eec_ctc_trie_pack": [hI32, hI64, i, i, i, i, hVOID, z, hI32, hI32],
+    "eec_ctc_lexbeam_workspace_bytes": (z, [i, i, i]),
+    "eec_ctc_lexbeam_decode": _LEXBEAM,
+    "eec_ngram_pack_bytes": (z, [i, hI64, i]),
+    "eec_ngram_pack": [i, hI64, H, H, H, hI32, i, i, i, hVOID, z, hI32],  # words, logp, backoff: HOST arrays of host pointers
+    "eec_ctc_lexbeam_lm_decode": _LEXBEAM + [VOID, f],
+    "eec_ctc_trie_smear_bytes": (z, [i]),
+    "eec_ctc_trie_smear": [hVOID, hVOID, hVOID, z],
+    "eec_ctc_lexbeam_lm_smear_decode": _LEXBEAM + [VOID, f, VOID],
+    "eec_ctc_lexbeam_logadd_decode": _LEXBEAM + [VOID, f, VOID],
+    "eec_ctc_log_add_host": (f, [f, f]),
+    "eec_ctc_log_add": [F32, F32, F32, i, STREAM],
+    "eec_ctc_lexbeam_wide_workspace_bytes": (z, [i, i, i]),
+    "eec_ctc_lexbeam_wide_decode": _LEXBEAM + [VOID, f, VOID, i],
+    "eec_ctc_align_workspace_bytes": (z, [i, i, i]),
+    "eec_ctc_align": [F32, i, i, i, I32, I64, I32, I32, i, i, i, I32, F32, F32, F32, I32, F32, VOID, STREAM],
+    "eec_lexicon_pack_bytes": (z, [i, i64, i]),
+    "eec_lexicon_pack": [hW32, hI64, i, hVOID, z, hI32, hI32],
+    "eec_lexicon_nearest_workspace_bytes": (z, [i, i]),
+    "eec_lexicon_nearest": [VOID, i, U8, I32, i, i, I32, I32, VOID, z, STREAM],
+    "eec_edit_distance_workspace_bytes": (z, [i, i, i, i]),
+    "eec_edit_distance": [I32, I32, i, i, I32, I32, i, i, I32, I32, U8, I32, VOID, z, STREAM],
+    "eec_specaug_draw": [I32, i, i, i, u64, u64, i, i, i, i, f, i, I32, STREAM],
+    "eec_specaug_apply": [F32, I32, I32, i, i, i, i, i, i, f, F32, STREAM],
+    "eec_resample_plan_bytes": (z, [i, hI32, hI32, i, d]),
+    "eec_resample_plan": [i, hI32, hI32, i, d, hVOID, z],
+    "eec_speed_draw": [I64, i, i, u64, u64, VOID, I32, I64, STREAM],
+    "eec_resample_lengths": [I64, I32, i, i, VOID, I64, STREAM],
+    "eec_resample": [F32, I64, I32, i, i, VOID, F32, i, I64, STREAM],
+    "eec_rir_bank_bytes": (z, [i, hF32, hI32, i, i]),
+    "eec_rir_bank": [i, hF32, hI32, i, i, hVOID, z],
+    "eec_noise_bank_bytes": (z, [i, hF32, hI32]),
+    "eec_noise_bank": [i, hF32, hI32, hVOID, z],
+    "eec_waveaug_partials_bytes": (z, [i, i]),
+    "eec_waveaug_draw": [i, u64, u64, VOID, u64, VOID, u64, i, i, d, d, I32, STREAM],
+    "eec_reverb": [F32, I64, I32, i, i, VOID, F32, F64, STREAM],
+    "eec_noise_energy": [F32, I64, I32, i, i, VOID, F64, STREAM],
+    "eec_noise_mix": [F32, I64, I32, i, i, VOID, hF64, i, F64, F32, F32, STREAM],  # snr_gain travels in the argument block
+    "eec_rir_spectra_bytes": (z, [hVOID]),
+    "eec_rir_spectra": [hVOID, hVOID, z],
+    "eec_reverb_fft_workspace_bytes": (z, [i, i]),
+    "eec_reverb_fft": [F32, I64, I32, i, i, VOID, VOID, F32, F64, VOID, z, STREAM],
+    "eec_reverb_fft_stage": [F32, I64, I32, i, i, VOID, VOID, F32, F64, VOID, z, i, STREAM],
+    "eec_frontend_last_error": (C.c_char_p, []),
+    "eec_frontend_create": [i, i, i, i, i, C.POINTER(H)],
+    "eec_frontend_destroy": (None, [H]),
+    "eec_frontend_frames": [i, i],
+    "eec_frontend_forward": [H, F32, I64, i, i, F32, STREAM],
+    "eec_trainer_last_error": (C.c_char_p, []),
+    "eec_trainer_create": [CFG, C.POINTER(H)],
+    "eec_trainer_destroy": (None, [H]),
+    "eec_trainer_workspace_bytes": (z, [H, i, i]),
+    "eec_train_forward": [H, PRM, F32, I64, i, i, i, f, u64, F32, F32, F32, VOID, z, STREAM],
+    "eec_train_backward": [H, PRM, PRM, F32, F32, F32, VOID, z, STREAM],
+    "eec_train_backward_ex": [H, PRM, PRM, F32, F32, F32, VOID, z, STREAM, GROUP_DONE_FN, H],
+    "eec_train_group_workspace_bytes": (z, [CFG, i, i, i]),
+    "eec_train_group_forward": [CFG, LAY, i, F32, I32, i, i, i, f, u64, u32, F32, F32, VOID, z, STREAM],
+    "eec_train_group_backward": [CFG, LAY, LAY, i, F32, I32, i, i, i, f, u64, u32, F32, F32, VOID, z, STREAM],
+    "eec_train_stem_workspace_bytes": (z, [CFG, i, i, i]),
+    "eec_train_stem_forward": [CFG, F32, F32, F32, F32, F32, F32, i, i, i, f, u64, u32, F32, VOID, z, STREAM],
+    "eec_train_stem_backward": [CFG, i, i, i, i, f, u64, u32, F32, F32, F32, F32, F32, VOID, z, STREAM],
+    "eec_train_head_forward": [F32, F32, F32, i, i, i, i, F32, F32, STREAM],
+    "eec_train_head_backward_scratch_floats": (z, [i, i, i]),
+    "eec_train_head_backward": [F32, F32, F32, F32, i, i, i, i, F32, F32, F32, F32, STREAM],
+    "eec_train_gemm": [F32, F32, F32, F32, i, i, i, i, i, i, STREAM],
+    "eec_decoder_last_error": (C.c_char_p, []),
+    "eec_decoder_workspace_bytes": (z, [i] * 7),
+    "eec_decoder_forward": [DEC, i, i, i, i, i, I64, F32, i, i, i, i, i, i, F32, VOID, z, STREAM],
+    "eec_decoder_score_workspace_bytes": (z, [i] * 8),
+    "eec_decoder_score": [DEC, i, i, i, i, i, i, i, I32, I32, F32, i, i, i, i, i, F32, VOID, z, STREAM],
+    "eec_hypothesis_score": [F32, I32, I32, i, i, i, i, F32, STREAM],
+    "eec_decoder_train_last_error": (C.c_char_p, []),
+    "eec_decoder_train_workspace_bytes": (z, [i] * 8),
+    "eec_decoder_train_forward": [DEC, i, i, i, i, i, I64, F32, i, i, i, i, f, u64, i, F32, VOID, z, STREAM],
+    "eec_decoder_train_backward": [DEC, DEC, i, i, i, i, I64, F32, i, i, i, i, f, u64, i, F32, F32, VOID, z, STREAM],
+    "eec_decoder_step_last_error": (C.c_char_p, []),
+    "eec_decoder_step_max_beams": [],
+    "eec_decoder_cache_bytes": (z, [i] * 7),
+    "eec_decoder_begin": [DEC, i, i, i, i, F32, i, i, i, VOID, z, STREAM],
+    "eec_decoder_step": [DEC, i, i, i, i, i, I64, I64, i, i, i, i, i, i, F32, VOID, z, STREAM],
+    "eec_decoder_step_multi": [i, DECS, i, i, i, i, i, I64, I64, i, i, i, i, i, i, F32, C.POINTER(H), z, STREAM],
+    "eec_decoder_batch_cache_bytes": (z, [i] * 9),
+    "eec_decoder_batch_begin": [DECS, i, i, i, i, i, i, F32, i, i, i, VOID, z, STREAM],
+    "eec_decoder_batch_step": [DECS, i, i, i, i, i, i, i, I64, I64, i, i, i, i, i, F32, VOID, z, STREAM],
+    "eec_beam_select": [i, i, i, i, F32, F32, f, F32, I64, I64, I64, I64, i, i, i, STREAM],
+    "eec_ctc_prefix_state_bytes": (z, [i, i, i]),
+    "eec_ctc_prefix_begin": [F32, I32, i, i, i, i, i, VOID, z, STREAM],
+    "eec_ctc_prefix_step": [F32, I32, i, i, i, i, i, I64, I64, i, i, i, F32, f, i, i, i, F32, VOID, z, STREAM],
+    "eec_context_graph_bytes": (z, [i, hI32, hI32, hI32, hF64, i, i, i, i]),
+    "eec_context_graph": [i, hI32, hI32, hI32, hF64, i, i, i, i, hVOID, z],
+    "eec_ctc_beam_decode_ctx": [F32, I32, i, i, i, i, i, f, i, VOID, I32, I32, F32, VOID, z, I32, F32, STREAM],
+    "eec_ctc_beam_decode_nbest_ctx": [F32, I32, i, i, i, i, i, f, i, i, VOID, I32, I32, F32, I32, VOID, z, I32, F32, STREAM],
+    "eec_context_bias_state_bytes": (z, [i, i]),
+    "eec_context_bias_step": [VOID, z, I32, i, i, i, i, i, i, I64, I64, F32, F32, VOID, z, STREAM],
+}
+EXPORTS = list(PROTOTYPES)
 KERNEL_CLASSES = ["stem", "ffn", "qkv", "attn", "proj_glu", "proj", "dw_pw2", "head", "chain"]
 
 _lib: Optional[C.CDLL] = None
@@ -139,246 +292,9 @@ def load() -> C.CDLL:
     # (libamdhip64.so.7), so the loader reuses it.  Loaded the other way round, /opt/rocm's copy comes in as well and one
     # process holds two HIP runtimes (the second to initialise then reports "no ROCm-capable device").
     lib = C.CDLL(LIB_PATH)
-    lib.eec_last_error.restype = C.c_char_p
-    lib.eec_abi_version.restype = C.c_int
-    lib.eec_out_frames.argtypes = [C.c_int]
-    lib.eec_encoder_create.argtypes = [C.POINTER(EecConfig), C.POINTER(C.c_void_p)]
-    lib.eec_encoder_destroy.argtypes = [C.c_void_p]
-    lib.eec_encoder_destroy.restype = None
-    lib.eec_encoder_pack.argtypes = [C.c_void_p, C.POINTER(EecParams), C.c_void_p]
-    lib.eec_encoder_pack_legacy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_encoder_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.eec_encoder_workspace_bytes.restype = C.c_size_t
-    lib.eec_encoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_encoder_forward_prefix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_encoder_group_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.eec_encoder_group_workspace_bytes.restype = C.c_size_t
-    lib.eec_encoder_group_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_encoder_head_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    lib.eec_encoder_stem1_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_encoder_lengths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_greedy_ctc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]
-    lib.eec_ctc_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                 C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_backward_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.eec_ctc_backward_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    # the _len entries: the lengths pointer follows the arguments it qualifies (NULL = T' everywhere = the entry without lengths)
-    lib.eec_ctc_loss_len.argtypes = lib.eec_ctc_loss.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss.argtypes[3:]
-    lib.eec_ctc_loss_forward_len.argtypes = lib.eec_ctc_loss_forward.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss_forward.argtypes[3:]
-    lib.eec_ctc_loss_backward_len.argtypes = lib.eec_ctc_loss_backward.argtypes[:3] + [C.c_void_p] + lib.eec_ctc_loss_backward.argtypes[3:]
-    lib.eec_greedy_ctc_len.argtypes = lib.eec_greedy_ctc.argtypes[:1] + [C.c_void_p] + lib.eec_greedy_ctc.argtypes[1:]
-    lib.eec_logsoftmax_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_exit_distill_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_exit_distill_workspace_bytes.restype = C.c_size_t
-    lib.eec_exit_distill_forward.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_exit_distill_backward.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_mwer_workspace_bytes.argtypes = [C.c_int] * 5
-    lib.eec_ctc_mwer_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_hyp_logp.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
-    # logp, input_len, hyp, hyp_len, risk; E, B, b0, nb, T', V, N, L, blank; ll, loss_eb, loss, workspace, its bytes, stream
-    lib.eec_ctc_mwer_forward.argtypes = [C.c_void_p] * 5 + [C.c_int] * 9 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
-    # logp, input_len, hyp, hyp_len; E, B, b0, nb, T', V, N, L, blank; workspace, its bytes, grad_loss, accumulate, dlogp, stream
-    lib.eec_ctc_mwer_backward.argtypes = [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_exit_stats_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_exit_stats_workspace_bytes.restype = C.c_size_t
-    lib.eec_exit_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_exit_route.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_beam_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.eec_ctc_beam_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_beam_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_beam_decode_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_beam_decode_len.argtypes = lib.eec_ctc_beam_decode_ex.argtypes[:1] + [C.c_void_p] + lib.eec_ctc_beam_decode_ex.argtypes[1:]
-    # N-best: nbest follows skip_drops_frame, n_hyp follows scores
-    lib.eec_ctc_beam_decode_nbest.argtypes = lib.eec_ctc_beam_decode_len.argtypes[:9] + [C.c_int] + lib.eec_ctc_beam_decode_len.argtypes[9:13] + \
-        [C.c_void_p, C.c_void_p]
-    lib.eec_ctc_align_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_ctc_align_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_align.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_trie_pack_bytes.argtypes = [C.c_int, C.c_int64]
-    lib.eec_ctc_trie_pack_bytes.restype = C.c_size_t
-    lib.eec_ctc_trie_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_lexbeam_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_ctc_lexbeam_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_lexbeam_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_float, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]
-    lib.eec_ctc_lexbeam_lm_decode.argtypes = lib.eec_ctc_lexbeam_decode.argtypes + [C.c_void_p, C.c_float]
-    lib.eec_ctc_lexbeam_lm_smear_decode.argtypes = lib.eec_ctc_lexbeam_lm_decode.argtypes + [C.c_void_p]
-    lib.eec_ctc_lexbeam_logadd_decode.argtypes = lib.eec_ctc_lexbeam_lm_smear_decode.argtypes
-    lib.eec_ctc_lexbeam_wide_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_ctc_lexbeam_wide_workspace_bytes.restype = C.c_size_t
-    lib.eec_ctc_lexbeam_wide_decode.argtypes = lib.eec_ctc_lexbeam_lm_smear_decode.argtypes + [C.c_int]
-    lib.eec_ctc_log_add_host.argtypes = [C.c_float, C.c_float]
-    lib.eec_ctc_log_add_host.restype = C.c_float
-    lib.eec_ctc_log_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.eec_ctc_trie_smear_bytes.argtypes = [C.c_int]
-    lib.eec_ctc_trie_smear_bytes.restype = C.c_size_t
-    lib.eec_ctc_trie_smear.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.eec_ngram_pack_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
-    lib.eec_ngram_pack_bytes.restype = C.c_size_t
-    lib.eec_ngram_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                   C.c_size_t, C.c_void_p]
-    lib.eec_lexicon_pack_bytes.argtypes = [C.c_int, C.c_int64, C.c_int]
-    lib.eec_lexicon_pack_bytes.restype = C.c_size_t
-    lib.eec_lexicon_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.eec_lexicon_nearest_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.eec_lexicon_nearest_workspace_bytes.restype = C.c_size_t
-    lib.eec_lexicon_nearest.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_void_p]
-    lib.eec_edit_distance_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.eec_edit_distance_workspace_bytes.restype = C.c_size_t
-    lib.eec_edit_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    # frame_len; B, n_mels, T; seed, utt_offset; W, n_freq_masks, F, n_time_masks, ratio, Tmax; params, stream
-    lib.eec_specaug_draw.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                     C.c_int, C.c_void_p, C.c_void_p]
-    # mel, frame_len, params; B, n_mels, T, n_freq_masks, n_time_masks, mode; mask_value; out, stream
-    lib.eec_specaug_apply.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
-    # R, orig, new, lowpass_filter_width, rolloff (; image, its bytes)
-    lib.eec_resample_plan_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double]
-    lib.eec_resample_plan_bytes.restype = C.c_size_t
-    lib.eec_resample_plan.argtypes = lib.eec_resample_plan_bytes.argtypes + [C.c_void_p, C.c_size_t]
-    # lengths; B, L; seed, utt_offset; plan, choice, out_len, stream
-    lib.eec_speed_draw.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    # lengths, choice; B, L; plan, out_len, stream
-    lib.eec_resample_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    # wave, lengths, choice; B, L; plan, out; L_out; out_len, stream
-    lib.eec_resample.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    # R, taps, n_taps, normalize, shift (; image, its bytes);  M, samples, n_samples (; image, its bytes)
-    lib.eec_rir_bank_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    lib.eec_rir_bank_bytes.restype = C.c_size_t
-    lib.eec_rir_bank.argtypes = lib.eec_rir_bank_bytes.argtypes + [C.c_void_p, C.c_size_t]
-    lib.eec_noise_bank_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_noise_bank_bytes.restype = C.c_size_t
-    lib.eec_noise_bank.argtypes = lib.eec_noise_bank_bytes.argtypes + [C.c_void_p, C.c_size_t]
-    lib.eec_waveaug_partials_bytes.argtypes = [C.c_int, C.c_int]
-    lib.eec_waveaug_partials_bytes.restype = C.c_size_t
-    # B; seed, utt_offset; rir_bank, thr_reverb; noise_bank, thr_noise; n_snrs, volume, lo, hi; params, stream
-    lib.eec_waveaug_draw.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_double,
-                                     C.c_double, C.c_void_p, C.c_void_p]
-    # wave, lengths, params; B, L; rir_bank, out, partials, stream
-    lib.eec_reverb.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4
-    lib.eec_rir_spectra_bytes.argtypes = [C.c_void_p]
-    lib.eec_rir_spectra_bytes.restype = C.c_size_t
-    lib.eec_rir_spectra.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.eec_reverb_fft_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.eec_reverb_fft_workspace_bytes.restype = C.c_size_t
-    # wave, lengths, params; B, L; rir_bank, rir_spectra, out, partials, workspace; workspace_bytes; stream
-    lib.eec_reverb_fft.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
-    lib.eec_reverb_fft_stage.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_int, C.c_void_p]
-    # signal, lengths, params; B, L; noise_bank, partials, stream
-    lib.eec_noise_energy.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
-    # y, lengths, params; B, L; noise_bank, snr_gain; n_snrs; partials, out, applied, stream
-    lib.eec_noise_mix.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    lib.eec_frontend_last_error.restype = C.c_char_p
-    lib.eec_frontend_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    lib.eec_frontend_destroy.argtypes = [C.c_void_p]
-    lib.eec_frontend_destroy.restype = None
-    lib.eec_frontend_frames.argtypes = [C.c_int, C.c_int]
-    lib.eec_frontend_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_trainer_last_error.restype = C.c_char_p
-    lib.eec_trainer_create.argtypes = [C.POINTER(EecConfig), C.POINTER(C.c_void_p)]
-    lib.eec_trainer_destroy.argtypes = [C.c_void_p]
-    lib.eec_trainer_destroy.restype = None
-    lib.eec_trainer_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.eec_trainer_workspace_bytes.restype = C.c_size_t
-    lib.eec_train_forward.argtypes = [C.c_void_p, C.POINTER(EecParams), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                      C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_backward.argtypes = [C.c_void_p, C.POINTER(EecParams), C.POINTER(EecParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_backward_ex.argtypes = [C.c_void_p, C.POINTER(EecParams), C.POINTER(EecParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_size_t, C.c_void_p, GROUP_DONE_FN, C.c_void_p]
-    lib.eec_train_group_workspace_bytes.argtypes = [C.POINTER(EecConfig), C.c_int, C.c_int, C.c_int]
-    lib.eec_train_group_workspace_bytes.restype = C.c_size_t
-    lib.eec_train_group_forward.argtypes = [C.POINTER(EecConfig), C.POINTER(EecLayerParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_group_backward.argtypes = [C.POINTER(EecConfig), C.POINTER(EecLayerParams), C.POINTER(EecLayerParams), C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_stem_workspace_bytes.argtypes = [C.POINTER(EecConfig), C.c_int, C.c_int, C.c_int]
-    lib.eec_train_stem_workspace_bytes.restype = C.c_size_t
-    lib.eec_train_stem_forward.argtypes = [C.POINTER(EecConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_stem_backward.argtypes = [C.POINTER(EecConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_train_head_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_train_head_backward_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_train_head_backward_scratch_floats.restype = C.c_size_t
-    lib.eec_train_head_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.eec_train_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_void_p]
-    lib.eec_decoder_last_error.restype = C.c_char_p
-    lib.eec_decoder_workspace_bytes.argtypes = [C.c_int] * 7
-    lib.eec_decoder_workspace_bytes.restype = C.c_size_t
-    lib.eec_decoder_forward.argtypes = [C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_decoder_score_workspace_bytes.argtypes = [C.c_int] * 8
-    lib.eec_decoder_score_workspace_bytes.restype = C.c_size_t
-    lib.eec_decoder_score.argtypes = [C.POINTER(EecDecoderParams)] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + \
-        [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_hypothesis_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_decoder_train_last_error.restype = C.c_char_p
-    lib.eec_decoder_train_workspace_bytes.argtypes = [C.c_int] * 8
-    lib.eec_decoder_train_workspace_bytes.restype = C.c_size_t
-    lib.eec_decoder_train_forward.argtypes = [C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_size_t, C.c_void_p]
-    lib.eec_decoder_train_backward.argtypes = [C.POINTER(EecDecoderParams), C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_decoder_step_last_error.restype = C.c_char_p
-    lib.eec_decoder_cache_bytes.argtypes = [C.c_int] * 7
-    lib.eec_decoder_cache_bytes.restype = C.c_size_t
-    lib.eec_decoder_begin.argtypes = [C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_decoder_step.argtypes = [C.POINTER(EecDecoderParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_decoder_step_multi.argtypes = [C.c_int, C.POINTER(C.POINTER(EecDecoderParams)), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p]
-    lib.eec_decoder_batch_cache_bytes.argtypes = [C.c_int] * 9
-    lib.eec_decoder_batch_cache_bytes.restype = C.c_size_t
-    lib.eec_decoder_batch_begin.argtypes = [C.POINTER(C.POINTER(EecDecoderParams)), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_decoder_batch_step.argtypes = [C.POINTER(C.POINTER(EecDecoderParams)), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]
-    lib.eec_beam_select.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.eec_upload_i64.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_prefix_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.eec_ctc_prefix_state_bytes.restype = C.c_size_t
-    lib.eec_ctc_prefix_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.eec_ctc_prefix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]
-    # G, n_phrases, phrase_len, tokens, boost; V, blank, eos, pad (; image, its bytes)
-    lib.eec_context_graph_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4
-    lib.eec_context_graph_bytes.restype = C.c_size_t
-    lib.eec_context_graph.argtypes = lib.eec_context_graph_bytes.argtypes + [C.c_void_p, C.c_size_t]
-    # the _len / _nbest entries, then image, its bytes, graph_of, bias in front of the stream
-    ctx = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.eec_ctc_beam_decode_ctx.argtypes = lib.eec_ctc_beam_decode_len.argtypes[:-1] + ctx + [C.c_void_p]
-    lib.eec_ctc_beam_decode_nbest_ctx.argtypes = lib.eec_ctc_beam_decode_nbest.argtypes[:-1] + ctx + [C.c_void_p]
-    lib.eec_context_bias_state_bytes.argtypes = [C.c_int, C.c_int]
-    lib.eec_context_bias_state_bytes.restype = C.c_size_t
-    # image, its bytes, graph_of; n, R, R_prev, R_max, V, s; parent, last, local, out, state, its bytes, stream
-    lib.eec_context_bias_step.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
-    lib.eec_encoder_set_profiling.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.eec_encoder_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
+    for name, proto in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = proto if isinstance(proto, tuple) else (C.c_int, proto)
     _lib = lib
     return lib
 
@@ -389,9 +305,34 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed (code {rc}): {load().eec_last_error().decode(errors='replace')}")
 
 
+def call(name: str, *args) -> None:
+    """Entry ``name``, which has no stream parameter (a packer, create / destroy, a setter): raises unless it returns 0."""
+    check(getattr(load(), name)(*args), name)
+
+
 def stream_ptr(dev) -> C.c_void_p:
-    """The current HIP stream of ``dev``, as the C entries take it."""
+    """The current HIP stream of ``dev``, as the C entries take it (``launch`` supplies it itself)."""
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+_stream_slot = {}  # entry -> position of its STREAM parameter
+
+
+def launch(name: str, dev, *args) -> None:
+    """Entry ``name`` on ``dev``: the device is made current for the call, its current stream goes into the entry's stream slot
+    (``args`` are the other arguments in order: the slot is not always the last), and a non-zero return code raises under the
+    entry's own name.  A ``dev`` that is no HIP device gets a NULL stream: the pointer types keep every CPU tensor out of a device
+    slot, so such a call ends in the entry's own refusal of its arguments, which is what the host tests ask of it."""
+    fn = getattr(load(), name)
+    k = _stream_slot.get(name)
+    if k is None:
+        k = _stream_slot[name] = fn.argtypes.index(STREAM)
+    if torch.device(dev).type != "cuda":
+        rc = fn(*args[:k], None, *args[k:])
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*args[:k], torch.cuda.current_stream(dev).cuda_stream, *args[k:])
+    check(rc, name)
 
 
 def aligned_ws(nbytes: int, dev):
@@ -424,8 +365,7 @@ def to_device(t, dev: torch.device, dtype: torch.dtype = torch.int64):
     dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
     host = t.to(torch.int64).contiguous()
     out = torch.empty(host.shape, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.eec_upload_i64(host.data_ptr(), host.numel(), out.data_ptr(), stream_ptr(dev)), "eec_upload_i64")
+    launch("eec_upload_i64", dev, host, host.numel(), out)
     return out
 
 

@@ -5,7 +5,6 @@ search (``eec_context_bias_step``; CPU tensors take a host path of the same stat
 ``ctc_beam_decode(context=, graph_of=)``."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -13,7 +12,6 @@ import torch
 from torch import Tensor
 
 from . import capi
-from .capi import stream_ptr
 
 
 class ContextGraph:
@@ -62,7 +60,7 @@ class ContextGraph:
         if nbytes == 0:
             capi.check(10001, "eec_context_graph_bytes")  # EEC_ERR_BAD_ARG: the message says what was refused
         image = torch.empty(nbytes // 4, dtype=torch.int32)
-        capi.check(lib.eec_context_graph(*head, image.data_ptr(), nbytes), "eec_context_graph")
+        capi.call("eec_context_graph", *head, image, nbytes)
         self.image = image
         self._on = {}
         self._flat = None
@@ -195,18 +193,15 @@ class ContextBiasSession:
             local = capi.require_fp32("local", local, dev)
             if last.device != dev or (parent is not None and parent.device != dev):
                 raise RuntimeError(f"last and parent must be on {dev}")
-            with torch.cuda.device(dev):
-                tok = last.to(torch.int64).contiguous()
-                par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
-                out = torch.empty_like(local)
-                capi.check(capi.load().eec_context_bias_step(self._image.data_ptr(), self.graph.nbytes, None if self._g is None else self._g.data_ptr(),
-                                                             n, R, self.rows, self.R_max, V, self.s, None if par is None else par.data_ptr(),
-                                                             tok.data_ptr(), local.data_ptr(), out.data_ptr(), self._state.data_ptr(), self._nbytes,
-                                                             stream_ptr(dev)), "eec_context_bias_step")
-                stream = torch.cuda.current_stream(dev)
-                for t in (local, tok, par):
-                    if t is not None:
-                        t.record_stream(stream)
+            tok = last.to(torch.int64).contiguous()
+            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            out = torch.empty_like(local)
+            capi.launch("eec_context_bias_step", dev, self._image, self.graph.nbytes, self._g, n, R, self.rows, self.R_max, V, self.s, par, tok,
+                        local, out, self._state, self._nbytes)
+            stream = torch.cuda.current_stream(dev)
+            for t in (local, tok, par):
+                if t is not None:
+                    t.record_stream(stream)
         self.s += 1
         self.rows = R
         return out

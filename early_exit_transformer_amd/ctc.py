@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import capi
-from .capi import stream_ptr, to_device
+from .capi import launch, to_device
 
 
 def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
@@ -23,29 +23,25 @@ def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
         raise RuntimeError("encoder_lengths runs on a HIP device only")
     lengths = lengths.to(torch.int64).contiguous()
     out = torch.empty((lengths.numel(),), dtype=torch.int32, device=lengths.device)
-    with torch.cuda.device(lengths.device):
-        capi.check(capi.load().eec_encoder_lengths(lengths.data_ptr(), lengths.numel(), int(t_out), out.data_ptr(),
-                                                   stream_ptr(lengths.device)), "eec_encoder_lengths")
+    launch("eec_encoder_lengths", lengths.device, lengths, lengths.numel(), int(t_out), out)
     return out
 
 
-def _frame_counts(name: str, arg: str, lens: Optional[Tensor], n: int, dev: torch.device) -> Optional[Tensor]:
-    """A per-sequence frame count argument (int32 or int64, any device) as the kernels read it: int32 [n] on ``dev``, or None."""
+def _frame_counts(name: str, arg: str, lens: Optional[Tensor], n: int, dev: torch.device, any_dtype: bool = False) -> Optional[Tensor]:
+    """A per-sequence frame count argument (int32 or int64, any device) as the kernels read it: int32 [n] on ``dev``, or None.
+    The kernels clamp a count to [0, T']: one that int32 cannot hold is clamped before it is narrowed, so that it stays on its own
+    side of that range.  ``any_dtype``: the callers that have always converted whatever they were given keep doing so."""
     if lens is None:
         return None
     if not isinstance(lens, Tensor):
         lens = torch.as_tensor(lens)
-    if lens.dtype not in (torch.int32, torch.int64):
+    if lens.dtype not in (torch.int32, torch.int64) and not any_dtype:
         raise ValueError(f"{name}: {arg} must be an int32 or int64 tensor, got {lens.dtype}")
     if lens.numel() != n:
         raise ValueError(f"{name}: {arg} must have {n} entries, got {lens.numel()}")
-    if lens.dtype == torch.int64:
-        lens = lens.clamp(-2 ** 31, 2 ** 31 - 1)  # the kernels clamp to [0, T']: keep a count that int32 cannot hold on its side
+    if lens.dtype != torch.int32:
+        lens = lens.to(torch.int64).clamp(-2 ** 31, 2 ** 31 - 1)
     return lens.reshape(n).to(device=dev, dtype=torch.int32).contiguous()
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -58,9 +54,7 @@ def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) ->
     el = _frame_counts("greedy_ctc", "em_len", em_len, N, logp.device)
     tokens = torch.empty((N, Tq), dtype=torch.int32, device=logp.device)
     counts = torch.empty((N,), dtype=torch.int32, device=logp.device)
-    with torch.cuda.device(logp.device):
-        capi.check(capi.load().eec_greedy_ctc_len(logp.data_ptr(), _ptr(el), N, Tq, V, blank, tokens.data_ptr(),
-                                                  counts.data_ptr(), stream_ptr(logp.device)), "eec_greedy_ctc")
+    launch("eec_greedy_ctc_len", logp.device, logp, el, N, Tq, V, blank, tokens, counts)
     return tokens, counts
 
 
@@ -87,53 +81,25 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
     N, Tq, V = logp.shape
     dev = logp.device
     el = _frame_counts("ctc_beam_decode", "em_len", em_len, N, dev)
-    lib = capi.load()
-    ws = torch.empty((lib.eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
     if context is None and graph_of is not None:
         raise ValueError("ctc_beam_decode: graph_of chooses among the graphs of context=, which was not given")
+    k = () if nbest is None else (int(nbest),)
+    ws = torch.empty((capi.load().eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
+    tokens = (torch.empty if nbest is None and context is None else torch.zeros)((N, *k, Tq), dtype=torch.int32, device=dev)
+    outs = [tokens, torch.empty((N, *k), dtype=torch.int32, device=dev), torch.empty((N, *k), dtype=torch.float32, device=dev)]
+    if k:
+        outs.append(torch.empty((N,), dtype=torch.int32, device=dev))  # n_hyp
+    tail = ()
     if context is not None:
         from .context import graph_rows
         if context.vocab_size != V or context.blank != blank:
             raise ValueError(f"ctc_beam_decode: the context graph is over {context.vocab_size} tokens with blank {context.blank}, "
                              f"the emission over {V} with blank {blank}")
-        image, rows = context.to(dev), graph_rows("ctc_beam_decode", graph_of, N, dev)
-        tail = (image.data_ptr(), context.nbytes, _ptr(rows))
-        k = () if nbest is None else (int(nbest),)
-        tokens = torch.zeros((N, *k, Tq), dtype=torch.int32, device=dev)
-        counts = torch.empty((N, *k), dtype=torch.int32, device=dev)
-        scores = torch.empty((N, *k), dtype=torch.float32, device=dev)
-        bias = torch.empty((N, *k), dtype=torch.float32, device=dev)
-        head = (logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)))
-        with torch.cuda.device(dev):
-            if nbest is None:
-                capi.check(lib.eec_ctc_beam_decode_ctx(*head, ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), *tail,
-                                                       bias.data_ptr(), stream_ptr(dev)), "eec_ctc_beam_decode_ctx")
-                return tokens, counts, scores, bias
-            n_hyp = torch.empty((N,), dtype=torch.int32, device=dev)
-            capi.check(lib.eec_ctc_beam_decode_nbest_ctx(*head, k[0], ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(),
-                                                         n_hyp.data_ptr(), *tail, bias.data_ptr(), stream_ptr(dev)), "eec_ctc_beam_decode_nbest_ctx")
-        return tokens, counts, scores, n_hyp, bias
-    if nbest is not None:
-        nbest = int(nbest)
-        tokens = torch.zeros((N, nbest, Tq), dtype=torch.int32, device=dev)
-        counts = torch.empty((N, nbest), dtype=torch.int32, device=dev)
-        scores = torch.empty((N, nbest), dtype=torch.float32, device=dev)
-        n_hyp = torch.empty((N,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            capi.check(lib.eec_ctc_beam_decode_nbest(logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold,
-                                                     int(bool(skip_drops_frame)), nbest, ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(),
-                                                     scores.data_ptr(), n_hyp.data_ptr(), stream_ptr(dev)),
-                       "eec_ctc_beam_decode_nbest")
-        return tokens, counts, scores, n_hyp
-    tokens = torch.empty((N, Tq), dtype=torch.int32, device=dev)
-    counts = torch.empty((N,), dtype=torch.int32, device=dev)
-    scores = torch.empty((N,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_beam_decode_len(logp.data_ptr(), _ptr(el), N, Tq, V, blank, beam_size, blank_skip_threshold,
-                                               int(bool(skip_drops_frame)), ws.data_ptr(), tokens.data_ptr(), counts.data_ptr(),
-                                               scores.data_ptr(), stream_ptr(dev)),
-                   "eec_ctc_beam_decode")
-    return tokens, counts, scores
+        tail = (context.to(dev), context.nbytes, graph_rows("ctc_beam_decode", graph_of, N, dev),
+                torch.empty((N, *k), dtype=torch.float32, device=dev))  # image, its bytes, graph_of, bias
+    entry = "eec_ctc_beam_decode" + (("_nbest" if k else "") + ("_ctx" if tail else "") or "_len")
+    launch(entry, dev, logp, el, N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)), *k, ws, *outs, *tail)
+    return (*outs, *tail[3:])
 
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,
@@ -184,32 +150,24 @@ def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int =
     max_words = Tq if max_words is None else int(max_words)
     words, word_count, tokens, token_count, timesteps, n_hyp = i32(n, nbest, max(max_words, 0)), i32(n, nbest), i32(n, nbest, Tq), i32(n, nbest), i32(n, nbest, Tq), i32(n)
     scores = torch.empty((n, nbest), dtype=torch.float32, device=dev)
-    if em_len is not None:
-        em_len = em_len.to(device=dev, dtype=torch.int32).contiguous()
-        if em_len.numel() != n:
-            raise ValueError(f"ctc_lexicon_decode: em_len must have {n} entries, got {em_len.numel()}")
+    em_len = _frame_counts("ctc_lexicon_decode", "em_len", em_len, n, dev, any_dtype=True)
     ws_bytes = (lib.eec_ctc_lexbeam_wide_workspace_bytes if wide else lib.eec_ctc_lexbeam_workspace_bytes)(n, Tq, beam_size)
     ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        args = (logp.data_ptr(), n, Tq, V, _ptr(em_len), trie.on(dev).data_ptr(), trie.blank, trie.sil,
-                int(beam_size), int(nbest), float(word_score), float(sil_score), float(beam_threshold), max_words, words.data_ptr(),
-                word_count.data_ptr(), tokens.data_ptr(), token_count.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), n_hyp.data_ptr(),
-                ws.data_ptr(), ws_bytes, stream_ptr(dev))
-        if wide:
-            capi.check(lib.eec_ctc_lexbeam_wide_decode(*args, None if lm is None else lm.on(dev).data_ptr(), float(lm_weight),
-                                                       None if smearing is None else lm.smear(trie).on(dev).data_ptr(), int(bool(log_add))),
-                       "eec_ctc_lexbeam_wide_decode")
-        elif log_add:
-            capi.check(lib.eec_ctc_lexbeam_logadd_decode(*args, None if lm is None else lm.on(dev).data_ptr(), float(lm_weight),
-                                                         None if smearing is None else lm.smear(trie).on(dev).data_ptr()),
-                       "eec_ctc_lexbeam_logadd_decode")
-        elif lm is None:
-            capi.check(lib.eec_ctc_lexbeam_decode(*args), "eec_ctc_lexbeam_decode")
-        elif smearing is None:
-            capi.check(lib.eec_ctc_lexbeam_lm_decode(*args, lm.on(dev).data_ptr(), float(lm_weight)), "eec_ctc_lexbeam_lm_decode")
-        else:
-            capi.check(lib.eec_ctc_lexbeam_lm_smear_decode(*args, lm.on(dev).data_ptr(), float(lm_weight), lm.smear(trie).on(dev).data_ptr()),
-                       "eec_ctc_lexbeam_lm_smear_decode")
+    lm_image = None if lm is None else lm.on(dev)
+    smear = None if smearing is None else lm.smear(trie).on(dev)
+    if wide:
+        entry, more = "eec_ctc_lexbeam_wide_decode", (lm_image, float(lm_weight), smear, int(bool(log_add)))
+    elif log_add:
+        entry, more = "eec_ctc_lexbeam_logadd_decode", (lm_image, float(lm_weight), smear)
+    elif lm is None:
+        entry, more = "eec_ctc_lexbeam_decode", ()
+    elif smearing is None:
+        entry, more = "eec_ctc_lexbeam_lm_decode", (lm_image, float(lm_weight))
+    else:
+        entry, more = "eec_ctc_lexbeam_lm_smear_decode", (lm_image, float(lm_weight), smear)
+    launch(entry, dev, logp, n, Tq, V, em_len, trie.on(dev), trie.blank, trie.sil, int(beam_size), int(nbest), float(word_score),
+           float(sil_score), float(beam_threshold), max_words, words, word_count, tokens, token_count, timesteps, scores, n_hyp, ws,
+           ws_bytes, *more)  # the stream sits in front of ``more``
     return words, word_count, tokens, token_count, timesteps, scores, n_hyp
 
 
@@ -231,13 +189,7 @@ def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em
     tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
     H, S = tokens.shape
 
-    def i32(t, n, name):
-        if t is None:
-            return None
-        t = t.to(device=dev, dtype=torch.int32).contiguous()
-        if t.numel() != n:
-            raise ValueError(f"ctc_align: {name} must have {n} entries, got {t.numel()}")
-        return t
+    i32 = lambda t, n, name: _frame_counts("ctc_align", name, t, n, dev, any_dtype=True)  # noqa: E731
     tok_len = torch.full((H,), S, dtype=torch.int32, device=dev) if tok_len is None else i32(tok_len, H, "tok_len")
     em_index, em_len = i32(em_index, H, "em_index"), i32(em_len, n_em, "em_len")
     if em_index is None and H > n_em:
@@ -248,13 +200,9 @@ def ctc_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em
     final_score = torch.empty((H,), dtype=torch.float32, device=dev)
     status = torch.empty((H,), dtype=torch.int32, device=dev)
     trellis = torch.empty((H, Tq + 1, S + 1), dtype=torch.float32, device=dev) if want_trellis else None
-    lib = capi.load()
-    ws = torch.empty((lib.eec_ctc_align_workspace_bytes(H, Tq, S),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_align(logp.data_ptr(), n_em, Tq, V, _ptr(em_len), tokens.data_ptr(), tok_len.data_ptr(), _ptr(em_index), H, S,
-                                     int(blank), point_token.data_ptr(), point_score.data_ptr(), path_score.data_ptr(),
-                                     final_score.data_ptr(), status.data_ptr(), _ptr(trellis), ws.data_ptr() if ws.numel() else None,
-                                     stream_ptr(dev)), "eec_ctc_align")
+    ws = torch.empty((capi.load().eec_ctc_align_workspace_bytes(H, Tq, S),), dtype=torch.uint8, device=dev)
+    launch("eec_ctc_align", dev, logp, n_em, Tq, V, em_len, tokens, tok_len, em_index, H, S, int(blank), point_token, point_score,
+           path_score, final_score, status, trellis, ws if ws.numel() else None)
     return point_token, point_score, path_score, final_score, status, trellis
 
 
@@ -313,22 +261,16 @@ class CtcPrefixSession:
         self.dev = emission.device
         self.emission = emission.contiguous()
         self.s, self.rows = 0, 0
-        if em_len is not None:
-            em_len = em_len.to(device=self.dev, dtype=torch.int32).contiguous()
-            if em_len.numel() != n:
-                raise ValueError(f"em_len must have {n} entries, got {em_len.numel()}")
-        self.em_len = em_len
+        self.em_len = _frame_counts("ctc_prefix_session", "em_len", em_len, n, self.dev, any_dtype=True)
         if not self.emission.is_cuda:
             self._host_begin()
             return
-        lib = capi.load()
-        self.nbytes = lib.eec_ctc_prefix_state_bytes(n, self.R_max, Tq)
-        with torch.cuda.device(self.dev):
-            self._state = capi.aligned_ws(self.nbytes, self.dev)
-            capi.check(lib.eec_ctc_prefix_begin(*self._head(), self._state[1], self.nbytes, stream_ptr(self.dev)), "eec_ctc_prefix_begin")
+        self.nbytes = capi.load().eec_ctc_prefix_state_bytes(n, self.R_max, Tq)
+        self._state = capi.aligned_ws(self.nbytes, self.dev)
+        launch("eec_ctc_prefix_begin", self.dev, *self._head(), self._state[1], self.nbytes)
 
     def _head(self):
-        return (self.emission.data_ptr(), _ptr(self.em_len), self.n, self.Tq, self.V, self.blank, self.R_max)
+        return (self.emission, self.em_len, self.n, self.Tq, self.V, self.blank, self.R_max)
 
     def step(self, att: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
         n, V = self.n, self.V
@@ -346,17 +288,15 @@ class CtcPrefixSession:
             att = capi.require_fp32("att", att, dev)
             if last.device != dev or (parent is not None and parent.device != dev):
                 raise RuntimeError(f"last and parent must be on {dev}")
-            with torch.cuda.device(dev):
-                tok = last.to(torch.int64).contiguous()
-                par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
-                local = torch.empty((n, R, V), dtype=torch.float32, device=dev)
-                capi.check(capi.load().eec_ctc_prefix_step(*self._head(), _ptr(par), tok.data_ptr(), R, self.rows, self.s,
-                                                           att.data_ptr(), self.weight, self.eos, self.pad, self.min_length, local.data_ptr(),
-                                                           self._state[1], self.nbytes, stream_ptr(dev)), "eec_ctc_prefix_step")
-                stream = torch.cuda.current_stream(dev)
-                for t in (att, tok, par):
-                    if t is not None:
-                        t.record_stream(stream)
+            tok = last.to(torch.int64).contiguous()
+            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            local = torch.empty((n, R, V), dtype=torch.float32, device=dev)
+            launch("eec_ctc_prefix_step", dev, *self._head(), par, tok, R, self.rows, self.s, att, self.weight, self.eos, self.pad,
+                   self.min_length, local, self._state[1], self.nbytes)
+            stream = torch.cuda.current_stream(dev)
+            for t in (att, tok, par):
+                if t is not None:
+                    t.record_stream(stream)
         self.s += 1
         self.rows = R
         return local
@@ -473,9 +413,7 @@ def _ctc_forward(x: Tensor, tg: Tensor, tl: Tensor, blank: int, il: Optional[Ten
     nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
     out = torch.empty((E,), dtype=torch.float32, device=dev)
     ws, ws_ptr = capi.aligned_ws(lib.eec_ctc_backward_workspace_bytes(E, B, Tq, tg.size(1)), dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_ctc_loss_forward_len(x.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1),
-                                                blank, nll.data_ptr(), out.data_ptr(), ws_ptr, stream_ptr(dev)), "eec_ctc_loss_forward")
+    launch("eec_ctc_loss_forward_len", dev, x, tg, tl, il, E, B, Tq, V, tg.size(1), blank, nll, out, ws_ptr)
     return out, nll, ws, ws_ptr
 
 
@@ -485,10 +423,7 @@ def _ctc_backward(x: Tensor, tg: Tensor, tl: Tensor, blank: int, il: Optional[Te
     E, B, Tq, V = x.shape
     dev = x.device
     g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        capi.check(capi.load().eec_ctc_loss_backward_len(x.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V,
-                                                         tg.size(1), blank, nll.data_ptr(), ws_ptr, g.data_ptr(),
-                                                         dlogp.data_ptr(), stream_ptr(dev)), "eec_ctc_loss_backward")
+    launch("eec_ctc_loss_backward_len", dev, x, tg, tl, il, E, B, Tq, V, tg.size(1), blank, nll, ws_ptr, g, dlogp)
 
 
 class _ExitCtcLossFn(torch.autograd.Function):
@@ -536,9 +471,7 @@ def exit_ctc_losses(enc_out: Tensor, targets: Tensor, target_len: Tensor, blank:
         return _ExitCtcLossFn.apply(enc_out, tg, tl, blank, il)
     nll = torch.empty((E * B,), dtype=torch.float32, device=dev)
     out = torch.empty((E,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(capi.load().eec_ctc_loss_len(enc_out.data_ptr(), tg.data_ptr(), tl.data_ptr(), _ptr(il), E, B, Tq, V, tg.size(1), blank,
-                                                nll.data_ptr(), out.data_ptr(), stream_ptr(dev)), "eec_ctc_loss")
+    launch("eec_ctc_loss_len", dev, enc_out, tg, tl, il, E, B, Tq, V, tg.size(1), blank, nll, out)
     return out
 
 
@@ -573,11 +506,7 @@ def _distill_args(name: str, enc_out: Tensor, frame_len: Optional[Tensor], teach
     if V > 256 or V % 4:
         raise ValueError(f"{name} needs a vocabulary of at most 256 entries, a multiple of 4 (got {V}): "
                          "the distillation kernels hold a vocabulary row in one wave")
-    if frame_len is not None:
-        frame_len = frame_len.to(device=enc_out.device, dtype=torch.int32).contiguous()
-        if frame_len.numel() != B:
-            raise ValueError(f"{name}: frame_len must have {B} entries, got {frame_len.numel()}")
-    return enc_out, frame_len, _teacher_map(teacher, E), float(temperature)
+    return enc_out, _frame_counts(name, "frame_len", frame_len, B, enc_out.device, any_dtype=True), _teacher_map(teacher, E), float(temperature)
 
 
 def _distill_forward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int, ...], tau: float) -> Tensor:
@@ -588,10 +517,7 @@ def _distill_forward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int,
     out = torch.empty((E,), dtype=torch.float32, device=dev)
     nbytes = lib.eec_exit_distill_workspace_bytes(E, B, Tq)
     ws, ws_ptr = capi.aligned_ws(nbytes, dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_exit_distill_forward(x.data_ptr(), _ptr(frame_len), (C.c_int32 * E)(*teacher),
-                                                E, B, Tq, V, tau, kl.data_ptr(), out.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)),
-                   "eec_exit_distill_forward")
+    launch("eec_exit_distill_forward", dev, x, frame_len, (C.c_int32 * E)(*teacher), E, B, Tq, V, tau, kl, out, ws_ptr, nbytes)
     return out
 
 
@@ -600,10 +526,7 @@ def _distill_backward(x: Tensor, frame_len: Optional[Tensor], teacher: Tuple[int
     E, B, Tq, V = x.shape
     dev = x.device
     g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        capi.check(capi.load().eec_exit_distill_backward(x.data_ptr(), _ptr(frame_len),
-                                                         (C.c_int32 * E)(*teacher), E, B, Tq, V, tau, g.data_ptr(), int(accumulate),
-                                                         dx.data_ptr(), stream_ptr(dev)), "eec_exit_distill_backward")
+    launch("eec_exit_distill_backward", dev, x, frame_len, (C.c_int32 * E)(*teacher), E, B, Tq, V, tau, g, int(accumulate), dx)
 
 
 class _ExitDistillFn(torch.autograd.Function):
@@ -704,8 +627,7 @@ def exit_statistics(enc_out: Tensor, frame_len: Optional[Tensor] = None) -> Exit
     stats = torch.empty((3, E, B), dtype=torch.float32, device=dev)
     nbytes = lib.eec_exit_stats_workspace_bytes(E, B, Tq)
     ws, ws_ptr = capi.aligned_ws(nbytes, dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.eec_exit_stats(x.data_ptr(), _ptr(fl), E, B, Tq, V, stats.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)), "eec_exit_stats")
+    launch("eec_exit_stats", dev, x, fl, E, B, Tq, V, stats, ws_ptr, nbytes)
     return ExitStatistics(stats[0], stats[1], stats[2])
 
 
@@ -722,9 +644,7 @@ def exit_route(score: Tensor, threshold: float, higher_is_better: bool = False, 
     n, dev = score.numel(), score.device
     idx = torch.full((2, n), n, dtype=torch.int32, device=dev)
     counts = torch.empty((2,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(capi.load().eec_exit_route(score.data_ptr(), n, float(threshold), int(bool(higher_is_better)), int(bool(force_all)),
-                                              idx[0].data_ptr(), idx[1].data_ptr(), counts.data_ptr(), stream_ptr(dev)), "eec_exit_route")
+    launch("eec_exit_route", dev, score, n, float(threshold), int(bool(higher_is_better)), int(bool(force_all)), idx[0], idx[1], counts)
     return idx[0], idx[1], counts
 
 
@@ -930,9 +850,7 @@ def _mwer_chunks(x: Tensor, N: int, L: int, max_workspace_bytes: int):
 def _mwer_forward_chunk(x, il, hyp, hl, risk, blank, b0, nb, ll, loss_eb, loss, ws_ptr, nbytes):
     E, B, Tq, V = x.shape
     N, L = hyp.shape[2:]
-    capi.check(capi.load().eec_ctc_mwer_forward(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), risk.data_ptr(), E, B, b0, nb, Tq, V, N, L,
-                                                int(blank), ll.data_ptr(), loss_eb.data_ptr(), loss.data_ptr(), ws_ptr, nbytes,
-                                                stream_ptr(x.device)), "eec_ctc_mwer_forward")
+    launch("eec_ctc_mwer_forward", x.device, x, il, hyp, hl, risk, E, B, b0, nb, Tq, V, N, L, int(blank), ll, loss_eb, loss, ws_ptr, nbytes)
 
 
 def _mwer_forward(x: Tensor, il: Optional[Tensor], hyp: Tensor, hl: Tensor, risk: Tensor, blank: int, max_workspace_bytes: int):
@@ -964,9 +882,8 @@ def _mwer_backward(x: Tensor, il: Optional[Tensor], hyp: Tensor, hl: Tensor, ris
     g = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
 
     def back(b0, nb, ws_ptr, nbytes):
-        capi.check(lib.eec_ctc_mwer_backward(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), E, B, b0, nb, Tq, V, N, L, int(blank),
-                                             ws_ptr, nbytes, g.data_ptr(), int(bool(accumulate)), dlogp.data_ptr(), stream_ptr(dev)),
-                   "eec_ctc_mwer_backward")
+        launch("eec_ctc_mwer_backward", dev, x, il, hyp, hl, E, B, b0, nb, Tq, V, N, L, int(blank), ws_ptr, nbytes, g,
+               int(bool(accumulate)), dlogp)
     with torch.cuda.device(dev):
         if kept is not None:
             back(0, B, kept[1], kept[2])
@@ -1019,9 +936,7 @@ def ctc_hyp_logp(enc_out: Tensor, hyp: Tensor, hyp_len: Tensor, input_len: Optio
     E, B, Tq, V = x.shape
     N, L = hyp.shape[2:]
     ll = torch.empty((E, B, N), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(capi.load().eec_ctc_hyp_logp(x.data_ptr(), _ptr(il), hyp.data_ptr(), hl.data_ptr(), E, B, Tq, V, N, L, int(blank),
-                                                ll.data_ptr(), stream_ptr(x.device)), "eec_ctc_hyp_logp")
+    launch("eec_ctc_hyp_logp", x.device, x, il, hyp, hl, E, B, Tq, V, N, L, int(blank), ll)
     return ll
 
 

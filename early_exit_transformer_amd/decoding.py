@@ -10,7 +10,7 @@ import torch
 from torch import Tensor
 
 from . import capi
-from .capi import aligned_ws, check as _check, stream_ptr
+from .capi import aligned_ws, launch
 
 
 def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old: Tensor, tokens_new: Tensor, length: int):
@@ -35,10 +35,9 @@ def beam_select(logp: Tensor, scores: Tensor, penalty: float, k: int, tokens_old
     out_s = torch.empty((n, k), dtype=torch.float32, device=dev)
     parent = torch.empty((n, k), dtype=torch.int64, device=dev)
     tok = torch.empty((n, k), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _check(capi.load().eec_beam_select(n, R, V, int(k), logp.contiguous().data_ptr(), scores.contiguous().data_ptr(), float(penalty),
-                                           out_s.data_ptr(), parent.data_ptr(), tok.data_ptr(), tokens_old.data_ptr(), tokens_new.data_ptr(),
-                                           int(length), tokens_old.size(2), tokens_old.size(1), stream_ptr(dev)), "eec_beam_select")
+    logp, scores = logp.contiguous(), scores.contiguous()  # named: they live across the call
+    launch("eec_beam_select", dev, n, R, V, int(k), logp, scores, float(penalty), out_s, parent, tok, tokens_old, tokens_new, int(length),
+           tokens_old.size(2), tokens_old.size(1))
     return out_s, parent, tok
 
 
@@ -47,7 +46,7 @@ class DecoderStepSession:
     returns the log-probs of the NEXT token of every live beam, [*lead, R, V] -- what
     ``model._decoder_(prefixes, enc, layer_n)[:, -1]`` returns (util/beam_infer.py:236-240) -- from the last token of every
     beam and the row of the previous step it extends.  ``lead`` is the shape of the searches advanced in lockstep by the same
-    launches; a subclass owns the cache(s) and contributes the two C calls, ``_begin`` (one per tensor of ``encs`` and cache)
+    launches; a subclass owns the cache(s) and contributes the two launches, ``_begin`` (one per tensor of ``encs`` and cache)
     and ``_step``."""
 
     MAX = 8  # decoders per call
@@ -63,18 +62,16 @@ class DecoderStepSession:
         self.ps = (C.POINTER(capi.EecDecoderParams) * len(ps_list))(*[C.pointer(p) for p in ps_list])
         self.geo = (cfg.d_model, cfg.n_heads, d_ff, V)
         self.pad_idx, passes = int(model.trg_pad_idx), int(model.decoder_passes)
-        with torch.cuda.device(self.dev):
-            stream = torch.cuda.current_stream(self.dev)
-            self._caches = [aligned_ws(nbytes, self.dev) for _ in encs]
-            self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
-            for i, enc in enumerate(encs):
-                enc_c = enc.contiguous().float()
-                _check(self._begin(lib, i, enc_c.data_ptr(), passes, stream_ptr(self.dev)), self.entry + "begin")
-                enc_c.record_stream(stream)
-                self._caches[i][0].record_stream(stream)
+        stream = torch.cuda.current_stream(self.dev)
+        self._caches = [aligned_ws(nbytes, self.dev) for _ in encs]
+        self.ptrs = (C.c_void_p * len(encs))(*[ptr for _, ptr in self._caches])
+        for i, enc in enumerate(encs):
+            enc_c = enc.contiguous().float()  # named: it lives across the call
+            self._begin(i, enc_c, passes)
+            enc_c.record_stream(stream)
+            self._caches[i][0].record_stream(stream)
 
     def step(self, last_tokens: Tensor, parent: Optional[Tensor] = None, log_softmax: bool = True) -> Tensor:
-        lib = capi.load()
         lead = self.lead
         if last_tokens.dim() != len(lead) + 1 or last_tokens.shape[:-1] != lead:
             raise ValueError(f"last_tokens must be [{', '.join(map(str, lead + ('live beams',)))}]")
@@ -86,16 +83,14 @@ class DecoderStepSession:
         if parent is not None and parent.shape != last_tokens.shape:
             raise ValueError("parent: one row of the previous step per live beam of every search")
         dev = self.dev
-        with torch.cuda.device(dev):
-            tok = last_tokens.to(device=dev, dtype=torch.int64).contiguous()
-            par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            _check(self._step(lib, tok.data_ptr(), par.data_ptr() if par is not None else None, R, int(log_softmax), out.data_ptr(),
-                              stream_ptr(dev)), self.entry + "step")
-            tok.record_stream(stream)
-            if par is not None:
-                par.record_stream(stream)
+        tok = last_tokens.to(device=dev, dtype=torch.int64).contiguous()
+        par = parent.to(device=dev, dtype=torch.int64).contiguous() if parent is not None and self.s > 0 else None
+        out = torch.empty((*lead, R, self.V), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        self._step(tok, par, R, int(log_softmax), out)
+        tok.record_stream(stream)
+        if par is not None:
+            par.record_stream(stream)
         self.s += 1
         self.rows = R
         return out
@@ -105,32 +100,30 @@ class _ExitSessions(DecoderStepSession):
     """n <= 8 exits of ONE utterance, a cache per exit (csrc/decoder_step.hip); ``lead`` is (n,), or () for a single exit.  A
     single exit is a group of one, as eec_decoder_step is eec_decoder_step_multi with n = 1."""
 
-    entry = "eec_decoder_"
+    def _begin(self, i, enc, passes):
+        launch("eec_decoder_begin", self.dev, self.ps[i], *self.geo, enc, self.Tq, self.max_steps, passes, self.ptrs[i], self.nbytes)
 
-    def _begin(self, lib, i, enc, passes, stream):
-        return lib.eec_decoder_begin(self.ps[i], *self.geo, enc, self.Tq, self.max_steps, passes, self.ptrs[i], self.nbytes, stream)
-
-    def _step(self, lib, tok, par, R, log_softmax, out, stream):
-        return lib.eec_decoder_step_multi(len(self.ps), self.ps, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps,
-                                          log_softmax, out, self.ptrs, self.nbytes, stream)
+    def _step(self, tok, par, R, log_softmax, out):
+        launch("eec_decoder_step_multi", self.dev, len(self.ps), self.ps, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq,
+               self.max_steps, log_softmax, out, self.ptrs, self.nbytes)
 
 
 class _BatchSession(DecoderStepSession):
     """E exits x B utterances of a padded batch, one cache for all of them (csrc/decoder_batch.hip); ``lead`` is (E, B).  The
     launches of a step do not depend on E or B.  Log-probs only."""
 
-    entry = "eec_decoder_batch_"
     E = property(lambda self: self.lead[0])
     B = property(lambda self: self.lead[1])
 
-    def _begin(self, lib, i, taps, passes, stream):
-        return lib.eec_decoder_batch_begin(self.ps, *self.lead, *self.geo, taps, self.Tq, self.max_steps, passes, self.ptrs[0], self.nbytes, stream)
+    def _begin(self, i, taps, passes):
+        launch("eec_decoder_batch_begin", self.dev, self.ps, *self.lead, *self.geo, taps, self.Tq, self.max_steps, passes, self.ptrs[0],
+               self.nbytes)
 
-    def _step(self, lib, tok, par, R, log_softmax, out, stream):
+    def _step(self, tok, par, R, log_softmax, out):
         if not log_softmax:
             raise ValueError("the batch session returns log-probs only")
-        return lib.eec_decoder_batch_step(self.ps, *self.lead, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq, self.max_steps, out,
-                                          self.ptrs[0], self.nbytes, stream)
+        launch("eec_decoder_batch_step", self.dev, self.ps, *self.lead, *self.geo, self.pad_idx, tok, par, R, self.rows, self.s, self.Tq,
+               self.max_steps, out, self.ptrs[0], self.nbytes)
 
 
 class _DecoderTrainFn(torch.autograd.Function):
@@ -161,9 +154,8 @@ class _DecoderTrainFn(torch.autograd.Function):
             ws, ws_ptr = aligned_ws(nbytes, dev)
             out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
             geo = (cfg.d_model, cfg.n_heads, d_ff, V)
-            _check(lib.eec_decoder_train_forward(C.byref(ps), *geo, int(model.trg_pad_idx), trg.data_ptr(), enc.data_ptr(), Bm, S, Tq,
-                                                 int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out.data_ptr(), ws_ptr,
-                                                 nbytes, stream_ptr(dev)), "eec_decoder_train_forward")
+            launch("eec_decoder_train_forward", dev, C.byref(ps), *geo, int(model.trg_pad_idx), trg, enc, Bm, S, Tq,
+                   int(model.decoder_passes), float(model.dropout), int(seed), int(idx), out, ws_ptr, nbytes)
         ctx.model, ctx.idx, ctx.names, ctx.seed, ctx.geo = model, idx, names, int(seed), geo
         ctx.ws, ctx.ws_ptr, ctx.nbytes, ctx.drop, ctx.passes = ws, ws_ptr, nbytes, float(model.dropout), int(model.decoder_passes)
         ctx.save_for_backward(trg, enc, *params)
@@ -177,7 +169,6 @@ class _DecoderTrainFn(torch.autograd.Function):
         model, idx, names = ctx.model, ctx.idx, ctx.names
         trg, enc, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
         dev = trg.device
-        lib = capi.load()
         Bm, S = trg.shape
         Tq = enc.size(1)
         g = g.contiguous().float()
@@ -187,9 +178,8 @@ class _DecoderTrainFn(torch.autograd.Function):
             grads = {k: torch.empty_like(v) for k, v in tensors.items()}
             gs, gkeep = model._decoder_struct(idx, grads, with_pe=False)
             g_enc = torch.empty_like(enc)
-            _check(lib.eec_decoder_train_backward(C.byref(ps), C.byref(gs), *ctx.geo, trg.data_ptr(), enc.data_ptr(), Bm, S, Tq, ctx.passes,
-                                                  ctx.drop, ctx.seed, int(idx), g.data_ptr(), g_enc.data_ptr(), ctx.ws_ptr, ctx.nbytes,
-                                                  stream_ptr(dev)), "eec_decoder_train_backward")
+            launch("eec_decoder_train_backward", dev, C.byref(ps), C.byref(gs), *ctx.geo, trg, enc, Bm, S, Tq, ctx.passes, ctx.drop, ctx.seed,
+                   int(idx), g, g_enc, ctx.ws_ptr, ctx.nbytes)
         ctx.ws = None
         need = ctx.needs_input_grad[6:]
         return (None, None, None, g_enc if ctx.needs_input_grad[3] else None, None, None,

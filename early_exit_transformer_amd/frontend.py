@@ -40,8 +40,7 @@ class MelFrontend:
         if self._fe is None:
             h = C.c_void_p()
             with torch.cuda.device(device):
-                rc = lib.eec_frontend_create(self.sample_rate, 2 * self.n_fft, self.win_length, self.hop_length, self.n_mels, C.byref(h))
-            capi.check(rc, "eec_frontend_create")
+                capi.call("eec_frontend_create", self.sample_rate, 2 * self.n_fft, self.win_length, self.hop_length, self.n_mels, C.byref(h))
             self._fe, self._device = h, device
         return self._fe
 
@@ -61,8 +60,6 @@ class MelFrontend:
         len_dev = lengths.to(device=dev, dtype=torch.int64).contiguous() if lengths is not None else None
         with torch.cuda.device(dev):
             fe = self._handle(dev)
-            rc = capi.load().eec_frontend_forward(fe, wave.data_ptr(), len_dev.data_ptr() if len_dev is not None else None, B, L,
-                                                  mel.data_ptr(), capi.stream_ptr(dev))
-            capi.check(rc, "eec_frontend_forward")
+            capi.launch("eec_frontend_forward", dev, fe, wave, len_dev, B, L, mel)
             wave.record_stream(torch.cuda.current_stream(dev))
         return mel[0] if squeeze else mel

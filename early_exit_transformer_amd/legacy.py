@@ -100,7 +100,7 @@ class Early_encoder(_HipEncoderMixin, nn.Module):
         return list(self.conv_subsample.parameters()) + list(self.encoders.parameters()) + \
             list(self.linears.parameters()) + [self.positional_encoder.pe]
 
-    def _pack(self, enc, ptr, stream, struct) -> None:  # its own layer struct and C entry; ``struct`` (EecParams) is not used
+    def _pack(self, enc, ptr, device, struct) -> None:  # its own layer struct and C entry; ``struct`` (EecParams) is not used
         E, L = self._cfg.n_exits, self._cfg.layers_per_exit
         layers = (EecLegacyLayerParams * (E * L))()
         for e in range(E):
@@ -112,7 +112,7 @@ class Early_encoder(_HipEncoderMixin, nn.Module):
                                  ptr("conv_subsample.sequential.1.weight"), ptr("conv_subsample.sequential.1.bias"),
                                  ptr("positional_encoder.pe"), layers, arr("encoders.{e}.layer_norm.weight"),
                                  arr("encoders.{e}.layer_norm.bias"), arr("linears.{e}.weight"), arr("linears.{e}.bias"))
-        capi.check(capi.load().eec_encoder_pack_legacy(enc, C.byref(params), stream), "eec_encoder_pack_legacy")
+        capi.launch("eec_encoder_pack_legacy", device, enc, C.byref(params))
 
     def forward(self, src: Tensor) -> Tensor:
         lengths = torch.full((src.size(0),), src.size(2), dtype=torch.int64)

@@ -83,8 +83,8 @@ class Lexicon:
         image = torch.empty((nbytes,), dtype=torch.uint8)
         code_map = np.empty(256, dtype=np.int32)
         n_codes = C.c_int32()
-        capi.check(lib.eec_lexicon_pack(symbols.ctypes.data if symbols.size else None, offsets.ctypes.data, len(self.words), image.data_ptr(),
-                                        nbytes, code_map.ctypes.data, C.byref(n_codes)), "eec_lexicon_pack")
+        capi.call("eec_lexicon_pack", symbols.ctypes.data if symbols.size else None, offsets.ctypes.data, len(self.words), image, nbytes,
+                  code_map.ctypes.data, C.byref(n_codes))
         self.alphabet = n_codes.value
         self._codes = _Codes({int(code_map[c]): c for c in range(1, self.alphabet + 1)})
         self._image = image
@@ -129,15 +129,13 @@ class Lexicon:
         lib = capi.load()
         with torch.cuda.device(dev):
             packed = self._packed_on(dev)
-            query = torch.from_numpy(buf).to(dev, non_blocking=True)
+            query = torch.from_numpy(buf).to(dev, non_blocking=True)  # int32 offsets [Q + 1], then the bytes
             ws_bytes = lib.eec_lexicon_nearest_workspace_bytes(Q, len(self.words))
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-            stream = capi.stream_ptr(dev)
-            capi.check(lib.eec_lexicon_nearest(packed.data_ptr(), len(self.words), query.data_ptr() + 4 * (Q + 1), query.data_ptr(), Q, longest,
-                                               out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws_bytes, stream),
-                       "eec_lexicon_nearest")
+            capi.launch("eec_lexicon_nearest", dev, packed, len(self.words), query.data_ptr() + 4 * (Q + 1), query.data_ptr(), Q, longest,
+                        out[0], out[1], ws, ws_bytes)
             self.launches += 1
-            self.last_stream = stream.value or 0
+            self.last_stream = torch.cuda.current_stream(dev).cuda_stream
         return out[0], out[1]
 
     def apply_batch(self, texts: Sequence[str]) -> List[str]:
@@ -177,8 +175,8 @@ class TokenTrie:
         nbytes = lib.eec_ctc_trie_pack_bytes(len(spellings), int(offsets[-1]))
         image = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
         n_nodes, n_shadowed = C.c_int32(), C.c_int32()
-        capi.check(lib.eec_ctc_trie_pack(flat.ctypes.data if flat.size else None, offsets.ctypes.data, len(spellings), self.V, self.blank,
-                                         self.sil, image.data_ptr(), nbytes, C.byref(n_nodes), C.byref(n_shadowed)), "eec_ctc_trie_pack")
+        capi.call("eec_ctc_trie_pack", flat.ctypes.data if flat.size else None, offsets.ctypes.data, len(spellings), self.V, self.blank,
+                  self.sil, image, nbytes, C.byref(n_nodes), C.byref(n_shadowed))
         self.n_nodes, self.n_shadowed = n_nodes.value, n_shadowed.value
         self._image = image[: 4 * int(image[36:40].view(torch.int32))]  # header[9]: the dwords actually used
         self._resident = None  # (device, device copy)
@@ -256,8 +254,8 @@ class NGramLM:
         image = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
         ptrs = lambda arrays: (C.c_void_p * order)(*[a.ctypes.data if a.size else None for a in arrays])  # noqa: E731
         n_nodes = C.c_int32()
-        capi.check(lib.eec_ngram_pack(order, counts.ctypes.data, ptrs(ids), ptrs(lps), ptrs(bos_), self.word_map.ctypes.data if self.n_words else None,
-                                      self.n_words, self.bos, self.eos, image.data_ptr(), nbytes, C.byref(n_nodes)), "eec_ngram_pack")
+        capi.call("eec_ngram_pack", order, counts.ctypes.data, ptrs(ids), ptrs(lps), ptrs(bos_), self.word_map.ctypes.data if self.n_words else None,
+                  self.n_words, self.bos, self.eos, image, nbytes, C.byref(n_nodes))
         self.n_nodes = n_nodes.value
         self._image = image[: 4 * int(image[60:64].view(torch.int32))]  # header[15]: the dwords actually used
         self._resident = None  # (device, device copy)
@@ -394,7 +392,7 @@ class NGramLM:
             lib = capi.load()
             nbytes = lib.eec_ctc_trie_smear_bytes(trie.n_nodes)
             table = torch.zeros((max(nbytes, 8),), dtype=torch.uint8)
-            capi.check(lib.eec_ctc_trie_smear(trie._image.data_ptr(), self._image.data_ptr(), table.data_ptr(), nbytes), "eec_ctc_trie_smear")
+            capi.call("eec_ctc_trie_smear", trie._image, self._image, table, nbytes)
             self._smear = (trie, SmearTable(table))
         return self._smear[1]
 

@@ -18,7 +18,7 @@ import torch
 from torch import Tensor, nn
 
 from . import capi
-from .capi import new_seed, stream_ptr
+from .capi import launch, new_seed
 from .capi import to_device as _to_device
 from .conformer import Conformer
 from .ctc import (CtcPrefixSession, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, exit_ctc_losses, exit_distill_losses,  # noqa: F401
@@ -111,44 +111,41 @@ class _HipEncoderMixin:
         """``handle`` on ``device`` with ``tensors`` packed (again, if one of them changed) from ``struct(ptr)``."""
         def repack(enc):
             sd = self.state_dict(keep_vars=True)
-            self._pack(enc, lambda name: capi.require_fp32(f"parameter {name}", sd[name], device).data_ptr(), stream_ptr(device),
+            self._pack(enc, lambda name: capi.require_fp32(f"parameter {name}", sd[name], device).data_ptr(), device,
                        struct or self._params_struct)
         return handle.ensure(device, tensors, repack)
 
     def _ensure_packed(self, device: torch.device) -> None:
         self._enc = self._packed(self._handle, self._param_tensors(), device)
 
-    def _pack(self, enc, ptr, stream, struct) -> None:
+    def _pack(self, enc, ptr, device, struct) -> None:
         params, keep = struct(ptr)
-        capi.check(capi.load().eec_encoder_pack(enc, C.byref(params), stream), "eec_encoder_pack")
+        launch("eec_encoder_pack", device, enc, C.byref(params))
 
     def _group(self, handle: capi.EncoderHandle, group: int, x: Tensor, key_len: Tensor) -> Tensor:
         """Group ``group`` of ``handle`` on x [B, T', D] fp32 contiguous, IN PLACE; key_len [B] int32 on the device."""
         B, Tq, _ = x.shape
         _, ws_ptr, ws_bytes = handle.workspace("group_", B, Tq, x.device)
-        capi.check(capi.load().eec_encoder_group_forward(handle.h, group, x.data_ptr(), key_len.data_ptr(), B, Tq,
-                                                         capi.PRECISIONS[self.precision], ws_ptr, ws_bytes, stream_ptr(x.device)),
-                   "eec_encoder_group_forward")
+        launch("eec_encoder_group_forward", x.device, handle.h, group, x, key_len, B, Tq, capi.PRECISIONS[self.precision], ws_ptr, ws_bytes)
         return x
 
     def _head(self, index: int, rows: Tensor, out: Tensor) -> Tensor:
         """Exit ``index``'s Linear + log_softmax of rows [..., D] into ``out`` [..., V]."""
-        capi.check(capi.load().eec_encoder_head_forward(self._enc, index, rows.data_ptr(), rows.numel() // rows.size(-1), out.data_ptr(),
-                                                        capi.PRECISIONS[self.precision], stream_ptr(rows.device)),
-                   "eec_encoder_head_forward")
+        launch("eec_encoder_head_forward", rows.device, self._enc, index, rows, rows.numel() // rows.size(-1), out,
+               capi.PRECISIONS[self.precision])
         return out
 
     # -- measurement hook -----------------------------------------------------
     def set_profiling(self, enable: bool, max_launches: int = 8192) -> None:
         if self._enc is None:
             raise RuntimeError("run one forward first (the encoder handle is created lazily)")
-        capi.check(capi.load().eec_encoder_set_profiling(self._enc, int(enable), max_launches), "set_profiling")
+        capi.call("eec_encoder_set_profiling", self._enc, int(enable), max_launches)
 
     def read_profile(self) -> Dict[str, Tuple[float, int]]:
         """{kernel class: (total ms, launches)} of the launches recorded since set_profiling(True)."""
         n = len(capi.KERNEL_CLASSES)
         ms, cnt = (C.c_double * n)(), (C.c_longlong * n)()
-        capi.check(capi.load().eec_encoder_profile_read(self._enc, ms, cnt, n), "profile_read")
+        capi.call("eec_encoder_profile_read", self._enc, ms, cnt, n)
         return {k: (ms[i], cnt[i]) for i, k in enumerate(capi.KERNEL_CLASSES)}
 
     # -- data-parallel training (BASELINE.json configs[3]) -----------------------
@@ -223,17 +220,12 @@ class _HipEncoderMixin:
             taps = torch.empty((E, B, Tq, D), dtype=torch.float32, device=dev) if want_taps else None
             xdbg = torch.empty((B, Tq, D), dtype=torch.float32, device=dev) if want_x else None
             _, ws_ptr, ws_bytes = self._handle.workspace("", B, T, dev)
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             if n_groups is not None:
-                rc = lib.eec_encoder_forward_prefix(
-                    self._enc, src.data_ptr(), len_dev.data_ptr(), B, T, capi.PRECISIONS[self.precision], E,
-                    ptr(out), ptr(taps), ptr(xdbg), ws_ptr, ws_bytes, stream_ptr(dev))
-                capi.check(rc, "eec_encoder_forward_prefix")
+                launch("eec_encoder_forward_prefix", dev, self._enc, src, len_dev, B, T, capi.PRECISIONS[self.precision], E, out, taps, xdbg,
+                       ws_ptr, ws_bytes)
             else:
-                rc = lib.eec_encoder_forward(
-                    self._enc, src.data_ptr(), len_dev.data_ptr(), B, T, capi.PRECISIONS[self.precision],
-                    ptr(out), ptr(taps), ws_ptr, ws_bytes, stop_after, ptr(xdbg), stream_ptr(dev))
-                capi.check(rc, "eec_encoder_forward")
+                launch("eec_encoder_forward", dev, self._enc, src, len_dev, B, T, capi.PRECISIONS[self.precision], out, taps, ws_ptr, ws_bytes,
+                       stop_after, xdbg)
             # src/len_dev must outlive the asynchronous launches on this stream
             src.record_stream(torch.cuda.current_stream(dev))
             len_dev.record_stream(torch.cuda.current_stream(dev))
@@ -583,8 +575,7 @@ class Early_zipformer(_HipEncoderMixin, nn.Module):
             self._ensure_packed(dev)
             B, _, T = src.shape
             enc = torch.empty((B, (T - 3) // 2 + 1, self._cfg.d_model), dtype=torch.float32, device=dev)
-            capi.check(capi.load().eec_encoder_stem1_forward(self._enc, src.data_ptr(), B, T, enc.data_ptr(), stream_ptr(dev)),
-                       "eec_encoder_stem1_forward")
+            launch("eec_encoder_stem1_forward", dev, self._enc, src, B, T, enc)
             src.record_stream(torch.cuda.current_stream(dev))
 
             def head(rows):
@@ -710,10 +701,8 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             nbytes = lib.eec_decoder_workspace_bytes(cfg.d_model, cfg.n_heads, d_ff, V, Bm, S, Tq)
             ws, ws_ptr = capi.aligned_ws(nbytes, dev)
             out = torch.empty((Bm, S, V), dtype=torch.float32, device=dev)
-            rc = lib.eec_decoder_forward(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), trg_c.data_ptr(),
-                                         enc_c.data_ptr(), Bm, S, Tq, int(shared), int(self.decoder_passes), int(log_softmax), out.data_ptr(),
-                                         ws_ptr, nbytes, stream_ptr(dev))
-            capi.check(rc, "eec_decoder_forward")
+            launch("eec_decoder_forward", dev, C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), trg_c, enc_c, Bm, S, Tq,
+                   int(shared), int(self.decoder_passes), int(log_softmax), out, ws_ptr, nbytes)
             for t in (ws, trg_c, enc_c):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out
@@ -768,10 +757,8 @@ class full_conformer(_HipEncoderMixin, nn.Module):
             ws, ws_ptr = capi.aligned_ws(nbytes, dev)
             for i in range(0, n, part):
                 m = min(part, n - i)
-                rc = lib.eec_decoder_score(C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), int(sos), int(eos),
-                                           tok[i:i + m].data_ptr(), ln[i:i + m].data_ptr(), enc_c[i:i + m].data_ptr(), m, R, L, Tq,
-                                           int(self.decoder_passes), out[i:i + m].data_ptr(), ws_ptr, nbytes, stream_ptr(dev))
-                capi.check(rc, "eec_decoder_score")
+                launch("eec_decoder_score", dev, C.byref(ps), cfg.d_model, cfg.n_heads, d_ff, V, int(self.trg_pad_idx), int(sos), int(eos),
+                       tok[i:i + m], ln[i:i + m], enc_c[i:i + m], m, R, L, Tq, int(self.decoder_passes), out[i:i + m], ws_ptr, nbytes)
             for t in (ws, tok, ln, enc_c):
                 t.record_stream(torch.cuda.current_stream(dev))
         return out

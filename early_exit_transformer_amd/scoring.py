@@ -20,7 +20,6 @@ import torch
 from torch import Tensor
 
 from . import capi
-from .capi import stream_ptr
 from .ctc import select_exits
 
 EDIT_MAX_LEN = 1024  # EEC_EDIT_MAX_LEN
@@ -153,18 +152,17 @@ def edit_counts(hyp: Tensor, hyp_len: Tensor, ref: Tensor, ref_len: Tensor, ref_
         n_ops = torch.zeros((P,), dtype=torch.int32, device=dev) if want_ops else None  # rows of no tokens have no ops to ask for
         per_pair = lib.eec_edit_distance_workspace_bytes(1, Lr, Lh, int(want_ops))
         step = max(1, int(max_workspace_bytes) // per_pair) if per_pair else max(P, 1)
-        ptr = lambda t, c=0: None if t is None or t.numel() == 0 else t[c:].data_ptr()  # noqa: E731
-        with torch.cuda.device(dev):
-            ws = ws_ptr = None
-            for c in range(0, P, step):
-                k = min(step, P - c)
-                nbytes = lib.eec_edit_distance_workspace_bytes(k, Lr, Lh, int(want_ops))
-                if nbytes and ws is None:
-                    ws, ws_ptr = capi.aligned_ws(nbytes, dev)  # the first chunk is the largest
-                # without ref_of a chunk scores against its own slice of the references
-                r_ptr, rl_ptr, n_refs = (ptr(ref, c), ptr(ref_len, c), k) if ref_of is None else (ptr(ref), ptr(ref_len), R)
-                capi.check(lib.eec_edit_distance(ptr(hyp, c), ptr(hyp_len, c), k, Lh, r_ptr, rl_ptr, n_refs, Lr, ptr(ref_of, c), ptr(counts, c),
-                                                 ptr(ops, c), ptr(n_ops, c), ws_ptr, nbytes, stream_ptr(dev)), "eec_edit_distance")
+        rows = lambda t, c=0: None if t is None or t.numel() == 0 else t[c:]  # noqa: E731
+        ws = ws_ptr = None
+        for c in range(0, P, step):
+            k = min(step, P - c)
+            nbytes = lib.eec_edit_distance_workspace_bytes(k, Lr, Lh, int(want_ops))
+            if nbytes and ws is None:
+                ws, ws_ptr = capi.aligned_ws(nbytes, dev)  # the first chunk is the largest
+            # without ref_of a chunk scores against its own slice of the references
+            refs, ref_lens, n_refs = (rows(ref, c), rows(ref_len, c), k) if ref_of is None else (rows(ref), rows(ref_len), R)
+            capi.launch("eec_edit_distance", dev, rows(hyp, c), rows(hyp_len, c), k, Lh, refs, ref_lens, n_refs, Lr, rows(ref_of, c),
+                        rows(counts, c), rows(ops, c), rows(n_ops, c), ws_ptr, nbytes)
     hits = torch.where(counts[:, 0] < 0, counts[:, 0], _ref_lengths(ref_len, ref_of, Lr, P) - counts[:, 1] - counts[:, 2])
     return EditCounts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], hits.to(torch.int32), ops, n_ops)
 

@@ -12,7 +12,7 @@ import torch
 from torch import Tensor, nn
 
 from . import capi
-from .capi import aligned_ws, check as _check, stream_ptr, to_device
+from .capi import aligned_ws, launch, to_device
 
 _GROUP_FIELDS = [f for f in capi._LAYER_FIELDS if f not in ("conv_bn_rm", "conv_bn_rv")]  # the 30 trainable tensors of a ConformerLayer
 
@@ -148,9 +148,8 @@ class _TrainGroupFn(torch.autograd.Function):
             ws, ws_ptr = aligned_ws(nbytes, dev)
             out = torch.empty_like(x)
             bn = torch.empty((L, 2, D), dtype=torch.float32, device=dev)
-            _check(lib.eec_train_group_forward(C.byref(cfg), layers, L, x.data_ptr(), key_len.data_ptr(), B, Tq, int(model.train_passes),
-                                               float(model.dropout), int(seed), int(site_base), out.data_ptr(), bn.data_ptr(), ws_ptr, nbytes,
-                                               stream_ptr(dev)), "eec_train_group_forward")
+            launch("eec_train_group_forward", dev, C.byref(cfg), layers, L, x, key_len, B, Tq, int(model.train_passes), float(model.dropout),
+                   int(seed), int(site_base), out, bn, ws_ptr, nbytes)
             _update_running_stats([group], bn, B * Tq)
         ctx.model, ctx.L, ctx.seed, ctx.site_base = model, L, int(seed), int(site_base)
         ctx.ws, ctx.ws_ptr, ctx.nbytes = ws, ws_ptr, nbytes
@@ -165,7 +164,6 @@ class _TrainGroupFn(torch.autograd.Function):
             raise RuntimeError("this group's recorded forward was already consumed by a backward")
         x, key_len, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
         dev = x.device
-        lib = capi.load()
         B, Tq, _ = x.shape
         g = g.contiguous().float()
         with torch.cuda.device(dev):
@@ -173,9 +171,8 @@ class _TrainGroupFn(torch.autograd.Function):
             grads = [torch.empty_like(t) for t in params]
             glayers = _group_struct(grads, ctx.L)
             g_in = torch.empty_like(x)
-            _check(lib.eec_train_group_backward(C.byref(ctx.model._cfg), layers, glayers, ctx.L, x.data_ptr(), key_len.data_ptr(), B, Tq,
-                                                ctx.passes, ctx.drop, ctx.seed, ctx.site_base, g.data_ptr(), g_in.data_ptr(), ctx.ws_ptr,
-                                                ctx.nbytes, stream_ptr(dev)), "eec_train_group_backward")
+            launch("eec_train_group_backward", dev, C.byref(ctx.model._cfg), layers, glayers, ctx.L, x, key_len, B, Tq, ctx.passes, ctx.drop,
+                   ctx.seed, ctx.site_base, g, g_in, ctx.ws_ptr, ctx.nbytes)
         ctx.ws = None
         need = ctx.needs_input_grad[6:]
         return (None, None, g_in if ctx.needs_input_grad[2] else None, None, None, None, *[gr if nd else None for gr, nd in zip(grads, need)])
@@ -200,10 +197,8 @@ class _TrainStemFn(torch.autograd.Function):
                 raise ValueError("unsupported geometry for the training stem")
             ws, ws_ptr = aligned_ws(nbytes, dev)
             out = torch.empty((B, To, cfg.d_model), dtype=torch.float32, device=dev)
-            _check(lib.eec_train_stem_forward(C.byref(cfg), w0.data_ptr(), b0.data_ptr(), w1.data_ptr() if two else None,
-                                              b1.data_ptr() if two else None, pe.data_ptr(), mel.data_ptr(), B, T, int(model.train_passes),
-                                              float(model.dropout), int(seed), int(site), out.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)),
-                   "eec_train_stem_forward")
+            launch("eec_train_stem_forward", dev, C.byref(cfg), w0, b0, w1, b1, pe, mel, B, T, int(model.train_passes), float(model.dropout),
+                   int(seed), int(site), out, ws_ptr, nbytes)
         ctx.model, ctx.geo, ctx.two = model, (B, T), two
         ctx.seed, ctx.site, ctx.passes, ctx.drop = int(seed), int(site), int(model.train_passes), float(model.dropout)
         ctx.ws, ctx.ws_ptr, ctx.nbytes = ws, ws_ptr, nbytes
@@ -216,17 +211,14 @@ class _TrainStemFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         w0, b0 = saved[1], saved[2]
         dev = g.device
-        lib = capi.load()
         B, T = ctx.geo
         g = g.contiguous().float()
         with torch.cuda.device(dev):
             g_w0, g_b0 = torch.empty_like(w0), torch.empty_like(b0)
             g_w1 = torch.empty_like(saved[3]) if ctx.two else None
             g_b1 = torch.empty_like(saved[4]) if ctx.two else None
-            _check(lib.eec_train_stem_backward(C.byref(ctx.model._cfg), int(ctx.two), B, T, ctx.passes, ctx.drop, ctx.seed, ctx.site,
-                                               g.data_ptr(), g_w0.data_ptr(), g_b0.data_ptr(), g_w1.data_ptr() if ctx.two else None,
-                                               g_b1.data_ptr() if ctx.two else None, ctx.ws_ptr, ctx.nbytes, stream_ptr(dev)),
-                   "eec_train_stem_backward")
+            launch("eec_train_stem_backward", dev, C.byref(ctx.model._cfg), int(ctx.two), B, T, ctx.passes, ctx.drop, ctx.seed, ctx.site, g,
+                   g_w0, g_b0, g_w1, g_b1, ctx.ws_ptr, ctx.nbytes)
         ctx.ws = None
         return (None, None, None, None, None, g_w0, g_b0, g_w1, g_b1)
 
@@ -236,7 +228,6 @@ class _TrainHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, passes, x, W, b):
-        lib = capi.load()
         dev = x.device
         x = x.contiguous().float()
         M, D = x.shape
@@ -244,8 +235,7 @@ class _TrainHeadFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             logp = torch.empty((M, V), dtype=torch.float32, device=dev)
             scratch = torch.empty((M, V), dtype=torch.float32, device=dev)
-            _check(lib.eec_train_head_forward(x.data_ptr(), W.data_ptr(), b.data_ptr(), M, V, D, int(passes), logp.data_ptr(),
-                                              scratch.data_ptr(), stream_ptr(dev)), "eec_train_head_forward")
+            launch("eec_train_head_forward", dev, x, W, b, M, V, D, int(passes), logp, scratch)
             scratch.record_stream(torch.cuda.current_stream(dev))
         ctx.passes = int(passes)
         ctx.save_for_backward(x, W, logp)
@@ -264,9 +254,7 @@ class _TrainHeadFn(torch.autograd.Function):
             dW, db = torch.empty_like(W), torch.empty((V,), dtype=torch.float32, device=dev)
             dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
             scratch = torch.empty((lib.eec_train_head_backward_scratch_floats(M, V, D),), dtype=torch.float32, device=dev)
-            _check(lib.eec_train_head_backward(x.data_ptr(), W.data_ptr(), logp.data_ptr(), g.data_ptr(), M, V, D, ctx.passes,
-                                               dx.data_ptr() if dx is not None else None, dW.data_ptr(), db.data_ptr(), scratch.data_ptr(),
-                                               stream_ptr(dev)), "eec_train_head_backward")
+            launch("eec_train_head_backward", dev, x, W, logp, g, M, V, D, ctx.passes, dx, dW, db, scratch)
             scratch.record_stream(torch.cuda.current_stream(dev))
         return (None, dx, dW, db)
 
@@ -312,9 +300,8 @@ class _ExitHeadsFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             scratch = torch.empty((lib.eec_train_head_backward_scratch_floats(M, V, D),), dtype=torch.float32, device=dev)
             for e in range(E):  # log-softmax backward + the two GEMMs of a Linear's backward on the training GEMM (bf16x3)
-                _check(lib.eec_train_head_backward(taps[e].data_ptr(), ws[e].data_ptr(), out[e].data_ptr(), g[e].data_ptr(), M, V, D, 3,
-                                                   dtaps[e].data_ptr() if dtaps is not None else None, dW[e].data_ptr(), db[e].data_ptr(),
-                                                   scratch.data_ptr(), stream_ptr(dev)), "eec_train_head_backward")
+                launch("eec_train_head_backward", dev, taps[e], ws[e], out[e], g[e], M, V, D, 3, None if dtaps is None else dtaps[e], dW[e],
+                       db[e], scratch)
             scratch.record_stream(torch.cuda.current_stream(dev))
         return (None, dtaps, *dW, *db)
 
@@ -347,7 +334,7 @@ class _EncoderTrainFn(torch.autograd.Function):
                 if getattr(model, "_trainer", None) is not None:
                     lib.eec_trainer_destroy(model._trainer)
                 h = C.c_void_p()
-                _check(lib.eec_trainer_create(C.byref(cfg), C.byref(h)), "eec_trainer_create")
+                capi.call("eec_trainer_create", C.byref(cfg), C.byref(h))
                 model._trainer, model._trainer_device = h, dev
             tensors = dict(zip(names, params))
             for k, v in _named_tensors(model)[1]:  # what model.state_dict(keep_vars=True) holds, without walking the module tree again
@@ -363,10 +350,8 @@ class _EncoderTrainFn(torch.autograd.Function):
             out = torch.empty((E, B, Tq, V), dtype=torch.float32, device=dev)
             taps = torch.empty((E, B, Tq, D), dtype=torch.float32, device=dev) if want_taps else None
             bn = torch.empty((E * L, 2, D), dtype=torch.float32, device=dev)
-            _check(lib.eec_train_forward(model._trainer, C.byref(pst), src.data_ptr(), len_dev.data_ptr(), B, T,
-                                         int(model.train_passes), float(model.dropout), capi.new_seed(), out.data_ptr(),
-                                         taps.data_ptr() if want_taps else None, bn.data_ptr(), ws_ptr, nbytes, stream_ptr(dev)),
-                   "eec_train_forward")
+            launch("eec_train_forward", dev, model._trainer, C.byref(pst), src, len_dev, B, T, int(model.train_passes), float(model.dropout),
+                   capi.new_seed(), out, taps, bn, ws_ptr, nbytes)
             model._train_generation = getattr(model, "_train_generation", 0) + 1
             ctx.generation = model._train_generation
             _update_running_stats(model.conformer, bn, B * Tq)
@@ -384,7 +369,6 @@ class _EncoderTrainFn(torch.autograd.Function):
             raise RuntimeError("the trainer records one forward at a time: run backward before the next training forward")
         out, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         dev = out.device
-        lib = capi.load()
         g = torch.zeros_like(out) if g is None else g.contiguous().float()
         g_taps = g_taps.contiguous().float() if g_taps is not None else None
         with torch.cuda.device(dev):
@@ -424,9 +408,8 @@ class _EncoderTrainFn(torch.autograd.Function):
                         err.append(ex)
                 if any(early):
                     cb = capi.GROUP_DONE_FN(on_group)
-            _check(lib.eec_train_backward_ex(model._trainer, C.byref(pst), C.byref(gst), out.data_ptr(), g.data_ptr(),
-                                             g_taps.data_ptr() if g_taps is not None else None, ctx.ws_ptr, ctx.nbytes,
-                                             stream_ptr(dev), cb, None), "eec_train_backward")
+            launch("eec_train_backward_ex", dev, model._trainer, C.byref(pst), C.byref(gst), out, g, g_taps, ctx.ws_ptr, ctx.nbytes,
+                   cb, None)  # the stream goes in front of the callback
             if err:
                 raise err[0]
         ctx.ws = None

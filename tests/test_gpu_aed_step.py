@@ -133,3 +133,25 @@ def test_weight_domain_leaves_the_fp32_step_decoder_where_it_was():
     """Plain fp32 is scale-free short of its range: the per-utterance decoder's error at e = 8 may not exceed its error at e = 0
     by more than a quarter of the bound."""
     assert _weight_domain(8)[0] <= _weight_domain(0)[0] + 0.25
+
+
+def test_beam_select_refuses_a_half_precision_logp_before_any_launch():
+    """eec_beam_select reads ``logp`` as fp32 through its address: an fp16 tensor (half the bytes) is refused by the binding as a
+    Python exception, nothing is launched and the outputs stay untouched; with fp32 the launch equals the host path of the same
+    function.  n = 1, R = 2, V = 4, one step."""
+    import ctypes
+    from early_exit_transformer_amd.decoding import beam_select
+    logp = torch.tensor([[[-0.5, -2.0, -0.25, -3.0], [-1.0, -0.125, -4.0, -1.5]]])
+    scores = torch.tensor([[0.0, -0.75]])
+    old = torch.tensor([[[7, 0], [9, 0]]])
+    want_new = torch.full_like(old, -1)
+    want = beam_select(logp, scores, 1.0, 2, old, want_new, 1)  # CPU tensors: the host path
+    new = torch.full_like(old, -1).cuda()
+    with pytest.raises(ctypes.ArgumentError, match=r"argument 5: TypeError: expected a float tensor, got torch\.float16"):
+        beam_select(logp.cuda().half(), scores.cuda(), 1.0, 2, old.cuda(), new, 1)
+    torch.cuda.synchronize()
+    assert (new.cpu() == -1).all()
+    got = beam_select(logp.cuda(), scores.cuda(), 1.0, 2, old.cuda(), new, 1)
+    for g, w in zip(got, want):
+        assert torch.equal(g.cpu(), w)
+    assert want[2].tolist() == [[2, 0]] and want[1].tolist() == [[0, 0]] and torch.equal(new.cpu(), want_new)

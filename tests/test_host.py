@@ -32,6 +32,73 @@ def test_library_exports_every_declared_symbol(lib):
         assert hasattr(lib, name), f"{name} declared in include/eec.h but not exported by libeec.so"
     assert set(capi.EXPORTS) == declared
     assert lib.eec_abi_version() == 16
+    protos = _prototypes(header)
+    assert set(protos) == declared
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(lib, name)
+        got = list(fn.argtypes or [])
+        if _RESTYPES[ret] is None:
+            wrong += [f"{name}: restype {fn.restype} for void"] if fn.restype is not None else []
+        elif fn.restype is None or _kind(fn.restype) != _RESTYPES[ret]:
+            wrong.append(f"{name}: restype {fn.restype} for {ret}")
+        if len(got) != len(params):
+            wrong.append(f"{name}: {len(got)} argtypes for {len(params)} parameters")
+            continue
+        wrong += [f"{name}: argument {k + 1}, {decl}: {why}" for k, (decl, g) in enumerate(zip(params, got)) for why in [_mismatch(decl, g)] if why]
+    assert not wrong, "\n".join(wrong)
+
+
+_RESTYPES = {"int": (4, "int"), "size_t": (8, "uint"), "float": (4, "float"), "const char*": (8, "char*"), "void": None}
+_SCALARS = {"int": (4, "int"), "float": (4, "float"), "double": (8, "float"), "size_t": (8, "uint"), "int64_t": (8, "int"),
+            "uint64_t": (8, "uint"), "uint32_t": (4, "uint")}
+_ELEMS = {"float": "float", "double": "double", "int32_t": "int32_t", "int64_t": "int64_t", "long long": "int64_t", "uint8_t": "uint8_t",
+          "unsigned char": "uint8_t", "uint32_t": "uint32_t", "void": "void"}
+_STRUCTS = {"eec_config": capi.EecConfig, "eec_params": capi.EecParams, "eec_layer_params": capi.EecLayerParams,
+            "eec_decoder_params": capi.EecDecoderParams}
+
+
+def _prototypes(header):
+    """{entry: (return type, [parameter declarations])} of every prototype of include/eec.h."""
+    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    text = re.sub(r"enum\s*\{.*?\}\s*;", " ", text, flags=re.S)
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(eec_\w+)\s*\(([^;{}()]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in m.group(3).split(",")]
+        out[m.group(2)] = (" ".join(m.group(1).split()), [] if params == ["void"] else params)
+    return out
+
+
+def _kind(t):
+    """(bytes, kind) of a plain ctypes type."""
+    code = getattr(t, "_type_", None)
+    kind = {"f": "float", "d": "float", "i": "int", "l": "int", "q": "int", "I": "uint", "L": "uint", "Q": "uint", "z": "char*"}.get(code)
+    return (C.sizeof(t), kind)
+
+
+def _mismatch(decl, got):
+    """Why the ``argtypes`` entry ``got`` does not serve the parameter declared as ``decl`` (None: it does)."""
+    ctype, name = re.match(r"(.*?)(\w+)$", decl).groups()
+    ctype = ctype.replace("const", " ").strip()
+    stars, base = ctype.count("*"), " ".join(ctype.replace("*", " ").split())
+    plain_pointer = got is C.c_void_p or (isinstance(got, type) and issubclass(got, C._Pointer))
+    if stars == 0:
+        if base == "eec_group_done_fn":
+            return None if got is capi.GROUP_DONE_FN else f"{got} is not the callback type"
+        return None if isinstance(got, type) and issubclass(got, C._SimpleCData) and _kind(got) == _SCALARS[base] else f"{got} for a {base}"
+    if name == "stream" and ctype == "void*":
+        return None if got is capi.STREAM else f"{got} is not the stream marker"
+    if got is capi.STREAM:
+        return "the stream marker on a parameter that is no stream"
+    if stars == 1 and base in _ELEMS:
+        if isinstance(got, type) and issubclass(got, capi.TensorPtr):
+            return None if got.elem == _ELEMS[base] else f"a {got.elem} pointer type for a {base}*"
+        return None if base == "void" and got is C.c_void_p else f"{got} for a {base}*: no typed pointer"
+    if stars == 1 and base in _STRUCTS:
+        return None if got is C.POINTER(_STRUCTS[base]) else f"{got} for a {base}*"
+    return None if plain_pointer else f"{got} for {ctype}"  # opaque handles, arrays of pointers, structs the binding does not model
 
 
 def test_loading_the_library_first_keeps_one_hip_runtime_in_the_process(lib):

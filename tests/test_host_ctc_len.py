@@ -94,7 +94,7 @@ def test_new_entries_are_declared_and_exported():
                             ("eec_ctc_loss_backward_len", "eec_ctc_loss_backward", 3), ("eec_greedy_ctc_len", "eec_greedy_ctc", 1),
                             ("eec_ctc_beam_decode_len", "eec_ctc_beam_decode_ex", 1)):
         a, b = list(getattr(lib, name).argtypes), list(getattr(lib, base).argtypes)
-        assert a[:pos] + a[pos + 1:] == b and a[pos] is capi.C.c_void_p, name
+        assert a[:pos] + a[pos + 1:] == b and a[pos] is capi.I32, name  # the typed device pointer of a const int32_t*
     assert lib.eec_abi_version() == 16
 
 
