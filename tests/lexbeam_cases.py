@@ -1,7 +1,9 @@
-"""Test-side statement of the lexicon-constrained CTC beam search (include/eec.h, csrc/ctc_lexbeam.hip): the search itself in
-plain Python with ``np.float32`` scores added in the written order and tuples for word histories, a reader of the packed trie
-image's documented layout, and the generators of the test cases.  Nothing in the arithmetic is a reduction or a transcendental, so
-comparisons against the statement are exact: scores bit for bit, words, tokens and timesteps as integers."""
+"""Test side of the lexicon-constrained CTC beam search (include/eec.h, csrc/ctc_lexbeam.hip): the trie and the hypothesis that the
+plain-Python statement of the search (tests/lexbeam_statement.py) walks, a reader of the packed trie image's documented layout, the
+lexica and the generators of the test cases.  The search adds ``np.float32`` scores in the written order -- nothing in it is a
+reduction or a transcendental --, so comparisons against the statement are exact: scores bit for bit, words, tokens and timesteps
+as integers."""
+import functools
 import json
 import os
 
@@ -51,91 +53,6 @@ class Hyp:
     def __init__(self, node, tok, pb, hist, score, parent=None, label=-1, word=-1):
         self.node, self.tok, self.pb, self.hist, self.score = node, tok, pb, hist, score
         self.parent, self.label, self.word = parent, label, word  # the back-pointer: previous hypothesis, this frame's label, completed word
-
-
-def decode(e, trie, beam=10, nbest=1, word_score=0.0, sil_score=0.0, beam_threshold=50.0, length=None):
-    """The statement for ONE sequence: ``e`` [T', V] float32 log-probs, ``length`` frames of it (None: all).  Returns the list
-    of at most ``nbest`` complete hypotheses, best first, each ``(words, tokens, timesteps, score)``: word indices, the collapsed
-    label sequence, the first frame of each label, the np.float32 score.  An empty list: no complete hypothesis, a length outside
-    [1, T'], or a frame that left no candidate."""
-    e = np.asarray(e)
-    assert e.dtype == np.float32
-    T = e.shape[0] if length is None else int(length)
-    if T < 1 or T > e.shape[0]:
-        return []
-    blank, sil = trie.blank, trie.sil
-    word_score, sil_score = F32(word_score), F32(sil_score)
-    hyps = [Hyp(0, -1, True, (), F32(0.0))]
-    with np.errstate(all="ignore"):
-        for t in range(T):
-            row = e[t]
-            cands = {}  # (node, tok, pb, hist) -> [score, id, parent, word]
-
-            def offer(node, tok, pb, hist, score, c, w, i, word=-1):
-                if not score > NEG_INF:  # -inf and NaN are dropped
-                    return
-                cid = (2 * c + w) * 16 + i
-                key = (node, tok, pb, hist)
-                old = cands.get(key)
-                if old is None or score > old[0] or (score == old[0] and cid < old[1]):
-                    cands[key] = [score, cid, hyps[i], word]
-
-            for i, h in enumerate(hyps):
-                offer(h.node, blank, True, h.hist, h.score + row[blank], blank, 0, i)
-                if not h.pb and h.tok >= 0:
-                    s = h.score + row[h.tok]
-                    if h.tok == sil:
-                        s = s + sil_score
-                    offer(h.node, h.tok, False, h.hist, s, h.tok, 0, i)
-                ktok = trie.ktok[h.node]
-                if len(ktok):
-                    inword = h.score + row[ktok]       # fp32 vector: element k is score + e[c_k]
-                    ended = inword + word_score        # (score + e[c]) + word_score
-                    for c, y, s_in, s_end in zip(ktok.tolist(), trie.knode[h.node], inword, ended):
-                        if c == h.tok and not h.pb:
-                            continue
-                        if trie.kids[y]:
-                            offer(y, c, False, h.hist, s_in, c, 0, i)
-                        if trie.word[y] >= 0:
-                            offer(0, c, False, h.hist + (trie.word[y],), s_end, c, 1, i, trie.word[y])
-                if h.node == 0 and sil >= 0 and (sil != h.tok or h.pb):
-                    offer(0, sil, False, h.hist, (h.score + row[sil]) + sil_score, sil, 0, i)
-
-            if not cands:
-                return []
-            best = max(v[0] for v in cands.values())
-            keep = list(cands.items())
-            if np.isfinite(F32(beam_threshold)):
-                thr = F32(best - F32(beam_threshold))
-                keep = [kv for kv in keep if kv[1][0] >= thr]
-            keep.sort(key=lambda kv: (-float(kv[1][0]), kv[1][1]))
-            hyps = [Hyp(k[0], k[1], k[2], k[3], v[0], v[2], k[1], v[3]) for k, v in keep[:beam]]
-            if not hyps:
-                return []
-    out = []
-    for h in hyps:  # rank order is score order: the complete ones in it are best first
-        if h.node != 0 or len(out) == nbest:
-            continue
-        labels, words, at = [], [], h
-        while at.parent is not None:
-            labels.append(at.label)
-            if at.word >= 0:
-                words.append(at.word)
-            at = at.parent
-        labels.reverse()
-        words.reverse()
-        assert tuple(words) == h.hist and len(labels) == T
-        tokens, steps = [], []
-        for t, c in enumerate(labels):
-            if c != blank and (t == 0 or labels[t - 1] != c):
-                tokens.append(c)
-                steps.append(t)
-        out.append((words, tokens, steps, h.score))
-    return out
-
-
-def decode_batch(em, trie, em_len=None, **kw):
-    return [decode(em[s], trie, length=None if em_len is None else em_len[s], **kw) for s in range(len(em))]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -210,6 +127,16 @@ def wide_lexicon(V=256, blank=0, sil=126, seed=3):
     out += [[hub, c, d] for c in second[:20] for d in rng.permutation(toks)[:3].tolist()]
     out += [[c, int(rng.choice(toks))] for c in first[50:150]]        # words whose prefix is a word (50..99) or not (100..149)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def lexicon(name):
+    """(spellings, V, sil or None, words) of ``fixture``, ``fixture+sil``, ``one``, ``prefix`` or ``wide``"""
+    if name.startswith("fixture"):
+        _, words, spellings = load_fixture()
+        return spellings, 256, (126 if name == "fixture+sil" else None), words
+    spellings, V, sil = {"one": (ONE_WORD, 40, None), "prefix": (PREFIX_DOUBLED, 32, None), "wide": (wide_lexicon(), 256, 126)}[name]
+    return spellings, V, sil, [f"w{i}" for i in range(len(spellings))]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1,12 +1,11 @@
-"""Test-side statement of the lexicon-constrained CTC beam search WITH a back-off n-gram word model (include/eec.h,
-csrc/ctc_lexbeam.hip): the search of tests/lexbeam_cases.py again, in plain Python with ``np.float32`` operations in the written
-order, extended by the model's score at every word end and its end-of-sentence term.  The model is a dict ``{word tuple: (logp,
-backoff)}`` of np.float32 values and the LM state is the word history itself.  Also here: a generator of random models over a
-lexicon, a writer of ARPA text, a reader of the packed n-gram image by its documented layout, and the emissions of the LM cases.
-With ``lm=None`` ``decode`` is the statement of lexbeam_cases, which stays the judge of the model-free search."""
+"""Test side of the lexicon-constrained CTC beam search WITH a back-off n-gram word model (include/eec.h, csrc/ctc_lexbeam.hip):
+the model's score, which the statement of the search (tests/lexbeam_statement.py) adds at every word end and as the end-of-sentence
+term, in plain Python with ``np.float32`` operations in the written order.  The model is a dict ``{word tuple: (logp, backoff)}``
+of np.float32 values and the LM state is the word history itself.  Also here: a generator of random models over a lexicon, a writer
+of ARPA text, a reader of the packed n-gram image by its documented layout, and the emissions of the LM cases."""
 import numpy as np
 
-from lexbeam_cases import F32, NEG_INF, Hyp, Trie, emissions, load_fixture, log_softmax, tie_emissions  # noqa: F401
+from lexbeam_cases import F32, load_fixture, log_softmax
 
 LM_MAGIC = 0x4E434545
 BOS, EOS, UNK = "<s>", "</s>", "<unk>"
@@ -56,112 +55,6 @@ def textbook(lm, ctx, v):
         return float(hit[0])
     assert ctx
     return (float(lm[ctx][1]) if ctx in lm else 0.0) + textbook(lm, ctx[1:], v)
-
-
-# ----------------------------------------------------------------------------------------------------------------------------
-# the search
-# ----------------------------------------------------------------------------------------------------------------------------
-def decode(e, trie, beam=10, nbest=1, word_score=0.0, sil_score=0.0, beam_threshold=50.0, length=None, lm=None, lm_weight=0.0,
-           lm_words=None, stats=None):
-    """The statement for ONE sequence, as ``lexbeam_cases.decode``; ``lm``: None or the model dict, ``lm_words[w]`` the string of
-    lexicon word w (None: ``"w<index>"``, the names ``TokenTrie.from_spellings`` gives).  ``stats`` (a dict) collects the back-off
-    depths taken, the (context, word) pairs asked for and whether the </s> term changed the order of the complete hypotheses."""
-    e = np.asarray(e)
-    assert e.dtype == np.float32
-    T = e.shape[0] if length is None else int(length)
-    if T < 1 or T > e.shape[0]:
-        return []
-    blank, sil = trie.blank, trie.sil
-    word_score, sil_score, lm_weight = F32(word_score), F32(sil_score), F32(lm_weight)
-    if lm is not None:
-        order = model_order(lm)
-        if lm_words is None:
-            lm_words = [f"w{w}" for w in range(max(trie.word) + 1)]
-    hyps = [Hyp(0, -1, True, (), F32(0.0))]
-    with np.errstate(all="ignore"):
-        for t in range(T):
-            row = e[t]
-            cands = {}  # (node, tok, pb, hist) -> [score, id, parent, word]
-
-            def offer(node, tok, pb, hist, score, c, w, i, word=-1):
-                if not score > NEG_INF:  # -inf and NaN are dropped
-                    return
-                cid = (2 * c + w) * 16 + i
-                key = (node, tok, pb, hist)
-                old = cands.get(key)
-                if old is None or score > old[0] or (score == old[0] and cid < old[1]):
-                    cands[key] = [score, cid, hyps[i], word]
-
-            for i, h in enumerate(hyps):
-                offer(h.node, blank, True, h.hist, h.score + row[blank], blank, 0, i)
-                if not h.pb and h.tok >= 0:
-                    s = h.score + row[h.tok]
-                    if h.tok == sil:
-                        s = s + sil_score
-                    offer(h.node, h.tok, False, h.hist, s, h.tok, 0, i)
-                ktok = trie.ktok[h.node]
-                if len(ktok):
-                    inword = h.score + row[ktok]       # fp32 vector: element k is score + e[c_k]
-                    ended = inword + word_score        # (score + e[c]) + word_score
-                    names = None
-                    for c, y, s_in, s_end in zip(ktok.tolist(), trie.knode[h.node], inword, ended):
-                        if c == h.tok and not h.pb:
-                            continue
-                        if trie.kids[y]:
-                            offer(y, c, False, h.hist, s_in, c, 0, i)
-                        wd = trie.word[y]
-                        if wd >= 0:
-                            if lm is not None:
-                                if names is None:
-                                    names = lm_names(lm, h.hist, lm_words)
-                                v = lm_words[wd] if (lm_words[wd],) in lm else UNK
-                                acc = lm_score(lm, order, names, v, stats)
-                                s_end = F32(s_end + F32(lm_weight * acc))  # the product is rounded on its own, then added
-                            offer(0, c, False, h.hist + (wd,), s_end, c, 1, i, wd)
-                if h.node == 0 and sil >= 0 and (sil != h.tok or h.pb):
-                    offer(0, sil, False, h.hist, (h.score + row[sil]) + sil_score, sil, 0, i)
-
-            if not cands:
-                return []
-            best = max(v[0] for v in cands.values())
-            keep = list(cands.items())
-            if np.isfinite(F32(beam_threshold)):
-                thr = F32(best - F32(beam_threshold))
-                keep = [kv for kv in keep if kv[1][0] >= thr]
-            keep.sort(key=lambda kv: (-float(kv[1][0]), kv[1][1]))
-            hyps = [Hyp(k[0], k[1], k[2], k[3], v[0], v[2], k[1], v[3]) for k, v in keep[:beam]]
-            if not hyps:
-                return []
-        # the complete hypotheses in rank order; with a model that has </s>, its term and a new order: (final score descending, rank)
-        done = [(h.score, r, h) for r, h in enumerate(hyps) if h.node == 0]
-        if lm is not None and (EOS,) in lm:
-            done = [(F32(s + F32(lm_weight * lm_score(lm, order, lm_names(lm, h.hist, lm_words), EOS, stats))), r, h) for s, r, h in done]
-            ranked = sorted(done, key=lambda d: (-float(d[0]), d[1]))
-            if stats is not None and [d[1] for d in ranked] != [d[1] for d in done]:
-                stats["eos_reordered"] = stats.get("eos_reordered", 0) + 1
-            done = ranked
-    out = []
-    for score, _, h in done[:nbest]:
-        labels, words, at = [], [], h
-        while at.parent is not None:
-            labels.append(at.label)
-            if at.word >= 0:
-                words.append(at.word)
-            at = at.parent
-        labels.reverse()
-        words.reverse()
-        assert tuple(words) == h.hist and len(labels) == T
-        tokens, steps = [], []
-        for t, c in enumerate(labels):
-            if c != blank and (t == 0 or labels[t - 1] != c):
-                tokens.append(c)
-                steps.append(t)
-        out.append((words, tokens, steps, score))
-    return out
-
-
-def decode_batch(em, trie, em_len=None, **kw):
-    return [decode(em[s], trie, length=None if em_len is None else em_len[s], **kw) for s in range(len(em))]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1,18 +1,11 @@
-"""Test-side statement of the lexicon-constrained CTC beam search with LOG-ADD merging (include/eec.h, csrc/ctc_lexbeam.hip,
-eec_ctc_lexbeam_logadd_decode): tries, emissions, models and smear tables are those of tests/lexbeam_cases.py, lexbeam_lm_cases.py
-and lexbeam_smear_cases.py; the candidates are generated by the rules of lexbeam_smear_cases.decode (which, with ``smax=None`` and
-``lm=None``, are the other two modules' rules).  What is restated here is the merge -- the members of a group folded in the stated
-pair order -- and ``log_add``, the stated sequence of fp32 operations, in ``np.float32``: every step is an exactly rounded IEEE
-operation, so comparisons against this statement stay exact, scores bit for bit.  With ``log_add=False`` ``decode`` is the Viterbi
-statement of the three modules, which stay the judges of the Viterbi entries.  Also here: the CTC forward log-likelihood in float64,
-the oracle that is independent of any beam search."""
+"""Test side of LOG-ADD merging in the lexicon-constrained CTC beam search (include/eec.h, csrc/ctc_lexbeam.hip,
+eec_ctc_lexbeam_logadd_decode): the merge -- the members of a group folded in the stated pair order -- and ``log_add``, the stated
+sequence of fp32 operations, in ``np.float32``: every step is an exactly rounded IEEE operation, so comparisons against the
+statement of the search (tests/lexbeam_statement.py, which calls ``fold`` under ``log_add=True``) stay exact, scores bit for bit.
+Also here: the CTC forward log-likelihood in float64, the oracle that is independent of any beam search."""
 import numpy as np
 
-import lexbeam_cases as L  # noqa: F401
-import lexbeam_lm_cases as M  # noqa: F401
-import lexbeam_smear_cases as S  # noqa: F401
-from lexbeam_cases import F32, NEG_INF, Hyp, Trie  # noqa: F401
-from lexbeam_lm_cases import EOS, UNK, lm_names, lm_score, model_order
+from lexbeam_cases import F32
 
 # ----------------------------------------------------------------------------------------------------------------------------
 # log_add: the constants and the order of include/eec.h
@@ -129,118 +122,6 @@ def fold(members, stats=None):
                 acc[p], alive[q] = total, False
     (k,) = [i for i, v in enumerate(alive) if v]
     return k, acc[k]
-
-
-def decode(e, trie, beam=10, nbest=1, word_score=0.0, sil_score=0.0, beam_threshold=50.0, length=None, lm=None, lm_weight=0.0,
-           lm_words=None, stats=None, smax=None, log_add=True):
-    """The statement for ONE sequence, as ``lexbeam_smear_cases.decode`` (same arguments, same return).  ``log_add``: True -- the
-    survivor of a group scores the fold of its members -- or False: the Viterbi merge.  ``stats`` also counts ``merges`` (pairs
-    folded), ``equal_merges`` (of those, pairs whose accumulators were equal: d = 0) and ``max_alive`` (hypotheses after a frame)."""
-    e = np.asarray(e)
-    assert e.dtype == np.float32
-    assert smax is None or lm is not None, "smearing needs a model"
-    T = e.shape[0] if length is None else int(length)
-    if T < 1 or T > e.shape[0]:
-        return []
-    blank, sil = trie.blank, trie.sil
-    word_score, sil_score, lm_weight = F32(word_score), F32(sil_score), F32(lm_weight)
-    if lm is not None:
-        order = model_order(lm)
-        if lm_words is None:
-            lm_words = S.default_words(trie)
-    hyps = [Hyp(0, -1, True, (), F32(0.0))]
-    with np.errstate(all="ignore"):
-        for t in range(T):
-            row = e[t]
-            groups = {}  # (node, tok, pb, hist) -> [(score, id, parent, word)]
-
-            def offer(node, tok, pb, hist, score, c, w, i, word=-1):
-                if not score > NEG_INF:  # -inf and NaN are dropped, before merging
-                    return
-                groups.setdefault((node, tok, pb, hist), []).append((score, (2 * c + w) * 16 + i, hyps[i], word))
-
-            for i, h in enumerate(hyps):
-                offer(h.node, blank, True, h.hist, h.score + row[blank], blank, 0, i)
-                if not h.pb and h.tok >= 0:
-                    s = h.score + row[h.tok]
-                    if h.tok == sil:
-                        s = s + sil_score
-                    offer(h.node, h.tok, False, h.hist, s, h.tok, 0, i)
-                ktok = trie.ktok[h.node]
-                if len(ktok):
-                    inword = h.score + row[ktok]       # fp32 vector: element k is score + e[c_k]
-                    ended = inword + word_score        # (score + e[c]) + word_score
-                    names = None
-                    pmax = None if smax is None else F32(smax[h.node])
-                    for c, y, s_in, s_end in zip(ktok.tolist(), trie.knode[h.node], inword, ended):
-                        if c == h.tok and not h.pb:
-                            continue
-                        if trie.kids[y]:
-                            if smax is not None:
-                                s_in = F32(s_in + F32(lm_weight * F32(F32(smax[y]) - pmax)))
-                            offer(y, c, False, h.hist, s_in, c, 0, i)
-                        wd = trie.word[y]
-                        if wd >= 0:
-                            if lm is not None:
-                                if names is None:
-                                    names = lm_names(lm, h.hist, lm_words)
-                                v = lm_words[wd] if (lm_words[wd],) in lm else UNK
-                                acc = lm_score(lm, order, names, v, stats)
-                                if smax is not None:
-                                    acc = F32(acc - pmax)
-                                s_end = F32(s_end + F32(lm_weight * acc))
-                            offer(0, c, False, h.hist + (wd,), s_end, c, 1, i, wd)
-                if h.node == 0 and sil >= 0 and (sil != h.tok or h.pb):
-                    offer(0, sil, False, h.hist, (h.score + row[sil]) + sil_score, sil, 0, i)
-
-            if not groups:
-                return []
-            cands = {}  # key -> [score, id, parent, word]
-            for key, members in groups.items():
-                members.sort(key=lambda m: m[1])
-                if log_add:
-                    k, merged = fold(members, stats)
-                else:  # the higher score survives, the lower id on equal scores
-                    k = min(range(len(members)), key=lambda j: (-float(members[j][0]), members[j][1]))
-                    merged = members[k][0]
-                cands[key] = [merged, members[k][1], members[k][2], members[k][3]]
-            best = max(v[0] for v in cands.values())
-            keep = list(cands.items())
-            if np.isfinite(F32(beam_threshold)):
-                thr = F32(best - F32(beam_threshold))
-                keep = [kv for kv in keep if kv[1][0] >= thr]
-            keep.sort(key=lambda kv: (-float(kv[1][0]), kv[1][1]))
-            hyps = [Hyp(k[0], k[1], k[2], k[3], v[0], v[2], k[1], v[3]) for k, v in keep[:beam]]
-            if stats is not None:
-                stats["max_alive"] = max(stats.get("max_alive", 0), len(keep))
-            if not hyps:
-                return []
-        done = [(h.score, r, h) for r, h in enumerate(hyps) if h.node == 0]
-        if lm is not None and (EOS,) in lm:
-            done = [(F32(s + F32(lm_weight * lm_score(lm, order, lm_names(lm, h.hist, lm_words), EOS, stats))), r, h) for s, r, h in done]
-            done = sorted(done, key=lambda d: (-float(d[0]), d[1]))
-    out = []
-    for score, _, h in done[:nbest]:
-        labels, words, at = [], [], h
-        while at.parent is not None:
-            labels.append(at.label)
-            if at.word >= 0:
-                words.append(at.word)
-            at = at.parent
-        labels.reverse()
-        words.reverse()
-        assert tuple(words) == h.hist and len(labels) == T
-        tokens, steps = [], []
-        for t, c in enumerate(labels):
-            if c != blank and (t == 0 or labels[t - 1] != c):
-                tokens.append(c)
-                steps.append(t)
-        out.append((words, tokens, steps, score))
-    return out
-
-
-def decode_batch(em, trie, em_len=None, **kw):
-    return [decode(em[s], trie, length=None if em_len is None else em_len[s], **kw) for s in range(len(em))]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

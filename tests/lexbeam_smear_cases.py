@@ -1,14 +1,13 @@
-"""Test-side statement of the lexicon-constrained CTC beam search with an n-gram word model AND LM look-ahead by max trie smearing
-(include/eec.h, csrc/ctc_lexbeam.hip): the search of tests/lexbeam_lm_cases.py again, in plain Python with ``np.float32``
-operations in the written order, with the two child rules that smearing changes.  Also here: the smear table itself (every node
-carries the maximum, over the words at or below it, of the model's score for the word from the start state), a reader of the packed
-table by its documented layout, and the cases of the pruning and telescoping tests.  With ``smax=None`` ``decode`` is the statement
-of lexbeam_lm_cases, which stays the judge of the unsmeared search."""
+"""Test side of LM look-ahead by max trie smearing in the lexicon-constrained CTC beam search (include/eec.h,
+csrc/ctc_lexbeam.hip): the smear table itself (every node carries the maximum, over the words at or below it, of the model's score
+for the word from the start state) in plain Python with ``np.float32`` operations in the written order, a reader of the packed
+table by its documented layout, and the cases of the pruning and telescoping tests.  The two child rules that smearing changes are
+in the statement of the search (tests/lexbeam_statement.py, ``smax=``)."""
 import numpy as np
 
 import lexbeam_lm_cases as M
-from lexbeam_cases import F32, MAGIC, NEG_INF, Hyp, Trie  # noqa: F401
-from lexbeam_lm_cases import BOS, EOS, UNK, lm_names, lm_score, model_order  # noqa: F401
+from lexbeam_cases import F32, MAGIC, NEG_INF
+from lexbeam_lm_cases import BOS, EOS, UNK, lm_names, lm_score, model_order
 
 SMEAR_MAGIC = 0x53434545  # "EECS"
 SMEAR_HEADER = 4
@@ -94,123 +93,6 @@ def table_in_image_order(trie, smax, image):
     """The statement's table as the bit patterns the packed table must hold: ``smax`` re-indexed by the image's node numbers."""
     node_of = {sp: n for n, sp in enumerate(statement_spellings(trie))}
     return [M.bits(smax[node_of[sp]]) for sp in image_spellings(image)]
-
-
-# ----------------------------------------------------------------------------------------------------------------------------
-# the search
-# ----------------------------------------------------------------------------------------------------------------------------
-def decode(e, trie, beam=10, nbest=1, word_score=0.0, sil_score=0.0, beam_threshold=50.0, length=None, lm=None, lm_weight=0.0,
-           lm_words=None, stats=None, smax=None):
-    """The statement for ONE sequence, as ``lexbeam_lm_cases.decode``; ``smax``: None, or the table of ``smear`` for this trie and
-    model -- then, with ``pmax = smax[node]`` of the hypothesis (0 at the root),
-        child, in-word (c -> y)    (score + e[c]) + lm_weight * (smax[y] - pmax)
-        child, word end (y: wd)    ((score + e[c]) + word_score) + lm_weight * (acc - pmax)
-    the difference rounded, the product rounded on its own, then added.  ``stats["max_candidates"]``: the largest number of
-    candidates (after merging, before pruning) any frame had."""
-    e = np.asarray(e)
-    assert e.dtype == np.float32
-    assert smax is None or lm is not None, "smearing needs a model"
-    T = e.shape[0] if length is None else int(length)
-    if T < 1 or T > e.shape[0]:
-        return []
-    blank, sil = trie.blank, trie.sil
-    word_score, sil_score, lm_weight = F32(word_score), F32(sil_score), F32(lm_weight)
-    if lm is not None:
-        order = model_order(lm)
-        if lm_words is None:
-            lm_words = default_words(trie)
-    hyps = [Hyp(0, -1, True, (), F32(0.0))]
-    with np.errstate(all="ignore"):
-        for t in range(T):
-            row = e[t]
-            cands = {}  # (node, tok, pb, hist) -> [score, id, parent, word]
-
-            def offer(node, tok, pb, hist, score, c, w, i, word=-1):
-                if not score > NEG_INF:  # -inf and NaN are dropped
-                    return
-                cid = (2 * c + w) * 16 + i
-                key = (node, tok, pb, hist)
-                old = cands.get(key)
-                if old is None or score > old[0] or (score == old[0] and cid < old[1]):
-                    cands[key] = [score, cid, hyps[i], word]
-
-            for i, h in enumerate(hyps):
-                offer(h.node, blank, True, h.hist, h.score + row[blank], blank, 0, i)
-                if not h.pb and h.tok >= 0:
-                    s = h.score + row[h.tok]
-                    if h.tok == sil:
-                        s = s + sil_score
-                    offer(h.node, h.tok, False, h.hist, s, h.tok, 0, i)
-                ktok = trie.ktok[h.node]
-                if len(ktok):
-                    inword = h.score + row[ktok]       # fp32 vector: element k is score + e[c_k]
-                    ended = inword + word_score        # (score + e[c]) + word_score
-                    names = None
-                    pmax = None if smax is None else F32(smax[h.node])
-                    for c, y, s_in, s_end in zip(ktok.tolist(), trie.knode[h.node], inword, ended):
-                        if c == h.tok and not h.pb:
-                            continue
-                        if trie.kids[y]:
-                            if smax is not None:
-                                s_in = F32(s_in + F32(lm_weight * F32(F32(smax[y]) - pmax)))
-                            offer(y, c, False, h.hist, s_in, c, 0, i)
-                        wd = trie.word[y]
-                        if wd >= 0:
-                            if lm is not None:
-                                if names is None:
-                                    names = lm_names(lm, h.hist, lm_words)
-                                v = lm_words[wd] if (lm_words[wd],) in lm else UNK
-                                acc = lm_score(lm, order, names, v, stats)
-                                if smax is not None:
-                                    acc = F32(acc - pmax)  # the advance payment is taken back: the difference is rounded
-                                s_end = F32(s_end + F32(lm_weight * acc))  # the product is rounded on its own, then added
-                            offer(0, c, False, h.hist + (wd,), s_end, c, 1, i, wd)
-                if h.node == 0 and sil >= 0 and (sil != h.tok or h.pb):
-                    offer(0, sil, False, h.hist, (h.score + row[sil]) + sil_score, sil, 0, i)
-
-            if not cands:
-                return []
-            if stats is not None:
-                stats["max_candidates"] = max(stats.get("max_candidates", 0), len(cands))
-            best = max(v[0] for v in cands.values())
-            keep = list(cands.items())
-            if np.isfinite(F32(beam_threshold)):
-                thr = F32(best - F32(beam_threshold))
-                keep = [kv for kv in keep if kv[1][0] >= thr]
-            keep.sort(key=lambda kv: (-float(kv[1][0]), kv[1][1]))
-            hyps = [Hyp(k[0], k[1], k[2], k[3], v[0], v[2], k[1], v[3]) for k, v in keep[:beam]]
-            if not hyps:
-                return []
-        # the complete hypotheses in rank order; with a model that has </s>, its term and a new order: (final score descending, rank)
-        done = [(h.score, r, h) for r, h in enumerate(hyps) if h.node == 0]
-        if lm is not None and (EOS,) in lm:
-            done = [(F32(s + F32(lm_weight * lm_score(lm, order, lm_names(lm, h.hist, lm_words), EOS, stats))), r, h) for s, r, h in done]
-            ranked = sorted(done, key=lambda d: (-float(d[0]), d[1]))
-            if stats is not None and [d[1] for d in ranked] != [d[1] for d in done]:
-                stats["eos_reordered"] = stats.get("eos_reordered", 0) + 1
-            done = ranked
-    out = []
-    for score, _, h in done[:nbest]:
-        labels, words, at = [], [], h
-        while at.parent is not None:
-            labels.append(at.label)
-            if at.word >= 0:
-                words.append(at.word)
-            at = at.parent
-        labels.reverse()
-        words.reverse()
-        assert tuple(words) == h.hist and len(labels) == T
-        tokens, steps = [], []
-        for t, c in enumerate(labels):
-            if c != blank and (t == 0 or labels[t - 1] != c):
-                tokens.append(c)
-                steps.append(t)
-        out.append((words, tokens, steps, score))
-    return out
-
-
-def decode_batch(em, trie, em_len=None, **kw):
-    return [decode(em[s], trie, length=None if em_len is None else em_len[s], **kw) for s in range(len(em))]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,7 @@
 """GPU tests of the lexicon-constrained CTC beam search (csrc/ctc_lexbeam.hip, ``ctc_lexicon_decode``, ``BeamInference.ctc_predict``)
-against the plain-Python statement of tests/lexbeam_cases.py.  There is nothing to tolerate: the arithmetic is fp32 additions in a
-stated order, so n_hyp, words, tokens, timesteps and counts are compared as integers and scores as bit patterns.  Lexica come from
-the fixture tests/golden/bpe256_lexicon_slice.json and from the small hand-made ones of the case module."""
-import ctypes as C
+against the plain-Python statement of tests/lexbeam_statement.py.  There is nothing to tolerate: the arithmetic is fp32 additions in
+a stated order, so n_hyp, words, tokens, timesteps and counts are compared as integers and scores as bit patterns.  Lexica come from
+the fixture tests/golden/bpe256_lexicon_slice.json and from the small hand-made ones of tests/lexbeam_cases.py."""
 import functools
 
 import numpy as np
@@ -10,61 +9,21 @@ import pytest
 import torch
 
 import lexbeam_cases as L
+import lexbeam_statement as D
 from early_exit_transformer_amd import capi
 from early_exit_transformer_amd.beam import BeamInference
 from early_exit_transformer_amd.lexicon import TokenTrie
 from early_exit_transformer_amd.model import ctc_lexicon_decode
+from lexbeam_helpers import captured_nodes, lexicon, raw_buffers, raw_call, run, same, tries
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
 
 
 @functools.lru_cache(maxsize=None)
-def lexicon(name):
-    """(spellings, V, sil or None, words or None)"""
-    if name.startswith("fixture"):
-        _, words, spellings = L.load_fixture()
-        return spellings, 256, (126 if name == "fixture+sil" else None), words
-    return {"one": (L.ONE_WORD, 40, None, None), "prefix": (L.PREFIX_DOUBLED, 32, None, None),
-            "wide": (L.wide_lexicon(), 256, 126, None)}[name]
-
-
-@functools.lru_cache(maxsize=None)
-def tries(name):
-    """(the statement's trie, the packed one)"""
-    spellings, V, sil, words = lexicon(name)
-    return L.Trie(spellings, V, 0, sil), TokenTrie.from_spellings(spellings, V, blank=0, sil=sil, words=words)
-
-
-def run(em, packed, em_len=None, **kw):
-    out = ctc_lexicon_decode(torch.from_numpy(em).cuda(), packed, em_len=None if em_len is None else torch.from_numpy(np.asarray(em_len, dtype=np.int32)),
-                             **kw)
-    return [o.cpu().numpy() for o in out]
-
-
-def same(got, want, nbest, max_words=None):
-    """Every output of a batch against the statement's hypothesis lists; returns n_hyp."""
-    words, wc, toks, tc, ts, sc, nh = got
-    assert nh.tolist() == [len(w) for w in want]
-    for s, hyps in enumerate(want):
-        for j in range(nbest):
-            if j >= len(hyps):
-                assert wc[s, j] == 0 and tc[s, j] == 0 and sc[s, j] == -np.inf, (s, j)
-                assert (words[s, j] == -1).all() and (toks[s, j] == -1).all() and (ts[s, j] == -1).all(), (s, j)
-                continue
-            w, tk, st, score = hyps[j]
-            kept = len(w) if max_words is None else min(len(w), max_words)
-            assert wc[s, j] == len(w) and words[s, j, :kept].tolist() == w[:kept] and (words[s, j, kept:] == -1).all(), (s, j)
-            assert tc[s, j] == len(tk) and toks[s, j, :len(tk)].tolist() == tk and ts[s, j, :len(tk)].tolist() == st, (s, j)
-            assert (toks[s, j, len(tk):] == -1).all() and (ts[s, j, len(tk):] == -1).all(), (s, j)
-            assert sc[s, j].view(np.int32) == np.float32(score).view(np.int32), (s, j, sc[s, j], score)
-    return nh
-
-
-@functools.lru_cache(maxsize=None)
 def main_reference():
     em, em_len, spellings, _ = L.main_case()
-    return em, em_len, L.decode_batch(em, tries("fixture+sil")[0], em_len, beam=10, nbest=10)
+    return em, em_len, D.decode_batch(em, tries("fixture+sil")[0], em_len, beam=10, nbest=10)
 
 
 def test_the_main_case_has_both_outcomes_and_equals_the_statement():
@@ -102,7 +61,7 @@ def test_shapes_lexica_and_options_equal_the_statement(name, n, T, beam, nbest, 
     if n == 70:
         em_len = np.random.default_rng(T).integers(0, T + 2, size=n).astype(np.int32)  # 0 and T' + 1 included
         em_len[:2] = [1, T]
-    want = L.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, **opts)
+    want = D.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, **opts)
     same(run(em, packed, em_len, beam_size=beam, nbest=nbest, **opts), want, nbest)
 
 
@@ -113,7 +72,7 @@ def test_ties_are_decided_by_the_candidate_id(name, n, T, beam):
     spellings, V, sil, _ = lexicon(name)
     ref, packed = tries(name)
     em = L.tie_emissions(7, spellings, n, T, V, 0, -1 if sil is None else sil)
-    want = L.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF)
+    want = D.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF)
     nh = same(run(em, packed, beam_size=beam, nbest=beam, beam_threshold=INF), want, beam)
     if name == "prefix":  # the small lexicon keeps hypotheses alive through the uniform frames: equal scores reach the end
         scores = [float(h[3]) for hyps in want for h in hyps]
@@ -131,7 +90,7 @@ def test_minus_infinity_and_nan_follow_the_drop_rule():
     clean = em.copy()
     em[1][rng.random(em[1].shape) < 0.1] = np.nan
     em[2, 5, :] = np.nan
-    want = L.decode_batch(em, ref, beam=10, nbest=10)
+    want = D.decode_batch(em, ref, beam=10, nbest=10)
     assert want[2] == [] and any(want[s] for s in (0, 3, 4, 5))
     got = run(em, packed, beam_size=10, nbest=10)
     same(got, want, 10)
@@ -182,7 +141,7 @@ def test_beam_inference_ctc_predict():
     em, _, spellings, words = L.main_case()
     ref, packed = tries("fixture+sil")
     em = em[40:56]  # full-length sequences
-    want = L.decode_batch(em, ref, beam=10, nbest=4)
+    want = D.decode_batch(em, ref, beam=10, nbest=4)
     assert any(want) and not all(want)
 
     class Args:
@@ -208,44 +167,16 @@ def test_beam_inference_ctc_predict():
         BeamInference(Args()).ctc_predict_(dev)
 
 
-def _hip():
-    """The HIP runtime already in the process (torch's), for the capture calls torch does not expose."""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = C.CDLL(path)
-    hip.hipStreamBeginCapture.argtypes = [C.c_void_p, C.c_int]
-    hip.hipStreamEndCapture.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    hip.hipGraphGetNodes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-    hip.hipGraphDestroy.argtypes = [C.c_void_p]
-    return hip
-
-
 def test_one_launch_whatever_the_batch_and_capturable():
     """The call is captured into a graph (never replayed): it enqueues the same number of nodes -- one kernel -- for 1 and for 384
     sequences, allocates nothing and synchronises nothing."""
-    hip, lib = _hip(), capi.load()
+    lib = capi.load()
     spellings, V, sil, _ = lexicon("prefix")
     packed = tries("prefix")[1]
     dev = torch.device("cuda", torch.cuda.current_device())
-    T, beam, nbest = 16, 10, 2
     counts = {}
     for n in (1, 384):
-        em = torch.from_numpy(L.emissions(n, spellings, n, T, V)).cuda()
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        words, wc, toks, tc, ts, nh = i32(n, nbest, T), i32(n, nbest), i32(n, nbest, T), i32(n, nbest), i32(n, nbest, T), i32(n)
-        sc = torch.empty((n, nbest), dtype=torch.float32, device=dev)
-        ws_bytes = lib.eec_ctc_lexbeam_workspace_bytes(n, T, beam)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        image = packed.on(dev)
-        side = torch.cuda.Stream()
-        torch.cuda.synchronize()
-        graph, n_nodes = C.c_void_p(), C.c_size_t(0)
-        assert hip.hipStreamBeginCapture(side.cuda_stream, 2) == 0  # relaxed mode: other threads are not affected
-        rc = lib.eec_ctc_lexbeam_decode(em.data_ptr(), n, T, V, None, image.data_ptr(), 0, -1, beam, nbest, 0.0, 0.0, 50.0, T, words.data_ptr(),
-                                        wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(), nh.data_ptr(), ws.data_ptr(),
-                                        ws_bytes, side.cuda_stream)
-        assert hip.hipStreamEndCapture(side.cuda_stream, C.byref(graph)) == 0
-        assert rc == 0, lib.eec_last_error()
-        assert hip.hipGraphGetNodes(graph, None, C.byref(n_nodes)) == 0
-        hip.hipGraphDestroy(graph)
-        counts[n] = n_nodes.value
+        em = torch.from_numpy(L.emissions(n, spellings, n, 16, V)).cuda()
+        image, bufs = packed.on(dev), raw_buffers(lib, em, 10, 2)
+        counts[n] = captured_nodes(lib, lambda stream: raw_call(lib, "eec_ctc_lexbeam_decode", em, image, 10, 2, bufs, stream=stream))
     assert counts[1] == counts[384] == 1, counts

@@ -1,10 +1,8 @@
 """GPU tests of log-add merging in the lexicon-constrained CTC beam search (csrc/ctc_lexbeam.hip, eec_ctc_lexbeam_logadd_decode,
 ``ctc_lexicon_decode(log_add=True)``, ``BeamInference.beam_predict``) against the plain-Python statement of
-tests/lexbeam_logadd_cases.py.  ``log_add`` is a stated sequence of exactly rounded fp32 operations, so, as in
+tests/lexbeam_statement.py (``log_add=True``).  ``log_add`` is a stated sequence of exactly rounded fp32 operations, so, as in
 tests/test_gpu_lexbeam.py, there is nothing to tolerate: n_hyp, words, tokens, timesteps and counts are compared as integers and
-scores as bit patterns.  Lexica, models and helpers are those of tests/test_gpu_lexbeam_lm.py."""
-import functools
-
+scores as bit patterns.  Lexica, models and helpers are those of tests/lexbeam_helpers.py."""
 import numpy as np
 import pytest
 import torch
@@ -13,30 +11,15 @@ import lexbeam_cases as L
 import lexbeam_logadd_cases as A
 import lexbeam_lm_cases as M
 import lexbeam_smear_cases as S
-import test_gpu_lexbeam_lm as G
+import lexbeam_statement as D
 from early_exit_transformer_amd import capi
 from early_exit_transformer_amd.beam import BeamInference
-from early_exit_transformer_amd.lexicon import TokenTrie
 from early_exit_transformer_amd.model import ctc_lexicon_decode
+from lexbeam_helpers import lexicon, models, raw_buffers, raw_call, run, same, tries
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
 BAD_ARG, UNSUPPORTED, WORKSPACE = 10001, 10002, 10003
-
-
-def lexicon(name):
-    """(spellings, V, sil or None, words)"""
-    if name == "one":
-        return L.ONE_WORD, 40, None, ["w0"]
-    return G.lexicon(name)
-
-
-@functools.lru_cache(maxsize=None)
-def tries(name):
-    """(the statement's trie, the packed one)"""
-    if name != "one":
-        return G.tries(name)
-    return L.Trie(L.ONE_WORD, 40, 0, None), TokenTrie.from_spellings(L.ONE_WORD, 40, blank=0, sil=None, words=["w0"])
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -67,9 +50,9 @@ def test_model_free_log_add_equals_the_statement(name, n, T, beam, nbest, opts):
         em_len = np.random.default_rng(T).integers(0, T + 2, size=n).astype(np.int32)
         em_len[:4] = [0, 1, T, T + 1]
     stats = {}
-    want = A.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, stats=stats, **opts)
+    want = D.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, log_add=True, stats=stats, **opts)
     assert T == 1 or stats.get("merges", 0) > 0
-    nh = G.same(G.run(em, packed, em_len, beam_size=beam, nbest=nbest, log_add=True, **opts), want, nbest)
+    nh = same(run(em, packed, em_len, beam_size=beam, nbest=nbest, log_add=True, **opts), want, nbest)
     assert T < 8 or (nh > 0).any(), "the case decodes something"
 
 
@@ -79,9 +62,9 @@ def test_ties_inside_merges_keep_the_lower_id_and_add_ln_2():
     ref, packed = tries("prefix")
     em = L.tie_emissions(7, spellings, 70, 16, V)
     stats = {}
-    want = A.decode_batch(em, ref, beam=10, nbest=10, beam_threshold=INF, stats=stats)
+    want = D.decode_batch(em, ref, beam=10, nbest=10, beam_threshold=INF, log_add=True, stats=stats)
     assert stats.get("equal_merges", 0) >= 1
-    nh = G.same(G.run(em, packed, beam_size=10, nbest=10, beam_threshold=INF, log_add=True), want, 10)
+    nh = same(run(em, packed, beam_size=10, nbest=10, beam_threshold=INF, log_add=True), want, 10)
     assert (nh > 0).sum() > 35
 
 
@@ -94,7 +77,7 @@ def test_ties_inside_merges_keep_the_lower_id_and_add_ln_2():
 def test_log_add_with_the_model_and_with_smearing_equals_the_statement(name, order, n, T, lm_weight, smearing):
     spellings, V, sil, words = lexicon(name)
     ref, packed_trie = tries(name)
-    lm, packed, favoured, disfavoured = G.models(name, order)
+    lm, packed, favoured, disfavoured = models(name, order)
     em = M.lm_emissions(300 + n + T, favoured, disfavoured, words, spellings, n, T, V, 0, -1 if sil is None else sil, peaks=(4.0, 8.0, 6.0))
     em_len = None
     if n == 70:
@@ -102,9 +85,9 @@ def test_log_add_with_the_model_and_with_smearing_equals_the_statement(name, ord
         em_len[:4] = [1, T, 0, T + 1]
     smax = None if smearing is None else S.smear(ref, lm, words)
     stats = {}
-    want = A.decode_batch(em, ref, em_len, beam=10, nbest=10, lm=lm, lm_weight=lm_weight, lm_words=words, smax=smax, stats=stats)
+    want = D.decode_batch(em, ref, em_len, beam=10, nbest=10, lm=lm, lm_weight=lm_weight, lm_words=words, smax=smax, log_add=True, stats=stats)
     assert stats.get("merges", 0) > 0
-    nh = G.same(G.run(em, packed_trie, em_len, beam_size=10, nbest=10, lm=packed, lm_weight=lm_weight, smearing=smearing, log_add=True), want, 10)
+    nh = same(run(em, packed_trie, em_len, beam_size=10, nbest=10, lm=packed, lm_weight=lm_weight, smearing=smearing, log_add=True), want, 10)
     assert (nh > 0).any(), "the case decodes something"
 
 
@@ -128,20 +111,12 @@ def test_device_log_add_equals_the_host_function_bit_for_bit():
 # ----------------------------------------------------------------------------------------------------------------------------
 # the entry
 # ----------------------------------------------------------------------------------------------------------------------------
-def raw_call(lib, entry, em, trie_image, beam, nbest, bufs, *more, stream=None, ws_bytes=None):
-    n, T, V = em.shape
-    words, wc, toks, tc, ts, sc, nh, ws = bufs
-    return getattr(lib, entry)(em.data_ptr(), n, T, V, None, trie_image.data_ptr(), 0, -1, beam, nbest, 0.0, 0.0, 50.0, T, words.data_ptr(),
-                               wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(), nh.data_ptr(), ws.data_ptr(),
-                               ws.numel() if ws_bytes is None else ws_bytes, capi.stream_ptr(em.device) if stream is None else stream, *more)
-
-
 def test_with_log_add_off_the_viterbi_entry_is_called_and_its_bits_come_back():
     lib = capi.load()
     spellings, V, _, _ = lexicon("prefix")
     packed = tries("prefix")[1]
     em = torch.from_numpy(L.emissions(5, spellings, 24, 16, V)).cuda()
-    bufs = G.raw_buffers(lib, em, 10, 10)
+    bufs = raw_buffers(lib, em, 10, 10)
     assert raw_call(lib, "eec_ctc_lexbeam_decode", em, packed.on(em.device), 10, 10, bufs) == 0
     got = ctc_lexicon_decode(em, packed, beam_size=10, nbest=10, log_add=False)
     for x, y in zip(got, bufs[:7]):
@@ -173,18 +148,18 @@ def test_the_log_add_launch_replays_from_a_graph():
         torch.cuda.synchronize()
         runs.append([o.cpu().numpy().copy() for o in out])
     assert all(x.tobytes() == y.tobytes() for x, y in zip(*runs))
-    G.same(runs[1], A.decode_batch(em_host, ref, beam=10, nbest=10), 10)
+    same(runs[1], D.decode_batch(em_host, ref, beam=10, nbest=10, log_add=True), 10)
 
 
 def test_argument_errors_come_before_any_device_work():
     lib = capi.load()
     spellings, V, _, words = lexicon("prefix")
     packed_trie = tries("prefix")[1]
-    packed = G.models("prefix", 2)[1]
+    packed = models("prefix", 2)[1]
     em = torch.from_numpy(L.emissions(5, spellings, 3, 16, V)).cuda()
     dev = em.device
     entry = "eec_ctc_lexbeam_logadd_decode"
-    bufs = G.raw_buffers(lib, em, 16, 1)
+    bufs = raw_buffers(lib, em, 16, 1)
     for b in bufs[:7]:
         b.fill_(-7)
     torch.cuda.synchronize()
@@ -218,7 +193,7 @@ def test_beam_predict_is_the_character_lexicon_decoder(tmp_path):
     V = len(CHAR_TOKENS)
     em = L.emissions(17, spellings, 2, 48, V, 0, 1, peaks=(3.0, 3.0))
     ref = L.Trie(spellings, V, 0, 1)
-    want = A.decode(em[0], ref, beam=8, nbest=1, word_score=-4.0)
+    want = D.decode(em[0], ref, beam=8, nbest=1, word_score=-4.0, log_add=True)
     text = " ".join(CHAR_WORDS[w] for w in want[0][0]).strip()
     assert want and len(want[0][0]) >= 2
 
@@ -234,7 +209,7 @@ def test_beam_predict_is_the_character_lexicon_decoder(tmp_path):
     infer = BeamInference(Args())
     dev_em = torch.from_numpy(em).cuda()
     assert infer.beam_predict(Model(), dev_em) == text
-    assert infer.beam_predict(Model(), dev_em[1:]) == " ".join(CHAR_WORDS[w] for w in A.decode(em[1], ref, beam=8, nbest=1, word_score=-4.0)[0][0])
+    assert infer.beam_predict(Model(), dev_em[1:]) == " ".join(CHAR_WORDS[w] for w in D.decode(em[1], ref, beam=8, nbest=1, word_score=-4.0, log_add=True)[0][0])
     assert BeamInference.WORD_SCORE == -4 and infer._trie is None, "the character trie is kept apart from the BPE trie"
 
 
@@ -243,8 +218,8 @@ def test_ctc_predict_with_log_add_returns_the_statements_transcripts():
     ref, packed = tries("prefix")
     em = L.emissions(5, spellings, 24, 16, V)
     text = lambda hyps: " ".join(words[w] for w in hyps[0][0]).strip() if hyps else ""  # noqa: E731
-    added = [text(h) for h in A.decode_batch(em, ref, beam=10)]
-    viterbi = [text(h) for h in L.decode_batch(em, ref, beam=10)]
+    added = [text(h) for h in D.decode_batch(em, ref, beam=10, log_add=True)]
+    viterbi = [text(h) for h in D.decode_batch(em, ref, beam=10)]
     assert sum(a != v for a, v in zip(added, viterbi)) >= 4
 
     class Args:

@@ -1,9 +1,9 @@
 """GPU tests of the lexicon-constrained CTC beam search with an n-gram model and LM look-ahead by max trie smearing
 (csrc/ctc_lexbeam.hip, ``ctc_lexicon_decode(lm=..., smearing="max")``, ``BeamInference(..., smearing="max")``) against the
-plain-Python statement of tests/lexbeam_smear_cases.py.  As in tests/test_gpu_lexbeam_lm.py, whose helpers and cached models are
-used here, there is nothing to tolerate: n_hyp, words, tokens, timesteps and counts are compared as integers and scores as bit
-patterns, and every model goes the whole way: dict, ARPA text, ``NGramLM.from_arpa``, ``NGramLM.smear``."""
-import ctypes as C
+plain-Python statement of tests/lexbeam_statement.py (``smax=``).  As in tests/test_gpu_lexbeam_lm.py, with which it shares the
+helpers and cached models of tests/lexbeam_helpers.py, there is nothing to tolerate: n_hyp, words, tokens, timesteps and counts are
+compared as integers and scores as bit patterns, and every model goes the whole way: dict, ARPA text, ``NGramLM.from_arpa``,
+``NGramLM.smear``."""
 import functools
 
 import numpy as np
@@ -13,20 +13,22 @@ import torch
 import lexbeam_cases as L
 import lexbeam_lm_cases as M
 import lexbeam_smear_cases as S
-import test_gpu_lexbeam_lm as G
+import lexbeam_statement as D
 from early_exit_transformer_amd import capi
 from early_exit_transformer_amd.beam import BeamInference
 from early_exit_transformer_amd.lexicon import NGramLM, TokenTrie
 from early_exit_transformer_amd.model import ctc_lexicon_decode
+from lexbeam_helpers import arpa_path, captured_nodes, lexicon, main_lm_reference, models, raw_buffers, raw_call, run, same, tries
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
+ENTRY = "eec_ctc_lexbeam_lm_smear_decode"
 
 
 @functools.lru_cache(maxsize=None)
 def table(name, order, seed=50, **variant):
-    """The statement's smear table for ``G.models(name, order, ...)`` over ``G.tries(name)``"""
-    return S.smear(G.tries(name)[0], G.models(name, order, seed, **variant)[0], G.lexicon(name)[3])
+    """The statement's smear table for ``models(name, order, ...)`` over ``tries(name)``"""
+    return S.smear(tries(name)[0], models(name, order, seed, **variant)[0], lexicon(name)[3])
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -34,10 +36,10 @@ def table(name, order, seed=50, **variant):
 # ----------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def main_smeared(lm_weight):
-    em, em_len, packed, plain, _, _, words, lm = G.main_reference(lm_weight)
-    ref = G.tries("fixture+sil")[0]
+    em, em_len, packed, plain, _, _, words, lm = main_lm_reference(lm_weight)
+    ref = tries("fixture+sil")[0]
     smax = S.smear(ref, lm, words)
-    return S.decode_batch(em, ref, em_len, beam=10, nbest=10, lm=lm, lm_weight=lm_weight, lm_words=words, smax=smax)
+    return D.decode_batch(em, ref, em_len, beam=10, nbest=10, lm=lm, lm_weight=lm_weight, lm_words=words, smax=smax)
 
 
 @pytest.mark.parametrize("lm_weight", [1.0, 3.23])
@@ -46,7 +48,7 @@ def test_the_main_case_makes_smearing_matter_and_equals_the_statement(lm_weight)
     all 10 hypotheses.  Before the device is asked, the statement alone must show that smearing changes the search: among the
     sequences that end with a hypothesis with and without it -- at least 10 -- the best final score differs in at least 5, and
     in at least one of them smearing finds the better one."""
-    em, em_len, packed, plain, _, _, words, lm = G.main_reference(lm_weight)
+    em, em_len, packed, plain, _, _, words, lm = main_lm_reference(lm_weight)
     want = main_smeared(lm_weight)
     both = [s for s in range(70) if want[s] and plain[s]]
     changed = [s for s in both if M.bits(want[s][0][3]) != M.bits(plain[s][0][3])]
@@ -54,7 +56,7 @@ def test_the_main_case_makes_smearing_matter_and_equals_the_statement(lm_weight)
           f"smeared better in {sum(1 for s in changed if want[s][0][3] > plain[s][0][3])}")
     assert len(both) >= 10 and len(changed) >= 5 and any(want[s][0][3] > plain[s][0][3] for s in changed)
     assert any(want[s][0][0] != plain[s][0][0] for s in changed), "... and with it the words"
-    nh = G.same(G.run(em, G.tries("fixture+sil")[1], em_len, beam_size=10, nbest=10, lm=packed, lm_weight=lm_weight, smearing="max"), want, 10)
+    nh = same(run(em, tries("fixture+sil")[1], em_len, beam_size=10, nbest=10, lm=packed, lm_weight=lm_weight, smearing="max"), want, 10)
     assert nh.tolist() == [len(h) for h in want]
 
 
@@ -88,27 +90,27 @@ def test_shapes_orders_lexica_and_options_equal_the_statement(name, order, varia
     """T' 1 and 2, beams 1, 2 and 16, 1, 3 and 70 sequences (ragged lengths with 0, 1, T' and T' + 1), V = 32 with words that are
     prefixes of words (a node both ends a word and has children), V = 256 where thread 255 owns a label and with sil, single-token
     words (pmax = 0 at the root), orders 1 to 4, no <s> / </s>, positive back-offs, word_score -4, a finite threshold."""
-    spellings, V, sil, words = G.lexicon(name)
-    ref, packed_trie = G.tries(name)
-    lm, packed, favoured, disfavoured = G.models(name, order, **variant)
+    spellings, V, sil, words = lexicon(name)
+    ref, packed_trie = tries(name)
+    lm, packed, favoured, disfavoured = models(name, order, **variant)
     em = M.lm_emissions(200 + n + T, favoured, disfavoured, words, spellings, n, T, V, 0, -1 if sil is None else sil, peaks=(4.0, 8.0, 6.0))
     em_len = None
     if n == 70:
         em_len = np.random.default_rng(T).integers(0, T + 2, size=n).astype(np.int32)  # 0 and T' + 1 included
         em_len[:4] = [1, T, 0, T + 1]
-    want = S.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, lm=lm, lm_words=words, smax=table(name, order, **variant), **opts)
-    nh = G.same(G.run(em, packed_trie, em_len, beam_size=beam, nbest=nbest, lm=packed, smearing="max", **opts), want, nbest)
+    want = D.decode_batch(em, ref, em_len, beam=beam, nbest=nbest, lm=lm, lm_words=words, smax=table(name, order, **variant), **opts)
+    nh = same(run(em, packed_trie, em_len, beam_size=beam, nbest=nbest, lm=packed, smearing="max", **opts), want, nbest)
     if T >= 16 and beam >= 10:
         assert (nh > 0).any(), "the case decodes something"
 
 
 @pytest.mark.parametrize("name,order,n,T,beam", [("fixture+sil", 3, 3, 32, 10), ("prefix", 2, 70, 16, 16), ("wide", 2, 3, 2, 1)])
 def test_at_lm_weight_0_smearing_is_the_unsmeared_entry_bitwise(name, order, n, T, beam):
-    spellings, V, sil, words = G.lexicon(name)
-    lm, packed, favoured, disfavoured = G.models(name, order)
+    spellings, V, sil, words = lexicon(name)
+    lm, packed, favoured, disfavoured = models(name, order)
     em = M.lm_emissions(300 + T, favoured, disfavoured, words, spellings, n, T, V, 0, -1 if sil is None else sil, peaks=(4.0, 8.0, 6.0))
-    plain = G.run(em, G.tries(name)[1], beam_size=beam, nbest=beam, lm=packed, lm_weight=0.0)
-    smeared = G.run(em, G.tries(name)[1], beam_size=beam, nbest=beam, lm=packed, lm_weight=0.0, smearing="max")
+    plain = run(em, tries(name)[1], beam_size=beam, nbest=beam, lm=packed, lm_weight=0.0)
+    smeared = run(em, tries(name)[1], beam_size=beam, nbest=beam, lm=packed, lm_weight=0.0, smearing="max")
     for a, b in zip(plain, smeared):
         assert a.tobytes() == b.tobytes()
     assert T < 16 or (plain[6] > 0).any()
@@ -118,13 +120,13 @@ def test_at_lm_weight_0_smearing_is_the_unsmeared_entry_bitwise(name, order, n, 
 def test_ties_with_a_grid_valued_model_are_decided_by_the_candidate_id(name, n, T, beam):
     """Log-probs on a grid of 0.25 with a block of uniform frames, model values -- and so the table's -- on a grid of 1/8,
     lm_weight 1: equal scores at every step, in merging, in pruning and in the final order."""
-    spellings, V, sil, words = G.lexicon(name)
-    ref, packed_trie = G.tries(name)
+    spellings, V, sil, words = lexicon(name)
+    ref, packed_trie = tries(name)
     order = 2 if name == "prefix" else 3
-    lm, packed, _, _ = G.models(name, order, grid=True)
+    lm, packed, _, _ = models(name, order, grid=True)
     em = L.tie_emissions(7, spellings, n, T, V, 0, -1 if sil is None else sil)
-    want = S.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF, lm=lm, lm_weight=1.0, lm_words=words, smax=table(name, order, grid=True))
-    nh = G.same(G.run(em, packed_trie, beam_size=beam, nbest=beam, beam_threshold=INF, lm=packed, lm_weight=1.0, smearing="max"), want, beam)
+    want = D.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF, lm=lm, lm_weight=1.0, lm_words=words, smax=table(name, order, grid=True))
+    nh = same(run(em, packed_trie, beam_size=beam, nbest=beam, beam_threshold=INF, lm=packed, lm_weight=1.0, smearing="max"), want, beam)
     if name == "prefix":
         scores = [float(h[3]) for hyps in want for h in hyps]
         assert len(scores) > len(set(scores)) and (nh > 0).sum() > n // 2
@@ -135,7 +137,7 @@ def test_ties_with_a_grid_valued_model_are_decided_by_the_candidate_id(name, n, 
 # ----------------------------------------------------------------------------------------------------------------------------
 def small_pair(tag, spellings, words, lm):
     trie = TokenTrie.from_spellings(spellings, S.PRUNE_V, blank=0, words=words)
-    return trie, NGramLM.from_arpa(G.arpa_path(lm, tag), trie)
+    return trie, NGramLM.from_arpa(arpa_path(lm, tag), trie)
 
 
 def test_at_beam_1_smearing_keeps_the_word_the_model_prefers():
@@ -144,20 +146,20 @@ def test_at_beam_1_smearing_keeps_the_word_the_model_prefers():
     spellings, words, lm, em = S.pruning_case()
     trie, packed = small_pair("prune", spellings, words, lm)
     kw = dict(beam_size=1, nbest=1, lm=packed, lm_weight=1.0)
-    plain, smeared = G.run(em[None], trie, **kw), G.run(em[None], trie, smearing="max", **kw)
+    plain, smeared = run(em[None], trie, **kw), run(em[None], trie, smearing="max", **kw)
     assert plain[0][0, 0, :1].tolist() == [1] and plain[5][0, 0] == np.float32(-6.875) and plain[2][0, 0, :2].tolist() == [S.C_, S.D]
     assert smeared[0][0, 0, :1].tolist() == [0] and smeared[5][0, 0] == np.float32(-3.0) and smeared[2][0, 0, :2].tolist() == [S.A, S.B_]
     ref = L.Trie(spellings, S.PRUNE_V, 0, None)
-    G.same(smeared, [S.decode(em, ref, beam=1, nbest=1, lm=lm, lm_weight=1.0, lm_words=words, smax=S.smear(ref, lm, words))], 1)
+    same(smeared, [D.decode(em, ref, beam=1, nbest=1, lm=lm, lm_weight=1.0, lm_words=words, smax=S.smear(ref, lm, words))], 1)
 
     spellings, words, lm, em = S.pruning_case(extra_abd=True)
     trie, packed = small_pair("prune-abd", spellings, words, lm)
     ref = L.Trie(spellings, S.PRUNE_V, 0, None)
     smax = S.smear(ref, lm, words)
     for beam, n_hyp in ((1, 0), (2, 1)):
-        got = G.run(em[None], trie, beam_size=beam, nbest=beam, lm=packed, lm_weight=1.0, smearing="max")
+        got = run(em[None], trie, beam_size=beam, nbest=beam, lm=packed, lm_weight=1.0, smearing="max")
         assert got[6].tolist() == [n_hyp]
-        G.same(got, [S.decode(em, ref, beam=beam, nbest=beam, lm=lm, lm_weight=1.0, lm_words=words, smax=smax)], beam)
+        same(got, [D.decode(em, ref, beam=beam, nbest=beam, lm=lm, lm_weight=1.0, lm_words=words, smax=smax)], beam)
 
 
 @pytest.mark.parametrize("T", [1, 2])
@@ -170,12 +172,12 @@ def test_where_nothing_is_pruned_the_payments_telescope(T):
         trie, packed = small_pair(f"tele-{T}-{seed}", spellings, words, lm)
         ref = L.Trie(spellings, S.PRUNE_V, 0, None)
         stats = {}
-        want = S.decode_batch(em, ref, beam=16, nbest=16, beam_threshold=INF, lm=lm, lm_weight=2.0, lm_words=words, smax=S.smear(ref, lm, words),
+        want = D.decode_batch(em, ref, beam=16, nbest=16, beam_threshold=INF, lm=lm, lm_weight=2.0, lm_words=words, smax=S.smear(ref, lm, words),
                               stats=stats)
         assert stats["max_candidates"] <= 16
         kw = dict(beam_size=16, nbest=16, beam_threshold=INF, lm=packed, lm_weight=2.0)
-        plain, smeared = G.run(em, trie, **kw), G.run(em, trie, smearing="max", **kw)
-        G.same(smeared, want, 16)
+        plain, smeared = run(em, trie, **kw), run(em, trie, smearing="max", **kw)
+        same(smeared, want, 16)
 
         def sets(out):
             words_, wc, toks, tc, ts, sc, nh = out
@@ -187,20 +189,10 @@ def test_where_nothing_is_pruned_the_payments_telescope(T):
 # ----------------------------------------------------------------------------------------------------------------------------
 # a table for another trie; determinism; the launch
 # ----------------------------------------------------------------------------------------------------------------------------
-def raw_call(lib, em, trie_image, lm_image, smear_image, beam, nbest, bufs, stream=None, sil=-1, lm_weight=1.0):
-    """The bare C entry on device buffers that exist already: the return code."""
-    n, T, V = em.shape
-    words, wc, toks, tc, ts, sc, nh, ws = bufs
-    return lib.eec_ctc_lexbeam_lm_smear_decode(em.data_ptr(), n, T, V, None, trie_image.data_ptr(), 0, sil, beam, nbest, 0.0, 0.0, 50.0, T,
-                                               words.data_ptr(), wc.data_ptr(), toks.data_ptr(), tc.data_ptr(), ts.data_ptr(), sc.data_ptr(),
-                                               nh.data_ptr(), ws.data_ptr(), ws.numel(), capi.stream_ptr(em.device) if stream is None else stream,
-                                               lm_image.data_ptr(), lm_weight, smear_image.data_ptr())
-
-
 def test_a_table_for_another_trie_is_refused_or_gives_no_hypothesis():
-    spellings, V, sil, words = G.lexicon("prefix")
-    _, packed_trie = G.tries("prefix")
-    lm, packed, favoured, disfavoured = G.models("prefix", 2)
+    spellings, V, sil, words = lexicon("prefix")
+    _, packed_trie = tries("prefix")
+    lm, packed, favoured, disfavoured = models("prefix", 2)
     shorter = TokenTrie.from_spellings(spellings[:-1], V, blank=0, words=words[:-1])
     em = M.lm_emissions(5, favoured, disfavoured, words, spellings, 3, 7, V, peaks=(8.0,))
     with pytest.raises(ValueError, match="packed for a lexicon of 8 words, the trie has 7"):
@@ -211,53 +203,46 @@ def test_a_table_for_another_trie_is_refused_or_gives_no_hypothesis():
     dev = torch.device("cuda", torch.cuda.current_device())
     dev_em = torch.from_numpy(em).to(dev)
     smear = packed.smear(packed_trie)
-    out = G.raw_buffers(lib, dev_em, 4, 2)
-    assert raw_call(lib, dev_em, packed_trie.on(dev), packed.on(dev), smear.on(dev), 4, 2, out) == 0 and (out[6] > 0).any()
+    out = raw_buffers(lib, dev_em, 4, 2)
+    assert raw_call(lib, ENTRY, dev_em, packed_trie.on(dev), 4, 2, out, packed.on(dev).data_ptr(), 1.0, smear.on(dev).data_ptr()) == 0 and (out[6] > 0).any()
     for dword, value in ((1, packed_trie.n_nodes - 1), (1, packed_trie.n_nodes + 1), (0, M.LM_MAGIC)):  # another node count; another image's magic
         image = smear._image.clone()
         image.view(torch.int32)[dword] = value
-        out = G.raw_buffers(lib, dev_em, 4, 2)
-        assert raw_call(lib, dev_em, packed_trie.on(dev), packed.on(dev), image.to(dev), 4, 2, out) == 0
+        image = image.to(dev)  # held in a name: the call takes its address
+        out = raw_buffers(lib, dev_em, 4, 2)
+        assert raw_call(lib, ENTRY, dev_em, packed_trie.on(dev), 4, 2, out, packed.on(dev).data_ptr(), 1.0, image.data_ptr()) == 0
         assert (out[6] == 0).all() and (out[5] == -np.inf).all() and (out[1] == 0).all() and (out[3] == 0).all() and (out[0] == -1).all()
 
 
 def test_a_sequence_alone_equals_itself_in_the_batch_and_runs_repeat():
-    em, em_len, packed, _, _, _, _, _ = G.main_reference(1.0)
+    em, em_len, packed, _, _, _, _, _ = main_lm_reference(1.0)
     want = main_smeared(1.0)
-    packed_trie = G.tries("fixture+sil")[1]
+    packed_trie = tries("fixture+sil")[1]
     kw = dict(beam_size=10, nbest=10, lm=packed, lm_weight=1.0, smearing="max")
-    first, again = G.run(em, packed_trie, em_len, **kw), G.run(em, packed_trie, em_len, **kw)
+    first, again = run(em, packed_trie, em_len, **kw), run(em, packed_trie, em_len, **kw)
     for a, b in zip(first, again):
         assert a.tobytes() == b.tobytes()
     for s in (0, 7, 41, 69):
-        alone = G.run(em[s:s + 1], packed_trie, em_len[s:s + 1], **kw)
+        alone = run(em[s:s + 1], packed_trie, em_len[s:s + 1], **kw)
         for a, b in zip(alone, first):
             assert a[0].tobytes() == b[s].tobytes(), s
-        G.same(alone, want[s:s + 1], 10)
+        same(alone, want[s:s + 1], 10)
 
 
 def test_one_launch_whatever_the_batch_and_capturable():
     """The call is captured into a graph (never replayed): it enqueues the same number of nodes -- one kernel -- for 1 and for 384
     sequences, allocates nothing and synchronises nothing."""
-    hip, lib = G._hip(), capi.load()
-    spellings, V, sil, words = G.lexicon("prefix")
-    packed_trie = G.tries("prefix")[1]
-    packed = G.models("prefix", 2)[1]
+    lib = capi.load()
+    spellings, V, sil, words = lexicon("prefix")
+    packed_trie = tries("prefix")[1]
+    packed = models("prefix", 2)[1]
     dev = torch.device("cuda", torch.cuda.current_device())
     counts = {}
     for n in (1, 384):
         em = torch.from_numpy(L.emissions(n, spellings, n, 16, V)).cuda()
-        trie_image, lm_image, smear_image, bufs = packed_trie.on(dev), packed.on(dev), packed.smear(packed_trie).on(dev), G.raw_buffers(lib, em, 10, 2)
-        side = torch.cuda.Stream()
-        torch.cuda.synchronize()
-        graph, n_nodes = C.c_void_p(), C.c_size_t(0)
-        assert hip.hipStreamBeginCapture(side.cuda_stream, 2) == 0  # relaxed mode: other threads are not affected
-        rc = raw_call(lib, em, trie_image, lm_image, smear_image, 10, 2, bufs, stream=side.cuda_stream)
-        assert hip.hipStreamEndCapture(side.cuda_stream, C.byref(graph)) == 0
-        assert rc == 0, lib.eec_last_error()
-        assert hip.hipGraphGetNodes(graph, None, C.byref(n_nodes)) == 0
-        hip.hipGraphDestroy(graph)
-        counts[n] = n_nodes.value
+        trie_image, lm_image, smear_image, bufs = packed_trie.on(dev), packed.on(dev), packed.smear(packed_trie).on(dev), raw_buffers(lib, em, 10, 2)
+        counts[n] = captured_nodes(lib, lambda stream: raw_call(lib, ENTRY, em, trie_image, 10, 2, bufs, lm_image.data_ptr(), 1.0, smear_image.data_ptr(),
+                                                                stream=stream))
     assert counts[1] == counts[384] == 1, counts
 
 
@@ -285,19 +270,19 @@ def test_beam_inference_with_smearing_and_the_default_issues_todays_calls(monkey
     """``BeamInference(..., smearing="max")`` and ``args.lm_smearing`` return the smeared statement's transcripts through one call
     of the new entry; with ``smearing=None`` the calls are the ones made before the keyword existed -- one eec_ctc_lexbeam_lm_decode
     with a model, one eec_ctc_lexbeam_decode without --, no table is built, and the outputs equal the call without the keyword."""
-    em, _, packed, _, _, _, words, lm = G.main_reference(1.0)
-    ref, packed_trie = G.tries("fixture+sil")
+    em, _, packed, _, _, _, words, lm = main_lm_reference(1.0)
+    ref, packed_trie = tries("fixture+sil")
     em = em[40:56]  # full-length sequences
     smax = S.smear(ref, lm, words)
-    want = S.decode_batch(em, ref, beam=10, nbest=4, lm=lm, lm_weight=1.0, lm_words=words, smax=smax)
-    plain = M.decode_batch(em, ref, beam=10, nbest=4, lm=lm, lm_weight=1.0, lm_words=words)
+    want = D.decode_batch(em, ref, beam=10, nbest=4, lm=lm, lm_weight=1.0, lm_words=words, smax=smax)
+    plain = D.decode_batch(em, ref, beam=10, nbest=4, lm=lm, lm_weight=1.0, lm_words=words)
     text = lambda hyps: " ".join(words[w] for w in hyps[0][0]).strip() if hyps else ""  # noqa: E731
     assert any(want) and [text(h) for h in want] != [text(h) for h in plain]
 
     class Args:
         beam_size = 10
     dev = torch.from_numpy(em).cuda()
-    fresh = NGramLM.from_arpa(G.arpa_path(lm, "main-fresh"), packed_trie)
+    fresh = NGramLM.from_arpa(arpa_path(lm, "main-fresh"), packed_trie)
     counted = _Counted(monkeypatch)
     off = BeamInference(Args(), trie=packed_trie, lm=fresh)
     assert off.ctc_predict_(dev, nbest=4) == [text(h) for h in plain]
@@ -324,4 +309,4 @@ def test_beam_inference_with_smearing_and_the_default_issues_todays_calls(monkey
             assert abs(float(pprob) - p[0] / p.sum()) <= 1e-6
         else:
             assert float(pprob) == 0.0
-    assert BeamInference(by_args, trie=packed_trie).ctc_predict_(dev, nbest=4) == [text(h) for h in L.decode_batch(em, ref, beam=10, nbest=4)]
+    assert BeamInference(by_args, trie=packed_trie).ctc_predict_(dev, nbest=4) == [text(h) for h in D.decode_batch(em, ref, beam=10, nbest=4)]

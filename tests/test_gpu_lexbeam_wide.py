@@ -1,6 +1,6 @@
 """GPU tests of the wide-beam lexicon CTC search (csrc/ctc_lexbeam_wide.hip, eec_ctc_lexbeam_wide_decode, ``ctc_lexicon_decode`` with
 ``beam_size`` 17..64 or ``wide=True``, ``BeamInference`` at beam 64) against the narrow entries at beams of 16 or less and against the
-plain-Python statement of tests/lexbeam_wide_cases.py above that.  As in tests/test_gpu_lexbeam.py there is nothing to tolerate:
+plain-Python statement of tests/lexbeam_statement.py above that.  As in tests/test_gpu_lexbeam.py there is nothing to tolerate:
 n_hyp, words, tokens, timesteps and counts are compared as integers and scores as bit patterns.  tests/test_host_lexbeam_wide.py
 shows with the statement alone that these cases fill the beam past 16, overflow the kernel's candidate list and hold ties that only
 the wide id decides."""
@@ -13,29 +13,15 @@ import torch
 import lexbeam_cases as L
 import lexbeam_lm_cases as M
 import lexbeam_smear_cases as S
+import lexbeam_statement as D
 import lexbeam_wide_cases as W
-import test_gpu_lexbeam_lm as G
 from early_exit_transformer_amd.beam import BeamInference
 from early_exit_transformer_amd.lexicon import TokenTrie
 from early_exit_transformer_amd.model import ctc_lexicon_decode
+from lexbeam_helpers import identical, lexicon, models, run, same, tries
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
-run, same = G.run, G.same
-
-
-@functools.lru_cache(maxsize=None)
-def tries(name):
-    """(the statement's trie, the packed one)"""
-    if name != "one":
-        return G.tries(name)
-    spellings, V, sil, words = W.lexicon(name)
-    return L.Trie(spellings, V, 0, sil), TokenTrie.from_spellings(spellings, V, blank=0, sil=sil, words=words)
-
-
-def identical(a, b):
-    for x, y in zip(a, b):
-        assert x.tobytes() == y.tobytes()
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -53,8 +39,8 @@ MODES = {
 @functools.lru_cache(maxsize=None)
 def model_case(order=3, **variant):
     """(emission [4, 32, 256], model dict, packed model) over fixture+sil, emissions in the style of lexbeam_lm_cases.main_lm_case"""
-    spellings, V, sil, words = W.lexicon("fixture+sil")
-    lm, packed, favoured, disfavoured = G.models("fixture+sil", order, **variant)
+    spellings, V, sil, words = lexicon("fixture+sil")
+    lm, packed, favoured, disfavoured = models("fixture+sil", order, **variant)
     em = M.lm_emissions(300 + order, favoured, disfavoured, words, spellings, 4, 32, V, 0, sil, peaks=M.MAIN_PEAKS)
     return em, lm, packed
 
@@ -74,7 +60,7 @@ def test_wide_at_narrow_beams_equals_the_narrow_entry(mode, beam):
         em, _, packed = model_case()
         settings = [mode_kwargs(mode, packed)]
     else:
-        spellings, V, sil, _ = W.lexicon("fixture+sil")
+        spellings, V, sil, _ = lexicon("fixture+sil")
         em = L.emissions(154, spellings, 6, 48, V, 0, sil)
         settings = [dict(MODES[mode], beam_threshold=50.0), dict(MODES[mode], beam_threshold=INF)]
     for kw in settings:
@@ -92,7 +78,7 @@ def test_wide_at_narrow_beams_equals_the_narrow_entry(mode, beam):
 def wide_reference(k):
     name, n, T, beam, nbest, opts = W.WIDE_CASES[k]
     em, em_len = W.wide_case_inputs(name, n, T)
-    return em, em_len, W.decode_batch(em, tries(name)[0], em_len, beam=beam, nbest=nbest, **opts)
+    return em, em_len, D.decode_batch(em, tries(name)[0], em_len, beam=beam, nbest=nbest, **opts)
 
 
 @pytest.mark.parametrize("k", range(len(W.WIDE_CASES)), ids=[f"{c[0]}-n{c[1]}-T{c[2]}-b{c[3]}-k{c[4]}" for c in W.WIDE_CASES])
@@ -114,7 +100,7 @@ def test_wide_beams_equal_the_statement(k):
 def test_wide_ties_are_decided_by_the_candidate_id(name, n, T, beam):
     ref, packed = tries(name)
     em = W.tie_case_inputs(name, n, T)
-    want = W.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF)
+    want = D.decode_batch(em, ref, beam=beam, nbest=beam, beam_threshold=INF)
     same(run(em, packed, beam_size=beam, nbest=beam, beam_threshold=INF), want, beam)
 
 
@@ -124,7 +110,7 @@ def test_wide_ties_are_decided_by_the_candidate_id(name, n, T, beam):
 def test_minus_infinity_and_nan_follow_the_drop_rule_at_beam_64():
     """The case of tests/test_gpu_lexbeam.py at beam 64: a fifth of the entries -inf in every sequence; NaN entries in sequence 1
     and a whole NaN frame in sequence 2 (it ends without a hypothesis); the neighbours are what they are without them."""
-    spellings, V, sil, _ = W.lexicon("prefix")
+    spellings, V, sil, _ = lexicon("prefix")
     ref, packed = tries("prefix")
     em = L.emissions(21, spellings, 6, 16, V, peaks=(4.0, 8.0))
     rng = np.random.default_rng(22)
@@ -132,7 +118,7 @@ def test_minus_infinity_and_nan_follow_the_drop_rule_at_beam_64():
     clean = em.copy()
     em[1][rng.random(em[1].shape) < 0.1] = np.nan
     em[2, 5, :] = np.nan
-    want = W.decode_batch(em, ref, beam=64, nbest=64)
+    want = D.decode_batch(em, ref, beam=64, nbest=64)
     assert want[2] == [] and any(want[s] for s in (0, 3, 4, 5))
     got = run(em, packed, beam_size=64, nbest=64)
     same(got, want, 64)
@@ -156,7 +142,7 @@ LM_CASES = ([(beam, mode, 3, 3.23, ()) for beam in (40, 64) for mode in LM_MODES
 def test_wide_beams_with_a_model_equal_the_statement(beam, mode, order, lm_weight, variant):
     """4 sequences x 32 frames over fixture+sil, every hypothesis returned.  `logadd` runs without the model (the mode the other
     three do not cover at these beams); the others under a model of order 2 or 3, with and without </s>, at lm_weight 0 and not 0."""
-    spellings, V, sil, words = W.lexicon("fixture+sil")
+    spellings, V, sil, words = lexicon("fixture+sil")
     ref, packed_trie = tries("fixture+sil")
     em, lm, packed = model_case(order, **dict(variant))
     kw = mode_kwargs(mode, packed, lm_weight)
@@ -164,7 +150,7 @@ def test_wide_beams_with_a_model_equal_the_statement(beam, mode, order, lm_weigh
     if "lm" in kw:
         st.update(lm=lm, lm_weight=lm_weight, lm_words=words, smax=S.smear(ref, lm, words) if kw.get("smearing") else None)
     stats = []
-    want = W.decode_batch(em, ref, beam=beam, nbest=beam, stats=stats, **st)
+    want = D.decode_batch(em, ref, beam=beam, nbest=beam, stats=stats, **st)
     assert W.wide_share(stats) >= 0.5
     nh = same(run(em, packed_trie, beam_size=beam, nbest=beam, **kw), want, beam)
     assert (nh > 0).any(), "the case decodes something"
@@ -223,7 +209,7 @@ def test_max_words_truncates_and_word_count_stays_true():
 
 
 def test_a_trie_packed_for_other_labels_gives_no_hypothesis():
-    spellings, V, sil, _ = W.lexicon("prefix")
+    spellings, V, sil, _ = lexicon("prefix")
     other = TokenTrie.from_spellings(spellings, V, blank=0, sil=None)
     other.sil = 20  # the call now states a sil token the image was not packed with
     em = L.emissions(5, spellings, 3, 7, V, peaks=(8.0,))
@@ -237,10 +223,10 @@ def test_a_trie_packed_for_other_labels_gives_no_hypothesis():
 def test_beam_inference_at_beam_64():
     """The transcripts are the statement's at beam 64; pprob is the softmax over up to 64 of its scores (a float64 softmax of
     identical fp32 inputs: 1e-6 covers its rounding).  The small lexicon ends more than 16 complete hypotheses per utterance."""
-    spellings, V, sil, words = W.lexicon("prefix")
+    spellings, V, sil, words = lexicon("prefix")
     ref, packed = tries("prefix")
     em = L.emissions(31, spellings, 6, 16, V)
-    want = W.decode_batch(em, ref, beam=64, nbest=64)
+    want = D.decode_batch(em, ref, beam=64, nbest=64)
     assert any(len(h) > 16 for h in want), "more hypotheses than a narrow beam could return"
 
     class Args:

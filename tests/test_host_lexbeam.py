@@ -1,16 +1,15 @@
 """CPU tests of the lexicon-constrained CTC beam search's host side: the trie packer (host code in csrc/ctc_lexbeam.hip) against a
 reader of the documented image layout, every argument error of both entry points (all decided before any device work), the
-size arithmetic, and the plain-Python statement of the search (tests/lexbeam_cases.py) against cases worked out by hand."""
+size arithmetic, and the plain-Python statement of the search (tests/lexbeam_statement.py) against cases worked out by hand."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import lexbeam_cases as L
-from early_exit_transformer_amd import capi
-from early_exit_transformer_amd.build import LIB_PATH
+import lexbeam_statement as D
 from early_exit_transformer_amd.lexicon import TokenTrie
+from lexbeam_helpers import library
 
 BAD_ARG, UNSUPPORTED, WORKSPACE = 10001, 10002, 10003
 NI = -np.inf
@@ -18,10 +17,7 @@ NI = -np.inf
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
 def _pack(lib, spellings, V, blank=0, sil=-1, image_bytes=None):
@@ -186,7 +182,8 @@ def test_the_python_entry_needs_a_device():
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the statement against cases worked out by hand.  V = 3 or 4: blank 0, a = 1, b = 2, (sil 3).  Log-probs are small binary
-# fractions, so every sum below is exact; NI = -inf switches a label off.  Candidate ids are (2 c + w) * 16 + i.
+# fractions, so every sum below is exact; NI = -inf switches a label off.  The candidate ids named below are the narrow
+# kernels' (2 c + w) * 16 + i; the statement's (2 c + w) * 64 + i puts them in the same order.
 # ---------------------------------------------------------------------------------------------------------------------------
 def em(*rows):
     return np.array(rows, dtype=np.float32)
@@ -205,36 +202,36 @@ def test_statement_two_word_lexicon():
     rank 0 is the lower id.  Frame 1: from rank 0 blank -3 [id 0] and the edge b, which ends "ab": -1.5 [id 80]; from rank 1 blank
     -3 [id 1] (a after a without a blank is no new edge, and the repeat is -inf).  Frame 2: blank, -0.25 each."""
     trie = L.Trie(A_AB, 3)
-    got = L.decode(CASE1, trie, beam=16, nbest=16, beam_threshold=np.inf)
+    got = D.decode(CASE1, trie, beam=16, nbest=16, beam_threshold=np.inf)
     assert got == [hyp([1], [1, 2], [0, 1], -1.75), hyp([0], [1], [0], -3.25)]  # the in-word hypothesis (y, blank) is not complete
-    assert L.decode(CASE1, trie, beam=16, nbest=1, beam_threshold=np.inf) == got[:1]
-    assert L.decode(CASE1, trie, beam=1, nbest=1, beam_threshold=np.inf) == got[:1]  # beam 1 keeps id 32, which leads to "ab"
-    assert L.decode(CASE1, trie, beam=16, nbest=16, beam_threshold=np.inf, length=2) == [hyp([1], [1, 2], [0, 1], -1.5), hyp([0], [1], [0], -3.0)]
-    assert L.decode(CASE1, trie, beam=16, nbest=16, length=1) == [hyp([0], [1], [0], -1.0)]
+    assert D.decode(CASE1, trie, beam=16, nbest=1, beam_threshold=np.inf) == got[:1]
+    assert D.decode(CASE1, trie, beam=1, nbest=1, beam_threshold=np.inf) == got[:1]  # beam 1 keeps id 32, which leads to "ab"
+    assert D.decode(CASE1, trie, beam=16, nbest=16, beam_threshold=np.inf, length=2) == [hyp([1], [1, 2], [0, 1], -1.5), hyp([0], [1], [0], -3.0)]
+    assert D.decode(CASE1, trie, beam=16, nbest=16, length=1) == [hyp([0], [1], [0], -1.0)]
     for bad in (0, -1, 4):
-        assert L.decode(CASE1, trie, length=bad) == []
+        assert D.decode(CASE1, trie, length=bad) == []
 
 
 def test_statement_beam_threshold_leaves_fewer_than_beam():
     """CASE1 with threshold 1: at frame 1 the best is -1.5, the two -3 candidates fall below -2.5, one hypothesis is left."""
-    assert L.decode(CASE1, L.Trie(A_AB, 3), beam=16, nbest=16, beam_threshold=1.0) == [hyp([1], [1, 2], [0, 1], -1.75)]
+    assert D.decode(CASE1, L.Trie(A_AB, 3), beam=16, nbest=16, beam_threshold=1.0) == [hyp([1], [1, 2], [0, 1], -1.75)]
     # threshold 1.5 keeps them: -3 >= -1.5 - 1.5
-    assert len(L.decode(CASE1, L.Trie(A_AB, 3), beam=16, nbest=16, beam_threshold=1.5)) == 2
+    assert len(D.decode(CASE1, L.Trie(A_AB, 3), beam=16, nbest=16, beam_threshold=1.5)) == 2
 
 
 def test_statement_repeat_after_word_end():
     """One word "a", three frames of a: the word ends at frame 0 [id 48], then a repeats through the repeat rule (-0.5, -0.25); it
     is not a second "a" (a after a needs a blank)."""
     e = em([NI, -1], [NI, -0.5], [NI, -0.25])
-    assert L.decode(e, L.Trie([[1]], 2), beam=4, nbest=4) == [hyp([0], [1], [0], -1.75)]
+    assert D.decode(e, L.Trie([[1]], 2), beam=4, nbest=4) == [hyp([0], [1], [0], -1.75)]
 
 
 def test_statement_blank_between_equal_tokens():
     """One word "aa".  Frame 1 offers blank -0.5 or a -0.25: the repeat scores higher (rank 0) but stays at the first a for good;
     only the hypothesis that took the blank can take the edge a again at frame 2 and end the word: -1 - 0.5 - 1 [id 49]."""
     e = em([NI, -1], [-0.5, -0.25], [NI, -1])
-    assert L.decode(e, L.Trie([[1, 1]], 2), beam=4, nbest=4) == [hyp([0], [1, 1], [0, 2], -2.5)]
-    assert L.decode(e, L.Trie([[1, 1]], 2), beam=1, nbest=1) == []  # beam 1 follows the repeat
+    assert D.decode(e, L.Trie([[1, 1]], 2), beam=4, nbest=4) == [hyp([0], [1, 1], [0, 2], -2.5)]
+    assert D.decode(e, L.Trie([[1, 1]], 2), beam=1, nbest=1) == []  # beam 1 follows the repeat
 
 
 def test_statement_sil_on_and_off():
@@ -242,15 +239,15 @@ def test_statement_sil_on_and_off():
     (sil_score -0.25): (0, sil) = (-1 - 0.5) - 0.25 [id 96] ahead of blank -4 [id 0].  A third frame of sil: rank 0 repeats it,
     (-1.75 - 0.5) - 0.25 = -2.5, rank 1 (after blank) enters sil with (-4 - 0.5) - 0.25: the same state, merged, the higher stays."""
     e = em([NI, -1, NI, NI], [-3, NI, NI, -0.5])
-    assert L.decode(e, L.Trie([[1]], 4), beam=4, nbest=4) == [hyp([0], [1], [0], -4.0)]
+    assert D.decode(e, L.Trie([[1]], 4), beam=4, nbest=4) == [hyp([0], [1], [0], -4.0)]
     on = L.Trie([[1]], 4, sil=3)
-    assert L.decode(e, on, beam=4, nbest=4, sil_score=-0.25) == [hyp([0], [1, 3], [0, 1], -1.75), hyp([0], [1], [0], -4.0)]
+    assert D.decode(e, on, beam=4, nbest=4, sil_score=-0.25) == [hyp([0], [1, 3], [0, 1], -1.75), hyp([0], [1], [0], -4.0)]
     e3 = em([NI, -1, NI, NI], [-3, NI, NI, -0.5], [NI, NI, NI, -0.5])
-    assert L.decode(e3, on, beam=4, nbest=4, sil_score=-0.25) == [hyp([0], [1, 3], [0, 1], -2.5)]
-    assert L.decode(e3, on, beam=4, nbest=4, sil_score=0.0) == [hyp([0], [1, 3], [0, 1], -2.0)]
+    assert D.decode(e3, on, beam=4, nbest=4, sil_score=-0.25) == [hyp([0], [1, 3], [0, 1], -2.5)]
+    assert D.decode(e3, on, beam=4, nbest=4, sil_score=0.0) == [hyp([0], [1, 3], [0, 1], -2.0)]
     # sil before any word, from the start state (pb): (0 - 0.5) + 0 at frame 0 needs label 3 there
     e0 = em([NI, NI, NI, -0.5], [NI, -1, NI, NI])
-    assert L.decode(e0, on, beam=4, nbest=4) == [hyp([0], [3, 1], [0, 1], -1.5)]
+    assert D.decode(e0, on, beam=4, nbest=4) == [hyp([0], [3, 1], [0, 1], -1.5)]
 
 
 def test_statement_word_score_changes_the_winner():
@@ -258,22 +255,22 @@ def test_statement_word_score_changes_the_winner():
     ws = +1: -1 against 0 (and at frame 0 the word end, 0, ranks above the in-word candidate, -1)."""
     trie = L.Trie([[1], [2], [1, 2]], 3)
     e = em([NI, -1, NI], [NI, NI, -1])
-    assert L.decode(e, trie, beam=4, nbest=4, word_score=-4.0, beam_threshold=np.inf) == [hyp([2], [1, 2], [0, 1], -6.0), hyp([0, 1], [1, 2], [0, 1], -10.0)]
-    assert L.decode(e, trie, beam=4, nbest=4, word_score=1.0, beam_threshold=np.inf) == [hyp([0, 1], [1, 2], [0, 1], 0.0), hyp([2], [1, 2], [0, 1], -1.0)]
-    assert L.decode(e, trie, beam=4, nbest=4, word_score=0.0, beam_threshold=np.inf) == [hyp([2], [1, 2], [0, 1], -2.0), hyp([0, 1], [1, 2], [0, 1], -2.0)]
+    assert D.decode(e, trie, beam=4, nbest=4, word_score=-4.0, beam_threshold=np.inf) == [hyp([2], [1, 2], [0, 1], -6.0), hyp([0, 1], [1, 2], [0, 1], -10.0)]
+    assert D.decode(e, trie, beam=4, nbest=4, word_score=1.0, beam_threshold=np.inf) == [hyp([0, 1], [1, 2], [0, 1], 0.0), hyp([2], [1, 2], [0, 1], -1.0)]
+    assert D.decode(e, trie, beam=4, nbest=4, word_score=0.0, beam_threshold=np.inf) == [hyp([2], [1, 2], [0, 1], -2.0), hyp([0, 1], [1, 2], [0, 1], -2.0)]
     # equal scores: at frame 0 the in-word candidate [id 32] ranks above the word end [id 48], so "ab" has id 80 and "a b" id 81
 
 
 def test_statement_no_complete_hypothesis_and_dead_frames():
     only_ab = L.Trie([[1, 2]], 3)
-    assert L.decode(em([NI, -1, NI]), only_ab, beam=4, nbest=4) == []           # ends inside the word
-    assert L.decode(em([-1, NI, NI]), only_ab, beam=4, nbest=4) == [hyp([], [], [], -1.0)]  # the empty transcript is complete
+    assert D.decode(em([NI, -1, NI]), only_ab, beam=4, nbest=4) == []           # ends inside the word
+    assert D.decode(em([-1, NI, NI]), only_ab, beam=4, nbest=4) == [hyp([], [], [], -1.0)]  # the empty transcript is complete
     dead = em([NI, -1, NI], [NI, NI, NI], [-1, -1, -1])
-    assert L.decode(dead, L.Trie(A_AB, 3), beam=4, nbest=4) == []               # an all-(-inf) frame leaves no candidate
+    assert D.decode(dead, L.Trie(A_AB, 3), beam=4, nbest=4) == []               # an all-(-inf) frame leaves no candidate
     nan = em([NI, -1, NI], [np.nan, np.nan, np.nan], [-1, -1, -1])
-    assert L.decode(nan, L.Trie(A_AB, 3), beam=4, nbest=4) == []                # NaN scores are dropped like -inf
+    assert D.decode(nan, L.Trie(A_AB, 3), beam=4, nbest=4) == []                # NaN scores are dropped like -inf
     part = em([NI, -1, NI], [np.nan, NI, -0.5], [-0.25, np.nan, NI])
-    assert L.decode(part, L.Trie(A_AB, 3), beam=4, nbest=4) == [hyp([1], [1, 2], [0, 1], -1.75)]
+    assert D.decode(part, L.Trie(A_AB, 3), beam=4, nbest=4) == [hyp([1], [1, 2], [0, 1], -1.75)]
 
 
 def test_the_gpu_suite_will_see_both_outcomes():
@@ -281,5 +278,5 @@ def test_the_gpu_suite_will_see_both_outcomes():
     with a hypothesis and at least a tenth without -- not counting the ones whose length is out of range."""
     e, em_len, spellings, _ = L.main_case()
     trie = L.Trie(spellings, 256, 0, 126)
-    n = [len(r) for r, k in zip(L.decode_batch(e, trie, em_len, beam=10, nbest=10), em_len) if 1 <= k <= 64]
+    n = [len(r) for r, k in zip(D.decode_batch(e, trie, em_len, beam=10, nbest=10), em_len) if 1 <= k <= 64]
     assert len(n) == 67 and sum(1 for k in n if k > 0) >= 0.25 * 70 and sum(1 for k in n if k == 0) >= 0.10 * 70, n

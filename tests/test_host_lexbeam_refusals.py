@@ -13,7 +13,7 @@ import os
 import pytest
 
 from early_exit_transformer_amd import capi
-from early_exit_transformer_amd.build import LIB_PATH
+from lexbeam_helpers import library
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lexbeam_refusals.txt")
 FAKE = 0x10000
@@ -58,10 +58,7 @@ CASES = [
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
 def answer(lib, entry, case):

@@ -1,8 +1,11 @@
-"""CPU tests of the wide-beam lexicon CTC search (eec_ctc_lexbeam_wide_decode, csrc/ctc_lexbeam_wide.hip): the wide statement
-(tests/lexbeam_wide_cases.py, candidate id (2 c + w) * 64 + i) against the four narrow statements at beams of 16 or less, the new
-entry's argument errors and size arithmetic (all decided before any device work), and the conditions that keep the cases of
-tests/test_gpu_lexbeam_wide.py from being vacuous, decided by the statement alone."""
+"""CPU tests of the wide-beam lexicon CTC search (eec_ctc_lexbeam_wide_decode, csrc/ctc_lexbeam_wide.hip): the statement
+(tests/lexbeam_statement.py, candidate id (2 c + w) * 64 + i) against what the four narrow statements it replaced returned at beams of
+16 or less (tests/golden/lexbeam_statement_pins.json), the entry's argument errors and size arithmetic (all decided before any
+device work), and the conditions that keep the cases of tests/test_gpu_lexbeam_wide.py from being vacuous, decided by the statement
+alone."""
 import functools
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -10,11 +13,10 @@ import pytest
 
 import lexbeam_cases as L
 import lexbeam_lm_cases as M
-import lexbeam_logadd_cases as A
 import lexbeam_smear_cases as S
+import lexbeam_statement as D
 import lexbeam_wide_cases as W
-from early_exit_transformer_amd import capi
-from early_exit_transformer_amd.build import LIB_PATH
+from lexbeam_helpers import library
 
 BAD_ARG, UNSUPPORTED, WORKSPACE = 10001, 10002, 10003
 INF = float("inf")
@@ -22,71 +24,70 @@ INF = float("inf")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
-def identical(got, want):
-    """Two batches of hypothesis lists: words, tokens, timesteps equal, scores equal as bit patterns."""
-    assert len(got) == len(want)
-    for s, (g, w) in enumerate(zip(got, want)):
-        assert len(g) == len(w), s
-        for j, (x, y) in enumerate(zip(g, w)):
-            assert x[:3] == y[:3], (s, j)
-            assert np.float32(x[3]).view(np.int32) == np.float32(y[3]).view(np.int32), (s, j, x[3], y[3])
+# ---------------------------------------------------------------------------------------------------------------------------
+# at beams of 16 or less the statement returns what the four narrow statements (candidate id (2 c + w) * 16 + i) returned
+# ---------------------------------------------------------------------------------------------------------------------------
+with open(os.path.join(L.GOLDEN, "lexbeam_statement_pins.json"), encoding="utf-8") as _f:
+    PINS = json.load(_f)
 
 
 @functools.lru_cache(maxsize=None)
-def lm_case():
-    """The first 8 sequences of lexbeam_lm_cases.main_lm_case (order 3), 32 frames of each: (em, em_len, trie, words, model)."""
+def pin_inputs(generator):
+    """(emission, em_len or None, trie, words or None, model or None), as the record's ``generators`` describe them"""
+    if generator == "main":  # the main case's first sequences with their ragged lengths
+        em, em_len, spellings, _ = L.main_case()
+        return em[:8, :40], np.minimum(em_len[:8], 41), L.Trie(spellings, 256, 0, 126), None, None
+    if generator == "wide":
+        wide = L.wide_lexicon()
+        return L.emissions(164, wide, 2, 12, 256, 0, 126), None, L.Trie(wide, 256, 0, 126), None, None
+    if generator == "ties":  # equal scores in every frame: the id decides, and must decide alike
+        return L.tie_emissions(7, L.PREFIX_DOUBLED, 12, 16, 32), None, L.Trie(L.PREFIX_DOUBLED, 32), None, None
+    assert generator == "lm"  # the first 8 sequences of lexbeam_lm_cases.main_lm_case (order 3), 32 frames of each
     em, em_len, spellings, words, lm = M.main_lm_case()
     return np.ascontiguousarray(em[:8, :32]), np.minimum(em_len[:8], 33), L.Trie(spellings, 256, 0, 126), words, lm
 
 
-# ---------------------------------------------------------------------------------------------------------------------------
-# the wide statement is the four narrow ones at beams of 16 or less
-# ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("beam", [1, 10, 16])
-def test_the_wide_statement_equals_lexbeam_cases(beam):
-    """The model-free Viterbi statement on its own generators: the main case's first sequences with their ragged lengths, the wide
-    lexicon, and tie emissions (equal scores in every frame: the id decides, and must decide alike)."""
-    em, em_len, spellings, _ = L.main_case()
-    ref = L.Trie(spellings, 256, 0, 126)
-    for opts in (dict(), dict(beam_threshold=INF, word_score=1.5, sil_score=-0.5)):
-        identical(W.decode_batch(em[:8, :40], ref, np.minimum(em_len[:8], 41), beam=beam, nbest=beam, **opts),
-                  L.decode_batch(em[:8, :40], ref, np.minimum(em_len[:8], 41), beam=beam, nbest=beam, **opts))
-    wide = L.wide_lexicon()
-    ref = L.Trie(wide, 256, 0, 126)
-    e = L.emissions(164, wide, 2, 12, 256, 0, 126)
-    identical(W.decode_batch(e, ref, beam=beam, nbest=beam), L.decode_batch(e, ref, beam=beam, nbest=beam))
-    ref = L.Trie(L.PREFIX_DOUBLED, 32)
-    e = L.tie_emissions(7, L.PREFIX_DOUBLED, 12, 16, 32)
-    identical(W.decode_batch(e, ref, beam=beam, nbest=beam, beam_threshold=INF), L.decode_batch(e, ref, beam=beam, nbest=beam, beam_threshold=INF))
+def digest(hyps):
+    """The record's ``serialisation`` of a batch of hypothesis lists."""
+    canon = [[[list(map(int, w)), list(map(int, tk)), list(map(int, st)), int(M.bits(sc))] for w, tk, st, sc in seq] for seq in hyps]
+    return hashlib.sha256(json.dumps(canon, separators=(",", ":")).encode()).hexdigest()
+
+
+def returns_the_pinned(narrow, beam, n_calls):
+    """Every recorded call of the narrow statements ``narrow`` at ``beam``, made again with the one statement."""
+    calls = [c for c in PINS["calls"] if c["narrow"] in narrow and c["beam"] == beam]
+    assert len(calls) == n_calls
+    for c in calls:
+        em, em_len, ref, words, lm = pin_inputs(c["generator"])
+        kw = {k: float(v) for k, v in c["options"].items()}
+        if c["model"]:
+            kw.update(lm=lm, lm_weight=c["lm_weight"], lm_words=words)
+        if c["smear"]:
+            kw.update(smax=S.smear(ref, lm, words))
+        got = D.decode_batch(em, ref, em_len, beam=beam, nbest=beam, log_add=c["log_add"], **kw)
+        assert [len(h) for h in got] == c["n_hyp"], c
+        assert digest(got) == c["sha256"], c
 
 
 @pytest.mark.parametrize("beam", [1, 10, 16])
-def test_the_wide_statement_equals_lexbeam_lm_cases_and_lexbeam_smear_cases(beam):
-    em, em_len, ref, words, lm = lm_case()
-    for lm_weight in (0.0, 3.23):
-        kw = dict(beam=beam, nbest=beam, lm=lm, lm_weight=lm_weight, lm_words=words)
-        identical(W.decode_batch(em, ref, em_len, **kw), M.decode_batch(em, ref, em_len, **kw))
-        smax = S.smear(ref, lm, words)
-        identical(W.decode_batch(em, ref, em_len, smax=smax, **kw), S.decode_batch(em, ref, em_len, smax=smax, **kw))
+def test_the_statement_returns_what_lexbeam_cases_returned(beam):
+    """The model-free Viterbi statement on its own generators: the main case with and without options, the wide lexicon, ties."""
+    returns_the_pinned(("lexbeam_cases",), beam, 4)
 
 
 @pytest.mark.parametrize("beam", [1, 10, 16])
-def test_the_wide_statement_equals_lexbeam_logadd_cases(beam):
-    em, em_len, ref, words, lm = lm_case()
-    smax = S.smear(ref, lm, words)
-    for kw in (dict(), dict(lm=lm, lm_weight=3.23, lm_words=words), dict(lm=lm, lm_weight=3.23, lm_words=words, smax=smax)):
-        identical(W.decode_batch(em, ref, em_len, beam=beam, nbest=beam, log_add=True, **kw),
-                  A.decode_batch(em, ref, em_len, beam=beam, nbest=beam, log_add=True, **kw))
-    ref = L.Trie(L.PREFIX_DOUBLED, 32)
-    e = L.tie_emissions(7, L.PREFIX_DOUBLED, 12, 16, 32)
-    identical(W.decode_batch(e, ref, beam=beam, nbest=beam, beam_threshold=INF, log_add=True),
-              A.decode_batch(e, ref, beam=beam, nbest=beam, beam_threshold=INF, log_add=True))
+def test_the_statement_returns_what_lexbeam_lm_cases_and_lexbeam_smear_cases_returned(beam):
+    """With the model at lm_weight 0 and 3.23, unsmeared (lexbeam_lm_cases) and smeared (lexbeam_smear_cases)."""
+    returns_the_pinned(("lexbeam_lm_cases", "lexbeam_smear_cases"), beam, 4)
+
+
+@pytest.mark.parametrize("beam", [1, 10, 16])
+def test_the_statement_returns_what_lexbeam_logadd_cases_returned(beam):
+    """Log-add merging without a model, with it, with it and smearing, and on ties."""
+    returns_the_pinned(("lexbeam_logadd_cases",), beam, 4)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -161,10 +162,10 @@ def test_the_wide_gpu_cases_hold_more_than_16_hypotheses(name, n, T, beam, nbest
     (all sequences' frames counted together; ragged batches hold sequences of 1 or 2 frames, which cannot).  The `one` lexicon is
     there for the opposite reason -- a beam far larger than the candidates -- and must stay at or below 16.  The merge groups stay
     within the bound derived for the kernel's comment (4), and the 12 928-candidate frame is where the issue says it is."""
-    spellings, V, sil, _ = W.lexicon(name)
+    spellings, V, sil, _ = L.lexicon(name)
     em, em_len = W.wide_case_inputs(name, n, T)
     stats = []
-    W.decode_batch(em, L.Trie(spellings, V, 0, sil), em_len, stats=stats, beam=beam, nbest=nbest, **opts)
+    D.decode_batch(em, L.Trie(spellings, V, 0, sil), em_len, stats=stats, beam=beam, nbest=nbest, **opts)
     assert max(st.get("max_group", 0) for st in stats) <= 4
     if name == "one":
         assert W.wide_share(stats) == 0.0
@@ -181,8 +182,8 @@ def test_the_wide_gpu_cases_hold_more_than_16_hypotheses(name, n, T, beam, nbest
 def test_the_tie_cases_have_ties_that_only_a_wide_id_decides(name, n, T, beam):
     """tie_emissions at the sizes the GPU test uses, the uniform block at the length tie_emissions gives it (T' // 4 frames): ties
     decided by the id between candidates of which at least one has a rank of 16 or more occur at both beams."""
-    spellings, V, sil, _ = W.lexicon(name)
+    spellings, V, sil, _ = L.lexicon(name)
     stats = []
-    W.decode_batch(W.tie_case_inputs(name, n, T), L.Trie(spellings, V, 0, sil), stats=stats, beam=beam, nbest=beam, beam_threshold=INF)
+    D.decode_batch(W.tie_case_inputs(name, n, T), L.Trie(spellings, V, 0, sil), stats=stats, beam=beam, nbest=beam, beam_threshold=INF)
     assert sum(st.get("wide_ties", 0) for st in stats) >= 1
     assert W.wide_share(stats) >= 0.5

@@ -1,6 +1,6 @@
 """CPU tests of log-add merging in the lexicon CTC beam search: the host entry ``eec_ctc_log_add_host`` -- the very function the
 kernel calls -- against the numpy float32 statement of tests/lexbeam_logadd_cases.py bit for bit, that statement's accuracy against
-float64, the statement of the search against CTC itself (the forward log-likelihood, which no beam search computed), and that the
+float64, the statement of the search (tests/lexbeam_statement.py) against CTC itself (the forward log-likelihood, which no beam search computed), and that the
 new statement with log-add off is the Viterbi statement."""
 import os
 
@@ -9,18 +9,16 @@ import pytest
 
 import lexbeam_cases as L
 import lexbeam_logadd_cases as A
-from early_exit_transformer_amd import capi
+import lexbeam_statement as D
 from early_exit_transformer_amd.build import LIB_PATH
+from lexbeam_helpers import library
 
 INF = float("inf")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
 def host_log_add(lib, a, b):
@@ -70,7 +68,7 @@ def test_the_statement_sums_to_the_ctc_forward_likelihood(T):
     em = L.emissions(9, L.ONE_WORD, 4, T, 40)
     for s in range(4):
         stats = {}
-        hyps = A.decode(em[s], trie, beam=16, nbest=16, beam_threshold=INF, stats=stats)
+        hyps = D.decode(em[s], trie, beam=16, nbest=16, beam_threshold=INF, log_add=True, stats=stats)
         assert stats["max_alive"] <= 13 < 16
         for words in ([0], [0, 0]):
             labels = [c for w in words for c in L.ONE_WORD[w]]
@@ -92,8 +90,8 @@ def test_with_log_add_off_the_new_statement_is_the_viterbi_statement(name):
     trie = L.Trie(spellings, V, 0, sil)
     em = L.emissions(31, spellings, 3, 12, V, 0, -1 if sil is None else sil)
     kw = dict(beam=6, nbest=6, word_score=-0.5, sil_score=-0.25, beam_threshold=20.0)
-    want = L.decode_batch(em, trie, **kw)
-    got = A.decode_batch(em, trie, log_add=False, **kw)
+    want = D.decode_batch(em, trie, **kw)
+    got = D.decode_batch(em, trie, log_add=False, **kw)
     assert any(want) and len(got) == len(want)
     for g, w in zip(got, want):
         assert [(h[0], h[1], h[2], int(A.bits(h[3]))) for h in g] == [(h[0], h[1], h[2], int(A.bits(h[3]))) for h in w]
@@ -106,8 +104,8 @@ def test_the_two_merge_rules_really_differ():
     for spellings, V, sil, n, T, least in ((L.PREFIX_DOUBLED, 32, None, 24, 16, 4), (fixture, 256, 126, 12, 64, 1)):
         trie = L.Trie(spellings, V, 0, sil)
         em = L.emissions(5, spellings, n, T, V, 0, -1 if sil is None else sil)
-        vit = L.decode_batch(em, trie, beam=10)
-        add = A.decode_batch(em, trie, beam=10)
+        vit = D.decode_batch(em, trie, beam=10)
+        add = D.decode_batch(em, trie, beam=10, log_add=True)
         differ = sum(1 for v, a in zip(vit, add) if [h[0] for h in v] != [h[0] for h in a])
         print(f"V = {V}: the best transcript differs in {differ} of {n} sequences")
         assert differ >= least

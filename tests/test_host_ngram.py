@@ -1,28 +1,24 @@
 """CPU tests of the n-gram language model's host side (``lexicon.NGramLM``, ``eec_ngram_pack`` in csrc/ctc_lexbeam.hip): generated
 models written as ARPA text, read back and packed, against a reader of the documented image layout; the plain-Python statement of
-the search with a model (tests/lexbeam_lm_cases.py) against the model-free statement and against a textbook back-off in float64;
+the search with a model (tests/lexbeam_statement.py, tests/lexbeam_lm_cases.py) against the model-free one and against a textbook back-off in float64;
 and every refusal of the reader, the packer and the decoder entry, all decided before any device work."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import lexbeam_cases as L
 import lexbeam_lm_cases as M
-from early_exit_transformer_amd import capi
-from early_exit_transformer_amd.build import LIB_PATH
+import lexbeam_statement as D
 from early_exit_transformer_amd.lexicon import NGramLM, TokenTrie
+from lexbeam_helpers import library, same_hyps
 
 BAD_ARG, UNSUPPORTED, WORKSPACE = 10001, 10002, 10003
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
 @pytest.fixture(scope="module")
@@ -81,23 +77,15 @@ def test_lexicon_entries_with_one_string_share_an_lm_word_and_normalize_is_appli
 # ---------------------------------------------------------------------------------------------------------------------------
 # the statement is sound
 # ---------------------------------------------------------------------------------------------------------------------------
-def _same_hyps(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert len(x) == len(y)
-        for (w1, t1, s1, sc1), (w2, t2, s2, sc2) in zip(x, y):
-            assert w1 == w2 and t1 == t2 and s1 == s2 and M.bits(sc1) == M.bits(sc2)
-
-
 def test_without_a_model_the_statement_is_the_model_free_one():
     em, em_len, spellings, _ = L.main_case()
     trie = L.Trie(spellings, 256, 0, 126)
-    _same_hyps(M.decode_batch(em, trie, em_len, beam=10, nbest=10), L.decode_batch(em, trie, em_len, beam=10, nbest=10))
+    same_hyps(D.decode_batch(em, trie, em_len, beam=10, nbest=10, lm=None), D.decode_batch(em, trie, em_len, beam=10, nbest=10))
     for spellings, V, sil, kw in ((L.ONE_WORD, 40, None, dict(beam=2, nbest=2)), (L.PREFIX_DOUBLED, 32, None, dict(beam=10, nbest=10, beam_threshold=2.0)),
                                   (L.wide_lexicon(), 256, 126, dict(beam=16, nbest=16, sil_score=-0.5, word_score=1.5))):
         trie = L.Trie(spellings, V, 0, sil)
         em = L.emissions(9, spellings, 3, 16, V, 0, -1 if sil is None else sil)
-        _same_hyps(M.decode_batch(em, trie, **kw), L.decode_batch(em, trie, **kw))
+        same_hyps(D.decode_batch(em, trie, lm=None, **kw), D.decode_batch(em, trie, **kw))
 
 
 def test_the_statements_word_score_is_the_textbook_back_off():
@@ -106,7 +94,7 @@ def test_the_statements_word_score_is_the_textbook_back_off():
     em, em_len, spellings, words, lm = M.main_lm_case()
     trie = L.Trie(spellings, 256, 0, 126)
     stats = {}
-    M.decode_batch(em[40:52], trie, beam=10, nbest=10, lm=lm, lm_weight=1.0, lm_words=words, stats=stats)
+    D.decode_batch(em[40:52], trie, beam=10, nbest=10, lm=lm, lm_weight=1.0, lm_words=words, stats=stats)
     assert len(stats["pairs"]) > 500 and set(stats["depth"]) == {0, 1, 2}
     for ctx, v in stats["pairs"]:
         assert abs(float(M.lm_score(lm, 3, ctx, v)) - M.textbook(lm, ctx, v)) <= 1e-5, (ctx, v)

@@ -1,11 +1,8 @@
 """CPU tests of the LM look-ahead's host side (max trie smearing: ``eec_ctc_trie_smear`` in csrc/ctc_lexbeam.hip,
 ``NGramLM.smear``): the packed table against the plain-Python statement of tests/lexbeam_smear_cases.py bit for bit, every refusal
 of the host entry and of the decoder entry (all decided before any device work), and the statement itself: without a table it is
-the statement of lexbeam_lm_cases, with one it prunes differently (the {ab, cd} case) and -- where nothing is pruned -- returns the
+the unsmeared statement (tests/lexbeam_statement.py), with one it prunes differently (the {ab, cd} case) and -- where nothing is pruned -- returns the
 same complete hypotheses with the same score bits (the payments telescope)."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -13,9 +10,9 @@ import torch
 import lexbeam_cases as L
 import lexbeam_lm_cases as M
 import lexbeam_smear_cases as S
-from early_exit_transformer_amd import capi
-from early_exit_transformer_amd.build import LIB_PATH
+import lexbeam_statement as D
 from early_exit_transformer_amd.lexicon import NGramLM, TokenTrie
+from lexbeam_helpers import library, same_hyps
 
 BAD_ARG, UNSUPPORTED, WORKSPACE = 10001, 10002, 10003
 INF = float("inf")
@@ -23,19 +20,12 @@ INF = float("inf")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB_PATH):
-        from early_exit_transformer_amd.build import build_library
-        build_library()
-    return capi.load()
+    return library()
 
 
 def lexicon(name):
-    """(spellings, V, sil or None, words)"""
-    if name == "fixture":
-        _, words, spellings = L.load_fixture()
-        return spellings, 256, 126, words
-    spellings, V, sil = {"prefix": (L.PREFIX_DOUBLED, 32, None), "wide": (L.wide_lexicon(), 256, 126)}[name]
-    return spellings, V, sil, [f"w{i}" for i in range(len(spellings))]
+    """(spellings, V, sil, words); this module's ``fixture`` is the fixture lexicon with sil"""
+    return L.lexicon("fixture+sil" if name == "fixture" else name)
 
 
 def packed_pair(tmp_path, spellings, V, sil, words, lm):
@@ -52,12 +42,9 @@ def test_without_a_table_the_statement_is_the_unsmeared_one():
     em, em_len, spellings, words, lm = M.main_lm_case()
     trie = L.Trie(spellings, 256, 0, 126)
     kw = dict(beam=10, nbest=10, lm=lm, lm_weight=1.0, lm_words=words)
-    mine, theirs = S.decode_batch(em, trie, em_len, **kw), M.decode_batch(em, trie, em_len, **kw)
+    mine, theirs = D.decode_batch(em, trie, em_len, smax=None, **kw), D.decode_batch(em, trie, em_len, **kw)
     assert len(mine) == len(theirs) == 70 and sum(1 for h in mine if h) >= 10
-    for a, b in zip(mine, theirs):
-        assert len(a) == len(b)
-        for (w1, t1, s1, sc1), (w2, t2, s2, sc2) in zip(a, b):
-            assert w1 == w2 and t1 == t2 and s1 == s2 and M.bits(sc1) == M.bits(sc2)
+    same_hyps(mine, theirs)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -192,11 +179,11 @@ def test_at_beam_1_smearing_keeps_the_word_the_model_prefers():
     spellings, words, lm, em = S.pruning_case()
     trie = L.Trie(spellings, S.PRUNE_V, 0, None)
     kw = dict(beam=1, nbest=1, lm=lm, lm_weight=1.0, lm_words=words)
-    plain = S.decode(em, trie, **kw)
+    plain = D.decode(em, trie, **kw)
     assert [(h[0], h[1], h[2], float(h[3])) for h in plain] == [([1], [S.C_, S.D], [0, 1], -6.875)]
     smax = S.smear(trie, lm, words)
     assert [float(v) for v in smax] == [0.0, -1.0, -1.0, -5.0, -5.0]
-    smeared = S.decode(em, trie, smax=smax, **kw)
+    smeared = D.decode(em, trie, smax=smax, **kw)
     assert [(h[0], h[1], h[2], float(h[3])) for h in smeared] == [([0], [S.A, S.B_], [0, 1], -3.0)]
 
 
@@ -207,10 +194,10 @@ def test_an_in_word_and_a_word_end_candidate_that_tie_are_decided_by_the_id():
     trie = L.Trie(spellings, S.PRUNE_V, 0, None)
     smax = S.smear(trie, lm, words)
     kw = dict(lm=lm, lm_weight=1.0, lm_words=words, smax=smax)
-    assert S.decode(em, trie, beam=1, nbest=1, **kw) == []
-    two = S.decode(em, trie, beam=2, nbest=2, **kw)
+    assert D.decode(em, trie, beam=1, nbest=1, **kw) == []
+    two = D.decode(em, trie, beam=2, nbest=2, **kw)
     assert [(h[0], float(h[3])) for h in two] == [([0], -3.0)]
-    assert S.decode(em, trie, beam=1, nbest=1, lm=lm, lm_weight=1.0, lm_words=words) != []  # unsmeared: cd, as before
+    assert D.decode(em, trie, beam=1, nbest=1, lm=lm, lm_weight=1.0, lm_words=words) != []  # unsmeared: cd, as before
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -227,8 +214,8 @@ def test_where_nothing_is_pruned_the_payments_telescope(T):
         smax = S.smear(trie, lm, words)
         kw = dict(beam=16, nbest=16, beam_threshold=INF, lm=lm, lm_weight=2.0, lm_words=words)
         s_plain, s_smear = {}, {}
-        plain = S.decode(em[0], trie, stats=s_plain, **kw)
-        smeared = S.decode(em[0], trie, stats=s_smear, smax=smax, **kw)
+        plain = D.decode(em[0], trie, stats=s_plain, **kw)
+        smeared = D.decode(em[0], trie, stats=s_smear, smax=smax, **kw)
         assert s_plain["max_candidates"] <= 16 and s_smear["max_candidates"] <= 16
         assert plain and S.as_set(plain) == S.as_set(smeared) and len(S.as_set(plain)) == len(plain)
 
@@ -238,5 +225,5 @@ def test_three_frames_pass_the_beam_and_the_count_shows_it():
     spellings, words, lm, em = S.telescoping_case(0, 3)
     trie = L.Trie(spellings, S.PRUNE_V, 0, None)
     stats = {}
-    S.decode(em[0], trie, beam=16, nbest=16, beam_threshold=INF, lm=lm, lm_weight=2.0, lm_words=words, stats=stats, smax=S.smear(trie, lm, words))
+    D.decode(em[0], trie, beam=16, nbest=16, beam_threshold=INF, lm=lm, lm_weight=2.0, lm_words=words, stats=stats, smax=S.smear(trie, lm, words))
     assert stats["max_candidates"] > 16
