@@ -4,10 +4,14 @@
 __version__ = "0.1.0"
 
 _CONTEXT = ("ContextGraph", "ContextBiasSession")  # contextual biasing (context.py), resolved at first use: importing the package stays light
+_LM_FUSION = ("TokenLM", "LMFusionSession")  # shallow fusion with a token-level n-gram model (lm_fusion.py), likewise
 
 
 def __getattr__(name):
     if name in _CONTEXT:
         from . import context
         return getattr(context, name)
+    if name in _LM_FUSION:
+        from . import lm_fusion
+        return getattr(lm_fusion, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

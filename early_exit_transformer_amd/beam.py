@@ -46,6 +46,7 @@ import torch
 from torch import Tensor
 
 from .context import ContextBiasSession
+from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
 from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
 
@@ -78,8 +79,9 @@ def sequence_length_penalty(length: int, alpha: float = 0.6) -> float:
 class CTCHypothesis:
     """One CTC beam-search hypothesis, with the attribute names of torchaudio's ``CUCTCHypothesis`` (tokens: List[int] without
     blanks / repeats, words: List[str] -- empty here, as for a lexicon-free decoder --, score: float).  ``bias`` is set by a search
-    under a context graph only: the contextual bias the hypothesis was ranked with, beside its ``score``."""
-    __slots__ = ("tokens", "words", "score", "text", "bias")
+    under a context graph only: the contextual bias the hypothesis was ranked with, beside its ``score``; ``fusion`` by a search under
+    a token-level language model only: its shallow-fusion score, in the same way."""
+    __slots__ = ("tokens", "words", "score", "text", "bias", "fusion")
 
     def __init__(self, tokens, words, score, text=None):
         self.tokens, self.words, self.score, self.text = tokens, words, score, text
@@ -101,6 +103,12 @@ class RescoredList(NamedTuple):
     ctc: List[float]
     att: List[float]
     joint: List[float]
+
+
+class FusedRescoredList(RescoredList):
+    """``RescoredList`` of a two-pass search under a token-level language model: it also carries ``fusion``, the shallow-fusion
+    scores of the list, which entered ``joint``."""
+    fusion: List[float]
 
 
 def _snapped_texts(token_lists, lexicon, detokenize) -> List[str]:
@@ -164,14 +172,24 @@ def _bias_session(context, graph_of, E: int, B: int, beam: int, V: int):
     return ContextBiasSession(context, E * B, beam, graph_of)
 
 
-def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None, bias=None):
+def _lm_session(fusion, n: int, beam: int, V: int) -> Optional[LMFusionSession]:
+    """The ``LMFusionSession`` of n lockstep searches under ``fusion`` = (model, weight, bonus) (``BeamInference._fusion``), or None."""
+    if fusion is None:
+        return None
+    lm, w, ts = fusion
+    check_lm("shallow fusion", lm, V, beam, w, ts)
+    return LMFusionSession(lm, n, beam, w, ts)
+
+
+def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None, bias=None, lm=None):
     """``max_length`` steps of n independent beam searches in lockstep, none of which finalises a beam on the way:
     ``step(last [n, R], parent [n, R] | None)`` returns the next token's log-probs [n, R, V] of every live beam.  The
     bookkeeping of a step is ``beam_select`` over two token buffers.  Returns ``(final_tokens, final_scores, best_tokens)``
     per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s.
     ``bias`` (a ``ContextBiasSession``, or None): its ``step`` adds the contextual bias to the step's log-probs before the selection,
     and after the last step ``bias.final`` takes the bonus of a still open partial match back (at the last step's penalty), as an
-    EOS would have."""
+    EOS would have.  ``lm`` (an ``LMFusionSession``, or None): its ``step`` adds the language model's increments in the same place;
+    the two compose, both are additive."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
@@ -181,6 +199,8 @@ def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, al
         logp = step(last, parent)
         if bias is not None:
             logp = bias.step(logp, last, parent)
+        if lm is not None:
+            logp = lm.step(logp, last, parent)
         scores, parent, last = beam_select(logp, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
     if bias is not None:  # every row is final as it stands: an open partial match gives its provisional bonus back
         scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
@@ -190,13 +210,14 @@ def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, al
     return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
 
 
-def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float, bias=None):
+def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float, bias=None,
+                           lm=None):
     """``max_length`` steps of n one-pass joint CTC / attention beam searches in lockstep (include/eec.h, "CTC prefix scores"):
     ``step(last [n, R], parent [n, R] | None)`` returns the decoder's log-probs [n, R, V] of every beam, ``prefix.step`` mixes in
     the CTC prefix scores and closes the beams that took EOS, ``beam_select`` ranks the result as in ``_lockstep_search``.  After
     ``max_length`` steps every row is final as it stands; a row holds only PAD after its EOS; the best beam is the one with the
     highest score, ties to the lower index.  Returns ``(final_tokens, final_scores, best_tokens)`` per search.  ``bias``: as in
-    ``_lockstep_search``, applied after ``prefix.step``."""
+    ``_lockstep_search``, applied after ``prefix.step``; ``lm`` after that."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
@@ -206,6 +227,8 @@ def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int,
         local = prefix.step(step(last, parent), last, parent)
         if bias is not None:
             local = bias.step(local, last, parent)
+        if lm is not None:
+            local = lm.step(local, last, parent)
         scores, parent, last = beam_select(local, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
     if bias is not None:  # rows that never took EOS give the provisional bonus of an open partial match back (0 for the others)
         scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
@@ -243,14 +266,23 @@ class BeamInference:
     LM_WEIGHT = 1.0  # util/beam_infer.py:40 (its comment keeps 3.23, the value of the "bigger LM" setting)
 
     def __init__(self, args=None, trie: Optional[TokenTrie] = None, lm=None, smearing: Optional[str] = None,
-                 log_add: Optional[bool] = None):
+                 log_add: Optional[bool] = None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """``lm``: an ``NGramLM``, or the path of an ARPA file (None: ``args.lm`` if there is one) that is read at the first use
         against the trie in use.  ``smearing``: None (then ``args.lm_smearing`` if there is one) or ``"max"``: LM look-ahead by max
         trie smearing in ``ctc_predict`` / ``ctc_predict_``.  The third-party decoder always smears; here the default is off, so
         a model alone decodes as before.  Without a model there is nothing to smear and the setting is not used.
         ``log_add``: None (then ``args.lm_log_add`` if there is one, else False) or a bool: log-add instead of Viterbi merging in
-        ``ctc_predict`` / ``ctc_predict_``.  ``beam_predict`` always merges by log-add, as the reference's decoder does."""
+        ``ctc_predict`` / ``ctc_predict_``.  ``beam_predict`` always merges by log-add, as the reference's decoder does.
+        ``token_lm``: a ``lm_fusion.TokenLM``, or the path of an ARPA file over the pieces (None: ``args.token_lm`` if there is one;
+        a path is read at the first use against the lines of ``args.tokens``, with blank 0 and the special tokens of ``args``) --
+        shallow fusion in the lexicon-free searches: ``ctc_cuda_predict``, ``ctc_adaptive_predict``, ``decode_batch`` (plain and
+        joint), ``decode_all_exits``, the lockstep searches and the two-pass rescoring, each of which also takes the three keywords
+        per call.  ``token_lm_weight`` (None: ``args.token_lm_weight``, else 0.3: customary, a choice and not tuned) and
+        ``token_score`` (None: ``args.token_score``, else 0: the per-token insertion bonus).  Without a model nothing changes."""
         self.args = args
+        self._token_lm = token_lm if token_lm is not None else getattr(args, "token_lm", None)
+        self._token_lm_weight = token_lm_weight if token_lm_weight is not None else getattr(args, "token_lm_weight", None)
+        self._token_score = token_score if token_score is not None else getattr(args, "token_score", None)
         self._trie = trie
         self._lm = lm if lm is not None else getattr(args, "lm", None)
         self._smearing = smearing if smearing is not None else getattr(args, "lm_smearing", None)
@@ -280,6 +312,31 @@ class BeamInference:
         if self._lm_read is None or self._lm_read[0] is not trie:
             self._lm_read = (trie, NGramLM.from_arpa(self._lm, trie))
         return self._lm_read[1]
+
+    def _fusion(self, token_lm=None, token_lm_weight=None, token_score=None):
+        """(model, weight, bonus) of a call's shallow fusion -- the call's keywords before the constructor's --, or None without a
+        model.  A path is read once."""
+        lm = token_lm if token_lm is not None else self._token_lm
+        if lm is None:
+            if token_lm_weight is not None or token_score is not None:
+                raise ValueError("token_lm_weight / token_score weigh token_lm=, which was not given")
+            return None
+        if not isinstance(lm, TokenLM):
+            if self.args is None or not hasattr(self.args, "tokens"):
+                raise ValueError("token_lm is a path: its pieces are the lines of args.tokens, which is missing")
+            with open(self.args.tokens, encoding="utf-8") as f:
+                pieces = [line.rstrip("\r\n") for line in f]
+            lm = TokenLM.from_arpa(lm, pieces, blank=0, sos=self._arg(None, "trg_sos_idx"), eos=self._arg(None, "trg_eos_idx"),
+                                   pad=self._arg(None, "trg_pad_idx"))
+            if token_lm is None:
+                self._token_lm = lm
+        w = token_lm_weight if token_lm_weight is not None else self._token_lm_weight
+        ts = token_score if token_score is not None else self._token_score
+        return lm, float(DEFAULT_LM_WEIGHT if w is None else w), float(0.0 if ts is None else ts)
+
+    @staticmethod
+    def _fusion_kw(fusion) -> dict:
+        return {} if fusion is None else {"token_lm": fusion[0], "token_lm_weight": fusion[1], "token_score": fusion[2]}
 
     def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size, lm_weight=None, log_add=None, word_score=None):
         """(transcript of the best hypothesis per utterance, scores [B, nbest] and n_hyp [B] on the host)."""
@@ -335,7 +392,7 @@ class BeamInference:
 
     def ctc_cuda_predict(self, emission: Tensor, tokens=None, beam_size: Optional[int] = None, lexicon=None,
                          detokenize=None, lengths: Optional[Tensor] = None, nbest: Optional[int] = None, context=None,
-                         graph_of=None) -> List[List["CTCHypothesis"]]:
+                         graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None) -> List[List["CTCHypothesis"]]:
         """util/beam_infer.py:102-112: the nbest (= 1) beam-search hypotheses of one exit's log-probs ``emission`` [B, T', V],
         input length T' for every utterance (``lengths`` [B] in encoder frames: the decoder's ``encoder_out_lens``), beam ``args.beam_size``, blank_skip_threshold 0.95 -- per utterance a list of
         hypothesis objects with ``.tokens`` / ``.words`` / ``.score`` like torchaudio's, so the reference's call sites
@@ -347,9 +404,14 @@ class BeamInference:
         many hypotheses per utterance, best first, as torchaudio's ``nbest`` -- the beam the same search ends with
         (``ctc_beam_decode(nbest=)``), so an utterance whose final beam is smaller returns fewer.  ``context`` (a
         ``context.ContextGraph``; None: unchanged) and ``graph_of`` [B]: the search is biased towards the graph's phrases
-        (``ctc_beam_decode(context=)``); ``.score`` stays the CTC log-probability and every hypothesis also carries ``.bias``."""
+        (``ctc_beam_decode(context=)``); ``.score`` stays the CTC log-probability and every hypothesis also carries ``.bias``.
+        ``token_lm`` / ``token_lm_weight`` / ``token_score`` (or the constructor's): shallow fusion with a token-level n-gram model
+        (``ctc_beam_decode(lm=)``); every hypothesis then carries ``.fusion`` beside its ``.score``.  Not together with ``context``."""
         beam = self._arg(beam_size, "beam_size")
         ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
+        fusion = self._fusion(token_lm, token_lm_weight, token_score)
+        if fusion is not None:
+            ctx.update(lm=fusion[0], lm_weight=fusion[1], token_score=fusion[2])
         out = [t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths, nbest=nbest,
                                                 **ctx)]
         if nbest is None:  # the best prefix alone: an N-best list of one
@@ -359,7 +421,7 @@ class BeamInference:
                 for b in range(tok.size(0))]
         for b, row in enumerate(hyps if bias else []):
             for r, h in enumerate(row):
-                h.bias = float(bias[0][b, r])
+                setattr(h, "bias" if fusion is None else "fusion", float(bias[0][b, r]))
         if lexicon is not None and detokenize is not None:
             flat = [h for row in hyps for h in row]
             for h, text in zip(flat, _snapped_texts([h.tokens for h in flat], lexicon, detokenize)):
@@ -496,16 +558,18 @@ class BeamInference:
     @torch.no_grad()
     def decode_all_exits(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
                          ctc_weight: Optional[float] = None, joint_ctc_weight: Optional[float] = None, context=None, graph_of=None,
-                         **kw) -> List[List[int]]:
+                         token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None, **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
         ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits).  ``ctc_weight``: the best beam of every exit is
         chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass).
         ``joint_ctc_weight`` (None: unchanged): the search itself is the one-pass joint one (``joint_search_exits``; ``min_length=``
         defaults to 0 there); not together with ``ctc_weight``.  ``context`` / ``graph_of`` [1]: contextual biasing of the lockstep
-        searches (``beam_search_batch``); ValueError where only the step-by-step ``beam_search`` could serve the call."""
+        searches (``beam_search_batch``); ValueError where only the step-by-step ``beam_search`` could serve the call.  ``token_lm`` /
+        ``token_lm_weight`` / ``token_score``: shallow fusion in the lockstep searches, under the same condition."""
         if max_length is None:
             max_length = default_max_length(spec.size(1))
         ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
+        ctx.update(self._fusion_kw(self._fusion(token_lm, token_lm_weight, token_score)))
         if joint_ctc_weight is not None:
             _check_joint_weight(joint_ctc_weight, ctc_weight)
             logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=True, want_taps=True, n_groups=model._cfg.n_exits)[:2]
@@ -527,7 +591,7 @@ class BeamInference:
             if together is not None:
                 return [best for _, _, best in together]
         if ctx:
-            raise ValueError("decode_all_exits: contextual biasing runs in the lockstep searches only, and none serves this call "
+            raise ValueError("decode_all_exits: contextual biasing and shallow fusion run in the lockstep searches only, and none serves this call "
                              "(kv_cache=False, max_length - 1 > min_length, or no session group for this model / geometry)")
         found = [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw) for n in exits]
         if ctc_weight is None:
@@ -540,7 +604,7 @@ class BeamInference:
                           max_length: int = 500, min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
                           ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
-                          context=None, graph_of=None):
+                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """``beam_search`` for several exits of one utterance in lockstep: the searches are independent, so every decoder
         launch and every bookkeeping op covers all of them (``model.decoder_session_group``).  Returns the list of
         ``(final_tokens, final_scores, best_tokens)`` per exit, the same values as ``beam_search`` exit by exit -- or None
@@ -557,7 +621,8 @@ class BeamInference:
             return None
         return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha,
                                 self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1),
-                                _bias_session(context, graph_of, len(layer_ns), 1, beam, V))
+                                _bias_session(context, graph_of, len(layer_ns), 1, beam, V),
+                                _lm_session(self._fusion(token_lm, token_lm_weight, token_score), len(layer_ns), beam, V))
 
     @staticmethod
     def _pick(ctc_weight, emission, emission_len, E: int, B: int):
@@ -578,7 +643,7 @@ class BeamInference:
                           min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
                           ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
-                          context=None, graph_of=None):
+                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """``beam_search_exits`` for every utterance of a padded batch at once: ``taps`` [E, B, T', D] (or E tensors [B, T', D]),
         exit ``layer_ns[e]``'s encoder output of every utterance.  The E * B searches are independent and run in lockstep through
         one ``model.decoder_batch_session`` (every decoder launch covers all of them) and one ``eec_beam_select`` per step.
@@ -590,7 +655,9 @@ class BeamInference:
         (``emission_len`` [B]: their frames, None = T'); ``final_tokens`` / ``final_scores`` are untouched.  ``context`` (a
         ``context.ContextGraph`` built with ``eos=`` / ``pad=``; None: unchanged, no new launch) and ``graph_of`` [B]: one
         ``eec_context_bias_step`` per step adds the contextual bias to the step's log-probs before the selection, so it shares the
-        step's length penalty (include/eec.h, "Contextual biasing")."""
+        step's length penalty (include/eec.h, "Contextual biasing").  ``token_lm`` (a ``lm_fusion.TokenLM`` built with the decoder's
+        ``sos=`` / ``eos=`` / ``pad=``; or the constructor's), ``token_lm_weight``, ``token_score``: shallow fusion -- one
+        ``eec_lm_fusion_step`` per step in the same place (include/eec.h, "Shallow fusion"); it composes with ``context``."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
             return None
@@ -603,7 +670,8 @@ class BeamInference:
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
         found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B),
-                                 _bias_session(context, graph_of, E, B, beam, V))
+                                 _bias_session(context, graph_of, E, B, beam, V),
+                                 _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     def _joint_args(self, emission, emission_len, E: int, B: int, V: int, joint_ctc_weight, EOS_token, PAD_token, blank: int):
@@ -621,7 +689,8 @@ class BeamInference:
     def joint_search_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor],
                            joint_ctc_weight: float, max_length: int, min_length: int = 0, vocab_size: Optional[int] = None,
                            SOS_token: Optional[int] = None, EOS_token: Optional[int] = None, PAD_token: Optional[int] = None,
-                           beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0, context=None, graph_of=None):
+                           beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0, context=None, graph_of=None,
+                           token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """One-pass joint CTC / attention decoding (Watanabe et al. 2017; include/eec.h states the semantics) of every exit and
         utterance of a padded batch in lockstep: ``taps`` as for ``beam_search_batch``, ``emission`` [E, B, T', V] the exits' CTC
         log-probs of the same encoder pass (``emission_len`` [B]: their frames, None = T').  At every step the local score of a
@@ -631,7 +700,7 @@ class BeamInference:
         ``eec_ctc_prefix_step`` and one ``eec_beam_select`` per step.  Returns ``out[b][e] = (final_tokens, final_scores,
         best_tokens)``; rows are ``max_length + 1`` long, SOS first.  ValueError where no batch session exists for the model /
         geometry / device: there is no reference search to fall back to.  ``context`` / ``graph_of`` [B]: as in ``beam_search_batch``,
-        applied after the CTC prefix scores."""
+        applied after the CTC prefix scores; ``token_lm`` / ``token_lm_weight`` / ``token_score`` too."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
         session = model.decoder_batch_session(taps, layer_ns, max_length) if max_length >= 1 and hasattr(model, "decoder_batch_session") else None
         if session is None or beam > session.max_beams:
@@ -644,7 +713,8 @@ class BeamInference:
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
         found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha,
-                                       _bias_session(context, graph_of, E, B, beam, V))
+                                       _bias_session(context, graph_of, E, B, beam, V),
+                                       _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @torch.no_grad()
@@ -652,7 +722,7 @@ class BeamInference:
                            emission_len: Optional[Tensor], joint_ctc_weight: float, max_length: int, min_length: int = 0,
                            vocab_size: Optional[int] = None, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                            PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0,
-                           context=None, graph_of=None):
+                           context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """``joint_search_batch`` for the exits of ONE utterance (``model.decoder_session_group``): ``encoder_outputs[i]`` [1, T', D]
         is exit ``layer_ns[i]``'s encoder output, ``emission`` [len(layer_ns), 1, T', V].  Returns the list of ``(final_tokens,
         final_scores, best_tokens)`` per exit; ValueError where no session group exists."""
@@ -666,12 +736,14 @@ class BeamInference:
         w, eos, pad, em, em_len, blank = self._joint_args(emission, emission_len, n, 1, V, joint_ctc_weight, EOS_token, PAD_token, blank)
         prefix = ctc_prefix_session(em, em_len, beam, w, eos, pad, blank=blank, min_length=min_length)
         return _joint_lockstep_search(group.step, prefix, n, encoder_outputs[0].device, max_length, sos, eos, pad, beam, alpha,
-                                      _bias_session(context, graph_of, n, 1, beam, V))
+                                      _bias_session(context, graph_of, n, 1, beam, V),
+                                      _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
                      max_batch: Optional[int] = None, ctc_weight: Optional[float] = None, lexicon=None, detokenize=None,
-                     joint_ctc_weight: Optional[float] = None, context=None, graph_of=None, **kw) -> List[List[List[int]]]:
+                     joint_ctc_weight: Optional[float] = None, context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None,
+                     **kw) -> List[List[List[int]]]:
         """What inference.py:18-62 (evaluate_batch_ae) computes for a padded batch: the best beam of every exit of every
         utterance, ``out[b][e]``.  ``spec`` [B, n_mels, T], ``valid_len`` [B].  The encoder runs once per chunk of at most
         ``max_batch`` utterances (taps of all exits), then ``beam_search_batch`` decodes all exits and utterances of the chunk in
@@ -687,12 +759,14 @@ class BeamInference:
         with ``ctc_weight``; ValueError where no batch session serves the model (there is no reference search to fall back to).
         ``context`` (a ``context.ContextGraph`` over the decoder's vocabulary, built with ``eos=`` / ``pad=``; None: unchanged) and
         ``graph_of`` [B] (a graph of a bank per utterance, the same for all its exits): the searches are biased towards the graph's
-        phrases, plain and joint alike (``beam_search_batch``)."""
+        phrases, plain and joint alike (``beam_search_batch``).  ``token_lm`` / ``token_lm_weight`` / ``token_score`` (or the
+        constructor's): shallow fusion with a token-level n-gram model in the same searches; without a model nothing changes."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
         if context is None and graph_of is not None:
             raise ValueError("decode_batch: graph_of chooses among the graphs of context=, which was not given")
         rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(-1)
+        fused = self._fusion_kw(self._fusion(token_lm, token_lm_weight, token_score))
         E = model._cfg.n_exits
         exits = list(range(1, E + 1))
         valid_len = valid_len.reshape(-1)
@@ -704,6 +778,7 @@ class BeamInference:
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             together, lockstep = None, _lockstep_kw(kw)
             ctx = {} if context is None else {"context": context, "graph_of": None if rows_of is None else rows_of[c0:c0 + step]}
+            ctx.update(fused)
             if joint_ctc_weight is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
                 together = self.joint_search_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), joint_ctc_weight,
@@ -717,7 +792,7 @@ class BeamInference:
                 together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc, **ctx)
                 del taps, logp, ctc
             if together is None:
-                one = lambda b: {} if not ctx else {"context": context, "graph_of": None if rows_of is None else rows_of[c0 + b: c0 + b + 1]}  # noqa: E731
+                one = lambda b: dict(fused) if context is None else {"context": context, "graph_of": None if rows_of is None else rows_of[c0 + b: c0 + b + 1], **fused}  # noqa: E731
                 out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight, **one(b), **kw)
                         for b in range(sp.size(0))]
             else:
@@ -735,7 +810,8 @@ class BeamInference:
     @torch.no_grad()
     def rescore_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor], nbest: int,
                       rescoring_ctc_weight: float, beam_size: Optional[int] = None, SOS_token: Optional[int] = None,
-                      EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30, context=None, graph_of=None):
+                      EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30, context=None, graph_of=None,
+                      token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
         """Two-pass decoding of exits ``layer_ns`` for every utterance of a padded batch: ``taps`` [E, B, T', D] (or E tensors
         [B, T', D]) and ``emission`` [E, B, T', V], the exits' encoder outputs and CTC log-probs of one encoder pass
         (``emission_len`` [B]: their frames, None = T').  First pass: the N-best lists of all E * B emissions in ONE prefix beam
@@ -747,7 +823,10 @@ class BeamInference:
         normalisation.  Returns ``out[b][e] = (best_tokens, RescoredList)``: the chosen ids (no SOS / EOS), and ``tokens``,
         ``ctc``, ``att``, ``joint`` of that search's whole list, best CTC score first.  ``context`` (a ``context.ContextGraph`` over
         the CTC vocabulary; None: unchanged) and ``graph_of`` [B]: the first pass is the biased search (``ctc_beam_decode(context=)``:
-        the list is ordered by CTC score + bias) and ``joint = (1 - w) * att + w * ctc + bias`` in fp64, ties to the lower rank."""
+        the list is ordered by CTC score + bias) and ``joint = (1 - w) * att + w * ctc + bias`` in fp64, ties to the lower rank.
+        ``token_lm`` / ``token_lm_weight`` / ``token_score`` (or the constructor's; not together with ``context``): the first pass is the
+        fused search (``ctc_beam_decode(lm=)``), ``joint = (1 - w) * att + w * ctc + fusion`` in fp64, and each list is a
+        ``FusedRescoredList`` that also carries ``fusion``."""
         w = float(rescoring_ctc_weight)
         if not 0.0 <= w <= 1.0:
             raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
@@ -766,20 +845,24 @@ class BeamInference:
             raise ValueError("rescore_batch: graph_of chooses among the graphs of context=, which was not given")
         rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(B).repeat(E)
         found = self._rescore(model, emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, groups, nbest, w, beam, sos, eos, blank,
-                              max_workspace_bytes, context, rows_of)
+                              max_workspace_bytes, context, rows_of, self._fusion(token_lm, token_lm_weight, token_score))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @staticmethod
     def _rescore(model, em: Tensor, em_len: Optional[Tensor], groups, nbest: int, w: float, beam: int, sos: int, eos: int, blank: int,
-                 max_workspace_bytes: int, context=None, graph_of=None):
+                 max_workspace_bytes: int, context=None, graph_of=None, fusion=None):
         """The two passes over n searches (``em`` [n, T', V], ``em_len`` [n] or None): one N-best launch for all of them, then one
         ``score_hypotheses`` call per ``(layer_n, enc [m, T', D], rows int64 [m])`` of ``groups`` -- the searches ``rows`` belong to
         exit ``layer_n``, search ``rows[i]`` has the memory ``enc[i]``; every search is in exactly one group.  Returns the list
         of ``(best_tokens, RescoredList)`` per search.  ``context`` / ``graph_of`` [n]: the first pass is biased and its bias enters
-        ``joint``."""
+        ``joint``.  ``fusion`` = (model, weight, bonus): the first pass is fused instead and its fusion scores enter ``joint``."""
         dev = em.device
         bias = None
-        if context is None:
+        if fusion is not None:
+            tokens, counts, ctc, n_hyp, bias = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
+                                                               context=context, graph_of=graph_of, lm=fusion[0], lm_weight=fusion[1],
+                                                               token_score=fusion[2])
+        elif context is None:
             tokens, counts, ctc, n_hyp = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest)
         else:
             tokens, counts, ctc, n_hyp, bias = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
@@ -801,11 +884,16 @@ class BeamInference:
         joint = torch.where(present, joint, torch.full_like(joint, -float("inf")))
         best = _first_argmax(joint).cpu().tolist()
         tokens, counts, n_hyp, ctc, att, joint = (t.cpu().tolist() for t in (tokens, counts, n_hyp, ctc, att, joint))
+        fused = None if fusion is None else bias.cpu().tolist()
 
         def one(i):
             k = n_hyp[i]
             toks = [tokens[i][r][: counts[i][r]] for r in range(k)]
-            return toks[best[i]], RescoredList(toks, ctc[i][:k], att[i][:k], joint[i][:k])
+            if fused is None:
+                return toks[best[i]], RescoredList(toks, ctc[i][:k], att[i][:k], joint[i][:k])
+            lst = FusedRescoredList(toks, ctc[i][:k], att[i][:k], joint[i][:k])
+            lst.fusion = fused[i][:k]
+            return toks[best[i]], lst
         return [one(i) for i in range(em.size(0))]
 
     @torch.no_grad()
@@ -816,7 +904,8 @@ class BeamInference:
         (``nbest`` of a beam of ``beam_size``, default ``max(args.beam_size, nbest)``) that scores best under ``(1 - w) * attention +
         w * CTC``.  One encoder pass per chunk of at most ``max_batch`` utterances (taps and log-probs of all exits), one N-best
         launch and one ``score_hypotheses`` call per exit; no decoder step loop.  ``rescoring_ctc_weight`` defaults to 0.5, WeNet's
-        customary value; it is not tuned here.  The ids carry no SOS / EOS.  ``lexicon`` / ``detokenize`` as in ``decode_batch``."""
+        customary value; it is not tuned here.  The ids carry no SOS / EOS.  ``lexicon`` / ``detokenize`` as in ``decode_batch``.
+        ``token_lm=`` / ``token_lm_weight=`` / ``token_score=`` go to ``rescore_batch`` with the other keywords."""
         if beam_size is None:
             beam_size = max(int(getattr(self.args, "beam_size", nbest)), nbest)
         E = model._cfg.n_exits
@@ -844,18 +933,19 @@ class BeamInference:
     # -- adaptive inference: every utterance decoded at the one exit it left the encoder at --------------------------------
     @torch.no_grad()
     def ctc_adaptive_predict(self, model, src: Tensor, lengths: Tensor, threshold=None, beam_size: Optional[int] = None, lexicon=None,
-                             detokenize=None, context=None, graph_of=None, **adaptive) -> Tuple[List[List["CTCHypothesis"]], Tensor]:
+                             detokenize=None, context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None,
+                             **adaptive) -> Tuple[List[List["CTCHypothesis"]], Tensor]:
         """``model.forward_adaptive(src, lengths, threshold, **adaptive)`` (``criterion=``, ``min_exit=``, ``max_exit=``, ``exit_of=``,
         ``compact=``) and then ONE ``ctc_cuda_predict`` over the B emissions of the chosen exits, over the encoder's own frame counts
         -- where decoding every exit of ``forward`` searches E * B sequences.  Returns ``(hypotheses, exit_of)``: per utterance the
         list ``ctc_cuda_predict`` returns, and the 0-based exit int32 [B] it was decoded at.  ``context`` / ``graph_of`` [B]: as in
-        ``ctc_cuda_predict``."""
+        ``ctc_cuda_predict``; ``token_lm`` / ``token_lm_weight`` / ``token_score`` too."""
         if adaptive.get("want_taps"):
             raise ValueError("ctc_adaptive_predict: the CTC search reads no taps")
         out = model.forward_adaptive(src, lengths, threshold, **adaptive)
         em_len = encoder_lengths(lengths.to(out.logp.device), out.logp.size(1))
         return self.ctc_cuda_predict(out.logp, beam_size=beam_size, lexicon=lexicon, detokenize=detokenize, lengths=em_len, context=context,
-                                     graph_of=graph_of), out.exit_of
+                                     graph_of=graph_of, token_lm=token_lm, token_lm_weight=token_lm_weight, token_score=token_score), out.exit_of
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

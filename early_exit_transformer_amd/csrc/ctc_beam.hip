@@ -26,21 +26,42 @@
 // work-item c reads delta[state_i][c] of every live beam i (one coalesced row per beam), the owner of a chosen extension reads its one
 // `next` entry and recomputes the extension's CTC mass from lpc, since the number that was ranked is the key.  Without the switch
 // every line of it is compiled out: the object of this file is the one it was.
+// Shallow fusion: EEC_CTC_LM compiles it a third time (ctc_beam_lm.hip) into ctc_beam_lm_kernel and the _lm entries (include/eec.h,
+// "Shallow fusion").  The same two fields and the same ranking by key -- the lines both switches share stand under EEC_CTC_BIAS --;
+// the per-label increment is a back-off walk instead of a table row, so a beam's V increments are kept in LDS (work-item c owns
+// column c of every row: no barrier of their own) and follow the beam through stays and skipped frames; only a new extension walks.
 #include <limits.h>
 
 #include "../../include/eec.h"
 #include "eec_host.h"
 #include "eec_kernels.h"
+#if defined(EEC_CTC_CTX) && defined(EEC_CTC_LM)
+#error "a context graph and a language model in one CTC search are not served"
+#endif
 #ifdef EEC_CTC_CTX
 #include "eec_ctx.h"
+#define EEC_CTC_BIAS 1
 #define CbBeam CbBeamCtx
 #define ctc_beam_kernel ctc_beam_ctx_kernel
 #define launch_ctc_beam launch_ctc_beam_ctx
-#define CB_CTX(...) , __VA_ARGS__  // the two fields a beam grows by, at the end of its initialiser
 #define CB_CTX_ARGS(...) , __VA_ARGS__
+#define CB_LM_ARGS(...)
+#elif defined(EEC_CTC_LM)
+#include "eec_lm.h"
+#define EEC_CTC_BIAS 1
+#define CbBeam CbBeamLm
+#define ctc_beam_kernel ctc_beam_lm_kernel
+#define launch_ctc_beam launch_ctc_beam_lm
+#define CB_CTX_ARGS(...)
+#define CB_LM_ARGS(...) , __VA_ARGS__
+#else
+#define CB_CTX_ARGS(...)
+#define CB_LM_ARGS(...)
+#endif
+#ifdef EEC_CTC_BIAS
+#define CB_CTX(...) , __VA_ARGS__  // the two fields a beam grows by, at the end of its initialiser
 #else
 #define CB_CTX(...)
-#define CB_CTX_ARGS(...)
 #endif
 
 namespace eec {
@@ -52,7 +73,7 @@ struct CbBeam {
   float pb, pnb;
   int last, len;
   unsigned long long hash;
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
   int state;
   float bias;
 #endif
@@ -76,7 +97,9 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
                                                               int* __restrict__ counts, float* __restrict__ scores,
                                                               int nbest, int* __restrict__ n_hyp
                                                               CB_CTX_ARGS(const int* __restrict__ image, long long image_words,
-                                                                          const int* __restrict__ graph_of, float* __restrict__ bias_out)) {
+                                                                          const int* __restrict__ graph_of, float* __restrict__ bias_out)
+                                                              CB_LM_ARGS(const int* __restrict__ image, long long image_words,
+                                                                         float lm_weight, float token_score, float* __restrict__ bias_out)) {
   __shared__ CbBeam bufs[2][kCbMaxBeam];
   __shared__ float tot[kCbMaxBeam], stay_pb[kCbMaxBeam], stay_pnb[kCbMaxBeam], row[256];
   __shared__ unsigned merge_mask[kCbMaxBeam];  // bit i of word j: extension of beam i by last[j] spells beam j
@@ -87,13 +110,31 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
   const float* lp_seq = logp + (size_t)seq * Tq * V;
   int* bp = backptr + (size_t)seq * Tq * kCbMaxBeam;
   const int Ts = ctc_frames(em_len, seq, Tq);
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
   __shared__ float fin_key[kCbMaxBeam], fin_bias[kCbMaxBeam];
+#endif
+#ifdef EEC_CTC_CTX
   const CtxTables G = ctx_tables(image, image_words, graph_of, seq, V);  // all-null: biasing is off for this sequence
+  const int start = 0;
+#endif
+#ifdef EEC_CTC_LM
+  __shared__ float inc_s[2][kCbMaxBeam][kCbThreads];  // inc(state of beam i, label c), of the beams of the frame and of the next one
+  __shared__ int chosen[kCbMaxBeam];                  // the candidate id behind every new beam
+  const TlmView G = tlm_view(image, image_words, V);
+  const bool fused = G.on && !(lm_weight == 0.f && token_score == 0.f);  // off: every increment is 0
+  const int start = G.on ? tlm_node(G, G.m.bos) : 0;
+  // the increment of label c from `state`; the blank is never an extension
+  auto inc_of = [&](int state) -> float {
+    if (!fused || c >= V || c == blank) return 0.f;
+    int next;
+    return tlm_inc(lm_weight, tlm_walk(G, tlm_node(G, state), tlm_word(G, c), next), token_score);
+  };
+  int icur = 0;
+  inc_s[0][0][c] = inc_of(start);
 #endif
   int cur = 0;
   if (c == 0) {
-    bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull CB_CTX(0, 0.f)};
+    bufs[0][0] = CbBeam{0.f, -INFINITY, -1, 0, 0x243F6A8885A308D3ull CB_CTX(start, 0.f)};
     nb_s = 1;
   }
   __syncthreads();
@@ -148,10 +189,13 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
 #ifdef EEC_CTC_CTX
         v = v + (B[i].bias + (G.delta ? G.delta[(size_t)B[i].state * V + c] : 0.f));  // the key; -inf stays -inf
 #endif
+#ifdef EEC_CTC_LM
+        v = v + (B[i].bias + inc_s[icur][i][c]);  // the key; -inf stays -inf
+#endif
       }
       ext[i] = v;
     }
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
     float stay = c < nb ? cb_lae(stay_pb[c], stay_pnb[c]) + B[c].bias : -INFINITY;
 #else
     float stay = c < nb ? cb_lae(stay_pb[c], stay_pnb[c]) : -INFINITY;
@@ -195,6 +239,9 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
           N[r] = CbBeam{stay_pb[c], stay_pnb[c], B[c].last, B[c].len, B[c].hash CB_CTX(B[c].state, B[c].bias)};
           bp[t * kCbMaxBeam + r] = c << 16;
           stay = -INFINITY;
+#ifdef EEC_CTC_LM
+          chosen[r] = gid;
+#endif
         }
       } else {
         const int cc = (gid - 16) >> 4, ii = (gid - 16) & 15;
@@ -203,6 +250,12 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
           const size_t at = (size_t)B[ii].state * V + cc;
           N[r] = CbBeam{-INFINITY, (B[ii].last == cc ? B[ii].pb : tot[ii]) + lpc, cc, B[ii].len + 1, cb_mix(B[ii].hash, cc),
                         G.delta ? ctx_state(G.next[at], G.S) : 0, B[ii].bias + (G.delta ? G.delta[at] : 0.f)};
+#elif defined(EEC_CTC_LM)
+          int next = start;
+          if (fused) tlm_walk(G, tlm_node(G, B[ii].state), tlm_word(G, cc), next);
+          N[r] = CbBeam{-INFINITY, (B[ii].last == cc ? B[ii].pb : tot[ii]) + lpc, cc, B[ii].len + 1, cb_mix(B[ii].hash, cc), next,
+                        B[ii].bias + inc_s[icur][ii][cc]};
+          chosen[r] = gid;
 #else
           N[r] = CbBeam{-INFINITY, gv, cc, B[ii].len + 1, cb_mix(B[ii].hash, cc)};
 #endif
@@ -217,16 +270,35 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     }
     if (c == 0) nb_s = n_new;
     __syncthreads();
+#ifdef EEC_CTC_LM
+    // the new beams' increments: a stay takes its row along, an extension walks from its new state (column c only: no barrier)
+    for (int r = 0; r < n_new; ++r) inc_s[icur ^ 1][r][c] = chosen[r] < 16 ? inc_s[icur][chosen[r]][c] : inc_of(N[r].state);
+    icur ^= 1;
+#endif
     cur ^= 1;
   }
+#ifdef EEC_CTC_LM
+  // the end of the sentence: fl(lm_weight * acc(</s>)) from a prefix's state, when the model has </s>
+  auto fin_of = [&](int state) -> float {
+#pragma clang fp contract(off)
+    if (!fused || G.m.eos < 0) return 0.f;
+    int next;
+    const float term = lm_weight * tlm_walk(G, tlm_node(G, state), G.m.eos, next);
+    return term;
+  };
+#endif
   if (n_hyp) {  // block-uniform
     // N-best: thread i < live beams ranks prefix i (the number of prefixes ahead of it: a higher total, or the same total and a
     // lower index) and, if it is among the first nbest, reads its labels off the back-pointers into row `rank` of the sequence
     if (c < kCbMaxBeam) tot[c] = c < nb_s ? cb_lae(bufs[cur][c].pb, bufs[cur][c].pnb) : -INFINITY;
-#ifdef EEC_CTC_CTX
-    // the open bonus is taken back, and the ranking is by the key: total + that final bias
+#ifdef EEC_CTC_BIAS
+    // the open bonus is taken back (the model's </s> is paid), and the ranking is by the key: total + that final bias
     if (c < kCbMaxBeam) {
+#ifdef EEC_CTC_CTX
       const float b = c < nb_s ? bufs[cur][c].bias + (G.delta ? G.fin[ctx_state(bufs[cur][c].state, G.S)] : 0.f) : 0.f;
+#else
+      const float b = c < nb_s ? bufs[cur][c].bias + fin_of(bufs[cur][c].state) : 0.f;
+#endif
       fin_bias[c] = b;
       fin_key[c] = tot[c] + b;
     }
@@ -246,7 +318,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
         int* out = tokens + ((size_t)seq * nbest + rank) * Tq;
         counts[(size_t)seq * nbest + rank] = n;
         scores[(size_t)seq * nbest + rank] = tot[c];
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
         bias_out[(size_t)seq * nbest + rank] = fin_bias[c];
 #endif
         for (int t = Ts - 1; t >= 0 && n > 0; --t) {
@@ -259,7 +331,7 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     if (c >= n_out && c < nbest) {  // absent hypotheses
       counts[(size_t)seq * nbest + c] = 0;
       scores[(size_t)seq * nbest + c] = -INFINITY;
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
       bias_out[(size_t)seq * nbest + c] = 0.f;
 #endif
     }
@@ -269,11 +341,15 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
     const CbBeam* B = bufs[cur];
     int best = 0;
     float bs = -INFINITY;
-#ifdef EEC_CTC_CTX
+#ifdef EEC_CTC_BIAS
     float best_key = -INFINITY, best_bias = 0.f;
     for (int i = 0; i < nb_s; ++i) {
       const float s = cb_lae(B[i].pb, B[i].pnb);
+#ifdef EEC_CTC_CTX
       const float b = B[i].bias + (G.delta ? G.fin[ctx_state(B[i].state, G.S)] : 0.f);
+#else
+      const float b = B[i].bias + fin_of(B[i].state);
+#endif
       if (s + b > best_key) {
         best_key = s + b;
         bs = s;
@@ -306,12 +382,14 @@ __global__ __launch_bounds__(kCbThreads) void ctc_beam_kernel(const float* __res
 // n_hyp != nullptr: the N-best end, into `nbest` rows per sequence; nullptr: the best prefix (nbest is not read)
 hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int Tq, int V, int blank, int beam, float blank_skip_threshold,
                            int skip_drops, int* backptr, int* tokens, int* counts, float* scores, int nbest, int* n_hyp, hipStream_t st
-                           CB_CTX_ARGS(const int* image, long long image_words, const int* graph_of, float* bias)) {
+                           CB_CTX_ARGS(const int* image, long long image_words, const int* graph_of, float* bias)
+                           CB_LM_ARGS(const int* image, long long image_words, float lm_weight, float token_score, float* bias)) {
   if (V < 1 || V > 256 || beam < 1 || beam > kCbMaxBeam || blank < 0 || blank >= V) return hipErrorInvalidValue;
   if (n_hyp && (nbest < 1 || nbest > beam)) return hipErrorInvalidValue;
   const float log_thr = (blank_skip_threshold > 0.f && blank_skip_threshold < 1.f) ? logf(blank_skip_threshold) : INFINITY;
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(n_seq), dim3(kCbThreads), 0, st, logp, em_len, Tq, V, blank, beam, log_thr, skip_drops, backptr, tokens,
-                     counts, scores, nbest, n_hyp CB_CTX_ARGS(image, image_words, graph_of, bias));
+                     counts, scores, nbest, n_hyp CB_CTX_ARGS(image, image_words, graph_of, bias)
+                     CB_LM_ARGS(image, image_words, lm_weight, token_score, bias));
   return hipGetLastError();
 }
 
@@ -319,7 +397,7 @@ hipError_t launch_ctc_beam(const float* logp, const int* em_len, int n_seq, int 
 
 extern "C" {
 
-#ifndef EEC_CTC_CTX
+#ifndef EEC_CTC_BIAS
 size_t eec_ctc_beam_workspace_bytes(int n_seq, int Tq) {
   return n_seq > 0 && Tq > 0 ? (size_t)n_seq * Tq * eec::kCbMaxBeam * sizeof(int) : 0;
 }
@@ -336,7 +414,7 @@ static int check_ctc_beam_args(const char* entry, bool have_pointers, int n_seq,
   return 0;
 }
 
-#ifndef EEC_CTC_CTX
+#ifndef EEC_CTC_BIAS
 int eec_ctc_beam_decode(const float* logp, int n_seq, int Tq, int V, int blank, int beam_size, float blank_skip_threshold,
                         void* workspace, int32_t* tokens, int32_t* counts, float* scores, void* stream) {
   return eec_ctc_beam_decode_len(logp, NULL, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, 0, workspace, tokens, counts, scores, stream);
@@ -368,7 +446,7 @@ int eec_ctc_beam_decode_nbest(const float* logp, const int32_t* em_len, int n_se
                                counts, scores, nbest, n_hyp, (hipStream_t)stream));
   return 0;
 }
-#else
+#elif defined(EEC_CTC_CTX)
 // the _len / _nbest entries with a graph image (a device pointer, or NULL: no biasing), graph_of [n_seq] (NULL: graph 0) and `bias`
 static int check_ctx_image(const char* entry, const void* image, size_t image_bytes) {
   if (image && (((uintptr_t)image & 3) != 0 || image_bytes < 16)) return eech::fail(EEC_ERR_BAD_ARG, std::string(entry) + ": image must be 4-byte aligned, image_bytes its size");
@@ -397,6 +475,41 @@ int eec_ctc_beam_decode_nbest_ctx(const float* logp, const int32_t* em_len, int 
   if (int rc = check_ctx_image("eec_ctc_beam_decode_nbest_ctx", image, image_bytes)) return rc;
   EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
                                counts, scores, nbest, n_hyp, (hipStream_t)stream, (const int*)image, (long long)(image_bytes / 4), graph_of, bias));
+  return 0;
+}
+#else
+// the _len / _nbest entries with a model image (a device pointer, or NULL: no fusion), its weight, the per-token bonus and `fusion`
+static int check_lm_args(const char* entry, const void* lm, size_t lm_bytes, float lm_weight, float token_score) {
+  const std::string name = entry;
+  if (lm && (((uintptr_t)lm & 3) != 0 || lm_bytes < 64)) return eech::fail(EEC_ERR_BAD_ARG, name + ": lm must be 4-byte aligned, lm_bytes its size");
+  if (!isfinite(lm_weight) || !isfinite(token_score)) return eech::fail(EEC_ERR_BAD_ARG, name + ": lm_weight and token_score must be finite");
+  return 0;
+}
+
+int eec_ctc_beam_decode_lm(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                           float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                           float* scores, const void* lm, size_t lm_bytes, float lm_weight, float token_score, float* fusion, void* stream) {
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode_lm", logp && workspace && tokens && counts && scores && fusion, n_seq, Tq, V, blank, beam_size))
+    return rc;
+  if (int rc = check_lm_args("eec_ctc_beam_decode_lm", lm, lm_bytes, lm_weight, token_score)) return rc;
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, 1, nullptr, (hipStream_t)stream, (const int*)lm, (long long)(lm_bytes / 4), lm_weight, token_score,
+                               fusion));
+  return 0;
+}
+
+int eec_ctc_beam_decode_nbest_lm(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                                 float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens,
+                                 int32_t* counts, float* scores, int32_t* n_hyp, const void* lm, size_t lm_bytes, float lm_weight,
+                                 float token_score, float* fusion, void* stream) {
+  if (int rc = check_ctc_beam_args("eec_ctc_beam_decode_nbest_lm", logp && workspace && tokens && counts && scores && n_hyp && fusion, n_seq, Tq, V,
+                                   blank, beam_size))
+    return rc;
+  if (nbest < 1 || nbest > beam_size) return eech::fail(EEC_ERR_BAD_ARG, "eec_ctc_beam_decode_nbest_lm: needs 1 <= nbest <= beam_size");
+  if (int rc = check_lm_args("eec_ctc_beam_decode_nbest_lm", lm, lm_bytes, lm_weight, token_score)) return rc;
+  EEC_HIP(eec::launch_ctc_beam(logp, em_len, n_seq, Tq, V, blank, beam_size, blank_skip_threshold, skip_drops_frame != 0, (int*)workspace, tokens,
+                               counts, scores, nbest, n_hyp, (hipStream_t)stream, (const int*)lm, (long long)(lm_bytes / 4), lm_weight,
+                               token_score, fusion));
   return 0;
 }
 #endif

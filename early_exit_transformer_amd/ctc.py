@@ -60,7 +60,7 @@ def greedy_ctc(logp: Tensor, blank: int = 0, em_len: Optional[Tensor] = None) ->
 
 def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_skip_threshold: float = 0.95,
                     skip_drops_frame: bool = False, em_len: Optional[Tensor] = None, nbest: Optional[int] = None, context=None,
-                    graph_of=None):
+                    graph_of=None, lm=None, lm_weight: Optional[float] = None, token_score: float = 0.0):
     """CTC prefix beam search of [N, T', V] log-probs on the device (eec_ctc_beam_decode): the best hypothesis per
     sequence, as ``BeamInference.ctc_cuda_predict`` uses torchaudio's cuda_ctc_decoder (util/beam_infer.py:102-112).
     ``skip_drops_frame``: a frame above ``blank_skip_threshold`` is dropped instead of being taken as a blank frame (the two
@@ -74,7 +74,16 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
     ``context`` (None: the call and its return values, unchanged): a ``context.ContextGraph`` -- the search ranks by total
     log-probability + bias (eec_ctc_beam_decode_ctx / _nbest_ctx, include/eec.h "Contextual biasing") and ``bias`` ([N] or [N, nbest]
     fp32, shaped like ``scores``) is appended to the tuple; ``scores`` stays the CTC log-probability alone.  ``graph_of`` [N] chooses a
-    graph of a bank per sequence (None: graph 0; an index outside the bank: no biasing for that sequence)."""
+    graph of a bank per sequence (None: graph 0; an index outside the bank: no biasing for that sequence).
+    ``lm`` (None: the call and its return values, unchanged): a ``lm_fusion.TokenLM`` over the V labels -- shallow fusion: the search
+    ranks by total log-probability + fusion, where every label adds ``lm_weight`` (None: 0.3, customary and not tuned) times the
+    model's log10 score plus ``token_score`` and the model's ``</s>`` closes a prefix (eec_ctc_beam_decode_lm / _nbest_lm,
+    include/eec.h "Shallow fusion"); ``fusion`` (shaped like ``scores``, which stay the CTC log-probability alone) is appended to the
+    tuple.  Not together with ``context``: a graph and a model in one CTC call are not served."""
+    if lm is not None and context is not None:
+        raise ValueError("ctc_beam_decode: a context graph and a language model in one CTC call are not served; choose one")
+    if lm is None and (lm_weight is not None or token_score != 0.0):
+        raise ValueError("ctc_beam_decode: lm_weight / token_score weigh lm=, which was not given")
     if not logp.is_cuda:
         raise RuntimeError("ctc_beam_decode runs on a HIP device only")
     logp = logp.contiguous().float()
@@ -85,7 +94,13 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
         raise ValueError("ctc_beam_decode: graph_of chooses among the graphs of context=, which was not given")
     k = () if nbest is None else (int(nbest),)
     ws = torch.empty((capi.load().eec_ctc_beam_workspace_bytes(N, Tq),), dtype=torch.uint8, device=dev)
-    tokens = (torch.empty if nbest is None and context is None else torch.zeros)((N, *k, Tq), dtype=torch.int32, device=dev)
+    if lm is not None:
+        from .lm_fusion import DEFAULT_LM_WEIGHT, check_lm
+        lm_weight = DEFAULT_LM_WEIGHT if lm_weight is None else float(lm_weight)
+        check_lm("ctc_beam_decode", lm, V, beam_size, lm_weight, token_score)
+        if lm.blank != blank:
+            raise ValueError(f"ctc_beam_decode: the language model was built with blank {lm.blank}, the emission has blank {blank}")
+    tokens = (torch.empty if nbest is None and context is None and lm is None else torch.zeros)((N, *k, Tq), dtype=torch.int32, device=dev)
     outs = [tokens, torch.empty((N, *k), dtype=torch.int32, device=dev), torch.empty((N, *k), dtype=torch.float32, device=dev)]
     if k:
         outs.append(torch.empty((N,), dtype=torch.int32, device=dev))  # n_hyp
@@ -97,9 +112,11 @@ def ctc_beam_decode(logp: Tensor, beam_size: int = 10, blank: int = 0, blank_ski
                              f"the emission over {V} with blank {blank}")
         tail = (context.to(dev), context.nbytes, graph_rows("ctc_beam_decode", graph_of, N, dev),
                 torch.empty((N, *k), dtype=torch.float32, device=dev))  # image, its bytes, graph_of, bias
-    entry = "eec_ctc_beam_decode" + (("_nbest" if k else "") + ("_ctx" if tail else "") or "_len")
+    if lm is not None:
+        tail = (lm.on(dev), lm.nbytes, lm_weight, float(token_score), torch.empty((N, *k), dtype=torch.float32, device=dev))  # .., fusion
+    entry = "eec_ctc_beam_decode" + (("_nbest" if k else "") + ("_lm" if lm is not None else "_ctx" if tail else "") or "_len")
     launch(entry, dev, logp, el, N, Tq, V, blank, beam_size, blank_skip_threshold, int(bool(skip_drops_frame)), *k, ws, *outs, *tail)
-    return (*outs, *tail[3:])
+    return (*outs, tail[-1]) if tail else tuple(outs)
 
 
 def ctc_lexicon_decode(emission: Tensor, trie, beam_size: int = 10, nbest: int = 1, word_score: float = 0.0, sil_score: float = 0.0,

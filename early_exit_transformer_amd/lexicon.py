@@ -262,12 +262,14 @@ class NGramLM:
         self._smear = None     # (the trie it was built for, its SmearTable)
 
     @classmethod
-    def from_arpa(cls, path, trie: "TokenTrie", normalize=None) -> "NGramLM":
+    def from_arpa(cls, path, trie: "TokenTrie", normalize=None, exempt: Sequence[int] = ()) -> "NGramLM":
         """The ARPA file ``path`` read against ``trie.words``: an LM word is matched exactly, after ``normalize`` (None: identity;
         ``<s>``, ``</s>`` and ``<unk>`` are matched as they stand) was applied to it; lexicon entries with the same string share an
         LM word; a lexicon word the model lacks scores as ``<unk>``.  N-grams with a word outside the lexicon and those three can
         never be asked for and are dropped.  The file's log10 values are kept as they are, rounded to fp32.  Raises a ``ValueError``
-        that names file and line for a malformed file, and one that counts the missing words when the model has no ``<unk>``."""
+        that names file and line for a malformed file, and one that counts the missing words when the model has no ``<unk>``.
+        Only ``trie.words`` is read.  ``exempt``: indices into it of entries that are never looked up (the special tokens of
+        ``lm_fusion.TokenLM``); they are not counted as missing and map to ``<unk>``, or to LM word 0 when the model has none."""
         lex = set(trie.words)
         special = (cls.BOS, cls.EOS, cls.UNK)
 
@@ -365,13 +367,14 @@ class NGramLM:
         if len(rows) != len(declared) or not declared:
             raise bad(line_no, f"\\data\\ states {len(declared)} orders, the file holds the sections of {len(rows)}")
         unk = ids.get(cls.UNK, -1)
-        missing = [w for w in dict.fromkeys(trie.words) if w not in ids]
+        spared = {trie.words[k] for k in exempt}
+        missing = [w for w in dict.fromkeys(trie.words) if w not in ids and w not in spared]
         if missing and unk < 0:
             raise ValueError(f"NGramLM: {path}: the model has no <unk> and lacks {len(missing)} of the lexicon's words: "
                              + ", ".join(repr(w) for w in missing[:5]) + (", ..." if len(missing) > 5 else ""))
         if not vocab:
             raise ValueError(f"NGramLM: {path}: no unigram of the model is a word of the lexicon")
-        word_map = np.fromiter((ids.get(w, unk) for w in trie.words), dtype=np.int32, count=len(trie.words))
+        word_map = np.fromiter((ids.get(w, unk if unk >= 0 or w not in spared else 0) for w in trie.words), dtype=np.int32, count=len(trie.words))
         return cls([np.array(r[0], dtype=np.int32).reshape(-1, k + 1) for k, r in enumerate(rows)], [np.array(r[1], dtype=np.float32) for r in rows],
                    [np.array(r[2], dtype=np.float32) for r in rows], word_map, ids.get(cls.BOS, -1), ids.get(cls.EOS, -1), unk, vocab)
 

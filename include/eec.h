@@ -1485,6 +1485,65 @@ int eec_context_bias_step(const void* image, size_t image_bytes, const int32_t* 
                           const int64_t* parent, const int64_t* last, const float* local, float* out, void* state, size_t state_bytes,
                           void* stream);
 
+/* ---- Shallow fusion: token-level n-gram model (csrc/lm_fusion.hip, csrc/ctc_beam_lm.hip, csrc/eec_lm.h) -----------------------------
+ * A back-off n-gram over the model's own tokens (sentencepiece pieces), added to the scores of the lexicon-free searches: the CTC
+ * prefix beam search and the AED lockstep searches.  WeNet, ESPnet and icefall offer the same; the reference's cuda_ctc_decoder and
+ * its AED beam search take no LM: an addition, not a parity item.  tests/lmfusion_cases.py restates everything below in plain
+ * Python and NumPy fp32 / fp64.
+ *
+ * Model.  A packed n-gram image as eec_ngram_pack makes it (above), with lex_words = V and word_map[v] the LM word of token v: ARPA
+ * words are piece strings, a piece the model lacks maps to <unk> (refused on the host when the model has none).  Values stay the
+ * file's log10 numbers; the weight absorbs ln 10.  At most 512 LM words (V <= 256 pieces and the three special words).
+ * Special tokens are arguments of the kernels and never looked up: `skip` tokens (blank, SOS, PAD; -1: none) pay 0 and keep the state;
+ * `eos` (-1: none) is tested before the skip tokens and scores as </s> when the model has one (header word 7), else with acc = 0;
+ * after `eos` a row is in the dead state, -1, where every token pays 0 and the state stays dead.  The start state is header word 6:
+ * <s>'s unigram, or the root.
+ * Increment of token v from state s:  acc = lm_walk(view, s, word_map[v], next) -- the walk stated above, in its addition order,
+ * beginning at acc = 0 --, inc = fl(fl(lm_weight * acc) + token_score): the product is rounded on its own, no fused multiply-add.
+ * token_score is the per-token insertion bonus; skip tokens and dead rows do not receive it (their inc is 0).  The state after v
+ * is `next`.  An entry whose inc is 0 keeps its bits.
+ * Fusion score of a row: fusion(y . v) = fl(fusion(y) + inc) in fp32 along the prefix, fusion() = 0: a function of the token row alone.
+ * Never trust the image: fusion is off for the call and the input is returned bit for bit when the image pointer is NULL, the magic
+ * is wrong, header word 5 is not V, the counts of the header contradict each other or the sections do not lie inside the image's
+ * bytes.  A state outside [0, n_nodes) is taken as the root, an edge bound or a suffix outside its section is brought back into it,
+ * a word_map entry outside the LM words reads as word 0, and the sixth node of a suffix chain is read as the root (a packed image
+ * reaches it within five): no value of the image is ever an address outside it.
+ *
+ * AED lockstep search: eec_lm_fusion_step, with the place and the argument order of eec_context_bias_step (no graph_of), then
+ * lm_weight, token_score, eos and three skip tokens.  state: int32 [2][n][R_max], eec_lm_fusion_state_bytes(n, R_max) bytes; step s
+ * reads half s & 1 and writes the other.  Row (i, r): the start state at s == 0 (the token there is SOS and is not read), else the
+ * state after last[i][r] from state_prev[parent[i][r]] (parent == NULL: r; a parent outside [0, R_prev) or a token outside [0, V):
+ * the start state); then out[i][r][v] = fl(local[i][r][v] + inc(state, v)); -inf stays -inf; out == local is allowed.  The increment
+ * is part of the step's log-prob and shares its length penalty: the closed form holds for pen_alpha = 0.  One launch, one workgroup
+ * per row, one work-item per token; the row's suffix chain is walked once and each chain node's edges are scattered into one LDS
+ * row, deepest node last, which leaves lm_walk's bits.  With lm_weight == 0 and token_score == 0 the states advance and out is
+ * local's bits.  EEC_ERR_BAD_ARG: a null pointer, R or R_prev outside [1, R_max], R_max outside [1, 16], V outside [1, 256], a weight
+ * or bonus that is not finite; n == 0 is a successful no-op.  No atomics, nothing read back, graph-capturable, bit-identical run to
+ * run and independent of n.
+ *
+ * CTC prefix beam search: eec_ctc_beam_decode_lm (the best-prefix end) and eec_ctc_beam_decode_nbest_lm (the N-best end) take the
+ * arguments of eec_ctc_beam_decode_len / _nbest and lm, lm_bytes, lm_weight, token_score and fusion ([n_seq], [n_seq][nbest]).  It is
+ * that search (csrc/ctc_beam.hip compiled with EEC_CTC_LM) under the change contextual biasing makes: a beam grows by a state and a
+ * bias, every ranking compares key = fl(total log-probability + bias).  The blank is this search's one skip token and it has no eos:
+ * every other label is scored through word_map.  An extension of beam i by label c has bias fl(bias_i + inc(state_i, c)) and the
+ * state after c; stays, merges, blank-skipped frames, candidate ids and tie rules are unchanged.  At the end, when the model has
+ * </s>, each prefix's bias becomes fl(bias + fl(lm_weight * acc(</s>))) from its state, and both ends rank by fl(total + that).
+ * scores stays the CTC log-probability alone; fusion is returned beside it (0 for an absent hypothesis).  lm == NULL, an image that
+ * is not trusted, or lm_weight == 0 with token_score == 0 return the tokens, counts and scores of the entries without a model bit
+ * for bit, with fusion 0.  EEC_ERR_BAD_ARG also for a weight or bonus that is not finite.  A context graph and a model in one CTC
+ * call are not served.  Graph-capturable; two runs and a split batch return the same bits. */
+int eec_ctc_beam_decode_lm(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                           float blank_skip_threshold, int skip_drops_frame, void* workspace, int32_t* tokens, int32_t* counts,
+                           float* scores, const void* lm, size_t lm_bytes, float lm_weight, float token_score, float* fusion, void* stream);
+int eec_ctc_beam_decode_nbest_lm(const float* logp, const int32_t* em_len, int n_seq, int Tq, int V, int blank, int beam_size,
+                                 float blank_skip_threshold, int skip_drops_frame, int nbest, void* workspace, int32_t* tokens,
+                                 int32_t* counts, float* scores, int32_t* n_hyp, const void* lm, size_t lm_bytes, float lm_weight,
+                                 float token_score, float* fusion, void* stream);
+size_t eec_lm_fusion_state_bytes(int n, int R_max);
+int eec_lm_fusion_step(const void* lm, size_t lm_bytes, int n, int R, int R_prev, int R_max, int V, int s, const int64_t* parent,
+                       const int64_t* last, const float* local, float* out, void* state, size_t state_bytes, float lm_weight,
+                       float token_score, int eos, int skip0, int skip1, int skip2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
