@@ -5,9 +5,13 @@ __version__ = "0.1.0"
 
 _CONTEXT = ("ContextGraph", "ContextBiasSession")  # contextual biasing (context.py), resolved at first use: importing the package stays light
 _LM_FUSION = ("TokenLM", "LMFusionSession")  # shallow fusion with a token-level n-gram model (lm_fusion.py), likewise
+_KEYWORD = ("KeywordSet", "KeywordHits", "keyword_search")  # keyword spotting on CTC emissions (keyword.py), likewise
 
 
 def __getattr__(name):
+    if name in _KEYWORD:
+        from . import keyword
+        return getattr(keyword, name)
     if name in _CONTEXT:
         from . import context
         return getattr(context, name)

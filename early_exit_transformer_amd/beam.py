@@ -31,6 +31,8 @@
   decoding (not in the reference).  The CTC head proposes an N-best list (``ctc_beam_decode(nbest=)``, csrc/ctc_beam.hip), the
   attention decoder scores the whole list in one teacher-forced pass (``model.score_hypotheses``, csrc/decoder_score.hip), and the
   best hypothesis is the one with the highest ``(1 - w) * att + w * ctc``: no autoregressive loop, no key / value cache.
+* ``BeamInference.spot``: keyword and phrase spotting (not in the reference): one encoder pass, then every keyword of a
+  ``KeywordSet`` against the CTC emissions of all exits (``keyword_search``, csrc/keyword.hip), and the shallowest exit that hits.
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 * ``BeamInference.error_table``: what any of the decoders above returned, scored against references (``scoring.error_table``;
@@ -46,6 +48,7 @@ import torch
 from torch import Tensor
 
 from .context import ContextBiasSession
+from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
 from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
@@ -946,6 +949,17 @@ class BeamInference:
         em_len = encoder_lengths(lengths.to(out.logp.device), out.logp.size(1))
         return self.ctc_cuda_predict(out.logp, beam_size=beam_size, lexicon=lexicon, detokenize=detokenize, lengths=em_len, context=context,
                                      graph_of=graph_of, token_lm=token_lm, token_lm_weight=token_lm_weight, token_score=token_score), out.exit_of
+
+    # -- keyword spotting: which phrases an utterance contains, and where, at every exit, without decoding it -----------------
+    @torch.no_grad()
+    def spot(self, model, spec: Tensor, valid_len: Tensor, keywords: KeywordSet, threshold=None):
+        """One encoder pass (the log-probs of all exits, no taps) and ``keyword_search`` over the E * B emissions and the encoder's
+        own frame counts.  Returns ``KeywordHits`` over [E, B, K], with the trace; with ``threshold`` (a float, or one per keyword)
+        ``(hits, hits.first_exit(threshold))``: the shallowest exit int64 [B, K] at which each keyword's best score reaches it."""
+        valid_len = valid_len.reshape(-1)
+        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
+        hits = keyword_search(logp, keywords, encoder_lengths(valid_len.to(logp.device), logp.size(2)), want_trace=True)
+        return hits if threshold is None else (hits, hits.first_exit(threshold))
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

@@ -276,6 +276,8 @@ PROTOTYPES = {
     "eec_ctc_beam_decode_nbest_lm": [F32, I32, i, i, i, i, i, f, i, i, VOID, I32, I32, F32, I32, VOID, z, f, f, F32, STREAM],
     "eec_lm_fusion_state_bytes": (z, [i, i]),
     "eec_lm_fusion_step": [VOID, z, i, i, i, i, i, i, I64, I64, F32, F32, VOID, z, f, f, i, i, i, i, STREAM],
+    "eec_keyword_search_workspace_bytes": (z, [i, i]),
+    "eec_keyword_search": [F32, i, i, i, I32, I32, I32, i, i, i, F32, I32, I32, F32, I32, VOID, z, STREAM],
 }
 EXPORTS = list(PROTOTYPES)
 KERNEL_CLASSES = ["stem", "ffn", "qkv", "attn", "proj_glu", "proj", "dw_pw2", "head", "chain"]

@@ -1544,6 +1544,47 @@ int eec_lm_fusion_step(const void* lm, size_t lm_bytes, int n, int R, int R_prev
                        const int64_t* last, const float* local, float* out, void* state, size_t state_bytes, float lm_weight,
                        float token_score, int eos, int skip0, int skip1, int skip2, void* stream);
 
+/* ---- Keyword spotting on CTC emissions (csrc/keyword.hip) ------------------------------------------------------------------------------
+ * "Does this emission contain one of these phrases, and where": for every (emission, keyword) pair the best segment of the emission
+ * whose frames CTC-collapse to the keyword, without decoding the utterance.  Max over paths only (no log-add).  The reference has
+ * nothing of the kind: an addition, not a parity item.  tests/kws_cases.py restates everything below in scalar fp32 loops and checks
+ * it against a brute force over all segments and label paths.
+ *
+ * Inputs.  Emission x [T', V] fp32 -- log-probs or logits: the score is invariant to a per-frame shift --, T = clamp(em_len, 0, T').
+ * Keyword y_1 .. y_L, no y_j equal to `blank`.  States s = 0 .. 2L - 2: lab(s) = y_{s/2 + 1} for even s, `blank` for odd s.  A match
+ * starts on a frame of y_1 and ends on a frame of y_L: there are no boundary blanks.
+ * Frame term.  m[t] = max_v x[t][v];  e[t][s] = fl(x[t][lab(s)] - m[t]), and -inf for every s when m[t] is not finite.  Every term is
+ * at most 0; a path scores 0 exactly when greedy decoding spells it.
+ * Recurrence.  Before frame 0 every d is -inf and every start -1.  At frame t state s takes a candidate (c, start) from these sources,
+ * in this order, a later one replacing an earlier one only if it is strictly greater:
+ *   1. d[t-1][s];  2. d[t-1][s-1] for s >= 1;  3. d[t-1][s-2] for even s >= 2 with lab(s) != lab(s-2);  4. for s = 0 only, the fresh
+ *   start (0, t).
+ * Then d[t][s] = fl(c + e[t][s]); the start travels with the candidate and becomes -1 again when d[t][s] is -inf.
+ * Outputs.  trace_score[t] = d[t][2L-2] and trace_start[t] its start for t < T; -inf and -1 for T <= t < T'.  score = the maximum of
+ * the trace over t, end = the first t that attains it, start = that frame's start; -inf, -1, -1 with no reachable end.  The tie
+ * rules are local: only the score is a global maximum, and [start, end] is a segment that attains it.
+ * Frames at or past a length are never read: a NaN there reaches nothing.  A NaN inside a valid frame gives unspecified scores and
+ * never an address out of range.  fp32 subtract, add and compare only: the kernel and a host restatement agree bit for bit.
+ *
+ *   logp [n_em, T', V] fp32, from any 4-byte boundary; V need not be a multiple of 4.  em_len [n_em] int32, or NULL = T' for all.
+ *   tokens [K, tok_stride] int32, tok_len [K] int32 (L), both on the device; blank in [0, V)
+ *   score fp32, start, end int32: [n_em, K]
+ *   trace_score fp32, trace_start int32: [n_em, K, T'], or both NULL
+ *   workspace: eec_keyword_search_workspace_bytes(n_em, T') bytes (the frame maxima), 256-byte aligned
+ * Refused before any device work.  EEC_ERR_BAD_ARG: K outside [1, 65536], tok_stride -- the table's width, hence the longest keyword --
+ * outside [1, 64], T' outside [1, 2^20], n_em < 1, V < 2, blank outside [0, V), a null required pointer, one trace pointer without the
+ * other.  EEC_ERR_UNSUPPORTED: n_em * T' or n_em * ceil(K / 4) at or above 2^31.  EEC_ERR_WORKSPACE: a null, misaligned or too small
+ * workspace.  The entry never reads device memory, so what only the table's contents show is the owner's to refuse: the package's
+ * KeywordSet is the one maker of token tables and raises for a length outside [1, 64] and for a token equal to `blank` or outside
+ * [0, V).  The device trusts neither: em_len is clamped, and a keyword with a length outside [1, tok_stride] or with such a token gets
+ * the fill values (-inf, -1, -1, the trace likewise) without any of its tokens becoming an address.
+ * Two launches (frame maxima; one wavefront per (emission, keyword)), no atomics, nothing read back, no allocation, no
+ * synchronisation; graph-capturable; two runs, a split over keywords and a split over emissions return the same bits. */
+size_t eec_keyword_search_workspace_bytes(int n_em, int Tq);
+int eec_keyword_search(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
+                       int K, int tok_stride, int blank, float* score, int32_t* start, int32_t* end, float* trace_score,
+                       int32_t* trace_start, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
