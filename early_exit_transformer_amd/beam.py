@@ -38,6 +38,10 @@
 * ``BeamInference.error_table``: what any of the decoders above returned, scored against references (``scoring.error_table``;
   csrc/edit_distance.hip): errors with their substitution / deletion / insertion split per exit and utterance, in tokens, or in
   words / characters after ``detokenize`` and ``apply_lex``.  The reference leaves this to tools outside its tree.
+
+Every lockstep search, plain and joint, is one loop (``_lockstep_search``) over an ordered sequence of scorers -- the CTC prefix
+session, the context bias, the language model: sessions over ``decoding.ScorerSession`` -- and a call's ``context`` / ``graph_of`` /
+``token_lm`` / ``token_lm_weight`` / ``token_score`` are resolved once into ``_Modifiers``, which the public methods hand to each other.
 """
 from __future__ import annotations
 
@@ -47,7 +51,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .context import ContextBiasSession
+from .context import ContextBiasSession, ContextGraph
 from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
 from .lexicon import NGramLM, TokenTrie, as_lexicon
@@ -119,6 +123,19 @@ def _snapped_texts(token_lists, lexicon, detokenize) -> List[str]:
     return as_lexicon(lexicon).apply_batch([detokenize(list(t)) for t in token_lists])
 
 
+def _with_texts(out, lexicon, detokenize, cut=lambda ids: ids):
+    """The table ``out[b][e]`` of decoded ids, with ``lexicon`` and ``detokenize`` both given as ``DecodedTokens`` that carry their
+    ``.text``: the snapped text of ``cut(ids)``, all of them resolved in one lexicon search."""
+    if lexicon is None or detokenize is None:
+        return out
+    texts = iter(_snapped_texts([cut(ids) for row in out for ids in row], lexicon, detokenize))
+    out = [[DecodedTokens(ids) for ids in row] for row in out]
+    for row in out:
+        for ids in row:
+            ids.text = next(texts)
+    return out
+
+
 def default_max_length(T: int) -> int:
     """inference.py:31-39 (p = 30, m = 5 / 200): the decoding length for T input frames."""
     return int(30 - T * 5 / 200) if T < 200 else int(T / 12)
@@ -161,38 +178,63 @@ def _ctc_pick(emission: Tensor, em_len: Optional[Tensor], weight_ctc: float, bla
     return pick
 
 
-def _bias_session(context, graph_of, E: int, B: int, beam: int, V: int):
-    """The ``ContextBiasSession`` of E * B lockstep searches (search e * B + b) under ``context``, or None without one: ``graph_of``
-    [B] is given per utterance and repeated over the exits."""
-    if context is None:
-        if graph_of is not None:
-            raise ValueError("graph_of chooses among the graphs of context=, which was not given")
-        return None
-    if context.vocab_size != V:
-        raise ValueError(f"the context graph is over {context.vocab_size} tokens, the decoder over {V}")
-    if graph_of is not None:
-        graph_of = torch.as_tensor(graph_of).reshape(B).repeat(E)
-    return ContextBiasSession(context, E * B, beam, graph_of)
+class _Modifiers(NamedTuple):
+    """The search modifiers of one call, resolved once (``BeamInference._modifiers``): the context graph (or None), the graph of its
+    bank per utterance (``graph_of``, 1-D, or None: graph 0) and the shallow-fusion triple (model, weight, bonus) (or None)."""
+    context: Optional[ContextGraph] = None
+    graph_of: Optional[Tensor] = None
+    fusion: Optional[tuple] = None
+
+    def chunk(self, c0: int, step: int) -> "_Modifiers":
+        """The modifiers of utterances ``c0 .. c0 + step``."""
+        return self if self.graph_of is None else self._replace(graph_of=self.graph_of[c0:c0 + step])
+
+    def over_exits(self, E: int, B: int) -> "_Modifiers":
+        """The modifiers of E * B searches (search e * B + b): the B graph rows repeated over the exits."""
+        return self if self.graph_of is None else self._replace(graph_of=self.graph_of.reshape(B).repeat(E))
+
+    def scorers(self, E: int, B: int, beam: int, V: int) -> list:
+        """The sessions of E * B lockstep searches, in their order of application: the ``ContextBiasSession``, then the
+        ``LMFusionSession``."""
+        out = []
+        if self.context is not None:
+            if self.context.vocab_size != V:
+                raise ValueError(f"the context graph is over {self.context.vocab_size} tokens, the decoder over {V}")
+            out.append(ContextBiasSession(self.context, E * B, beam, self.over_exits(E, B).graph_of))
+        if self.fusion is not None:
+            lm, w, ts = self.fusion
+            check_lm("shallow fusion", lm, V, beam, w, ts)
+            out.append(LMFusionSession(lm, E * B, beam, w, ts))
+        return out
+
+    def ctc_kw(self) -> dict:
+        """The keywords of ``ctc_beam_decode``, whose extra output, if there is one, is the bias or the fusion."""
+        kw = {} if self.context is None else {"context": self.context, "graph_of": self.graph_of}
+        if self.fusion is not None:
+            kw.update(lm=self.fusion[0], lm_weight=self.fusion[1], token_score=self.fusion[2])
+        return kw
 
 
-def _lm_session(fusion, n: int, beam: int, V: int) -> Optional[LMFusionSession]:
-    """The ``LMFusionSession`` of n lockstep searches under ``fusion`` = (model, weight, bonus) (``BeamInference._fusion``), or None."""
-    if fusion is None:
-        return None
-    lm, w, ts = fusion
-    check_lm("shallow fusion", lm, V, beam, w, ts)
-    return LMFusionSession(lm, n, beam, w, ts)
+def _exit_emission(word: str, emission, emission_len, E: int, B: Optional[int] = None):
+    """What ``word`` needs: ``emission`` [E, B, T', V] and ``emission_len`` [B] (None: T') as the E * B searches read them (search
+    e * B + b) -> (emission [E * B, T', V], em_len int32 [E * B] or None)."""
+    if emission is None or emission.dim() != 4 or emission.size(0) != E or B not in (None, emission.size(1)):
+        raise ValueError(f"{word} needs emission [{E}, {'B' if B is None else B}, T', V]: the CTC log-probs of every exit and utterance")
+    B = emission.size(1)
+    em_len = None if emission_len is None else emission_len.to(emission.device, torch.int32).reshape(B).repeat(E)
+    return emission.reshape(E * B, emission.size(2), emission.size(3)), em_len
 
 
-def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None, bias=None, lm=None):
+def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, alpha: float, pick=None, scorers=()):
     """``max_length`` steps of n independent beam searches in lockstep, none of which finalises a beam on the way:
     ``step(last [n, R], parent [n, R] | None)`` returns the next token's log-probs [n, R, V] of every live beam.  The
     bookkeeping of a step is ``beam_select`` over two token buffers.  Returns ``(final_tokens, final_scores, best_tokens)``
-    per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s.
-    ``bias`` (a ``ContextBiasSession``, or None): its ``step`` adds the contextual bias to the step's log-probs before the selection,
-    and after the last step ``bias.final`` takes the bonus of a still open partial match back (at the last step's penalty), as an
-    EOS would have.  ``lm`` (an ``LMFusionSession``, or None): its ``step`` adds the language model's increments in the same place;
-    the two compose, both are additive."""
+    per search; the best beam is the one with the highest score, or ``pick(tokens [n, R, L], scores [n, R]) -> [n]``'s, which may
+    also finish the rows in place.  ``scorers``: sessions (``decoding.ScorerSession``) whose ``step(logp, last, parent)`` rewrites the
+    step's scores before the selection, applied in their order -- the CTC prefix scores of a joint search, then the contextual
+    bias, then the language model's increments; the last two are additive.  After the last step every row is final as it stands:
+    a scorer with a ``final(last, parent)`` adds it then, at the last step's penalty (the bias takes the provisional bonus of a
+    still open partial match back, as an EOS would have)."""
     scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
     bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
     bufs[0][:, 0, 0] = sos
@@ -200,53 +242,41 @@ def _lockstep_search(step, n: int, dev, max_length: int, sos: int, beam: int, al
     parent: Optional[Tensor] = None
     for i in range(max_length):
         logp = step(last, parent)
-        if bias is not None:
-            logp = bias.step(logp, last, parent)
-        if lm is not None:
-            logp = lm.step(logp, last, parent)
+        for scorer in scorers:
+            logp = scorer.step(logp, last, parent)
         scores, parent, last = beam_select(logp, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
-    if bias is not None:  # every row is final as it stands: an open partial match gives its provisional bonus back
-        scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
+    for scorer in scorers:
+        if hasattr(scorer, "final"):
+            scores = scores + scorer.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
     tokens = bufs[max_length & 1][:, :beam]
     best = (scores.argmax(dim=1) if pick is None else pick(tokens, scores)).tolist()
     tokens_h = tokens.cpu()
     return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
 
 
-def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float, bias=None,
-                           lm=None):
-    """``max_length`` steps of n one-pass joint CTC / attention beam searches in lockstep (include/eec.h, "CTC prefix scores"):
-    ``step(last [n, R], parent [n, R] | None)`` returns the decoder's log-probs [n, R, V] of every beam, ``prefix.step`` mixes in
-    the CTC prefix scores and closes the beams that took EOS, ``beam_select`` ranks the result as in ``_lockstep_search``.  After
-    ``max_length`` steps every row is final as it stands; a row holds only PAD after its EOS; the best beam is the one with the
-    highest score, ties to the lower index.  Returns ``(final_tokens, final_scores, best_tokens)`` per search.  ``bias``: as in
-    ``_lockstep_search``, applied after ``prefix.step``; ``lm`` after that."""
-    scores = torch.zeros((n, 1), dtype=torch.float32, device=dev)
-    bufs = [torch.zeros((n, max(beam, 1), max_length + 1), dtype=torch.long, device=dev) for _ in range(2)]
-    bufs[0][:, 0, 0] = sos
-    last = bufs[0][:, :1, 0].contiguous()
-    parent: Optional[Tensor] = None
-    for i in range(max_length):
-        local = prefix.step(step(last, parent), last, parent)
-        if bias is not None:
-            local = bias.step(local, last, parent)
-        if lm is not None:
-            local = lm.step(local, last, parent)
-        scores, parent, last = beam_select(local, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
-    if bias is not None:  # rows that never took EOS give the provisional bonus of an open partial match back (0 for the others)
-        scores = scores + bias.final(last, parent) / sequence_length_penalty(max(max_length, 1), alpha)
-    tokens = bufs[max_length & 1][:, :beam]
-    ended = torch.cumsum((tokens == eos).to(torch.int32), dim=2) > 0
-    tokens[:, :, 1:] = torch.where(ended[:, :, :-1], torch.full_like(tokens[:, :, 1:], pad), tokens[:, :, 1:])  # rows of score -inf too
-    best = _first_argmax(scores).tolist()
-    tokens_h = tokens.cpu()
-    return [(list(tokens[i]), list(scores[i]), tokens_h[i, best[i]].tolist()) for i in range(n)]
+def _joint_lockstep_search(step, prefix, n: int, dev, max_length: int, sos: int, eos: int, pad: int, beam: int, alpha: float, scorers=()):
+    """``_lockstep_search`` as the one-pass joint CTC / attention search (include/eec.h, "CTC prefix scores"): ``prefix.step`` (a
+    ``CtcPrefixSession``) mixes the CTC prefix scores into the decoder's log-probs and closes the beams that took EOS, before the
+    other ``scorers``; at the end a row holds only PAD after its EOS, and the best beam is the one with the highest score, ties to
+    the lower index."""
+    def pick(tokens: Tensor, scores: Tensor) -> Tensor:
+        ended = torch.cumsum((tokens == eos).to(torch.int32), dim=2) > 0
+        tokens[:, :, 1:] = torch.where(ended[:, :, :-1], torch.full_like(tokens[:, :, 1:], pad), tokens[:, :, 1:])  # rows of score -inf too
+        return _first_argmax(scores)
+    return _lockstep_search(step, n, dev, max_length, sos, beam, alpha, pick, (prefix, *scorers))
 
 
 def _before_eos(ids, eos: int):
     """``ids`` up to, and excluding, the first EOS."""
     ids = list(ids)
     return ids[: ids.index(eos)] if eos in ids else ids
+
+
+def _check_rescoring_weight(rescoring_ctc_weight) -> float:
+    w = float(rescoring_ctc_weight)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
+    return w
 
 
 def _check_joint_weight(joint_ctc_weight, ctc_weight=None) -> float:
@@ -337,9 +367,15 @@ class BeamInference:
         ts = token_score if token_score is not None else self._token_score
         return lm, float(DEFAULT_LM_WEIGHT if w is None else w), float(0.0 if ts is None else ts)
 
-    @staticmethod
-    def _fusion_kw(fusion) -> dict:
-        return {} if fusion is None else {"token_lm": fusion[0], "token_lm_weight": fusion[1], "token_score": fusion[2]}
+    def _modifiers(self, name: str, context, graph_of, token_lm, token_lm_weight, token_score, given: Optional[_Modifiers] = None) -> _Modifiers:
+        """The modifiers of a call of the public method ``name`` from its five keywords, or ``given``: the ones a calling method has
+        resolved already (its ``_mods=``)."""
+        if given is not None:
+            return given
+        if context is None and graph_of is not None:
+            raise ValueError(f"{name}: graph_of chooses among the graphs of context=, which was not given")
+        return _Modifiers(context, None if graph_of is None else torch.as_tensor(graph_of).reshape(-1),
+                          self._fusion(token_lm, token_lm_weight, token_score))
 
     def _lexicon_decode(self, emission: Tensor, trie, nbest, beam_size, lm_weight=None, log_add=None, word_score=None):
         """(transcript of the best hypothesis per utterance, scores [B, nbest] and n_hyp [B] on the host)."""
@@ -411,12 +447,9 @@ class BeamInference:
         ``token_lm`` / ``token_lm_weight`` / ``token_score`` (or the constructor's): shallow fusion with a token-level n-gram model
         (``ctc_beam_decode(lm=)``); every hypothesis then carries ``.fusion`` beside its ``.score``.  Not together with ``context``."""
         beam = self._arg(beam_size, "beam_size")
-        ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
-        fusion = self._fusion(token_lm, token_lm_weight, token_score)
-        if fusion is not None:
-            ctx.update(lm=fusion[0], lm_weight=fusion[1], token_score=fusion[2])
+        mods = self._modifiers("ctc_cuda_predict", context, graph_of, token_lm, token_lm_weight, token_score)
         out = [t.cpu() for t in ctc_beam_decode(emission, beam_size=beam, blank=0, blank_skip_threshold=0.95, em_len=lengths, nbest=nbest,
-                                                **ctx)]
+                                                **mods.ctc_kw())]
         if nbest is None:  # the best prefix alone: an N-best list of one
             out = [t.unsqueeze(1) for t in out[:3]] + [torch.ones(out[0].size(0), dtype=torch.int32)] + [t.unsqueeze(1) for t in out[3:]]
         tok, cnt, score, n_hyp, *bias = out
@@ -424,7 +457,7 @@ class BeamInference:
                 for b in range(tok.size(0))]
         for b, row in enumerate(hyps if bias else []):
             for r, h in enumerate(row):
-                setattr(h, "bias" if fusion is None else "fusion", float(bias[0][b, r]))
+                setattr(h, "bias" if mods.fusion is None else "fusion", float(bias[0][b, r]))
         if lexicon is not None and detokenize is not None:
             flat = [h for row in hyps for h in row]
             for h, text in zip(flat, _snapped_texts([h.tokens for h in flat], lexicon, detokenize)):
@@ -561,7 +594,7 @@ class BeamInference:
     @torch.no_grad()
     def decode_all_exits(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
                          ctc_weight: Optional[float] = None, joint_ctc_weight: Optional[float] = None, context=None, graph_of=None,
-                         token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None, **kw) -> List[List[int]]:
+                         token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None, _mods=None, **kw) -> List[List[int]]:
         """What inference.py:31-51 does for ONE utterance: the best beam of every exit.  ``spec`` [n_mels, T],
         ``valid_len`` 0-D / [1].  The encoder runs once (taps of all exits).  ``ctc_weight``: the best beam of every exit is
         chosen jointly with that exit's CTC log-probs (``ctc_rescore``'s rule; they come from the same encoder pass).
@@ -571,15 +604,14 @@ class BeamInference:
         ``token_lm_weight`` / ``token_score``: shallow fusion in the lockstep searches, under the same condition."""
         if max_length is None:
             max_length = default_max_length(spec.size(1))
-        ctx = {} if context is None and graph_of is None else {"context": context, "graph_of": graph_of}
-        ctx.update(self._fusion_kw(self._fusion(token_lm, token_lm_weight, token_score)))
+        mods = self._modifiers("decode_all_exits", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
         if joint_ctc_weight is not None:
             _check_joint_weight(joint_ctc_weight, ctc_weight)
             logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=True, want_taps=True, n_groups=model._cfg.n_exits)[:2]
             exits = list(range(1, model._cfg.n_exits + 1))
             found = self.joint_search_exits(model, [taps[n - 1] for n in exits], exits, logp,
                                             encoder_lengths(valid_len.reshape(1).to(logp.device), logp.size(2)), joint_ctc_weight,
-                                            max_length, beam_size=beam_size, **(_lockstep_kw(kw) or {}), **ctx)
+                                            max_length, beam_size=beam_size, **(_lockstep_kw(kw) or {}), _mods=mods)
             return [best for _, _, best in found]
         logp, taps = model._run_encoder(spec.unsqueeze(0), valid_len.reshape(1), want_out=ctc_weight is not None, want_taps=True,
                                         n_groups=model._cfg.n_exits)[:2]
@@ -590,10 +622,10 @@ class BeamInference:
         lockstep = _lockstep_kw(kw)
         if lockstep is not None:
             together = self.beam_search_exits(model, [taps[n - 1] for n in exits], exits, max_length=max_length, beam_size=beam_size,
-                                              **lockstep, **ctc, **ctx)
+                                              **lockstep, **ctc, _mods=mods)
             if together is not None:
                 return [best for _, _, best in together]
-        if ctx:
+        if mods.context is not None or mods.fusion is not None:
             raise ValueError("decode_all_exits: contextual biasing and shallow fusion run in the lockstep searches only, and none serves this call "
                              "(kv_cache=False, max_length - 1 > min_length, or no session group for this model / geometry)")
         found = [self.beam_search(model, taps[n - 1], n, max_length=max_length, beam_size=beam_size, **kw) for n in exits]
@@ -607,7 +639,8 @@ class BeamInference:
                           max_length: int = 500, min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
                           ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
-                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
+                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None,
+                          _mods=None):
         """``beam_search`` for several exits of one utterance in lockstep: the searches are independent, so every decoder
         launch and every bookkeeping op covers all of them (``model.decoder_session_group``).  Returns the list of
         ``(final_tokens, final_scores, best_tokens)`` per exit, the same values as ``beam_search`` exit by exit -- or None
@@ -615,6 +648,7 @@ class BeamInference:
         (``max_length - 1 > min_length``), which would let the exits' beam counts diverge.  ``ctc_weight`` with ``emission``
         [len(layer_ns), 1, T', V] (and ``emission_len`` [1]): as in ``beam_search_batch``; ``context`` / ``graph_of`` [1] too."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        mods = self._modifiers("beam_search_exits", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_session_group"):
             return None
         if any(e.size(0) != 1 for e in encoder_outputs):
@@ -623,19 +657,14 @@ class BeamInference:
         if group is None or beam > group.max_beams:
             return None
         return _lockstep_search(group.step, len(layer_ns), encoder_outputs[0].device, max_length, sos, beam, alpha,
-                                self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1),
-                                _bias_session(context, graph_of, len(layer_ns), 1, beam, V),
-                                _lm_session(self._fusion(token_lm, token_lm_weight, token_score), len(layer_ns), beam, V))
+                                self._pick(ctc_weight, emission, emission_len, len(layer_ns), 1), mods.scorers(len(layer_ns), 1, beam, V))
 
     @staticmethod
     def _pick(ctc_weight, emission, emission_len, E: int, B: int):
         """The best-beam rule of E * B lockstep searches (search e * B + b): None without a CTC weight."""
         if ctc_weight is None:
             return None
-        if emission is None or emission.dim() != 4 or emission.size(0) != E or emission.size(1) != B:
-            raise ValueError(f"ctc_weight needs emission [{E}, {B}, T', V]: the CTC log-probs of every exit and utterance")
-        em_len = None if emission_len is None else emission_len.to(emission.device, torch.int32).reshape(B).repeat(E)
-        return _ctc_pick(emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, float(ctc_weight))
+        return _ctc_pick(*_exit_emission("ctc_weight", emission, emission_len, E, B), float(ctc_weight))
 
     def _lockstep_args(self, vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha):
         self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")  # accepted and unused: no beam finalises
@@ -646,7 +675,8 @@ class BeamInference:
                           min_length: int = 300, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                           PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None,
                           ctc_weight: Optional[float] = None, emission: Optional[Tensor] = None, emission_len: Optional[Tensor] = None,
-                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
+                          context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None,
+                          _mods=None):
         """``beam_search_exits`` for every utterance of a padded batch at once: ``taps`` [E, B, T', D] (or E tensors [B, T', D]),
         exit ``layer_ns[e]``'s encoder output of every utterance.  The E * B searches are independent and run in lockstep through
         one ``model.decoder_batch_session`` (every decoder launch covers all of them) and one ``eec_beam_select`` per step.
@@ -662,6 +692,7 @@ class BeamInference:
         ``sos=`` / ``eos=`` / ``pad=``; or the constructor's), ``token_lm_weight``, ``token_score``: shallow fusion -- one
         ``eec_lm_fusion_step`` per step in the same place (include/eec.h, "Shallow fusion"); it composes with ``context``."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        mods = self._modifiers("beam_search_batch", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
         if max_length < 1 or max_length - 1 > min_length or not hasattr(model, "decoder_batch_session"):
             return None
         session = model.decoder_batch_session(taps, layer_ns, max_length)
@@ -673,27 +704,24 @@ class BeamInference:
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
         found = _lockstep_search(step, n, session.dev, max_length, sos, beam, alpha, self._pick(ctc_weight, emission, emission_len, E, B),
-                                 _bias_session(context, graph_of, E, B, beam, V),
-                                 _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
+                                 mods.scorers(E, B, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     def _joint_args(self, emission, emission_len, E: int, B: int, V: int, joint_ctc_weight, EOS_token, PAD_token, blank: int):
         """The checked arguments of a joint search over E * B lockstep searches (search e * B + b)."""
         w = _check_joint_weight(joint_ctc_weight)
         eos, pad = self._arg(EOS_token, "trg_eos_idx"), self._arg(PAD_token, "trg_pad_idx")
-        if emission is None or emission.dim() != 4 or emission.size(0) != E or emission.size(1) != B:
-            raise ValueError(f"joint_ctc_weight needs emission [{E}, {B}, T', V]: the CTC log-probs of every exit and utterance")
-        if emission.size(3) != V:
-            raise ValueError(f"joint decoding needs one vocabulary for both heads: the decoder has {V} tokens, the emission {emission.size(3)}")
-        em_len = None if emission_len is None else emission_len.to(emission.device, torch.int32).reshape(B).repeat(E)
-        return w, eos, pad, emission.reshape(E * B, emission.size(2), V).float(), em_len, int(blank)
+        em, em_len = _exit_emission("joint_ctc_weight", emission, emission_len, E, B)
+        if em.size(2) != V:
+            raise ValueError(f"joint decoding needs one vocabulary for both heads: the decoder has {V} tokens, the emission {em.size(2)}")
+        return w, eos, pad, em.float(), em_len, int(blank)
 
     @torch.no_grad()
     def joint_search_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor],
                            joint_ctc_weight: float, max_length: int, min_length: int = 0, vocab_size: Optional[int] = None,
                            SOS_token: Optional[int] = None, EOS_token: Optional[int] = None, PAD_token: Optional[int] = None,
                            beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0, context=None, graph_of=None,
-                           token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
+                           token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None, _mods=None):
         """One-pass joint CTC / attention decoding (Watanabe et al. 2017; include/eec.h states the semantics) of every exit and
         utterance of a padded batch in lockstep: ``taps`` as for ``beam_search_batch``, ``emission`` [E, B, T', V] the exits' CTC
         log-probs of the same encoder pass (``emission_len`` [B]: their frames, None = T').  At every step the local score of a
@@ -705,6 +733,7 @@ class BeamInference:
         geometry / device: there is no reference search to fall back to.  ``context`` / ``graph_of`` [B]: as in ``beam_search_batch``,
         applied after the CTC prefix scores; ``token_lm`` / ``token_lm_weight`` / ``token_score`` too."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        mods = self._modifiers("joint_search_batch", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
         session = model.decoder_batch_session(taps, layer_ns, max_length) if max_length >= 1 and hasattr(model, "decoder_batch_session") else None
         if session is None or beam > session.max_beams:
             raise ValueError("joint_search_batch: no batched decoder session for this model, geometry, device or beam size")
@@ -715,9 +744,7 @@ class BeamInference:
 
         def step(last, parent):
             return session.step(last.view(E, B, -1), None if parent is None else parent.view(E, B, -1)).view(n, -1, V)
-        found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha,
-                                       _bias_session(context, graph_of, E, B, beam, V),
-                                       _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
+        found = _joint_lockstep_search(step, prefix, n, session.dev, max_length, sos, eos, pad, beam, alpha, mods.scorers(E, B, beam, V))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @torch.no_grad()
@@ -725,11 +752,13 @@ class BeamInference:
                            emission_len: Optional[Tensor], joint_ctc_weight: float, max_length: int, min_length: int = 0,
                            vocab_size: Optional[int] = None, SOS_token: Optional[int] = None, EOS_token: Optional[int] = None,
                            PAD_token: Optional[int] = None, beam_size: Optional[int] = None, pen_alpha: Optional[float] = None, blank: int = 0,
-                           context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
+                           context=None, graph_of=None, token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None,
+                           _mods=None):
         """``joint_search_batch`` for the exits of ONE utterance (``model.decoder_session_group``): ``encoder_outputs[i]`` [1, T', D]
         is exit ``layer_ns[i]``'s encoder output, ``emission`` [len(layer_ns), 1, T', V].  Returns the list of ``(final_tokens,
         final_scores, best_tokens)`` per exit; ValueError where no session group exists."""
         V, sos, beam, alpha = self._lockstep_args(vocab_size, SOS_token, EOS_token, PAD_token, beam_size, pen_alpha)
+        mods = self._modifiers("joint_search_exits", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
         group = None
         if max_length >= 1 and hasattr(model, "decoder_session_group") and all(e.size(0) == 1 for e in encoder_outputs):
             group = model.decoder_session_group(encoder_outputs, layer_ns, max_length)
@@ -739,8 +768,7 @@ class BeamInference:
         w, eos, pad, em, em_len, blank = self._joint_args(emission, emission_len, n, 1, V, joint_ctc_weight, EOS_token, PAD_token, blank)
         prefix = ctc_prefix_session(em, em_len, beam, w, eos, pad, blank=blank, min_length=min_length)
         return _joint_lockstep_search(group.step, prefix, n, encoder_outputs[0].device, max_length, sos, eos, pad, beam, alpha,
-                                      _bias_session(context, graph_of, n, 1, beam, V),
-                                      _lm_session(self._fusion(token_lm, token_lm_weight, token_score), n, beam, V))
+                                      mods.scorers(n, 1, beam, V))
 
     @torch.no_grad()
     def decode_batch(self, model, spec: Tensor, valid_len: Tensor, max_length: Optional[int] = None, beam_size: int = 10,
@@ -766,10 +794,7 @@ class BeamInference:
         constructor's): shallow fusion with a token-level n-gram model in the same searches; without a model nothing changes."""
         if max_length is None:  # one length for the whole padded batch
             max_length = default_max_length(spec.size(2))
-        if context is None and graph_of is not None:
-            raise ValueError("decode_batch: graph_of chooses among the graphs of context=, which was not given")
-        rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(-1)
-        fused = self._fusion_kw(self._fusion(token_lm, token_lm_weight, token_score))
+        mods = self._modifiers("decode_batch", context, graph_of, token_lm, token_lm_weight, token_score)
         E = model._cfg.n_exits
         exits = list(range(1, E + 1))
         valid_len = valid_len.reshape(-1)
@@ -780,41 +805,33 @@ class BeamInference:
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             together, lockstep = None, _lockstep_kw(kw)
-            ctx = {} if context is None else {"context": context, "graph_of": None if rows_of is None else rows_of[c0:c0 + step]}
-            ctx.update(fused)
             if joint_ctc_weight is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
                 together = self.joint_search_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), joint_ctc_weight,
-                                                   max_length, beam_size=beam_size, **(lockstep or {}), **ctx)
+                                                   max_length, beam_size=beam_size, **(lockstep or {}), _mods=mods.chunk(c0, step))
                 del taps, logp
             elif lockstep is not None:
                 logp, taps = model._run_encoder(sp, vl, want_out=ctc_weight is not None, want_taps=True, n_groups=E)[:2]
                 ctc = {}
                 if ctc_weight is not None:
                     ctc = dict(ctc_weight=ctc_weight, emission=logp, emission_len=encoder_lengths(vl.to(logp.device), logp.size(2)))
-                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc, **ctx)
+                together = self.beam_search_batch(model, taps, exits, max_length=max_length, beam_size=beam_size, **lockstep, **ctc,
+                                                  _mods=mods.chunk(c0, step))
                 del taps, logp, ctc
             if together is None:
-                one = lambda b: dict(fused) if context is None else {"context": context, "graph_of": None if rows_of is None else rows_of[c0 + b: c0 + b + 1], **fused}  # noqa: E731
-                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight, **one(b), **kw)
-                        for b in range(sp.size(0))]
+                out += [self.decode_all_exits(model, sp[b], vl[b], max_length=max_length, beam_size=beam_size, ctc_weight=ctc_weight,
+                                              _mods=mods.chunk(c0 + b, 1), **kw) for b in range(sp.size(0))]
             else:
                 out += [[best for _, _, best in row] for row in together]
-        if lexicon is not None and detokenize is not None:
-            cut = (lambda ids: ids) if joint_ctc_weight is None else (lambda ids: _before_eos(ids, self._arg(kw.get("EOS_token"), "trg_eos_idx")))
-            texts = iter(_snapped_texts([cut(ids) for row in out for ids in row], lexicon, detokenize))
-            out = [[DecodedTokens(ids) for ids in row] for row in out]
-            for row in out:
-                for ids in row:
-                    ids.text = next(texts)
-        return out
+        cut = (lambda ids: ids) if joint_ctc_weight is None else (lambda ids: _before_eos(ids, self._arg(kw.get("EOS_token"), "trg_eos_idx")))
+        return _with_texts(out, lexicon, detokenize, cut)
 
     # -- two-pass decoding: the CTC head proposes an N-best list, the attention decoder scores it in one teacher-forced pass ---
     @torch.no_grad()
     def rescore_batch(self, model, taps, layer_ns: Sequence[int], emission: Tensor, emission_len: Optional[Tensor], nbest: int,
                       rescoring_ctc_weight: float, beam_size: Optional[int] = None, SOS_token: Optional[int] = None,
                       EOS_token: Optional[int] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30, context=None, graph_of=None,
-                      token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None):
+                      token_lm=None, token_lm_weight: Optional[float] = None, token_score: Optional[float] = None, _mods=None):
         """Two-pass decoding of exits ``layer_ns`` for every utterance of a padded batch: ``taps`` [E, B, T', D] (or E tensors
         [B, T', D]) and ``emission`` [E, B, T', V], the exits' encoder outputs and CTC log-probs of one encoder pass
         (``emission_len`` [B]: their frames, None = T').  First pass: the N-best lists of all E * B emissions in ONE prefix beam
@@ -830,46 +847,33 @@ class BeamInference:
         ``token_lm`` / ``token_lm_weight`` / ``token_score`` (or the constructor's; not together with ``context``): the first pass is the
         fused search (``ctc_beam_decode(lm=)``), ``joint = (1 - w) * att + w * ctc + fusion`` in fp64, and each list is a
         ``FusedRescoredList`` that also carries ``fusion``."""
-        w = float(rescoring_ctc_weight)
-        if not 0.0 <= w <= 1.0:
-            raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
+        w = _check_rescoring_weight(rescoring_ctc_weight)
         if not hasattr(model, "score_hypotheses"):
             raise ValueError("rescore_batch: the model has no attention decoder to rescore with (full_conformer)")
         beam = self._arg(beam_size, "beam_size")
         sos, eos = self._arg(SOS_token, "trg_sos_idx"), self._arg(EOS_token, "trg_eos_idx")
         E = len(layer_ns)
-        if emission is None or emission.dim() != 4 or emission.size(0) != E or len(taps) != E or taps[0].size(0) != emission.size(1):
-            raise ValueError(f"rescore_batch needs taps [{E}, B, T', D] and emission [{E}, B, T', V] of one encoder pass")
+        em, em_len = _exit_emission("rescore_batch", emission, emission_len, E)
         B = emission.size(1)
-        dev = emission.device
-        em_len = None if emission_len is None else emission_len.to(dev, torch.int32).reshape(B).repeat(E)
-        groups = [(layer_ns[e], taps[e], torch.arange(e * B, (e + 1) * B, device=dev)) for e in range(E)]
-        if context is None and graph_of is not None:
-            raise ValueError("rescore_batch: graph_of chooses among the graphs of context=, which was not given")
-        rows_of = None if graph_of is None else torch.as_tensor(graph_of).reshape(B).repeat(E)
-        found = self._rescore(model, emission.reshape(E * B, emission.size(2), emission.size(3)), em_len, groups, nbest, w, beam, sos, eos, blank,
-                              max_workspace_bytes, context, rows_of, self._fusion(token_lm, token_lm_weight, token_score))
+        if len(taps) != E or taps[0].size(0) != B:
+            raise ValueError(f"rescore_batch needs taps [{E}, B, T', D] and emission [{E}, B, T', V] of one encoder pass")
+        groups = [(layer_ns[e], taps[e], torch.arange(e * B, (e + 1) * B, device=em.device)) for e in range(E)]
+        mods = self._modifiers("rescore_batch", context, graph_of, token_lm, token_lm_weight, token_score, _mods)
+        found = self._rescore(model, em, em_len, groups, nbest, w, beam, sos, eos, blank, max_workspace_bytes, mods.over_exits(E, B))
         return [[found[e * B + b] for e in range(E)] for b in range(B)]
 
     @staticmethod
     def _rescore(model, em: Tensor, em_len: Optional[Tensor], groups, nbest: int, w: float, beam: int, sos: int, eos: int, blank: int,
-                 max_workspace_bytes: int, context=None, graph_of=None, fusion=None):
+                 max_workspace_bytes: int, mods: _Modifiers = _Modifiers()):
         """The two passes over n searches (``em`` [n, T', V], ``em_len`` [n] or None): one N-best launch for all of them, then one
         ``score_hypotheses`` call per ``(layer_n, enc [m, T', D], rows int64 [m])`` of ``groups`` -- the searches ``rows`` belong to
         exit ``layer_n``, search ``rows[i]`` has the memory ``enc[i]``; every search is in exactly one group.  Returns the list
-        of ``(best_tokens, RescoredList)`` per search.  ``context`` / ``graph_of`` [n]: the first pass is biased and its bias enters
-        ``joint``.  ``fusion`` = (model, weight, bonus): the first pass is fused instead and its fusion scores enter ``joint``."""
+        of ``(best_tokens, RescoredList)`` per search.  ``mods`` (its ``graph_of`` [n]): under a context graph the first pass is biased
+        and its bias enters ``joint``; under a language model it is fused instead and its fusion scores enter ``joint``."""
         dev = em.device
-        bias = None
-        if fusion is not None:
-            tokens, counts, ctc, n_hyp, bias = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
-                                                               context=context, graph_of=graph_of, lm=fusion[0], lm_weight=fusion[1],
-                                                               token_score=fusion[2])
-        elif context is None:
-            tokens, counts, ctc, n_hyp = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest)
-        else:
-            tokens, counts, ctc, n_hyp, bias = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
-                                                               context=context, graph_of=graph_of)
+        tokens, counts, ctc, n_hyp, *extra = ctc_beam_decode(em, beam_size=beam, blank=blank, blank_skip_threshold=0.95, em_len=em_len, nbest=nbest,
+                                                             **mods.ctc_kw())
+        bias = extra[0] if extra else None
         present = torch.arange(nbest, device=dev).view(1, -1) < n_hyp.view(-1, 1)
         lengths = torch.where(present, counts, torch.full_like(counts, -1))
         L = max(int(counts.max()), 1)  # the one host read in front of the second pass: the decoder rows are L + 1 long
@@ -887,7 +891,7 @@ class BeamInference:
         joint = torch.where(present, joint, torch.full_like(joint, -float("inf")))
         best = _first_argmax(joint).cpu().tolist()
         tokens, counts, n_hyp, ctc, att, joint = (t.cpu().tolist() for t in (tokens, counts, n_hyp, ctc, att, joint))
-        fused = None if fusion is None else bias.cpu().tolist()
+        fused = None if mods.fusion is None else bias.cpu().tolist()
 
         def one(i):
             k = n_hyp[i]
@@ -908,7 +912,8 @@ class BeamInference:
         w * CTC``.  One encoder pass per chunk of at most ``max_batch`` utterances (taps and log-probs of all exits), one N-best
         launch and one ``score_hypotheses`` call per exit; no decoder step loop.  ``rescoring_ctc_weight`` defaults to 0.5, WeNet's
         customary value; it is not tuned here.  The ids carry no SOS / EOS.  ``lexicon`` / ``detokenize`` as in ``decode_batch``.
-        ``token_lm=`` / ``token_lm_weight=`` / ``token_score=`` go to ``rescore_batch`` with the other keywords."""
+        ``token_lm=`` / ``token_lm_weight=`` / ``token_score=`` are ``rescore_batch``'s; the other keywords go to it as they are."""
+        mods = self._modifiers("decode_batch_rescoring", context, graph_of, *(kw.pop(k, None) for k in ("token_lm", "token_lm_weight", "token_score")))
         if beam_size is None:
             beam_size = max(int(getattr(self.args, "beam_size", nbest)), nbest)
         E = model._cfg.n_exits
@@ -919,19 +924,11 @@ class BeamInference:
         for c0 in range(0, spec.size(0), step):
             sp, vl = spec[c0:c0 + step], valid_len[c0:c0 + step]
             logp, taps = model._run_encoder(sp, vl, want_out=True, want_taps=True, n_groups=E)[:2]
-            ctx = {} if context is None and graph_of is None else \
-                {"context": context, "graph_of": None if graph_of is None else torch.as_tensor(graph_of).reshape(-1)[c0:c0 + step]}
             found = self.rescore_batch(model, taps, exits, logp, encoder_lengths(vl.to(logp.device), logp.size(2)), nbest,
-                                       rescoring_ctc_weight, beam_size=beam_size, **ctx, **kw)
+                                       rescoring_ctc_weight, beam_size=beam_size, _mods=mods.chunk(c0, step), **kw)
             out += [[best for best, _ in row] for row in found]
             del taps, logp
-        if lexicon is not None and detokenize is not None:
-            texts = iter(_snapped_texts([ids for row in out for ids in row], lexicon, detokenize))
-            out = [[DecodedTokens(ids) for ids in row] for row in out]
-            for row in out:
-                for ids in row:
-                    ids.text = next(texts)
-        return out
+        return _with_texts(out, lexicon, detokenize)
 
     # -- adaptive inference: every utterance decoded at the one exit it left the encoder at --------------------------------
     @torch.no_grad()
@@ -983,9 +980,7 @@ class BeamInference:
         if rescoring_ctc_weight is not None:
             if joint_ctc_weight is not None:
                 raise ValueError("decode_batch_adaptive: rescoring_ctc_weight and joint_ctc_weight are two different searches; give one")
-            w = float(rescoring_ctc_weight)
-            if not 0.0 <= w <= 1.0:
-                raise ValueError(f"rescoring_ctc_weight must lie in [0, 1], got {rescoring_ctc_weight!r}")
+            w = _check_rescoring_weight(rescoring_ctc_weight)
             unknown = sorted(set(kw) - {"SOS_token", "EOS_token", "blank", "max_workspace_bytes"})
             if unknown:
                 raise TypeError(f"decode_batch_adaptive: with rescoring_ctc_weight the keywords {unknown} have no meaning")

@@ -12,6 +12,7 @@ import torch
 from torch import Tensor
 
 from . import capi
+from .decoding import BeamStateSession
 
 
 class ContextGraph:
@@ -147,7 +148,7 @@ def graph_rows(name: str, graph_of, n: int, dev) -> Optional[Tensor]:
     return g.reshape(n).clamp(-1, 2 ** 31 - 1).to(device=dev, dtype=torch.int32).contiguous()
 
 
-class ContextBiasSession:
+class ContextBiasSession(BeamStateSession):
     """The bias of n lockstep beam searches of up to ``R`` beams each: ``step(local [n, R', V], last [n, R'], parent [n, R'] | None)
     -> local`` first advances every beam's graph state -- beam r extends row ``parent[i, r]`` of the previous step by the token
     ``last[i, r]``; the first call starts at the root and does not read ``last`` (SOS) -- and then adds ``delta[state][v]`` to the row
@@ -160,57 +161,17 @@ class ContextBiasSession:
             raise ValueError(f"1 .. 16 beams per search, got {R}")
         self.graph, self.n, self.R_max, self.V = graph, int(n), int(R), graph.vocab_size
         self._graph_of = graph_rows("ContextBiasSession", graph_of, self.n, "cpu")
-        self.s, self.rows = 0, 0
-        self._dev = None
-        self._host_state = None
 
     def _begin(self, dev) -> None:
-        self._dev = dev
         if dev.type != "cuda":
             return
         self._image = self.graph.to(dev)
         self._g = None if self._graph_of is None else self._graph_of.to(dev)
-        self._nbytes = capi.load().eec_context_bias_state_bytes(self.n, self.R_max)
-        self._state = torch.zeros(max(self._nbytes // 4, 1), dtype=torch.int32, device=dev)
+        self._new_state(capi.load().eec_context_bias_state_bytes(self.n, self.R_max))
 
-    def step(self, local: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
-        n, V = self.n, self.V
-        if local.dim() != 3 or local.size(0) != n or local.size(2) != V:
-            raise ValueError(f"local must be [{n}, live beams, {V}], got {tuple(local.shape)}")
-        R = int(local.size(1))
-        if not 1 <= R <= self.R_max:
-            raise ValueError(f"1 .. {self.R_max} live beams per search and step, got {R}")
-        if tuple(last.shape) != (n, R) or (parent is not None and tuple(parent.shape) != (n, R)):
-            raise ValueError(f"last and parent must be [{n}, {R}]")
-        if self._dev is None:
-            self._begin(local.device)
-        elif local.device != self._dev:
-            raise RuntimeError(f"the session lives on {self._dev}, local is on {local.device}")
-        if not local.is_cuda:
-            out = self._host_step(local.float(), last.to(torch.int64), None if parent is None else parent.to(torch.int64), R)
-        else:
-            dev = self._dev
-            local = capi.require_fp32("local", local, dev)
-            if last.device != dev or (parent is not None and parent.device != dev):
-                raise RuntimeError(f"last and parent must be on {dev}")
-            tok = last.to(torch.int64).contiguous()
-            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty_like(local)
-            capi.launch("eec_context_bias_step", dev, self._image, self.graph.nbytes, self._g, n, R, self.rows, self.R_max, V, self.s, par, tok,
-                        local, out, self._state, self._nbytes)
-            stream = torch.cuda.current_stream(dev)
-            for t in (local, tok, par):
-                if t is not None:
-                    t.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        return out
-
-    def states(self) -> Tensor:
-        """The graph state int32 [n, R'] of the current beams (after the last ``step``)."""
-        if self._dev is None or self._dev.type != "cuda":
-            return self._host_state.to(torch.int32).clone()
-        return self._state[: 2 * self.n * self.R_max].view(2, self.n, self.R_max)[self.s & 1, :, : max(self.rows, 1)].clone()
+    def _launch(self, local, tok, par, R, out) -> None:
+        capi.launch("eec_context_bias_step", self._dev, self._image, self.graph.nbytes, self._g, self.n, R, self.rows, self.R_max, self.V,
+                    self.s, par, tok, local, out, self._state, self._nbytes)
 
     def final(self, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
         """``final[state]`` [n, R'] fp32 of the beams the last selection made -- beam r extends row ``parent[i, r]`` of the last ``step``

@@ -198,22 +198,12 @@ size_t eec_context_bias_state_bytes(int n, int R_max) {
 int eec_context_bias_step(const void* image, size_t image_bytes, const int32_t* graph_of, int n, int R, int R_prev, int R_max, int V, int s,
                           const int64_t* parent, const int64_t* last, const float* local, float* out, void* state, size_t state_bytes,
                           void* stream) {
-  using eech::fail;
-  if (n < 0 || V < 1 || V > 256 || R_max < 1 || R_max > 16)
-    return fail(EEC_ERR_BAD_ARG, "eec_context_bias_step: needs n >= 0, 1 <= V <= 256 and 1 <= R_max <= 16");
-  if (R < 1 || R > R_max || s < 0 || (s > 0 && (R_prev < 1 || R_prev > R_max)))
-    return fail(EEC_ERR_BAD_ARG, "eec_context_bias_step: 1 <= R, R_prev <= R_max and s >= 0");
-  if (n == 0) return 0;
-  if ((long long)n * R > 0x7fffffffLL) return fail(EEC_ERR_UNSUPPORTED, "eec_context_bias_step: n * R must stay below 2^31");
-  if (!local || !out || !state || (s > 0 && !last)) return fail(EEC_ERR_BAD_ARG, "eec_context_bias_step: null argument (local, out, state, last)");
-  if (((uintptr_t)state & 3) != 0 || ((uintptr_t)image & 3) != 0) return fail(EEC_ERR_WORKSPACE, "eec_context_bias_step: image and state must be 4-byte aligned");
-  if (state_bytes < eec_context_bias_state_bytes(n, R_max))
-    return fail(EEC_ERR_WORKSPACE, "eec_context_bias_step: state buffer too small (eec_context_bias_state_bytes)");
-  int* base = (int*)state;
-  const size_t half = (size_t)n * R_max;
+  eech::StepHalves h;
+  const int rc = eech::step_head("eec_context_bias_step", "image", nullptr, image, n, R, R_prev, R_max, V, s, last, local, out, state, state_bytes, &h);
+  if (rc != 0 || !h.src) return rc;
   hipLaunchKernelGGL(eec::context_bias_step_kernel, dim3(n * R), dim3((V + 63) / 64 * 64), 0, (hipStream_t)stream, (const int*)image,
                      (long long)(image_bytes / 4), graph_of, R, R_prev, R_max, V, s, (const long long*)parent, (const long long*)last, local, out,
-                     base + (size_t)(s & 1) * half, base + (size_t)((s + 1) & 1) * half);
+                     h.src, h.dst);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : eech::hip_fail(e, "eec_context_bias_step launch");
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <string>
 
@@ -85,6 +86,36 @@ inline int check_precision(int precision) {
 }
 inline int check_passes(int passes) {
   if (passes != 1 && passes != 3) return fail(EEC_ERR_BAD_ARG, "passes: 1 (bf16) or 3 (bf16x3)");
+  return 0;
+}
+
+// The head of a step entry over one int32 state per beam, double-buffered [2, n, R_max] (eec_context_bias_step,
+// eec_lm_fusion_step): the refusals under the entry's name `me` (`image_arg` names its image argument; `refused`: a refusal of
+// the entry's own, or nullptr, reported after the range checks), then the half step s reads and the one it writes.  Returns the
+// entry's return code; src stays nullptr where there is nothing to launch (a refusal, or n == 0).  `me` ends in "step", the
+// name of its size function in "state_bytes".
+struct StepHalves {
+  int *src = nullptr, *dst = nullptr;
+};
+inline int step_head(const char* me, const char* image_arg, const char* refused, const void* image, int n, int R, int R_prev, int R_max,
+                     int V, int s, const void* last, const void* local, const void* out, void* state, size_t state_bytes,
+                     StepHalves* h) {
+  const std::string m = std::string(me) + ": ";
+  if (n < 0 || V < 1 || V > 256 || R_max < 1 || R_max > 16)
+    return fail(EEC_ERR_BAD_ARG, m + "needs n >= 0, 1 <= V <= 256 and 1 <= R_max <= 16");
+  if (R < 1 || R > R_max || s < 0 || (s > 0 && (R_prev < 1 || R_prev > R_max)))
+    return fail(EEC_ERR_BAD_ARG, m + "1 <= R, R_prev <= R_max and s >= 0");
+  if (refused) return fail(EEC_ERR_BAD_ARG, m + refused);
+  if (n == 0) return 0;
+  if ((long long)n * R > 0x7fffffffLL) return fail(EEC_ERR_UNSUPPORTED, m + "n * R must stay below 2^31");
+  if (!local || !out || !state || (s > 0 && !last)) return fail(EEC_ERR_BAD_ARG, m + "null argument (local, out, state, last)");
+  if (((uintptr_t)state & 3) != 0 || ((uintptr_t)image & 3) != 0)
+    return fail(EEC_ERR_WORKSPACE, m + image_arg + " and state must be 4-byte aligned");
+  const size_t half = (size_t)n * R_max;
+  if (state_bytes < 2 * half * sizeof(int32_t))
+    return fail(EEC_ERR_WORKSPACE, m + "state buffer too small (" + std::string(me, strlen(me) - 4) + "state_bytes)");
+  h->src = (int*)state + (size_t)(s & 1) * half;
+  h->dst = (int*)state + (size_t)((s + 1) & 1) * half;
   return 0;
 }
 

@@ -100,23 +100,13 @@ size_t eec_lm_fusion_state_bytes(int n, int R_max) {
 int eec_lm_fusion_step(const void* lm, size_t lm_bytes, int n, int R, int R_prev, int R_max, int V, int s, const int64_t* parent,
                        const int64_t* last, const float* local, float* out, void* state, size_t state_bytes, float lm_weight,
                        float token_score, int eos, int skip0, int skip1, int skip2, void* stream) {
-  using eech::fail;
-  if (n < 0 || V < 1 || V > 256 || R_max < 1 || R_max > 16)
-    return fail(EEC_ERR_BAD_ARG, "eec_lm_fusion_step: needs n >= 0, 1 <= V <= 256 and 1 <= R_max <= 16");
-  if (R < 1 || R > R_max || s < 0 || (s > 0 && (R_prev < 1 || R_prev > R_max)))
-    return fail(EEC_ERR_BAD_ARG, "eec_lm_fusion_step: 1 <= R, R_prev <= R_max and s >= 0");
-  if (!isfinite(lm_weight) || !isfinite(token_score)) return fail(EEC_ERR_BAD_ARG, "eec_lm_fusion_step: lm_weight and token_score must be finite");
-  if (n == 0) return 0;
-  if ((long long)n * R > 0x7fffffffLL) return fail(EEC_ERR_UNSUPPORTED, "eec_lm_fusion_step: n * R must stay below 2^31");
-  if (!local || !out || !state || (s > 0 && !last)) return fail(EEC_ERR_BAD_ARG, "eec_lm_fusion_step: null argument (local, out, state, last)");
-  if (((uintptr_t)state & 3) != 0 || ((uintptr_t)lm & 3) != 0) return fail(EEC_ERR_WORKSPACE, "eec_lm_fusion_step: lm and state must be 4-byte aligned");
-  if (state_bytes < eec_lm_fusion_state_bytes(n, R_max))
-    return fail(EEC_ERR_WORKSPACE, "eec_lm_fusion_step: state buffer too small (eec_lm_fusion_state_bytes)");
-  int* base = (int*)state;
-  const size_t half = (size_t)n * R_max;
+  const char* refused = isfinite(lm_weight) && isfinite(token_score) ? nullptr : "lm_weight and token_score must be finite";
+  eech::StepHalves h;
+  const int rc = eech::step_head("eec_lm_fusion_step", "lm", refused, lm, n, R, R_prev, R_max, V, s, last, local, out, state, state_bytes, &h);
+  if (rc != 0 || !h.src) return rc;
   hipLaunchKernelGGL(eec::lm_fusion_step_kernel, dim3(n * R), dim3((V + 63) / 64 * 64), 0, (hipStream_t)stream, (const int*)lm,
                      (long long)(lm_bytes / 4), R, R_prev, R_max, V, s, (const long long*)parent, (const long long*)last, local, out,
-                     base + (size_t)(s & 1) * half, base + (size_t)((s + 1) & 1) * half, lm_weight, token_score, eos, skip0, skip1, skip2);
+                     h.src, h.dst, lm_weight, token_score, eos, skip0, skip1, skip2);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : eech::hip_fail(e, "eec_lm_fusion_step launch");
 }

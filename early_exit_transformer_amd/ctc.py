@@ -15,6 +15,7 @@ from torch import Tensor
 
 from . import capi
 from .capi import launch, to_device
+from .decoding import ScorerSession
 
 
 def encoder_lengths(lengths: Tensor, t_out: int) -> Tensor:
@@ -253,7 +254,7 @@ def log_add32(a: Tensor, b: Tensor) -> Tensor:
     return torch.where(near, hi + s, hi)
 
 
-class CtcPrefixSession:
+class CtcPrefixSession(ScorerSession):
     """CTC prefix scores of n lockstep beam searches for one-pass joint CTC / attention decoding (include/eec.h,
     csrc/ctc_prefix.hip): ``step(att [n, R, V], last [n, R], parent [n, R] | None)`` first advances the state to the R current
     beams -- beam r extends row ``parent[i, r]`` of the previous step by the token ``last[i, r]`` --, then returns the joint local
@@ -277,7 +278,6 @@ class CtcPrefixSession:
         self.blank, self.eos, self.pad, self.weight, self.min_length = int(blank), int(eos), int(pad), float(weight), int(min_length)
         self.dev = emission.device
         self.emission = emission.contiguous()
-        self.s, self.rows = 0, 0
         self.em_len = _frame_counts("ctc_prefix_session", "em_len", em_len, n, self.dev, any_dtype=True)
         if not self.emission.is_cuda:
             self._host_begin()
@@ -289,34 +289,21 @@ class CtcPrefixSession:
     def _head(self):
         return (self.emission, self.em_len, self.n, self.Tq, self.V, self.blank, self.R_max)
 
+    _arg = "att"
+
     def step(self, att: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
-        n, V = self.n, self.V
-        if att.dim() != 3 or att.size(0) != n or att.size(2) != V:
-            raise ValueError(f"att must be [{n}, live beams, {V}], got {tuple(att.shape)}")
-        R = int(att.size(1))
-        if tuple(last.shape) != (n, R) or (parent is not None and tuple(parent.shape) != (n, R)):
-            raise ValueError(f"last and parent must be [{n}, {R}]")
-        if not self.emission.is_cuda:
-            if not 1 <= R <= self.R_max:
-                raise ValueError(f"1 .. {self.R_max} live beams per search and step, got {R}")
-            local = self._host_step(att.float(), last.to(torch.int64), None if parent is None else parent.to(torch.int64), R)
-        else:
-            dev = self.dev
-            att = capi.require_fp32("att", att, dev)
-            if last.device != dev or (parent is not None and parent.device != dev):
-                raise RuntimeError(f"last and parent must be on {dev}")
-            tok = last.to(torch.int64).contiguous()
-            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            local = torch.empty((n, R, V), dtype=torch.float32, device=dev)
-            launch("eec_ctc_prefix_step", dev, *self._head(), par, tok, R, self.rows, self.s, att, self.weight, self.eos, self.pad,
-                   self.min_length, local, self._state[1], self.nbytes)
-            stream = torch.cuda.current_stream(dev)
-            for t in (att, tok, par):
-                if t is not None:
-                    t.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        return local
+        return super().step(att, last, parent)
+
+    def _device(self, att: Tensor):
+        return self.dev  # the emission's
+
+    def _check_rows(self, R: int) -> None:
+        if not self.emission.is_cuda:  # the device entry refuses a count outside its range itself
+            super()._check_rows(R)
+
+    def _launch(self, att, tok, par, R, local) -> None:
+        launch("eec_ctc_prefix_step", self.dev, *self._head(), par, tok, R, self.rows, self.s, att, self.weight, self.eos, self.pad,
+               self.min_length, local, self._state[1], self.nbytes)
 
     def prefix_scores(self) -> Tensor:
         """``pfx`` [n, R] of the current beams (after the last ``step``): the CTC log prefix probability of an open beam's

@@ -1,6 +1,6 @@
 """Attention-decoder side of ``full_conformer`` on the HIP path: one step of beam bookkeeping (``beam_select``), the step-wise
-decoding sessions over key / value caches (csrc/decoder_step.hip, decoder_batch.hip) and the decoder's training step behind
-autograd (csrc/decoder_train.hip)."""
+decoding sessions over key / value caches (csrc/decoder_step.hip, decoder_batch.hip), the base of the sessions that rescore a
+step of a lockstep search (``ScorerSession``) and the decoder's training step behind autograd (csrc/decoder_train.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -94,6 +94,75 @@ class DecoderStepSession:
         self.s += 1
         self.rows = R
         return out
+
+
+class ScorerSession:
+    """What the scorers of a lockstep search share (``ctc.CtcPrefixSession``, ``context.ContextBiasSession``,
+    ``lm_fusion.LMFusionSession``): ``step(local [n, R, V], last [n, R], parent [n, R] | None) -> [n, R, V]`` checks the shapes,
+    hands fp32 / int64 tensors to the host path (CPU tensors) or to the one launch of the device path -- on the current stream, no
+    synchronisation; ``parent`` is not read at step 0 -- and counts the step (``s``) and its live beams (``rows``).  A subclass has
+    ``n``, ``V`` and ``R_max`` and contributes ``_device(local)`` (where the session lives), ``_launch(local, tok, par, R, out)``
+    and ``_host_step(local, last, parent, R) -> out``."""
+
+    _arg = "local"  # the first argument's name in messages
+    s = rows = 0
+
+    def _check_rows(self, R: int) -> None:
+        if not 1 <= R <= self.R_max:
+            raise ValueError(f"1 .. {self.R_max} live beams per search and step, got {R}")
+
+    def step(self, local: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
+        n, V = self.n, self.V
+        if local.dim() != 3 or local.size(0) != n or local.size(2) != V:
+            raise ValueError(f"{self._arg} must be [{n}, live beams, {V}], got {tuple(local.shape)}")
+        R = int(local.size(1))
+        self._check_rows(R)
+        if tuple(last.shape) != (n, R) or (parent is not None and tuple(parent.shape) != (n, R)):
+            raise ValueError(f"last and parent must be [{n}, {R}]")
+        dev = self._device(local)
+        if dev.type != "cuda":
+            out = self._host_step(local.float(), last.to(torch.int64), None if parent is None else parent.to(torch.int64), R)
+        else:
+            local = capi.require_fp32(self._arg, local, dev)
+            if last.device != dev or (parent is not None and parent.device != dev):
+                raise RuntimeError(f"last and parent must be on {dev}")
+            tok = last.to(torch.int64).contiguous()
+            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
+            out = torch.empty_like(local)
+            self._launch(local, tok, par, R, out)
+            stream = torch.cuda.current_stream(dev)
+            for t in (local, tok, par):
+                if t is not None:
+                    t.record_stream(stream)
+        self.s += 1
+        self.rows = R
+        return out
+
+
+class BeamStateSession(ScorerSession):
+    """A scorer whose state is one int32 per beam, double-buffered on the device ([2, n, R_max] in ``_state``: step s reads half
+    ``s & 1`` and writes the other) and ``_host_state`` [n, R'] on the host.  It lives where the tensors of its first step live;
+    ``_begin(dev)`` prepares that device."""
+
+    _dev = _host_state = None
+
+    def _device(self, local: Tensor):
+        if self._dev is None:
+            self._dev = local.device
+            self._begin(local.device)
+        elif local.device != self._dev:
+            raise RuntimeError(f"the session lives on {self._dev}, local is on {local.device}")
+        return self._dev
+
+    def _new_state(self, nbytes: int) -> None:
+        self._nbytes = nbytes
+        self._state = torch.zeros(max(nbytes // 4, 1), dtype=torch.int32, device=self._dev)
+
+    def states(self) -> Tensor:
+        """The state int32 [n, R'] of the current beams (after the last ``step``)."""
+        if self._dev is None or self._dev.type != "cuda":
+            return self._host_state.to(torch.int32).clone()
+        return self._state[: 2 * self.n * self.R_max].view(2, self.n, self.R_max)[self.s & 1, :, : max(self.rows, 1)].clone()
 
 
 class _ExitSessions(DecoderStepSession):

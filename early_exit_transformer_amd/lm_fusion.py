@@ -13,6 +13,7 @@ import torch
 from torch import Tensor
 
 from . import capi
+from .decoding import BeamStateSession
 from .lexicon import NGramLM
 
 DEFAULT_LM_WEIGHT = 0.3
@@ -238,14 +239,15 @@ def check_lm(name: str, lm, V: int, beam: int, lm_weight: float, token_score: fl
         raise ValueError(f"{name}: lm_weight and token_score must be finite")
 
 
-class LMFusionSession:
+class LMFusionSession(BeamStateSession):
     """Shallow fusion for n lockstep beam searches of up to ``R`` beams each: ``step(local [n, R', V], last [n, R'], parent [n, R'] |
     None) -> local`` first advances every beam's LM state -- beam r extends row ``parent[i, r]`` of the previous step by the token
     ``last[i, r]``; the first call starts at the model's start state and does not read ``last`` (SOS) -- and then adds
     ``inc(state, v)`` to the row (-inf stays -inf).  ``ContextBiasSession.step``'s signature and place in the loop; the two compose,
-    both are additive.  Device tensors: one launch per step on the current stream (eec_lm_fusion_step), no synchronisation.  CPU
-    tensors: the same statement in NumPy fp32, bit for bit -- per row, the back-off walk's additions in its order, one rounded product
-    ``lm_weight * acc``, one rounded sum with ``token_score``, one rounded sum with the entry."""
+    both are additive; ``states()`` are the LM states, -1 for a row past its EOS.  Device tensors: one launch per step on the current
+    stream (eec_lm_fusion_step), no synchronisation.  CPU tensors: the same statement in NumPy fp32, bit for bit -- per row, the back-off
+    walk's additions in its order, one rounded product ``lm_weight * acc``, one rounded sum with ``token_score``, one rounded sum with
+    the entry."""
 
     def __init__(self, lm: TokenLM, n: int, R: int, lm_weight: float = DEFAULT_LM_WEIGHT, token_score: float = 0.0, image: Optional[Tensor] = None):
         """``image`` (None: the model's own): the packed image the session hands to the kernel instead, a host uint8 tensor -- for
@@ -254,57 +256,17 @@ class LMFusionSession:
         self._host_image = image
         self.lm, self.n, self.R_max, self.V = lm, int(n), int(R), lm.V
         self.lm_weight, self.token_score = float(lm_weight), float(token_score)
-        self.s, self.rows = 0, 0
-        self._dev = None
-        self._host_state = None
 
     def _begin(self, dev) -> None:
-        self._dev = dev
         if dev.type != "cuda":
             return
         self._image = self.lm.on(dev) if self._host_image is None else self._host_image.to(dev)
         self._image_bytes = self.lm.nbytes if self._host_image is None else int(self._host_image.numel() * self._host_image.element_size())
-        self._nbytes = capi.load().eec_lm_fusion_state_bytes(self.n, self.R_max)
-        self._state = torch.zeros(max(self._nbytes // 4, 1), dtype=torch.int32, device=dev)
+        self._new_state(capi.load().eec_lm_fusion_state_bytes(self.n, self.R_max))
 
-    def step(self, local: Tensor, last: Tensor, parent: Optional[Tensor] = None) -> Tensor:
-        n, V = self.n, self.V
-        if local.dim() != 3 or local.size(0) != n or local.size(2) != V:
-            raise ValueError(f"local must be [{n}, live beams, {V}], got {tuple(local.shape)}")
-        R = int(local.size(1))
-        if not 1 <= R <= self.R_max:
-            raise ValueError(f"1 .. {self.R_max} live beams per search and step, got {R}")
-        if tuple(last.shape) != (n, R) or (parent is not None and tuple(parent.shape) != (n, R)):
-            raise ValueError(f"last and parent must be [{n}, {R}]")
-        if self._dev is None:
-            self._begin(local.device)
-        elif local.device != self._dev:
-            raise RuntimeError(f"the session lives on {self._dev}, local is on {local.device}")
-        if not local.is_cuda:
-            out = self._host_step(local.float(), last.to(torch.int64), None if parent is None else parent.to(torch.int64), R)
-        else:
-            dev, lm = self._dev, self.lm
-            local = capi.require_fp32("local", local, dev)
-            if last.device != dev or (parent is not None and parent.device != dev):
-                raise RuntimeError(f"last and parent must be on {dev}")
-            tok = last.to(torch.int64).contiguous()
-            par = parent.to(torch.int64).contiguous() if parent is not None and self.s > 0 else None
-            out = torch.empty_like(local)
-            capi.launch("eec_lm_fusion_step", dev, self._image, self._image_bytes, n, R, self.rows, self.R_max, V, self.s, par, tok, local, out,
-                        self._state, self._nbytes, self.lm_weight, self.token_score, lm.eos, *lm.skip)
-            stream = torch.cuda.current_stream(dev)
-            for t in (local, tok, par):
-                if t is not None:
-                    t.record_stream(stream)
-        self.s += 1
-        self.rows = R
-        return out
-
-    def states(self) -> Tensor:
-        """The LM state int32 [n, R'] of the current beams (after the last ``step``); -1: a row past its EOS."""
-        if self._dev is None or self._dev.type != "cuda":
-            return self._host_state.to(torch.int32).clone()
-        return self._state[: 2 * self.n * self.R_max].view(2, self.n, self.R_max)[self.s & 1, :, : max(self.rows, 1)].clone()
+    def _launch(self, local, tok, par, R, out) -> None:
+        capi.launch("eec_lm_fusion_step", self._dev, self._image, self._image_bytes, self.n, R, self.rows, self.R_max, self.V, self.s, par, tok,
+                    local, out, self._state, self._nbytes, self.lm_weight, self.token_score, self.lm.eos, *self.lm.skip)
 
     def _host_step(self, local: Tensor, last: Tensor, parent: Optional[Tensor], R: int) -> Tensor:
         n, V, lm = self.n, self.V, self.lm

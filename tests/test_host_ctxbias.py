@@ -232,7 +232,7 @@ def test_a_biased_lockstep_search_on_the_host_equals_a_plain_python_beam_search(
         return step
     moved = 0
     for alpha in (0.0, 0.6):
-        found = _lockstep_search(stepper(), n, torch.device("cpu"), steps, sos, beam, alpha, bias=ContextBiasSession(graph, n, beam))
+        found = _lockstep_search(stepper(), n, torch.device("cpu"), steps, sos, beam, alpha, scorers=[ContextBiasSession(graph, n, beam)])
         plain = _lockstep_search(stepper(), n, torch.device("cpu"), steps, sos, beam, alpha)
         for i in range(n):
             beams = [([sos], np.float32(0.0), 0)]

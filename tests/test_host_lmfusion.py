@@ -279,6 +279,63 @@ def test_beam_inference_resolves_the_model_and_its_weights(tmp_path):
     assert "fusion" in CTCHypothesis.__slots__ and RescoredList._fields == FusedRescoredList._fields
 
 
+def test_the_joint_lockstep_loop_applies_prefix_then_bias_then_model_and_the_final_term():
+    """``_joint_lockstep_search`` on CPU tensors with all three scorers -- a ``CtcPrefixSession``, a ``ContextBiasSession`` and an
+    ``LMFusionSession`` -- against the same three ``step`` calls written out around ``beam_select``, in the order prefix, bias, model,
+    with the ``final`` tail, the PAD rewrite and the first-best pick: tokens and scores bit for bit.  n = 2 searches, beam 3, 5 steps.
+    Search 0's emission allows the blank and one label over two frames, so two of its beams take EOS in the first two steps (asserted)
+    and go on by PAD, and its third row is dead (score -inf); search 1 follows a six-token phrase, which is still open when the steps
+    run out, so the ``final`` term is not zero (asserted)."""
+    from early_exit_transformer_amd.beam import _joint_lockstep_search, sequence_length_penalty
+    from early_exit_transformer_amd.context import ContextBiasSession, ContextGraph
+    from early_exit_transformer_amd.model import CtcPrefixSession, beam_select
+    model = X.random_model(2, 3, 37, lacking=4)
+    lm = X.token_lm(model)
+    n, beam, V, steps, alpha, w = 2, 3, model.V, 5, 0.6, 0.5
+    sos, eos, pad = model.sos, model.eos, model.pad
+    g = torch.Generator().manual_seed(3)
+    table = torch.log_softmax(torch.randn(n, steps, V, V, generator=g), -1)
+    em = torch.log_softmax(torch.randn(n, 6, V, generator=g), -1)
+    em[0] = NEG
+    em[0, :, 0], em[0, :, 5] = float(np.log(0.7)), float(np.log(0.3))
+    em_len = torch.tensor([2, 6])
+    graph = ContextGraph([(8, 9, 10, 11, 12, 13), (5,)], [3.0, 0.5], vocab_size=V, eos=eos, pad=pad)
+
+    def sessions():
+        return CtcPrefixSession(em, em_len, beam, w, eos, pad, blank=0), ContextBiasSession(graph, n, beam), LMFusionSession(lm, n, beam, 0.4, 0.1)
+
+    def _rows(k, last):  # a toy decoder: the log-probs depend on the step and the last token
+        return torch.stack([table[i, k][last[i]] for i in range(n)])
+    at = iter(range(steps))
+    prefix, bias, fusion = sessions()
+    found = _joint_lockstep_search(lambda last, parent: _rows(next(at), last), prefix, n, torch.device("cpu"), steps, sos, eos, pad, beam, alpha, [bias, fusion])
+
+    prefix, bias, fusion = sessions()
+    scores = torch.zeros((n, 1))
+    bufs = [torch.zeros((n, beam, steps + 1), dtype=torch.long) for _ in range(2)]
+    bufs[0][:, 0, 0] = sos
+    last, parent = bufs[0][:, :1, 0].contiguous(), None
+    for i in range(steps):
+        local = prefix.step(_rows(i, last), last, parent)
+        local = bias.step(local, last, parent)
+        local = fusion.step(local, last, parent)
+        scores, parent, last = beam_select(local, scores, sequence_length_penalty(i + 1, alpha), beam, bufs[i & 1], bufs[(i + 1) & 1], i + 1)
+    tail = bias.final(last, parent) / sequence_length_penalty(steps, alpha)
+    scores = scores + tail
+    raw = bufs[steps & 1]
+    tokens = raw.clone()
+    for i in range(n):
+        for r in range(beam):
+            row = raw[i, r].tolist()
+            if eos in row:
+                tokens[i, r, row.index(eos) + 1:] = pad
+    assert (raw[0, :2, 1:3] == eos).any(dim=1).all() and (tail != 0).any() and torch.isfinite(scores).any(dim=1).all()
+    for i in range(n):
+        final_tokens, final_scores, best = found[i]
+        assert torch.equal(torch.stack(final_tokens), tokens[i]) and torch.equal(torch.stack(final_scores), scores[i])
+        assert best == tokens[i, max(range(beam), key=lambda r: (float(scores[i, r]), -r))].tolist()
+
+
 def test_the_gpu_tests_inputs_leave_enough_ranks_to_compare():
     """The restated search at the GPU test's blocks, weights and variants: at least MIN_COMPARED of the present ranks have key gaps
     above BEAM_MARGIN, and fusion moves the best hypothesis of some sequences."""
