@@ -6,9 +6,14 @@ __version__ = "0.1.0"
 _CONTEXT = ("ContextGraph", "ContextBiasSession")  # contextual biasing (context.py), resolved at first use: importing the package stays light
 _LM_FUSION = ("TokenLM", "LMFusionSession")  # shallow fusion with a token-level n-gram model (lm_fusion.py), likewise
 _KEYWORD = ("KeywordSet", "KeywordHits", "keyword_search")  # keyword spotting on CTC emissions (keyword.py), likewise
+# word and token timestamps: CTC forced alignment in the standard topology (alignment.py), likewise
+_ALIGNMENT = ("Alignment", "TokenSpan", "WordSpan", "ctc_forced_align", "word_spans", "starts_word_from_pieces")
 
 
 def __getattr__(name):
+    if name in _ALIGNMENT:
+        from . import alignment
+        return getattr(alignment, name)
     if name in _KEYWORD:
         from . import keyword
         return getattr(keyword, name)

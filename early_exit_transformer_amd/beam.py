@@ -33,6 +33,9 @@
   best hypothesis is the one with the highest ``(1 - w) * att + w * ctc``: no autoregressive loop, no key / value cache.
 * ``BeamInference.spot``: keyword and phrase spotting (not in the reference): one encoder pass, then every keyword of a
   ``KeywordSet`` against the CTC emissions of all exits (``keyword_search``, csrc/keyword.hip), and the shallowest exit that hits.
+* ``BeamInference.timestamps``: token and word timestamps with confidences (not in the reference): one encoder pass, then the
+  transcripts any decoder above returned aligned against the CTC emission of an exit, or of every exit, in the standard CTC
+  topology (``ctc_forced_align``, csrc/ctc_forced_align.hip).
 * ``lexicon=`` / ``detokenize=`` on ``decode_batch`` and ``ctc_cuda_predict``: the ``apply_lex`` step inference.py:51,71 puts
   every printed hypothesis through, for all hypotheses of the call in one device search (``lexicon.Lexicon.apply_batch``).
 * ``BeamInference.error_table``: what any of the decoders above returned, scored against references (``scoring.error_table``;
@@ -51,6 +54,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from .alignment import FRAME_SECONDS, Alignment, ctc_forced_align, starts_word_from_pieces, transcript_rows, word_spans
 from .context import ContextBiasSession, ContextGraph
 from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
@@ -110,6 +114,14 @@ class RescoredList(NamedTuple):
     ctc: List[float]
     att: List[float]
     joint: List[float]
+
+
+class Timestamps(NamedTuple):
+    """What ``BeamInference.timestamps`` returns: per utterance ([B], or [E][B] for ``exits="all"``) the ``TokenSpan`` list and --
+    with ``pieces`` -- the ``WordSpan`` list (else ``words`` is None), and the ``Alignment`` they were read off."""
+    tokens: list
+    words: Optional[list]
+    alignment: Alignment
 
 
 class FusedRescoredList(RescoredList):
@@ -957,6 +969,56 @@ class BeamInference:
         logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
         hits = keyword_search(logp, keywords, encoder_lengths(valid_len.to(logp.device), logp.size(2)), want_trace=True)
         return hits if threshold is None else (hits, hits.first_exit(threshold))
+
+    # -- timestamps: when each token (and word) of a transcript was said, at any exit ------------------------------------------
+    @torch.no_grad()
+    def timestamps(self, model, spec: Tensor, valid_len: Tensor, hyps, exits=None, pieces: Optional[Sequence[str]] = None,
+                   frame_seconds: Optional[float] = None, blank: int = 0) -> Timestamps:
+        """One encoder pass (the log-probs of all exits, no taps) and ONE ``ctc_forced_align`` call that aligns the transcript of
+        every utterance against the CTC emission of an exit, over the encoder's own frame counts.  ``hyps[b]``: the tokens of
+        utterance b as any ``decode_batch*``, ``ctc_cuda_predict`` or ``greedy_decode`` call returns them (a list of ids, a tensor, a
+        hypothesis with ``.tokens``, or a list of those, whose first is taken); the SOS, EOS and PAD ids of ``args`` are removed, a
+        ``blank`` in a row is refused.  ``exits``: None -- the last exit --, one 0-based exit per utterance, or ``"all"``: every
+        exit, and the results are nested ``[E][B]`` instead of ``[B]``.  Returns ``Timestamps(tokens, words, alignment)``: the
+        ``TokenSpan`` list of every utterance in seconds (``frame_seconds``; None: 4 * args.hop_length / args.sample_rate, 0.04
+        without those; the stem's receptive-field offset is not corrected, see ``Alignment.spans``), the ``WordSpan`` lists where
+        ``pieces`` (the vocabulary's pieces: a piece beginning with U+2581 opens a word) is given, else None, and the ``Alignment``
+        itself, row e * B + b for ``"all"`` and row b otherwise.  An utterance whose transcript does not fit its frames has
+        status 1 there and empty lists here."""
+        valid_len = valid_len.reshape(-1)
+        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
+        E, B = int(logp.size(0)), int(logp.size(1))
+        if len(hyps) != B:
+            raise ValueError(f"timestamps: {B} utterances, {len(hyps)} hypotheses")
+        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
+        rows = transcript_rows(hyps, drop, int(blank))
+        if isinstance(exits, str):
+            if exits != "all":
+                raise ValueError(f"timestamps: exits must be None, one exit per utterance or 'all', got {exits!r}")
+            pairs = [(e, b) for e in range(E) for b in range(B)]
+        else:
+            of = [E - 1] * B if exits is None else [int(e) for e in (exits.tolist() if torch.is_tensor(exits) else exits)]
+            if len(of) != B or any(not 0 <= e < E for e in of):
+                raise ValueError(f"timestamps: exits must hold one exit of 0 .. {E - 1} per utterance ({B})")
+            pairs = [(e, b) for b, e in enumerate(of)]
+        S = max(1, max(len(r) for r in rows))
+        tokens = torch.zeros((len(pairs), S), dtype=torch.int32)
+        for h, (_, b) in enumerate(pairs):
+            tokens[h, :len(rows[b])] = torch.tensor(rows[b], dtype=torch.int32)
+        tok_len = torch.tensor([len(rows[b]) for _, b in pairs], dtype=torch.int32)
+        em_index = torch.tensor([e * B + b for e, b in pairs], dtype=torch.int32)
+        al = ctc_forced_align(logp, tokens, tok_len, em_index, encoder_lengths(valid_len.to(logp.device), logp.size(2)), blank=int(blank))
+        if frame_seconds is None:
+            hop, rate = getattr(self.args, "hop_length", None), getattr(self.args, "sample_rate", None)
+            frame_seconds = 4.0 * hop / rate if hop and rate else FRAME_SECONDS
+        host = Alignment(*(t.cpu() for t in (al.tok_start, al.tok_end, al.tok_score, al.frame_token, al.path_score, al.status)),
+                         tokens=al.tokens.cpu(), tok_len=al.tok_len.cpu())  # one copy each, not one per span
+        tok = [host.spans(h, frame_seconds) for h in range(len(pairs))]
+        words = None if pieces is None else [word_spans(sp, starts_word_from_pieces(pieces)) for sp in tok]
+        if isinstance(exits, str):
+            tok = [tok[e * B:(e + 1) * B] for e in range(E)]
+            words = None if words is None else [words[e * B:(e + 1) * B] for e in range(E)]
+        return Timestamps(tok, words, al)
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

@@ -278,6 +278,8 @@ PROTOTYPES = {
     "eec_lm_fusion_step": [VOID, z, i, i, i, i, i, i, I64, I64, F32, F32, VOID, z, f, f, i, i, i, i, STREAM],
     "eec_keyword_search_workspace_bytes": (z, [i, i]),
     "eec_keyword_search": [F32, i, i, i, I32, I32, I32, i, i, i, F32, I32, I32, F32, I32, VOID, z, STREAM],
+    "eec_ctc_forced_align_workspace_bytes": (z, [i, i, i]),
+    "eec_ctc_forced_align": [F32, i, i, i, I32, I32, I32, I32, i, i, i, I32, I32, F32, I32, F32, I32, VOID, z, STREAM],
 }
 EXPORTS = list(PROTOTYPES)
 KERNEL_CLASSES = ["stem", "ffn", "qkv", "attn", "proj_glu", "proj", "dw_pw2", "head", "chain"]

@@ -1585,6 +1585,52 @@ int eec_keyword_search(const float* logp, int n_em, int Tq, int V, const int32_t
                        int K, int tok_stride, int blank, float* score, int32_t* start, int32_t* end, float* trace_score,
                        int32_t* trace_start, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC forced alignment, standard topology (csrc/ctc_forced_align.hip) -----------------------------------------------------------------
+ * "When was each token said, for how long, and how surely": the Viterbi path of a token row through the real CTC topology of one
+ * emission -- 2N + 1 states, optional blanks, a blank forced between equal neighbours -- and the spans and scores read off it.  Max
+ * over paths only.  eec_ctc_align above is the reference's trellis (one frame per token, kept quirk for quirk) and stays what it is;
+ * the reference has nothing like this entry: an addition, not a parity item.  tests/forced_align_cases.py restates everything below in
+ * scalar fp32 and checks it against a brute force over all frame labellings.
+ *
+ * Inputs, per hypothesis h.  x = logp[em_index[h]] ([T', V] fp32, log-probs or logits), T = clamp(em_len[em_index[h]], 0, T') (em_len
+ * NULL: T'), y the N = tok_len[h] labels of tokens[h].  States s = 0 .. 2N: lab(s) = blank for even s, y[(s-1)/2] for odd s.
+ * Recursion.  a[0][0] = x[0][blank], a[0][1] = x[0][y_0], all others -inf.  For t >= 1 the candidates of state s are, in this order:
+ *   stay a[t-1][s];  step a[t-1][s-1] for s >= 1;  skip a[t-1][s-2] for odd s >= 3 with y[(s-1)/2] != y[(s-3)/2].
+ * best starts as stay and is replaced only by a strictly greater (>) later candidate, so ties go stay, then step, then skip.  d[t][s]
+ * in {0, 1, 2} is the move taken and a[t][s] = best + x[t][lab(s)], one fp32 add.  -inf is an ordinary value, and a decision is only
+ * ever one of the moves the state has.
+ * End and backtrack.  s_end = 2N if a[T-1][2N] > a[T-1][2N-1], else 2N - 1;  path_score = a[T-1][s_end].  s = s_end; for t = T-1 down
+ * to 1: state[t] = s, s -= d[t][s]; then state[0] = s.  The walk is exactly T - 1 steps, never loops on data and never leaves
+ * [0, 2N].
+ * Status.  0 iff path_score > -inf, path_score is not NaN and state[0] <= 1.  1 (not alignable) for N = 0; for T < N + R, R the
+ * number of adjacent equal pairs of y; for a bad row -- N > tok_stride, a token outside [0, V) or equal to blank, an em_index outside
+ * [0, n_em) --; and for a NaN in the valid frames that leaves the walk short.  None of these values is ever used as an address; a
+ * status-1 row gets the fill values.
+ * Outputs.  frame_token[t]: j at a frame in state 2j + 1, -1 at a blank frame, -2 for t >= T and in status-1 rows.  Per token j < N:
+ * tok_start[j] the first frame in state 2j + 1, tok_end[j] the last such frame plus 1, tok_score[j] the sum of x[t][y_j] over those
+ * frames in frame order, fp32, beginning with the first frame's value; -1, -1, -inf for j >= N and in status-1 rows.
+ * Frames at or past a length are never read: a NaN there reaches nothing.  Only fp32 adds and compares occur, so the kernel, the
+ * package's host path and a scalar restatement agree bit for bit.
+ *
+ *   logp [n_em, T', V] fp32, from any 4-byte boundary; em_len [n_em] int32, or NULL = T' for all
+ *   tokens [n_hyp, tok_stride] int32, tok_len [n_hyp] int32 (N); em_index [n_hyp] int32, or NULL = the row's own index h
+ *   tok_start, tok_end int32 and tok_score fp32: [n_hyp, tok_stride];  frame_token [n_hyp, T'] int32;  path_score fp32 and status
+ *   int32: [n_hyp]
+ *   workspace: eec_ctc_forced_align_workspace_bytes(n_hyp, T', tok_stride) bytes, 256-byte aligned: the decisions, two bits per
+ *   (frame, state), n_hyp * ceil(T' * C / 16) * 256 bytes with C = 1, 2, 4, 8 states per lane for tok_stride <= 31, 63, 127, 255.
+ *   The size is a multiple of 8, does not decrease in any argument and is 0 when an argument is <= 0.
+ * All checks come before any device work, in the codes and order of eec_ctc_align.  EEC_ERR_BAD_ARG: a null required pointer, blank
+ * outside [0, V), tok_stride < 1, n_hyp < 0, T' < 1, n_em < 1; n_hyp == 0 is a successful no-op.  EEC_ERR_UNSUPPORTED: tok_stride >
+ * 255, V < 2.  EEC_ERR_WORKSPACE: a null, short or misaligned workspace.
+ * One launch (one wavefront per hypothesis, four to a workgroup: rows that follow each other and share an emission share its cache
+ * lines), no atomics, nothing read back, no allocation, no synchronisation; graph-capturable; two runs and any split of the
+ * hypotheses return the same bits. */
+size_t eec_ctc_forced_align_workspace_bytes(int n_hyp, int Tq, int tok_stride);
+int eec_ctc_forced_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
+                         const int32_t* em_index, int n_hyp, int tok_stride, int blank, int32_t* tok_start, int32_t* tok_end,
+                         float* tok_score, int32_t* frame_token, float* path_score, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
