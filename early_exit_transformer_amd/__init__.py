@@ -8,9 +8,14 @@ _LM_FUSION = ("TokenLM", "LMFusionSession")  # shallow fusion with a token-level
 _KEYWORD = ("KeywordSet", "KeywordHits", "keyword_search")  # keyword spotting on CTC emissions (keyword.py), likewise
 # word and token timestamps: CTC forced alignment in the standard topology (alignment.py), likewise
 _ALIGNMENT = ("Alignment", "TokenSpan", "WordSpan", "ctc_forced_align", "word_spans", "starts_word_from_pieces")
+# token posteriors and soft timestamps: CTC forward-backward in the standard topology (posterior.py), likewise
+_POSTERIOR = ("Posteriors", "SoftSpan", "SoftWordSpan", "ctc_posteriors", "soft_word_spans", "nbest_posteriors")
 
 
 def __getattr__(name):
+    if name in _POSTERIOR:
+        from . import posterior
+        return getattr(posterior, name)
     if name in _ALIGNMENT:
         from . import alignment
         return getattr(alignment, name)

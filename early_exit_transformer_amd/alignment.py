@@ -157,6 +157,24 @@ def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: n
     return state, score, ok & (s <= 1)
 
 
+def host_row_checks(shape, lens: Optional[np.ndarray], tokens: np.ndarray, tok_len: np.ndarray, em_index: Optional[np.ndarray],
+                    blank: int):
+    """The header's row checks on the host: ``(ok [H] bool, N [H], ei [H], inside [H, S] bool, tk [H, S] int64, T_all [n_em])``."""
+    n_em, Tq, V = shape
+    H, S = tokens.shape
+    N = tok_len.astype(np.int64)
+    ei = np.arange(H, dtype=np.int64) if em_index is None else em_index.astype(np.int64)
+    ok = (ei >= 0) & (ei < n_em) & (N >= 1) & (N <= S)
+    inside = np.arange(S)[None, :] < np.where(ok, N, 0)[:, None]
+    tk = tokens.astype(np.int64)
+    ok &= ~(inside & ((tk < 0) | (tk >= V) | (tk == blank))).any(axis=1)
+    R = (inside[:, 1:] & (tk[:, 1:] == tk[:, :-1])).sum(axis=1)
+    ei_c = np.clip(ei, 0, n_em - 1)
+    T_all = np.full(n_em, Tq, dtype=np.int64) if lens is None else np.clip(lens.astype(np.int64), 0, Tq)
+    ok &= T_all[ei_c] >= N + R
+    return ok, N, ei, inside, tk, T_all
+
+
 def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, tok_len: np.ndarray, em_index: Optional[np.ndarray],
                 blank: int):
     n_em, Tq, V = x.shape
@@ -168,16 +186,7 @@ def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, t
     frame_token = np.full((H, Tq), -2, dtype=np.int32)
     path_score = np.full((H,), NEG, dtype=np.float32)
     status = np.ones((H,), dtype=np.int32)
-    N = tok_len.astype(np.int64)
-    ei = np.arange(H, dtype=np.int64) if em_index is None else em_index.astype(np.int64)
-    ok = (ei >= 0) & (ei < n_em) & (N >= 1) & (N <= S)
-    inside = np.arange(S)[None, :] < np.where(ok, N, 0)[:, None]
-    tk = tokens.astype(np.int64)
-    ok &= ~(inside & ((tk < 0) | (tk >= V) | (tk == blank))).any(axis=1)
-    R = (inside[:, 1:] & (tk[:, 1:] == tk[:, :-1])).sum(axis=1)
-    ei_c = np.clip(ei, 0, n_em - 1)
-    T_all = np.full(n_em, Tq, dtype=np.int64) if lens is None else np.clip(lens.astype(np.int64), 0, Tq)
-    ok &= T_all[ei_c] >= N + R
+    ok, N, ei, inside, tk, T_all = host_row_checks(x.shape, lens, tokens, tok_len, em_index, blank)
     keep = np.nonzero(ok)[0]
     step = max(1, (1 << 26) // max(1, Tq * (2 * S + 1)))  # bounds the [T, K, 2S + 1] decisions
     for c0 in range(0, keep.size, step):
@@ -231,6 +240,46 @@ def _device_align(logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index,
     return out
 
 
+def row_arguments(name: str, logp: Tensor, tokens, tok_len, em_index, em_len, blank: int):
+    """The arguments ``ctc_forced_align`` and ``ctc_posteriors`` share, checked and in the kernels' form: ``(flat [n_em, T', V], lens
+    int32 [n_em] or None, tokens int32 [H, S], tok_len int32 [H], em_index int32 [H] or None, blank)``, all on ``logp``'s device."""
+    if logp.dim() not in (3, 4):
+        raise ValueError(f"{name}: logp must be [n_em, T', V] or [E, B, T', V], got {tuple(logp.shape)}")
+    if logp.dtype != torch.float32:
+        raise ValueError(f"{name}: logp must be fp32, got {logp.dtype}")
+    lead = tuple(logp.shape[:-2])
+    Tq, V = int(logp.size(-2)), int(logp.size(-1))
+    n = int(np.prod(lead))
+    blank = int(blank)
+    if n < 1 or Tq < 1:
+        raise ValueError(f"{name}: no emissions")
+    if V < 2 or not 0 <= blank < V:
+        raise ValueError(f"{name}: needs V >= 2 and blank in [0, V), got {V} and {blank}")
+    tokens = torch.as_tensor(tokens)
+    if tokens.dim() != 2 or tokens.dtype.is_floating_point or tokens.dtype == torch.bool:
+        raise ValueError(f"{name}: tokens must be an integer tensor [H, S], got {tokens.dtype} {tuple(tokens.shape)}")
+    H, S = tokens.shape
+    if not 1 <= S <= MAX_TOKENS:
+        raise ValueError(f"{name}: a row has 1 .. {MAX_TOKENS} tokens, got S = {S}")
+    dev = logp.device
+    flat = logp.reshape(n, Tq, V)
+    if not flat.is_contiguous():
+        flat = flat.contiguous()
+    # an id that int32 cannot hold is outside every vocabulary: it stays outside after the narrowing
+    tokens = tokens.to(torch.int64).clamp(-1, 2 ** 31 - 1).to(device=dev, dtype=torch.int32).contiguous()
+    tok_len = torch.full((H,), S, dtype=torch.int32, device=dev) if tok_len is None else \
+        _frame_counts(name, "tok_len", tok_len, H, dev)
+    em_index = _frame_counts(name, "em_index", em_index, H, dev)
+    if em_index is None and H > n:
+        raise ValueError(f"{name}: {H} rows, {n} emissions and no em_index")
+    if em_len is not None:
+        em_len = torch.as_tensor(em_len)
+        if len(lead) == 2 and em_len.numel() == lead[1] and lead[0] != 1:
+            em_len = em_len.reshape(1, lead[1]).expand(lead[0], lead[1]).reshape(-1)
+    lens = _frame_counts(name, "em_len", em_len, n, dev)
+    return flat, lens, tokens, tok_len, em_index, blank
+
+
 def ctc_forced_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = None, em_index: Optional[Tensor] = None,
                      em_len: Optional[Tensor] = None, blank: int = 0, max_workspace_bytes: int = 2 << 30) -> Alignment:
     """Viterbi forced alignment of H token rows in the standard CTC topology (the statement: include/eec.h).  ``logp``
@@ -242,40 +291,7 @@ def ctc_forced_align(logp: Tensor, tokens: Tensor, tok_len: Optional[Tensor] = N
     has status 1 and the fill values.  Device tensors: one launch on the current stream, nothing read back, graph-capturable; a
     call whose decisions (``eec_ctc_forced_align_workspace_bytes``) exceed ``max_workspace_bytes`` is split over rows, which changes
     no bit.  CPU tensors: a NumPy host path with the same bits."""
-    if logp.dim() not in (3, 4):
-        raise ValueError(f"ctc_forced_align: logp must be [n_em, T', V] or [E, B, T', V], got {tuple(logp.shape)}")
-    if logp.dtype != torch.float32:
-        raise ValueError(f"ctc_forced_align: logp must be fp32, got {logp.dtype}")
-    lead = tuple(logp.shape[:-2])
-    Tq, V = int(logp.size(-2)), int(logp.size(-1))
-    n = int(np.prod(lead))
-    blank = int(blank)
-    if n < 1 or Tq < 1:
-        raise ValueError("ctc_forced_align: no emissions")
-    if V < 2 or not 0 <= blank < V:
-        raise ValueError(f"ctc_forced_align: needs V >= 2 and blank in [0, V), got {V} and {blank}")
-    tokens = torch.as_tensor(tokens)
-    if tokens.dim() != 2 or tokens.dtype.is_floating_point or tokens.dtype == torch.bool:
-        raise ValueError(f"ctc_forced_align: tokens must be an integer tensor [H, S], got {tokens.dtype} {tuple(tokens.shape)}")
-    H, S = tokens.shape
-    if not 1 <= S <= MAX_TOKENS:
-        raise ValueError(f"ctc_forced_align: a row has 1 .. {MAX_TOKENS} tokens, got S = {S}")
-    dev = logp.device
-    flat = logp.reshape(n, Tq, V)
-    if not flat.is_contiguous():
-        flat = flat.contiguous()
-    # an id that int32 cannot hold is outside every vocabulary: it stays outside after the narrowing
-    tokens = tokens.to(torch.int64).clamp(-1, 2 ** 31 - 1).to(device=dev, dtype=torch.int32).contiguous()
-    tok_len = torch.full((H,), S, dtype=torch.int32, device=dev) if tok_len is None else \
-        _frame_counts("ctc_forced_align", "tok_len", tok_len, H, dev)
-    em_index = _frame_counts("ctc_forced_align", "em_index", em_index, H, dev)
-    if em_index is None and H > n:
-        raise ValueError(f"ctc_forced_align: {H} rows, {n} emissions and no em_index")
-    if em_len is not None:
-        em_len = torch.as_tensor(em_len)
-        if len(lead) == 2 and em_len.numel() == lead[1] and lead[0] != 1:
-            em_len = em_len.reshape(1, lead[1]).expand(lead[0], lead[1]).reshape(-1)
-    lens = _frame_counts("ctc_forced_align", "em_len", em_len, n, dev)
+    flat, lens, tokens, tok_len, em_index, blank = row_arguments("ctc_forced_align", logp, tokens, tok_len, em_index, em_len, blank)
     if logp.is_cuda:
         out = _device_align(flat, lens, tokens, tok_len, em_index, blank, max_workspace_bytes)
     else:

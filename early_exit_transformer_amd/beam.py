@@ -60,6 +60,7 @@ from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
 from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
+from .posterior import TOKEN_FIELDS, Posteriors, ctc_posteriors, soft_word_spans
 
 
 class GreedyCTCDecoder(torch.nn.Module):
@@ -122,6 +123,14 @@ class Timestamps(NamedTuple):
     tokens: list
     words: Optional[list]
     alignment: Alignment
+
+
+class Confidences(NamedTuple):
+    """What ``BeamInference.confidences`` returns: per utterance ([B], or [E][B] for ``exits="all"``) the ``SoftSpan`` list and --
+    with ``pieces`` -- the ``SoftWordSpan`` list (else ``words`` is None), and the ``Posteriors`` they were read off."""
+    tokens: list
+    words: Optional[list]
+    posteriors: Posteriors
 
 
 class FusedRescoredList(RescoredList):
@@ -1019,6 +1028,52 @@ class BeamInference:
             tok = [tok[e * B:(e + 1) * B] for e in range(E)]
             words = None if words is None else [words[e * B:(e + 1) * B] for e in range(E)]
         return Timestamps(tok, words, al)
+
+    @torch.no_grad()
+    def confidences(self, model, spec: Tensor, valid_len: Tensor, hyps, exits=None, pieces: Optional[Sequence[str]] = None,
+                    frame_seconds: Optional[float] = None, blank: int = 0) -> Confidences:
+        """``timestamps`` summed over every alignment instead of read off the best one: one encoder pass and ONE ``ctc_posteriors``
+        call over the transcripts, the CTC emission of an exit and the encoder's own frame counts.  ``hyps``, ``exits`` (None -- the
+        last exit --, one 0-based exit per utterance, or ``"all"``: every exit, results nested ``[E][B]``), ``pieces`` and
+        ``frame_seconds`` are ``timestamps``'.  Returns ``Confidences(tokens, words, posteriors)``: the ``SoftSpan`` list of every
+        utterance (expected boundaries with their standard deviations, in seconds; expected frames; confidence), the
+        ``SoftWordSpan`` lists where ``pieces`` is given, else None, and the ``Posteriors`` itself, row e * B + b for ``"all"`` and
+        row b otherwise -- ``nbest_posteriors(posteriors.row_logp, ...)`` compares an utterance's exits or hypotheses.  An utterance
+        whose transcript does not fit its frames has status 1 there and empty lists here."""
+        valid_len = valid_len.reshape(-1)
+        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
+        E, B = int(logp.size(0)), int(logp.size(1))
+        if len(hyps) != B:
+            raise ValueError(f"confidences: {B} utterances, {len(hyps)} hypotheses")
+        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
+        rows = transcript_rows(hyps, drop, int(blank))
+        if isinstance(exits, str):
+            if exits != "all":
+                raise ValueError(f"confidences: exits must be None, one exit per utterance or 'all', got {exits!r}")
+            pairs = [(e, b) for e in range(E) for b in range(B)]
+        else:
+            of = [E - 1] * B if exits is None else [int(e) for e in (exits.tolist() if torch.is_tensor(exits) else exits)]
+            if len(of) != B or any(not 0 <= e < E for e in of):
+                raise ValueError(f"confidences: exits must hold one exit of 0 .. {E - 1} per utterance ({B})")
+            pairs = [(e, b) for b, e in enumerate(of)]
+        S = max(1, max(len(r) for r in rows))
+        tokens = torch.zeros((len(pairs), S), dtype=torch.int32)
+        for h, (_, b) in enumerate(pairs):
+            tokens[h, :len(rows[b])] = torch.tensor(rows[b], dtype=torch.int32)
+        tok_len = torch.tensor([len(rows[b]) for _, b in pairs], dtype=torch.int32)
+        em_index = torch.tensor([e * B + b for e, b in pairs], dtype=torch.int32)
+        po = ctc_posteriors(logp, tokens, tok_len, em_index, encoder_lengths(valid_len.to(logp.device), logp.size(2)), blank=int(blank))
+        if frame_seconds is None:
+            hop, rate = getattr(self.args, "hop_length", None), getattr(self.args, "sample_rate", None)
+            frame_seconds = 4.0 * hop / rate if hop and rate else FRAME_SECONDS
+        host = Posteriors(po.row_logp.cpu(), *(getattr(po, n).cpu() for n in TOKEN_FIELDS), None, po.status.cpu(),
+                          tokens=po.tokens.cpu(), tok_len=po.tok_len.cpu())  # one copy each, not one per span
+        tok = [host.spans(h, frame_seconds) for h in range(len(pairs))]
+        words = None if pieces is None else [soft_word_spans(sp, starts_word_from_pieces(pieces)) for sp in tok]
+        if isinstance(exits, str):
+            tok = [tok[e * B:(e + 1) * B] for e in range(E)]
+            words = None if words is None else [words[e * B:(e + 1) * B] for e in range(E)]
+        return Confidences(tok, words, po)
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

@@ -1631,6 +1631,75 @@ int eec_ctc_forced_align(const float* logp, int n_em, int Tq, int V, const int32
                          float* tok_score, int32_t* frame_token, float* path_score, int32_t* status, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- CTC posteriors, standard topology (csrc/ctc_posterior.hip) ---------------------------------------------------------------------------
+ * "How sure is the model of this token, summed over every way of aligning it, and where does it begin and end in expectation": the
+ * forward-backward occupancy of the lattice eec_ctc_forced_align walks -- the same 2N + 1 states, the same inputs, the same row
+ * checks -- and the per-token sums read off it.  Sum over paths where eec_ctc_forced_align takes the best path; per state where
+ * eec_ctc_hyp_logp keeps only the total.  The reference has nothing like this entry: an addition, not a parity item.
+ * tests/posterior_cases.py restates everything below in fp64 and checks it against a brute force over all frame labellings.
+ *
+ * Inputs, per row h: exactly eec_ctc_forced_align's.  x = logp[em_index[h]] ([T', V] fp32 log-probs), T = clamp(em_len[em_index[h]],
+ * 0, T') (em_len NULL: T'), y the N = tok_len[h] labels of tokens[h].  States s = 0 .. 2N: lab(s) = blank for even s, y[(s-1)/2] for
+ * odd s; skip(s) holds for odd s >= 3 with y[(s-1)/2] != y[(s-3)/2].  x_t(v) = x[t][v].
+ * Recursions, fp32, in log space.  log_add(a, b) is the sequence stated under eec_ctc_log_add; log_add(a, b, c) = log_add(log_add(a,
+ * b), c), and a candidate a state does not have (s - 1 of state 0, a skip that does not hold, a state past 2N) is -inf, for which
+ * log_add returns its other argument unchanged.  The fold order is stay, step, skip.  -inf is an ordinary value; there is no range
+ * limit and no scaling.
+ *   alpha_0(0) = x_0(blank), alpha_0(1) = x_0(y_0), every other state -inf;
+ *   alpha_t(s) = log_add(alpha_{t-1}(s), alpha_{t-1}(s-1), [skip(s)] alpha_{t-1}(s-2)) + x_t(lab(s))            one add
+ *   beta_{T-1}(2N) = beta_{T-1}(2N-1) = 0, every other state -inf;  c_t(s) = x_t(lab(s)) + beta_t(s)             one add
+ *   beta_t(s) = log_add(c_{t+1}(s), c_{t+1}(s+1), [skip(s+2)] c_{t+1}(s+2))      (beta_t does not hold frame t's own emission)
+ *   ll = log_add(alpha_{T-1}(2N), alpha_{T-1}(2N-1))
+ *   gamma_t(s) = exp((alpha_t(s) + beta_t(s)) - ll)
+ * and for token j, s = 2j + 1, the posterior of t being its first and its last frame, written without cancellation:
+ *   f_t(j) = exp(((log_add(alpha_{t-1}(s-1), [skip(s)] alpha_{t-1}(s-2)) + x_t(y_j)) + beta_t(s)) - ll) for t >= 1;
+ *   f_0(0) = gamma_0(1), f_0(j) = 0 for j >= 1
+ *   l_t(j) = exp((alpha_t(s) + log_add(c_{t+1}(s+1), [skip(s+2)] c_{t+1}(s+2))) - ll) for t < T - 1;  l_{T-1}(j) = gamma_{T-1}(s)
+ * Additions and subtractions are single fp32 operations in the written order; exp is the fp32 library exponential (it is not one of
+ * the exactly stated operations: the device's results are its own, reproducible bit for bit on the device, and other
+ * implementations of this statement agree with it within the bound below).
+ * Per-token sums, each accumulated in fp64 over t = T-1 down to 0 -- the order of the backward sweep, which is where the terms come
+ * to exist -- from the fp32 terms above and rounded ONCE to fp32:
+ *   tok_frames[j] = sum_t gamma_t(s)                      the expected number of frames the token holds
+ *   tok_score[j]  = sum_t gamma_t(s) * x_t(y_j)           (a frame with gamma_t(s) = 0 adds 0, whatever x_t(y_j) is);
+ *                                                         exp(tok_score / tok_frames) is the token's confidence
+ *   tok_start[j]  = sum_t t f_t(j)                        tok_start_var[j] = sum_t t^2 f_t(j) - (sum_t t f_t(j))^2
+ *   tok_end[j]    = sum_t (t + 1) l_t(j)                  tok_end_var[j]   = sum_t (t+1)^2 l_t(j) - (sum_t (t+1) l_t(j))^2
+ * with the subtraction and the square in fp64 on the unrounded sums.  A token's frames are contiguous on every path, so in exact
+ * arithmetic sum_t f_t(j) = sum_t l_t(j) = 1, tok_end - tok_start = tok_frames and the variances are >= 0; in fp32 these hold within
+ * the bound below and a variance near 0 may come out slightly negative.
+ * row_logp[h] = ll.  gamma (optional) [n_hyp, T', tok_stride] fp32: gamma[h][t][j] = gamma_t(2j + 1); 0 for j >= N and for t >= T.
+ * The blank's share of a frame is one minus the row's sum.
+ * Status.  1: the row fails eec_ctc_forced_align's row checks -- N = 0; T < N + R, R the number of adjacent equal pairs of y; N >
+ * tok_stride, a token outside [0, V) or equal to blank, an em_index outside [0, n_em) --; none of these values is ever used as an
+ * address.  2: the row passes them and ll is not finite (-inf emissions on every path; a NaN that reaches ll.  log_add drops a NaN
+ * argument in favour of the other one, so a NaN emission inside the length gives status 0 or 2 and unspecified values, never an
+ * address out of range).  0 otherwise.  Status 1 and 2 write the fill values: row_logp = -inf, the six token outputs -1.0 over the
+ * whole tok_stride, the row's gamma 0.  A status-0 row has -1.0 in the six token outputs for j >= N.
+ * Frames at or past a length are never read: a NaN there reaches nothing.
+ * Accuracy.  With bound(T, M) = T * (2^-22 * M + 4e-7) the model every log_add lattice of this library is held to (M the largest
+ * finite magnitude of alpha and beta), |row_logp - ll| <= bound, every posterior is within a factor exp(+-3 bound) * (1 +- 2^-22)
+ * of its exact value, and so every sum above is within (expm1(3 bound) + 2^-22) times the sum of the absolute values of its terms,
+ * plus its one rounding.  tests/test_gpu_posterior.py holds the device to that against the fp64 restatement.
+ *
+ *   logp [n_em, T', V] fp32, from any 4-byte boundary; em_len [n_em] int32, or NULL = T' for all
+ *   tokens [n_hyp, tok_stride] int32, tok_len [n_hyp] int32 (N); em_index [n_hyp] int32, or NULL = the row's own index h
+ *   row_logp fp32 and status int32: [n_hyp];  tok_frames, tok_score, tok_start, tok_end, tok_start_var, tok_end_var fp32:
+ *   [n_hyp, tok_stride];  gamma fp32 [n_hyp, T', tok_stride], or NULL: not wanted
+ *   workspace: eec_ctc_posteriors_workspace_bytes(n_hyp, T', tok_stride) bytes, 256-byte aligned: alpha, one 256-byte line per
+ *   (frame, slot of the state strip), n_hyp * T' * C * 256 bytes with C = 1, 2, 4, 8 states per lane for tok_stride <= 31, 63, 127,
+ *   255.  The size is a multiple of 8, does not decrease in any argument and is 0 when an argument is <= 0.
+ * All checks come before any device work, in the codes and order of eec_ctc_forced_align.  EEC_ERR_BAD_ARG: a null required pointer,
+ * blank outside [0, V), tok_stride < 1, n_hyp < 0, T' < 1, n_em < 1; n_hyp == 0 is a successful no-op.  EEC_ERR_UNSUPPORTED:
+ * tok_stride > 255, V < 2.  EEC_ERR_WORKSPACE: a null, short or misaligned workspace.  Errors through eec_last_error().
+ * One launch (one wavefront per row, four to a workgroup), no atomics, nothing read back, no allocation, no synchronisation;
+ * graph-capturable; two runs and any split of the rows return the same bits. */
+size_t eec_ctc_posteriors_workspace_bytes(int n_hyp, int Tq, int tok_stride);
+int eec_ctc_posteriors(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
+                       const int32_t* em_index, int n_hyp, int tok_stride, int blank, float* row_logp, float* tok_frames, float* tok_score,
+                       float* tok_start, float* tok_end, float* tok_start_var, float* tok_end_var, float* gamma, int32_t* status,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
