@@ -154,7 +154,7 @@ def masked_decoder_logits(model: nn.Module, trg: Tensor, enc: Tensor, idx: int, 
         x = x + a * masks(site + 1, a.shape)
         c = explicit_attention(layer.multihead_attn, layer.norm2(x), enc, prob_mul=masks(site + 2, (B * H, S, Tq)))
         x = x + c * masks(site + 3, c.shape)
-        h = torch.relu(layer.linear1(layer.norm3(x)))
+        h = layer.activation(layer.linear1(layer.norm3(x)))  # relu (nn.TransformerDecoderLayer's default), or a caller's stand-in for it
         h = h * masks(site + 4, h.shape)
         y = layer.linear2(h)
         x = x + y * masks(site + 5, y.shape)
