@@ -76,24 +76,29 @@ def starts_word_from_pieces(pieces: Sequence[str], marker: str = "\u2581") -> np
     return np.asarray([str(p).startswith(marker) for p in pieces], dtype=bool)
 
 
-def word_spans(spans: Sequence[TokenSpan], starts_word: Union[Sequence[bool], Callable[[int], bool]]) -> List[WordSpan]:
-    """Token spans merged into words, on the host: a token for which ``starts_word`` (a bool array over the vocabulary, or a callable
-    on the id) holds opens a word, as does the first token.  A word runs from its first token's start to its last token's end; its
-    confidence is the geometric mean over all of its label frames, exp(sum of scores / sum of frames) in fp64."""
+def group_words(spans, starts_word: Union[Sequence[bool], Callable[[int], bool]]) -> List[list]:
+    """``spans`` (anything with a ``.token``) cut into words: a token for which ``starts_word`` holds opens one, as does the first."""
     opens = starts_word if callable(starts_word) else (lambda t, table=np.asarray(starts_word, dtype=bool): bool(table[t]))
-    groups: List[List[TokenSpan]] = []
+    groups: List[list] = []
     for sp in spans:
         if not groups or opens(sp.token):
             groups.append([])
         groups[-1].append(sp)
+    return groups
+
+
+def word_spans(spans: Sequence[TokenSpan], starts_word: Union[Sequence[bool], Callable[[int], bool]]) -> List[WordSpan]:
+    """Token spans merged into words, on the host: a token for which ``starts_word`` (a bool array over the vocabulary, or a callable
+    on the id) holds opens a word, as does the first token.  A word runs from its first token's start to its last token's end; its
+    confidence is the geometric mean over all of its label frames, exp(sum of scores / sum of frames) in fp64."""
     return [WordSpan(tuple(sp.token for sp in g), g[0].start, g[-1].end,
-                     math.exp(math.fsum(sp.score for sp in g) / sum(sp.frames for sp in g))) for g in groups]
+                     math.exp(math.fsum(sp.score for sp in g) / sum(sp.frames for sp in g))) for g in group_words(spans, starts_word)]
 
 
-def transcript_rows(hyps, drop=(), blank: int = 0) -> List[List[int]]:
+def transcript_rows(hyps, drop=(), blank: int = 0, name: str = "timestamps") -> List[List[int]]:
     """Decoder output as label rows: ``hyps[b]`` is a list of ids, a tensor, a hypothesis with ``.tokens``, or an n-best list of
     those, whose first is taken; the ids of ``drop`` (SOS, EOS, PAD) are removed.  A ``blank`` in a row is refused: it is no
-    label, and the alignment could only answer it with status 1."""
+    label, and the alignment could only answer it with status 1.  ``name``: the caller, for the message."""
     rows = []
     for b, hyp in enumerate(hyps):
         if isinstance(hyp, (list, tuple)) and hyp and not isinstance(hyp[0], (int, np.integer)) and not torch.is_tensor(hyp[0]):
@@ -102,9 +107,53 @@ def transcript_rows(hyps, drop=(), blank: int = 0) -> List[List[int]]:
         ids = [int(t) for t in (ids.reshape(-1).tolist() if torch.is_tensor(ids) else ids)]
         ids = [t for t in ids if t not in drop]
         if blank in ids:
-            raise ValueError(f"timestamps: the transcript of utterance {b} holds the blank ({blank})")
+            raise ValueError(f"{name}: the transcript of utterance {b} holds the blank ({blank})")
         rows.append(ids)
     return rows
+
+
+def exit_rows(name: str, hyps, exits, E: int, B: int, drop=(), blank: int = 0):
+    """The rows ``BeamInference.timestamps`` / ``.confidences`` (``name``, for the messages) hand to the lattice kernels: the
+    transcripts of ``hyps`` (``transcript_rows``) paired with exits -- ``exits`` None: the last of the E exits for each of the B
+    utterances; one 0-based exit per utterance; ``"all"``: every exit, exit-major.  Returns ``(pairs [(e, b)], tokens int32 [H, S]
+    zero-padded to S = max(1, longest), tok_len int32 [H], em_index int32 [H] = e * B + b)``."""
+    if len(hyps) != B:
+        raise ValueError(f"{name}: {B} utterances, {len(hyps)} hypotheses")
+    rows = transcript_rows(hyps, drop, blank, name)
+    if isinstance(exits, str):
+        if exits != "all":
+            raise ValueError(f"{name}: exits must be None, one exit per utterance or 'all', got {exits!r}")
+        pairs = [(e, b) for e in range(E) for b in range(B)]
+    else:
+        of = [E - 1] * B if exits is None else [int(e) for e in (exits.tolist() if torch.is_tensor(exits) else exits)]
+        if len(of) != B or any(not 0 <= e < E for e in of):
+            raise ValueError(f"{name}: exits must hold one exit of 0 .. {E - 1} per utterance ({B})")
+        pairs = [(e, b) for b, e in enumerate(of)]
+    S = max(1, max(len(r) for r in rows))
+    tokens = torch.zeros((len(pairs), S), dtype=torch.int32)
+    for h, (_, b) in enumerate(pairs):
+        tokens[h, :len(rows[b])] = torch.tensor(rows[b], dtype=torch.int32)
+    tok_len = torch.tensor([len(rows[b]) for _, b in pairs], dtype=torch.int32)
+    em_index = torch.tensor([e * B + b for e, b in pairs], dtype=torch.int32)
+    return pairs, tokens, tok_len, em_index
+
+
+def host_lattice(y: np.ndarray, N: np.ndarray, blank: int):
+    """The lattice of K rows ``y`` [K, S] (blank past ``N`` [K]) over [K, 2S + 1] states: ``(lab int64 the label of every state --
+    the states past 2N compute on the blank and feed nothing --, skip bool: state s takes from s - 2, skipn bool: state s gives to
+    s + 2, valid bool: s <= 2N)``."""
+    K, S = y.shape
+    NS = 2 * S + 1
+    valid = np.arange(NS)[None, :] <= 2 * N[:, None]
+    lab = np.full((K, NS), blank, dtype=np.int64)
+    lab[:, 1::2] = y
+    skip = np.zeros((K, NS), dtype=bool)
+    if S > 1:
+        skip[:, 3::2] = y[:, 1:] != y[:, :-1]
+    skip &= valid  # skip is set on odd states only: s <= 2N is s <= 2N - 1 there
+    skipn = np.zeros((K, NS), dtype=bool)
+    skipn[:, :-2] = skip[:, 2:]
+    return lab, skip, skipn, valid
 
 
 def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: np.ndarray, blank: int):
@@ -115,14 +164,7 @@ def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: n
     Tq = x.shape[1]
     NS = 2 * S + 1
     NEG = np.float32(-np.inf)
-    s_idx = np.arange(NS)[None, :]
-    lab = np.full((K, NS), blank, dtype=np.int64)
-    lab[:, 1::2] = y
-    lab = np.where(s_idx <= 2 * N[:, None], lab, blank)  # states past 2N compute on the blank and feed nothing
-    skip = np.zeros((K, NS), dtype=bool)
-    if S > 1:
-        skip[:, 3::2] = y[:, 1:] != y[:, :-1]
-    skip &= s_idx <= 2 * N[:, None] - 1
+    lab, skip, _, _ = host_lattice(y, N, blank)
     rows = np.arange(K)
     a = np.full((K, NS), NEG, dtype=np.float32)
     a[:, 0] = x[ei, 0, blank]
@@ -214,29 +256,35 @@ def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, t
     return tok_start, tok_end, tok_score, frame_token, path_score, status
 
 
-def _device_align(logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, max_workspace_bytes: int):
+def launch_rows(entry: str, logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, outs, max_workspace_bytes: int):
+    """``entry`` (``eec_ctc_forced_align``, ``eec_ctc_posteriors``) over the H rows into ``outs``, the entry's outputs in its order
+    (tensors with a leading H; None where it takes a null).  A call whose workspace exceeds the bound is split over rows: a wave's
+    result depends on its own row alone."""
     dev = logp.device
     n_em, Tq, V = logp.shape
     H, S = tokens.shape
-    lib = capi.load()
-    out = (torch.empty((H, S), dtype=torch.int32, device=dev), torch.empty((H, S), dtype=torch.int32, device=dev),
-           torch.empty((H, S), dtype=torch.float32, device=dev), torch.empty((H, Tq), dtype=torch.int32, device=dev),
-           torch.empty((H,), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.int32, device=dev))
     if H == 0:
-        return out
-    # a call above the bound is split over hypotheses: a wave's result depends on its own row alone
-    per_row = max(1, lib.eec_ctc_forced_align_workspace_bytes(1, Tq, S))
-    Hc = max(1, min(H, int(max_workspace_bytes) // per_row))
+        return
+    size = getattr(capi.load(), entry + "_workspace_bytes")
+    Hc = max(1, min(H, int(max_workspace_bytes) // max(1, size(1, Tq, S))))
     if em_index is None and Hc < H:  # the rows of a later part are no longer their emissions' indices
         em_index = torch.arange(H, dtype=torch.int32, device=dev)
-    ws_bytes = lib.eec_ctc_forced_align_workspace_bytes(Hc, Tq, S)
+    ws_bytes = size(Hc, Tq, S)
     ws, ws_ptr = capi.aligned_ws(ws_bytes, dev)
     for h0 in range(0, H, Hc):
         h1 = min(H, h0 + Hc)
-        capi.launch("eec_ctc_forced_align", dev, logp, n_em, Tq, V, lens, tokens[h0:h1], tok_len[h0:h1],
-                    None if em_index is None else em_index[h0:h1], h1 - h0, S,
-                    blank, *(t[h0:h1] for t in out), ws_ptr, ws_bytes)
+        capi.launch(entry, dev, logp, n_em, Tq, V, lens, tokens[h0:h1], tok_len[h0:h1], None if em_index is None else em_index[h0:h1],
+                    h1 - h0, S, blank, *(None if t is None else t[h0:h1] for t in outs), ws_ptr, ws_bytes)
     del ws
+
+
+def _device_align(logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, max_workspace_bytes: int):
+    dev, Tq = logp.device, logp.size(1)
+    H, S = tokens.shape
+    out = (torch.empty((H, S), dtype=torch.int32, device=dev), torch.empty((H, S), dtype=torch.int32, device=dev),
+           torch.empty((H, S), dtype=torch.float32, device=dev), torch.empty((H, Tq), dtype=torch.int32, device=dev),
+           torch.empty((H,), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.int32, device=dev))
+    launch_rows("eec_ctc_forced_align", logp, lens, tokens, tok_len, em_index, blank, out, max_workspace_bytes)
     return out
 
 

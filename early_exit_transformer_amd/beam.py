@@ -54,7 +54,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .alignment import FRAME_SECONDS, Alignment, ctc_forced_align, starts_word_from_pieces, transcript_rows, word_spans
+from .alignment import FRAME_SECONDS, Alignment, ctc_forced_align, exit_rows, starts_word_from_pieces, word_spans
 from .context import ContextBiasSession, ContextGraph
 from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
@@ -980,6 +980,29 @@ class BeamInference:
         return hits if threshold is None else (hits, hits.first_exit(threshold))
 
     # -- timestamps: when each token (and word) of a transcript was said, at any exit ------------------------------------------
+    def _lattice_rows(self, name: str, model, spec: Tensor, valid_len: Tensor, hyps, exits, blank: int):
+        """What ``timestamps`` and ``confidences`` (``name``) begin with: one encoder pass (the log-probs of all exits, no taps), the
+        encoder's own frame counts, and ``exit_rows`` over the transcripts without the SOS, EOS and PAD ids of ``args``."""
+        valid_len = valid_len.reshape(-1)
+        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
+        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
+        return (logp, encoder_lengths(valid_len.to(logp.device), logp.size(2)),
+                exit_rows(name, hyps, exits, int(logp.size(0)), int(logp.size(1)), drop, int(blank)))
+
+    def _frame_seconds(self, frame_seconds: Optional[float]) -> float:
+        if frame_seconds is not None:
+            return frame_seconds
+        hop, rate = getattr(self.args, "hop_length", None), getattr(self.args, "sample_rate", None)
+        return 4.0 * hop / rate if hop and rate else FRAME_SECONDS
+
+    @staticmethod
+    def _per_exit(rows, exits, logp: Tensor):
+        """``rows`` [H] as they are, or nested ``[E][B]`` where ``exits`` was ``"all"``."""
+        if rows is None or not isinstance(exits, str):
+            return rows
+        E, B = int(logp.size(0)), int(logp.size(1))
+        return [rows[e * B:(e + 1) * B] for e in range(E)]
+
     @torch.no_grad()
     def timestamps(self, model, spec: Tensor, valid_len: Tensor, hyps, exits=None, pieces: Optional[Sequence[str]] = None,
                    frame_seconds: Optional[float] = None, blank: int = 0) -> Timestamps:
@@ -994,40 +1017,14 @@ class BeamInference:
         ``pieces`` (the vocabulary's pieces: a piece beginning with U+2581 opens a word) is given, else None, and the ``Alignment``
         itself, row e * B + b for ``"all"`` and row b otherwise.  An utterance whose transcript does not fit its frames has
         status 1 there and empty lists here."""
-        valid_len = valid_len.reshape(-1)
-        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
-        E, B = int(logp.size(0)), int(logp.size(1))
-        if len(hyps) != B:
-            raise ValueError(f"timestamps: {B} utterances, {len(hyps)} hypotheses")
-        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
-        rows = transcript_rows(hyps, drop, int(blank))
-        if isinstance(exits, str):
-            if exits != "all":
-                raise ValueError(f"timestamps: exits must be None, one exit per utterance or 'all', got {exits!r}")
-            pairs = [(e, b) for e in range(E) for b in range(B)]
-        else:
-            of = [E - 1] * B if exits is None else [int(e) for e in (exits.tolist() if torch.is_tensor(exits) else exits)]
-            if len(of) != B or any(not 0 <= e < E for e in of):
-                raise ValueError(f"timestamps: exits must hold one exit of 0 .. {E - 1} per utterance ({B})")
-            pairs = [(e, b) for b, e in enumerate(of)]
-        S = max(1, max(len(r) for r in rows))
-        tokens = torch.zeros((len(pairs), S), dtype=torch.int32)
-        for h, (_, b) in enumerate(pairs):
-            tokens[h, :len(rows[b])] = torch.tensor(rows[b], dtype=torch.int32)
-        tok_len = torch.tensor([len(rows[b]) for _, b in pairs], dtype=torch.int32)
-        em_index = torch.tensor([e * B + b for e, b in pairs], dtype=torch.int32)
-        al = ctc_forced_align(logp, tokens, tok_len, em_index, encoder_lengths(valid_len.to(logp.device), logp.size(2)), blank=int(blank))
-        if frame_seconds is None:
-            hop, rate = getattr(self.args, "hop_length", None), getattr(self.args, "sample_rate", None)
-            frame_seconds = 4.0 * hop / rate if hop and rate else FRAME_SECONDS
+        logp, lens, (pairs, tokens, tok_len, em_index) = self._lattice_rows("timestamps", model, spec, valid_len, hyps, exits, blank)
+        al = ctc_forced_align(logp, tokens, tok_len, em_index, lens, blank=int(blank))
+        frame_seconds = self._frame_seconds(frame_seconds)
         host = Alignment(*(t.cpu() for t in (al.tok_start, al.tok_end, al.tok_score, al.frame_token, al.path_score, al.status)),
                          tokens=al.tokens.cpu(), tok_len=al.tok_len.cpu())  # one copy each, not one per span
         tok = [host.spans(h, frame_seconds) for h in range(len(pairs))]
         words = None if pieces is None else [word_spans(sp, starts_word_from_pieces(pieces)) for sp in tok]
-        if isinstance(exits, str):
-            tok = [tok[e * B:(e + 1) * B] for e in range(E)]
-            words = None if words is None else [words[e * B:(e + 1) * B] for e in range(E)]
-        return Timestamps(tok, words, al)
+        return Timestamps(self._per_exit(tok, exits, logp), self._per_exit(words, exits, logp), al)
 
     @torch.no_grad()
     def confidences(self, model, spec: Tensor, valid_len: Tensor, hyps, exits=None, pieces: Optional[Sequence[str]] = None,
@@ -1040,40 +1037,14 @@ class BeamInference:
         ``SoftWordSpan`` lists where ``pieces`` is given, else None, and the ``Posteriors`` itself, row e * B + b for ``"all"`` and
         row b otherwise -- ``nbest_posteriors(posteriors.row_logp, ...)`` compares an utterance's exits or hypotheses.  An utterance
         whose transcript does not fit its frames has status 1 there and empty lists here."""
-        valid_len = valid_len.reshape(-1)
-        logp = model._run_encoder(spec, valid_len, want_out=True, want_taps=False, n_groups=model._cfg.n_exits)[0]
-        E, B = int(logp.size(0)), int(logp.size(1))
-        if len(hyps) != B:
-            raise ValueError(f"confidences: {B} utterances, {len(hyps)} hypotheses")
-        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
-        rows = transcript_rows(hyps, drop, int(blank))
-        if isinstance(exits, str):
-            if exits != "all":
-                raise ValueError(f"confidences: exits must be None, one exit per utterance or 'all', got {exits!r}")
-            pairs = [(e, b) for e in range(E) for b in range(B)]
-        else:
-            of = [E - 1] * B if exits is None else [int(e) for e in (exits.tolist() if torch.is_tensor(exits) else exits)]
-            if len(of) != B or any(not 0 <= e < E for e in of):
-                raise ValueError(f"confidences: exits must hold one exit of 0 .. {E - 1} per utterance ({B})")
-            pairs = [(e, b) for b, e in enumerate(of)]
-        S = max(1, max(len(r) for r in rows))
-        tokens = torch.zeros((len(pairs), S), dtype=torch.int32)
-        for h, (_, b) in enumerate(pairs):
-            tokens[h, :len(rows[b])] = torch.tensor(rows[b], dtype=torch.int32)
-        tok_len = torch.tensor([len(rows[b]) for _, b in pairs], dtype=torch.int32)
-        em_index = torch.tensor([e * B + b for e, b in pairs], dtype=torch.int32)
-        po = ctc_posteriors(logp, tokens, tok_len, em_index, encoder_lengths(valid_len.to(logp.device), logp.size(2)), blank=int(blank))
-        if frame_seconds is None:
-            hop, rate = getattr(self.args, "hop_length", None), getattr(self.args, "sample_rate", None)
-            frame_seconds = 4.0 * hop / rate if hop and rate else FRAME_SECONDS
+        logp, lens, (pairs, tokens, tok_len, em_index) = self._lattice_rows("confidences", model, spec, valid_len, hyps, exits, blank)
+        po = ctc_posteriors(logp, tokens, tok_len, em_index, lens, blank=int(blank))
+        frame_seconds = self._frame_seconds(frame_seconds)
         host = Posteriors(po.row_logp.cpu(), *(getattr(po, n).cpu() for n in TOKEN_FIELDS), None, po.status.cpu(),
                           tokens=po.tokens.cpu(), tok_len=po.tok_len.cpu())  # one copy each, not one per span
         tok = [host.spans(h, frame_seconds) for h in range(len(pairs))]
         words = None if pieces is None else [soft_word_spans(sp, starts_word_from_pieces(pieces)) for sp in tok]
-        if isinstance(exits, str):
-            tok = [tok[e * B:(e + 1) * B] for e in range(E)]
-            words = None if words is None else [words[e * B:(e + 1) * B] for e in range(E)]
-        return Confidences(tok, words, po)
+        return Confidences(self._per_exit(tok, exits, logp), self._per_exit(words, exits, logp), po)
 
     @torch.no_grad()
     def decode_batch_adaptive(self, model, spec: Tensor, valid_len: Tensor, threshold=None, max_length: Optional[int] = None,

@@ -41,11 +41,6 @@ constexpr size_t kAlMaxLds = 64 * 1024;  // decision words + path emissions + pa
 
 __host__ __device__ inline size_t al_lds_bytes(int Tq, int C) { return ((size_t)Tq * (C * 8 + 4 + 2) + 15) & ~(size_t)15; }
 
-// lane l receives lane l - 1's v (DPP wave_shr:1); lane 0 receives `first`
-__device__ __forceinline__ float al_from_left(float v, float first) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-
 template <int C, bool TRELLIS>
 __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logp, int n_em, int Tq, int V, const int* __restrict__ em_len,
                                                        const long long* __restrict__ tokens, const int* __restrict__ tok_len,
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
         for (int k = 0; k < C; ++k) rg[u][k] = row[id[k]];
       }
       if (t >= T) continue;
-      const float left = al_from_left(tr[C - 1], 0.f);
+      const float left = from_left(tr[C - 1], 0.f);
       unsigned long long m[C];
 #pragma unroll
       for (int k = C - 1; k >= 0; --k) {  // descending: tr[k - 1] is still the previous row's

@@ -3,15 +3,10 @@
 // of every frame, the first and last frame of every token, the token's summed emission, the path's score.  The statement -- the
 // candidates, their order, the tie rule, the end rule, the status -- is the header's; this file is its layout on the device.
 //
-// One launch, no atomics, no barrier, nothing read back.  One wave per hypothesis, four per workgroup: hypothesis h is wave h & 3
-// of workgroup h >> 2, so rows that follow each other and share an emission (the beams of one utterance) fetch its rows from memory
-// once and serve them to each other from the caches.
-//   Forward.  The states live in registers as a strip of C = 1, 2, 4 or 8 consecutive states per lane (lane l: states l * C ..
-//     l * C + C - 1), C chosen per wave from the row's own N (31, 63, 127, 255 tokens at most).  For C >= 2 the even slots of a strip
-//     are blanks and the odd ones labels, and the one value that crosses a lane boundary -- the left neighbour's last state, which is
-//     s - 1 of slot 0 and s - 2 of slot 1 -- comes by one DPP wave shift; for C = 1 (odd lanes the labels) by two.  A frame is a short
-//     chain of shifts, compares, selects and one add per state.  The frame's loads -- the gathers x[t][lab(s)] of the strip's labels
-//     and x[t][blank] -- are issued kFaAhead frames before their use, off that chain.
+// One launch, no atomics, no barrier, nothing read back.  One wave per hypothesis on the state strips of eec_ctc_strip.h, which
+// also holds the row checks, the strip's labels, frame 0 and the end read.
+//   Forward.  A frame is a short chain of shifts, compares, selects and one add per state.  The frame's loads -- the gathers
+//     x[t][lab(s)] of the strip's labels and x[t][blank] -- are issued kFaAhead frames before their use, off that chain.
 //   Decisions.  Two bits per (frame, state), the strip's 2 * C bits packed per lane, 16 / C frames to a dword; a dword per lane is
 //     one coalesced 256-byte store, so a row of T frames costs ceil(T * C / 16) such stores.  They go to the WORKSPACE, not to the
 //     LDS: at the benchmarked shape (T' = 256, 200 tokens) a row has 32 KiB of them, and four waves' worth would hold a compute
@@ -22,31 +17,17 @@
 //     t & 63 keeps state[t], so frame_token leaves as whole 256-byte lines, and a lane whose frame opens or closes a run of a label
 //     state 2j + 1 writes tok_start[j] / tok_end[j]: the index is the token index, nothing is compacted.  tok_score is then summed
 //     by lane j over its own frames, in frame order.
-// A row the device cannot serve (the header's status 1) gets the fill values and none of its values becomes an address; em_len is
-// clamped to [0, T'] and frames from the length on are never read.
-#include <limits.h>
-#include <math.h>
-
+// A row the device cannot serve (the header's status 1) gets the fill values.
 #include "../../include/eec.h"
-#include "eec_host.h"
+#include "eec_ctc_strip.h"
 #include "eec_kernels.h"
 
 namespace eec {
 
-constexpr int kFaAhead = 8;        // frames of look-ahead held in registers
-constexpr int kFaWaves = 4;        // hypotheses per workgroup
-constexpr int kFaMaxTokens = 255;  // N: 2N + 1 = 511 states in 64 lanes, eight per lane
+constexpr int kFaAhead = 8;  // frames of look-ahead held in registers
 
-// states per lane for a row of N tokens: 2N + 1 <= 64 * C
-__host__ __device__ inline int fa_strip(int N) { return N <= 31 ? 1 : N <= 63 ? 2 : N <= 127 ? 4 : 8; }
 // decision dwords per lane of one hypothesis: 16 / C frames to a dword
 __host__ __device__ inline size_t fa_words(int Tq, int C) { return ((size_t)Tq * C + 15) / 16; }
-
-// lane l receives lane l - 1's v (DPP wave_shr:1); lane 0 receives `first`
-__device__ __forceinline__ int fa_from_left(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ float fa_from_left(float v, float first) {
-  return __builtin_bit_cast(float, fa_from_left(__builtin_bit_cast(int, v), __builtin_bit_cast(int, first)));
-}
 
 struct FaOut {
   int* tok_start;     // [tok_stride]
@@ -70,33 +51,18 @@ template <int C>
 __device__ __forceinline__ void fa_row(const float* __restrict__ em, int T, int Tq, int V, int blank, int N, int tok_stride,
                                        const int* __restrict__ tk, int lane, unsigned* __restrict__ dec, int* __restrict__ spans,
                                        const FaOut& o) {
-  constexpr int NL = C >= 2 ? C / 2 : 1;                      // label states of a strip
-  constexpr int G = 16 / C;                                   // frames per decision dword
-  constexpr int LOGC = C == 1 ? 0 : C == 2 ? 1 : C == 4 ? 2 : 3;
-  int id[NL];     // the token of the strip's label slot (slot 2 * i + 1; for C == 1 the odd lanes' only slot); else the blank
-  bool skip[NL];  // ... and whether state s - 2 is a candidate of it
+  constexpr int NL = strip_labels(C), LOGC = strip_log2(C);
+  constexpr int G = 16 / C;  // frames per decision dword
+  int id[NL];     // the strip's labels
+  bool skip[NL];  // ... and whether state s - 2 is a candidate of the label slot
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
-    const int j = C == 1 ? lane >> 1 : lane * NL + i;
-    const bool label = (C == 1 ? (lane & 1) != 0 : true) && j < N;
-    const int y = label ? tk[j] : blank, p = (label && j >= 1) ? tk[j - 1] : blank;
-    id[i] = y;  // the states past 2N compute on the blank and feed nothing
-    skip[i] = label && j >= 1 && y != p;
+    const StripLabel l = strip_label<C>(tk, N, blank, lane, i);
+    id[i] = l.id, skip[i] = l.skip;
   }
 
   float a[C];
-  {  // frame 0: states 0 and 1 only
-    const float xb = em[blank], x0 = em[id[0]];
-#pragma unroll
-    for (int k = 0; k < C; ++k) a[k] = -INFINITY;
-    if (C == 1) {
-      if (lane == 0) a[0] = xb;
-      if (lane == 1) a[0] = x0;
-    } else if (lane == 0) {
-      a[0] = xb;
-      a[C > 1 ? 1 : 0] = x0;
-    }
-  }
+  strip_frame0<C>(a, em, blank, id[0], lane);
   float rg[kFaAhead][NL], rb[kFaAhead];  // x[t][label] and (C >= 2) x[t][blank] of the frames ahead; slot u: frame t0 + u
 #pragma unroll
   for (int u = 0; u < kFaAhead; ++u) {
@@ -124,13 +90,13 @@ __device__ __forceinline__ void fa_row(const float* __restrict__ em, int T, int 
       // the candidates in the statement's order; a later one replaces only if strictly greater
       unsigned dd = 0;
       if (C == 1) {
-        const float p1 = fa_from_left(a[0], -INFINITY), p2 = fa_from_left(p1, -INFINITY);
+        const float p1 = from_left(a[0], -INFINITY), p2 = from_left(p1, -INFINITY);
         float best = a[0];
         if (p1 > best) best = p1, dd = 1;  // lane 0 receives -inf, which is greater than nothing: state 0 only stays
         if (skip[0] && p2 > best) best = p2, dd = 2;
         a[0] = best + g[0];
       } else {
-        const float left = fa_from_left(a[C - 1], -INFINITY);
+        const float left = from_left(a[C - 1], -INFINITY);
         static_range<0, C>([&](auto tag) {  // descending: a[k - 1] and a[k - 2] are still the previous frame's
           constexpr int k = C - 1 - decltype(tag)::value;
           float best = a[k];
@@ -155,14 +121,8 @@ __device__ __forceinline__ void fa_row(const float* __restrict__ em, int T, int 
   if (T & (G - 1)) dec[(size_t)((T - 1) / G) * 64 + lane] = word;
 
   const int sN = 2 * N;
-  float hi = a[0], lo = a[0];  // states 2N and 2N - 1: slot (wave-uniform) and lane
-  static_range<1, C>([&](auto tag) {
-    constexpr int k = decltype(tag)::value;
-    if ((sN & (C - 1)) == k) hi = a[k];
-    if (((sN - 1) & (C - 1)) == k) lo = a[k];
-  });
-  hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi), sN >> LOGC));
-  lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo), (sN - 1) >> LOGC));
+  float hi, lo;
+  strip_end<C>(a, N, hi, lo);
   const bool at_blank = hi > lo;
   const float ps = at_blank ? hi : lo;
   if (!(ps > -INFINITY)) {  // no path (or a NaN on it)
@@ -210,7 +170,7 @@ __device__ __forceinline__ void fa_row(const float* __restrict__ em, int T, int 
       st = s + __popcll(x0 & ~odd) + 2 * __popcll(x0 & odd) + __popcll(x1 & ~odd) + 2 * __popcll(x1 & odd);
     }
     const int t = t0 + lane;
-    const int prev = fa_from_left(st, s);  // lane 0: state[t0 - 1], where the walk now stands
+    const int prev = from_left(st, s);  // lane 0: state[t0 - 1], where the walk now stands
     int next = __shfl_down(st, 1);
     if (lane == 63) next = above;
     above = __builtin_amdgcn_readfirstlane(st);
@@ -244,42 +204,26 @@ __device__ __forceinline__ void fa_row(const float* __restrict__ em, int T, int 
   if (lane == 0) *o.path_score = ps, *o.status = 0;
 }
 
-__global__ __launch_bounds__(64 * kFaWaves) void ctc_forced_align_kernel(
+__global__ __launch_bounds__(64 * kStripWaves) void ctc_forced_align_kernel(
     const float* __restrict__ logp, int n_em, int Tq, int V, const int* __restrict__ em_len, const int* __restrict__ tokens,
     const int* __restrict__ tok_len, const int* __restrict__ em_index, int n_hyp, int tok_stride, int blank, int* __restrict__ tok_start,
     int* __restrict__ tok_end, float* __restrict__ tok_score, int* __restrict__ frame_token, float* __restrict__ path_score,
     int* __restrict__ status, unsigned* __restrict__ ws, size_t hyp_words) {
-  __shared__ int spans[kFaWaves][2 * 256];
+  __shared__ int spans[kStripWaves][2 * 256];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int h = blockIdx.x * kFaWaves + w;
+  const int h = blockIdx.x * kStripWaves + w;
   if (h >= n_hyp) return;  // wave-uniform; the kernel has no barrier
   const FaOut o{tok_start + (size_t)h * tok_stride, tok_end + (size_t)h * tok_stride, tok_score + (size_t)h * tok_stride,
                 frame_token + (size_t)h * Tq,       path_score + h,                   status + h};
-  const int N = __builtin_amdgcn_readfirstlane(tok_len[h]);
-  const int ei = __builtin_amdgcn_readfirstlane(em_index ? em_index[h] : h);
   const int* tk = tokens + (size_t)h * tok_stride;
-  bool ok = ei >= 0 && ei < n_em && N >= 1 && N <= tok_stride && N <= kFaMaxTokens;
-  int T = 0;
-  if (ok) {
-    T = __builtin_amdgcn_readfirstlane(em_len ? min(max(em_len[ei], 0), Tq) : Tq);
-    bool bad = false;
-    int R = 0;  // adjacent equal pairs: each needs a blank frame between its two tokens
-    for (int j0 = 0; j0 < N; j0 += 64) {
-      const int j = j0 + lane;
-      const bool in = j < N;
-      const int y = in ? tk[j] : 0, p = (in && j >= 1) ? tk[j - 1] : -1;
-      bad = bad || (in && (y < 0 || y >= V || y == blank));
-      R += __popcll(__ballot(in && j >= 1 && y == p));
-    }
-    ok = __ballot(bad) == 0 && T >= N + R;
-  }
-  if (!ok) {  // not alignable: the fill values, and none of the row's values is used as an address
+  const auto [N, T, ei, ok] = strip_row(tk, tok_len, em_index, em_len, h, n_em, Tq, V, tok_stride, blank, lane);
+  if (!ok) {  // not alignable: the fill values
     fa_fill(o, Tq, tok_stride, lane);
     return;
   }
   const float* em = logp + (size_t)ei * Tq * V;
   unsigned* dec = ws + (size_t)h * hyp_words * 64;
-  switch (fa_strip(N)) {
+  switch (strip_states(N)) {
     case 1: fa_row<1>(em, T, Tq, V, blank, N, tok_stride, tk, lane, dec, spans[w], o); break;
     case 2: fa_row<2>(em, T, Tq, V, blank, N, tok_stride, tk, lane, dec, spans[w], o); break;
     case 4: fa_row<4>(em, T, Tq, V, blank, N, tok_stride, tk, lane, dec, spans[w], o); break;
@@ -293,25 +237,19 @@ extern "C" {
 
 size_t eec_ctc_forced_align_workspace_bytes(int n_hyp, int Tq, int tok_stride) {
   if (n_hyp < 1 || Tq < 1 || tok_stride < 1) return 0;
-  return (size_t)n_hyp * eec::fa_words(Tq, eec::fa_strip(tok_stride)) * 64 * sizeof(uint32_t);  // the decisions
+  return (size_t)n_hyp * eec::fa_words(Tq, eec::strip_states(tok_stride)) * 64 * sizeof(uint32_t);  // the decisions
 }
 
 int eec_ctc_forced_align(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
                          const int32_t* em_index, int n_hyp, int tok_stride, int blank, int32_t* tok_start, int32_t* tok_end,
                          float* tok_score, int32_t* frame_token, float* path_score, int32_t* status, void* workspace, size_t workspace_bytes,
                          void* stream) {
-  using eech::fail;
-  if (n_hyp < 0 || Tq < 1 || tok_stride < 1 || n_em < 1 || V < 1 || blank < 0 || blank >= V)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_forced_align: needs n_hyp >= 0, Tq, tok_stride, n_em, V >= 1 and blank in [0, V)");
-  if (n_hyp == 0) return 0;
-  if (!logp || !tokens || !tok_len || !tok_start || !tok_end || !tok_score || !frame_token || !path_score || !status)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_forced_align: null argument");
-  if (V < 2 || tok_stride > eec::kFaMaxTokens)
-    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_forced_align: needs V >= 2 and tok_stride <= " + std::to_string(eec::kFaMaxTokens));
-  if (!workspace) return fail(EEC_ERR_WORKSPACE, "eec_ctc_forced_align: null workspace");
-  if (int rc = eech::check_workspace(workspace, workspace_bytes, eec_ctc_forced_align_workspace_bytes(n_hyp, Tq, tok_stride))) return rc;
-  const size_t hyp_words = eec::fa_words(Tq, eec::fa_strip(tok_stride));
-  hipLaunchKernelGGL(eec::ctc_forced_align_kernel, dim3((n_hyp + eec::kFaWaves - 1) / eec::kFaWaves), dim3(64 * eec::kFaWaves), 0,
+  const int rc = eech::strip_entry_head("eec_ctc_forced_align", {logp, tokens, tok_len, tok_start, tok_end, tok_score, frame_token, path_score, status},
+                                        n_em, Tq, V, n_hyp, tok_stride, blank, workspace, workspace_bytes,
+                                        eec_ctc_forced_align_workspace_bytes(n_hyp, Tq, tok_stride));
+  if (rc || n_hyp == 0) return rc;
+  const size_t hyp_words = eec::fa_words(Tq, eec::strip_states(tok_stride));
+  hipLaunchKernelGGL(eec::ctc_forced_align_kernel, dim3((n_hyp + eec::kStripWaves - 1) / eec::kStripWaves), dim3(64 * eec::kStripWaves), 0,
                      (hipStream_t)stream, logp, n_em, Tq, V, em_len, tokens, tok_len, em_index, n_hyp, tok_stride, blank, tok_start, tok_end,
                      tok_score, frame_token, path_score, status, (unsigned*)workspace, hyp_words);
   EEC_HIP(hipGetLastError());

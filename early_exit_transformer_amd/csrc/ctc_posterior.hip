@@ -4,15 +4,11 @@
 // occupancy itself, and the row's sum-over-paths log-likelihood.  The statement -- the recursions, the fold order of log_add, the
 // order of every fp32 operation, the status -- is the header's; this file is its layout on the device.
 //
-// One launch, no atomics, no barrier, no LDS, nothing read back.  One wave per row, four per workgroup: row h is wave h & 3 of
-// workgroup h >> 2, so rows that follow each other and share an emission (the beams of one utterance, the exits' copies of one
-// transcript) fetch its lines from memory once.  The state layout is ctc_forced_align.hip's: a strip of C = 1, 2, 4 or 8
-// consecutive states per lane (lane l: states l * C .. l * C + C - 1), C chosen per wave from the row's own N; for C >= 2 the even
-// slots of a strip are blanks and the odd ones labels, for C = 1 the odd lanes are the labels.
-//   Forward.  alpha in registers.  The one value that crosses a lane boundary -- the left neighbour's last state, s - 1 of slot 0
-//     and s - 2 of slot 1 -- comes by one DPP wave shift (C = 1: two).  Every frame's strip goes to the WORKSPACE as C coalesced
-//     256-byte lines (line t * C + k holds slot k of all 64 lanes), so a row of T frames costs T * C lines and
-//     eec_ctc_posteriors_workspace_bytes is n_hyp * T' * C(tok_stride) * 256.  A lane later reads only what it stored itself.
+// One launch, no atomics, no barrier, no LDS, nothing read back.  One wave per row on the state strips of eec_ctc_strip.h, which
+// also holds the row checks, the strip's labels, frame 0 and the end read.
+//   Forward.  alpha in registers.  Every frame's strip goes to the WORKSPACE as C coalesced 256-byte lines (line t * C + k holds
+//     slot k of all 64 lanes), so a row of T frames costs T * C lines and eec_ctc_posteriors_workspace_bytes is
+//     n_hyp * T' * C(tok_stride) * 256.  A lane later reads only what it stored itself.
 //   Backward.  beta in registers; what crosses a lane boundary are the right neighbour's slots 0 and 1 (s + 1 and s + 2 of the last
 //     slot), two DPP wave shifts.  At frame t the lane has beta_t of its strip, reads alpha_t (carried: it was alpha_{t-1} one
 //     step earlier; at T - 1 it is still in the forward's registers) and alpha_{t-1} (its own lines), and adds the frame's terms to
@@ -22,34 +18,16 @@
 //     kPoAheadF / kPoAheadB frames before their use into a register queue that advances by one frame per frame; the frame loop is
 //     not unrolled over the queue (a frame is 12 to 20 inlined log_adds at C = 8: unrolled copies would not fit the instruction
 //     cache).
-// A row the device cannot serve (the header's status 1) gets the fill values and none of its values becomes an address; em_len is
-// clamped to [0, T'] and frames from the length on are never read.
-#include <limits.h>
-#include <math.h>
-
+// A row the device cannot serve (the header's status 1) gets the fill values.
 #include "../../include/eec.h"
-#include "eec_host.h"
+#include "eec_ctc_strip.h"
 #include "eec_kernels.h"
 #include "eec_lexbeam.h"
 
 namespace eec {
 
-constexpr int kPoAheadF = 8;       // frames of look-ahead held in registers, forward (NL + 1 values each)
-constexpr int kPoAheadB = 4;       // ... and backward (NL + 1 + C values each)
-constexpr int kPoWaves = 4;        // rows per workgroup
-constexpr int kPoMaxTokens = 255;  // N: 2N + 1 = 511 states in 64 lanes, eight per lane
-
-// states per lane for a row of N tokens: 2N + 1 <= 64 * C
-__host__ __device__ inline int po_strip(int N) { return N <= 31 ? 1 : N <= 63 ? 2 : N <= 127 ? 4 : 8; }
-
-// lane l receives lane l - 1's v (DPP wave_shr:1); lane 0 receives `first`
-__device__ __forceinline__ float po_from_left(float v, float first) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-// lane l receives lane l + 1's v (DPP wave_shl:1); lane 63 receives `last`
-__device__ __forceinline__ float po_from_right(float v, float last) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, last), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
-}
+constexpr int kPoAheadF = 8;  // frames of look-ahead held in registers, forward (NL + 1 values each)
+constexpr int kPoAheadB = 4;  // ... and backward (NL + 1 + C values each)
 
 struct PoOut {
   float* row_logp;  // [1]
@@ -77,40 +55,21 @@ __device__ __forceinline__ void po_fill(const PoOut& o, int Tq, int tok_stride, 
 template <int C>
 __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int Tq, int V, int blank, int N, int tok_stride,
                                        const int* __restrict__ tk, int lane, float* __restrict__ al, const PoOut& o) {
-  constexpr int NL = C >= 2 ? C / 2 : 1;  // label states of a strip
-  constexpr int LOGC = C == 1 ? 0 : C == 2 ? 1 : C == 4 ? 2 : 3;
+  constexpr int NL = strip_labels(C);
   constexpr float NEG = -INFINITY;
-  int id[NL];      // the token of the strip's label slot (slot 2 * i + 1; for C == 1 the lane's only slot); else the blank
-  bool own[NL];    // the slot is a label state of the row
-  bool skip[NL];   // state s - 2 feeds it
-  bool skipn[NL];  // it feeds state s + 2
+  int id[NL];                      // the strip's labels; the states past 2N are held at -inf backward
+  bool own[NL], skip[NL], skipn[NL];
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
-    const int j = C == 1 ? lane >> 1 : lane * NL + i;
-    const bool label = (C == 1 ? (lane & 1) != 0 : true) && j < N;
-    const int y = label ? tk[j] : blank, p = (label && j >= 1) ? tk[j - 1] : blank, nx = (label && j + 1 < N) ? tk[j + 1] : blank;
-    id[i] = y;  // the states past 2N compute on the blank: forward they feed nothing, backward they are held at -inf
-    own[i] = label;
-    skip[i] = label && j >= 1 && y != p;
-    skipn[i] = label && j + 1 < N && nx != y;
+    const StripLabel l = strip_label<C>(tk, N, blank, lane, i);
+    id[i] = l.id, own[i] = l.own, skip[i] = l.skip, skipn[i] = l.skipn;
   }
 
   // ---- forward ---------------------------------------------------------------------------------------------------------------------
   float a[C];
-  {  // frame 0: states 0 and 1 only
-    const float xb = em[blank], x0 = em[id[0]];
+  strip_frame0<C>(a, em, blank, id[0], lane);
 #pragma unroll
-    for (int k = 0; k < C; ++k) a[k] = NEG;
-    if (C == 1) {
-      if (lane == 0) a[0] = xb;
-      if (lane == 1) a[0] = x0;
-    } else if (lane == 0) {
-      a[0] = xb;
-      a[C > 1 ? 1 : 0] = x0;
-    }
-#pragma unroll
-    for (int k = 0; k < C; ++k) al[(size_t)k * 64 + lane] = a[k];
-  }
+  for (int k = 0; k < C; ++k) al[(size_t)k * 64 + lane] = a[k];
   {
     float rg[kPoAheadF][NL], rb[kPoAheadF];  // x[t][label] and (C >= 2) x[t][blank]; slot u: frame t + u
 #pragma unroll
@@ -139,12 +98,12 @@ __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int 
       }
       // the fold in the statement's order: stay, step, skip
       if (C == 1) {
-        const float p1 = po_from_left(a[0], NEG), p2 = po_from_left(p1, NEG);
+        const float p1 = from_left(a[0], NEG), p2 = from_left(p1, NEG);
         float v = lb_log_add(a[0], p1);
         v = lb_log_add(v, skip[0] ? p2 : NEG);
         a[0] = v + g[0];
       } else {
-        const float left = po_from_left(a[C - 1], NEG);
+        const float left = from_left(a[C - 1], NEG);
         static_range<0, C>([&](auto tag) {  // descending: a[k - 1] and a[k - 2] are still the previous frame's
           constexpr int k = C - 1 - decltype(tag)::value;
           float v = lb_log_add(a[k], k >= 1 ? a[k >= 1 ? k - 1 : 0] : left);
@@ -161,14 +120,8 @@ __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int 
   }
 
   const int sN = 2 * N;
-  float hi = a[0], lo = a[0];  // states 2N and 2N - 1: slot (wave-uniform) and lane
-  static_range<1, C>([&](auto tag) {
-    constexpr int k = decltype(tag)::value;
-    if ((sN & (C - 1)) == k) hi = a[k];
-    if (((sN - 1) & (C - 1)) == k) lo = a[k];
-  });
-  hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi), sN >> LOGC));
-  lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo), (sN - 1) >> LOGC));
+  float hi, lo;
+  strip_end<C>(a, N, hi, lo);
   const float ll = lb_log_add(hi, lo);
   if (!(fabsf(ll) < INFINITY)) {  // no path of finite mass (or a NaN)
     po_fill(o, Tq, tok_stride, lane, 2);
@@ -238,8 +191,8 @@ __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int 
     }
 
     // the frame's posteriors of the label slots
-    const float pl1 = po_from_left(ap[C - 1], NEG);                // alpha_{t-1}: C >= 2: s - 2 of slot 1; C == 1: s - 1
-    const float pl2 = C == 1 ? po_from_left(pl1, NEG) : NEG;       // C == 1: s - 2
+    const float pl1 = from_left(ap[C - 1], NEG);                // alpha_{t-1}: C >= 2: s - 2 of slot 1; C == 1: s - 1
+    const float pl2 = C == 1 ? from_left(pl1, NEG) : NEG;       // C == 1: s - 2
     const double td = (double)t, te = (double)(t + 1);
     float gam[NL];
     static_range<0, NL>([&](auto tag) {
@@ -296,8 +249,8 @@ __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int 
     float c[C];
 #pragma unroll
     for (int k = 0; k < C; ++k) c[k] = valid[k] ? ((C == 1 || (k & 1)) ? g[k >> 1] : xb) + b[k] : NEG;
-    const float r1 = po_from_right(c[0], NEG);                           // s + 1 of the last slot
-    const float r2 = C == 1 ? po_from_right(r1, NEG) : po_from_right(c[C > 1 ? 1 : 0], NEG);  // s + 2 of the last slot
+    const float r1 = from_right(c[0], NEG);                           // s + 1 of the last slot
+    const float r2 = C == 1 ? from_right(r1, NEG) : from_right(c[C > 1 ? 1 : 0], NEG);  // s + 2 of the last slot
     if (C == 1) {
       const float two = skipn[0] ? r2 : NEG;
       b[0] = lb_log_add(lb_log_add(c[0], r1), two);
@@ -338,45 +291,29 @@ __device__ __forceinline__ void po_row(const float* __restrict__ em, int T, int 
   if (lane == 0) *o.row_logp = ll, *o.status = 0;
 }
 
-__global__ __launch_bounds__(64 * kPoWaves) void ctc_posterior_kernel(
+__global__ __launch_bounds__(64 * kStripWaves) void ctc_posterior_kernel(
     const float* __restrict__ logp, int n_em, int Tq, int V, const int* __restrict__ em_len, const int* __restrict__ tokens,
     const int* __restrict__ tok_len, const int* __restrict__ em_index, int n_hyp, int tok_stride, int blank, float* __restrict__ row_logp,
     float* __restrict__ tok_frames, float* __restrict__ tok_score, float* __restrict__ tok_start, float* __restrict__ tok_end,
     float* __restrict__ tok_start_var, float* __restrict__ tok_end_var, float* __restrict__ gamma, int* __restrict__ status,
     float* __restrict__ ws, size_t hyp_floats) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int h = blockIdx.x * kPoWaves + w;
+  const int h = blockIdx.x * kStripWaves + w;
   if (h >= n_hyp) return;  // wave-uniform; the kernel has no barrier
   const size_t at = (size_t)h * tok_stride;
   const PoOut o{row_logp + h,       tok_frames + at,  tok_score + at,
                 tok_start + at,     tok_end + at,     tok_start_var + at,
                 tok_end_var + at,   gamma ? gamma + (size_t)h * Tq * tok_stride : nullptr,
                 status + h};
-  const int N = __builtin_amdgcn_readfirstlane(tok_len[h]);
-  const int ei = __builtin_amdgcn_readfirstlane(em_index ? em_index[h] : h);
   const int* tk = tokens + at;
-  bool ok = ei >= 0 && ei < n_em && N >= 1 && N <= tok_stride && N <= kPoMaxTokens;
-  int T = 0;
-  if (ok) {
-    T = __builtin_amdgcn_readfirstlane(em_len ? min(max(em_len[ei], 0), Tq) : Tq);
-    bool bad = false;
-    int R = 0;  // adjacent equal pairs: each needs a blank frame between its two tokens
-    for (int j0 = 0; j0 < N; j0 += 64) {
-      const int j = j0 + lane;
-      const bool in = j < N;
-      const int y = in ? tk[j] : 0, p = (in && j >= 1) ? tk[j - 1] : -1;
-      bad = bad || (in && (y < 0 || y >= V || y == blank));
-      R += __popcll(__ballot(in && j >= 1 && y == p));
-    }
-    ok = __ballot(bad) == 0 && T >= N + R;
-  }
-  if (!ok) {  // the fill values, and none of the row's values is used as an address
+  const auto [N, T, ei, ok] = strip_row(tk, tok_len, em_index, em_len, h, n_em, Tq, V, tok_stride, blank, lane);
+  if (!ok) {  // the fill values
     po_fill(o, Tq, tok_stride, lane, 1);
     return;
   }
   const float* em = logp + (size_t)ei * Tq * V;
   float* al = ws + (size_t)h * hyp_floats;
-  switch (po_strip(N)) {
+  switch (strip_states(N)) {
     case 1: po_row<1>(em, T, Tq, V, blank, N, tok_stride, tk, lane, al, o); break;
     case 2: po_row<2>(em, T, Tq, V, blank, N, tok_stride, tk, lane, al, o); break;
     case 4: po_row<4>(em, T, Tq, V, blank, N, tok_stride, tk, lane, al, o); break;
@@ -390,26 +327,19 @@ extern "C" {
 
 size_t eec_ctc_posteriors_workspace_bytes(int n_hyp, int Tq, int tok_stride) {
   if (n_hyp < 1 || Tq < 1 || tok_stride < 1) return 0;
-  return (size_t)n_hyp * Tq * eec::po_strip(tok_stride) * 64 * sizeof(float);  // the alpha lines
+  return (size_t)n_hyp * Tq * eec::strip_states(tok_stride) * 64 * sizeof(float);  // the alpha lines
 }
 
 int eec_ctc_posteriors(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
                        const int32_t* em_index, int n_hyp, int tok_stride, int blank, float* row_logp, float* tok_frames, float* tok_score,
                        float* tok_start, float* tok_end, float* tok_start_var, float* tok_end_var, float* gamma, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  using eech::fail;
-  if (n_hyp < 0 || Tq < 1 || tok_stride < 1 || n_em < 1 || V < 1 || blank < 0 || blank >= V)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_posteriors: needs n_hyp >= 0, Tq, tok_stride, n_em, V >= 1 and blank in [0, V)");
-  if (n_hyp == 0) return 0;
-  if (!logp || !tokens || !tok_len || !row_logp || !tok_frames || !tok_score || !tok_start || !tok_end || !tok_start_var || !tok_end_var ||
-      !status)
-    return fail(EEC_ERR_BAD_ARG, "eec_ctc_posteriors: null argument");
-  if (V < 2 || tok_stride > eec::kPoMaxTokens)
-    return fail(EEC_ERR_UNSUPPORTED, "eec_ctc_posteriors: needs V >= 2 and tok_stride <= " + std::to_string(eec::kPoMaxTokens));
-  if (!workspace) return fail(EEC_ERR_WORKSPACE, "eec_ctc_posteriors: null workspace");
-  if (int rc = eech::check_workspace(workspace, workspace_bytes, eec_ctc_posteriors_workspace_bytes(n_hyp, Tq, tok_stride))) return rc;
-  const size_t hyp_floats = (size_t)Tq * eec::po_strip(tok_stride) * 64;
-  hipLaunchKernelGGL(eec::ctc_posterior_kernel, dim3((n_hyp + eec::kPoWaves - 1) / eec::kPoWaves), dim3(64 * eec::kPoWaves), 0,
+  const int rc = eech::strip_entry_head(
+      "eec_ctc_posteriors", {logp, tokens, tok_len, row_logp, tok_frames, tok_score, tok_start, tok_end, tok_start_var, tok_end_var, status},
+      n_em, Tq, V, n_hyp, tok_stride, blank, workspace, workspace_bytes, eec_ctc_posteriors_workspace_bytes(n_hyp, Tq, tok_stride));
+  if (rc || n_hyp == 0) return rc;
+  const size_t hyp_floats = (size_t)Tq * eec::strip_states(tok_stride) * 64;
+  hipLaunchKernelGGL(eec::ctc_posterior_kernel, dim3((n_hyp + eec::kStripWaves - 1) / eec::kStripWaves), dim3(64 * eec::kStripWaves), 0,
                      (hipStream_t)stream, logp, n_em, Tq, V, em_len, tokens, tok_len, em_index, n_hyp, tok_stride, blank, row_logp, tok_frames,
                      tok_score, tok_start, tok_end, tok_start_var, tok_end_var, gamma, status, (float*)workspace, hyp_floats);
   EEC_HIP(hipGetLastError());

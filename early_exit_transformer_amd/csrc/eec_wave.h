@@ -78,6 +78,16 @@ __device__ __forceinline__ int wave_all_max(int v, int from = 32) {
   return v;
 }
 
+// One-lane shifts on the DPP crossbar.  from_left: lane l receives lane l - 1's v (wave_shr:1), lane 0 receives `first`;
+// from_right: lane l receives lane l + 1's v (wave_shl:1), lane 63 receives `last`.
+__device__ __forceinline__ int from_left(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ float from_left(float v, float first) {
+  return __builtin_bit_cast(float, from_left(__builtin_bit_cast(int, v), __builtin_bit_cast(int, first)));
+}
+__device__ __forceinline__ float from_right(float v, float last) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, last), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
+
 // f(IntTag<K0>{}), ..., f(IntTag<K1-1>{}): a loop whose index is a compile-time constant in the body (register arrays
 // indexed by it never fall back to scratch memory, whatever the unroller decides)
 template <int I>

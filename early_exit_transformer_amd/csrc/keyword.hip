@@ -37,11 +37,6 @@ constexpr int kKwMaxFrames = 1 << 20;   // T'
 
 __device__ __forceinline__ int kw_frames(const int* __restrict__ em_len, int n, int Tq) { return em_len ? min(max(em_len[n], 0), Tq) : Tq; }
 
-// lane l receives lane l - 1's v (DPP wave_shr:1); lane 0 receives `first`
-__device__ __forceinline__ int kw_from_left(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ float kw_from_left(float v, float first) {
-  return __builtin_bit_cast(float, kw_from_left(__builtin_bit_cast(int, v), __builtin_bit_cast(int, first)));
-}
 __device__ __forceinline__ float kw_lane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
 // m[row] = max_v x[row][v], row = n * Tq + t, for the frames t < T_n; the others are left alone (nothing reads them)
@@ -113,10 +108,10 @@ __device__ __forceinline__ void kw_walk(const float* __restrict__ em, const floa
         // the candidates of the label state, in the statement's order; a later one replaces only if strictly greater
         float c = d[0];
         int cs = st[0];
-        const float p1 = kw_from_left(d[C - 1], -INFINITY);  // state s - 1
-        const int s1 = kw_from_left(st[C - 1], -1);
-        const float p2 = C == 1 ? kw_from_left(p1, -INFINITY) : kw_from_left(d[0], -INFINITY);  // state s - 2
-        const int s2 = C == 1 ? kw_from_left(s1, -1) : kw_from_left(st[0], -1);
+        const float p1 = from_left(d[C - 1], -INFINITY);  // state s - 1
+        const int s1 = from_left(st[C - 1], -1);
+        const float p2 = C == 1 ? from_left(p1, -INFINITY) : from_left(d[0], -INFINITY);  // state s - 2
+        const int s2 = C == 1 ? from_left(s1, -1) : from_left(st[0], -1);
         if (p1 > c) c = p1, cs = s1;
         if (skip && p2 > c) c = p2, cs = s2;
         if (lane == 0 && 0.f > c) c = 0.f, cs = t;  // the fresh start, state 0 only

@@ -18,8 +18,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import capi
-from .alignment import host_row_checks, row_arguments
+from .alignment import group_words, host_lattice, host_row_checks, launch_rows, row_arguments
 
 TOKEN_FIELDS = ("tok_frames", "tok_score", "tok_start", "tok_end", "tok_start_var", "tok_end_var")
 
@@ -88,14 +87,8 @@ def soft_word_spans(spans: Sequence[SoftSpan], starts_word: Union[Sequence[bool]
     the vocabulary -- ``starts_word_from_pieces`` makes one --, or a callable on the id) holds opens a word, as does the first
     token.  A word runs from its first token's start (and deviation) to its last token's end; its confidence is
     exp(sum of scores / sum of frames) in fp64, a token's score being frames * log(confidence)."""
-    opens = starts_word if callable(starts_word) else (lambda t, table=np.asarray(starts_word, dtype=bool): bool(table[t]))
-    groups: List[List[SoftSpan]] = []
-    for sp in spans:
-        if not groups or opens(sp.token):
-            groups.append([])
-        groups[-1].append(sp)
     out = []
-    for g in groups:
+    for g in group_words(spans, starts_word):
         frames = math.fsum(sp.frames for sp in g)
         dead = frames <= 0.0 or any(sp.confidence <= 0.0 and sp.frames > 0.0 for sp in g)
         conf = 0.0 if dead else math.exp(math.fsum(sp.frames * math.log(sp.confidence) for sp in g if sp.frames > 0.0) / frames)
@@ -134,15 +127,7 @@ def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: n
     NEG = -np.inf
     rows = np.arange(K)
     s_idx = np.arange(NS)[None, :]
-    valid = s_idx <= 2 * N[:, None]
-    lab = np.full((K, NS), blank, dtype=np.int64)
-    lab[:, 1::2] = y
-    skip = np.zeros((K, NS), dtype=bool)  # state s takes from s - 2
-    if S > 1:
-        skip[:, 3::2] = y[:, 1:] != y[:, :-1]
-    skip &= valid
-    skipn = np.zeros((K, NS), dtype=bool)  # state s gives to s + 2
-    skipn[:, :-2] = skip[:, 2:]
+    lab, skip, skipn, valid = host_lattice(y, N, blank)
     t_max = int(T.max())
 
     def emit(t):
@@ -225,29 +210,13 @@ def _host_posteriors(x, lens, tokens, tok_len, em_index, blank: int, want_gamma:
 
 def _device_posteriors(logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, want_gamma: bool,
                        max_workspace_bytes: int):
-    dev = logp.device
-    n_em, Tq, V = logp.shape
+    dev, Tq = logp.device, logp.size(1)
     H, S = tokens.shape
-    lib = capi.load()
     row_logp = torch.empty((H,), dtype=torch.float32, device=dev)
     tok = [torch.empty((H, S), dtype=torch.float32, device=dev) for _ in TOKEN_FIELDS]
     gamma = torch.empty((H, Tq, S), dtype=torch.float32, device=dev) if want_gamma else None
     status = torch.empty((H,), dtype=torch.int32, device=dev)
-    if H == 0:
-        return (row_logp, *tok, gamma, status)
-    # a call above the bound is split over rows: a wave's result depends on its own row alone
-    per_row = max(1, lib.eec_ctc_posteriors_workspace_bytes(1, Tq, S))
-    Hc = max(1, min(H, int(max_workspace_bytes) // per_row))
-    if em_index is None and Hc < H:  # the rows of a later part are no longer their emissions' indices
-        em_index = torch.arange(H, dtype=torch.int32, device=dev)
-    ws_bytes = lib.eec_ctc_posteriors_workspace_bytes(Hc, Tq, S)
-    ws, ws_ptr = capi.aligned_ws(ws_bytes, dev)
-    for h0 in range(0, H, Hc):
-        h1 = min(H, h0 + Hc)
-        capi.launch("eec_ctc_posteriors", dev, logp, n_em, Tq, V, lens, tokens[h0:h1], tok_len[h0:h1],
-                    None if em_index is None else em_index[h0:h1], h1 - h0, S, blank, row_logp[h0:h1], *(t[h0:h1] for t in tok),
-                    None if gamma is None else gamma[h0:h1], status[h0:h1], ws_ptr, ws_bytes)
-    del ws
+    launch_rows("eec_ctc_posteriors", logp, lens, tokens, tok_len, em_index, blank, (row_logp, *tok, gamma, status), max_workspace_bytes)
     return (row_logp, *tok, gamma, status)
 
 

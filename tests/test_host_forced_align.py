@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import forced_align_cases as fc
 from early_exit_transformer_amd import Alignment, TokenSpan, WordSpan, capi, ctc_forced_align, starts_word_from_pieces, word_spans
-from early_exit_transformer_amd.alignment import FRAME_SECONDS, transcript_rows
+from early_exit_transformer_amd.alignment import FRAME_SECONDS, exit_rows, transcript_rows
 from early_exit_transformer_amd.build import LIB_PATH
 
 NEG = float("-inf")
@@ -219,6 +219,35 @@ def test_refusals_of_the_package():
         b = ctc_forced_align(x, torch.tensor([[1, 2]], dtype=dt))
         assert all(fc.same_bits(getattr(a, n), getattr(b, n)) for n in fc.FIELDS)
     assert ctc_forced_align(x, torch.tensor([[1, (1 << 32) + 2]])).status.tolist() == [1]
+
+
+def test_exit_rows_pairs_padding_and_refusals():
+    """What ``BeamInference.timestamps`` / ``.confidences`` hand to the kernels, against a literal table: E = 3 exits, B = 2
+    utterances of 3 and 1 tokens after the special ids 1 and 2 left."""
+    hyps = [[1, 7, 3, 9, 2], torch.tensor([8])]
+    last = ([(2, 0), (2, 1)], [[7, 3, 9], [8, 0, 0]], [3, 1], [4, 5])
+    table = {"none": (None, last),
+             "list": ([1, 0], ([(1, 0), (0, 1)], [[7, 3, 9], [8, 0, 0]], [3, 1], [2, 1])),
+             "tensor": (torch.tensor([0, 2]), ([(0, 0), (2, 1)], [[7, 3, 9], [8, 0, 0]], [3, 1], [0, 5])),
+             "all": ("all", ([(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1)], [[7, 3, 9], [8, 0, 0]] * 3, [3, 1] * 3, [0, 1, 2, 3, 4, 5]))}
+    for exits, want in table.values():
+        pairs, tokens, tok_len, em_index = exit_rows("confidences", hyps, exits, 3, 2, drop={1, 2})
+        assert all(t.dtype == torch.int32 for t in (tokens, tok_len, em_index))
+        assert (pairs, tokens.tolist(), tok_len.tolist(), em_index.tolist()) == want
+        assert em_index.tolist() == [e * 2 + b for e, b in pairs]
+    # the padding is max(1, longest): rows without a token still have a column
+    pairs, tokens, tok_len, em_index = exit_rows("timestamps", [[1, 2], []], None, 3, 2, drop={1, 2})
+    assert (tuple(tokens.shape), tokens.tolist(), tok_len.tolist(), em_index.tolist()) == ((2, 1), [[0], [0]], [0, 0], [4, 5])
+    for name in ("timestamps", "confidences"):
+        with pytest.raises(ValueError, match=rf"^{name}: 2 utterances, 3 hypotheses$"):
+            exit_rows(name, hyps + [[5]], None, 3, 2)
+        with pytest.raises(ValueError, match=rf"^{name}: exits must be None, one exit per utterance or 'all', got 'every'$"):
+            exit_rows(name, hyps, "every", 3, 2)
+        for bad in ([0, 3], [-1, 0], [0], torch.tensor([0, 1, 2])):
+            with pytest.raises(ValueError, match=rf"^{name}: exits must hold one exit of 0 \.\. 2 per utterance \(2\)$"):
+                exit_rows(name, hyps, bad, 3, 2)
+        with pytest.raises(ValueError, match=rf"^{name}: the transcript of utterance 1 holds the blank \(0\)$"):
+            exit_rows(name, [[5], [5, 0, 6]], None, 3, 2)
 
 
 @pytest.fixture(scope="module")
