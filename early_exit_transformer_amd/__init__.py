@@ -10,9 +10,14 @@ _KEYWORD = ("KeywordSet", "KeywordHits", "keyword_search")  # keyword spotting o
 _ALIGNMENT = ("Alignment", "TokenSpan", "WordSpan", "ctc_forced_align", "word_spans", "starts_word_from_pieces")
 # token posteriors and soft timestamps: CTC forward-backward in the standard topology (posterior.py), likewise
 _POSTERIOR = ("Posteriors", "SoftSpan", "SoftWordSpan", "ctc_posteriors", "soft_word_spans", "nbest_posteriors")
+# long transcripts: multi-wave CTC segmentation with free ends, utterance spans, windowed emissions (segment.py), likewise
+_SEGMENT = ("UtteranceSpan", "ctc_segment", "utterance_spans", "windowed_emission")
 
 
 def __getattr__(name):
+    if name in _SEGMENT:
+        from . import segment
+        return getattr(segment, name)
     if name in _POSTERIOR:
         from . import posterior
         return getattr(posterior, name)

@@ -156,9 +156,11 @@ def host_lattice(y: np.ndarray, N: np.ndarray, blank: int):
     return lab, skip, skipn, valid
 
 
-def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: np.ndarray, blank: int):
+def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: np.ndarray, blank: int, free_start: bool = False,
+               free_end: bool = False):
     """The header's statement for K rows that passed its row checks, one step per frame over [K, 2S + 1] states: fp32 adds and
-    compares in its order.  ``x`` [n_em, T', V], ``T`` / ``ei`` / ``N`` [K], ``y`` [K, S] (blank past N).  Returns
+    compares in its order.  ``x`` [n_em, T', V], ``T`` / ``ei`` / ``N`` [K], ``y`` [K, S] (blank past N).  ``free_start`` /
+    ``free_end``: eec_ctc_segment's flags -- the emission term of state 0 (of state 2N, from frame 1 on) is 0.0f.  Returns
     ``(state [K, T'] (-1 past T), path_score [K], ok [K])``."""
     K, S = y.shape
     Tq = x.shape[1]
@@ -167,7 +169,7 @@ def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: n
     lab, skip, _, _ = host_lattice(y, N, blank)
     rows = np.arange(K)
     a = np.full((K, NS), NEG, dtype=np.float32)
-    a[:, 0] = x[ei, 0, blank]
+    a[:, 0] = np.float32(0.0) if free_start else x[ei, 0, blank]
     a[:, 1] = x[ei, 0, y[:, 0]]
     t_max = int(T.max())
     dec = np.zeros((t_max, K, NS), dtype=np.uint8)
@@ -176,6 +178,10 @@ def _host_rows(x: np.ndarray, T: np.ndarray, ei: np.ndarray, y: np.ndarray, N: n
         for t in range(1, t_max):
             act = T > t
             e = np.take_along_axis(x[ei, min(t, Tq - 1), :], lab, axis=1)  # a row past its length: computed, not kept
+            if free_start:
+                e[:, 0] = 0.0
+            if free_end:
+                e[rows, 2 * N] = 0.0
             best, d = a, np.zeros((K, NS), dtype=np.uint8)
             step = np.concatenate([neg1, a[:, :-1]], axis=1)
             take = step > best
@@ -218,7 +224,7 @@ def host_row_checks(shape, lens: Optional[np.ndarray], tokens: np.ndarray, tok_l
 
 
 def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, tok_len: np.ndarray, em_index: Optional[np.ndarray],
-                blank: int):
+                blank: int, free_start: bool = False, free_end: bool = False):
     n_em, Tq, V = x.shape
     H, S = tokens.shape
     NEG = np.float32(-np.inf)
@@ -235,7 +241,7 @@ def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, t
         r = keep[c0:c0 + step]
         Tr, er, Nr = T_all[ei[r]], ei[r], N[r]
         y = np.where(inside[r], tk[r], blank)
-        state, score, good = _host_rows(x, Tr, er, y, Nr, blank)
+        state, score, good = _host_rows(x, Tr, er, y, Nr, blank, free_start, free_end)
         g = np.nonzero(good)[0]
         state, rg, Tg, eg, yg = state[g], r[g], Tr[g], er[g], y[g]
         path_score[rg], status[rg] = score[g], 0
@@ -256,10 +262,11 @@ def _host_align(x: np.ndarray, lens: Optional[np.ndarray], tokens: np.ndarray, t
     return tok_start, tok_end, tok_score, frame_token, path_score, status
 
 
-def launch_rows(entry: str, logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, outs, max_workspace_bytes: int):
-    """``entry`` (``eec_ctc_forced_align``, ``eec_ctc_posteriors``) over the H rows into ``outs``, the entry's outputs in its order
-    (tensors with a leading H; None where it takes a null).  A call whose workspace exceeds the bound is split over rows: a wave's
-    result depends on its own row alone."""
+def launch_rows(entry: str, logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index, blank: int, outs, max_workspace_bytes: int,
+                extra=()):
+    """``entry`` (``eec_ctc_forced_align``, ``eec_ctc_posteriors``, ``eec_ctc_segment``) over the H rows into ``outs``, the entry's
+    outputs in its order (tensors with a leading H; None where it takes a null); ``extra``: what the entry takes between ``blank``
+    and its outputs.  A call whose workspace exceeds the bound is split over rows: a row's result depends on that row alone."""
     dev = logp.device
     n_em, Tq, V = logp.shape
     H, S = tokens.shape
@@ -274,7 +281,7 @@ def launch_rows(entry: str, logp: Tensor, lens, tokens: Tensor, tok_len: Tensor,
     for h0 in range(0, H, Hc):
         h1 = min(H, h0 + Hc)
         capi.launch(entry, dev, logp, n_em, Tq, V, lens, tokens[h0:h1], tok_len[h0:h1], None if em_index is None else em_index[h0:h1],
-                    h1 - h0, S, blank, *(None if t is None else t[h0:h1] for t in outs), ws_ptr, ws_bytes)
+                    h1 - h0, S, blank, *extra, *(None if t is None else t[h0:h1] for t in outs), ws_ptr, ws_bytes)
     del ws
 
 
@@ -288,9 +295,10 @@ def _device_align(logp: Tensor, lens, tokens: Tensor, tok_len: Tensor, em_index,
     return out
 
 
-def row_arguments(name: str, logp: Tensor, tokens, tok_len, em_index, em_len, blank: int):
-    """The arguments ``ctc_forced_align`` and ``ctc_posteriors`` share, checked and in the kernels' form: ``(flat [n_em, T', V], lens
-    int32 [n_em] or None, tokens int32 [H, S], tok_len int32 [H], em_index int32 [H] or None, blank)``, all on ``logp``'s device."""
+def row_arguments(name: str, logp: Tensor, tokens, tok_len, em_index, em_len, blank: int, max_tokens: int = MAX_TOKENS):
+    """The arguments ``ctc_forced_align``, ``ctc_posteriors`` and ``ctc_segment`` share, checked and in the kernels' form: ``(flat
+    [n_em, T', V], lens int32 [n_em] or None, tokens int32 [H, S], tok_len int32 [H], em_index int32 [H] or None, blank)``, all on
+    ``logp``'s device.  ``max_tokens``: the entry's limit on S."""
     if logp.dim() not in (3, 4):
         raise ValueError(f"{name}: logp must be [n_em, T', V] or [E, B, T', V], got {tuple(logp.shape)}")
     if logp.dtype != torch.float32:
@@ -307,8 +315,8 @@ def row_arguments(name: str, logp: Tensor, tokens, tok_len, em_index, em_len, bl
     if tokens.dim() != 2 or tokens.dtype.is_floating_point or tokens.dtype == torch.bool:
         raise ValueError(f"{name}: tokens must be an integer tensor [H, S], got {tokens.dtype} {tuple(tokens.shape)}")
     H, S = tokens.shape
-    if not 1 <= S <= MAX_TOKENS:
-        raise ValueError(f"{name}: a row has 1 .. {MAX_TOKENS} tokens, got S = {S}")
+    if not 1 <= S <= max_tokens:
+        raise ValueError(f"{name}: a row has 1 .. {max_tokens} tokens, got S = {S}")
     dev = logp.device
     flat = logp.reshape(n, Tq, V)
     if not flat.is_contiguous():

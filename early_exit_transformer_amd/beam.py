@@ -54,13 +54,14 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .alignment import FRAME_SECONDS, Alignment, ctc_forced_align, exit_rows, starts_word_from_pieces, word_spans
+from .alignment import FRAME_SECONDS, Alignment, ctc_forced_align, exit_rows, starts_word_from_pieces, transcript_rows, word_spans
 from .context import ContextBiasSession, ContextGraph
 from .keyword import KeywordSet, keyword_search
 from .lm_fusion import DEFAULT_LM_WEIGHT, LMFusionSession, TokenLM, check_lm
 from .lexicon import NGramLM, TokenTrie, as_lexicon
 from .model import beam_select, ctc_align, ctc_beam_decode, ctc_lexicon_decode, ctc_prefix_session, encoder_lengths, greedy_ctc
 from .posterior import TOKEN_FIELDS, Posteriors, ctc_posteriors, soft_word_spans
+from .segment import ctc_segment, utterance_spans, windowed_emission
 
 
 class GreedyCTCDecoder(torch.nn.Module):
@@ -123,6 +124,14 @@ class Timestamps(NamedTuple):
     tokens: list
     words: Optional[list]
     alignment: Alignment
+
+
+class Segmentation(NamedTuple):
+    """What ``BeamInference.segment`` returns: the ``Alignment`` of the concatenated transcript (one row), the ``UtteranceSpan``
+    of every utterance and -- with ``pieces`` -- the ``WordSpan`` list of every utterance (else ``words`` is None)."""
+    alignment: Alignment
+    utterances: list
+    words: Optional[list]
 
 
 class Confidences(NamedTuple):
@@ -1025,6 +1034,44 @@ class BeamInference:
         tok = [host.spans(h, frame_seconds) for h in range(len(pairs))]
         words = None if pieces is None else [word_spans(sp, starts_word_from_pieces(pieces)) for sp in tok]
         return Timestamps(self._per_exit(tok, exits, logp), self._per_exit(words, exits, logp), al)
+
+    @torch.no_grad()
+    def segment(self, model, spec: Tensor, utterances, exit: Optional[int] = None, window: Optional[int] = None, overlap: int = 64,
+                pieces: Optional[Sequence[str]] = None, frame_seconds: Optional[float] = None, score_window: int = 30,
+                blank: int = 0) -> Segmentation:
+        """CTC segmentation of ONE recording, which may be longer than the model's ``max_len``: where each of its ``utterances``
+        (token lists as ``timestamps`` takes them, in the order they were said; the SOS, EOS and PAD ids of ``args`` are removed)
+        lies in ``spec`` [n_mels, T], and how surely.  ``windowed_emission`` at ``exit`` (0-based; None: the last) with ``window``
+        (None: the largest the model takes) and ``overlap`` mel frames, ONE ``ctc_segment`` of the concatenated utterances with
+        both ends free, and ``utterance_spans`` with ``score_window`` frames per confidence window; bounds in seconds
+        (``frame_seconds`` as in ``timestamps``).  With ``pieces``: ``word_spans`` per utterance.  A transcript that does not fit
+        the recording has status 1 in the alignment and empty lists here."""
+        drop = {int(getattr(self.args, n)) for n in ("trg_sos_idx", "trg_eos_idx", "trg_pad_idx") if hasattr(self.args, n)} - {int(blank)}
+        rows = transcript_rows(utterances, drop, int(blank), "segment")
+        if not rows or any(not r for r in rows):
+            raise ValueError("segment: every utterance needs at least one token")
+        overlap = int(overlap)
+        if window is None:
+            window = overlap + (int(model._cfg.max_len) - overlap) // 4 * 4
+        logp = windowed_emission(model, spec, window, overlap)
+        E = int(logp.size(0))
+        e = E - 1 if exit is None else int(exit)
+        if not 0 <= e < E:
+            raise ValueError(f"segment: exit must be one of 0 .. {E - 1}, got {exit}")
+        row = logp[e, 0]
+        tokens = torch.tensor([[t for r in rows for t in r]], dtype=torch.int32)
+        al = ctc_segment(row[None], tokens, blank=int(blank), free_start=True, free_end=True)
+        frame_seconds = self._frame_seconds(frame_seconds)
+        host = Alignment(*(t.cpu() for t in (al.tok_start, al.tok_end, al.tok_score, al.frame_token, al.path_score, al.status)),
+                         tokens=al.tokens.cpu(), tok_len=al.tok_len.cpu())  # one copy each, not one per span
+        utts = utterance_spans(host, 0, [len(r) for r in rows], row, int(blank), score_window, frame_seconds)
+        words = None
+        if pieces is not None:
+            tok, table, words, j = host.spans(0, frame_seconds), starts_word_from_pieces(pieces), [], 0
+            for r in rows:
+                words.append(word_spans(tok[j:j + len(r)], table) if tok else [])
+                j += len(r)
+        return Segmentation(al, utts, words)
 
     @torch.no_grad()
     def confidences(self, model, spec: Tensor, valid_len: Tensor, hyps, exits=None, pieces: Optional[Sequence[str]] = None,

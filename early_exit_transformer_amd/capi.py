@@ -282,6 +282,8 @@ PROTOTYPES = {
     "eec_ctc_forced_align": [F32, i, i, i, I32, I32, I32, I32, i, i, i, I32, I32, F32, I32, F32, I32, VOID, z, STREAM],
     "eec_ctc_posteriors_workspace_bytes": (z, [i, i, i]),
     "eec_ctc_posteriors": [F32, i, i, i, I32, I32, I32, I32, i, i, i, F32, F32, F32, F32, F32, F32, F32, F32, I32, VOID, z, STREAM],
+    "eec_ctc_segment_workspace_bytes": (z, [i, i, i]),
+    "eec_ctc_segment": [F32, i, i, i, I32, I32, I32, I32, i, i, i, i, I32, I32, F32, I32, F32, I32, VOID, z, STREAM],
 }
 EXPORTS = list(PROTOTYPES)
 KERNEL_CLASSES = ["stem", "ffn", "qkv", "attn", "proj_glu", "proj", "dw_pw2", "head", "chain"]

@@ -6,6 +6,8 @@
 // that crosses a lane boundary forward -- the left neighbour's last state, s - 1 of slot 0 and s - 2 of slot 1 -- comes by one
 // from_left (C = 1: two).  One wave serves one row, kStripWaves rows a workgroup: row h is wave h & 3 of workgroup h >> 2, so rows
 // that follow each other and share an emission fetch its lines from memory once.  The frame loops are the consumers' own.
+// ctc_segment.hip lays a row of up to 4095 tokens over several waves of one workgroup, each a C = 8 strip of 512 states: it takes
+// the row checks and the entry head with its own limit (max_tokens) and strip_label<8> with the lane index moved by the wave's.
 #pragma once
 #include <math.h>
 
@@ -26,7 +28,8 @@ constexpr int strip_labels(int C) { return C >= 2 ? C / 2 : 1; }                
 constexpr int strip_log2(int C) { return C == 1 ? 0 : C == 2 ? 1 : C == 4 ? 2 : 3; }  // state s: lane s >> log2 C, slot s & (C - 1)
 
 // The row checks of row h, wave-uniform: N tokens, T frames (em_len clamped to [0, Tq]; frames from T on are never read) of
-// emission ei.  ok: 0 <= ei < n_em, 1 <= N <= tok_stride, every token a label of [0, V) other than the blank, and T >= N + R.
+// emission ei.  ok: 0 <= ei < n_em, 1 <= N <= min(tok_stride, max_tokens), every token a label of [0, V) other than the blank, and
+// T >= N + R.
 // None of the row's values becomes an address unless ok: N bounds the token reads only once it is known to be within tok_stride,
 // ei indexes em_len only once it is known to be an emission, and the caller forms no emission address and runs no strip before
 // it has seen ok (a row that is not ok gets the caller's fill values).
@@ -36,10 +39,10 @@ struct StripRow {
 };
 __device__ __forceinline__ StripRow strip_row(const int* __restrict__ tk, const int* __restrict__ tok_len, const int* __restrict__ em_index,
                                               const int* __restrict__ em_len, int h, int n_em, int Tq, int V, int tok_stride, int blank,
-                                              int lane) {
+                                              int lane, int max_tokens = kStripMaxTokens) {
   const int N = __builtin_amdgcn_readfirstlane(tok_len[h]);
   const int ei = __builtin_amdgcn_readfirstlane(em_index ? em_index[h] : h);
-  bool ok = ei >= 0 && ei < n_em && N >= 1 && N <= tok_stride && N <= kStripMaxTokens;
+  bool ok = ei >= 0 && ei < n_em && N >= 1 && N <= tok_stride && N <= max_tokens;
   int T = 0;
   if (ok) {
     T = __builtin_amdgcn_readfirstlane(em_len ? min(max(em_len[ei], 0), Tq) : Tq);
@@ -107,18 +110,19 @@ __device__ __forceinline__ void strip_end(const float (&a)[C], int N, float& hi,
 namespace eech {
 
 // The head of an entry over lattice rows (`me`: its name): the argument, limit and workspace refusals, `required` the pointers
-// that may not be null and `need` the entry's workspace size.  Returns the entry's return code; 0 with n_hyp == 0 means there is
+// that may not be null, `need` the entry's workspace size and `max_tokens` its limit on tok_stride.  Returns the entry's return code; 0 with n_hyp == 0 means there is
 // nothing to launch.
 inline int strip_entry_head(const char* me, std::initializer_list<const void*> required, int n_em, int Tq, int V, int n_hyp,
-                            int tok_stride, int blank, const void* workspace, size_t workspace_bytes, size_t need) {
+                            int tok_stride, int blank, const void* workspace, size_t workspace_bytes, size_t need,
+                            int max_tokens = eec::kStripMaxTokens) {
   const std::string m = std::string(me) + ": ";
   if (n_hyp < 0 || Tq < 1 || tok_stride < 1 || n_em < 1 || V < 1 || blank < 0 || blank >= V)
     return fail(EEC_ERR_BAD_ARG, m + "needs n_hyp >= 0, Tq, tok_stride, n_em, V >= 1 and blank in [0, V)");
   if (n_hyp == 0) return 0;
   for (const void* p : required)
     if (!p) return fail(EEC_ERR_BAD_ARG, m + "null argument");
-  if (V < 2 || tok_stride > eec::kStripMaxTokens)
-    return fail(EEC_ERR_UNSUPPORTED, m + "needs V >= 2 and tok_stride <= " + std::to_string(eec::kStripMaxTokens));
+  if (V < 2 || tok_stride > max_tokens)
+    return fail(EEC_ERR_UNSUPPORTED, m + "needs V >= 2 and tok_stride <= " + std::to_string(max_tokens));
   if (!workspace) return fail(EEC_ERR_WORKSPACE, m + "null workspace");
   return check_workspace(workspace, workspace_bytes, need);
 }

@@ -1700,6 +1700,48 @@ int eec_ctc_posteriors(const float* logp, int n_em, int Tq, int V, const int32_t
                        float* tok_start, float* tok_end, float* tok_start_var, float* tok_end_var, float* gamma, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC segmentation: long rows, free ends (csrc/ctc_segment.hip) -------------------------------------------------------------------------
+ * "Where in this recording is this transcript": eec_ctc_forced_align for rows of up to EEC_SEG_MAX_TOKENS = 4095 tokens -- a
+ * character-level utterance, or the concatenated transcript of a talk aligned against the whole recording as in CTC segmentation
+ * (Kuerzinger et al. 2020) -- with two flags that make the audio before the first and after the last token cost nothing.  The
+ * reference has nothing like this entry: an addition, not a parity item.  tests/segment_cases.py restates it in scalar fp32 and
+ * checks it against a brute force over all frame labellings.
+ *
+ * Arguments: eec_ctc_forced_align's, in its order, with `flags` after `blank`; the outputs are the same.
+ * Semantics: eec_ctc_forced_align's statement word for word -- states, candidates, their order stay / step / skip, the strict > tie
+ * rule, the end rule, the walk back, the row checks, status 0 / 1, the fill values, "frames at or past a length are never read" --
+ * with one term changed per flag:
+ *   EEC_SEG_FREE_START (bit 0): the emission term of state 0 is 0.0f at every frame: a[0][0] = 0, and a[t][0] = best + 0.0f.
+ *   EEC_SEG_FREE_END   (bit 1): the emission term of state 2N is 0.0f at every frame t >= 1.
+ * Any other bit set is EEC_ERR_BAD_ARG.  Everything else is unchanged, tok_score included, which sums label frames only.  With
+ * flags = 0 the statement IS eec_ctc_forced_align's.  Adding 0.0f is exact in fp32, so the kernel, the package's host path and a
+ * scalar restatement still agree bit for bit.
+ * Accumulation.  A path score is a plain fp32 sum over as many frames as the emission has, tens of thousands for a recording.  The
+ * statement stays exact -- every implementation performs the same adds -- but the precision of the SCORE shrinks with its magnitude:
+ * at |score| around 2^16 one add rounds to 2^-8.  Nothing is rescaled; a decision between two candidates closer than that rounding
+ * goes by the tie rule.
+ * Limits.  tok_stride <= EEC_SEG_MAX_TOKENS (the 2N + 1 <= 8191 states lie on up to 16 wavefronts of one workgroup, 512 states
+ * each), V >= 2.  A row with tok_len > tok_stride has status 1 like every bad row.
+ *
+ *   workspace: eec_ctc_segment_workspace_bytes(n_hyp, T', tok_stride) bytes, 256-byte aligned: the decisions, two bits per (frame,
+ *   state): n_hyp * ceil(T' / 2) * W * 256 bytes with W = ceil((2 * tok_stride + 1) / 512) wavefronts per row.  The size does not
+ *   decrease in any argument and is 0 when an argument is <= 0.
+ * All checks come before any device work, through eec_last_error().  EEC_ERR_BAD_ARG: a flags bit other than the two; then, in the
+ * codes and order of eec_ctc_forced_align, a null required pointer, blank outside [0, V), tok_stride < 1, n_hyp < 0, T' < 1, n_em <
+ * 1; n_hyp == 0 is a successful no-op.  EEC_ERR_UNSUPPORTED: tok_stride > 4095 (the message names the limit), V < 2.
+ * EEC_ERR_WORKSPACE: a null, short or misaligned workspace.
+ * One launch, one workgroup per row -- the best path is sequential in time, so a recording is one workgroup however long it is --,
+ * no atomics, nothing read back, no allocation, no synchronisation; graph-capturable; two runs and any split of the rows return the
+ * same bits.  Rows of at most 255 tokens are served faster by eec_ctc_forced_align, which needs no barrier. */
+#define EEC_SEG_MAX_TOKENS 4095
+#define EEC_SEG_FREE_START 1
+#define EEC_SEG_FREE_END 2
+size_t eec_ctc_segment_workspace_bytes(int n_hyp, int Tq, int tok_stride);
+int eec_ctc_segment(const float* logp, int n_em, int Tq, int V, const int32_t* em_len, const int32_t* tokens, const int32_t* tok_len,
+                    const int32_t* em_index, int n_hyp, int tok_stride, int blank, int flags, int32_t* tok_start, int32_t* tok_end,
+                    float* tok_score, int32_t* frame_token, float* path_score, int32_t* status, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
